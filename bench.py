@@ -2,7 +2,7 @@
 """Benchmark of the LeRF LUT resampling hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4,5}] [--mode frames|strips|blocks]
-                    [--scale S] [--channels {1,3,4}] [--sustained SECONDS]
+                    [--scale S] [--channels {1,3,4}] [--sustained SECONDS] [--dump-outputs DIR]
 
 Default = BASELINE.json configs[1], the configuration the headline metric is quoted on: LeRF-G LUT x2 SR,
 1920x1080 -> 3840x2160 RGB.  One "step" = one pass of the hot path (stage-1 LUTs -> stage-2 LUTs -> spatially
@@ -24,6 +24,9 @@ one rank per GPU, RCCL); a failing rank makes the whole command fail.  Under tor
 
 Prints ONE JSON line (rank 0).  `roofline` prices the launch against HBM bandwidth using the ALGORITHMIC bytes of
 SURVEY.md 8(d); `cpu_baseline` is the C port of the oracle timed on this box's host cores (rank 0, N = 1 only).
+
+--dump-outputs DIR writes the output of the last timed step (see dump_outputs); the synthetic inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -428,6 +431,34 @@ def other_config_legs(torch, L, ops, steps=20, warmup=5):
     return legs
 
 
+# --------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET_BYTES = 64 << 20                            # everything written under DIR
+DUMP_SAMPLE = 4 << 20                                   # elements kept of an output that does not fit (16 MB values + 32 MB indices)
+
+
+def dump_outputs(torch, d, arrays):
+    """Write the arrays a caller of the timed path received in its last step as DIR/<name>.npy (float32).  An output whose
+    float32 copy would take more than half the budget is written as a fixed sample instead: DIR/<name>_sample.npy (float32
+    values) and DIR/<name>_sample_index.npy (float64 flat C-order indices into the output, drawn by a generator seeded with 0
+    and sorted, so they depend on the output's shape only).  Returns the description that goes into the JSON line."""
+    os.makedirs(d, exist_ok=True)
+    desc = {}
+    for name, t in arrays.items():
+        n = t.numel()
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+        if 4 * n <= DUMP_BUDGET_BYTES // 2:
+            np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
+            entry["written"] = "full"
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            vals = t.contiguous().view(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+            np.save(os.path.join(d, name + "_sample.npy"), vals)
+            np.save(os.path.join(d, name + "_sample_index.npy"), idx.astype(np.float64))
+            entry["written"] = "sample of %d elements" % DUMP_SAMPLE
+        desc[name] = entry
+    return {"dir": d, "arrays": desc}
+
+
 # --------------------------------------------------------------------------------------------- rank launcher
 def _free_port():
     s = socket.socket()
@@ -508,7 +539,15 @@ def parse():
                          "blocks: every frame is split into a 2-D grid of blocks over the GPUs (8 GPUs: 2 x 4) with an RCCL halo "
                          "exchange (default for --config 5 with N > 1); strips: LR strips instead; rows (config 4): every "
                          "frame's OUTPUT rows over the GPUs, each rank warps from its band of the source (no exchange)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output of the last one as DIR/<name>.npy (float32; a seeded sample when "
+                         "large, at most 64 MB in all; rank 0's part with N > 1).  Configs 2-5 of the fused path")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.config == 1 or args.path != "fused"):
+        ap.error("--dump-outputs covers the timed path of configs 2-5 (--path fused)")
+    return args
 
 
 def main():
@@ -723,6 +762,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # (before any later leg can run the step again: `out` holds what the last timed step wrote)
+    dumped = dump_outputs(torch, args.dump_outputs, {"out": out}) if (args.dump_outputs and rank == 0) else None
 
     weak = cfg != 5 and not strips
     pix_per_step = (n_gpus if weak else 1) * (B_local if weak else B) * oH * oW
@@ -892,6 +933,8 @@ def main():
                             "value": round(pix_per_step * sustained[0] / sustained[1] / 1e6, 2), "unit": "Mpix/s",
                             "ms_per_step": round(sustained[1] / sustained[0] * 1e3, 4)}
     res.update(extra)
+    if dumped:
+        res["dump_outputs"] = dumped
 
     if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not strips:
         if cfg == 4:

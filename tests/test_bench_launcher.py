@@ -19,15 +19,20 @@ def _fake_torch(tmp_path, body):
 
 
 def test_parent_stays_off_torch_and_reports_failed_ranks(tmp_path):
-    # a torch that records who imported it (and then fails like a box without devices)
+    # a torch that records who imported it (and then fails like a box without devices).  It fails only once both ranks
+    # have recorded themselves (or after 60 s): the launcher kills the other ranks as soon as one fails, which would
+    # otherwise race the second rank's import.
     log = tmp_path / "imports.log"
     fake = _fake_torch(tmp_path, """
-        import os
+        import os, time
         with open(%r, "a") as f:
             f.write("%%s %%s %%s %%s %%s\\n" %% (os.environ.get("RANK"), os.environ.get("LOCAL_RANK"), os.environ.get("WORLD_SIZE"),
                                             os.environ.get("MASTER_ADDR"), os.environ.get("MASTER_PORT")))
+        t0 = time.time()
+        while time.time() - t0 < 60 and len(open(%r).read().splitlines()) < 2:
+            time.sleep(0.02)
         raise ImportError("no GPU stack in this test")
-        """ % str(log))
+        """ % (str(log), str(log)))
     env = dict(os.environ, PYTHONPATH=fake + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
