@@ -219,8 +219,8 @@ int lerf_lut_interp(const lerf_plane_t* img, int img_h, int img_w, int C, int h,
 
 /* ABI 7.  lerf_lut_interp with per-call flags (0 = lerf_lut_interp).  For the shipped interval (4) the pass runs in persistent
  * workgroups that keep one byte plane of the LUT in LDS (csrc/lerf_lut_interp.hip) when the launch is large enough to pay for it
- * (>= 65 536 positions), the pattern reaches no further than 3 pixels and C <= 4; the direct kernel (LUT gathered from L1 / L2)
- * serves everything else -- same values either way.
+ * (>= 65 536 positions), the pattern reaches no further than 3 pixels, C <= 4, the image strides are non-negative and one of the
+ * output strides sy / sx is +-1; the direct kernel (LUT gathered from L1 / L2) serves everything else -- same values either way.
  *   LERF_INTERP_ACCUMULATE  out += result instead of out = result: the call sites' `pred += FourSimplexInterpFaster(...)`
  *                           (resample/eval_lut_sr.py:555, :564, :589, :601) without a second pass over the planes.  The planes
  *                           must hold valid numbers (the first call of a sum runs without the flag).
@@ -286,8 +286,9 @@ int lerf_resize(const lerf_plane_t* feat, const lerf_plane_t hyper[3],
  * 409-449), the fixed-kernel baselines Bicubic/Bilinear/Lanczos2/Lanczos3Warp2dNumpy
  * (:451-494) and the Torch twins (resize_right2d_torch.py:346-487).
  * Pixels whose weights all vanish are NaN in float outputs (the reference's
- * 0/0) and 0 in uint8 outputs.  If `mask_out` (uint8 [out_h][out_w]) is
- * non-NULL and kind == NEAREST, it receives out == 255 per pixel. */
+ * 0/0) and 0 in uint8 outputs.  There is no mask operand: the harness's validity
+ * mask (eval_lut_warp.py:197-204) is a NEAREST warp (S = 1) of a white frame with
+ * a black border, compared with 255 by the caller. */
 int lerf_warp(const lerf_plane_t* feat, const lerf_plane_t hyper[3],
               int H, int W, int C, const lerf_warp_geo_t* geo,
               int kind, double max_sigma, const lerf_mplane_t* out, void* stream);

@@ -840,6 +840,8 @@ static int try_lut_interp_lds(const void* img, int in_dtype, int64_t sy, int64_t
                               int h, int w, Offsets4 off, const int8_t* lut, int oC, void* out, int out_dtype, int64_t oy, int64_t ox,
                               int64_t ocs, int flags, hipStream_t st) {
     if (flags & LERF_INTERP_DIRECT) return LERF_EUNSUPPORTED;
+    // a lane stores its two positions as one adjacent pair (li_store2): the plane must be contiguous along x or y
+    if (ox != 1 && ox != -1 && oy != 1 && oy != -1) return LERF_EUNSUPPORTED;
     if (C > LI_CMAX || (reinterpret_cast<uintptr_t>(lut) & 15)) return LERF_EUNSUPPORTED;
     if (!(flags & LERF_INTERP_LDS) && (int64_t)h * w * C < 65536) return LERF_EUNSUPPORTED;
     int miny = 127, maxy = -127, minx = 127, maxx = -127;
@@ -861,7 +863,7 @@ static int try_lut_interp_lds(const void* img, int in_dtype, int64_t sy, int64_t
     A.max_off = (int64_t)(C - 1) * sc + (int64_t)(img_h - 1) * sy + (int64_t)(img_w - 1) * sx;
     A.img_h = img_h; A.img_w = img_w; A.C = C; A.h = h; A.w = w;
     A.lut = lut; A.lut_planar = (flags & LERF_INTERP_LUT_PLANAR) ? 1 : 0; A.out = out; A.ocs = ocs;
-    // lanes run along the axis on which the output plane is contiguous
+    // lanes run along the axis on which the output plane is contiguous (x when both are)
     A.lane_is_y = ((oy == 1 || oy == -1) && !(ox == 1 || ox == -1)) ? 1 : 0;
     A.ol = A.lane_is_y ? oy : ox;
     A.oo = A.lane_is_y ? ox : oy;
@@ -973,6 +975,8 @@ int launch_lut_interp(const void* img, int in_dtype, int64_t sy, int64_t sx, int
         const int rc = try_lut_interp_lds(img, in_dtype, sy, sx, sc, img_h, img_w, C, h, w, off, lut, oC, out, out_dtype, oy, ox, ocs, flags, st);
         if (rc != LERF_EUNSUPPORTED) return rc;
         if (flags & (LERF_INTERP_LDS | LERF_INTERP_LUT_PLANAR)) return LERF_EUNSUPPORTED;   // the caller insisted on the LDS kernel (a planar LUT is its format)
+    } else if (flags & LERF_INTERP_LDS) {
+        return LERF_EUNSUPPORTED;                                                       // the LDS kernel is interval 4 only
     }
     const bool acc = (flags & LERF_INTERP_ACCUMULATE) != 0;
 #define LERF_LI(OC, TIN, TOUT)                                                                                                  \
