@@ -428,6 +428,21 @@ int lerf_resize_bwd_f32(const float* feat, const float* h0, const float* h1, con
                         const lerf_sr_geo_t* geo, int kind, double max_sigma, const float* grad_out, float* grad_feat,
                         float* grad_h0, float* grad_h1, float* grad_h2, void* stream);
 
+/* Backward of lerf_warp on planar float32 maps, as autograd derives it for the reference's torch warps
+ * (SteeringGaussianWarp2dTorch / AmplifiedLinearWarp2dTorch / NearestWarp2dTorch / BicubicWarp2dTorch.warp and the
+ * bilinear / lanczos kinds on the same base class, resize_right2d_torch.py:249-487): float64 distances, weights and
+ * normalisation; each tap's terms rounded to float32 and summed in float32.
+ * feat, h0..h2: float32 [N][H][W] (hyper maps in [0,1]; h0 alone for LINEAR, none for the fixed kinds), grad_out: float64
+ * [N][out_h][out_w] (the warps return float64).  grad_feat / grad_h*: float32 [N][H][W], ACCUMULATED into with float
+ * atomics (zero them first); any of them may be NULL.  Kinds GAUSS and LINEAR give image and hyper-map gradients, the fixed
+ * kinds the image gradient only.  geo: whole outputs only (out_y0 = out_x0 = src_y0 = 0, else LERF_EUNSUPPORTED); the image
+ * gradient follows geo->pad_mode (constant: taps outside the frame get nothing; replicate / reflect / wrap: the pixel the pad
+ * names, F.pad's backward), hyper gradients land on the clamped tap pixel (replicate).  Pixels whose weights all vanish are
+ * NaN in the forward and hand their taps NaN, as autograd does. */
+int lerf_warp_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W,
+                  const lerf_warp_geo_t* geo, int kind, double max_sigma, const double* grad_out, float* grad_feat,
+                  float* grad_h0, float* grad_h1, float* grad_h2, void* stream);
+
 /* ---- net -> LUT transfer (resample/transfer_to_lut.py:12-170): one hyper-network of the reference's SRNetsSWF2
  * (resample/model.py:81-99; an SRNet = SRUnit MLP, common/network.py:40-163) evaluated on all L^4 sampled pixel
  * tuples (L = 2^(8-interval) + 1; get_input_tensor :12-42, first pixel = slowest axis) and quantised like :117-119:

@@ -47,7 +47,7 @@ EXPORTS = [
     "lerf_stages_packed_u8", "lerf_unpack_stages", "lerf_warp_packed", "lerf_rect_copy_u8",
     "lerf_warp_tile_boxes", "lerf_warp_fused_supported", "lerf_warp_fused_u8",
     "lerf_metric_y_sse_u8", "lerf_metric_ssim_y_u8", "lerf_metric_masked_sse_u8",
-    "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32",
+    "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd",
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_ubench_lds_gather",
 ]
 
@@ -207,6 +207,8 @@ def lib():
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_resize_bwd_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SrGeo),
                                       C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lerf_warp_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WarpGeo),
+                                C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_srnet_weight_floats.restype = C.c_size_t
     L.lerf_srnet_weight_floats.argtypes = [C.c_int]
     L.lerf_srnet_to_lut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -14,6 +14,7 @@
 #include "lerf_kernels.h"
 #include "lerf_stage3.h"
 #include "lerf_warp_px.h"
+#include "lerf_warp_taps.h"
 
 namespace lerf {
 
@@ -514,26 +515,6 @@ int launch_resize(const ResizeArgs& a, hipStream_t st) {
     return LERF_EUNSUPPORTED;
 }
 
-// fixed interpolation kernels of resize_right/interp_methods.py:35-70 (the reference's non-learned warps,
-// resize_right2d_numpy.py:451-494); evaluated in float64 like the reference, eps = float32 eps
-__device__ __forceinline__ double fixed_kernel_1d(int kind, double x) {
-#pragma clang fp contract(off)
-    const double pi = 3.141592653589793;
-    const double eps = (double)kEps32;
-    if (kind == LERF_KIND_CUBIC) {                                        // :35-43
-        const double a = fabs(x), a2 = a * a, a3 = a * a * a;
-        return (1.5 * a3 - 2.5 * a2 + 1.0) * (a <= 1.0 ? 1.0 : 0.0) +
-               (-0.5 * a3 + 2.5 * a2 - 4.0 * a + 2.0) * ((1.0 < a && a <= 2.0) ? 1.0 : 0.0);
-    }
-    if (kind == LERF_KIND_LANCZOS2)                                       // :46-50
-        return ((sin(pi * x) * sin(pi * x / 2) + eps) / ((pi * pi * (x * x) / 2) + eps)) * (fabs(x) < 2.0 ? 1.0 : 0.0);
-    if (kind == LERF_KIND_LANCZOS3)                                       // :53-57
-        return ((sin(pi * x) * sin(pi * x / 3) + eps) / ((pi * pi * (x * x) / 3) + eps)) * (fabs(x) < 3.0 ? 1.0 : 0.0);
-    if (kind == LERF_KIND_BILINEAR)                                       // :60-64
-        return (x + 1.0) * ((-1.0 <= x && x < 0.0) ? 1.0 : 0.0) + (1.0 - x) * ((0.0 <= x && x <= 1.0) ? 1.0 : 0.0);
-    return ((-1.0 <= x && x < 0.0) ? 1.0 : 0.0) + ((0.0 <= x && x <= 1.0) ? 1.0 : 0.0);   // box :67-70
-}
-
 // ---------------------------------------------------------------------------
 // Fixed-kernel SR: Resize2dTorch.resize + BicubicResize2dTorch (resize_right2d_torch.py:105-138)
 // and its bilinear / lanczos / box siblings on the separable SR geometry.  weight(dx, dy) = k(dx) k(dy), normalised
@@ -612,25 +593,19 @@ warp_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
     int j = xc / C;
     int c = xc - j * C;
     const int S = g.S;
-    double gr, gc;
-    project_point(g.minv, i + g.oy0, j + g.ox0, H, W, &gr, &gc);
-    int lr = left_boundary(gr, S) + g.pad_r_lo;
-    int lc = left_boundary(gc, S) + g.pad_c_lo;
-    gr += (double)g.pad_r_lo;      // calc_pad_sz shifts grid and field of view (:366-367)
-    gc += (double)g.pad_c_lo;
+    const WarpPixel px = warp_pixel(g, i, j, H, W);
+    const int lr = px.lr, lc = px.lc;
+    const double gr = px.gr, gc = px.gc;
     A emin = 0, num = 0, den = 0;
     for (int pass = (KIND == LERF_KIND_GAUSS ? 0 : 1); pass < 2; ++pass) {
         for (int a = 0; a < S; ++a)
             for (int b = 0; b < S; ++b) {
-                // field of view clipped to [0, in-1] while indexing the PADDED arrays (:396-398)
-                int pr = clampi(lr + b, 0, H - 1), pc = clampi(lc + a, 0, W - 1);
-                double dxd = gr - (double)pr, dyd = gc - (double)pc;
-                A dx = (A)dxd, dy = (A)dyd;
-                int sr = pr - g.pad_r_lo, sc_ = pc - g.pad_c_lo;       // unpadded source coordinates
-                int rcl = clampi(sr, 0, H - 1), ccl = clampi(sc_, 0, W - 1);
-                bool zr, zc;                                           // image pad rule (:560)
-                const int rs = pad_index(sr, H, g.pad_mode, &zr), cs = pad_index(sc_, W, g.pad_mode, &zc);
-                int64_t ho = rcl * hy + ccl * hx + c * hc;
+                const WarpTap<A> tp = warp_tap<A>(g, px, a, b, H, W);
+                const double dxd = tp.dxd, dyd = tp.dyd;
+                const A dx = tp.dx, dy = tp.dy;
+                const int rs = tp.rs, cs = tp.cs;
+                const bool zr = tp.zr, zc = tp.zc;
+                int64_t ho = tp.rcl * hy + tp.ccl * hx + c * hc;
                 A w;
                 if (KIND == LERF_KIND_GAUSS) {
                     float p0 = Loader<TH>::hyper(h0 + ho), p1 = Loader<TH>::hyper(h1 + ho), p2 = Loader<TH>::hyper(h2 + ho);

@@ -14,6 +14,9 @@
 //   lerf::resize_linear AmplifiedLinearResize2dTorch.resize        resize_right/resize_right2d_torch.py:214-247
 //   lerf::resize_backward  what autograd derives for the two above (train_model.py:431-441); the autograd formulas
 //                       themselves are attached in lerf_pytorch_amd/torch_ops.py (torch.library.register_autograd)
+//   lerf::warp_gauss    SteeringGaussianWarp2dTorch.warp           resize_right/resize_right2d_torch.py:403-437
+//   lerf::warp_linear   AmplifiedLinearWarp2dTorch.warp            resize_right/resize_right2d_torch.py:439-487
+//   lerf::warp_backward what autograd derives for the two above (registered the same way)
 // LUT sets travel as tensor lists: luts_s1 = [s, c, t] int8 [17^4, 1]; luts_s2 = [s_r0, s_r1, c_r0, c_r1, t_r0, t_r1]
 // int8 [17^4, outC]; pack = the fused LUT pack (lerf_fused_lutpack_build) or None.
 #include <ATen/ATen.h>
@@ -264,6 +267,82 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> resize_backward(int64
     return {gx, g0, g1, g2};
 }
 
+// homography geometry of the torch warp classes: torch.linalg.inv(matrix) in float64 (resize_right2d_torch.py:287), constant pad
+lerf_warp_geo_t warp_geometry(const at::Tensor& matrix, int H, int W, int64_t out_h, int64_t out_w, int S) {
+    TORCH_CHECK(matrix.numel() == 9, "matrix must be 3x3 (input -> output coordinates)");
+    TORCH_CHECK(out_h >= 1 && out_w >= 1 && S >= 1 && S <= LERF_MAX_SUPPORT, "bad output size / support");
+    lerf_warp_geo_t g{};
+    g.S = S;
+    g.out_h = (int)out_h;
+    g.out_w = (int)out_w;
+    at::Tensor minv = at::linalg_inv(matrix.detach().to(at::kCPU, at::kDouble).reshape({3, 3})).contiguous();
+    memcpy(g.minv, minv.data_ptr<double>(), sizeof(g.minv));
+    int32_t pads[4];
+    check_rc(lerf_warp_pads(g.minv, H, W, g.out_h, g.out_w, g.S, pads), "lerf_warp_pads");
+    g.pad_r_lo = pads[0]; g.pad_r_hi = pads[1]; g.pad_c_lo = pads[2]; g.pad_c_hi = pads[3];
+    g.pad_mode = LERF_PAD_CONSTANT;
+    return g;
+}
+
+// planar float32 maps [B,C,H,W] -> float64 [B,C,out_h,out_w]
+at::Tensor warp_planar(int kind, const at::Tensor& feat, const std::vector<at::Tensor>& hs, const at::Tensor& matrix, int64_t out_h,
+                       int64_t out_w, int64_t S, double ms) {
+    TORCH_CHECK(feat.dim() == 4 && feat.scalar_type() == at::kFloat, "feat must be float32 [B,C,H,W]");
+    DeviceGuard guard(feat.device());
+    const int B = (int)feat.size(0), C = (int)feat.size(1), H = (int)feat.size(2), W = (int)feat.size(3);
+    at::Tensor x = feat.contiguous();
+    std::vector<at::Tensor> h;
+    for (const at::Tensor& t : hs) {
+        TORCH_CHECK(t.sizes() == feat.sizes() && t.scalar_type() == at::kFloat && t.device() == feat.device(),
+                    "hyper-parameter maps must match feat (float32, same shape and device)");
+        h.push_back(t.contiguous());
+    }
+    const lerf_warp_geo_t g = warp_geometry(matrix, H, W, out_h, out_w, (int)S);
+    at::Tensor out = at::empty({B, C, out_h, out_w}, x.options().dtype(at::kDouble));
+    const int64_t hw = (int64_t)H * W;
+    lerf_plane_t pf{x.data_ptr(), LERF_F32, W, 1, hw};
+    lerf_plane_t hp[3];
+    for (int k = 0; k < 3; ++k) hp[k] = lerf_plane_t{h[k < (int)h.size() ? k : 0].data_ptr(), LERF_F32, W, 1, hw};
+    lerf_mplane_t po{out.data_ptr(), LERF_F64, out_w, 1, out_h * out_w};
+    check_rc(lerf_warp(&pf, hp, H, W, B * C, &g, kind, ms, &po, cur_stream()), "lerf_warp");
+    return out;
+}
+
+at::Tensor warp_gauss(const at::Tensor& feat, const at::Tensor& rho, const at::Tensor& sigma_x, const at::Tensor& sigma_y, const at::Tensor& matrix,
+                      int64_t out_h, int64_t out_w, int64_t support, double max_sigma) {
+    return warp_planar(LERF_KIND_GAUSS, feat, {rho, sigma_x, sigma_y}, matrix, out_h, out_w, support, max_sigma);
+}
+
+at::Tensor warp_linear(const at::Tensor& feat, const at::Tensor& alpha, const at::Tensor& matrix, int64_t out_h, int64_t out_w, double max_sigma) {
+    return warp_planar(LERF_KIND_LINEAR, feat, {alpha}, matrix, out_h, out_w, 2, max_sigma);
+}
+
+// gradients of warp_gauss (kind 0: feat, rho, sigma_x, sigma_y) / warp_linear (kind 1: feat, alpha; the last two are zeros)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> warp_backward(int64_t kind, const at::Tensor& grad_out, const at::Tensor& feat,
+                                                                         const at::Tensor& h0, const at::Tensor& h1, const at::Tensor& h2,
+                                                                         const at::Tensor& matrix, int64_t out_h, int64_t out_w, int64_t support,
+                                                                         double max_sigma) {
+    TORCH_CHECK(kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR, "kind: 0 = gauss, 1 = linear");
+    TORCH_CHECK(feat.dim() == 4 && feat.scalar_type() == at::kFloat, "feat must be float32 [B,C,H,W]");
+    DeviceGuard guard(feat.device());
+    const int B = (int)feat.size(0), C = (int)feat.size(1), H = (int)feat.size(2), W = (int)feat.size(3);
+    const bool gauss = kind == LERF_KIND_GAUSS;
+    const lerf_warp_geo_t g = warp_geometry(matrix, H, W, out_h, out_w, gauss ? (int)support : 2);
+    TORCH_CHECK(grad_out.dim() == 4 && grad_out.size(0) == B && grad_out.size(1) == C && grad_out.size(2) == out_h && grad_out.size(3) == out_w &&
+                    grad_out.device() == feat.device(),
+                "grad_out must be [B,C,out_h,out_w], on feat's device");
+    for (const at::Tensor* t : {&h0, &h1, &h2})         // all three are read by the Gaussian kernel, h0 by the linear one
+        TORCH_CHECK((t != &h0 && !gauss) || (t->sizes() == feat.sizes() && t->scalar_type() == at::kFloat && t->device() == feat.device()),
+                    "hyper-parameter maps must match feat (float32, same shape and device)");
+    at::Tensor x = feat.contiguous(), go = grad_out.to(at::kDouble).contiguous(), a = h0.contiguous(), b = h1.contiguous(), c = h2.contiguous();
+    at::Tensor gx = at::zeros_like(x), g0 = at::zeros_like(x), g1 = at::zeros_like(x), g2 = at::zeros_like(x);
+    check_rc(lerf_warp_bwd(x.data_ptr<float>(), a.data_ptr<float>(), gauss ? b.data_ptr<float>() : nullptr, gauss ? c.data_ptr<float>() : nullptr,
+                           B * C, H, W, &g, (int)kind, max_sigma, go.data_ptr<double>(), gx.data_ptr<float>(), g0.data_ptr<float>(),
+                           gauss ? g1.data_ptr<float>() : nullptr, gauss ? g2.data_ptr<float>() : nullptr, cur_stream()),
+             "lerf_warp_bwd");
+    return {gx, g0, g1, g2};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(lerf, m) {
@@ -273,6 +352,9 @@ TORCH_LIBRARY(lerf, m) {
     m.def("resize_gauss(Tensor feat, Tensor rho, Tensor sigma_x, Tensor sigma_y, float scale_h, float scale_w, int support, float max_sigma) -> Tensor");
     m.def("resize_linear(Tensor feat, Tensor alpha, float scale_h, float scale_w, float max_sigma) -> Tensor");
     m.def("resize_backward(int kind, Tensor grad_out, Tensor feat, Tensor h0, Tensor h1, Tensor h2, float scale_h, float scale_w, int support, float max_sigma) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("warp_gauss(Tensor feat, Tensor rho, Tensor sigma_x, Tensor sigma_y, Tensor matrix, int out_h, int out_w, int support, float max_sigma) -> Tensor");
+    m.def("warp_linear(Tensor feat, Tensor alpha, Tensor matrix, int out_h, int out_w, float max_sigma) -> Tensor");
+    m.def("warp_backward(int kind, Tensor grad_out, Tensor feat, Tensor h0, Tensor h1, Tensor h2, Tensor matrix, int out_h, int out_w, int support, float max_sigma) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 // PyTorch-ROCm dispatches HIP tensors under the key named CUDA
@@ -283,4 +365,7 @@ TORCH_LIBRARY_IMPL(lerf, CUDA, m) {
     m.impl("resize_gauss", resize_gauss);
     m.impl("resize_linear", resize_linear);
     m.impl("resize_backward", resize_backward);
+    m.impl("warp_gauss", warp_gauss);
+    m.impl("warp_linear", warp_linear);
+    m.impl("warp_backward", warp_backward);
 }

@@ -4,7 +4,8 @@ reference's resize_right/resize_right2d_torch.py ([B,C,H,W] tensors on the GPU).
 SR geometry follows the torch classes' own float32 arithmetic (resize_right2d_torch.py:48-103, bit-equal tables:
 lerf_sr_axis_tables_f32), warp geometry the float64 one; SR returns float32, warps return float64 like
 the reference (its warp distances are double, resize_right2d_torch.py:286-296).
-The SR classes carry autograd (HIP backward, `_ResizeFn`); the warp classes are forward only.
+The SR classes carry autograd (HIP backward, `_ResizeFn`), and so do the warp classes (`_WarpFn`, every kind and pad
+mode: the gradient autograd derives for the reference's torch warps, resize_right2d_torch.py:249-487).
 """
 from __future__ import annotations
 
@@ -43,6 +44,29 @@ class _ResizeFn(torch.autograd.Function):
                                                   _lib.KINDS[kind], max_sigma, C.c_void_p(g.data_ptr()), gp[0], gp[1], gp[2],
                                                   gp[3], _lib.current_stream()), "lerf_resize_bwd_f32")
         return (None, None, None) + tuple(grads)
+
+
+class _WarpFn(torch.autograd.Function):
+    """lerf_warp forward (float64 out), lerf_warp_bwd backward (what autograd derives for resize_right2d_torch.py:249-487)
+    -- used when an input of warp() requires grad.  Gradients come back in each leaf's dtype."""
+
+    @staticmethod
+    def forward(ctx, geo, kind, max_sigma, x, *hs):
+        xf = x.detach().contiguous().float()
+        hf = [h.detach().contiguous().float() for h in hs]
+        out = ops.warp_planar(xf, hf, geo, kind, max_sigma, out="f64")
+        ctx.save_for_backward(xf, *hf)
+        ctx.meta = (geo, kind, float(max_sigma), [t.dtype for t in (x,) + hs])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, *hs = ctx.saved_tensors
+        geo, kind, max_sigma, dtypes = ctx.meta
+        need = ctx.needs_input_grad[3:]
+        grads = [torch.zeros_like(x) if need[k] else None for k in range(1 + len(hs))]
+        ops.warp_bwd_planar(x, hs, geo, kind, max_sigma, grad_out, grads)
+        return (None, None, None) + tuple(g.to(dt) if g is not None else None for g, dt in zip(grads, dtypes))
 
 
 def _check_dev(t, name):
@@ -213,7 +237,10 @@ class Warp2dTorch(object):
         for h in hypers:
             _check_dev(h, "hyper-parameter map")
             hs.append(h.reshape(B * Cn, H, W))
-        out = ops.warp_planar(x, hs, self.geo, kind, max_sigma, out="f64")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + hs):
+            out = _WarpFn.apply(self.geo, kind, max_sigma, x, *hs)
+        else:
+            out = ops.warp_planar(x, hs, self.geo, kind, max_sigma, out="f64")
         return out.reshape(B, Cn, self.out_sz[0], self.out_sz[1])
 
 

@@ -3,7 +3,8 @@
 The schemas and the device kernels' launchers are registered in C++ (`csrc/lerf_torch.cpp`, TORCH_LIBRARY /
 TORCH_LIBRARY_IMPL under the HIP backend's dispatch key) in `liblerf_torch.so`, which this module loads.  On top of
 that it attaches what is naturally Python: the fake (meta) kernels for shape inference / torch.compile tracing and the
-autograd formulas of the two float resamplers (their backward is itself an op, `lerf::resize_backward`).  There is no
+autograd formulas of the two float resamplers and the two float warps (their backward is itself an op,
+`lerf::resize_backward` / `lerf::warp_backward`).  There is no
 CPU kernel: CPU tensors are refused by the dispatcher, and a missing library raises here.
 
     s1, s2, pack = torch_ops.lut_args(LutSet.shipped("lerf-g"))
@@ -12,6 +13,8 @@ CPU kernel: CPU tensors are refused by the dispatcher, and a missing library rai
     out      = torch.ops.lerf.resize_gauss(feat_f32, rho, sx, sy, 2.0, 2.0, 2, 10.0)       # differentiable
     out      = torch.ops.lerf.resize_linear(feat_f32, alpha, 2.0, 2.0, 1.0)                # differentiable
     out      = torch.ops.lerf.warp_fused(img_u8, s1, s2, pack, M_3x3_f64, 2160, 3840, 2, 10.0)
+    out_f64  = torch.ops.lerf.warp_gauss(feat_f32, rho, sx, sy, M_3x3_f64, 2160, 3840, 2, 10.0)   # differentiable
+    out_f64  = torch.ops.lerf.warp_linear(feat_f32, alpha, M_3x3_f64, 2160, 3840, 1.0)           # differentiable
 """
 from __future__ import annotations
 
@@ -81,6 +84,23 @@ def _(kind, grad_out, feat, h0, h1, h2, scale_h, scale_w, support, max_sigma):
     return tuple(torch.empty_like(feat) for _ in range(4))
 
 
+@torch.library.register_fake("lerf::warp_gauss")
+def _(feat, rho, sigma_x, sigma_y, matrix, out_h, out_w, support, max_sigma):
+    B, C, H, W = feat.shape
+    return feat.new_empty((B, C, out_h, out_w), dtype=torch.float64)
+
+
+@torch.library.register_fake("lerf::warp_linear")
+def _(feat, alpha, matrix, out_h, out_w, max_sigma):
+    B, C, H, W = feat.shape
+    return feat.new_empty((B, C, out_h, out_w), dtype=torch.float64)
+
+
+@torch.library.register_fake("lerf::warp_backward")
+def _(kind, grad_out, feat, h0, h1, h2, matrix, out_h, out_w, support, max_sigma):
+    return tuple(torch.empty_like(feat) for _ in range(4))
+
+
 # ---- autograd of the float resamplers: what autograd derives for SteeringGaussianResize2dTorch.resize /
 #      AmplifiedLinearResize2dTorch.resize (resize_right2d_torch.py:154-247), computed by lerf_resize_bwd_f32
 def _gauss_setup(ctx, inputs, output):
@@ -111,3 +131,35 @@ def _linear_backward(ctx, grad_out):
 
 torch.library.register_autograd("lerf::resize_gauss", _gauss_backward, setup_context=_gauss_setup)
 torch.library.register_autograd("lerf::resize_linear", _linear_backward, setup_context=_linear_setup)
+
+
+# ---- autograd of the float warps: what autograd derives for SteeringGaussianWarp2dTorch.warp /
+#      AmplifiedLinearWarp2dTorch.warp (resize_right2d_torch.py:403-487), computed by lerf_warp_bwd
+def _warp_gauss_setup(ctx, inputs, output):
+    feat, rho, sx, sy, matrix, oh, ow, S, ms = inputs
+    ctx.save_for_backward(feat, rho, sx, sy, matrix)
+    ctx.meta = (oh, ow, S, ms)
+
+
+def _warp_gauss_backward(ctx, grad_out):
+    feat, rho, sx, sy, matrix = ctx.saved_tensors
+    oh, ow, S, ms = ctx.meta
+    gx, g0, g1, g2 = torch.ops.lerf.warp_backward(0, grad_out.contiguous(), feat, rho, sx, sy, matrix, oh, ow, S, ms)
+    return gx, g0, g1, g2, None, None, None, None, None
+
+
+def _warp_linear_setup(ctx, inputs, output):
+    feat, alpha, matrix, oh, ow, ms = inputs
+    ctx.save_for_backward(feat, alpha, matrix)
+    ctx.meta = (oh, ow, ms)
+
+
+def _warp_linear_backward(ctx, grad_out):
+    feat, alpha, matrix = ctx.saved_tensors
+    oh, ow, ms = ctx.meta
+    gx, g0, _, _ = torch.ops.lerf.warp_backward(1, grad_out.contiguous(), feat, alpha, alpha, alpha, matrix, oh, ow, 2, ms)
+    return gx, g0, None, None, None, None
+
+
+torch.library.register_autograd("lerf::warp_gauss", _warp_gauss_backward, setup_context=_warp_gauss_setup)
+torch.library.register_autograd("lerf::warp_linear", _warp_linear_backward, setup_context=_warp_linear_setup)
