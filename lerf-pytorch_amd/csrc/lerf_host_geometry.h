@@ -1,8 +1,10 @@
 // Host-side geometry of the LeRF path, free of any HIP dependency: what lerf_api.hip exports as lerf_sr_axis_tables(_f32),
 // lerf_out_size, lerf_invert3x3, lerf_warp_pads, lerf_mode_offsets, and the helpers the kernels share with it (pattern
-// offsets, homography projection, support boundary).  One source for both builds: liblerf_hip.so (hipcc) and the
-// AddressSanitizer / UBSan host build of the same functions (csrc/lerf_host_sanitize.cpp, `make asan`), which the CPU suite
-// runs against the product library (tests/test_sanitizers_cpu.py).
+// offsets, image pad rule, homography projection, support boundary, and the one definition of the homographic warp's tap
+// geometry: warp_pixel + axis_tap, which every warp kernel, its tie guard and the tile-fused warp's ownership key derive
+// their taps from).  One source for both builds: liblerf_hip.so (hipcc) and the AddressSanitizer / UBSan host build of the
+// same functions (csrc/lerf_host_sanitize.cpp, `make asan`), which the CPU suite runs against the product library
+// (tests/test_sanitizers_cpu.py).
 #pragma once
 
 #include <math.h>
@@ -69,6 +71,70 @@ LERF_HD inline void project_point(const double* m, int i, int j, int H, int W, d
 LERF_HD inline int left_boundary(double g, int S) {
 #pragma clang fp contract(off)
     return (int)ceil(g - (double)S / 2 - (double)kEps32);
+}
+
+
+// Source index of padded position i (unpadded coordinates, may lie outside [0, n)) under the padding rule of the IMAGE
+// operand: np.pad(input, pad_vec, mode=self.pad_mode) (resize_right/resize_right2d_numpy.py:208, :560) /
+// F.pad(input, pad_vec, mode=self.pad_mode) (resize_right2d_torch.py:189, :362).  *zero: the value is 0 (constant).
+// reflect / symmetric / wrap follow numpy for any pad width (periodic extension).
+LERF_HD inline int pad_index(int i, int n, int mode, bool* zero) {
+    *zero = false;
+    if (i >= 0 && i < n) return i;
+    if (mode == 1) return i < 0 ? 0 : n - 1;                          // edge / replicate
+    if (mode == 2) {                                                  // reflect (no edge repeat)
+        const int p = 2 * (n - 1);
+        if (p == 0) return 0;
+        const int m = ((i % p) + p) % p;
+        return m < n ? m : p - m;
+    }
+    if (mode == 3) {                                                  // symmetric (edge repeated)
+        const int p = 2 * n;
+        const int m = ((i % p) + p) % p;
+        return m < n ? m : p - 1 - m;
+    }
+    if (mode == 4) return ((i % n) + n) % n;                          // wrap / circular
+    *zero = true;                                                     // constant (0)
+    return i < 0 ? 0 : n - 1;
+}
+
+// Warp2dNumpy.set_shape / get_distance (resize_right2d_numpy.py:321-407): output pixel (i, j) of the homographic warp in
+// padded coordinates.  The projected point is clipped to [0, in] and shifted by the low pads (calc_pad_sz, :366-367); lr, lc
+// are the support's left boundary.
+struct WarpPixel {
+    double gr, gc;      // projected point (padded coordinates)
+    int lr, lc;         // left boundary of the support (padded coordinates)
+};
+
+LERF_HD inline WarpPixel warp_pixel(const double minv[9], int S, int pad_r_lo, int pad_c_lo, int i, int j, int H, int W) {
+    WarpPixel p;
+    project_point(minv, i, j, H, W, &p.gr, &p.gc);
+    p.lr = left_boundary(p.gr, S) + pad_r_lo;
+    p.lc = left_boundary(p.gc, S) + pad_c_lo;
+    p.gr += (double)pad_r_lo;
+    p.gc += (double)pad_c_lo;
+    return p;
+}
+
+// Tap k of the support along one axis (rows: g = gr, l = lr, n = H, the row pads; columns likewise).  The taps are
+// separable: a row tap depends on the row offset alone, a column tap on the column offset alone.
+struct AxisTap {
+    double d;           // float64 distance of the projected point from the tap
+    int cl;             // clamped source index: where the replicate-padded hyper-parameter maps are read
+    bool inside;        // the tap lies inside the frame (the packed warps take the image as 0 outside it)
+    int s;              // image index under the image's pad rule
+    bool z;             // the image value is the constant pad (0)
+};
+
+LERF_HD inline AxisTap axis_tap(double g, int l, int k, int n, int pad_lo, int pad_mode) {
+    AxisTap t;
+    const int p = clampi(l + k, 0, n - 1);      // field of view clipped to [0, in-1] while indexing the PADDED arrays (:396-398)
+    t.d = g - (double)p;
+    const int s = p - pad_lo;                   // unpadded source coordinate
+    t.cl = clampi(s, 0, n - 1);
+    t.inside = s == t.cl;
+    t.s = pad_index(s, n, pad_mode, &t.z);      // image pad rule (:560)
+    return t;
 }
 
 
@@ -187,10 +253,8 @@ inline int warp_pads(const double minv[9], int in_h, int in_w, int out_h, int ou
 // left of it, which the tile's stage-2 region holds.  (Pixels projected outside the frame are clipped onto its border and belong
 // to the border tiles.)
 LERF_HD inline void warp_owner_key(const double minv[9], int pad_r_lo, int pad_c_lo, int i, int j, int H, int W, int* key_r, int* key_c) {
-    double gr, gc;
-    project_point(minv, i, j, H, W, &gr, &gc);
-    const int lr = left_boundary(gr, 2) + pad_r_lo, lc = left_boundary(gc, 2) + pad_c_lo;
-    const int r0 = clampi(clampi(lr, 0, H - 1) - pad_r_lo, 0, H - 1), c0 = clampi(clampi(lc, 0, W - 1) - pad_c_lo, 0, W - 1);
+    const WarpPixel p = warp_pixel(minv, 2, pad_r_lo, pad_c_lo, i, j, H, W);
+    const int r0 = axis_tap(p.gr, p.lr, 0, H, pad_r_lo, LERF_PAD_CONSTANT).cl, c0 = axis_tap(p.gc, p.lc, 0, W, pad_c_lo, LERF_PAD_CONSTANT).cl;
     *key_r = r0 + 1 < H - 1 ? r0 + 1 : H - 1;
     *key_c = c0 + 1 < W - 1 ? c0 + 1 : W - 1;
 }

@@ -594,8 +594,6 @@ warp_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
     int c = xc - j * C;
     const int S = g.S;
     const WarpPixel px = warp_pixel(g, i, j, H, W);
-    const int lr = px.lr, lc = px.lc;
-    const double gr = px.gr, gc = px.gc;
     A emin = 0, num = 0, den = 0;
     for (int pass = (KIND == LERF_KIND_GAUSS ? 0 : 1); pass < 2; ++pass) {
         for (int a = 0; a < S; ++a)
@@ -641,7 +639,7 @@ warp_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
             const uint32_t k12 = KIND == LERF_KIND_GAUSS ? (((uint32_t)h1[ho]) << 8) | (((uint32_t)h2[ho]) << 16) : 0u;
             return k0 | k12 | ((uint32_t)feat[rcl * fy + ccl * fx + c * fc] << 24);
         };
-        if (warp_tie_guard<KIND>((float)res, S, H, W, g, lr, lc, gr, gc, (float)max_sigma, tap,
+        if (warp_tie_guard<KIND>((float)res, S, H, W, g, px, (float)max_sigma, tap,
                                  reinterpret_cast<uint8_t*>(out + i * oy + j * ox + c * oc)))
             return;
     }
@@ -716,27 +714,17 @@ warp_packed_kernel(const uint32_t* __restrict__ packed, int64_t packed_sn, int H
     int j = xc / C;
     int c = xc - j * C;
     const int S = g.S;
-    double gr, gc;
-    project_point(g.minv, i + g.oy0, j + g.ox0, H, W, &gr, &gc);
-    int lr = left_boundary(gr, S) + g.pad_r_lo;
-    int lc = left_boundary(gc, S) + g.pad_c_lo;
-    gr += (double)g.pad_r_lo;
-    gc += (double)g.pad_c_lo;
+    const WarpPixel px = warp_pixel(g, i, j, H, W);
     float emin = 0, num = 0, den = 0;
     for (int pass = (KIND == LERF_KIND_GAUSS ? 0 : 1); pass < 2; ++pass) {
         for (int a = 0; a < S; ++a)
             for (int b = 0; b < S; ++b) {
-                int pr = clampi(lr + b, 0, H - 1), pc = clampi(lc + a, 0, W - 1);       // :396-398
-                double dxd = gr - (double)pr, dyd = gc - (double)pc;
-                float dx = (float)dxd, dy = (float)dyd;
-                int sr = pr - g.pad_r_lo, sc_ = pc - g.pad_c_lo;
-                int rcl = clampi(sr, 0, H - 1), ccl = clampi(sc_, 0, W - 1);
-                bool inside = (sr == rcl) && (sc_ == ccl);
-                const uint32_t d = packed[((int64_t)rcl * W + ccl) * C + c];
+                const WarpTap<float> tp = warp_tap<float>(g, px, a, b, H, W);
+                const uint32_t d = packed[((int64_t)tp.rcl * W + tp.ccl) * C + c];
                 float w;
                 if (KIND == LERF_KIND_GAUSS) {
                     float e = s3::gauss_form(s3::u8_over_255((float)(d & 0xFFu)), s3::u8_over_255((float)((d >> 8) & 0xFFu)),
-                                             s3::u8_over_255((float)((d >> 16) & 0xFFu)), max_sigma, dx, dy);
+                                             s3::u8_over_255((float)((d >> 16) & 0xFFu)), max_sigma, tp.dx, tp.dy);
                     if (pass == 0) {
                         emin = (a == 0 && b == 0) ? e : fminf(e, emin);
                         continue;
@@ -744,9 +732,9 @@ warp_packed_kernel(const uint32_t* __restrict__ packed, int64_t packed_sn, int H
                     w = s3::gauss_weight(e, emin);
                 } else {
                     float alpha = s3::lin_alpha_of(s3::u8_over_255((float)(d & 0xFFu)), max_sigma);
-                    w = s3::lin_factor(alpha, dx, dist_class(dxd)) * s3::lin_factor(alpha, dy, dist_class(dyd));
+                    w = s3::lin_factor(alpha, tp.dx, dist_class(tp.dxd)) * s3::lin_factor(alpha, tp.dy, dist_class(tp.dyd));
                 }
-                float val = inside ? (float)(d >> 24) : 0.0f;
+                float val = tp.inside ? (float)(d >> 24) : 0.0f;
                 num += w * val;
                 den += w;
             }
@@ -755,8 +743,7 @@ warp_packed_kernel(const uint32_t* __restrict__ packed, int64_t packed_sn, int H
     if (KIND == LERF_KIND_GAUSS && emin * 0.5f > 745.2f) res = __builtin_nanf("");
     if (sizeof(TO) == 1) {
         auto tap = [&](int rcl, int ccl) -> uint32_t { return packed[((int64_t)rcl * W + ccl) * C + c]; };
-        if (warp_tie_guard<KIND>(res, S, H, W, g, lr, lc, gr, gc, max_sigma, tap,
-                                 reinterpret_cast<uint8_t*>(out + i * oy + j * ox + c * oc)))
+        if (warp_tie_guard<KIND>(res, S, H, W, g, px, max_sigma, tap, reinterpret_cast<uint8_t*>(out + i * oy + j * ox + c * oc)))
             return;
     }
     Storer<TO>::put(out + i * oy + j * ox + c * oc, res);
@@ -783,23 +770,15 @@ warp_packed_px_kernel(const uint32_t* __restrict__ packed0, int64_t packed_sn, i
     const int j = (b - i * gx) * 256 + (int)threadIdx.x;
     if (j >= g.oW) return;
     const WarpPx2 G = warp_px_geometry(g, i, j, H, W);
-    const int lr = G.lr, lc = G.lc;
-    const double gr = G.gr, gc = G.gc;
     int64_t pos[S * S];
-    float dx[S], dy[S];
-    int cx[S], cy[S];
-    bool in_r[S], in_c[S];
-#pragma unroll
-    for (int b = 0; b < S; ++b) { dx[b] = G.dx[b]; cx[b] = G.cx[b]; in_r[b] = G.in_r[b]; dy[b] = G.dy[b]; cy[b] = G.cy[b]; in_c[b] = G.in_c[b]; }
 #pragma unroll
     for (int a = 0; a < S; ++a)
 #pragma unroll
         for (int b = 0; b < S; ++b) pos[a * S + b] = ((int64_t)G.rrow[b] * W + G.rcol[a]) * C;
     float dxs[S], dys[S];
     const float gsc = (PROD && KIND == LERF_KIND_GAUSS) ? s3::gauss_scale(max_sigma) : 1.0f;
-    const float ms255 = max_sigma * (1.0f / 255.0f);
 #pragma unroll
-    for (int b = 0; b < S; ++b) { dxs[b] = dx[b] * gsc; dys[b] = dy[b] * gsc; }
+    for (int b = 0; b < S; ++b) { dxs[b] = G.dx[b] * gsc; dys[b] = G.dy[b] * gsc; }
     // the frames of the batch share the homography: the float64 projection and the tap geometry above are paid once per
     // output pixel, not once per frame (round 3: a fifth of this kernel's instructions went into repeating them)
 #pragma unroll 1
@@ -808,48 +787,18 @@ warp_packed_px_kernel(const uint32_t* __restrict__ packed0, int64_t packed_sn, i
     TO* __restrict__ out = out0 + (int64_t)fr * out_sn;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        uint32_t d[S * S];
-#pragma unroll
-        for (int t = 0; t < S * S; ++t) d[t] = packed[pos[t] + c];
+        TO* dst = out + i * oy + j * ox + c * oc;
+        auto tap = [&](int rcl, int ccl) -> uint32_t { return packed[((int64_t)rcl * W + ccl) * C + c]; };
+        float res;
         if constexpr (PROD) {
             static_assert(sizeof(TO) == 1, "production arithmetic: uint8 outputs");
-            TO* dst = out + i * oy + j * ox + c * oc;
-            auto tap = [&](int rcl, int ccl) -> uint32_t { return packed[((int64_t)rcl * W + ccl) * C + c]; };
-            float res;
             if (warp_px_value_u8<KIND>(G, g, H, W, max_sigma, dxs, dys, tap, reinterpret_cast<uint8_t*>(dst), &res)) continue;
-            Storer<TO>::put(dst, res);
-            continue;
-        }
-        float e[S * S], emin = 0.0f, num = 0.0f, den = 0.0f;
+        } else {
+            uint32_t d[S * S];
 #pragma unroll
-        for (int a = 0; a < S; ++a)
-#pragma unroll
-            for (int b = 0; b < S; ++b) {
-                const uint32_t q = d[a * S + b];
-                if (KIND == LERF_KIND_GAUSS) {
-                    e[a * S + b] = s3::gauss_form(s3::u8_over_255((float)(q & 0xFFu)), s3::u8_over_255((float)((q >> 8) & 0xFFu)),
-                                                  s3::u8_over_255((float)((q >> 16) & 0xFFu)), max_sigma, dx[b], dy[a]);
-                    emin = (a == 0 && b == 0) ? e[0] : fminf(e[a * S + b], emin);
-                } else {
-                    const float alpha = s3::lin_alpha_of(s3::u8_over_255((float)(q & 0xFFu)), max_sigma);
-                    e[a * S + b] = s3::lin_factor(alpha, dx[b], cx[b]) * s3::lin_factor(alpha, dy[a], cy[a]);
-                }
-            }
-#pragma unroll
-        for (int a = 0; a < S; ++a)
-#pragma unroll
-            for (int b = 0; b < S; ++b) {
-                const float w = KIND == LERF_KIND_GAUSS ? s3::gauss_weight(e[a * S + b], emin) : e[a * S + b];
-                const float val = (in_r[b] && in_c[a]) ? (float)(d[a * S + b] >> 24) : 0.0f;
-                num += w * val;
-                den += w;
-            }
-        float res = num / den;
-        if (KIND == LERF_KIND_GAUSS && emin * 0.5f > 745.2f) res = __builtin_nanf("");
-        TO* dst = out + i * oy + j * ox + c * oc;
-        if (sizeof(TO) == 1) {
-            auto tap = [&](int rcl, int ccl) -> uint32_t { return packed[((int64_t)rcl * W + ccl) * C + c]; };
-            if (warp_tie_guard<KIND>(res, S, H, W, g, lr, lc, gr, gc, max_sigma, tap, reinterpret_cast<uint8_t*>(dst))) continue;
+            for (int t = 0; t < S * S; ++t) d[t] = packed[pos[t] + c];
+            res = warp_px_value<KIND>(G, max_sigma, d);
+            if (sizeof(TO) == 1 && warp_tie_guard<KIND>(res, S, H, W, g, G.p, max_sigma, tap, reinterpret_cast<uint8_t*>(dst))) continue;
         }
         Storer<TO>::put(dst, res);
     }

@@ -1,8 +1,9 @@
-// One output pixel of a homographic warp (S = 2, RGB) on the PACKED stage outputs (hq0 | hq1 << 8 | hq2 << 16 | feat << 24 per
-// pixel-channel): the float64 projection and tap geometry of Warp2dNumpy (resize_right/resize_right2d_numpy.py:306-407) and the
-// float32 production arithmetic + float64 tie guard of the uint8 path.  Shared by warp_packed_px_kernel (taps from the packed
-// maps in HBM / L2) and the tile-fused warp (taps from the tile's packed dwords in LDS, lerf_fused_impl.h): the same
-// instructions in both, so fused == unfused bit for bit.
+// The S = 2 RGB homographic warp on the PACKED stage outputs (hq0 | hq1 << 8 | hq2 << 16 | feat << 24 per pixel-channel) and
+// the float64 tie guard of every uint8 warp.  WarpPx2 is the per-pixel tap geometry of warp_pixel / axis_tap
+// (lerf_host_geometry.h) evaluated once for the two rows and two columns of taps; warp_px_value_u8 is the float32
+// production arithmetic (max_sigma <= s3::kNoShiftMaxSigma), warp_px_value the exact float32 parameter formation.  Shared by
+// warp_packed_px_kernel (taps from the packed maps in HBM / L2) and the tile-fused warp (taps from the tile's packed dwords in
+// LDS, lerf_fused_impl.h): the same instructions in both, so fused == unfused bit for bit.
 #pragma once
 
 #include "lerf_kernels.h"
@@ -23,42 +24,40 @@ __device__ __forceinline__ int dist_class(A x) {
 }
 
 // Tie guard of the uint8 warps: an output within kTieEps of a half-integer is resolved in float64 (s3::resolve_u8: the
-// reference's float64 forms, and its whole dtype chain where that is still undecided), like the SR kernels do; `tap(r, c)` returns (k0 | k1<<8 | k2<<16 | val<<24)
-// of the clamped source pixel.
+// reference's float64 forms, and its whole dtype chain where that is still undecided), like the SR kernels do, on the taps of
+// pixel p rebuilt with axis_tap; `tap(r, c)` returns (k0 | k1<<8 | k2<<16 | val<<24) of the clamped source pixel.
 template <int KIND, int S, typename F>
-__device__ __forceinline__ uint8_t warp_resolve_u8(int H, int W, const WarpGeo& g, int lr, int lc, double gr, double gc,
-                                                   float max_sigma, F tap) {
+__device__ __forceinline__ uint8_t warp_resolve_u8(int H, int W, const WarpGeo& g, const WarpPixel& p, float max_sigma, F tap) {
     uint32_t dd[S * S];
     double dx[S], dy[S];
 #pragma unroll
-    for (int b = 0; b < S; ++b) dx[b] = gr - (double)clampi(lr + b, 0, H - 1);
-#pragma unroll
-    for (int a = 0; a < S; ++a) dy[a] = gc - (double)clampi(lc + a, 0, W - 1);
+    for (int k = 0; k < S; ++k) {
+        dx[k] = axis_tap(p.gr, p.lr, k, H, g.pad_r_lo, g.pad_mode).d;
+        dy[k] = axis_tap(p.gc, p.lc, k, W, g.pad_c_lo, g.pad_mode).d;
+    }
 #pragma unroll
     for (int a = 0; a < S; ++a)
 #pragma unroll
         for (int b = 0; b < S; ++b) {
-            const int sr = clampi(lr + b, 0, H - 1) - g.pad_r_lo, sc_ = clampi(lc + a, 0, W - 1) - g.pad_c_lo;
-            const int rcl = clampi(sr, 0, H - 1), ccl = clampi(sc_, 0, W - 1);
-            const uint32_t d = tap(rcl, ccl);
-            dd[a * S + b] = ((sr == rcl) && (sc_ == ccl)) ? d : (d & 0x00FFFFFFu);      // zero image outside the frame
+            const AxisTap r = axis_tap(p.gr, p.lr, b, H, g.pad_r_lo, g.pad_mode), c = axis_tap(p.gc, p.lc, a, W, g.pad_c_lo, g.pad_mode);
+            const uint32_t d = tap(r.cl, c.cl);
+            dd[a * S + b] = (r.inside && c.inside) ? d : (d & 0x00FFFFFFu);      // zero image outside the frame
         }
     return s3::resolve_u8<KIND == LERF_KIND_GAUSS, S>(dd, dx, dy, max_sigma);
 }
 
 template <int KIND, typename F>
-__device__ __forceinline__ bool warp_tie_guard(float res, int S, int H, int W, const WarpGeo& g, int lr, int lc, double gr,
-                                               double gc, float max_sigma, F tap, uint8_t* dst) {
+__device__ __forceinline__ bool warp_tie_guard(float res, int S, int H, int W, const WarpGeo& g, const WarpPixel& p, float max_sigma,
+                                               F tap, uint8_t* dst) {
     if (!(KIND == LERF_KIND_GAUSS || KIND == LERF_KIND_LINEAR) || !s3::near_tie(res)) return false;
-    if (S == 2) *dst = warp_resolve_u8<KIND, 2>(H, W, g, lr, lc, gr, gc, max_sigma, tap);
-    else if (S == 4) *dst = warp_resolve_u8<KIND, 4>(H, W, g, lr, lc, gr, gc, max_sigma, tap);
+    if (S == 2) *dst = warp_resolve_u8<KIND, 2>(H, W, g, p, max_sigma, tap);
+    else if (S == 4) *dst = warp_resolve_u8<KIND, 4>(H, W, g, p, max_sigma, tap);
     else return false;
     return true;
 }
 
 struct WarpPx2 {
-    int lr, lc;                // first tap in PADDED coordinates
-    double gr, gc;             // projected position in padded coordinates
+    WarpPixel p;               // projected position and first tap (padded coordinates)
     float dx[2], dy[2];        // distances to the two rows / columns of taps
     int cx[2], cy[2];          // their classes for the amplified-linear kernel
     int rrow[2], rcol[2];      // the taps' source rows / columns, clamped into the frame (where the hyper-parameters are read)
@@ -66,35 +65,20 @@ struct WarpPx2 {
 };
 
 __device__ __forceinline__ WarpPx2 warp_px_geometry(const WarpGeo& g, int i, int j, int H, int W) {
-    constexpr int S = 2;
     WarpPx2 G;
-    double gr, gc;
-    project_point(g.minv, i + g.oy0, j + g.ox0, H, W, &gr, &gc);
-    G.lr = left_boundary(gr, S) + g.pad_r_lo;
-    G.lc = left_boundary(gc, S) + g.pad_c_lo;
-    gr += (double)g.pad_r_lo;
-    gc += (double)g.pad_c_lo;
-    G.gr = gr;
-    G.gc = gc;
+    G.p = warp_pixel(g.minv, 2, g.pad_r_lo, g.pad_c_lo, i + g.oy0, j + g.ox0, H, W);
 #pragma unroll
-    for (int b = 0; b < S; ++b) {
-        const int pr = clampi(G.lr + b, 0, H - 1);
-        const double d = gr - (double)pr;
-        G.dx[b] = (float)d;
-        G.cx[b] = dist_class(d);
-        const int sr = pr - g.pad_r_lo;
-        G.rrow[b] = clampi(sr, 0, H - 1);
-        G.in_r[b] = sr == G.rrow[b];
-    }
-#pragma unroll
-    for (int a = 0; a < S; ++a) {
-        const int pc = clampi(G.lc + a, 0, W - 1);
-        const double d = gc - (double)pc;
-        G.dy[a] = (float)d;
-        G.cy[a] = dist_class(d);
-        const int sc_ = pc - g.pad_c_lo;
-        G.rcol[a] = clampi(sc_, 0, W - 1);
-        G.in_c[a] = sc_ == G.rcol[a];
+    for (int k = 0; k < 2; ++k) {
+        const AxisTap r = axis_tap(G.p.gr, G.p.lr, k, H, g.pad_r_lo, g.pad_mode);
+        G.dx[k] = (float)r.d;
+        G.cx[k] = dist_class(r.d);
+        G.rrow[k] = r.cl;
+        G.in_r[k] = r.inside;
+        const AxisTap c = axis_tap(G.p.gc, G.p.lc, k, W, g.pad_c_lo, g.pad_mode);
+        G.dy[k] = (float)c.d;
+        G.cy[k] = dist_class(c.d);
+        G.rcol[k] = c.cl;
+        G.in_c[k] = c.inside;
     }
     return G;
 }
@@ -133,7 +117,41 @@ __device__ __forceinline__ bool warp_px_value_u8(const WarpPx2& G, const WarpGeo
         if (emin > 1075.1f) res = __builtin_nanf("");
     }
     *res_out = res;
-    return warp_tie_guard<KIND>(res, S, H, W, g, G.lr, G.lc, G.gr, G.gc, max_sigma, tap, dst);
+    return warp_tie_guard<KIND>(res, S, H, W, g, G.p, max_sigma, tap, dst);
+}
+
+// channel value of the pixel with the exact float32 parameter formation (float outputs, and uint8 outputs above
+// s3::kNoShiftMaxSigma); d[a * 2 + b] = packed dword of tap (a, b), this channel.  NaN where every weight vanishes.
+template <int KIND>
+__device__ __forceinline__ float warp_px_value(const WarpPx2& G, float max_sigma, const uint32_t (&d)[4]) {
+    constexpr int S = 2;
+    float e[S * S], emin = 0.0f, num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (int a = 0; a < S; ++a)
+#pragma unroll
+        for (int b = 0; b < S; ++b) {
+            const uint32_t q = d[a * S + b];
+            if (KIND == LERF_KIND_GAUSS) {
+                e[a * S + b] = s3::gauss_form(s3::u8_over_255((float)(q & 0xFFu)), s3::u8_over_255((float)((q >> 8) & 0xFFu)),
+                                              s3::u8_over_255((float)((q >> 16) & 0xFFu)), max_sigma, G.dx[b], G.dy[a]);
+                emin = (a == 0 && b == 0) ? e[0] : fminf(e[a * S + b], emin);
+            } else {
+                const float alpha = s3::lin_alpha_of(s3::u8_over_255((float)(q & 0xFFu)), max_sigma);
+                e[a * S + b] = s3::lin_factor(alpha, G.dx[b], G.cx[b]) * s3::lin_factor(alpha, G.dy[a], G.cy[a]);
+            }
+        }
+#pragma unroll
+    for (int a = 0; a < S; ++a)
+#pragma unroll
+        for (int b = 0; b < S; ++b) {
+            const float w = KIND == LERF_KIND_GAUSS ? s3::gauss_weight(e[a * S + b], emin) : e[a * S + b];
+            const float val = (G.in_r[b] && G.in_c[a]) ? (float)(d[a * S + b] >> 24) : 0.0f;
+            num += w * val;
+            den += w;
+        }
+    float res = num / den;
+    if (KIND == LERF_KIND_GAUSS && emin * 0.5f > 745.2f) res = __builtin_nanf("");
+    return res;
 }
 
 }  // namespace lerf

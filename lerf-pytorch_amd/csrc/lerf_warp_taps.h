@@ -1,8 +1,8 @@
-// Per-output-pixel geometry of the homographic warp on planar operands (Warp2dTorch.get_distance / warp,
-// resize_right2d_torch.py:249-487, float64 like the reference's distances): the projection, the support's left
-// boundary, the pad shift, the taps of the S x S patch and the fixed interpolation kernels.  Shared by the forward
-// (warp_kernel, lerf_kernels.hip) and the backward (lerf_warp_bwd.hip) so that the two enumerate the same taps with the
-// same float64 distances and weights.
+// The homographic warp's taps on planar operands (Warp2dTorch.get_distance / warp, resize_right2d_torch.py:249-487, float64
+// like the reference's distances) in the form the per-tap kernels take them -- the forward warp_kernel and the packed
+// per-channel warp_packed_kernel (lerf_kernels.hip), and the backward (lerf_warp_bwd.hip) -- plus the fixed interpolation
+// kernels.  The geometry itself (projection, support boundary, pad shift, clamps, distances, pad rule) is warp_pixel /
+// axis_tap of lerf_host_geometry.h, which the S = 2 packed paths (lerf_warp_px.h) share.
 #pragma once
 
 #include "lerf_kernels.h"
@@ -29,20 +29,9 @@ __device__ __forceinline__ double fixed_kernel_1d(int kind, double x) {
     return ((-1.0 <= x && x < 0.0) ? 1.0 : 0.0) + ((0.0 <= x && x <= 1.0) ? 1.0 : 0.0);   // box :67-70
 }
 
-struct WarpPixel {
-    double gr, gc;      // projected point, clipped to [0, in] and shifted by the low pads (padded coordinates)
-    int lr, lc;         // left boundary of the support in padded coordinates
-};
-
 // output pixel (i, j) of the launch's rectangle
 __device__ __forceinline__ WarpPixel warp_pixel(const WarpGeo& g, int i, int j, int H, int W) {
-    WarpPixel p;
-    project_point(g.minv, i + g.oy0, j + g.ox0, H, W, &p.gr, &p.gc);
-    p.lr = left_boundary(p.gr, g.S) + g.pad_r_lo;
-    p.lc = left_boundary(p.gc, g.S) + g.pad_c_lo;
-    p.gr += (double)g.pad_r_lo;      // calc_pad_sz shifts grid and field of view (:366-367)
-    p.gc += (double)g.pad_c_lo;
-    return p;
+    return warp_pixel(g.minv, g.S, g.pad_r_lo, g.pad_c_lo, i + g.oy0, j + g.ox0, H, W);
 }
 
 template <typename A>
@@ -52,23 +41,25 @@ struct WarpTap {
     int rcl, ccl;       // clamped source pixel: where the replicate-padded hyper-parameter maps are read
     int rs, cs;         // image pixel under the image's pad rule
     bool zr, zc;        // the image value is the constant pad (0)
+    bool inside;        // the tap lies inside the frame
 };
 
 // tap (a, b) of the patch: column offset a, row offset b
 template <typename A>
 __device__ __forceinline__ WarpTap<A> warp_tap(const WarpGeo& g, const WarpPixel& p, int a, int b, int H, int W) {
+    const AxisTap r = axis_tap(p.gr, p.lr, b, H, g.pad_r_lo, g.pad_mode), c = axis_tap(p.gc, p.lc, a, W, g.pad_c_lo, g.pad_mode);
     WarpTap<A> t;
-    // field of view clipped to [0, in-1] while indexing the PADDED arrays (:396-398)
-    const int pr = clampi(p.lr + b, 0, H - 1), pc = clampi(p.lc + a, 0, W - 1);
-    t.dxd = p.gr - (double)pr;
-    t.dyd = p.gc - (double)pc;
-    t.dx = (A)t.dxd;
-    t.dy = (A)t.dyd;
-    const int sr = pr - g.pad_r_lo, sc = pc - g.pad_c_lo;      // unpadded source coordinates
-    t.rcl = clampi(sr, 0, H - 1);
-    t.ccl = clampi(sc, 0, W - 1);
-    t.rs = pad_index(sr, H, g.pad_mode, &t.zr);                // image pad rule (:560)
-    t.cs = pad_index(sc, W, g.pad_mode, &t.zc);
+    t.dxd = r.d;
+    t.dyd = c.d;
+    t.dx = (A)r.d;
+    t.dy = (A)c.d;
+    t.rcl = r.cl;
+    t.ccl = c.cl;
+    t.rs = r.s;
+    t.cs = c.s;
+    t.zr = r.z;
+    t.zc = c.z;
+    t.inside = r.inside && c.inside;
     return t;
 }
 

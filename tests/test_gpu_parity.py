@@ -464,6 +464,34 @@ def test_warp_packed_equals_direct_warp(torch, eng_g, p):
     assert float((a[ok] - b[ok]).abs().max()) <= 1e-3
 
 
+@pytest.mark.parametrize("out", ["u8", "f32"])
+@pytest.mark.parametrize("C,S,max_sigma", [(3, 2, 10.0), (3, 2, 16.0), (1, 2, 10.0), (3, 4, 10.0)])
+@pytest.mark.parametrize("kind", ["gauss", "linear"])
+def test_warp_packed_paths_vs_oracle(torch, golden, oracle, eng_g, eng_l, kind, C, S, max_sigma, out):
+    """every lerf_warp_packed kernel against the float64 oracle on a non-affine homography: the per-pixel RGB kernel
+    (S = 2, C = 3) with the production arithmetic (uint8, max_sigma <= 13) and without it, and the per-channel kernel
+    (C = 1, S = 4).  uint8 bytes exactly, float32 within F32_TOL with NaN at the same positions."""
+    from lerf_pytorch_amd import ops
+    M = golden("g4_warp.npz")["isc/matrix"]
+    out_hw = (60, 70)
+    imgs = np.random.default_rng(100 * C + S + int(max_sigma)).integers(0, 256, (2, 52, 52, C), dtype=np.uint8)
+    luts = (eng_g if kind == "gauss" else eng_l).luts
+    packed = ops.stages_packed(torch.from_numpy(imgs).cuda(), luts)
+    geo = ops.WarpGeometry((52, 52), M, out_hw, S)
+    got = ops.warp_packed(packed, geo, kind, max_sigma, out=out).cpu().numpy()
+    for n in range(2):
+        feat, hq = (t.cpu().numpy() for t in ops.unpack_stages(packed[n], luts.oC))
+        ref = oracle.warp_u8(feat, hq, M, out_hw, S, max_sigma, kind)
+        if out == "u8":
+            want = oracle.to_u8(np.nan_to_num(ref, nan=0.0))
+            assert np.array_equal(got[n], want), "%d of %d bytes differ" % ((got[n] != want).sum(), want.size)
+        else:
+            assert np.array_equal(np.isnan(got[n]), np.isnan(ref))
+            ok = ~np.isnan(ref)
+            err = np.max(np.abs(got[n][ok] - ref[ok]))
+            assert err <= F32_TOL, err
+
+
 @pytest.mark.parametrize("H,W,scale,S", [
     (1, 1, 2, 2), (2, 3, 2, 2), (7, 5, 3, 2), (63, 65, 2, 2), (64, 64, 1, 2), (64, 128, 4, 2), (65, 64, 2.5, 2),
     (33, 200, (1.5, 2.0), 2), (130, 70, (1.0, 3.0), 2), (100, 90, 2, 4), (40, 300, 1.25, 4), (129, 129, 4, 4)])
