@@ -419,11 +419,17 @@ int lerf_swf2lut_interp_f32(const float* weight, int oC, char mode, const float*
 int lerf_swf2lut_interp_bwd_f32(const float* weight, int oC, char mode, const float* img, const float* grad_out,
                                 int n_planes, int h, int w, int bd, float* grad_weight, float* grad_img, void* stream);
 
-/* Backward of lerf_resize (kinds GAUSS, LINEAR) on planar float32 maps, as autograd derives it for
- * SteeringGaussianResize2dTorch.resize / AmplifiedLinearResize2dTorch.resize (resize_right2d_torch.py:154-247):
- * feat, h0..h2: float32 [N][H][W] (hyper maps in [0,1]; h1, h2 unused for LINEAR), grad_out: float32
- * [N][out_h][out_w].  grad_feat / grad_h*: float32 [N][H][W], ACCUMULATED into with float atomics (zero them first);
- * any of them may be NULL.  Uses the float32 distance tables of `geo`. */
+/* Backward of lerf_resize on planar float32 maps, as autograd derives it for the reference's torch resizes
+ * (SteeringGaussianResize2dTorch / AmplifiedLinearResize2dTorch.resize, Resize2dTorch.resize with BicubicResize2dTorch's
+ * cubic and the bilinear / lanczos kinds on the same base class, resize_right2d_torch.py:105-247), on the float32 distance
+ * tables of `geo`.
+ * feat, h0..h2: float32 [N][H][W] (hyper maps in [0,1]; h0..h2 for GAUSS, h0 alone for LINEAR, none for the fixed kinds
+ * NEAREST..LANCZOS3, where they may be NULL), grad_out: float32 [N][out_h][out_w].  grad_feat / grad_h*: float32 [N][H][W],
+ * ACCUMULATED into with float atomics (zero them first); any of them may be NULL.  Kinds GAUSS and LINEAR give image and
+ * hyper-map gradients, the fixed kinds the image gradient only (their weights are the forward's k(dx) k(dy) / (sr sc),
+ * not normalised at S = 1).  The image gradient follows geo->pad_mode, LERF_PAD_CONSTANT..LERF_PAD_WRAP (else LERF_EINVAL):
+ * constant: taps outside the frame get nothing; edge / reflect / symmetric / wrap: the pixel the pad names, F.pad's
+ * backward.  Hyper gradients land on the clamped tap pixel (replicate). */
 int lerf_resize_bwd_f32(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W,
                         const lerf_sr_geo_t* geo, int kind, double max_sigma, const float* grad_out, float* grad_feat,
                         float* grad_h0, float* grad_h1, float* grad_h2, void* stream);

@@ -507,6 +507,30 @@ def resize_planar(feat, hypers, geo: SrGeometry, kind="gauss", max_sigma=10.0, o
     return o
 
 
+def resize_bwd_planar(feat, hypers, geo: SrGeometry, kind, max_sigma, grad_out, grads):
+    """lerf_resize_bwd_f32: accumulate the gradients of resize_planar(feat, hypers, geo, kind, max_sigma, out="f32") for the
+    float32 upstream gradient `grad_out` [N, oH, oW] into `grads` = [grad_feat, grad_h0, grad_h1, grad_h2] (float32
+    [N, H, W] contiguous tensors, or None to skip a map; the fixed kinds have grad_feat alone).  feat / hypers: float32
+    [N, H, W].  The image gradient follows geo.pad_mode."""
+    feat = feat.contiguous().float()
+    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
+    hs = [h.contiguous().float() for h in hypers[:nh]]
+    g = grad_out.contiguous().float()
+    N, H, W = feat.shape
+    if tuple(g.shape) != (N, geo.out_hw[0], geo.out_hw[1]):
+        raise ValueError("grad_out must be [N, out_h, out_w] of the geometry")
+    grads = list(grads) + [None] * (4 - len(grads))
+    for t in grads:
+        if t is not None and (t.dtype != feat.dtype or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
+            raise ValueError("gradient buffers must be contiguous float32 [N, H, W]")
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+    hp = [ptr(h) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
+    _lib.check(_lib.lib().lerf_resize_bwd_f32(ptr(feat), hp[0], hp[1], hp[2], N, H, W, geo.ref(), KINDS[kind], float(max_sigma),
+                                              ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]),
+                                              _lib.current_stream()), "lerf_resize_bwd_f32")
+    return grads
+
+
 def resize_planar_u8(feat_u8, hq_u8, geo: SrGeometry, kind="gauss", max_sigma=10.0):
     """stage 3 on planar uint8 maps: feat [N,H,W] (any strides), hq = list of uint8 numerator maps [N,H,W] with identical
     strides (hyper = hq / 255) -> uint8 [oH,oW,N] = clip(rne(value), 0, 255): the production arithmetic of the fused path"""

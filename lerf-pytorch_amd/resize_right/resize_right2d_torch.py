@@ -4,8 +4,10 @@ reference's resize_right/resize_right2d_torch.py ([B,C,H,W] tensors on the GPU).
 SR geometry follows the torch classes' own float32 arithmetic (resize_right2d_torch.py:48-103, bit-equal tables:
 lerf_sr_axis_tables_f32), warp geometry the float64 one; SR returns float32, warps return float64 like
 the reference (its warp distances are double, resize_right2d_torch.py:286-296).
-The SR classes carry autograd (HIP backward, `_ResizeFn`), and so do the warp classes (`_WarpFn`, every kind and pad
-mode: the gradient autograd derives for the reference's torch warps, resize_right2d_torch.py:249-487).
+The SR classes carry autograd (`_ResizeFn`, HIP backward lerf_resize_bwd_f32: every kind -- gauss, linear and the
+fixed-kernel subclasses -- and every pad mode, the gradient autograd derives for resize_right2d_torch.py:105-247), and so
+do the warp classes (`_WarpFn`, every kind and pad mode: the gradient autograd derives for the reference's torch warps,
+resize_right2d_torch.py:249-487).  With no operand requiring grad, both run the plain forward and return no graph.
 """
 from __future__ import annotations
 
@@ -17,33 +19,27 @@ from .. import _lib, ops
 
 
 class _ResizeFn(torch.autograd.Function):
-    """lerf_resize forward, lerf_resize_bwd_f32 backward (the gradient autograd derives for
-    resize_right2d_torch.py:154-247) -- used when an input of resize() requires grad (train_model.py:431-441)."""
+    """lerf_resize forward, lerf_resize_bwd_f32 backward (the gradient autograd derives for resize_right2d_torch.py:105-247,
+    every kind and image pad mode) -- used when an input of resize() requires grad (train_model.py:431-441).  Gradients
+    come back in each leaf's dtype."""
 
     @staticmethod
     def forward(ctx, geo, kind, max_sigma, x, *hs):
-        x = x.detach().contiguous().float()
-        hs = [h.detach().contiguous().float() for h in hs]
-        out = ops.resize_planar(x, hs, geo, kind, max_sigma, out="f32")
-        ctx.save_for_backward(x, *hs)
-        ctx.meta = (geo, kind, float(max_sigma))
+        xf = x.detach().contiguous().float()
+        hf = [h.detach().contiguous().float() for h in hs]
+        out = ops.resize_planar(xf, hf, geo, kind, max_sigma, out="f32")
+        ctx.save_for_backward(xf, *hf)
+        ctx.meta = (geo, kind, float(max_sigma), [t.dtype for t in (x,) + hs])
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        import ctypes as C
         x, *hs = ctx.saved_tensors
-        geo, kind, max_sigma = ctx.meta
-        g = grad_out.contiguous().float()
-        N, H, W = x.shape
+        geo, kind, max_sigma, dtypes = ctx.meta
         need = ctx.needs_input_grad[3:]
         grads = [torch.zeros_like(x) if need[k] else None for k in range(1 + len(hs))]
-        hp = [C.c_void_p(h.data_ptr()) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
-        gp = [C.c_void_p(t.data_ptr() if t is not None else None) for t in grads] + [C.c_void_p(None)] * (3 - len(hs))
-        _lib.check(_lib.lib().lerf_resize_bwd_f32(C.c_void_p(x.data_ptr()), hp[0], hp[1], hp[2], N, H, W, geo.ref(),
-                                                  _lib.KINDS[kind], max_sigma, C.c_void_p(g.data_ptr()), gp[0], gp[1], gp[2],
-                                                  gp[3], _lib.current_stream()), "lerf_resize_bwd_f32")
-        return (None, None, None) + tuple(grads)
+        ops.resize_bwd_planar(x, hs, geo, kind, max_sigma, grad_out, grads)
+        return (None, None, None) + tuple(g.to(dt) if g is not None else None for g, dt in zip(grads, dtypes))
 
 
 class _WarpFn(torch.autograd.Function):
@@ -145,9 +141,7 @@ class Resize2dTorch(object):
         for h in hypers:
             _check_dev(h, "hyper-parameter map")
             hs.append(h.reshape(B * Cn, H, W))
-        if kind in ("gauss", "linear") and torch.is_grad_enabled() and any(t.requires_grad for t in [x] + hs):
-            if self._pad_code != 0:
-                raise NotImplementedError("autograd is implemented for pad_mode='constant' (what train_model.py uses)")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + hs):
             out = _ResizeFn.apply(self.geo, kind, max_sigma, x, *hs)
         else:
             out = ops.resize_planar(x, hs, self.geo, kind, max_sigma, out="f32")
