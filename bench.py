@@ -2,7 +2,7 @@
 """Benchmark of the LeRF LUT resampling hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4,5}] [--mode frames|strips|blocks]
-                    [--scale S] [--channels {1,3,4}] [--sustained SECONDS] [--dump-outputs DIR]
+                    [--scale S] [--channels {1,3,4}] [--full] [--sustained SECONDS] [--dump-outputs DIR]
 
 Default = BASELINE.json configs[1], the configuration the headline metric is quoted on: LeRF-G LUT x2 SR,
 1920x1080 -> 3840x2160 RGB.  One "step" = one pass of the hot path (stage-1 LUTs -> stage-2 LUTs -> spatially
@@ -23,7 +23,13 @@ one rank per GPU, RCCL); a failing rank makes the whole command fail.  Under tor
           matrices of SURVEY.md 8d), 5 = batch of 8 frames 2160x3840 -> 4320x7680 (strips by default when N > 1).
 
 Prints ONE JSON line (rank 0).  `roofline` prices the launch against HBM bandwidth using the ALGORITHMIC bytes of
-SURVEY.md 8(d); `cpu_baseline` is the C port of the oracle timed on this box's host cores (rank 0, N = 1 only).
+SURVEY.md 8(d).  A plain run does only what that line's headline needs: set-up, `--warmup` + `--steps` steps, the dump
+of --dump-outputs, the line.  --full adds every secondary leg after the timed steps: `sustained` (5 s unless --sustained
+says otherwise), the other input and one-frame latency, end-to-end host buffers, the Set5 PSNR delta vs the reference,
+the second scale / matrix of configs 3 / 4, `roofline_lds` (its own micro-benchmark runs), `cpu_baseline` (the C port
+of the oracle timed on the host's cores; rank 0, N = 1 only) with the parity of the timed output against it, and
+`other_configs`.  The --no-* switches skip single legs of a --full run.  --config 1 and --path callsite / classes-torch
+are lines of their own that --full does not change.
 
 --dump-outputs DIR writes the output of the last timed step (see dump_outputs); the synthetic inputs are seeded, so two builds
 run with the same arguments can be compared output for output.
@@ -516,24 +522,28 @@ def parse():
     ap.add_argument("--frames", type=int, default=8, help="frames per step (per GPU in frames mode; total batch in config 5)")
     ap.add_argument("--input", choices=["noise", "natural"], default=None)
     ap.add_argument("--support", type=int, choices=[2, 4], default=2, help="S (config 2 only: 4 = the class default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every secondary leg (CPU baseline and parity, other inputs, latency, end-to-end, "
+                         "PSNR delta, roofline_lds, sustained, other configurations); a plain run times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity against it")
     ap.add_argument("--no-other-input", action="store_true",
-                    help="skip the short secondary runs (profiling: keeps the kernel trace to one workload)")
+                    help="--full: skip the short secondary runs (profiling: keeps the kernel trace to one workload)")
     ap.add_argument("--path", choices=["fused", "callsite", "classes-torch"], default="fused",
                     help="fused (default): the engine path the headline is quoted on; callsite: one 1080p frame through the UNCHANGED call "
                          "sites of eltr._worker (24 FourSimplexInterpFaster calls + set_shape + resize through the mirrors, host numpy in, "
                          "uint8 numpy out); classes-torch: the torch resampler twins on device tensors (training / validation shapes)")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-buffer-in / host-buffer-out legs (config 2)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the host-buffer-in / host-buffer-out legs (config 2)")
     ap.add_argument("--warp-fused", action="store_true", help="config 4: the tile-fused warp (lerf_warp_fused_u8: no packed stage outputs in HBM) instead of the three-launch path")
     ap.add_argument("--overlap-halo", action="store_true", help="blocks mode: launch the block's interior under the halo exchange, its border after it (dist.OverlappedBlock)")
-    ap.add_argument("--no-psnr", action="store_true", help="skip the Set5 PSNR-delta-vs-reference block of the default line (config 2)")
+    ap.add_argument("--no-psnr", action="store_true", help="--full: skip the Set5 PSNR-delta-vs-reference block (config 2)")
     ap.add_argument("--unfused", action="store_true", help="config 2: time the 3-launch direct path instead")
     ap.add_argument("--scale", type=float, default=None, help="config 2: scale factor (default 2; > 4.9 takes the general kernels)")
     ap.add_argument("--channels", type=int, choices=[1, 3, 4], default=3, help="config 2: channels per pixel (1 / 4: general kernels)")
-    ap.add_argument("--sustained", type=float, default=5.0,
-                    help="seconds of back-to-back steps for the `sustained` leg (0 = skip; reported beside `value`, never replacing it)")
+    ap.add_argument("--sustained", type=float, default=None,
+                    help="seconds of back-to-back steps for the `sustained` leg (default 5 with --full, else 0 = skip; reported beside "
+                         "`value`, never replacing it)")
     ap.add_argument("--lib", default=None, help="diagnostic: load this build of liblerf_hip.so (A/B variants, tools/ab.sh); reported in the line")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short legs of the other BASELINE configurations (default run only)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the short legs of the other BASELINE configurations")
     ap.add_argument("--mode", choices=["frames", "strips", "blocks", "rows"], default=None,
                     help="frames: independent frames per GPU (default; config 5: the batch is divided over the GPUs); "
                          "blocks: every frame is split into a 2-D grid of blocks over the GPUs (8 GPUs: 2 x 4) with an RCCL halo "
@@ -547,6 +557,8 @@ def parse():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and (args.config == 1 or args.path != "fused"):
         ap.error("--dump-outputs covers the timed path of configs 2-5 (--path fused)")
+    if args.sustained is None:
+        args.sustained = 5.0 if args.full else 0.0
     return args
 
 
@@ -794,7 +806,7 @@ def main():
         sustained = (n_sus, ds)
 
     extra = {}
-    single = rank == 0 and world == 1 and not args.no_other_input
+    single = args.full and rank == 0 and world == 1 and not args.no_other_input
     if single and cfg in (2, 3, 5) and not args.unfused:
         # (a) the other input distribution, same shapes, short run
         other = "natural" if input_kind == "noise" else "noise"
@@ -888,7 +900,7 @@ def main():
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": tsrc,
                      "kernel_ms": round(launch_ms, 4), "algorithmic_bytes_per_launch": alg_bytes,
-                     "binding_resource": "lds_gather (the LUT gathers at the random-address rate of the LDS, see roofline_lds; then VALU issue. HBM is "
+                     "binding_resource": "lds_gather (the LUT gathers at the random-address rate of the LDS, see roofline_lds of --full; then VALU issue. HBM is "
                                          "the nominal roofline only: %.2f B per output pixel; DESIGN.md section 5)"
                                          % ((alg_bytes - LUT_BYTES[model]) / (B_local * out_px_local)),
                      "binding_resources_from_pmc": binding},
@@ -899,7 +911,7 @@ def main():
     # entries for LeRF-G, bytes for LeRF-L) from LUTs staged in LDS, the stage-2 ones also on the tile halo; a wave64 gather at
     # random addresses takes 3.53 ns of a CU's LDS (32 lanes on 32 banks per cycle: 7.6 cycles, tools/ubench/lds_gather.hip,
     # profiles/r03_lds_gather_and_clocks.txt), conflict-free it would take 0.9.  achieved = wave-gathers per second and CU.
-    if not args.unfused:
+    if args.full and not args.unfused:
         r3 = 0 if cfg == 4 else S // 2              # the EMIT kernels of the warp path look up the tile itself, no stage-3 ring
         halo = ((64 + 2 * r3) * (192 // C + 2 * r3) * C) / float(64 * 192)
         wave_gathers = B_local * H * W * C * 60.0 * (1.0 + halo) / 64.0
@@ -936,7 +948,7 @@ def main():
     if dumped:
         res["dump_outputs"] = dumped
 
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not strips:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not strips:
         if cfg == 4:
             cb, cpu_out, cpu_mask = cpu_baseline_warp(host[0], np.array(M_ISC), (oH, oW))
             res["cpu_baseline"] = cb
@@ -977,7 +989,7 @@ def main():
             diff = np.abs(out[ref_idx].cpu().numpy().astype(int) - cpu_out.astype(int))
             res["parity_vs_cpu_port"] = {"max_abs_diff_u8": int(diff.max()), "mismatches": int((diff != 0).sum())}
     default_run = cfg == 2 and S == 2 and C == 3 and scale == (2.0, 2.0) and not args.unfused and input_kind == "noise"
-    if rank == 0 and world == 1 and default_run and not args.no_other_configs and not args.no_other_input:
+    if args.full and rank == 0 and world == 1 and default_run and not args.no_other_configs and not args.no_other_input:
         del out, frames
         torch.cuda.empty_cache()
         res["other_configs"] = other_config_legs(torch, L, ops)

@@ -351,16 +351,38 @@ def test_bench_two_ranks_on_one_shared_gpu(torch, launcher, extra):
         assert abs(j["value"] - 2 * 7680 * 4320 / (j["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * j["value"]
 
 
+def test_bench_plain_line_is_the_headline_alone(torch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` sets up, times its steps and prints the line: the headline fields and
+    none of the secondary legs of --full; with LERF_TEST_PERF=1, at most 30 s of the whole run outside its steps."""
+    import json
+    import time
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "LERF_BENCH_SHARE_GPU"):
+        env.pop(k, None)
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 20 and j["warmup"] == 5 and j["value"] > 0 and j["ms_per_step"] > 0 and j["higher_is_better"] is True
+    assert j["unit"] == "Mpix/s" and j["metric"].startswith("Mpix/s LeRF-G x2 SR") and j["dtype"] == "i32+f32 (u8 io)"
+    moved = {"sustained", "mpix_s_other_input", "latency_one_frame_per_launch", "end_to_end", "psnr_delta_vs_ref_db", "roofline_lds",
+             "cpu_baseline", "cpu_baseline_single_thread", "cpu_baseline_half_budget", "parity_vs_cpu_port", "other_configs"}
+    assert not moved & set(j), sorted(moved & set(j))
+    assert not PERF or wall - (20 + 5) * j["ms_per_step"] * 1e-3 < 30.0, wall
+
+
 def test_bench_default_line_carries_every_baseline_config(torch):
-    """the default `python bench.py` line (what the driver records) holds a leg for configs 3, 4, 5 (one GPU)
-    and S = 4, each with its own in-run byte parity against the C port and a roofline block; and `--config 5 --frames 4` (the
-    N = 1 point of the driver's scaling run in frames mode) agrees with the config-5 leg."""
+    """the `python bench.py --full` line holds a leg for configs 3, 4, 5 (one GPU) and S = 4, each with its own
+    in-run byte parity against the C port and a roofline block; and `--config 5 --frames 4` (the N = 1 point of a scaling run
+    in frames mode) agrees with the config-5 leg."""
     import json
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "LERF_BENCH_SHARE_GPU"):
         env.pop(k, None)
     base = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "10", "--warmup", "3", "--sustained", "0"]
-    r = subprocess.run(base + ["--no-end-to-end", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    r = subprocess.run(base + ["--full", "--no-end-to-end", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 1 and j["config"]["ranks_reported_by_rccl"] == 1 and j["config"]["library"].endswith("liblerf_hip.so")
