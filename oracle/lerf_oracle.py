@@ -547,11 +547,17 @@ _SWF_PATTERN = {"s": ((0, 0), (0, 1), (1, 0), (1, 1)), "d": ((0, 0), (0, 2), (2,
                 "t": ((0, 0), (1, 1), (2, 2), (3, 3))}
 
 
-def swf2lut_interp(weight, outC, mode, img_in, bd, grad_out=None):
+def swf2lut_interp(weight, outC, mode, img_in, bd, grad_out=None, bounds=False):
     """weight float32 [17^4, outC] (LUT / 127), img_in float32 [B, C, h+bd, w+bd] integer-valued.
     Returns out [B, C*outC, h, w] float32; with grad_out also (grad_weight, grad_img) as torch autograd derives them
     for the reference code: round = straight-through, clamp gate on the rounded value, torch.remainder passes the
-    gradient to the LSB source pixels, ties ordered by the reference's case chain (later axis first)."""
+    gradient to the LSB source pixels, ties ordered by the reference's case chain (later axis first).
+
+    bounds=True (with grad_out) appends a dict of per-entry error-bound material, float64, shaped like the gradients:
+    'gw_count' / 'gw_abs': the number of terms g/q * w_n * 127 summed into each grad_weight entry (corners with w_n != 0,
+    behind the clamp gate) and the sum of their magnitudes; 'gimg_count' / 'gimg_abs': the same for the terms
+    g[oc] * (P_{n+1} - P_n) / q summed into each grad_img entry (one per pixel, sorted axis and output channel).  An entry
+    with count 0 receives no term and is exactly zero."""
     if mode not in _SWF_PATTERN:
         raise ValueError("Mode {} not implemented.".format(mode))
     weight = np.asarray(weight, np.float32)
@@ -581,18 +587,34 @@ def swf2lut_interp(weight, outC, mode, img_in, bd, grad_out=None):
         return out
     g = np.asarray(grad_out, np.float64).reshape(B, Cn, outC, h, w).transpose(0, 1, 3, 4, 2) / Q      # [B,C,h,w,outC]
     gw = np.zeros(weight.shape, np.float64)
+    if bounds:
+        gw_cnt, gw_abs = np.zeros(weight.shape, np.float64), np.zeros(weight.shape, np.float64)
     for wn, i in zip(wts, idx):
-        np.add.at(gw, i.reshape(-1), (g * wn[..., None]).reshape(-1, outC) * 127.0)
+        t = (g * wn[..., None]).reshape(-1, outC) * 127.0
+        np.add.at(gw, i.reshape(-1), t)
+        if bounds:
+            np.add.at(gw_cnt, i.reshape(-1), np.broadcast_to((wn != 0).reshape(-1, 1), t.shape).astype(np.float64))
+            np.add.at(gw_abs, i.reshape(-1), np.abs(t))
     gw *= gate
     gimg = np.zeros(img.shape, np.float64)
+    if bounds:
+        gw_cnt *= gate
+        gw_abs *= gate
+        gi_cnt, gi_abs = np.zeros(img.shape, np.float64), np.zeros(img.shape, np.float64)
     bb, cc, yy, xx = np.meshgrid(np.arange(B), np.arange(Cn), np.arange(h), np.arange(w), indexing="ij")
     ldy = np.array([p[0] for p in pl]).reshape(4, 1, 1, 1, 1)
     ldx = np.array([p[1] for p in pl]).reshape(4, 1, 1, 1, 1)
     for n in range(4):
-        gf = np.sum(g * (P[n + 1].astype(np.float64) - P[n].astype(np.float64)), axis=-1)
+        t = g * (P[n + 1].astype(np.float64) - P[n].astype(np.float64))
+        gf = np.sum(t, axis=-1)
         ay = np.take_along_axis(np.broadcast_to(ldy, f.shape), order, axis=0)[n]
         ax = np.take_along_axis(np.broadcast_to(ldx, f.shape), order, axis=0)[n]
         np.add.at(gimg, (bb, cc, yy + ay, xx + ax), gf)
+        if bounds:
+            np.add.at(gi_cnt, (bb, cc, yy + ay, xx + ax), float(outC))
+            np.add.at(gi_abs, (bb, cc, yy + ay, xx + ax), np.sum(np.abs(t), axis=-1))
+    if bounds:
+        return out, gw, gimg, {"gw_count": gw_cnt, "gw_abs": gw_abs, "gimg_count": gi_cnt, "gimg_abs": gi_abs}
     return out, gw, gimg
 
 
@@ -624,22 +646,37 @@ def transfer_inputs(interval: int = 4) -> np.ndarray:
     return (base[idx].astype(np.float32) / np.float32(255.0)).astype(np.float32)
 
 
-def srnet_forward(weights: dict, key: str, x: np.ndarray, dtype=np.float64) -> np.ndarray:
+def srnet_forward(weights: dict, key: str, x: np.ndarray, dtype=np.float64, absolute=False):
     """One SRNet of the reference's SRNetsSWF2 (resample/model.py:81-99) on [N,4] pixel tuples (a,b,c,d):
     SRUnit (network.py:40-71): conv1 over the 4 sampled pixels (2x2 kernel for mode s, 1x4 for c/t after the pixel
     pick of SRNet.forward :139-152 -- either way the flattened kernel meets (a,b,c,d) in order) + ReLU, four dense
     1x1 layers whose outputs are concatenated to their inputs (:26-37), conv6 + tanh.  Returns [N, outC] in (-1, 1).
-    `weights`: the module's state_dict as arrays (assets/models/<model>/srnets_weights.npz)."""
+    `weights`: the module's state_dict as arrays (assets/models/<model>/srnets_weights.npz).
+
+    absolute=True returns (y, M6): M6 [N, outC] is the pre-tanh sum of the absolute network -- |W|, |b|, |x|, ReLU the
+    identity on magnitudes -- which bounds every partial sum of the forward pass that feeds conv6 (the magnitude a
+    first-order forward-error bound scales with)."""
     p = key + ".model."
     h = x.astype(dtype)
+    a = np.abs(h)
     w1 = weights[p + "conv1.conv.weight"].reshape(-1, 4).astype(dtype)
-    h = np.maximum(h @ w1.T + weights[p + "conv1.conv.bias"].astype(dtype), 0)
+    b1 = weights[p + "conv1.conv.bias"].astype(dtype)
+    h = np.maximum(h @ w1.T + b1, 0)
+    if absolute:
+        a = a @ np.abs(w1).T + np.abs(b1)
     for k in (2, 3, 4, 5):
         w = weights[p + "conv%d.conv1.conv.weight" % k].reshape(64, -1).astype(dtype)
-        f = np.maximum(h @ w.T + weights[p + "conv%d.conv1.conv.bias" % k].astype(dtype), 0)
+        b = weights[p + "conv%d.conv1.conv.bias" % k].astype(dtype)
+        f = np.maximum(h @ w.T + b, 0)
         h = np.concatenate([h, f], axis=1)
+        if absolute:
+            a = np.concatenate([a, a @ np.abs(w).T + np.abs(b)], axis=1)
     w6 = weights[p + "conv6.conv.weight"].reshape(-1, h.shape[1]).astype(dtype)
-    return np.tanh(h @ w6.T + weights[p + "conv6.conv.bias"].astype(dtype))
+    b6 = weights[p + "conv6.conv.bias"].astype(dtype)
+    y = np.tanh(h @ w6.T + b6)
+    if absolute:
+        return y, a @ np.abs(w6).T + np.abs(b6)
+    return y
 
 
 def transfer_lut(weights: dict, key: str, interval: int = 4, dtype=np.float64, return_float=False):
