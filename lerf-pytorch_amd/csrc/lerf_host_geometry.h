@@ -1,10 +1,10 @@
 // Host-side geometry of the LeRF path, free of any HIP dependency: what lerf_api.hip exports as lerf_sr_axis_tables(_f32),
 // lerf_out_size, lerf_invert3x3, lerf_warp_pads, lerf_mode_offsets, and the helpers the kernels share with it (pattern
-// offsets, image pad rule, homography projection, support boundary, and the one definition of the homographic warp's tap
-// geometry: warp_pixel + axis_tap, which every warp kernel, its tie guard and the tile-fused warp's ownership key derive
-// their taps from).  One source for both builds: liblerf_hip.so (hipcc) and the AddressSanitizer / UBSan host build of the
-// same functions (csrc/lerf_host_sanitize.cpp, `make asan`), which the CPU suite runs against the product library
-// (tests/test_sanitizers_cpu.py).
+// offsets, image pad rule, homography projection, support boundary, the one source-index rule of every resampler's taps,
+// source_tap, and the homographic warp's tap geometry built on it: warp_pixel + axis_tap, which every warp kernel, its tie
+// guard and the tile-fused warp's ownership key derive their taps from).  One source for both builds: liblerf_hip.so (hipcc)
+// and the AddressSanitizer / UBSan host build of the same functions (csrc/lerf_host_sanitize.cpp, `make asan`), which the
+// CPU suite runs against the product library (tests/test_sanitizers_cpu.py).
 #pragma once
 
 #include <math.h>
@@ -116,24 +116,39 @@ LERF_HD inline WarpPixel warp_pixel(const double minv[9], int S, int pad_r_lo, i
     return p;
 }
 
-// Tap k of the support along one axis (rows: g = gr, l = lr, n = H, the row pads; columns likewise).  The taps are
-// separable: a row tap depends on the row offset alone, a column tap on the column offset alone.
-struct AxisTap {
-    double d;           // float64 distance of the projected point from the tap
+// Unpadded source coordinate s of a tap along one axis of n pixels (may lie outside [0, n)): where the replicate-padded
+// hyper-parameter maps are read (:172-174) and where the image is read under its pad rule (:208, :560).  The one source-index
+// rule of every resampler: the SR taps (SrTap, lerf_taps.h) and, through axis_tap, the warp's.
+struct SourceTap {
     int cl;             // clamped source index: where the replicate-padded hyper-parameter maps are read
     bool inside;        // the tap lies inside the frame (the packed warps take the image as 0 outside it)
     int s;              // image index under the image's pad rule
     bool z;             // the image value is the constant pad (0)
 };
 
+LERF_HD inline SourceTap source_tap(int s, int n, int pad_mode) {
+    SourceTap t;
+    t.cl = clampi(s, 0, n - 1);
+    t.inside = s == t.cl;
+    t.s = pad_index(s, n, pad_mode, &t.z);
+    return t;
+}
+
+// Tap k of the warp's support along one axis (rows: g = gr, l = lr, n = H, the row pads; columns likewise).  The taps are
+// separable: a row tap depends on the row offset alone, a column tap on the column offset alone.
+struct AxisTap : SourceTap {
+    double d;           // float64 distance of the projected point from the tap
+};
+
 LERF_HD inline AxisTap axis_tap(double g, int l, int k, int n, int pad_lo, int pad_mode) {
     AxisTap t;
     const int p = clampi(l + k, 0, n - 1);      // field of view clipped to [0, in-1] while indexing the PADDED arrays (:396-398)
     t.d = g - (double)p;
-    const int s = p - pad_lo;                   // unpadded source coordinate
-    t.cl = clampi(s, 0, n - 1);
-    t.inside = s == t.cl;
-    t.s = pad_index(s, n, pad_mode, &t.z);      // image pad rule (:560)
+    const SourceTap s = source_tap(p - pad_lo, n, pad_mode);
+    t.cl = s.cl;
+    t.inside = s.inside;
+    t.s = s.s;
+    t.z = s.z;
     return t;
 }
 

@@ -14,7 +14,7 @@
 #include "lerf_kernels.h"
 #include "lerf_stage3.h"
 #include "lerf_warp_px.h"
-#include "lerf_warp_taps.h"
+#include "lerf_taps.h"
 
 namespace lerf {
 
@@ -86,6 +86,12 @@ template <> struct Loader<float> {
     static __device__ __forceinline__ float hyper(const float* p) { return *p; }
     static __device__ __forceinline__ float pixel(const float* p) { return *p; }
 };
+
+// the reference's float32 Gaussian parameters of the tap at offset o of the hyper-parameter maps
+template <typename TH>
+__device__ __forceinline__ s3::GaussParams gauss_params(const TH* h0, const TH* h1, const TH* h2, int64_t o, float max_sigma) {
+    return s3::gauss_params_of(Loader<TH>::hyper(h0 + o), Loader<TH>::hyper(h1 + o), Loader<TH>::hyper(h2 + o), max_sigma);
+}
 
 template <typename T> struct Storer;
 template <> struct Storer<uint8_t> {
@@ -195,18 +201,11 @@ resize_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
         for (int a = 0; a < MAXS; ++a) {
 #pragma unroll
             for (int b = 0; b < MAXS; ++b) {
-                int rr = lr + b, cc = lc + a;
-                int rcl = clampi(rr, 0, H - 1), ccl = clampi(cc, 0, W - 1);
-                bool zr, zc;                                                                           // image pad rule (:208)
-                const int rs = pad_index(rr, H, pad_mode, &zr), cs = pad_index(cc, W, pad_mode, &zc);
-                v[a * MAXS + b] = (zr || zc) ? 0.0f : Loader<TI>::pixel(feat + rs * fy + cs * fx + c * fc);
-                if (sizeof(TH) == 1 && sizeof(TO) == 1) {
-                    const int64_t hh = rcl * hy + ccl * hx + c * hc;
-                    dd[a * MAXS + b] = (uint32_t)h0[hh] | ((KIND == LERF_KIND_GAUSS ? (uint32_t)h1[hh] : 0u) << 8) |
-                                       ((KIND == LERF_KIND_GAUSS ? (uint32_t)h2[hh] : 0u) << 16) |
-                                       ((uint32_t)v[a * MAXS + b] << 24);
-                }
-                int64_t ho = rcl * hy + ccl * hx + c * hc;                                                    // edge pad (:172-174)
+                const SrTap t = sr_tap(lr, lc, a, b, H, W, pad_mode);
+                v[a * MAXS + b] = t.z ? 0.0f : Loader<TI>::pixel(feat + t.rs * fy + t.cs * fx + c * fc);
+                const int64_t ho = t.rcl * hy + t.ccl * hx + c * hc;
+                if (sizeof(TH) == 1 && sizeof(TO) == 1)
+                    dd[a * MAXS + b] = s3::tie_word<KIND == LERF_KIND_GAUSS>(h0, h1, h2, ho, (uint32_t)v[a * MAXS + b]);
                 float dx = (float)dis_r[i * S + b], dy = (float)dis_c[j * S + a];
                 // uint8 in / uint8 out: the production arithmetic of the fused kernel (bit-identical results);
                 // float outputs keep the exact float32 parameter formation of the reference
@@ -249,21 +248,15 @@ resize_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
         for (int a = 0; a < MAXS; ++a) {
 #pragma unroll
             for (int b = 0; b < MAXS; ++b) {
-                int rr = lr + b, cc = lc + a;
-                int rcl = clampi(rr, 0, H - 1), ccl = clampi(cc, 0, W - 1);
-                bool zr, zc;                                                                           // image pad rule (:208)
-                const int rs = pad_index(rr, H, pad_mode, &zr), cs = pad_index(cc, W, pad_mode, &zc);
-                A val = (zr || zc) ? (A)0 : (A)Loader<TI>::pixel(feat + rs * fy + cs * fx + c * fc);
-                int64_t ho = rcl * hy + ccl * hx + c * hc;                                             // edge pad (:172-174)
+                const SrTap t = sr_tap(lr, lc, a, b, H, W, pad_mode);
+                A val = t.z ? (A)0 : (A)Loader<TI>::pixel(feat + t.rs * fy + t.cs * fx + c * fc);
+                const int64_t ho = t.rcl * hy + t.ccl * hx + c * hc;
                 A dx = dis_r[i * S + b], dy = dis_c[j * S + a];
                 if (KIND == LERF_KIND_GAUSS) {
-                    float p0 = Loader<TH>::hyper(h0 + ho), p1 = Loader<TH>::hyper(h1 + ho), p2 = Loader<TH>::hyper(h2 + ho);
-                    // float32 parameter formation (:168-170)
-                    float rho = p0 * 2.0f - 1.0f, sx = p1 * (float)max_sigma, sy = p2 * (float)max_sigma;
-                    acc.add_gauss((A)rho, (A)sx, (A)sy, dx, dy, val);
+                    const s3::GaussParams p = gauss_params(h0, h1, h2, ho, (float)max_sigma);
+                    acc.add_gauss((A)p.rho, (A)p.sx, (A)p.sy, dx, dy, val);
                 } else {
-                    float p0 = Loader<TH>::hyper(h0 + ho);
-                    float alpha = (float)max_sigma * (p0 * 2.0f - 1.0f);
+                    float alpha = s3::lin_alpha_ref(Loader<TH>::hyper(h0 + ho), (float)max_sigma);
                     A w = lin_factor<A>((A)alpha, dx, dist_class(dx)) * lin_factor<A>((A)alpha, dy, dist_class(dy));
                     acc.add_weight(w, val);
                 }
@@ -277,16 +270,13 @@ resize_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
     for (int pass = 0; pass < 2; ++pass) {
         for (int a = 0; a < S; ++a)
             for (int b = 0; b < S; ++b) {
-                int rr = lr + b, cc = lc + a;
-                int rcl = clampi(rr, 0, H - 1), ccl = clampi(cc, 0, W - 1);
-                bool zr, zc;
-                const int rs = pad_index(rr, H, pad_mode, &zr), cs = pad_index(cc, W, pad_mode, &zc);
-                int64_t ho = rcl * hy + ccl * hx + c * hc;
+                const SrTap t = sr_tap(lr, lc, a, b, H, W, pad_mode);
+                const int64_t ho = t.rcl * hy + t.ccl * hx + c * hc;
                 A dx = dis_r[i * S + b], dy = dis_c[j * S + a];
                 A w;
                 if (KIND == LERF_KIND_GAUSS) {
-                    float p0 = Loader<TH>::hyper(h0 + ho), p1 = Loader<TH>::hyper(h1 + ho), p2 = Loader<TH>::hyper(h2 + ho);
-                    A rho = (A)(p0 * 2.0f - 1.0f), sx = (A)(p1 * (float)max_sigma), sy = (A)(p2 * (float)max_sigma);
+                    const s3::GaussParams p = gauss_params(h0, h1, h2, ho, (float)max_sigma);
+                    A rho = (A)p.rho, sx = (A)p.sx, sy = (A)p.sy;
                     A tx = sx * dx, ty = sy * dy;
                     A e = tx * tx - (A)2 * rho * (tx * ty) + ty * ty;
                     if (pass == 0) {
@@ -296,11 +286,10 @@ resize_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
                     w = sizeof(A) == 4 ? (A)__expf((float)((A)-0.5 * (e - emin))) : (A)exp((double)((A)-0.5 * (e - emin)));
                 } else {
                     if (pass == 0) continue;
-                    float p0 = Loader<TH>::hyper(h0 + ho);
-                    A alpha = (A)((float)max_sigma * (p0 * 2.0f - 1.0f));
+                    A alpha = (A)s3::lin_alpha_ref(Loader<TH>::hyper(h0 + ho), (float)max_sigma);
                     w = lin_factor<A>(alpha, dx, dist_class(dx)) * lin_factor<A>(alpha, dy, dist_class(dy));
                 }
-                A val = (zr || zc) ? (A)0 : (A)Loader<TI>::pixel(feat + rs * fy + cs * fx + c * fc);
+                A val = t.z ? (A)0 : (A)Loader<TI>::pixel(feat + t.rs * fy + t.cs * fx + c * fc);
                 num += w * val;
                 den += w;
             }
@@ -354,13 +343,9 @@ resize_cells_u8_kernel(const uint8_t* __restrict__ feat, int fy, int fx, int fc,
     for (int a = 0; a < S; ++a) {
 #pragma unroll
         for (int b = 0; b < S; ++b) {
-            const int rr = lr + b, cc = lc + a;
-            const int rcl = clampi(rr, 0, H - 1), ccl = clampi(cc, 0, W - 1);                          // hyper: edge pad (:172-174)
-            bool zr, zc;                                                                               // image pad rule (:208)
-            const int rs = pad_index(rr, H, pad_mode, &zr), cs = pad_index(cc, W, pad_mode, &zc);
-            const uint32_t val = (zr || zc) ? 0u : (uint32_t)feat[rs * fy + cs * fx + c * fc];
-            const int hh = rcl * hy + ccl * hx + c * hc;
-            dd[a * S + b] = (uint32_t)h0[hh] | ((GAUSS ? (uint32_t)h1[hh] : 0u) << 8) | ((GAUSS ? (uint32_t)h2[hh] : 0u) << 16) | (val << 24);
+            const SrTap t = sr_tap(lr, lc, a, b, H, W, pad_mode);
+            const uint32_t val = t.z ? 0u : (uint32_t)feat[t.rs * fy + t.cs * fx + c * fc];
+            dd[a * S + b] = s3::tie_word<GAUSS>(h0, h1, h2, t.rcl * hy + t.ccl * hx + c * hc, val);
             v[a * S + b] = (float)val;
         }
     }
@@ -541,14 +526,12 @@ resize_fixed_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t
     }
     A num = 0;
     for (int a = 0; a < S; ++a) {
-        bool zc;
-        const int cc = pad_index(lc + a, W, pad_mode, &zc);
-        if (zc) continue;
+        const SourceTap tc = source_tap(lc + a, W, pad_mode);
+        if (tc.z) continue;
         A row = 0;
         for (int b = 0; b < S; ++b) {
-            bool zr;
-            const int rr = pad_index(lr + b, H, pad_mode, &zr);
-            if (!zr) row += kr[b] * (A)Loader<TI>::pixel(feat + rr * fy + cc * fx + c * fc);
+            const SourceTap tr = source_tap(lr + b, H, pad_mode);
+            if (!tr.z) row += kr[b] * (A)Loader<TI>::pixel(feat + tr.s * fy + tc.s * fx + c * fc);
         }
         num += kc[a] * row;
     }
@@ -606,8 +589,8 @@ warp_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
                 int64_t ho = tp.rcl * hy + tp.ccl * hx + c * hc;
                 A w;
                 if (KIND == LERF_KIND_GAUSS) {
-                    float p0 = Loader<TH>::hyper(h0 + ho), p1 = Loader<TH>::hyper(h1 + ho), p2 = Loader<TH>::hyper(h2 + ho);
-                    A rho = (A)(p0 * 2.0f - 1.0f), sx = (A)(p1 * (float)max_sigma), sy = (A)(p2 * (float)max_sigma);
+                    const s3::GaussParams p = gauss_params(h0, h1, h2, ho, (float)max_sigma);
+                    A rho = (A)p.rho, sx = (A)p.sx, sy = (A)p.sy;
                     A tx = sx * dx, ty = sy * dy;
                     A e = tx * tx - (A)2 * rho * (tx * ty) + ty * ty;
                     if (pass == 0) {
@@ -616,8 +599,7 @@ warp_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
                     }
                     w = sizeof(A) == 4 ? (A)__expf((float)((A)-0.5 * (e - emin))) : (A)exp((double)((A)-0.5 * (e - emin)));
                 } else if (KIND == LERF_KIND_LINEAR) {
-                    float p0 = Loader<TH>::hyper(h0 + ho);
-                    A alpha = (A)((float)max_sigma * (p0 * 2.0f - 1.0f));
+                    A alpha = (A)s3::lin_alpha_ref(Loader<TH>::hyper(h0 + ho), (float)max_sigma);
                     // class decisions on the float64 distances
                     w = lin_factor<A>(alpha, dx, dist_class(dxd)) * lin_factor<A>(alpha, dy, dist_class(dyd));
                 } else if (KIND == LERF_KIND_NEAREST) {

@@ -15,7 +15,8 @@
 #include <stdint.h>
 
 #include "lerf_common.h"
-#include "lerf_warp_taps.h"
+#include "lerf_stage3.h"
+#include "lerf_taps.h"
 
 namespace lerf {
 namespace resize_bwd {
@@ -29,30 +30,30 @@ struct Tap {
 
 template <int KIND, bool PADDED>
 __device__ __forceinline__ Tap load_tap(const float* __restrict__ feat, const float* __restrict__ h0, const float* __restrict__ h1,
-                                        const float* __restrict__ h2, int64_t plane, int H, int W, int rr, int cc, float dx, float dy,
-                                        float max_sigma, int pad_mode) {
+                                        const float* __restrict__ h2, int64_t plane, int H, int W, int lr, int lc, int a, int b, float dx,
+                                        float dy, float max_sigma, int pad_mode) {
     Tap t;
-    const int rcl = clampi(rr, 0, H - 1), ccl = clampi(cc, 0, W - 1);
-    t.pos = plane + (int64_t)rcl * W + ccl;
+    const SrTap s = sr_tap(lr, lc, a, b, H, W, pad_mode);
+    t.pos = plane + (int64_t)s.rcl * W + s.ccl;
     if (PADDED) {
-        bool zr, zc;
-        t.rs = pad_index(rr, H, pad_mode, &zr);
-        t.cs = pad_index(cc, W, pad_mode, &zc);
-        t.inside = !(zr || zc);
+        t.rs = s.rs;
+        t.cs = s.cs;
+        t.inside = !s.z;
         t.v = t.inside ? feat[plane + (int64_t)t.rs * W + t.cs] : 0.0f;
     } else {
-        t.inside = (rr == rcl) && (cc == ccl);
+        t.inside = s.inside;
         t.v = t.inside ? feat[t.pos] : 0.0f;
     }
     t.dx = dx;
     t.dy = dy;
     if (KIND == LERF_KIND_GAUSS) {
-        t.rho = h0[t.pos] * 2.0f - 1.0f;
-        t.tx = h1[t.pos] * max_sigma * dx;
-        t.ty = h2[t.pos] * max_sigma * dy;
+        const s3::GaussParams p = s3::gauss_params_of(h0[t.pos], h1[t.pos], h2[t.pos], max_sigma);
+        t.rho = p.rho;
+        t.tx = p.sx * dx;
+        t.ty = p.sy * dy;
         t.w = t.tx * t.tx - 2.0f * t.rho * (t.tx * t.ty) + t.ty * t.ty;      // the exponent e; turned into a weight by the caller
     } else {
-        t.alpha = max_sigma * (h0[t.pos] * 2.0f - 1.0f);
+        t.alpha = s3::lin_alpha_ref(h0[t.pos], max_sigma);
         t.lx = (t.alpha * dx + 1.0f) * ((-1.0f <= dx && dx < 0.0f) ? 1.0f : 0.0f) + (1.0f - t.alpha * dx) * ((0.0f <= dx && dx <= 1.0f) ? 1.0f : 0.0f);
         t.ly = (t.alpha * dy + 1.0f) * ((-1.0f <= dy && dy < 0.0f) ? 1.0f : 0.0f) + (1.0f - t.alpha * dy) * ((0.0f <= dy && dy <= 1.0f) ? 1.0f : 0.0f);
         t.cx = fmaxf(t.lx, 0.0f);
@@ -100,7 +101,7 @@ resize_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ h0, 
         if (KIND == LERF_KIND_GAUSS) {
             for (int a = 0; a < S; ++a)
                 for (int b = 0; b < S; ++b) {
-                    const Tap t = load_tap<KIND, PADDED>(feat, h0, h1, h2, plane, H, W, lr + b, lc + a, dis_r[i * S + b], dis_c[j * S + a],
+                    const Tap t = load_tap<KIND, PADDED>(feat, h0, h1, h2, plane, H, W, lr, lc, a, b, dis_r[i * S + b], dis_c[j * S + a],
                                                          max_sigma, pad_mode);
                     emin = (a == 0 && b == 0) ? t.w : fminf(emin, t.w);
                 }
@@ -108,7 +109,7 @@ resize_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ h0, 
         float Wsum = 0.0f, num = 0.0f;
         for (int a = 0; a < S; ++a)
             for (int b = 0; b < S; ++b) {
-                Tap t = load_tap<KIND, PADDED>(feat, h0, h1, h2, plane, H, W, lr + b, lc + a, dis_r[i * S + b], dis_c[j * S + a],
+                Tap t = load_tap<KIND, PADDED>(feat, h0, h1, h2, plane, H, W, lr, lc, a, b, dis_r[i * S + b], dis_c[j * S + a],
                                                max_sigma, pad_mode);
                 const float w = KIND == LERF_KIND_GAUSS ? __expf(-0.5f * (t.w - emin)) : t.w;
                 Wsum += w;
@@ -118,7 +119,7 @@ resize_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ h0, 
         const float g = gout[((int64_t)n * oH + i) * oW + j];
         for (int a = 0; a < S; ++a)
             for (int b = 0; b < S; ++b) {
-                Tap t = load_tap<KIND, PADDED>(feat, h0, h1, h2, plane, H, W, lr + b, lc + a, dis_r[i * S + b], dis_c[j * S + a],
+                Tap t = load_tap<KIND, PADDED>(feat, h0, h1, h2, plane, H, W, lr, lc, a, b, dis_r[i * S + b], dis_c[j * S + a],
                                                max_sigma, pad_mode);
                 const float w = KIND == LERF_KIND_GAUSS ? __expf(-0.5f * (t.w - emin)) : t.w;
                 const int64_t rel = t.pos - plane;
@@ -215,18 +216,16 @@ resize_bwd_fixed_kernel(int H, int W, int S, int oH, int oW, const int* __restri
         const float g = gout[((int64_t)n * oH + i) * oW + j];
         const float gn = S == 1 ? g : g / (sr[ii] * sc[jj]);
         for (int a = 0; a < S; ++a) {
-            bool zc;
-            const int cc = pad_index(lc + a, W, pad_mode, &zc);
-            if (zc) continue;
+            const SourceTap tc = source_tap(lc + a, W, pad_mode);
+            if (tc.z) continue;
             const float ga = gn * kc[jj * S + a];
             for (int b = 0; b < S; ++b) {
-                bool zr;
-                const int rr = pad_index(lr + b, H, pad_mode, &zr);
-                if (zr) continue;
+                const SourceTap tr = source_tap(lr + b, H, pad_mode);
+                if (tr.z) continue;
                 const float v = ga * kr[ii * S + b];
-                const int wr = rr - wr0, wc = cc - wc0;
+                const int wr = tr.s - wr0, wc = tc.s - wc0;
                 if (lds && wr >= 0 && wr < wh && wc >= 0 && wc < ww) atomicAdd(&win[wr * ww + wc], v);
-                else if (v != 0.0f) atomicAdd(gfeat + plane + (int64_t)rr * W + cc, v);
+                else if (v != 0.0f) atomicAdd(gfeat + plane + (int64_t)tr.s * W + tc.s, v);
             }
         }
     }

@@ -88,6 +88,14 @@ __device__ __forceinline__ float gauss_weight(float e, float emin) {
     return __builtin_amdgcn_exp2f((emin - e) * 0.72134752044448170368f);   // 0.5 * log2(e)
 }
 
+// The reference's float32 parameters from hyper-parameter values h (:168-170, :249-250) as the direct kernels' float paths
+// form them: with the default contraction, which fuses 2 h0 - 1 into one FMA (the same value: 2 h0 is exact).
+struct GaussParams { float rho, sx, sy; };
+__device__ __forceinline__ GaussParams gauss_params_of(float h0, float h1, float h2, float max_sigma) {
+    return {h0 * 2.0f - 1.0f, h1 * max_sigma, h2 * max_sigma};
+}
+__device__ __forceinline__ float lin_alpha_ref(float h0, float max_sigma) { return max_sigma * (h0 * 2.0f - 1.0f); }
+
 __device__ __forceinline__ float lin_alpha_of(float h0, float max_sigma) {
 #pragma clang fp contract(off)
     return max_sigma * (h0 * 2.0f - 1.0f);                                 // :249-250
@@ -298,7 +306,14 @@ __device__ __forceinline__ uint32_t to_u8_tie(float x, bool* tie) {
     return (uint32_t)(int)fminf(fmaxf(r, 0.0f), 255.0f);
 }
 
-// d[a*S+b] = (k0 | k1<<8 | k2<<16 | val<<24) of tap (column offset a, row offset b); dx[b], dy[a] float64
+// the word eval64 / resolve_u8 read per tap: k0 | k1<<8 | k2<<16 | val<<24, the hyper-parameter numerators at offset o (the
+// linear kind has k0 alone) and the image value
+template <bool GAUSS, typename T, typename I>
+__device__ __forceinline__ uint32_t tie_word(const T* h0, const T* h1, const T* h2, I o, uint32_t val) {
+    return (uint32_t)h0[o] | ((GAUSS ? (uint32_t)h1[o] : 0u) << 8) | ((GAUSS ? (uint32_t)h2[o] : 0u) << 16) | (val << 24);
+}
+
+// d[a*S+b] = tie_word of tap (column offset a, row offset b); dx[b], dy[a] float64
 template <bool GAUSS, int S>
 __device__ __forceinline__ double eval64(const uint32_t (&d)[S * S], const double (&dx)[S], const double (&dy)[S],
                                          float max_sigma) {

@@ -1,8 +1,8 @@
-// The homographic warp's taps on planar operands (Warp2dTorch.get_distance / warp, resize_right2d_torch.py:249-487, float64
-// like the reference's distances) in the form the per-tap kernels take them -- the forward warp_kernel and the packed
-// per-channel warp_packed_kernel (lerf_kernels.hip), and the backward (lerf_warp_bwd.hip) -- plus the fixed interpolation
-// kernels.  The geometry itself (projection, support boundary, pad shift, clamps, distances, pad rule) is warp_pixel /
-// axis_tap of lerf_host_geometry.h, which the S = 2 packed paths (lerf_warp_px.h) share.
+// The taps of both resamplers in the form the per-tap kernels take them: SrTap for the separable SR geometry (resize_kernel,
+// resize_cells_u8_kernel, resize_fixed_kernel and the backward, lerf_resize_bwd.hip), WarpTap for the homographic warp on planar
+// operands (Warp2dTorch.get_distance / warp, resize_right2d_torch.py:249-487; warp_kernel, warp_packed_kernel and the backward,
+// lerf_warp_bwd.hip), plus the fixed interpolation kernels.  The geometry itself (source_tap: clamps and pad rule; warp_pixel /
+// axis_tap: projection, support boundary, distances) is lerf_host_geometry.h's, which lerf_warp_px.h shares.
 #pragma once
 
 #include "lerf_kernels.h"
@@ -29,6 +29,20 @@ __device__ __forceinline__ double fixed_kernel_1d(int kind, double x) {
     return ((-1.0 <= x && x < 0.0) ? 1.0 : 0.0) + ((0.0 <= x && x <= 1.0) ? 1.0 : 0.0);   // box :67-70
 }
 
+// tap (a, b) of SR output pixel (i, j) -- column offset a, row offset b -- from its support's left boundaries lr = left_r[i],
+// lc = left_c[j]
+struct SrTap {
+    int rcl, ccl;       // clamped source pixel: where the replicate-padded hyper-parameter maps are read (:172-174)
+    int rs, cs;         // image pixel under the image's pad rule (:208)
+    bool z;             // the image value is the constant pad (0)
+    bool inside;        // the tap lies inside the frame
+};
+
+__device__ __forceinline__ SrTap sr_tap(int lr, int lc, int a, int b, int H, int W, int pad_mode) {
+    const SourceTap r = source_tap(lr + b, H, pad_mode), c = source_tap(lc + a, W, pad_mode);
+    return {r.cl, c.cl, r.s, c.s, r.z || c.z, r.inside && c.inside};
+}
+
 // output pixel (i, j) of the launch's rectangle
 __device__ __forceinline__ WarpPixel warp_pixel(const WarpGeo& g, int i, int j, int H, int W) {
     return warp_pixel(g.minv, g.S, g.pad_r_lo, g.pad_c_lo, i + g.oy0, j + g.ox0, H, W);
@@ -48,19 +62,7 @@ struct WarpTap {
 template <typename A>
 __device__ __forceinline__ WarpTap<A> warp_tap(const WarpGeo& g, const WarpPixel& p, int a, int b, int H, int W) {
     const AxisTap r = axis_tap(p.gr, p.lr, b, H, g.pad_r_lo, g.pad_mode), c = axis_tap(p.gc, p.lc, a, W, g.pad_c_lo, g.pad_mode);
-    WarpTap<A> t;
-    t.dxd = r.d;
-    t.dyd = c.d;
-    t.dx = (A)r.d;
-    t.dy = (A)c.d;
-    t.rcl = r.cl;
-    t.ccl = c.cl;
-    t.rs = r.s;
-    t.cs = c.s;
-    t.zr = r.z;
-    t.zc = c.z;
-    t.inside = r.inside && c.inside;
-    return t;
+    return {r.d, c.d, (A)r.d, (A)c.d, r.cl, c.cl, r.s, c.s, r.z, c.z, r.inside && c.inside};
 }
 
 }  // namespace lerf

@@ -17,7 +17,7 @@
 #include <string.h>
 
 #include "lerf_warp_px.h"
-#include "lerf_warp_taps.h"
+#include "lerf_taps.h"
 
 namespace lerf {
 namespace warp_bwd {

@@ -375,7 +375,7 @@ def warp_geometry(matrix, in_hw, out_hw, S):
 
 
 def fixed_kernel(kind, x):
-    """cubic / lanczos2 / lanczos3 / bilinear 1-D kernels (resize_right/interp_methods.py:35-64)."""
+    """cubic / lanczos2 / lanczos3 / bilinear / box (nearest) 1-D kernels (resize_right/interp_methods.py:35-70)."""
     x = np.asarray(x, dtype=np.float64)
     pi = math.pi
     if kind == "cubic":
@@ -388,6 +388,8 @@ def fixed_kernel(kind, x):
         return ((np.sin(pi * x) * np.sin(pi * x / 3) + EPS32) / ((pi ** 2 * x ** 2 / 3) + EPS32)) * (np.abs(x) < 3)
     if kind == "bilinear":
         return (x + 1) * ((-1 <= x) & (x < 0)) + (1 - x) * ((0 <= x) & (x <= 1))
+    if kind == "nearest":     # box (interp_methods.py:67-70)
+        return ((-1 <= x) & (x < 0)).astype(np.float64) + ((0 <= x) & (x <= 1)).astype(np.float64)
     raise ValueError(kind)
 
 

@@ -492,6 +492,93 @@ def test_warp_packed_paths_vs_oracle(torch, golden, oracle, eng_g, eng_l, kind, 
             assert err <= F32_TOL, err
 
 
+def _sr_kernel(inp, out, kind, S, in_hw, out_hw, max_sigma):
+    """the kernel launch_resize (csrc/lerf_kernels.hip) gives an SR call: the fixed kinds resize_fixed_kernel; uint8 in / out
+    the float32 arithmetic A = float unless gauss with max_sigma > 13 (float64, A = double), every float output A = double;
+    the cell kernel for A = float, S = 2 and an up-sampling grid; else resize_kernel<.., A, ST>, ST = S for S in (2, 4), else
+    ST = 0 (two passes, any S)."""
+    if kind not in ("gauss", "linear"):
+        return "fixed"
+    A = "float" if inp == out == "u8" and not (kind == "gauss" and max_sigma > 13) else "double"
+    if A == "float" and S == 2 and out_hw[0] >= in_hw[0] and out_hw[1] >= in_hw[1]:
+        return "cells"
+    return "resize<%s,%d>" % (A, S if S in (2, 4) else 0)
+
+
+# (in, out, kind, S, scale, max_sigma, kernel).  Up-sampling rows, down-sampling columns where the cell kernel must decline;
+# the oracle's anti-aliasing (row factor < 1) is never triggered.
+RESIZE_PATH_CASES = (
+    [("u8", "u8", k, 2, (2.0, 2.5), 10.0, "cells") for k in ("gauss", "linear")]
+    + [("u8", "u8", k, 2, (2.0, 0.75), 10.0, "resize<float,2>") for k in ("gauss", "linear")]
+    + [("u8", "u8", k, 4, (2.0, 1.5), 10.0, "resize<float,4>") for k in ("gauss", "linear")]
+    + [("u8", "u8", "gauss", S, (2.0, 2.5), 16.0, "resize<double,%d>" % (S if S != 3 else 0)) for S in (2, 3, 4)]
+    + [("u8", "u8", k, S, (2.0, 1.5), 10.0, "resize<float,0>") for k in ("gauss", "linear") for S in (3, 6)]
+    + [("f32", "f32", k, S, (2.0, 1.5), 10.0, "resize<double,0>") for k in ("gauss", "linear") for S in (3, 6)]
+    + [(i, o, k, S, (2.0, 1.5), 10.0, "resize<double,%d>" % S)
+       for i in ("u8", "f32") for o in ("f32", "f64") for k in ("gauss", "linear") for S in (2, 4)]
+    + [(i, o, k, S, (2.0, 1.5), 1.0, "fixed")
+       for i, o in (("u8", "u8"), ("f32", "f32"), ("f32", "f64"))
+       for k, S in (("nearest", 2), ("cubic", 4), ("bilinear", 2), ("lanczos2", 4), ("lanczos3", 6))])
+# uint8 outputs that are byte-exact: the tie-guarded float32 paths and the float64 arithmetic.  The others (float32 arithmetic
+# without the tie guard: resize<float,0>, fixed) may differ by one where the oracle lies within RESIZE_U8_TIE_WIN of a
+# half-integer (observed: 9.2e-8 at most).  Float outputs: float64 within 1e-9; float32 from the float64 arithmetic within
+# RESIZE_F32_OF_F64 (one rounding of the output, half an ulp at 255: 7.6e-6), from the fixed kernels' float32 arithmetic
+# within F32_OBSERVED (observed: 8.2e-5).
+RESIZE_U8_EXACT = ("cells", "resize<float,2>", "resize<float,4>", "resize<double,2>", "resize<double,4>", "resize<double,0>")
+RESIZE_U8_TIE_WIN = 1e-6
+RESIZE_F32_OF_F64 = 1e-5
+
+
+def _resize_path_case(torch, oracle, inp, out, kind, S, scale, max_sigma, pad):
+    """(kernel output, float64 oracle) of one SR call, both [C, oH, oW]"""
+    from lerf_pytorch_amd import _lib, ops
+    C, H, W = 2, 13, 17
+    rng = np.random.default_rng([S, int(scale[1] * 4), int(max_sigma), len(kind), len(pad)])
+    feat = rng.integers(0, 256, (C, H, W)).astype(np.uint8)
+    hq = rng.integers(0, 256, (3, C, H, W)).astype(np.uint8)
+    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
+    geo = ops.SrGeometry((H, W), list(scale), None, S, pad_mode=_lib.PAD_MODES[pad])
+    if inp == "u8":
+        h = oracle._hyper_f32(hq)
+        f8 = torch.from_numpy(np.ascontiguousarray(feat.transpose(1, 2, 0))).cuda()
+        h8 = torch.from_numpy(np.ascontiguousarray(hq.transpose(2, 3, 1, 0))).cuda() if nh else None
+        got = ops.resize_hwc_u8(f8, h8, geo, kind, max_sigma, out=out).cpu().numpy().transpose(2, 0, 1)
+    else:
+        h = rng.random((3, C, H, W), dtype=np.float32)
+        hyp = [torch.from_numpy(h[k]).cuda() for k in range(nh)]
+        got = ops.resize_planar(torch.from_numpy(feat.astype(np.float32)).cuda(), hyp, geo, kind, max_sigma, out=out).cpu().numpy()
+    ref = oracle.resize_params_f32(feat.astype(np.float32), h[0], h[1], h[2], scale[0], scale[1], S, max_sigma, kind,
+                                   pad_mode=pad)
+    assert got.shape == ref.shape == (C,) + geo.out_hw
+    return got, ref
+
+
+@pytest.mark.parametrize("pad", ["constant", "edge", "reflect", "symmetric", "wrap"])
+@pytest.mark.parametrize("inp,out,kind,S,scale,max_sigma,kernel", RESIZE_PATH_CASES)
+def test_resize_paths_vs_oracle(torch, oracle, inp, out, kind, S, scale, max_sigma, kernel, pad):
+    """every SR forward kernel (resize_cells_u8_kernel, resize_kernel for ST = 2, 4 and 0 in float32 and float64 arithmetic,
+    resize_fixed_kernel for every fixed kind) against the float64 oracle under every pad mode of the image operand.  uint8
+    bytes exactly where the arithmetic is tie-guarded or float64 (RESIZE_U8_EXACT), float outputs within the bounds above, NaN
+    (uint8: 0) at the same positions."""
+    H, W = 13, 17
+    oracle_out_hw = (oracle.out_size(H, scale[0]), oracle.out_size(W, scale[1]))
+    assert _sr_kernel(inp, out, kind, S, (H, W), oracle_out_hw, max_sigma) == kernel
+    got, ref = _resize_path_case(torch, oracle, inp, out, kind, S, scale, max_sigma, pad)
+    if out == "u8":
+        want = oracle.to_u8(np.nan_to_num(ref, nan=0.0))
+        if kernel in RESIZE_U8_EXACT:
+            assert np.array_equal(got, want), "%d of %d bytes differ" % ((got != want).sum(), want.size)
+        else:
+            near_tie = np.abs(ref - np.floor(ref) - 0.5) < RESIZE_U8_TIE_WIN
+            assert np.all((got == want) | near_tie)
+            assert np.max(np.abs(got.astype(int) - want)) <= 1
+    else:
+        assert np.array_equal(np.isnan(got), np.isnan(ref))
+        ok = ~np.isnan(ref)
+        err = np.max(np.abs(got[ok] - ref[ok]))
+        assert err <= (1e-9 if out == "f64" else F32_OBSERVED if kernel == "fixed" else RESIZE_F32_OF_F64), err
+
+
 @pytest.mark.parametrize("H,W,scale,S", [
     (1, 1, 2, 2), (2, 3, 2, 2), (7, 5, 3, 2), (63, 65, 2, 2), (64, 64, 1, 2), (64, 128, 4, 2), (65, 64, 2.5, 2),
     (33, 200, (1.5, 2.0), 2), (130, 70, (1.0, 3.0), 2), (100, 90, 2, 4), (40, 300, 1.25, 4), (129, 129, 4, 4)])
