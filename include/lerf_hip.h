@@ -461,6 +461,26 @@ int lerf_warp_bwd(const float* feat, const float* h0, const float* h1, const flo
 size_t lerf_srnet_weight_floats(int outC);
 int lerf_srnet_to_lut(const float* weights, int outC, int interval, int8_t* lut, float* y, void* stream);
 
+/* ---- training the hyper-networks (train_model.py -e ... --twoStage, model SRNetsSWF2, resample/model.py:69-129): one
+ * SRNet on image planes, forward and backward, the trainable twin of lerf_srnet_to_lut.
+ * weights: device, lerf_srnet_weight_floats(outC) floats in the packed layout above; outC 1..4 (else LERF_EUNSUPPORTED).
+ * img: float32 [n_planes][h+bd][w+bd] (values in [0,1] as the reference feeds its nets), already rotated and
+ * replicate-padded by the caller (SRNetsSWF2.predict); mode: one of "sdyct" with its own pattern pixels (lerf_mode_offsets,
+ * rotation 0: no LSB quirk), bd >= the pattern reach (mode_pad_dict: s 1, d 2, y 2, c 3, t 3), else LERF_EINVAL.
+ * out / grad_out: float32 [n_planes][outC][h][w] (= [B][C*outC][h][w]); out = tanh(net), SRNet.forward (common/network.py:
+ * 127-163) -- the scale by norm//2, the straight-through round and the rotation stay with the caller.
+ * Backward = what autograd derives for the reference module, the forward recomputed inside (nothing is kept between the
+ * calls): grad_weights (packed layout, required) and grad_img (float32 [n_planes][h+bd][w+bd], may be NULL) are ACCUMULATED
+ * into.  Deterministic: no float atomics, repeated calls give bitwise-identical gradients.  workspace: device memory of at
+ * least lerf_srnet_bwd_workspace_bytes(outC, n_planes, h, w) bytes (else LERF_EINVAL), contents arbitrary, used by this
+ * call only (per-workgroup weight-gradient slabs and a per-position input-gradient buffer); 0 for a bad outC or shape. */
+int lerf_srnet_fwd_f32(const float* weights, int outC, char mode, const float* img, int n_planes, int h, int w, int bd,
+                       float* out, void* stream);
+size_t lerf_srnet_bwd_workspace_bytes(int outC, int n_planes, int h, int w);
+int lerf_srnet_bwd_f32(const float* weights, int outC, char mode, const float* img, const float* grad_out, int n_planes, int h,
+                       int w, int bd, float* grad_weights, float* grad_img, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- calibration (bench.py roofline_lds): `workgroups` x 1024 threads, each wave issuing 10 x `iters` ds_read_b32 gathers
  * into a 134-KB LDS table -- pattern 0: random addresses (the rate a data-dependent LUT gather gets), pattern 1:
  * conflict-free.  The caller times the launch (one workgroup per CU: wave-gathers per CU = 160 x iters) and owns `sink`

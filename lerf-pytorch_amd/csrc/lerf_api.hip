@@ -346,6 +346,38 @@ int lerf_srnet_to_lut(const float* weights, int outC, int interval, int8_t* lut,
     return rc != LERF_OK ? rc : check_launch();
 }
 
+// the trainable net: the shape checks both entry points share (outC first: LERF_EUNSUPPORTED outranks a bad shape)
+static int srnet_args(int outC, int n_planes, int h, int w, int bd) {
+    if (outC < 1 || outC > 4) return LERF_EUNSUPPORTED;
+    if (n_planes < 1 || h < 1 || w < 1 || bd < 0) return LERF_EINVAL;
+    if ((int64_t)n_planes * (h + bd) * (w + bd) > 0x7FFFFFFF) return LERF_EUNSUPPORTED;
+    return LERF_OK;
+}
+
+int lerf_srnet_fwd_f32(const float* weights, int outC, char mode, const float* img, int n_planes, int h, int w, int bd,
+                       float* out, void* stream) {
+    int rc = srnet_args(outC, n_planes, h, w, bd);
+    if (rc != LERF_OK) return rc;
+    if (!weights || !img || !out) return LERF_EINVAL;
+    rc = launch_srnet_fwd(weights, outC, mode, img, n_planes, h, w, bd, out, as_stream(stream));
+    return rc != LERF_OK ? rc : check_launch();
+}
+
+size_t lerf_srnet_bwd_workspace_bytes(int outC, int n_planes, int h, int w) {
+    return srnet_args(outC, n_planes, h, w, 0) == LERF_OK ? srnet_bwd_workspace_bytes(outC, n_planes, h, w) : 0;
+}
+
+int lerf_srnet_bwd_f32(const float* weights, int outC, char mode, const float* img, const float* grad_out, int n_planes, int h,
+                       int w, int bd, float* grad_weights, float* grad_img, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    int rc = srnet_args(outC, n_planes, h, w, bd);
+    if (rc != LERF_OK) return rc;
+    if (!weights || !img || !grad_out || !grad_weights || !workspace) return LERF_EINVAL;
+    rc = launch_srnet_bwd(weights, outC, mode, img, grad_out, n_planes, h, w, bd, grad_weights, grad_img, workspace,
+                          workspace_bytes, as_stream(stream));
+    return rc != LERF_OK ? rc : check_launch();
+}
+
 int lerf_ubench_lds_gather(int pattern, int iters, int workgroups, uint32_t* sink, void* stream) {
     if ((pattern != 0 && pattern != 1) || iters < 1 || workgroups < 1 || !sink) return LERF_EINVAL;
     int rc = launch_ubench_lds_gather(pattern, iters, workgroups, sink, as_stream(stream));

@@ -104,6 +104,13 @@ int launch_stages_fused_c4(const FusedArgs& a, hipStream_t st);
 // lerf_transfer.hip
 size_t srnet_weight_floats(int outC);
 int launch_srnet_to_lut(const float* weights, int outC, int interval, int8_t* lut, float* y, hipStream_t st);
+// lerf_srnet.hip
+size_t srnet_bwd_workspace_bytes(int outC, int n_planes, int h, int w);
+int launch_srnet_fwd(const float* weights, int outC, char mode, const float* img, int n_planes, int h, int w, int bd,
+                     float* out, hipStream_t st);
+int launch_srnet_bwd(const float* weights, int outC, char mode, const float* img, const float* grad_out, int n_planes, int h,
+                     int w, int bd, float* grad_weights, float* grad_img, void* workspace, size_t workspace_bytes,
+                     hipStream_t st);
 
 // lerf_ubench.hip
 int launch_ubench_lds_gather(int pattern, int iters, int blocks, uint32_t* sink, hipStream_t st);

@@ -17,23 +17,17 @@
 #include <stdint.h>
 
 #include "lerf_kernels.h"
+#include "lerf_srnet_layout.h"
 
 namespace lerf {
 
 namespace transfer {
+using srnet::NF;
+using srnet::ACT;
+using srnet::off_w;                  // packed weights of one SRNet: lerf_srnet_layout.h
 constexpr int ROWS = 64;             // tuples per workgroup
-constexpr int NF = 64;               // hidden width (option.py: --nf 64)
-constexpr int ACT = 5 * NF;          // 320 concatenated activations
 constexpr int PITCH = ACT + 4;       // LDS row pitch in floats (bank spread)
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-// packed weights of one SRNet (floats): W1[64][4] b1[64] W2[64][64] b2[64] W3[64][128] b3[64] W4[64][192] b4[64]
-// W5[64][256] b5[64] W6[outC][320] b6[outC]
-__host__ __device__ constexpr int off_w(int layer) {      // layer 1..6 -> offset of W_layer
-    int o = 0;
-    for (int l = 1; l < layer; ++l) o += NF * (l == 1 ? 4 : (l - 1) * NF) + NF;
-    return o;
-}
 
 __global__ void __launch_bounds__(256)
 srnet_lut_kernel(const float* __restrict__ W, int outC, int interval, int L, int n_entries, int8_t* __restrict__ lut,
@@ -121,7 +115,7 @@ srnet_lut_kernel(const float* __restrict__ W, int outC, int interval, int L, int
 }
 }  // namespace transfer
 
-size_t srnet_weight_floats(int outC) { return (size_t)transfer::off_w(6) + (size_t)outC * transfer::ACT + outC; }
+size_t srnet_weight_floats(int outC) { return (size_t)srnet::weight_floats(outC); }
 
 int launch_srnet_to_lut(const float* weights, int outC, int interval, int8_t* lut, float* y, hipStream_t st) {
     if (outC < 1 || outC > 4 || interval < 1 || interval > 7) return LERF_EUNSUPPORTED;

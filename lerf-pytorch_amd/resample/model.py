@@ -1,5 +1,7 @@
-"""The trainable LUT model of the reference, on the MI355X path: mirror of `SWF2LUT` in resample/model.py:130-431
-(`InterpTorchBatch`, `forward`, `predict`) -- LUT fine-tuning, scripts.sh:28-30.
+"""The trainable models of the reference, on the MI355X path: mirror of `SWF2LUT` in resample/model.py:130-431
+(`InterpTorchBatch`, `forward`, `predict`) -- LUT fine-tuning, scripts.sh:28-30 -- and of the hyper-networks
+`SRNetsSWF2` (:69-129) that train_model.py --twoStage trains and transfer_to_lut turns into LUTs (`SRNetsSWF2`,
+`export_srnets`; the nets run in lerf_srnet_fwd_f32 / lerf_srnet_bwd_f32).
 
 The LUT pass runs in liblerf_hip.so (lerf_swf2lut_interp_f32 / _bwd_f32) behind a torch.autograd.Function whose
 backward is the gradient autograd derives for the reference code: into the LUT parameters (straight-through round,
@@ -112,16 +114,18 @@ class SWF2LUT(nn.Module):
         outC = 1 if stage == 1 else self.outC
         return self.InterpTorchBatch(getattr(self, "weight_" + key), outC, mode, x, pad)
 
-    def _rotation_ensemble(self, x, modes, stage, lut_of_rotation):
+    def _rotation_ensemble(self, x, modes, stage, lut_of_rotation, scale=None):
         """Sum over modes and the four quarter-turns of one stage: rotate, replicate-pad bottom/right by the mode's
-        reach, LUT pass, rotate back, straight-through round (model.py:405-412, 419-424)."""
+        reach, LUT pass, rotate back, straight-through round (model.py:405-412, 419-424).  `scale` multiplies the
+        rotated-back pass before the round (SRNetsSWF2: the net's tanh output times norm//2, model.py:101-124)."""
         total = 0
         for mode in modes:
             reach = mode_pad_dict[mode]
             for quarter_turns in range(4):
                 rotated = F.pad(torch.rot90(x, quarter_turns, [2, 3]), (0, reach, 0, reach), mode="replicate")
                 passed = self.forward(rotated, stage=stage, mode=mode, r=lut_of_rotation(quarter_turns))
-                total = total + round_func(torch.rot90(passed, (4 - quarter_turns) % 4, [2, 3]))
+                back = torch.rot90(passed, (4 - quarter_turns) % 4, [2, 3])
+                total = total + round_func(back if scale is None else back * scale)
         return total
 
     def predict(self, x, stage=None):
@@ -140,6 +144,151 @@ class SWF2LUT(nn.Module):
             else:
                 x = torch.clamp(round_func(pred / (len(self.modes) * 4)) + self.norm // 2, 0, self.norm) / float(self.norm)
         return x
+
+
+class _SRNetFn(torch.autograd.Function):
+    """One SRNet on [B, C, h+bd, w+bd] planes -> tanh output [B, C*outC, h, w] (lerf_srnet_fwd_f32 / lerf_srnet_bwd_f32);
+    the weights arrive packed (torch.cat of the parameters, so autograd hands each parameter its slice of the packed
+    gradient)."""
+
+    @staticmethod
+    def forward(ctx, flat, img_in, outC, mode, bd):
+        if not (flat.is_cuda and img_in.is_cuda):
+            raise ValueError("SRNetsSWF2 runs on the GPU (there is no CPU path)")
+        w = flat.detach().contiguous().float()
+        x = img_in.detach().contiguous().float()
+        B, Cn, hp, wp = x.shape
+        h, wd = hp - bd, wp - bd
+        out = torch.empty((B, Cn * outC, h, wd), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().lerf_srnet_fwd_f32(C.c_void_p(w.data_ptr()), int(outC), _mode_char(mode), C.c_void_p(x.data_ptr()),
+                                                 B * Cn, h, wd, int(bd), C.c_void_p(out.data_ptr()), _lib.current_stream()),
+                   "lerf_srnet_fwd_f32")
+        ctx.save_for_backward(w, x)
+        ctx.meta = (int(outC), mode, int(bd))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        w, x = ctx.saved_tensors
+        outC, mode, bd = ctx.meta
+        B, Cn, hp, wp = x.shape
+        h, wd = hp - bd, wp - bd
+        g = grad_out.contiguous().float()
+        gw = torch.zeros_like(w)
+        gx = torch.zeros_like(x) if ctx.needs_input_grad[1] else None
+        L = _lib.lib()
+        nbytes = L.lerf_srnet_bwd_workspace_bytes(outC, B * Cn, h, wd)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+        _lib.check(L.lerf_srnet_bwd_f32(C.c_void_p(w.data_ptr()), outC, _mode_char(mode), C.c_void_p(x.data_ptr()),
+                                        C.c_void_p(g.data_ptr()), B * Cn, h, wd, bd, C.c_void_p(gw.data_ptr()),
+                                        C.c_void_p(gx.data_ptr() if gx is not None else None), C.c_void_p(ws.data_ptr()),
+                                        nbytes, _lib.current_stream()), "lerf_srnet_bwd_f32")
+        return (gw if ctx.needs_input_grad[0] else None), gx, None, None, None
+
+
+class _Conv(nn.Module):
+    """common/network.py:14-28: Conv2d with MSRA (Kaiming-normal) weights and zero biases; only its parameters are used
+    here (the layer runs inside lerf_srnet_fwd_f32)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super(_Conv, self).__init__()
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size)
+        nn.init.kaiming_normal_(self.conv.weight)
+        nn.init.constant_(self.conv.bias, 0)
+
+
+class _DenseConv(nn.Module):
+    def __init__(self, in_nf, nf=64):                            # network.py:31-41
+        super(_DenseConv, self).__init__()
+        self.conv1 = _Conv(in_nf, nf, 1)
+
+
+class _SRUnit(nn.Module):
+    def __init__(self, mode, nf, outC):                          # network.py:43-71 (upscale 1)
+        super(_SRUnit, self).__init__()
+        self.conv1 = _Conv(1, nf, 2 if mode in "sd" else (1, 4))
+        self.conv2 = _DenseConv(nf, nf)
+        self.conv3 = _DenseConv(nf + nf * 1, nf)
+        self.conv4 = _DenseConv(nf + nf * 2, nf)
+        self.conv5 = _DenseConv(nf + nf * 3, nf)
+        self.conv6 = _Conv(nf * 5, outC, 1)
+
+
+class _SRNet(nn.Module):
+    """network.py:74-163 for the modes sdyct at upscale 1: parameters under `model.`, the pass in HIP."""
+
+    def __init__(self, mode, nf, outC):
+        super(_SRNet, self).__init__()
+        _mode_char(mode)
+        self.mode = mode
+        self.outC = outC
+        self.model = _SRUnit(mode, nf, outC)
+
+    def packed(self):
+        """the parameters flattened in module order: the packed layout of lerf_srnet_fwd_f32"""
+        return torch.cat([p.reshape(-1) for p in self.parameters()])
+
+    def forward(self, x):
+        return _SRNetFn.apply(self.packed(), x, self.outC, self.mode, mode_pad_dict[self.mode])
+
+
+class SRNetsSWF2(nn.Module):
+    """The trainable hyper-networks of the reference, resample/model.py:69-129 (train_model.py --twoStage, scripts.sh
+    step 1): one SRNet per stage-1 mode (`s1_<mode>r0`, one output channel) and two per stage-2 mode (`s2_<mode>r0` for
+    rotations 0 and 2, `s2_<mode>r1` for 1 and 3, outC channels).  Parameter names and shapes are the reference's
+    state_dict keys, so `load_state_dict(dict(np.load("srnets_weights.npz")))` loads an exported model.  The nets run in
+    liblerf_hip.so (lerf_srnet_fwd_f32 / lerf_srnet_bwd_f32); `predict` is the reference's torch glue."""
+
+    def __init__(self, opt, inC=1, outC=3):
+        super(SRNetsSWF2, self).__init__()
+        nf = opt.nf
+        if nf != 64:
+            raise NotImplementedError("only nf=64 (the shipped models) is implemented")
+        self.modes2 = opt.modes2
+        self.modes = opt.modes
+        self.stages = opt.stages
+        self.norm = opt.norm
+        self.outC = outC
+        for s in range(self.stages):
+            if s + 1 == self.stages:
+                for mode in self.modes2:
+                    for r in [0, 1]:
+                        self.add_module("s{}_{}r{}".format(s + 1, mode, r), _SRNet(mode, nf, outC))
+            else:
+                for mode in self.modes:
+                    self.add_module("s{}_{}r0".format(s + 1, mode), _SRNet(mode, nf, 1))
+
+    def forward(self, x, stage, mode, r):
+        """[B, C, h+P, w+P] -> tanh of the net, [B, C*outC, h, w] (P = the mode's reach)"""
+        _mode_char(mode)
+        return getattr(self, "s{}_{}r{}".format(str(stage), mode, r))(x)
+
+    _rotation_ensemble = SWF2LUT._rotation_ensemble
+
+    def predict(self, x, stage=None):
+        """x in [0, 1]; stage 2 -> hyper-parameter maps in [0, 1], otherwise the pre-filtered image in 0..255
+        (model.py:101-129)."""
+        half = self.norm // 2
+        if stage == 2:          # hyper stage: net r0 serves rotations 0 and 2, net r1 rotations 1 and 3
+            pred = self._rotation_ensemble(x, self.modes2, self.stages, lambda q: q & 1, scale=half)
+            return torch.clamp(round_func(pred / (len(self.modes2) * 4) + half), 0, self.norm) / float(self.norm)
+        for s in range(self.stages - 1):
+            pred = self._rotation_ensemble(x, self.modes, s + 1, lambda q: 0, scale=half)
+            if s + 1 == self.stages - 1:
+                avg_factor, bias, norm = len(self.modes), 0, 1
+            else:
+                avg_factor, bias, norm = len(self.modes) * 4, half, float(self.norm)
+            x = torch.clamp(round_func(pred / avg_factor) + bias, 0, self.norm) / norm
+        return x
+
+
+def export_srnets(model: SRNetsSWF2, exp_dir: str):
+    """`<exp_dir>/srnets_weights.npz`: the model's state_dict as float32 arrays, what transfer_to_lut.load_weights reads
+    (python -m lerf_pytorch_amd.resample.transfer_to_lut -e <exp_dir> then writes the LUTs)."""
+    os.makedirs(exp_dir, exist_ok=True)
+    path = os.path.join(exp_dir, "srnets_weights.npz")
+    np.savez(path, **{k: v.detach().float().cpu().numpy() for k, v in model.state_dict().items()})
+    return path
 
 
 def export_luts(model: SWF2LUT, exp_dir: str, lut_name: str = "LUTft"):
