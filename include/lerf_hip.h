@@ -481,6 +481,27 @@ int lerf_srnet_bwd_f32(const float* weights, int outC, char mode, const float* i
                        int w, int bd, float* grad_weights, float* grad_img, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ---- LeRF-Net (resample/model.py:434-537): the forward of one IMDN_RTC net at upscale 1, i.e. one stage of IMDN2
+ * (stage1: in_nc -> in_nc channels, stage2: in_nc -> in_nc * outC).  fea_conv 3x3, five IMDModule_speed (c1..c3 3x3 +
+ * LeakyReLU(0.05), distilled d = nf/4 channels split off each; c4 3x3 -> d; c5 1x1 over the 4d concatenated channels +
+ * the module input), LR_conv 1x1 + fea, upsampler conv 3x3 -> out_nc; every conv zero-padded by (k-1)/2.
+ * weights: device, lerf_imdn_weight_floats(nf, in_nc, out_nc) floats: the state_dict tensors of the IMDN_RTC in
+ * state_dict order, each in PyTorch's [out][in][kh][kw] order (model.0, model.1.sub.{0..4}.c{1..5}, model.1.sub.5,
+ * model.2; weight then bias; csrc/lerf_imdn_layout.h).  nf a multiple of 16 in [16, 64], in_nc 1 or 3, out_nc 1, 3 or 9
+ * (else LERF_EUNSUPPORTED; 0 from the size queries).
+ * x: float32 NCHW [B][in_nc][H][W]; out: float32 NCHW [B][out_nc][H][W]; B, H, W >= 1.
+ * post: 0 the raw net output, 1 clamp(y, -1, 1) * 127 + 127 (IMDN2.predict stage 1 at norm 255), 2 clamp(y, -1, 1) / 2
+ * + 1/2 (stage 2); each step rounded to float32 as the reference's torch ops are.
+ * workspace: device memory of at least lerf_imdn_workspace_bytes(nf, B, H, W) bytes (18 nf bytes per pixel; NHWC
+ * activations), contents arbitrary, used by this call only.  A short workspace, a null pointer or a bad shape or post is
+ * LERF_EINVAL, and nothing is written.  Float32 products and sums on the matrix cores (v_mfma_f32_16x16x4_f32); no
+ * atomics, so the output is deterministic and image b of a batch equals image b run alone.  Launches on `stream`, no
+ * sync. */
+size_t lerf_imdn_weight_floats(int nf, int in_nc, int out_nc);
+size_t lerf_imdn_workspace_bytes(int nf, int B, int H, int W);
+int lerf_imdn_fwd_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                      void* workspace, size_t workspace_bytes, float* out, void* stream);
+
 /* ---- calibration (bench.py roofline_lds): `workgroups` x 1024 threads, each wave issuing 10 x `iters` ds_read_b32 gathers
  * into a 134-KB LDS table -- pattern 0: random addresses (the rate a data-dependent LUT gather gets), pattern 1:
  * conflict-free.  The caller times the launch (one workgroup per CU: wave-gathers per CU = 160 x iters) and owns `sink`

@@ -49,6 +49,7 @@ EXPORTS = [
     "lerf_metric_y_sse_u8", "lerf_metric_ssim_y_u8", "lerf_metric_masked_sse_u8",
     "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd",
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_srnet_fwd_f32", "lerf_srnet_bwd_workspace_bytes", "lerf_srnet_bwd_f32",
+    "lerf_imdn_weight_floats", "lerf_imdn_workspace_bytes", "lerf_imdn_fwd_f32",
     "lerf_ubench_lds_gather",
 ]
 
@@ -219,6 +220,12 @@ def lib():
     L.lerf_srnet_bwd_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.lerf_srnet_bwd_f32.argtypes = [C.c_void_p, C.c_int, C.c_char, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.lerf_imdn_weight_floats.restype = C.c_size_t
+    L.lerf_imdn_weight_floats.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.lerf_imdn_workspace_bytes.restype = C.c_size_t
+    L.lerf_imdn_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.lerf_imdn_fwd_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)

@@ -378,6 +378,33 @@ int lerf_srnet_bwd_f32(const float* weights, int outC, char mode, const float* i
     return rc != LERF_OK ? rc : check_launch();
 }
 
+// LeRF-Net: nf a multiple of 16 in [16, 64], in_nc 1 or 3, out_nc 1, 3 or 9 (else LERF_EUNSUPPORTED, outranking a bad shape)
+static int imdn_args(int nf, int in_nc, int out_nc, int B, int H, int W) {
+    if (nf < 16 || nf > 64 || nf % 16 != 0 || (in_nc != 1 && in_nc != 3) || (out_nc != 1 && out_nc != 3 && out_nc != 9))
+        return LERF_EUNSUPPORTED;
+    if (B < 1 || H < 1 || W < 1) return LERF_EINVAL;
+    if ((int64_t)B * H * W > 0x7FFFFFFF) return LERF_EUNSUPPORTED;
+    return LERF_OK;
+}
+
+size_t lerf_imdn_weight_floats(int nf, int in_nc, int out_nc) {
+    return imdn_args(nf, in_nc, out_nc, 1, 1, 1) == LERF_OK ? imdn_weight_floats(nf, in_nc, out_nc) : 0;
+}
+
+size_t lerf_imdn_workspace_bytes(int nf, int B, int H, int W) {
+    return imdn_args(nf, 3, 3, B, H, W) == LERF_OK ? imdn_workspace_bytes(nf, B, H, W) : 0;
+}
+
+int lerf_imdn_fwd_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                      void* workspace, size_t workspace_bytes, float* out, void* stream) {
+    int rc = imdn_args(nf, in_nc, out_nc, B, H, W);
+    if (rc != LERF_OK) return rc;
+    if (!weights || !x || !out || !workspace || post < 0 || post > 2) return LERF_EINVAL;
+    if (workspace_bytes < imdn_workspace_bytes(nf, B, H, W)) return LERF_EINVAL;
+    rc = launch_imdn_fwd(weights, nf, in_nc, out_nc, x, B, H, W, post, workspace, out, as_stream(stream));
+    return rc != LERF_OK ? rc : check_launch();
+}
+
 int lerf_ubench_lds_gather(int pattern, int iters, int workgroups, uint32_t* sink, void* stream) {
     if ((pattern != 0 && pattern != 1) || iters < 1 || workgroups < 1 || !sink) return LERF_EINVAL;
     int rc = launch_ubench_lds_gather(pattern, iters, workgroups, sink, as_stream(stream));

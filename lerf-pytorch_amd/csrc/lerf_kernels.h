@@ -111,6 +111,11 @@ int launch_srnet_fwd(const float* weights, int outC, char mode, const float* img
 int launch_srnet_bwd(const float* weights, int outC, char mode, const float* img, const float* grad_out, int n_planes, int h,
                      int w, int bd, float* grad_weights, float* grad_img, void* workspace, size_t workspace_bytes,
                      hipStream_t st);
+// lerf_imdn.hip
+size_t imdn_weight_floats(int nf, int in_nc, int out_nc);
+size_t imdn_workspace_bytes(int nf, int B, int H, int W);
+int launch_imdn_fwd(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                    void* workspace, float* out, hipStream_t st);
 
 // lerf_ubench.hip
 int launch_ubench_lds_gather(int pattern, int iters, int blocks, uint32_t* sink, hipStream_t st);

@@ -337,3 +337,120 @@ def lutft_step(model_G, resizer, im, lb, opt_G=None, linear=False, norm=255, fea
         if opt_G is not None:
             opt_G.step()
     return loss_G
+
+
+# ------------------------------------------------------------------ LeRF-Net: IMDN2 (resample/model.py:434-537)
+def _conv_layer(in_channels, out_channels, kernel_size):
+    """model.py:435-438 conv_layer: zero padding (k-1)/2, PyTorch's default Conv2d initialisation"""
+    return nn.Conv2d(in_channels, out_channels, kernel_size, 1, padding=(kernel_size - 1) // 2, bias=True)
+
+
+class ShortcutBlock(nn.Module):
+    def __init__(self, submodule):                               # model.py:452-459
+        super(ShortcutBlock, self).__init__()
+        self.sub = submodule
+
+
+class IMDModule_speed(nn.Module):
+    """model.py:483-508: parameter holder (c1..c5); the module runs inside lerf_imdn_fwd_f32"""
+
+    def __init__(self, in_channels, distillation_rate=0.25):
+        super(IMDModule_speed, self).__init__()
+        self.distilled_channels = int(in_channels * distillation_rate)
+        self.remaining_channels = int(in_channels - self.distilled_channels)
+        self.c1 = _conv_layer(in_channels, in_channels, 3)
+        self.c2 = _conv_layer(self.remaining_channels, in_channels, 3)
+        self.c3 = _conv_layer(self.remaining_channels, in_channels, 3)
+        self.c4 = _conv_layer(self.remaining_channels, self.distilled_channels, 3)
+        self.act = nn.LeakyReLU(0.05, True)
+        self.c5 = _conv_layer(self.distilled_channels * 4, in_channels, 1)
+
+
+class IMDN_RTC(nn.Module):
+    """model.py:512-527 at upscale 1 (the only scale IMDN2 uses): fea_conv, ShortcutBlock(5 x IMDModule_speed +
+    LR_conv), upsampler conv + PixelShuffle(1).  Parameters under the reference's `model.*` keys; the forward runs in
+    liblerf_hip.so (lerf_imdn_fwd_f32), on the GPU, without autograd."""
+
+    def __init__(self, in_nc=3, nf=12, num_modules=5, out_nc=3, upscale=1):
+        super(IMDN_RTC, self).__init__()
+        if upscale != 1 or num_modules != 5:
+            raise NotImplementedError("IMDN_RTC is implemented at upscale 1 with 5 modules (IMDN2's configuration)")
+        self.nf, self.in_nc, self.out_nc = nf, in_nc, out_nc
+        rb_blocks = [IMDModule_speed(in_channels=nf) for _ in range(num_modules)]
+        self.model = nn.Sequential(_conv_layer(in_nc, nf, 3), ShortcutBlock(nn.Sequential(*rb_blocks, _conv_layer(nf, nf, 1))),
+                                   _conv_layer(nf, out_nc, 3), nn.PixelShuffle(1))
+
+    def packed(self):
+        """the parameters flattened in state_dict order: the packed layout of lerf_imdn_fwd_f32"""
+        return torch.cat([p.detach().reshape(-1) for p in self.parameters()]).float().contiguous()
+
+    def run(self, x, post=0):
+        """[B, in_nc, H, W] -> [B, out_nc, H, W]: the net (post 0), or predict's clamp and affine fused (1, 2)"""
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("IMDN2 has no backward here: run it under torch.no_grad() (training is out of scope)")
+        if not x.is_cuda:
+            raise ValueError("IMDN2 runs on the GPU (there is no CPU path)")
+        if x.dim() != 4 or x.shape[1] != self.in_nc:
+            raise ValueError("expected [B, %d, H, W], got %s" % (self.in_nc, tuple(x.shape)))
+        w = self.packed().to(x.device)
+        xin = x.detach().contiguous().float()
+        B, _, H, W = xin.shape
+        L = _lib.lib()
+        nbytes = L.lerf_imdn_workspace_bytes(self.nf, B, H, W)
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=x.device)
+        out = torch.empty((B, self.out_nc, H, W), dtype=torch.float32, device=x.device)
+        _lib.check(L.lerf_imdn_fwd_f32(C.c_void_p(w.data_ptr()), self.nf, self.in_nc, self.out_nc, C.c_void_p(xin.data_ptr()),
+                                       B, H, W, int(post), C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(out.data_ptr()),
+                                       _lib.current_stream()), "lerf_imdn_fwd_f32")
+        return out
+
+    def forward(self, input):
+        return self.run(input, 0)
+
+
+class IMDN2(nn.Module):
+    """LeRF-Net / LeRF-Net++ (model.py:530-545): stage1 in_nc -> inC, stage2 inC -> inC * outC, both IMDN_RTC nets of
+    width opt.nf.  predict(x, 1) = clamp(y1, -1, 1) * (norm // 2) + norm // 2, predict(x, 2) = clamp(y2, -1, 1) / 2 + 1/2.
+    Forward only (there is no backward here): evaluate under torch.no_grad(), as the reference's evaluation does."""
+
+    def __init__(self, opt, inC=1, outC=1):
+        super(IMDN2, self).__init__()
+        self.norm = opt.norm
+        self.stage1 = IMDN_RTC(nf=opt.nf, in_nc=inC, out_nc=inC, upscale=1)
+        self.stage2 = IMDN_RTC(nf=opt.nf, in_nc=inC, out_nc=inC * outC, upscale=1)
+
+    def predict(self, x, stage=1):
+        if stage == 2:  # hyper: [0-1]
+            return self.stage2.run(x, 2)
+        half = self.norm // 2
+        if half == 127:
+            return self.stage1.run(x, 1)
+        return torch.clamp(self.stage1.run(x, 0), -1, 1) * half + half
+
+
+def export_imdn2(model: IMDN2, exp_dir: str):
+    """`<exp_dir>/imdn2_weights.npz`: the model's state_dict as float32 arrays (what load_imdn2 and eval_model read)."""
+    os.makedirs(exp_dir, exist_ok=True)
+    path = os.path.join(exp_dir, "imdn2_weights.npz")
+    np.savez(path, **{k: v.detach().float().cpu().numpy() for k, v in model.state_dict().items()})
+    return path
+
+
+def load_state(path):
+    """A state dict from an exported `*_weights.npz` or from a `.pth` holding a plain state dict (a reference
+    Model_XXXXXX.pth pickles the whole module: convert it once with torch.save(torch.load(p).state_dict(), q))."""
+    if path.endswith(".npz"):
+        with np.load(path) as z:
+            return {k: torch.from_numpy(z[k].copy()) for k in z.files}
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(sd, dict):
+        raise ValueError("%s does not hold a plain state dict" % path)
+    return sd
+
+
+def load_imdn2(model: IMDN2, path: str):
+    """load_state_dict(strict=True) from imdn2_weights.npz or a state-dict .pth (a directory: its imdn2_weights.npz)"""
+    if os.path.isdir(path):
+        path = os.path.join(path, "imdn2_weights.npz")
+    model.load_state_dict(load_state(path), strict=True)
+    return model
