@@ -913,7 +913,19 @@ static int try_lut_interp_lds(const void* img, int in_dtype, int64_t sy, int64_t
 //   np.round(np.clip(pred / avg_factor + bias, 0, norm)).astype(np.float32)
 // pred = numerators / q (exact in float64); every step is the float64 operation numpy performs, in numpy's order, no
 // contraction -- the float32 array the caller gets is bit for bit numpy's.  The steps come as a small program.
+// "Bit for bit" covers every int16 numerator, every interval 1..7 and any program of up to 8 steps with any double operands
+// (tests/test_gpu_numer_epilogue.py): the sign of zero (np.clip keeps x where x equals a bound, so clip(-0.0, 0, 255) is -0.0;
+// np.round(-0.3) is -0.0), infinities, and NaN as NaN (x / 0 at x == 0 stays NaN through clip and round; a NaN clip bound
+// makes every element NaN).  Only the PAYLOAD of a NaN is not pinned.
 // ---------------------------------------------------------------------------
+// np.clip(x, lo, hi) in numpy's own comparisons: a bound replaces x only where x is strictly beyond it, so an x equal to a bound
+// keeps its own sign of zero, and a NaN x fails both comparisons and passes through (fmax / fmin would return the bound).
+__device__ __forceinline__ double epi_clip(double x, double lo, double hi) {
+    if (lo != lo || hi != hi) return __builtin_nan("");
+    x = x < lo ? lo : x;
+    return x > hi ? hi : x;
+}
+
 struct EpiProgram { int n; int op[LERF_EPI_MAX_OPS]; double a[LERF_EPI_MAX_OPS], b[LERF_EPI_MAX_OPS]; };
 
 __global__ void __launch_bounds__(256)
@@ -938,7 +950,7 @@ numer_epilogue_kernel(const int16_t* __restrict__ acc, int64_t n, double inv_q, 
                 case LERF_EPI_DIV: x = x / P.a[j]; break;
                 case LERF_EPI_MUL: x = x * P.a[j]; break;
                 case LERF_EPI_ADD: x = x + P.a[j]; break;
-                case LERF_EPI_CLIP: x = fmin(fmax(x, P.a[j]), P.b[j]); break;
+                case LERF_EPI_CLIP: x = epi_clip(x, P.a[j], P.b[j]); break;
                 default: x = __builtin_rint(x); break;          // LERF_EPI_ROUND: half to even, np.round
             }
         }

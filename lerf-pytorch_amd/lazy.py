@@ -13,7 +13,8 @@ same pixels up again).  `DeviceArray` keeps the values in HBM and answers exactl
 numpy would use (float64 sums of multiples of 1/16, IEEE division, round-half-even: bit-equal), so the unchanged call
 sites run stage 1 -> stage 2 -> stage 3 without leaving the device; anything else numpy asks of it (`np.asarray`,
 `__array_interface__` for PIL, an unsupported function) materialises the host copy once and proceeds on that -- slower,
-never different.  `set_enabled(False)` restores plain numpy results.
+never different: the tests hold the deferred sums, the expressions derived from them and the fused stage epilogue to numpy's bit
+patterns, the sign of zero included, and to NaN where numpy gives NaN.  `set_enabled(False)` restores plain numpy results.
 """
 from __future__ import annotations
 
@@ -236,9 +237,21 @@ class DeviceArray(object):
         ok = (not kw and (lo is not None or hi is not None) and all(v is None or isinstance(v, _PY_SCALARS) for v in (lo, hi))
               and _result_dtype(np.add, self, 0 if lo is None else lo) == self.dtype
               and _result_dtype(np.add, self, 0 if hi is None else hi) == self.dtype)
+        if ok and self.t.is_floating_point() and any(v is not None and v != v for v in (lo, hi)):
+            ok = False                                                          # a NaN bound: numpy's own answer (all NaN)
         if not ok or out is not None:
             return _with_out(lambda: self.numpy().clip(_host(min), _host(max), **kw), out)
-        return DeviceArray(self.t.clamp(min=lo, max=hi))
+        if not self.t.is_floating_point():
+            return DeviceArray(self.t.clamp(min=lo, max=hi))
+        # numpy's comparisons, not a max / min instruction: a bound replaces x only where x is strictly beyond it, so x keeps its
+        # own sign of zero where it equals a bound (np.clip(-0.0, 0, 255) is -0.0) and a NaN x stays NaN
+        torch = _torch()
+        t = self.t
+        if lo is not None:
+            t = torch.where(t < lo, torch.full((), float(lo), dtype=t.dtype, device=t.device), t)
+        if hi is not None:
+            t = torch.where(t > hi, torch.full((), float(hi), dtype=t.dtype, device=t.device), t)
+        return DeviceArray(t if t is not self.t else t.clone())
 
     def __getattr__(self, name):
         # anything else an ndarray offers (max, mean, flags ...): on the (read-only) host copy
@@ -635,7 +648,9 @@ class LazyArray(DeviceArray):
         if len(steps) >= 8:
             return None
         steps.append((op,) + tuple(float(v) for v in operands))
-        return _expr_array(acc, interval, steps)
+        # the expression reads the sum's numerators: it lists the sum (for an expression of an expression: the sum it came from) as
+        # what it depends on, so that the next `pred += F(...)`, which adds into `acc` in place, runs it first (_fold_into_add)
+        return _expr_array(acc, interval, steps, [self] if kind == "sum" else self._deps)
 
     # ---- the worker's last statement on a resampler result (resample/eval_lut_sr.py:663-665):
     #      np.clip(np.round(out).transpose((1, 2, 0)), 0, norm).astype(np.uint8)
@@ -682,8 +697,12 @@ class LazyArray(DeviceArray):
             f = ops.numer_epilogue(acc, interval, [(code[st[0]],) + tuple(st[1:]) for st in steps])
             kinds = [st[0] for st in steps[-2:]]
             clip = [st for st in steps[-2:] if st[0] == "clip"]
-            if sorted(kinds) == ["clip", "round"] and clip[0][1] >= 0 and clip[0][2] <= 255:
-                return DeviceArray(f, u8=(f.to(_torch().uint8), 1.0))           # integers 0..255: the stage's uint8 output, exactly
+            if sorted(kinds) == ["clip", "round"] and clip[0][1] >= 0 and clip[0][2] <= 255 and _steps_stay_finite(steps) \
+                    and (kinds[-1] == "round" or (float(clip[0][1]).is_integer() and float(clip[0][2]).is_integer())):
+                # integers 0..255: the stage's uint8 output, exactly.  Only when that is TRUE of every element: round is the last
+                # step, or the clip after it has integer bounds (np.clip(np.round(x), 0.5, 254.5) holds 0.5), and no step can
+                # have made a NaN, which the clip would pass on
+                return DeviceArray(f, u8=(f.to(_torch().uint8), 1.0))
             return DeviceArray(f)
         return DeviceArray.astype(self, dtype, *a, **k)
 
@@ -696,10 +715,11 @@ class LazyArray(DeviceArray):
             # the sum is still int16 numerators: add this pass's numerators (same interval, no overflow: |n| <= 127 q per pass)
             _, acc, interval, bound = target._recipe
             mine = self._recipe[2]
-            if inplace and mine == interval and tuple(acc.shape) == self._shape and bound + (127 << interval) <= 32767 \
-                    and self._recipe[1](acc, True):
-                target._recipe = ("sum", acc, interval, bound + (127 << interval))
-                return target
+            if inplace and mine == interval and tuple(acc.shape) == self._shape and bound + (127 << interval) <= 32767:
+                _flush_dependents(target._vc)                   # `half = pred / 2` before this `pred +=`: numpy computed it then
+                if self._recipe[1](acc, True):
+                    target._recipe = ("sum", acc, interval, bound + (127 << interval))
+                    return target
         tt = target.t
         if tt.dtype != torch.float64 or tuple(tt.shape) != self._shape or not tt.is_cuda or not tt.is_contiguous():
             return None
@@ -727,6 +747,27 @@ def _apply_tail(root, steps):
 
 
 
+def _steps_stay_finite(steps):
+    """True when no element of a sum (|value| <= 2^15) can become infinite or NaN under these steps: bounds on the magnitude"""
+    m = 32768.0
+    for st in steps:
+        if any(v != v or v in (float("inf"), float("-inf")) for v in st[1:]):
+            return False
+        if st[0] == "div":
+            if st[1] == 0:
+                return False
+            m = m / abs(st[1])
+        elif st[0] == "mul":
+            m = m * abs(st[1])
+        elif st[0] == "add":
+            m = m + abs(st[1])
+        elif st[0] == "clip":
+            m = min(m, max(abs(st[1]), abs(st[2]))) if st[1] <= st[2] else max(abs(st[1]), abs(st[2]))
+        if not m < 1e300:
+            return False
+    return True
+
+
 def _sum_array(acc, interval, bound):
     """pending float64 array = acc / 2^interval (exact), kept as the int16 numerators"""
     torch = _torch()
@@ -749,9 +790,9 @@ def _apply_steps(x, steps):
     return x
 
 
-def _expr_array(acc, interval, steps):
+def _expr_array(acc, interval, steps, deps):
     torch = _torch()
-    return LazyArray(acc.shape, np.float64, [],
+    return LazyArray(acc.shape, np.float64, deps,
                      lambda: _apply_steps(DeviceArray(acc.to(torch.float64) / float(1 << interval)), steps).t, ("expr", acc, interval, steps))
 
 

@@ -124,6 +124,37 @@ def s_copy_semantics(interp, pads, luts, dev):
     return [c, a, x, np.array(x), np.asarray(x).dtype.str]
 
 
+def s_derived_from_sum_then_accumulated(interp, pads, luts, dev):
+    pred = 0
+    pred += _pass(interp, pads, luts, dev(_img(13)))
+    half = pred / 2                                      # numpy computes these four NOW, from one pass ...
+    c = np.clip(pred, 0, 255)
+    r = np.round(pred)
+    p = pred + 1
+    pred += _pass(interp, pads, luts, dev(_img(14)), mode="c", key="s1_cr0", r=1)      # ... whatever the sum becomes later
+    return [half, c, r, p, pred]
+
+
+def s_expr_of_expr_then_accumulated(interp, pads, luts, dev):
+    pred = 0
+    pred += _pass(interp, pads, luts, dev(_img(15)))
+    pred += _pass(interp, pads, luts, dev(_img(15)), r=2)
+    q = (pred / 3 + 0.5)                                 # an expression of an expression of the sum
+    pred += _pass(interp, pads, luts, dev(_img(16)), mode="t", key="s1_tr0", r=3)
+    return [np.round(q).astype(np.float32), q, pred]
+
+
+def s_round_then_clip_with_fractional_bounds(interp, pads, luts, dev):
+    s = 0
+    for m, k in (("s", "s1_sr0"), ("c", "s1_cr0"), ("t", "s1_tr0")):
+        for r in (0, 1, 2, 3):
+            s += _pass(interp, pads, luts, dev(_img(17)), key=k, mode=m, r=r)
+    f = np.clip(np.round(s / 3), 0.5, 254.5).astype(np.float32)      # ends in {round, clip}, and is NOT a uint8 image: 0.5, 254.5
+    hyper = f / 255.0
+    s2 = _pass(interp, pads, luts, f.transpose((1, 2, 0)), key="s2_sr0", oC=3)
+    return [hyper, s2, f]
+
+
 def _stages(interp, pads, luts, dev, seed):
     import callsite_driver as cd
     img = dev(_img(seed))
@@ -161,8 +192,19 @@ def s_resize_after_operands_changed(interp, pads, luts, dev, resizer):
 
 SCENARIOS = [s_used_twice, s_mutated_after_derivation, s_view_before_iadd, s_operand_overwritten_while_pending,
              s_sum_started_on_the_host, s_int_start_and_reversed_operands, s_stage_epilogue_variants,
-             s_results_dropped_unread, s_three_channel_lut_and_slices, s_copy_semantics]
+             s_results_dropped_unread, s_three_channel_lut_and_slices, s_copy_semantics,
+             s_derived_from_sum_then_accumulated, s_expr_of_expr_then_accumulated, s_round_then_clip_with_fractional_bounds]
+# compared by bit pattern (the sign of zero counts, NaN must be NaN): the scenarios of the deferred sum / expression / epilogue
+BITWISE = {s_stage_epilogue_variants, s_derived_from_sum_then_accumulated, s_expr_of_expr_then_accumulated,
+           s_round_then_clip_with_fractional_bounds}
 RESIZE_SCENARIOS = [s_resize_tails, s_resize_after_operands_changed]
+
+
+def _same_bits(g, w):
+    """equal bit patterns, or NaN on both sides (any payload)"""
+    u = {4: np.uint32, 8: np.uint64}[g.dtype.itemsize]
+    g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+    return (g.view(u) == w.view(u)) | (np.isnan(g) & np.isnan(w))
 
 
 @pytest.mark.parametrize("hw", [(41, 57), (260, 330)])
@@ -187,6 +229,11 @@ def test_lazy_results_equal_numpy_results(env, scenario, device_image, hw):
         gn, wn = np.asarray(g), np.asarray(w)
         assert gn.dtype == wn.dtype and gn.shape == wn.shape, (scenario.__name__, k, gn.dtype, wn.dtype, gn.shape, wn.shape)
         assert np.array_equal(gn, wn), (scenario.__name__, k, float(np.max(np.abs(gn.astype(np.float64) - wn.astype(np.float64)))))
+        if scenario in BITWISE:
+            ok = _same_bits(gn, wn)
+            i = int(np.flatnonzero(~ok.reshape(-1))[0]) if not ok.all() else 0
+            assert ok.all(), (scenario.__name__, k, "%d bit patterns differ; first at %d: got %r, numpy %r"
+                              % (int((~ok).sum()), i, gn.reshape(-1)[i].item(), wn.reshape(-1)[i].item()))
 
 
 @pytest.mark.parametrize("device_image", [True, False])
@@ -208,3 +255,34 @@ def test_lazy_resize_chains_equal_numpy_results(env, scenario, device_image):
             np.testing.assert_allclose(gn, wn, rtol=0, atol=1e-9, err_msg="%s %d" % (scenario.__name__, k))
         else:
             assert np.array_equal(gn, wn), (scenario.__name__, k, int((gn != wn).sum()))
+
+
+@pytest.mark.parametrize("hw", [(41, 57), (260, 330)])
+def test_exact_uint8_tag_is_only_set_when_it_is_true(env, hw):
+    """`exact_u8()` promises array == uint8 / scale for EVERY element (the resamplers read the uint8 form instead of the array):
+    stage epilogues that end in {round, clip} but hold non-integers or NaN must not carry it, and `/ 255` must not pass it on"""
+    import torch
+    interp, pads, resizer, luts = env
+    HW[:] = hw
+
+    def total():
+        s = 0
+        for r in (0, 1, 2, 3):
+            s += _pass(interp, pads, luts, _img(18), r=r)
+        return s
+    with np.errstate(all="ignore"):
+        cases = {"clip round": np.round(np.clip(total() / 3 + 0, 0, 255)).astype(np.float32),
+                 "round clip": np.clip(np.round(total() / 3), 0, 255).astype(np.float32),
+                 "fractional clip, then round": np.round(np.clip(total() / 3, 0.5, 254.5)).astype(np.float32),
+                 "round, then fractional clip": np.clip(np.round(total() / 3), 0.5, 254.5).astype(np.float32),
+                 "NaN through clip and round": np.round(np.clip(total() * 0 / 0, 0, 255)).astype(np.float32),
+                 "inf - inf": np.clip(np.round(total() * 1e300 * 1e300 * 0), 0, 255).astype(np.float32)}
+    for what, f in cases.items():
+        for a in (f, f / 255.0, f.transpose((1, 2, 0))):
+            u = a.exact_u8()
+            if u is not None:
+                assert u[0].dtype == torch.uint8 and tuple(u[0].shape) == a.shape, what
+                scale = torch.full((), u[1], dtype=a.t.dtype, device=a.t.device)          # IEEE division in the array's own dtype
+                assert bool((u[0].to(a.t.dtype) / scale == a.t).all()), what + ": tagged, and not equal to its uint8 form"
+    assert cases["clip round"].exact_u8() is not None and cases["round clip"].exact_u8() is not None      # the stages keep their fast path
+    assert cases["fractional clip, then round"].exact_u8() is not None
