@@ -502,6 +502,41 @@ size_t lerf_imdn_workspace_bytes(int nf, int B, int H, int W);
 int lerf_imdn_fwd_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
                       void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* ---- resize_right.resize (resize_right/resize_right.py:36-127): one axis pass of the separable, anti-aliased, any-scale
+ * resize, and its adjoint.  The tensor is viewed as [outer][n][inner], contiguous:
+ *     out[o][j][i] = sum_k w[j][k] * in[o][src(left[j] + k)][i],   j < n_out, k < taps
+ * src() is the image pad rule `pad_mode` (LERF_PAD_*; a tap in a constant pad contributes w * 0), left[j] the first source
+ * index of output j in unpadded coordinates (get_field_of_view :145-154, may be negative), w the weights normalised per output
+ * (get_weights :208-218); both tables are built by the caller (O(n_out * taps)) and live on the device.  taps is not bounded
+ * by LERF_MAX_SUPPORT.  Products and sums are rounded separately and added in tap order, in the accumulator type.
+ * taps == 0 selects the CSR form, used for the adjoint: row j sums w[e] * in[o][idx[e]][i] over e in
+ * [row_ptr[j], row_ptr[j + 1]), every idx in [0, n_in); build it with lerf_rr_adjoint_csr and run it with n_in / n_out
+ * exchanged: it then maps the output gradient [outer][n_out][inner] to the input gradient [outer][n_in][inner], without
+ * atomics and in a fixed order. */
+typedef struct {
+    int n_in, n_out;
+    int taps;                 /* > 0: forward form (left, w[n_out][taps]); 0: CSR form (row_ptr, idx, w[nnz]) */
+    const int32_t* left;      /* device [n_out] */
+    const int32_t* row_ptr;   /* device [n_out + 1] */
+    const int32_t* idx;       /* device [nnz] */
+    const void* w;            /* device, element type = acc_dtype */
+    int pad_mode;             /* forward form only */
+} lerf_rr_axis_t;
+
+/* in: LERF_U8 / LERF_F32 / LERF_F64; acc_dtype: LERF_F32 / LERF_F64 (the type of w, of the products and of the sum);
+ * out_dtype: acc_dtype, or LERF_U8 with a float64 accumulator: round-half-to-even of the sum clipped to [0, 255]
+ * (np.round(np.clip(x, 0, 255)).astype(np.uint8)).  Other combinations: LERF_EUNSUPPORTED.  in and out must not overlap.
+ * Launches on `stream`, no sync. */
+int lerf_rr_axis(const void* in, int in_dtype, int64_t outer, int64_t inner, const lerf_rr_axis_t* axis, int acc_dtype,
+                 void* out, int out_dtype, void* stream);
+
+/* Host: the adjoint table of a forward axis (HOST pointers).  For every source index s < n_in the outputs that read it:
+ * row_ptr[n_in + 1], idx[nnz] = j, wt[nnz] = w[j][k], in (j, k) order per source; padded taps of the non-constant pad
+ * modes fold onto the source index the pad rule names, taps in a constant pad are dropped.  w / wt: w_dtype = LERF_F32 or
+ * LERF_F64; idx and wt must hold n_out * taps entries.  Returns nnz >= 0, or a negative LERF_E* code. */
+int lerf_rr_adjoint_csr(int n_in, int n_out, int taps, const int32_t* left, const void* w, int w_dtype, int pad_mode,
+                        int32_t* row_ptr, int32_t* idx, void* wt);
+
 /* ---- calibration (bench.py roofline_lds): `workgroups` x 1024 threads, each wave issuing 10 x `iters` ds_read_b32 gathers
  * into a 134-KB LDS table -- pattern 0: random addresses (the rate a data-dependent LUT gather gets), pattern 1:
  * conflict-free.  The caller times the launch (one workgroup per CU: wave-gathers per CU = 160 x iters) and owns `sink`

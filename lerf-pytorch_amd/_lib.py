@@ -50,6 +50,7 @@ EXPORTS = [
     "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd",
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_srnet_fwd_f32", "lerf_srnet_bwd_workspace_bytes", "lerf_srnet_bwd_f32",
     "lerf_imdn_weight_floats", "lerf_imdn_workspace_bytes", "lerf_imdn_fwd_f32",
+    "lerf_rr_axis", "lerf_rr_adjoint_csr",
     "lerf_ubench_lds_gather",
 ]
 
@@ -117,6 +118,11 @@ class WarpGeo(C.Structure):
         ("pad_mode", C.c_int),
         ("out_y0", C.c_int), ("out_x0", C.c_int), ("src_y0", C.c_int),       # ABI 7: a rectangle of the output from a band of the source
     ]
+
+
+class RrAxis(C.Structure):         # lerf_rr_axis_t
+    _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("taps", C.c_int), ("left", C.c_void_p), ("row_ptr", C.c_void_p),
+                ("idx", C.c_void_p), ("w", C.c_void_p), ("pad_mode", C.c_int)]
 
 
 _lib = None
@@ -226,6 +232,9 @@ def lib():
     L.lerf_imdn_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.lerf_imdn_fwd_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.lerf_rr_axis.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(RrAxis), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.lerf_rr_adjoint_csr.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)

@@ -302,5 +302,38 @@ inline int warp_tile_boxes(const double minv[9], int pad_r_lo, int pad_c_lo, int
     return LERF_OK;
 }
 
+// Adjoint table of one axis pass of the separable resize (lerf_rr_axis): for every source index s of the n_in inputs the
+// outputs j that read it and their weights, CSR: row_ptr[n_in + 1], idx[nnz] = j, wt[nnz] = w[j][k], entries of one source
+// in (j, k) order.  A padded tap of a non-constant pad mode folds onto the source index the pad rule names (source_tap);
+// a tap in a constant pad has no source and is dropped.  w / wt: float32 or float64 (w_dtype), idx and wt sized for
+// n_out * taps entries.  Returns nnz, or a negative LERF_E* code.
+inline int rr_adjoint_csr(int n_in, int n_out, int taps, const int32_t* left, const void* w, int w_dtype, int pad_mode,
+                          int32_t* row_ptr, int32_t* idx, void* wt) {
+    if (n_in < 1 || n_out < 1 || taps < 1 || !left || !w || !row_ptr || !idx || !wt) return LERF_EINVAL;
+    if (w_dtype != LERF_F32 && w_dtype != LERF_F64) return LERF_EINVAL;
+    if (pad_mode < LERF_PAD_CONSTANT || pad_mode > LERF_PAD_WRAP) return LERF_EINVAL;
+    if ((int64_t)n_out * taps > 0x7fffffff) return LERF_EUNSUPPORTED;
+    for (int s = 0; s <= n_in; ++s) row_ptr[s] = 0;
+    for (int j = 0; j < n_out; ++j)
+        for (int k = 0; k < taps; ++k) {
+            const SourceTap t = source_tap(left[j] + k, n_in, pad_mode);
+            if (!t.z) ++row_ptr[t.s + 1];
+        }
+    for (int s = 0; s < n_in; ++s) row_ptr[s + 1] += row_ptr[s];
+    const int nnz = row_ptr[n_in];
+    for (int j = 0; j < n_out; ++j)                     // row_ptr[s] serves as the cursor of source s ...
+        for (int k = 0; k < taps; ++k) {
+            const SourceTap t = source_tap(left[j] + k, n_in, pad_mode);
+            if (t.z) continue;
+            const int e = row_ptr[t.s]++;
+            idx[e] = j;
+            if (w_dtype == LERF_F64) ((double*)wt)[e] = ((const double*)w)[(int64_t)j * taps + k];
+            else ((float*)wt)[e] = ((const float*)w)[(int64_t)j * taps + k];
+        }
+    for (int s = n_in; s > 0; --s) row_ptr[s] = row_ptr[s - 1];      // ... and now holds the start of s + 1: shift back
+    row_ptr[0] = 0;
+    return nnz;
+}
+
 }  // namespace host
 }  // namespace lerf

@@ -26,4 +26,10 @@ int lerf_warp_tile_boxes(const lerf_warp_geo_t* geo, int H, int W, int32_t* boxe
     if (!geo || geo->S != 2) return LERF_EINVAL;
     return host::warp_tile_boxes(geo->minv, geo->pad_r_lo, geo->pad_c_lo, H, W, geo->out_h, geo->out_w, 64, boxes);
 }
+int lerf_rr_adjoint_csr(int n_in, int n_out, int taps, const int32_t* left, const void* w, int w_dtype, int pad_mode,
+                        int32_t* row_ptr, int32_t* idx, void* wt) {
+    return host::rr_adjoint_csr(n_in, n_out, taps, left, w, w_dtype, pad_mode, row_ptr, idx, wt);
+}
+// device entry point: no kernels in this build
+int lerf_rr_axis(const void*, int, int64_t, int64_t, const lerf_rr_axis_t*, int, void*, int, void*) { return LERF_ENODEVICE; }
 }

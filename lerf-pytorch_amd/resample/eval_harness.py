@@ -129,6 +129,12 @@ def warp_table(etr, datasets=("Set5",), modes=("isc", "osc")):
     return lines
 
 
+def _scale_pair(text):
+    """'2x2' / '1.5x2' -> (h, w); whole numbers stay ints, so the default table prints as before"""
+    from .make_lr import parse_pair
+    return tuple(int(v) if float(v).is_integer() else v for v in parse_pair(text))
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("task", choices=["sr", "warp"])
@@ -143,6 +149,8 @@ def parse(argv=None):
     ap.add_argument("--testDir", type=str, default=None)
     ap.add_argument("--resultRoot", type=str, default="")
     ap.add_argument("--datasets", type=str, nargs="+", default=["Set5"])
+    ap.add_argument("--scales", type=_scale_pair, nargs="+", default=[(2, 2), (3, 3), (4, 4)],
+                    help="sr: the scale pairs of the table, e.g. 2x2 1.5x2 (folders rrLR_X{h:.2f}_{w:.2f}; resample/make_lr.py makes them)")
     opt = ap.parse_args(argv)
     if opt.testDir is None:
         opt.testDir = "./data/rrBenchmark" if opt.task == "sr" else "./data/WarpBenchmark"
@@ -153,7 +161,7 @@ def main(argv=None):
     opt = parse(argv)
     luts = LutSet.from_dir(opt.expDir, linear=opt.linear, lut_name=opt.lutName, modes=opt.modes, modes2=opt.modes2)
     etr = Eltr(opt, luts)
-    for line in (sr_table(etr, opt.datasets) if opt.task == "sr" else warp_table(etr, opt.datasets)):
+    for line in (sr_table(etr, opt.datasets, opt.scales) if opt.task == "sr" else warp_table(etr, opt.datasets)):
         print(line)
 
 
