@@ -502,6 +502,33 @@ size_t lerf_imdn_workspace_bytes(int nf, int B, int H, int W);
 int lerf_imdn_fwd_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
                       void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* ---- training LeRF-Net (train_model.py with model IMDN2): the saving forward and the backward of one IMDN_RTC net, the
+ * trainable twin of lerf_imdn_fwd_f32.  weights, nf, in_nc, out_nc, x, B, H, W, post, out: as lerf_imdn_fwd_f32, the same
+ * supported set (else LERF_EUNSUPPORTED; 0 from the size queries).
+ * lerf_imdn_fwd_train_f32: out is bit-equal to lerf_imdn_fwd_f32's for the same arguments.  saved: device memory of at
+ * least lerf_imdn_saved_bytes(nf, in_nc, out_nc, B, H, W) bytes ((23.25 nf + out_nc) floats per pixel: fea, every module's
+ * output, concatenated distilled channels and three remaining-channel planes, the upsampler conv's input, the raw output
+ * that decides the clamp mask); it needs no other workspace.  Hand saved, unchanged, with the same weights, x, shape and
+ * post to lerf_imdn_bwd_f32.
+ * lerf_imdn_bwd_f32: what autograd derives for the reference module and IMDN2.predict's clamp and affine (post 1: 127 where
+ * -1 <= y <= 1, post 2: 1/2 there, 0 elsewhere; LeakyReLU(0.05)'s slope where the activation is <= 0).
+ * grad_out: float32 NCHW [B][out_nc][H][W].  grad_weights: lerf_imdn_weight_floats floats in the packed layout; every float
+ * is written exactly once: OVERWRITTEN, not accumulated into (no need to zero it).  grad_x: float32 NCHW [B][in_nc][H][W],
+ * overwritten, or NULL to skip the input gradient.  workspace: device memory of at least
+ * lerf_imdn_bwd_workspace_bytes(nf, in_nc, out_nc, B, H, W) bytes, contents arbitrary, used by this call only (gradient
+ * planes, and per-workgroup weight-gradient slabs that a second pass sums in slab order).
+ * A short saved or workspace, a null pointer (grad_x excepted) or a bad shape or post is LERF_EINVAL, and nothing is
+ * written.  Float32 products and sums on the matrix cores (v_mfma_f32_16x16x4_f32), no float atomics: repeated calls give
+ * bitwise-identical gradients, and grad_x of image b equals that of image b run alone.  Launches on `stream`, no sync,
+ * no allocation, no global state. */
+size_t lerf_imdn_saved_bytes(int nf, int in_nc, int out_nc, int B, int H, int W);
+int lerf_imdn_fwd_train_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                            void* saved, size_t saved_bytes, float* out, void* stream);
+size_t lerf_imdn_bwd_workspace_bytes(int nf, int in_nc, int out_nc, int B, int H, int W);
+int lerf_imdn_bwd_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                      const void* saved, size_t saved_bytes, const float* grad_out, float* grad_weights, float* grad_x,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- resize_right.resize (resize_right/resize_right.py:36-127): one axis pass of the separable, anti-aliased, any-scale
  * resize, and its adjoint.  The tensor is viewed as [outer][n][inner], contiguous:
  *     out[o][j][i] = sum_k w[j][k] * in[o][src(left[j] + k)][i],   j < n_out, k < taps

@@ -50,6 +50,7 @@ EXPORTS = [
     "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd",
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_srnet_fwd_f32", "lerf_srnet_bwd_workspace_bytes", "lerf_srnet_bwd_f32",
     "lerf_imdn_weight_floats", "lerf_imdn_workspace_bytes", "lerf_imdn_fwd_f32",
+    "lerf_imdn_saved_bytes", "lerf_imdn_fwd_train_f32", "lerf_imdn_bwd_workspace_bytes", "lerf_imdn_bwd_f32",
     "lerf_rr_axis", "lerf_rr_adjoint_csr",
     "lerf_ubench_lds_gather",
 ]
@@ -232,6 +233,14 @@ def lib():
     L.lerf_imdn_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.lerf_imdn_fwd_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.lerf_imdn_saved_bytes.restype = C.c_size_t
+    L.lerf_imdn_saved_bytes.argtypes = [C.c_int] * 6
+    L.lerf_imdn_fwd_train_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.lerf_imdn_bwd_workspace_bytes.restype = C.c_size_t
+    L.lerf_imdn_bwd_workspace_bytes.argtypes = [C.c_int] * 6
+    L.lerf_imdn_bwd_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.lerf_rr_axis.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(RrAxis), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.lerf_rr_adjoint_csr.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p]

@@ -405,6 +405,37 @@ int lerf_imdn_fwd_f32(const float* weights, int nf, int in_nc, int out_nc, const
     return rc != LERF_OK ? rc : check_launch();
 }
 
+size_t lerf_imdn_saved_bytes(int nf, int in_nc, int out_nc, int B, int H, int W) {
+    return imdn_args(nf, in_nc, out_nc, B, H, W) == LERF_OK ? imdn_saved_bytes(nf, out_nc, B, H, W) : 0;
+}
+
+int lerf_imdn_fwd_train_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                            void* saved, size_t saved_bytes, float* out, void* stream) {
+    int rc = imdn_args(nf, in_nc, out_nc, B, H, W);
+    if (rc != LERF_OK) return rc;
+    if (!weights || !x || !out || !saved || post < 0 || post > 2) return LERF_EINVAL;
+    if (saved_bytes < imdn_saved_bytes(nf, out_nc, B, H, W)) return LERF_EINVAL;
+    rc = launch_imdn_fwd_train(weights, nf, in_nc, out_nc, x, B, H, W, post, saved, out, as_stream(stream));
+    return rc != LERF_OK ? rc : check_launch();
+}
+
+size_t lerf_imdn_bwd_workspace_bytes(int nf, int in_nc, int out_nc, int B, int H, int W) {
+    return imdn_args(nf, in_nc, out_nc, B, H, W) == LERF_OK ? imdn_bwd_workspace_bytes(nf, B, H, W) : 0;
+}
+
+int lerf_imdn_bwd_f32(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                      const void* saved, size_t saved_bytes, const float* grad_out, float* grad_weights, float* grad_x,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = imdn_args(nf, in_nc, out_nc, B, H, W);
+    if (rc != LERF_OK) return rc;
+    if (!weights || !x || !saved || !grad_out || !grad_weights || !workspace || post < 0 || post > 2) return LERF_EINVAL;
+    if (saved_bytes < imdn_saved_bytes(nf, out_nc, B, H, W) || workspace_bytes < imdn_bwd_workspace_bytes(nf, B, H, W))
+        return LERF_EINVAL;
+    rc = launch_imdn_bwd(weights, nf, in_nc, out_nc, x, B, H, W, post, const_cast<void*>(saved), grad_out, grad_weights, grad_x,
+                         workspace, as_stream(stream));
+    return rc != LERF_OK ? rc : check_launch();
+}
+
 int lerf_ubench_lds_gather(int pattern, int iters, int workgroups, uint32_t* sink, void* stream) {
     if ((pattern != 0 && pattern != 1) || iters < 1 || workgroups < 1 || !sink) return LERF_EINVAL;
     int rc = launch_ubench_lds_gather(pattern, iters, workgroups, sink, as_stream(stream));

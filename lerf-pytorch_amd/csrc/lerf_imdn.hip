@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lerf_imdn_conv.h"
 #include "lerf_imdn_layout.h"
 #include "lerf_kernels.h"
 
@@ -28,22 +29,6 @@ constexpr int PIX = 128;             // output pixels per workgroup (32 per wave
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 __device__ inline floatx4 mfma4(float a, float b, floatx4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// a [B][C][H][W] tensor in any channel order: element (b, y, x, c) at p + b sb + (y W + x) sp + c sc
-struct View {
-    float* p;
-    int64_t sb, sp, sc;
-};
-
-struct ConvArgs {
-    const float* w;                  // [cout][cin][KK] (PyTorch order), then bias[cout]
-    int cin, cout, split;            // channels n < split go to lo (channel n), the others to hi (channel n - split)
-    View in, lo, hi;
-    const float* res;                // nullable: added after the activation, laid out like lo
-    int act, post;                   // act: LeakyReLU(0.05); post: 0 raw, 1 clamp * 127 + 127, 2 clamp / 2 + 1/2
-    int H, W;
-    int64_t n_pix;                   // B H W
-};
 
 template <int NB, int KK>
 __global__ void __launch_bounds__(NT) imdn_conv_kernel(ConvArgs a) {
@@ -132,6 +117,11 @@ void launch_conv(const ConvArgs& a, hipStream_t st) {
     }
 }
 
+void launch_conv(const ConvArgs& a, bool k3, hipStream_t st) {
+    if (k3) launch_conv<9>(a, st);
+    else launch_conv<1>(a, st);
+}
+
 }  // namespace imdn
 
 size_t imdn_weight_floats(int nf, int in_nc, int out_nc) { return (size_t)imdn::weight_floats(nf, in_nc, out_nc); }
@@ -154,8 +144,7 @@ int launch_imdn_fwd(const float* weights, int nf, int in_nc, int out_nc, const f
     auto conv = [&](int off, int cin, int cout, int split, View in, View lo, View hi, const float* res, int act, int pst,
                     bool k3) {
         ConvArgs a{weights + off, cin, cout, split, in, lo, hi, res, act, pst, H, W, P};
-        if (k3) launch_conv<9>(a, st);
-        else launch_conv<1>(a, st);
+        launch_conv(a, k3, st);
     };
     const View none{nullptr, 0, 0, 0};
     // fea_conv, reading the NCHW input

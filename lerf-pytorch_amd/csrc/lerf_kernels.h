@@ -116,6 +116,13 @@ size_t imdn_weight_floats(int nf, int in_nc, int out_nc);
 size_t imdn_workspace_bytes(int nf, int B, int H, int W);
 int launch_imdn_fwd(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
                     void* workspace, float* out, hipStream_t st);
+// lerf_imdn_bwd.hip
+size_t imdn_saved_bytes(int nf, int out_nc, int B, int H, int W);
+size_t imdn_bwd_workspace_bytes(int nf, int B, int H, int W);
+int launch_imdn_fwd_train(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                          void* saved, float* out, hipStream_t st);
+int launch_imdn_bwd(const float* weights, int nf, int in_nc, int out_nc, const float* x, int B, int H, int W, int post,
+                    void* saved, const float* grad_out, float* grad_weights, float* grad_x, void* workspace, hipStream_t st);
 
 // lerf_ubench.hip
 int launch_ubench_lds_gather(int pattern, int iters, int blocks, uint32_t* sink, hipStream_t st);

@@ -313,16 +313,17 @@ def mulut_predict(model_G, x, stage=1, inC=1):
     return model_G.predict(x, stage=stage)
 
 
-def lutft_step(model_G, resizer, im, lb, opt_G=None, linear=False, norm=255, featC=1, reduce_grads=None):
+def lutft_step(model_G, resizer, im, lb, opt_G=None, linear=False, norm=255, featC=1, reduce_grads=None, inC=1):
     """One LUT fine-tuning iteration, train_model.py:416-442 (`--lutft --twoStage`): stage 1 -> stage 2 -> spatially
     varying resize -> clamp -> MSE against the HR patch; backward; optimiser step.  `resizer` is a torch-facing
     resampler with set_shape already called for im's shape.  `reduce_grads(model)` (e.g. dist.allreduce_grads) runs
-    between backward and step for data-parallel training.  Returns the loss tensor."""
+    between backward and step for data-parallel training.  `inC` is the reference's opt.inC: 1 shows the model one channel
+    at a time, 3 (LeRF-Net: IMDN2(opt, inC=3, outC=3), featC=3) all of them.  Returns the loss tensor."""
     if opt_G is not None:
         opt_G.zero_grad()
-    feat_im = mulut_predict(model_G, im, 1)
+    feat_im = mulut_predict(model_G, im, 1, inC)
     hyper_in = feat_im / float(norm)
-    pred_hyper = mulut_predict(model_G, hyper_in, 2)
+    pred_hyper = mulut_predict(model_G, hyper_in, 2, inC)
     if linear:
         pred = resizer.resize(feat_im, pred_hyper)
     else:
@@ -366,16 +367,58 @@ class IMDModule_speed(nn.Module):
         self.c5 = _conv_layer(self.distilled_channels * 4, in_channels, 1)
 
 
+class _IMDNFn(torch.autograd.Function):
+    """One IMDN_RTC net with its backward (lerf_imdn_fwd_train_f32 / lerf_imdn_bwd_f32); the weights arrive packed
+    (torch.cat of the parameters, so autograd hands each parameter its slice of the packed gradient)."""
+
+    @staticmethod
+    def forward(ctx, flat, x, nf, in_nc, out_nc, post):
+        if not (flat.is_cuda and x.is_cuda):
+            raise ValueError("IMDN2 runs on the GPU (there is no CPU path)")
+        w = flat.detach().contiguous().float()
+        xin = x.detach().contiguous().float()
+        B, _, H, W = xin.shape
+        L = _lib.lib()
+        nbytes = L.lerf_imdn_saved_bytes(nf, in_nc, out_nc, B, H, W)
+        saved = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=x.device)
+        out = torch.empty((B, out_nc, H, W), dtype=torch.float32, device=x.device)
+        _lib.check(L.lerf_imdn_fwd_train_f32(C.c_void_p(w.data_ptr()), nf, in_nc, out_nc, C.c_void_p(xin.data_ptr()), B, H, W,
+                                             int(post), C.c_void_p(saved.data_ptr()), nbytes, C.c_void_p(out.data_ptr()),
+                                             _lib.current_stream()), "lerf_imdn_fwd_train_f32")
+        ctx.save_for_backward(w, xin, saved)
+        ctx.meta = (nf, in_nc, out_nc, int(post), nbytes)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        w, x, saved = ctx.saved_tensors
+        nf, in_nc, out_nc, post, nbytes = ctx.meta
+        B, _, H, W = x.shape
+        g = grad_out.contiguous().float()
+        gw = torch.empty_like(w)                                  # overwritten, every float
+        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        L = _lib.lib()
+        ws_bytes = L.lerf_imdn_bwd_workspace_bytes(nf, in_nc, out_nc, B, H, W)
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=x.device)
+        _lib.check(L.lerf_imdn_bwd_f32(C.c_void_p(w.data_ptr()), nf, in_nc, out_nc, C.c_void_p(x.data_ptr()), B, H, W, post,
+                                       C.c_void_p(saved.data_ptr()), nbytes, C.c_void_p(g.data_ptr()), C.c_void_p(gw.data_ptr()),
+                                       C.c_void_p(gx.data_ptr() if gx is not None else None), C.c_void_p(ws.data_ptr()), ws_bytes,
+                                       _lib.current_stream()), "lerf_imdn_bwd_f32")
+        return (gw if ctx.needs_input_grad[0] else None), gx, None, None, None, None
+
+
 class IMDN_RTC(nn.Module):
     """model.py:512-527 at upscale 1 (the only scale IMDN2 uses): fea_conv, ShortcutBlock(5 x IMDModule_speed +
-    LR_conv), upsampler conv + PixelShuffle(1).  Parameters under the reference's `model.*` keys; the forward runs in
-    liblerf_hip.so (lerf_imdn_fwd_f32), on the GPU, without autograd."""
+    LR_conv), upsampler conv + PixelShuffle(1).  Parameters under the reference's `model.*` keys; the net runs in
+    liblerf_hip.so, on the GPU: lerf_imdn_fwd_f32 without autograd, and after enable_backward() the trainable pair
+    lerf_imdn_fwd_train_f32 / lerf_imdn_bwd_f32 whenever autograd is recording."""
 
     def __init__(self, in_nc=3, nf=12, num_modules=5, out_nc=3, upscale=1):
         super(IMDN_RTC, self).__init__()
         if upscale != 1 or num_modules != 5:
             raise NotImplementedError("IMDN_RTC is implemented at upscale 1 with 5 modules (IMDN2's configuration)")
         self.nf, self.in_nc, self.out_nc = nf, in_nc, out_nc
+        self._hip_backward = False
         rb_blocks = [IMDModule_speed(in_channels=nf) for _ in range(num_modules)]
         self.model = nn.Sequential(_conv_layer(in_nc, nf, 3), ShortcutBlock(nn.Sequential(*rb_blocks, _conv_layer(nf, nf, 1))),
                                    _conv_layer(nf, out_nc, 3), nn.PixelShuffle(1))
@@ -384,14 +427,26 @@ class IMDN_RTC(nn.Module):
         """the parameters flattened in state_dict order: the packed layout of lerf_imdn_fwd_f32"""
         return torch.cat([p.detach().reshape(-1) for p in self.parameters()]).float().contiguous()
 
+    def enable_backward(self, flag=True):
+        """Opt in to (or out of) training: with it, `run` under autograd goes through lerf_imdn_fwd_train_f32 and
+        lerf_imdn_bwd_f32; without it (the default) autograd is refused.  torch.no_grad() takes the inference path
+        either way."""
+        self._hip_backward = bool(flag)
+        return self
+
     def run(self, x, post=0):
         """[B, in_nc, H, W] -> [B, out_nc, H, W]: the net (post 0), or predict's clamp and affine fused (1, 2)"""
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("IMDN2 has no backward here: run it under torch.no_grad() (training is out of scope)")
+        recording = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if recording and not self._hip_backward:
+            raise NotImplementedError("IMDN2 refuses autograd by default: run it under torch.no_grad(), or opt in to "
+                                      "training with enable_backward()")
         if not x.is_cuda:
             raise ValueError("IMDN2 runs on the GPU (there is no CPU path)")
         if x.dim() != 4 or x.shape[1] != self.in_nc:
             raise ValueError("expected [B, %d, H, W], got %s" % (self.in_nc, tuple(x.shape)))
+        if recording:
+            flat = torch.cat([p.reshape(-1) for p in self.parameters()])
+            return _IMDNFn.apply(flat, x, self.nf, self.in_nc, self.out_nc, int(post))
         w = self.packed().to(x.device)
         xin = x.detach().contiguous().float()
         B, _, H, W = xin.shape
@@ -411,13 +466,20 @@ class IMDN_RTC(nn.Module):
 class IMDN2(nn.Module):
     """LeRF-Net / LeRF-Net++ (model.py:530-545): stage1 in_nc -> inC, stage2 inC -> inC * outC, both IMDN_RTC nets of
     width opt.nf.  predict(x, 1) = clamp(y1, -1, 1) * (norm // 2) + norm // 2, predict(x, 2) = clamp(y2, -1, 1) / 2 + 1/2.
-    Forward only (there is no backward here): evaluate under torch.no_grad(), as the reference's evaluation does."""
+    Autograd is refused by default (evaluate under torch.no_grad(), as the reference's evaluation does);
+    enable_backward() opts both stages in to training, e.g. lutft_step(model.enable_backward(), resizer, im, lb, opt)."""
 
     def __init__(self, opt, inC=1, outC=1):
         super(IMDN2, self).__init__()
         self.norm = opt.norm
         self.stage1 = IMDN_RTC(nf=opt.nf, in_nc=inC, out_nc=inC, upscale=1)
         self.stage2 = IMDN_RTC(nf=opt.nf, in_nc=inC, out_nc=inC * outC, upscale=1)
+
+    def enable_backward(self, flag=True):
+        """both stages' IMDN_RTC.enable_backward"""
+        self.stage1.enable_backward(flag)
+        self.stage2.enable_backward(flag)
+        return self
 
     def predict(self, x, stage=1):
         if stage == 2:  # hyper: [0-1]
