@@ -564,6 +564,32 @@ int lerf_rr_axis(const void* in, int in_dtype, int64_t outer, int64_t inner, con
 int lerf_rr_adjoint_csr(int n_in, int n_out, int taps, const int32_t* left, const void* w, int w_dtype, int pad_mode,
                         int32_t* row_ptr, int32_t* idx, void* wt);
 
+/* ---- the training batch of the DIV2K provider (resample/data.py:107-165).  The decoded train images live once in a device
+ * pool of uint8 HWC RGB images; a sample is a descriptor, and one launch fills the whole batch:
+ *     im [B][C][sz][sz], lb [B][C][hsz][hsz] float32, dense
+ * Output (b, c) is, in the reference's order: crop rows [i, i + n), columns [j, j + n) of the image (n = sz at (li, lj) of
+ * the LR image, hsz at (hi, hj) of the HR image); channel `chan` for C == 1, channel c for C == 3; np.fliplr if `fliplr`;
+ * np.flipud if `flipud`; np.rot90(., k); float32(u8) / 255.0f as an IEEE division.  `noise` (device float32 [B][C][sz][sz], or
+ * NULL) is added to im after the division, in float32 (:163).
+ * Descriptors are read by the kernel from DEVICE memory (`desc`, B entries).  `desc_host` is the same array in host memory,
+ * or NULL: when given, every entry is checked before the launch and a crop that leaves its image, an image that leaves the
+ * pool (off < 0, off + h * pitch > pool_bytes, pitch < 3 * w), chan outside 0..2 (C == 1) or k outside 0..3 is LERF_EINVAL
+ * with nothing launched.  The kernel repeats the same check per sample and never reads outside [off, off + h * pitch): a
+ * sample whose descriptor fails it gets im and lb filled with zeros.  Null pool / desc / im / lb, pool_bytes <= 0, B <= 0,
+ * C not 1 or 3, sz <= 0 or hsz <= 0: LERF_EINVAL.  One launch on `stream`, no sync, no allocation. */
+typedef struct {
+    int64_t lr_off, hr_off;          /* byte offset of the image's first pixel in the pool */
+    int32_t lr_h, lr_w, lr_pitch;    /* rows, columns, bytes between rows (>= 3 * w) */
+    int32_t hr_h, hr_w, hr_pitch;
+    int32_t li, lj, hi, hj;          /* crop origins (row, column) */
+    int32_t chan;                    /* 0..2 for C == 1, ignored for C == 3 */
+    int32_t fliplr, flipud;          /* 0 / 1 */
+    int32_t k;                       /* np.rot90 quarter turns, 0..3 */
+} lerf_patch_desc_t;
+
+int lerf_patch_batch_u8(const uint8_t* pool, int64_t pool_bytes, const lerf_patch_desc_t* desc, const lerf_patch_desc_t* desc_host,
+                        int B, int C, int sz, int hsz, const float* noise, float* im, float* lb, void* stream);
+
 /* ---- calibration (bench.py roofline_lds): `workgroups` x 1024 threads, each wave issuing 10 x `iters` ds_read_b32 gathers
  * into a 134-KB LDS table -- pattern 0: random addresses (the rate a data-dependent LUT gather gets), pattern 1:
  * conflict-free.  The caller times the launch (one workgroup per CU: wave-gathers per CU = 160 x iters) and owns `sink`

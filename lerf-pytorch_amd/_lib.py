@@ -51,7 +51,7 @@ EXPORTS = [
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_srnet_fwd_f32", "lerf_srnet_bwd_workspace_bytes", "lerf_srnet_bwd_f32",
     "lerf_imdn_weight_floats", "lerf_imdn_workspace_bytes", "lerf_imdn_fwd_f32",
     "lerf_imdn_saved_bytes", "lerf_imdn_fwd_train_f32", "lerf_imdn_bwd_workspace_bytes", "lerf_imdn_bwd_f32",
-    "lerf_rr_axis", "lerf_rr_adjoint_csr",
+    "lerf_rr_axis", "lerf_rr_adjoint_csr", "lerf_patch_batch_u8",
     "lerf_ubench_lds_gather",
 ]
 
@@ -124,6 +124,18 @@ class WarpGeo(C.Structure):
 class RrAxis(C.Structure):         # lerf_rr_axis_t
     _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("taps", C.c_int), ("left", C.c_void_p), ("row_ptr", C.c_void_p),
                 ("idx", C.c_void_p), ("w", C.c_void_p), ("pad_mode", C.c_int)]
+
+
+class PatchDesc(C.Structure):      # lerf_patch_desc_t
+    _fields_ = [("lr_off", C.c_int64), ("hr_off", C.c_int64), ("lr_h", C.c_int32), ("lr_w", C.c_int32), ("lr_pitch", C.c_int32),
+                ("hr_h", C.c_int32), ("hr_w", C.c_int32), ("hr_pitch", C.c_int32), ("li", C.c_int32), ("lj", C.c_int32),
+                ("hi", C.c_int32), ("hj", C.c_int32), ("chan", C.c_int32), ("fliplr", C.c_int32), ("flipud", C.c_int32),
+                ("k", C.c_int32)]
+
+
+# the same layout as a numpy record: a batch of descriptors is one array, uploaded in one copy
+PATCH_DESC_DTYPE = np.dtype([(n, np.int64 if t is C.c_int64 else np.int32) for n, t in PatchDesc._fields_])
+assert PATCH_DESC_DTYPE.itemsize == C.sizeof(PatchDesc) == 72
 
 
 _lib = None
@@ -244,6 +256,8 @@ def lib():
     L.lerf_rr_axis.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(RrAxis), C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.lerf_rr_adjoint_csr.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
+    L.lerf_patch_batch_u8.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)

@@ -768,3 +768,29 @@ def rect_copy(frames_u8, staging_u8, rects, to_staging):
     with _lib.on_device(frames_u8):
         _lib.check(_lib.lib().lerf_rect_copy_u8(frames_u8.data_ptr(), N, fh, fw, Cn, staging_u8.data_ptr(), arr, len(rects),
                                                 1 if to_staging else 0, _lib.current_stream()), "lerf_rect_copy_u8")
+
+
+def patch_batch(pool_u8, desc, C_out, sz, hsz, noise=None, desc_dev=None, im=None, lb=None):
+    """lerf_patch_batch_u8: the DIV2K training batch (im [B,C,sz,sz], lb [B,C,hsz,hsz], float32) cut from a device pool of
+    uint8 HWC images in ONE launch.  `desc`: a numpy record array of _lib.PATCH_DESC_DTYPE, checked on the host and uploaded
+    here (or already on the device as `desc_dev`, uint8 [B * 72]); `noise`: device float32 [B,C,sz,sz] added to im."""
+    torch = _torch()
+    if pool_u8.dtype != torch.uint8 or not pool_u8.is_cuda or not pool_u8.is_contiguous():
+        raise ValueError("the pool must be a contiguous uint8 tensor on the GPU")
+    desc = np.ascontiguousarray(desc, dtype=_lib.PATCH_DESC_DTYPE).reshape(-1)
+    B = int(desc.shape[0])
+    dev = pool_u8.device
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(desc.view(np.uint8)).to(dev)
+    if noise is not None and (noise.dtype != torch.float32 or noise.device != dev or not noise.is_contiguous()
+                              or tuple(noise.shape) != (B, C_out, sz, sz)):
+        raise ValueError("noise must be a contiguous float32 [B,C,sz,sz] tensor on the pool's device")
+    if im is None:
+        im = torch.empty((B, C_out, sz, sz), dtype=torch.float32, device=dev)
+    if lb is None:
+        lb = torch.empty((B, C_out, hsz, hsz), dtype=torch.float32, device=dev)
+    with _lib.on_device(pool_u8):
+        _lib.check(_lib.lib().lerf_patch_batch_u8(pool_u8.data_ptr(), pool_u8.numel(), desc_dev.data_ptr(), desc.ctypes.data, B,
+                                                  int(C_out), int(sz), int(hsz), noise.data_ptr() if noise is not None else None,
+                                                  im.data_ptr(), lb.data_ptr(), _lib.current_stream()), "lerf_patch_batch_u8")
+    return im, lb

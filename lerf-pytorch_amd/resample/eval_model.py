@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from .. import metrics
-from ..resize_right.resize_right2d_torch import NearestWarp2dTorch, SteeringGaussianResize2dTorch, SteeringGaussianWarp2dTorch
+from ..resize_right.resize_right2d_torch import (AmplifiedLinearResize2dTorch, AmplifiedLinearWarp2dTorch, NearestWarp2dTorch,
+                                                  SteeringGaussianResize2dTorch, SteeringGaussianWarp2dTorch)
 from . import model as M
 from .eval_harness import _load_matrix, _load_rgb
 
@@ -37,7 +38,10 @@ def mulut_predict(model_G, x, stage, opt):
 
 
 def split_hyper(pred_hyper, opt):
-    """the three hyper-parameter maps: interleaved ([0::3], [1::3], [2::3]) for inC 1, blocks of featC for inC 3"""
+    """the three hyper-parameter maps: interleaved ([0::3], [1::3], [2::3]) for inC 1, blocks of featC for inC 3; the one
+    amplitude map of the linear resampling function (train_model.py:116-118)"""
+    if getattr(opt, "linear", False):
+        return (pred_hyper,)
     if opt.inC == 1:
         return pred_hyper[:, 0::3], pred_hyper[:, 1::3], pred_hyper[:, 2::3]
     f = opt.featC
@@ -51,8 +55,12 @@ class Eltr:
         self.opt = opt
         self.model_G = model_G
         self.norm = 255
-        self.resizer = SteeringGaussianResize2dTorch(support_sz=opt.suppSize, max_sigma=opt.maxSigma)
-        self.warper = SteeringGaussianWarp2dTorch(support_sz=opt.suppSize, max_sigma=opt.maxSigma)
+        if getattr(opt, "linear", False):
+            self.resizer = AmplifiedLinearResize2dTorch(support_sz=opt.suppSize)
+            self.warper = AmplifiedLinearWarp2dTorch(support_sz=opt.suppSize)
+        else:
+            self.resizer = SteeringGaussianResize2dTorch(support_sz=opt.suppSize, max_sigma=opt.maxSigma)
+            self.warper = SteeringGaussianWarp2dTorch(support_sz=opt.suppSize, max_sigma=opt.maxSigma)
         self.nn_warper = NearestWarp2dTorch()
 
     def _files(self, dataset):

@@ -313,16 +313,21 @@ def mulut_predict(model_G, x, stage=1, inC=1):
     return model_G.predict(x, stage=stage)
 
 
-def lutft_step(model_G, resizer, im, lb, opt_G=None, linear=False, norm=255, featC=1, reduce_grads=None, inC=1):
+def lutft_step(model_G, resizer, im, lb, opt_G=None, linear=False, norm=255, featC=1, reduce_grads=None, inC=1, two_stage=True):
     """One LUT fine-tuning iteration, train_model.py:416-442 (`--lutft --twoStage`): stage 1 -> stage 2 -> spatially
     varying resize -> clamp -> MSE against the HR patch; backward; optimiser step.  `resizer` is a torch-facing
     resampler with set_shape already called for im's shape.  `reduce_grads(model)` (e.g. dist.allreduce_grads) runs
     between backward and step for data-parallel training.  `inC` is the reference's opt.inC: 1 shows the model one channel
-    at a time, 3 (LeRF-Net: IMDN2(opt, inC=3, outC=3), featC=3) all of them.  Returns the loss tensor."""
+    at a time, 3 (LeRF-Net: IMDN2(opt, inC=3, outC=3), featC=3) all of them.  `two_stage=False` is the reference without
+    --twoStage (:423-425): no pre-filter stage, the resampler reads round(im * norm).  Returns the loss tensor."""
     if opt_G is not None:
         opt_G.zero_grad()
-    feat_im = mulut_predict(model_G, im, 1, inC)
-    hyper_in = feat_im / float(norm)
+    if two_stage:
+        feat_im = mulut_predict(model_G, im, 1, inC)
+        hyper_in = feat_im / float(norm)
+    else:
+        feat_im = torch.round(im * norm)
+        hyper_in = im
     pred_hyper = mulut_predict(model_G, hyper_in, 2, inC)
     if linear:
         pred = resizer.resize(feat_im, pred_hyper)
