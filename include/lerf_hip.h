@@ -158,6 +158,29 @@ typedef struct {
     int out_y0, out_x0, src_y0;
 } lerf_warp_geo_t;
 
+/* Remap geometry: the homographic warp with its projected grid READ from a dense coordinate map instead of projected through a
+ * matrix -- lens undistortion, rectification, optical-flow and mesh warps.  Entry (i, j) of the map is (row, col) of the source
+ * position of output pixel (i, j) in the reference's convention: integers are pixel indices, the values are what
+ * get_projected_grid2d (resize_right/resize_right2d_numpy.py:306-342) holds before its clip.  Everything after the point is the
+ * warp's: clip to [0, H] x [0, W], support boundary, low pads, taps, arithmetic, tie guard.  A NaN row or column coordinate reads
+ * no memory and yields 0 (uint8) / NaN (float); +-inf clip like any other out-of-range value; no map value can produce an
+ * out-of-range address. */
+#define LERF_REMAP_PADS_FROM_MAP (-1)
+typedef struct {
+    int S;
+    int out_h, out_w;
+    const void* coords;      /* device [out_h][row_stride] elements, (row, col) pairs: entry (i, j) at coords + i * row_stride + 2 * j.
+                              * Aligned to one entry (16 bytes LERF_F64, 8 bytes LERF_F32): a kernel reads an entry with one load */
+    int coords_dtype;        /* LERF_F64 or LERF_F32 (promoted exactly to float64) */
+    int64_t row_stride;      /* ELEMENTS between rows of the map; even, >= 2 * out_w */
+    int pad_mode;            /* LERF_PAD_*; non-constant modes: float outputs of lerf_remap only */
+    int pad_r_lo, pad_c_lo;  /* low pads (calc_pad_sz, :363-369).  LERF_REMAP_PADS_FROM_MAP: the reference's, derived on the device
+                              * from coords[0][0] -- max(-left_boundary(clip(.)), 0) -- which makes the map of a homography reproduce
+                              * lerf_warp bit for bit.  A tile of a larger map (coords = the tile's first entry, out_h / out_w its
+                              * size) passes the WHOLE map's pads explicitly, like lerf_warp_geo_t's rectangles keep the whole
+                              * output's.  (Only the low pads reach a tap; the high pads are never needed.) */
+} lerf_remap_geo_t;
+
 /* ---------------------------------------------------------------- host side */
 int lerf_abi_version(void);
 const char* lerf_strerror(int code);
@@ -310,6 +333,21 @@ int lerf_unpack_stages(const uint32_t* packed, int64_t n_pxch, int oC, uint8_t* 
  * strides packed_sn in dwords, out_sn in elements of `out`; n = 1: one frame) in ONE launch; out: uint8 or float32 */
 int lerf_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_warp_geo_t* geo,
                      int kind, double max_sigma, const lerf_mplane_t* out, int64_t out_sn, void* stream);
+
+/* Stage 3 by a dense coordinate map (lerf_remap_geo_t): lerf_warp / lerf_warp_packed with the point of every output pixel read from
+ * the map.  Same operands, dtype table, kinds, supports, pad modes and arithmetic as their namesakes -- after the point is known the
+ * kernels run the same code -- so the map of a homography (its unclipped projected grid) gives lerf_warp's bytes.  There is no
+ * tile-fused remap (a dense map has no closed-form tile boxes) and no backward.
+ *   lerf_remap_host_geometry   host, no GPU: geo->coords is HOST memory; writes what the kernels derive from the map -- pads[2] =
+ *                              the low pads (row, col) and, per output pixel, the clipped point gr / gc (padded coordinates) and the
+ *                              support's first tap lr / lc ([out_h * out_w] each; any may be NULL). */
+int lerf_remap(const lerf_plane_t* feat, const lerf_plane_t hyper[3],
+               int H, int W, int C, const lerf_remap_geo_t* geo,
+               int kind, double max_sigma, const lerf_mplane_t* out, void* stream);
+int lerf_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_remap_geo_t* geo,
+                      int kind, double max_sigma, const lerf_mplane_t* out, int64_t out_sn, void* stream);
+int lerf_remap_host_geometry(const lerf_remap_geo_t* geo, int H, int W, double* gr, double* gc, int32_t* lr, int32_t* lc,
+                             int32_t pads[2]);
 
 /* ABI 7.  The whole warp path of the harness (resample/eval_lut_warp.py:100-222: stage 1, stage 2, SteeringGaussianWarp2dNumpy /
  * AmplifiedLinearWarp2dNumpy.warp, resize_right/resize_right2d_numpy.py:516-636) for `n` RGB frames that share one homography,

@@ -7,10 +7,10 @@ Host side = Python mirroring the reference's class / function API; device side
 from . import _lib  # noqa: F401
 from ._lib import LerfError  # noqa: F401
 from .luts import LutSet, load_lut_arrays  # noqa: F401
-from .pipeline import LerfEngine, sr, warp  # noqa: F401
-from . import metrics, stream  # noqa: F401
+from .pipeline import LerfEngine, sr, warp, remap  # noqa: F401
+from . import metrics, stream, coords  # noqa: F401
 
-__all__ = ["LerfEngine", "LutSet", "load_lut_arrays", "sr", "warp", "LerfError", "LIB_PATH"]
+__all__ = ["LerfEngine", "LutSet", "load_lut_arrays", "sr", "warp", "remap", "LerfError", "LIB_PATH"]
 
 
 def __getattr__(name):

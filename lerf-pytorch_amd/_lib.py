@@ -46,6 +46,7 @@ EXPORTS = [
     "lerf_sr_ragged_workspace_bytes", "lerf_sr_fused_ragged_u8", "lerf_stages_ragged_workspace_bytes", "lerf_stages_packed_ragged_u8",
     "lerf_stages_packed_u8", "lerf_unpack_stages", "lerf_warp_packed", "lerf_rect_copy_u8",
     "lerf_warp_tile_boxes", "lerf_warp_fused_supported", "lerf_warp_fused_u8",
+    "lerf_remap", "lerf_remap_packed", "lerf_remap_host_geometry",
     "lerf_metric_y_sse_u8", "lerf_metric_ssim_y_u8", "lerf_metric_masked_sse_u8",
     "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd",
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_srnet_fwd_f32", "lerf_srnet_bwd_workspace_bytes", "lerf_srnet_bwd_f32",
@@ -118,6 +119,18 @@ class WarpGeo(C.Structure):
         ("pad_r_lo", C.c_int), ("pad_r_hi", C.c_int), ("pad_c_lo", C.c_int), ("pad_c_hi", C.c_int),
         ("pad_mode", C.c_int),
         ("out_y0", C.c_int), ("out_x0", C.c_int), ("src_y0", C.c_int),       # ABI 7: a rectangle of the output from a band of the source
+    ]
+
+
+REMAP_PADS_FROM_MAP = -1
+
+
+class RemapGeo(C.Structure):       # lerf_remap_geo_t
+    _fields_ = [
+        ("S", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int),
+        ("coords", C.c_void_p), ("coords_dtype", C.c_int), ("row_stride", C.c_int64),
+        ("pad_mode", C.c_int),
+        ("pad_r_lo", C.c_int), ("pad_c_lo", C.c_int),                        # REMAP_PADS_FROM_MAP: derived from coords[0][0]
     ]
 
 
@@ -203,6 +216,12 @@ def lib():
     L.lerf_unpack_stages.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_warp_packed.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WarpGeo), C.c_int, C.c_double,
                                    C.POINTER(Plane), C.c_int64, C.c_void_p]
+    L.lerf_remap.argtypes = [C.POINTER(Plane), C.POINTER(Plane), C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo),
+                             C.c_int, C.c_double, C.POINTER(Plane), C.c_void_p]
+    L.lerf_remap_packed.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo), C.c_int, C.c_double,
+                                    C.POINTER(Plane), C.c_int64, C.c_void_p]
+    L.lerf_remap_host_geometry.argtypes = [C.POINTER(RemapGeo), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]
     L.lerf_rect_copy_u8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Rect), C.c_int, C.c_int,
                                     C.c_void_p]
     L.lerf_sr_fused_supported.argtypes = [C.c_int, C.POINTER(Luts), C.POINTER(SrGeo), C.c_int, C.c_int, C.c_int, C.c_double]
@@ -329,6 +348,26 @@ def warp_pads(minv: np.ndarray, in_hw, out_hw, S: int):
     check(lib().lerf_warp_pads(m.ctypes.data, int(in_hw[0]), int(in_hw[1]), int(out_hw[0]), int(out_hw[1]), int(S),
                                pads.ctypes.data), "lerf_warp_pads")
     return tuple(int(p) for p in pads)
+
+
+def remap_host_geometry(coords: np.ndarray, in_hw, S: int, pads=None):
+    """What the remap kernels derive from a coordinate map, on the host (lerf_remap_host_geometry): coords float64 / float32
+    [oH, oW, 2] -> (gr, gc float64 [oH, oW], lr, lc int32 [oH, oW], (pad_r_lo, pad_c_lo)); pads=None: derived from coords[0, 0]."""
+    c = np.asarray(coords)
+    if c.ndim != 3 or c.shape[2] != 2 or c.dtype not in (np.float32, np.float64):
+        raise ValueError("coords must be a float32 / float64 [oH, oW, 2] array")
+    c = np.ascontiguousarray(c)
+    oH, oW = c.shape[:2]
+    g = RemapGeo()
+    g.S, g.out_h, g.out_w = int(S), oH, oW
+    g.coords, g.coords_dtype, g.row_stride = c.ctypes.data, (LERF_F32 if c.dtype == np.float32 else LERF_F64), 2 * oW
+    g.pad_r_lo, g.pad_c_lo = (REMAP_PADS_FROM_MAP, REMAP_PADS_FROM_MAP) if pads is None else (int(pads[0]), int(pads[1]))
+    gr, gc = np.zeros((oH, oW), np.float64), np.zeros((oH, oW), np.float64)
+    lr, lc = np.zeros((oH, oW), np.int32), np.zeros((oH, oW), np.int32)
+    out = np.zeros(2, np.int32)
+    check(lib().lerf_remap_host_geometry(C.byref(g), int(in_hw[0]), int(in_hw[1]), gr.ctypes.data, gc.ctypes.data, lr.ctypes.data,
+                                         lc.ctypes.data, out.ctypes.data), "lerf_remap_host_geometry")
+    return gr, gc, lr, lc, (int(out[0]), int(out[1]))
 
 
 # ------------------------------------------------------------------ device plumbing

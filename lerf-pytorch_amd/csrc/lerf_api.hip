@@ -327,6 +327,65 @@ int lerf_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, in
     return rc != LERF_OK ? rc : check_launch();
 }
 
+// lerf_remap_geo_t -> RemapGeo; what can be checked on the host is (the map's values cannot, and need not be: lerf_remap.hip)
+static int remap_geo(const lerf_remap_geo_t* geo, RemapGeo& m) {
+    if (!geo || !geo->coords || geo->out_h < 1 || geo->out_w < 1) return LERF_EINVAL;
+    if (geo->coords_dtype != LERF_F32 && geo->coords_dtype != LERF_F64) return LERF_EINVAL;
+    const size_t entry = geo->coords_dtype == LERF_F32 ? 8 : 16;               // one aligned load per entry
+    if ((size_t)(uintptr_t)geo->coords % entry != 0 || (geo->row_stride & 1) || geo->row_stride < 2 * (int64_t)geo->out_w) return LERF_EINVAL;
+    if (geo->pad_mode < LERF_PAD_CONSTANT || geo->pad_mode > LERF_PAD_WRAP) return LERF_EINVAL;
+    // explicit low pads: what calc_pad_sz can yield for a clipped point, 0 .. ceil(S / 2) (the field of view starts at >= -S/2)
+    for (int p : {geo->pad_r_lo, geo->pad_c_lo})
+        if (p != LERF_REMAP_PADS_FROM_MAP && (p < 0 || p > LERF_MAX_SUPPORT)) return LERF_EINVAL;
+    m.S = geo->S; m.oH = geo->out_h; m.oW = geo->out_w;
+    m.coords = geo->coords; m.f32 = geo->coords_dtype == LERF_F32; m.stride = geo->row_stride;
+    m.pad_r_lo = geo->pad_r_lo; m.pad_c_lo = geo->pad_c_lo; m.pad_mode = geo->pad_mode;
+    return LERF_OK;
+}
+
+int lerf_remap(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
+               int kind, double max_sigma, const lerf_mplane_t* out, void* stream) {
+    if (!plane_ok(feat) || !geo || !out || !out->ptr || H < 1 || W < 1 || C < 1) return LERF_EINVAL;
+    int nh = kind == LERF_KIND_GAUSS ? 3 : (kind == LERF_KIND_LINEAR ? 1 : 0);
+    if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
+    if (nh > 0 && !hyper) return LERF_EINVAL;
+    for (int k = 0; k < nh; ++k)
+        if (!hyper[k].ptr || hyper[k].dtype != hyper[0].dtype || hyper[k].sy != hyper[0].sy ||
+            hyper[k].sx != hyper[0].sx || hyper[k].sc != hyper[0].sc)
+            return LERF_EINVAL;
+    RemapGeo m{};
+    int rc = remap_geo(geo, m);
+    if (rc != LERF_OK) return rc;
+    if (geo->pad_mode != LERF_PAD_CONSTANT && out->dtype == LERF_U8) return LERF_EUNSUPPORTED;
+    WarpArgs a{};
+    a.feat = feat->ptr; a.in_dtype = feat->dtype; a.fy = feat->sy; a.fx = feat->sx; a.fc = feat->sc;
+    for (int k = 0; k < 3; ++k) a.h[k] = nh > 0 ? (k < nh ? hyper[k].ptr : hyper[0].ptr) : feat->ptr;
+    a.h_dtype = nh > 0 ? hyper[0].dtype : feat->dtype;
+    a.hy = nh > 0 ? hyper[0].sy : 0; a.hx = nh > 0 ? hyper[0].sx : 0; a.hc = nh > 0 ? hyper[0].sc : 0;
+    a.H = H; a.W = W; a.C = C;
+    a.kind = kind; a.max_sigma = max_sigma;
+    a.out = out->ptr; a.out_dtype = out->dtype; a.oy = out->sy; a.ox = out->sx; a.oc = out->sc;
+    rc = launch_remap(a, m, as_stream(stream));
+    return rc != LERF_OK ? rc : check_launch();
+}
+
+int lerf_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_remap_geo_t* geo, int kind,
+                      double max_sigma, const lerf_mplane_t* out, int64_t out_sn, void* stream) {
+    if (!packed || !geo || !out || !out->ptr || n < 1 || H < 1 || W < 1 || C < 1) return LERF_EINVAL;
+    RemapGeo m{};
+    int rc = remap_geo(geo, m);
+    if (rc != LERF_OK) return rc;
+    if (geo->pad_mode != LERF_PAD_CONSTANT) return LERF_EUNSUPPORTED;
+    rc = launch_remap_packed(packed, packed_sn, n, H, W, C, m, kind, (float)max_sigma, out->ptr, out->dtype, out->sy, out->sx,
+                             out->sc, out_sn, as_stream(stream));
+    return rc != LERF_OK ? rc : check_launch();
+}
+
+int lerf_remap_host_geometry(const lerf_remap_geo_t* geo, int H, int W, double* gr, double* gc, int32_t* lr, int32_t* lc,
+                             int32_t pads[2]) {
+    return host::remap_geometry(geo, H, W, gr, gc, lr, lc, pads);
+}
+
 int lerf_rect_copy_u8(uint8_t* frames, int n, int fh, int fw, int C, uint8_t* staging, const lerf_rect_t* rects, int n_rects,
                       int to_staging, void* stream) {
     if (!frames || !staging || !rects || n < 1 || fh < 1 || fw < 1 || C < 1 || n_rects < 1 || n_rects > LERF_MAX_RECTS) return LERF_EINVAL;

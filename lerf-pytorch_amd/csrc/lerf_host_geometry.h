@@ -106,14 +106,39 @@ struct WarpPixel {
     int lr, lc;         // left boundary of the support (padded coordinates)
 };
 
-LERF_HD inline WarpPixel warp_pixel(const double minv[9], int S, int pad_r_lo, int pad_c_lo, int i, int j, int H, int W) {
+// ... of a point (gr, gc) already clipped to [0, H] x [0, W]: the one place where a source position becomes a WarpPixel,
+// whatever produced it (a homography: warp_pixel; a dense coordinate map: remap_pixel).
+LERF_HD inline WarpPixel pixel_of_point(double gr, double gc, int S, int pad_r_lo, int pad_c_lo) {
     WarpPixel p;
-    project_point(minv, i, j, H, W, &p.gr, &p.gc);
+    p.gr = gr;
+    p.gc = gc;
     p.lr = left_boundary(p.gr, S) + pad_r_lo;
     p.lc = left_boundary(p.gc, S) + pad_c_lo;
     p.gr += (double)pad_r_lo;
     p.gc += (double)pad_c_lo;
     return p;
+}
+
+LERF_HD inline WarpPixel warp_pixel(const double minv[9], int S, int pad_r_lo, int pad_c_lo, int i, int j, int H, int W) {
+    double gr, gc;
+    project_point(minv, i, j, H, W, &gr, &gc);
+    return pixel_of_point(gr, gc, S, pad_r_lo, pad_c_lo);
+}
+
+// Remap: the projected grid is read from a dense coordinate map instead of being projected -- entry (i, j) = (row, col) of the
+// source position of output pixel (i, j), in the coordinates get_projected_grid2d holds BEFORE its clip (:335).  clip_coord is
+// that clip (:338-339) in a form no value can escape: -inf -> 0, +inf -> n, and NaN -> 0 (a NaN entry is never resampled --
+// the kernels write 0 / NaN for it -- but nothing downstream of this line can see a value outside [0, n]).
+LERF_HD inline double clip_coord(double v, int n) { return !(v >= 0.0) ? 0.0 : (v > (double)n ? (double)n : v); }
+
+LERF_HD inline WarpPixel remap_pixel(double row, double col, int S, int pad_r_lo, int pad_c_lo, int H, int W) {
+    return pixel_of_point(clip_coord(row, H), clip_coord(col, W), S, pad_r_lo, pad_c_lo);
+}
+
+// calc_pad_sz's low pad (:365) of one axis from the map's FIRST entry: max(-left_boundary(clip(map[0, 0])), 0)
+LERF_HD inline int remap_pad_lo(double v0, int n, int S) {
+    const int l = left_boundary(clip_coord(v0, n), S);
+    return -l > 0 ? -l : 0;
 }
 
 // Unpadded source coordinate s of a tap along one axis of n pixels (may lie outside [0, n)): where the replicate-padded
@@ -259,6 +284,30 @@ inline int warp_pads(const double minv[9], int in_h, int in_w, int out_h, int ou
     pads[1] = (l1r + S - 1 - in_h + 1) > 0 ? (l1r + S - 1 - in_h + 1) : 0;
     pads[2] = -l0c > 0 ? -l0c : 0;
     pads[3] = (l1c + S - 1 - in_w + 1) > 0 ? (l1c + S - 1 - in_w + 1) : 0;
+    return LERF_OK;
+}
+
+// Host mirror of what the remap kernels derive from a coordinate map in HOST memory (lerf_remap_host_geometry): the low pads
+// (geo->pad_*_lo, or remap_pad_lo of the map's first entry) and, per output pixel, remap_pixel's gr, gc, lr, lc.
+inline int remap_geometry(const lerf_remap_geo_t* geo, int H, int W, double* gr, double* gc, int32_t* lr, int32_t* lc, int32_t pads[2]) {
+    if (!geo || !geo->coords || H < 1 || W < 1 || geo->out_h < 1 || geo->out_w < 1 || geo->S < 1 || geo->S > LERF_MAX_SUPPORT) return LERF_EINVAL;
+    if ((geo->coords_dtype != LERF_F32 && geo->coords_dtype != LERF_F64) || geo->row_stride < 2 * (int64_t)geo->out_w) return LERF_EINVAL;
+    auto entry = [&](int i, int j, int k) -> double {
+        const int64_t o = (int64_t)i * geo->row_stride + 2 * (int64_t)j + k;
+        return geo->coords_dtype == LERF_F32 ? (double)((const float*)geo->coords)[o] : ((const double*)geo->coords)[o];
+    };
+    const int pr = geo->pad_r_lo < 0 ? remap_pad_lo(entry(0, 0, 0), H, geo->S) : geo->pad_r_lo;
+    const int pc = geo->pad_c_lo < 0 ? remap_pad_lo(entry(0, 0, 1), W, geo->S) : geo->pad_c_lo;
+    if (pads) { pads[0] = pr; pads[1] = pc; }
+    for (int i = 0; i < geo->out_h; ++i)
+        for (int j = 0; j < geo->out_w; ++j) {
+            const WarpPixel p = remap_pixel(entry(i, j, 0), entry(i, j, 1), geo->S, pr, pc, H, W);
+            const int64_t o = (int64_t)i * geo->out_w + j;
+            if (gr) gr[o] = p.gr;
+            if (gc) gc[o] = p.gc;
+            if (lr) lr[o] = p.lr;
+            if (lc) lc[o] = p.lc;
+        }
     return LERF_OK;
 }
 

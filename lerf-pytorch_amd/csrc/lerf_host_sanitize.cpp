@@ -30,6 +30,10 @@ int lerf_rr_adjoint_csr(int n_in, int n_out, int taps, const int32_t* left, cons
                         int32_t* row_ptr, int32_t* idx, void* wt) {
     return host::rr_adjoint_csr(n_in, n_out, taps, left, w, w_dtype, pad_mode, row_ptr, idx, wt);
 }
+int lerf_remap_host_geometry(const lerf_remap_geo_t* geo, int H, int W, double* gr, double* gc, int32_t* lr, int32_t* lc,
+                             int32_t pads[2]) {
+    return host::remap_geometry(geo, H, W, gr, gc, lr, lc, pads);
+}
 // device entry point: no kernels in this build
 int lerf_rr_axis(const void*, int, int64_t, int64_t, const lerf_rr_axis_t*, int, void*, int, void*) { return LERF_ENODEVICE; }
 }

@@ -45,6 +45,18 @@ struct WarpArgs {
     void* out; int out_dtype; int64_t oy, ox, oc;
 };
 
+// lerf_remap_geo_t as the remap kernels take it (lerf_remap.hip); they build the WarpGeo of the shared bodies from it
+struct RemapGeo {
+    int S, oH, oW;
+    const void* coords; int f32;     // [oH][stride] elements, (row, col) pairs; f32: float32 entries (else float64)
+    int64_t stride;
+    int pad_r_lo, pad_c_lo;          // < 0: derived from coords[0][0] (remap_pad_lo)
+    int pad_mode;
+};
+int launch_remap(const WarpArgs& a, const RemapGeo& m, hipStream_t st);      // a.geo is not read: the geometry is m
+int launch_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const RemapGeo& m, int kind,
+                        float max_sigma, void* out, int out_dtype, int64_t oy, int64_t ox, int64_t oc, int64_t out_sn, hipStream_t st);
+
 int launch_lut_interp(const void* img, int in_dtype, int64_t sy, int64_t sx, int64_t sc, int img_h, int img_w, int C,
                       int h, int w, Offsets4 off, const int8_t* lut, int oC, int interval, void* out, int out_dtype, int64_t oy,
                       int64_t ox, int64_t ocs, int flags, hipStream_t st);

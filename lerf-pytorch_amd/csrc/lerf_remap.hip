@@ -1,0 +1,201 @@
+// Stage 3 by a DENSE COORDINATE MAP (lerf_remap_geo_t): the homographic warp with its projected grid read from memory --
+// lens undistortion, rectification, optical-flow and mesh warps, one source position per output pixel with no matrix behind it.
+//
+//   remap_kernel             counterpart of warp_kernel            (planar / strided operands, every kind, S, pad mode, dtype)
+//   remap_packed_kernel      counterpart of warp_packed_kernel     (packed stage dwords, any C, per channel)
+//   remap_packed_px_kernel   counterpart of warp_packed_px_kernel  (packed stage dwords, RGB, S = 2, one thread per pixel: hot path)
+//
+// A kernel here differs from its counterpart in ONE statement: where that one projects (i, j) through the inverse matrix
+// (warp_pixel), this one loads the map entry -- one 16-byte (float64) or 8-byte (float32) load per output pixel, consecutive
+// lanes on consecutive entries -- and clips it (remap_pixel, lerf_host_geometry.h).  Everything from the point on is the shared
+// body of lerf_warp_kernels.h, so the map of a homography gives the homographic warp's bytes.
+//
+// Addresses: the map is read at (i, j) inside the launch's [oH][oW] only; the point is clipped to [0, H] x [0, W] BEFORE any
+// conversion to int (clip_coord sends NaN to 0 and +-inf to the borders), and every tap index passes axis_tap's clamps, so no
+// map value -- NaN, infinite, or 1e300 -- can form an address outside the operands.  A NaN entry reads nothing further and
+// stores 0 (uint8) / NaN (float).
+#include "lerf_warp_kernels.h"
+
+namespace lerf {
+
+struct MapPoint {
+    double r, c;
+};
+
+// entry (i, j) of the map in ONE load; float32 entries are promoted exactly
+__device__ __forceinline__ MapPoint remap_entry(const RemapGeo& m, int i, int j) {
+    const int64_t o = (int64_t)i * m.stride + 2 * (int64_t)j;
+    if (m.f32) {
+        const float2 v = *reinterpret_cast<const float2*>(static_cast<const float*>(m.coords) + o);
+        return {(double)v.x, (double)v.y};
+    }
+    const double2 v = *reinterpret_cast<const double2*>(static_cast<const double*>(m.coords) + o);
+    return {v.x, v.y};
+}
+
+__device__ __forceinline__ bool no_point(const MapPoint& q) { return q.r != q.r || q.c != q.c; }
+
+// the WarpGeo the shared bodies read (S, output size, low pads, pad mode; no matrix, no rectangle offsets).  Low pads the caller
+// left to the map come from its first entry: a uniform load, no host round trip for a device-resident map.
+__device__ __forceinline__ WarpGeo remap_warp_geo(const RemapGeo& m, int H, int W) {
+    WarpGeo g;
+    g.S = m.S; g.oH = m.oH; g.oW = m.oW;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) g.minv[k] = 0.0;
+    g.pad_r_lo = m.pad_r_lo; g.pad_c_lo = m.pad_c_lo;
+    if (m.pad_r_lo < 0 || m.pad_c_lo < 0) {
+        const MapPoint q0 = remap_entry(m, 0, 0);
+        if (m.pad_r_lo < 0) g.pad_r_lo = remap_pad_lo(q0.r, H, m.S);
+        if (m.pad_c_lo < 0) g.pad_c_lo = remap_pad_lo(q0.c, W, m.S);
+    }
+    g.pad_r_hi = 0; g.pad_c_hi = 0;
+    g.pad_mode = m.pad_mode;
+    g.oy0 = 0; g.ox0 = 0;
+    return g;
+}
+
+__device__ __forceinline__ WarpPixel remap_pixel(const WarpGeo& g, const MapPoint& q, int H, int W) {
+    return remap_pixel(q.r, q.c, g.S, g.pad_r_lo, g.pad_c_lo, H, W);
+}
+
+// ---------------------------------------------------------------------------
+// general remap
+// ---------------------------------------------------------------------------
+template <typename TI, typename TH, typename TO, typename A, int KIND>
+__global__ void __launch_bounds__(256)
+remap_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
+             const TH* __restrict__ h0, const TH* __restrict__ h1, const TH* __restrict__ h2,
+             int64_t hy, int64_t hx, int64_t hc, int H, int W, int C, RemapGeo m,
+             A max_sigma, TO* __restrict__ out, int64_t oy, int64_t ox, int64_t oc) {
+    int xc = blockIdx.x * blockDim.x + threadIdx.x;
+    int i = blockIdx.y;
+    if (xc >= m.oW * C) return;
+    int j = xc / C;
+    int c = xc - j * C;
+    TO* dst = out + i * oy + j * ox + c * oc;
+    const MapPoint q = remap_entry(m, i, j);
+    if (no_point(q)) { store_no_value(dst); return; }
+    const WarpGeo g = remap_warp_geo(m, H, W);
+    warp_body<TI, TH, TO, A, KIND>(feat, fy, fx, fc, h0, h1, h2, hy, hx, hc, H, W, g, remap_pixel(g, q, H, W), c, max_sigma, dst);
+}
+
+template <typename TI, typename TH, typename TO, typename A>
+static int remap_dispatch_kind(const WarpArgs& a, const RemapGeo& m, hipStream_t st) {
+    dim3 block(256), grid((m.oW * a.C + 255) / 256, m.oH);
+#define LERF_RM(KIND)                                                                                        \
+    hipLaunchKernelGGL((remap_kernel<TI, TH, TO, A, KIND>), grid, block, 0, st, (const TI*)a.feat, a.fy,     \
+                       a.fx, a.fc, (const TH*)a.h[0], (const TH*)a.h[1], (const TH*)a.h[2], a.hy, a.hx,      \
+                       a.hc, a.H, a.W, a.C, m, (A)a.max_sigma, (TO*)a.out, a.oy, a.ox, a.oc)
+    if (a.kind == LERF_KIND_GAUSS) LERF_RM(LERF_KIND_GAUSS);
+    else if (a.kind == LERF_KIND_LINEAR) LERF_RM(LERF_KIND_LINEAR);
+    else if (a.kind == LERF_KIND_NEAREST) LERF_RM(LERF_KIND_NEAREST);
+    else if (a.kind == LERF_KIND_CUBIC) LERF_RM(LERF_KIND_CUBIC);
+    else if (a.kind == LERF_KIND_BILINEAR) LERF_RM(LERF_KIND_BILINEAR);
+    else if (a.kind == LERF_KIND_LANCZOS2) LERF_RM(LERF_KIND_LANCZOS2);
+    else if (a.kind == LERF_KIND_LANCZOS3) LERF_RM(LERF_KIND_LANCZOS3);
+    else return LERF_EUNSUPPORTED;
+#undef LERF_RM
+    return LERF_OK;
+}
+
+// the dtype and arithmetic table of launch_warp
+int launch_remap(const WarpArgs& a, const RemapGeo& m, hipStream_t st) {
+    if (m.S < 1 || m.S > LERF_MAX_SUPPORT || m.oH > 65535) return LERF_EUNSUPPORTED;
+    const bool fixed = a.kind >= LERF_KIND_NEAREST;     // no hyper-parameter maps
+    if (a.in_dtype == LERF_U8 && (a.h_dtype == LERF_U8 || fixed)) {
+        if (a.out_dtype == LERF_U8) return remap_dispatch_kind<uint8_t, uint8_t, uint8_t, float>(a, m, st);
+        if (a.out_dtype == LERF_F32) return remap_dispatch_kind<uint8_t, uint8_t, float, double>(a, m, st);     // float64 arithmetic, rounded once
+        if (a.out_dtype == LERF_F64) return remap_dispatch_kind<uint8_t, uint8_t, double, double>(a, m, st);
+    } else if (a.in_dtype == LERF_F32 && (a.h_dtype == LERF_F32 || fixed)) {
+        if (a.out_dtype == LERF_F32) return remap_dispatch_kind<float, float, float, double>(a, m, st);
+        if (a.out_dtype == LERF_F64) return remap_dispatch_kind<float, float, double, double>(a, m, st);
+    }
+    return LERF_EUNSUPPORTED;
+}
+
+// ---------------------------------------------------------------------------
+// packed stage outputs
+// ---------------------------------------------------------------------------
+template <typename TO, int KIND>
+__global__ void __launch_bounds__(256)
+remap_packed_kernel(const uint32_t* __restrict__ packed, int64_t packed_sn, int H, int W, int C, RemapGeo m, float max_sigma,
+                    TO* __restrict__ out, int64_t oy, int64_t ox, int64_t oc, int64_t out_sn) {
+    packed += (int64_t)blockIdx.z * packed_sn;             // frame of the batch (one map for all)
+    out += (int64_t)blockIdx.z * out_sn;
+    int xc = blockIdx.x * blockDim.x + threadIdx.x;
+    int i = blockIdx.y;
+    if (xc >= m.oW * C) return;
+    int j = xc / C;
+    int c = xc - j * C;
+    TO* dst = out + i * oy + j * ox + c * oc;
+    const MapPoint q = remap_entry(m, i, j);
+    if (no_point(q)) { store_no_value(dst); return; }
+    const WarpGeo g = remap_warp_geo(m, H, W);
+    warp_packed_body<TO, KIND>(packed, H, W, C, g, remap_pixel(g, q, H, W), c, max_sigma, dst);
+}
+
+// one thread per output PIXEL of an RGB frame with S = 2; the block order of warp_packed_px_kernel (warp_px_block), so the
+// lanes of a wave read 64 consecutive map entries (1 KiB of float64 entries per load instruction)
+template <typename TO, int KIND, bool PROD = false>
+__global__ void __launch_bounds__(256)
+remap_packed_px_kernel(const uint32_t* __restrict__ packed0, int64_t packed_sn, int n_frames, int H, int W, RemapGeo m, float max_sigma,
+                       TO* __restrict__ out0, int64_t oy, int64_t ox, int64_t oc, int64_t out_sn) {
+    int i, j;
+    warp_px_block(m.oW, &i, &j);
+    if (j >= m.oW) return;
+    const MapPoint q = remap_entry(m, i, j);
+    if (no_point(q)) {
+        for (int fr = 0; fr < n_frames; ++fr)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) store_no_value(out0 + (int64_t)fr * out_sn + i * oy + j * ox + c * oc);
+        return;
+    }
+    const WarpGeo g = remap_warp_geo(m, H, W);
+    const WarpPx2 G = warp_px_geometry(g, remap_pixel(g, q, H, W), H, W);
+    warp_packed_px_body<TO, KIND, PROD>(packed0, packed_sn, n_frames, H, W, g, G, i, j, max_sigma, out0, oy, ox, oc, out_sn);
+}
+
+// the path selection of launch_warp_packed
+int launch_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const RemapGeo& m, int kind,
+                        float max_sigma, void* out, int out_dtype, int64_t oy, int64_t ox, int64_t oc, int64_t out_sn, hipStream_t st) {
+    if (m.S < 1 || m.S > LERF_MAX_SUPPORT) return LERF_EUNSUPPORTED;
+    if (n < 1 || n > 65535 || m.oH > 65535) return LERF_EUNSUPPORTED;
+    if (C == 3 && m.S == 2 && (kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) &&
+        (out_dtype == LERF_U8 || out_dtype == LERF_F32)) {
+        dim3 blockp(256), gridp((unsigned)(((m.oW + 255) / 256) * m.oH), 1, 1);
+#define LERF_RPX(TO, KIND, PROD)                                                                                      \
+    hipLaunchKernelGGL((remap_packed_px_kernel<TO, KIND, PROD>), gridp, blockp, 0, st, packed, packed_sn, n, H, W, m, max_sigma, (TO*)out, \
+                       oy, ox, oc, out_sn)
+        const bool prod = out_dtype == LERF_U8 && max_sigma <= s3::kNoShiftMaxSigma;     // production arithmetic + tie guard
+        if (kind == LERF_KIND_GAUSS) {
+            if (prod) LERF_RPX(uint8_t, LERF_KIND_GAUSS, true);
+            else if (out_dtype == LERF_U8) LERF_RPX(uint8_t, LERF_KIND_GAUSS, false);
+            else LERF_RPX(float, LERF_KIND_GAUSS, false);
+        } else {
+            if (prod) LERF_RPX(uint8_t, LERF_KIND_LINEAR, true);
+            else if (out_dtype == LERF_U8) LERF_RPX(uint8_t, LERF_KIND_LINEAR, false);
+            else LERF_RPX(float, LERF_KIND_LINEAR, false);
+        }
+#undef LERF_RPX
+        return LERF_OK;
+    }
+    dim3 block(256), grid((m.oW * C + 255) / 256, m.oH, n);
+#define LERF_RPK(TO, KIND)                                                                                         \
+    hipLaunchKernelGGL((remap_packed_kernel<TO, KIND>), grid, block, 0, st, packed, packed_sn, H, W, C, m, max_sigma, (TO*)out, \
+                       oy, ox, oc, out_sn)
+    if (kind == LERF_KIND_GAUSS) {
+        if (out_dtype == LERF_U8) LERF_RPK(uint8_t, LERF_KIND_GAUSS);
+        else if (out_dtype == LERF_F32) LERF_RPK(float, LERF_KIND_GAUSS);
+        else return LERF_EUNSUPPORTED;
+    } else if (kind == LERF_KIND_LINEAR) {
+        if (out_dtype == LERF_U8) LERF_RPK(uint8_t, LERF_KIND_LINEAR);
+        else if (out_dtype == LERF_F32) LERF_RPK(float, LERF_KIND_LINEAR);
+        else return LERF_EUNSUPPORTED;
+    } else {
+        return LERF_EUNSUPPORTED;
+    }
+#undef LERF_RPK
+    return LERF_OK;
+}
+
+}  // namespace lerf

@@ -3,7 +3,8 @@
 // (lerf_host_geometry.h) evaluated once for the two rows and two columns of taps; warp_px_value_u8 is the float32
 // production arithmetic (max_sigma <= s3::kNoShiftMaxSigma), warp_px_value the exact float32 parameter formation.  Shared by
 // warp_packed_px_kernel (taps from the packed maps in HBM / L2) and the tile-fused warp (taps from the tile's packed dwords in
-// LDS, lerf_fused_impl.h): the same instructions in both, so fused == unfused bit for bit.
+// LDS, lerf_fused_impl.h): the same instructions in both, so fused == unfused bit for bit.  warp_px_geometry takes the pixel's
+// point as a WarpPixel, so the remap (lerf_remap.hip: the point is read from a coordinate map) shares all of it as well.
 #pragma once
 
 #include "lerf_kernels.h"
@@ -64,9 +65,10 @@ struct WarpPx2 {
     bool in_r[2], in_c[2];     // the tap lies inside the frame (the image is zero outside)
 };
 
-__device__ __forceinline__ WarpPx2 warp_px_geometry(const WarpGeo& g, int i, int j, int H, int W) {
+// ... of a pixel whose point is known (projected: the overload below; read from a coordinate map: lerf_remap.hip)
+__device__ __forceinline__ WarpPx2 warp_px_geometry(const WarpGeo& g, const WarpPixel& p, int H, int W) {
     WarpPx2 G;
-    G.p = warp_pixel(g.minv, 2, g.pad_r_lo, g.pad_c_lo, i + g.oy0, j + g.ox0, H, W);
+    G.p = p;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const AxisTap r = axis_tap(G.p.gr, G.p.lr, k, H, g.pad_r_lo, g.pad_mode);
@@ -81,6 +83,10 @@ __device__ __forceinline__ WarpPx2 warp_px_geometry(const WarpGeo& g, int i, int
         G.in_c[k] = c.inside;
     }
     return G;
+}
+
+__device__ __forceinline__ WarpPx2 warp_px_geometry(const WarpGeo& g, int i, int j, int H, int W) {
+    return warp_px_geometry(g, warp_pixel(g.minv, 2, g.pad_r_lo, g.pad_c_lo, i + g.oy0, j + g.ox0, H, W), H, W);
 }
 
 // channel value of the pixel in production arithmetic; tap(r, c) -> packed dword of the clamped source pixel (this channel).

@@ -188,6 +188,81 @@ class WarpGeometry:
         return cache[key][0]
 
 
+class RemapGeometry:
+    """Dense-coordinate-map geometry (lerf_remap_geo_t): the warp with its projected grid read from `coords` instead of
+    projected through a matrix.  coords: float64 / float32 [oH, oW, 2], entry (i, j) = (row, col) of the source position of
+    output pixel (i, j), unclipped, integers = pixel indices (coords.py builds such maps).  A numpy array (or a host tensor)
+    is uploaded once per device and kept with the geometry; a device tensor is used in place -- its last dimension must be
+    contiguous and its column stride 2, its row stride is free (a tile of a larger map is a view of it)."""
+
+    def __init__(self, in_hw, coords, support=2, pad_mode=0, pads=None):
+        """pads = (pad_r_lo, pad_c_lo): explicit low pads -- a tile of a larger map passes the WHOLE map's (whole.pads());
+        None: the reference's, derived on the device from coords[0, 0] (calc_pad_sz, resize_right2d_numpy.py:363-369)."""
+        self.in_hw, self.S, self.pad_mode = (int(in_hw[0]), int(in_hw[1])), int(support), int(pad_mode)
+        if self.in_hw[0] < 1 or self.in_hw[1] < 1:
+            raise ValueError("in_hw must be positive")
+        dev = getattr(coords, "is_cuda", False)
+        c = coords if dev else np.asarray(coords.detach().numpy() if hasattr(coords, "detach") else coords)
+        if c.ndim != 3 or c.shape[2] != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+            raise ValueError("coords must be [oH, oW, 2]")
+        if dev:
+            torch = _torch()
+            if c.dtype not in (torch.float32, torch.float64):
+                raise ValueError("coords must be float32 or float64")
+            if c.stride(2) != 1 or c.stride(1) != 2 or c.stride(0) % 2 or c.stride(0) < 2 * c.shape[1] \
+                    or c.data_ptr() % (2 * c.element_size()):
+                raise ValueError("device coords: contiguous (row, col) pairs, column stride 2, even row stride, entry-aligned")
+            self._host, self._dev = None, {str(c.device): c}
+        else:
+            if c.dtype not in (np.float32, np.float64):
+                c = c.astype(np.float64)
+            self._host, self._dev = np.ascontiguousarray(c), {}
+        self.out_hw = (int(c.shape[0]), int(c.shape[1]))
+        self.explicit_pads = None if pads is None else (int(pads[0]), int(pads[1]))
+        if self.explicit_pads is not None and not all(0 <= p <= _lib.LERF_MAX_SUPPORT for p in self.explicit_pads):
+            raise ValueError("pads must be non-negative low pads")
+
+    def device_coords(self, device):
+        key = str(device)
+        if key not in self._dev:
+            if self._host is None:
+                raise ValueError("the coordinate map lives on %s, the operands on %s" % (next(iter(self._dev)), key))
+            self._dev[key] = _torch().from_numpy(self._host).to(device)
+        return self._dev[key]
+
+    def struct(self, device):
+        c = self.device_coords(device)
+        g = _lib.RemapGeo()
+        g.S, g.out_h, g.out_w = self.S, self.out_hw[0], self.out_hw[1]
+        g.coords, g.coords_dtype, g.row_stride = c.data_ptr(), _lib._dt(c), c.stride(0)
+        g.pad_mode = self.pad_mode
+        g.pad_r_lo, g.pad_c_lo = self.explicit_pads if self.explicit_pads is not None else (_lib.REMAP_PADS_FROM_MAP,) * 2
+        return g, c
+
+    def _first_entry(self):
+        if self._host is not None:
+            return self._host[:1, :1]
+        return next(iter(self._dev.values()))[:1, :1].cpu().numpy()
+
+    def pads(self):
+        """(pad_r_lo, pad_c_lo) the kernels use: the explicit ones, else derived from coords[0, 0] (host mirror of the kernels' rule)"""
+        if self.explicit_pads is not None:
+            return self.explicit_pads
+        return _lib.remap_host_geometry(self._first_entry(), self.in_hw, self.S)[4]
+
+    def host_geometry(self):
+        """host mirror of the kernels' per-pixel geometry: (gr, gc, lr, lc, pads), see _lib.remap_host_geometry"""
+        c = self._host if self._host is not None else next(iter(self._dev.values())).cpu().numpy()
+        return _lib.remap_host_geometry(c, self.in_hw, self.S, self.explicit_pads)
+
+    def rows(self, i0, i1):
+        """the geometry of output rows [i0, i1) alone, with THIS map's pads (a view of the map, nothing is copied)"""
+        if not 0 <= i0 < i1 <= self.out_hw[0]:
+            raise ValueError("rows outside the map")
+        src = self._host if self._host is not None else next(iter(self._dev.values()))
+        return RemapGeometry(self.in_hw, src[i0:i1], self.S, self.pad_mode, pads=self.pads())
+
+
 # --------------------------------------------------------------------------- helpers
 def _planes_chw(t):
     """[N,H,W] contiguous-ish tensor -> Plane with channel = leading dim."""
@@ -413,6 +488,32 @@ def warp_packed(packed, geo: "WarpGeometry", kind="gauss", max_sigma=10.0, out="
     return o[0] if squeeze else o
 
 
+def remap_packed(packed, geo: "RemapGeometry", kind="gauss", max_sigma=10.0, out="u8"):
+    """warp_packed by a coordinate map (lerf_remap_packed): packed int32 [H,W,C] or a batch [N,H,W,C] sharing the map (ONE launch
+    for the batch).  out: "u8" / "f32" (a fresh tensor) or a caller-owned uint8 / float32 tensor of the output shape."""
+    torch = _torch()
+    squeeze = packed.dim() == 3
+    p = packed.unsqueeze(0) if squeeze else packed
+    if not p[0].is_contiguous():
+        p = p.contiguous()
+    N, H, W, Cn = p.shape
+    if (H, W) != geo.in_hw:
+        raise ValueError("packed maps do not match the geometry's frame")
+    oshape = (N, geo.out_hw[0], geo.out_hw[1], Cn)
+    if isinstance(out, str):
+        o = torch.empty(oshape, dtype=_out_dtype(out), device=p.device)
+    else:
+        o = out.unsqueeze(0) if (squeeze and out.dim() == 3) else out
+        if tuple(o.shape) != oshape or o.dtype not in (torch.uint8, torch.float32) or o.device != p.device \
+                or o.stride(3) != 1:
+            raise ValueError("out must be a uint8/float32 tensor of shape %s on the input's device" % (oshape[1:] if squeeze else oshape,))
+    po = _lib.plane(o, o.stride(1), o.stride(2), o.stride(3))
+    g, _keep = geo.struct(p.device)
+    _lib.check(_lib.lib().lerf_remap_packed(p.data_ptr(), p.stride(0), N, H, W, Cn, C.byref(g), KINDS[kind], float(max_sigma),
+                                            C.byref(po), o.stride(0), _lib.current_stream()), "lerf_remap_packed")
+    return o[0] if squeeze else o
+
+
 def warp_fused_supported(img_u8, luts, geo: "WarpGeometry", kind="gauss", max_sigma=10.0):
     H, W, Cn = img_u8.shape[-3:]
     return bool(_lib.lib().lerf_warp_fused_supported(Cn, luts.ref(), geo.ref(), H, W, KINDS[kind], float(max_sigma)))
@@ -586,6 +687,50 @@ def warp_planar(feat, hypers, geo: WarpGeometry, kind="gauss", max_sigma=10.0, o
     po = _planes_chw(o)
     _lib.check(_lib.lib().lerf_warp(C.byref(pf), ph, H, W, N, geo.ref(), KINDS[kind], float(max_sigma),
                                     C.byref(po), _lib.current_stream()), "lerf_warp")
+    return o
+
+
+def remap_hwc_u8(feat_u8, hq_u8, geo: RemapGeometry, kind="gauss", max_sigma=10.0, out="u8"):
+    """warp_hwc_u8 by a coordinate map (lerf_remap)"""
+    torch = _torch()
+    feat = feat_u8.contiguous()
+    H, W, Cn = feat.shape
+    if (H, W) != geo.in_hw:
+        raise ValueError("the maps do not match the geometry's frame")
+    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
+    o = torch.empty((geo.out_hw[0], geo.out_hw[1], Cn), dtype=_out_dtype(out), device=feat.device)
+    pf = _planes_hwc(feat)
+    if nh:
+        hq = hq_u8.contiguous()
+        ph, _keep = _hyper_planes(hq, "hwck", nh)
+    else:
+        ph = None
+    po = _planes_hwc(o)
+    g, _keepc = geo.struct(feat.device)
+    _lib.check(_lib.lib().lerf_remap(C.byref(pf), ph, H, W, Cn, C.byref(g), KINDS[kind], float(max_sigma),
+                                     C.byref(po), _lib.current_stream()), "lerf_remap")
+    return o
+
+
+def remap_planar(feat, hypers, geo: RemapGeometry, kind="gauss", max_sigma=10.0, out="f32"):
+    """warp_planar by a coordinate map (lerf_remap): float32 [N,H,W] planes -> [N,oH,oW]"""
+    torch = _torch()
+    feat = feat.contiguous().float()
+    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
+    N, H, W = feat.shape
+    if (H, W) != geo.in_hw:
+        raise ValueError("the maps do not match the geometry's frame")
+    o = torch.empty((N, geo.out_hw[0], geo.out_hw[1]), dtype=_out_dtype(out), device=feat.device)
+    pf = _planes_chw(feat)
+    if nh:
+        hypers = [h.contiguous().float() for h in hypers[:nh]]
+        ph, _keep = _hyper_planes(hypers, "planar", nh)
+    else:
+        ph = None
+    po = _planes_chw(o)
+    g, _keepc = geo.struct(feat.device)
+    _lib.check(_lib.lib().lerf_remap(C.byref(pf), ph, H, W, N, C.byref(g), KINDS[kind], float(max_sigma),
+                                     C.byref(po), _lib.current_stream()), "lerf_remap")
     return o
 
 

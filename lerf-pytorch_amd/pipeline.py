@@ -129,6 +129,44 @@ class LerfEngine:
         return o, mask
 
 
+    # -- remap: the warp by a dense coordinate map
+    def remap(self, img, coords, border=4, return_mask=True, out="u8"):
+        """uint8 [H,W,C] -> (uint8 [oH,oW,C], bool mask [oH,oW,C]) like warp(), with the source position of every output pixel
+        read from `coords` ([oH,oW,2] float64 / float32 (row, col), numpy or a device tensor; or an ops.RemapGeometry of this
+        engine's support, which keeps the uploaded map between frames).  Same path selection as warp() minus the tile-fused
+        branch (a dense map has no closed-form tile boxes); the mask is the NEAREST S = 1 remap of the white frame with a
+        `border`-px black rim."""
+        torch = _lib.require_gpu()
+        x, as_np = self._dev(img)
+        H, W, Cn = x.shape
+        if isinstance(coords, ops.RemapGeometry):
+            geo = coords
+            if geo.in_hw != (H, W) or geo.S != self.support:
+                raise ValueError("the RemapGeometry was built for another frame size or support")
+            src = geo.device_coords(x.device)
+        else:
+            src = coords.to(x.device) if isinstance(coords, torch.Tensor) else coords
+            geo = ops.RemapGeometry((H, W), src, self.support)
+            src = geo.device_coords(x.device)
+        if self._fused_stages_ok(x) and out == "u8":
+            o = ops.remap_packed(ops.stages_packed(x, self.luts), geo, self.kind, self.max_sigma, out=out)
+        else:
+            # float outputs: float64 arithmetic in the direct kernel (f32 = rounded once at the store)
+            if self._fused_stages_ok(x):
+                feat, hq = ops.unpack_stages(ops.stages_packed(x, self.luts), self.luts.oC)
+            else:
+                feat, hq = ops.lut_stages(x, self.luts)
+            o = ops.remap_hwc_u8(feat, hq, geo, self.kind, self.max_sigma, out=out)
+        mask = None
+        if return_mask:
+            white = torch.zeros((H, W, Cn), dtype=torch.uint8, device=x.device)
+            white[border:H - border, border:W - border] = 255
+            ngeo = ops.RemapGeometry((H, W), src, 1)
+            mask = ops.remap_hwc_u8(white, None, ngeo, "nearest", 1.0, out="f32") == 255
+        if as_np:
+            return o.cpu().numpy(), (mask.cpu().numpy() if mask is not None else None)
+        return o, mask
+
     def warp_many(self, imgs, matrices, out_hws, border=4):
         """The warp harness over a folder (eval_lut_warp.py:42-68): the LUT stages of ALL images in one ragged launch pair,
         then one warp + one mask launch per image (every image has its own homography and size).
@@ -165,3 +203,7 @@ def sr(img_u8_hwc, scale, model="lerf-g", support=2, max_sigma=10.0):
 
 def warp(img_u8_hwc, matrix, out_hw, model="lerf-g", support=2, max_sigma=10.0):
     return _engine(model, support, max_sigma).warp(img_u8_hwc, matrix, out_hw)
+
+
+def remap(img_u8_hwc, coords, model="lerf-g", support=2, max_sigma=10.0):
+    return _engine(model, support, max_sigma).remap(img_u8_hwc, coords)

@@ -229,3 +229,61 @@ class Lanczos3Warp2dNumpy(Warp2dNumpy):
 
     def warp(self, input):
         return self._run("lanczos3", input, [], 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Remap twins: the *Warp2dNumpy classes with set_shape(in_shape, coords) in place of (in_shape, matrix, out_shape) -- the
+# projected grid comes from a dense coordinate map ([oH, oW, 2] (row, col), unclipped: coords.py) instead of a matrix
+# (ops.RemapGeometry).  On coords.from_homography(matrix, out_hw) they return what the *Warp2dNumpy classes return.
+# ---------------------------------------------------------------------------------------------------------------------
+class Remap2dNumpy(Warp2dNumpy):
+    """Coordinate-map geometry holder."""
+
+    def set_shape(self, in_shape, coords):
+        in_shape = list(in_shape)                                           # [C, H, W]
+        self.in_shape, self.coords = in_shape, coords
+        self.in_sz = [in_shape[1], in_shape[2]]
+        self.geo = ops.RemapGeometry(self.in_sz, coords, self.support_sz, pad_mode=self._pad_code)
+        self.out_sz = list(self.geo.out_hw)
+        self.out_shape = [in_shape[0]] + self.out_sz
+
+    def _run(self, kind, input, hypers, max_sigma):
+        x = _to_dev(input)
+        if list(x.shape) != list(self.in_shape):
+            raise ValueError("input shape {} does not match set_shape({})".format(list(x.shape), self.in_shape))
+        hs = [_to_dev(h) for h in hypers]
+        return _result(ops.remap_planar(x, hs, self.geo, kind, max_sigma, out="f64"), [input] + list(hypers))
+
+
+class NearestRemap2dNumpy(Remap2dNumpy):
+    def __init__(self, support_sz=1, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("nearest", input, [], 1.0)
+
+
+class SteeringGaussianRemap2dNumpy(Remap2dNumpy):
+    def __init__(self, support_sz=4, device="CPU", pad_mode="constant", max_sigma=10):
+        super().__init__(support_sz, device, pad_mode)
+        self.max_sigma = max_sigma
+
+    def warp(self, input, rho, sigma_x, sigma_y):
+        return self._run("gauss", input, [rho, sigma_x, sigma_y], self.max_sigma)
+
+
+class AmplifiedLinearRemap2dNumpy(Remap2dNumpy):
+    def __init__(self, support_sz=2, device="CPU", pad_mode="constant", max_sigma=1):
+        super().__init__(support_sz, device, pad_mode)
+        self.max_sigma = max_sigma
+
+    def warp(self, input, alpha):
+        return self._run("linear", input, [alpha], self.max_sigma)
+
+
+class BicubicRemap2dNumpy(Remap2dNumpy):
+    def __init__(self, support_sz=4, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("cubic", input, [], 1.0)

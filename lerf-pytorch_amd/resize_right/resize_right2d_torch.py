@@ -296,3 +296,69 @@ class Lanczos3Warp2dTorch(Warp2dTorch):
 
     def warp(self, input):
         return self._run("lanczos3", input, [], 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Remap twins: the *Warp2dTorch classes with set_shape(in_shape, coords) in place of (in_shape, matrix, out_shape) -- the
+# projected grid comes from a dense coordinate map ([oH, oW, 2] (row, col), unclipped: coords.py; numpy or a device tensor)
+# instead of a matrix (ops.RemapGeometry).  FORWARD ONLY: there is no backward kernel for the remap yet (lerf_warp_bwd shows
+# the shape it would take), so an input that requires grad is an error rather than a silently detached result.
+# ---------------------------------------------------------------------------------------------------------------------
+class Remap2dTorch(Warp2dTorch):
+    def set_shape(self, in_shape, coords):
+        in_shape = list(in_shape)                                           # [B, C, H, W]
+        self.in_shape, self.coords = in_shape, coords
+        self.in_sz = [in_shape[2], in_shape[3]]
+        self.geo = ops.RemapGeometry(self.in_sz, coords, self.support_sz, pad_mode=self._pad_code)
+        self.out_sz = list(self.geo.out_hw)
+        self.out_shape = in_shape[:2] + self.out_sz
+
+    def _run(self, kind, input, hypers, max_sigma):
+        _check_dev(input, "input")
+        B, Cn, H, W = input.shape
+        if [H, W] != list(self.in_sz):
+            raise ValueError("input shape does not match set_shape")
+        x = input.reshape(B * Cn, H, W)
+        hs = []
+        for h in hypers:
+            _check_dev(h, "hyper-parameter map")
+            hs.append(h.reshape(B * Cn, H, W))
+        if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + hs):
+            raise NotImplementedError("the remap classes are forward-only: an input requires grad and there is no remap backward "
+                                      "(detach the inputs or run under torch.no_grad(); the *Warp2dTorch classes differentiate)")
+        out = ops.remap_planar(x, hs, self.geo, kind, max_sigma, out="f64")
+        return out.reshape(B, Cn, self.out_sz[0], self.out_sz[1])
+
+
+class NearestRemap2dTorch(Remap2dTorch):
+    def __init__(self, support_sz=1, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("nearest", input, [], 1.0)
+
+
+class SteeringGaussianRemap2dTorch(Remap2dTorch):
+    def __init__(self, support_sz=4, device="GPU", pad_mode="constant", max_sigma=10):
+        super().__init__(support_sz, device, pad_mode)
+        self.max_sigma = max_sigma
+
+    def warp(self, input, rho, sigma_x, sigma_y):
+        return self._run("gauss", input, [rho, sigma_x, sigma_y], self.max_sigma)
+
+
+class AmplifiedLinearRemap2dTorch(Remap2dTorch):
+    def __init__(self, support_sz=2, device="GPU", pad_mode="constant", max_sigma=1):
+        super().__init__(support_sz, device, pad_mode)
+        self.max_sigma = max_sigma
+
+    def warp(self, input, alpha):
+        return self._run("linear", input, [alpha], self.max_sigma)
+
+
+class BicubicRemap2dTorch(Remap2dTorch):
+    def __init__(self, support_sz=4, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("cubic", input, [], 1.0)
