@@ -337,7 +337,7 @@ int lerf_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, in
 /* Stage 3 by a dense coordinate map (lerf_remap_geo_t): lerf_warp / lerf_warp_packed with the point of every output pixel read from
  * the map.  Same operands, dtype table, kinds, supports, pad modes and arithmetic as their namesakes -- after the point is known the
  * kernels run the same code -- so the map of a homography (its unclipped projected grid) gives lerf_warp's bytes.  There is no
- * tile-fused remap (a dense map has no closed-form tile boxes) and no backward.
+ * tile-fused remap (a dense map has no closed-form tile boxes); the backward is lerf_remap_bwd (at the end of this header).
  *   lerf_remap_host_geometry   host, no GPU: geo->coords is HOST memory; writes what the kernels derive from the map -- pads[2] =
  *                              the low pads (row, col) and, per output pixel, the clipped point gr / gc (padded coordinates) and the
  *                              support's first tap lr / lc ([out_h * out_w] each; any may be NULL). */
@@ -633,6 +633,22 @@ int lerf_patch_batch_u8(const uint8_t* pool, int64_t pool_bytes, const lerf_patc
  * conflict-free.  The caller times the launch (one workgroup per CU: wave-gathers per CU = 160 x iters) and owns `sink`
  * (4 bytes of device memory, practically never written).  Not part of the reference's path: a ruler for it. */
 int lerf_ubench_lds_gather(int pattern, int iters, int workgroups, uint32_t* sink, void* stream);
+
+/* Backward of lerf_remap on planar float32 maps: lerf_warp_bwd with the point of every output pixel read from the coordinate map
+ * (the same operands, kinds, supports, pad modes, formulas, NaN rule and float-atomic accumulation; see there), plus the gradient
+ * with respect to the MAP, which a homography has no tensor for.
+ * grad_coords: float64 [N][out_h][out_w][2], dense, 16-byte aligned, PER PLANE -- d loss / d (row, col) of entry (i, j) through
+ * plane n; the caller sums over the planes that share the map.  The point enters through the distances alone; the tap set, the
+ * pads and the amplified-linear classes are piecewise constant, so this is the gradient autograd gives with them held fixed, with
+ * torch.clamp's backward for the clip to [0, H] x [0, W] (it passes at the borders, is 0 outside and for +-inf).  Float64
+ * throughout; every element has one writer (a plain load-add-store: ACCUMULATED into like the other gradients, no atomics,
+ * bit-equal from run to run).  Identically 0 for LERF_KIND_NEAREST.
+ * A NaN entry is masked: the pixel contributes to no gradient and adds nothing to its own.  Any gradient pointer may be NULL and
+ * is then skipped.  geo: as lerf_remap takes it (row_stride and explicit low pads included, so a row tile of a larger map works:
+ * grad_out and grad_coords are then the tile's rows).  Refuses what lerf_warp_bwd and lerf_remap refuse. */
+int lerf_remap_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W,
+                   const lerf_remap_geo_t* geo, int kind, double max_sigma, const double* grad_out,
+                   float* grad_feat, float* grad_h0, float* grad_h1, float* grad_h2, double* grad_coords, void* stream);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,7 @@ EXPORTS = [
     "lerf_warp_tile_boxes", "lerf_warp_fused_supported", "lerf_warp_fused_u8",
     "lerf_remap", "lerf_remap_packed", "lerf_remap_host_geometry",
     "lerf_metric_y_sse_u8", "lerf_metric_ssim_y_u8", "lerf_metric_masked_sse_u8",
-    "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd",
+    "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd", "lerf_remap_bwd",
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_srnet_fwd_f32", "lerf_srnet_bwd_workspace_bytes", "lerf_srnet_bwd_f32",
     "lerf_imdn_weight_floats", "lerf_imdn_workspace_bytes", "lerf_imdn_fwd_f32",
     "lerf_imdn_saved_bytes", "lerf_imdn_fwd_train_f32", "lerf_imdn_bwd_workspace_bytes", "lerf_imdn_bwd_f32",
@@ -249,6 +249,8 @@ def lib():
                                       C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_warp_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WarpGeo),
                                 C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lerf_remap_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo),
+                                 C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_srnet_weight_floats.restype = C.c_size_t
     L.lerf_srnet_weight_floats.argtypes = [C.c_int]
     L.lerf_srnet_to_lut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -3,7 +3,8 @@
 A map is a float64 (or float32) array [oH, oW, 2]; entry (i, j) is (row, col) of the source position of output pixel
 (i, j), in the reference's convention: integers are pixel indices, the values are what Warp2dNumpy.get_projected_grid2d
 (resize_right/resize_right2d_numpy.py:306-342) holds BEFORE its clip -- the remap clips.  Host numpy: a map is built once per
-transform, not per frame.
+transform, not per frame -- except from_flow_torch, which builds the map of a flow on the flow's device and keeps it in the
+autograd graph (a flow fitted by gradient).
 """
 from __future__ import annotations
 
@@ -59,6 +60,19 @@ def from_flow(flow):
         raise ValueError("flow must be [H, W, 2]")
     ii, jj = _grid(f.shape[:2])
     return np.ascontiguousarray(np.stack([ii + f[..., 0], jj + f[..., 1]], axis=-1))
+
+
+def from_flow_torch(flow):
+    """from_flow with torch ops on the flow's device: flow [H, W, 2] tensor (float32 or float64) -> identity + flow in the flow's
+    dtype, same device.  A flow that requires grad stays in the graph, so a remap class that has opted in with enable_backward()
+    hands it d loss / d flow (resize_right2d_torch.Remap2dTorch)."""
+    import torch
+    if not isinstance(flow, torch.Tensor) or flow.ndim != 3 or flow.shape[2] != 2 or not flow.is_floating_point():
+        raise ValueError("flow must be a floating-point [H, W, 2] tensor")
+    ii = torch.arange(flow.shape[0], dtype=flow.dtype, device=flow.device)
+    jj = torch.arange(flow.shape[1], dtype=flow.dtype, device=flow.device)
+    grid = torch.stack(torch.meshgrid(ii, jj, indexing="ij"), dim=-1)
+    return grid + flow
 
 
 def radial(in_hw, out_hw, k1, k2=0.0, centre=None):

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "lerf_kernels.h"
+#include "lerf_remap_point.h"
 
 using namespace lerf;
 
@@ -325,22 +326,6 @@ int lerf_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, in
     int rc = launch_warp_packed(packed, packed_sn, n, H, W, C, g, kind, (float)max_sigma, out->ptr, out->dtype, out->sy, out->sx,
                                 out->sc, out_sn, as_stream(stream));
     return rc != LERF_OK ? rc : check_launch();
-}
-
-// lerf_remap_geo_t -> RemapGeo; what can be checked on the host is (the map's values cannot, and need not be: lerf_remap.hip)
-static int remap_geo(const lerf_remap_geo_t* geo, RemapGeo& m) {
-    if (!geo || !geo->coords || geo->out_h < 1 || geo->out_w < 1) return LERF_EINVAL;
-    if (geo->coords_dtype != LERF_F32 && geo->coords_dtype != LERF_F64) return LERF_EINVAL;
-    const size_t entry = geo->coords_dtype == LERF_F32 ? 8 : 16;               // one aligned load per entry
-    if ((size_t)(uintptr_t)geo->coords % entry != 0 || (geo->row_stride & 1) || geo->row_stride < 2 * (int64_t)geo->out_w) return LERF_EINVAL;
-    if (geo->pad_mode < LERF_PAD_CONSTANT || geo->pad_mode > LERF_PAD_WRAP) return LERF_EINVAL;
-    // explicit low pads: what calc_pad_sz can yield for a clipped point, 0 .. ceil(S / 2) (the field of view starts at >= -S/2)
-    for (int p : {geo->pad_r_lo, geo->pad_c_lo})
-        if (p != LERF_REMAP_PADS_FROM_MAP && (p < 0 || p > LERF_MAX_SUPPORT)) return LERF_EINVAL;
-    m.S = geo->S; m.oH = geo->out_h; m.oW = geo->out_w;
-    m.coords = geo->coords; m.f32 = geo->coords_dtype == LERF_F32; m.stride = geo->row_stride;
-    m.pad_r_lo = geo->pad_r_lo; m.pad_c_lo = geo->pad_c_lo; m.pad_mode = geo->pad_mode;
-    return LERF_OK;
 }
 
 int lerf_remap(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,

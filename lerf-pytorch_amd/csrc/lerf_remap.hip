@@ -7,56 +7,18 @@
 //
 // A kernel here differs from its counterpart in ONE statement: where that one projects (i, j) through the inverse matrix
 // (warp_pixel), this one loads the map entry -- one 16-byte (float64) or 8-byte (float32) load per output pixel, consecutive
-// lanes on consecutive entries -- and clips it (remap_pixel, lerf_host_geometry.h).  Everything from the point on is the shared
-// body of lerf_warp_kernels.h, so the map of a homography gives the homographic warp's bytes.
+// lanes on consecutive entries -- and clips it (remap_entry / remap_pixel, lerf_remap_point.h, shared with the backward).
+// Everything from the point on is the shared body of lerf_warp_kernels.h, so the map of a homography gives the homographic
+// warp's bytes.
 //
 // Addresses: the map is read at (i, j) inside the launch's [oH][oW] only; the point is clipped to [0, H] x [0, W] BEFORE any
 // conversion to int (clip_coord sends NaN to 0 and +-inf to the borders), and every tap index passes axis_tap's clamps, so no
 // map value -- NaN, infinite, or 1e300 -- can form an address outside the operands.  A NaN entry reads nothing further and
 // stores 0 (uint8) / NaN (float).
 #include "lerf_warp_kernels.h"
+#include "lerf_remap_point.h"
 
 namespace lerf {
-
-struct MapPoint {
-    double r, c;
-};
-
-// entry (i, j) of the map in ONE load; float32 entries are promoted exactly
-__device__ __forceinline__ MapPoint remap_entry(const RemapGeo& m, int i, int j) {
-    const int64_t o = (int64_t)i * m.stride + 2 * (int64_t)j;
-    if (m.f32) {
-        const float2 v = *reinterpret_cast<const float2*>(static_cast<const float*>(m.coords) + o);
-        return {(double)v.x, (double)v.y};
-    }
-    const double2 v = *reinterpret_cast<const double2*>(static_cast<const double*>(m.coords) + o);
-    return {v.x, v.y};
-}
-
-__device__ __forceinline__ bool no_point(const MapPoint& q) { return q.r != q.r || q.c != q.c; }
-
-// the WarpGeo the shared bodies read (S, output size, low pads, pad mode; no matrix, no rectangle offsets).  Low pads the caller
-// left to the map come from its first entry: a uniform load, no host round trip for a device-resident map.
-__device__ __forceinline__ WarpGeo remap_warp_geo(const RemapGeo& m, int H, int W) {
-    WarpGeo g;
-    g.S = m.S; g.oH = m.oH; g.oW = m.oW;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) g.minv[k] = 0.0;
-    g.pad_r_lo = m.pad_r_lo; g.pad_c_lo = m.pad_c_lo;
-    if (m.pad_r_lo < 0 || m.pad_c_lo < 0) {
-        const MapPoint q0 = remap_entry(m, 0, 0);
-        if (m.pad_r_lo < 0) g.pad_r_lo = remap_pad_lo(q0.r, H, m.S);
-        if (m.pad_c_lo < 0) g.pad_c_lo = remap_pad_lo(q0.c, W, m.S);
-    }
-    g.pad_r_hi = 0; g.pad_c_hi = 0;
-    g.pad_mode = m.pad_mode;
-    g.oy0 = 0; g.ox0 = 0;
-    return g;
-}
-
-__device__ __forceinline__ WarpPixel remap_pixel(const WarpGeo& g, const MapPoint& q, int H, int W) {
-    return remap_pixel(q.r, q.c, g.S, g.pad_r_lo, g.pad_c_lo, H, W);
-}
 
 // ---------------------------------------------------------------------------
 // general remap

@@ -29,6 +29,30 @@ __device__ __forceinline__ double fixed_kernel_1d(int kind, double x) {
     return ((-1.0 <= x && x < 0.0) ? 1.0 : 0.0) + ((0.0 <= x && x <= 1.0) ? 1.0 : 0.0);   // box :67-70
 }
 
+// d/dx of fixed_kernel_1d as autograd derives it for the forms of interp_methods.py (the remap's map gradient, lerf_warp_bwd_kernels.h):
+// the support masks are constants, |x|' = sign(x) with sign(0) = 0, the hat's kink at 0 belongs to its right branch (-1), the
+// Lanczos quotient (sin sin + eps) / (pi^2 x^2 / a + eps) is differentiated with its eps, box has no gradient.
+__device__ __forceinline__ double fixed_kernel_1d_deriv(int kind, double x) {
+#pragma clang fp contract(off)
+    const double pi = 3.141592653589793;
+    const double eps = (double)kEps32;
+    if (kind == LERF_KIND_CUBIC) {
+        const double a = fabs(x), sg = x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0);
+        return sg * ((4.5 * (a * a) - 5.0 * a) * (a <= 1.0 ? 1.0 : 0.0) +
+                     (-1.5 * (a * a) + 5.0 * a - 4.0) * ((1.0 < a && a <= 2.0) ? 1.0 : 0.0));
+    }
+    if (kind == LERF_KIND_LANCZOS2 || kind == LERF_KIND_LANCZOS3) {
+        const double a = kind == LERF_KIND_LANCZOS2 ? 2.0 : 3.0;
+        const double s1 = sin(pi * x), c1 = cos(pi * x), s2 = sin(pi * x / a), c2 = cos(pi * x / a);
+        const double num = s1 * s2 + eps, den = (pi * pi * (x * x) / a) + eps;
+        const double dnum = pi * c1 * s2 + (pi / a) * (s1 * c2), dden = 2.0 * (pi * pi) * x / a;
+        return (dnum / den - num * dden / (den * den)) * (fabs(x) < a ? 1.0 : 0.0);
+    }
+    if (kind == LERF_KIND_BILINEAR)
+        return ((-1.0 <= x && x < 0.0) ? 1.0 : 0.0) - ((0.0 <= x && x <= 1.0) ? 1.0 : 0.0);
+    return 0.0;                                                             // box
+}
+
 // tap (a, b) of SR output pixel (i, j) -- column offset a, row offset b -- from its support's left boundaries lr = left_r[i],
 // lc = left_c[j]
 struct SrTap {

@@ -207,6 +207,7 @@ class RemapGeometry:
             raise ValueError("coords must be [oH, oW, 2]")
         if dev:
             torch = _torch()
+            c = c.detach()                   # the geometry reads the map's memory; its graph, if any, is the caller's (_RemapFn)
             if c.dtype not in (torch.float32, torch.float64):
                 raise ValueError("coords must be float32 or float64")
             if c.stride(2) != 1 or c.stride(1) != 2 or c.stride(0) % 2 or c.stride(0) < 2 * c.shape[1] \
@@ -754,6 +755,38 @@ def warp_bwd_planar(feat, hypers, geo: WarpGeometry, kind, max_sigma, grad_out, 
     _lib.check(_lib.lib().lerf_warp_bwd(ptr(feat), hp[0], hp[1], hp[2], N, H, W, geo.ref(), KINDS[kind], float(max_sigma),
                                         ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]),
                                         _lib.current_stream()), "lerf_warp_bwd")
+    return grads
+
+
+def remap_bwd_planar(feat, hypers, geo: RemapGeometry, kind, max_sigma, grad_out, grads, grad_coords=None):
+    """lerf_remap_bwd: accumulate the gradients of remap_planar(feat, hypers, geo, kind, max_sigma, out="f64") for the
+    float64 upstream gradient `grad_out` [N, oH, oW] into `grads` = [grad_feat, grad_h0, grad_h1, grad_h2] (float32
+    [N, H, W] contiguous tensors, or None to skip a map) and, when given, the map gradient into `grad_coords` (float64
+    [N, oH, oW, 2] contiguous, PER PLANE: the caller sums over the planes that share the map).  feat / hypers: float32
+    [N, H, W]."""
+    torch = _torch()
+    feat = feat.contiguous().float()
+    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
+    hs = [h.contiguous().float() for h in hypers[:nh]]
+    g = grad_out.contiguous().double()
+    N, H, W = feat.shape
+    if (H, W) != geo.in_hw:
+        raise ValueError("the maps do not match the geometry's frame")
+    if tuple(g.shape) != (N, geo.out_hw[0], geo.out_hw[1]):
+        raise ValueError("grad_out must be [N, out_h, out_w] of the geometry")
+    grads = list(grads) + [None] * (4 - len(grads))
+    for t in grads:
+        if t is not None and (t.dtype != feat.dtype or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
+            raise ValueError("gradient buffers must be contiguous float32 [N, H, W]")
+    if grad_coords is not None and (grad_coords.dtype != torch.float64 or tuple(grad_coords.shape) != (N,) + tuple(geo.out_hw) + (2,)
+                                    or not grad_coords.is_contiguous()):
+        raise ValueError("grad_coords must be contiguous float64 [N, out_h, out_w, 2]")
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+    hp = [ptr(h) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
+    gs, _keepc = geo.struct(feat.device)
+    _lib.check(_lib.lib().lerf_remap_bwd(ptr(feat), hp[0], hp[1], hp[2], N, H, W, C.byref(gs), KINDS[kind], float(max_sigma),
+                                         ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]), ptr(grad_coords),
+                                         _lib.current_stream()), "lerf_remap_bwd")
     return grads
 
 

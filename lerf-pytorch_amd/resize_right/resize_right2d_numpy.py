@@ -287,3 +287,27 @@ class BicubicRemap2dNumpy(Remap2dNumpy):
 
     def warp(self, input):
         return self._run("cubic", input, [], 1.0)
+
+
+class BilinearRemap2dNumpy(Remap2dNumpy):
+    def __init__(self, support_sz=2, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("bilinear", input, [], 1.0)
+
+
+class Lanczos2Remap2dNumpy(Remap2dNumpy):
+    def __init__(self, support_sz=4, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("lanczos2", input, [], 1.0)
+
+
+class Lanczos3Remap2dNumpy(Remap2dNumpy):
+    def __init__(self, support_sz=6, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("lanczos3", input, [], 1.0)

@@ -8,6 +8,8 @@ The SR classes carry autograd (`_ResizeFn`, HIP backward lerf_resize_bwd_f32: ev
 fixed-kernel subclasses -- and every pad mode, the gradient autograd derives for resize_right2d_torch.py:105-247), and so
 do the warp classes (`_WarpFn`, every kind and pad mode: the gradient autograd derives for the reference's torch warps,
 resize_right2d_torch.py:249-487).  With no operand requiring grad, both run the plain forward and return no graph.
+The remap twins (set_shape takes a coordinate map) differentiate after enable_backward() (`_RemapFn`, lerf_remap_bwd),
+the map included when it is a device tensor that requires grad.
 """
 from __future__ import annotations
 
@@ -301,10 +303,54 @@ class Lanczos3Warp2dTorch(Warp2dTorch):
 # ---------------------------------------------------------------------------------------------------------------------
 # Remap twins: the *Warp2dTorch classes with set_shape(in_shape, coords) in place of (in_shape, matrix, out_shape) -- the
 # projected grid comes from a dense coordinate map ([oH, oW, 2] (row, col), unclipped: coords.py; numpy or a device tensor)
-# instead of a matrix (ops.RemapGeometry).  FORWARD ONLY: there is no backward kernel for the remap yet (lerf_warp_bwd shows
-# the shape it would take), so an input that requires grad is an error rather than a silently detached result.
+# instead of a matrix (ops.RemapGeometry).  Forward-only by default: an input that requires grad is an error rather than a
+# silently detached result.  enable_backward() (opt-in, like IMDN2's) turns autograd on: `_RemapFn`, HIP backward
+# lerf_remap_bwd -- the image and hyper-parameter gradients of the warp classes and, when the map given to set_shape is a
+# device tensor that requires grad, the gradient with respect to the map (a flow field, a mesh, a lens model fitted by
+# gradient: coords.from_flow_torch keeps a flow in the graph).
 # ---------------------------------------------------------------------------------------------------------------------
+class _RemapFn(torch.autograd.Function):
+    """lerf_remap forward (float64 out), lerf_remap_bwd backward.  `cm` is the map given to set_shape when it is a device
+    tensor that requires grad (else None): its gradient is the per-plane map gradient summed over the planes, in the map's
+    dtype and shape (autograd carries it through a strided view).  Leaf gradients come back in each leaf's dtype."""
+
+    @staticmethod
+    def forward(ctx, geo, kind, max_sigma, cm, x, *hs):
+        xf = x.detach().contiguous().float()
+        hf = [h.detach().contiguous().float() for h in hs]
+        out = ops.remap_planar(xf, hf, geo, kind, max_sigma, out="f64")
+        # the kernels read the map through the geometry's detached alias; saving the map itself lets autograd's version counter
+        # refuse a backward after the map was modified in place (it would differentiate another map than the forward used)
+        ctx.save_for_backward(xf, *hf, *([] if cm is None else [cm]))
+        ctx.meta = (geo, kind, float(max_sigma), [t.dtype for t in (x,) + hs], None if cm is None else cm.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        geo, kind, max_sigma, dtypes, cdtype = ctx.meta
+        saved = ctx.saved_tensors                                          # raises if a saved tensor was modified in place
+        x, *hs = saved if cdtype is None else saved[:-1]
+        need = ctx.needs_input_grad[4:]
+        grads = [torch.zeros_like(x) if need[k] else None for k in range(1 + len(hs))]
+        gc = None
+        if cdtype is not None and ctx.needs_input_grad[3]:
+            gc = torch.zeros((x.shape[0],) + tuple(geo.out_hw) + (2,), dtype=torch.float64, device=x.device)
+        ops.remap_bwd_planar(x, hs, geo, kind, max_sigma, grad_out, grads, gc)
+        return (None, None, None, None if gc is None else gc.sum(0).to(cdtype)) + \
+            tuple(g.to(dt) if g is not None else None for g, dt in zip(grads, dtypes))
+
+
 class Remap2dTorch(Warp2dTorch):
+    _backward = False
+
+    def enable_backward(self):
+        """Opt in to autograd through warp(): image, hyper-parameter and map gradients by lerf_remap_bwd.  Returns self.
+        The map gets a gradient when the tensor given to set_shape lives on the GPU and requires grad; a numpy map is data; a
+        HOST tensor that requires grad is refused (ValueError) rather than silently detached.  The geometry reads the map's
+        memory in place: modifying a leaf map in place between warp() and backward() is an error autograd reports."""
+        self._backward = True
+        return self
+
     def set_shape(self, in_shape, coords):
         in_shape = list(in_shape)                                           # [B, C, H, W]
         self.in_shape, self.coords = in_shape, coords
@@ -323,10 +369,20 @@ class Remap2dTorch(Warp2dTorch):
         for h in hypers:
             _check_dev(h, "hyper-parameter map")
             hs.append(h.reshape(B * Cn, H, W))
-        if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + hs):
-            raise NotImplementedError("the remap classes are forward-only: an input requires grad and there is no remap backward "
-                                      "(detach the inputs or run under torch.no_grad(); the *Warp2dTorch classes differentiate)")
-        out = ops.remap_planar(x, hs, self.geo, kind, max_sigma, out="f64")
+        cm = self.coords if isinstance(self.coords, torch.Tensor) and self.coords.requires_grad else None
+        if cm is not None and not cm.is_cuda and torch.is_grad_enabled():
+            raise ValueError("the coordinate map requires grad but lives on the host: it was uploaded as data and would get no "
+                             "gradient (build it on the GPU, e.g. coords.from_flow_torch of a device flow, or detach it)")
+        if cm is not None and not cm.is_cuda:
+            cm = None
+        if torch.is_grad_enabled() and (cm is not None or any(t.requires_grad for t in [x] + hs)):
+            if not self._backward:
+                raise NotImplementedError("the remap classes are forward-only: an input requires grad and there is no remap backward "
+                                          "(detach the inputs or run under torch.no_grad(); the *Warp2dTorch classes differentiate) "
+                                          "unless the class has opted in with enable_backward()")
+            out = _RemapFn.apply(self.geo, kind, max_sigma, cm, x, *hs)
+        else:
+            out = ops.remap_planar(x, hs, self.geo, kind, max_sigma, out="f64")
         return out.reshape(B, Cn, self.out_sz[0], self.out_sz[1])
 
 
@@ -362,3 +418,27 @@ class BicubicRemap2dTorch(Remap2dTorch):
 
     def warp(self, input):
         return self._run("cubic", input, [], 1.0)
+
+
+class BilinearRemap2dTorch(Remap2dTorch):
+    def __init__(self, support_sz=2, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("bilinear", input, [], 1.0)
+
+
+class Lanczos2Remap2dTorch(Remap2dTorch):
+    def __init__(self, support_sz=4, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("lanczos2", input, [], 1.0)
+
+
+class Lanczos3Remap2dTorch(Remap2dTorch):
+    def __init__(self, support_sz=6, device="CPU", pad_mode="constant"):
+        super().__init__(support_sz, device, pad_mode)
+
+    def warp(self, input):
+        return self._run("lanczos3", input, [], 1.0)
