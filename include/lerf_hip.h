@@ -650,6 +650,71 @@ int lerf_remap_bwd(const float* feat, const float* h0, const float* h1, const fl
                    const lerf_remap_geo_t* geo, int kind, double max_sigma, const double* grad_out,
                    float* grad_feat, float* grad_h0, float* grad_h1, float* grad_h2, double* grad_coords, void* stream);
 
+/* ---- Coordinate maps on the device (csrc/lerf_coords.hip, arithmetic: csrc/lerf_coords_models.h).  A map is what
+ * lerf_remap_geo_t.coords reads: [oH][row_stride] elements, (row, col) pairs, entry (i, j) at out + i * row_stride + 2 * j,
+ * LERF_F64 or LERF_F32, row_stride even and >= 2 * oW, the base aligned to one entry (16 / 8 bytes).  Values are UNCLIPPED source
+ * positions; the remap clips.  Everything is computed in float64 with + - * / only and no FMA contraction, so each device entry
+ * point and its *_host twin (the same statements in a plain loop over HOST pointers; no GPU needed) agree bit for bit; a
+ * float32 map is the float64 value rounded once at the store.  Device entry points: one launch on `stream` (two for
+ * lerf_coords_mesh_bwd), no sync, no allocation, no global state.  Refused (LERF_EINVAL, nothing is launched or written): a
+ * null pointer, oH or oW < 1, gh or gw < 2, an odd or short row stride, a misaligned base pointer, an unknown model, dtype or
+ * interp, a parameter count that is not the model's, a non-finite model parameter, a negative origin or a tile outside the
+ * whole map, a short workspace.  Operands must not overlap the output. */
+enum { LERF_COORDS_HOMOGRAPHY = 0, LERF_COORDS_RADIAL = 1, LERF_COORDS_BROWN = 2 };
+enum { LERF_MESH_BILINEAR = 0, LERF_MESH_BICUBIC = 1 };
+#define LERF_COORDS_MAX_PARAMS 21
+
+/* Entry (i, j) of the tile = the model's point of output pixel (i0 + i, j0 + j): a tile of a larger map built in place (out = the
+ * tile's first entry, row_stride the whole map's) equals those entries of the whole map bit for bit.  params: HOST doubles,
+ *   LERF_COORDS_HOMOGRAPHY  9: the INVERSE matrix, row-major; the warp kernels' projection without its clip (lerf_remap on this
+ *                              map = lerf_warp of the matrix, bit for bit)
+ *   LERF_COORDS_RADIAL      8: cr, cc, no, ni, hr, hc, k1, k2 -- centre (row, col) in the source, half-diagonals of the output
+ *                              and of the source, half-extents (oH - 1) / 2, (oW - 1) / 2 of the WHOLE output, coefficients:
+ *                              ur = (i - hr) / no, uc = (j - hc) / no, r2 = ur ur + uc uc, f = 1 + k1 r2 + (k2 r2) r2,
+ *                              row = cr + (ur f) ni, col = cc + (uc f) ni
+ *   LERF_COORDS_BROWN      21: m[9] = inv(new_K . R) row-major, fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6 -- the pinhole +
+ *                              Brown-Conrady model of cv::initUndistortRectifyMap without skew: (x, y) = m (j, i, 1) divided
+ *                              through, r2 = x x + y y, rad = (1 + r2 (k1 + r2 (k2 + r2 k3))) / (1 + r2 (k4 + r2 (k5 + r2 k6))),
+ *                              x'' = x rad + 2 p1 x y + p2 (r2 + 2 x x), y'' = y rad + p1 (r2 + 2 y y) + 2 p2 x y,
+ *                              col = fx x'' + cx, row = fy y'' + cy
+ * (the rounding order of every statement: the top of csrc/lerf_coords_models.h). */
+int lerf_coords_build(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride,
+                      int oH, int oW, int i0, int j0, void* stream);
+int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride,
+                           int oH, int oW, int i0, int j0);
+
+/* Mesh upsample: ctrl [gh][gw][2] (LERF_F32 / LERF_F64, dense, entry-aligned) holds absolute source positions at control
+ * vertices placed align-corners over the WHOLE output [full_h][full_w] (vertex a at output row a (full_h - 1) / (gh - 1)); the
+ * tile [oH][oW] at origin (i0, j0) of it is written (i0 + oH <= full_h, j0 + oW <= full_w).  interp: LERF_MESH_BILINEAR, or
+ * LERF_MESH_BICUBIC = Keys A = -0.75 with border taps clamped, torch's upsample_bicubic2d(align_corners=True) forms. */
+int lerf_coords_mesh(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w,
+                     void* out, int out_dtype, int64_t row_stride, int oH, int oW, int i0, int j0, void* stream);
+int lerf_coords_mesh_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w,
+                          void* out, int out_dtype, int64_t row_stride, int oH, int oW, int i0, int j0);
+
+/* Adjoint of lerf_coords_mesh over a whole map (the exact transpose of its weights, clamped bicubic taps included):
+ * grad_map float64 [oH][oW][2] dense, 16-byte aligned (what lerf_remap_bwd's grad_coords holds after the sum over planes);
+ * grad_ctrl float64 [gh][gw][2] dense, 16-byte aligned, ACCUMULATED into (plain load-add-store, one writer per vertex).
+ * Gather-shaped in two separable passes -- rows into the workspace ([gh][oW][2] doubles), then columns -- each sum in a fixed
+ * order, no atomics: two runs are bit-equal.  workspace: device, >= lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW) bytes
+ * (0 from the query for refused sizes), 16-byte aligned, contents arbitrary, used by this call's two launches only. */
+size_t lerf_coords_mesh_bwd_workspace_bytes(int gh, int gw, int oH, int oW);
+int lerf_coords_mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Composition C[i][j] = A(B[i][j]): the outer map a [aH][aW][2] sampled bilinearly at the position the inner map b [oH][oW][2]
+ * holds, so that remapping by b the result of remapping by a describes the geometry of ONE remap by C.  Each of a, b, out obeys
+ * the strided map contract with its own dtype.  Per axis the position is clipped onto [0, aH - 1] (-inf -> 0, +inf -> aH - 1),
+ * i0 = min(floor(r), aH - 2) (0 when aH == 1), t = r - i0.  A NaN in either coordinate of b gives (NaN, NaN) and reads nothing
+ * of a; a tap whose weight is exactly 0 is not read (a NaN in a reaches C only through a tap that counts); no value of b can
+ * form an address outside a. */
+int lerf_coords_compose(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                        const void* b, int b_dtype, int64_t b_row_stride,
+                        void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, void* stream);
+int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                             const void* b, int b_dtype, int64_t b_row_stride,
+                             void* out, int out_dtype, int64_t out_row_stride, int oH, int oW);
+
 #ifdef __cplusplus
 }
 #endif

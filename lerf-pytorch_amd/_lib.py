@@ -53,6 +53,8 @@ EXPORTS = [
     "lerf_imdn_weight_floats", "lerf_imdn_workspace_bytes", "lerf_imdn_fwd_f32",
     "lerf_imdn_saved_bytes", "lerf_imdn_fwd_train_f32", "lerf_imdn_bwd_workspace_bytes", "lerf_imdn_bwd_f32",
     "lerf_rr_axis", "lerf_rr_adjoint_csr", "lerf_patch_batch_u8",
+    "lerf_coords_build", "lerf_coords_build_host", "lerf_coords_mesh", "lerf_coords_mesh_host", "lerf_coords_mesh_bwd_workspace_bytes",
+    "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -123,6 +125,11 @@ class WarpGeo(C.Structure):
 
 
 REMAP_PADS_FROM_MAP = -1
+
+# coordinate-map builders (include/lerf_hip.h LERF_COORDS_*, LERF_MESH_*)
+COORDS_MODELS = {"homography": 0, "radial": 1, "brown": 2}
+COORDS_MODEL_PARAMS = {"homography": 9, "radial": 8, "brown": 21}
+MESH_INTERPS = {"bilinear": 0, "bicubic": 1}
 
 
 class RemapGeo(C.Structure):       # lerf_remap_geo_t
@@ -279,6 +286,15 @@ def lib():
                                       C.c_void_p]
     L.lerf_patch_batch_u8.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    _build = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+    _mesh = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+    _compose = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int]
+    L.lerf_coords_build.argtypes, L.lerf_coords_build_host.argtypes = _build + [C.c_void_p], _build
+    L.lerf_coords_mesh.argtypes, L.lerf_coords_mesh_host.argtypes = _mesh + [C.c_void_p], _mesh
+    L.lerf_coords_compose.argtypes, L.lerf_coords_compose_host.argtypes = _compose + [C.c_void_p], _compose
+    L.lerf_coords_mesh_bwd_workspace_bytes.restype = C.c_size_t
+    L.lerf_coords_mesh_bwd_workspace_bytes.argtypes = [C.c_int] * 4
+    L.lerf_coords_mesh_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -370,6 +386,78 @@ def remap_host_geometry(coords: np.ndarray, in_hw, S: int, pads=None):
     check(lib().lerf_remap_host_geometry(C.byref(g), int(in_hw[0]), int(in_hw[1]), gr.ctypes.data, gc.ctypes.data, lr.ctypes.data,
                                          lc.ctypes.data, out.ctypes.data), "lerf_remap_host_geometry")
     return gr, gc, lr, lc, (int(out[0]), int(out[1]))
+
+
+def _np_dt(a):
+    if a.dtype == np.float32:
+        return LERF_F32
+    if a.dtype == np.float64:
+        return LERF_F64
+    raise ValueError("float32 or float64 expected, got %s" % a.dtype)
+
+
+def _np_map(a, what):
+    """(array, row stride in elements) of a host map under the strided contract: [h, w, 2], pairs contiguous, rows free"""
+    if not isinstance(a, np.ndarray) or a.ndim != 3 or a.shape[2] != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("%s must be a numpy [h, w, 2] array" % what)
+    e = a.itemsize
+    _np_dt(a)
+    if a.strides[2] != e or a.strides[1] != 2 * e or a.strides[0] % e:
+        raise ValueError("%s: contiguous (row, col) pairs, column stride 2" % what)
+    return a, a.strides[0] // e
+
+
+def _np_out(out, out_hw, dtype, what):
+    if out is None:
+        out = np.empty((int(out_hw[0]), int(out_hw[1]), 2), dtype=np.dtype(dtype))
+    elif tuple(out.shape[:2]) != (int(out_hw[0]), int(out_hw[1])):
+        raise ValueError("%s: out must be [%d, %d, 2]" % (what, out_hw[0], out_hw[1]))
+    return _np_map(out, "out")
+
+
+def coords_model_params(model, params):
+    """(model code, float64 parameter vector) of a coordinate-map model; the count is checked by the library"""
+    if model not in COORDS_MODELS:
+        raise ValueError("unknown coordinate-map model %r (known: %s)" % (model, ", ".join(COORDS_MODELS)))
+    return COORDS_MODELS[model], np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+
+
+def mesh_interp_code(interp):
+    if interp not in MESH_INTERPS:
+        raise ValueError("interp is 'bilinear' or 'bicubic', not %r" % (interp,))
+    return MESH_INTERPS[interp]
+
+
+def coords_build_host(model, params, out_hw, dtype=np.float64, out=None, origin=(0, 0)):
+    """lerf_coords_build_host: the map of a model built on the host by the kernels' own arithmetic (bit-equal to the device's)"""
+    code, p = coords_model_params(model, params)
+    out, stride = _np_out(out, out_hw, dtype, "lerf_coords_build_host")
+    check(lib().lerf_coords_build_host(code, p.ctypes.data, int(p.size), out.ctypes.data, _np_dt(out), stride, int(out_hw[0]),
+                                       int(out_hw[1]), int(origin[0]), int(origin[1])), "lerf_coords_build_host")
+    return out
+
+
+def coords_mesh_host(ctrl, out_hw, interp="bilinear", dtype=np.float64, out=None, origin=(0, 0), full_hw=None):
+    """lerf_coords_mesh_host: ctrl [gh, gw, 2] float32 / float64 upsampled to the tile out_hw at `origin` of the map full_hw"""
+    c = np.ascontiguousarray(ctrl)
+    if c.ndim != 3 or c.shape[2] != 2:
+        raise ValueError("ctrl must be [gh, gw, 2]")
+    full_hw = out_hw if full_hw is None else full_hw
+    out, stride = _np_out(out, out_hw, dtype, "lerf_coords_mesh_host")
+    check(lib().lerf_coords_mesh_host(c.ctypes.data, _np_dt(c), c.shape[0], c.shape[1], mesh_interp_code(interp), int(full_hw[0]),
+                                      int(full_hw[1]), out.ctypes.data, _np_dt(out), stride, int(out_hw[0]), int(out_hw[1]),
+                                      int(origin[0]), int(origin[1])), "lerf_coords_mesh_host")
+    return out
+
+
+def coords_compose_host(outer, inner, dtype=np.float64, out=None):
+    """lerf_coords_compose_host: C[i, j] = outer(inner[i, j]), host arrays under the strided map contract"""
+    a, sa = _np_map(outer, "outer")
+    b, sb = _np_map(inner, "inner")
+    out, so = _np_out(out, b.shape[:2], dtype, "lerf_coords_compose_host")
+    check(lib().lerf_coords_compose_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
+                                         out.ctypes.data, _np_dt(out), so, b.shape[0], b.shape[1]), "lerf_coords_compose_host")
+    return out
 
 
 # ------------------------------------------------------------------ device plumbing

@@ -5,6 +5,11 @@ A map is a float64 (or float32) array [oH, oW, 2]; entry (i, j) is (row, col) of
 (resize_right/resize_right2d_numpy.py:306-342) holds BEFORE its clip -- the remap clips.  Host numpy: a map is built once per
 transform, not per frame -- except from_flow_torch, which builds the map of a flow on the flow's device and keeps it in the
 autograd graph (a flow fitted by gradient).
+
+With device=<a torch device> the builders write the map ON the device with the kernels of csrc/lerf_coords.hip (one store per
+entry, no host array, no upload): from_homography, radial, undistort_rectify, from_mesh; from_mesh_torch keeps a control mesh
+in the autograd graph through the mesh upsample's adjoint, and compose chains two maps into one.  The kernels' arithmetic is
+float64 with + - * / only, bit-equal to its host twin (csrc/lerf_coords_models.h).
 """
 from __future__ import annotations
 
@@ -18,7 +23,27 @@ def _grid(out_hw):
     return np.meshgrid(np.arange(oH), np.arange(oW), indexing="ij")
 
 
-def from_homography(matrix, out_hw, arithmetic="device"):
+def _np_dtype(dtype):
+    """numpy dtype of a dtype= argument (numpy or torch float32 / float64; None: float64)"""
+    name = "float64" if dtype is None else str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+    if name not in ("float32", "float64"):
+        raise ValueError("dtype is float32 or float64")
+    return np.dtype(name)
+
+
+def _build(model, params, out_hw, dtype, device):
+    """the map of a model by the kernels' arithmetic: on `device` by the kernel, or (device None) by its bit-equal host twin"""
+    dt = _np_dtype(dtype)
+    _grid((out_hw[0], 1)), _grid((1, out_hw[1]))
+    if device is None:
+        from . import _lib
+        return _lib.coords_build_host(model, params, out_hw, dt)
+    import torch
+    from . import ops
+    return ops.coords_build(model, params, out_hw, dtype=getattr(torch, dt.name), device=device)
+
+
+def from_homography(matrix, out_hw, arithmetic="device", device=None, dtype=None):
     """The projected grid of the homographic warp of `matrix` (3 x 3, source -> output like Warp2dNumpy.set_shape's), unclipped,
     float64 [oH, oW, 2]: the reference's get_projected_grid2d (:312-335) -- (col, row, 1) through the inverse matrix, the two
     divisions -- in one of two roundings of the three-term sums:
@@ -28,12 +53,21 @@ def from_homography(matrix, out_hw, arithmetic="device"):
         for the matrix BIT FOR BIT, float64 outputs included.
     "reference": np.dot with the inverse matrix exactly as :327 writes it (and oracle.warp_geometry restates it).  A BLAS
         kernel fuses its multiply-adds, so this grid differs from the device's in the last bit at a few per cent to a third
-        of the entries (1e-16 relative): invisible to a byte, visible in the last bits of a float64 output."""
+        of the entries (1e-16 relative): invisible to a byte, visible in the last bits of a float64 output.
+
+    device: a torch device -> the map is written there by the kernel (lerf_coords_build, the "device" arithmetic; bit-equal to
+    the host array) and returned as a tensor; "reference" arithmetic is a host form and is refused with a device.  dtype:
+    float64 (default) or float32 (the float64 value rounded once)."""
     m = np.asarray(matrix.detach().cpu().numpy() if hasattr(matrix, "detach") else matrix, dtype=np.float64)
     if m.shape != (3, 3):
         raise ValueError("matrix must be 3x3")
     if arithmetic not in ("device", "reference"):
         raise ValueError("arithmetic is 'device' or 'reference'")
+    if device is not None:
+        if arithmetic != "device":
+            raise ValueError("from_homography on a device computes the 'device' arithmetic; 'reference' is a host form")
+        return _build("homography", np.linalg.inv(m).reshape(9), out_hw, dtype, device)
+    dt = _np_dtype(dtype)
     ii, jj = _grid(out_hw)
     oH, oW = ii.shape
     minv = np.linalg.inv(m)                                                                          # :327
@@ -43,13 +77,13 @@ def from_homography(matrix, out_hw, arithmetic="device"):
         g = np.dot(minv, pts.transpose(1, 0)).transpose(1, 0)
         g[:, 0] /= g[:, -1]
         g[:, 1] /= g[:, -1]
-        return np.ascontiguousarray(np.stack([g[:, 1].reshape(oH, oW), g[:, 0].reshape(oH, oW)], axis=-1))
+        return np.ascontiguousarray(np.stack([g[:, 1].reshape(oH, oW), g[:, 0].reshape(oH, oW)], axis=-1)).astype(dt, copy=False)
     q = minv.reshape(9)
     x, y = jj.astype(np.float64), ii.astype(np.float64)
     X = q[0] * x + q[1] * y + q[2]                               # numpy rounds each elementwise product and sum: project_point's order
     Y = q[3] * x + q[4] * y + q[5]
     Wh = q[6] * x + q[7] * y + q[8]
-    return np.ascontiguousarray(np.stack([Y / Wh, X / Wh], axis=-1))
+    return np.ascontiguousarray(np.stack([Y / Wh, X / Wh], axis=-1)).astype(dt, copy=False)
 
 
 def from_flow(flow):
@@ -75,19 +109,143 @@ def from_flow_torch(flow):
     return grid + flow
 
 
-def radial(in_hw, out_hw, k1, k2=0.0, centre=None):
+def radial(in_hw, out_hw, k1, k2=0.0, centre=None, device=None, dtype=None):
     """Radial (Brown) lens model about `centre` (row, col of the SOURCE frame; default: its middle): the output pixel at
     normalised offset u from the output's middle reads the source at centre + u (1 + k1 r^2 + k2 r^4) * half-diagonal, r = |u|,
     offsets normalised by the half-diagonal of each frame (so k1 = k2 = 0 is the plain resize between the two sizes).
-    float64 [oH, oW, 2]."""
+    float64 [oH, oW, 2].  device: a torch device -> built there by the kernel (the same statements in the same order, bit-equal);
+    dtype: float64 (default) or float32."""
     H, W = int(in_hw[0]), int(in_hw[1])
-    ii, jj = _grid(out_hw)
-    oH, oW = ii.shape
+    oH, oW = int(out_hw[0]), int(out_hw[1])
     cr, cc = ((H - 1) / 2.0, (W - 1) / 2.0) if centre is None else (float(centre[0]), float(centre[1]))
     no = np.hypot(oH, oW) / 2.0
     ni = np.hypot(H, W) / 2.0
+    if device is not None:
+        return _build("radial", [cr, cc, no, ni, (oH - 1) / 2.0, (oW - 1) / 2.0, float(k1), float(k2)], out_hw, dtype, device)
+    ii, jj = _grid(out_hw)
     ur = (ii - (oH - 1) / 2.0) / no
     uc = (jj - (oW - 1) / 2.0) / no
     r2 = ur * ur + uc * uc
     f = 1.0 + float(k1) * r2 + float(k2) * r2 * r2
-    return np.ascontiguousarray(np.stack([cr + ur * f * ni, cc + uc * f * ni], axis=-1))
+    return np.ascontiguousarray(np.stack([cr + ur * f * ni, cc + uc * f * ni], axis=-1)).astype(_np_dtype(dtype), copy=False)
+
+
+def _host(a, dtype=np.float64):
+    return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=dtype)
+
+
+def brown_params(K, dist=None, R=None, new_K=None):
+    """The 21 parameters of the "brown" model from what cv::initUndistortRectifyMap takes: K (3 x 3 source camera, no skew), dist
+    (k1 k2 p1 p2 [k3 [k4 k5 k6]], missing ones 0), R (rectifying rotation, default I), new_K (default K) ->
+    inv(new_K . R)[9], fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6."""
+    K = _host(K)
+    if K.shape != (3, 3):
+        raise ValueError("K must be 3x3")
+    if K[0, 1] != 0.0 or K[1, 0] != 0.0 or K[2, 0] != 0.0 or K[2, 1] != 0.0 or K[2, 2] != 1.0:
+        raise ValueError("K must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (skew is not supported)")
+    d = np.zeros(8) if dist is None else _host(dist).reshape(-1)
+    if d.size not in (4, 5, 8):
+        raise ValueError("dist holds 4, 5 or 8 coefficients (k1 k2 p1 p2 [k3 [k4 k5 k6]])")
+    d = np.concatenate([d, np.zeros(8 - d.size)])
+    R = np.eye(3) if R is None else _host(R)
+    new_K = K if new_K is None else _host(new_K)
+    if R.shape != (3, 3) or new_K.shape != (3, 3):
+        raise ValueError("R and new_K must be 3x3")
+    minv = np.linalg.inv(np.dot(new_K, R))
+    return np.concatenate([minv.reshape(9), [K[0, 0], K[1, 1], K[0, 2], K[1, 2]], d])
+
+
+def undistort_rectify(K, dist, R, new_K, out_hw, device=None, dtype=None):
+    """The map of cv::initUndistortRectifyMap (pinhole + Brown-Conrady, 4 / 5 / 8 distortion coefficients in OpenCV's order, a
+    rectifying rotation R and the new camera matrix new_K; R and new_K may be None = identity / K): output pixel (u = j, v = i)
+    goes through inv(new_K . R) to the normalised (x, y), is distorted, and lands at (row, col) = (fy y'' + cy, fx x'' + cx) of
+    the source.  [oH, oW, 2], float64 (default) or float32; device None: host numpy through the kernel's host twin, else a
+    device tensor written by the kernel -- bit-equal to each other.  remap() of a distorted frame with this map undistorts and
+    rectifies it."""
+    return _build("brown", brown_params(K, dist, R, new_K), out_hw, dtype, device)
+
+
+def from_mesh(ctrl, out_hw, interp="bilinear", device=None, dtype=None):
+    """A control mesh upsampled to a dense map: ctrl [gh, gw, 2] (gh, gw >= 2) holds the absolute source position (row, col) at
+    control vertices spread align-corners over the output (vertex a at output row a (oH - 1) / (gh - 1)); interp "bilinear", or
+    "bicubic" (Keys A = -0.75 with clamped border taps: F.interpolate(mode="bicubic", align_corners=True)).  device None and a
+    host ctrl: host numpy (the kernel's host twin); a torch device, or a ctrl already on one: a device tensor written by the
+    kernel.  dtype: the map's, default ctrl's (float64 for anything that is not float32)."""
+    on_dev = getattr(ctrl, "is_cuda", False)
+    if device is None and not on_dev:
+        from . import _lib
+        c = np.asarray(ctrl.detach().numpy() if hasattr(ctrl, "detach") else ctrl)
+        if c.dtype not in (np.float32, np.float64):
+            c = c.astype(np.float64)
+        _grid(out_hw)
+        return _lib.coords_mesh_host(c, out_hw, interp, c.dtype if dtype is None else _np_dtype(dtype))
+    import torch
+    from . import ops
+    if not isinstance(ctrl, torch.Tensor):
+        c = np.asarray(ctrl)
+        ctrl = torch.from_numpy(np.ascontiguousarray(c if c.dtype in (np.float32, np.float64) else c.astype(np.float64)))
+    if device is not None:
+        ctrl = ctrl.to(device)
+    return ops.coords_mesh(ctrl, out_hw, interp, dtype=None if dtype is None else getattr(torch, _np_dtype(dtype).name))
+
+
+_MESH_FN = None
+
+
+def _mesh_fn():
+    global _MESH_FN
+    if _MESH_FN is None:
+        import torch
+        from . import ops
+
+        class _MeshFn(torch.autograd.Function):
+            """map = ops.coords_mesh(ctrl); backward: ops.coords_mesh_bwd in float64, cast to ctrl's dtype"""
+
+            @staticmethod
+            def forward(ctx, ctrl, out_hw, interp):
+                ctx.interp, ctx.ctrl_hw, ctx.dtype = interp, tuple(ctrl.shape[:2]), ctrl.dtype
+                return ops.coords_mesh(ctrl, out_hw, interp)
+
+            @staticmethod
+            def backward(ctx, grad):
+                g = ops.coords_mesh_bwd(grad.contiguous().double(), ctx.ctrl_hw, ctx.interp)
+                return g.to(ctx.dtype), None, None
+
+        _MESH_FN = _MeshFn
+    return _MESH_FN
+
+
+def from_mesh_torch(ctrl, out_hw, interp="bilinear"):
+    """from_mesh on ctrl's device, differentiable: ctrl [gh, gw, 2] device tensor (float32 or float64) -> the map in ctrl's
+    dtype.  A ctrl that requires grad stays in the graph: a remap class that has opted in with enable_backward() hands it
+    d loss / d ctrl through the upsample's adjoint (lerf_coords_mesh_bwd: float64, deterministic, cast to ctrl's dtype)."""
+    import torch
+    if not isinstance(ctrl, torch.Tensor) or ctrl.ndim != 3 or ctrl.shape[2] != 2 or not ctrl.is_floating_point() or not ctrl.is_cuda:
+        raise ValueError("ctrl must be a floating-point [gh, gw, 2] device tensor")
+    if interp not in ("bilinear", "bicubic"):
+        raise ValueError("interp is 'bilinear' or 'bicubic'")
+    return _mesh_fn().apply(ctrl, (int(out_hw[0]), int(out_hw[1])), interp)
+
+
+def compose(outer, inner, dtype=None):
+    """One map for two chained remaps: C[i, j] = outer(inner[i, j]), the outer map sampled bilinearly at the position the inner
+    map holds, so remap(remap(img, outer), inner) and remap(img, compose(outer, inner)) describe the same geometry -- one pass
+    through the LUT stages and one interpolation instead of two.  Positions outside the outer map are clipped onto its border;
+    a NaN entry of the inner map stays (NaN, NaN).  numpy in -> numpy out (the kernel's host twin); device tensors in -> a
+    device tensor; mixed operands are refused.  dtype: default the inner map's.  No autograd: an operand that requires grad
+    (with grad mode on) is refused."""
+    dev = [bool(getattr(t, "is_cuda", False)) for t in (outer, inner)]
+    if dev[0] != dev[1]:
+        raise ValueError("compose: both maps on the host or both on one device, not mixed")
+    if any(getattr(t, "requires_grad", False) for t in (outer, inner)):
+        import torch
+        if torch.is_grad_enabled():
+            raise ValueError("compose has no autograd: detach() the maps (or call it under torch.no_grad())")
+    if dev[0]:
+        import torch
+        from . import ops
+        return ops.coords_compose(outer, inner, dtype=None if dtype is None else getattr(torch, _np_dtype(dtype).name))
+    from . import _lib
+    a, b = (np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (outer, inner))
+    a, b = (t if t.dtype in (np.float32, np.float64) else t.astype(np.float64) for t in (a, b))
+    return _lib.coords_compose_host(a, b, b.dtype if dtype is None else _np_dtype(dtype))

@@ -1,0 +1,320 @@
+// Coordinate maps built, upsampled and composed on the device: the maps lerf_remap reads (lerf_remap_geo_t.coords), written by
+// kernels instead of host numpy + an upload.  The arithmetic of every entry is lerf_coords_models.h (float64, + - * / only, no
+// FMA contraction), shared with the host twins at the end of this file, which run the same functions in a plain loop over host
+// pointers: device and host agree bit for bit.
+//
+//   coords_build_kernel<MODEL, TO>          one thread per entry: the model's point of pixel (i0 + i, j0 + j), ONE 16-byte (float64)
+//                                           or 8-byte (float32) store; the 64 lanes of a wave write 64 consecutive entries of a row
+//   coords_mesh_kernel<INTERP, TC, TO>      the same shape; 2 x 2 or 4 x 4 control entries per thread, read through the caches (the
+//                                           control mesh is small -- 33 x 61 x 2 doubles are 32 KB -- and neighbouring lanes read
+//                                           the same entries, so the loads are broadcasts out of L1 / L2; staging it in LDS would
+//                                           cost every block of 256 entries a 32-KB fill for the 4 to 16 entries a lane needs)
+//   coords_compose_kernel<TA, TB, TO>       one thread per entry: one load of B, up to four of A, one store
+//   coords_mesh_bwd_{rows,cols}_kernel      the adjoint of the mesh upsample, map = Wr . ctrl . Wc^T  =>  grad_ctrl = Wr^T . grad_map . Wc,
+//                                           in two gather-shaped passes, each sum in a fixed order and without atomics:
+//       rows   tmp[a][j] = sum_i Wr[i][a] grad_map[i][j]: a block owns vertex row a and 64 columns; its 4 waves take the rows of a's
+//              reach i = lo + w, lo + w + 4, ... (any reach beyond 4 rows takes more than one pass of the block), every lane keeps
+//              its own running sum, the 4 partial sums meet in LDS and wave 0 adds them in the order 0, 1, 2, 3
+//       cols   grad_ctrl[a][b] += sum_j Wc[j][b] tmp[a][j]: ONE wave per vertex; lane l takes the columns lo + l, lo + l + 64, ...
+//              (a reach beyond 64 columns takes more than one pass), then a shuffle tree (offsets 32, 16, .. 1), lane 0 is the
+//              vertex's one writer (load-add-store: the accumulate contract of lerf_remap_bwd)
+//       The weight Wr[i][a] is recomputed from mesh_axis -- the forward's own function -- for every row of a conservative reach
+//       (mesh_reach); rows without a tap on a weigh exactly 0 and are skipped, so the transpose is exact, clamped border taps
+//       of the bicubic included.  A 33 x 61 mesh under 2160 x 3840: 270 rows per vertex row in pass 1 (68 per wave), 252 columns per
+//       vertex in pass 2 (4 per lane); grad_map is read 4 times (bicubic) or twice (bilinear), coalesced, tmp is 2 MB.
+//
+// Addresses: every kernel guards (i, j) against the tile, writes entry (i, j) of `out` only, and reads ctrl / A at indices that
+// mesh_axis / compose_axis clamp into the operand after clipping the position in floating point (no value of B reaches an int
+// conversion unclipped).  The passes of the adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].
+#include "lerf_common.h"
+#include "lerf_coords_models.h"
+
+#include <cmath>
+
+namespace lerf {
+namespace coords {
+
+constexpr int CB_COLS = 64, CB_ROWS = 4;     // block = 4 waves, one row of 64 entries each
+
+template <typename TO>
+LERF_HD inline void store_entry(TO* out, int64_t stride, int i, int j, const Point& q) {
+    Entry<TO> v;
+    v.r = (TO)q.r;                               // float32: the float64 value rounded once, here
+    v.c = (TO)q.c;
+    *reinterpret_cast<Entry<TO>*>(out + (int64_t)i * stride + 2 * (int64_t)j) = v;
+}
+
+template <typename T>
+LERF_HD inline Point load_entry(const T* m, int64_t stride, int i, int j) {
+    const Entry<T> v = *reinterpret_cast<const Entry<T>*>(m + (int64_t)i * stride + 2 * (int64_t)j);
+    return {(double)v.r, (double)v.c};
+}
+
+template <int MODEL, typename TO>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_build_kernel(Params prm, TO* __restrict__ out, int64_t stride, int oH, int oW, int i0, int j0) {
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= oH || j >= oW) return;
+    store_entry(out, stride, i, j, model_point<MODEL>(prm.p, i0 + i, j0 + j));
+}
+
+template <int INTERP, typename TC, typename TO>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_mesh_kernel(const TC* __restrict__ ctrl, int gh, int gw, int full_h, int full_w, TO* __restrict__ out, int64_t stride, int oH,
+                   int oW, int i0, int j0) {
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= oH || j >= oW) return;
+    store_entry(out, stride, i, j, mesh_point<INTERP>(ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j));
+}
+
+template <typename TA, typename TB, typename TO>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_compose_kernel(const TA* __restrict__ A, int64_t a_stride, int aH, int aW, const TB* __restrict__ B, int64_t b_stride,
+                      TO* __restrict__ out, int64_t o_stride, int oH, int oW) {
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= oH || j >= oW) return;
+    const Point q = load_entry(B, b_stride, i, j);
+    store_entry(out, o_stride, i, j, compose_point(q.r, q.c, aH, aW, [&](int r, int c) { return load_entry(A, a_stride, r, c); }));
+}
+
+// pass 1 of the adjoint: grid (ceil(oW / 64), gh), block (64, 4)
+template <int INTERP>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_mesh_bwd_rows_kernel(const double2* __restrict__ gmap, int oH, int oW, int gh, double2* __restrict__ tmp) {
+#pragma clang fp contract(off)
+    __shared__ double2 part[CB_ROWS][CB_COLS];
+    const int a = blockIdx.y, j = blockIdx.x * CB_COLS + threadIdx.x, w = threadIdx.y;
+    int lo, hi;
+    mesh_reach<INTERP>(a, oH, gh, &lo, &hi);
+    double2 acc = make_double2(0.0, 0.0);
+    if (j < oW)
+        for (int i = lo + w; i <= hi; i += CB_ROWS) {
+            const double wt = mesh_weight_on<INTERP>(i, oH, gh, a);
+            if (wt == 0.0) continue;
+            const double2 g = gmap[(int64_t)i * oW + j];
+            acc.x = acc.x + wt * g.x;
+            acc.y = acc.y + wt * g.y;
+        }
+    part[w][threadIdx.x] = acc;
+    __syncthreads();
+    if (w == 0 && j < oW) {
+        double2 s = part[0][threadIdx.x];
+#pragma unroll
+        for (int k = 1; k < CB_ROWS; ++k) {
+            s.x = s.x + part[k][threadIdx.x].x;
+            s.y = s.y + part[k][threadIdx.x].y;
+        }
+        tmp[(int64_t)a * oW + j] = s;
+    }
+}
+
+// pass 2: grid (gw, gh), block 64 = one wave per vertex
+template <int INTERP>
+__global__ void __launch_bounds__(64)
+coords_mesh_bwd_cols_kernel(const double2* __restrict__ tmp, int oW, int gw, double2* __restrict__ gctrl) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
+    int lo, hi;
+    mesh_reach<INTERP>(b, oW, gw, &lo, &hi);
+    double sx = 0.0, sy = 0.0;
+    for (int j = lo + lane; j <= hi; j += 64) {
+        const double wt = mesh_weight_on<INTERP>(j, oW, gw, b);
+        if (wt == 0.0) continue;
+        const double2 t = tmp[(int64_t)a * oW + j];
+        sx = sx + wt * t.x;
+        sy = sy + wt * t.y;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sx = sx + __shfl_down(sx, off, 64);
+        sy = sy + __shfl_down(sy, off, 64);
+    }
+    if (lane == 0) {
+        double2* dst = gctrl + (int64_t)a * gw + b;
+        double2 v = *dst;
+        v.x += sx;
+        v.y += sy;
+        *dst = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ argument checks (host)
+inline bool float_dtype(int dt) { return dt == LERF_F32 || dt == LERF_F64; }
+inline size_t entry_bytes(int dt) { return dt == LERF_F32 ? 8 : 16; }
+
+// a map operand under the strided contract
+inline bool map_ok(const void* p, int dt, int64_t stride, int h, int w) {
+    return p && float_dtype(dt) && h >= 1 && w >= 1 && !(stride & 1) && stride >= 2 * (int64_t)w && (size_t)(uintptr_t)p % entry_bytes(dt) == 0;
+}
+
+inline bool tile_ok(int oH, int oW, int i0, int j0) {
+    return i0 >= 0 && j0 >= 0 && (int64_t)i0 + oH <= 0x7fffffff && (int64_t)j0 + oW <= 0x7fffffff && (oH + CB_ROWS - 1) / CB_ROWS <= 65535;
+}
+
+inline int build_args(int model, const double* params, int n_params, const void* out, int out_dtype, int64_t stride, int oH, int oW,
+                      int i0, int j0, Params& prm) {
+    if (!params || !map_ok(out, out_dtype, stride, oH, oW) || !tile_ok(oH, oW, i0, j0)) return LERF_EINVAL;
+    if (model_params(model) < 0 || n_params != model_params(model)) return LERF_EINVAL;
+    for (int k = 0; k < kMaxParams; ++k) prm.p[k] = 0.0;
+    for (int k = 0; k < n_params; ++k) {
+        if (!std::isfinite(params[k])) return LERF_EINVAL;
+        prm.p[k] = params[k];
+    }
+    return LERF_OK;
+}
+
+inline int mesh_args(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, const void* out, int out_dtype,
+                     int64_t stride, int oH, int oW, int i0, int j0) {
+    if (!ctrl || !float_dtype(ctrl_dtype) || (size_t)(uintptr_t)ctrl % entry_bytes(ctrl_dtype) != 0 || gh < 2 || gw < 2) return LERF_EINVAL;
+    if (interp != LERF_MESH_BILINEAR && interp != LERF_MESH_BICUBIC) return LERF_EINVAL;
+    if (!map_ok(out, out_dtype, stride, oH, oW) || !tile_ok(oH, oW, i0, j0)) return LERF_EINVAL;
+    if (full_h < 1 || full_w < 1 || (int64_t)i0 + oH > full_h || (int64_t)j0 + oW > full_w) return LERF_EINVAL;
+    return LERF_OK;
+}
+
+inline int compose_args(const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
+                        const void* out, int out_dtype, int64_t o_stride, int oH, int oW) {
+    if (!map_ok(a, a_dtype, a_stride, aH, aW) || !map_ok(b, b_dtype, b_stride, oH, oW) || !map_ok(out, out_dtype, o_stride, oH, oW))
+        return LERF_EINVAL;
+    return tile_ok(oH, oW, 0, 0) ? LERF_OK : LERF_EINVAL;
+}
+
+inline dim3 entry_grid(int oH, int oW) { return dim3((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS); }
+
+}  // namespace coords
+}  // namespace lerf
+
+using namespace lerf;
+using namespace lerf::coords;
+
+// run F with the C++ type of a float dtype code
+#define LERF_COORDS_DT(code, T, ...)          \
+    do {                                      \
+        if ((code) == LERF_F32) { using T = float; __VA_ARGS__; } \
+        else { using T = double; __VA_ARGS__; } \
+    } while (0)
+
+extern "C" {
+
+int lerf_coords_build(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
+                      int i0, int j0, void* stream) {
+    Params prm;
+    const int rc = build_args(model, params, n_params, out, out_dtype, row_stride, oH, oW, i0, j0, prm);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
+    hipStream_t st = (hipStream_t)stream;
+#define LERF_CB(MODEL) \
+    LERF_COORDS_DT(out_dtype, TO, hipLaunchKernelGGL((coords_build_kernel<MODEL, TO>), grid, block, 0, st, prm, (TO*)out, row_stride, oH, oW, i0, j0))
+    switch (model) {
+        case LERF_COORDS_HOMOGRAPHY: LERF_CB(LERF_COORDS_HOMOGRAPHY); break;
+        case LERF_COORDS_RADIAL: LERF_CB(LERF_COORDS_RADIAL); break;
+        default: LERF_CB(LERF_COORDS_BROWN); break;
+    }
+#undef LERF_CB
+    return launch_status();
+}
+
+int lerf_coords_mesh(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+                     int64_t row_stride, int oH, int oW, int i0, int j0, void* stream) {
+    const int rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
+    hipStream_t st = (hipStream_t)stream;
+#define LERF_CM(INTERP)                                                                                                             \
+    LERF_COORDS_DT(ctrl_dtype, TC, LERF_COORDS_DT(out_dtype, TO,                                                                    \
+        hipLaunchKernelGGL((coords_mesh_kernel<INTERP, TC, TO>), grid, block, 0, st, (const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, \
+                           row_stride, oH, oW, i0, j0)))
+    if (interp == LERF_MESH_BILINEAR) LERF_CM(LERF_MESH_BILINEAR);
+    else LERF_CM(LERF_MESH_BICUBIC);
+#undef LERF_CM
+    return launch_status();
+}
+
+size_t lerf_coords_mesh_bwd_workspace_bytes(int gh, int gw, int oH, int oW) {
+    if (gh < 2 || gw < 2 || oH < 1 || oW < 1) return 0;
+    return (size_t)gh * (size_t)oW * 2 * sizeof(double);
+}
+
+int lerf_coords_mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!grad_map || !grad_ctrl || !workspace || oH < 1 || oW < 1 || gh < 2 || gw < 2) return LERF_EINVAL;
+    if (interp != LERF_MESH_BILINEAR && interp != LERF_MESH_BICUBIC) return LERF_EINVAL;
+    if ((size_t)(uintptr_t)grad_map % 16 != 0 || (size_t)(uintptr_t)grad_ctrl % 16 != 0 || (size_t)(uintptr_t)workspace % 16 != 0) return LERF_EINVAL;
+    if (workspace_bytes < lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW) || gh > 65535) return LERF_EINVAL;
+    clear_stale_error();
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + CB_COLS - 1) / CB_COLS, gh), b2(64), g2(gw, gh);
+    const double2* gm = reinterpret_cast<const double2*>(grad_map);
+    double2* tmp = reinterpret_cast<double2*>(workspace);
+    double2* gc = reinterpret_cast<double2*>(grad_ctrl);
+    if (interp == LERF_MESH_BILINEAR) {
+        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BILINEAR>), g1, b1, 0, st, gm, oH, oW, gh, tmp);
+        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BILINEAR>), g2, b2, 0, st, tmp, oW, gw, gc);
+    } else {
+        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BICUBIC>), g1, b1, 0, st, gm, oH, oW, gh, tmp);
+        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BICUBIC>), g2, b2, 0, st, tmp, oW, gw, gc);
+    }
+    return launch_status();
+}
+
+int lerf_coords_compose(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
+                        void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, void* stream) {
+    const int rc = compose_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
+    hipStream_t st = (hipStream_t)stream;
+    LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB, LERF_COORDS_DT(out_dtype, TO,
+        hipLaunchKernelGGL((coords_compose_kernel<TA, TB, TO>), grid, block, 0, st, (const TA*)a, a_row_stride, aH, aW, (const TB*)b,
+                           b_row_stride, (TO*)out, out_row_stride, oH, oW))));
+    return launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ host twins: the same functions, a plain loop
+int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
+                           int i0, int j0) {
+    Params prm;
+    const int rc = build_args(model, params, n_params, out, out_dtype, row_stride, oH, oW, i0, j0, prm);
+    if (rc != LERF_OK) return rc;
+    for (int i = 0; i < oH; ++i)
+        for (int j = 0; j < oW; ++j) {
+            const Point q = model == LERF_COORDS_HOMOGRAPHY ? model_point<LERF_COORDS_HOMOGRAPHY>(prm.p, i0 + i, j0 + j)
+                            : model == LERF_COORDS_RADIAL   ? model_point<LERF_COORDS_RADIAL>(prm.p, i0 + i, j0 + j)
+                                                            : model_point<LERF_COORDS_BROWN>(prm.p, i0 + i, j0 + j);
+            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, row_stride, i, j, q));
+        }
+    return LERF_OK;
+}
+
+int lerf_coords_mesh_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+                          int64_t row_stride, int oH, int oW, int i0, int j0) {
+    const int rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
+    if (rc != LERF_OK) return rc;
+    for (int i = 0; i < oH; ++i)
+        for (int j = 0; j < oW; ++j) {
+            Point q;
+            LERF_COORDS_DT(ctrl_dtype, TC,
+                           q = interp == LERF_MESH_BILINEAR ? mesh_point<LERF_MESH_BILINEAR>((const TC*)ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j)
+                                                            : mesh_point<LERF_MESH_BICUBIC>((const TC*)ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j));
+            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, row_stride, i, j, q));
+        }
+    return LERF_OK;
+}
+
+int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                             int64_t b_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW) {
+    const int rc = compose_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
+    if (rc != LERF_OK) return rc;
+    for (int i = 0; i < oH; ++i)
+        for (int j = 0; j < oW; ++j) {
+            Point q, v;
+            LERF_COORDS_DT(b_dtype, TB, q = load_entry((const TB*)b, b_row_stride, i, j));
+            LERF_COORDS_DT(a_dtype, TA, v = compose_point(q.r, q.c, aH, aW, [&](int r, int c) { return load_entry((const TA*)a, a_row_stride, r, c); }));
+            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, out_row_stride, i, j, v));
+        }
+    return LERF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,228 @@
+// Arithmetic of the coordinate-map builders (lerf_coords.hip), HIP-free on the host side: one source for the kernels and for the
+// host twins (lerf_coords_*_host), so a machine without a GPU tests the same statements.  Float64, only + - * /, no sqrt and no
+// transcendental, FMA contraction off: the device and the host agree BIT FOR BIT, like project_point against
+// coords.from_homography(arithmetic="device").  Every function returns the UNCLIPPED (row, col) of one output pixel (i, j) of
+// the whole map; the remap clips (remap_pixel).
+//
+// The exact operation order (tests/coords_ref.py restates it; every product and sum is rounded, sums run left to right):
+//
+//   HOMOGRAPHY  p = inverse matrix m[9]:  project_unclipped (lerf_host_geometry.h)
+//                 X = m0*x + m1*y + m2,  Y = m3*x + m4*y + m5,  Wh = m6*x + m7*y + m8,  x = (double)j, y = (double)i
+//                 col = X / Wh,  row = Y / Wh
+//   RADIAL      p = cr, cc, no, ni, hr, hc, k1, k2  (coords.radial's scalars: centre, the two half-diagonals, the half-extents
+//               (oH - 1) / 2 and (oW - 1) / 2 of the WHOLE output):
+//                 ur = (i - hr) / no,  uc = (j - hc) / no,  r2 = ur*ur + uc*uc
+//                 f = (1 + k1*r2) + (k2*r2)*r2
+//                 row = cr + (ur*f)*ni,  col = cc + (uc*f)*ni
+//   BROWN       p = m[9] (inv(new_K . R), the host's), fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6
+//               (cv::initUndistortRectifyMap's pinhole + Brown-Conrady model, no skew):
+//                 (y, x) = project_unclipped(m, i, j)              -- u = j, v = i through the matrix, the two divisions
+//                 r2  = x*x + y*y
+//                 rad = (1 + r2*(k1 + r2*(k2 + r2*k3))) / (1 + r2*(k4 + r2*(k5 + r2*k6)))
+//                 xy  = x*y
+//                 xd  = (x*rad + (2*p1)*xy) + p2*(r2 + 2*(x*x))
+//                 yd  = (y*rad + p1*(r2 + 2*(y*y))) + (2*p2)*xy
+//                 col = fx*xd + cx,  row = fy*yd + cy
+//   mesh        ctrl [gh][gw][2], vertices align-corners over the WHOLE output [full_h][full_w]; per axis (rows: n = full_h,
+//               g = gh, k = i):
+//                 u = ((double)k * (double)(g - 1)) / (double)(n - 1)           (0 when n == 1)
+//                 bilinear: a0 = min((int)floor(u), g - 2), t = u - a0, taps a0, a0 + 1, weights 1 - t, t
+//                 bicubic:  f = (int)floor(u), t = u - f, taps f - 1 .. f + 2 clamped to [0, g - 1], Keys weights with A = -0.75 in
+//                           torch's upsample_bicubic2d forms:  c1(x) = ((A + 2)*x - (A + 3))*x*x + 1,
+//                           c2(x) = ((A*x - 5*A)*x + 8*A)*x - 4*A,  w = c2(t + 1), c1(t), c1(1 - t), c2(2 - t)
+//               value = sum_a wr[a] * (sum_b wc[b] * ctrl[a][b]), both sums left to right starting from their first product
+//   compose     C[i][j] = A(B[i][j]), A [aH][aW][2] sampled bilinearly at the position B holds; per axis (rows: n = aH, v = row):
+//                 r = clip of v onto [0, n - 1] (clip_coord: -inf -> 0, +inf -> n - 1)
+//                 i0 = min((int)floor(r), n - 2)  (0 when n == 1),  t = r - i0,  weights 1 - t, t
+//               value = acc over rows a = 0, 1 of wr[a] * (acc over columns b = 0, 1 of wc[b] * A[i0 + a][j0 + b]), every acc
+//               starting at +0.0 and adding its terms in order; a term whose weight is exactly 0 is NOT added and its entry of
+//               A is NOT read.  A NaN in either coordinate of B[i][j]: (NaN, NaN), nothing of A is read.  No value of B forms
+//               an address outside A: the position is clipped before any conversion to int, and a tap outside A (n == 1,
+//               or r on the last row) has weight exactly 0.
+#pragma once
+
+#include "lerf_host_geometry.h"
+
+namespace lerf {
+namespace coords {
+
+struct Point {
+    double r, c;
+};
+
+// one (row, col) entry of a map or of a control mesh, aligned so that it moves in ONE 16-byte (double) / 8-byte (float) access
+template <typename T>
+struct alignas(2 * sizeof(T)) Entry {
+    T r, c;
+};
+
+constexpr int kMaxParams = LERF_COORDS_MAX_PARAMS;
+
+struct Params {
+    double p[kMaxParams];
+};
+
+LERF_HD inline int model_params(int model) {
+    return model == LERF_COORDS_HOMOGRAPHY ? 9 : model == LERF_COORDS_RADIAL ? 8 : model == LERF_COORDS_BROWN ? 21 : -1;
+}
+
+template <int MODEL>
+LERF_HD inline Point model_point(const double* p, int i, int j) {
+#pragma clang fp contract(off)
+    Point q;
+    if (MODEL == LERF_COORDS_HOMOGRAPHY) {
+        project_unclipped(p, i, j, &q.r, &q.c);
+    } else if (MODEL == LERF_COORDS_RADIAL) {
+        const double cr = p[0], cc = p[1], no = p[2], ni = p[3], hr = p[4], hc = p[5], k1 = p[6], k2 = p[7];
+        const double ur = ((double)i - hr) / no;
+        const double uc = ((double)j - hc) / no;
+        const double r2 = ur * ur + uc * uc;
+        const double f = (1.0 + k1 * r2) + (k2 * r2) * r2;
+        q.r = cr + (ur * f) * ni;
+        q.c = cc + (uc * f) * ni;
+    } else {
+        const double fx = p[9], fy = p[10], cx = p[11], cy = p[12];
+        const double k1 = p[13], k2 = p[14], p1 = p[15], p2 = p[16], k3 = p[17], k4 = p[18], k5 = p[19], k6 = p[20];
+        double x, y;
+        project_unclipped(p, i, j, &y, &x);
+        const double r2 = x * x + y * y;
+        const double rad = (1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))) / (1.0 + r2 * (k4 + r2 * (k5 + r2 * k6)));
+        const double xy = x * y;
+        const double xd = (x * rad + (2.0 * p1) * xy) + p2 * (r2 + 2.0 * (x * x));
+        const double yd = (y * rad + p1 * (r2 + 2.0 * (y * y))) + (2.0 * p2) * xy;
+        q.c = fx * xd + cx;
+        q.r = fy * yd + cy;
+    }
+    return q;
+}
+
+// ---- mesh: the taps of output index k along one axis of n outputs over g vertices; returns the tap count (2 or 4)
+LERF_HD inline double cubic1(double x) {
+#pragma clang fp contract(off)
+    const double A = -0.75;
+    return ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0;
+}
+
+LERF_HD inline double cubic2(double x) {
+#pragma clang fp contract(off)
+    const double A = -0.75;
+    return ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A;
+}
+
+template <int INTERP>
+LERF_HD inline int mesh_axis(int k, int n, int g, int idx[4], double w[4]) {
+#pragma clang fp contract(off)
+    const double u = n > 1 ? ((double)k * (double)(g - 1)) / (double)(n - 1) : 0.0;      // in [0, g - 1]: k in [0, n)
+    const int f = (int)floor(u);
+    if (INTERP == LERF_MESH_BILINEAR) {
+        const int a0 = f < g - 2 ? f : g - 2;
+        const double t = u - (double)a0;
+        idx[0] = a0; idx[1] = a0 + 1;
+        w[0] = 1.0 - t; w[1] = t;
+        return 2;
+    }
+    const double t = u - (double)f;
+    idx[0] = clampi(f - 1, 0, g - 1); idx[1] = clampi(f, 0, g - 1); idx[2] = clampi(f + 1, 0, g - 1); idx[3] = clampi(f + 2, 0, g - 1);
+    w[0] = cubic2(t + 1.0); w[1] = cubic1(t); w[2] = cubic1(1.0 - t); w[3] = cubic2(2.0 - t);
+    return 4;
+}
+
+template <typename TC>
+LERF_HD inline Point ctrl_entry(const TC* ctrl, int gw, int a, int b) {
+    const Entry<TC> e = *reinterpret_cast<const Entry<TC>*>(ctrl + 2 * ((int64_t)a * gw + b));
+    return {(double)e.r, (double)e.c};
+}
+
+template <int INTERP, typename TC>
+LERF_HD inline Point mesh_point(const TC* ctrl, int gh, int gw, int full_h, int full_w, int i, int j) {
+#pragma clang fp contract(off)
+    constexpr int nt = INTERP == LERF_MESH_BILINEAR ? 2 : 4;
+    int ir[4], ic[4];
+    double wr[4], wc[4];
+    mesh_axis<INTERP>(i, full_h, gh, ir, wr);
+    mesh_axis<INTERP>(j, full_w, gw, ic, wc);
+    Point v{0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < nt; ++a) {
+        Point s{0.0, 0.0};
+#pragma unroll
+        for (int b = 0; b < nt; ++b) {
+            const Point e = ctrl_entry(ctrl, gw, ir[a], ic[b]);
+            if (b == 0) { s.r = wc[0] * e.r; s.c = wc[0] * e.c; }
+            else { s.r = s.r + wc[b] * e.r; s.c = s.c + wc[b] * e.c; }
+        }
+        if (a == 0) { v.r = wr[0] * s.r; v.c = wr[0] * s.c; }
+        else { v.r = v.r + wr[a] * s.r; v.c = v.c + wr[a] * s.c; }
+    }
+    return v;
+}
+
+// Adjoint side of mesh_axis: the weight output index k puts on vertex a (clamped taps that fall on the same vertex add up, in tap
+// order), 0 when no tap of k is a.  mesh_reach: a range of output indices that contains every k with a tap on a (conservative by
+// one on each side; the weight decides).
+template <int INTERP>
+LERF_HD inline double mesh_weight_on(int k, int n, int g, int a) {
+#pragma clang fp contract(off)
+    int idx[4];
+    double w[4];
+    constexpr int nt = INTERP == LERF_MESH_BILINEAR ? 2 : 4;
+    mesh_axis<INTERP>(k, n, g, idx, w);
+    double s = 0.0;
+#pragma unroll
+    for (int t = 0; t < nt; ++t)
+        if (idx[t] == a) s = s + w[t];
+    return s;
+}
+
+template <int INTERP>
+LERF_HD inline void mesh_reach(int a, int n, int g, int* lo, int* hi) {
+    const int K = INTERP == LERF_MESH_BILINEAR ? 1 : 2;               // a tap on a needs floor(u) in [a - K, a + K - 1]
+    if (n == 1) { *lo = 0; *hi = 0; return; }
+    const int64_t l = ((int64_t)(a - K) * (n - 1)) / (g - 1) - 2, h = ((int64_t)(a + K) * (n - 1)) / (g - 1) + 2;
+    *lo = l < 0 ? 0 : (int)l;
+    *hi = h > n - 1 ? n - 1 : (int)h;
+}
+
+// ---- compose
+struct ComposeAxis {
+    int i0;
+    double w0, w1;
+};
+
+LERF_HD inline ComposeAxis compose_axis(double v, int n) {
+#pragma clang fp contract(off)
+    const double r = clip_coord(v, n - 1);
+    const int f = (int)floor(r);
+    ComposeAxis x;
+    x.i0 = n > 1 ? (f < n - 2 ? f : n - 2) : 0;
+    const double t = r - (double)x.i0;
+    x.w0 = 1.0 - t;
+    x.w1 = t;
+    return x;
+}
+
+// READ(row, col) -> Point: entry of A; called only for taps that count
+template <typename READ>
+LERF_HD inline Point compose_point(double row, double col, int aH, int aW, READ read) {
+#pragma clang fp contract(off)
+    if (row != row || col != col) return {__builtin_nan(""), __builtin_nan("")};      // the canonical quiet NaN, whatever B held
+    const ComposeAxis R = compose_axis(row, aH), Cx = compose_axis(col, aW);
+    const double wr[2] = {R.w0, R.w1}, wc[2] = {Cx.w0, Cx.w1};
+    Point v{0.0, 0.0};
+    for (int a = 0; a < 2; ++a) {
+        if (wr[a] == 0.0) continue;
+        Point s{0.0, 0.0};
+        for (int b = 0; b < 2; ++b) {
+            if (wc[b] == 0.0) continue;
+            const Point e = read(R.i0 + a, Cx.i0 + b);
+            s.r = s.r + wc[b] * e.r;
+            s.c = s.c + wc[b] * e.c;
+        }
+        v.r = v.r + wr[a] * s.r;
+        v.c = v.c + wr[a] * s.c;
+    }
+    return v;
+}
+
+}  // namespace coords
+}  // namespace lerf

@@ -53,7 +53,9 @@ LERF_HD inline bool mode_offsets(char mode, int rot, int8_t dy[4], int8_t dx[4])
 
 // Homography projection of output pixel (row i, col j) in float64, operation
 // order of resize_right/resize_right2d_numpy.py:321-339 (no FMA contraction).
-LERF_HD inline void project_point(const double* m, int i, int j, int H, int W, double* gr, double* gc) {
+// project_unclipped: the products, sums and two divisions (:327-335), the one copy of them -- the warp kernels clip the
+// result (project_point), the coordinate-map builders store it as it is (lerf_coords_models.h).
+LERF_HD inline void project_unclipped(const double* m, int i, int j, double* row, double* col) {
 #pragma clang fp contract(off)
     double x = (double)j, y = (double)i;
     double X = m[0] * x + m[1] * y + m[2];
@@ -61,7 +63,13 @@ LERF_HD inline void project_point(const double* m, int i, int j, int H, int W, d
     double Wh = m[6] * x + m[7] * y + m[8];
     X = X / Wh;
     Y = Y / Wh;
-    double r = Y, c = X;
+    *row = Y;
+    *col = X;
+}
+
+LERF_HD inline void project_point(const double* m, int i, int j, int H, int W, double* gr, double* gc) {
+    double r, c;
+    project_unclipped(m, i, j, &r, &c);
     r = r < 0.0 ? 0.0 : (r > (double)H ? (double)H : r);
     c = c < 0.0 ? 0.0 : (c > (double)W ? (double)W : c);
     *gr = r;

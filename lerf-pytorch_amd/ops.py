@@ -972,3 +972,114 @@ def patch_batch(pool_u8, desc, C_out, sz, hsz, noise=None, desc_dev=None, im=Non
                                                   int(C_out), int(sz), int(hsz), noise.data_ptr() if noise is not None else None,
                                                   im.data_ptr(), lb.data_ptr(), _lib.current_stream()), "lerf_patch_batch_u8")
     return im, lb
+
+
+# --------------------------------------------------------------------------- coordinate maps on the device
+def _map_tensor(t, what):
+    """(tensor, row stride) of a device map under the strided contract ([h, w, 2], column stride 2, any row stride)"""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.ndim != 3 or t.shape[2] != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("%s must be a device tensor [h, w, 2]" % what)
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError("%s must be float32 or float64" % what)
+    if t.stride(2) != 1 or t.stride(1) != 2:
+        raise ValueError("%s: contiguous (row, col) pairs, column stride 2" % what)
+    return t, t.stride(0)
+
+
+def _map_out(out, out_hw, dtype, device, what):
+    torch = _torch()
+    oH, oW = int(out_hw[0]), int(out_hw[1])
+    if out is None:
+        if oH < 1 or oW < 1:
+            raise ValueError("%s: out_hw must be positive" % what)
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: dtype is torch.float32 or torch.float64" % what)
+        out = torch.empty((oH, oW, 2), dtype=dtype, device=device)
+    elif tuple(out.shape[:2]) != (oH, oW):
+        raise ValueError("%s: out must be [%d, %d, 2]" % (what, oH, oW))
+    return _map_tensor(out, "out")
+
+
+def coords_build(model, params, out_hw, dtype=None, out=None, origin=(0, 0), device=None):
+    """lerf_coords_build: the map [oH, oW, 2] of `model` ("homography": the 9 entries of the INVERSE matrix; "radial": cr, cc,
+    no, ni, hr, hc, k1, k2; "brown": inv(new_K . R)[9], fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) written by the kernel.
+    out: a device tensor or a strided tile view of a larger map, built in place at `origin` = (i0, j0) of the whole map; else a
+    new tensor of `dtype` (default float64) on `device` (default: the current one)."""
+    torch = _torch()
+    code, p = _lib.coords_model_params(model, params)
+    dev = out.device if out is not None else torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out, stride = _map_out(out, out_hw, torch.float64 if dtype is None else dtype, dev, "lerf_coords_build")
+    with _lib.on_device(out):
+        _lib.check(_lib.lib().lerf_coords_build(code, p.ctypes.data, int(p.size), out.data_ptr(), _lib._dt(out), stride, int(out_hw[0]),
+                                                int(out_hw[1]), int(origin[0]), int(origin[1]), _lib.current_stream(out.device)),
+                   "lerf_coords_build")
+    return out
+
+
+def _ctrl_tensor(ctrl, what):
+    torch = _torch()
+    if not isinstance(ctrl, torch.Tensor) or not ctrl.is_cuda or ctrl.ndim != 3 or ctrl.shape[2] != 2:
+        raise ValueError("%s: ctrl must be a device tensor [gh, gw, 2]" % what)
+    if ctrl.dtype not in (torch.float32, torch.float64):
+        raise ValueError("%s: ctrl must be float32 or float64" % what)
+    return ctrl.detach().contiguous()
+
+
+def coords_mesh(ctrl, out_hw, interp="bilinear", dtype=None, out=None, origin=(0, 0), full_hw=None):
+    """lerf_coords_mesh: the control mesh ctrl [gh, gw, 2] (device, float32 / float64, absolute source positions at vertices
+    placed align-corners over the map full_hw, default out_hw) upsampled to the tile out_hw at `origin`; interp "bilinear" or
+    "bicubic" (Keys A = -0.75, clamped border taps).  dtype: the map's, default ctrl's."""
+    c = _ctrl_tensor(ctrl, "lerf_coords_mesh")
+    code = _lib.mesh_interp_code(interp)
+    full_hw = out_hw if full_hw is None else full_hw
+    out, stride = _map_out(out, out_hw, c.dtype if dtype is None else dtype, c.device, "lerf_coords_mesh")
+    if out.device != c.device:
+        raise ValueError("lerf_coords_mesh: ctrl and out live on different devices")
+    with _lib.on_device(c):
+        _lib.check(_lib.lib().lerf_coords_mesh(c.data_ptr(), _lib._dt(c), c.shape[0], c.shape[1], code, int(full_hw[0]), int(full_hw[1]),
+                                               out.data_ptr(), _lib._dt(out), stride, int(out_hw[0]), int(out_hw[1]), int(origin[0]),
+                                               int(origin[1]), _lib.current_stream(c.device)), "lerf_coords_mesh")
+    return out
+
+
+def coords_mesh_bwd(grad_map, ctrl_hw, interp="bilinear", grad_ctrl=None):
+    """lerf_coords_mesh_bwd: ACCUMULATE the adjoint of coords_mesh (whole map) of the float64 contiguous grad_map [oH, oW, 2] into
+    grad_ctrl (float64 contiguous [gh, gw, 2]; None: a zeroed one).  Deterministic: two calls on the same input are bit-equal."""
+    torch = _torch()
+    gh, gw = int(ctrl_hw[0]), int(ctrl_hw[1])
+    code = _lib.mesh_interp_code(interp)
+    g = grad_map
+    if not isinstance(g, torch.Tensor) or not g.is_cuda or g.ndim != 3 or g.shape[2] != 2 or g.dtype != torch.float64 or not g.is_contiguous():
+        raise ValueError("lerf_coords_mesh_bwd: grad_map must be a contiguous float64 device tensor [oH, oW, 2]")
+    if gh < 2 or gw < 2:
+        raise ValueError("lerf_coords_mesh_bwd: the control mesh is at least 2 x 2")
+    if grad_ctrl is None:
+        grad_ctrl = torch.zeros((gh, gw, 2), dtype=torch.float64, device=g.device)
+    elif grad_ctrl.dtype != torch.float64 or tuple(grad_ctrl.shape) != (gh, gw, 2) or not grad_ctrl.is_contiguous() \
+            or grad_ctrl.device != g.device:
+        raise ValueError("lerf_coords_mesh_bwd: grad_ctrl must be contiguous float64 [gh, gw, 2] on grad_map's device")
+    oH, oW = int(g.shape[0]), int(g.shape[1])
+    need = int(_lib.lib().lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW))
+    with _lib.on_device(g):
+        ws = _cached_workspace(need, g.device)
+        _lib.check(_lib.lib().lerf_coords_mesh_bwd(g.data_ptr(), oH, oW, code, gh, gw, grad_ctrl.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   _lib.current_stream(g.device)), "lerf_coords_mesh_bwd")
+    return grad_ctrl
+
+
+def coords_compose(outer, inner, dtype=None, out=None):
+    """lerf_coords_compose: C[i, j] = outer(inner[i, j]) -- the outer map sampled bilinearly at the positions the inner map
+    holds, so remap(remap(img, outer), inner) and remap(img, C) describe the same geometry.  Device maps under the strided
+    contract, any mix of float32 / float64; dtype: C's, default inner's."""
+    a, sa = _map_tensor(outer, "outer")
+    b, sb = _map_tensor(inner, "inner")
+    if a.device != b.device:
+        raise ValueError("lerf_coords_compose: outer and inner live on different devices")
+    a, b = a.detach(), b.detach()
+    out, so = _map_out(out, b.shape[:2], b.dtype if dtype is None else dtype, b.device, "lerf_coords_compose")
+    with _lib.on_device(b):
+        _lib.check(_lib.lib().lerf_coords_compose(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], b.data_ptr(), _lib._dt(b), sb,
+                                                  out.data_ptr(), _lib._dt(out), so, b.shape[0], b.shape[1],
+                                                  _lib.current_stream(b.device)), "lerf_coords_compose")
+    return out

@@ -1,0 +1,134 @@
+"""Times the coordinate-map builders on the MI355X for a 2160 x 3840 float64 map (133 MB):
+
+  build     every model (homography, radial, brown) written by lerf_coords_build, against the SAME map built by the numpy builder
+            of coords.py plus torch.from_numpy(...).to(device) (wall clock, median of --host-repeats)
+  mesh      a 33 x 61 control mesh upsampled (bilinear, bicubic) and the adjoint of each (lerf_coords_mesh_bwd)
+  compose   an outer 2160 x 3840 map sampled at an inner 2160 x 3840 map
+
+Device times: device events around `--iters` calls after `--warmup` calls, median of `--repeats` windows (tools/bench_remap.py's
+scheme).  With each device time go the bytes the call must move at least once and the share of the HBM peak they imply:
+16 B per entry written; the adjoint reads the map gradient once per tap row (2 or 4 times); compose reads 16 B of the inner map,
+writes 16 B and reads the outer map once (its taps are neighbours' taps).  Prints ONE JSON line; no speed gate -- the in-run
+check is that every device map equals its host form bit for bit.
+
+    python tools/bench_coords.py [--iters 20] [--warmup 5] [--repeats 7] [--host-repeats 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+M_ISC = [[2.05, 0.12, 15.0], [-0.08, 1.95, 40.0], [1.5e-5, -1.0e-5, 1.0]]     # bench.py config 4
+HBM_PEAK = 8.0e12
+
+
+def device_ms(fn, iters, warmup, repeats):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b) / iters)
+    return float(np.median(ms)), float(min(ms)), float(max(ms))
+
+
+def host_ms(fn, repeats):
+    import torch
+    ms, out = [], None
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(ms)), out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--host-repeats", type=int, default=3)
+    ap.add_argument("--in-hw", type=int, nargs=2, default=[1080, 1920])
+    ap.add_argument("--out-hw", type=int, nargs=2, default=[2160, 3840])
+    ap.add_argument("--mesh-hw", type=int, nargs=2, default=[33, 61])
+    a = ap.parse_args()
+    import torch
+    from lerf_pytorch_amd import _lib, coords, ops
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    in_hw, hw, ghw = tuple(a.in_hw), tuple(a.out_hw), tuple(a.mesh_hw)
+    entries = hw[0] * hw[1]
+    K = np.array([[0.9 * in_hw[1], 0.0, (in_hw[1] - 1) / 2.0], [0.0, 0.9 * in_hw[1], (in_hw[0] - 1) / 2.0], [0.0, 0.0, 1.0]])
+    new_K = K * np.array([[2.0], [2.0], [1.0]])
+    dist = [-0.12, 0.03, 0.001, -0.0005, 0.002]
+    builders = {
+        "homography": lambda d: coords.from_homography(np.array(M_ISC), hw, device=d),
+        "radial": lambda d: coords.radial(in_hw, hw, 0.08, -0.02, device=d),
+        "brown": lambda d: coords.undistort_rectify(K, dist, None, new_K, hw, device=d),
+    }
+
+    def row(t, nbytes):
+        return {"ms": round(t[0], 4), "ms_min": round(t[1], 4), "ms_max": round(t[2], 4), "bytes": int(nbytes),
+                "hbm_fraction": round(nbytes / (t[0] * 1e-3) / HBM_PEAK, 4)}
+
+    res = {"tool": "bench_coords", "in_hw": list(in_hw), "out_hw": list(hw), "mesh_hw": list(ghw), "dtype": "float64",
+           "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "host_repeats": a.host_repeats, "map_bytes": 16 * entries}
+    equal = True
+    build = {}
+    for name, fn in builders.items():
+        out = torch.empty(hw + (2,), dtype=torch.float64, device=dev)
+        code, p = _lib.coords_model_params(name, {
+            "homography": np.linalg.inv(np.array(M_ISC)).reshape(9),
+            "radial": [(in_hw[0] - 1) / 2.0, (in_hw[1] - 1) / 2.0, np.hypot(*hw) / 2.0, np.hypot(*in_hw) / 2.0, (hw[0] - 1) / 2.0, (hw[1] - 1) / 2.0, 0.08, -0.02],
+            "brown": coords.brown_params(K, dist, None, new_K)}[name])
+        t = device_ms(lambda: ops.coords_build(name, p, hw, out=out), a.iters, a.warmup, a.repeats)
+        h_ms, h_map = host_ms(lambda: torch.from_numpy(fn(None)).to(dev), a.host_repeats)
+        same = bool(torch.equal(fn(dev), h_map))
+        equal = equal and same
+        build[name] = dict(row(t, 16 * entries), host_numpy_plus_upload_ms=round(h_ms, 2), speedup=round(h_ms / t[0], 1), equals_host=same)
+    res["build"] = build
+
+    rng = np.random.default_rng(0)
+    gy, gx = np.meshgrid(np.linspace(0, in_hw[0] - 1, ghw[0]), np.linspace(0, in_hw[1] - 1, ghw[1]), indexing="ij")
+    ctrl_np = np.stack([gy, gx], axis=-1) + rng.normal(0, 2.0, ghw + (2,))
+    ctrl = torch.from_numpy(ctrl_np).to(dev)
+    G = torch.randn(hw + (2,), dtype=torch.float64, device=dev)
+    gctrl = torch.zeros(ghw + (2,), dtype=torch.float64, device=dev)
+    out = torch.empty(hw + (2,), dtype=torch.float64, device=dev)
+    mesh = {}
+    for interp, taps in (("bilinear", 2), ("bicubic", 4)):
+        t = device_ms(lambda: ops.coords_mesh(ctrl, hw, interp, out=out), a.iters, a.warmup, a.repeats)
+        mesh[interp] = row(t, 16 * entries + ctrl.numel() * 8)
+        tb = device_ms(lambda: ops.coords_mesh_bwd(G, ghw, interp, grad_ctrl=gctrl), a.iters, a.warmup, a.repeats)
+        mesh[interp + "_adjoint"] = row(tb, taps * 16 * entries + 2 * 16 * ghw[0] * hw[1] + 2 * 16 * ghw[0] * ghw[1])
+        same = bool(torch.equal(ops.coords_mesh(ctrl, hw, interp), torch.from_numpy(coords.from_mesh(ctrl_np, hw, interp)).to(dev)))
+        equal = equal and same
+        mesh[interp]["equals_host"] = same
+    res["mesh"] = mesh
+
+    outer = coords.radial(in_hw, hw, 0.08, -0.02, device=dev)
+    inner = coords.from_homography(np.array([[1.01, 0.004, 3.0], [-0.003, 0.99, 5.0], [1e-6, -1e-6, 1.0]]), hw, device=dev)
+    t = device_ms(lambda: ops.coords_compose(outer, inner, out=out), a.iters, a.warmup, a.repeats)
+    res["compose"] = row(t, 3 * 16 * entries)
+    res["device_equals_host"] = equal
+    print(json.dumps(res))
+    if not equal:
+        raise SystemExit("a device-built map differs from its host form")
+
+
+if __name__ == "__main__":
+    main()
