@@ -349,6 +349,22 @@ int lerf_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, i
 int lerf_remap_host_geometry(const lerf_remap_geo_t* geo, int H, int W, double* gr, double* gc, int32_t* lr, int32_t* lc,
                              int32_t pads[2]);
 
+/* The same with ONE MAP PER SAMPLE: `n_maps` maps of geo's shape, dtype and row_stride, `map_stride` ELEMENTS apart; geo describes
+ * map 0.  A call returns exactly what n_maps calls of the plain entry point return, one per map, in one launch:
+ *   lerf_remap_batched          C == n_maps * planes_per_map planes; plane p reads map p / planes_per_map
+ *   lerf_remap_packed_batched   n == n_maps frames; frame f reads map f (RGB S = 2 gauss / linear: one thread per pixel and frame)
+ * LERF_REMAP_PADS_FROM_MAP is resolved per map, from that map's own first entry; explicit pads apply to every map of the call.
+ * Refused with LERF_EINVAL before anything is launched: n_maps < 1; a plane or frame count other than n_maps * planes_per_map
+ * (n_maps for the packed form); a negative or odd map_stride (an entry is two elements: an even stride keeps every map's entries
+ * aligned like map 0's); for n_maps > 1 a map_stride below (out_h - 1) * row_stride + 2 * out_w (overlapping maps).  n_maps == 1
+ * is the plain entry point.  The map builders (lerf_coords_*) stay one parameter set or mesh per launch. */
+int lerf_remap_batched(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
+                       int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const lerf_mplane_t* out,
+                       void* stream);
+int lerf_remap_packed_batched(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_remap_geo_t* geo,
+                              int n_maps, int64_t map_stride, int kind, double max_sigma, const lerf_mplane_t* out, int64_t out_sn,
+                              void* stream);
+
 /* ABI 7.  The whole warp path of the harness (resample/eval_lut_warp.py:100-222: stage 1, stage 2, SteeringGaussianWarp2dNumpy /
  * AmplifiedLinearWarp2dNumpy.warp, resize_right/resize_right2d_numpy.py:516-636) for `n` RGB frames that share one homography,
  * TILE-FUSED: stage 1 runs once per pixel into the workspace (as in lerf_sr_fused_u8); the second launch runs stage 2 per 64 x 64
@@ -649,6 +665,13 @@ int lerf_ubench_lds_gather(int pattern, int iters, int workgroups, uint32_t* sin
 int lerf_remap_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W,
                    const lerf_remap_geo_t* geo, int kind, double max_sigma, const double* grad_out,
                    float* grad_feat, float* grad_h0, float* grad_h1, float* grad_h2, double* grad_coords, void* stream);
+/* lerf_remap_bwd with one map per sample (see lerf_remap_batched): N == n_maps * planes_per_map planes, plane n reads map
+ * n / planes_per_map.  grad_coords stays PER PLANE, float64 [N][out_h][out_w][2], one writer per element: the sum over a sample's
+ * planes is the caller's.  Refuses what lerf_remap_bwd and lerf_remap_batched refuse. */
+int lerf_remap_bwd_batched(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W,
+                           const lerf_remap_geo_t* geo, int n_maps, int64_t map_stride, int planes_per_map, int kind,
+                           double max_sigma, const double* grad_out, float* grad_feat, float* grad_h0, float* grad_h1,
+                           float* grad_h2, double* grad_coords, void* stream);
 
 /* ---- Coordinate maps on the device (csrc/lerf_coords.hip, arithmetic: csrc/lerf_coords_models.h).  A map is what
  * lerf_remap_geo_t.coords reads: [oH][row_stride] elements, (row, col) pairs, entry (i, j) at out + i * row_stride + 2 * j,

@@ -46,9 +46,10 @@ EXPORTS = [
     "lerf_sr_ragged_workspace_bytes", "lerf_sr_fused_ragged_u8", "lerf_stages_ragged_workspace_bytes", "lerf_stages_packed_ragged_u8",
     "lerf_stages_packed_u8", "lerf_unpack_stages", "lerf_warp_packed", "lerf_rect_copy_u8",
     "lerf_warp_tile_boxes", "lerf_warp_fused_supported", "lerf_warp_fused_u8",
-    "lerf_remap", "lerf_remap_packed", "lerf_remap_host_geometry",
+    "lerf_remap", "lerf_remap_packed", "lerf_remap_host_geometry", "lerf_remap_batched", "lerf_remap_packed_batched",
     "lerf_metric_y_sse_u8", "lerf_metric_ssim_y_u8", "lerf_metric_masked_sse_u8",
     "lerf_swf2lut_interp_f32", "lerf_swf2lut_interp_bwd_f32", "lerf_resize_bwd_f32", "lerf_warp_bwd", "lerf_remap_bwd",
+    "lerf_remap_bwd_batched",
     "lerf_srnet_weight_floats", "lerf_srnet_to_lut", "lerf_srnet_fwd_f32", "lerf_srnet_bwd_workspace_bytes", "lerf_srnet_bwd_f32",
     "lerf_imdn_weight_floats", "lerf_imdn_workspace_bytes", "lerf_imdn_fwd_f32",
     "lerf_imdn_saved_bytes", "lerf_imdn_fwd_train_f32", "lerf_imdn_bwd_workspace_bytes", "lerf_imdn_bwd_f32",
@@ -227,6 +228,11 @@ def lib():
                              C.c_int, C.c_double, C.POINTER(Plane), C.c_void_p]
     L.lerf_remap_packed.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo), C.c_int, C.c_double,
                                     C.POINTER(Plane), C.c_int64, C.c_void_p]
+    # one map per sample: geo describes map 0, then n_maps, map_stride (elements) and, for the planar forms, planes per map
+    L.lerf_remap_batched.argtypes = [C.POINTER(Plane), C.POINTER(Plane), C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo), C.c_int,
+                                     C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(Plane), C.c_void_p]
+    L.lerf_remap_packed_batched.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo), C.c_int,
+                                            C.c_int64, C.c_int, C.c_double, C.POINTER(Plane), C.c_int64, C.c_void_p]
     L.lerf_remap_host_geometry.argtypes = [C.POINTER(RemapGeo), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]
     L.lerf_rect_copy_u8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Rect), C.c_int, C.c_int,
@@ -258,6 +264,9 @@ def lib():
                                 C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_remap_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo),
                                  C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lerf_remap_bwd_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RemapGeo),
+                                         C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_srnet_weight_floats.restype = C.c_size_t
     L.lerf_srnet_weight_floats.argtypes = [C.c_int]
     L.lerf_srnet_to_lut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -88,25 +88,51 @@ def from_homography(matrix, out_hw, arithmetic="device", device=None, dtype=None
 
 def from_flow(flow):
     """identity + displacement: flow [H, W, 2] = (d_row, d_col) of every output pixel -> float64 [H, W, 2]; from_flow(0 * flow) is
-    the identity grid (row i, col j)."""
+    the identity grid (row i, col j).  A batch of flows [B, H, W, 2] -> [B, H, W, 2], one map per sample."""
     f = np.asarray(flow.detach().cpu().numpy() if hasattr(flow, "detach") else flow, dtype=np.float64)
-    if f.ndim != 3 or f.shape[2] != 2:
-        raise ValueError("flow must be [H, W, 2]")
-    ii, jj = _grid(f.shape[:2])
+    if f.ndim not in (3, 4) or f.shape[-1] != 2:
+        raise ValueError("flow must be [H, W, 2] or [B, H, W, 2]")
+    ii, jj = _grid(f.shape[-3:-1])
     return np.ascontiguousarray(np.stack([ii + f[..., 0], jj + f[..., 1]], axis=-1))
 
 
 def from_flow_torch(flow):
-    """from_flow with torch ops on the flow's device: flow [H, W, 2] tensor (float32 or float64) -> identity + flow in the flow's
-    dtype, same device.  A flow that requires grad stays in the graph, so a remap class that has opted in with enable_backward()
-    hands it d loss / d flow (resize_right2d_torch.Remap2dTorch)."""
+    """from_flow with torch ops on the flow's device: flow [H, W, 2] (or a batch [B, H, W, 2]) tensor (float32 or float64) ->
+    identity + flow in the flow's dtype, same device.  A flow that requires grad stays in the graph, so a remap class that has
+    opted in with enable_backward() hands it d loss / d flow (resize_right2d_torch.Remap2dTorch)."""
     import torch
-    if not isinstance(flow, torch.Tensor) or flow.ndim != 3 or flow.shape[2] != 2 or not flow.is_floating_point():
-        raise ValueError("flow must be a floating-point [H, W, 2] tensor")
-    ii = torch.arange(flow.shape[0], dtype=flow.dtype, device=flow.device)
-    jj = torch.arange(flow.shape[1], dtype=flow.dtype, device=flow.device)
+    if not isinstance(flow, torch.Tensor) or flow.ndim not in (3, 4) or flow.shape[-1] != 2 or not flow.is_floating_point():
+        raise ValueError("flow must be a floating-point [H, W, 2] or [B, H, W, 2] tensor")
+    ii = torch.arange(flow.shape[-3], dtype=flow.dtype, device=flow.device)
+    jj = torch.arange(flow.shape[-2], dtype=flow.dtype, device=flow.device)
     grid = torch.stack(torch.meshgrid(ii, jj, indexing="ij"), dim=-1)
     return grid + flow
+
+
+def from_grid_sample(grid, in_hw, align_corners=False):
+    """The (row, col) maps of an F.grid_sample grid: grid [B, oH, oW, 2] (or [oH, oW, 2]) of normalised (x, y) in [-1, 1] ->
+    maps of the same shape, dtype and device for a source frame of in_hw = (H, W), with torch ops, so a grid that requires grad
+    stays in the graph:
+
+        align_corners=True:   row = (y + 1) / 2 * (H - 1)          (-1 and +1 are the centres of the first and last pixel)
+        align_corners=False:  row = ((y + 1) * H - 1) / 2          (-1 and +1 are the outer edges: -0.5 and H - 0.5)
+
+    and the columns alike with x and W.  This converts COORDINATES only.  What the remap does with them stays the reference's,
+    not grid_sample's: the point is clipped to [0, H] x [0, W], the support, pads, border handling (pad_mode) and the weights'
+    normalisation are the warp's -- there is no padding_mode / zeros-outside rule of grid_sample here, and a bilinear remap is
+    the reference's bilinear kernel on its own tap set."""
+    import torch
+    if not isinstance(grid, torch.Tensor) or grid.ndim not in (3, 4) or grid.shape[-1] != 2 or not grid.is_floating_point():
+        raise ValueError("grid must be a floating-point [B, oH, oW, 2] (or [oH, oW, 2]) tensor of normalised (x, y)")
+    H, W = int(in_hw[0]), int(in_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("in_hw must be positive")
+    x, y = grid[..., 0], grid[..., 1]
+    if align_corners:
+        row, col = (y + 1) / 2 * (H - 1), (x + 1) / 2 * (W - 1)
+    else:
+        row, col = ((y + 1) * H - 1) / 2, ((x + 1) * W - 1) / 2
+    return torch.stack([row, col], dim=-1)
 
 
 def radial(in_hw, out_hw, k1, k2=0.0, centre=None, device=None, dtype=None):

@@ -328,8 +328,10 @@ int lerf_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, in
     return rc != LERF_OK ? rc : check_launch();
 }
 
-int lerf_remap(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
-               int kind, double max_sigma, const lerf_mplane_t* out, void* stream) {
+// lerf_remap / lerf_remap_batched: n_maps maps, planes_per_map planes each (the plain one: one map, C planes)
+static int remap_planes(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
+                        int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const lerf_mplane_t* out,
+                        void* stream) {
     if (!plane_ok(feat) || !geo || !out || !out->ptr || H < 1 || W < 1 || C < 1) return LERF_EINVAL;
     int nh = kind == LERF_KIND_GAUSS ? 3 : (kind == LERF_KIND_LINEAR ? 1 : 0);
     if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
@@ -339,7 +341,7 @@ int lerf_remap(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int
             hyper[k].sx != hyper[0].sx || hyper[k].sc != hyper[0].sc)
             return LERF_EINVAL;
     RemapGeo m{};
-    int rc = remap_geo(geo, m);
+    int rc = remap_geo_batched(geo, n_maps, map_stride, C, planes_per_map, m);
     if (rc != LERF_OK) return rc;
     if (geo->pad_mode != LERF_PAD_CONSTANT && out->dtype == LERF_U8) return LERF_EUNSUPPORTED;
     WarpArgs a{};
@@ -354,16 +356,41 @@ int lerf_remap(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int
     return rc != LERF_OK ? rc : check_launch();
 }
 
-int lerf_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_remap_geo_t* geo, int kind,
-                      double max_sigma, const lerf_mplane_t* out, int64_t out_sn, void* stream) {
+int lerf_remap(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
+               int kind, double max_sigma, const lerf_mplane_t* out, void* stream) {
+    return remap_planes(feat, hyper, H, W, C, geo, 1, 0, C, kind, max_sigma, out, stream);
+}
+
+int lerf_remap_batched(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
+                       int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const lerf_mplane_t* out,
+                       void* stream) {
+    return remap_planes(feat, hyper, H, W, C, geo, n_maps, map_stride, planes_per_map, kind, max_sigma, out, stream);
+}
+
+// lerf_remap_packed / lerf_remap_packed_batched: n_maps == 0 is the plain one (the n frames share the map), else frame f reads map f
+static int remap_packed_frames(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_remap_geo_t* geo,
+                               int n_maps, int64_t map_stride, int kind, double max_sigma, const lerf_mplane_t* out, int64_t out_sn,
+                               void* stream) {
     if (!packed || !geo || !out || !out->ptr || n < 1 || H < 1 || W < 1 || C < 1) return LERF_EINVAL;
     RemapGeo m{};
-    int rc = remap_geo(geo, m);
+    int rc = n_maps == 0 ? remap_geo(geo, m) : remap_geo_batched(geo, n_maps, map_stride, n, 1, m);
     if (rc != LERF_OK) return rc;
     if (geo->pad_mode != LERF_PAD_CONSTANT) return LERF_EUNSUPPORTED;
     rc = launch_remap_packed(packed, packed_sn, n, H, W, C, m, kind, (float)max_sigma, out->ptr, out->dtype, out->sy, out->sx,
                              out->sc, out_sn, as_stream(stream));
     return rc != LERF_OK ? rc : check_launch();
+}
+
+int lerf_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_remap_geo_t* geo, int kind,
+                      double max_sigma, const lerf_mplane_t* out, int64_t out_sn, void* stream) {
+    return remap_packed_frames(packed, packed_sn, n, H, W, C, geo, 0, 0, kind, max_sigma, out, out_sn, stream);
+}
+
+int lerf_remap_packed_batched(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const lerf_remap_geo_t* geo,
+                              int n_maps, int64_t map_stride, int kind, double max_sigma, const lerf_mplane_t* out, int64_t out_sn,
+                              void* stream) {
+    if (n_maps < 1) return LERF_EINVAL;
+    return remap_packed_frames(packed, packed_sn, n, H, W, C, geo, n_maps, map_stride, kind, max_sigma, out, out_sn, stream);
 }
 
 int lerf_remap_host_geometry(const lerf_remap_geo_t* geo, int H, int W, double* gr, double* gc, int32_t* lr, int32_t* lc,

@@ -50,8 +50,11 @@ struct RemapGeo {
     int S, oH, oW;
     const void* coords; int f32;     // [oH][stride] elements, (row, col) pairs; f32: float32 entries (else float64)
     int64_t stride;
-    int pad_r_lo, pad_c_lo;          // < 0: derived from coords[0][0] (remap_pad_lo)
+    int pad_r_lo, pad_c_lo;          // < 0: derived from coords[0][0] (remap_pad_lo) of the thread's own map
     int pad_mode;
+    // one map per sample (lerf_remap*_batched): plane / frame p reads map p / ppm, `map_stride` elements after the one before.
+    // map_stride == 0: ONE map for the whole call (the plain entry points), and ppm is not read
+    int64_t map_stride; int ppm;
 };
 int launch_remap(const WarpArgs& a, const RemapGeo& m, hipStream_t st);      // a.geo is not read: the geometry is m
 int launch_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const RemapGeo& m, int kind,

@@ -11,7 +11,12 @@
 // Everything from the point on is the shared body of lerf_warp_kernels.h, so the map of a homography gives the homographic
 // warp's bytes.
 //
-// Addresses: the map is read at (i, j) inside the launch's [oH][oW] only; the point is clipped to [0, H] x [0, W] BEFORE any
+// One map per sample (lerf_remap*_batched, RemapGeo.map_stride != 0): the plane (remap_kernel) or the frame (the packed kernels)
+// of a thread selects its map before the load (remap_select); pads left to the map come from THAT map's first entry.  With per-frame
+// maps the per-pixel kernel has no pixel geometry to share between frames, so the frame goes on the grid (PER_FRAME).
+//
+// Addresses: the map is read at (i, j) inside the launch's [oH][oW] of one of the call's maps only (remap_geo_batched: the maps are
+// n_maps disjoint extents, map_stride apart); the point is clipped to [0, H] x [0, W] BEFORE any
 // conversion to int (clip_coord sends NaN to 0 and +-inf to the borders), and every tap index passes axis_tap's clamps, so no
 // map value -- NaN, infinite, or 1e300 -- can form an address outside the operands.  A NaN entry reads nothing further and
 // stores 0 (uint8) / NaN (float).
@@ -35,6 +40,7 @@ remap_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
     int j = xc / C;
     int c = xc - j * C;
     TO* dst = out + i * oy + j * ox + c * oc;
+    remap_select(m, c);                                    // plane c reads its sample's map
     const MapPoint q = remap_entry(m, i, j);
     if (no_point(q)) { store_no_value(dst); return; }
     const WarpGeo g = remap_warp_geo(m, H, W);
@@ -82,8 +88,9 @@ template <typename TO, int KIND>
 __global__ void __launch_bounds__(256)
 remap_packed_kernel(const uint32_t* __restrict__ packed, int64_t packed_sn, int H, int W, int C, RemapGeo m, float max_sigma,
                     TO* __restrict__ out, int64_t oy, int64_t ox, int64_t oc, int64_t out_sn) {
-    packed += (int64_t)blockIdx.z * packed_sn;             // frame of the batch (one map for all)
+    packed += (int64_t)blockIdx.z * packed_sn;             // frame of the batch (one map for all, or its own)
     out += (int64_t)blockIdx.z * out_sn;
+    remap_select(m, (int)blockIdx.z);
     int xc = blockIdx.x * blockDim.x + threadIdx.x;
     int i = blockIdx.y;
     if (xc >= m.oW * C) return;
@@ -97,11 +104,21 @@ remap_packed_kernel(const uint32_t* __restrict__ packed, int64_t packed_sn, int 
 }
 
 // one thread per output PIXEL of an RGB frame with S = 2; the block order of warp_packed_px_kernel (warp_px_block), so the
-// lanes of a wave read 64 consecutive map entries (1 KiB of float64 entries per load instruction)
-template <typename TO, int KIND, bool PROD = false>
+// lanes of a wave read 64 consecutive map entries (1 KiB of float64 entries per load instruction).
+// PER_FRAME: every frame has its own map, so there is no pixel geometry to share between frames: the frame goes on the grid
+// (blockIdx.y), one frame per thread, the block order inside a frame unchanged -- a wave still reads 64 consecutive entries of
+// its frame's map.  Otherwise one thread walks the batch's frames with the geometry of the shared map
+template <typename TO, int KIND, bool PROD = false, bool PER_FRAME = false>
 __global__ void __launch_bounds__(256)
 remap_packed_px_kernel(const uint32_t* __restrict__ packed0, int64_t packed_sn, int n_frames, int H, int W, RemapGeo m, float max_sigma,
                        TO* __restrict__ out0, int64_t oy, int64_t ox, int64_t oc, int64_t out_sn) {
+    if constexpr (PER_FRAME) {
+        const int fr = (int)blockIdx.y;
+        packed0 += (int64_t)fr * packed_sn;
+        out0 += (int64_t)fr * out_sn;
+        remap_select(m, fr);
+        n_frames = 1;
+    }
     int i, j;
     warp_px_block(m.oW, &i, &j);
     if (j >= m.oW) return;
@@ -124,10 +141,16 @@ int launch_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H,
     if (n < 1 || n > 65535 || m.oH > 65535) return LERF_EUNSUPPORTED;
     if (C == 3 && m.S == 2 && (kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) &&
         (out_dtype == LERF_U8 || out_dtype == LERF_F32)) {
-        dim3 blockp(256), gridp((unsigned)(((m.oW + 255) / 256) * m.oH), 1, 1);
-#define LERF_RPX(TO, KIND, PROD)                                                                                      \
-    hipLaunchKernelGGL((remap_packed_px_kernel<TO, KIND, PROD>), gridp, blockp, 0, st, packed, packed_sn, n, H, W, m, max_sigma, (TO*)out, \
-                       oy, ox, oc, out_sn)
+        const bool per_frame = m.map_stride != 0;
+        dim3 blockp(256), gridp((unsigned)(((m.oW + 255) / 256) * m.oH), per_frame ? n : 1, 1);
+#define LERF_RPX1(TO, KIND, PROD, PER_FRAME)                                                                                      \
+    hipLaunchKernelGGL((remap_packed_px_kernel<TO, KIND, PROD, PER_FRAME>), gridp, blockp, 0, st, packed, packed_sn, n, H, W, m, max_sigma, \
+                       (TO*)out, oy, ox, oc, out_sn)
+#define LERF_RPX(TO, KIND, PROD)                     \
+    do {                                             \
+        if (per_frame) LERF_RPX1(TO, KIND, PROD, true); \
+        else LERF_RPX1(TO, KIND, PROD, false);       \
+    } while (0)
         const bool prod = out_dtype == LERF_U8 && max_sigma <= s3::kNoShiftMaxSigma;     // production arithmetic + tie guard
         if (kind == LERF_KIND_GAUSS) {
             if (prod) LERF_RPX(uint8_t, LERF_KIND_GAUSS, true);
@@ -139,6 +162,7 @@ int launch_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H,
             else LERF_RPX(float, LERF_KIND_LINEAR, false);
         }
 #undef LERF_RPX
+#undef LERF_RPX1
         return LERF_OK;
     }
     dim3 block(256), grid((m.oW * C + 255) / 256, m.oH, n);

@@ -32,6 +32,7 @@ remap_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ h0, c
     const int tid = threadIdx.x;
     const int i = blockIdx.y * WB_ROWS + tid / WB_COLS, j = blockIdx.x * WB_COLS + tid % WB_COLS, n = blockIdx.z;
     bool act = i < m.oH && j < m.oW;
+    remap_select(m, n);                                    // plane n reads its sample's map (uniform over the block)
     const WarpGeo g = remap_warp_geo(m, H, W);
     MapPoint q{0.0, 0.0};
     WarpPixel px{};
@@ -58,14 +59,13 @@ remap_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ h0, c
 using namespace lerf;
 using namespace lerf::warp_bwd;
 
-extern "C" {
-
-int lerf_remap_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W, const lerf_remap_geo_t* geo,
-                   int kind, double max_sigma, const double* grad_out, float* grad_feat, float* grad_h0, float* grad_h1, float* grad_h2,
-                   double* grad_coords, void* stream) {
+// both entry points: n_maps maps, planes_per_map planes each (the plain one: one map, N planes)
+static int remap_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W, const lerf_remap_geo_t* geo,
+                     int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const double* grad_out, float* grad_feat,
+                     float* grad_h0, float* grad_h1, float* grad_h2, double* grad_coords, void* stream) {
     if (!feat || !geo || !grad_out || N < 1 || H < 1 || W < 1) return LERF_EINVAL;
     RemapGeo m{};
-    const int rc = remap_geo(geo, m);
+    const int rc = remap_geo_batched(geo, n_maps, map_stride, N, planes_per_map, m);
     if (rc != LERF_OK) return rc;
     if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
     if ((kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) && !h0) return LERF_EINVAL;
@@ -97,6 +97,23 @@ int lerf_remap_bwd(const float* feat, const float* h0, const float* h1, const fl
 #undef LERF_RB
 #undef LERF_RB1
     return launch_status();
+}
+
+extern "C" {
+
+int lerf_remap_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W, const lerf_remap_geo_t* geo,
+                   int kind, double max_sigma, const double* grad_out, float* grad_feat, float* grad_h0, float* grad_h1, float* grad_h2,
+                   double* grad_coords, void* stream) {
+    return remap_bwd(feat, h0, h1, h2, N, H, W, geo, 1, 0, N, kind, max_sigma, grad_out, grad_feat, grad_h0, grad_h1, grad_h2,
+                     grad_coords, stream);
+}
+
+int lerf_remap_bwd_batched(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W,
+                           const lerf_remap_geo_t* geo, int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma,
+                           const double* grad_out, float* grad_feat, float* grad_h0, float* grad_h1, float* grad_h2, double* grad_coords,
+                           void* stream) {
+    return remap_bwd(feat, h0, h1, h2, N, H, W, geo, n_maps, map_stride, planes_per_map, kind, max_sigma, grad_out, grad_feat, grad_h0,
+                     grad_h1, grad_h2, grad_coords, stream);
 }
 
 }  // extern "C"

@@ -23,6 +23,15 @@ __device__ __forceinline__ MapPoint remap_entry(const RemapGeo& m, int i, int j)
     return {v.x, v.y};
 }
 
+// the map of plane (or frame) p of a call with one map per sample: `coords` moves to map p / ppm, everything else is shared.  A
+// call with ONE map (map_stride == 0) takes the uniform branch and pays no division
+__device__ __forceinline__ void remap_select(RemapGeo& m, int p) {
+    if (m.map_stride == 0) return;
+    const int64_t o = (int64_t)(p / m.ppm) * m.map_stride;
+    m.coords = m.f32 ? static_cast<const void*>(static_cast<const float*>(m.coords) + o)
+                     : static_cast<const void*>(static_cast<const double*>(m.coords) + o);
+}
+
 __device__ __forceinline__ bool no_point(const MapPoint& q) { return q.r != q.r || q.c != q.c; }
 
 // the WarpGeo the shared bodies read (S, output size, low pads, pad mode; no matrix, no rectangle offsets).  Low pads the caller
@@ -61,6 +70,23 @@ inline int remap_geo(const lerf_remap_geo_t* geo, RemapGeo& m) {
     m.S = geo->S; m.oH = geo->out_h; m.oW = geo->out_w;
     m.coords = geo->coords; m.f32 = geo->coords_dtype == LERF_F32; m.stride = geo->row_stride;
     m.pad_r_lo = geo->pad_r_lo; m.pad_c_lo = geo->pad_c_lo; m.pad_mode = geo->pad_mode;
+    m.map_stride = 0; m.ppm = 1;
+    return LERF_OK;
+}
+
+// the same for `n_maps` maps, `map_stride` elements apart, geo describing map 0 (the *_batched entry points): `count` planes or
+// frames, `ppm` of them per map.  An even stride keeps every map's entries aligned like map 0's (an entry is two elements); maps
+// may not overlap.  One map: the stride is checked and then not used -- the call is the plain entry point's
+inline int remap_geo_batched(const lerf_remap_geo_t* geo, int n_maps, int64_t map_stride, int count, int ppm, RemapGeo& m) {
+    const int rc = remap_geo(geo, m);
+    if (rc != LERF_OK) return rc;
+    if (n_maps < 1 || ppm < 1 || count < 1 || count % n_maps != 0 || (int64_t)n_maps * ppm != count) return LERF_EINVAL;
+    const size_t elem = geo->coords_dtype == LERF_F32 ? 4 : 8;
+    if (map_stride < 0 || (map_stride & 1) || ((size_t)map_stride * elem) % (2 * elem) != 0) return LERF_EINVAL;
+    if (n_maps > 1) {
+        if (map_stride < (int64_t)(geo->out_h - 1) * geo->row_stride + 2 * (int64_t)geo->out_w) return LERF_EINVAL;
+        m.map_stride = map_stride; m.ppm = ppm;
+    }
     return LERF_OK;
 }
 

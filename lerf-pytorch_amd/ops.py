@@ -193,32 +193,43 @@ class RemapGeometry:
     projected through a matrix.  coords: float64 / float32 [oH, oW, 2], entry (i, j) = (row, col) of the source position of
     output pixel (i, j), unclipped, integers = pixel indices (coords.py builds such maps).  A numpy array (or a host tensor)
     is uploaded once per device and kept with the geometry; a device tensor is used in place -- its last dimension must be
-    contiguous and its column stride 2, its row stride is free (a tile of a larger map is a view of it)."""
+    contiguous and its column stride 2, its row stride is free (a tile of a larger map is a view of it).
+
+    ONE MAP PER SAMPLE: coords [B, oH, oW, 2] (`batched`, `n_maps` = B) -- the planes or frames of a call are dealt to the maps
+    in order, planes-per-map at a time, and the call returns what B calls with one map each return (lerf_remap*_batched: one
+    launch).  The batch stride of a device tensor is free like the row stride: even, and for B > 1 at least one map's extent
+    (oH - 1) * row stride + 2 * oW.  Each map has its own derived low pads."""
 
     def __init__(self, in_hw, coords, support=2, pad_mode=0, pads=None):
         """pads = (pad_r_lo, pad_c_lo): explicit low pads -- a tile of a larger map passes the WHOLE map's (whole.pads());
-        None: the reference's, derived on the device from coords[0, 0] (calc_pad_sz, resize_right2d_numpy.py:363-369)."""
+        None: the reference's, derived on the device from coords[0, 0] (calc_pad_sz, resize_right2d_numpy.py:363-369), of
+        every map its own.  Explicit pads apply to every map of a batch."""
         self.in_hw, self.S, self.pad_mode = (int(in_hw[0]), int(in_hw[1])), int(support), int(pad_mode)
         if self.in_hw[0] < 1 or self.in_hw[1] < 1:
             raise ValueError("in_hw must be positive")
         dev = getattr(coords, "is_cuda", False)
         c = coords if dev else np.asarray(coords.detach().numpy() if hasattr(coords, "detach") else coords)
-        if c.ndim != 3 or c.shape[2] != 2 or c.shape[0] < 1 or c.shape[1] < 1:
-            raise ValueError("coords must be [oH, oW, 2]")
+        if c.ndim not in (3, 4) or c.shape[-1] != 2 or any(n < 1 for n in c.shape[:-1]):
+            raise ValueError("coords must be [oH, oW, 2] or [B, oH, oW, 2]")
+        self.batched = c.ndim == 4
+        self.n_maps = int(c.shape[0]) if self.batched else 1
         if dev:
             torch = _torch()
             c = c.detach()                   # the geometry reads the map's memory; its graph, if any, is the caller's (_RemapFn)
             if c.dtype not in (torch.float32, torch.float64):
                 raise ValueError("coords must be float32 or float64")
-            if c.stride(2) != 1 or c.stride(1) != 2 or c.stride(0) % 2 or c.stride(0) < 2 * c.shape[1] \
+            if c.stride(-1) != 1 or c.stride(-2) != 2 or c.stride(-3) % 2 or c.stride(-3) < 2 * c.shape[-2] \
                     or c.data_ptr() % (2 * c.element_size()):
                 raise ValueError("device coords: contiguous (row, col) pairs, column stride 2, even row stride, entry-aligned")
+            if self.batched and (c.stride(0) % 2 or c.stride(0) < 0 or
+                                 (self.n_maps > 1 and c.stride(0) < (c.shape[1] - 1) * c.stride(1) + 2 * c.shape[2])):
+                raise ValueError("device coords: even batch stride of at least one map's extent")
             self._host, self._dev = None, {str(c.device): c}
         else:
             if c.dtype not in (np.float32, np.float64):
                 c = c.astype(np.float64)
             self._host, self._dev = np.ascontiguousarray(c), {}
-        self.out_hw = (int(c.shape[0]), int(c.shape[1]))
+        self.out_hw = (int(c.shape[-3]), int(c.shape[-2]))
         self.explicit_pads = None if pads is None else (int(pads[0]), int(pads[1]))
         if self.explicit_pads is not None and not all(0 <= p <= _lib.LERF_MAX_SUPPORT for p in self.explicit_pads):
             raise ValueError("pads must be non-negative low pads")
@@ -232,32 +243,51 @@ class RemapGeometry:
         return self._dev[key]
 
     def struct(self, device):
+        """(lerf_remap_geo_t of the map -- of map 0 of a batch --, the device tensor it points into)"""
         c = self.device_coords(device)
         g = _lib.RemapGeo()
         g.S, g.out_h, g.out_w = self.S, self.out_hw[0], self.out_hw[1]
-        g.coords, g.coords_dtype, g.row_stride = c.data_ptr(), _lib._dt(c), c.stride(0)
+        g.coords, g.coords_dtype, g.row_stride = c.data_ptr(), _lib._dt(c), c.stride(-3)
         g.pad_mode = self.pad_mode
         g.pad_r_lo, g.pad_c_lo = self.explicit_pads if self.explicit_pads is not None else (_lib.REMAP_PADS_FROM_MAP,) * 2
         return g, c
 
+    def map_stride(self, device):
+        """elements between consecutive maps of a batch on `device` (what lerf_remap*_batched take beside struct())"""
+        if not self.batched:
+            raise ValueError("one map: no batch stride")
+        return int(self.device_coords(device).stride(0))
+
     def _first_entry(self):
+        """the first entry of the map, [1, 1, 2] (of every map of a batch: [B, 1, 1, 2]), on the host"""
         if self._host is not None:
-            return self._host[:1, :1]
-        return next(iter(self._dev.values()))[:1, :1].cpu().numpy()
+            return self._host[..., :1, :1, :]
+        return next(iter(self._dev.values()))[..., :1, :1, :].cpu().numpy()
 
     def pads(self):
-        """(pad_r_lo, pad_c_lo) the kernels use: the explicit ones, else derived from coords[0, 0] (host mirror of the kernels' rule)"""
+        """(pad_r_lo, pad_c_lo) the kernels use: the explicit ones, else derived from coords[0, 0] (host mirror of the kernels' rule).
+        A batch: int32 [B, 2], one row per map."""
+        if not self.batched:
+            if self.explicit_pads is not None:
+                return self.explicit_pads
+            return _lib.remap_host_geometry(self._first_entry(), self.in_hw, self.S)[4]
         if self.explicit_pads is not None:
-            return self.explicit_pads
-        return _lib.remap_host_geometry(self._first_entry(), self.in_hw, self.S)[4]
+            return np.array([self.explicit_pads] * self.n_maps, dtype=np.int32)
+        return np.array([_lib.remap_host_geometry(e, self.in_hw, self.S)[4] for e in self._first_entry()], dtype=np.int32)
 
     def host_geometry(self):
-        """host mirror of the kernels' per-pixel geometry: (gr, gc, lr, lc, pads), see _lib.remap_host_geometry"""
+        """host mirror of the kernels' per-pixel geometry: (gr, gc, lr, lc, pads), see _lib.remap_host_geometry.  A batch: the
+        per-map results stacked on a leading axis ([B, oH, oW] each, pads int32 [B, 2])."""
         c = self._host if self._host is not None else next(iter(self._dev.values())).cpu().numpy()
-        return _lib.remap_host_geometry(c, self.in_hw, self.S, self.explicit_pads)
+        if not self.batched:
+            return _lib.remap_host_geometry(c, self.in_hw, self.S, self.explicit_pads)
+        per = [_lib.remap_host_geometry(m, self.in_hw, self.S, self.explicit_pads) for m in c]
+        return tuple(np.stack([p[k] for p in per]) for k in range(4)) + (np.array([p[4] for p in per], dtype=np.int32),)
 
     def rows(self, i0, i1):
         """the geometry of output rows [i0, i1) alone, with THIS map's pads (a view of the map, nothing is copied)"""
+        if self.batched:
+            raise ValueError("rows() of a batched map: every map has its own pads, and explicit pads apply to all maps of a call")
         if not 0 <= i0 < i1 <= self.out_hw[0]:
             raise ValueError("rows outside the map")
         src = self._host if self._host is not None else next(iter(self._dev.values()))
@@ -491,7 +521,8 @@ def warp_packed(packed, geo: "WarpGeometry", kind="gauss", max_sigma=10.0, out="
 
 def remap_packed(packed, geo: "RemapGeometry", kind="gauss", max_sigma=10.0, out="u8"):
     """warp_packed by a coordinate map (lerf_remap_packed): packed int32 [H,W,C] or a batch [N,H,W,C] sharing the map (ONE launch
-    for the batch).  out: "u8" / "f32" (a fresh tensor) or a caller-owned uint8 / float32 tensor of the output shape."""
+    for the batch).  A batched geometry (one map per frame, lerf_remap_packed_batched): frame f reads map f, N == geo.n_maps, still
+    one launch.  out: "u8" / "f32" (a fresh tensor) or a caller-owned uint8 / float32 tensor of the output shape."""
     torch = _torch()
     squeeze = packed.dim() == 3
     p = packed.unsqueeze(0) if squeeze else packed
@@ -500,6 +531,8 @@ def remap_packed(packed, geo: "RemapGeometry", kind="gauss", max_sigma=10.0, out
     N, H, W, Cn = p.shape
     if (H, W) != geo.in_hw:
         raise ValueError("packed maps do not match the geometry's frame")
+    if geo.batched and N != geo.n_maps:
+        raise ValueError("%d frames for %d maps: a batched geometry takes one frame per map" % (N, geo.n_maps))
     oshape = (N, geo.out_hw[0], geo.out_hw[1], Cn)
     if isinstance(out, str):
         o = torch.empty(oshape, dtype=_out_dtype(out), device=p.device)
@@ -510,8 +543,13 @@ def remap_packed(packed, geo: "RemapGeometry", kind="gauss", max_sigma=10.0, out
             raise ValueError("out must be a uint8/float32 tensor of shape %s on the input's device" % (oshape[1:] if squeeze else oshape,))
     po = _lib.plane(o, o.stride(1), o.stride(2), o.stride(3))
     g, _keep = geo.struct(p.device)
-    _lib.check(_lib.lib().lerf_remap_packed(p.data_ptr(), p.stride(0), N, H, W, Cn, C.byref(g), KINDS[kind], float(max_sigma),
-                                            C.byref(po), o.stride(0), _lib.current_stream()), "lerf_remap_packed")
+    if geo.batched:
+        _lib.check(_lib.lib().lerf_remap_packed_batched(p.data_ptr(), p.stride(0), N, H, W, Cn, C.byref(g), geo.n_maps,
+                                                        geo.map_stride(p.device), KINDS[kind], float(max_sigma), C.byref(po),
+                                                        o.stride(0), _lib.current_stream()), "lerf_remap_packed_batched")
+    else:
+        _lib.check(_lib.lib().lerf_remap_packed(p.data_ptr(), p.stride(0), N, H, W, Cn, C.byref(g), KINDS[kind], float(max_sigma),
+                                                C.byref(po), o.stride(0), _lib.current_stream()), "lerf_remap_packed")
     return o[0] if squeeze else o
 
 
@@ -691,14 +729,47 @@ def warp_planar(feat, hypers, geo: WarpGeometry, kind="gauss", max_sigma=10.0, o
     return o
 
 
+def _remap_call(geo, device, pf, ph, H, W, planes, kind, max_sigma, po):
+    """lerf_remap, or lerf_remap_batched for a geometry with one map per sample (`planes` = n_maps * planes per map)"""
+    g, _keepc = geo.struct(device)
+    if geo.batched:
+        if planes % geo.n_maps:
+            raise ValueError("%d planes for %d maps: every map takes the same number of planes" % (planes, geo.n_maps))
+        _lib.check(_lib.lib().lerf_remap_batched(C.byref(pf), ph, H, W, planes, C.byref(g), geo.n_maps, geo.map_stride(device),
+                                                 planes // geo.n_maps, KINDS[kind], float(max_sigma), C.byref(po),
+                                                 _lib.current_stream()), "lerf_remap_batched")
+    else:
+        _lib.check(_lib.lib().lerf_remap(C.byref(pf), ph, H, W, planes, C.byref(g), KINDS[kind], float(max_sigma),
+                                         C.byref(po), _lib.current_stream()), "lerf_remap")
+
+
 def remap_hwc_u8(feat_u8, hq_u8, geo: RemapGeometry, kind="gauss", max_sigma=10.0, out="u8"):
-    """warp_hwc_u8 by a coordinate map (lerf_remap)"""
+    """warp_hwc_u8 by a coordinate map (lerf_remap).  A batched geometry (one map per frame, lerf_remap_batched): feat
+    [N,H,W,C], hq [N,H,W,C,oC], N == geo.n_maps -> [N,oH,oW,C] in ONE launch.  The C ABI strides planes by one step, so the
+    frames are interleaved for it ([H,W,N,C]: plane n * C + c) and the output is copied back to frame-major."""
     torch = _torch()
+    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
+    if geo.batched:
+        if feat_u8.dim() != 4 or feat_u8.shape[0] != geo.n_maps:
+            raise ValueError("a batched geometry takes [N,H,W,C] frames, one per map (N = %d)" % geo.n_maps)
+        N, H, W, Cn = feat_u8.shape
+        if (H, W) != geo.in_hw:
+            raise ValueError("the maps do not match the geometry's frame")
+        feat = feat_u8.permute(1, 2, 0, 3).contiguous().view(H, W, N * Cn)
+        o = torch.empty((geo.out_hw[0], geo.out_hw[1], N * Cn), dtype=_out_dtype(out), device=feat.device)
+        if nh:
+            if hq_u8.dim() != 5 or tuple(hq_u8.shape[:4]) != (N, H, W, Cn) or hq_u8.shape[4] < nh:
+                raise ValueError("hyper shape mismatch")
+            hq = hq_u8.permute(1, 2, 0, 3, 4).contiguous().view(H, W, N * Cn, hq_u8.shape[4])
+            ph, _keep = _hyper_planes(hq, "hwck", nh)
+        else:
+            ph = None
+        _remap_call(geo, feat.device, _planes_hwc(feat), ph, H, W, N * Cn, kind, max_sigma, _planes_hwc(o))
+        return o.view(geo.out_hw[0], geo.out_hw[1], N, Cn).permute(2, 0, 1, 3).contiguous()
     feat = feat_u8.contiguous()
     H, W, Cn = feat.shape
     if (H, W) != geo.in_hw:
         raise ValueError("the maps do not match the geometry's frame")
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
     o = torch.empty((geo.out_hw[0], geo.out_hw[1], Cn), dtype=_out_dtype(out), device=feat.device)
     pf = _planes_hwc(feat)
     if nh:
@@ -707,20 +778,21 @@ def remap_hwc_u8(feat_u8, hq_u8, geo: RemapGeometry, kind="gauss", max_sigma=10.
     else:
         ph = None
     po = _planes_hwc(o)
-    g, _keepc = geo.struct(feat.device)
-    _lib.check(_lib.lib().lerf_remap(C.byref(pf), ph, H, W, Cn, C.byref(g), KINDS[kind], float(max_sigma),
-                                     C.byref(po), _lib.current_stream()), "lerf_remap")
+    _remap_call(geo, feat.device, pf, ph, H, W, Cn, kind, max_sigma, po)
     return o
 
 
 def remap_planar(feat, hypers, geo: RemapGeometry, kind="gauss", max_sigma=10.0, out="f32"):
-    """warp_planar by a coordinate map (lerf_remap): float32 [N,H,W] planes -> [N,oH,oW]"""
+    """warp_planar by a coordinate map (lerf_remap): float32 [N,H,W] planes -> [N,oH,oW].  A batched geometry (lerf_remap_batched):
+    N = geo.n_maps * P, planes [b * P, (b + 1) * P) read map b."""
     torch = _torch()
     feat = feat.contiguous().float()
     nh = {"gauss": 3, "linear": 1}.get(kind, 0)
     N, H, W = feat.shape
     if (H, W) != geo.in_hw:
         raise ValueError("the maps do not match the geometry's frame")
+    if geo.batched and N % geo.n_maps:
+        raise ValueError("%d planes for %d maps: every map takes the same number of planes" % (N, geo.n_maps))
     o = torch.empty((N, geo.out_hw[0], geo.out_hw[1]), dtype=_out_dtype(out), device=feat.device)
     pf = _planes_chw(feat)
     if nh:
@@ -729,9 +801,7 @@ def remap_planar(feat, hypers, geo: RemapGeometry, kind="gauss", max_sigma=10.0,
     else:
         ph = None
     po = _planes_chw(o)
-    g, _keepc = geo.struct(feat.device)
-    _lib.check(_lib.lib().lerf_remap(C.byref(pf), ph, H, W, N, C.byref(g), KINDS[kind], float(max_sigma),
-                                     C.byref(po), _lib.current_stream()), "lerf_remap")
+    _remap_call(geo, feat.device, pf, ph, H, W, N, kind, max_sigma, po)
     return o
 
 
@@ -763,7 +833,7 @@ def remap_bwd_planar(feat, hypers, geo: RemapGeometry, kind, max_sigma, grad_out
     float64 upstream gradient `grad_out` [N, oH, oW] into `grads` = [grad_feat, grad_h0, grad_h1, grad_h2] (float32
     [N, H, W] contiguous tensors, or None to skip a map) and, when given, the map gradient into `grad_coords` (float64
     [N, oH, oW, 2] contiguous, PER PLANE: the caller sums over the planes that share the map).  feat / hypers: float32
-    [N, H, W]."""
+    [N, H, W].  A batched geometry (lerf_remap_bwd_batched): N = geo.n_maps * P, planes [b * P, (b + 1) * P) read map b."""
     torch = _torch()
     feat = feat.contiguous().float()
     nh = {"gauss": 3, "linear": 1}.get(kind, 0)
@@ -772,6 +842,8 @@ def remap_bwd_planar(feat, hypers, geo: RemapGeometry, kind, max_sigma, grad_out
     N, H, W = feat.shape
     if (H, W) != geo.in_hw:
         raise ValueError("the maps do not match the geometry's frame")
+    if geo.batched and N % geo.n_maps:
+        raise ValueError("%d planes for %d maps: every map takes the same number of planes" % (N, geo.n_maps))
     if tuple(g.shape) != (N, geo.out_hw[0], geo.out_hw[1]):
         raise ValueError("grad_out must be [N, out_h, out_w] of the geometry")
     grads = list(grads) + [None] * (4 - len(grads))
@@ -784,6 +856,12 @@ def remap_bwd_planar(feat, hypers, geo: RemapGeometry, kind, max_sigma, grad_out
     ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
     hp = [ptr(h) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
     gs, _keepc = geo.struct(feat.device)
+    if geo.batched:
+        _lib.check(_lib.lib().lerf_remap_bwd_batched(ptr(feat), hp[0], hp[1], hp[2], N, H, W, C.byref(gs), geo.n_maps,
+                                                     geo.map_stride(feat.device), N // geo.n_maps, KINDS[kind], float(max_sigma),
+                                                     ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]),
+                                                     ptr(grad_coords), _lib.current_stream()), "lerf_remap_bwd_batched")
+        return grads
     _lib.check(_lib.lib().lerf_remap_bwd(ptr(feat), hp[0], hp[1], hp[2], N, H, W, C.byref(gs), KINDS[kind], float(max_sigma),
                                          ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]), ptr(grad_coords),
                                          _lib.current_stream()), "lerf_remap_bwd")

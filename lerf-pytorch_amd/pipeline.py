@@ -135,9 +135,15 @@ class LerfEngine:
         read from `coords` ([oH,oW,2] float64 / float32 (row, col), numpy or a device tensor; or an ops.RemapGeometry of this
         engine's support, which keeps the uploaded map between frames).  Same path selection as warp() minus the tile-fused
         branch (a dense map has no closed-form tile boxes); the mask is the NEAREST S = 1 remap of the white frame with a
-        `border`-px black rim."""
+        `border`-px black rim.
+
+        A batch [N,H,W,C] -> ([N,oH,oW,C], mask [N,oH,oW,C]): with a [oH,oW,2] map the frames share it (the shared-map
+        launch, one mask for all); with a [N,oH,oW,2] map frame f reads map f -- one batched stage-3 launch and one batched
+        nearest launch for the N masks -- and the result is what N single-frame calls return."""
         torch = _lib.require_gpu()
         x, as_np = self._dev(img)
+        if x.dim() == 4:
+            return self._remap_batch(x, as_np, coords, border, return_mask, out)
         H, W, Cn = x.shape
         if isinstance(coords, ops.RemapGeometry):
             geo = coords
@@ -148,6 +154,8 @@ class LerfEngine:
             src = coords.to(x.device) if isinstance(coords, torch.Tensor) else coords
             geo = ops.RemapGeometry((H, W), src, self.support)
             src = geo.device_coords(x.device)
+        if geo.batched:
+            raise ValueError("one frame takes one [oH,oW,2] map; a [N,oH,oW,2] map goes with [N,H,W,C] frames")
         if self._fused_stages_ok(x) and out == "u8":
             o = ops.remap_packed(ops.stages_packed(x, self.luts), geo, self.kind, self.max_sigma, out=out)
         else:
@@ -163,6 +171,45 @@ class LerfEngine:
             white[border:H - border, border:W - border] = 255
             ngeo = ops.RemapGeometry((H, W), src, 1)
             mask = ops.remap_hwc_u8(white, None, ngeo, "nearest", 1.0, out="f32") == 255
+        if as_np:
+            return o.cpu().numpy(), (mask.cpu().numpy() if mask is not None else None)
+        return o, mask
+
+    def _remap_batch(self, x, as_np, coords, border, return_mask, out):
+        """remap() of [N,H,W,C] frames: a shared [oH,oW,2] map or one map per frame [N,oH,oW,2]"""
+        torch = _lib.require_gpu()
+        N, H, W, Cn = x.shape
+        if isinstance(coords, ops.RemapGeometry):
+            geo = coords
+            if geo.in_hw != (H, W) or geo.S != self.support:
+                raise ValueError("the RemapGeometry was built for another frame size or support")
+        else:
+            geo = ops.RemapGeometry((H, W), coords.to(x.device) if isinstance(coords, torch.Tensor) else coords, self.support)
+        src = geo.device_coords(x.device)
+        if geo.batched and geo.n_maps != N:
+            raise ValueError("%d frames for %d maps: a [N,oH,oW,2] map holds one map per frame" % (N, geo.n_maps))
+        if self._fused_stages_ok(x) and out == "u8":
+            o = ops.remap_packed(ops.stages_packed(x, self.luts), geo, self.kind, self.max_sigma, out=out)
+        else:
+            if self._fused_stages_ok(x):
+                feat, hq = ops.unpack_stages(ops.stages_packed(x, self.luts), self.luts.oC)
+            else:
+                feat, hq = (torch.stack(t) for t in zip(*[ops.lut_stages(f, self.luts) for f in x]))
+            if geo.batched:
+                o = ops.remap_hwc_u8(feat, hq, geo, self.kind, self.max_sigma, out=out)
+            else:
+                o = torch.stack([ops.remap_hwc_u8(f, h, geo, self.kind, self.max_sigma, out=out) for f, h in zip(feat, hq)])
+        mask = None
+        if return_mask:
+            # the channels of the white frame are equal, so the mask is computed for one and shown for all
+            white = torch.zeros((H, W, 1), dtype=torch.uint8, device=x.device)
+            white[border:H - border, border:W - border] = 255
+            ngeo = ops.RemapGeometry((H, W), src, 1)
+            if geo.batched:
+                m = ops.remap_hwc_u8(white.expand(N, H, W, 1), None, ngeo, "nearest", 1.0, out="f32") == 255
+            else:
+                m = (ops.remap_hwc_u8(white, None, ngeo, "nearest", 1.0, out="f32") == 255).unsqueeze(0).expand(N, -1, -1, -1)
+            mask = m.expand(-1, -1, -1, Cn).contiguous()
         if as_np:
             return o.cpu().numpy(), (mask.cpu().numpy() if mask is not None else None)
         return o, mask

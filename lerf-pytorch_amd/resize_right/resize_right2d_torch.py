@@ -302,9 +302,9 @@ class Lanczos3Warp2dTorch(Warp2dTorch):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Remap twins: the *Warp2dTorch classes with set_shape(in_shape, coords) in place of (in_shape, matrix, out_shape) -- the
-# projected grid comes from a dense coordinate map ([oH, oW, 2] (row, col), unclipped: coords.py; numpy or a device tensor)
-# instead of a matrix (ops.RemapGeometry).  Forward-only by default: an input that requires grad is an error rather than a
-# silently detached result.  enable_backward() (opt-in, like IMDN2's) turns autograd on: `_RemapFn`, HIP backward
+# projected grid comes from a dense coordinate map ([oH, oW, 2] (row, col), unclipped: coords.py; numpy or a device tensor; or
+# [B, oH, oW, 2], one map per sample of the batch, one launch) instead of a matrix (ops.RemapGeometry).  Forward-only by
+# default: an input that requires grad is an error rather than a silently detached result.  enable_backward() (opt-in, like IMDN2's) turns autograd on: `_RemapFn`, HIP backward
 # lerf_remap_bwd -- the image and hyper-parameter gradients of the warp classes and, when the map given to set_shape is a
 # device tensor that requires grad, the gradient with respect to the map (a flow field, a mesh, a lens model fitted by
 # gradient: coords.from_flow_torch keeps a flow in the graph).
@@ -312,7 +312,8 @@ class Lanczos3Warp2dTorch(Warp2dTorch):
 class _RemapFn(torch.autograd.Function):
     """lerf_remap forward (float64 out), lerf_remap_bwd backward.  `cm` is the map given to set_shape when it is a device
     tensor that requires grad (else None): its gradient is the per-plane map gradient summed over the planes, in the map's
-    dtype and shape (autograd carries it through a strided view).  Leaf gradients come back in each leaf's dtype."""
+    dtype and shape (autograd carries it through a strided view) -- for a [B, oH, oW, 2] map, every sample's gradient summed
+    over that sample's planes only.  Leaf gradients come back in each leaf's dtype."""
 
     @staticmethod
     def forward(ctx, geo, kind, max_sigma, cm, x, *hs):
@@ -336,7 +337,9 @@ class _RemapFn(torch.autograd.Function):
         if cdtype is not None and ctx.needs_input_grad[3]:
             gc = torch.zeros((x.shape[0],) + tuple(geo.out_hw) + (2,), dtype=torch.float64, device=x.device)
         ops.remap_bwd_planar(x, hs, geo, kind, max_sigma, grad_out, grads, gc)
-        return (None, None, None, None if gc is None else gc.sum(0).to(cdtype)) + \
+        if gc is not None:                                                 # planes [b * P, (b + 1) * P) read map b
+            gc = (gc.view((geo.n_maps, -1) + tuple(gc.shape[1:])).sum(1) if geo.batched else gc.sum(0)).to(cdtype)
+        return (None, None, None, gc) + \
             tuple(g.to(dt) if g is not None else None for g, dt in zip(grads, dtypes))
 
 
@@ -356,6 +359,8 @@ class Remap2dTorch(Warp2dTorch):
         self.in_shape, self.coords = in_shape, coords
         self.in_sz = [in_shape[2], in_shape[3]]
         self.geo = ops.RemapGeometry(self.in_sz, coords, self.support_sz, pad_mode=self._pad_code)
+        if self.geo.batched and self.geo.n_maps != in_shape[0]:            # [B, oH, oW, 2]: sample b's C planes read map b
+            raise ValueError("a 4-D coordinate map holds one map per sample: its leading size must equal in_shape[0]")
         self.out_sz = list(self.geo.out_hw)
         self.out_shape = in_shape[:2] + self.out_sz
 
@@ -364,6 +369,8 @@ class Remap2dTorch(Warp2dTorch):
         B, Cn, H, W = input.shape
         if [H, W] != list(self.in_sz):
             raise ValueError("input shape does not match set_shape")
+        if self.geo.batched and B != self.geo.n_maps:
+            raise ValueError("input batch does not match the %d maps of set_shape" % self.geo.n_maps)
         x = input.reshape(B * Cn, H, W)
         hs = []
         for h in hypers:
