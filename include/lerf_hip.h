@@ -738,6 +738,35 @@ int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, i
                              const void* b, int b_dtype, int64_t b_row_stride,
                              void* out, int out_dtype, int64_t out_row_stride, int oH, int oW);
 
+/* Inverse of a map: entry (i, j) of out [oH][oW][2] is the position u with F(u) = (i0 + i, j0 + j), where F(u) is the bilinear
+ * interpolant of the map f [fH][fW][2] (fH, fW >= 2) under lerf_coords_compose's per-axis rule (the position clipped onto
+ * [0, fH - 1], i = min(floor(r), fH - 2), t = r - i) -- so lerf_coords_compose(f, out) holds (i0 + i, j0 + j) within tol at every
+ * entry of out that is not NaN.  out is shaped like the frame f points INTO; a tile of a larger inverse written in place (out =
+ * the tile's first entry, the whole map's row stride, its origin) equals those entries of the whole inverse bit for bit.  Each
+ * of f, init, out obeys the strided map contract with its own dtype; a float32 map is promoted exactly on load, the float64
+ * result is rounded once at the store.
+ * Newton's method per entry, at most max_iter passes (each reads ALL FOUR corners of the cell that holds the clipped iterate and
+ * evaluates e = F(u) - target): max(|e.r|, |e.c|) <= tol ends it with the clipped iterate as the result; else the step solves
+ * the patch's 2 x 2 Jacobian by Cramer's rule.  The start is entry (i, j) of init ([oH][oW][2], e.g. a model's analytic inverse or
+ * the previous frame's inverse), or, with init NULL (init_dtype and init_row_stride are then ignored), the affine guess through
+ * f[0][0], f[fH - 1][0] and f[0][fW - 1] (the middle of f when those three are degenerate), which does not depend on the tile.
+ * (NaN, NaN) is written for: a NaN start, a NaN among the four corners read, a Jacobian determinant that is 0 or not finite (a
+ * fold or a constant stretch of f), and an entry that has not met tol after max_iter passes -- the targets f does not reach.
+ * lerf_remap treats such an entry as "no source" (mask false, output 0 / NaN).  No value of f, init or the target forms an
+ * address outside f: the iterate is clipped in floating point before any conversion to int, +-inf in init is clipped like any
+ * iterate.  One thread per entry, one store per entry, no atomics, no allocation; the rounding order of every statement: the
+ * top of csrc/lerf_coords_models.h.  Refused in addition to the family's list: fH or fW < 2, max_iter outside 1..64, a tol that
+ * is negative or not finite, a negative i0 / j0, a non-null init that violates the map contract, out's bytes (first entry to
+ * last) intersecting f's or init's. */
+int lerf_coords_invert(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                       const void* init, int init_dtype, int64_t init_row_stride,
+                       void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                       int max_iter, double tol, void* stream);
+int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                            const void* init, int init_dtype, int64_t init_row_stride,
+                            void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                            int max_iter, double tol);
+
 #ifdef __cplusplus
 }
 #endif

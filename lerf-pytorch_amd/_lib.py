@@ -55,7 +55,7 @@ EXPORTS = [
     "lerf_imdn_saved_bytes", "lerf_imdn_fwd_train_f32", "lerf_imdn_bwd_workspace_bytes", "lerf_imdn_bwd_f32",
     "lerf_rr_axis", "lerf_rr_adjoint_csr", "lerf_patch_batch_u8",
     "lerf_coords_build", "lerf_coords_build_host", "lerf_coords_mesh", "lerf_coords_mesh_host", "lerf_coords_mesh_bwd_workspace_bytes",
-    "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host",
+    "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host", "lerf_coords_invert", "lerf_coords_invert_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -301,6 +301,9 @@ def lib():
     L.lerf_coords_build.argtypes, L.lerf_coords_build_host.argtypes = _build + [C.c_void_p], _build
     L.lerf_coords_mesh.argtypes, L.lerf_coords_mesh_host.argtypes = _mesh + [C.c_void_p], _mesh
     L.lerf_coords_compose.argtypes, L.lerf_coords_compose_host.argtypes = _compose + [C.c_void_p], _compose
+    _invert = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+               C.c_int, C.c_int, C.c_int, C.c_double]
+    L.lerf_coords_invert.argtypes, L.lerf_coords_invert_host.argtypes = _invert + [C.c_void_p], _invert
     L.lerf_coords_mesh_bwd_workspace_bytes.restype = C.c_size_t
     L.lerf_coords_mesh_bwd_workspace_bytes.argtypes = [C.c_int] * 4
     L.lerf_coords_mesh_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -466,6 +469,20 @@ def coords_compose_host(outer, inner, dtype=np.float64, out=None):
     out, so = _np_out(out, b.shape[:2], dtype, "lerf_coords_compose_host")
     check(lib().lerf_coords_compose_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
                                          out.ctypes.data, _np_dt(out), so, b.shape[0], b.shape[1]), "lerf_coords_compose_host")
+    return out
+
+
+def coords_invert_host(f, out_hw, init=None, dtype=np.float64, out=None, origin=(0, 0), max_iter=16, tol=1e-9):
+    """lerf_coords_invert_host: G[i, j] = the u with f(u) = origin + (i, j), f read bilinearly, by Newton's method from init[i, j]
+    (None: the affine guess from three corners of f); NaN where f does not reach.  Host arrays under the strided map contract."""
+    a, sa = _np_map(f, "f")
+    b, sb = (None, 0) if init is None else _np_map(init, "init")
+    out, so = _np_out(out, out_hw, dtype, "lerf_coords_invert_host")
+    if b is not None and tuple(b.shape[:2]) != tuple(out.shape[:2]):
+        raise ValueError("lerf_coords_invert_host: init must have out's shape")
+    check(lib().lerf_coords_invert_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], None if b is None else b.ctypes.data,
+                                        LERF_F64 if b is None else _np_dt(b), sb, out.ctypes.data, _np_dt(out), so, out.shape[0],
+                                        out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol)), "lerf_coords_invert_host")
     return out
 
 

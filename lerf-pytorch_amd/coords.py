@@ -8,7 +8,8 @@ autograd graph (a flow fitted by gradient).
 
 With device=<a torch device> the builders write the map ON the device with the kernels of csrc/lerf_coords.hip (one store per
 entry, no host array, no upload): from_homography, radial, undistort_rectify, from_mesh; from_mesh_torch keeps a control mesh
-in the autograd graph through the mesh upsample's adjoint, and compose chains two maps into one.  The kernels' arithmetic is
+in the autograd graph through the mesh upsample's adjoint, compose chains two maps into one, and invert / invert_flow solve a
+map for its inverse (distort <-> undistort, forward flow -> backward map).  The kernels' arithmetic is
 float64 with + - * / only, bit-equal to its host twin (csrc/lerf_coords_models.h).
 """
 from __future__ import annotations
@@ -275,3 +276,81 @@ def compose(outer, inner, dtype=None):
     a, b = (np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (outer, inner))
     a, b = (t if t.dtype in (np.float32, np.float64) else t.astype(np.float64) for t in (a, b))
     return _lib.coords_compose_host(a, b, b.dtype if dtype is None else _np_dtype(dtype))
+
+
+def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
+    """The inverse of a map: G [H, W, 2] with in_hw = (H, W) the size of the frame `map` points INTO (and so the shape of the
+    inverse); G[i, j] is the position u at which the map, read bilinearly like compose reads its outer map, holds (i, j) -- so
+    compose(map, G) is the identity within tol wherever G is not NaN.  A map that distorts gives the map that undistorts; the map of
+    a forward flow gives the backward map a remap needs.  Newton's method per entry on the device (lerf_coords_invert: one thread per
+    entry, float64), at most max_iter (1..64) passes, stopped when both residuals are <= tol.
+
+    init: a map [H, W, 2] of starting positions -- the analytic inverse of a model (radial(..., -k1) for radial(..., k1)), the
+    previous frame's inverse -- for maps far from affine; None: the affine guess through three corners of the map.  An entry is
+    (NaN, NaN) where the map does not reach (i, j), where it folds (a singular Jacobian), where the cell read holds a NaN, or where
+    max_iter passes did not meet tol; the remap treats a NaN entry as "no source" (mask false).
+
+    numpy in -> numpy out (the kernel's host twin, bit-equal); device tensors in -> a device tensor; mixed map / init is refused.
+    dtype: default the map's.  A batch [B, fH, fW, 2] (init [B, H, W, 2] or None) gives [B, H, W, 2]: one launch per map into the
+    slices of one output tensor -- a single batched launch is not implemented.  No autograd: an operand that requires grad (with
+    grad mode on) is refused."""
+    ops_ = [t for t in (map, init) if t is not None]
+    dev = [bool(getattr(t, "is_cuda", False)) for t in ops_]
+    if any(d != dev[0] for d in dev):
+        raise ValueError("invert: map and init on the host or both on one device, not mixed")
+    if any(getattr(t, "requires_grad", False) for t in ops_):
+        import torch
+        if torch.is_grad_enabled():
+            raise ValueError("invert has no autograd: detach() the maps (or call it under torch.no_grad())")
+    H, W = int(in_hw[0]), int(in_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("in_hw must be positive")
+    nd = getattr(map, "ndim", None)
+    if nd not in (3, 4) or (init is not None and getattr(init, "ndim", None) != nd):
+        raise ValueError("invert: map is [fH, fW, 2] or [B, fH, fW, 2], init (if given) [H, W, 2] or [B, H, W, 2] alike")
+    if nd == 4 and init is not None and init.shape[0] != map.shape[0]:
+        raise ValueError("invert: map and init hold different numbers of maps")
+    if dev[0]:
+        import torch
+        from . import ops
+        tdt = map.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
+        if nd == 3:
+            return ops.coords_invert(map, (H, W), init=init, dtype=tdt, max_iter=max_iter, tol=tol)
+        out = torch.empty((map.shape[0], H, W, 2), dtype=tdt, device=map.device)
+        for n in range(map.shape[0]):
+            ops.coords_invert(map[n], (H, W), init=None if init is None else init[n], out=out[n], max_iter=max_iter, tol=tol)
+        return out
+    from . import _lib
+    a, b = (None if t is None else np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (map, init))
+    a, b = (t if t is None or t.dtype in (np.float32, np.float64) else t.astype(np.float64) for t in (a, b))
+    dt = a.dtype if dtype is None else _np_dtype(dtype)
+    if nd == 3:
+        return _lib.coords_invert_host(a, (H, W), init=b, dtype=dt, max_iter=max_iter, tol=tol)
+    out = np.empty((a.shape[0], H, W, 2), dtype=dt)
+    for n in range(a.shape[0]):
+        _lib.coords_invert_host(a[n], (H, W), init=None if b is None else b[n], out=out[n], max_iter=max_iter, tol=tol)
+    return out
+
+
+def invert_flow(flow, init=None, max_iter=16, tol=1e-9):
+    """The backward flow of a forward flow: flow [H, W, 2] (or a batch [B, H, W, 2]) = (d_row, d_col) of every pixel, numpy or a
+    device tensor -> b = invert(identity + flow, (H, W)) - identity, in the flow's dtype and place, so that the map identity + flow
+    read at identity + b is the identity (within tol); NaN where no pixel of the flow lands.  init, max_iter, tol: invert's (init
+    is a MAP of starting positions, not a flow).  No autograd."""
+    if getattr(flow, "ndim", None) not in (3, 4) or flow.shape[-1] != 2:
+        raise ValueError("flow must be [H, W, 2] or [B, H, W, 2]")
+    H, W = int(flow.shape[-3]), int(flow.shape[-2])
+    if getattr(flow, "is_cuda", False):
+        import torch
+        if flow.requires_grad and torch.is_grad_enabled():
+            raise ValueError("invert has no autograd: detach() the maps (or call it under torch.no_grad())")
+        ident = from_flow_torch(torch.zeros((H, W, 2), dtype=flow.dtype, device=flow.device))
+        return invert(ident + flow.detach(), (H, W), init=init, max_iter=max_iter, tol=tol) - ident
+    if getattr(flow, "requires_grad", False):
+        import torch
+        if torch.is_grad_enabled():
+            raise ValueError("invert has no autograd: detach() the maps (or call it under torch.no_grad())")
+    f = np.asarray(flow.detach().numpy() if hasattr(flow, "detach") else flow)
+    f = f if f.dtype in (np.float32, np.float64) else f.astype(np.float64)
+    ident = from_flow(np.zeros((H, W, 2))).astype(f.dtype)
+    return invert(ident + f, (H, W), init=init, max_iter=max_iter, tol=tol) - ident

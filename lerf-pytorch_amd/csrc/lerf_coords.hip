@@ -1,4 +1,4 @@
-// Coordinate maps built, upsampled and composed on the device: the maps lerf_remap reads (lerf_remap_geo_t.coords), written by
+// Coordinate maps built, upsampled, composed and inverted on the device: the maps lerf_remap reads (lerf_remap_geo_t.coords), written by
 // kernels instead of host numpy + an upload.  The arithmetic of every entry is lerf_coords_models.h (float64, + - * / only, no
 // FMA contraction), shared with the host twins at the end of this file, which run the same functions in a plain loop over host
 // pointers: device and host agree bit for bit.
@@ -10,6 +10,11 @@
 //                                           the same entries, so the loads are broadcasts out of L1 / L2; staging it in LDS would
 //                                           cost every block of 256 entries a 32-KB fill for the 4 to 16 entries a lane needs)
 //   coords_compose_kernel<TA, TB, TO>       one thread per entry: one load of B, up to four of A, one store
+//   coords_invert_kernel<TF, TI, TO>        one thread per entry of the inverse: Newton's method on the piecewise-bilinear F (invert_point),
+//                                           four dependent 16-byte gathers of one cell of F per pass, read through the caches like
+//                                           compose's taps (neighbouring targets walk neighbouring cells); a lane leaves the loop
+//                                           when its residual meets tol, the wave runs as long as its slowest lane; ONE store per
+//                                           entry, after the loop; no LDS, no atomics, float64 throughout
 //   coords_mesh_bwd_{rows,cols}_kernel      the adjoint of the mesh upsample, map = Wr . ctrl . Wc^T  =>  grad_ctrl = Wr^T . grad_map . Wc,
 //                                           in two gather-shaped passes, each sum in a fixed order and without atomics:
 //       rows   tmp[a][j] = sum_i Wr[i][a] grad_map[i][j]: a block owns vertex row a and 64 columns; its 4 waves take the rows of a's
@@ -25,7 +30,9 @@
 //
 // Addresses: every kernel guards (i, j) against the tile, writes entry (i, j) of `out` only, and reads ctrl / A at indices that
 // mesh_axis / compose_axis clamp into the operand after clipping the position in floating point (no value of B reaches an int
-// conversion unclipped).  The passes of the adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].
+// conversion unclipped).  The inverse reads init at entry (i, j) only and F at the three corners of its start and at cells
+// compose_axis picks for the iterate (fH, fW >= 2, so i0 + 1 <= fH - 1), whatever F, init or the iterate hold.  The passes of the
+// adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
 
@@ -75,6 +82,19 @@ coords_compose_kernel(const TA* __restrict__ A, int64_t a_stride, int aH, int aW
     if (i >= oH || j >= oW) return;
     const Point q = load_entry(B, b_stride, i, j);
     store_entry(out, o_stride, i, j, compose_point(q.r, q.c, aH, aW, [&](int r, int c) { return load_entry(A, a_stride, r, c); }));
+}
+
+// init == nullptr: the affine start (three more loads of F, the same entries for every lane: broadcasts)
+template <typename TF, typename TI, typename TO>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_invert_kernel(const TF* __restrict__ F, int64_t f_stride, int fH, int fW, const TI* __restrict__ init, int64_t i_stride,
+                     TO* __restrict__ out, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol) {
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= oH || j >= oW) return;
+    const auto load = [&](int r, int c) { return load_entry(F, f_stride, r, c); };
+    const double q_r = (double)(i0 + i), q_c = (double)(j0 + j);
+    const Point u0 = init ? load_entry(init, i_stride, i, j) : invert_start(q_r, q_c, fH, fW, load);
+    store_entry(out, o_stride, i, j, invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, load));
 }
 
 // pass 1 of the adjoint: grid (ceil(oW / 64), gh), block (64, 4)
@@ -179,6 +199,24 @@ inline int compose_args(const void* a, int a_dtype, int64_t a_stride, int aH, in
     return tile_ok(oH, oW, 0, 0) ? LERF_OK : LERF_EINVAL;
 }
 
+// the bytes a map operand spans: first entry to one past the last
+inline bool maps_overlap(const void* p, int pdt, int64_t ps, int ph, int pw, const void* q, int qdt, int64_t qs, int qh, int qw) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    const uintptr_t ae = a + (uintptr_t)(((int64_t)(ph - 1) * ps + 2 * (int64_t)pw) * (int64_t)(entry_bytes(pdt) / 2));
+    const uintptr_t be = b + (uintptr_t)(((int64_t)(qh - 1) * qs + 2 * (int64_t)qw) * (int64_t)(entry_bytes(qdt) / 2));
+    return a < be && b < ae;
+}
+
+inline int invert_args(const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* init, int init_dtype, int64_t i_stride,
+                       const void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol) {
+    if (!map_ok(f, f_dtype, f_stride, fH, fW) || fH < 2 || fW < 2 || !map_ok(out, out_dtype, o_stride, oH, oW)) return LERF_EINVAL;
+    if (!tile_ok(oH, oW, i0, j0) || max_iter < 1 || max_iter > 64 || !(tol >= 0.0) || !std::isfinite(tol)) return LERF_EINVAL;
+    if (maps_overlap(out, out_dtype, o_stride, oH, oW, f, f_dtype, f_stride, fH, fW)) return LERF_EINVAL;
+    if (init && (!map_ok(init, init_dtype, i_stride, oH, oW) || maps_overlap(out, out_dtype, o_stride, oH, oW, init, init_dtype, i_stride, oH, oW)))
+        return LERF_EINVAL;
+    return LERF_OK;
+}
+
 inline dim3 entry_grid(int oH, int oW) { return dim3((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS); }
 
 }  // namespace coords
@@ -272,6 +310,22 @@ int lerf_coords_compose(const void* a, int a_dtype, int64_t a_row_stride, int aH
     return launch_status();
 }
 
+int lerf_coords_invert(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                       int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_iter,
+                       double tol, void* stream) {
+    const int rc = invert_args(f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW,
+                               i0, j0, max_iter, tol);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
+    hipStream_t st = (hipStream_t)stream;
+    if (!init) init_dtype = LERF_F64;                     // the kernel never reads a null init: one instantiation serves
+    LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(init_dtype, TI, LERF_COORDS_DT(out_dtype, TO,
+        hipLaunchKernelGGL((coords_invert_kernel<TF, TI, TO>), grid, block, 0, st, (const TF*)f, f_row_stride, fH, fW, (const TI*)init,
+                           init_row_stride, (TO*)out, out_row_stride, oH, oW, i0, j0, max_iter, tol))));
+    return launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------ host twins: the same functions, a plain loop
 int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
                            int i0, int j0) {
@@ -312,6 +366,27 @@ int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, i
             Point q, v;
             LERF_COORDS_DT(b_dtype, TB, q = load_entry((const TB*)b, b_row_stride, i, j));
             LERF_COORDS_DT(a_dtype, TA, v = compose_point(q.r, q.c, aH, aW, [&](int r, int c) { return load_entry((const TA*)a, a_row_stride, r, c); }));
+            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, out_row_stride, i, j, v));
+        }
+    return LERF_OK;
+}
+
+int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                            int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                            int max_iter, double tol) {
+    const int rc = invert_args(f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW,
+                               i0, j0, max_iter, tol);
+    if (rc != LERF_OK) return rc;
+    for (int i = 0; i < oH; ++i)
+        for (int j = 0; j < oW; ++j) {
+            const double q_r = (double)(i0 + i), q_c = (double)(j0 + j);
+            Point u0, v;
+            LERF_COORDS_DT(f_dtype, TF, {
+                const auto load = [&](int r, int c) { return load_entry((const TF*)f, f_row_stride, r, c); };
+                if (init) LERF_COORDS_DT(init_dtype, TI, u0 = load_entry((const TI*)init, init_row_stride, i, j));
+                else u0 = invert_start(q_r, q_c, fH, fW, load);
+                v = invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, load);
+            });
             LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, out_row_stride, i, j, v));
         }
     return LERF_OK;

@@ -39,6 +39,29 @@
 //               A is NOT read.  A NaN in either coordinate of B[i][j]: (NaN, NaN), nothing of A is read.  No value of B forms
 //               an address outside A: the position is clipped before any conversion to int, and a tap outside A (n == 1,
 //               or r on the last row) has weight exactly 0.
+//   invert      G[q] = the u with F(u) = q, F [fH][fW][2] (fH, fW >= 2) read as its bilinear interpolant under compose's per-axis rule
+//               (compose_axis: clip onto [0, n - 1], i0 = min(floor(r), n - 2), t = r - i0, weights w0 = 1 - t, w1 = t), by Newton's
+//               method on the piecewise-bilinear patch; q = ((double)(i0 + i), (double)(j0 + j)).
+//               start, when no init map gives it (invert_start; it does not depend on the tile):
+//                 A = F[0][0],  P = F[fH - 1][0],  Q = F[0][fW - 1]
+//                 B = (P - A) / (double)(fH - 1),  C = (Q - A) / (double)(fW - 1)          (per component)
+//                 det = B.r*C.c - B.c*C.r,  d = q - A
+//                 u.r = (d.r*C.c - C.r*d.c) / det,  u.c = (B.r*d.c - B.c*d.r) / det
+//                 det == 0 or not finite (det - det != 0):  u = ((double)(fH - 1) / 2, (double)(fW - 1) / 2)
+//               iteration k = 0 .. max_iter - 1 (invert_point):
+//                 a NaN in u: (NaN, NaN), nothing is read
+//                 R = compose_axis(u.r, fH), Cx = compose_axis(u.c, fW)
+//                 P00 = F[R.i0][Cx.i0], P01 = F[R.i0][Cx.i0 + 1], P10 = F[R.i0 + 1][Cx.i0], P11 = F[R.i0 + 1][Cx.i0 + 1]: ALL FOUR
+//                 are read, whatever their weights (a NaN corner of the cell makes the entry NaN)
+//                 V = R.w0*(Cx.w0*P00 + Cx.w1*P01) + R.w1*(Cx.w0*P10 + Cx.w1*P11)   (per component; compose_point's value of a
+//                                                                                     finite cell, up to the sign of a zero)
+//                 e = V - q;  a NaN in e: (NaN, NaN);  |e.r| <= tol and |e.c| <= tol: the result is the clipped u, (r, c), where
+//                 r = clip_coord(u.r, fH - 1), c = clip_coord(u.c, fW - 1)
+//                 Jr = Cx.w0*(P10 - P00) + Cx.w1*(P11 - P01),  Jc = R.w0*(P01 - P00) + R.w1*(P11 - P10)   (dV/dr, dV/dc)
+//                 det = Jr.r*Jc.c - Jr.c*Jc.r;  det == 0 or not finite: (NaN, NaN)
+//                 u.r = r - (e.r*Jc.c - Jc.r*e.c) / det,  u.c = c - (Jr.r*e.c - Jr.c*e.r) / det
+//               no iteration met tol: (NaN, NaN) -- a target F does not reach.  No value of F, init or q forms an address
+//               outside F: u goes through compose_axis (clipped in floating point before the conversion to int, fH, fW >= 2).
 #pragma once
 
 #include "lerf_host_geometry.h"
@@ -222,6 +245,49 @@ LERF_HD inline Point compose_point(double row, double col, int aH, int aW, READ 
         v.c = v.c + wr[a] * s.c;
     }
     return v;
+}
+
+// ---- invert
+LERF_HD inline bool finite_nonzero(double d) { return d != 0.0 && d - d == 0.0; }      // d - d is NaN for +-inf and NaN
+
+// LOAD(row, col) -> Point: entry of F.  The affine guess of the u with F(u) = q from three corners of F.
+template <typename LOAD>
+LERF_HD inline Point invert_start(double q_r, double q_c, int fH, int fW, LOAD load) {
+#pragma clang fp contract(off)
+    const Point A = load(0, 0), P = load(fH - 1, 0), Q = load(0, fW - 1);
+    const double nr = (double)(fH - 1), nc = (double)(fW - 1);
+    const Point B{(P.r - A.r) / nr, (P.c - A.c) / nr}, Cc{(Q.r - A.r) / nc, (Q.c - A.c) / nc};
+    const double det = B.r * Cc.c - B.c * Cc.r;
+    if (!finite_nonzero(det)) return {nr / 2.0, nc / 2.0};
+    const Point d{q_r - A.r, q_c - A.c};
+    return {(d.r * Cc.c - Cc.r * d.c) / det, (B.r * d.c - B.c * d.r) / det};
+}
+
+// Newton's method on the piecewise-bilinear F from the start u0; max_iter >= 1, fH, fW >= 2.  Every pass reads the four corners
+// of ONE cell of F, at indices compose_axis clamps into F.
+template <typename LOAD>
+LERF_HD inline Point invert_point(double q_r, double q_c, int fH, int fW, Point u0, int max_iter, double tol, LOAD load) {
+#pragma clang fp contract(off)
+    const Point nan2{__builtin_nan(""), __builtin_nan("")};
+    Point u = u0;
+    for (int k = 0; k < max_iter; ++k) {
+        if (u.r != u.r || u.c != u.c) return nan2;
+        const ComposeAxis R = compose_axis(u.r, fH), Cx = compose_axis(u.c, fW);
+        const Point P00 = load(R.i0, Cx.i0), P01 = load(R.i0, Cx.i0 + 1), P10 = load(R.i0 + 1, Cx.i0), P11 = load(R.i0 + 1, Cx.i0 + 1);
+        const Point V{R.w0 * (Cx.w0 * P00.r + Cx.w1 * P01.r) + R.w1 * (Cx.w0 * P10.r + Cx.w1 * P11.r),
+                      R.w0 * (Cx.w0 * P00.c + Cx.w1 * P01.c) + R.w1 * (Cx.w0 * P10.c + Cx.w1 * P11.c)};
+        const Point e{V.r - q_r, V.c - q_c};
+        if (e.r != e.r || e.c != e.c) return nan2;
+        const double r = clip_coord(u.r, fH - 1), c = clip_coord(u.c, fW - 1);
+        if (fabs(e.r) <= tol && fabs(e.c) <= tol) return {r, c};
+        const Point Jr{Cx.w0 * (P10.r - P00.r) + Cx.w1 * (P11.r - P01.r), Cx.w0 * (P10.c - P00.c) + Cx.w1 * (P11.c - P01.c)};
+        const Point Jc{R.w0 * (P01.r - P00.r) + R.w1 * (P11.r - P10.r), R.w0 * (P01.c - P00.c) + R.w1 * (P11.c - P10.c)};
+        const double det = Jr.r * Jc.c - Jr.c * Jc.r;
+        if (!finite_nonzero(det)) return nan2;
+        u.r = r - (e.r * Jc.c - Jc.r * e.c) / det;
+        u.c = c - (Jr.r * e.c - Jr.c * e.r) / det;
+    }
+    return nan2;
 }
 
 }  // namespace coords

@@ -1161,3 +1161,28 @@ def coords_compose(outer, inner, dtype=None, out=None):
                                                   out.data_ptr(), _lib._dt(out), so, b.shape[0], b.shape[1],
                                                   _lib.current_stream(b.device)), "lerf_coords_compose")
     return out
+
+
+def coords_invert(f, out_hw, init=None, dtype=None, out=None, origin=(0, 0), max_iter=16, tol=1e-9):
+    """lerf_coords_invert: G[i, j] = the position u with f(u) = origin + (i, j), f [fH, fW, 2] read as its bilinear interpolant
+    (compose's rule), by Newton's method per entry from init[i, j] (None: the affine guess from three corners of f), at most
+    max_iter passes, stopped at max |f(u) - target| <= tol; (NaN, NaN) where f does not reach, folds, or holds a NaN in the cell
+    read.  out_hw: the size of the frame f points into.  Device maps under the strided contract (tile views of f, init and out
+    with `origin` = the tile's place in the whole inverse), any mix of float32 / float64; dtype: G's, default f's.  One launch on
+    the current stream, no sync."""
+    a, sa = _map_tensor(f, "f")
+    a = a.detach()
+    b, sb = (None, 0) if init is None else _map_tensor(init, "init")
+    out, so = _map_out(out, out_hw, a.dtype if dtype is None else dtype, a.device, "lerf_coords_invert")
+    if out.device != a.device or (b is not None and b.device != a.device):
+        raise ValueError("lerf_coords_invert: f, init and out live on different devices")
+    if b is not None:
+        b = b.detach()
+        if tuple(b.shape[:2]) != tuple(out.shape[:2]):
+            raise ValueError("lerf_coords_invert: init must have out's shape")
+    with _lib.on_device(a):
+        _lib.check(_lib.lib().lerf_coords_invert(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], None if b is None else b.data_ptr(),
+                                                 _lib.LERF_F64 if b is None else _lib._dt(b), sb, out.data_ptr(), _lib._dt(out), so,
+                                                 out.shape[0], out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol),
+                                                 _lib.current_stream(a.device)), "lerf_coords_invert")
+    return out

@@ -4,11 +4,18 @@
             of coords.py plus torch.from_numpy(...).to(device) (wall clock, median of --host-repeats)
   mesh      a 33 x 61 control mesh upsampled (bilinear, bicubic) and the adjoint of each (lerf_coords_mesh_bwd)
   compose   an outer 2160 x 3840 map sampled at an inner 2160 x 3840 map
+  invert    a 2160 x 3840 radial map (over a 2160 x 3840 source) inverted into a 2160 x 3840 inverse (lerf_coords_invert), as a
+            float64 and as a float32 map, from the affine start; beside it, in the same run, compose of the map with its inverse
+            (the same sizes) and the host twin (wall clock); the mean and the largest number of Newton passes
 
 Device times: device events around `--iters` calls after `--warmup` calls, median of `--repeats` windows (tools/bench_remap.py's
 scheme).  With each device time go the bytes the call must move at least once and the share of the HBM peak they imply:
 16 B per entry written; the adjoint reads the map gradient once per tap row (2 or 4 times); compose reads 16 B of the inner map,
-writes 16 B and reads the outer map once (its taps are neighbours' taps).  Prints ONE JSON line; no speed gate -- the in-run
+writes 16 B and reads the outer map once (its taps are neighbours' taps); invert writes 16 B (8 B) per entry and reads the map
+once.  One pass of invert moves what compose moves -- four dependent 16-byte gathers -- so invert's time over compose's should sit
+near the mean number of passes; the passes are counted without touching the kernel: an entry that needs p passes is NaN with
+max_iter < p, so the count of non-NaN entries at max_iter = 1, 2, ... gives the histogram (entries still NaN at --max-iter ran all
+of them).  Prints ONE JSON line; no speed gate -- the in-run
 check is that every device map equals its host form bit for bit.
 
     python tools/bench_coords.py [--iters 20] [--warmup 5] [--repeats 7] [--host-repeats 3]
@@ -65,6 +72,8 @@ def main():
     ap.add_argument("--in-hw", type=int, nargs=2, default=[1080, 1920])
     ap.add_argument("--out-hw", type=int, nargs=2, default=[2160, 3840])
     ap.add_argument("--mesh-hw", type=int, nargs=2, default=[33, 61])
+    ap.add_argument("--max-iter", type=int, default=16)
+    ap.add_argument("--tol", type=float, default=1e-9)
     a = ap.parse_args()
     import torch
     from lerf_pytorch_amd import _lib, coords, ops
@@ -124,6 +133,35 @@ def main():
     inner = coords.from_homography(np.array([[1.01, 0.004, 3.0], [-0.003, 0.99, 5.0], [1e-6, -1e-6, 1.0]]), hw, device=dev)
     t = device_ms(lambda: ops.coords_compose(outer, inner, out=out), a.iters, a.warmup, a.repeats)
     res["compose"] = row(t, 3 * 16 * entries)
+
+    # invert: F = a radial map over a source of the inverse's size, so most targets are reached; compose(F, G) beside it
+    F = coords.radial(hw, hw, 0.08, -0.02, device=dev)
+    inv = {"max_iter": a.max_iter, "tol": a.tol}
+    G = None
+    for name, Fm in (("float64", F), ("float32", F.float())):
+        o = torch.empty(hw + (2,), dtype=Fm.dtype, device=dev)
+        t = device_ms(lambda: ops.coords_invert(Fm, hw, out=o, max_iter=a.max_iter, tol=a.tol), a.iters, a.warmup, a.repeats)
+        eb = 16 if name == "float64" else 8
+        inv[name] = row(t, 2 * eb * entries)
+        done = [int((~torch.isnan(ops.coords_invert(Fm, hw, out=o, max_iter=k, tol=a.tol)[..., 0])).sum()) for k in range(1, a.max_iter + 1)]
+        hist = [done[0]] + [done[k] - done[k - 1] for k in range(1, len(done))]
+        passes = sum((k + 1) * n for k, n in enumerate(hist)) + a.max_iter * (entries - done[-1])
+        inv[name].update(reached_fraction=round(done[-1] / entries, 4), mean_passes=round(passes / entries, 3),
+                         mean_passes_reached=round(sum((k + 1) * n for k, n in enumerate(hist)) / max(done[-1], 1), 3),
+                         max_passes_reached=max(k + 1 for k, n in enumerate(hist) if n) if done[-1] else 0)
+        if name == "float64":
+            G = o.clone()
+    t = device_ms(lambda: ops.coords_compose(F, G, out=out), a.iters, a.warmup, a.repeats)
+    inv["compose_same_size"] = row(t, 3 * 16 * entries)
+    inv["float64"]["ratio_to_compose"] = round(inv["float64"]["ms"] / inv["compose_same_size"]["ms"], 2)
+    inv["float32"]["ratio_to_compose"] = round(inv["float32"]["ms"] / inv["compose_same_size"]["ms"], 2)
+    F_np = F.cpu().numpy()
+    h_ms, h_map = host_ms(lambda: torch.from_numpy(_lib.coords_invert_host(F_np, hw, max_iter=a.max_iter, tol=a.tol)).to(dev), 1)
+    same = bool(torch.equal(torch.nan_to_num(G, nan=-1.0), torch.nan_to_num(h_map, nan=-1.0)))
+    equal = equal and same
+    inv["host_twin_plus_upload_ms"] = round(h_ms, 1)
+    inv["equals_host"] = same
+    res["invert"] = inv
     res["device_equals_host"] = equal
     print(json.dumps(res))
     if not equal:
