@@ -4,6 +4,7 @@
 #include <math.h>
 #include <string.h>
 
+#include "lerf_dispatch.h"
 #include "lerf_kernels.h"
 #include "lerf_remap_point.h"
 
@@ -20,6 +21,32 @@ inline hipStream_t as_stream(void* s) {
 inline int check_launch() { return launch_status(); }
 
 inline bool plane_ok(const lerf_plane_t* p) { return p && p->ptr; }
+
+// hyper-parameter maps of a kind: gauss 3, linear 1, the fixed kernels none
+inline int hyper_count(int kind) { return kind == LERF_KIND_GAUSS ? 3 : (kind == LERF_KIND_LINEAR ? 1 : 0); }
+
+// the nh maps a kind reads are there and share dtype and strides (the kernels take one stride triple for all three)
+inline bool hyper_planes_ok(const lerf_plane_t* hyper, int nh) {
+    if (nh > 0 && !hyper) return false;
+    for (int k = 0; k < nh; ++k)
+        if (!hyper[k].ptr || hyper[k].dtype != hyper[0].dtype || hyper[k].sy != hyper[0].sy ||
+            hyper[k].sx != hyper[0].sx || hyper[k].sc != hyper[0].sc)
+            return false;
+    return true;
+}
+
+// the operands of lerf_warp / lerf_remap as the launches take them (a.geo is the caller's); a kind without hyper-parameter maps gets
+// the image in their place: its kernels never read them
+void warp_operands(WarpArgs& a, const lerf_plane_t* feat, const lerf_plane_t* hyper, int nh, int H, int W, int C, int kind, double max_sigma,
+                   const lerf_mplane_t* out) {
+    a.feat = feat->ptr; a.in_dtype = feat->dtype; a.fy = feat->sy; a.fx = feat->sx; a.fc = feat->sc;
+    for (int k = 0; k < 3; ++k) a.h[k] = nh > 0 ? (k < nh ? hyper[k].ptr : hyper[0].ptr) : feat->ptr;
+    a.h_dtype = nh > 0 ? hyper[0].dtype : feat->dtype;
+    a.hy = nh > 0 ? hyper[0].sy : 0; a.hx = nh > 0 ? hyper[0].sx : 0; a.hc = nh > 0 ? hyper[0].sc : 0;
+    a.H = H; a.W = W; a.C = C;
+    a.kind = kind; a.max_sigma = max_sigma;
+    a.out = out->ptr; a.out_dtype = out->dtype; a.oy = out->sy; a.ox = out->sx; a.oc = out->sc;
+}
 
 int build_stage_luts(const lerf_luts_t* L, int stage, StageLuts* out) {
     int n = stage == 1 ? L->n_modes1 : L->n_modes2;
@@ -157,12 +184,8 @@ int lerf_resize(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, in
                 int kind, double max_sigma, const lerf_mplane_t* out, void* stream) {
     if (!plane_ok(feat) || !geo || !out || !out->ptr || H < 1 || W < 1 || C < 1) return LERF_EINVAL;
     if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
-    int nh = kind == LERF_KIND_GAUSS ? 3 : (kind == LERF_KIND_LINEAR ? 1 : 0);   // fixed kernels take no hyper maps
-    if (nh > 0 && !hyper) return LERF_EINVAL;
-    for (int k = 0; k < nh; ++k)
-        if (!hyper[k].ptr || hyper[k].dtype != hyper[0].dtype || hyper[k].sy != hyper[0].sy ||
-            hyper[k].sx != hyper[0].sx || hyper[k].sc != hyper[0].sc)
-            return LERF_EINVAL;
+    const int nh = hyper_count(kind);
+    if (!hyper_planes_ok(hyper, nh)) return LERF_EINVAL;
     if (!geo->left_r || !geo->left_c || geo->out_h < 1 || geo->out_w < 1) return LERF_EINVAL;
     ResizeArgs a{};
     a.feat = feat->ptr; a.in_dtype = feat->dtype; a.fy = feat->sy; a.fx = feat->sx; a.fc = feat->sc;
@@ -182,26 +205,13 @@ int lerf_resize(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, in
 int lerf_warp(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_warp_geo_t* geo,
               int kind, double max_sigma, const lerf_mplane_t* out, void* stream) {
     if (!plane_ok(feat) || !geo || !out || !out->ptr || H < 1 || W < 1 || C < 1) return LERF_EINVAL;
-    int nh = kind == LERF_KIND_GAUSS ? 3 : (kind == LERF_KIND_LINEAR ? 1 : 0);
+    const int nh = hyper_count(kind);
     if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
-    if (nh > 0 && !hyper) return LERF_EINVAL;
-    for (int k = 0; k < nh; ++k)
-        if (!hyper[k].ptr || hyper[k].dtype != hyper[0].dtype || hyper[k].sy != hyper[0].sy ||
-            hyper[k].sx != hyper[0].sx || hyper[k].sc != hyper[0].sc)
-            return LERF_EINVAL;
+    if (!hyper_planes_ok(hyper, nh)) return LERF_EINVAL;
     if (geo->out_h < 1 || geo->out_w < 1) return LERF_EINVAL;
     WarpArgs a{};
-    a.feat = feat->ptr; a.in_dtype = feat->dtype; a.fy = feat->sy; a.fx = feat->sx; a.fc = feat->sc;
-    for (int k = 0; k < 3; ++k) a.h[k] = nh > 0 ? (k < nh ? hyper[k].ptr : hyper[0].ptr) : feat->ptr;
-    a.h_dtype = nh > 0 ? hyper[0].dtype : feat->dtype;
-    a.hy = nh > 0 ? hyper[0].sy : 0; a.hx = nh > 0 ? hyper[0].sx : 0; a.hc = nh > 0 ? hyper[0].sc : 0;
-    a.H = H; a.W = W; a.C = C;
-    a.geo.S = geo->S; a.geo.oH = geo->out_h; a.geo.oW = geo->out_w;
-    memcpy(a.geo.minv, geo->minv, sizeof(a.geo.minv));
-    a.geo.pad_r_lo = geo->pad_r_lo; a.geo.pad_r_hi = geo->pad_r_hi;
-    a.geo.pad_c_lo = geo->pad_c_lo; a.geo.pad_c_hi = geo->pad_c_hi;
-    a.geo.pad_mode = geo->pad_mode;
-    a.geo.oy0 = geo->out_y0; a.geo.ox0 = geo->out_x0;
+    warp_operands(a, feat, hyper, nh, H, W, C, kind, max_sigma, out);
+    a.geo = to_warp_geo(*geo);
     if (geo->out_y0 < 0 || geo->out_x0 < 0 || geo->src_y0 < 0 || geo->src_y0 >= H) return LERF_EINVAL;
     if (geo->src_y0 > 0) {
         // the operands start at source row src_y0: addressed with the frame's row numbers through pointers moved back by that many rows
@@ -215,8 +225,6 @@ int lerf_warp(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int 
     }
     if (geo->pad_mode < LERF_PAD_CONSTANT || geo->pad_mode > LERF_PAD_WRAP) return LERF_EINVAL;
     if (geo->pad_mode != LERF_PAD_CONSTANT && out->dtype == LERF_U8) return LERF_EUNSUPPORTED;
-    a.kind = kind; a.max_sigma = max_sigma;
-    a.out = out->ptr; a.out_dtype = out->dtype; a.oy = out->sy; a.ox = out->sx; a.oc = out->sc;
     int rc = launch_warp(a, as_stream(stream));
     return rc != LERF_OK ? rc : check_launch();
 }
@@ -272,11 +280,7 @@ int lerf_warp_tile_boxes(const lerf_warp_geo_t* geo, int H, int W, int32_t* boxe
 
 static void warp_fused_args(FusedArgs& f, WarpGeo& wg, int n, int H, int W, int C, const lerf_luts_t* luts, const lerf_warp_geo_t* geo, int kind,
                             double max_sigma) {
-    wg.S = geo->S; wg.oH = geo->out_h; wg.oW = geo->out_w;
-    memcpy(wg.minv, geo->minv, sizeof(wg.minv));
-    wg.pad_r_lo = geo->pad_r_lo; wg.pad_r_hi = geo->pad_r_hi; wg.pad_c_lo = geo->pad_c_lo; wg.pad_c_hi = geo->pad_c_hi;
-    wg.pad_mode = geo->pad_mode;
-    wg.oy0 = geo->out_y0; wg.ox0 = geo->out_x0;
+    wg = to_warp_geo(*geo);
     f.n = n; f.H = H; f.W = W; f.C = C; f.luts = luts; f.S = geo->S; f.oH = geo->out_h; f.oW = geo->out_w;
     f.kind = kind; f.max_sigma = (float)max_sigma; f.wgeo = &wg;
 }
@@ -314,13 +318,8 @@ int lerf_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, in
                      double max_sigma, const lerf_mplane_t* out, int64_t out_sn, void* stream) {
     if (!packed || !geo || !out || !out->ptr || n < 1 || H < 1 || W < 1 || C < 1 || geo->out_h < 1 || geo->out_w < 1)
         return LERF_EINVAL;
-    WarpGeo g;
-    g.S = geo->S; g.oH = geo->out_h; g.oW = geo->out_w;
-    memcpy(g.minv, geo->minv, sizeof(g.minv));
-    g.pad_r_lo = geo->pad_r_lo; g.pad_r_hi = geo->pad_r_hi; g.pad_c_lo = geo->pad_c_lo; g.pad_c_hi = geo->pad_c_hi;
-    g.pad_mode = LERF_PAD_CONSTANT;
-    g.oy0 = geo->out_y0; g.ox0 = geo->out_x0;
     if (geo->pad_mode != LERF_PAD_CONSTANT) return LERF_EUNSUPPORTED;
+    const WarpGeo g = to_warp_geo(*geo);
     if (geo->out_y0 < 0 || geo->out_x0 < 0 || geo->src_y0 < 0 || geo->src_y0 >= H) return LERF_EINVAL;
     packed -= (int64_t)geo->src_y0 * W * C;                    // rows of the frame from src_y0 on (lerf_warp_geo_t)
     int rc = launch_warp_packed(packed, packed_sn, n, H, W, C, g, kind, (float)max_sigma, out->ptr, out->dtype, out->sy, out->sx,
@@ -333,25 +332,15 @@ static int remap_planes(const lerf_plane_t* feat, const lerf_plane_t hyper[3], i
                         int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const lerf_mplane_t* out,
                         void* stream) {
     if (!plane_ok(feat) || !geo || !out || !out->ptr || H < 1 || W < 1 || C < 1) return LERF_EINVAL;
-    int nh = kind == LERF_KIND_GAUSS ? 3 : (kind == LERF_KIND_LINEAR ? 1 : 0);
+    const int nh = hyper_count(kind);
     if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
-    if (nh > 0 && !hyper) return LERF_EINVAL;
-    for (int k = 0; k < nh; ++k)
-        if (!hyper[k].ptr || hyper[k].dtype != hyper[0].dtype || hyper[k].sy != hyper[0].sy ||
-            hyper[k].sx != hyper[0].sx || hyper[k].sc != hyper[0].sc)
-            return LERF_EINVAL;
+    if (!hyper_planes_ok(hyper, nh)) return LERF_EINVAL;
     RemapGeo m{};
     int rc = remap_geo_batched(geo, n_maps, map_stride, C, planes_per_map, m);
     if (rc != LERF_OK) return rc;
     if (geo->pad_mode != LERF_PAD_CONSTANT && out->dtype == LERF_U8) return LERF_EUNSUPPORTED;
     WarpArgs a{};
-    a.feat = feat->ptr; a.in_dtype = feat->dtype; a.fy = feat->sy; a.fx = feat->sx; a.fc = feat->sc;
-    for (int k = 0; k < 3; ++k) a.h[k] = nh > 0 ? (k < nh ? hyper[k].ptr : hyper[0].ptr) : feat->ptr;
-    a.h_dtype = nh > 0 ? hyper[0].dtype : feat->dtype;
-    a.hy = nh > 0 ? hyper[0].sy : 0; a.hx = nh > 0 ? hyper[0].sx : 0; a.hc = nh > 0 ? hyper[0].sc : 0;
-    a.H = H; a.W = W; a.C = C;
-    a.kind = kind; a.max_sigma = max_sigma;
-    a.out = out->ptr; a.out_dtype = out->dtype; a.oy = out->sy; a.ox = out->sx; a.oc = out->sc;
+    warp_operands(a, feat, hyper, nh, H, W, C, kind, max_sigma, out);
     rc = launch_remap(a, m, as_stream(stream));
     return rc != LERF_OK ? rc : check_launch();
 }

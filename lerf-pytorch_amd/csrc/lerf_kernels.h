@@ -142,6 +142,18 @@ int launch_imdn_bwd(const float* weights, int nf, int in_nc, int out_nc, const f
 // lerf_ubench.hip
 int launch_ubench_lds_gather(int pattern, int iters, int blocks, uint32_t* sink, hipStream_t st);
 
+// Argument checks the three stage-3 backward entry points share (lerf_resize_bwd_f32, lerf_warp_bwd, lerf_remap_bwd*).  Two pieces,
+// because each entry point validates its own geometry between them.
+inline bool bwd_operands_ok(const void* feat, const void* geo, const void* grad_out, int N, int H, int W) {
+    return feat && geo && grad_out && N >= 1 && H >= 1 && W >= 1;
+}
+inline int bwd_kind_check(int kind, const float* h0, const float* h1, const float* h2) {
+    if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
+    if ((kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) && !h0) return LERF_EINVAL;
+    if (kind == LERF_KIND_GAUSS && (!h1 || !h2)) return LERF_EINVAL;
+    return LERF_OK;
+}
+
 int launch_unpack_stages(const uint32_t* packed, int64_t n_pxch, int oC, uint8_t* feat, uint8_t* hq, hipStream_t st);
 int launch_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, int W, int C, const WarpGeo& geo, int kind,
                        float max_sigma, void* out, int out_dtype, int64_t oy, int64_t ox, int64_t oc, int64_t out_sn, hipStream_t st);

@@ -12,6 +12,7 @@
 // CHW tensors, arbitrary modes / support sizes).  The tile-fused uint8 path
 // lives in lerf_fused.hip.
 #include "lerf_kernels.h"
+#include "lerf_dispatch.h"
 #include "lerf_stage3.h"
 #include "lerf_warp_px.h"
 #include "lerf_taps.h"
@@ -429,24 +430,23 @@ static int resize_dispatch_S(const ResizeArgs& a, hipStream_t st) {
     const A* dr = sizeof(A) == 4 ? (const A*)a.dis_r : (const A*)a.dis_r64;
     const A* dc = sizeof(A) == 4 ? (const A*)a.dis_c : (const A*)a.dis_c64;
     if (!dr || !dc) return LERF_EINVAL;
-#define LERF_RS(ST)                                                                                         \
-    hipLaunchKernelGGL((resize_kernel<TI, TH, TO, A, KIND, ST>), grid, block, 0, st, (const TI*)a.feat,     \
-                       a.fy, a.fx, a.fc, (const TH*)a.h[0], (const TH*)a.h[1], (const TH*)a.h[2], a.hy,     \
-                       a.hx, a.hc, a.H, a.W, a.C, a.S, a.oH, a.oW, a.left_r, dr, a.left_c, dc,              \
-                       (a.dis_r64 && a.dis_c64) ? a.dis_r64 : nullptr, (a.dis_r64 && a.dis_c64) ? a.dis_c64 : nullptr, \
-                       (A)a.max_sigma, (TO*)a.out, a.oy, a.ox, a.oc, a.pad_mode)
-    if (a.S == 2) LERF_RS(2);
-    else if (a.S == 4) LERF_RS(4);
-    else LERF_RS(0);
-#undef LERF_RS
+    const bool guard = a.dis_r64 && a.dis_c64;
+    auto launch = [&](auto ST) {                             // the support as a template argument: 2, 4, or 0 = read a.S
+        hipLaunchKernelGGL((resize_kernel<TI, TH, TO, A, KIND, decltype(ST)::value>), grid, block, 0, st, (const TI*)a.feat,
+                           a.fy, a.fx, a.fc, (const TH*)a.h[0], (const TH*)a.h[1], (const TH*)a.h[2], a.hy,
+                           a.hx, a.hc, a.H, a.W, a.C, a.S, a.oH, a.oW, a.left_r, dr, a.left_c, dc,
+                           guard ? a.dis_r64 : nullptr, guard ? a.dis_c64 : nullptr,
+                           (A)a.max_sigma, (TO*)a.out, a.oy, a.ox, a.oc, a.pad_mode);
+    };
+    if (a.S == 2) launch(std::integral_constant<int, 2>{});
+    else if (a.S == 4) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, 0>{});
     return LERF_OK;
 }
 
 template <typename TI, typename TH, typename TO, typename A>
 static int resize_dispatch_kind(const ResizeArgs& a, hipStream_t st) {
-    if (a.kind == LERF_KIND_GAUSS) return resize_dispatch_S<TI, TH, TO, A, LERF_KIND_GAUSS>(a, st);
-    if (a.kind == LERF_KIND_LINEAR) return resize_dispatch_S<TI, TH, TO, A, LERF_KIND_LINEAR>(a, st);
-    return LERF_EUNSUPPORTED;
+    return with_hyper_kind(a.kind, [&](auto K) { return resize_dispatch_S<TI, TH, TO, A, decltype(K)::value>(a, st); });
 }
 
 static int launch_resize_fixed(const ResizeArgs& a, hipStream_t st);
@@ -551,37 +551,20 @@ warp_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
                                    out + i * oy + j * ox + c * oc);
 }
 
-template <typename TI, typename TH, typename TO, typename A>
-static int warp_dispatch_kind(const WarpArgs& a, hipStream_t st) {
-    dim3 block(256), grid((a.geo.oW * a.C + 255) / 256, a.geo.oH);
-#define LERF_WP(KIND)                                                                                        \
-    hipLaunchKernelGGL((warp_kernel<TI, TH, TO, A, KIND>), grid, block, 0, st, (const TI*)a.feat, a.fy,      \
-                       a.fx, a.fc, (const TH*)a.h[0], (const TH*)a.h[1], (const TH*)a.h[2], a.hy, a.hx,      \
-                       a.hc, a.H, a.W, a.C, a.geo, (A)a.max_sigma, (TO*)a.out, a.oy, a.ox, a.oc)
-    if (a.kind == LERF_KIND_GAUSS) LERF_WP(LERF_KIND_GAUSS);
-    else if (a.kind == LERF_KIND_LINEAR) LERF_WP(LERF_KIND_LINEAR);
-    else if (a.kind == LERF_KIND_NEAREST) LERF_WP(LERF_KIND_NEAREST);
-    else if (a.kind == LERF_KIND_CUBIC) LERF_WP(LERF_KIND_CUBIC);
-    else if (a.kind == LERF_KIND_BILINEAR) LERF_WP(LERF_KIND_BILINEAR);
-    else if (a.kind == LERF_KIND_LANCZOS2) LERF_WP(LERF_KIND_LANCZOS2);
-    else if (a.kind == LERF_KIND_LANCZOS3) LERF_WP(LERF_KIND_LANCZOS3);
-    else return LERF_EUNSUPPORTED;
-#undef LERF_WP
-    return LERF_OK;
-}
-
 int launch_warp(const WarpArgs& a, hipStream_t st) {
     if (a.geo.S < 1 || a.geo.S > LERF_MAX_SUPPORT) return LERF_EUNSUPPORTED;
+    dim3 block(256), grid((a.geo.oW * a.C + 255) / 256, a.geo.oH);
     const bool fixed = a.kind >= LERF_KIND_NEAREST;     // no hyper-parameter maps
-    if (a.in_dtype == LERF_U8 && (a.h_dtype == LERF_U8 || fixed)) {
-        if (a.out_dtype == LERF_U8) return warp_dispatch_kind<uint8_t, uint8_t, uint8_t, float>(a, st);
-        if (a.out_dtype == LERF_F32) return warp_dispatch_kind<uint8_t, uint8_t, float, double>(a, st);     // float64 arithmetic, rounded once
-        if (a.out_dtype == LERF_F64) return warp_dispatch_kind<uint8_t, uint8_t, double, double>(a, st);
-    } else if (a.in_dtype == LERF_F32 && (a.h_dtype == LERF_F32 || fixed)) {
-        if (a.out_dtype == LERF_F32) return warp_dispatch_kind<float, float, float, double>(a, st);
-        if (a.out_dtype == LERF_F64) return warp_dispatch_kind<float, float, double, double>(a, st);
-    }
-    return LERF_EUNSUPPORTED;
+    return with_stage3_types(a.in_dtype, a.h_dtype, a.out_dtype, fixed, [&](auto T) {
+        using TI = typename decltype(T)::TI; using TH = typename decltype(T)::TH;
+        using TO = typename decltype(T)::TO; using A = typename decltype(T)::A;
+        return with_kind(a.kind, [&](auto K) {
+            hipLaunchKernelGGL((warp_kernel<TI, TH, TO, A, decltype(K)::value>), grid, block, 0, st, (const TI*)a.feat, a.fy,
+                               a.fx, a.fc, (const TH*)a.h[0], (const TH*)a.h[1], (const TH*)a.h[2], a.hy, a.hx,
+                               a.hc, a.H, a.W, a.C, a.geo, (A)a.max_sigma, (TO*)a.out, a.oy, a.ox, a.oc);
+            return LERF_OK;
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -648,39 +631,31 @@ int launch_warp_packed(const uint32_t* packed, int64_t packed_sn, int n, int H, 
     if (C == 3 && geo.S == 2 && (kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) &&
         (out_dtype == LERF_U8 || out_dtype == LERF_F32)) {
         dim3 blockp(256), gridp((unsigned)(((geo.oW + 255) / 256) * geo.oH), 1, 1);
-#define LERF_WPX(TO, KIND, PROD)                                                                                      \
-    hipLaunchKernelGGL((warp_packed_px_kernel<TO, KIND, PROD>), gridp, blockp, 0, st, packed, packed_sn, n, H, W, geo, max_sigma, (TO*)out, \
-                       oy, ox, oc, out_sn)
         const bool prod = out_dtype == LERF_U8 && max_sigma <= s3::kNoShiftMaxSigma;     // production arithmetic + tie guard
-        if (kind == LERF_KIND_GAUSS) {
-            if (prod) LERF_WPX(uint8_t, LERF_KIND_GAUSS, true);
-            else if (out_dtype == LERF_U8) LERF_WPX(uint8_t, LERF_KIND_GAUSS, false);
-            else LERF_WPX(float, LERF_KIND_GAUSS, false);
-        } else {
-            if (prod) LERF_WPX(uint8_t, LERF_KIND_LINEAR, true);
-            else if (out_dtype == LERF_U8) LERF_WPX(uint8_t, LERF_KIND_LINEAR, false);
-            else LERF_WPX(float, LERF_KIND_LINEAR, false);
-        }
-#undef LERF_WPX
-        return LERF_OK;
+        return with_hyper_kind(kind, [&](auto K) {
+            auto launch = [&](auto* o, auto PROD) {
+                using TO = std::remove_pointer_t<decltype(o)>;
+                hipLaunchKernelGGL((warp_packed_px_kernel<TO, decltype(K)::value, decltype(PROD)::value>), gridp, blockp, 0, st, packed,
+                                   packed_sn, n, H, W, geo, max_sigma, o, oy, ox, oc, out_sn);
+            };
+            if (prod) launch((uint8_t*)out, std::true_type{});
+            else if (out_dtype == LERF_U8) launch((uint8_t*)out, std::false_type{});
+            else launch((float*)out, std::false_type{});
+            return LERF_OK;
+        });
     }
+    if (out_dtype != LERF_U8 && out_dtype != LERF_F32) return LERF_EUNSUPPORTED;
     dim3 block(256), grid((geo.oW * C + 255) / 256, geo.oH, n);
-#define LERF_WPK(TO, KIND)                                                                                         \
-    hipLaunchKernelGGL((warp_packed_kernel<TO, KIND>), grid, block, 0, st, packed, packed_sn, H, W, C, geo, max_sigma, (TO*)out, \
-                       oy, ox, oc, out_sn)
-    if (kind == LERF_KIND_GAUSS) {
-        if (out_dtype == LERF_U8) LERF_WPK(uint8_t, LERF_KIND_GAUSS);
-        else if (out_dtype == LERF_F32) LERF_WPK(float, LERF_KIND_GAUSS);
-        else return LERF_EUNSUPPORTED;
-    } else if (kind == LERF_KIND_LINEAR) {
-        if (out_dtype == LERF_U8) LERF_WPK(uint8_t, LERF_KIND_LINEAR);
-        else if (out_dtype == LERF_F32) LERF_WPK(float, LERF_KIND_LINEAR);
-        else return LERF_EUNSUPPORTED;
-    } else {
-        return LERF_EUNSUPPORTED;
-    }
-#undef LERF_WPK
-    return LERF_OK;
+    return with_hyper_kind(kind, [&](auto K) {
+        auto launch = [&](auto* o) {
+            using TO = std::remove_pointer_t<decltype(o)>;
+            hipLaunchKernelGGL((warp_packed_kernel<TO, decltype(K)::value>), grid, block, 0, st, packed, packed_sn, H, W, C, geo, max_sigma,
+                               o, oy, ox, oc, out_sn);
+        };
+        if (out_dtype == LERF_U8) launch((uint8_t*)out);
+        else launch((float*)out);
+        return LERF_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------

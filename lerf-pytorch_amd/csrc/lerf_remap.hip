@@ -20,6 +20,7 @@
 // conversion to int (clip_coord sends NaN to 0 and +-inf to the borders), and every tap index passes axis_tap's clamps, so no
 // map value -- NaN, infinite, or 1e300 -- can form an address outside the operands.  A NaN entry reads nothing further and
 // stores 0 (uint8) / NaN (float).
+#include "lerf_dispatch.h"
 #include "lerf_warp_kernels.h"
 #include "lerf_remap_point.h"
 
@@ -47,38 +48,20 @@ remap_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
     warp_body<TI, TH, TO, A, KIND>(feat, fy, fx, fc, h0, h1, h2, hy, hx, hc, H, W, g, remap_pixel(g, q, H, W), c, max_sigma, dst);
 }
 
-template <typename TI, typename TH, typename TO, typename A>
-static int remap_dispatch_kind(const WarpArgs& a, const RemapGeo& m, hipStream_t st) {
-    dim3 block(256), grid((m.oW * a.C + 255) / 256, m.oH);
-#define LERF_RM(KIND)                                                                                        \
-    hipLaunchKernelGGL((remap_kernel<TI, TH, TO, A, KIND>), grid, block, 0, st, (const TI*)a.feat, a.fy,     \
-                       a.fx, a.fc, (const TH*)a.h[0], (const TH*)a.h[1], (const TH*)a.h[2], a.hy, a.hx,      \
-                       a.hc, a.H, a.W, a.C, m, (A)a.max_sigma, (TO*)a.out, a.oy, a.ox, a.oc)
-    if (a.kind == LERF_KIND_GAUSS) LERF_RM(LERF_KIND_GAUSS);
-    else if (a.kind == LERF_KIND_LINEAR) LERF_RM(LERF_KIND_LINEAR);
-    else if (a.kind == LERF_KIND_NEAREST) LERF_RM(LERF_KIND_NEAREST);
-    else if (a.kind == LERF_KIND_CUBIC) LERF_RM(LERF_KIND_CUBIC);
-    else if (a.kind == LERF_KIND_BILINEAR) LERF_RM(LERF_KIND_BILINEAR);
-    else if (a.kind == LERF_KIND_LANCZOS2) LERF_RM(LERF_KIND_LANCZOS2);
-    else if (a.kind == LERF_KIND_LANCZOS3) LERF_RM(LERF_KIND_LANCZOS3);
-    else return LERF_EUNSUPPORTED;
-#undef LERF_RM
-    return LERF_OK;
-}
-
-// the dtype and arithmetic table of launch_warp
 int launch_remap(const WarpArgs& a, const RemapGeo& m, hipStream_t st) {
     if (m.S < 1 || m.S > LERF_MAX_SUPPORT || m.oH > 65535) return LERF_EUNSUPPORTED;
+    dim3 block(256), grid((m.oW * a.C + 255) / 256, m.oH);
     const bool fixed = a.kind >= LERF_KIND_NEAREST;     // no hyper-parameter maps
-    if (a.in_dtype == LERF_U8 && (a.h_dtype == LERF_U8 || fixed)) {
-        if (a.out_dtype == LERF_U8) return remap_dispatch_kind<uint8_t, uint8_t, uint8_t, float>(a, m, st);
-        if (a.out_dtype == LERF_F32) return remap_dispatch_kind<uint8_t, uint8_t, float, double>(a, m, st);     // float64 arithmetic, rounded once
-        if (a.out_dtype == LERF_F64) return remap_dispatch_kind<uint8_t, uint8_t, double, double>(a, m, st);
-    } else if (a.in_dtype == LERF_F32 && (a.h_dtype == LERF_F32 || fixed)) {
-        if (a.out_dtype == LERF_F32) return remap_dispatch_kind<float, float, float, double>(a, m, st);
-        if (a.out_dtype == LERF_F64) return remap_dispatch_kind<float, float, double, double>(a, m, st);
-    }
-    return LERF_EUNSUPPORTED;
+    return with_stage3_types(a.in_dtype, a.h_dtype, a.out_dtype, fixed, [&](auto T) {
+        using TI = typename decltype(T)::TI; using TH = typename decltype(T)::TH;
+        using TO = typename decltype(T)::TO; using A = typename decltype(T)::A;
+        return with_kind(a.kind, [&](auto K) {
+            hipLaunchKernelGGL((remap_kernel<TI, TH, TO, A, decltype(K)::value>), grid, block, 0, st, (const TI*)a.feat, a.fy,
+                               a.fx, a.fc, (const TH*)a.h[0], (const TH*)a.h[1], (const TH*)a.h[2], a.hy, a.hx,
+                               a.hc, a.H, a.W, a.C, m, (A)a.max_sigma, (TO*)a.out, a.oy, a.ox, a.oc);
+            return LERF_OK;
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -143,45 +126,34 @@ int launch_remap_packed(const uint32_t* packed, int64_t packed_sn, int n, int H,
         (out_dtype == LERF_U8 || out_dtype == LERF_F32)) {
         const bool per_frame = m.map_stride != 0;
         dim3 blockp(256), gridp((unsigned)(((m.oW + 255) / 256) * m.oH), per_frame ? n : 1, 1);
-#define LERF_RPX1(TO, KIND, PROD, PER_FRAME)                                                                                      \
-    hipLaunchKernelGGL((remap_packed_px_kernel<TO, KIND, PROD, PER_FRAME>), gridp, blockp, 0, st, packed, packed_sn, n, H, W, m, max_sigma, \
-                       (TO*)out, oy, ox, oc, out_sn)
-#define LERF_RPX(TO, KIND, PROD)                     \
-    do {                                             \
-        if (per_frame) LERF_RPX1(TO, KIND, PROD, true); \
-        else LERF_RPX1(TO, KIND, PROD, false);       \
-    } while (0)
         const bool prod = out_dtype == LERF_U8 && max_sigma <= s3::kNoShiftMaxSigma;     // production arithmetic + tie guard
-        if (kind == LERF_KIND_GAUSS) {
-            if (prod) LERF_RPX(uint8_t, LERF_KIND_GAUSS, true);
-            else if (out_dtype == LERF_U8) LERF_RPX(uint8_t, LERF_KIND_GAUSS, false);
-            else LERF_RPX(float, LERF_KIND_GAUSS, false);
-        } else {
-            if (prod) LERF_RPX(uint8_t, LERF_KIND_LINEAR, true);
-            else if (out_dtype == LERF_U8) LERF_RPX(uint8_t, LERF_KIND_LINEAR, false);
-            else LERF_RPX(float, LERF_KIND_LINEAR, false);
-        }
-#undef LERF_RPX
-#undef LERF_RPX1
-        return LERF_OK;
+        return with_hyper_kind(kind, [&](auto K) {
+            auto launch = [&](auto* o, auto PROD) {
+                using TO = std::remove_pointer_t<decltype(o)>;
+                with_bool(per_frame, [&](auto PER_FRAME) {
+                    hipLaunchKernelGGL((remap_packed_px_kernel<TO, decltype(K)::value, decltype(PROD)::value, decltype(PER_FRAME)::value>),
+                                       gridp, blockp, 0, st, packed, packed_sn, n, H, W, m, max_sigma, o, oy, ox, oc, out_sn);
+                    return LERF_OK;
+                });
+            };
+            if (prod) launch((uint8_t*)out, std::true_type{});
+            else if (out_dtype == LERF_U8) launch((uint8_t*)out, std::false_type{});
+            else launch((float*)out, std::false_type{});
+            return LERF_OK;
+        });
     }
+    if (out_dtype != LERF_U8 && out_dtype != LERF_F32) return LERF_EUNSUPPORTED;
     dim3 block(256), grid((m.oW * C + 255) / 256, m.oH, n);
-#define LERF_RPK(TO, KIND)                                                                                         \
-    hipLaunchKernelGGL((remap_packed_kernel<TO, KIND>), grid, block, 0, st, packed, packed_sn, H, W, C, m, max_sigma, (TO*)out, \
-                       oy, ox, oc, out_sn)
-    if (kind == LERF_KIND_GAUSS) {
-        if (out_dtype == LERF_U8) LERF_RPK(uint8_t, LERF_KIND_GAUSS);
-        else if (out_dtype == LERF_F32) LERF_RPK(float, LERF_KIND_GAUSS);
-        else return LERF_EUNSUPPORTED;
-    } else if (kind == LERF_KIND_LINEAR) {
-        if (out_dtype == LERF_U8) LERF_RPK(uint8_t, LERF_KIND_LINEAR);
-        else if (out_dtype == LERF_F32) LERF_RPK(float, LERF_KIND_LINEAR);
-        else return LERF_EUNSUPPORTED;
-    } else {
-        return LERF_EUNSUPPORTED;
-    }
-#undef LERF_RPK
-    return LERF_OK;
+    return with_hyper_kind(kind, [&](auto K) {
+        auto launch = [&](auto* o) {
+            using TO = std::remove_pointer_t<decltype(o)>;
+            hipLaunchKernelGGL((remap_packed_kernel<TO, decltype(K)::value>), grid, block, 0, st, packed, packed_sn, H, W, C, m, max_sigma,
+                               o, oy, ox, oc, out_sn);
+        };
+        if (out_dtype == LERF_U8) launch((uint8_t*)out);
+        else launch((float*)out);
+        return LERF_OK;
+    });
 }
 
 }  // namespace lerf

@@ -17,6 +17,7 @@
 //
 // Addresses: as in lerf_remap.hip -- the map is read at (i, j) inside [oH][oW] only, the point is clipped before any conversion to
 // int and every tap index passes axis_tap's clamps; grad_coords is written at the same (n, i, j).
+#include "lerf_dispatch.h"
 #include "lerf_warp_bwd_kernels.h"
 #include "lerf_remap_point.h"
 
@@ -63,13 +64,11 @@ using namespace lerf::warp_bwd;
 static int remap_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W, const lerf_remap_geo_t* geo,
                      int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const double* grad_out, float* grad_feat,
                      float* grad_h0, float* grad_h1, float* grad_h2, double* grad_coords, void* stream) {
-    if (!feat || !geo || !grad_out || N < 1 || H < 1 || W < 1) return LERF_EINVAL;
+    if (!bwd_operands_ok(feat, geo, grad_out, N, H, W)) return LERF_EINVAL;
     RemapGeo m{};
-    const int rc = remap_geo_batched(geo, n_maps, map_stride, N, planes_per_map, m);
+    int rc = remap_geo_batched(geo, n_maps, map_stride, N, planes_per_map, m);
+    if (rc == LERF_OK) rc = bwd_kind_check(kind, h0, h1, h2);
     if (rc != LERF_OK) return rc;
-    if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
-    if ((kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) && !h0) return LERF_EINVAL;
-    if (kind == LERF_KIND_GAUSS && (!h1 || !h2)) return LERF_EINVAL;
     if (geo->S < 1 || geo->S > LERF_MAX_SUPPORT) return LERF_EUNSUPPORTED;
     if (N > 65535 || geo->out_h > 65535 * WB_ROWS) return LERF_EINVAL;
     if (grad_coords && (size_t)(uintptr_t)grad_coords % 16 != 0) return LERF_EINVAL;      // one 16-byte load / store per entry
@@ -77,25 +76,15 @@ static int remap_bwd(const float* feat, const float* h0, const float* h1, const 
     dim3 block(WB_NT), grid((m.oW + WB_COLS - 1) / WB_COLS, (m.oH + WB_ROWS - 1) / WB_ROWS, N);
     hipStream_t st = (hipStream_t)stream;
     const float ms = (float)max_sigma;
-#define LERF_RB1(KIND, COORD, A1, A2, A3)                                                                                       \
-    hipLaunchKernelGGL((remap_bwd_kernel<KIND, COORD>), grid, block, 0, st, feat, h0, h1, h2, H, W, m, ms, grad_out, grad_feat, A1, A2, \
-                       A3, grad_coords)
-#define LERF_RB(KIND, A1, A2, A3)                        \
-    do {                                                 \
-        if (grad_coords) LERF_RB1(KIND, true, A1, A2, A3); \
-        else LERF_RB1(KIND, false, A1, A2, A3);          \
-    } while (0)
-    switch (kind) {
-        case LERF_KIND_GAUSS: LERF_RB(LERF_KIND_GAUSS, grad_h0, grad_h1, grad_h2); break;
-        case LERF_KIND_LINEAR: LERF_RB(LERF_KIND_LINEAR, grad_h0, nullptr, nullptr); break;
-        case LERF_KIND_NEAREST: LERF_RB(LERF_KIND_NEAREST, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_CUBIC: LERF_RB(LERF_KIND_CUBIC, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_BILINEAR: LERF_RB(LERF_KIND_BILINEAR, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_LANCZOS2: LERF_RB(LERF_KIND_LANCZOS2, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_LANCZOS3: LERF_RB(LERF_KIND_LANCZOS3, nullptr, nullptr, nullptr); break;
-    }
-#undef LERF_RB
-#undef LERF_RB1
+    with_kind(kind, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;            // a kind's kernel is handed the gradients of the maps it reads only
+        return with_bool(grad_coords != nullptr, [&](auto COORD) {
+            hipLaunchKernelGGL((remap_bwd_kernel<KIND, decltype(COORD)::value>), grid, block, 0, st, feat, h0, h1, h2, H, W, m, ms, grad_out,
+                               grad_feat, KIND <= LERF_KIND_LINEAR ? grad_h0 : nullptr, KIND == LERF_KIND_GAUSS ? grad_h1 : nullptr,
+                               KIND == LERF_KIND_GAUSS ? grad_h2 : nullptr, grad_coords);
+            return LERF_OK;
+        });
+    });
     return launch_status();
 }
 

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "lerf_common.h"
+#include "lerf_dispatch.h"
 #include "lerf_stage3.h"
 #include "lerf_taps.h"
 
@@ -249,11 +250,10 @@ extern "C" {
 int lerf_resize_bwd_f32(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W,
                         const lerf_sr_geo_t* geo, int kind, double max_sigma, const float* grad_out, float* grad_feat,
                         float* grad_h0, float* grad_h1, float* grad_h2, void* stream) {
-    if (!feat || !geo || !grad_out || N < 1 || H < 1 || W < 1) return LERF_EINVAL;
+    if (!bwd_operands_ok(feat, geo, grad_out, N, H, W)) return LERF_EINVAL;
     if (geo->pad_mode < LERF_PAD_CONSTANT || geo->pad_mode > LERF_PAD_WRAP) return LERF_EINVAL;
-    if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
-    if ((kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) && !h0) return LERF_EINVAL;
-    if (kind == LERF_KIND_GAUSS && (!h1 || !h2)) return LERF_EINVAL;
+    const int rc = bwd_kind_check(kind, h0, h1, h2);
+    if (rc != LERF_OK) return rc;
     if (!geo->left_r || !geo->left_c || !geo->dis_r || !geo->dis_c || geo->out_h < 1 || geo->out_w < 1) return LERF_EINVAL;
     if (geo->S < 1 || geo->S > LERF_MAX_SUPPORT) return LERF_EUNSUPPORTED;
     clear_stale_error();
@@ -261,33 +261,25 @@ int lerf_resize_bwd_f32(const float* feat, const float* h0, const float* h1, con
     hipStream_t st = (hipStream_t)stream;
     const int pm = geo->pad_mode;
     const float ms = (float)max_sigma;
-#define LERF_RB(KIND, PADDED, A1, A2, A3)                                                                                  \
-    hipLaunchKernelGGL((resize_bwd_kernel<KIND, PADDED>), grid, block, 0, st, feat, h0, h1, h2, N, H, W, geo->S, geo->out_h, \
-                       geo->out_w, geo->left_r, geo->dis_r, geo->left_c, geo->dis_c, ms, pm, grad_out, grad_feat, A1, A2, A3)
-#define LERF_RF(KIND)                                                                                                        \
-    hipLaunchKernelGGL(resize_bwd_fixed_kernel<KIND>, grid, block, 0, st, H, W, geo->S, geo->out_h, geo->out_w, geo->left_r, \
-                       geo->dis_r, geo->left_c, geo->dis_c, pm, grad_out, grad_feat)
-    switch (kind) {
-        case LERF_KIND_GAUSS:
-            if (pm == LERF_PAD_CONSTANT) LERF_RB(LERF_KIND_GAUSS, false, grad_h0, grad_h1, grad_h2);
-            else LERF_RB(LERF_KIND_GAUSS, true, grad_h0, grad_h1, grad_h2);
-            break;
-        case LERF_KIND_LINEAR:
-            if (pm == LERF_PAD_CONSTANT) LERF_RB(LERF_KIND_LINEAR, false, grad_h0, nullptr, nullptr);
-            else LERF_RB(LERF_KIND_LINEAR, true, grad_h0, nullptr, nullptr);
-            break;
-        default:
-            if (!grad_feat) return LERF_OK;                 // nothing to compute: the fixed kinds have no other gradient
-            switch (kind) {
-                case LERF_KIND_NEAREST: LERF_RF(LERF_KIND_NEAREST); break;
-                case LERF_KIND_CUBIC: LERF_RF(LERF_KIND_CUBIC); break;
-                case LERF_KIND_BILINEAR: LERF_RF(LERF_KIND_BILINEAR); break;
-                case LERF_KIND_LANCZOS2: LERF_RF(LERF_KIND_LANCZOS2); break;
-                case LERF_KIND_LANCZOS3: LERF_RF(LERF_KIND_LANCZOS3); break;
-            }
+    if (kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) {
+        with_hyper_kind(kind, [&](auto K) {
+            constexpr int KIND = decltype(K)::value;        // the linear kernel has one hyper-parameter map to differentiate
+            return with_bool(pm == LERF_PAD_CONSTANT, [&](auto CONSTANT_PAD) {
+                hipLaunchKernelGGL((resize_bwd_kernel<KIND, !decltype(CONSTANT_PAD)::value>), grid, block, 0, st, feat, h0, h1, h2, N, H, W,
+                                   geo->S, geo->out_h, geo->out_w, geo->left_r, geo->dis_r, geo->left_c, geo->dis_c, ms, pm, grad_out,
+                                   grad_feat, grad_h0, KIND == LERF_KIND_GAUSS ? grad_h1 : nullptr,
+                                   KIND == LERF_KIND_GAUSS ? grad_h2 : nullptr);
+                return LERF_OK;
+            });
+        });
+    } else {
+        if (!grad_feat) return LERF_OK;                     // nothing to compute: the fixed kinds have no other gradient
+        with_fixed_kind(kind, [&](auto K) {
+            hipLaunchKernelGGL(resize_bwd_fixed_kernel<decltype(K)::value>, grid, block, 0, st, H, W, geo->S, geo->out_h, geo->out_w,
+                               geo->left_r, geo->dis_r, geo->left_c, geo->dis_c, pm, grad_out, grad_feat);
+            return LERF_OK;
+        });
     }
-#undef LERF_RB
-#undef LERF_RF
     return launch_status();
 }
 

@@ -165,6 +165,22 @@ at::Tensor sr_fused(const at::Tensor& img, at::TensorList s1, at::TensorList s2,
     return squeeze ? out.squeeze(0) : out;
 }
 
+// homography geometry of the warp ops: the inverse of `matrix` in float64 (np.linalg.inv, eval_lut_warp.py:327; torch.linalg.inv,
+// resize_right2d_torch.py:287) and its pads, constant pad.  No checks: warp_geometry below has those of the planar ops
+lerf_warp_geo_t fill_warp_geometry(const at::Tensor& matrix, int H, int W, int64_t out_h, int64_t out_w, int S) {
+    lerf_warp_geo_t g{};
+    g.S = S;
+    g.out_h = (int)out_h;
+    g.out_w = (int)out_w;
+    at::Tensor minv = at::linalg_inv(matrix.detach().to(at::kCPU, at::kDouble).reshape({3, 3})).contiguous();
+    memcpy(g.minv, minv.data_ptr<double>(), sizeof(g.minv));
+    int32_t pads[4];
+    check_rc(lerf_warp_pads(g.minv, H, W, g.out_h, g.out_w, g.S, pads), "lerf_warp_pads");
+    g.pad_r_lo = pads[0]; g.pad_r_hi = pads[1]; g.pad_c_lo = pads[2]; g.pad_c_hi = pads[3];
+    g.pad_mode = LERF_PAD_CONSTANT;
+    return g;
+}
+
 at::Tensor warp_fused(const at::Tensor& img, at::TensorList s1, at::TensorList s2, const c10::optional<at::Tensor>& pack,
                       const at::Tensor& matrix, int64_t out_h, int64_t out_w, int64_t support, double max_sigma) {
     TORCH_CHECK(img.scalar_type() == at::kByte && img.dim() == 3, "img must be uint8 [H,W,C]");
@@ -174,16 +190,7 @@ at::Tensor warp_fused(const at::Tensor& img, at::TensorList s1, at::TensorList s
     LutView L = make_luts(s1, s2, pack, x.device());
     const bool linear = L.st.oC == 1;
     const int H = (int)x.size(0), W = (int)x.size(1), C = (int)x.size(2);
-    lerf_warp_geo_t g{};
-    g.S = linear ? 2 : (int)support;
-    g.out_h = (int)out_h;
-    g.out_w = (int)out_w;
-    at::Tensor minv = at::linalg_inv(matrix.detach().to(at::kCPU, at::kDouble).reshape({3, 3})).contiguous();   // np.linalg.inv (:327)
-    memcpy(g.minv, minv.data_ptr<double>(), sizeof(g.minv));
-    int32_t pads[4];
-    check_rc(lerf_warp_pads(g.minv, H, W, g.out_h, g.out_w, g.S, pads), "lerf_warp_pads");
-    g.pad_r_lo = pads[0]; g.pad_r_hi = pads[1]; g.pad_c_lo = pads[2]; g.pad_c_hi = pads[3];
-    g.pad_mode = LERF_PAD_CONSTANT;
+    const lerf_warp_geo_t g = fill_warp_geometry(matrix, H, W, out_h, out_w, linear ? 2 : (int)support);
     const int kind = linear ? LERF_KIND_LINEAR : LERF_KIND_GAUSS;
     const double ms = linear ? 1.0 : max_sigma;
     at::Tensor out = at::empty({out_h, out_w, C}, x.options());
@@ -208,26 +215,38 @@ at::Tensor warp_fused(const at::Tensor& img, at::TensorList s1, at::TensorList s
     return out;
 }
 
+// the operands of the planar forward ops: float32 [B,C,H,W] maps, made contiguous, as B * C planes of the C ABI
+struct PlanarOperands {
+    at::Tensor x;
+    std::vector<at::Tensor> h;
+    int B, C, H, W;
+    lerf_plane_t pf, hp[3];
+};
+
+PlanarOperands planar_operands(const at::Tensor& feat, const std::vector<at::Tensor>& hs) {
+    PlanarOperands p;
+    p.B = (int)feat.size(0); p.C = (int)feat.size(1); p.H = (int)feat.size(2); p.W = (int)feat.size(3);
+    p.x = feat.contiguous();
+    for (const at::Tensor& t : hs) {
+        TORCH_CHECK(t.sizes() == feat.sizes() && t.scalar_type() == at::kFloat && t.device() == feat.device(),
+                    "hyper-parameter maps must match feat (float32, same shape and device)");
+        p.h.push_back(t.contiguous());
+    }
+    const int64_t hw = (int64_t)p.H * p.W;
+    p.pf = lerf_plane_t{p.x.data_ptr(), LERF_F32, p.W, 1, hw};
+    for (int k = 0; k < 3; ++k) p.hp[k] = lerf_plane_t{p.h[k < (int)p.h.size() ? k : 0].data_ptr(), LERF_F32, p.W, 1, hw};
+    return p;
+}
+
 // planar float32 maps [B,C,H,W] -> [B,C,oH,oW]; float32 geometry of the torch classes (resize_right2d_torch.py:48-103)
 at::Tensor resize_planar(int kind, const at::Tensor& feat, const std::vector<at::Tensor>& hs, double sh, double sw, int64_t S, double ms) {
     TORCH_CHECK(feat.dim() == 4 && feat.scalar_type() == at::kFloat, "feat must be float32 [B,C,H,W]");
     DeviceGuard guard(feat.device());
-    const int B = (int)feat.size(0), C = (int)feat.size(1), H = (int)feat.size(2), W = (int)feat.size(3);
-    at::Tensor x = feat.contiguous();
-    std::vector<at::Tensor> h;
-    for (const at::Tensor& t : hs) {
-        TORCH_CHECK(t.sizes() == feat.sizes() && t.scalar_type() == at::kFloat && t.device() == feat.device(),
-                    "hyper-parameter maps must match feat (float32, same shape and device)");
-        h.push_back(t.contiguous());
-    }
-    const SrGeo& g = sr_geometry(H, W, sh, sw, (int)S, true, x.device());
-    at::Tensor out = at::empty({B, C, g.oH, g.oW}, x.options());
-    const int64_t hw = (int64_t)H * W;
-    lerf_plane_t pf{x.data_ptr(), LERF_F32, W, 1, hw};
-    lerf_plane_t hp[3];
-    for (int k = 0; k < 3; ++k) hp[k] = lerf_plane_t{h[k < (int)h.size() ? k : 0].data_ptr(), LERF_F32, W, 1, hw};
+    const PlanarOperands p = planar_operands(feat, hs);
+    const SrGeo& g = sr_geometry(p.H, p.W, sh, sw, (int)S, true, p.x.device());
+    at::Tensor out = at::empty({p.B, p.C, g.oH, g.oW}, p.x.options());
     lerf_mplane_t po{out.data_ptr(), LERF_F32, g.oW, 1, (int64_t)g.oH * g.oW};
-    check_rc(lerf_resize(&pf, hp, H, W, B * C, &g.st, kind, ms, &po, cur_stream()), "lerf_resize");
+    check_rc(lerf_resize(&p.pf, p.hp, p.H, p.W, p.B * p.C, &g.st, kind, ms, &po, cur_stream()), "lerf_resize");
     return out;
 }
 
@@ -238,6 +257,31 @@ at::Tensor resize_gauss(const at::Tensor& feat, const at::Tensor& rho, const at:
 
 at::Tensor resize_linear(const at::Tensor& feat, const at::Tensor& alpha, double scale_h, double scale_w, double max_sigma) {
     return resize_planar(LERF_KIND_LINEAR, feat, {alpha}, scale_h, scale_w, 2, max_sigma);
+}
+
+// the operands of the planar backward ops, made contiguous (the upstream gradient in the type its entry point reads: float64 for
+// the warp), and the four zeroed gradients they accumulate into; the pointers of the
+// maps and gradients the linear kernel has no use for are null
+struct BackwardOperands {
+    at::Tensor x, go, a, b, c, gx, g0, g1, g2;
+    bool gauss;
+    const float* hp(int k) const { return k == 0 ? a.data_ptr<float>() : (gauss ? (k == 1 ? b : c).data_ptr<float>() : nullptr); }
+    float* gp(int k) const { return k == 0 ? g0.data_ptr<float>() : (gauss ? (k == 1 ? g1 : g2).data_ptr<float>() : nullptr); }
+    std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> grads() const { return {gx, g0, g1, g2}; }
+};
+
+BackwardOperands backward_operands(bool gauss, const at::Tensor& feat, const at::Tensor& grad_out, bool go_double, const at::Tensor& h0,
+                                   const at::Tensor& h1, const at::Tensor& h2) {
+    for (const at::Tensor* t : {&h0, &h1, &h2})         // all three are read by the Gaussian kernel, h0 by the linear one
+        TORCH_CHECK((t != &h0 && !gauss) || (t->sizes() == feat.sizes() && t->scalar_type() == at::kFloat && t->device() == feat.device()),
+                    "hyper-parameter maps must match feat (float32, same shape and device)");
+    BackwardOperands o;
+    o.gauss = gauss;
+    o.x = feat.contiguous();
+    o.go = go_double ? grad_out.to(at::kDouble).contiguous() : grad_out.contiguous();
+    o.a = h0.contiguous(); o.b = h1.contiguous(); o.c = h2.contiguous();
+    o.gx = at::zeros_like(o.x); o.g0 = at::zeros_like(o.x); o.g1 = at::zeros_like(o.x); o.g2 = at::zeros_like(o.x);
+    return o;
 }
 
 // gradients of resize_gauss (kind 0: feat, rho, sigma_x, sigma_y) / resize_linear (kind 1: feat, alpha; the last two are zeros)
@@ -252,36 +296,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> resize_backward(int64
     TORCH_CHECK(grad_out.dim() == 4 && grad_out.size(0) == B && grad_out.size(1) == C && grad_out.size(2) == g.oH && grad_out.size(3) == g.oW &&
                     grad_out.device() == feat.device(),
                 "grad_out must be [B,C,oH,oW] of the output geometry, on feat's device");
-    for (const at::Tensor* t : {&h0, &h1, &h2})         // all three are read by the Gaussian kernel, h0 by the linear one
-        TORCH_CHECK((t != &h0 && kind == LERF_KIND_LINEAR) ||
-                        (t->sizes() == feat.sizes() && t->scalar_type() == at::kFloat && t->device() == feat.device()),
-                    "hyper-parameter maps must match feat (float32, same shape and device)");
-    at::Tensor x = feat.contiguous(), go = grad_out.contiguous(), a = h0.contiguous(), b = h1.contiguous(), c = h2.contiguous();
-    at::Tensor gx = at::zeros_like(x), g0 = at::zeros_like(x), g1 = at::zeros_like(x), g2 = at::zeros_like(x);
-    const bool gauss = kind == LERF_KIND_GAUSS;
-    check_rc(lerf_resize_bwd_f32(x.data_ptr<float>(), a.data_ptr<float>(), gauss ? b.data_ptr<float>() : nullptr,
-                                 gauss ? c.data_ptr<float>() : nullptr, B * C, H, W, &g.st, (int)kind, max_sigma, go.data_ptr<float>(),
-                                 gx.data_ptr<float>(), g0.data_ptr<float>(), gauss ? g1.data_ptr<float>() : nullptr,
-                                 gauss ? g2.data_ptr<float>() : nullptr, cur_stream()),
+    const BackwardOperands o = backward_operands(kind == LERF_KIND_GAUSS, feat, grad_out, false, h0, h1, h2);
+    check_rc(lerf_resize_bwd_f32(o.x.data_ptr<float>(), o.hp(0), o.hp(1), o.hp(2), B * C, H, W, &g.st, (int)kind, max_sigma, o.go.data_ptr<float>(),
+                                 o.gx.data_ptr<float>(), o.gp(0), o.gp(1), o.gp(2), cur_stream()),
              "lerf_resize_bwd_f32");
-    return {gx, g0, g1, g2};
+    return o.grads();
 }
 
-// homography geometry of the torch warp classes: torch.linalg.inv(matrix) in float64 (resize_right2d_torch.py:287), constant pad
+// homography geometry of the torch warp classes
 lerf_warp_geo_t warp_geometry(const at::Tensor& matrix, int H, int W, int64_t out_h, int64_t out_w, int S) {
     TORCH_CHECK(matrix.numel() == 9, "matrix must be 3x3 (input -> output coordinates)");
     TORCH_CHECK(out_h >= 1 && out_w >= 1 && S >= 1 && S <= LERF_MAX_SUPPORT, "bad output size / support");
-    lerf_warp_geo_t g{};
-    g.S = S;
-    g.out_h = (int)out_h;
-    g.out_w = (int)out_w;
-    at::Tensor minv = at::linalg_inv(matrix.detach().to(at::kCPU, at::kDouble).reshape({3, 3})).contiguous();
-    memcpy(g.minv, minv.data_ptr<double>(), sizeof(g.minv));
-    int32_t pads[4];
-    check_rc(lerf_warp_pads(g.minv, H, W, g.out_h, g.out_w, g.S, pads), "lerf_warp_pads");
-    g.pad_r_lo = pads[0]; g.pad_r_hi = pads[1]; g.pad_c_lo = pads[2]; g.pad_c_hi = pads[3];
-    g.pad_mode = LERF_PAD_CONSTANT;
-    return g;
+    return fill_warp_geometry(matrix, H, W, out_h, out_w, S);
 }
 
 // planar float32 maps [B,C,H,W] -> float64 [B,C,out_h,out_w]
@@ -289,22 +315,11 @@ at::Tensor warp_planar(int kind, const at::Tensor& feat, const std::vector<at::T
                        int64_t out_w, int64_t S, double ms) {
     TORCH_CHECK(feat.dim() == 4 && feat.scalar_type() == at::kFloat, "feat must be float32 [B,C,H,W]");
     DeviceGuard guard(feat.device());
-    const int B = (int)feat.size(0), C = (int)feat.size(1), H = (int)feat.size(2), W = (int)feat.size(3);
-    at::Tensor x = feat.contiguous();
-    std::vector<at::Tensor> h;
-    for (const at::Tensor& t : hs) {
-        TORCH_CHECK(t.sizes() == feat.sizes() && t.scalar_type() == at::kFloat && t.device() == feat.device(),
-                    "hyper-parameter maps must match feat (float32, same shape and device)");
-        h.push_back(t.contiguous());
-    }
-    const lerf_warp_geo_t g = warp_geometry(matrix, H, W, out_h, out_w, (int)S);
-    at::Tensor out = at::empty({B, C, out_h, out_w}, x.options().dtype(at::kDouble));
-    const int64_t hw = (int64_t)H * W;
-    lerf_plane_t pf{x.data_ptr(), LERF_F32, W, 1, hw};
-    lerf_plane_t hp[3];
-    for (int k = 0; k < 3; ++k) hp[k] = lerf_plane_t{h[k < (int)h.size() ? k : 0].data_ptr(), LERF_F32, W, 1, hw};
+    const PlanarOperands p = planar_operands(feat, hs);
+    const lerf_warp_geo_t g = warp_geometry(matrix, p.H, p.W, out_h, out_w, (int)S);
+    at::Tensor out = at::empty({p.B, p.C, out_h, out_w}, p.x.options().dtype(at::kDouble));
     lerf_mplane_t po{out.data_ptr(), LERF_F64, out_w, 1, out_h * out_w};
-    check_rc(lerf_warp(&pf, hp, H, W, B * C, &g, kind, ms, &po, cur_stream()), "lerf_warp");
+    check_rc(lerf_warp(&p.pf, p.hp, p.H, p.W, p.B * p.C, &g, kind, ms, &po, cur_stream()), "lerf_warp");
     return out;
 }
 
@@ -331,16 +346,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> warp_backward(int64_t
     TORCH_CHECK(grad_out.dim() == 4 && grad_out.size(0) == B && grad_out.size(1) == C && grad_out.size(2) == out_h && grad_out.size(3) == out_w &&
                     grad_out.device() == feat.device(),
                 "grad_out must be [B,C,out_h,out_w], on feat's device");
-    for (const at::Tensor* t : {&h0, &h1, &h2})         // all three are read by the Gaussian kernel, h0 by the linear one
-        TORCH_CHECK((t != &h0 && !gauss) || (t->sizes() == feat.sizes() && t->scalar_type() == at::kFloat && t->device() == feat.device()),
-                    "hyper-parameter maps must match feat (float32, same shape and device)");
-    at::Tensor x = feat.contiguous(), go = grad_out.to(at::kDouble).contiguous(), a = h0.contiguous(), b = h1.contiguous(), c = h2.contiguous();
-    at::Tensor gx = at::zeros_like(x), g0 = at::zeros_like(x), g1 = at::zeros_like(x), g2 = at::zeros_like(x);
-    check_rc(lerf_warp_bwd(x.data_ptr<float>(), a.data_ptr<float>(), gauss ? b.data_ptr<float>() : nullptr, gauss ? c.data_ptr<float>() : nullptr,
-                           B * C, H, W, &g, (int)kind, max_sigma, go.data_ptr<double>(), gx.data_ptr<float>(), g0.data_ptr<float>(),
-                           gauss ? g1.data_ptr<float>() : nullptr, gauss ? g2.data_ptr<float>() : nullptr, cur_stream()),
+    const BackwardOperands o = backward_operands(gauss, feat, grad_out, true, h0, h1, h2);
+    check_rc(lerf_warp_bwd(o.x.data_ptr<float>(), o.hp(0), o.hp(1), o.hp(2), B * C, H, W, &g, (int)kind, max_sigma, o.go.data_ptr<double>(),
+                           o.gx.data_ptr<float>(), o.gp(0), o.gp(1), o.gp(2), cur_stream()),
              "lerf_warp_bwd");
-    return {gx, g0, g1, g2};
+    return o.grads();
 }
 
 }  // namespace

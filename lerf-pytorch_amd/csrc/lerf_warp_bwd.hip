@@ -11,8 +11,7 @@
 // A pixel whose weights all vanish is NaN in the forward (0/0); the same formulas hand its taps NaN, as autograd does.
 // Hyper-parameter gradients land on the clamped source pixel (the maps are replicate-padded), the image gradient on
 // the pixel the image's pad rule names (nothing for a constant pad outside the frame: F.pad's backward).
-#include <string.h>
-
+#include "lerf_dispatch.h"
 #include "lerf_warp_bwd_kernels.h"
 
 namespace lerf {
@@ -44,36 +43,25 @@ extern "C" {
 int lerf_warp_bwd(const float* feat, const float* h0, const float* h1, const float* h2, int N, int H, int W, const lerf_warp_geo_t* geo,
                   int kind, double max_sigma, const double* grad_out, float* grad_feat, float* grad_h0, float* grad_h1, float* grad_h2,
                   void* stream) {
-    if (!feat || !geo || !grad_out || N < 1 || H < 1 || W < 1) return LERF_EINVAL;
+    if (!bwd_operands_ok(feat, geo, grad_out, N, H, W)) return LERF_EINVAL;
     if (geo->out_h < 1 || geo->out_w < 1 || geo->pad_mode < LERF_PAD_CONSTANT || geo->pad_mode > LERF_PAD_WRAP) return LERF_EINVAL;
-    if (kind < LERF_KIND_GAUSS || kind > LERF_KIND_LANCZOS3) return LERF_EUNSUPPORTED;
-    if ((kind == LERF_KIND_GAUSS || kind == LERF_KIND_LINEAR) && !h0) return LERF_EINVAL;
-    if (kind == LERF_KIND_GAUSS && (!h1 || !h2)) return LERF_EINVAL;
+    const int rc = bwd_kind_check(kind, h0, h1, h2);
+    if (rc != LERF_OK) return rc;
     if (geo->S < 1 || geo->S > LERF_MAX_SUPPORT) return LERF_EUNSUPPORTED;
     if (geo->out_y0 != 0 || geo->out_x0 != 0 || geo->src_y0 != 0) return LERF_EUNSUPPORTED;     // whole outputs only
     if (N > 65535 || geo->out_h > 65535 * WB_ROWS) return LERF_EINVAL;
     clear_stale_error();
-    WarpGeo g{};
-    g.S = geo->S; g.oH = geo->out_h; g.oW = geo->out_w;
-    memcpy(g.minv, geo->minv, sizeof(g.minv));
-    g.pad_r_lo = geo->pad_r_lo; g.pad_r_hi = geo->pad_r_hi;
-    g.pad_c_lo = geo->pad_c_lo; g.pad_c_hi = geo->pad_c_hi;
-    g.pad_mode = geo->pad_mode;
+    const WarpGeo g = to_warp_geo(*geo);
     dim3 block(WB_NT), grid((g.oW + WB_COLS - 1) / WB_COLS, (g.oH + WB_ROWS - 1) / WB_ROWS, N);
     hipStream_t st = (hipStream_t)stream;
     const float ms = (float)max_sigma;
-#define LERF_WB(KIND, A1, A2, A3)                                                                                          \
-    hipLaunchKernelGGL(warp_bwd_kernel<KIND>, grid, block, 0, st, feat, h0, h1, h2, H, W, g, ms, grad_out, grad_feat, A1, A2, A3)
-    switch (kind) {
-        case LERF_KIND_GAUSS: LERF_WB(LERF_KIND_GAUSS, grad_h0, grad_h1, grad_h2); break;
-        case LERF_KIND_LINEAR: LERF_WB(LERF_KIND_LINEAR, grad_h0, nullptr, nullptr); break;
-        case LERF_KIND_NEAREST: LERF_WB(LERF_KIND_NEAREST, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_CUBIC: LERF_WB(LERF_KIND_CUBIC, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_BILINEAR: LERF_WB(LERF_KIND_BILINEAR, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_LANCZOS2: LERF_WB(LERF_KIND_LANCZOS2, nullptr, nullptr, nullptr); break;
-        case LERF_KIND_LANCZOS3: LERF_WB(LERF_KIND_LANCZOS3, nullptr, nullptr, nullptr); break;
-    }
-#undef LERF_WB
+    with_kind(kind, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;            // a kind's kernel is handed the gradients of the maps it reads only
+        hipLaunchKernelGGL(warp_bwd_kernel<KIND>, grid, block, 0, st, feat, h0, h1, h2, H, W, g, ms, grad_out, grad_feat,
+                           KIND <= LERF_KIND_LINEAR ? grad_h0 : nullptr, KIND == LERF_KIND_GAUSS ? grad_h1 : nullptr,
+                           KIND == LERF_KIND_GAUSS ? grad_h2 : nullptr);
+        return LERF_OK;
+    });
     return launch_status();
 }
 

@@ -493,26 +493,40 @@ def unpack_stages(packed, oC):
     return feat, hq
 
 
-def warp_packed(packed, geo: "WarpGeometry", kind="gauss", max_sigma=10.0, out="u8"):
-    """packed: int32 [H,W,C] or a batch [N,H,W,C] sharing the homography (ONE launch for the batch).
-    out: "u8" / "f32" (a fresh tensor) or a caller-owned uint8 / float32 tensor of the output shape to write into."""
-    torch = _torch()
+def _hyper_count(kind):
+    """hyper-parameter maps of a kind: the fixed kernels (cubic, bilinear, ...) take none"""
+    return {"gauss": 3, "linear": 1}.get(kind, 0)
+
+
+def _packed_frames(packed):
+    """packed int32 [H,W,C] or [N,H,W,C] -> ([N,H,W,C] with dense frames, whether the result drops the batch axis again)"""
     squeeze = packed.dim() == 3
     p = packed.unsqueeze(0) if squeeze else packed
     if not p[0].is_contiguous():
         p = p.contiguous()
+    return p, squeeze
+
+
+def _batched_out(out, oshape, squeeze, device):
+    """`out` of the packed warps as [N,oH,oW,C]: "u8" / "f32" (a fresh tensor) or the caller's own, [oH,oW,C] for a 3-D input"""
+    torch = _torch()
+    if isinstance(out, str):
+        return torch.empty(oshape, dtype=_out_dtype(out), device=device)
+    o = out.unsqueeze(0) if (squeeze and out.dim() == 3) else out
+    if tuple(o.shape) != oshape or o.dtype not in (torch.uint8, torch.float32) or o.device != device or o.stride(3) != 1:
+        raise ValueError("out must be a uint8/float32 tensor of shape %s on the input's device" % (oshape[1:] if squeeze else oshape,))
+    return o
+
+
+def warp_packed(packed, geo: "WarpGeometry", kind="gauss", max_sigma=10.0, out="u8"):
+    """packed: int32 [H,W,C] or a batch [N,H,W,C] sharing the homography (ONE launch for the batch).
+    out: "u8" / "f32" (a fresh tensor) or a caller-owned uint8 / float32 tensor of the output shape to write into."""
+    p, squeeze = _packed_frames(packed)
     N, Hb, W, Cn = p.shape
     H = geo.in_hw[0]                                        # the frame's height; `packed` may hold its rows from geo.src_y0 on only
     if W != geo.in_hw[1] or geo.src_y0 + Hb > H:
         raise ValueError("packed maps do not match the geometry's frame")
-    oshape = (N, geo.out_hw[0], geo.out_hw[1], Cn)
-    if isinstance(out, str):
-        o = torch.empty(oshape, dtype=_out_dtype(out), device=p.device)
-    else:
-        o = out.unsqueeze(0) if (squeeze and out.dim() == 3) else out
-        if tuple(o.shape) != oshape or o.dtype not in (torch.uint8, torch.float32) or o.device != p.device \
-                or o.stride(3) != 1:
-            raise ValueError("out must be a uint8/float32 tensor of shape %s on the input's device" % (oshape[1:] if squeeze else oshape,))
+    o = _batched_out(out, (N, geo.out_hw[0], geo.out_hw[1], Cn), squeeze, p.device)
     po = _lib.plane(o, o.stride(1), o.stride(2), o.stride(3))
     _lib.check(_lib.lib().lerf_warp_packed(p.data_ptr(), p.stride(0), N, H, W, Cn, geo.ref(), KINDS[kind], float(max_sigma),
                                            C.byref(po), o.stride(0), _lib.current_stream()), "lerf_warp_packed")
@@ -523,24 +537,13 @@ def remap_packed(packed, geo: "RemapGeometry", kind="gauss", max_sigma=10.0, out
     """warp_packed by a coordinate map (lerf_remap_packed): packed int32 [H,W,C] or a batch [N,H,W,C] sharing the map (ONE launch
     for the batch).  A batched geometry (one map per frame, lerf_remap_packed_batched): frame f reads map f, N == geo.n_maps, still
     one launch.  out: "u8" / "f32" (a fresh tensor) or a caller-owned uint8 / float32 tensor of the output shape."""
-    torch = _torch()
-    squeeze = packed.dim() == 3
-    p = packed.unsqueeze(0) if squeeze else packed
-    if not p[0].is_contiguous():
-        p = p.contiguous()
+    p, squeeze = _packed_frames(packed)
     N, H, W, Cn = p.shape
     if (H, W) != geo.in_hw:
         raise ValueError("packed maps do not match the geometry's frame")
     if geo.batched and N != geo.n_maps:
         raise ValueError("%d frames for %d maps: a batched geometry takes one frame per map" % (N, geo.n_maps))
-    oshape = (N, geo.out_hw[0], geo.out_hw[1], Cn)
-    if isinstance(out, str):
-        o = torch.empty(oshape, dtype=_out_dtype(out), device=p.device)
-    else:
-        o = out.unsqueeze(0) if (squeeze and out.dim() == 3) else out
-        if tuple(o.shape) != oshape or o.dtype not in (torch.uint8, torch.float32) or o.device != p.device \
-                or o.stride(3) != 1:
-            raise ValueError("out must be a uint8/float32 tensor of shape %s on the input's device" % (oshape[1:] if squeeze else oshape,))
+    o = _batched_out(out, (N, geo.out_hw[0], geo.out_hw[1], Cn), squeeze, p.device)
     po = _lib.plane(o, o.stride(1), o.stride(2), o.stride(3))
     g, _keep = geo.struct(p.device)
     if geo.batched:
@@ -604,58 +607,81 @@ def _hyper_planes(hyper, layout, nh):
     return arr, keep
 
 
-def resize_hwc_u8(feat_u8, hq_u8, geo: SrGeometry, kind="gauss", max_sigma=10.0, out="u8"):
-    """stage 3 on the uint8 stage outputs: feat [H,W,C], hq [H,W,C,oC] -> [oH,oW,C]."""
+def _stage3_hwc(call, feat, hq_u8, kind, geo, out, match=False):
+    """One stage-3 launch on the uint8 stage outputs: feat [H,W,C] (contiguous), hq [H,W,C,oC] -> a fresh [oH,oW,C].  `call` takes
+    the image, hyper and output planes; the operands live until it returns.  match: hq must have feat's shape (the SR contract)"""
     torch = _torch()
-    feat = feat_u8.contiguous()
-    H, W, Cn = feat.shape
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)          # fixed kernels (cubic, bilinear, ...) take no hyper maps
-    o = torch.empty((geo.out_hw[0], geo.out_hw[1], Cn), dtype=_out_dtype(out), device=feat.device)
+    nh = _hyper_count(kind)
+    o = torch.empty((geo.out_hw[0], geo.out_hw[1], feat.shape[2]), dtype=_out_dtype(out), device=feat.device)
     pf = _planes_hwc(feat)
+    ph = None
     if nh:
         hq = hq_u8.contiguous()
-        if hq.shape[:3] != feat.shape or hq.shape[3] < nh:
+        if match and (hq.shape[:3] != feat.shape or hq.shape[3] < nh):
             raise ValueError("hyper shape mismatch")
         ph, _keep = _hyper_planes(hq, "hwck", nh)
-    else:
-        ph = None
-    po = _planes_hwc(o)
-    _lib.check(_lib.lib().lerf_resize(C.byref(pf), ph, H, W, Cn, geo.ref(), KINDS[kind], float(max_sigma),
-                                      C.byref(po), _lib.current_stream()), "lerf_resize")
+    call(pf, ph, _planes_hwc(o))
     return o
+
+
+def _stage3_planar(call, feat, hypers, kind, geo, out, match=False):
+    """The same on planar float32 maps: feat [N,H,W] (contiguous float32), hypers = list of [N,H,W] -> a fresh [N,oH,oW]"""
+    torch = _torch()
+    nh = _hyper_count(kind)
+    o = torch.empty((feat.shape[0], geo.out_hw[0], geo.out_hw[1]), dtype=_out_dtype(out), device=feat.device)
+    pf = _planes_chw(feat)
+    ph = None
+    if nh:
+        hypers = [h.contiguous().float() for h in hypers[:nh]]
+        for h in hypers:
+            if match and h.shape != feat.shape:
+                raise ValueError("hyper maps must have the shape of the input")
+        ph, _keep = _hyper_planes(hypers, "planar", nh)
+    call(pf, ph, _planes_chw(o))
+    return o
+
+
+def _resize_call(geo, H, W, planes, kind, max_sigma):
+    return lambda pf, ph, po: _lib.check(_lib.lib().lerf_resize(C.byref(pf), ph, H, W, planes, geo.ref(), KINDS[kind], float(max_sigma),
+                                                                C.byref(po), _lib.current_stream()), "lerf_resize")
+
+
+def _warp_call(geo, H, W, planes, kind, max_sigma):
+    return lambda pf, ph, po: _lib.check(_lib.lib().lerf_warp(C.byref(pf), ph, H, W, planes, geo.ref(), KINDS[kind], float(max_sigma),
+                                                              C.byref(po), _lib.current_stream()), "lerf_warp")
+
+
+def resize_hwc_u8(feat_u8, hq_u8, geo: SrGeometry, kind="gauss", max_sigma=10.0, out="u8"):
+    """stage 3 on the uint8 stage outputs: feat [H,W,C], hq [H,W,C,oC] -> [oH,oW,C]."""
+    feat = feat_u8.contiguous()
+    H, W, Cn = feat.shape
+    return _stage3_hwc(_resize_call(geo, H, W, Cn, kind, max_sigma), feat, hq_u8, kind, geo, out, match=True)
 
 
 def resize_planar(feat, hypers, geo: SrGeometry, kind="gauss", max_sigma=10.0, out="f32"):
     """stage 3 on planar float32 maps: feat [N,H,W], hypers = list of [N,H,W] in [0,1] -> [N,oH,oW]."""
-    torch = _torch()
     feat = feat.contiguous().float()
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
     N, H, W = feat.shape
-    o = torch.empty((N, geo.out_hw[0], geo.out_hw[1]), dtype=_out_dtype(out), device=feat.device)
-    pf = _planes_chw(feat)
-    if nh:
-        hypers = [h.contiguous().float() for h in hypers[:nh]]
-        for h in hypers:
-            if h.shape != feat.shape:
-                raise ValueError("hyper maps must have the shape of the input")
-        ph, _keep = _hyper_planes(hypers, "planar", nh)
-    else:
-        ph = None
-    po = _planes_chw(o)
-    _lib.check(_lib.lib().lerf_resize(C.byref(pf), ph, H, W, N, geo.ref(), KINDS[kind], float(max_sigma),
-                                      C.byref(po), _lib.current_stream()), "lerf_resize")
-    return o
+    return _stage3_planar(_resize_call(geo, H, W, N, kind, max_sigma), feat, hypers, kind, geo, out, match=True)
 
 
-def resize_bwd_planar(feat, hypers, geo: SrGeometry, kind, max_sigma, grad_out, grads):
-    """lerf_resize_bwd_f32: accumulate the gradients of resize_planar(feat, hypers, geo, kind, max_sigma, out="f32") for the
-    float32 upstream gradient `grad_out` [N, oH, oW] into `grads` = [grad_feat, grad_h0, grad_h1, grad_h2] (float32
-    [N, H, W] contiguous tensors, or None to skip a map; the fixed kinds have grad_feat alone).  feat / hypers: float32
-    [N, H, W].  The image gradient follows geo.pad_mode."""
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _bwd_inputs(feat, hypers, kind, grad_out, double):
+    """the tensors a stage-3 backward reads: contiguous float32 planes and the upstream gradient in the forward's output type"""
     feat = feat.contiguous().float()
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
-    hs = [h.contiguous().float() for h in hypers[:nh]]
-    g = grad_out.contiguous().float()
+    hs = [h.contiguous().float() for h in hypers[:_hyper_count(kind)]]
+    g = grad_out.contiguous()
+    return feat, hs, g.double() if double else g.float()
+
+
+def _bwd_buffers(feat, hs, g, geo, grads):
+    """checks grad_out and the gradient buffers of a stage-3 backward -> (grads padded to four, operands, gradients): the two
+    argument runs every lerf_*_bwd prototype shares, in its order --
+    operands = (feat, h0, h1, h2, N, H, W), before the geometry; gradients = (grad_out, grad_feat, grad_h0, grad_h1, grad_h2),
+    after kind and max_sigma"""
     N, H, W = feat.shape
     if tuple(g.shape) != (N, geo.out_hw[0], geo.out_hw[1]):
         raise ValueError("grad_out must be [N, out_h, out_w] of the geometry")
@@ -663,11 +689,19 @@ def resize_bwd_planar(feat, hypers, geo: SrGeometry, kind, max_sigma, grad_out, 
     for t in grads:
         if t is not None and (t.dtype != feat.dtype or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
             raise ValueError("gradient buffers must be contiguous float32 [N, H, W]")
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-    hp = [ptr(h) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
-    _lib.check(_lib.lib().lerf_resize_bwd_f32(ptr(feat), hp[0], hp[1], hp[2], N, H, W, geo.ref(), KINDS[kind], float(max_sigma),
-                                              ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]),
-                                              _lib.current_stream()), "lerf_resize_bwd_f32")
+    hp = [_ptr(h) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
+    return grads, (_ptr(feat), hp[0], hp[1], hp[2], N, H, W), (_ptr(g),) + tuple(_ptr(t) for t in grads)
+
+
+def resize_bwd_planar(feat, hypers, geo: SrGeometry, kind, max_sigma, grad_out, grads):
+    """lerf_resize_bwd_f32: accumulate the gradients of resize_planar(feat, hypers, geo, kind, max_sigma, out="f32") for the
+    float32 upstream gradient `grad_out` [N, oH, oW] into `grads` = [grad_feat, grad_h0, grad_h1, grad_h2] (float32
+    [N, H, W] contiguous tensors, or None to skip a map; the fixed kinds have grad_feat alone).  feat / hypers: float32
+    [N, H, W].  The image gradient follows geo.pad_mode."""
+    feat, hs, g = _bwd_inputs(feat, hypers, kind, grad_out, double=False)
+    grads, operands, gradients = _bwd_buffers(feat, hs, g, geo, grads)
+    _lib.check(_lib.lib().lerf_resize_bwd_f32(*operands, geo.ref(), KINDS[kind], float(max_sigma), *gradients, _lib.current_stream()),
+               "lerf_resize_bwd_f32")
     return grads
 
 
@@ -685,62 +719,40 @@ def resize_planar_u8(feat_u8, hq_u8, geo: SrGeometry, kind="gauss", max_sigma=10
     ph, _keep = _hyper_planes(hq, "planar", nh)
     po = _planes_hwc(o)
     with _lib.on_device(o):
-        _lib.check(_lib.lib().lerf_resize(C.byref(pf), ph, H, W, N, geo.ref(), KINDS[kind], float(max_sigma),
-                                          C.byref(po), _lib.current_stream()), "lerf_resize")
+        _resize_call(geo, H, W, N, kind, max_sigma)(pf, ph, po)
     return o
 
 
 def warp_hwc_u8(feat_u8, hq_u8, geo: WarpGeometry, kind="gauss", max_sigma=10.0, out="u8"):
-    torch = _torch()
     feat = feat_u8.contiguous()
     Hb, W, Cn = feat.shape
     H = geo.in_hw[0]                                        # (a band of the frame from geo.src_y0 on: see WarpGeometry)
     if W != geo.in_hw[1] or geo.src_y0 + Hb > H:
         raise ValueError("the maps do not match the geometry's frame")
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
-    o = torch.empty((geo.out_hw[0], geo.out_hw[1], Cn), dtype=_out_dtype(out), device=feat.device)
-    pf = _planes_hwc(feat)
-    if nh:
-        hq = hq_u8.contiguous()
-        ph, _keep = _hyper_planes(hq, "hwck", nh)
-    else:
-        ph = None
-    po = _planes_hwc(o)
-    _lib.check(_lib.lib().lerf_warp(C.byref(pf), ph, H, W, Cn, geo.ref(), KINDS[kind], float(max_sigma),
-                                    C.byref(po), _lib.current_stream()), "lerf_warp")
-    return o
+    return _stage3_hwc(_warp_call(geo, H, W, Cn, kind, max_sigma), feat, hq_u8, kind, geo, out)
 
 
 def warp_planar(feat, hypers, geo: WarpGeometry, kind="gauss", max_sigma=10.0, out="f32"):
-    torch = _torch()
     feat = feat.contiguous().float()
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
     N, H, W = feat.shape
-    o = torch.empty((N, geo.out_hw[0], geo.out_hw[1]), dtype=_out_dtype(out), device=feat.device)
-    pf = _planes_chw(feat)
-    if nh:
-        hypers = [h.contiguous().float() for h in hypers[:nh]]
-        ph, _keep = _hyper_planes(hypers, "planar", nh)
-    else:
-        ph = None
-    po = _planes_chw(o)
-    _lib.check(_lib.lib().lerf_warp(C.byref(pf), ph, H, W, N, geo.ref(), KINDS[kind], float(max_sigma),
-                                    C.byref(po), _lib.current_stream()), "lerf_warp")
-    return o
+    return _stage3_planar(_warp_call(geo, H, W, N, kind, max_sigma), feat, hypers, kind, geo, out)
 
 
-def _remap_call(geo, device, pf, ph, H, W, planes, kind, max_sigma, po):
-    """lerf_remap, or lerf_remap_batched for a geometry with one map per sample (`planes` = n_maps * planes per map)"""
-    g, _keepc = geo.struct(device)
-    if geo.batched:
-        if planes % geo.n_maps:
-            raise ValueError("%d planes for %d maps: every map takes the same number of planes" % (planes, geo.n_maps))
-        _lib.check(_lib.lib().lerf_remap_batched(C.byref(pf), ph, H, W, planes, C.byref(g), geo.n_maps, geo.map_stride(device),
-                                                 planes // geo.n_maps, KINDS[kind], float(max_sigma), C.byref(po),
-                                                 _lib.current_stream()), "lerf_remap_batched")
-    else:
-        _lib.check(_lib.lib().lerf_remap(C.byref(pf), ph, H, W, planes, C.byref(g), KINDS[kind], float(max_sigma),
-                                         C.byref(po), _lib.current_stream()), "lerf_remap")
+def _remap_call(geo, device, H, W, planes, kind, max_sigma):
+    """lerf_remap, or lerf_remap_batched for a geometry with one map per sample (`planes` = n_maps * planes per map), on the image,
+    hyper and output planes"""
+    def call(pf, ph, po):
+        g, _keepc = geo.struct(device)
+        if geo.batched:
+            if planes % geo.n_maps:
+                raise ValueError("%d planes for %d maps: every map takes the same number of planes" % (planes, geo.n_maps))
+            _lib.check(_lib.lib().lerf_remap_batched(C.byref(pf), ph, H, W, planes, C.byref(g), geo.n_maps, geo.map_stride(device),
+                                                     planes // geo.n_maps, KINDS[kind], float(max_sigma), C.byref(po),
+                                                     _lib.current_stream()), "lerf_remap_batched")
+        else:
+            _lib.check(_lib.lib().lerf_remap(C.byref(pf), ph, H, W, planes, C.byref(g), KINDS[kind], float(max_sigma),
+                                             C.byref(po), _lib.current_stream()), "lerf_remap")
+    return call
 
 
 def remap_hwc_u8(feat_u8, hq_u8, geo: RemapGeometry, kind="gauss", max_sigma=10.0, out="u8"):
@@ -748,8 +760,8 @@ def remap_hwc_u8(feat_u8, hq_u8, geo: RemapGeometry, kind="gauss", max_sigma=10.
     [N,H,W,C], hq [N,H,W,C,oC], N == geo.n_maps -> [N,oH,oW,C] in ONE launch.  The C ABI strides planes by one step, so the
     frames are interleaved for it ([H,W,N,C]: plane n * C + c) and the output is copied back to frame-major."""
     torch = _torch()
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
     if geo.batched:
+        nh = _hyper_count(kind)
         if feat_u8.dim() != 4 or feat_u8.shape[0] != geo.n_maps:
             raise ValueError("a batched geometry takes [N,H,W,C] frames, one per map (N = %d)" % geo.n_maps)
         N, H, W, Cn = feat_u8.shape
@@ -764,67 +776,35 @@ def remap_hwc_u8(feat_u8, hq_u8, geo: RemapGeometry, kind="gauss", max_sigma=10.
             ph, _keep = _hyper_planes(hq, "hwck", nh)
         else:
             ph = None
-        _remap_call(geo, feat.device, _planes_hwc(feat), ph, H, W, N * Cn, kind, max_sigma, _planes_hwc(o))
+        _remap_call(geo, feat.device, H, W, N * Cn, kind, max_sigma)(_planes_hwc(feat), ph, _planes_hwc(o))
         return o.view(geo.out_hw[0], geo.out_hw[1], N, Cn).permute(2, 0, 1, 3).contiguous()
     feat = feat_u8.contiguous()
     H, W, Cn = feat.shape
     if (H, W) != geo.in_hw:
         raise ValueError("the maps do not match the geometry's frame")
-    o = torch.empty((geo.out_hw[0], geo.out_hw[1], Cn), dtype=_out_dtype(out), device=feat.device)
-    pf = _planes_hwc(feat)
-    if nh:
-        hq = hq_u8.contiguous()
-        ph, _keep = _hyper_planes(hq, "hwck", nh)
-    else:
-        ph = None
-    po = _planes_hwc(o)
-    _remap_call(geo, feat.device, pf, ph, H, W, Cn, kind, max_sigma, po)
-    return o
+    return _stage3_hwc(_remap_call(geo, feat.device, H, W, Cn, kind, max_sigma), feat, hq_u8, kind, geo, out)
 
 
 def remap_planar(feat, hypers, geo: RemapGeometry, kind="gauss", max_sigma=10.0, out="f32"):
     """warp_planar by a coordinate map (lerf_remap): float32 [N,H,W] planes -> [N,oH,oW].  A batched geometry (lerf_remap_batched):
     N = geo.n_maps * P, planes [b * P, (b + 1) * P) read map b."""
-    torch = _torch()
     feat = feat.contiguous().float()
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
     N, H, W = feat.shape
     if (H, W) != geo.in_hw:
         raise ValueError("the maps do not match the geometry's frame")
     if geo.batched and N % geo.n_maps:
         raise ValueError("%d planes for %d maps: every map takes the same number of planes" % (N, geo.n_maps))
-    o = torch.empty((N, geo.out_hw[0], geo.out_hw[1]), dtype=_out_dtype(out), device=feat.device)
-    pf = _planes_chw(feat)
-    if nh:
-        hypers = [h.contiguous().float() for h in hypers[:nh]]
-        ph, _keep = _hyper_planes(hypers, "planar", nh)
-    else:
-        ph = None
-    po = _planes_chw(o)
-    _remap_call(geo, feat.device, pf, ph, H, W, N, kind, max_sigma, po)
-    return o
+    return _stage3_planar(_remap_call(geo, feat.device, H, W, N, kind, max_sigma), feat, hypers, kind, geo, out)
 
 
 def warp_bwd_planar(feat, hypers, geo: WarpGeometry, kind, max_sigma, grad_out, grads):
     """lerf_warp_bwd: accumulate the gradients of warp_planar(feat, hypers, geo, kind, max_sigma, out="f64") for the
     float64 upstream gradient `grad_out` [N, oH, oW] into `grads` = [grad_feat, grad_h0, grad_h1, grad_h2] (float32
     [N, H, W] contiguous tensors, or None to skip a map).  feat / hypers: float32 [N, H, W]."""
-    feat = feat.contiguous().float()
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
-    hs = [h.contiguous().float() for h in hypers[:nh]]
-    g = grad_out.contiguous().double()
-    N, H, W = feat.shape
-    if tuple(g.shape) != (N, geo.out_hw[0], geo.out_hw[1]):
-        raise ValueError("grad_out must be [N, out_h, out_w] of the geometry")
-    grads = list(grads) + [None] * (4 - len(grads))
-    for t in grads:
-        if t is not None and (t.dtype != feat.dtype or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
-            raise ValueError("gradient buffers must be contiguous float32 [N, H, W]")
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-    hp = [ptr(h) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
-    _lib.check(_lib.lib().lerf_warp_bwd(ptr(feat), hp[0], hp[1], hp[2], N, H, W, geo.ref(), KINDS[kind], float(max_sigma),
-                                        ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]),
-                                        _lib.current_stream()), "lerf_warp_bwd")
+    feat, hs, g = _bwd_inputs(feat, hypers, kind, grad_out, double=True)
+    grads, operands, gradients = _bwd_buffers(feat, hs, g, geo, grads)
+    _lib.check(_lib.lib().lerf_warp_bwd(*operands, geo.ref(), KINDS[kind], float(max_sigma), *gradients, _lib.current_stream()),
+               "lerf_warp_bwd")
     return grads
 
 
@@ -835,36 +815,24 @@ def remap_bwd_planar(feat, hypers, geo: RemapGeometry, kind, max_sigma, grad_out
     [N, oH, oW, 2] contiguous, PER PLANE: the caller sums over the planes that share the map).  feat / hypers: float32
     [N, H, W].  A batched geometry (lerf_remap_bwd_batched): N = geo.n_maps * P, planes [b * P, (b + 1) * P) read map b."""
     torch = _torch()
-    feat = feat.contiguous().float()
-    nh = {"gauss": 3, "linear": 1}.get(kind, 0)
-    hs = [h.contiguous().float() for h in hypers[:nh]]
-    g = grad_out.contiguous().double()
+    feat, hs, g = _bwd_inputs(feat, hypers, kind, grad_out, double=True)
     N, H, W = feat.shape
     if (H, W) != geo.in_hw:
         raise ValueError("the maps do not match the geometry's frame")
     if geo.batched and N % geo.n_maps:
         raise ValueError("%d planes for %d maps: every map takes the same number of planes" % (N, geo.n_maps))
-    if tuple(g.shape) != (N, geo.out_hw[0], geo.out_hw[1]):
-        raise ValueError("grad_out must be [N, out_h, out_w] of the geometry")
-    grads = list(grads) + [None] * (4 - len(grads))
-    for t in grads:
-        if t is not None and (t.dtype != feat.dtype or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
-            raise ValueError("gradient buffers must be contiguous float32 [N, H, W]")
+    grads, operands, gradients = _bwd_buffers(feat, hs, g, geo, grads)
     if grad_coords is not None and (grad_coords.dtype != torch.float64 or tuple(grad_coords.shape) != (N,) + tuple(geo.out_hw) + (2,)
                                     or not grad_coords.is_contiguous()):
         raise ValueError("grad_coords must be contiguous float64 [N, out_h, out_w, 2]")
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-    hp = [ptr(h) for h in hs] + [C.c_void_p(None)] * (3 - len(hs))
     gs, _keepc = geo.struct(feat.device)
     if geo.batched:
-        _lib.check(_lib.lib().lerf_remap_bwd_batched(ptr(feat), hp[0], hp[1], hp[2], N, H, W, C.byref(gs), geo.n_maps,
-                                                     geo.map_stride(feat.device), N // geo.n_maps, KINDS[kind], float(max_sigma),
-                                                     ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]),
-                                                     ptr(grad_coords), _lib.current_stream()), "lerf_remap_bwd_batched")
-        return grads
-    _lib.check(_lib.lib().lerf_remap_bwd(ptr(feat), hp[0], hp[1], hp[2], N, H, W, C.byref(gs), KINDS[kind], float(max_sigma),
-                                         ptr(g), ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]), ptr(grad_coords),
-                                         _lib.current_stream()), "lerf_remap_bwd")
+        _lib.check(_lib.lib().lerf_remap_bwd_batched(*operands, C.byref(gs), geo.n_maps, geo.map_stride(feat.device), N // geo.n_maps,
+                                                     KINDS[kind], float(max_sigma), *gradients, _ptr(grad_coords),
+                                                     _lib.current_stream()), "lerf_remap_bwd_batched")
+    else:
+        _lib.check(_lib.lib().lerf_remap_bwd(*operands, C.byref(gs), KINDS[kind], float(max_sigma), *gradients, _ptr(grad_coords),
+                                             _lib.current_stream()), "lerf_remap_bwd")
     return grads
 
 
