@@ -767,6 +767,51 @@ int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, in
                             void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
                             int max_iter, double tol);
 
+/* Adjoints of lerf_coords_compose and lerf_coords_invert (the rounding order of every statement: the top of
+ * csrc/lerf_coords_models.h).  a, b, f, g obey the strided map contract, LERF_F32 / LERF_F64 in any mix, promoted exactly on
+ * load; aH, aW, fH, fW >= 2, so the four corners of a cell are inside the map.  grad_out [oH][oW][2], grad_a [aH][aW][2], grad_b
+ * [oH][oW][2] and grad_f [fH][fW][2] are dense float64, 16-byte aligned, and the gradients are ACCUMULATED into (the contract of
+ * lerf_remap_bwd's grad_coords and of lerf_coords_mesh_bwd: the caller zeroes them).
+ *
+ * Compose, one entry with inner point (row, col) = b[i][j] and upstream g = grad_out[i][j]: a NaN in row or col contributes
+ * nothing, whatever g holds -- nothing of a is read, nothing is scattered, grad_b gains (0, 0).  Else, with the forward's cell
+ * and weights (lerf_coords_compose's per-axis rule),
+ *   grad_a[i0 + p][j0 + q] += (wr[p] wc[q]) g  for the taps with wr[p] != 0 and wc[q] != 0 (the forward's rule: a tap of weight
+ *                             exactly 0 gets nothing and forms no address; a position clipped onto the border still scatters to
+ *                             the border taps the forward read);
+ *   grad_b[i][j] += (pass_r ? Jr . g : 0, pass_c ? Jc . g : 0), Jr = dC/drow and Jc = dC/dcol of the bilinear patch formed from
+ *                             ALL FOUR corners of the cell, whatever their weights (lerf_coords_invert's Jacobian statements), and
+ *                             pass_r = (0 <= row <= aH - 1), pass_c alike: torch.clamp's backward, a select -- the border passes,
+ *                             outside and +-inf are blocked even when the sum behind is NaN.  This is the derivative of the
+ *                             plain bilinear formula with the cell held constant: at an integer position it is that of cell
+ *                             min(floor(r), n - 2), and a NaN corner gives a NaN entry of grad_b.
+ * grad_a or grad_b may be NULL to skip that half (no atomics / no loads of a); both NULL is refused.
+ *
+ * Invert, one entry (r, c) = g[i][j] of the inverse (what lerf_coords_invert wrote for f) with upstream grad_out[i][j]: by the
+ * implicit function theorem on F(G[q]) = q, grad_f gains the same bilinear scatter, at the cell of (r, c), of v = -J^-T g (J the
+ * Jacobian above, solved by Cramer's rule).  A NaN in (r, c), a NaN among the four corners read, or a determinant that is 0 or
+ * not finite contributes nothing.  init, max_iter and tol have no gradient.
+ *
+ * How the sums are formed: grad_b has ONE writer per entry, a plain 16-byte load-add-store -- bit-equal from run to run and to
+ * the host twin.  grad_a and grad_f are data-dependent scatters: float64 atomic adds to global memory, so they are equal from run
+ * to run (and to the host twin's row-major order) up to the rounding of a reordered float64 sum, not bit for bit -- like the image
+ * and hyper gradients of lerf_remap_bwd.  The gradient buffers are ordinary (coarse-grained) device memory.  One launch, one
+ * thread per entry, no sync, no allocation, no workspace, no global state.  Refused in addition to the family's list: aH, aW, fH
+ * or fW < 2; grad_a and grad_b both NULL; a gradient buffer whose bytes intersect an operand's, grad_out's or the other gradient
+ * buffer's. */
+int lerf_coords_compose_bwd(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                            const void* b, int b_dtype, int64_t b_row_stride,
+                            const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, void* stream);
+int lerf_coords_compose_bwd_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                 const void* b, int b_dtype, int64_t b_row_stride,
+                                 const double* grad_out, int oH, int oW, double* grad_a, double* grad_b);
+int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                           const void* g, int g_dtype, int64_t g_row_stride,
+                           const double* grad_out, int oH, int oW, double* grad_f, void* stream);
+int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                const void* g, int g_dtype, int64_t g_row_stride,
+                                const double* grad_out, int oH, int oW, double* grad_f);
+
 #ifdef __cplusplus
 }
 #endif

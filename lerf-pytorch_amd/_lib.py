@@ -56,6 +56,7 @@ EXPORTS = [
     "lerf_rr_axis", "lerf_rr_adjoint_csr", "lerf_patch_batch_u8",
     "lerf_coords_build", "lerf_coords_build_host", "lerf_coords_mesh", "lerf_coords_mesh_host", "lerf_coords_mesh_bwd_workspace_bytes",
     "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host", "lerf_coords_invert", "lerf_coords_invert_host",
+    "lerf_coords_compose_bwd", "lerf_coords_compose_bwd_host", "lerf_coords_invert_bwd", "lerf_coords_invert_bwd_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -304,6 +305,10 @@ def lib():
     _invert = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                C.c_int, C.c_int, C.c_int, C.c_double]
     L.lerf_coords_invert.argtypes, L.lerf_coords_invert_host.argtypes = _invert + [C.c_void_p], _invert
+    _compose_bwd = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _invert_bwd = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.lerf_coords_compose_bwd.argtypes, L.lerf_coords_compose_bwd_host.argtypes = _compose_bwd + [C.c_void_p], _compose_bwd
+    L.lerf_coords_invert_bwd.argtypes, L.lerf_coords_invert_bwd_host.argtypes = _invert_bwd + [C.c_void_p], _invert_bwd
     L.lerf_coords_mesh_bwd_workspace_bytes.restype = C.c_size_t
     L.lerf_coords_mesh_bwd_workspace_bytes.argtypes = [C.c_int] * 4
     L.lerf_coords_mesh_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -484,6 +489,46 @@ def coords_invert_host(f, out_hw, init=None, dtype=np.float64, out=None, origin=
                                         LERF_F64 if b is None else _np_dt(b), sb, out.ctypes.data, _np_dt(out), so, out.shape[0],
                                         out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol)), "lerf_coords_invert_host")
     return out
+
+
+def _np_grad(g, shape, what):
+    """a dense float64 gradient buffer [h, w, 2] on the host (None: a zeroed one)"""
+    if g is None:
+        return np.zeros(shape, np.float64)
+    if not isinstance(g, np.ndarray) or g.dtype != np.float64 or tuple(g.shape) != tuple(shape) or not g.flags.c_contiguous:
+        raise ValueError("%s must be a C-contiguous float64 array %s" % (what, list(shape)))
+    return g
+
+
+def coords_compose_bwd_host(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):
+    """lerf_coords_compose_bwd_host: ACCUMULATE the adjoint of compose(outer, inner) of the float64 grad_out [oH, oW, 2] into
+    grad_outer [aH, aW, 2] and grad_inner [oH, oW, 2] (None: zeroed ones; need[k] False: that half is skipped and None is
+    returned for it) -> (grad_outer, grad_inner)."""
+    a, sa = _np_map(outer, "outer")
+    b, sb = _np_map(inner, "inner")
+    if grad_out is None:
+        raise ValueError("grad_out must be a C-contiguous float64 array")
+    g = _np_grad(grad_out, b.shape, "grad_out")
+    ga = _np_grad(grad_outer, a.shape, "grad_outer") if need[0] else None
+    gb = _np_grad(grad_inner, b.shape, "grad_inner") if need[1] else None
+    check(lib().lerf_coords_compose_bwd_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
+                                             g.ctypes.data, b.shape[0], b.shape[1], None if ga is None else ga.ctypes.data,
+                                             None if gb is None else gb.ctypes.data), "lerf_coords_compose_bwd_host")
+    return ga, gb
+
+
+def coords_invert_bwd_host(f, inverse, grad_out, grad_f=None):
+    """lerf_coords_invert_bwd_host: ACCUMULATE the implicit-function adjoint of inverse = invert(f) of the float64 grad_out
+    [oH, oW, 2] into grad_f [fH, fW, 2] (None: a zeroed one)."""
+    a, sa = _np_map(f, "f")
+    b, sb = _np_map(inverse, "inverse")
+    if grad_out is None:
+        raise ValueError("grad_out must be a C-contiguous float64 array")
+    g = _np_grad(grad_out, b.shape, "grad_out")
+    gf = _np_grad(grad_f, a.shape, "grad_f")
+    check(lib().lerf_coords_invert_bwd_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
+                                            g.ctypes.data, b.shape[0], b.shape[1], gf.ctypes.data), "lerf_coords_invert_bwd_host")
+    return gf
 
 
 # ------------------------------------------------------------------ device plumbing

@@ -11,6 +11,12 @@ entry, no host array, no upload): from_homography, radial, undistort_rectify, fr
 in the autograd graph through the mesh upsample's adjoint, compose chains two maps into one, and invert / invert_flow solve a
 map for its inverse (distort <-> undistort, forward flow -> backward map).  The kernels' arithmetic is
 float64 with + - * / only, bit-equal to its host twin (csrc/lerf_coords_models.h).
+
+compose, invert and invert_flow refuse operands that require grad.  Their opt-in twins compose_torch, invert_torch and
+invert_flow_torch (device tensors only) run the same forward kernels and keep the maps in the autograd graph through the HIP
+adjoints lerf_coords_compose_bwd and lerf_coords_invert_bwd, so a loss reaches a flow or a control mesh through
+chained maps: coarse-to-fine refinement (compose_torch(upsampled, residual)), scaling and squaring (compose_torch(phi, phi)),
+inverse-consistency losses (invert_torch).  Once differentiable; init, max_iter and tol have no gradient.
 """
 from __future__ import annotations
 
@@ -260,14 +266,14 @@ def compose(outer, inner, dtype=None):
     through the LUT stages and one interpolation instead of two.  Positions outside the outer map are clipped onto its border;
     a NaN entry of the inner map stays (NaN, NaN).  numpy in -> numpy out (the kernel's host twin); device tensors in -> a
     device tensor; mixed operands are refused.  dtype: default the inner map's.  No autograd: an operand that requires grad
-    (with grad mode on) is refused."""
+    (with grad mode on) is refused -- compose_torch is the differentiable twin."""
     dev = [bool(getattr(t, "is_cuda", False)) for t in (outer, inner)]
     if dev[0] != dev[1]:
         raise ValueError("compose: both maps on the host or both on one device, not mixed")
     if any(getattr(t, "requires_grad", False) for t in (outer, inner)):
         import torch
         if torch.is_grad_enabled():
-            raise ValueError("compose has no autograd: detach() the maps (or call it under torch.no_grad())")
+            raise ValueError("compose has no autograd: use compose_torch, or detach() the maps (or call it under torch.no_grad())")
     if dev[0]:
         import torch
         from . import ops
@@ -293,7 +299,7 @@ def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
     numpy in -> numpy out (the kernel's host twin, bit-equal); device tensors in -> a device tensor; mixed map / init is refused.
     dtype: default the map's.  A batch [B, fH, fW, 2] (init [B, H, W, 2] or None) gives [B, H, W, 2]: one launch per map into the
     slices of one output tensor -- a single batched launch is not implemented.  No autograd: an operand that requires grad (with
-    grad mode on) is refused."""
+    grad mode on) is refused -- invert_torch is the differentiable twin."""
     ops_ = [t for t in (map, init) if t is not None]
     dev = [bool(getattr(t, "is_cuda", False)) for t in ops_]
     if any(d != dev[0] for d in dev):
@@ -301,7 +307,7 @@ def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
     if any(getattr(t, "requires_grad", False) for t in ops_):
         import torch
         if torch.is_grad_enabled():
-            raise ValueError("invert has no autograd: detach() the maps (or call it under torch.no_grad())")
+            raise ValueError("invert has no autograd: use invert_torch, or detach() the maps (or call it under torch.no_grad())")
     H, W = int(in_hw[0]), int(in_hw[1])
     if H < 1 or W < 1:
         raise ValueError("in_hw must be positive")
@@ -313,13 +319,7 @@ def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
     if dev[0]:
         import torch
         from . import ops
-        tdt = map.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
-        if nd == 3:
-            return ops.coords_invert(map, (H, W), init=init, dtype=tdt, max_iter=max_iter, tol=tol)
-        out = torch.empty((map.shape[0], H, W, 2), dtype=tdt, device=map.device)
-        for n in range(map.shape[0]):
-            ops.coords_invert(map[n], (H, W), init=None if init is None else init[n], out=out[n], max_iter=max_iter, tol=tol)
-        return out
+        return _invert_dev(map, (H, W), init, max_iter, tol, map.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name))
     from . import _lib
     a, b = (None if t is None else np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (map, init))
     a, b = (t if t is None or t.dtype in (np.float32, np.float64) else t.astype(np.float64) for t in (a, b))
@@ -332,25 +332,179 @@ def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
     return out
 
 
+def _invert_dev(map, hw, init, max_iter, tol, tdt):
+    """invert on the device: one map, or one launch per map of a batch into the slices of one output tensor"""
+    import torch
+    from . import ops
+    if map.ndim == 3:
+        return ops.coords_invert(map, hw, init=init, dtype=tdt, max_iter=max_iter, tol=tol)
+    out = torch.empty((map.shape[0], hw[0], hw[1], 2), dtype=tdt, device=map.device)
+    for n in range(map.shape[0]):
+        ops.coords_invert(map[n], hw, init=None if init is None else init[n], out=out[n], max_iter=max_iter, tol=tol)
+    return out
+
+
 def invert_flow(flow, init=None, max_iter=16, tol=1e-9):
     """The backward flow of a forward flow: flow [H, W, 2] (or a batch [B, H, W, 2]) = (d_row, d_col) of every pixel, numpy or a
     device tensor -> b = invert(identity + flow, (H, W)) - identity, in the flow's dtype and place, so that the map identity + flow
     read at identity + b is the identity (within tol); NaN where no pixel of the flow lands.  init, max_iter, tol: invert's (init
-    is a MAP of starting positions, not a flow).  No autograd."""
+    is a MAP of starting positions, not a flow).  No autograd (invert_flow_torch is the differentiable twin)."""
     if getattr(flow, "ndim", None) not in (3, 4) or flow.shape[-1] != 2:
         raise ValueError("flow must be [H, W, 2] or [B, H, W, 2]")
     H, W = int(flow.shape[-3]), int(flow.shape[-2])
     if getattr(flow, "is_cuda", False):
         import torch
         if flow.requires_grad and torch.is_grad_enabled():
-            raise ValueError("invert has no autograd: detach() the maps (or call it under torch.no_grad())")
+            raise ValueError("invert has no autograd: use invert_torch, or detach() the maps (or call it under torch.no_grad())")
         ident = from_flow_torch(torch.zeros((H, W, 2), dtype=flow.dtype, device=flow.device))
         return invert(ident + flow.detach(), (H, W), init=init, max_iter=max_iter, tol=tol) - ident
     if getattr(flow, "requires_grad", False):
         import torch
         if torch.is_grad_enabled():
-            raise ValueError("invert has no autograd: detach() the maps (or call it under torch.no_grad())")
+            raise ValueError("invert has no autograd: use invert_torch, or detach() the maps (or call it under torch.no_grad())")
     f = np.asarray(flow.detach().numpy() if hasattr(flow, "detach") else flow)
     f = f if f.dtype in (np.float32, np.float64) else f.astype(np.float64)
     ident = from_flow(np.zeros((H, W, 2))).astype(f.dtype)
     return invert(ident + f, (H, W), init=init, max_iter=max_iter, tol=tol) - ident
+
+
+# ---------------------------------------------------------------------------------------------- differentiable twins
+def _compose_dev(outer, inner, tdt):
+    """compose on the device: one pair, or one launch per sample of a batch (outer [B, aH, aW, 2] or one shared [aH, aW, 2])"""
+    import torch
+    from . import ops
+    if inner.ndim == 3:
+        return ops.coords_compose(outer, inner, dtype=tdt)
+    out = torch.empty(tuple(inner.shape), dtype=tdt, device=inner.device)
+    for n in range(inner.shape[0]):
+        ops.coords_compose(outer if outer.ndim == 3 else outer[n], inner[n], out=out[n])
+    return out
+
+
+_CHAIN_FNS = None
+
+
+def _chain_fns():
+    global _CHAIN_FNS
+    if _CHAIN_FNS is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+        from . import ops
+
+        class _ComposeFn(torch.autograd.Function):
+            """C = compose(outer, inner); backward: ops.coords_compose_bwd in float64, one launch per sample, a shared outer map's
+            gradient summed into one buffer; each gradient cast to its operand's dtype"""
+
+            @staticmethod
+            def forward(ctx, outer, inner, tdt):
+                ctx.save_for_backward(outer, inner)
+                return _compose_dev(outer.detach(), inner.detach(), tdt)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                outer, inner = ctx.saved_tensors
+                need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+                g = grad.contiguous().double()
+                ga = torch.zeros(tuple(outer.shape), dtype=torch.float64, device=g.device) if need[0] else None
+                gb = torch.zeros(tuple(inner.shape), dtype=torch.float64, device=g.device) if need[1] else None
+                if inner.ndim == 3:
+                    ops.coords_compose_bwd(outer, inner, g, ga, gb, need)
+                else:
+                    for n in range(inner.shape[0]):
+                        ops.coords_compose_bwd(outer if outer.ndim == 3 else outer[n], inner[n], g[n],
+                                               ga if ga is None or outer.ndim == 3 else ga[n], None if gb is None else gb[n], need)
+                return None if ga is None else ga.to(outer.dtype), None if gb is None else gb.to(inner.dtype), None
+
+        class _InvertFn(torch.autograd.Function):
+            """G = invert(map); backward: ops.coords_invert_bwd in float64 at the saved inverse (the implicit function theorem), cast
+            to the map's dtype; init is a constant"""
+
+            @staticmethod
+            def forward(ctx, map, init, hw, max_iter, tol, tdt):
+                out = _invert_dev(map.detach(), hw, None if init is None else init.detach(), max_iter, tol, tdt)
+                ctx.save_for_backward(map, out)
+                return out
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                map, out = ctx.saved_tensors
+                g = grad.contiguous().double()
+                gf = torch.zeros(tuple(map.shape), dtype=torch.float64, device=g.device)
+                if map.ndim == 3:
+                    ops.coords_invert_bwd(map, out, g, gf)
+                else:
+                    for n in range(map.shape[0]):
+                        ops.coords_invert_bwd(map[n], out[n], g[n], gf[n])
+                return gf.to(map.dtype), None, None, None, None, None
+
+        _CHAIN_FNS = (_ComposeFn, _InvertFn)
+    return _CHAIN_FNS
+
+
+def _device_map(t, what, batch=True):
+    """a floating-point device tensor [h, w, 2] (or [B, h, w, 2]) or ValueError"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_floating_point():
+        raise ValueError("%s must be a floating-point device tensor" % what)
+    if t.ndim not in ((3, 4) if batch else (3,)) or t.shape[-1] != 2:
+        raise ValueError("%s must be [h, w, 2]%s" % (what, " or [B, h, w, 2]" if batch else ""))
+    return t
+
+
+def compose_torch(outer, inner, dtype=None):
+    """compose on the maps' device, differentiable: C[i, j] = outer(inner[i, j]) by the same kernel (bit-equal to compose when
+    grad mode is off or no operand requires grad); an operand that requires grad stays in the graph through
+    lerf_coords_compose_bwd: the outer map's gradient is the bilinear scatter of the upstream gradient (float64 atomic adds), the
+    inner map's is J^T g with the clip's gradient that of torch.clamp (it passes on the border, blocks outside) and the cell held
+    constant at integer positions.  Floating-point device tensors only; dtype: C's, default the inner map's; each gradient is
+    computed in float64 and cast to its operand's dtype.  A batch: inner [B, H, W, 2] with outer [B, aH, aW, 2] or one shared
+    [aH, aW, 2] (its gradient is the sum over the samples) -- one launch per sample.  compose_torch(phi, phi) returns the sum of
+    both gradients to phi.  The differentiable path needs an outer map of at least 2 x 2.  Once differentiable."""
+    import torch
+    a, b = _device_map(outer, "compose_torch: outer"), _device_map(inner, "compose_torch: inner")
+    if a.device != b.device:
+        raise ValueError("compose_torch: outer and inner live on different devices")
+    if a.ndim == 4 and (b.ndim != 4 or a.shape[0] != b.shape[0]):
+        raise ValueError("compose_torch: a batch of outer maps needs a batch of as many inner maps")
+    tdt = b.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
+    if not (torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)):
+        return _compose_dev(a.detach(), b.detach(), tdt)
+    if a.shape[-3] < 2 or a.shape[-2] < 2:
+        raise ValueError("compose_torch: the gradient needs an outer map of at least 2 x 2")
+    return _chain_fns()[0].apply(a, b, tdt)
+
+
+def invert_torch(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
+    """invert on the map's device, differentiable: the same Newton kernel (bit-equal to invert when grad mode is off or the map
+    does not require grad); a map that requires grad stays in the graph through lerf_coords_invert_bwd, the implicit-function
+    gradient of map(G[q]) = q at the inverse returned: the bilinear scatter of -J^-T g.  Entries of the inverse that are NaN, cells
+    with a NaN corner and folded cells contribute nothing.  init is a constant (no gradient), as are max_iter and tol.
+    Floating-point device tensors only; a batch [B, fH, fW, 2] (init [B, H, W, 2]) runs one launch per map.  The gradient is
+    computed in float64 and cast to the map's dtype.  Once differentiable."""
+    import torch
+    a = _device_map(map, "invert_torch: map")
+    H, W = int(in_hw[0]), int(in_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("in_hw must be positive")
+    if init is not None:
+        b = _device_map(init, "invert_torch: init")
+        if b.device != a.device:
+            raise ValueError("invert_torch: map and init live on different devices")
+        if b.ndim != a.ndim or tuple(b.shape[-3:-1]) != (H, W) or (a.ndim == 4 and b.shape[0] != a.shape[0]):
+            raise ValueError("invert_torch: init is [H, W, 2], or [B, H, W, 2] for a batch of B maps")
+    tdt = a.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
+    if not (torch.is_grad_enabled() and a.requires_grad):
+        return _invert_dev(a.detach(), (H, W), None if init is None else init.detach(), max_iter, tol, tdt)
+    return _chain_fns()[1].apply(a, init, (H, W), int(max_iter), float(tol), tdt)
+
+
+def invert_flow_torch(flow, init=None, max_iter=16, tol=1e-9):
+    """invert_flow on the flow's device, differentiable: b = invert_torch(identity + flow, (H, W)) - identity in the flow's
+    dtype; a flow that requires grad receives its gradient through lerf_coords_invert_bwd.  init, max_iter, tol: invert_torch's."""
+    import torch
+    f = _device_map(flow, "invert_flow_torch: flow")
+    H, W = int(f.shape[-3]), int(f.shape[-2])
+    ident = from_flow_torch(torch.zeros((H, W, 2), dtype=f.dtype, device=f.device))
+    return invert_torch(ident + f, (H, W), init=init, max_iter=max_iter, tol=tol) - ident

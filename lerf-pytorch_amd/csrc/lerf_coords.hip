@@ -27,12 +27,24 @@
 //       (mesh_reach); rows without a tap on a weigh exactly 0 and are skipped, so the transpose is exact, clamped border taps
 //       of the bicubic included.  A 33 x 61 mesh under 2160 x 3840: 270 rows per vertex row in pass 1 (68 per wave), 252 columns per
 //       vertex in pass 2 (4 per lane); grad_map is read 4 times (bicubic) or twice (bilinear), coalesced, tmp is 2 MB.
+//   coords_compose_bwd_kernel<TA, TB>       the adjoint of compose, one thread per entry (compose_bwd_point): one load of B and of
+//                                           grad_out; the inner gradient reads the four corners of the cell of A and has ONE writer per
+//                                           entry -- a plain 16-byte load-add-store into grad_b, bit-equal from run to run and to the host
+//                                           twin; the outer gradient is a data-dependent bilinear scatter: up to four taps, two float64
+//                                           atomicAdd each, into grad_a in global memory -- equal from run to run up to the rounding of a
+//                                           reordered float64 sum, like the image and hyper gradients of lerf_remap_bwd.  A null grad_a
+//                                           issues no atomics, a null grad_b no loads of A.  No LDS, no workspace.
+//   coords_invert_bwd_kernel<TF, TG>        the adjoint of invert by the implicit function theorem (invert_bwd_point): one load of G and
+//                                           of grad_out, the four corners of one cell of F, the 2 x 2 solve v = -J^-T g, the same scatter
+//                                           of v into grad_f (float64 atomicAdd)
 //
 // Addresses: every kernel guards (i, j) against the tile, writes entry (i, j) of `out` only, and reads ctrl / A at indices that
 // mesh_axis / compose_axis clamp into the operand after clipping the position in floating point (no value of B reaches an int
 // conversion unclipped).  The inverse reads init at entry (i, j) only and F at the three corners of its start and at cells
 // compose_axis picks for the iterate (fH, fW >= 2, so i0 + 1 <= fH - 1), whatever F, init or the iterate hold.  The passes of the
-// adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].
+// adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].  The adjoints of compose and invert read
+// B / G, grad_out and grad_b at entry (i, j) only, and read A / F and add into grad_a / grad_f at the cell compose_axis picks (aH, aW,
+// fH, fW >= 2 are checked on the host, so i0 + 1 <= n - 1), whatever the maps hold.
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
 
@@ -158,6 +170,60 @@ coords_mesh_bwd_cols_kernel(const double2* __restrict__ tmp, int oW, int gw, dou
     }
 }
 
+// the scatter of the device side: grad [h][w][2] dense float64, two atomic adds per tap
+struct AtomicAdd2 {
+    double* grad;
+    int w;
+    __device__ void operator()(int r, int c, double dr, double dc) const {
+        double* p = grad + 2 * ((int64_t)r * w + c);
+        atomicAdd(p, dr);
+        atomicAdd(p + 1, dc);
+    }
+};
+
+// the host twin's: a plain add
+struct PlainAdd2 {
+    double* grad;
+    int w;
+    void operator()(int r, int c, double dr, double dc) const {
+        double* p = grad + 2 * ((int64_t)r * w + c);
+        p[0] += dr;
+        p[1] += dc;
+    }
+};
+
+// gA == nullptr: no scatter; gB == nullptr: A is not read
+template <typename TA, typename TB>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_compose_bwd_kernel(const TA* __restrict__ A, int64_t a_stride, int aH, int aW, const TB* __restrict__ B, int64_t b_stride,
+                          const double2* __restrict__ gout, int oH, int oW, double* __restrict__ gA, double2* __restrict__ gB) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= oH || j >= oW) return;
+    const Point q = load_entry(B, b_stride, i, j);
+    const double2 g = gout[(int64_t)i * oW + j];
+    const Point d = compose_bwd_point(q.r, q.c, Point{g.x, g.y}, aH, aW, gA != nullptr, gB != nullptr,
+                                      [&](int r, int c) { return load_entry(A, a_stride, r, c); }, AtomicAdd2{gA, aW});
+    if (gB) {
+        double2* dst = gB + (int64_t)i * oW + j;
+        double2 v = *dst;
+        v.x += d.r;
+        v.y += d.c;
+        *dst = v;
+    }
+}
+
+template <typename TF, typename TG>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_invert_bwd_kernel(const TF* __restrict__ F, int64_t f_stride, int fH, int fW, const TG* __restrict__ G, int64_t g_stride,
+                         const double2* __restrict__ gout, int oH, int oW, double* __restrict__ gF) {
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= oH || j >= oW) return;
+    const Point u = load_entry(G, g_stride, i, j);
+    const double2 g = gout[(int64_t)i * oW + j];
+    invert_bwd_point(u.r, u.c, Point{g.x, g.y}, fH, fW, [&](int r, int c) { return load_entry(F, f_stride, r, c); }, AtomicAdd2{gF, fW});
+}
+
 // ------------------------------------------------------------------------------------------------ argument checks (host)
 inline bool float_dtype(int dt) { return dt == LERF_F32 || dt == LERF_F64; }
 inline size_t entry_bytes(int dt) { return dt == LERF_F32 ? 8 : 16; }
@@ -213,6 +279,43 @@ inline int invert_args(const void* f, int f_dtype, int64_t f_stride, int fH, int
     if (!tile_ok(oH, oW, i0, j0) || max_iter < 1 || max_iter > 64 || !(tol >= 0.0) || !std::isfinite(tol)) return LERF_EINVAL;
     if (maps_overlap(out, out_dtype, o_stride, oH, oW, f, f_dtype, f_stride, fH, fW)) return LERF_EINVAL;
     if (init && (!map_ok(init, init_dtype, i_stride, oH, oW) || maps_overlap(out, out_dtype, o_stride, oH, oW, init, init_dtype, i_stride, oH, oW)))
+        return LERF_EINVAL;
+    return LERF_OK;
+}
+
+// a dense float64 gradient [h][w][2]
+inline bool dense_ok(const void* p) { return p && (size_t)(uintptr_t)p % 16 == 0; }
+inline bool dense_overlaps_map(const void* d, int h, int w, const void* q, int qdt, int64_t qs, int qh, int qw) {
+    return maps_overlap(d, LERF_F64, 2 * (int64_t)w, h, w, q, qdt, qs, qh, qw);
+}
+inline bool dense_overlap(const void* d, int h, int w, const void* e, int eh, int ew) {
+    return dense_overlaps_map(d, h, w, e, LERF_F64, 2 * (int64_t)ew, eh, ew);
+}
+
+inline int compose_bwd_args(const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
+                            const double* grad_out, int oH, int oW, const double* grad_a, const double* grad_b) {
+    if (!map_ok(a, a_dtype, a_stride, aH, aW) || aH < 2 || aW < 2 || !map_ok(b, b_dtype, b_stride, oH, oW) || !tile_ok(oH, oW, 0, 0))
+        return LERF_EINVAL;
+    if (!dense_ok(grad_out) || (!grad_a && !grad_b) || (grad_a && !dense_ok(grad_a)) || (grad_b && !dense_ok(grad_b))) return LERF_EINVAL;
+    const void* grads[2] = {grad_a, grad_b};
+    const int gh[2] = {aH, oH}, gw[2] = {aW, oW};
+    for (int k = 0; k < 2; ++k) {
+        if (!grads[k]) continue;
+        if (dense_overlaps_map(grads[k], gh[k], gw[k], a, a_dtype, a_stride, aH, aW) ||
+            dense_overlaps_map(grads[k], gh[k], gw[k], b, b_dtype, b_stride, oH, oW) || dense_overlap(grads[k], gh[k], gw[k], grad_out, oH, oW))
+            return LERF_EINVAL;
+    }
+    if (grad_a && grad_b && dense_overlap(grad_a, aH, aW, grad_b, oH, oW)) return LERF_EINVAL;
+    return LERF_OK;
+}
+
+inline int invert_bwd_args(const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_stride,
+                           const double* grad_out, int oH, int oW, const double* grad_f) {
+    if (!map_ok(f, f_dtype, f_stride, fH, fW) || fH < 2 || fW < 2 || !map_ok(g, g_dtype, g_stride, oH, oW) || !tile_ok(oH, oW, 0, 0))
+        return LERF_EINVAL;
+    if (!dense_ok(grad_out) || !dense_ok(grad_f)) return LERF_EINVAL;
+    if (dense_overlaps_map(grad_f, fH, fW, f, f_dtype, f_stride, fH, fW) || dense_overlaps_map(grad_f, fH, fW, g, g_dtype, g_stride, oH, oW) ||
+        dense_overlap(grad_f, fH, fW, grad_out, oH, oW))
         return LERF_EINVAL;
     return LERF_OK;
 }
@@ -326,6 +429,32 @@ int lerf_coords_invert(const void* f, int f_dtype, int64_t f_row_stride, int fH,
     return launch_status();
 }
 
+int lerf_coords_compose_bwd(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
+                            const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, void* stream) {
+    const int rc = compose_bwd_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
+    hipStream_t st = (hipStream_t)stream;
+    LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB,
+        hipLaunchKernelGGL((coords_compose_bwd_kernel<TA, TB>), grid, block, 0, st, (const TA*)a, a_row_stride, aH, aW, (const TB*)b,
+                           b_row_stride, reinterpret_cast<const double2*>(grad_out), oH, oW, grad_a, reinterpret_cast<double2*>(grad_b))));
+    return launch_status();
+}
+
+int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_row_stride,
+                           const double* grad_out, int oH, int oW, double* grad_f, void* stream) {
+    const int rc = invert_bwd_args(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
+    hipStream_t st = (hipStream_t)stream;
+    LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(g_dtype, TG,
+        hipLaunchKernelGGL((coords_invert_bwd_kernel<TF, TG>), grid, block, 0, st, (const TF*)f, f_row_stride, fH, fW, (const TG*)g,
+                           g_row_stride, reinterpret_cast<const double2*>(grad_out), oH, oW, grad_f)));
+    return launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------ host twins: the same functions, a plain loop
 int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
                            int i0, int j0) {
@@ -388,6 +517,44 @@ int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, in
                 v = invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, load);
             });
             LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, out_row_stride, i, j, v));
+        }
+    return LERF_OK;
+}
+
+int lerf_coords_compose_bwd_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                 int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
+#pragma clang fp contract(off)
+    const int rc = compose_bwd_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
+    if (rc != LERF_OK) return rc;
+    for (int i = 0; i < oH; ++i)
+        for (int j = 0; j < oW; ++j) {
+            const int64_t e = 2 * ((int64_t)i * oW + j);
+            Point q, d;
+            LERF_COORDS_DT(b_dtype, TB, q = load_entry((const TB*)b, b_row_stride, i, j));
+            LERF_COORDS_DT(a_dtype, TA, d = compose_bwd_point(q.r, q.c, Point{grad_out[e], grad_out[e + 1]}, aH, aW, grad_a != nullptr,
+                                                              grad_b != nullptr,
+                                                              [&](int r, int c) { return load_entry((const TA*)a, a_row_stride, r, c); },
+                                                              PlainAdd2{grad_a, aW}));
+            if (grad_b) {
+                grad_b[e] += d.r;
+                grad_b[e + 1] += d.c;
+            }
+        }
+    return LERF_OK;
+}
+
+int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f) {
+    const int rc = invert_bwd_args(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
+    if (rc != LERF_OK) return rc;
+    for (int i = 0; i < oH; ++i)
+        for (int j = 0; j < oW; ++j) {
+            const int64_t e = 2 * ((int64_t)i * oW + j);
+            Point u;
+            LERF_COORDS_DT(g_dtype, TG, u = load_entry((const TG*)g, g_row_stride, i, j));
+            LERF_COORDS_DT(f_dtype, TF, invert_bwd_point(u.r, u.c, Point{grad_out[e], grad_out[e + 1]}, fH, fW,
+                                                         [&](int r, int c) { return load_entry((const TF*)f, f_row_stride, r, c); },
+                                                         PlainAdd2{grad_f, fW}));
         }
     return LERF_OK;
 }

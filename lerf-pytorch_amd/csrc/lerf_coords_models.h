@@ -62,6 +62,27 @@
 //                 u.r = r - (e.r*Jc.c - Jc.r*e.c) / det,  u.c = c - (Jr.r*e.c - Jr.c*e.r) / det
 //               no iteration met tol: (NaN, NaN) -- a target F does not reach.  No value of F, init or q forms an address
 //               outside F: u goes through compose_axis (clipped in floating point before the conversion to int, fH, fW >= 2).
+//   compose backward (compose_bwd_point; aH, aW >= 2)   one entry with inner point (row, col) and upstream g = (g.r, g.c):
+//                 a NaN in row or col: nothing is read, nothing is scattered, the inner gradient is (0, 0) whatever g holds (a select)
+//                 R = compose_axis(row, aH), Cx = compose_axis(col, aW), wr = {R.w0, R.w1}, wc = {Cx.w0, Cx.w1}: the forward's
+//               outer gradient (scatter_taps), taps in the order (0,0) (0,1) (1,0) (1,1); a tap with wr[a] == 0 or wc[b] == 0 is skipped
+//               and forms no address:
+//                 w = wr[a]*wc[b];  grad_A[R.i0 + a][Cx.i0 + b] += (w*g.r, w*g.c)
+//               inner gradient: P00, P01, P10, P11 as in invert_point, ALL FOUR read whatever their weights (cell_jacobian):
+//                 Jr = Cx.w0*(P10 - P00) + Cx.w1*(P11 - P01),  Jc = R.w0*(P01 - P00) + R.w1*(P11 - P10)      (invert_point's statements)
+//                 d.r = Jr.r*g.r + Jr.c*g.c  if 0 <= row <= aH - 1, else 0;  d.c = Jc.r*g.r + Jc.c*g.c  if 0 <= col <= aW - 1, else 0
+//               (torch.clamp's backward: the border passes, outside and +-inf are blocked by a select, so a NaN sum behind a blocked
+//               clip is 0; a NaN that passes is returned as the canonical quiet NaN, so the host and the device agree on its bits).  The derivative of the plain bilinear formula with i0 held constant: at an integer position it is that of
+//               cell i0 = min(floor(r), n - 2), and a NaN corner makes the inner gradient NaN even where the forward did not read it.
+//   invert backward (invert_bwd_point; fH, fW >= 2)   one entry G = (r, c) of the inverse with upstream g; F(G[q]) = q gives
+//               dG = -J^-1 dF(G), so the gradient on F is the bilinear scatter of v = -J^-T g:
+//                 a NaN in r or c: nothing is read or scattered
+//                 R = compose_axis(r, fH), Cx = compose_axis(c, fW);  P00 .. P11 all read;  a NaN in any of their 8 values: nothing
+//                 Jr, Jc as above;  det = Jr.r*Jc.c - Jr.c*Jc.r;  det == 0 or not finite: nothing
+//                 v.r = -(Jc.c*g.r - Jr.c*g.c) / det,  v.c = -(Jr.r*g.c - Jc.r*g.r) / det
+//                 scatter_taps of v into grad_F at the cell (R.i0, Cx.i0), the same rule and order as the outer gradient
+//               init, max_iter and tol have no gradient.  Neither backward forms an address outside its map: the cell comes from
+//               compose_axis and n >= 2 puts i0 + 1 <= n - 1.
 #pragma once
 
 #include "lerf_host_geometry.h"
@@ -288,6 +309,69 @@ LERF_HD inline Point invert_point(double q_r, double q_c, int fH, int fW, Point 
         u.c = c - (Jr.r * e.c - Jr.c * e.r) / det;
     }
     return nan2;
+}
+
+// ---- adjoints of compose and invert (aH, aW, fH, fW >= 2: the four corners of a cell are inside the map)
+struct CellJacobian {
+    Point Jr, Jc;      // dV/dr, dV/dc of the bilinear patch: invert_point's statements
+    bool nan;          // a NaN among the 8 values read
+};
+
+template <typename LOAD>
+LERF_HD inline CellJacobian cell_jacobian(const ComposeAxis& R, const ComposeAxis& Cx, LOAD load) {
+#pragma clang fp contract(off)
+    const Point P00 = load(R.i0, Cx.i0), P01 = load(R.i0, Cx.i0 + 1), P10 = load(R.i0 + 1, Cx.i0), P11 = load(R.i0 + 1, Cx.i0 + 1);
+    CellJacobian J;
+    J.Jr = {Cx.w0 * (P10.r - P00.r) + Cx.w1 * (P11.r - P01.r), Cx.w0 * (P10.c - P00.c) + Cx.w1 * (P11.c - P01.c)};
+    J.Jc = {R.w0 * (P01.r - P00.r) + R.w1 * (P11.r - P10.r), R.w0 * (P01.c - P00.c) + R.w1 * (P11.c - P10.c)};
+    J.nan = P00.r != P00.r || P00.c != P00.c || P01.r != P01.r || P01.c != P01.c || P10.r != P10.r || P10.c != P10.c || P11.r != P11.r ||
+            P11.c != P11.c;
+    return J;
+}
+
+// ADD(row, col, dr, dc): entry (row, col) of the gradient map gains (dr, dc); called only for taps whose two weights are not 0
+template <typename ADD>
+LERF_HD inline void scatter_taps(const ComposeAxis& R, const ComposeAxis& Cx, Point g, ADD add) {
+#pragma clang fp contract(off)
+    const double wr[2] = {R.w0, R.w1}, wc[2] = {Cx.w0, Cx.w1};
+    for (int a = 0; a < 2; ++a) {
+        if (wr[a] == 0.0) continue;
+        for (int b = 0; b < 2; ++b) {
+            if (wc[b] == 0.0) continue;
+            const double w = wr[a] * wc[b];
+            add(R.i0 + a, Cx.i0 + b, w * g.r, w * g.c);
+        }
+    }
+}
+
+// returns the inner gradient (0, 0 when !inner); outer: scatter into grad_A through ADD; LOAD is called only when inner
+template <typename LOAD, typename ADD>
+LERF_HD inline Point compose_bwd_point(double row, double col, Point g, int aH, int aW, bool outer, bool inner, LOAD load, ADD add) {
+#pragma clang fp contract(off)
+    if (row != row || col != col) return {0.0, 0.0};
+    const ComposeAxis R = compose_axis(row, aH), Cx = compose_axis(col, aW);
+    if (outer) scatter_taps(R, Cx, g, add);
+    if (!inner) return {0.0, 0.0};
+    const CellJacobian J = cell_jacobian(R, Cx, load);
+    const bool pass_r = row >= 0.0 && row <= (double)(aH - 1), pass_c = col >= 0.0 && col <= (double)(aW - 1);
+    const double dr = J.Jr.r * g.r + J.Jr.c * g.c, dc = J.Jc.r * g.r + J.Jc.c * g.c;
+    Point d{pass_r ? dr : 0.0, pass_c ? dc : 0.0};
+    if (d.r != d.r) d.r = __builtin_nan("");      // the canonical quiet NaN, whatever sign and payload the sum carried
+    if (d.c != d.c) d.c = __builtin_nan("");
+    return d;
+}
+
+template <typename LOAD, typename ADD>
+LERF_HD inline void invert_bwd_point(double r, double c, Point g, int fH, int fW, LOAD load, ADD add) {
+#pragma clang fp contract(off)
+    if (r != r || c != c) return;
+    const ComposeAxis R = compose_axis(r, fH), Cx = compose_axis(c, fW);
+    const CellJacobian J = cell_jacobian(R, Cx, load);
+    if (J.nan) return;
+    const double det = J.Jr.r * J.Jc.c - J.Jr.c * J.Jc.r;
+    if (!finite_nonzero(det)) return;
+    const Point v{-(J.Jc.c * g.r - J.Jr.c * g.c) / det, -(J.Jr.r * g.c - J.Jc.r * g.r) / det};
+    scatter_taps(R, Cx, v, add);
 }
 
 }  // namespace coords

@@ -1154,3 +1154,62 @@ def coords_invert(f, out_hw, init=None, dtype=None, out=None, origin=(0, 0), max
                                                  out.shape[0], out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol),
                                                  _lib.current_stream(a.device)), "lerf_coords_invert")
     return out
+
+
+def _grad_tensor(g, shape, device, what):
+    """a dense float64 gradient buffer [h, w, 2] on `device` (None: a zeroed one)"""
+    torch = _torch()
+    if g is None:
+        return torch.zeros(tuple(shape), dtype=torch.float64, device=device)
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float64 or tuple(g.shape) != tuple(shape) or not g.is_contiguous() \
+            or g.device != device:
+        raise ValueError("%s must be a contiguous float64 tensor %s on the maps' device" % (what, list(shape)))
+    return g
+
+
+def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):
+    """lerf_coords_compose_bwd: ACCUMULATE the adjoint of coords_compose(outer, inner) of grad_out (float64 contiguous [oH, oW, 2])
+    into grad_outer (float64 contiguous [aH, aW, 2]: a bilinear scatter by float64 atomic adds, reproducible up to the rounding of
+    a reordered sum) and grad_inner (float64 contiguous [oH, oW, 2]: one writer per entry, bit-reproducible); None: zeroed ones;
+    need[k] False skips that half and returns None for it.  The maps are device tensors under the strided contract, the outer
+    map at least 2 x 2.  One launch on the current stream, no sync -> (grad_outer, grad_inner)."""
+    a, sa = _map_tensor(outer, "outer")
+    b, sb = _map_tensor(inner, "inner")
+    if a.device != b.device:
+        raise ValueError("lerf_coords_compose_bwd: outer and inner live on different devices")
+    if not (need[0] or need[1]):
+        raise ValueError("lerf_coords_compose_bwd: at least one of the two gradients is needed")
+    a, b = a.detach(), b.detach()
+    if grad_out is None:
+        raise ValueError("lerf_coords_compose_bwd: grad_out must be a contiguous float64 device tensor [oH, oW, 2]")
+    g = _grad_tensor(grad_out, b.shape, b.device, "lerf_coords_compose_bwd: grad_out")
+    ga = _grad_tensor(grad_outer, a.shape, b.device, "lerf_coords_compose_bwd: grad_outer") if need[0] else None
+    gb = _grad_tensor(grad_inner, b.shape, b.device, "lerf_coords_compose_bwd: grad_inner") if need[1] else None
+    with _lib.on_device(b):
+        _lib.check(_lib.lib().lerf_coords_compose_bwd(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], b.data_ptr(), _lib._dt(b), sb,
+                                                      g.data_ptr(), b.shape[0], b.shape[1], None if ga is None else ga.data_ptr(),
+                                                      None if gb is None else gb.data_ptr(), _lib.current_stream(b.device)),
+                   "lerf_coords_compose_bwd")
+    return ga, gb
+
+
+def coords_invert_bwd(f, inverse, grad_out, grad_f=None):
+    """lerf_coords_invert_bwd: ACCUMULATE the adjoint of inverse = coords_invert(f, ...) of grad_out (float64 contiguous
+    [oH, oW, 2]) into grad_f (float64 contiguous [fH, fW, 2]; None: a zeroed one) by the implicit function theorem: the bilinear
+    scatter of -J^-T grad_out at the cell of every entry of the inverse (float64 atomic adds); NaN entries of the inverse, NaN
+    corners and folded cells contribute nothing.  Device maps under the strided contract.  One launch on the current stream, no
+    sync."""
+    a, sa = _map_tensor(f, "f")
+    b, sb = _map_tensor(inverse, "inverse")
+    if a.device != b.device:
+        raise ValueError("lerf_coords_invert_bwd: f and inverse live on different devices")
+    a, b = a.detach(), b.detach()
+    if grad_out is None:
+        raise ValueError("lerf_coords_invert_bwd: grad_out must be a contiguous float64 device tensor [oH, oW, 2]")
+    g = _grad_tensor(grad_out, b.shape, b.device, "lerf_coords_invert_bwd: grad_out")
+    gf = _grad_tensor(grad_f, a.shape, b.device, "lerf_coords_invert_bwd: grad_f")
+    with _lib.on_device(b):
+        _lib.check(_lib.lib().lerf_coords_invert_bwd(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], b.data_ptr(), _lib._dt(b), sb,
+                                                     g.data_ptr(), b.shape[0], b.shape[1], gf.data_ptr(), _lib.current_stream(b.device)),
+                   "lerf_coords_invert_bwd")
+    return gf
