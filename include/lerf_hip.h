@@ -357,7 +357,8 @@ int lerf_remap_host_geometry(const lerf_remap_geo_t* geo, int H, int W, double* 
  * Refused with LERF_EINVAL before anything is launched: n_maps < 1; a plane or frame count other than n_maps * planes_per_map
  * (n_maps for the packed form); a negative or odd map_stride (an entry is two elements: an even stride keeps every map's entries
  * aligned like map 0's); for n_maps > 1 a map_stride below (out_h - 1) * row_stride + 2 * out_w (overlapping maps).  n_maps == 1
- * is the plain entry point.  The map builders (lerf_coords_*) stay one parameter set or mesh per launch. */
+ * is the plain entry point.  lerf_coords_build_dev writes such a batch of model maps in one launch; the mesh builder, compose and
+ * invert stay one map per launch. */
 int lerf_remap_batched(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
                        int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const lerf_mplane_t* out,
                        void* stream);
@@ -679,10 +680,11 @@ int lerf_remap_bwd_batched(const float* feat, const float* h0, const float* h1, 
  * positions; the remap clips.  Everything is computed in float64 with + - * / only and no FMA contraction, so each device entry
  * point and its *_host twin (the same statements in a plain loop over HOST pointers; no GPU needed) agree bit for bit; a
  * float32 map is the float64 value rounded once at the store.  Device entry points: one launch on `stream` (two for
- * lerf_coords_mesh_bwd), no sync, no allocation, no global state.  Refused (LERF_EINVAL, nothing is launched or written): a
- * null pointer, oH or oW < 1, gh or gw < 2, an odd or short row stride, a misaligned base pointer, an unknown model, dtype or
- * interp, a parameter count that is not the model's, a non-finite model parameter, a negative origin or a tile outside the
- * whole map, a short workspace.  Operands must not overlap the output. */
+ * lerf_coords_mesh_bwd and lerf_coords_build_bwd), no sync, no allocation, no global state.  Refused (LERF_EINVAL, nothing is
+ * launched or written): a null pointer, oH or oW < 1, gh or gw < 2, an odd or short row stride, a misaligned base pointer, an
+ * unknown model, dtype or interp, a parameter count that is not the model's, a non-finite model parameter (where the parameters
+ * are HOST memory: lerf_coords_build, lerf_coords_build_host), a negative origin or a tile outside the whole map, a short
+ * workspace.  Operands must not overlap the output. */
 enum { LERF_COORDS_HOMOGRAPHY = 0, LERF_COORDS_RADIAL = 1, LERF_COORDS_BROWN = 2 };
 enum { LERF_MESH_BILINEAR = 0, LERF_MESH_BICUBIC = 1 };
 #define LERF_COORDS_MAX_PARAMS 21
@@ -811,6 +813,43 @@ int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int
 int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
                                 const void* g, int g_dtype, int64_t g_row_stride,
                                 const double* grad_out, int oH, int oW, double* grad_f);
+
+/* The model builders with their parameters in DEVICE memory, and their adjoint (the rounding order of every statement
+ * and the ORDER OF THE SUMS: the top of csrc/lerf_coords_models.h).
+ *
+ * lerf_coords_build_dev is lerf_coords_build with two changes: params_dev is DEVICE memory, float64 [n_sets][n_params], dense, and
+ * n_sets >= 1 maps are written in one launch, map s at out + s * set_stride ELEMENTS (each map under the strided contract with
+ * row_stride; set_stride even and, for n_sets > 1, >= (oH - 1) * row_stride + 2 * oW).  Map s is bit-equal to lerf_coords_build
+ * of the same 9 / 8 / 21 doubles; lerf_coords_build_host per set is the host twin.  No host round trip, no sync: the parameters
+ * are not visible to the host, so NON-FINITE PARAMETERS ARE NOT REFUSED here (they give non-finite entries, which the remap
+ * treats as it treats any map's).  Everything else on the family's list is refused, and n_sets outside 1 .. 65535, a misaligned
+ * params_dev, params_dev's bytes intersecting the maps'.
+ *
+ * lerf_coords_build_bwd: grad_params[s][k] += sum over the entries (i, j) of map s of
+ * d row / d p[k] * grad_map[s][i][j][0] + d col / d p[k] * grad_map[s][i][j][1], for EVERY entry of the parameter vector (radial's
+ * geometry scalars included), by the hand-written reverse mode model_point_bwd.  grad_map: float64 [n_sets][oH][oW][2], dense,
+ * 16-byte aligned (what lerf_remap_bwd_batched's grad_coords holds after the sum over a sample's planes); (i0, j0): the tile's
+ * origin in the whole map, as in the forward.  grad_params: float64 [n_sets][n_params], ACCUMULATED into by a plain load-add-store
+ * with one writer per value (the contract of lerf_remap_bwd and lerf_coords_mesh_bwd: the caller zeroes it).
+ * An entry whose forward point is not finite in either coordinate (Wh == 0 and the like) contributes EXACTLY NOTHING, whatever
+ * grad_map holds there -- a select, unlike autograd, which would return NaN; a NaN in grad_map at a finite point propagates.
+ * Two passes, no atomics: every lane of pass 1 keeps n_params running sums over the entries it owns, a block (64 columns x a band
+ * of 64 rows) combines them in a fixed order into ONE partial vector in the workspace; pass 2 sums the partials per (set, k) in
+ * a fixed order.  The order is a function of (oH, oW, n_sets) only -- not of the CU count, the resident grid or timing -- so two
+ * runs are bit-equal, and lerf_coords_build_bwd_host (host pointers, the same order) equals the device bit for bit.
+ * workspace: device, >= lerf_coords_build_bwd_workspace_bytes(n_params, n_sets, oH, oW) bytes (n_sets * n_params *
+ * ceil(oW / 64) * ceil(oH / 64) doubles; 0 from the query for refused sizes), 16-byte aligned, contents arbitrary, used by this
+ * call's two launches only.  Two launches on `stream`, no sync, no allocation, no global state.  Refused in addition to the
+ * family's list: n_sets outside 1 .. 65535, a short or misaligned workspace, grad_params' bytes intersecting params', grad_map's
+ * or the workspace's. */
+int lerf_coords_build_dev(int model, const double* params_dev, int n_sets, int n_params, void* out, int out_dtype,
+                          int64_t set_stride, int64_t row_stride, int oH, int oW, int i0, int j0, void* stream);
+size_t lerf_coords_build_bwd_workspace_bytes(int n_params, int n_sets, int oH, int oW);
+int lerf_coords_build_bwd(int model, const double* params_dev, int n_sets, int n_params, const double* grad_map,
+                          int oH, int oW, int i0, int j0, double* grad_params,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int n_params, const double* grad_map,
+                               int oH, int oW, int i0, int j0, double* grad_params);
 
 #ifdef __cplusplus
 }

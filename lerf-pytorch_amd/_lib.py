@@ -57,6 +57,7 @@ EXPORTS = [
     "lerf_coords_build", "lerf_coords_build_host", "lerf_coords_mesh", "lerf_coords_mesh_host", "lerf_coords_mesh_bwd_workspace_bytes",
     "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host", "lerf_coords_invert", "lerf_coords_invert_host",
     "lerf_coords_compose_bwd", "lerf_coords_compose_bwd_host", "lerf_coords_invert_bwd", "lerf_coords_invert_bwd_host",
+    "lerf_coords_build_dev", "lerf_coords_build_bwd_workspace_bytes", "lerf_coords_build_bwd", "lerf_coords_build_bwd_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -312,6 +313,12 @@ def lib():
     L.lerf_coords_mesh_bwd_workspace_bytes.restype = C.c_size_t
     L.lerf_coords_mesh_bwd_workspace_bytes.argtypes = [C.c_int] * 4
     L.lerf_coords_mesh_bwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.lerf_coords_build_dev.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_void_p]
+    _build_bwd = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.lerf_coords_build_bwd.argtypes, L.lerf_coords_build_bwd_host.argtypes = _build_bwd + [C.c_void_p, C.c_size_t, C.c_void_p], _build_bwd
+    L.lerf_coords_build_bwd_workspace_bytes.restype = C.c_size_t
+    L.lerf_coords_build_bwd_workspace_bytes.argtypes = [C.c_int] * 4
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -529,6 +536,25 @@ def coords_invert_bwd_host(f, inverse, grad_out, grad_f=None):
     check(lib().lerf_coords_invert_bwd_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
                                             g.ctypes.data, b.shape[0], b.shape[1], gf.ctypes.data), "lerf_coords_invert_bwd_host")
     return gf
+
+
+def coords_build_bwd_host(model, params, grad_map, origin=(0, 0)):
+    """lerf_coords_build_bwd_host: the adjoint of the model builders on the host, in the device's summation order (bit-equal to it).
+    params float64 [n] or [B, n] (the model's 9 / 8 / 21), grad_map float64 [oH, oW, 2] or [B, oH, oW, 2] -> a NEW zeroed
+    gradient of params' shape with the sums added (pre-filled buffers: the C entry point accumulates)."""
+    if model not in COORDS_MODELS:
+        raise ValueError("unknown coordinate-map model %r (known: %s)" % (model, ", ".join(COORDS_MODELS)))
+    p = np.ascontiguousarray(np.asarray(params, dtype=np.float64))
+    g = np.asarray(grad_map)
+    if p.ndim not in (1, 2) or g.ndim != p.ndim + 2 or g.shape[-1] != 2 or (p.ndim == 2 and g.shape[0] != p.shape[0]):
+        raise ValueError("lerf_coords_build_bwd_host: params is [n] with grad_map [oH, oW, 2], or [B, n] with [B, oH, oW, 2]")
+    if g.dtype != np.float64 or not g.flags.c_contiguous:
+        raise ValueError("lerf_coords_build_bwd_host: grad_map must be a C-contiguous float64 array")
+    out = np.zeros(p.shape, np.float64)
+    check(lib().lerf_coords_build_bwd_host(COORDS_MODELS[model], p.ctypes.data, 1 if p.ndim == 1 else p.shape[0], p.shape[-1], g.ctypes.data,
+                                           g.shape[-3], g.shape[-2], int(origin[0]), int(origin[1]), out.ctypes.data),
+          "lerf_coords_build_bwd_host")
+    return out
 
 
 # ------------------------------------------------------------------ device plumbing

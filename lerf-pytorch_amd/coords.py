@@ -12,6 +12,13 @@ in the autograd graph through the mesh upsample's adjoint, compose chains two ma
 map for its inverse (distort <-> undistort, forward flow -> backward map).  The kernels' arithmetic is
 float64 with + - * / only, bit-equal to its host twin (csrc/lerf_coords_models.h).
 
+from_homography_torch, radial_torch and undistort_rectify_torch (with brown_params_torch) are the differentiable twins of the
+closed-form builders: their operands are DEVICE tensors (a matrix, lens coefficients, camera matrices -- one set or a leading
+batch B, one map per sample in one launch), the map is written by lerf_coords_build_dev from parameters that never leave the
+device, and a loss reaches the operands through lerf_coords_build_bwd: direct image alignment, calibration
+refinement, a spatial-transformer head.  An entry whose point is not finite (a homography's Wh == 0) contributes nothing to the
+gradient -- unlike autograd of the same formulas, which would return NaN.
+
 compose, invert and invert_flow refuse operands that require grad.  Their opt-in twins compose_torch, invert_torch and
 invert_flow_torch (device tensors only) run the same forward kernels and keep the maps in the autograd graph through the HIP
 adjoints lerf_coords_compose_bwd and lerf_coords_invert_bwd, so a loss reaches a flow or a control mesh through
@@ -508,3 +515,162 @@ def invert_flow_torch(flow, init=None, max_iter=16, tol=1e-9):
     H, W = int(f.shape[-3]), int(f.shape[-2])
     ident = from_flow_torch(torch.zeros((H, W, 2), dtype=f.dtype, device=f.device))
     return invert_torch(ident + f, (H, W), init=init, max_iter=max_iter, tol=tol) - ident
+
+
+# ---------------------------------------------------------------------------------------------- differentiable model builders
+_BUILD_FN = None
+
+
+def _build_fn():
+    global _BUILD_FN
+    if _BUILD_FN is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+        from . import ops
+
+        class _BuildFn(torch.autograd.Function):
+            """map = ops.coords_build_params(model, params), params float64 [n] or [B, n] on the device; backward:
+            ops.coords_build_bwd, the gradient of EVERY entry of the parameter vector in float64 (autograd carries it on to the
+            operands the vector was assembled from, constants drop theirs)"""
+
+            @staticmethod
+            def forward(ctx, params, model, out_hw, tdt):
+                p = params.detach().contiguous()
+                ctx.save_for_backward(p)
+                ctx.model = model
+                return ops.coords_build_params(model, p, out_hw, dtype=tdt)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                p, = ctx.saved_tensors
+                return ops.coords_build_bwd(ctx.model, p, grad.contiguous().double()), None, None, None
+
+        _BUILD_FN = _BuildFn
+    return _BUILD_FN
+
+
+def _build_torch(model, params, out_hw, tdt):
+    """the map of float64 device parameters [n] or [B, n] by the kernel; in the autograd graph when they require grad"""
+    import torch
+    from . import ops
+    hw = (int(out_hw[0]), int(out_hw[1]))
+    if hw[0] < 1 or hw[1] < 1:
+        raise ValueError("out_hw must be positive")
+    if torch.is_grad_enabled() and params.requires_grad:
+        return _build_fn().apply(params, model, hw, tdt)
+    return ops.coords_build_params(model, params.detach(), hw, dtype=tdt)
+
+
+def _operand(t, what, shapes):
+    """a float32 / float64 device tensor whose shape is one of `shapes` or one of them behind a leading B, or ValueError -> B (0: none)"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.float32, torch.float64):
+        raise ValueError("%s must be a float32 or float64 device tensor" % what)
+    for shp in shapes:
+        if tuple(t.shape) == tuple(shp):
+            return 0
+        if t.ndim == len(shp) + 1 and tuple(t.shape[1:]) == tuple(shp) and t.shape[0] >= 1:
+            return int(t.shape[0])
+    raise ValueError("%s must be %s, or that behind a leading batch size" % (what, " or ".join(str(list(x)) for x in shapes)))
+
+
+def _one_batch(what, operands, sizes):
+    """the common B of the operands (0: none is batched); all on one device"""
+    B = 0
+    for t, b in zip(operands, sizes):
+        if t.device != operands[0].device:
+            raise ValueError("%s: the operands live on different devices" % what)
+        if b and B and b != B:
+            raise ValueError("%s: the operands hold different numbers of samples (%d and %d)" % (what, B, b))
+        B = B or b
+    return B
+
+
+def _map_dtype(dtype, default):
+    import torch
+    return default if dtype is None else getattr(torch, _np_dtype(dtype).name)
+
+
+def from_homography_torch(matrix, out_hw, dtype=None):
+    """from_homography on the matrix's device, differentiable: matrix [3, 3] (source -> output, as from_homography takes it) or a batch
+    [B, 3, 3] device tensor, float32 or float64 -> the map [oH, oW, 2] or [B, oH, oW, 2] (one launch) in the matrix's dtype (or
+    `dtype`).  The inverse is torch.linalg.inv(matrix.double()) on the device, differentiated by autograd; its nine entries go
+    through the kernel (lerf_coords_build_dev, the "device" arithmetic) and, for a matrix that requires grad, through its HIP
+    adjoint lerf_coords_build_bwd: float64, a fixed summation order (bit-equal from run to run), cast to the matrix's dtype.
+    The map is bit-equal to from_homography(..., device=) for EQUAL INVERSE ENTRIES -- not necessarily for equal matrices:
+    torch.linalg.inv and np.linalg.inv may round the inverse differently.  An entry with Wh == 0 (a point that is not finite)
+    contributes nothing to the gradient.  Once differentiable."""
+    import torch
+    B = _operand(matrix, "from_homography_torch: matrix", [(3, 3)])
+    minv = torch.linalg.inv(matrix.double())
+    return _build_torch("homography", minv.reshape(((B,) if B else ()) + (9,)), out_hw, _map_dtype(dtype, matrix.dtype))
+
+
+def radial_torch(in_hw, out_hw, k1, k2=0.0, centre=None, dtype=None):
+    """radial on the coefficients' device, differentiable: k1 a 0-d or [B] device tensor (float32 or float64); k2 alike, or a
+    number (a constant); centre a device tensor [2] or [B, 2] (row, col of the source), or None = the middle of the source (a
+    constant) -> the map [oH, oW, 2], or [B, oH, oW, 2] when any operand carries a B (the others are shared), in k1's dtype (or
+    `dtype`).  The geometry scalars (the half-diagonals, the half-extents of the output) are constants: the kernel returns their
+    gradient entries and they are dropped.  Bit-equal to radial(..., device=) for the same numbers."""
+    import torch
+    H, W = int(in_hw[0]), int(in_hw[1])
+    oH, oW = int(out_hw[0]), int(out_hw[1])
+    what = "radial_torch"
+    ops_, sizes = [k1], [_operand(k1, what + ": k1", [()])]
+    if isinstance(k2, torch.Tensor):
+        ops_.append(k2), sizes.append(_operand(k2, what + ": k2", [()]))
+    if centre is not None:
+        ops_.append(centre), sizes.append(_operand(centre, what + ": centre", [(2,)]))
+    B = _one_batch(what, ops_, sizes)
+    lead = (B,) if B else ()
+    const = lambda v: torch.full(lead, float(v), dtype=torch.float64, device=k1.device)
+    k2t = k2.double().expand(lead) if isinstance(k2, torch.Tensor) else const(k2)
+    if centre is None:
+        cr, cc = const((H - 1) / 2.0), const((W - 1) / 2.0)
+    else:
+        c = centre.double().expand(lead + (2,))
+        cr, cc = c[..., 0], c[..., 1]
+    params = torch.stack([cr, cc, const(np.hypot(oH, oW) / 2.0), const(np.hypot(H, W) / 2.0), const((oH - 1) / 2.0), const((oW - 1) / 2.0),
+                          k1.double().expand(lead), k2t], dim=-1)
+    return _build_torch("radial", params, (oH, oW), _map_dtype(dtype, k1.dtype))
+
+
+def brown_params_torch(K, dist=None, R=None, new_K=None):
+    """brown_params in torch ops on the operands' device, differentiable in all four: K [3, 3] (no skew), dist [4], [5] or [8]
+    (missing coefficients 0; None: all 0), R [3, 3] (None: identity), new_K [3, 3] (None: K), each a float32 / float64 device
+    tensor, single or behind a leading B (single operands are shared by the batch) -> float64 [21] or [B, 21]:
+    inv(new_K . R) by torch.linalg.inv, fx, fy, cx, cy picked from K, dist padded to 8.  The skew check reads K (one sync)."""
+    import torch
+    what = "brown_params_torch"
+    ops_, sizes = [K], [_operand(K, what + ": K", [(3, 3)])]
+    if dist is not None:
+        ops_.append(dist), sizes.append(_operand(dist, what + ": dist", [(4,), (5,), (8,)]))
+    for t, name in ((R, "R"), (new_K, "new_K")):
+        if t is not None:
+            ops_.append(t), sizes.append(_operand(t, "%s: %s" % (what, name), [(3, 3)]))
+    B = _one_batch(what, ops_, sizes)
+    lead = (B,) if B else ()
+    Kd = K.double()
+    with torch.no_grad():
+        skew = (Kd[..., 0, 1] != 0) | (Kd[..., 1, 0] != 0) | (Kd[..., 2, 0] != 0) | (Kd[..., 2, 1] != 0) | (Kd[..., 2, 2] != 1)
+        if bool(skew.any()):
+            raise ValueError("K must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (skew is not supported)")
+    Rd = torch.eye(3, dtype=torch.float64, device=K.device) if R is None else R.double()
+    Nd = Kd if new_K is None else new_K.double()
+    minv = torch.linalg.inv(torch.matmul(Nd, Rd)).expand(lead + (3, 3))
+    Kd = Kd.expand(lead + (3, 3))
+    cam = torch.stack([Kd[..., 0, 0], Kd[..., 1, 1], Kd[..., 0, 2], Kd[..., 1, 2]], dim=-1)
+    d = torch.zeros(lead + (8,), dtype=torch.float64, device=K.device) if dist is None else dist.double().expand(lead + (dist.shape[-1],))
+    if d.shape[-1] < 8:
+        d = torch.cat([d, torch.zeros(lead + (8 - d.shape[-1],), dtype=torch.float64, device=K.device)], dim=-1)
+    return torch.cat([minv.reshape(lead + (9,)), cam, d], dim=-1)
+
+
+def undistort_rectify_torch(K, dist, R, new_K, out_hw, dtype=None):
+    """undistort_rectify on the operands' device, differentiable: the operands of brown_params_torch (device tensors, single or
+    behind a leading B; dist, R and new_K may be None) -> the map [oH, oW, 2] or [B, oH, oW, 2] in K's dtype (or `dtype`).  K, dist,
+    R and new_K each receive a gradient when they require one: the 21 parameters go through lerf_coords_build_dev and its
+    adjoint lerf_coords_build_bwd, the assembly (the 3 x 3 inverse included) through autograd.  Calibration refinement: fit k1 ..
+    k6, p1, p2, fx, fy, cx, cy against a rectified target through a remap class that has opted in with enable_backward()."""
+    return _build_torch("brown", brown_params_torch(K, dist, R, new_K), out_hw, _map_dtype(dtype, K.dtype))

@@ -37,6 +37,16 @@
 //   coords_invert_bwd_kernel<TF, TG>        the adjoint of invert by the implicit function theorem (invert_bwd_point): one load of G and
 //                                           of grad_out, the four corners of one cell of F, the 2 x 2 solve v = -J^-T g, the same scatter
 //                                           of v into grad_f (float64 atomicAdd)
+//   coords_build_dev_kernel<MODEL, TO>      coords_build_kernel with the parameters in DEVICE memory, [n_sets][n_params] float64: blockIdx.z is
+//                                           the set, its parameters are read at a wave-uniform address (scalar loads), model_point is
+//                                           called unchanged: map s is bit-equal to lerf_coords_build of the same doubles
+//   coords_build_bwd_{partial,sum}_kernel   the adjoint of the builders, grad_params[s][k] += sum over the entries of dp[k] (model_point_bwd):
+//                                           a reduction of 9 / 8 / 21 sums over every entry, in two passes, fixed order, no atomics
+//       partial  a block owns 64 columns x a band of 64 rows of one set; wave w takes the rows w, w + 4, ... of the band (16 per lane),
+//                every lane keeps its n_params running sums in registers; a shuffle tree (offsets 32 .. 1) per sum, the 4 wave sums meet in
+//                LDS and are added in the order 0, 1, 2, 3; ONE partial vector per block goes to the workspace ([set][k][block])
+//       sum      ONE wave per (set, k): lane l adds the partials l, l + 64, ..., the same tree, lane 0 is the one writer (load-add-store)
+//       2160 x 3840: 2 040 blocks a set in pass 1 (8 per CU), 343 KB of partials for the 21 sums of brown; grad_map is read once, coalesced
 //
 // Addresses: every kernel guards (i, j) against the tile, writes entry (i, j) of `out` only, and reads ctrl / A at indices that
 // mesh_axis / compose_axis clamp into the operand after clipping the position in floating point (no value of B reaches an int
@@ -44,11 +54,14 @@
 // compose_axis picks for the iterate (fH, fW >= 2, so i0 + 1 <= fH - 1), whatever F, init or the iterate hold.  The passes of the
 // adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].  The adjoints of compose and invert read
 // B / G, grad_out and grad_b at entry (i, j) only, and read A / F and add into grad_a / grad_f at the cell compose_axis picks (aH, aW,
-// fH, fW >= 2 are checked on the host, so i0 + 1 <= n - 1), whatever the maps hold.
+// fH, fW >= 2 are checked on the host, so i0 + 1 <= n - 1), whatever the maps hold.  The kernels that read device parameters index
+// params and grad_params inside [n_sets][n_params], grad_map at (set, i, j) with i < oH, j < oW, the workspace inside
+// [n_sets][n_params][blocks]; no parameter value forms an address.
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
 
 #include <cmath>
+#include <vector>
 
 namespace lerf {
 namespace coords {
@@ -224,6 +237,69 @@ coords_invert_bwd_kernel(const TF* __restrict__ F, int64_t f_stride, int fH, int
     invert_bwd_point(u.r, u.c, Point{g.x, g.y}, fH, fW, [&](int r, int c) { return load_entry(F, f_stride, r, c); }, AtomicAdd2{gF, fW});
 }
 
+// the builders with device parameters: grid (ceil(oW / 64), ceil(oH / 4), n_sets)
+template <int MODEL, typename TO>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_build_dev_kernel(const double* __restrict__ params, TO* __restrict__ out, int64_t set_stride, int64_t stride, int oH, int oW, int i0,
+                        int j0) {
+    constexpr int NP = MODEL == LERF_COORDS_HOMOGRAPHY ? 9 : MODEL == LERF_COORDS_RADIAL ? 8 : 21;
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= oH || j >= oW) return;
+    const double* p = params + (size_t)blockIdx.z * NP;                 // the same address in every lane: scalar loads
+    store_entry(out + (int64_t)blockIdx.z * set_stride, stride, i, j, model_point<MODEL>(p, i0 + i, j0 + j));
+}
+
+static_assert(kBwdCols == CB_COLS && kBwdWaves == CB_ROWS && kBwdBand % kBwdWaves == 0, "the band of the build backward is the block's");
+
+// pass 1 of the build backward: grid (ceil(oW / 64), ceil(oH / 64), n_sets), block (64, 4); part [n_sets][NP][nblk]
+template <int MODEL>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_build_bwd_partial_kernel(const double* __restrict__ params, const double2* __restrict__ gmap, int oH, int oW, int i0, int j0,
+                                double* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int NP = MODEL == LERF_COORDS_HOMOGRAPHY ? 9 : MODEL == LERF_COORDS_RADIAL ? 8 : 21;
+    __shared__ double wsum[kBwdWaves][NP];
+    const int s = blockIdx.z, w = threadIdx.y, j = blockIdx.x * CB_COLS + threadIdx.x;
+    const double* p = params + (size_t)s * NP;
+    const double2* g = gmap + (size_t)s * oH * oW;
+    double acc[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) acc[k] = 0.0;
+    if (j < oW)
+        for (int i = blockIdx.y * kBwdBand + w; i < oH && i < (int)(blockIdx.y + 1) * kBwdBand; i += kBwdWaves) {
+            const double2 gv = g[(int64_t)i * oW + j];
+            double dp[NP];
+            model_point_bwd<MODEL>(p, i0 + i, j0 + j, Point{gv.x, gv.y}, dp);
+#pragma unroll
+            for (int k = 0; k < NP; ++k) acc[k] = acc[k] + dp[k];
+        }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[k] = acc[k] + __shfl_down(acc[k], off, 64);
+        if (threadIdx.x == 0) wsum[w][k] = acc[k];
+    }
+    __syncthreads();
+    const int k = threadIdx.y * CB_COLS + threadIdx.x;
+    if (k < NP) {
+        const int nblk = gridDim.x * gridDim.y, blk = blockIdx.y * gridDim.x + blockIdx.x;
+        part[((size_t)s * NP + k) * nblk + blk] = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+    }
+}
+
+// pass 2: grid (n_params, n_sets), block 64 = one wave per sum
+__global__ void __launch_bounds__(64)
+coords_build_bwd_sum_kernel(const double* __restrict__ part, int nblk, double* __restrict__ gparams) {
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const double* src = part + e * nblk;
+    double v = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += 64) v = v + src[b];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
+    if (threadIdx.x == 0) gparams[e] = gparams[e] + v;
+}
+
 // ------------------------------------------------------------------------------------------------ argument checks (host)
 inline bool float_dtype(int dt) { return dt == LERF_F32 || dt == LERF_F64; }
 inline size_t entry_bytes(int dt) { return dt == LERF_F32 ? 8 : 16; }
@@ -317,6 +393,37 @@ inline int invert_bwd_args(const void* f, int f_dtype, int64_t f_stride, int fH,
     if (dense_overlaps_map(grad_f, fH, fW, f, f_dtype, f_stride, fH, fW) || dense_overlaps_map(grad_f, fH, fW, g, g_dtype, g_stride, oH, oW) ||
         dense_overlap(grad_f, fH, fW, grad_out, oH, oW))
         return LERF_EINVAL;
+    return LERF_OK;
+}
+
+// plain byte ranges [p, p + pn) and [q, q + qn)
+inline bool bytes_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qn && b < a + pn;
+}
+
+// device parameters cannot be inspected here: their count, the pointers and the layout of the n_sets maps are what is checked
+inline int build_dev_args(int model, const double* params, int n_sets, int n_params, const void* out, int out_dtype, int64_t set_stride,
+                          int64_t stride, int oH, int oW, int i0, int j0) {
+    if (!params || (size_t)(uintptr_t)params % sizeof(double) != 0 || !map_ok(out, out_dtype, stride, oH, oW) || !tile_ok(oH, oW, i0, j0))
+        return LERF_EINVAL;
+    if (model_params(model) < 0 || n_params != model_params(model) || n_sets < 1 || n_sets > 65535) return LERF_EINVAL;
+    const int64_t span = (int64_t)(oH - 1) * stride + 2 * (int64_t)oW;      // elements from a map's first entry to one past its last
+    if (set_stride < 0 || (set_stride & 1) || (n_sets > 1 && set_stride < span)) return LERF_EINVAL;
+    const size_t el = entry_bytes(out_dtype) / 2;
+    if (bytes_overlap(params, (size_t)n_sets * n_params * sizeof(double), out, (size_t)((int64_t)(n_sets - 1) * set_stride + span) * el))
+        return LERF_EINVAL;
+    return LERF_OK;
+}
+
+inline int build_bwd_args(int model, const double* params, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
+                          const double* grad_params) {
+    if (!params || !grad_params || (size_t)(uintptr_t)params % sizeof(double) != 0 || (size_t)(uintptr_t)grad_params % sizeof(double) != 0)
+        return LERF_EINVAL;
+    if (!dense_ok(grad_map) || oH < 1 || oW < 1 || !tile_ok(oH, oW, i0, j0)) return LERF_EINVAL;
+    if (model_params(model) < 0 || n_params != model_params(model) || n_sets < 1 || n_sets > 65535) return LERF_EINVAL;
+    const size_t pb = (size_t)n_sets * n_params * sizeof(double), mb = (size_t)n_sets * oH * oW * 2 * sizeof(double);
+    if (bytes_overlap(grad_params, pb, params, pb) || bytes_overlap(grad_params, pb, grad_map, mb)) return LERF_EINVAL;
     return LERF_OK;
 }
 
@@ -455,6 +562,60 @@ int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int
     return launch_status();
 }
 
+int lerf_coords_build_dev(int model, const double* params_dev, int n_sets, int n_params, void* out, int out_dtype, int64_t set_stride,
+                          int64_t row_stride, int oH, int oW, int i0, int j0, void* stream) {
+    const int rc = build_dev_args(model, params_dev, n_sets, n_params, out, out_dtype, set_stride, row_stride, oH, oW, i0, j0);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    const dim3 block(CB_COLS, CB_ROWS), grid((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS, n_sets);
+    hipStream_t st = (hipStream_t)stream;
+#define LERF_CBD(MODEL)                                                                                                                 \
+    LERF_COORDS_DT(out_dtype, TO, hipLaunchKernelGGL((coords_build_dev_kernel<MODEL, TO>), grid, block, 0, st, params_dev, (TO*)out, set_stride, \
+                                                     row_stride, oH, oW, i0, j0))
+    switch (model) {
+        case LERF_COORDS_HOMOGRAPHY: LERF_CBD(LERF_COORDS_HOMOGRAPHY); break;
+        case LERF_COORDS_RADIAL: LERF_CBD(LERF_COORDS_RADIAL); break;
+        default: LERF_CBD(LERF_COORDS_BROWN); break;
+    }
+#undef LERF_CBD
+    return launch_status();
+}
+
+size_t lerf_coords_build_bwd_workspace_bytes(int n_params, int n_sets, int oH, int oW) {
+    if (n_params < 1 || n_params > kMaxParams || n_sets < 1 || n_sets > 65535 || oH < 1 || oW < 1) return 0;
+    return (size_t)n_sets * (size_t)n_params * (size_t)build_bwd_blocks(oH, oW) * sizeof(double);
+}
+
+int lerf_coords_build_bwd(int model, const double* params_dev, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
+                          double* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = build_bwd_args(model, params_dev, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params);
+    if (rc != LERF_OK) return rc;
+    const size_t need = lerf_coords_build_bwd_workspace_bytes(n_params, n_sets, oH, oW);
+    if (!workspace || (size_t)(uintptr_t)workspace % 16 != 0 || workspace_bytes < need) return LERF_EINVAL;
+    if (bytes_overlap(workspace, need, grad_params, (size_t)n_sets * n_params * sizeof(double)) ||
+        bytes_overlap(workspace, need, params_dev, (size_t)n_sets * n_params * sizeof(double)) ||
+        bytes_overlap(workspace, need, grad_map, (size_t)n_sets * oH * oW * 2 * sizeof(double)))
+        return LERF_EINVAL;
+    clear_stale_error();
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + kBwdCols - 1) / kBwdCols, (oH + kBwdBand - 1) / kBwdBand, n_sets), b2(64), g2(n_params, n_sets);
+    const double2* gm = reinterpret_cast<const double2*>(grad_map);
+    double* part = reinterpret_cast<double*>(workspace);
+    switch (model) {
+        case LERF_COORDS_HOMOGRAPHY:
+            hipLaunchKernelGGL((coords_build_bwd_partial_kernel<LERF_COORDS_HOMOGRAPHY>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part);
+            break;
+        case LERF_COORDS_RADIAL:
+            hipLaunchKernelGGL((coords_build_bwd_partial_kernel<LERF_COORDS_RADIAL>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part);
+            break;
+        default:
+            hipLaunchKernelGGL((coords_build_bwd_partial_kernel<LERF_COORDS_BROWN>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part);
+            break;
+    }
+    hipLaunchKernelGGL(coords_build_bwd_sum_kernel, g2, b2, 0, st, part, (int)(g1.x * g1.y), grad_params);
+    return launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------ host twins: the same functions, a plain loop
 int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
                            int i0, int j0) {
@@ -556,6 +717,57 @@ int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride
                                                          [&](int r, int c) { return load_entry((const TF*)f, f_row_stride, r, c); },
                                                          PlainAdd2{grad_f, fW}));
         }
+    return LERF_OK;
+}
+
+// the device's two passes, lane by lane: the same bands, the same trees, the same order (the top of lerf_coords_models.h)
+int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
+                               double* grad_params) {
+#pragma clang fp contract(off)
+    const int rc = build_bwd_args(model, params, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params);
+    if (rc != LERF_OK) return rc;
+    const int nbx = (oW + kBwdCols - 1) / kBwdCols, nby = (oH + kBwdBand - 1) / kBwdBand, nblk = nbx * nby;
+    std::vector<double> part((size_t)n_params * nblk);
+    std::vector<double> lanes((size_t)kMaxParams * 64);
+    for (int s = 0; s < n_sets; ++s) {
+        const double* p = params + (size_t)s * n_params;
+        const double* g = grad_map + (size_t)s * oH * oW * 2;
+        for (int by = 0; by < nby; ++by)
+            for (int bx = 0; bx < nbx; ++bx) {
+                double wsum[kBwdWaves][kMaxParams];
+                for (int w = 0; w < kBwdWaves; ++w) {
+                    for (int l = 0; l < 64; ++l) {
+                        const int j = bx * kBwdCols + l;
+                        double acc[kMaxParams];
+                        for (int k = 0; k < n_params; ++k) acc[k] = 0.0;
+                        if (j < oW)
+                            for (int i = by * kBwdBand + w; i < oH && i < (by + 1) * kBwdBand; i += kBwdWaves) {
+                                const int64_t e = 2 * ((int64_t)i * oW + j);
+                                const Point gv{g[e], g[e + 1]};
+                                double dp[kMaxParams];
+                                if (model == LERF_COORDS_HOMOGRAPHY) model_point_bwd<LERF_COORDS_HOMOGRAPHY>(p, i0 + i, j0 + j, gv, dp);
+                                else if (model == LERF_COORDS_RADIAL) model_point_bwd<LERF_COORDS_RADIAL>(p, i0 + i, j0 + j, gv, dp);
+                                else model_point_bwd<LERF_COORDS_BROWN>(p, i0 + i, j0 + j, gv, dp);
+                                for (int k = 0; k < n_params; ++k) acc[k] = acc[k] + dp[k];
+                            }
+                        for (int k = 0; k < n_params; ++k) lanes[(size_t)k * 64 + l] = acc[k];
+                    }
+                    for (int k = 0; k < n_params; ++k) wsum[w][k] = tree64(&lanes[(size_t)k * 64]);
+                }
+                for (int k = 0; k < n_params; ++k)
+                    part[(size_t)k * nblk + by * nbx + bx] = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+            }
+        for (int k = 0; k < n_params; ++k) {
+            double v[64];
+            for (int l = 0; l < 64; ++l) {
+                double acc = 0.0;
+                for (int b = l; b < nblk; b += 64) acc = acc + part[(size_t)k * nblk + b];
+                v[l] = acc;
+            }
+            double* dst = grad_params + (size_t)s * n_params + k;
+            *dst = *dst + tree64(v);
+        }
+    }
     return LERF_OK;
 }
 

@@ -83,6 +83,51 @@
 //                 scatter_taps of v into grad_F at the cell (R.i0, Cx.i0), the same rule and order as the outer gradient
 //               init, max_iter and tol have no gradient.  Neither backward forms an address outside its map: the cell comes from
 //               compose_axis and n >= 2 puts i0 + 1 <= n - 1.
+//   model backward (model_point_bwd<MODEL>; HOMOGRAPHY, RADIAL, BROWN)   one entry (i, j) with upstream g = (g.r, g.c): the hand-written
+//               reverse mode of model_point, dp[k] = d(row)/d(p[k]) * g.r + d(col)/d(p[k]) * g.c for EVERY entry of the parameter
+//               vector (radial's geometry scalars no, ni, hr, hc included; the caller keeps what it fits).  The forward is
+//               recomputed by the forward's own statements; (row, col) = model_point(p, i, j).
+//                 row or col not finite (row - row != 0: Wh == 0, an overflow, a NaN parameter): dp[k] = 0 for every k, whatever g
+//                 holds -- a select, as in compose_bwd_point; this is NOT autograd's rule (autograd returns NaN or inf there).  A
+//                 NaN in g at a finite point propagates.
+//               HOMOGRAPHY  x = (double)j, y = (double)i, X, Y, Wh, col, row as above
+//                 dX = g.c / Wh,  dY = g.r / Wh,  dWh = -((g.c*col + g.r*row) / Wh)
+//                 dp[0..2] = dX*x, dX*y, dX;  dp[3..5] = dY*x, dY*y, dY;  dp[6..8] = dWh*x, dWh*y, dWh
+//               RADIAL      ur, uc, r2, f as above
+//                 dp[cr] = g.r,  dp[cc] = g.c
+//                 dp[ni] = g.r*(ur*f) + g.c*(uc*f)
+//                 ar = g.r*ni,  ac = g.c*ni                                  -- d/d(ur*f), d/d(uc*f)
+//                 df = ar*ur + ac*uc
+//                 dp[k1] = df*r2,  dp[k2] = df*(r2*r2)
+//                 dr2 = df*(k1 + (2*k2)*r2)
+//                 dur = ar*f + dr2*(2*ur),  duc = ac*f + dr2*(2*uc)
+//                 dp[hr] = -(dur / no),  dp[hc] = -(duc / no),  dp[no] = -((dur*ur + duc*uc) / no)
+//               BROWN       u = (double)j, v = (double)i, X, Y, Wh, x = X / Wh, y = Y / Wh, r2, xy as above, and
+//                 num = 1 + r2*(k1 + r2*(k2 + r2*k3)),  den = 1 + r2*(k4 + r2*(k5 + r2*k6)),  rad = num / den
+//                 a1 = r2 + 2*(x*x),  a2 = r2 + 2*(y*y),  xd, yd as above
+//                 dp[fx] = g.c*xd,  dp[cx] = g.c,  dp[fy] = g.r*yd,  dp[cy] = g.r
+//                 dxd = g.c*fx,  dyd = g.r*fy
+//                 dp[p1] = dxd*(2*xy) + dyd*a2,  dp[p2] = dxd*a1 + dyd*(2*xy)
+//                 drad = dxd*x + dyd*y,  dnum = drad / den,  dden = -((drad*rad) / den)
+//                 r4 = r2*r2,  r6 = r4*r2
+//                 dp[k1] = dnum*r2, dp[k2] = dnum*r4, dp[k3] = dnum*r6, dp[k4] = dden*r2, dp[k5] = dden*r4, dp[k6] = dden*r6
+//                 dr2 = (dnum*(k1 + r2*(2*k2 + r2*(3*k3))) + dden*(k4 + r2*(2*k5 + r2*(3*k6)))) + (dxd*p2 + dyd*p1)
+//                 dx = (((dxd*rad + dxd*((2*p1)*y)) + (dxd*p2)*(4*x)) + dyd*((2*p2)*y)) + dr2*(2*x)
+//                 dy = (((dyd*rad + (dyd*p1)*(4*y)) + dxd*((2*p1)*x)) + dyd*((2*p2)*x)) + dr2*(2*y)
+//                 dX = dx / Wh,  dY = dy / Wh,  dWh = -((dx*x + dy*y) / Wh)
+//                 dp[0..2] = dX*u, dX*v, dX;  dp[3..5] = dY*u, dY*v, dY;  dp[6..8] = dWh*u, dWh*v, dWh
+//   build backward (lerf_coords_build_bwd / _host)   grad_params[s][k] += sum over the entries of map s of dp[k].  THE ORDER OF THE SUM IS
+//               PART OF THE CONTRACT: a function of (oH, oW, n_sets) only, the same on the device and in the host twin, so two runs and
+//               the two sides agree bit for bit.  With C = 64 columns and R = 64 rows per band (kBwdCols, kBwdBand), nbx = ceil(oW / C),
+//               nby = ceil(oH / R), nblk = nbx*nby:
+//                 pass 1, band (bx, by) of set s, its 4 x 64 "lanes" (w, l), w = 0 .. 3, l = 0 .. 63, column j = bx*C + l:
+//                   acc = +0.0;  for t = 0 .. 15: i = by*R + w + 4*t;  if i < oH and j < oW: acc = acc + dp[k] of entry (i, j)
+//                   (a lane or row outside the map adds nothing, which equals adding +0.0: acc is never -0.0)
+//                 the 64 lanes of w by the tree  for off = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l + off]  (l < off), result v[0]
+//                 partial[s][k][by*nbx + bx] = ((v0[w = 0] + v0[1]) + v0[2]) + v0[3]
+//                 pass 2, per (s, k): 64 lanes, lane l: acc = +0.0; for b = l, l + 64, ... < nblk: acc = acc + partial[s][k][b];
+//                   the same tree;  grad_params[s][k] = grad_params[s][k] + v[0]   (one writer: a plain load-add-store)
+//               The workspace holds the partials: n_sets * n_params * nblk doubles (2160 x 3840, brown: 60 * 34 * 21 * 8 B = 343 KB a set).
 #pragma once
 
 #include "lerf_host_geometry.h"
@@ -138,6 +183,90 @@ LERF_HD inline Point model_point(const double* p, int i, int j) {
         q.r = fy * yd + cy;
     }
     return q;
+}
+
+// ---- adjoint of model_point (the statement order: the comment block at the top of this file)
+LERF_HD inline bool finite_value(double d) { return d - d == 0.0; }      // false for +-inf and NaN
+
+template <int MODEL>
+LERF_HD inline void model_point_bwd(const double* p, int i, int j, Point g, double* dp) {
+#pragma clang fp contract(off)
+    constexpr int NP = MODEL == LERF_COORDS_HOMOGRAPHY ? 9 : MODEL == LERF_COORDS_RADIAL ? 8 : 21;
+    const Point q = model_point<MODEL>(p, i, j);
+    if (MODEL == LERF_COORDS_RADIAL) {
+        const double no = p[2], ni = p[3], hr = p[4], hc = p[5], k1 = p[6], k2 = p[7];
+        const double ur = ((double)i - hr) / no;
+        const double uc = ((double)j - hc) / no;
+        const double r2 = ur * ur + uc * uc;
+        const double f = (1.0 + k1 * r2) + (k2 * r2) * r2;
+        dp[0] = g.r;
+        dp[1] = g.c;
+        dp[3] = g.r * (ur * f) + g.c * (uc * f);
+        const double ar = g.r * ni, ac = g.c * ni;
+        const double df = ar * ur + ac * uc;
+        dp[6] = df * r2;
+        dp[7] = df * (r2 * r2);
+        const double dr2 = df * (k1 + (2.0 * k2) * r2);
+        const double dur = ar * f + dr2 * (2.0 * ur), duc = ac * f + dr2 * (2.0 * uc);
+        dp[4] = -(dur / no);
+        dp[5] = -(duc / no);
+        dp[2] = -((dur * ur + duc * uc) / no);
+    } else {
+        const double u = (double)j, v = (double)i;
+        const double Wh = p[6] * u + p[7] * v + p[8];                   // project_unclipped's statement
+        double dx, dy, x, y;
+        if (MODEL == LERF_COORDS_HOMOGRAPHY) {
+            x = q.c; y = q.r;
+            dx = g.c; dy = g.r;
+        } else {
+            const double fx = p[9], fy = p[10];
+            const double k1 = p[13], k2 = p[14], p1 = p[15], p2 = p[16], k3 = p[17], k4 = p[18], k5 = p[19], k6 = p[20];
+            project_unclipped(p, i, j, &y, &x);
+            const double r2 = x * x + y * y;
+            const double den = 1.0 + r2 * (k4 + r2 * (k5 + r2 * k6));
+            const double rad = (1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))) / den;
+            const double xy = x * y;
+            const double a1 = r2 + 2.0 * (x * x), a2 = r2 + 2.0 * (y * y);
+            const double xd = (x * rad + (2.0 * p1) * xy) + p2 * a1;
+            const double yd = (y * rad + p1 * a2) + (2.0 * p2) * xy;
+            dp[9] = g.c * xd;
+            dp[11] = g.c;
+            dp[10] = g.r * yd;
+            dp[12] = g.r;
+            const double dxd = g.c * fx, dyd = g.r * fy;
+            dp[15] = dxd * (2.0 * xy) + dyd * a2;
+            dp[16] = dxd * a1 + dyd * (2.0 * xy);
+            const double drad = dxd * x + dyd * y;
+            const double dnum = drad / den, dden = -((drad * rad) / den);
+            const double r4 = r2 * r2, r6 = r4 * r2;
+            dp[13] = dnum * r2; dp[14] = dnum * r4; dp[17] = dnum * r6;
+            dp[18] = dden * r2; dp[19] = dden * r4; dp[20] = dden * r6;
+            const double dr2 = (dnum * (k1 + r2 * (2.0 * k2 + r2 * (3.0 * k3))) + dden * (k4 + r2 * (2.0 * k5 + r2 * (3.0 * k6)))) +
+                               (dxd * p2 + dyd * p1);
+            dx = (((dxd * rad + dxd * ((2.0 * p1) * y)) + (dxd * p2) * (4.0 * x)) + dyd * ((2.0 * p2) * y)) + dr2 * (2.0 * x);
+            dy = (((dyd * rad + (dyd * p1) * (4.0 * y)) + dxd * ((2.0 * p1) * x)) + dyd * ((2.0 * p2) * x)) + dr2 * (2.0 * y);
+        }
+        const double dX = dx / Wh, dY = dy / Wh, dWh = -((dx * x + dy * y) / Wh);
+        dp[0] = dX * u; dp[1] = dX * v; dp[2] = dX;
+        dp[3] = dY * u; dp[4] = dY * v; dp[5] = dY;
+        dp[6] = dWh * u; dp[7] = dWh * v; dp[8] = dWh;
+    }
+    const bool fin = finite_value(q.r) && finite_value(q.c);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) dp[k] = fin ? dp[k] : 0.0;             // a select: a point that is not finite contributes nothing
+}
+
+// the band a block of the build backward's pass 1 owns, and the fixed-order tree of 64 values (the host twin's form of the wave's
+// shuffle tree): v[0] is the result
+constexpr int kBwdCols = 64, kBwdBand = 64, kBwdWaves = 4;
+
+inline int build_bwd_blocks(int oH, int oW) { return ((oW + kBwdCols - 1) / kBwdCols) * ((oH + kBwdBand - 1) / kBwdBand); }
+
+inline double tree64(double* v) {
+#pragma clang fp contract(off)
+    for (int off = 32; off > 0; off >>= 1)
+        for (int l = 0; l < off; ++l) v[l] = v[l] + v[l + off];
+    return v[0];
 }
 
 // ---- mesh: the taps of output index k along one axis of n outputs over g vertices; returns the tap count (2 or 4)

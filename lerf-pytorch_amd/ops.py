@@ -1063,6 +1063,78 @@ def coords_build(model, params, out_hw, dtype=None, out=None, origin=(0, 0), dev
     return out
 
 
+def _params_tensor(model, params, what):
+    """(model code, detached contiguous float64 device tensor [n] or [B, n]) of a model's parameters held on the device"""
+    torch = _torch()
+    if model not in _lib.COORDS_MODELS:
+        raise ValueError("unknown coordinate-map model %r (known: %s)" % (model, ", ".join(_lib.COORDS_MODELS)))
+    n = (9, 8, 21)[_lib.COORDS_MODELS[model]]
+    if not isinstance(params, torch.Tensor) or not params.is_cuda or params.dtype != torch.float64 or params.ndim not in (1, 2) \
+            or params.shape[-1] != n or params.shape[0] < 1:
+        raise ValueError("%s: params must be a float64 device tensor [%d] or [B, %d] for model %r" % (what, n, n, model))
+    return _lib.COORDS_MODELS[model], params.detach().contiguous()
+
+
+def coords_build_params(model, params, out_hw, dtype=None, out=None, origin=(0, 0)):
+    """lerf_coords_build_dev: coords_build with the parameters read from DEVICE memory -- params float64 [n] -> the map
+    [oH, oW, 2], or [B, n] -> [B, oH, oW, 2], one map per parameter set in ONE launch; no host round trip, no sync.  Map b is
+    bit-equal to coords_build of the same doubles.  Non-finite parameters are not refused (the host does not see them).  out: a
+    device tensor of that shape or a strided tile view of a larger buffer, built in place at `origin`; else a new tensor of
+    `dtype` (default float64) on params' device."""
+    torch = _torch()
+    code, p = _params_tensor(model, params, "lerf_coords_build_dev")
+    oH, oW = int(out_hw[0]), int(out_hw[1])
+    B = 1 if p.ndim == 1 else int(p.shape[0])
+    if out is None:
+        dtype = torch.float64 if dtype is None else dtype
+        if oH < 1 or oW < 1:
+            raise ValueError("lerf_coords_build_dev: out_hw must be positive")
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("lerf_coords_build_dev: dtype is torch.float32 or torch.float64")
+        out = torch.empty(((oH, oW, 2) if p.ndim == 1 else (B, oH, oW, 2)), dtype=dtype, device=p.device)
+    elif not isinstance(out, torch.Tensor) or out.ndim != p.ndim + 2 or tuple(out.shape[-3:]) != (oH, oW, 2) or (p.ndim == 2 and out.shape[0] != B):
+        raise ValueError("lerf_coords_build_dev: out must be %s" % ("[%d, %d, 2]" % (oH, oW) if p.ndim == 1 else "[%d, %d, %d, 2]" % (B, oH, oW)))
+    elif out.device != p.device:
+        raise ValueError("lerf_coords_build_dev: params and out live on different devices")
+    _, stride = _map_tensor(out if p.ndim == 1 else out[0], "out")
+    set_stride = 0 if p.ndim == 1 else int(out.stride(0))
+    with _lib.on_device(out):
+        _lib.check(_lib.lib().lerf_coords_build_dev(code, p.data_ptr(), B, int(p.shape[-1]), out.data_ptr(), _lib._dt(out), set_stride, stride,
+                                                    oH, oW, int(origin[0]), int(origin[1]), _lib.current_stream(out.device)),
+                   "lerf_coords_build_dev")
+    return out
+
+
+def coords_build_bwd(model, params, grad_map, grad_params=None, origin=(0, 0)):
+    """lerf_coords_build_bwd: ACCUMULATE the adjoint of coords_build_params(model, params) of grad_map (float64 contiguous
+    [oH, oW, 2], or [B, oH, oW, 2] for params [B, n]) into grad_params (float64 contiguous, params' shape; None: a zeroed one):
+    d loss / d every entry of the parameter vector.  An entry whose forward point is not finite contributes nothing.  Two
+    launches, fixed summation order, no atomics: two calls on the same input are bit-equal, and equal to
+    _lib.coords_build_bwd_host."""
+    torch = _torch()
+    code, p = _params_tensor(model, params, "lerf_coords_build_bwd")
+    g = grad_map
+    if not isinstance(g, torch.Tensor) or not g.is_cuda or g.dtype != torch.float64 or g.ndim != p.ndim + 2 or g.shape[-1] != 2 \
+            or not g.is_contiguous() or g.shape[-3] < 1 or g.shape[-2] < 1 or (p.ndim == 2 and g.shape[0] != p.shape[0]):
+        raise ValueError("lerf_coords_build_bwd: grad_map must be a contiguous float64 device tensor [oH, oW, 2] ([B, oH, oW, 2] for "
+                         "params [B, n])")
+    if g.device != p.device:
+        raise ValueError("lerf_coords_build_bwd: params and grad_map live on different devices")
+    if grad_params is None:
+        grad_params = torch.zeros(tuple(p.shape), dtype=torch.float64, device=g.device)
+    elif not isinstance(grad_params, torch.Tensor) or grad_params.dtype != torch.float64 or tuple(grad_params.shape) != tuple(p.shape) \
+            or not grad_params.is_contiguous() or grad_params.device != g.device:
+        raise ValueError("lerf_coords_build_bwd: grad_params must be contiguous float64 of params' shape on grad_map's device")
+    B, n, oH, oW = (1 if p.ndim == 1 else int(p.shape[0])), int(p.shape[-1]), int(g.shape[-3]), int(g.shape[-2])
+    need = int(_lib.lib().lerf_coords_build_bwd_workspace_bytes(n, B, oH, oW))
+    with _lib.on_device(g):
+        ws = _cached_workspace(need, g.device)
+        _lib.check(_lib.lib().lerf_coords_build_bwd(code, p.data_ptr(), B, n, g.data_ptr(), oH, oW, int(origin[0]), int(origin[1]),
+                                                    grad_params.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream(g.device)),
+                   "lerf_coords_build_bwd")
+    return grad_params
+
+
 def _ctrl_tensor(ctrl, what):
     torch = _torch()
     if not isinstance(ctrl, torch.Tensor) or not ctrl.is_cuda or ctrl.ndim != 3 or ctrl.shape[2] != 2:
