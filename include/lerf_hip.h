@@ -685,7 +685,7 @@ int lerf_remap_bwd_batched(const float* feat, const float* h0, const float* h1, 
  * unknown model, dtype or interp, a parameter count that is not the model's, a non-finite model parameter (where the parameters
  * are HOST memory: lerf_coords_build, lerf_coords_build_host), a negative origin or a tile outside the whole map, a short
  * workspace.  Operands must not overlap the output. */
-enum { LERF_COORDS_HOMOGRAPHY = 0, LERF_COORDS_RADIAL = 1, LERF_COORDS_BROWN = 2 };
+enum { LERF_COORDS_HOMOGRAPHY = 0, LERF_COORDS_RADIAL = 1, LERF_COORDS_BROWN = 2, LERF_COORDS_FISHEYE = 16, LERF_COORDS_EQUIRECT = 17 };
 enum { LERF_MESH_BILINEAR = 0, LERF_MESH_BICUBIC = 1 };
 #define LERF_COORDS_MAX_PARAMS 21
 
@@ -702,6 +702,17 @@ enum { LERF_MESH_BILINEAR = 0, LERF_MESH_BICUBIC = 1 };
  *                              through, r2 = x x + y y, rad = (1 + r2 (k1 + r2 (k2 + r2 k3))) / (1 + r2 (k4 + r2 (k5 + r2 k6))),
  *                              x'' = x rad + 2 p1 x y + p2 (r2 + 2 x x), y'' = y rad + p1 (r2 + 2 y y) + 2 p2 x y,
  *                              col = fx x'' + cx, row = fy y'' + cy
+ *   LERF_COORDS_FISHEYE    17: m[9] = inv(new_K . R), fx, fy, cx, cy, k1, k2, k3, k4 -- cv::fisheye::initUndistortRectifyMap's
+ *                              equidistant model without skew: (x, y) = m (j, i, 1) divided through by Wh; Wh <= 0 (a ray behind the
+ *                              camera): (NaN, NaN); r = sqrt(x x + y y), th = atan(r), th_d = th (1 + k1 th^2 + k2 th^4 + k3 th^6 +
+ *                              k4 th^8), s = th_d / r (1 at r = 0), col = fx x s + cx, row = fy y s + cy
+ *   LERF_COORDS_EQUIRECT   13: m[9] = inv(K_view . R), sx, sy, cxp, cyp -- a pinhole view of an equirectangular panorama:
+ *                              d = m (j, i, 1), lon = atan2(d.x, d.z), lat = atan2(d.y, sqrt(d.x d.x + d.z d.z)),
+ *                              col = cxp + sx lon, row = cyp + sy lat; for a panorama [Hp][Wp]: sx = Wp / (2 pi), sy = Hp / pi,
+ *                              cxp = (Wp - 1) / 2, cyp = (Hp - 1) / 2.  The seam lon = +-pi is clipped like any border.
+ * Codes 3 .. 15 are not models.  The models from 16 on take their square root and arc tangents from sqrt_pm / atan_pm / atan2_pm
+ * of csrc/lerf_coords_models.h (float64 + - * /, selects and bit-casts; within 1 ulp (sqrt, atan) and 2 ulp (atan2) of the exact
+ * value, NOT equal to a math library's), so they too agree bit for bit between a device entry point and its host twin.
  * (the rounding order of every statement: the top of csrc/lerf_coords_models.h). */
 int lerf_coords_build(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride,
                       int oH, int oW, int i0, int j0, void* stream);
@@ -820,7 +831,7 @@ int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride
  * lerf_coords_build_dev is lerf_coords_build with two changes: params_dev is DEVICE memory, float64 [n_sets][n_params], dense, and
  * n_sets >= 1 maps are written in one launch, map s at out + s * set_stride ELEMENTS (each map under the strided contract with
  * row_stride; set_stride even and, for n_sets > 1, >= (oH - 1) * row_stride + 2 * oW).  Map s is bit-equal to lerf_coords_build
- * of the same 9 / 8 / 21 doubles; lerf_coords_build_host per set is the host twin.  No host round trip, no sync: the parameters
+ * of the same 9 / 8 / 21 / 17 / 13 doubles; lerf_coords_build_host per set is the host twin.  No host round trip, no sync: the parameters
  * are not visible to the host, so NON-FINITE PARAMETERS ARE NOT REFUSED here (they give non-finite entries, which the remap
  * treats as it treats any map's).  Everything else on the family's list is refused, and n_sets outside 1 .. 65535, a misaligned
  * params_dev, params_dev's bytes intersecting the maps'.
@@ -850,6 +861,15 @@ int lerf_coords_build_bwd(int model, const double* params_dev, int n_sets, int n
                           void* workspace, size_t workspace_bytes, void* stream);
 int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int n_params, const double* grad_map,
                                int oH, int oW, int i0, int j0, double* grad_params);
+
+/* The helpers of the fisheye and equirect models on their own, for tests: out[e] = sqrt_pm(x[e]) / atan_pm(x[e]) / atan2_pm(x[e], y[e])
+ * for e < n, float64, dense.  y is ignored (and may be null) for the unary ops; out may be x or y.  lerf_coords_math takes DEVICE
+ * pointers and runs one thread per element (one launch on `stream`, no sync); lerf_coords_math_host is its host twin, bit-equal.
+ * Refused with LERF_EINVAL before anything is written: a null x or out, a null y for LERF_MATH_ATAN2, n < 0 or n > 2^31 - 1, an
+ * unknown op.  n == 0 is a no-op. */
+enum { LERF_MATH_SQRT = 0, LERF_MATH_ATAN = 1, LERF_MATH_ATAN2 = 2 };
+int lerf_coords_math(int op, const double* x, const double* y, int64_t n, double* out, void* stream);
+int lerf_coords_math_host(int op, const double* x, const double* y, int64_t n, double* out);
 
 #ifdef __cplusplus
 }

@@ -57,7 +57,7 @@ EXPORTS = [
     "lerf_coords_build", "lerf_coords_build_host", "lerf_coords_mesh", "lerf_coords_mesh_host", "lerf_coords_mesh_bwd_workspace_bytes",
     "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host", "lerf_coords_invert", "lerf_coords_invert_host",
     "lerf_coords_compose_bwd", "lerf_coords_compose_bwd_host", "lerf_coords_invert_bwd", "lerf_coords_invert_bwd_host",
-    "lerf_coords_build_dev", "lerf_coords_build_bwd_workspace_bytes", "lerf_coords_build_bwd", "lerf_coords_build_bwd_host",
+    "lerf_coords_build_dev", "lerf_coords_build_bwd_workspace_bytes", "lerf_coords_build_bwd", "lerf_coords_build_bwd_host", "lerf_coords_math", "lerf_coords_math_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -130,8 +130,9 @@ class WarpGeo(C.Structure):
 REMAP_PADS_FROM_MAP = -1
 
 # coordinate-map builders (include/lerf_hip.h LERF_COORDS_*, LERF_MESH_*)
-COORDS_MODELS = {"homography": 0, "radial": 1, "brown": 2}
-COORDS_MODEL_PARAMS = {"homography": 9, "radial": 8, "brown": 21}
+COORDS_MODELS = {"homography": 0, "radial": 1, "brown": 2, "fisheye": 16, "equirect": 17}
+COORDS_MODEL_PARAMS = {"homography": 9, "radial": 8, "brown": 21, "fisheye": 17, "equirect": 13}
+COORDS_MATH_OPS = {"sqrt": 0, "atan": 1, "atan2": 2}
 MESH_INTERPS = {"bilinear": 0, "bicubic": 1}
 
 
@@ -317,6 +318,8 @@ def lib():
                                         C.c_int, C.c_int, C.c_void_p]
     _build_bwd = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.lerf_coords_build_bwd.argtypes, L.lerf_coords_build_bwd_host.argtypes = _build_bwd + [C.c_void_p, C.c_size_t, C.c_void_p], _build_bwd
+    _math = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.lerf_coords_math.argtypes, L.lerf_coords_math_host.argtypes = _math + [C.c_void_p], _math
     L.lerf_coords_build_bwd_workspace_bytes.restype = C.c_size_t
     L.lerf_coords_build_bwd_workspace_bytes.argtypes = [C.c_int] * 4
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -439,11 +442,19 @@ def _np_out(out, out_hw, dtype, what):
     return _np_map(out, "out")
 
 
-def coords_model_params(model, params):
-    """(model code, float64 parameter vector) of a coordinate-map model; the count is checked by the library"""
+def coords_model_count(model, n, what):
+    """ValueError unless `model` is known and takes n parameters"""
     if model not in COORDS_MODELS:
         raise ValueError("unknown coordinate-map model %r (known: %s)" % (model, ", ".join(COORDS_MODELS)))
-    return COORDS_MODELS[model], np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+    if int(n) != COORDS_MODEL_PARAMS[model]:
+        raise ValueError("%s: unknown parameter layout for model %r: it takes %d parameters, not %d" % (what, model, COORDS_MODEL_PARAMS[model], n))
+
+
+def coords_model_params(model, params, what="lerf_coords_build"):
+    """(model code, float64 parameter vector) of a coordinate-map model"""
+    p = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+    coords_model_count(model, p.size, what)
+    return COORDS_MODELS[model], p
 
 
 def mesh_interp_code(interp):
@@ -454,7 +465,7 @@ def mesh_interp_code(interp):
 
 def coords_build_host(model, params, out_hw, dtype=np.float64, out=None, origin=(0, 0)):
     """lerf_coords_build_host: the map of a model built on the host by the kernels' own arithmetic (bit-equal to the device's)"""
-    code, p = coords_model_params(model, params)
+    code, p = coords_model_params(model, params, "lerf_coords_build_host")
     out, stride = _np_out(out, out_hw, dtype, "lerf_coords_build_host")
     check(lib().lerf_coords_build_host(code, p.ctypes.data, int(p.size), out.ctypes.data, _np_dt(out), stride, int(out_hw[0]),
                                        int(out_hw[1]), int(origin[0]), int(origin[1])), "lerf_coords_build_host")
@@ -540,7 +551,7 @@ def coords_invert_bwd_host(f, inverse, grad_out, grad_f=None):
 
 def coords_build_bwd_host(model, params, grad_map, origin=(0, 0)):
     """lerf_coords_build_bwd_host: the adjoint of the model builders on the host, in the device's summation order (bit-equal to it).
-    params float64 [n] or [B, n] (the model's 9 / 8 / 21), grad_map float64 [oH, oW, 2] or [B, oH, oW, 2] -> a NEW zeroed
+    params float64 [n] or [B, n] (n = COORDS_MODEL_PARAMS[model]), grad_map float64 [oH, oW, 2] or [B, oH, oW, 2] -> a NEW zeroed
     gradient of params' shape with the sums added (pre-filled buffers: the C entry point accumulates)."""
     if model not in COORDS_MODELS:
         raise ValueError("unknown coordinate-map model %r (known: %s)" % (model, ", ".join(COORDS_MODELS)))
@@ -548,12 +559,33 @@ def coords_build_bwd_host(model, params, grad_map, origin=(0, 0)):
     g = np.asarray(grad_map)
     if p.ndim not in (1, 2) or g.ndim != p.ndim + 2 or g.shape[-1] != 2 or (p.ndim == 2 and g.shape[0] != p.shape[0]):
         raise ValueError("lerf_coords_build_bwd_host: params is [n] with grad_map [oH, oW, 2], or [B, n] with [B, oH, oW, 2]")
+    coords_model_count(model, p.shape[-1], "lerf_coords_build_bwd_host")
     if g.dtype != np.float64 or not g.flags.c_contiguous:
         raise ValueError("lerf_coords_build_bwd_host: grad_map must be a C-contiguous float64 array")
     out = np.zeros(p.shape, np.float64)
     check(lib().lerf_coords_build_bwd_host(COORDS_MODELS[model], p.ctypes.data, 1 if p.ndim == 1 else p.shape[0], p.shape[-1], g.ctypes.data,
                                            g.shape[-3], g.shape[-2], int(origin[0]), int(origin[1]), out.ctypes.data),
           "lerf_coords_build_bwd_host")
+    return out
+
+
+def coords_math_host(op, x, y=None):
+    """lerf_coords_math_host: sqrt_pm(x), atan_pm(x) or atan2_pm(x, y) (op "sqrt", "atan", "atan2") of float64 arrays, element by element,
+    by the HOST twin of the helpers the fisheye and equirect models are built on (csrc/lerf_coords_models.h: + - * / only, bit-equal to
+    the device's ops.coords_math, a few ulp from numpy's) -> a new float64 array of x's shape"""
+    if op not in COORDS_MATH_OPS:
+        raise ValueError("op is one of %s, not %r" % (", ".join(COORDS_MATH_OPS), op))
+    a = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    b = None
+    if op == "atan2":
+        if y is None:
+            raise ValueError("lerf_coords_math_host: atan2 takes x and y")
+        b = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
+        if b.shape != a.shape:
+            raise ValueError("lerf_coords_math_host: x and y must have one shape")
+    out = np.empty(a.shape, np.float64)
+    check(lib().lerf_coords_math_host(COORDS_MATH_OPS[op], a.ctypes.data, None if b is None else b.ctypes.data, a.size, out.ctypes.data),
+          "lerf_coords_math_host")
     return out
 
 

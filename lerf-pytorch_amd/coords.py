@@ -7,12 +7,15 @@ transform, not per frame -- except from_flow_torch, which builds the map of a fl
 autograd graph (a flow fitted by gradient).
 
 With device=<a torch device> the builders write the map ON the device with the kernels of csrc/lerf_coords.hip (one store per
-entry, no host array, no upload): from_homography, radial, undistort_rectify, from_mesh; from_mesh_torch keeps a control mesh
+entry, no host array, no upload): from_homography, radial, undistort_rectify, fisheye_undistort_rectify, equirect_view,
+from_mesh; from_mesh_torch keeps a control mesh
 in the autograd graph through the mesh upsample's adjoint, compose chains two maps into one, and invert / invert_flow solve a
 map for its inverse (distort <-> undistort, forward flow -> backward map).  The kernels' arithmetic is
-float64 with + - * / only, bit-equal to its host twin (csrc/lerf_coords_models.h).
+float64 with + - * / only, bit-equal to its host twin (csrc/lerf_coords_models.h); the square root and arc tangents of the
+fisheye and equirectangular models are written in those operations too (_lib.coords_math_host), not taken from a math library.
 
-from_homography_torch, radial_torch and undistort_rectify_torch (with brown_params_torch) are the differentiable twins of the
+from_homography_torch, radial_torch, undistort_rectify_torch (with brown_params_torch), fisheye_undistort_rectify_torch (with
+fisheye_params_torch) and equirect_view_torch are the differentiable twins of the
 closed-form builders: their operands are DEVICE tensors (a matrix, lens coefficients, camera matrices -- one set or a leading
 batch B, one map per sample in one launch), the map is written by lerf_coords_build_dev from parameters that never leave the
 device, and a loss reaches the operands through lerf_coords_build_bwd: direct image alignment, calibration
@@ -178,19 +181,11 @@ def brown_params(K, dist=None, R=None, new_K=None):
     """The 21 parameters of the "brown" model from what cv::initUndistortRectifyMap takes: K (3 x 3 source camera, no skew), dist
     (k1 k2 p1 p2 [k3 [k4 k5 k6]], missing ones 0), R (rectifying rotation, default I), new_K (default K) ->
     inv(new_K . R)[9], fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6."""
-    K = _host(K)
-    if K.shape != (3, 3):
-        raise ValueError("K must be 3x3")
-    if K[0, 1] != 0.0 or K[1, 0] != 0.0 or K[2, 0] != 0.0 or K[2, 1] != 0.0 or K[2, 2] != 1.0:
-        raise ValueError("K must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (skew is not supported)")
+    K, R, new_K = _camera(K, R, new_K)
     d = np.zeros(8) if dist is None else _host(dist).reshape(-1)
     if d.size not in (4, 5, 8):
         raise ValueError("dist holds 4, 5 or 8 coefficients (k1 k2 p1 p2 [k3 [k4 k5 k6]])")
     d = np.concatenate([d, np.zeros(8 - d.size)])
-    R = np.eye(3) if R is None else _host(R)
-    new_K = K if new_K is None else _host(new_K)
-    if R.shape != (3, 3) or new_K.shape != (3, 3):
-        raise ValueError("R and new_K must be 3x3")
     minv = np.linalg.inv(np.dot(new_K, R))
     return np.concatenate([minv.reshape(9), [K[0, 0], K[1, 1], K[0, 2], K[1, 2]], d])
 
@@ -203,6 +198,69 @@ def undistort_rectify(K, dist, R, new_K, out_hw, device=None, dtype=None):
     device tensor written by the kernel -- bit-equal to each other.  remap() of a distorted frame with this map undistorts and
     rectifies it."""
     return _build("brown", brown_params(K, dist, R, new_K), out_hw, dtype, device)
+
+
+def _camera(K, R, new_K, what="K"):
+    """(K, R, new_K) as float64 host arrays, defaults filled in, K checked for skew"""
+    K = _host(K)
+    if K.shape != (3, 3):
+        raise ValueError("%s must be 3x3" % what)
+    if K[0, 1] != 0.0 or K[1, 0] != 0.0 or K[2, 0] != 0.0 or K[2, 1] != 0.0 or K[2, 2] != 1.0:
+        raise ValueError("%s must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (skew is not supported)" % what)
+    R = np.eye(3) if R is None else _host(R)
+    new_K = K if new_K is None else _host(new_K)
+    if R.shape != (3, 3) or new_K.shape != (3, 3):
+        raise ValueError("R and new_K must be 3x3")
+    return K, R, new_K
+
+
+def fisheye_params(K, dist4, R=None, new_K=None):
+    """The 17 parameters of the "fisheye" model from what cv::fisheye::initUndistortRectifyMap takes: K (3 x 3 source camera, no
+    skew), dist4 (k1 k2 k3 k4 of the equidistant model; None: all 0), R (rectifying rotation, default I), new_K (default K) ->
+    inv(new_K . R)[9], fx, fy, cx, cy, k1, k2, k3, k4."""
+    K, R, new_K = _camera(K, R, new_K)
+    d = np.zeros(4) if dist4 is None else _host(dist4).reshape(-1)
+    if d.size != 4:
+        raise ValueError("dist holds the 4 coefficients k1 k2 k3 k4 of the fisheye model")
+    minv = np.linalg.inv(np.dot(new_K, R))
+    return np.concatenate([minv.reshape(9), [K[0, 0], K[1, 1], K[0, 2], K[1, 2]], d])
+
+
+def fisheye_undistort_rectify(K, dist, R, new_K, out_hw, device=None, dtype=None):
+    """The map of cv::fisheye::initUndistortRectifyMap (the equidistant fisheye model, 4 coefficients, a rectifying rotation R and
+    the new camera matrix new_K; R and new_K may be None = identity / K, no skew): output pixel (u = j, v = i) of the PINHOLE
+    view goes through inv(new_K . R) to the normalised (x, y), r = |(x, y)|, theta = atan(r), theta_d = theta (1 + k1 theta^2 +
+    k2 theta^4 + k3 theta^6 + k4 theta^8), and lands at (row, col) = (fy y theta_d / r + cy, fx x theta_d / r + cx) of the fisheye
+    frame.  A ray behind the camera (Wh <= 0) has no source: (NaN, NaN), which the remap masks.  [oH, oW, 2], float64 (default) or
+    float32; device None: host numpy through the kernel's host twin, else a device tensor written by the kernel -- bit-equal to
+    each other: the square root and the arc tangent are the library's own (csrc/lerf_coords_models.h), within 1 ulp of numpy's
+    and not equal to them.  remap() of a fisheye frame with this map rectifies it to the pinhole view.  The opposite direction
+    needs no model of its own: invert(this map, fisheye_hw) is the map that distorts a pinhole frame into the fisheye's."""
+    return _build("fisheye", fisheye_params(K, dist, R, new_K), out_hw, dtype, device)
+
+
+def equirect_params(pano_hw, K_view, R=None):
+    """The 13 parameters of the "equirect" model: a panorama of pano_hw = (Hp, Wp) pixels (pixel centres; longitude -pi .. pi
+    over the width, latitude -pi/2 .. pi/2 over the height, rows growing with the view's y), the pinhole view's camera matrix
+    K_view (3 x 3, no skew) and its rotation R (view -> panorama axes, default I) ->
+    inv(K_view . R)[9], sx = Wp / (2 pi), sy = Hp / pi, cxp = (Wp - 1) / 2, cyp = (Hp - 1) / 2."""
+    Hp, Wp = int(pano_hw[0]), int(pano_hw[1])
+    if Hp < 1 or Wp < 1:
+        raise ValueError("pano_hw must be positive")
+    K, R, _ = _camera(K_view, R, None, "K_view")
+    minv = np.linalg.inv(np.dot(K, R))
+    return np.concatenate([minv.reshape(9), [Wp / (2.0 * np.pi), Hp / np.pi, (Wp - 1) / 2.0, (Hp - 1) / 2.0]])
+
+
+def equirect_view(pano_hw, K_view, R, out_hw, device=None, dtype=None):
+    """The map of a pinhole view of an equirectangular (360 degree) panorama: output pixel (u = j, v = i) is the ray
+    d = inv(K_view . R) (u, v, 1), lon = atan2(d.x, d.z), lat = atan2(d.y, |(d.x, d.z)|), and reads the panorama at
+    (row, col) = (cyp + sy lat, cxp + sx lon) (equirect_params).  R may be None.  The seam lon = +-pi is an ordinary border: the
+    remap clips there, it does not wrap around.  [oH, oW, 2], float64 (default) or float32; device None: the kernel's host twin,
+    else a device tensor written by the kernel, bit-equal to each other (the library's own square root and arc tangent, see
+    fisheye_undistort_rectify).  remap() of a panorama with this map renders the view; invert(this map, pano_hw) is the map
+    that pastes the view back into the panorama's frame (NaN where the view does not reach)."""
+    return _build("equirect", equirect_params(pano_hw, K_view, R), out_hw, dtype, device)
 
 
 def from_mesh(ctrl, out_hw, interp="bilinear", device=None, dtype=None):
@@ -641,11 +699,15 @@ def brown_params_torch(K, dist=None, R=None, new_K=None):
     (missing coefficients 0; None: all 0), R [3, 3] (None: identity), new_K [3, 3] (None: K), each a float32 / float64 device
     tensor, single or behind a leading B (single operands are shared by the batch) -> float64 [21] or [B, 21]:
     inv(new_K . R) by torch.linalg.inv, fx, fy, cx, cy picked from K, dist padded to 8.  The skew check reads K (one sync)."""
+    return _camera_params_torch("brown_params_torch", K, dist, R, new_K, [(4,), (5,), (8,)], 8)
+
+
+def _camera_params_torch(what, K, dist, R, new_K, dist_shapes, n_dist):
+    """inv(new_K . R)[9], fx, fy, cx, cy, dist padded to n_dist -> float64 [13 + n_dist] or [B, 13 + n_dist], in torch ops"""
     import torch
-    what = "brown_params_torch"
     ops_, sizes = [K], [_operand(K, what + ": K", [(3, 3)])]
     if dist is not None:
-        ops_.append(dist), sizes.append(_operand(dist, what + ": dist", [(4,), (5,), (8,)]))
+        ops_.append(dist), sizes.append(_operand(dist, what + ": dist", dist_shapes))
     for t, name in ((R, "R"), (new_K, "new_K")):
         if t is not None:
             ops_.append(t), sizes.append(_operand(t, "%s: %s" % (what, name), [(3, 3)]))
@@ -661,9 +723,9 @@ def brown_params_torch(K, dist=None, R=None, new_K=None):
     minv = torch.linalg.inv(torch.matmul(Nd, Rd)).expand(lead + (3, 3))
     Kd = Kd.expand(lead + (3, 3))
     cam = torch.stack([Kd[..., 0, 0], Kd[..., 1, 1], Kd[..., 0, 2], Kd[..., 1, 2]], dim=-1)
-    d = torch.zeros(lead + (8,), dtype=torch.float64, device=K.device) if dist is None else dist.double().expand(lead + (dist.shape[-1],))
-    if d.shape[-1] < 8:
-        d = torch.cat([d, torch.zeros(lead + (8 - d.shape[-1],), dtype=torch.float64, device=K.device)], dim=-1)
+    d = torch.zeros(lead + (n_dist,), dtype=torch.float64, device=K.device) if dist is None else dist.double().expand(lead + (dist.shape[-1],))
+    if d.shape[-1] < n_dist:
+        d = torch.cat([d, torch.zeros(lead + (n_dist - d.shape[-1],), dtype=torch.float64, device=K.device)], dim=-1)
     return torch.cat([minv.reshape(lead + (9,)), cam, d], dim=-1)
 
 
@@ -674,3 +736,36 @@ def undistort_rectify_torch(K, dist, R, new_K, out_hw, dtype=None):
     adjoint lerf_coords_build_bwd, the assembly (the 3 x 3 inverse included) through autograd.  Calibration refinement: fit k1 ..
     k6, p1, p2, fx, fy, cx, cy against a rectified target through a remap class that has opted in with enable_backward()."""
     return _build_torch("brown", brown_params_torch(K, dist, R, new_K), out_hw, _map_dtype(dtype, K.dtype))
+
+
+def fisheye_params_torch(K, dist4=None, R=None, new_K=None):
+    """fisheye_params in torch ops on the operands' device, differentiable in all four: K [3, 3] (no skew), dist4 [4] (None: all 0), R
+    [3, 3] (None: identity), new_K [3, 3] (None: K), each a float32 / float64 device tensor, single or behind a leading B (single
+    operands are shared by the batch) -> float64 [17] or [B, 17].  The skew check reads K (one sync)."""
+    return _camera_params_torch("fisheye_params_torch", K, dist4, R, new_K, [(4,)], 4)
+
+
+def fisheye_undistort_rectify_torch(K, dist, R, new_K, out_hw, dtype=None):
+    """fisheye_undistort_rectify on the operands' device, differentiable: the operands of fisheye_params_torch (device tensors,
+    single or behind a leading B, one map per sample in one launch; dist, R and new_K may be None) -> the map [oH, oW, 2] or
+    [B, oH, oW, 2] in K's dtype (or `dtype`).  K, dist, R and new_K each receive a gradient when they require one: the 17
+    parameters go through lerf_coords_build_dev and its adjoint lerf_coords_build_bwd, the assembly (the inverse of new_K . R
+    included) through autograd.  An entry behind the camera contributes nothing; at the principal ray the gradient is the
+    pinhole's.  invert_torch of this map distorts a pinhole frame."""
+    return _build_torch("fisheye", fisheye_params_torch(K, dist, R, new_K), out_hw, _map_dtype(dtype, K.dtype))
+
+
+def equirect_view_torch(pano_hw, K_view, R, out_hw, dtype=None):
+    """equirect_view on the operands' device, differentiable in K_view and R: K_view [3, 3] (no skew) and R [3, 3] (None: identity)
+    float32 / float64 device tensors, single or behind a leading B -> the map [oH, oW, 2] or [B, oH, oW, 2] in K_view's dtype (or
+    `dtype`).  The panorama's scalars (equirect_params) are constants: the kernel returns their gradient entries and they are
+    dropped.  At a pole (d.x = d.z = 0) the matrix receives nothing from that entry.  invert_torch of this map pastes a view
+    into the panorama's frame."""
+    import torch
+    Hp, Wp = int(pano_hw[0]), int(pano_hw[1])
+    if Hp < 1 or Wp < 1:
+        raise ValueError("pano_hw must be positive")
+    cam = _camera_params_torch("equirect_view_torch", K_view, None, R, None, [], 0)          # inv(K_view . R)[9], fx, fy, cx, cy
+    pano = torch.tensor([Wp / (2.0 * np.pi), Hp / np.pi, (Wp - 1) / 2.0, (Hp - 1) / 2.0], dtype=torch.float64, device=K_view.device)
+    params = torch.cat([cam[..., :9], pano.expand(tuple(cam.shape[:-1]) + (4,))], dim=-1)
+    return _build_torch("equirect", params, out_hw, _map_dtype(dtype, K_view.dtype))

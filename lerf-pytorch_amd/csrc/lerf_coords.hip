@@ -1,7 +1,8 @@
 // Coordinate maps built, upsampled, composed and inverted on the device: the maps lerf_remap reads (lerf_remap_geo_t.coords), written by
 // kernels instead of host numpy + an upload.  The arithmetic of every entry is lerf_coords_models.h (float64, + - * / only, no
 // FMA contraction), shared with the host twins at the end of this file, which run the same functions in a plain loop over host
-// pointers: device and host agree bit for bit.
+// pointers: device and host agree bit for bit.  The fisheye and equirect models (codes 16, 17) take their square root and arc
+// tangents from the same header (sqrt_pm, atan_pm, atan2_pm), not from a math library, so the same holds for them.
 //
 //   coords_build_kernel<MODEL, TO>          one thread per entry: the model's point of pixel (i0 + i, j0 + j), ONE 16-byte (float64)
 //                                           or 8-byte (float32) store; the 64 lanes of a wave write 64 consecutive entries of a row
@@ -41,12 +42,15 @@
 //                                           the set, its parameters are read at a wave-uniform address (scalar loads), model_point is
 //                                           called unchanged: map s is bit-equal to lerf_coords_build of the same doubles
 //   coords_build_bwd_{partial,sum}_kernel   the adjoint of the builders, grad_params[s][k] += sum over the entries of dp[k] (model_point_bwd):
-//                                           a reduction of 9 / 8 / 21 sums over every entry, in two passes, fixed order, no atomics
+//                                           a reduction of 9 / 8 / 21 / 17 / 13 sums over every entry, in two passes, fixed order, no atomics
 //       partial  a block owns 64 columns x a band of 64 rows of one set; wave w takes the rows w, w + 4, ... of the band (16 per lane),
 //                every lane keeps its n_params running sums in registers; a shuffle tree (offsets 32 .. 1) per sum, the 4 wave sums meet in
 //                LDS and are added in the order 0, 1, 2, 3; ONE partial vector per block goes to the workspace ([set][k][block])
 //       sum      ONE wave per (set, k): lane l adds the partials l, l + 64, ..., the same tree, lane 0 is the one writer (load-add-store)
 //       2160 x 3840: 2 040 blocks a set in pass 1 (8 per CU), 343 KB of partials for the 21 sums of brown; grad_map is read once, coalesced
+//
+//   coords_math_kernel                      sqrt_pm / atan_pm / atan2_pm of lerf_coords_models.h, one thread per element: what the fisheye and
+//                                           equirect models are built on, exported so that their bit-equality with the host is tested directly
 //
 // Addresses: every kernel guards (i, j) against the tile, writes entry (i, j) of `out` only, and reads ctrl / A at indices that
 // mesh_axis / compose_axis clamp into the operand after clipping the position in floating point (no value of B reaches an int
@@ -56,7 +60,8 @@
 // B / G, grad_out and grad_b at entry (i, j) only, and read A / F and add into grad_a / grad_f at the cell compose_axis picks (aH, aW,
 // fH, fW >= 2 are checked on the host, so i0 + 1 <= n - 1), whatever the maps hold.  The kernels that read device parameters index
 // params and grad_params inside [n_sets][n_params], grad_map at (set, i, j) with i < oH, j < oW, the workspace inside
-// [n_sets][n_params][blocks]; no parameter value forms an address.
+// [n_sets][n_params][blocks]; no parameter value forms an address.  coords_math_kernel reads x (and y, for atan2 only) and writes out at
+// element e < n alone; no argument value forms an address.
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
 
@@ -242,7 +247,7 @@ template <int MODEL, typename TO>
 __global__ void __launch_bounds__(CB_COLS * CB_ROWS)
 coords_build_dev_kernel(const double* __restrict__ params, TO* __restrict__ out, int64_t set_stride, int64_t stride, int oH, int oW, int i0,
                         int j0) {
-    constexpr int NP = MODEL == LERF_COORDS_HOMOGRAPHY ? 9 : MODEL == LERF_COORDS_RADIAL ? 8 : 21;
+    constexpr int NP = model_params(MODEL);
     const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
     if (i >= oH || j >= oW) return;
     const double* p = params + (size_t)blockIdx.z * NP;                 // the same address in every lane: scalar loads
@@ -257,7 +262,7 @@ __global__ void __launch_bounds__(CB_COLS * CB_ROWS)
 coords_build_bwd_partial_kernel(const double* __restrict__ params, const double2* __restrict__ gmap, int oH, int oW, int i0, int j0,
                                 double* __restrict__ part) {
 #pragma clang fp contract(off)
-    constexpr int NP = MODEL == LERF_COORDS_HOMOGRAPHY ? 9 : MODEL == LERF_COORDS_RADIAL ? 8 : 21;
+    constexpr int NP = model_params(MODEL);
     __shared__ double wsum[kBwdWaves][NP];
     const int s = blockIdx.z, w = threadIdx.y, j = blockIdx.x * CB_COLS + threadIdx.x;
     const double* p = params + (size_t)s * NP;
@@ -298,6 +303,14 @@ coords_build_bwd_sum_kernel(const double* __restrict__ part, int nblk, double* _
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
     if (threadIdx.x == 0) gparams[e] = gparams[e] + v;
+}
+
+// the helpers of the lens models on their own (lerf_coords_math): one thread per element, grid ceil(n / 256)
+__global__ void __launch_bounds__(256)
+coords_math_kernel(int op, const double* __restrict__ x, const double* __restrict__ y, int64_t n, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    out[e] = op == LERF_MATH_SQRT ? sqrt_pm(x[e]) : op == LERF_MATH_ATAN ? atan_pm(x[e]) : atan2_pm(x[e], y[e]);
 }
 
 // ------------------------------------------------------------------------------------------------ argument checks (host)
@@ -427,6 +440,24 @@ inline int build_bwd_args(int model, const double* params, int n_sets, int n_par
     return LERF_OK;
 }
 
+// run F with MODEL = the compile-time constant of a model code the argument checks have accepted
+#define LERF_COORDS_MODEL(code, MODEL, ...)                                                                  \
+    do {                                                                                                     \
+        switch (code) {                                                                                      \
+            case LERF_COORDS_HOMOGRAPHY: { constexpr int MODEL = LERF_COORDS_HOMOGRAPHY; __VA_ARGS__; } break; \
+            case LERF_COORDS_RADIAL: { constexpr int MODEL = LERF_COORDS_RADIAL; __VA_ARGS__; } break;       \
+            case LERF_COORDS_BROWN: { constexpr int MODEL = LERF_COORDS_BROWN; __VA_ARGS__; } break;         \
+            case LERF_COORDS_FISHEYE: { constexpr int MODEL = LERF_COORDS_FISHEYE; __VA_ARGS__; } break;     \
+            default: { constexpr int MODEL = LERF_COORDS_EQUIRECT; __VA_ARGS__; } break;                     \
+        }                                                                                                    \
+    } while (0)
+
+inline int math_args(int op, const double* x, const double* y, int64_t n, const double* out) {
+    if (op != LERF_MATH_SQRT && op != LERF_MATH_ATAN && op != LERF_MATH_ATAN2) return LERF_EINVAL;
+    if (!x || !out || (op == LERF_MATH_ATAN2 && !y) || n < 0 || n > 0x7fffffff) return LERF_EINVAL;
+    return LERF_OK;
+}
+
 inline dim3 entry_grid(int oH, int oW) { return dim3((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS); }
 
 }  // namespace coords
@@ -452,14 +483,8 @@ int lerf_coords_build(int model, const double* params, int n_params, void* out, 
     clear_stale_error();
     const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
     hipStream_t st = (hipStream_t)stream;
-#define LERF_CB(MODEL) \
-    LERF_COORDS_DT(out_dtype, TO, hipLaunchKernelGGL((coords_build_kernel<MODEL, TO>), grid, block, 0, st, prm, (TO*)out, row_stride, oH, oW, i0, j0))
-    switch (model) {
-        case LERF_COORDS_HOMOGRAPHY: LERF_CB(LERF_COORDS_HOMOGRAPHY); break;
-        case LERF_COORDS_RADIAL: LERF_CB(LERF_COORDS_RADIAL); break;
-        default: LERF_CB(LERF_COORDS_BROWN); break;
-    }
-#undef LERF_CB
+    LERF_COORDS_MODEL(model, MODEL, LERF_COORDS_DT(out_dtype, TO,
+        hipLaunchKernelGGL((coords_build_kernel<MODEL, TO>), grid, block, 0, st, prm, (TO*)out, row_stride, oH, oW, i0, j0)));
     return launch_status();
 }
 
@@ -569,15 +594,8 @@ int lerf_coords_build_dev(int model, const double* params_dev, int n_sets, int n
     clear_stale_error();
     const dim3 block(CB_COLS, CB_ROWS), grid((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS, n_sets);
     hipStream_t st = (hipStream_t)stream;
-#define LERF_CBD(MODEL)                                                                                                                 \
-    LERF_COORDS_DT(out_dtype, TO, hipLaunchKernelGGL((coords_build_dev_kernel<MODEL, TO>), grid, block, 0, st, params_dev, (TO*)out, set_stride, \
-                                                     row_stride, oH, oW, i0, j0))
-    switch (model) {
-        case LERF_COORDS_HOMOGRAPHY: LERF_CBD(LERF_COORDS_HOMOGRAPHY); break;
-        case LERF_COORDS_RADIAL: LERF_CBD(LERF_COORDS_RADIAL); break;
-        default: LERF_CBD(LERF_COORDS_BROWN); break;
-    }
-#undef LERF_CBD
+    LERF_COORDS_MODEL(model, MODEL, LERF_COORDS_DT(out_dtype, TO,
+        hipLaunchKernelGGL((coords_build_dev_kernel<MODEL, TO>), grid, block, 0, st, params_dev, (TO*)out, set_stride, row_stride, oH, oW, i0, j0)));
     return launch_status();
 }
 
@@ -601,22 +619,30 @@ int lerf_coords_build_bwd(int model, const double* params_dev, int n_sets, int n
     const dim3 b1(CB_COLS, CB_ROWS), g1((oW + kBwdCols - 1) / kBwdCols, (oH + kBwdBand - 1) / kBwdBand, n_sets), b2(64), g2(n_params, n_sets);
     const double2* gm = reinterpret_cast<const double2*>(grad_map);
     double* part = reinterpret_cast<double*>(workspace);
-    switch (model) {
-        case LERF_COORDS_HOMOGRAPHY:
-            hipLaunchKernelGGL((coords_build_bwd_partial_kernel<LERF_COORDS_HOMOGRAPHY>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part);
-            break;
-        case LERF_COORDS_RADIAL:
-            hipLaunchKernelGGL((coords_build_bwd_partial_kernel<LERF_COORDS_RADIAL>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part);
-            break;
-        default:
-            hipLaunchKernelGGL((coords_build_bwd_partial_kernel<LERF_COORDS_BROWN>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part);
-            break;
-    }
+    LERF_COORDS_MODEL(model, MODEL,
+        hipLaunchKernelGGL((coords_build_bwd_partial_kernel<MODEL>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part));
     hipLaunchKernelGGL(coords_build_bwd_sum_kernel, g2, b2, 0, st, part, (int)(g1.x * g1.y), grad_params);
     return launch_status();
 }
 
+int lerf_coords_math(int op, const double* x, const double* y, int64_t n, double* out, void* stream) {
+    const int rc = math_args(op, x, y, n, out);
+    if (rc != LERF_OK) return rc;
+    if (n == 0) return LERF_OK;
+    clear_stale_error();
+    hipLaunchKernelGGL(coords_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, op, x, y, n, out);
+    return launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------ host twins: the same functions, a plain loop
+int lerf_coords_math_host(int op, const double* x, const double* y, int64_t n, double* out) {
+    const int rc = math_args(op, x, y, n, out);
+    if (rc != LERF_OK) return rc;
+    for (int64_t e = 0; e < n; ++e)
+        out[e] = op == LERF_MATH_SQRT ? sqrt_pm(x[e]) : op == LERF_MATH_ATAN ? atan_pm(x[e]) : atan2_pm(x[e], y[e]);
+    return LERF_OK;
+}
+
 int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
                            int i0, int j0) {
     Params prm;
@@ -624,9 +650,8 @@ int lerf_coords_build_host(int model, const double* params, int n_params, void* 
     if (rc != LERF_OK) return rc;
     for (int i = 0; i < oH; ++i)
         for (int j = 0; j < oW; ++j) {
-            const Point q = model == LERF_COORDS_HOMOGRAPHY ? model_point<LERF_COORDS_HOMOGRAPHY>(prm.p, i0 + i, j0 + j)
-                            : model == LERF_COORDS_RADIAL   ? model_point<LERF_COORDS_RADIAL>(prm.p, i0 + i, j0 + j)
-                                                            : model_point<LERF_COORDS_BROWN>(prm.p, i0 + i, j0 + j);
+            Point q;
+            LERF_COORDS_MODEL(model, MODEL, q = model_point<MODEL>(prm.p, i0 + i, j0 + j));
             LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, row_stride, i, j, q));
         }
     return LERF_OK;
@@ -745,9 +770,7 @@ int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int 
                                 const int64_t e = 2 * ((int64_t)i * oW + j);
                                 const Point gv{g[e], g[e + 1]};
                                 double dp[kMaxParams];
-                                if (model == LERF_COORDS_HOMOGRAPHY) model_point_bwd<LERF_COORDS_HOMOGRAPHY>(p, i0 + i, j0 + j, gv, dp);
-                                else if (model == LERF_COORDS_RADIAL) model_point_bwd<LERF_COORDS_RADIAL>(p, i0 + i, j0 + j, gv, dp);
-                                else model_point_bwd<LERF_COORDS_BROWN>(p, i0 + i, j0 + j, gv, dp);
+                                LERF_COORDS_MODEL(model, MODEL, model_point_bwd<MODEL>(p, i0 + i, j0 + j, gv, dp));
                                 for (int k = 0; k < n_params; ++k) acc[k] = acc[k] + dp[k];
                             }
                         for (int k = 0; k < n_params; ++k) lanes[(size_t)k * 64 + l] = acc[k];

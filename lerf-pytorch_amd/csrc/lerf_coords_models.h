@@ -1,8 +1,9 @@
 // Arithmetic of the coordinate-map builders (lerf_coords.hip), HIP-free on the host side: one source for the kernels and for the
-// host twins (lerf_coords_*_host), so a machine without a GPU tests the same statements.  Float64, only + - * /, no sqrt and no
-// transcendental, FMA contraction off: the device and the host agree BIT FOR BIT, like project_point against
-// coords.from_homography(arithmetic="device").  Every function returns the UNCLIPPED (row, col) of one output pixel (i, j) of
-// the whole map; the remap clips (remap_pixel).
+// host twins (lerf_coords_*_host), so a machine without a GPU tests the same statements.  Float64, only + - * /, comparisons,
+// selects and bit-casts, FMA contraction off, NO LIBRARY FUNCTION on either side: the square root and the arc tangents the lens
+// models need are sqrt_pm, atan_pm and atan2_pm below, written in these operations (a few ulp from libm's, NOT equal to them), so
+// the device and the host agree BIT FOR BIT, like project_point against coords.from_homography(arithmetic="device").  Every
+// function returns the UNCLIPPED (row, col) of one output pixel (i, j) of the whole map; the remap clips (remap_pixel).
 //
 // The exact operation order (tests/coords_ref.py restates it; every product and sum is rounded, sums run left to right):
 //
@@ -23,6 +24,41 @@
 //                 xd  = (x*rad + (2*p1)*xy) + p2*(r2 + 2*(x*x))
 //                 yd  = (y*rad + p1*(r2 + 2*(y*y))) + (2*p2)*xy
 //                 col = fx*xd + cx,  row = fy*yd + cy
+//   sqrt_pm(x)  a bit-cast start and six Heron passes (within 1 ulp of the exact root; 0 -> +0, x < 0 or NaN -> NaN, +inf -> +inf):
+//                 xs = x * 2^108 if x < 2^-1022 (a subnormal: exact), else x
+//                 y = the double whose bits are (bits(xs) >> 1) + 0x1FF8000000000000          (within 6.1 % of the root)
+//                 six times:  y = 0.5 * (y + xs / y)
+//                 y * 2^-54 if x < 2^-1022 (exact); then the selects of 0, +inf, NaN
+//   atan_pm(x)  fdlibm's reduction onto four anchors and its odd polynomial (within 1 ulp; NaN -> NaN, +-inf -> +-pi/2 rounded to
+//               a double, |x| < 2^-29 -> x), ax = |x| by a select:
+//                 ax < 7/16:   t = ax / 1                              hi = lo = 0
+//                 ax < 11/16:  t = (2*ax - 1) / (2 + ax)               hi + lo = atan(1/2)
+//                 ax < 19/16:  t = (ax - 1) / (ax + 1)                 hi + lo = atan(1)
+//                 ax < 39/16:  t = (ax - 1.5) / (1 + 1.5*ax)           hi + lo = atan(3/2)
+//                 else:        t = -1 / ax                             hi + lo = atan(inf) = pi/2
+//               (numerator, denominator, hi, lo by selects, ONE division)
+//                 z = t*t,  w = z*z
+//                 s1 = z*(a0 + w*(a2 + w*(a4 + w*(a6 + w*(a8 + w*a10))))),  s2 = w*(a1 + w*(a3 + w*(a5 + w*(a7 + w*a9))))
+//                 r = hi - ((t*(s1 + s2) - lo) - t);  -r if x < 0: atan_pm(-x) = -atan_pm(x) bit for bit
+//   atan2_pm(y, x)  a = atan_pm(y / x), then by selects (pi = pi_hi + pi_lo, two doubles):
+//                 x > 0:  a
+//                 x < 0:  (a + pi_lo) + pi_hi if y >= 0 -- y = +0 and y = -0 both count as + -- else (a - pi_lo) - pi_hi
+//                 x == 0: +pi/2 if y > 0, -pi/2 if y < 0, 0 if y == 0
+//                 a NaN in y or x: NaN.  (inf, inf) is NaN, unlike libm's; atan2_pm(-y, x) = -atan2_pm(y, x) bit for bit, y != 0
+//   FISHEYE     p = m[9] (inv(new_K . R), the host's), fx, fy, cx, cy, k1, k2, k3, k4   (cv::fisheye::initUndistortRectifyMap's
+//               equidistant model, no skew):
+//                 (y, x) = project_unclipped(m, i, j),  Wh = m6*u + m7*v + m8  (project_unclipped's statement)
+//                 not Wh > 0 (a ray behind the camera, Wh = 0, a NaN):  (NaN, NaN), by a select
+//                 r = sqrt_pm(x*x + y*y),  th = atan_pm(r),  th2 = th*th
+//                 thd = th*(1 + th2*(k1 + th2*(k2 + th2*(k3 + th2*k4))))
+//                 s = thd / r,  1 where r == 0 (a select)
+//                 col = fx*(x*s) + cx,  row = fy*(y*s) + cy
+//   EQUIRECT    p = m[9] (inv(K_view . R)), sx, sy, cxp, cyp   (a pinhole view of an equirectangular panorama; for a panorama
+//               [Hp][Wp] with pixel centres sx = Wp / (2 pi), sy = Hp / pi, cxp = (Wp - 1) / 2, cyp = (Hp - 1) / 2):
+//                 u = (double)j, v = (double)i
+//                 dx = m0*u + m1*v + m2,  dy = m3*u + m4*v + m5,  dz = m6*u + m7*v + m8          (no division)
+//                 lon = atan2_pm(dx, dz),  h = sqrt_pm(dx*dx + dz*dz),  lat = atan2_pm(dy, h)
+//                 col = cxp + sx*lon,  row = cyp + sy*lat          (the seam lon = +-pi is clipped like any border)
 //   mesh        ctrl [gh][gw][2], vertices align-corners over the WHOLE output [full_h][full_w]; per axis (rows: n = full_h,
 //               g = gh, k = i):
 //                 u = ((double)k * (double)(g - 1)) / (double)(n - 1)           (0 when n == 1)
@@ -83,11 +119,11 @@
 //                 scatter_taps of v into grad_F at the cell (R.i0, Cx.i0), the same rule and order as the outer gradient
 //               init, max_iter and tol have no gradient.  Neither backward forms an address outside its map: the cell comes from
 //               compose_axis and n >= 2 puts i0 + 1 <= n - 1.
-//   model backward (model_point_bwd<MODEL>; HOMOGRAPHY, RADIAL, BROWN)   one entry (i, j) with upstream g = (g.r, g.c): the hand-written
+//   model backward (model_point_bwd<MODEL>; every model)   one entry (i, j) with upstream g = (g.r, g.c): the hand-written
 //               reverse mode of model_point, dp[k] = d(row)/d(p[k]) * g.r + d(col)/d(p[k]) * g.c for EVERY entry of the parameter
 //               vector (radial's geometry scalars no, ni, hr, hc included; the caller keeps what it fits).  The forward is
 //               recomputed by the forward's own statements; (row, col) = model_point(p, i, j).
-//                 row or col not finite (row - row != 0: Wh == 0, an overflow, a NaN parameter): dp[k] = 0 for every k, whatever g
+//                 row or col not finite (row - row != 0: Wh == 0, fisheye's Wh <= 0, an overflow, a NaN parameter): dp[k] = 0 for every k, whatever g
 //                 holds -- a select, as in compose_bwd_point; this is NOT autograd's rule (autograd returns NaN or inf there).  A
 //                 NaN in g at a finite point propagates.
 //               HOMOGRAPHY  x = (double)j, y = (double)i, X, Y, Wh, col, row as above
@@ -116,6 +152,27 @@
 //                 dy = (((dyd*rad + (dyd*p1)*(4*y)) + dxd*((2*p1)*x)) + dyd*((2*p2)*x)) + dr2*(2*y)
 //                 dX = dx / Wh,  dY = dy / Wh,  dWh = -((dx*x + dy*y) / Wh)
 //                 dp[0..2] = dX*u, dX*v, dX;  dp[3..5] = dY*u, dY*v, dY;  dp[6..8] = dWh*u, dWh*v, dWh
+//               FISHEYE     u, v, Wh, x, y, r, th, th2, thd, s as above, xs = x*s, ys = y*s
+//                 dp[fx] = g.c*xs,  dp[cx] = g.c,  dp[fy] = g.r*ys,  dp[cy] = g.r
+//                 dxs = g.c*fx,  dys = g.r*fy,  ds = dxs*x + dys*y
+//                 dthd = ds / r,  drs = -((ds*s) / r);  both 0 where r == 0 (a select)               -- s = thd / r
+//                 th3 = th*th2, th5 = th3*th2, th7 = th5*th2, th9 = th7*th2
+//                 dp[k1] = dthd*th3, dp[k2] = dthd*th5, dp[k3] = dthd*th7, dp[k4] = dthd*th9
+//                 dth = dthd*(1 + th2*(3*k1 + th2*(5*k2 + th2*(7*k3 + th2*(9*k4)))))
+//                 dr = drs + dth / (1 + r*r)                                                           -- d atan(r) = dr / (1 + r*r)
+//                 dv = dr / (2*r);  0 where r == 0 (a select)                                        -- d sqrt(v) = dv / (2 sqrt(v))
+//                 dx = dxs*s + dv*(2*x),  dy = dys*s + dv*(2*y)
+//                 dX = dx / Wh,  dY = dy / Wh,  dWh = -((dx*x + dy*y) / Wh);  dp[0..8] as for BROWN
+//               at the principal ray (r == 0) the model is the pinhole's, col = fx*x + cx: what is left is its gradient
+//               EQUIRECT    u, v, dx, dy, dz, lon, h, lat as above
+//                 dp[cxp] = g.c,  dp[sx] = g.c*lon,  dp[cyp] = g.r,  dp[sy] = g.r*lat
+//                 dlon = g.c*sx,  dlat = g.r*sy
+//                 n2 = dy*dy + h*h                                           -- d atan2(a, b) = (b*da - a*db) / (a*a + b*b)
+//                 ddy = (h*dlat) / n2,  dh = -((dy*dlat) / n2);  both 0 where n2 == 0 (a select)
+//                 v2 = dx*dx + dz*dz,  dv = dh / (2*h)
+//                 ddx = (dz*dlon) / v2 + dv*(2*dx),  ddz = -((dx*dlon) / v2) + dv*(2*dz);  dv, ddx, ddz 0 where h == 0 (a select:
+//                 at a pole lon is the constant 0 and lat the constant +-pi/2)
+//                 dp[0..2] = ddx*u, ddx*v, ddx;  dp[3..5] = ddy*u, ddy*v, ddy;  dp[6..8] = ddz*u, ddz*v, ddz
 //   build backward (lerf_coords_build_bwd / _host)   grad_params[s][k] += sum over the entries of map s of dp[k].  THE ORDER OF THE SUM IS
 //               PART OF THE CONTRACT: a function of (oH, oW, n_sets) only, the same on the device and in the host twin, so two runs and
 //               the two sides agree bit for bit.  With C = 64 columns and R = 64 rows per band (kBwdCols, kBwdBand), nbx = ceil(oW / C),
@@ -151,8 +208,58 @@ struct Params {
     double p[kMaxParams];
 };
 
-LERF_HD inline int model_params(int model) {
-    return model == LERF_COORDS_HOMOGRAPHY ? 9 : model == LERF_COORDS_RADIAL ? 8 : model == LERF_COORDS_BROWN ? 21 : -1;
+LERF_HD constexpr int model_params(int model) {
+    return model == LERF_COORDS_HOMOGRAPHY ? 9 : model == LERF_COORDS_RADIAL ? 8 : model == LERF_COORDS_BROWN ? 21
+           : model == LERF_COORDS_FISHEYE ? 17 : model == LERF_COORDS_EQUIRECT ? 13 : -1;
+}
+
+// ---- the square root and the arc tangents in + - * /, selects and bit-casts (the statement order: the comment block at the top)
+LERF_HD inline double bits_to_double(int64_t b) { return __builtin_bit_cast(double, b); }
+LERF_HD inline int64_t double_to_bits(double d) { return __builtin_bit_cast(int64_t, d); }
+
+LERF_HD inline double sqrt_pm(double x) {
+#pragma clang fp contract(off)
+    const bool tiny = x < 2.2250738585072014e-308;                       // below 2^-1022: a subnormal (or 0, or negative)
+    const double xs = tiny ? x * 3.24518553658426726783e+32 : x;         // * 2^108
+    double y = bits_to_double((double_to_bits(xs) >> 1) + 0x1FF8000000000000LL);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) y = 0.5 * (y + xs / y);
+    y = tiny ? y * 5.55111512312578270212e-17 : y;                       // * 2^-54
+    y = x == 0.0 ? 0.0 : y;
+    y = x > 1.7976931348623157e+308 ? x : y;                             // +inf
+    return x >= 0.0 ? y : __builtin_nan("");                            // x < 0 and NaN
+}
+
+LERF_HD inline double atan_pm(double x) {
+#pragma clang fp contract(off)
+    const double ax = x < 0.0 ? -x : x;
+    const int id = ax < 0.4375 ? -1 : ax < 0.6875 ? 0 : ax < 1.1875 ? 1 : ax < 2.4375 ? 2 : 3;
+    const double num = id < 0 ? ax : id == 0 ? 2.0 * ax - 1.0 : id == 1 ? ax - 1.0 : id == 2 ? ax - 1.5 : -1.0;
+    const double den = id < 0 ? 1.0 : id == 0 ? 2.0 + ax : id == 1 ? ax + 1.0 : id == 2 ? 1.0 + 1.5 * ax : ax;
+    const double hi = id < 0 ? 0.0 : id == 0 ? 4.63647609000806093515e-01 : id == 1 ? 7.85398163397448278999e-01
+                      : id == 2 ? 9.82793723247329054082e-01 : 1.57079632679489655800e+00;
+    const double lo = id < 0 ? 0.0 : id == 0 ? 2.26987774529616870924e-17 : id == 1 ? 3.06161699786838301793e-17
+                      : id == 2 ? 1.39033110312309984516e-17 : 6.12323399573676603587e-17;
+    const double t = num / den;
+    const double z = t * t, w = z * z;
+    const double s1 = z * (3.33333333333329318027e-01 + w * (1.42857142725034663711e-01 + w * (9.09088713343650656196e-02 +
+                      w * (6.66107313738753120669e-02 + w * (4.97687799461593236017e-02 + w * 1.62858201153657823623e-02)))));
+    const double s2 = w * (-1.99999999998764832476e-01 + w * (-1.11111104054623557880e-01 + w * (-7.69187620504482999495e-02 +
+                      w * (-5.83357013379057348645e-02 + w * -3.65315727442169155270e-02))));
+    double r = hi - ((t * (s1 + s2) - lo) - t);
+    r = x < 0.0 ? -r : r;
+    r = ax < 1.862645149230957e-09 ? x : r;                              // |x| < 2^-29: atan(x) = x to the last bit
+    return x != x ? __builtin_nan("") : r;
+}
+
+LERF_HD inline double atan2_pm(double y, double x) {
+#pragma clang fp contract(off)
+    const double pi_hi = 3.14159265358979311600e+00, pi_lo = 1.22464679914735317723e-16, half_pi = 1.57079632679489655800e+00;
+    const double a = atan_pm(y / x);
+    const bool neg = y < 0.0;                                            // false for y = -0
+    double r = x < 0.0 ? (neg ? (a - pi_lo) - pi_hi : (a + pi_lo) + pi_hi) : a;
+    r = x == 0.0 ? (y == 0.0 ? 0.0 : neg ? -half_pi : half_pi) : r;
+    return (x != x || y != y) ? __builtin_nan("") : r;
 }
 
 template <int MODEL>
@@ -169,6 +276,27 @@ LERF_HD inline Point model_point(const double* p, int i, int j) {
         const double f = (1.0 + k1 * r2) + (k2 * r2) * r2;
         q.r = cr + (ur * f) * ni;
         q.c = cc + (uc * f) * ni;
+    } else if (MODEL == LERF_COORDS_FISHEYE) {
+        const double fx = p[9], fy = p[10], cx = p[11], cy = p[12], k1 = p[13], k2 = p[14], k3 = p[15], k4 = p[16];
+        double x, y;
+        project_unclipped(p, i, j, &y, &x);
+        const double Wh = p[6] * (double)j + p[7] * (double)i + p[8];    // project_unclipped's statement
+        const double r = sqrt_pm(x * x + y * y);
+        const double th = atan_pm(r), th2 = th * th;
+        const double thd = th * (1.0 + th2 * (k1 + th2 * (k2 + th2 * (k3 + th2 * k4))));
+        const double s = r == 0.0 ? 1.0 : thd / r;
+        const bool front = Wh > 0.0;                                     // false for a NaN
+        q.c = front ? fx * (x * s) + cx : __builtin_nan("");
+        q.r = front ? fy * (y * s) + cy : __builtin_nan("");
+    } else if (MODEL == LERF_COORDS_EQUIRECT) {
+        const double sx = p[9], sy = p[10], cxp = p[11], cyp = p[12];
+        const double u = (double)j, v = (double)i;
+        const double dx = p[0] * u + p[1] * v + p[2], dy = p[3] * u + p[4] * v + p[5], dz = p[6] * u + p[7] * v + p[8];
+        const double lon = atan2_pm(dx, dz);
+        const double h = sqrt_pm(dx * dx + dz * dz);
+        const double lat = atan2_pm(dy, h);
+        q.c = cxp + sx * lon;
+        q.r = cyp + sy * lat;
     } else {
         const double fx = p[9], fy = p[10], cx = p[11], cy = p[12];
         const double k1 = p[13], k2 = p[14], p1 = p[15], p2 = p[16], k3 = p[17], k4 = p[18], k5 = p[19], k6 = p[20];
@@ -191,9 +319,32 @@ LERF_HD inline bool finite_value(double d) { return d - d == 0.0; }      // fals
 template <int MODEL>
 LERF_HD inline void model_point_bwd(const double* p, int i, int j, Point g, double* dp) {
 #pragma clang fp contract(off)
-    constexpr int NP = MODEL == LERF_COORDS_HOMOGRAPHY ? 9 : MODEL == LERF_COORDS_RADIAL ? 8 : 21;
+    constexpr int NP = model_params(MODEL);
     const Point q = model_point<MODEL>(p, i, j);
-    if (MODEL == LERF_COORDS_RADIAL) {
+    if (MODEL == LERF_COORDS_EQUIRECT) {
+        const double sx = p[9], sy = p[10];
+        const double u = (double)j, v = (double)i;
+        const double dx = p[0] * u + p[1] * v + p[2], dy = p[3] * u + p[4] * v + p[5], dz = p[6] * u + p[7] * v + p[8];
+        const double lon = atan2_pm(dx, dz);
+        const double v2 = dx * dx + dz * dz;
+        const double h = sqrt_pm(v2);
+        const double lat = atan2_pm(dy, h);
+        dp[11] = g.c;
+        dp[9] = g.c * lon;
+        dp[12] = g.r;
+        dp[10] = g.r * lat;
+        const double dlon = g.c * sx, dlat = g.r * sy;
+        const double n2 = dy * dy + h * h;
+        const double ddy = n2 == 0.0 ? 0.0 : (h * dlat) / n2;
+        const double dh = n2 == 0.0 ? 0.0 : -((dy * dlat) / n2);
+        const bool pole = h == 0.0;
+        const double dv = pole ? 0.0 : dh / (2.0 * h);
+        const double ddx = pole ? 0.0 : (dz * dlon) / v2 + dv * (2.0 * dx);
+        const double ddz = pole ? 0.0 : -((dx * dlon) / v2) + dv * (2.0 * dz);
+        dp[0] = ddx * u; dp[1] = ddx * v; dp[2] = ddx;
+        dp[3] = ddy * u; dp[4] = ddy * v; dp[5] = ddy;
+        dp[6] = ddz * u; dp[7] = ddz * v; dp[8] = ddz;
+    } else if (MODEL == LERF_COORDS_RADIAL) {
         const double no = p[2], ni = p[3], hr = p[4], hc = p[5], k1 = p[6], k2 = p[7];
         const double ur = ((double)i - hr) / no;
         const double uc = ((double)j - hc) / no;
@@ -218,6 +369,28 @@ LERF_HD inline void model_point_bwd(const double* p, int i, int j, Point g, doub
         if (MODEL == LERF_COORDS_HOMOGRAPHY) {
             x = q.c; y = q.r;
             dx = g.c; dy = g.r;
+        } else if (MODEL == LERF_COORDS_FISHEYE) {
+            const double fx = p[9], fy = p[10], k1 = p[13], k2 = p[14], k3 = p[15], k4 = p[16];
+            project_unclipped(p, i, j, &y, &x);
+            const double r = sqrt_pm(x * x + y * y);
+            const double th = atan_pm(r), th2 = th * th;
+            const double thd = th * (1.0 + th2 * (k1 + th2 * (k2 + th2 * (k3 + th2 * k4))));
+            const bool centre = r == 0.0;
+            const double s = centre ? 1.0 : thd / r;
+            dp[9] = g.c * (x * s);
+            dp[11] = g.c;
+            dp[10] = g.r * (y * s);
+            dp[12] = g.r;
+            const double dxs = g.c * fx, dys = g.r * fy;
+            const double ds = dxs * x + dys * y;
+            const double dthd = centre ? 0.0 : ds / r, drs = centre ? 0.0 : -((ds * s) / r);
+            const double th3 = th * th2, th5 = th3 * th2, th7 = th5 * th2, th9 = th7 * th2;
+            dp[13] = dthd * th3; dp[14] = dthd * th5; dp[15] = dthd * th7; dp[16] = dthd * th9;
+            const double dth = dthd * (1.0 + th2 * (3.0 * k1 + th2 * (5.0 * k2 + th2 * (7.0 * k3 + th2 * (9.0 * k4)))));
+            const double dr = drs + dth / (1.0 + r * r);
+            const double dv = centre ? 0.0 : dr / (2.0 * r);
+            dx = dxs * s + dv * (2.0 * x);
+            dy = dys * s + dv * (2.0 * y);
         } else {
             const double fx = p[9], fy = p[10];
             const double k1 = p[13], k2 = p[14], p1 = p[15], p2 = p[16], k3 = p[17], k4 = p[18], k5 = p[19], k6 = p[20];

@@ -1049,7 +1049,8 @@ def _map_out(out, out_hw, dtype, device, what):
 
 def coords_build(model, params, out_hw, dtype=None, out=None, origin=(0, 0), device=None):
     """lerf_coords_build: the map [oH, oW, 2] of `model` ("homography": the 9 entries of the INVERSE matrix; "radial": cr, cc,
-    no, ni, hr, hc, k1, k2; "brown": inv(new_K . R)[9], fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) written by the kernel.
+    no, ni, hr, hc, k1, k2; "brown": inv(new_K . R)[9], fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6; "fisheye": inv(new_K . R)[9],
+    fx, fy, cx, cy, k1, k2, k3, k4; "equirect": inv(K_view . R)[9], sx, sy, cxp, cyp) written by the kernel.
     out: a device tensor or a strided tile view of a larger map, built in place at `origin` = (i0, j0) of the whole map; else a
     new tensor of `dtype` (default float64) on `device` (default: the current one)."""
     torch = _torch()
@@ -1068,7 +1069,7 @@ def _params_tensor(model, params, what):
     torch = _torch()
     if model not in _lib.COORDS_MODELS:
         raise ValueError("unknown coordinate-map model %r (known: %s)" % (model, ", ".join(_lib.COORDS_MODELS)))
-    n = (9, 8, 21)[_lib.COORDS_MODELS[model]]
+    n = _lib.COORDS_MODEL_PARAMS[model]
     if not isinstance(params, torch.Tensor) or not params.is_cuda or params.dtype != torch.float64 or params.ndim not in (1, 2) \
             or params.shape[-1] != n or params.shape[0] < 1:
         raise ValueError("%s: params must be a float64 device tensor [%d] or [B, %d] for model %r" % (what, n, n, model))
@@ -1133,6 +1134,27 @@ def coords_build_bwd(model, params, grad_map, grad_params=None, origin=(0, 0)):
                                                     grad_params.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream(g.device)),
                    "lerf_coords_build_bwd")
     return grad_params
+
+
+def coords_math(op, x, y=None):
+    """lerf_coords_math: sqrt_pm(x), atan_pm(x) or atan2_pm(x, y) (op "sqrt", "atan", "atan2") of float64 device tensors, one thread per
+    element: the helpers the fisheye and equirect models are built on, bit-equal to _lib.coords_math_host -> a new float64 tensor of
+    x's shape on x's device"""
+    torch = _torch()
+    if op not in _lib.COORDS_MATH_OPS:
+        raise ValueError("op is one of %s, not %r" % (", ".join(_lib.COORDS_MATH_OPS), op))
+    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64
+    if not ok(x) or (op == "atan2" and (not ok(y) or y.shape != x.shape or y.device != x.device)):
+        raise ValueError("lerf_coords_math: x (and y for atan2) must be float64 device tensors of one shape on one device")
+    a = x.detach().contiguous()
+    b = y.detach().contiguous() if op == "atan2" else None
+    out = torch.empty_like(a)
+    if a.numel() == 0:
+        return out
+    with _lib.on_device(a):
+        _lib.check(_lib.lib().lerf_coords_math(_lib.COORDS_MATH_OPS[op], a.data_ptr(), None if b is None else b.data_ptr(), a.numel(),
+                                               out.data_ptr(), _lib.current_stream(a.device)), "lerf_coords_math")
+    return out
 
 
 def _ctrl_tensor(ctrl, what):

@@ -1,7 +1,10 @@
 """Times the coordinate-map builders on the MI355X for a 2160 x 3840 float64 map (133 MB):
 
-  build     every model (homography, radial, brown) written by lerf_coords_build, against the SAME map built by the numpy builder
-            of coords.py plus torch.from_numpy(...).to(device) (wall clock, median of --host-repeats)
+  build     every model (homography, radial, brown, fisheye, equirect) written by lerf_coords_build, against the SAME map built by the
+            numpy builder of coords.py (fisheye, equirect: the host twin, the only host form bit-equal to the kernel) plus
+            torch.from_numpy(...).to(device) (wall clock, median of --host-repeats); fisheye and equirect add a chain of divisions
+            (sqrt_pm's six Heron passes, atan_pm's reduction) to a kernel that otherwise only writes: their time over brown's, measured in
+            the same run, is the number of interest (ratio_to_brown)
   mesh      a 33 x 61 control mesh upsampled (bilinear, bicubic) and the adjoint of each (lerf_coords_mesh_bwd)
   compose   an outer 2160 x 3840 map sampled at an inner 2160 x 3840 map
   invert    a 2160 x 3840 radial map (over a 2160 x 3840 source) inverted into a 2160 x 3840 inverse (lerf_coords_invert), as a
@@ -32,6 +35,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 M_ISC = [[2.05, 0.12, 15.0], [-0.08, 1.95, 40.0], [1.5e-5, -1.0e-5, 1.0]]     # bench.py config 4
 HBM_PEAK = 8.0e12
+FISH_DIST = [0.05, -0.012, 0.004, -0.0009]
+PANO_HW = (4096, 8192)
+VIEW_R = [[0.8660254037844387, 0.0, 0.5], [0.0, 1.0, 0.0], [-0.5, 0.0, 0.8660254037844387]]      # the view turned 30 degrees about y
 
 
 def device_ms(fn, iters, warmup, repeats):
@@ -88,6 +94,8 @@ def main():
         "homography": lambda d: coords.from_homography(np.array(M_ISC), hw, device=d),
         "radial": lambda d: coords.radial(in_hw, hw, 0.08, -0.02, device=d),
         "brown": lambda d: coords.undistort_rectify(K, dist, None, new_K, hw, device=d),
+        "fisheye": lambda d: coords.fisheye_undistort_rectify(K, FISH_DIST, None, new_K, hw, device=d),
+        "equirect": lambda d: coords.equirect_view(PANO_HW, new_K, VIEW_R, hw, device=d),
     }
 
     def row(t, nbytes):
@@ -103,12 +111,15 @@ def main():
         code, p = _lib.coords_model_params(name, {
             "homography": np.linalg.inv(np.array(M_ISC)).reshape(9),
             "radial": [(in_hw[0] - 1) / 2.0, (in_hw[1] - 1) / 2.0, np.hypot(*hw) / 2.0, np.hypot(*in_hw) / 2.0, (hw[0] - 1) / 2.0, (hw[1] - 1) / 2.0, 0.08, -0.02],
-            "brown": coords.brown_params(K, dist, None, new_K)}[name])
+            "brown": coords.brown_params(K, dist, None, new_K), "fisheye": coords.fisheye_params(K, FISH_DIST, None, new_K),
+            "equirect": coords.equirect_params(PANO_HW, new_K, VIEW_R)}[name])
         t = device_ms(lambda: ops.coords_build(name, p, hw, out=out), a.iters, a.warmup, a.repeats)
         h_ms, h_map = host_ms(lambda: torch.from_numpy(fn(None)).to(dev), a.host_repeats)
         same = bool(torch.equal(fn(dev), h_map))
         equal = equal and same
         build[name] = dict(row(t, 16 * entries), host_numpy_plus_upload_ms=round(h_ms, 2), speedup=round(h_ms / t[0], 1), equals_host=same)
+    for name in ("fisheye", "equirect"):
+        build[name]["ratio_to_brown"] = round(build[name]["ms"] / build["brown"]["ms"], 2)
     res["build"] = build
 
     rng = np.random.default_rng(0)

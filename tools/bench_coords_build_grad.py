@@ -1,5 +1,7 @@
 """Times the model builders with device parameters and their adjoint on the MI355X for 2160 x 3840 float64 maps (133 MB each), the
-homography and the brown model, one parameter set and a batch of 8:
+homography, the brown, the fisheye and the equirect model, one parameter set and a batch of 8 (fisheye and equirect carry the
+library's own square root and arc tangents, a chain of divisions: their times over brown's, in the same run, are reported as
+over_brown):
 
   build_bwd     lerf_coords_build_bwd: grad_params[s][k] += sum over the entries of dp[k], two passes, no atomics
   build         lerf_coords_build_dev: the forward from parameters in device memory, in the same run
@@ -27,6 +29,9 @@ HBM_PEAK = 8.0e12
 M_ISC = np.array([[2.05, 0.12, 15.0], [-0.08, 1.95, 40.0], [1.5e-5, -1.0e-5, 1.0]])
 K0 = np.array([[1900.0, 0.0, 1935.5], [0.0, 1890.0, 1071.25], [0.0, 0.0, 1.0]])               # a 4K camera, mild distortion
 DIST8 = [0.11, -0.04, 0.002, -0.003, 0.013, 0.02, -0.007, 0.001]
+FISH_DIST = [0.05, -0.012, 0.004, -0.0009]
+PANO_HW = (4096, 8192)
+VIEW_R = [[0.8660254037844387, 0.0, 0.5], [0.0, 1.0, 0.0], [-0.5, 0.0, 0.8660254037844387]]      # the view turned 30 degrees about y
 
 
 def torch_model(torch, model, p, hw):
@@ -35,7 +40,17 @@ def torch_model(torch, model, p, hw):
     x = torch.arange(hw[1], dtype=torch.float64, device=p.device)[None, None, :]
     q = [p[:, k, None, None] for k in range(p.shape[1])]
     X, Y, Wh = q[0] * x + q[1] * y + q[2], q[3] * x + q[4] * y + q[5], q[6] * x + q[7] * y + q[8]
+    if model == "equirect":
+        sx, sy, cxp, cyp = q[9:]
+        return torch.stack([cyp + sy * torch.atan2(Y, torch.sqrt(X * X + Wh * Wh)), cxp + sx * torch.atan2(X, Wh)], dim=-1)
     u, v = X / Wh, Y / Wh
+    if model == "fisheye":
+        fx, fy, cx, cy, k1, k2, k3, k4 = q[9:]
+        r = torch.sqrt(u * u + v * v)
+        th = torch.atan(r)
+        th2 = th * th
+        s = th * (1 + th2 * (k1 + th2 * (k2 + th2 * (k3 + th2 * k4)))) / r
+        return torch.stack([fy * (v * s) + cy, fx * (u * s) + cx], dim=-1)
     if model == "homography":
         return torch.stack([v, u], dim=-1)
     fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6 = q[9:]
@@ -81,11 +96,12 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     hw = tuple(a.hw)
     entries = hw[0] * hw[1]
-    base = {"homography": np.linalg.inv(M_ISC).reshape(9), "brown": coords.brown_params(K0, DIST8, None, None)}
+    base = {"homography": np.linalg.inv(M_ISC).reshape(9), "brown": coords.brown_params(K0, DIST8, None, None),
+            "fisheye": coords.fisheye_params(K0, FISH_DIST, None, None), "equirect": coords.equirect_params(PANO_HW, K0, VIEW_R)}
     res = {"tool": "bench_coords_build_grad", "hw": list(hw), "dtype": "float64", "iters": a.iters, "torch_iters": a.torch_iters,
            "warmup": a.warmup, "repeats": a.repeats, "map_bytes": 16 * entries, "cases": {}}
     ok = True
-    for model in ("homography", "brown"):
+    for model in ("homography", "brown", "fisheye", "equirect"):
         for B in (1, a.batch):
             n = base[model].size
             p = torch.from_numpy(np.stack([base[model] * (1.0 + 1e-3 * s) for s in range(B)])).to(dev)
@@ -124,6 +140,9 @@ def main():
             err = float((got - leaf.grad).abs().max())
             case["grad_max_error"], case["grad_scale"] = err, scale
             ok = ok and err <= 1e-9 * scale
+            if model in ("fisheye", "equirect"):
+                brown = res["cases"]["brown_B%d" % B]
+                case["over_brown"] = {k: round(case[k]["ms"] / brown[k]["ms"], 2) for k in ("build", "build_bwd")}
             res["cases"]["%s_B%d" % (model, B)] = case
             del g, out, leaf
             torch.cuda.empty_cache()
