@@ -415,31 +415,113 @@ def remap_host_geometry(coords: np.ndarray, in_hw, S: int, pads=None):
     return gr, gc, lr, lc, (int(out[0]), int(out[1]))
 
 
-def _np_dt(a):
-    if a.dtype == np.float32:
-        return LERF_F32
-    if a.dtype == np.float64:
-        return LERF_F64
-    raise ValueError("float32 or float64 expected, got %s" % a.dtype)
+# ------------------------------------------------------------------ coordinate maps: one marshaller for host arrays and device tensors
+class _Operands:
+    """What the coords_* wrappers ask of their operands, written once.  HostOperands (numpy arrays, the lerf_coords_*_host entry
+    points) and DeviceOperands (torch device tensors, the current stream) supply the primitives."""
+
+    def is_float(self, a):
+        return a.dtype == self.f32 or a.dtype == self.f64
+
+    def code(self, a):
+        return LERF_F32 if a.dtype == self.f32 else LERF_F64
+
+    def map(self, a, what):
+        """(a, row stride in elements) of a map under the strided contract: [h, w, 2] float32 / float64, pairs contiguous, rows free"""
+        if not self.is_array(a) or a.ndim != 3 or a.shape[2] != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise ValueError("%s must be %s [h, w, 2]" % (what, self.noun))
+        if not self.is_float(a):
+            raise ValueError("%s must be float32 or float64, not %s" % (what, a.dtype))
+        s = self.strides(a)
+        if s[2] != 1 or s[1] != 2 or s[0] is None:
+            raise ValueError("%s: contiguous (row, col) pairs, column stride 2" % what)
+        return a, s[0]
+
+    def out(self, out, out_hw, dtype, default, device, what):
+        """a new map of `dtype` (None: `default`) or the checked `out`, with its row stride"""
+        oH, oW = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            if oH < 1 or oW < 1:
+                raise ValueError("%s: out_hw must be positive" % what)
+            out = self.new((oH, oW, 2), self.dtype(dtype, default, what), device)
+        elif tuple(out.shape[:2]) != (oH, oW):
+            raise ValueError("%s: out must be [%d, %d, 2]" % (what, oH, oW))
+        return self.map(out, "out")
+
+    def grad(self, g, shape, device, what):
+        """a dense float64 gradient buffer [h, w, 2] (None: a zeroed one)"""
+        if g is None:
+            return self.new(shape, self.f64, device, zero=True)
+        if not self.is_array(g) or g.dtype != self.f64 or tuple(g.shape) != tuple(shape) or not self.is_contiguous(g) or self.device(g) != device:
+            raise ValueError("%s must be a contiguous float64 %s beside the maps" % (what, list(shape)))
+        return g
+
+    def one_device(self, what, names, first, *others):
+        for a in others:
+            if a is not None and self.device(a) != self.device(first):
+                raise ValueError("%s: %s live on different devices" % (what, " and ".join(names)))
+
+    def operand(self, a, stride):
+        return self.ptr(a), self.code(a), stride
 
 
-def _np_map(a, what):
-    """(array, row stride in elements) of a host map under the strided contract: [h, w, 2], pairs contiguous, rows free"""
-    if not isinstance(a, np.ndarray) or a.ndim != 3 or a.shape[2] != 2 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("%s must be a numpy [h, w, 2] array" % what)
-    e = a.itemsize
-    _np_dt(a)
-    if a.strides[2] != e or a.strides[1] != 2 * e or a.strides[0] % e:
-        raise ValueError("%s: contiguous (row, col) pairs, column stride 2" % what)
-    return a, a.strides[0] // e
+class HostOperands(_Operands):
+    suffix, noun, f32, f64 = "_host", "a numpy array", np.float32, np.float64
+    is_array = staticmethod(lambda a: isinstance(a, np.ndarray))
+    strides = staticmethod(lambda a: tuple(s // a.itemsize if s % a.itemsize == 0 else None for s in a.strides))
+    is_contiguous = staticmethod(lambda a: a.flags.c_contiguous)
+    device = staticmethod(lambda a: None)
+    ptr = staticmethod(lambda a: None if a is None else a.ctypes.data)
+    dtype = staticmethod(lambda dtype, default, what: np.dtype(dtype))               # the host signatures default to float64
+    new = staticmethod(lambda shape, dtype, device, zero=False: (np.zeros if zero else np.empty)(tuple(shape), dtype))
+    contiguous = staticmethod(np.ascontiguousarray)                                  # array-likes too
+    float64 = staticmethod(lambda x, what: np.ascontiguousarray(np.asarray(x, dtype=np.float64)))
+
+    def call(self, name, anchor, *args):
+        check(getattr(lib(), name)(*args), name)
 
 
-def _np_out(out, out_hw, dtype, what):
-    if out is None:
-        out = np.empty((int(out_hw[0]), int(out_hw[1]), 2), dtype=np.dtype(dtype))
-    elif tuple(out.shape[:2]) != (int(out_hw[0]), int(out_hw[1])):
-        raise ValueError("%s: out must be [%d, %d, 2]" % (what, out_hw[0], out_hw[1]))
-    return _np_map(out, "out")
+class DeviceOperands(_Operands):
+    suffix, noun = "", "a device tensor"
+
+    _one = None
+
+    def __new__(cls):                                  # one instance, made at the first call that finds the GPU (require_gpu raises without)
+        if cls._one is None:
+            torch = require_gpu()
+            cls._one = super().__new__(cls)
+            cls._one.torch, cls._one.f32, cls._one.f64 = torch, torch.float32, torch.float64
+        return cls._one
+
+    strides = staticmethod(lambda t: t.stride())
+    is_contiguous = staticmethod(lambda t: t.is_contiguous())
+    device = staticmethod(lambda t: t.device)
+    ptr = staticmethod(lambda t: None if t is None else t.data_ptr())
+
+    def is_array(self, t):
+        return isinstance(t, self.torch.Tensor) and t.is_cuda
+
+    def dtype(self, dtype, default, what):
+        dtype = default if dtype is None else dtype
+        if dtype not in (self.f32, self.f64):
+            raise ValueError("%s: dtype is torch.float32 or torch.float64" % what)
+        return dtype
+
+    def new(self, shape, dtype, device, zero=False):
+        return (self.torch.zeros if zero else self.torch.empty)(tuple(shape), dtype=dtype, device=device)
+
+    def contiguous(self, t):
+        return t.detach().contiguous() if self.is_array(t) else t
+
+    def float64(self, x, what):
+        if not self.is_array(x) or x.dtype != self.f64:
+            raise ValueError("%s: x (and y for atan2) must be float64 device tensors" % what)
+        return self.contiguous(x)
+
+    def call(self, name, anchor, *args):
+        """the launch on `anchor`'s device and its current stream"""
+        with on_device(anchor):
+            check(getattr(lib(), name)(*args, current_stream(anchor.device)), name)
 
 
 def coords_model_count(model, n, what):
@@ -463,90 +545,136 @@ def mesh_interp_code(interp):
     return MESH_INTERPS[interp]
 
 
+_HOST = HostOperands()
+
+
+# The seven operations that exist on both sides, over X = HostOperands() or DeviceOperands(): ops.coords_* and coords_*_host below
+# bind them and carry the documentation.
+def coords_build_on(X, model, params, out_hw, dtype, out, origin, device=None):
+    what = "lerf_coords_build" + X.suffix
+    code, p = coords_model_params(model, params, what)
+    out, stride = X.out(out, out_hw, dtype, X.f64, device, what)
+    X.call(what, out, code, p.ctypes.data, int(p.size), *X.operand(out, stride), int(out_hw[0]), int(out_hw[1]), int(origin[0]), int(origin[1]))
+    return out
+
+
+def coords_mesh_on(X, ctrl, out_hw, interp, dtype, out, origin, full_hw):
+    what = "lerf_coords_mesh" + X.suffix
+    c = X.contiguous(ctrl)
+    if not X.is_array(c) or c.ndim != 3 or c.shape[2] != 2:
+        raise ValueError("%s: ctrl must be %s [gh, gw, 2]" % (what, X.noun))
+    if not X.is_float(c):
+        raise ValueError("%s: ctrl must be float32 or float64" % what)
+    code = mesh_interp_code(interp)
+    full_hw = out_hw if full_hw is None else full_hw
+    out, stride = X.out(out, out_hw, dtype, c.dtype, X.device(c), what)
+    X.one_device(what, ("ctrl", "out"), c, out)
+    X.call(what, c, X.ptr(c), X.code(c), c.shape[0], c.shape[1], code, int(full_hw[0]), int(full_hw[1]), *X.operand(out, stride),
+           int(out_hw[0]), int(out_hw[1]), int(origin[0]), int(origin[1]))
+    return out
+
+
+def coords_compose_on(X, outer, inner, dtype, out):
+    what = "lerf_coords_compose" + X.suffix
+    a, sa = X.map(outer, "outer")
+    b, sb = X.map(inner, "inner")
+    X.one_device(what, ("outer", "inner"), a, b)
+    out, so = X.out(out, b.shape[:2], dtype, b.dtype, X.device(b), what)
+    X.call(what, b, *X.operand(a, sa), a.shape[0], a.shape[1], *X.operand(b, sb), *X.operand(out, so), b.shape[0], b.shape[1])
+    return out
+
+
+def coords_invert_on(X, f, out_hw, init, dtype, out, origin, max_iter, tol):
+    what = "lerf_coords_invert" + X.suffix
+    a, sa = X.map(f, "f")
+    b, sb = (None, 0) if init is None else X.map(init, "init")
+    out, so = X.out(out, out_hw, dtype, a.dtype, X.device(a), what)
+    X.one_device(what, ("f", "out", "init"), a, out, b)
+    if b is not None and tuple(b.shape[:2]) != tuple(out.shape[:2]):
+        raise ValueError("%s: init must have out's shape" % what)
+    X.call(what, a, *X.operand(a, sa), a.shape[0], a.shape[1], X.ptr(b), LERF_F64 if b is None else X.code(b), sb, *X.operand(out, so),
+           out.shape[0], out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol))
+    return out
+
+
+def _coords_bwd_operands(X, what, first, second, names, grad_out):
+    """the two maps of an adjoint and its upstream gradient, which has the second map's shape"""
+    a, sa = X.map(first, names[0])
+    b, sb = X.map(second, names[1])
+    X.one_device(what, names, a, b)
+    if grad_out is None:
+        raise ValueError("%s: grad_out must be contiguous float64 [oH, oW, 2]" % what)
+    return a, sa, b, sb, X.grad(grad_out, b.shape, X.device(b), what + ": grad_out")
+
+
+def coords_compose_bwd_on(X, outer, inner, grad_out, grad_outer, grad_inner, need):
+    what = "lerf_coords_compose_bwd" + X.suffix
+    a, sa, b, sb, g = _coords_bwd_operands(X, what, outer, inner, ("outer", "inner"), grad_out)
+    if not (need[0] or need[1]):
+        raise ValueError("%s: at least one of the two gradients is needed" % what)
+    ga = X.grad(grad_outer, a.shape, X.device(b), what + ": grad_outer") if need[0] else None
+    gb = X.grad(grad_inner, b.shape, X.device(b), what + ": grad_inner") if need[1] else None
+    X.call(what, b, *X.operand(a, sa), a.shape[0], a.shape[1], *X.operand(b, sb), X.ptr(g), b.shape[0], b.shape[1], X.ptr(ga), X.ptr(gb))
+    return ga, gb
+
+
+def coords_invert_bwd_on(X, f, inverse, grad_out, grad_f):
+    what = "lerf_coords_invert_bwd" + X.suffix
+    a, sa, b, sb, g = _coords_bwd_operands(X, what, f, inverse, ("f", "inverse"), grad_out)
+    gf = X.grad(grad_f, a.shape, X.device(b), what + ": grad_f")
+    X.call(what, b, *X.operand(a, sa), a.shape[0], a.shape[1], *X.operand(b, sb), X.ptr(g), b.shape[0], b.shape[1], X.ptr(gf))
+    return gf
+
+
+def coords_math_on(X, op, x, y):
+    what = "lerf_coords_math" + X.suffix
+    if op not in COORDS_MATH_OPS:
+        raise ValueError("op is one of %s, not %r" % (", ".join(COORDS_MATH_OPS), op))
+    if op == "atan2" and y is None:
+        raise ValueError("%s: atan2 takes x and y" % what)
+    a = X.float64(x, what)
+    b = X.float64(y, what) if op == "atan2" else None
+    if b is not None and (b.shape != a.shape or X.device(b) != X.device(a)):
+        raise ValueError("%s: x and y must have one shape, on one device" % what)
+    out = X.new(a.shape, X.f64, X.device(a))
+    n = int(np.prod(a.shape, dtype=np.int64))
+    if n:
+        X.call(what, a, COORDS_MATH_OPS[op], X.ptr(a), X.ptr(b), n, X.ptr(out))
+    return out
+
+
 def coords_build_host(model, params, out_hw, dtype=np.float64, out=None, origin=(0, 0)):
     """lerf_coords_build_host: the map of a model built on the host by the kernels' own arithmetic (bit-equal to the device's)"""
-    code, p = coords_model_params(model, params, "lerf_coords_build_host")
-    out, stride = _np_out(out, out_hw, dtype, "lerf_coords_build_host")
-    check(lib().lerf_coords_build_host(code, p.ctypes.data, int(p.size), out.ctypes.data, _np_dt(out), stride, int(out_hw[0]),
-                                       int(out_hw[1]), int(origin[0]), int(origin[1])), "lerf_coords_build_host")
-    return out
+    return coords_build_on(_HOST, model, params, out_hw, dtype, out, origin)
 
 
 def coords_mesh_host(ctrl, out_hw, interp="bilinear", dtype=np.float64, out=None, origin=(0, 0), full_hw=None):
     """lerf_coords_mesh_host: ctrl [gh, gw, 2] float32 / float64 upsampled to the tile out_hw at `origin` of the map full_hw"""
-    c = np.ascontiguousarray(ctrl)
-    if c.ndim != 3 or c.shape[2] != 2:
-        raise ValueError("ctrl must be [gh, gw, 2]")
-    full_hw = out_hw if full_hw is None else full_hw
-    out, stride = _np_out(out, out_hw, dtype, "lerf_coords_mesh_host")
-    check(lib().lerf_coords_mesh_host(c.ctypes.data, _np_dt(c), c.shape[0], c.shape[1], mesh_interp_code(interp), int(full_hw[0]),
-                                      int(full_hw[1]), out.ctypes.data, _np_dt(out), stride, int(out_hw[0]), int(out_hw[1]),
-                                      int(origin[0]), int(origin[1])), "lerf_coords_mesh_host")
-    return out
+    return coords_mesh_on(_HOST, ctrl, out_hw, interp, dtype, out, origin, full_hw)
 
 
 def coords_compose_host(outer, inner, dtype=np.float64, out=None):
     """lerf_coords_compose_host: C[i, j] = outer(inner[i, j]), host arrays under the strided map contract"""
-    a, sa = _np_map(outer, "outer")
-    b, sb = _np_map(inner, "inner")
-    out, so = _np_out(out, b.shape[:2], dtype, "lerf_coords_compose_host")
-    check(lib().lerf_coords_compose_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
-                                         out.ctypes.data, _np_dt(out), so, b.shape[0], b.shape[1]), "lerf_coords_compose_host")
-    return out
+    return coords_compose_on(_HOST, outer, inner, dtype, out)
 
 
 def coords_invert_host(f, out_hw, init=None, dtype=np.float64, out=None, origin=(0, 0), max_iter=16, tol=1e-9):
     """lerf_coords_invert_host: G[i, j] = the u with f(u) = origin + (i, j), f read bilinearly, by Newton's method from init[i, j]
     (None: the affine guess from three corners of f); NaN where f does not reach.  Host arrays under the strided map contract."""
-    a, sa = _np_map(f, "f")
-    b, sb = (None, 0) if init is None else _np_map(init, "init")
-    out, so = _np_out(out, out_hw, dtype, "lerf_coords_invert_host")
-    if b is not None and tuple(b.shape[:2]) != tuple(out.shape[:2]):
-        raise ValueError("lerf_coords_invert_host: init must have out's shape")
-    check(lib().lerf_coords_invert_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], None if b is None else b.ctypes.data,
-                                        LERF_F64 if b is None else _np_dt(b), sb, out.ctypes.data, _np_dt(out), so, out.shape[0],
-                                        out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol)), "lerf_coords_invert_host")
-    return out
-
-
-def _np_grad(g, shape, what):
-    """a dense float64 gradient buffer [h, w, 2] on the host (None: a zeroed one)"""
-    if g is None:
-        return np.zeros(shape, np.float64)
-    if not isinstance(g, np.ndarray) or g.dtype != np.float64 or tuple(g.shape) != tuple(shape) or not g.flags.c_contiguous:
-        raise ValueError("%s must be a C-contiguous float64 array %s" % (what, list(shape)))
-    return g
+    return coords_invert_on(_HOST, f, out_hw, init, dtype, out, origin, max_iter, tol)
 
 
 def coords_compose_bwd_host(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):
     """lerf_coords_compose_bwd_host: ACCUMULATE the adjoint of compose(outer, inner) of the float64 grad_out [oH, oW, 2] into
     grad_outer [aH, aW, 2] and grad_inner [oH, oW, 2] (None: zeroed ones; need[k] False: that half is skipped and None is
     returned for it) -> (grad_outer, grad_inner)."""
-    a, sa = _np_map(outer, "outer")
-    b, sb = _np_map(inner, "inner")
-    if grad_out is None:
-        raise ValueError("grad_out must be a C-contiguous float64 array")
-    g = _np_grad(grad_out, b.shape, "grad_out")
-    ga = _np_grad(grad_outer, a.shape, "grad_outer") if need[0] else None
-    gb = _np_grad(grad_inner, b.shape, "grad_inner") if need[1] else None
-    check(lib().lerf_coords_compose_bwd_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
-                                             g.ctypes.data, b.shape[0], b.shape[1], None if ga is None else ga.ctypes.data,
-                                             None if gb is None else gb.ctypes.data), "lerf_coords_compose_bwd_host")
-    return ga, gb
+    return coords_compose_bwd_on(_HOST, outer, inner, grad_out, grad_outer, grad_inner, need)
 
 
 def coords_invert_bwd_host(f, inverse, grad_out, grad_f=None):
     """lerf_coords_invert_bwd_host: ACCUMULATE the implicit-function adjoint of inverse = invert(f) of the float64 grad_out
     [oH, oW, 2] into grad_f [fH, fW, 2] (None: a zeroed one)."""
-    a, sa = _np_map(f, "f")
-    b, sb = _np_map(inverse, "inverse")
-    if grad_out is None:
-        raise ValueError("grad_out must be a C-contiguous float64 array")
-    g = _np_grad(grad_out, b.shape, "grad_out")
-    gf = _np_grad(grad_f, a.shape, "grad_f")
-    check(lib().lerf_coords_invert_bwd_host(a.ctypes.data, _np_dt(a), sa, a.shape[0], a.shape[1], b.ctypes.data, _np_dt(b), sb,
-                                            g.ctypes.data, b.shape[0], b.shape[1], gf.ctypes.data), "lerf_coords_invert_bwd_host")
-    return gf
+    return coords_invert_bwd_on(_HOST, f, inverse, grad_out, grad_f)
 
 
 def coords_build_bwd_host(model, params, grad_map, origin=(0, 0)):
@@ -573,20 +701,7 @@ def coords_math_host(op, x, y=None):
     """lerf_coords_math_host: sqrt_pm(x), atan_pm(x) or atan2_pm(x, y) (op "sqrt", "atan", "atan2") of float64 arrays, element by element,
     by the HOST twin of the helpers the fisheye and equirect models are built on (csrc/lerf_coords_models.h: + - * / only, bit-equal to
     the device's ops.coords_math, a few ulp from numpy's) -> a new float64 array of x's shape"""
-    if op not in COORDS_MATH_OPS:
-        raise ValueError("op is one of %s, not %r" % (", ".join(COORDS_MATH_OPS), op))
-    a = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
-    b = None
-    if op == "atan2":
-        if y is None:
-            raise ValueError("lerf_coords_math_host: atan2 takes x and y")
-        b = np.ascontiguousarray(np.asarray(y, dtype=np.float64))
-        if b.shape != a.shape:
-            raise ValueError("lerf_coords_math_host: x and y must have one shape")
-    out = np.empty(a.shape, np.float64)
-    check(lib().lerf_coords_math_host(COORDS_MATH_OPS[op], a.ctypes.data, None if b is None else b.ctypes.data, a.size, out.ctypes.data),
-          "lerf_coords_math_host")
-    return out
+    return coords_math_on(_HOST, op, x, y)
 
 
 # ------------------------------------------------------------------ device plumbing

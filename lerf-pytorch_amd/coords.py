@@ -383,29 +383,27 @@ def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
         raise ValueError("invert: map and init hold different numbers of maps")
     if dev[0]:
         import torch
-        from . import ops
-        return _invert_dev(map, (H, W), init, max_iter, tol, map.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name))
-    from . import _lib
+        return _invert_maps(map, (H, W), init, max_iter, tol, map.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name))
     a, b = (None if t is None else np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (map, init))
     a, b = (t if t is None or t.dtype in (np.float32, np.float64) else t.astype(np.float64) for t in (a, b))
-    dt = a.dtype if dtype is None else _np_dtype(dtype)
-    if nd == 3:
-        return _lib.coords_invert_host(a, (H, W), init=b, dtype=dt, max_iter=max_iter, tol=tol)
-    out = np.empty((a.shape[0], H, W, 2), dtype=dt)
-    for n in range(a.shape[0]):
-        _lib.coords_invert_host(a[n], (H, W), init=None if b is None else b[n], out=out[n], max_iter=max_iter, tol=tol)
-    return out
+    return _invert_maps(a, (H, W), b, max_iter, tol, a.dtype if dtype is None else _np_dtype(dtype))
 
 
-def _invert_dev(map, hw, init, max_iter, tol, tdt):
-    """invert on the device: one map, or one launch per map of a batch into the slices of one output tensor"""
-    import torch
-    from . import ops
+def _invert_maps(map, hw, init, max_iter, tol, dt):
+    """invert of numpy maps by the host twin or of device tensors by the kernel (dt: a numpy or a torch dtype alike): one map, or
+    one call per map of a batch into the slices of one output"""
+    if getattr(map, "is_cuda", False):
+        import torch
+        from . import ops
+        one, new = ops.coords_invert, lambda shape: torch.empty(shape, dtype=dt, device=map.device)
+    else:
+        from . import _lib
+        one, new = _lib.coords_invert_host, lambda shape: np.empty(shape, dtype=dt)
     if map.ndim == 3:
-        return ops.coords_invert(map, hw, init=init, dtype=tdt, max_iter=max_iter, tol=tol)
-    out = torch.empty((map.shape[0], hw[0], hw[1], 2), dtype=tdt, device=map.device)
+        return one(map, hw, init=init, dtype=dt, max_iter=max_iter, tol=tol)
+    out = new((map.shape[0], hw[0], hw[1], 2))
     for n in range(map.shape[0]):
-        ops.coords_invert(map[n], hw, init=None if init is None else init[n], out=out[n], max_iter=max_iter, tol=tol)
+        one(map[n], hw, init=None if init is None else init[n], out=out[n], max_iter=max_iter, tol=tol)
     return out
 
 
@@ -487,7 +485,7 @@ def _chain_fns():
 
             @staticmethod
             def forward(ctx, map, init, hw, max_iter, tol, tdt):
-                out = _invert_dev(map.detach(), hw, None if init is None else init.detach(), max_iter, tol, tdt)
+                out = _invert_maps(map.detach(), hw, None if init is None else init.detach(), max_iter, tol, tdt)
                 ctx.save_for_backward(map, out)
                 return out
 
@@ -561,7 +559,7 @@ def invert_torch(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
             raise ValueError("invert_torch: init is [H, W, 2], or [B, H, W, 2] for a batch of B maps")
     tdt = a.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
     if not (torch.is_grad_enabled() and a.requires_grad):
-        return _invert_dev(a.detach(), (H, W), None if init is None else init.detach(), max_iter, tol, tdt)
+        return _invert_maps(a.detach(), (H, W), None if init is None else init.detach(), max_iter, tol, tdt)
     return _chain_fns()[1].apply(a, init, (H, W), int(max_iter), float(tol), tdt)
 
 

@@ -1,21 +1,21 @@
 // Coordinate maps built, upsampled, composed and inverted on the device: the maps lerf_remap reads (lerf_remap_geo_t.coords), written by
 // kernels instead of host numpy + an upload.  The arithmetic of every entry is lerf_coords_models.h (float64, + - * / only, no
-// FMA contraction), shared with the host twins at the end of this file, which run the same functions in a plain loop over host
-// pointers: device and host agree bit for bit.  The fisheye and equirect models (codes 16, 17) take their square root and arc
-// tangents from the same header (sqrt_pm, atan_pm, atan2_pm), not from a math library, so the same holds for them.
+// FMA contraction; the fisheye and equirect models, codes 16 and 17, take their square root and arc tangents from the same header,
+// not from a math library).
 //
-//   coords_build_kernel<MODEL, TO>          one thread per entry: the model's point of pixel (i0 + i, j0 + j), ONE 16-byte (float64)
-//                                           or 8-byte (float32) store; the 64 lanes of a wave write 64 consecutive entries of a row
-//   coords_mesh_kernel<INTERP, TC, TO>      the same shape; 2 x 2 or 4 x 4 control entries per thread, read through the caches (the
-//                                           control mesh is small -- 33 x 61 x 2 doubles are 32 KB -- and neighbouring lanes read
-//                                           the same entries, so the loads are broadcasts out of L1 / L2; staging it in LDS would
-//                                           cost every block of 256 entries a 32-KB fill for the 4 to 16 entries a lane needs)
-//   coords_compose_kernel<TA, TB, TO>       one thread per entry: one load of B, up to four of A, one store
-//   coords_invert_kernel<TF, TI, TO>        one thread per entry of the inverse: Newton's method on the piecewise-bilinear F (invert_point),
-//                                           four dependent 16-byte gathers of one cell of F per pass, read through the caches like
-//                                           compose's taps (neighbouring targets walk neighbouring cells); a lane leaves the loop
-//                                           when its residual meets tol, the wave runs as long as its slowest lane; ONE store per
-//                                           entry, after the loop; no LDS, no atomics, float64 throughout
+// ONE TEXT FOR DEVICE AND HOST.  Every one-thread-per-entry operation is a small functor op(i, j, s) -- entry (i, j) of set s -- that
+// holds its operands by value (BuildOp, BuildDevOp, MeshOp, ComposeOp, InvertOp, ComposeBwdOp, InvertBwdOp; the notes on loads,
+// stores and atomics are with each).  Two runners with one call shape execute it:
+//   OnDevice{stream}   launches entry_kernel<OP>: block 64 x 4 (4 waves, one row of 64 entries each, so a wave's stores are 64
+//                      consecutive entries of a row), grid (ceil(oW / 64), ceil(oH / 4), sets), the (i, j) guard, blockIdx.z = the set
+//   OnHost{}           the plain s, i, j loop over host pointers
+// and every operation is ONE function template over the runner (coords::build, mesh, compose, ...): the argument checks, the dtype and
+// model dispatch, run(Op{...}, oH, oW[, sets]).  The C entry points lerf_coords_X / lerf_coords_X_host are that template with one
+// runner or the other, so the device and the host twin cannot drift apart: they agree bit for bit by construction (the two
+// scatters excepted, below).  Add2 is the one scatter: two float64 atomicAdd where compiled for the device, a plain add on the host.
+// MapReader is the one strided-map reader handed to the *_point functions; a dense float64 gradient [h][w][2] is a map of row stride 2w.
+//
+// Kernels of their own shape (unchanged by the above):
 //   coords_mesh_bwd_{rows,cols}_kernel      the adjoint of the mesh upsample, map = Wr . ctrl . Wc^T  =>  grad_ctrl = Wr^T . grad_map . Wc,
 //                                           in two gather-shaped passes, each sum in a fixed order and without atomics:
 //       rows   tmp[a][j] = sum_i Wr[i][a] grad_map[i][j]: a block owns vertex row a and 64 columns; its 4 waves take the rows of a's
@@ -28,19 +28,6 @@
 //       (mesh_reach); rows without a tap on a weigh exactly 0 and are skipped, so the transpose is exact, clamped border taps
 //       of the bicubic included.  A 33 x 61 mesh under 2160 x 3840: 270 rows per vertex row in pass 1 (68 per wave), 252 columns per
 //       vertex in pass 2 (4 per lane); grad_map is read 4 times (bicubic) or twice (bilinear), coalesced, tmp is 2 MB.
-//   coords_compose_bwd_kernel<TA, TB>       the adjoint of compose, one thread per entry (compose_bwd_point): one load of B and of
-//                                           grad_out; the inner gradient reads the four corners of the cell of A and has ONE writer per
-//                                           entry -- a plain 16-byte load-add-store into grad_b, bit-equal from run to run and to the host
-//                                           twin; the outer gradient is a data-dependent bilinear scatter: up to four taps, two float64
-//                                           atomicAdd each, into grad_a in global memory -- equal from run to run up to the rounding of a
-//                                           reordered float64 sum, like the image and hyper gradients of lerf_remap_bwd.  A null grad_a
-//                                           issues no atomics, a null grad_b no loads of A.  No LDS, no workspace.
-//   coords_invert_bwd_kernel<TF, TG>        the adjoint of invert by the implicit function theorem (invert_bwd_point): one load of G and
-//                                           of grad_out, the four corners of one cell of F, the 2 x 2 solve v = -J^-T g, the same scatter
-//                                           of v into grad_f (float64 atomicAdd)
-//   coords_build_dev_kernel<MODEL, TO>      coords_build_kernel with the parameters in DEVICE memory, [n_sets][n_params] float64: blockIdx.z is
-//                                           the set, its parameters are read at a wave-uniform address (scalar loads), model_point is
-//                                           called unchanged: map s is bit-equal to lerf_coords_build of the same doubles
 //   coords_build_bwd_{partial,sum}_kernel   the adjoint of the builders, grad_params[s][k] += sum over the entries of dp[k] (model_point_bwd):
 //                                           a reduction of 9 / 8 / 21 / 17 / 13 sums over every entry, in two passes, fixed order, no atomics
 //       partial  a block owns 64 columns x a band of 64 rows of one set; wave w takes the rows w, w + 4, ... of the band (16 per lane),
@@ -48,20 +35,20 @@
 //                LDS and are added in the order 0, 1, 2, 3; ONE partial vector per block goes to the workspace ([set][k][block])
 //       sum      ONE wave per (set, k): lane l adds the partials l, l + 64, ..., the same tree, lane 0 is the one writer (load-add-store)
 //       2160 x 3840: 2 040 blocks a set in pass 1 (8 per CU), 343 KB of partials for the 21 sums of brown; grad_map is read once, coalesced
-//
+//       The host twin emulates the two passes lane by lane (lerf_coords_build_bwd_host, at the end of this file).
 //   coords_math_kernel                      sqrt_pm / atan_pm / atan2_pm of lerf_coords_models.h, one thread per element: what the fisheye and
 //                                           equirect models are built on, exported so that their bit-equality with the host is tested directly
 //
-// Addresses: every kernel guards (i, j) against the tile, writes entry (i, j) of `out` only, and reads ctrl / A at indices that
+// Addresses: entry_kernel guards (i, j) against the tile; a functor writes entry (i, j) of `out` only, and reads ctrl / A at indices that
 // mesh_axis / compose_axis clamp into the operand after clipping the position in floating point (no value of B reaches an int
 // conversion unclipped).  The inverse reads init at entry (i, j) only and F at the three corners of its start and at cells
 // compose_axis picks for the iterate (fH, fW >= 2, so i0 + 1 <= fH - 1), whatever F, init or the iterate hold.  The passes of the
-// adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].  The adjoints of compose and invert read
+// mesh adjoint index grad_map inside [oH][oW], tmp inside [gh][oW], grad_ctrl inside [gh][gw].  The adjoints of compose and invert read
 // B / G, grad_out and grad_b at entry (i, j) only, and read A / F and add into grad_a / grad_f at the cell compose_axis picks (aH, aW,
 // fH, fW >= 2 are checked on the host, so i0 + 1 <= n - 1), whatever the maps hold.  The kernels that read device parameters index
-// params and grad_params inside [n_sets][n_params], grad_map at (set, i, j) with i < oH, j < oW, the workspace inside
-// [n_sets][n_params][blocks]; no parameter value forms an address.  coords_math_kernel reads x (and y, for atan2 only) and writes out at
-// element e < n alone; no argument value forms an address.
+// params and grad_params inside [n_sets][n_params], out and grad_map at (set, i, j) with set < n_sets, i < oH, j < oW, the workspace
+// inside [n_sets][n_params][blocks]; no parameter value forms an address.  coords_math_kernel reads x (and y, for atan2 only) and writes
+// out at element e < n alone; no argument value forms an address.
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
 
@@ -87,45 +74,171 @@ LERF_HD inline Point load_entry(const T* m, int64_t stride, int i, int j) {
     return {(double)v.r, (double)v.c};
 }
 
+// a map operand under the strided contract, read at (row, col): what the *_point functions take as READ / LOAD
+template <typename T>
+struct MapReader {
+    const T* m;
+    int64_t stride;
+    LERF_HD Point operator()(int r, int c) const { return load_entry(m, stride, r, c); }
+};
+
+// the scatter of the two adjoints: grad [h][w][2] dense float64.  Device: two float64 atomicAdd per tap into global memory -- equal
+// from run to run up to the rounding of a reordered sum, like the image and hyper gradients of lerf_remap_bwd.  Host: a plain add.
+struct Add2 {
+    double* grad;
+    int w;
+    LERF_HD void operator()(int r, int c, double dr, double dc) const {
+        double* p = grad + 2 * ((int64_t)r * w + c);
+#ifdef __HIP_DEVICE_COMPILE__
+        atomicAdd(p, dr);
+        atomicAdd(p + 1, dc);
+#else
+        p[0] += dr;
+        p[1] += dc;
+#endif
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ the per-entry operations
+// the model's point of pixel (i0 + i, j0 + j), ONE 16-byte (float64) or 8-byte (float32) store; the parameters travel by value
 template <int MODEL, typename TO>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_build_kernel(Params prm, TO* __restrict__ out, int64_t stride, int oH, int oW, int i0, int j0) {
-    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
-    if (i >= oH || j >= oW) return;
-    store_entry(out, stride, i, j, model_point<MODEL>(prm.p, i0 + i, j0 + j));
-}
+struct BuildOp {
+    Params prm;
+    TO* out;
+    int64_t stride;
+    int i0, j0;
+    LERF_HD void operator()(int i, int j, int) const { store_entry(out, stride, i, j, model_point<MODEL>(prm.p, i0 + i, j0 + j)); }
+};
 
+// BuildOp with the parameters in DEVICE memory, [n_sets][n_params] float64: set s reads its own at a wave-uniform address (scalar
+// loads) and writes map s; model_point is called unchanged, so map s is bit-equal to lerf_coords_build of the same doubles
+template <int MODEL, typename TO>
+struct BuildDevOp {
+    const double* params;
+    TO* out;
+    int64_t set_stride, stride;
+    int i0, j0;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const double* p = params + (size_t)s * model_params(MODEL);
+        store_entry(out + (int64_t)s * set_stride, stride, i, j, model_point<MODEL>(p, i0 + i, j0 + j));
+    }
+};
+
+// 2 x 2 or 4 x 4 control entries per entry, read through the caches (the control mesh is small -- 33 x 61 x 2 doubles are 32 KB -- and
+// neighbouring lanes read the same entries, so the loads are broadcasts out of L1 / L2; staging it in LDS would cost every block of
+// 256 entries a 32-KB fill for the 4 to 16 entries a lane needs); one store
 template <int INTERP, typename TC, typename TO>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_mesh_kernel(const TC* __restrict__ ctrl, int gh, int gw, int full_h, int full_w, TO* __restrict__ out, int64_t stride, int oH,
-                   int oW, int i0, int j0) {
-    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
-    if (i >= oH || j >= oW) return;
-    store_entry(out, stride, i, j, mesh_point<INTERP>(ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j));
-}
+struct MeshOp {
+    const TC* ctrl;
+    int gh, gw, full_h, full_w;
+    TO* out;
+    int64_t stride;
+    int i0, j0;
+    LERF_HD void operator()(int i, int j, int) const {
+        store_entry(out, stride, i, j, mesh_point<INTERP>(ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j));
+    }
+};
 
+// one load of B, up to four of A, one store
 template <typename TA, typename TB, typename TO>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_compose_kernel(const TA* __restrict__ A, int64_t a_stride, int aH, int aW, const TB* __restrict__ B, int64_t b_stride,
-                      TO* __restrict__ out, int64_t o_stride, int oH, int oW) {
+struct ComposeOp {
+    MapReader<TA> A;
+    int aH, aW;
+    MapReader<TB> B;
+    TO* out;
+    int64_t stride;
+    LERF_HD void operator()(int i, int j, int) const {
+        const Point q = B(i, j);
+        store_entry(out, stride, i, j, compose_point(q.r, q.c, aH, aW, A));
+    }
+};
+
+// one entry of the inverse: Newton's method on the piecewise-bilinear F (invert_point), four dependent 16-byte gathers of one cell of
+// F per pass, read through the caches like compose's taps (neighbouring targets walk neighbouring cells); on the device a lane leaves
+// the loop when its residual meets tol and the wave runs as long as its slowest lane; ONE store per entry, after the loop; no LDS, no
+// atomics, float64 throughout.  init.m == nullptr: the affine start (three more loads of F, the same entries for every lane: broadcasts)
+template <typename TF, typename TI, typename TO>
+struct InvertOp {
+    MapReader<TF> F;
+    int fH, fW;
+    MapReader<TI> init;
+    TO* out;
+    int64_t stride;
+    int i0, j0, max_iter;
+    double tol;
+    LERF_HD void operator()(int i, int j, int) const {
+        const double q_r = (double)(i0 + i), q_c = (double)(j0 + j);
+        const Point u0 = init.m ? init(i, j) : invert_start(q_r, q_c, fH, fW, F);
+        store_entry(out, stride, i, j, invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, F));
+    }
+};
+
+// the adjoint of compose (compose_bwd_point): one load of B and of grad_out; the inner gradient reads the four corners of the cell of A
+// and has ONE writer per entry -- a plain 16-byte load-add-store into grad_b, bit-equal from run to run and between device and host; the
+// outer gradient is a data-dependent bilinear scatter, up to four taps through Add2 into grad_a.  A null grad_a issues no scatter, a
+// null grad_b no loads of A.  No LDS, no workspace.
+template <typename TA, typename TB>
+struct ComposeBwdOp {
+    MapReader<TA> A;
+    int aH, aW;
+    MapReader<TB> B;
+    MapReader<double> gout;
+    double *gA, *gB;
+    LERF_HD void operator()(int i, int j, int) const {
+#pragma clang fp contract(off)
+        const Point q = B(i, j);
+        const Point d = compose_bwd_point(q.r, q.c, gout(i, j), aH, aW, gA != nullptr, gB != nullptr, A, Add2{gA, aW});
+        if (gB) {
+            const Point v = load_entry(gB, gout.stride, i, j);
+            store_entry(gB, gout.stride, i, j, Point{v.r + d.r, v.c + d.c});
+        }
+    }
+};
+
+// the adjoint of invert by the implicit function theorem (invert_bwd_point): one load of G and of grad_out, the four corners of one cell
+// of F, the 2 x 2 solve v = -J^-T g, the scatter of v through Add2 into grad_f
+template <typename TF, typename TG>
+struct InvertBwdOp {
+    MapReader<TF> F;
+    int fH, fW;
+    MapReader<TG> G;
+    MapReader<double> gout;
+    double* gF;
+    LERF_HD void operator()(int i, int j, int) const {
+        const Point u = G(i, j);
+        invert_bwd_point(u.r, u.c, gout(i, j), fH, fW, F, Add2{gF, fW});
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ the two runners
+// 8 waves per SIMD (64 VGPRs) hold for every operation; stated, so that the bicubic mesh over a float64 control mesh stays at 64, not 66
+template <typename OP>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS) __attribute__((amdgpu_waves_per_eu(8))) entry_kernel(const OP op, int oH, int oW) {
     const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
     if (i >= oH || j >= oW) return;
-    const Point q = load_entry(B, b_stride, i, j);
-    store_entry(out, o_stride, i, j, compose_point(q.r, q.c, aH, aW, [&](int r, int c) { return load_entry(A, a_stride, r, c); }));
+    op(i, j, (int)blockIdx.z);
 }
 
-// init == nullptr: the affine start (three more loads of F, the same entries for every lane: broadcasts)
-template <typename TF, typename TI, typename TO>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_invert_kernel(const TF* __restrict__ F, int64_t f_stride, int fH, int fW, const TI* __restrict__ init, int64_t i_stride,
-                     TO* __restrict__ out, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol) {
-    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
-    if (i >= oH || j >= oW) return;
-    const auto load = [&](int r, int c) { return load_entry(F, f_stride, r, c); };
-    const double q_r = (double)(i0 + i), q_c = (double)(j0 + j);
-    const Point u0 = init ? load_entry(init, i_stride, i, j) : invert_start(q_r, q_c, fH, fW, load);
-    store_entry(out, o_stride, i, j, invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, load));
-}
+struct OnDevice {
+    hipStream_t stream;
+    template <typename OP>
+    int operator()(const OP& op, int oH, int oW, int sets = 1) const {
+        clear_stale_error();
+        const dim3 grid((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS, sets);
+        hipLaunchKernelGGL(entry_kernel<OP>, grid, dim3(CB_COLS, CB_ROWS), 0, stream, op, oH, oW);
+        return launch_status();
+    }
+};
+
+struct OnHost {
+    template <typename OP>
+    int operator()(const OP& op, int oH, int oW, int sets = 1) const {
+        for (int s = 0; s < sets; ++s)
+            for (int i = 0; i < oH; ++i)
+                for (int j = 0; j < oW; ++j) op(i, j, s);
+        return LERF_OK;
+    }
+};
 
 // pass 1 of the adjoint: grid (ceil(oW / 64), gh), block (64, 4)
 template <int INTERP>
@@ -186,72 +299,6 @@ coords_mesh_bwd_cols_kernel(const double2* __restrict__ tmp, int oW, int gw, dou
         v.y += sy;
         *dst = v;
     }
-}
-
-// the scatter of the device side: grad [h][w][2] dense float64, two atomic adds per tap
-struct AtomicAdd2 {
-    double* grad;
-    int w;
-    __device__ void operator()(int r, int c, double dr, double dc) const {
-        double* p = grad + 2 * ((int64_t)r * w + c);
-        atomicAdd(p, dr);
-        atomicAdd(p + 1, dc);
-    }
-};
-
-// the host twin's: a plain add
-struct PlainAdd2 {
-    double* grad;
-    int w;
-    void operator()(int r, int c, double dr, double dc) const {
-        double* p = grad + 2 * ((int64_t)r * w + c);
-        p[0] += dr;
-        p[1] += dc;
-    }
-};
-
-// gA == nullptr: no scatter; gB == nullptr: A is not read
-template <typename TA, typename TB>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_compose_bwd_kernel(const TA* __restrict__ A, int64_t a_stride, int aH, int aW, const TB* __restrict__ B, int64_t b_stride,
-                          const double2* __restrict__ gout, int oH, int oW, double* __restrict__ gA, double2* __restrict__ gB) {
-#pragma clang fp contract(off)
-    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
-    if (i >= oH || j >= oW) return;
-    const Point q = load_entry(B, b_stride, i, j);
-    const double2 g = gout[(int64_t)i * oW + j];
-    const Point d = compose_bwd_point(q.r, q.c, Point{g.x, g.y}, aH, aW, gA != nullptr, gB != nullptr,
-                                      [&](int r, int c) { return load_entry(A, a_stride, r, c); }, AtomicAdd2{gA, aW});
-    if (gB) {
-        double2* dst = gB + (int64_t)i * oW + j;
-        double2 v = *dst;
-        v.x += d.r;
-        v.y += d.c;
-        *dst = v;
-    }
-}
-
-template <typename TF, typename TG>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_invert_bwd_kernel(const TF* __restrict__ F, int64_t f_stride, int fH, int fW, const TG* __restrict__ G, int64_t g_stride,
-                         const double2* __restrict__ gout, int oH, int oW, double* __restrict__ gF) {
-    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
-    if (i >= oH || j >= oW) return;
-    const Point u = load_entry(G, g_stride, i, j);
-    const double2 g = gout[(int64_t)i * oW + j];
-    invert_bwd_point(u.r, u.c, Point{g.x, g.y}, fH, fW, [&](int r, int c) { return load_entry(F, f_stride, r, c); }, AtomicAdd2{gF, fW});
-}
-
-// the builders with device parameters: grid (ceil(oW / 64), ceil(oH / 4), n_sets)
-template <int MODEL, typename TO>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_build_dev_kernel(const double* __restrict__ params, TO* __restrict__ out, int64_t set_stride, int64_t stride, int oH, int oW, int i0,
-                        int j0) {
-    constexpr int NP = model_params(MODEL);
-    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
-    if (i >= oH || j >= oW) return;
-    const double* p = params + (size_t)blockIdx.z * NP;                 // the same address in every lane: scalar loads
-    store_entry(out + (int64_t)blockIdx.z * set_stride, stride, i, j, model_point<MODEL>(p, i0 + i, j0 + j));
 }
 
 static_assert(kBwdCols == CB_COLS && kBwdWaves == CB_ROWS && kBwdBand % kBwdWaves == 0, "the band of the build backward is the block's");
@@ -458,14 +505,6 @@ inline int math_args(int op, const double* x, const double* y, int64_t n, const 
     return LERF_OK;
 }
 
-inline dim3 entry_grid(int oH, int oW) { return dim3((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS); }
-
-}  // namespace coords
-}  // namespace lerf
-
-using namespace lerf;
-using namespace lerf::coords;
-
 // run F with the C++ type of a float dtype code
 #define LERF_COORDS_DT(code, T, ...)          \
     do {                                      \
@@ -473,36 +512,150 @@ using namespace lerf::coords;
         else { using T = double; __VA_ARGS__; } \
     } while (0)
 
+// ------------------------------------------------------------------------------------------------ the operations, over a runner
+template <typename RUN>
+int build(RUN run, int model, const double* params, int n_params, void* out, int out_dtype, int64_t stride, int oH, int oW, int i0, int j0) {
+    Params prm;
+    const int rc = build_args(model, params, n_params, out, out_dtype, stride, oH, oW, i0, j0, prm);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_MODEL(model, MODEL, LERF_COORDS_DT(out_dtype, TO, return run(BuildOp<MODEL, TO>{prm, (TO*)out, stride, i0, j0}, oH, oW)));
+}
+
+template <typename RUN>
+int build_dev(RUN run, int model, const double* params, int n_sets, int n_params, void* out, int out_dtype, int64_t set_stride,
+              int64_t stride, int oH, int oW, int i0, int j0) {
+    const int rc = build_dev_args(model, params, n_sets, n_params, out, out_dtype, set_stride, stride, oH, oW, i0, j0);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_MODEL(model, MODEL, LERF_COORDS_DT(out_dtype, TO,
+        return run(BuildDevOp<MODEL, TO>{params, (TO*)out, set_stride, stride, i0, j0}, oH, oW, n_sets)));
+}
+
+template <typename RUN>
+int mesh(RUN run, const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+         int64_t stride, int oH, int oW, int i0, int j0) {
+    const int rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, stride, oH, oW, i0, j0);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(ctrl_dtype, TC, LERF_COORDS_DT(out_dtype, TO, {
+        if (interp == LERF_MESH_BILINEAR)
+            return run(MeshOp<LERF_MESH_BILINEAR, TC, TO>{(const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, stride, i0, j0}, oH, oW);
+        return run(MeshOp<LERF_MESH_BICUBIC, TC, TO>{(const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, stride, i0, j0}, oH, oW);
+    }));
+}
+
+template <typename RUN>
+int compose(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride, void* out,
+            int out_dtype, int64_t o_stride, int oH, int oW) {
+    const int rc = compose_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, out, out_dtype, o_stride, oH, oW);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB, LERF_COORDS_DT(out_dtype, TO,
+        return run(ComposeOp<TA, TB, TO>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, (TO*)out, o_stride}, oH, oW))));
+}
+
+template <typename RUN>
+int invert(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* init, int init_dtype, int64_t i_stride,
+           void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol) {
+    const int rc = invert_args(f, f_dtype, f_stride, fH, fW, init, init_dtype, i_stride, out, out_dtype, o_stride, oH, oW, i0, j0, max_iter, tol);
+    if (rc != LERF_OK) return rc;
+    if (!init) init_dtype = LERF_F64;                     // a null init is never read: one instantiation serves
+    LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(init_dtype, TI, LERF_COORDS_DT(out_dtype, TO,
+        return run(InvertOp<TF, TI, TO>{{(const TF*)f, f_stride}, fH, fW, {(const TI*)init, i_stride}, (TO*)out, o_stride, i0, j0, max_iter, tol},
+                   oH, oW))));
+}
+
+template <typename RUN>
+int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
+                const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
+    const int rc = compose_bwd_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, grad_out, oH, oW, grad_a, grad_b);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB,
+        return run(ComposeBwdOp<TA, TB>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, {grad_out, 2 * (int64_t)oW}, grad_a, grad_b},
+                   oH, oW)));
+}
+
+template <typename RUN>
+int invert_bwd(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_stride,
+               const double* grad_out, int oH, int oW, double* grad_f) {
+    const int rc = invert_bwd_args(f, f_dtype, f_stride, fH, fW, g, g_dtype, g_stride, grad_out, oH, oW, grad_f);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(g_dtype, TG,
+        return run(InvertBwdOp<TF, TG>{{(const TF*)f, f_stride}, fH, fW, {(const TG*)g, g_stride}, {grad_out, 2 * (int64_t)oW}, grad_f}, oH, oW)));
+}
+
+}  // namespace coords
+}  // namespace lerf
+
+using namespace lerf;
+using namespace lerf::coords;
+
 extern "C" {
 
 int lerf_coords_build(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
                       int i0, int j0, void* stream) {
-    Params prm;
-    const int rc = build_args(model, params, n_params, out, out_dtype, row_stride, oH, oW, i0, j0, prm);
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
-    hipStream_t st = (hipStream_t)stream;
-    LERF_COORDS_MODEL(model, MODEL, LERF_COORDS_DT(out_dtype, TO,
-        hipLaunchKernelGGL((coords_build_kernel<MODEL, TO>), grid, block, 0, st, prm, (TO*)out, row_stride, oH, oW, i0, j0)));
-    return launch_status();
+    return build(OnDevice{(hipStream_t)stream}, model, params, n_params, out, out_dtype, row_stride, oH, oW, i0, j0);
+}
+
+int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
+                           int i0, int j0) {
+    return build(OnHost{}, model, params, n_params, out, out_dtype, row_stride, oH, oW, i0, j0);
+}
+
+int lerf_coords_build_dev(int model, const double* params_dev, int n_sets, int n_params, void* out, int out_dtype, int64_t set_stride,
+                          int64_t row_stride, int oH, int oW, int i0, int j0, void* stream) {
+    return build_dev(OnDevice{(hipStream_t)stream}, model, params_dev, n_sets, n_params, out, out_dtype, set_stride, row_stride, oH, oW, i0, j0);
 }
 
 int lerf_coords_mesh(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
                      int64_t row_stride, int oH, int oW, int i0, int j0, void* stream) {
-    const int rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
-    hipStream_t st = (hipStream_t)stream;
-#define LERF_CM(INTERP)                                                                                                             \
-    LERF_COORDS_DT(ctrl_dtype, TC, LERF_COORDS_DT(out_dtype, TO,                                                                    \
-        hipLaunchKernelGGL((coords_mesh_kernel<INTERP, TC, TO>), grid, block, 0, st, (const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, \
-                           row_stride, oH, oW, i0, j0)))
-    if (interp == LERF_MESH_BILINEAR) LERF_CM(LERF_MESH_BILINEAR);
-    else LERF_CM(LERF_MESH_BICUBIC);
-#undef LERF_CM
-    return launch_status();
+    return mesh(OnDevice{(hipStream_t)stream}, ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
+}
+
+int lerf_coords_mesh_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+                          int64_t row_stride, int oH, int oW, int i0, int j0) {
+    return mesh(OnHost{}, ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
+}
+
+int lerf_coords_compose(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
+                        void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, void* stream) {
+    return compose(OnDevice{(hipStream_t)stream}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
+}
+
+int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                             int64_t b_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW) {
+    return compose(OnHost{}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
+}
+
+int lerf_coords_invert(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                       int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_iter,
+                       double tol, void* stream) {
+    return invert(OnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype,
+                  out_row_stride, oH, oW, i0, j0, max_iter, tol);
+}
+
+int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                            int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                            int max_iter, double tol) {
+    return invert(OnHost{}, f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW, i0, j0,
+                  max_iter, tol);
+}
+
+int lerf_coords_compose_bwd(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
+                            const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, void* stream) {
+    return compose_bwd(OnDevice{(hipStream_t)stream}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
+}
+
+int lerf_coords_compose_bwd_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                 int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
+    return compose_bwd(OnHost{}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
+}
+
+int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_row_stride,
+                           const double* grad_out, int oH, int oW, double* grad_f, void* stream) {
+    return invert_bwd(OnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
+}
+
+int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f) {
+    return invert_bwd(OnHost{}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
 }
 
 size_t lerf_coords_mesh_bwd_workspace_bytes(int gh, int gw, int oH, int oW) {
@@ -529,73 +682,6 @@ int lerf_coords_mesh_bwd(const double* grad_map, int oH, int oW, int interp, int
         hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BICUBIC>), g1, b1, 0, st, gm, oH, oW, gh, tmp);
         hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BICUBIC>), g2, b2, 0, st, tmp, oW, gw, gc);
     }
-    return launch_status();
-}
-
-int lerf_coords_compose(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
-                        void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, void* stream) {
-    const int rc = compose_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
-    hipStream_t st = (hipStream_t)stream;
-    LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB, LERF_COORDS_DT(out_dtype, TO,
-        hipLaunchKernelGGL((coords_compose_kernel<TA, TB, TO>), grid, block, 0, st, (const TA*)a, a_row_stride, aH, aW, (const TB*)b,
-                           b_row_stride, (TO*)out, out_row_stride, oH, oW))));
-    return launch_status();
-}
-
-int lerf_coords_invert(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
-                       int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_iter,
-                       double tol, void* stream) {
-    const int rc = invert_args(f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW,
-                               i0, j0, max_iter, tol);
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
-    hipStream_t st = (hipStream_t)stream;
-    if (!init) init_dtype = LERF_F64;                     // the kernel never reads a null init: one instantiation serves
-    LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(init_dtype, TI, LERF_COORDS_DT(out_dtype, TO,
-        hipLaunchKernelGGL((coords_invert_kernel<TF, TI, TO>), grid, block, 0, st, (const TF*)f, f_row_stride, fH, fW, (const TI*)init,
-                           init_row_stride, (TO*)out, out_row_stride, oH, oW, i0, j0, max_iter, tol))));
-    return launch_status();
-}
-
-int lerf_coords_compose_bwd(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
-                            const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, void* stream) {
-    const int rc = compose_bwd_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
-    hipStream_t st = (hipStream_t)stream;
-    LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB,
-        hipLaunchKernelGGL((coords_compose_bwd_kernel<TA, TB>), grid, block, 0, st, (const TA*)a, a_row_stride, aH, aW, (const TB*)b,
-                           b_row_stride, reinterpret_cast<const double2*>(grad_out), oH, oW, grad_a, reinterpret_cast<double2*>(grad_b))));
-    return launch_status();
-}
-
-int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_row_stride,
-                           const double* grad_out, int oH, int oW, double* grad_f, void* stream) {
-    const int rc = invert_bwd_args(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    const dim3 block(CB_COLS, CB_ROWS), grid = entry_grid(oH, oW);
-    hipStream_t st = (hipStream_t)stream;
-    LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(g_dtype, TG,
-        hipLaunchKernelGGL((coords_invert_bwd_kernel<TF, TG>), grid, block, 0, st, (const TF*)f, f_row_stride, fH, fW, (const TG*)g,
-                           g_row_stride, reinterpret_cast<const double2*>(grad_out), oH, oW, grad_f)));
-    return launch_status();
-}
-
-int lerf_coords_build_dev(int model, const double* params_dev, int n_sets, int n_params, void* out, int out_dtype, int64_t set_stride,
-                          int64_t row_stride, int oH, int oW, int i0, int j0, void* stream) {
-    const int rc = build_dev_args(model, params_dev, n_sets, n_params, out, out_dtype, set_stride, row_stride, oH, oW, i0, j0);
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    const dim3 block(CB_COLS, CB_ROWS), grid((oW + CB_COLS - 1) / CB_COLS, (oH + CB_ROWS - 1) / CB_ROWS, n_sets);
-    hipStream_t st = (hipStream_t)stream;
-    LERF_COORDS_MODEL(model, MODEL, LERF_COORDS_DT(out_dtype, TO,
-        hipLaunchKernelGGL((coords_build_dev_kernel<MODEL, TO>), grid, block, 0, st, params_dev, (TO*)out, set_stride, row_stride, oH, oW, i0, j0)));
     return launch_status();
 }
 
@@ -634,114 +720,12 @@ int lerf_coords_math(int op, const double* x, const double* y, int64_t n, double
     return launch_status();
 }
 
-// ------------------------------------------------------------------------------------------------ host twins: the same functions, a plain loop
+// the host twins that are not a runner away: a plain loop, and the device's two passes lane by lane
 int lerf_coords_math_host(int op, const double* x, const double* y, int64_t n, double* out) {
     const int rc = math_args(op, x, y, n, out);
     if (rc != LERF_OK) return rc;
     for (int64_t e = 0; e < n; ++e)
         out[e] = op == LERF_MATH_SQRT ? sqrt_pm(x[e]) : op == LERF_MATH_ATAN ? atan_pm(x[e]) : atan2_pm(x[e], y[e]);
-    return LERF_OK;
-}
-
-int lerf_coords_build_host(int model, const double* params, int n_params, void* out, int out_dtype, int64_t row_stride, int oH, int oW,
-                           int i0, int j0) {
-    Params prm;
-    const int rc = build_args(model, params, n_params, out, out_dtype, row_stride, oH, oW, i0, j0, prm);
-    if (rc != LERF_OK) return rc;
-    for (int i = 0; i < oH; ++i)
-        for (int j = 0; j < oW; ++j) {
-            Point q;
-            LERF_COORDS_MODEL(model, MODEL, q = model_point<MODEL>(prm.p, i0 + i, j0 + j));
-            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, row_stride, i, j, q));
-        }
-    return LERF_OK;
-}
-
-int lerf_coords_mesh_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
-                          int64_t row_stride, int oH, int oW, int i0, int j0) {
-    const int rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
-    if (rc != LERF_OK) return rc;
-    for (int i = 0; i < oH; ++i)
-        for (int j = 0; j < oW; ++j) {
-            Point q;
-            LERF_COORDS_DT(ctrl_dtype, TC,
-                           q = interp == LERF_MESH_BILINEAR ? mesh_point<LERF_MESH_BILINEAR>((const TC*)ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j)
-                                                            : mesh_point<LERF_MESH_BICUBIC>((const TC*)ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j));
-            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, row_stride, i, j, q));
-        }
-    return LERF_OK;
-}
-
-int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
-                             int64_t b_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW) {
-    const int rc = compose_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
-    if (rc != LERF_OK) return rc;
-    for (int i = 0; i < oH; ++i)
-        for (int j = 0; j < oW; ++j) {
-            Point q, v;
-            LERF_COORDS_DT(b_dtype, TB, q = load_entry((const TB*)b, b_row_stride, i, j));
-            LERF_COORDS_DT(a_dtype, TA, v = compose_point(q.r, q.c, aH, aW, [&](int r, int c) { return load_entry((const TA*)a, a_row_stride, r, c); }));
-            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, out_row_stride, i, j, v));
-        }
-    return LERF_OK;
-}
-
-int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
-                            int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
-                            int max_iter, double tol) {
-    const int rc = invert_args(f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW,
-                               i0, j0, max_iter, tol);
-    if (rc != LERF_OK) return rc;
-    for (int i = 0; i < oH; ++i)
-        for (int j = 0; j < oW; ++j) {
-            const double q_r = (double)(i0 + i), q_c = (double)(j0 + j);
-            Point u0, v;
-            LERF_COORDS_DT(f_dtype, TF, {
-                const auto load = [&](int r, int c) { return load_entry((const TF*)f, f_row_stride, r, c); };
-                if (init) LERF_COORDS_DT(init_dtype, TI, u0 = load_entry((const TI*)init, init_row_stride, i, j));
-                else u0 = invert_start(q_r, q_c, fH, fW, load);
-                v = invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, load);
-            });
-            LERF_COORDS_DT(out_dtype, TO, store_entry((TO*)out, out_row_stride, i, j, v));
-        }
-    return LERF_OK;
-}
-
-int lerf_coords_compose_bwd_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
-                                 int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
-#pragma clang fp contract(off)
-    const int rc = compose_bwd_args(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
-    if (rc != LERF_OK) return rc;
-    for (int i = 0; i < oH; ++i)
-        for (int j = 0; j < oW; ++j) {
-            const int64_t e = 2 * ((int64_t)i * oW + j);
-            Point q, d;
-            LERF_COORDS_DT(b_dtype, TB, q = load_entry((const TB*)b, b_row_stride, i, j));
-            LERF_COORDS_DT(a_dtype, TA, d = compose_bwd_point(q.r, q.c, Point{grad_out[e], grad_out[e + 1]}, aH, aW, grad_a != nullptr,
-                                                              grad_b != nullptr,
-                                                              [&](int r, int c) { return load_entry((const TA*)a, a_row_stride, r, c); },
-                                                              PlainAdd2{grad_a, aW}));
-            if (grad_b) {
-                grad_b[e] += d.r;
-                grad_b[e + 1] += d.c;
-            }
-        }
-    return LERF_OK;
-}
-
-int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
-                                int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f) {
-    const int rc = invert_bwd_args(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
-    if (rc != LERF_OK) return rc;
-    for (int i = 0; i < oH; ++i)
-        for (int j = 0; j < oW; ++j) {
-            const int64_t e = 2 * ((int64_t)i * oW + j);
-            Point u;
-            LERF_COORDS_DT(g_dtype, TG, u = load_entry((const TG*)g, g_row_stride, i, j));
-            LERF_COORDS_DT(f_dtype, TF, invert_bwd_point(u.r, u.c, Point{grad_out[e], grad_out[e + 1]}, fH, fW,
-                                                         [&](int r, int c) { return load_entry((const TF*)f, f_row_stride, r, c); },
-                                                         PlainAdd2{grad_f, fW}));
-        }
     return LERF_OK;
 }
 

@@ -1021,47 +1021,15 @@ def patch_batch(pool_u8, desc, C_out, sz, hsz, noise=None, desc_dev=None, im=Non
 
 
 # --------------------------------------------------------------------------- coordinate maps on the device
-def _map_tensor(t, what):
-    """(tensor, row stride) of a device map under the strided contract ([h, w, 2], column stride 2, any row stride)"""
-    torch = _torch()
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.ndim != 3 or t.shape[2] != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError("%s must be a device tensor [h, w, 2]" % what)
-    if t.dtype not in (torch.float32, torch.float64):
-        raise ValueError("%s must be float32 or float64" % what)
-    if t.stride(2) != 1 or t.stride(1) != 2:
-        raise ValueError("%s: contiguous (row, col) pairs, column stride 2" % what)
-    return t, t.stride(0)
-
-
-def _map_out(out, out_hw, dtype, device, what):
-    torch = _torch()
-    oH, oW = int(out_hw[0]), int(out_hw[1])
-    if out is None:
-        if oH < 1 or oW < 1:
-            raise ValueError("%s: out_hw must be positive" % what)
-        if dtype not in (torch.float32, torch.float64):
-            raise ValueError("%s: dtype is torch.float32 or torch.float64" % what)
-        out = torch.empty((oH, oW, 2), dtype=dtype, device=device)
-    elif tuple(out.shape[:2]) != (oH, oW):
-        raise ValueError("%s: out must be [%d, %d, 2]" % (what, oH, oW))
-    return _map_tensor(out, "out")
-
-
 def coords_build(model, params, out_hw, dtype=None, out=None, origin=(0, 0), device=None):
     """lerf_coords_build: the map [oH, oW, 2] of `model` ("homography": the 9 entries of the INVERSE matrix; "radial": cr, cc,
     no, ni, hr, hc, k1, k2; "brown": inv(new_K . R)[9], fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6; "fisheye": inv(new_K . R)[9],
     fx, fy, cx, cy, k1, k2, k3, k4; "equirect": inv(K_view . R)[9], sx, sy, cxp, cyp) written by the kernel.
     out: a device tensor or a strided tile view of a larger map, built in place at `origin` = (i0, j0) of the whole map; else a
     new tensor of `dtype` (default float64) on `device` (default: the current one)."""
-    torch = _torch()
-    code, p = _lib.coords_model_params(model, params)
-    dev = out.device if out is not None else torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    out, stride = _map_out(out, out_hw, torch.float64 if dtype is None else dtype, dev, "lerf_coords_build")
-    with _lib.on_device(out):
-        _lib.check(_lib.lib().lerf_coords_build(code, p.ctypes.data, int(p.size), out.data_ptr(), _lib._dt(out), stride, int(out_hw[0]),
-                                                int(out_hw[1]), int(origin[0]), int(origin[1]), _lib.current_stream(out.device)),
-                   "lerf_coords_build")
-    return out
+    X = _lib.DeviceOperands()
+    dev = out.device if out is not None else X.torch.device("cuda", X.torch.cuda.current_device()) if device is None else X.torch.device(device)
+    return _lib.coords_build_on(X, model, params, out_hw, dtype, out, origin, dev)
 
 
 def _params_tensor(model, params, what):
@@ -1097,7 +1065,7 @@ def coords_build_params(model, params, out_hw, dtype=None, out=None, origin=(0, 
         raise ValueError("lerf_coords_build_dev: out must be %s" % ("[%d, %d, 2]" % (oH, oW) if p.ndim == 1 else "[%d, %d, %d, 2]" % (B, oH, oW)))
     elif out.device != p.device:
         raise ValueError("lerf_coords_build_dev: params and out live on different devices")
-    _, stride = _map_tensor(out if p.ndim == 1 else out[0], "out")
+    _, stride = _lib.DeviceOperands().map(out if p.ndim == 1 else out[0], "out")
     set_stride = 0 if p.ndim == 1 else int(out.stride(0))
     with _lib.on_device(out):
         _lib.check(_lib.lib().lerf_coords_build_dev(code, p.data_ptr(), B, int(p.shape[-1]), out.data_ptr(), _lib._dt(out), set_stride, stride,
@@ -1140,47 +1108,14 @@ def coords_math(op, x, y=None):
     """lerf_coords_math: sqrt_pm(x), atan_pm(x) or atan2_pm(x, y) (op "sqrt", "atan", "atan2") of float64 device tensors, one thread per
     element: the helpers the fisheye and equirect models are built on, bit-equal to _lib.coords_math_host -> a new float64 tensor of
     x's shape on x's device"""
-    torch = _torch()
-    if op not in _lib.COORDS_MATH_OPS:
-        raise ValueError("op is one of %s, not %r" % (", ".join(_lib.COORDS_MATH_OPS), op))
-    ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64
-    if not ok(x) or (op == "atan2" and (not ok(y) or y.shape != x.shape or y.device != x.device)):
-        raise ValueError("lerf_coords_math: x (and y for atan2) must be float64 device tensors of one shape on one device")
-    a = x.detach().contiguous()
-    b = y.detach().contiguous() if op == "atan2" else None
-    out = torch.empty_like(a)
-    if a.numel() == 0:
-        return out
-    with _lib.on_device(a):
-        _lib.check(_lib.lib().lerf_coords_math(_lib.COORDS_MATH_OPS[op], a.data_ptr(), None if b is None else b.data_ptr(), a.numel(),
-                                               out.data_ptr(), _lib.current_stream(a.device)), "lerf_coords_math")
-    return out
-
-
-def _ctrl_tensor(ctrl, what):
-    torch = _torch()
-    if not isinstance(ctrl, torch.Tensor) or not ctrl.is_cuda or ctrl.ndim != 3 or ctrl.shape[2] != 2:
-        raise ValueError("%s: ctrl must be a device tensor [gh, gw, 2]" % what)
-    if ctrl.dtype not in (torch.float32, torch.float64):
-        raise ValueError("%s: ctrl must be float32 or float64" % what)
-    return ctrl.detach().contiguous()
+    return _lib.coords_math_on(_lib.DeviceOperands(), op, x, y)
 
 
 def coords_mesh(ctrl, out_hw, interp="bilinear", dtype=None, out=None, origin=(0, 0), full_hw=None):
     """lerf_coords_mesh: the control mesh ctrl [gh, gw, 2] (device, float32 / float64, absolute source positions at vertices
     placed align-corners over the map full_hw, default out_hw) upsampled to the tile out_hw at `origin`; interp "bilinear" or
     "bicubic" (Keys A = -0.75, clamped border taps).  dtype: the map's, default ctrl's."""
-    c = _ctrl_tensor(ctrl, "lerf_coords_mesh")
-    code = _lib.mesh_interp_code(interp)
-    full_hw = out_hw if full_hw is None else full_hw
-    out, stride = _map_out(out, out_hw, c.dtype if dtype is None else dtype, c.device, "lerf_coords_mesh")
-    if out.device != c.device:
-        raise ValueError("lerf_coords_mesh: ctrl and out live on different devices")
-    with _lib.on_device(c):
-        _lib.check(_lib.lib().lerf_coords_mesh(c.data_ptr(), _lib._dt(c), c.shape[0], c.shape[1], code, int(full_hw[0]), int(full_hw[1]),
-                                               out.data_ptr(), _lib._dt(out), stride, int(out_hw[0]), int(out_hw[1]), int(origin[0]),
-                                               int(origin[1]), _lib.current_stream(c.device)), "lerf_coords_mesh")
-    return out
+    return _lib.coords_mesh_on(_lib.DeviceOperands(), ctrl, out_hw, interp, dtype, out, origin, full_hw)
 
 
 def coords_mesh_bwd(grad_map, ctrl_hw, interp="bilinear", grad_ctrl=None):
@@ -1212,17 +1147,7 @@ def coords_compose(outer, inner, dtype=None, out=None):
     """lerf_coords_compose: C[i, j] = outer(inner[i, j]) -- the outer map sampled bilinearly at the positions the inner map
     holds, so remap(remap(img, outer), inner) and remap(img, C) describe the same geometry.  Device maps under the strided
     contract, any mix of float32 / float64; dtype: C's, default inner's."""
-    a, sa = _map_tensor(outer, "outer")
-    b, sb = _map_tensor(inner, "inner")
-    if a.device != b.device:
-        raise ValueError("lerf_coords_compose: outer and inner live on different devices")
-    a, b = a.detach(), b.detach()
-    out, so = _map_out(out, b.shape[:2], b.dtype if dtype is None else dtype, b.device, "lerf_coords_compose")
-    with _lib.on_device(b):
-        _lib.check(_lib.lib().lerf_coords_compose(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], b.data_ptr(), _lib._dt(b), sb,
-                                                  out.data_ptr(), _lib._dt(out), so, b.shape[0], b.shape[1],
-                                                  _lib.current_stream(b.device)), "lerf_coords_compose")
-    return out
+    return _lib.coords_compose_on(_lib.DeviceOperands(), outer, inner, dtype, out)
 
 
 def coords_invert(f, out_hw, init=None, dtype=None, out=None, origin=(0, 0), max_iter=16, tol=1e-9):
@@ -1232,33 +1157,7 @@ def coords_invert(f, out_hw, init=None, dtype=None, out=None, origin=(0, 0), max
     read.  out_hw: the size of the frame f points into.  Device maps under the strided contract (tile views of f, init and out
     with `origin` = the tile's place in the whole inverse), any mix of float32 / float64; dtype: G's, default f's.  One launch on
     the current stream, no sync."""
-    a, sa = _map_tensor(f, "f")
-    a = a.detach()
-    b, sb = (None, 0) if init is None else _map_tensor(init, "init")
-    out, so = _map_out(out, out_hw, a.dtype if dtype is None else dtype, a.device, "lerf_coords_invert")
-    if out.device != a.device or (b is not None and b.device != a.device):
-        raise ValueError("lerf_coords_invert: f, init and out live on different devices")
-    if b is not None:
-        b = b.detach()
-        if tuple(b.shape[:2]) != tuple(out.shape[:2]):
-            raise ValueError("lerf_coords_invert: init must have out's shape")
-    with _lib.on_device(a):
-        _lib.check(_lib.lib().lerf_coords_invert(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], None if b is None else b.data_ptr(),
-                                                 _lib.LERF_F64 if b is None else _lib._dt(b), sb, out.data_ptr(), _lib._dt(out), so,
-                                                 out.shape[0], out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol),
-                                                 _lib.current_stream(a.device)), "lerf_coords_invert")
-    return out
-
-
-def _grad_tensor(g, shape, device, what):
-    """a dense float64 gradient buffer [h, w, 2] on `device` (None: a zeroed one)"""
-    torch = _torch()
-    if g is None:
-        return torch.zeros(tuple(shape), dtype=torch.float64, device=device)
-    if not isinstance(g, torch.Tensor) or g.dtype != torch.float64 or tuple(g.shape) != tuple(shape) or not g.is_contiguous() \
-            or g.device != device:
-        raise ValueError("%s must be a contiguous float64 tensor %s on the maps' device" % (what, list(shape)))
-    return g
+    return _lib.coords_invert_on(_lib.DeviceOperands(), f, out_hw, init, dtype, out, origin, max_iter, tol)
 
 
 def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):
@@ -1267,24 +1166,7 @@ def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None,
     a reordered sum) and grad_inner (float64 contiguous [oH, oW, 2]: one writer per entry, bit-reproducible); None: zeroed ones;
     need[k] False skips that half and returns None for it.  The maps are device tensors under the strided contract, the outer
     map at least 2 x 2.  One launch on the current stream, no sync -> (grad_outer, grad_inner)."""
-    a, sa = _map_tensor(outer, "outer")
-    b, sb = _map_tensor(inner, "inner")
-    if a.device != b.device:
-        raise ValueError("lerf_coords_compose_bwd: outer and inner live on different devices")
-    if not (need[0] or need[1]):
-        raise ValueError("lerf_coords_compose_bwd: at least one of the two gradients is needed")
-    a, b = a.detach(), b.detach()
-    if grad_out is None:
-        raise ValueError("lerf_coords_compose_bwd: grad_out must be a contiguous float64 device tensor [oH, oW, 2]")
-    g = _grad_tensor(grad_out, b.shape, b.device, "lerf_coords_compose_bwd: grad_out")
-    ga = _grad_tensor(grad_outer, a.shape, b.device, "lerf_coords_compose_bwd: grad_outer") if need[0] else None
-    gb = _grad_tensor(grad_inner, b.shape, b.device, "lerf_coords_compose_bwd: grad_inner") if need[1] else None
-    with _lib.on_device(b):
-        _lib.check(_lib.lib().lerf_coords_compose_bwd(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], b.data_ptr(), _lib._dt(b), sb,
-                                                      g.data_ptr(), b.shape[0], b.shape[1], None if ga is None else ga.data_ptr(),
-                                                      None if gb is None else gb.data_ptr(), _lib.current_stream(b.device)),
-                   "lerf_coords_compose_bwd")
-    return ga, gb
+    return _lib.coords_compose_bwd_on(_lib.DeviceOperands(), outer, inner, grad_out, grad_outer, grad_inner, need)
 
 
 def coords_invert_bwd(f, inverse, grad_out, grad_f=None):
@@ -1293,17 +1175,4 @@ def coords_invert_bwd(f, inverse, grad_out, grad_f=None):
     scatter of -J^-T grad_out at the cell of every entry of the inverse (float64 atomic adds); NaN entries of the inverse, NaN
     corners and folded cells contribute nothing.  Device maps under the strided contract.  One launch on the current stream, no
     sync."""
-    a, sa = _map_tensor(f, "f")
-    b, sb = _map_tensor(inverse, "inverse")
-    if a.device != b.device:
-        raise ValueError("lerf_coords_invert_bwd: f and inverse live on different devices")
-    a, b = a.detach(), b.detach()
-    if grad_out is None:
-        raise ValueError("lerf_coords_invert_bwd: grad_out must be a contiguous float64 device tensor [oH, oW, 2]")
-    g = _grad_tensor(grad_out, b.shape, b.device, "lerf_coords_invert_bwd: grad_out")
-    gf = _grad_tensor(grad_f, a.shape, b.device, "lerf_coords_invert_bwd: grad_f")
-    with _lib.on_device(b):
-        _lib.check(_lib.lib().lerf_coords_invert_bwd(a.data_ptr(), _lib._dt(a), sa, a.shape[0], a.shape[1], b.data_ptr(), _lib._dt(b), sb,
-                                                     g.data_ptr(), b.shape[0], b.shape[1], gf.data_ptr(), _lib.current_stream(b.device)),
-                   "lerf_coords_invert_bwd")
-    return gf
+    return _lib.coords_invert_bwd_on(_lib.DeviceOperands(), f, inverse, grad_out, grad_f)

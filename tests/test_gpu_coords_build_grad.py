@@ -1,4 +1,4 @@
-"""The model builders with device parameters and their adjoint on the device (coords_build_dev_kernel and
+"""The model builders with device parameters and their adjoint on the device (entry_kernel<BuildDevOp> and
 coords_build_bwd_{partial,sum}_kernel of csrc/lerf_coords.hip behind ops.coords_build_params / coords_build_bwd and
 coords.from_homography_torch / radial_torch / undistort_rectify_torch).  The bounds are the ones tests/test_coords_build_grad_cpu.py
 settles on the host twin:

@@ -1,4 +1,4 @@
-"""The adjoints of compose and invert on the device (coords_compose_bwd_kernel, coords_invert_bwd_kernel of csrc/lerf_coords.hip behind
+"""The adjoints of compose and invert on the device (entry_kernel<ComposeBwdOp>, entry_kernel<InvertBwdOp> of csrc/lerf_coords.hip behind
 ops.coords_compose_bwd / coords_invert_bwd and coords.compose_torch / invert_torch / invert_flow_torch).  The bounds are the ones
 tests/test_coords_grad_cpu.py settles on the host twins:
 

@@ -1,4 +1,4 @@
-"""The map inverse on the device (coords_invert_kernel of csrc/lerf_coords.hip behind ops.coords_invert and coords.invert):
+"""The map inverse on the device (entry_kernel<InvertOp> of csrc/lerf_coords.hip behind ops.coords_invert and coords.invert):
 
   8. bit equality with the host twin on the maps of the residual contract: every dtype combination, with and without init, strided
      tile views inside sentinel-filled buffers, a 1 x 1 and a 1 x 53 output;

@@ -1,4 +1,4 @@
-"""The fisheye and equirectangular map models on the device (coords_build_kernel, coords_build_dev_kernel, coords_build_bwd_partial_kernel
+"""The fisheye and equirectangular map models on the device (entry_kernel<BuildOp>, entry_kernel<BuildDevOp>, coords_build_bwd_partial_kernel
 of csrc/lerf_coords.hip instantiated for the model codes 16 and 17, and coords_math_kernel) behind ops.coords_build / coords_build_params
 / coords_build_bwd / coords_math and coords.fisheye_undistort_rectify[_torch] / equirect_view[_torch].  The bounds are the ones
 tests/test_coords_lens_cpu.py settles on the host twins:
