@@ -590,7 +590,8 @@ int lerf_imdn_bwd_f32(const float* weights, int nf, int in_nc, int out_nc, const
  * src() is the image pad rule `pad_mode` (LERF_PAD_*; a tap in a constant pad contributes w * 0), left[j] the first source
  * index of output j in unpadded coordinates (get_field_of_view :145-154, may be negative), w the weights normalised per output
  * (get_weights :208-218); both tables are built by the caller (O(n_out * taps)) and live on the device.  taps is not bounded
- * by LERF_MAX_SUPPORT.  Products and sums are rounded separately and added in tap order, in the accumulator type.
+ * by LERF_MAX_SUPPORT.  left needs no particular order: it may decrease, repeat or jump, and every tap still follows the
+ * pad rule.  Products and sums are rounded separately and added in tap order, in the accumulator type.
  * taps == 0 selects the CSR form, used for the adjoint: row j sums w[e] * in[o][idx[e]][i] over e in
  * [row_ptr[j], row_ptr[j + 1]), every idx in [0, n_in); build it with lerf_rr_adjoint_csr and run it with n_in / n_out
  * exchanged: it then maps the output gradient [outer][n_out][inner] to the input gradient [outer][n_in][inner], without

@@ -116,7 +116,7 @@ rr_narrow_kernel(const TI* __restrict__ in, TO* __restrict__ out, const TA* __re
     bool lds = false;
     if (!CSR) {
         lo = ax.left[j0];
-        const int64_t sp = (int64_t)ax.left[j1] + ax.taps - lo;       // left[] is non-decreasing (a monotone grid)
+        const int64_t sp = (int64_t)ax.left[j1] + ax.taps - lo;       // exact for a monotone grid; any other order: taps outside it read global
         lds = sp > 0 && sp * inner <= kWin;
         span = lds ? (int)sp : 0;
     }
