@@ -781,6 +781,43 @@ int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, in
                             void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
                             int max_iter, double tol);
 
+/* Rasterising inverse with a depth test, for maps that fold or tear: entry (i, j) of out [oH][oW][2] is the position
+ * u with T(u) = (i0 + i, j0 + j), T the PIECEWISE-LINEAR interpolant of the map f [fH][fW][2] (fH, fW >= 2) over two triangles a
+ * cell -- cell (i, j) gives triangle t = 2 (i (fW - 1) + j) with vertices A = (i, j), B = (i, j + 1), C = (i + 1, j) and triangle
+ * t + 1 with A = (i + 1, j + 1), B = (i + 1, j), C = (i, j + 1) -- not lerf_coords_invert's bilinear patch; lerf_coords_invert with
+ * init = out polishes to that one.  Every triangle is rasterised into the tile; where several cover a pixel the smallest key
+ * (sortable(z) << 32) | t wins: z is the triangle's depth there (depth [fH][fW] float32 dense at the vertices, interpolated in
+ * float64 and rounded once; NULL: z = 0 everywhere), sortable() the order-preserving map of float32 bits to uint32 (a NaN z sorts
+ * last), so the NEAREST surface wins and ties go to the lowest triangle.  A pixel no triangle covers gets (NaN, NaN), which
+ * lerf_remap treats as "no source".
+ * A triangle is skipped -- it contributes nothing and forms no address -- when one of its six coordinates is not finite or one of
+ * its three depths is NaN; when area2 = (B - A) x (C - A) is 0 or not finite; when orient = +1 and area2 < 0 or orient = -1 and
+ * area2 > 0 (back-face culling: +1 keeps the identity's orientation, 0 keeps both); or when its box of integer pixels, ceil(min)
+ * .. floor(max) per axis BEFORE the clip to the tile, holds more than max_span (1..64) pixels on either axis (the tear rule: a
+ * cell stretched across a disocclusion does not fill it).  The box is clipped onto the tile in floating point before any
+ * conversion to int: no value of f forms an address or overflows an int.  The inside test is closed and watertight: each edge
+ * function is evaluated with its endpoints in ascending index i fW + j and negated for the triangle that runs the other way, so
+ * the two triangles on an edge see one number; a pixel on a shared edge or vertex belongs to every triangle around it and the
+ * key decides.  The statement order: the top of csrc/lerf_coords_models.h.
+ * keys [oH][oW] uint64, 8-byte aligned, caller-owned (the library allocates nothing), contents arbitrary: workspace AND result.
+ * On return entry (i, j) holds the winning key -- low 32 bits the triangle, high 32 sortable(z) -- or all ones for a hole.  Three
+ * launches on the stream (fill keys; one thread per cell of f, one 64-bit integer atomic min per covered pixel; one thread per
+ * entry resolves its key and is the entry's one writer), no sync.  A minimum over integers does not depend on the order: out and
+ * keys are bit-equal from run to run and to the host twin, a row-major loop over the cells.  f and out obey the strided map
+ * contract with their own dtypes; a tile of a larger inverse written in place (out = the tile's first entry, the whole map's row
+ * stride, its origin; keys dense for the tile) equals those entries of the whole.
+ * Refused in addition to the family's list: fH or fW < 2, 2 (fH - 1) (fW - 1) >= 2^32 or more than 262140 rows of cells,
+ * max_span outside 1..64, orient outside -1..1, a null or misaligned keys, a misaligned depth, a negative i0 / j0, out's or keys'
+ * bytes intersecting f's, depth's or each other.  A refused call writes nothing. */
+int lerf_coords_invert_raster(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                              const float* depth,
+                              void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                              int max_span, int orient, uint64_t* keys, void* stream);
+int lerf_coords_invert_raster_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                   const float* depth,
+                                   void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                                   int max_span, int orient, uint64_t* keys);
+
 /* Adjoints of lerf_coords_compose and lerf_coords_invert (the rounding order of every statement: the top of
  * csrc/lerf_coords_models.h).  a, b, f, g obey the strided map contract, LERF_F32 / LERF_F64 in any mix, promoted exactly on
  * load; aH, aW, fH, fW >= 2, so the four corners of a cell are inside the map.  grad_out [oH][oW][2], grad_a [aH][aW][2], grad_b

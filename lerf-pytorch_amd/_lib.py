@@ -56,7 +56,7 @@ EXPORTS = [
     "lerf_rr_axis", "lerf_rr_adjoint_csr", "lerf_patch_batch_u8",
     "lerf_coords_build", "lerf_coords_build_host", "lerf_coords_mesh", "lerf_coords_mesh_host", "lerf_coords_mesh_bwd_workspace_bytes",
     "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host", "lerf_coords_invert", "lerf_coords_invert_host",
-    "lerf_coords_compose_bwd", "lerf_coords_compose_bwd_host", "lerf_coords_invert_bwd", "lerf_coords_invert_bwd_host",
+    "lerf_coords_invert_raster", "lerf_coords_invert_raster_host", "lerf_coords_compose_bwd", "lerf_coords_compose_bwd_host", "lerf_coords_invert_bwd", "lerf_coords_invert_bwd_host",
     "lerf_coords_build_dev", "lerf_coords_build_bwd_workspace_bytes", "lerf_coords_build_bwd", "lerf_coords_build_bwd_host", "lerf_coords_math", "lerf_coords_math_host",
     "lerf_ubench_lds_gather",
 ]
@@ -307,6 +307,9 @@ def lib():
     _invert = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                C.c_int, C.c_int, C.c_int, C.c_double]
     L.lerf_coords_invert.argtypes, L.lerf_coords_invert_host.argtypes = _invert + [C.c_void_p], _invert
+    _raster = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+               C.c_int, C.c_int, C.c_void_p]
+    L.lerf_coords_invert_raster.argtypes, L.lerf_coords_invert_raster_host.argtypes = _raster + [C.c_void_p], _raster
     _compose_bwd = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     _invert_bwd = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.lerf_coords_compose_bwd.argtypes, L.lerf_coords_compose_bwd_host.argtypes = _compose_bwd + [C.c_void_p], _compose_bwd
@@ -456,6 +459,14 @@ class _Operands:
             raise ValueError("%s must be a contiguous float64 %s beside the maps" % (what, list(shape)))
         return g
 
+    def dense(self, a, shape, dtype, device, what):
+        """a contiguous buffer of `dtype` and `shape` beside the maps (None: a new one)"""
+        if a is None:
+            return self.new(shape, dtype, device)
+        if not self.is_array(a) or a.dtype != dtype or tuple(a.shape) != tuple(shape) or not self.is_contiguous(a) or self.device(a) != device:
+            raise ValueError("%s must be a contiguous %s %s beside the maps" % (what, getattr(dtype, "__name__", dtype), list(shape)))
+        return a
+
     def one_device(self, what, names, first, *others):
         for a in others:
             if a is not None and self.device(a) != self.device(first):
@@ -466,7 +477,7 @@ class _Operands:
 
 
 class HostOperands(_Operands):
-    suffix, noun, f32, f64 = "_host", "a numpy array", np.float32, np.float64
+    suffix, noun, f32, f64, key = "_host", "a numpy array", np.float32, np.float64, np.uint64
     is_array = staticmethod(lambda a: isinstance(a, np.ndarray))
     strides = staticmethod(lambda a: tuple(s // a.itemsize if s % a.itemsize == 0 else None for s in a.strides))
     is_contiguous = staticmethod(lambda a: a.flags.c_contiguous)
@@ -491,6 +502,7 @@ class DeviceOperands(_Operands):
             torch = require_gpu()
             cls._one = super().__new__(cls)
             cls._one.torch, cls._one.f32, cls._one.f64 = torch, torch.float32, torch.float64
+            cls._one.key = torch.int64                 # the 64 bits of a raster key (numpy's side holds them as uint64)
         return cls._one
 
     strides = staticmethod(lambda t: t.stride())
@@ -548,7 +560,7 @@ def mesh_interp_code(interp):
 _HOST = HostOperands()
 
 
-# The seven operations that exist on both sides, over X = HostOperands() or DeviceOperands(): ops.coords_* and coords_*_host below
+# The eight operations that exist on both sides, over X = HostOperands() or DeviceOperands(): ops.coords_* and coords_*_host below
 # bind them and carry the documentation.
 def coords_build_on(X, model, params, out_hw, dtype, out, origin, device=None):
     what = "lerf_coords_build" + X.suffix
@@ -595,6 +607,18 @@ def coords_invert_on(X, f, out_hw, init, dtype, out, origin, max_iter, tol):
     X.call(what, a, *X.operand(a, sa), a.shape[0], a.shape[1], X.ptr(b), LERF_F64 if b is None else X.code(b), sb, *X.operand(out, so),
            out.shape[0], out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol))
     return out
+
+
+def coords_invert_raster_on(X, f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys):
+    what = "lerf_coords_invert_raster" + X.suffix
+    a, sa = X.map(f, "f")
+    out, so = X.out(out, out_hw, dtype, a.dtype, X.device(a), what)
+    d = None if depth is None else X.dense(depth, a.shape[:2], X.f32, X.device(a), what + ": depth")
+    k = X.dense(keys, out.shape[:2], X.key, X.device(a), what + ": keys")
+    X.one_device(what, ("f", "out"), a, out)
+    X.call(what, a, *X.operand(a, sa), a.shape[0], a.shape[1], X.ptr(d), *X.operand(out, so), out.shape[0], out.shape[1], int(origin[0]),
+           int(origin[1]), int(max_span), int(orient), X.ptr(k))
+    return (out, k) if return_keys else out
 
 
 def _coords_bwd_operands(X, what, first, second, names, grad_out):
@@ -662,6 +686,15 @@ def coords_invert_host(f, out_hw, init=None, dtype=np.float64, out=None, origin=
     """lerf_coords_invert_host: G[i, j] = the u with f(u) = origin + (i, j), f read bilinearly, by Newton's method from init[i, j]
     (None: the affine guess from three corners of f); NaN where f does not reach.  Host arrays under the strided map contract."""
     return coords_invert_on(_HOST, f, out_hw, init, dtype, out, origin, max_iter, tol)
+
+
+def coords_invert_raster_host(f, out_hw, depth=None, dtype=np.float64, out=None, origin=(0, 0), max_span=16, orient=0, keys=None,
+                              return_keys=False):
+    """lerf_coords_invert_raster_host: the rasterising inverse of f [fH, fW, 2] into the tile out_hw at `origin` by the row-major host
+    loop over the kernel's own per-triangle arithmetic (bit-equal to ops.coords_invert_raster in G and in keys).  depth: float32
+    contiguous [fH, fW] or None; keys: a contiguous uint64 [oH, oW] workspace (None: a new one) -> G, or (G, keys) with
+    return_keys=True: the winning keys, low 32 bits the triangle, all ones for a hole."""
+    return coords_invert_raster_on(_HOST, f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys)
 
 
 def coords_compose_bwd_host(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):

@@ -10,7 +10,10 @@ With device=<a torch device> the builders write the map ON the device with the k
 entry, no host array, no upload): from_homography, radial, undistort_rectify, fisheye_undistort_rectify, equirect_view,
 from_mesh; from_mesh_torch keeps a control mesh
 in the autograd graph through the mesh upsample's adjoint, compose chains two maps into one, and invert / invert_flow solve a
-map for its inverse (distort <-> undistort, forward flow -> backward map).  The kernels' arithmetic is
+map for its inverse (distort <-> undistort, forward flow -> backward map).  invert_raster / invert_flow_raster invert a map that
+FOLDS or TEARS (a forward flow with occlusions, a folded mesh), where Newton's method has no basin to start in: every triangle of
+the map is drawn into the frame with a depth test (lerf_coords_invert_raster), the nearest surface wins, a cell
+stretched across a disocclusion fills nothing; its result is also the start invert lacks on such a map.  The kernels' arithmetic is
 float64 with + - * / only, bit-equal to its host twin (csrc/lerf_coords_models.h); the square root and arc tangents of the
 fisheye and equirectangular models are written in those operations too (_lib.coords_math_host), not taken from a math library.
 
@@ -22,7 +25,7 @@ device, and a loss reaches the operands through lerf_coords_build_bwd (DESIGN 4.
 refinement, a spatial-transformer head.  An entry whose point is not finite (a homography's Wh == 0) contributes nothing to the
 gradient -- unlike autograd of the same formulas, which would return NaN.
 
-compose, invert and invert_flow refuse operands that require grad.  Their opt-in twins compose_torch, invert_torch and
+compose, invert, invert_flow, invert_raster and invert_flow_raster refuse operands that require grad.  The first three have opt-in twins: compose_torch, invert_torch and
 invert_flow_torch (device tensors only) run the same forward kernels and keep the maps in the autograd graph through the HIP
 adjoints lerf_coords_compose_bwd and lerf_coords_invert_bwd, so a loss reaches a flow or a control mesh through
 chained maps: coarse-to-fine refinement (compose_torch(upsampled, residual)), scaling and squaring (compose_torch(phi, phi)),
@@ -429,6 +432,88 @@ def invert_flow(flow, init=None, max_iter=16, tol=1e-9):
     f = f if f.dtype in (np.float32, np.float64) else f.astype(np.float64)
     ident = from_flow(np.zeros((H, W, 2))).astype(f.dtype)
     return invert(ident + f, (H, W), init=init, max_iter=max_iter, tol=tol) - ident
+
+
+def _no_autograd(what, operands):
+    if any(getattr(t, "requires_grad", False) for t in operands):
+        import torch
+        if torch.is_grad_enabled():
+            raise ValueError("%s has no autograd: detach() the operands (or call it under torch.no_grad())" % what)
+
+
+def invert_raster(map, in_hw, depth=None, max_span=16, orient=0, dtype=None):
+    """The inverse of a map that FOLDS or TEARS, by rasterisation with a depth test: G [H, W, 2] with in_hw = (H, W) the size of the
+    frame `map` points INTO; G[i, j] is the position u at which the map, read as its piecewise-LINEAR interpolant over two triangles
+    a cell, holds (i, j).  Every triangle of the map is drawn into the frame (lerf_coords_invert_raster: one thread per cell, one
+    64-bit integer atomic min per covered pixel), so nothing depends on a starting guess or on a Jacobian that never vanishes -- what
+    invert needs, and why it returns NaN on such maps.
+
+    depth: [fH, fW] (read as float32), the depth of every vertex of the map: where several surfaces land on one pixel the NEAREST
+    (smallest depth) wins -- the foreground of an optical flow with occlusions; None: the lowest-numbered triangle.  max_span
+    (1..64): a triangle whose box of pixels is wider than this on either axis is a TEAR -- a cell stretched across a disocclusion --
+    and fills nothing: the disoccluded area stays (NaN, NaN), which the remap treats as "no source" (mask false).  orient: +1 keeps
+    only triangles with the identity's orientation, -1 only the reversed ones, 0 (default) both.
+
+    The result differs from invert's by the difference of the two interpolants (hundredths of a pixel on a smooth map that stretches
+    by 1.7), and it is the start Newton's method lacks on a folded map:
+
+        invert(map, in_hw, init=invert_raster(map, in_hw))          a bilinear-exact inverse of a folded map
+        remap(img, invert_flow_raster(flow, depth) + identity)      carries a frame forward along its flow
+
+    numpy in -> numpy out (the kernel's host twin, bit-equal); device tensors in -> a device tensor; mixed map / depth is refused.
+    dtype: default the map's.  A batch [B, fH, fW, 2] (depth [B, fH, fW] or None) gives [B, H, W, 2]: one call per map into the
+    slices of one output.  Bit-equal from run to run.  No autograd: an operand that requires grad (with grad mode on) is refused."""
+    ops_ = [t for t in (map, depth) if t is not None]
+    dev = [bool(getattr(t, "is_cuda", False)) for t in ops_]
+    if any(d != dev[0] for d in dev):
+        raise ValueError("invert_raster: map and depth on the host or both on one device, not mixed")
+    _no_autograd("invert_raster", ops_)
+    H, W = int(in_hw[0]), int(in_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("in_hw must be positive")
+    nd = getattr(map, "ndim", None)
+    if nd not in (3, 4) or (depth is not None and (getattr(depth, "ndim", None) != nd - 1 or tuple(depth.shape) != tuple(map.shape[:-1]))):
+        raise ValueError("invert_raster: map is [fH, fW, 2] or [B, fH, fW, 2], depth (if given) [fH, fW] or [B, fH, fW] alike")
+    if dev[0]:
+        import torch
+        from . import ops
+        a, d = map.detach(), None if depth is None else depth.detach().to(torch.float32).contiguous()
+        dt = a.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
+        one, new = ops.coords_invert_raster, lambda shape: torch.empty(shape, dtype=dt, device=a.device)
+    else:
+        from . import _lib
+        a, d = (None if t is None else np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (map, depth))
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        d = None if d is None else np.ascontiguousarray(d, dtype=np.float32)
+        dt = a.dtype if dtype is None else _np_dtype(dtype)
+        one, new = _lib.coords_invert_raster_host, lambda shape: np.empty(shape, dtype=dt)
+    if nd == 3:
+        return one(a, (H, W), depth=d, dtype=dt, max_span=max_span, orient=orient)
+    out = new((a.shape[0], H, W, 2))
+    keys = None
+    for n in range(a.shape[0]):                            # one workspace serves every map of the batch
+        _, keys = one(a[n], (H, W), depth=None if d is None else d[n], out=out[n], max_span=max_span, orient=orient, keys=keys, return_keys=True)
+    return out
+
+
+def invert_flow_raster(flow, depth=None, max_span=16, orient=0):
+    """The backward flow of a forward flow WITH OCCLUSIONS: flow [H, W, 2] (or a batch [B, H, W, 2]) = (d_row, d_col) of every pixel,
+    numpy or a device tensor -> b = invert_raster(identity + flow, (H, W), depth, max_span, orient) - identity, in the flow's dtype
+    and place.  Where a foreground moves over a background the surface with the smaller depth wins; the area it uncovers stays
+    NaN (no stretched cell fills it: max_span).  remap(img, invert_flow_raster(flow, depth) + identity) carries a frame forward
+    along its flow.  No autograd."""
+    if getattr(flow, "ndim", None) not in (3, 4) or flow.shape[-1] != 2:
+        raise ValueError("flow must be [H, W, 2] or [B, H, W, 2]")
+    H, W = int(flow.shape[-3]), int(flow.shape[-2])
+    _no_autograd("invert_flow_raster", [flow])
+    if getattr(flow, "is_cuda", False):
+        import torch
+        ident = from_flow_torch(torch.zeros((H, W, 2), dtype=flow.dtype, device=flow.device))
+        return invert_raster(ident + flow.detach(), (H, W), depth, max_span, orient) - ident
+    f = np.asarray(flow.detach().numpy() if hasattr(flow, "detach") else flow)
+    f = f if f.dtype in (np.float32, np.float64) else f.astype(np.float64)
+    ident = from_flow(np.zeros((H, W, 2))).astype(f.dtype)
+    return invert_raster(ident + f, (H, W), depth, max_span, orient) - ident
 
 
 # ---------------------------------------------------------------------------------------------- differentiable twins

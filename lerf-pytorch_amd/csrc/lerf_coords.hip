@@ -12,8 +12,13 @@
 // and every operation is ONE function template over the runner (coords::build, mesh, compose, ...): the argument checks, the dtype and
 // model dispatch, run(Op{...}, oH, oW[, sets]).  The C entry points lerf_coords_X / lerf_coords_X_host are that template with one
 // runner or the other, so the device and the host twin cannot drift apart: they agree bit for bit by construction (the two
-// scatters excepted, below).  Add2 is the one scatter: two float64 atomicAdd where compiled for the device, a plain add on the host.
+// float scatters excepted, below).  Add2 is the one float scatter: two float64 atomicAdd where compiled for the device, a plain add on the host.
 // MapReader is the one strided-map reader handed to the *_point functions; a dense float64 gradient [h][w][2] is a map of row stride 2w.
+//
+// The rasterising inverse (lerf_coords_invert_raster) is three passes: KeyFillOp and ResolveOp are per-entry functors under the two
+// runners above; RasterOp is a SCATTER operation, one call per cell of F, under ScatterOnDevice{stream} (cell_kernel<OP>, the same
+// block and grid, a 64-bit integer atomic min) / ScatterOnHost{} (the row-major loop, a plain min).  An integer minimum does not
+// depend on the order of its operands, so this scatter IS bit-equal between the two and from run to run.
 //
 // Kernels of their own shape (unchanged by the above):
 //   coords_mesh_bwd_{rows,cols}_kernel      the adjoint of the mesh upsample, map = Wr . ctrl . Wc^T  =>  grad_ctrl = Wr^T . grad_map . Wc,
@@ -47,7 +52,11 @@
 // B / G, grad_out and grad_b at entry (i, j) only, and read A / F and add into grad_a / grad_f at the cell compose_axis picks (aH, aW,
 // fH, fW >= 2 are checked on the host, so i0 + 1 <= n - 1), whatever the maps hold.  The kernels that read device parameters index
 // params and grad_params inside [n_sets][n_params], out and grad_map at (set, i, j) with set < n_sets, i < oH, j < oW, the workspace
-// inside [n_sets][n_params][blocks]; no parameter value forms an address.  coords_math_kernel reads x (and y, for atan2 only) and writes
+// inside [n_sets][n_params][blocks]; no parameter value forms an address.  The rasterising inverse: cell_kernel guards (i, j) against
+// the cells [fH - 1][fW - 1] and reads F and depth at the cell's four corners; a triangle's pixel box is clipped onto the tile in
+// floating point before its conversion to int (raster_axis), so keys is indexed inside [oH][oW] whatever F holds; the resolve reads
+// keys at entry (i, j) and F at the three vertices of the triangle the key names -- a key this call's raster pass wrote, t < 2 (fH - 1)
+// (fW - 1) -- and writes entry (i, j) of out.  coords_math_kernel reads x (and y, for atan2 only) and writes
 // out at element e < n alone; no argument value forms an address.
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
@@ -210,6 +219,44 @@ struct InvertBwdOp {
     }
 };
 
+// The rasterising inverse (raster_cell / raster_resolve of lerf_coords_models.h) in three passes over caller-owned keys [oH][oW]:
+//   KeyFillOp     per entry: the key of an untouched pixel (all ones), one 8-byte store
+//   RasterOp      per CELL of F, under the scatter runners below: four 16-byte (float64) loads of the cell's corners -- a wave reads one
+//                 row of 65 neighbouring vertices twice, coalesced -- four 4-byte loads of depth when given, then for each of the two
+//                 triangles a loop over its clipped box (at most max_span x max_span <= 64 x 64 pixels) and ONE 64-bit min per covered
+//                 pixel, handed to the runner's MINKEY.  The loop is data-dependent: a wave runs as long as its largest box.
+//   ResolveOp     per entry: one 8-byte load of the key, three gathers of F at the winning triangle, one store; a single writer
+template <typename TF>
+struct RasterOp {
+    MapReader<TF> F;
+    int fW;
+    const float* depth;
+    int orient, max_span, i0, j0, oH, oW;
+    template <typename MINKEY>
+    LERF_HD void operator()(int i, int j, MINKEY minkey) const {
+        raster_cell(i, j, fW, F, depth, orient, max_span, i0, j0, oH, oW, minkey);
+    }
+};
+
+struct KeyFillOp {
+    uint64_t* keys;
+    int oW;
+    LERF_HD void operator()(int i, int j, int) const { keys[(int64_t)i * oW + j] = kNoKey; }
+};
+
+template <typename TF, typename TO>
+struct ResolveOp {
+    MapReader<TF> F;
+    int fW;
+    const uint64_t* keys;
+    TO* out;
+    int64_t stride;
+    int i0, j0, oW;
+    LERF_HD void operator()(int i, int j, int) const {
+        store_entry(out, stride, i, j, raster_resolve(keys[(int64_t)i * oW + j], fW, (double)(i0 + i), (double)(j0 + j), F));
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ the two runners
 // 8 waves per SIMD (64 VGPRs) hold for every operation; stated, so that the bicubic mesh over a float64 control mesh stays at 64, not 66
 template <typename OP>
@@ -236,6 +283,55 @@ struct OnHost {
         for (int s = 0; s < sets; ++s)
             for (int i = 0; i < oH; ++i)
                 for (int j = 0; j < oW; ++j) op(i, j, s);
+        return LERF_OK;
+    }
+};
+
+// The two runners of a SCATTER operation op(i, j, minkey) -- one call per cell (i, j) of [cH][cW], which hands (index, key) pairs to
+// minkey: keys[index] = min(keys[index], key).  The runner owns the combiner, the operation owns the arithmetic:
+//   ScatterOnDevice{stream}   cell_kernel<OP>: the block and grid of entry_kernel, one thread per cell; KeyMinDevice = one 64-bit
+//                             unsigned atomic min into global memory (a single hardware instruction on gfx950, no return value).  A
+//                             plain load first: keys only decrease, so a key that is already smaller stays smaller and the atomic
+//                             is skipped; a stale load costs an atomic that changes nothing.
+//   ScatterOnHost{}           the row-major loop over cells, KeyMinHost = a plain min
+// A minimum over integers does not depend on the order of its operands: the two agree bit for bit, as do two runs.
+struct KeyMinDevice {
+    uint64_t* keys;
+    __device__ void operator()(int64_t e, uint64_t key) const {
+        unsigned long long* p = reinterpret_cast<unsigned long long*>(keys + e);
+        if (__atomic_load_n(p, __ATOMIC_RELAXED) < key) return;
+        atomicMin(p, (unsigned long long)key);
+    }
+};
+
+struct KeyMinHost {
+    uint64_t* keys;
+    void operator()(int64_t e, uint64_t key) const { keys[e] = key < keys[e] ? key : keys[e]; }
+};
+
+template <typename OP>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS) cell_kernel(const OP op, int cH, int cW, uint64_t* keys) {
+    const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
+    if (i >= cH || j >= cW) return;
+    op(i, j, KeyMinDevice{keys});
+}
+
+struct ScatterOnDevice {
+    hipStream_t stream;
+    template <typename OP>
+    int operator()(const OP& op, int cH, int cW, uint64_t* keys) const {
+        clear_stale_error();
+        const dim3 grid((cW + CB_COLS - 1) / CB_COLS, (cH + CB_ROWS - 1) / CB_ROWS);
+        hipLaunchKernelGGL(cell_kernel<OP>, grid, dim3(CB_COLS, CB_ROWS), 0, stream, op, cH, cW, keys);
+        return launch_status();
+    }
+};
+
+struct ScatterOnHost {
+    template <typename OP>
+    int operator()(const OP& op, int cH, int cW, uint64_t* keys) const {
+        for (int i = 0; i < cH; ++i)
+            for (int j = 0; j < cW; ++j) op(i, j, KeyMinHost{keys});
         return LERF_OK;
     }
 };
@@ -419,6 +515,31 @@ inline int invert_args(const void* f, int f_dtype, int64_t f_stride, int fH, int
     return LERF_OK;
 }
 
+// plain byte ranges [p, p + pn) and [q, q + qn)
+inline bool bytes_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qn && b < a + pn;
+}
+
+// the bytes of a map operand, first entry to one past the last
+inline size_t map_bytes(int dt, int64_t stride, int h, int w) {
+    return (size_t)(((int64_t)(h - 1) * stride + 2 * (int64_t)w) * (int64_t)(entry_bytes(dt) / 2));
+}
+
+inline int invert_raster_args(const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const float* depth, const void* out, int out_dtype,
+                              int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, const uint64_t* keys) {
+    if (!map_ok(f, f_dtype, f_stride, fH, fW) || fH < 2 || fW < 2 || !map_ok(out, out_dtype, o_stride, oH, oW) || !tile_ok(oH, oW, i0, j0))
+        return LERF_EINVAL;
+    if (2 * (int64_t)(fH - 1) * (int64_t)(fW - 1) >= ((int64_t)1 << 32) || (fH - 1 + CB_ROWS - 1) / CB_ROWS > 65535) return LERF_EINVAL;
+    if (max_span < 1 || max_span > kMaxSpan || orient < -1 || orient > 1) return LERF_EINVAL;
+    if (!keys || (size_t)(uintptr_t)keys % 8 != 0 || (depth && (size_t)(uintptr_t)depth % 4 != 0)) return LERF_EINVAL;
+    const size_t fb = map_bytes(f_dtype, f_stride, fH, fW), ob = map_bytes(out_dtype, o_stride, oH, oW);
+    const size_t kb = (size_t)oH * oW * sizeof(uint64_t), db = (size_t)fH * fW * sizeof(float);
+    if (bytes_overlap(out, ob, f, fb) || bytes_overlap(keys, kb, f, fb) || bytes_overlap(out, ob, keys, kb)) return LERF_EINVAL;
+    if (depth && (bytes_overlap(out, ob, depth, db) || bytes_overlap(keys, kb, depth, db))) return LERF_EINVAL;
+    return LERF_OK;
+}
+
 // a dense float64 gradient [h][w][2]
 inline bool dense_ok(const void* p) { return p && (size_t)(uintptr_t)p % 16 == 0; }
 inline bool dense_overlaps_map(const void* d, int h, int w, const void* q, int qdt, int64_t qs, int qh, int qw) {
@@ -454,12 +575,6 @@ inline int invert_bwd_args(const void* f, int f_dtype, int64_t f_stride, int fH,
         dense_overlap(grad_f, fH, fW, grad_out, oH, oW))
         return LERF_EINVAL;
     return LERF_OK;
-}
-
-// plain byte ranges [p, p + pn) and [q, q + qn)
-inline bool bytes_overlap(const void* p, size_t pn, const void* q, size_t qn) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
 }
 
 // device parameters cannot be inspected here: their count, the pointers and the layout of the n_sets maps are what is checked
@@ -562,6 +677,21 @@ int invert(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW
                    oH, oW))));
 }
 
+// fill, raster, resolve: three launches in stream order (the host: three loops), no sync, no allocation
+template <typename RUN, typename SCATTER>
+int invert_raster(RUN run, SCATTER scatter, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const float* depth, void* out,
+                  int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys) {
+    int rc = invert_raster_args(f, f_dtype, f_stride, fH, fW, depth, out, out_dtype, o_stride, oH, oW, i0, j0, max_span, orient, keys);
+    if (rc != LERF_OK) return rc;
+    rc = run(KeyFillOp{keys, oW}, oH, oW);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(f_dtype, TF,
+        rc = scatter(RasterOp<TF>{{(const TF*)f, f_stride}, fW, depth, orient, max_span, i0, j0, oH, oW}, fH - 1, fW - 1, keys));
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(out_dtype, TO,
+        return run(ResolveOp<TF, TO>{{(const TF*)f, f_stride}, fW, keys, (TO*)out, o_stride, i0, j0, oW}, oH, oW)));
+}
+
 template <typename RUN>
 int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
                 const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
@@ -636,6 +766,19 @@ int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, in
                             int max_iter, double tol) {
     return invert(OnHost{}, f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW, i0, j0,
                   max_iter, tol);
+}
+
+int lerf_coords_invert_raster(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out, int out_dtype,
+                              int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, void* stream) {
+    return invert_raster(OnDevice{(hipStream_t)stream}, ScatterOnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, depth, out,
+                         out_dtype, out_row_stride, oH, oW, i0, j0, max_span, orient, keys);
+}
+
+int lerf_coords_invert_raster_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out,
+                                   int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient,
+                                   uint64_t* keys) {
+    return invert_raster(OnHost{}, ScatterOnHost{}, f, f_dtype, f_row_stride, fH, fW, depth, out, out_dtype, out_row_stride, oH, oW, i0, j0,
+                         max_span, orient, keys);
 }
 
 int lerf_coords_compose_bwd(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,

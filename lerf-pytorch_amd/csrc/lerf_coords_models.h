@@ -98,6 +98,33 @@
 //                 u.r = r - (e.r*Jc.c - Jc.r*e.c) / det,  u.c = c - (Jr.r*e.c - Jr.c*e.r) / det
 //               no iteration met tol: (NaN, NaN) -- a target F does not reach.  No value of F, init or q forms an address
 //               outside F: u goes through compose_axis (clipped in floating point before the conversion to int, fH, fW >= 2).
+//   invert_raster   G[q] = the u with T(u) = q, T the PIECEWISE-LINEAR interpolant of F [fH][fW][2] (fH, fW >= 2) over two triangles a
+//               cell (not invert's bilinear patch), by rasterising every triangle into the tile and keeping, per pixel, the smallest
+//               64-bit key; q = ((double)(i0 + i), (double)(j0 + j)).  Cell (i, j), 0 <= i < fH - 1, 0 <= j < fW - 1, P00 = F[i][j],
+//               P01 = F[i][j + 1], P10 = F[i + 1][j], P11 = F[i + 1][j + 1]:
+//                 triangle t = 2*(i*(fW - 1) + j)   (even):  A = P00, B = P01, C = P10
+//                 triangle t + 1                    (odd):   A = P11, B = P10, C = P01
+//               edge(P, Q, q) = (Q.c - P.c)*(q.r - P.r) - (Q.r - P.r)*(q.c - P.c)      ((Q - P) x (q - P); the identity's triangles are > 0)
+//               set-up of one triangle (raster_setup); a triangle that fails a test is SKIPPED: it contributes nothing, forms no address:
+//                 the six coordinates finite (v - v == 0); with depth, no NaN among zA, zB, zC
+//                 area2 = edge(A, B, C);  area2 != 0 and finite;  not (orient > 0 and area2 < 0), not (orient < 0 and area2 > 0)
+//                 per axis (rows: v = A.r, B.r, C.r):  lo = ceil(min v), hi = floor(max v)   (min / max by selects, left to right)
+//                 (hi - lo) + 1 > (double)max_span on either axis: skipped   (the tear rule, BEFORE the clip; in float64)
+//                 lo = max(lo, (double)first), hi = min(hi, (double)last), first / last the tile's first and last row (column);
+//                 lo > hi on either axis: skipped;  only now the conversion to int
+//               per pixel q of the box, rows outer, columns inner (tri_edges: each edge with its endpoints in ascending index i*fW + j,
+//               negated where the triangle A -> B -> C -> A runs the other way, so the two triangles on an edge see ONE number):
+//                 even:  e_c = edge(A, B, q),   e_a = edge(B, C, q),   e_b = -edge(A, C, q)
+//                 odd:   e_c = -edge(B, A, q),  e_a = -edge(C, B, q),  e_b = edge(C, A, q)
+//                 inside (closed):  area2 > 0: e_a >= 0, e_b >= 0, e_c >= 0;  area2 < 0: all three <= 0
+//                 l_b = e_b / area2,  l_c = e_c / area2                                                  (tri_value)
+//                 even:  u = ((double)i + l_c, (double)j + l_b);   odd:  u = ((double)(i + 1) - l_c, (double)(j + 1) - l_b)
+//                 z = (float)(zA + (l_b*(zB - zA) + l_c*(zC - zA)))   in float64 from the float32 depths, rounded once; a NaN z is the
+//                 canonical quiet NaN 0x7FC00000;  without depth z = +0.0f and l_b, l_c are not needed                (tri_depth)
+//                 key = (sortable(z) << 32) | t,  sortable(b) = ~b if b has its sign bit, else b | 0x80000000, b the bits of z
+//                 keys[q] = min(keys[q], key)     (the device: one 64-bit atomic min; an integer min does not depend on the order)
+//               resolve, per entry: keys[q] all ones (untouched): (NaN, NaN);  else t = the low 32 bits, cell = t >> 1, i = cell / (fW - 1),
+//               j = cell % (fW - 1), the triangle's three vertices are read again, area2 = edge(A, B, C), tri_edges, tri_value: u.
 //   compose backward (compose_bwd_point; aH, aW >= 2)   one entry with inner point (row, col) and upstream g = (g.r, g.c):
 //                 a NaN in row or col: nothing is read, nothing is scattered, the inner gradient is (0, 0) whatever g holds (a select)
 //                 R = compose_axis(row, aH), Cx = compose_axis(col, aW), wr = {R.w0, R.w1}, wc = {Cx.w0, Cx.w1}: the forward's
@@ -674,6 +701,128 @@ LERF_HD inline void invert_bwd_point(double r, double c, Point g, int fH, int fW
     if (!finite_nonzero(det)) return;
     const Point v{-(J.Jc.c * g.r - J.Jr.c * g.c) / det, -(J.Jr.r * g.c - J.Jc.r * g.r) / det};
     scatter_taps(R, Cx, v, add);
+}
+
+// ---- invert_raster: the per-triangle and per-pixel arithmetic of the rasterising inverse (the statement order: the top of this file)
+constexpr uint64_t kNoKey = ~(uint64_t)0;      // an untouched pixel
+constexpr int kMaxSpan = 64;
+
+LERF_HD inline double edge_fn(Point P, Point Q, double q_r, double q_c) {
+#pragma clang fp contract(off)
+    return (Q.c - P.c) * (q_r - P.r) - (Q.r - P.r) * (q_c - P.c);
+}
+
+struct TriEdges {
+    double a, b, c;      // the edge functions opposite A, B, C
+};
+
+LERF_HD inline TriEdges tri_edges(Point A, Point B, Point C, bool odd, double q_r, double q_c) {
+#pragma clang fp contract(off)
+    TriEdges e;
+    e.c = odd ? -edge_fn(B, A, q_r, q_c) : edge_fn(A, B, q_r, q_c);
+    e.a = odd ? -edge_fn(C, B, q_r, q_c) : edge_fn(B, C, q_r, q_c);
+    e.b = odd ? edge_fn(C, A, q_r, q_c) : -edge_fn(A, C, q_r, q_c);
+    return e;
+}
+
+LERF_HD inline bool tri_inside(const TriEdges& e, double area2) {
+    return area2 > 0.0 ? (e.a >= 0.0 && e.b >= 0.0 && e.c >= 0.0) : (e.a <= 0.0 && e.b <= 0.0 && e.c <= 0.0);
+}
+
+// the position in F's index space of the point with edge functions e in triangle `odd` of cell (i, j)
+LERF_HD inline Point tri_value(int i, int j, bool odd, const TriEdges& e, double area2) {
+#pragma clang fp contract(off)
+    const double lb = e.b / area2, lc = e.c / area2;
+    return odd ? Point{(double)(i + 1) - lc, (double)(j + 1) - lb} : Point{(double)i + lc, (double)j + lb};
+}
+
+LERF_HD inline float tri_depth(const TriEdges& e, double area2, float zA, float zB, float zC) {
+#pragma clang fp contract(off)
+    const double lb = e.b / area2, lc = e.c / area2;
+    const float z = (float)((double)zA + (lb * ((double)zB - (double)zA) + lc * ((double)zC - (double)zA)));
+    return z != z ? __builtin_nanf("") : z;
+}
+
+LERF_HD inline uint64_t raster_key(float z, uint32_t t) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, z);
+    const uint32_t s = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((uint64_t)s << 32) | (uint64_t)t;
+}
+
+struct RasterBox {
+    double area2;
+    int r0, r1, c0, c1;      // the pixels of the tile the triangle may cover, inclusive
+};
+
+LERF_HD inline double min3(double a, double b, double c) { const double m = b < a ? b : a; return c < m ? c : m; }
+LERF_HD inline double max3(double a, double b, double c) { const double m = b > a ? b : a; return c > m ? c : m; }
+
+// one axis of the box: false = skipped (torn, or no pixel of the tile); the clip precedes the conversion to int
+LERF_HD inline bool raster_axis(double a, double b, double c, int max_span, int first, int n, int* lo_i, int* hi_i) {
+#pragma clang fp contract(off)
+    double lo = ceil(min3(a, b, c)), hi = floor(max3(a, b, c));
+    if ((hi - lo) + 1.0 > (double)max_span) return false;
+    const double f = (double)first, l = (double)first + (double)(n - 1);
+    lo = lo < f ? f : lo;
+    hi = hi > l ? l : hi;
+    if (lo > hi) return false;
+    *lo_i = (int)lo;
+    *hi_i = (int)hi;
+    return true;
+}
+
+// false: the triangle is skipped.  has_depth: zA, zB, zC are tested for NaN.
+LERF_HD inline bool raster_setup(Point A, Point B, Point C, bool has_depth, float zA, float zB, float zC, int orient, int max_span, int i0, int j0,
+                                 int oH, int oW, RasterBox* box) {
+#pragma clang fp contract(off)
+    if (!(finite_value(A.r) && finite_value(A.c) && finite_value(B.r) && finite_value(B.c) && finite_value(C.r) && finite_value(C.c))) return false;
+    if (has_depth && (zA != zA || zB != zB || zC != zC)) return false;
+    const double area2 = edge_fn(A, B, C.r, C.c);
+    if (!finite_nonzero(area2)) return false;
+    if ((orient > 0 && area2 < 0.0) || (orient < 0 && area2 > 0.0)) return false;
+    box->area2 = area2;
+    return raster_axis(A.r, B.r, C.r, max_span, i0, oH, &box->r0, &box->r1) && raster_axis(A.c, B.c, C.c, max_span, j0, oW, &box->c0, &box->c1);
+}
+
+// Both triangles of cell (i, j) into the tile.  LOAD(row, col) -> Point of F; depth: dense [fH][fW] float32 or null;
+// MINKEY(index, key): keys[index] = min(keys[index], key), index = (row - i0)*oW + (col - j0) inside [oH][oW] by the clipped box.
+template <typename LOAD, typename MINKEY>
+LERF_HD inline void raster_cell(int i, int j, int fW, LOAD load, const float* depth, int orient, int max_span, int i0, int j0, int oH, int oW,
+                                MINKEY minkey) {
+#pragma clang fp contract(off)
+    const Point P[4] = {load(i, j), load(i, j + 1), load(i + 1, j), load(i + 1, j + 1)};
+    float Z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (depth) {
+        const float* d = depth + (int64_t)i * fW + j;
+        Z[0] = d[0]; Z[1] = d[1]; Z[2] = d[fW]; Z[3] = d[fW + 1];
+    }
+    const uint32_t t0 = 2u * ((uint32_t)i * (uint32_t)(fW - 1) + (uint32_t)j);
+    for (int odd = 0; odd < 2; ++odd) {
+        const int a = odd ? 3 : 0, b = odd ? 2 : 1, c = odd ? 1 : 2;
+        const Point A = P[a], B = P[b], C = P[c];
+        RasterBox box;
+        if (!raster_setup(A, B, C, depth != nullptr, Z[a], Z[b], Z[c], orient, max_span, i0, j0, oH, oW, &box)) continue;
+        for (int r = box.r0; r <= box.r1; ++r)
+            for (int q = box.c0; q <= box.c1; ++q) {
+                const TriEdges e = tri_edges(A, B, C, odd != 0, (double)r, (double)q);
+                if (!tri_inside(e, box.area2)) continue;
+                const float z = depth ? tri_depth(e, box.area2, Z[a], Z[b], Z[c]) : 0.0f;
+                minkey((int64_t)(r - i0) * oW + (q - j0), raster_key(z, t0 + (uint32_t)odd));
+            }
+    }
+}
+
+// the entry of the inverse a winning key stands for
+template <typename LOAD>
+LERF_HD inline Point raster_resolve(uint64_t key, int fW, double q_r, double q_c, LOAD load) {
+#pragma clang fp contract(off)
+    if (key == kNoKey) return {__builtin_nan(""), __builtin_nan("")};
+    const uint32_t t = (uint32_t)key, cell = t >> 1;
+    const bool odd = (t & 1u) != 0;
+    const int i = (int)(cell / (uint32_t)(fW - 1)), j = (int)(cell % (uint32_t)(fW - 1));
+    const Point A = odd ? load(i + 1, j + 1) : load(i, j), B = odd ? load(i + 1, j) : load(i, j + 1), C = odd ? load(i, j + 1) : load(i + 1, j);
+    const double area2 = edge_fn(A, B, C.r, C.c);
+    return tri_value(i, j, odd, tri_edges(A, B, C, odd, q_r, q_c), area2);
 }
 
 }  // namespace coords

@@ -2,8 +2,9 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer on its host side and linked with this main, which calls lerf_coords_build_host,
 // lerf_coords_build_bwd_host and lerf_coords_math_host (the fisheye and equirect models, the special arguments of the helpers) and
 // lerf_coords_{mesh,compose,invert,compose_bwd,invert_bwd}_host on exactly-sized heap buffers -- strided tiles with an origin, both
-// dtypes of every operand, a batch of sets, init and the gradient halves null and given, the refusals.  The host twins of the five
-// run the very functors the device runs (OnHost in lerf_coords.hip), so this pass checks the addressing of the shared per-entry code.
+// dtypes of every operand, a batch of sets, init and the gradient halves null and given, the refusals -- and lerf_coords_invert_raster_host
+// on a folded map with NaN, +-inf and 1e300 entries, tiles at a non-zero origin, max_span 1 and 64.  The host twins of the six
+// run the very functors the device runs (OnHost, ScatterOnHost in lerf_coords.hip), so this pass checks the addressing of the shared code.
 // It needs no GPU and is never loaded into another process.  Exit status 0 and "ok" on the last line: no report.
 #include "lerf_hip.h"
 
@@ -117,6 +118,46 @@ static void entry_ops(int oH, int oW) {
             }
 }
 
+// the rasterising inverse: a folded map with NaN, +-inf and 1e300 entries drawn into tiles [oH][oW] at origin (3, 7) of exactly-sized
+// buffers (F, depth, out, keys), every dtype mix, with and without depth, max_span 1 and 64, every orient, then the refusals
+static void raster_ops(int oH, int oW) {
+    const int DT[2] = {LERF_F32, LERF_F64};
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int fH = 9, fW = 70;
+    for (int tf : DT)
+        for (int to : DT) {
+            Map F(tf, fH, fW), out(to, oH, oW), keep(to, oH, oW);
+            for (int i = 0; i < fH; ++i)
+                for (int j = 0; j < fW; ++j) F.set(i, j, 1.3 * i + 0.5 * std::sin(0.7 * j), 1.1 * j + 4.0 * std::sin(j / 2.5) + 0.25 * i);      // folds
+            F.set(2, 5, nan, 3.0); F.set(4, 9, inf, 1.0); F.set(5, 20, 2.0, -inf); F.set(6, 30, 1e300, 1e300); F.set(1, 40, -1e300, 5.0);
+            F.set(0, 0, 1e300, -1e300); F.set(fH - 1, fW - 1, nan, nan);
+            std::vector<float> depth((size_t)fH * fW);
+            for (size_t k = 0; k < depth.size(); ++k) depth[k] = k % 31 == 7 ? (float)nan : k % 37 == 9 ? (float)inf : 2.0f + std::sin(0.3f * (float)k);
+            std::vector<uint64_t> keys((size_t)oH * oW, 5), keys0 = keys;
+            for (const float* d : {(const float*)nullptr, (const float*)depth.data()})
+                for (int span : {1, 4, 64})
+                    for (int orient : {-1, 0, 1}) {
+                        EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, d, out.p(), to, out.stride, oH, oW, 3, 7, span, orient, keys.data()) == LERF_OK);
+                        EXPECT(keys != keys0);
+                    }
+            // a far tile, and one that a 1e300 entry would reach if anything unclipped became an int
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, depth.data(), out.p(), to, out.stride, oH, oW, 0x7fffffff - oH, 0x7fffffff - oW, 64, 0, keys.data()) == LERF_OK);
+            EXPECT(keys[0] == ~(uint64_t)0);
+            keys = keys0;
+            const int64_t s = out.stride;
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, nullptr, keep.p(), to, s, oH, oW, 3, 7, 0, 0, keys.data()) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, nullptr, keep.p(), to, s, oH, oW, 3, 7, 65, 0, keys.data()) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, nullptr, keep.p(), to, s, oH, oW, 3, 7, 16, 2, keys.data()) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, nullptr, keep.p(), to, s, oH, oW, 3, 7, 16, 0, nullptr) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, nullptr, keep.p(), to, s, oH, oW, -1, 7, 16, 0, keys.data()) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, 1, fW, nullptr, keep.p(), to, s, oH, oW, 3, 7, 16, 0, keys.data()) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, nullptr, keep.p(), to, s, oH, oW, 3, 7, 16, 0, (uint64_t*)((char*)keys.data() + 4)) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, nullptr, keep.p(), to, s, oH, oW, 3, 7, 16, 0, (uint64_t*)F.p()) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_raster_host(F.p(), tf, F.stride, fH, fW, (const float*)keep.p(), keep.p(), to, s, oH, oW, 3, 7, 16, 0, keys.data()) == LERF_EINVAL);
+            EXPECT(keep.same(Map(to, oH, oW)) && keys == keys0);
+        }
+}
+
 int main() {
     const double pi = 3.14159265358979323846;
     const double fish[17] = {1.0 / 35, 0, -27.5 / 35, 0, 1.0 / 33, -16.0 / 33, 0.001, -0.0005, 1, 61.5, 58.75, 25.25, 17.5, 0.05, -0.012, 0.004, -0.0009};
@@ -154,6 +195,9 @@ int main() {
     entry_ops(1, 1);
     entry_ops(2, 2);
     entry_ops(5, 67);
+    raster_ops(1, 1);
+    raster_ops(2, 2);
+    raster_ops(5, 67);
     std::printf(fails ? "%d check(s) failed\n" : "ok\n", fails);
     return fails ? 1 : 0;
 }

@@ -1160,6 +1160,19 @@ def coords_invert(f, out_hw, init=None, dtype=None, out=None, origin=(0, 0), max
     return _lib.coords_invert_on(_lib.DeviceOperands(), f, out_hw, init, dtype, out, origin, max_iter, tol)
 
 
+def coords_invert_raster(f, out_hw, depth=None, dtype=None, out=None, origin=(0, 0), max_span=16, orient=0, keys=None, return_keys=False):
+    """lerf_coords_invert_raster: the inverse of f [fH, fW, 2] read as its PIECEWISE-LINEAR interpolant over two triangles a cell, by
+    rasterising every triangle into the tile out_hw at `origin` with a depth test: for maps that fold or tear, where coords_invert
+    gives NaN.  Where several triangles cover a pixel the smallest depth wins (depth: float32 contiguous [fH, fW] on f's device;
+    None: the lowest triangle); a triangle whose pixel box is wider than max_span (1..64) is a tear and fills nothing; orient +1 /
+    -1 culls triangles of the other orientation (+1: the identity's), 0 keeps both; (NaN, NaN) where nothing lands.  keys: an int64
+    contiguous [oH, oW] workspace on f's device (None: a new one), which holds the winning 64-bit keys afterwards -- low 32 bits the
+    triangle, -1 (all ones) for a hole.  -> G, or (G, keys) with return_keys=True.  Device maps under the strided contract, any mix
+    of float32 / float64; dtype: G's, default f's.  Three launches on the current stream, no sync; bit-equal from run to run and to
+    _lib.coords_invert_raster_host."""
+    return _lib.coords_invert_raster_on(_lib.DeviceOperands(), f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys)
+
+
 def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):
     """lerf_coords_compose_bwd: ACCUMULATE the adjoint of coords_compose(outer, inner) of grad_out (float64 contiguous [oH, oW, 2])
     into grad_outer (float64 contiguous [aH, aW, 2]: a bilinear scatter by float64 atomic adds, reproducible up to the rounding of

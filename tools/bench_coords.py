@@ -10,6 +10,11 @@
   invert    a 2160 x 3840 radial map (over a 2160 x 3840 source) inverted into a 2160 x 3840 inverse (lerf_coords_invert), as a
             float64 and as a float32 map, from the affine start; beside it, in the same run, compose of the map with its inverse
             (the same sizes) and the host twin (wall clock); the mean and the largest number of Newton passes
+  invert_raster   the same radial map inverted by rasterisation (lerf_coords_invert_raster: fill, one thread per cell with a 64-bit
+            integer atomic min per covered pixel, resolve), float64 and float32, max_span = 16, with and without a depth plane, next to
+            invert and compose in the same run: its time over invert's, the share of pixels reached, device against host twin (G and
+            keys) on a 135 x 240 crop from the middle of the map, and the atomics per output pixel -- the (triangle, pixel) pairs that
+            pass the inside test on that crop, counted in numpy; the kernel's skip of an atomic behind a smaller key only lowers it
 
 Device times: device events around `--iters` calls after `--warmup` calls, median of `--repeats` windows (tools/bench_remap.py's
 scheme).  With each device time go the bytes the call must move at least once and the share of the HBM peak they imply:
@@ -67,6 +72,33 @@ def host_ms(fn, repeats):
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t) * 1e3)
     return float(np.median(ms)), out
+
+
+def raster_candidates(F, out_hw, origin, max_span):
+    """The (triangle, pixel) pairs that pass lerf_coords_invert_raster's inside test on a small float64 map, counted in numpy (orient 0;
+    a statistic: the edge functions are not evaluated in the kernel's canonical endpoint order, so a pixel exactly on an edge may
+    round the other way): the 64-bit atomics the raster pass issues when no load lets one be skipped -- the skip only lowers it."""
+    def edge(P, Q, qr, qc):
+        return (Q[..., 1] - P[..., 1]) * (qr - P[..., 0]) - (Q[..., 0] - P[..., 0]) * (qc - P[..., 1])
+    P00, P01, P10, P11 = F[:-1, :-1], F[:-1, 1:], F[1:, :-1], F[1:, 1:]
+    total = 0
+    for A, B, C in ((P00, P01, P10), (P11, P10, P01)):
+        with np.errstate(all="ignore"):
+            area2 = edge(A, B, C[..., 0], C[..., 1])
+            ok = np.isfinite(A).all(-1) & np.isfinite(B).all(-1) & np.isfinite(C).all(-1) & np.isfinite(area2) & (area2 != 0.0)
+            box = []
+            for k, (first, n) in enumerate(zip(origin, out_hw)):
+                v = np.stack([A[..., k], B[..., k], C[..., k]])
+                lo, hi = np.ceil(v.min(0)), np.floor(v.max(0))
+                ok &= ~((hi - lo) + 1.0 > max_span)
+                box.append((np.maximum(lo, first), np.minimum(hi, first + n - 1)))
+            for dr in range(max_span):
+                for dc in range(max_span):
+                    qr, qc = box[0][0] + dr, box[1][0] + dc
+                    e = (edge(A, B, qr, qc), edge(B, C, qr, qc), edge(C, A, qr, qc))
+                    inside = np.where(area2 > 0.0, (e[0] >= 0) & (e[1] >= 0) & (e[2] >= 0), (e[0] <= 0) & (e[1] <= 0) & (e[2] <= 0))
+                    total += int((ok & (qr <= box[0][1]) & (qc <= box[1][1]) & inside).sum())
+    return total
 
 
 def main():
@@ -173,6 +205,38 @@ def main():
     inv["host_twin_plus_upload_ms"] = round(h_ms, 1)
     inv["equals_host"] = same
     res["invert"] = inv
+
+    # invert_raster: the same radial map drawn triangle by triangle (lerf_coords_invert_raster), next to invert in the same run
+    ras = {"max_span": 16}
+    depth = (1.0 + 1e-3 * torch.arange(hw[0], device=dev)[:, None] + 5e-4 * torch.arange(hw[1], device=dev)[None, :]).float().contiguous()
+    keys = torch.empty(hw, dtype=torch.int64, device=dev)
+    ci, cj, ch, cw = hw[0] // 2 - 67, hw[1] // 2 - 120, min(135, hw[0]), min(240, hw[1])
+    ci, cj = max(ci, 0), max(cj, 0)
+    for name, Fm in (("float64", F), ("float32", F.float())):
+        o = torch.empty(hw + (2,), dtype=Fm.dtype, device=dev)
+        eb = 16 if name == "float64" else 8
+        crop = Fm[ci:ci + ch, cj:cj + cw].contiguous()
+        mid = crop[ch // 2, cw // 2].double().cpu().numpy()
+        origin = (max(int(mid[0]) - ch // 2, 0), max(int(mid[1]) - cw // 2, 0))
+        for dname, d in (("", None), ("_depth", depth)):
+            t = device_ms(lambda: ops.coords_invert_raster(Fm, hw, depth=d, out=o, max_span=16, keys=keys), a.iters, a.warmup, a.repeats)
+            # F and depth read once, keys filled, touched by the atomics and read, the inverse written
+            r = row(t, (eb + (4 if d is not None else 0) + 24 + eb) * entries)
+            r["ratio_to_invert"] = round(t[0] / inv[name]["ms"], 2)
+            r["reached_fraction"] = round(float((keys != -1).double().mean()), 4)
+            dc = None if d is None else d[ci:ci + ch, cj:cj + cw].contiguous()
+            g_dev, k_dev = ops.coords_invert_raster(crop, (ch, cw), depth=dc, origin=origin, max_span=16, return_keys=True)
+            crop_np = crop.cpu().numpy()
+            g_host, k_host = _lib.coords_invert_raster_host(crop_np, (ch, cw), depth=None if dc is None else dc.cpu().numpy(), dtype=crop_np.dtype,
+                                                            origin=origin, max_span=16, return_keys=True)
+            same = bool(np.array_equal(k_dev.cpu().numpy().view(np.uint64), k_host)) and \
+                bool(torch.equal(torch.nan_to_num(g_dev, nan=-1.0), torch.nan_to_num(torch.from_numpy(g_host).to(dev), nan=-1.0)))
+            equal = equal and same
+            r["equals_host_on_crop"] = same
+            ras[name + dname] = r
+    ras["crop"] = {"hw": [ch, cw], "origin": list(origin)}
+    ras["atomics_per_pixel_max"] = round(raster_candidates(F[ci:ci + ch, cj:cj + cw].cpu().numpy(), (ch, cw), origin, 16) / (ch * cw), 3)
+    res["invert_raster"] = ras
     res["device_equals_host"] = equal
     print(json.dumps(res))
     if not equal:
