@@ -357,8 +357,8 @@ int lerf_remap_host_geometry(const lerf_remap_geo_t* geo, int H, int W, double* 
  * Refused with LERF_EINVAL before anything is launched: n_maps < 1; a plane or frame count other than n_maps * planes_per_map
  * (n_maps for the packed form); a negative or odd map_stride (an entry is two elements: an even stride keeps every map's entries
  * aligned like map 0's); for n_maps > 1 a map_stride below (out_h - 1) * row_stride + 2 * out_w (overlapping maps).  n_maps == 1
- * is the plain entry point.  lerf_coords_build_dev writes such a batch of model maps in one launch; the mesh builder, compose and
- * invert stay one map per launch. */
+ * is the plain entry point.  lerf_coords_build_dev writes such a batch of model maps in one launch; the mesh builder, compose,
+ * invert and their adjoints take a batch through lerf_coords_*_batched (the end of this header). */
 int lerf_remap_batched(const lerf_plane_t* feat, const lerf_plane_t hyper[3], int H, int W, int C, const lerf_remap_geo_t* geo,
                        int n_maps, int64_t map_stride, int planes_per_map, int kind, double max_sigma, const lerf_mplane_t* out,
                        void* stream);
@@ -908,6 +908,89 @@ int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int 
 enum { LERF_MATH_SQRT = 0, LERF_MATH_ATAN = 1, LERF_MATH_ATAN2 = 2 };
 int lerf_coords_math(int op, const double* x, const double* y, int64_t n, double* out, void* stream);
 int lerf_coords_math_host(int op, const double* x, const double* y, int64_t n, double* out);
+
+/* The chained operations on a BATCH of n_sets maps in one launch: each entry point below is its single-map form with
+ * n_sets and one SET STRIDE per operand appended; set s reads and writes operand base + s * set_stride ELEMENTS (of the operand's own
+ * dtype: a map's floats or doubles, a float64 gradient's doubles, keys' uint64, depth's floats; the workspace of the mesh adjoint is
+ * dense per set).  Every set has the shapes, dtypes, row strides and scalars of the single-map arguments, and set s of a batched call
+ * is the single-map call on the same operands BIT FOR BIT (where the single-map form is bit-reproducible; the two atomic scatters
+ * grad_a and grad_f stay equal up to the rounding of a reordered float64 sum).  The single-map entry points are the n_sets = 1 case
+ * of the same kernels; with n_sets = 1 the set strides are not used (0 will do).
+ * Set strides: non-negative; EVEN for maps and float64 gradients (pairs: every set's entries stay aligned like set 0's; keys and
+ * depth hold scalars and take any stride); for n_sets > 1 at least the operand's extent, first element to one past the last --
+ * (h - 1) * row_stride + 2 * w for a map, 2 * h * w for a gradient or a control mesh, h * w for keys and depth -- so sets do not
+ * overlap, OR 0 = ONE operand shared by all sets, which is allowed for exactly these:
+ *   read-only   a (the outer map of compose and of its adjoint), f, init, depth
+ *   grad_a      the gradient of a shared outer map: every set scatters into the one buffer, which gains the SUM over the sets (device:
+ *               the float64 atomic adds the scatter uses anyway; host twin: plain adds in set order, i.e. the single-map host twin
+ *               called once per set on the same buffer, bit for bit).  grad_a_set_stride = 0 needs a_set_stride = 0.
+ * Not shareable (0 refused for n_sets > 1): every single-writer output (out, grad_b, keys, grad_ctrl), the inner map b / the inverse g,
+ * grad_out / grad_map, ctrl.  Where the single-map form refuses operands whose bytes intersect, the batched form refuses the same
+ * pairs over the WHOLE batch: an operand's bytes run from its first element of set 0 to one past its last of set n_sets - 1.
+ * lerf_coords_compose_batched with n_sets > 1 also refuses an out whose batch intersects a's, or b's unless it IS b (same base,
+ * dtype, row and set stride: in place).  n_sets < 1: LERF_EINVAL; n_sets > 65535 (the grid's z limit): LERF_EUNSUPPORTED.  A
+ * refused call launches and writes nothing; the device entry points refuse before they touch the device.
+ * lerf_coords_invert_raster_batched: n_sets key planes (8 bytes per output pixel PER SET).  lerf_coords_mesh_bwd_batched: workspace
+ * >= n_sets * lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW) bytes, [n_sets][gh][oW][2] doubles. */
+int lerf_coords_mesh_batched(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w,
+                             void* out, int out_dtype, int64_t row_stride, int oH, int oW, int i0, int j0,
+                             int n_sets, int64_t ctrl_set_stride, int64_t out_set_stride, void* stream);
+int lerf_coords_mesh_batched_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w,
+                                  void* out, int out_dtype, int64_t row_stride, int oH, int oW, int i0, int j0,
+                                  int n_sets, int64_t ctrl_set_stride, int64_t out_set_stride);
+int lerf_coords_mesh_bwd_batched(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl,
+                                 void* workspace, size_t workspace_bytes,
+                                 int n_sets, int64_t grad_map_set_stride, int64_t grad_ctrl_set_stride, void* stream);
+int lerf_coords_compose_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                const void* b, int b_dtype, int64_t b_row_stride,
+                                void* out, int out_dtype, int64_t out_row_stride, int oH, int oW,
+                                int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t out_set_stride, void* stream);
+int lerf_coords_compose_batched_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                     const void* b, int b_dtype, int64_t b_row_stride,
+                                     void* out, int out_dtype, int64_t out_row_stride, int oH, int oW,
+                                     int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t out_set_stride);
+int lerf_coords_invert_batched(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                               const void* init, int init_dtype, int64_t init_row_stride,
+                               void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                               int max_iter, double tol,
+                               int n_sets, int64_t f_set_stride, int64_t init_set_stride, int64_t out_set_stride, void* stream);
+int lerf_coords_invert_batched_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                    const void* init, int init_dtype, int64_t init_row_stride,
+                                    void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                                    int max_iter, double tol,
+                                    int n_sets, int64_t f_set_stride, int64_t init_set_stride, int64_t out_set_stride);
+int lerf_coords_invert_raster_batched(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                      const float* depth,
+                                      void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                                      int max_span, int orient, uint64_t* keys,
+                                      int n_sets, int64_t f_set_stride, int64_t depth_set_stride, int64_t out_set_stride,
+                                      int64_t keys_set_stride, void* stream);
+int lerf_coords_invert_raster_batched_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                           const float* depth,
+                                           void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                                           int max_span, int orient, uint64_t* keys,
+                                           int n_sets, int64_t f_set_stride, int64_t depth_set_stride, int64_t out_set_stride,
+                                           int64_t keys_set_stride);
+int lerf_coords_compose_bwd_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                    const void* b, int b_dtype, int64_t b_row_stride,
+                                    const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                    int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride,
+                                    int64_t grad_a_set_stride, int64_t grad_b_set_stride, void* stream);
+int lerf_coords_compose_bwd_batched_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                         const void* b, int b_dtype, int64_t b_row_stride,
+                                         const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                         int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride,
+                                         int64_t grad_a_set_stride, int64_t grad_b_set_stride);
+int lerf_coords_invert_bwd_batched(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                   const void* g, int g_dtype, int64_t g_row_stride,
+                                   const double* grad_out, int oH, int oW, double* grad_f,
+                                   int n_sets, int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride,
+                                   int64_t grad_f_set_stride, void* stream);
+int lerf_coords_invert_bwd_batched_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                        const void* g, int g_dtype, int64_t g_row_stride,
+                                        const double* grad_out, int oH, int oW, double* grad_f,
+                                        int n_sets, int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride,
+                                        int64_t grad_f_set_stride);
 
 #ifdef __cplusplus
 }

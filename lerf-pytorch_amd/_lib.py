@@ -58,6 +58,9 @@ EXPORTS = [
     "lerf_coords_mesh_bwd", "lerf_coords_compose", "lerf_coords_compose_host", "lerf_coords_invert", "lerf_coords_invert_host",
     "lerf_coords_invert_raster", "lerf_coords_invert_raster_host", "lerf_coords_compose_bwd", "lerf_coords_compose_bwd_host", "lerf_coords_invert_bwd", "lerf_coords_invert_bwd_host",
     "lerf_coords_build_dev", "lerf_coords_build_bwd_workspace_bytes", "lerf_coords_build_bwd", "lerf_coords_build_bwd_host", "lerf_coords_math", "lerf_coords_math_host",
+    "lerf_coords_mesh_batched", "lerf_coords_mesh_batched_host", "lerf_coords_mesh_bwd_batched", "lerf_coords_compose_batched", "lerf_coords_compose_batched_host",
+    "lerf_coords_invert_batched", "lerf_coords_invert_batched_host", "lerf_coords_invert_raster_batched", "lerf_coords_invert_raster_batched_host",
+    "lerf_coords_compose_bwd_batched", "lerf_coords_compose_bwd_batched_host", "lerf_coords_invert_bwd_batched", "lerf_coords_invert_bwd_batched_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -325,6 +328,13 @@ def lib():
     L.lerf_coords_math.argtypes, L.lerf_coords_math_host.argtypes = _math + [C.c_void_p], _math
     L.lerf_coords_build_bwd_workspace_bytes.restype = C.c_size_t
     L.lerf_coords_build_bwd_workspace_bytes.argtypes = [C.c_int] * 4
+    # the batched forms: the single-map arguments, n_sets, one set stride per operand (then the stream)
+    for name, single, n_strides in (("mesh", _mesh, 2), ("compose", _compose, 3), ("invert", _invert, 3), ("invert_raster", _raster, 4),
+                                    ("compose_bwd", _compose_bwd, 5), ("invert_bwd", _invert_bwd, 4)):
+        batched = single + [C.c_int] + [C.c_int64] * n_strides
+        getattr(L, "lerf_coords_%s_batched" % name).argtypes = batched + [C.c_void_p]
+        getattr(L, "lerf_coords_%s_batched_host" % name).argtypes = batched
+    L.lerf_coords_mesh_bwd_batched.argtypes = L.lerf_coords_mesh_bwd.argtypes[:-1] + [C.c_int, C.c_int64, C.c_int64, C.c_void_p]
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -451,6 +461,50 @@ class _Operands:
             raise ValueError("%s: out must be [%d, %d, 2]" % (what, oH, oW))
         return self.map(out, "out")
 
+    def batch(self, a, what, out=False):
+        """(a, row stride, set stride, B) of a batch of maps [B, h, w, 2], set stride in elements like the row stride; a single map
+        [h, w, 2] gives B = 0 and set stride 0 (in a batched call: one map shared by every set).  A batch is passed through when its
+        strides meet the C contract (pairs contiguous, even row and set strides, sets that do not overlap); any other view of an
+        input is made contiguous, any other view of an output is refused."""
+        if not (self.is_array(a) and a.ndim == 4):
+            a, s = self.map(a, what)
+            return a, s, 0, 0
+        if a.shape[3] != 2 or min(a.shape[:3]) < 1:
+            raise ValueError("%s must be %s [B, h, w, 2]" % (what, self.noun))
+        if not self.is_float(a):
+            raise ValueError("%s must be float32 or float64, not %s" % (what, a.dtype))
+        for copy in (False, True):
+            if copy:
+                if out:
+                    raise ValueError("%s: contiguous (row, col) pairs, even row and set strides, sets that do not overlap" % what)
+                a = self.contiguous(a)
+            s = self.strides(a)
+            B, h, w = a.shape[:3]
+            if s[3] == 1 and s[2] == 2 and s[1] is not None and s[1] % 2 == 0 and s[1] >= 2 * w and (
+                    B == 1 or (s[0] is not None and s[0] % 2 == 0 and s[0] >= (h - 1) * s[1] + 2 * w)):
+                return a, s[1], (0 if B == 1 else s[0]), B
+        raise ValueError("%s: contiguous (row, col) pairs, column stride 2" % what)
+
+    def outs(self, out, B, out_hw, dtype, default, device, what):
+        """out() for a batch: a new [B, oH, oW, 2] or the checked `out`, with its row and set strides (B == 0: one map, set stride 0)"""
+        if not B:
+            return self.out(out, out_hw, dtype, default, device, what) + (0,)
+        oH, oW = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            if oH < 1 or oW < 1:
+                raise ValueError("%s: out_hw must be positive" % what)
+            out = self.new((B, oH, oW, 2), self.dtype(dtype, default, what), device)
+        elif not self.is_array(out) or tuple(out.shape[:3]) != (B, oH, oW):
+            raise ValueError("%s: out must be [%d, %d, %d, 2]" % (what, B, oH, oW))
+        return self.batch(out, "out", out=True)[:3]
+
+    def run(self, name, B, anchor, args, set_strides):
+        """ONE library call: the single-map entry point `name`, or (B > 0) its batched form with n_sets = B and the set strides"""
+        if B:
+            self.call(name + "_batched" + self.suffix, anchor, *args, B, *[int(x) for x in set_strides])
+        else:
+            self.call(name + self.suffix, anchor, *args)
+
     def grad(self, g, shape, device, what):
         """a dense float64 gradient buffer [h, w, 2] (None: a zeroed one)"""
         if g is None:
@@ -561,7 +615,9 @@ _HOST = HostOperands()
 
 
 # The eight operations that exist on both sides, over X = HostOperands() or DeviceOperands(): ops.coords_* and coords_*_host below
-# bind them and carry the documentation.
+# bind them and carry the documentation.  Mesh, compose, invert, invert_raster and the two adjoints take a leading B on their maps
+# ([B, h, w, 2]) and then make ONE call of the batched entry point (lerf_coords_*_batched); a 3-D operand beside a batch is shared
+# where the C contract allows it.
 def coords_build_on(X, model, params, out_hw, dtype, out, origin, device=None):
     what = "lerf_coords_build" + X.suffix
     code, p = coords_model_params(model, params, what)
@@ -573,80 +629,115 @@ def coords_build_on(X, model, params, out_hw, dtype, out, origin, device=None):
 def coords_mesh_on(X, ctrl, out_hw, interp, dtype, out, origin, full_hw):
     what = "lerf_coords_mesh" + X.suffix
     c = X.contiguous(ctrl)
-    if not X.is_array(c) or c.ndim != 3 or c.shape[2] != 2:
-        raise ValueError("%s: ctrl must be %s [gh, gw, 2]" % (what, X.noun))
+    if not X.is_array(c) or c.ndim not in (3, 4) or c.shape[-1] != 2:
+        raise ValueError("%s: ctrl must be %s [gh, gw, 2] or [B, gh, gw, 2]" % (what, X.noun))
     if not X.is_float(c):
         raise ValueError("%s: ctrl must be float32 or float64" % what)
     code = mesh_interp_code(interp)
     full_hw = out_hw if full_hw is None else full_hw
-    out, stride = X.out(out, out_hw, dtype, c.dtype, X.device(c), what)
+    B = c.shape[0] if c.ndim == 4 else 0
+    if c.ndim == 4 and B < 1:
+        raise ValueError("%s: an empty batch" % what)
+    gh, gw = c.shape[-3], c.shape[-2]
+    out, stride, set_stride = X.outs(out, B, out_hw, dtype, c.dtype, X.device(c), what)
     X.one_device(what, ("ctrl", "out"), c, out)
-    X.call(what, c, X.ptr(c), X.code(c), c.shape[0], c.shape[1], code, int(full_hw[0]), int(full_hw[1]), *X.operand(out, stride),
-           int(out_hw[0]), int(out_hw[1]), int(origin[0]), int(origin[1]))
+    X.run("lerf_coords_mesh", B, c, (X.ptr(c), X.code(c), gh, gw, code, int(full_hw[0]), int(full_hw[1]), *X.operand(out, stride),
+                                     int(out_hw[0]), int(out_hw[1]), int(origin[0]), int(origin[1])), (2 * gh * gw, set_stride))
     return out
+
+
+def _one_batch(what, names, *sizes):
+    """the common B of operands that hold B (batched) or 0 (single, shared) maps"""
+    B = max(sizes)
+    if any(b and b != B for b in sizes):
+        raise ValueError("%s: %s hold different numbers of maps" % (what, " and ".join(names)))
+    return B
 
 
 def coords_compose_on(X, outer, inner, dtype, out):
     what = "lerf_coords_compose" + X.suffix
-    a, sa = X.map(outer, "outer")
-    b, sb = X.map(inner, "inner")
+    a, sa, ta, Ba = X.batch(outer, "outer")
+    b, sb, tb, Bb = X.batch(inner, "inner")
     X.one_device(what, ("outer", "inner"), a, b)
-    out, so = X.out(out, b.shape[:2], dtype, b.dtype, X.device(b), what)
-    X.call(what, b, *X.operand(a, sa), a.shape[0], a.shape[1], *X.operand(b, sb), *X.operand(out, so), b.shape[0], b.shape[1])
+    if Ba and not Bb:
+        raise ValueError("%s: a batch of outer maps needs a batch of as many inner maps" % what)
+    B = _one_batch(what, ("outer", "inner"), Ba, Bb)
+    out, so, to = X.outs(out, B, b.shape[-3:-1], dtype, b.dtype, X.device(b), what)
+    X.run("lerf_coords_compose", B, b, (*X.operand(a, sa), a.shape[-3], a.shape[-2], *X.operand(b, sb), *X.operand(out, so), b.shape[-3],
+                                        b.shape[-2]), (ta, tb, to))
     return out
 
 
 def coords_invert_on(X, f, out_hw, init, dtype, out, origin, max_iter, tol):
     what = "lerf_coords_invert" + X.suffix
-    a, sa = X.map(f, "f")
-    b, sb = (None, 0) if init is None else X.map(init, "init")
-    out, so = X.out(out, out_hw, dtype, a.dtype, X.device(a), what)
+    a, sa, ta, Ba = X.batch(f, "f")
+    b, sb, tb, Bb = (None, 0, 0, 0) if init is None else X.batch(init, "init")
+    B = _one_batch(what, ("f", "init"), Ba, Bb)
+    out, so, to = X.outs(out, B, out_hw, dtype, a.dtype, X.device(a), what)
     X.one_device(what, ("f", "out", "init"), a, out, b)
-    if b is not None and tuple(b.shape[:2]) != tuple(out.shape[:2]):
+    if b is not None and tuple(b.shape[-3:-1]) != tuple(out.shape[-3:-1]):
         raise ValueError("%s: init must have out's shape" % what)
-    X.call(what, a, *X.operand(a, sa), a.shape[0], a.shape[1], X.ptr(b), LERF_F64 if b is None else X.code(b), sb, *X.operand(out, so),
-           out.shape[0], out.shape[1], int(origin[0]), int(origin[1]), int(max_iter), float(tol))
+    X.run("lerf_coords_invert", B, a, (*X.operand(a, sa), a.shape[-3], a.shape[-2], X.ptr(b), LERF_F64 if b is None else X.code(b), sb,
+                                       *X.operand(out, so), out.shape[-3], out.shape[-2], int(origin[0]), int(origin[1]), int(max_iter),
+                                       float(tol)), (ta, tb, to))
     return out
 
 
 def coords_invert_raster_on(X, f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys):
     what = "lerf_coords_invert_raster" + X.suffix
-    a, sa = X.map(f, "f")
-    out, so = X.out(out, out_hw, dtype, a.dtype, X.device(a), what)
-    d = None if depth is None else X.dense(depth, a.shape[:2], X.f32, X.device(a), what + ": depth")
-    k = X.dense(keys, out.shape[:2], X.key, X.device(a), what + ": keys")
+    a, sa, ta, Ba = X.batch(f, "f")
+    fhw = tuple(a.shape[-3:-1])
+    Bd = a.shape[0] if Ba and depth is not None and getattr(depth, "ndim", 0) == 3 else 0        # depth [fH, fW]: one for every map
+    B = _one_batch(what, ("f", "depth"), Ba, Bd)
+    out, so, to = X.outs(out, B, out_hw, dtype, a.dtype, X.device(a), what)
+    d = None if depth is None else X.dense(depth, ((Bd,) if Bd else ()) + fhw, X.f32, X.device(a), what + ": depth")
+    k = X.dense(keys, tuple(out.shape[:-1]), X.key, X.device(a), what + ": keys")
     X.one_device(what, ("f", "out"), a, out)
-    X.call(what, a, *X.operand(a, sa), a.shape[0], a.shape[1], X.ptr(d), *X.operand(out, so), out.shape[0], out.shape[1], int(origin[0]),
-           int(origin[1]), int(max_span), int(orient), X.ptr(k))
+    ohw = tuple(out.shape[-3:-1])
+    X.run("lerf_coords_invert_raster", B, a, (*X.operand(a, sa), fhw[0], fhw[1], X.ptr(d), *X.operand(out, so), ohw[0], ohw[1], int(origin[0]),
+                                              int(origin[1]), int(max_span), int(orient), X.ptr(k)),
+          (ta, fhw[0] * fhw[1] if Bd > 1 else 0, to, ohw[0] * ohw[1] if B > 1 else 0))
     return (out, k) if return_keys else out
 
 
 def _coords_bwd_operands(X, what, first, second, names, grad_out):
-    """the two maps of an adjoint and its upstream gradient, which has the second map's shape"""
-    a, sa = X.map(first, names[0])
-    b, sb = X.map(second, names[1])
+    """the two maps (or batches) of an adjoint and its upstream gradient, which has the second one's shape"""
+    a, sa, ta, Ba = X.batch(first, names[0])
+    b, sb, tb, Bb = X.batch(second, names[1])
     X.one_device(what, names, a, b)
+    if Ba and not Bb:
+        raise ValueError("%s: a batch of %s maps needs a batch of as many %s maps" % (what, names[0], names[1]))
+    B = _one_batch(what, names, Ba, Bb)
     if grad_out is None:
         raise ValueError("%s: grad_out must be contiguous float64 [oH, oW, 2]" % what)
-    return a, sa, b, sb, X.grad(grad_out, b.shape, X.device(b), what + ": grad_out")
+    return a, sa, ta, b, sb, tb, B, X.grad(grad_out, b.shape, X.device(b), what + ": grad_out")
+
+
+def _dense_set(B, t):
+    """the set stride of a contiguous float64 gradient: its maps are back to back (0: a single, shared one)"""
+    return 0 if B < 2 or t is None or t.ndim == 3 else 2 * t.shape[-3] * t.shape[-2]
 
 
 def coords_compose_bwd_on(X, outer, inner, grad_out, grad_outer, grad_inner, need):
     what = "lerf_coords_compose_bwd" + X.suffix
-    a, sa, b, sb, g = _coords_bwd_operands(X, what, outer, inner, ("outer", "inner"), grad_out)
+    a, sa, ta, b, sb, tb, B, g = _coords_bwd_operands(X, what, outer, inner, ("outer", "inner"), grad_out)
     if not (need[0] or need[1]):
         raise ValueError("%s: at least one of the two gradients is needed" % what)
     ga = X.grad(grad_outer, a.shape, X.device(b), what + ": grad_outer") if need[0] else None
     gb = X.grad(grad_inner, b.shape, X.device(b), what + ": grad_inner") if need[1] else None
-    X.call(what, b, *X.operand(a, sa), a.shape[0], a.shape[1], *X.operand(b, sb), X.ptr(g), b.shape[0], b.shape[1], X.ptr(ga), X.ptr(gb))
+    X.run("lerf_coords_compose_bwd", B, b, (*X.operand(a, sa), a.shape[-3], a.shape[-2], *X.operand(b, sb), X.ptr(g), b.shape[-3], b.shape[-2],
+                                            X.ptr(ga), X.ptr(gb)), (ta, tb, _dense_set(B, g), _dense_set(B, ga), _dense_set(B, gb)))
     return ga, gb
 
 
 def coords_invert_bwd_on(X, f, inverse, grad_out, grad_f):
     what = "lerf_coords_invert_bwd" + X.suffix
-    a, sa, b, sb, g = _coords_bwd_operands(X, what, f, inverse, ("f", "inverse"), grad_out)
+    a, sa, ta, b, sb, tb, B, g = _coords_bwd_operands(X, what, f, inverse, ("f", "inverse"), grad_out)
+    if B and a.ndim == 3:
+        raise ValueError("%s: a batch of inverses needs a batch of as many maps f (grad_f has one writer per set)" % what)
     gf = X.grad(grad_f, a.shape, X.device(b), what + ": grad_f")
-    X.call(what, b, *X.operand(a, sa), a.shape[0], a.shape[1], *X.operand(b, sb), X.ptr(g), b.shape[0], b.shape[1], X.ptr(gf))
+    X.run("lerf_coords_invert_bwd", B, b, (*X.operand(a, sa), a.shape[-3], a.shape[-2], *X.operand(b, sb), X.ptr(g), b.shape[-3], b.shape[-2],
+                                           X.ptr(gf)), (ta, tb, _dense_set(B, g), _dense_set(B, gf)))
     return gf
 
 
@@ -673,18 +764,21 @@ def coords_build_host(model, params, out_hw, dtype=np.float64, out=None, origin=
 
 
 def coords_mesh_host(ctrl, out_hw, interp="bilinear", dtype=np.float64, out=None, origin=(0, 0), full_hw=None):
-    """lerf_coords_mesh_host: ctrl [gh, gw, 2] float32 / float64 upsampled to the tile out_hw at `origin` of the map full_hw"""
+    """lerf_coords_mesh_host: ctrl [gh, gw, 2] float32 / float64 upsampled to the tile out_hw at `origin` of the map full_hw; a batch
+    ctrl [B, gh, gw, 2] -> [B, oH, oW, 2] by one call of lerf_coords_mesh_batched_host"""
     return coords_mesh_on(_HOST, ctrl, out_hw, interp, dtype, out, origin, full_hw)
 
 
 def coords_compose_host(outer, inner, dtype=np.float64, out=None):
-    """lerf_coords_compose_host: C[i, j] = outer(inner[i, j]), host arrays under the strided map contract"""
+    """lerf_coords_compose_host: C[i, j] = outer(inner[i, j]), host arrays under the strided map contract; a batch inner [B, oH, oW, 2]
+    with outer [B, aH, aW, 2] or one shared [aH, aW, 2] -> [B, oH, oW, 2] by one call of lerf_coords_compose_batched_host"""
     return coords_compose_on(_HOST, outer, inner, dtype, out)
 
 
 def coords_invert_host(f, out_hw, init=None, dtype=np.float64, out=None, origin=(0, 0), max_iter=16, tol=1e-9):
     """lerf_coords_invert_host: G[i, j] = the u with f(u) = origin + (i, j), f read bilinearly, by Newton's method from init[i, j]
-    (None: the affine guess from three corners of f); NaN where f does not reach.  Host arrays under the strided map contract."""
+    (None: the affine guess from three corners of f); NaN where f does not reach.  Host arrays under the strided map contract.  A batch
+    f [B, fH, fW, 2] (init batched, shared or None) -> [B, oH, oW, 2] by one call of lerf_coords_invert_batched_host."""
     return coords_invert_on(_HOST, f, out_hw, init, dtype, out, origin, max_iter, tol)
 
 
@@ -693,20 +787,23 @@ def coords_invert_raster_host(f, out_hw, depth=None, dtype=np.float64, out=None,
     """lerf_coords_invert_raster_host: the rasterising inverse of f [fH, fW, 2] into the tile out_hw at `origin` by the row-major host
     loop over the kernel's own per-triangle arithmetic (bit-equal to ops.coords_invert_raster in G and in keys).  depth: float32
     contiguous [fH, fW] or None; keys: a contiguous uint64 [oH, oW] workspace (None: a new one) -> G, or (G, keys) with
-    return_keys=True: the winning keys, low 32 bits the triangle, all ones for a hole."""
+    return_keys=True: the winning keys, low 32 bits the triangle, all ones for a hole.  A batch f [B, fH, fW, 2] (depth [B, fH, fW], one
+    shared [fH, fW] or None; keys [B, oH, oW], one plane per sample) -> [B, oH, oW, 2] by one call of lerf_coords_invert_raster_batched_host."""
     return coords_invert_raster_on(_HOST, f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys)
 
 
 def coords_compose_bwd_host(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):
     """lerf_coords_compose_bwd_host: ACCUMULATE the adjoint of compose(outer, inner) of the float64 grad_out [oH, oW, 2] into
     grad_outer [aH, aW, 2] and grad_inner [oH, oW, 2] (None: zeroed ones; need[k] False: that half is skipped and None is
-    returned for it) -> (grad_outer, grad_inner)."""
+    returned for it) -> (grad_outer, grad_inner).  A batch (inner and grad_out [B, oH, oW, 2]; outer [B, aH, aW, 2] or one shared
+    [aH, aW, 2], whose gradient gains the sum over the samples in sample order) is one call of lerf_coords_compose_bwd_batched_host."""
     return coords_compose_bwd_on(_HOST, outer, inner, grad_out, grad_outer, grad_inner, need)
 
 
 def coords_invert_bwd_host(f, inverse, grad_out, grad_f=None):
     """lerf_coords_invert_bwd_host: ACCUMULATE the implicit-function adjoint of inverse = invert(f) of the float64 grad_out
-    [oH, oW, 2] into grad_f [fH, fW, 2] (None: a zeroed one)."""
+    [oH, oW, 2] into grad_f [fH, fW, 2] (None: a zeroed one).  A batch (every operand with a leading B) is one call of
+    lerf_coords_invert_bwd_batched_host."""
     return coords_invert_bwd_on(_HOST, f, inverse, grad_out, grad_f)
 
 

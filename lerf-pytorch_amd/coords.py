@@ -271,7 +271,9 @@ def from_mesh(ctrl, out_hw, interp="bilinear", device=None, dtype=None):
     control vertices spread align-corners over the output (vertex a at output row a (oH - 1) / (gh - 1)); interp "bilinear", or
     "bicubic" (Keys A = -0.75 with clamped border taps: F.interpolate(mode="bicubic", align_corners=True)).  device None and a
     host ctrl: host numpy (the kernel's host twin); a torch device, or a ctrl already on one: a device tensor written by the
-    kernel.  dtype: the map's, default ctrl's (float64 for anything that is not float32)."""
+    kernel.  dtype: the map's, default ctrl's (float64 for anything that is not float32).  A batch of meshes ctrl [B, gh, gw, 2]
+    gives [B, oH, oW, 2], one map per sample in ONE launch (lerf_coords_mesh_batched; on the host one call of its host twin), map s
+    bit-equal to from_mesh(ctrl[s])."""
     on_dev = getattr(ctrl, "is_cuda", False)
     if device is None and not on_dev:
         from . import _lib
@@ -300,11 +302,12 @@ def _mesh_fn():
         from . import ops
 
         class _MeshFn(torch.autograd.Function):
-            """map = ops.coords_mesh(ctrl); backward: ops.coords_mesh_bwd in float64, cast to ctrl's dtype"""
+            """map = ops.coords_mesh(ctrl); backward: ops.coords_mesh_bwd in float64, cast to ctrl's dtype; a batch of meshes goes through
+            both in one call each"""
 
             @staticmethod
             def forward(ctx, ctrl, out_hw, interp):
-                ctx.interp, ctx.ctrl_hw, ctx.dtype = interp, tuple(ctrl.shape[:2]), ctrl.dtype
+                ctx.interp, ctx.ctrl_hw, ctx.dtype = interp, tuple(ctrl.shape[-3:-1]), ctrl.dtype
                 return ops.coords_mesh(ctrl, out_hw, interp)
 
             @staticmethod
@@ -319,10 +322,13 @@ def _mesh_fn():
 def from_mesh_torch(ctrl, out_hw, interp="bilinear"):
     """from_mesh on ctrl's device, differentiable: ctrl [gh, gw, 2] device tensor (float32 or float64) -> the map in ctrl's
     dtype.  A ctrl that requires grad stays in the graph: a remap class that has opted in with enable_backward() hands it
-    d loss / d ctrl through the upsample's adjoint (lerf_coords_mesh_bwd: float64, deterministic, cast to ctrl's dtype)."""
+    d loss / d ctrl through the upsample's adjoint (lerf_coords_mesh_bwd: float64, deterministic, cast to ctrl's dtype).  A batch
+    ctrl [B, gh, gw, 2] gives [B, oH, oW, 2] and the gradient [B, gh, gw, 2]: one launch forward (lerf_coords_mesh_batched), one call
+    of two launches backward (lerf_coords_mesh_bwd_batched), sample s bit-equal to the single-mesh call."""
     import torch
-    if not isinstance(ctrl, torch.Tensor) or ctrl.ndim != 3 or ctrl.shape[2] != 2 or not ctrl.is_floating_point() or not ctrl.is_cuda:
-        raise ValueError("ctrl must be a floating-point [gh, gw, 2] device tensor")
+    if not isinstance(ctrl, torch.Tensor) or ctrl.ndim not in (3, 4) or ctrl.shape[-1] != 2 or not ctrl.is_floating_point() or not ctrl.is_cuda \
+            or ctrl.shape[0] < 1:
+        raise ValueError("ctrl must be a floating-point [gh, gw, 2] or [B, gh, gw, 2] device tensor")
     if interp not in ("bilinear", "bicubic"):
         raise ValueError("interp is 'bilinear' or 'bicubic'")
     return _mesh_fn().apply(ctrl, (int(out_hw[0]), int(out_hw[1])), interp)
@@ -333,8 +339,10 @@ def compose(outer, inner, dtype=None):
     map holds, so remap(remap(img, outer), inner) and remap(img, compose(outer, inner)) describe the same geometry -- one pass
     through the LUT stages and one interpolation instead of two.  Positions outside the outer map are clipped onto its border;
     a NaN entry of the inner map stays (NaN, NaN).  numpy in -> numpy out (the kernel's host twin); device tensors in -> a
-    device tensor; mixed operands are refused.  dtype: default the inner map's.  No autograd: an operand that requires grad
-    (with grad mode on) is refused -- compose_torch is the differentiable twin."""
+    device tensor; mixed operands are refused.  dtype: default the inner map's.  A batch: inner [B, H, W, 2] with outer
+    [B, aH, aW, 2] or one shared [aH, aW, 2] gives [B, H, W, 2] in ONE launch (lerf_coords_compose_batched; on the host one call of its
+    host twin).  No autograd: an operand that requires grad (with grad mode on) is refused -- compose_torch is the differentiable
+    twin."""
     dev = [bool(getattr(t, "is_cuda", False)) for t in (outer, inner)]
     if dev[0] != dev[1]:
         raise ValueError("compose: both maps on the host or both on one device, not mixed")
@@ -365,9 +373,10 @@ def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
     max_iter passes did not meet tol; the remap treats a NaN entry as "no source" (mask false).
 
     numpy in -> numpy out (the kernel's host twin, bit-equal); device tensors in -> a device tensor; mixed map / init is refused.
-    dtype: default the map's.  A batch [B, fH, fW, 2] (init [B, H, W, 2] or None) gives [B, H, W, 2]: one launch per map into the
-    slices of one output tensor -- a single batched launch is not implemented.  No autograd: an operand that requires grad (with
-    grad mode on) is refused -- invert_torch is the differentiable twin."""
+    dtype: default the map's.  A batch [B, fH, fW, 2] (init [B, H, W, 2] or None) gives [B, H, W, 2] in ONE launch
+    (lerf_coords_invert_batched: the sample is the grid's third axis; a wave still runs as long as its slowest lane, a sample as long
+    as its slowest wave, and no sample waits for another's).  No autograd: an operand that requires grad (with grad mode on) is
+    refused -- invert_torch is the differentiable twin."""
     ops_ = [t for t in (map, init) if t is not None]
     dev = [bool(getattr(t, "is_cuda", False)) for t in ops_]
     if any(d != dev[0] for d in dev):
@@ -393,21 +402,13 @@ def invert(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
 
 
 def _invert_maps(map, hw, init, max_iter, tol, dt):
-    """invert of numpy maps by the host twin or of device tensors by the kernel (dt: a numpy or a torch dtype alike): one map, or
-    one call per map of a batch into the slices of one output"""
+    """invert of numpy maps by the host twin or of device tensors by the kernel (dt: a numpy or a torch dtype alike): one map, or a
+    batch in one call"""
     if getattr(map, "is_cuda", False):
-        import torch
         from . import ops
-        one, new = ops.coords_invert, lambda shape: torch.empty(shape, dtype=dt, device=map.device)
-    else:
-        from . import _lib
-        one, new = _lib.coords_invert_host, lambda shape: np.empty(shape, dtype=dt)
-    if map.ndim == 3:
-        return one(map, hw, init=init, dtype=dt, max_iter=max_iter, tol=tol)
-    out = new((map.shape[0], hw[0], hw[1], 2))
-    for n in range(map.shape[0]):
-        one(map[n], hw, init=None if init is None else init[n], out=out[n], max_iter=max_iter, tol=tol)
-    return out
+        return ops.coords_invert(map, hw, init=init, dtype=dt, max_iter=max_iter, tol=tol)
+    from . import _lib
+    return _lib.coords_invert_host(map, hw, init=init, dtype=dt, max_iter=max_iter, tol=tol)
 
 
 def invert_flow(flow, init=None, max_iter=16, tol=1e-9):
@@ -461,8 +462,10 @@ def invert_raster(map, in_hw, depth=None, max_span=16, orient=0, dtype=None):
         remap(img, invert_flow_raster(flow, depth) + identity)      carries a frame forward along its flow
 
     numpy in -> numpy out (the kernel's host twin, bit-equal); device tensors in -> a device tensor; mixed map / depth is refused.
-    dtype: default the map's.  A batch [B, fH, fW, 2] (depth [B, fH, fW] or None) gives [B, H, W, 2]: one call per map into the
-    slices of one output.  Bit-equal from run to run.  No autograd: an operand that requires grad (with grad mode on) is refused."""
+    dtype: default the map's.  A batch [B, fH, fW, 2] (depth [B, fH, fW] or None) gives [B, H, W, 2] in ONE call of three launches
+    (lerf_coords_invert_raster_batched).  The batched call needs one plane of 64-bit keys PER SAMPLE -- 8 bytes per output pixel per
+    sample, B * H * W * 8 bytes allocated here for the call (a loop over the samples could reuse one plane; the single launch cannot).
+    Bit-equal from run to run.  No autograd: an operand that requires grad (with grad mode on) is refused."""
     ops_ = [t for t in (map, depth) if t is not None]
     dev = [bool(getattr(t, "is_cuda", False)) for t in ops_]
     if any(d != dev[0] for d in dev):
@@ -479,21 +482,15 @@ def invert_raster(map, in_hw, depth=None, max_span=16, orient=0, dtype=None):
         from . import ops
         a, d = map.detach(), None if depth is None else depth.detach().to(torch.float32).contiguous()
         dt = a.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
-        one, new = ops.coords_invert_raster, lambda shape: torch.empty(shape, dtype=dt, device=a.device)
+        one = ops.coords_invert_raster
     else:
         from . import _lib
         a, d = (None if t is None else np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (map, depth))
         a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
         d = None if d is None else np.ascontiguousarray(d, dtype=np.float32)
         dt = a.dtype if dtype is None else _np_dtype(dtype)
-        one, new = _lib.coords_invert_raster_host, lambda shape: np.empty(shape, dtype=dt)
-    if nd == 3:
-        return one(a, (H, W), depth=d, dtype=dt, max_span=max_span, orient=orient)
-    out = new((a.shape[0], H, W, 2))
-    keys = None
-    for n in range(a.shape[0]):                            # one workspace serves every map of the batch
-        _, keys = one(a[n], (H, W), depth=None if d is None else d[n], out=out[n], max_span=max_span, orient=orient, keys=keys, return_keys=True)
-    return out
+        one = _lib.coords_invert_raster_host
+    return one(a, (H, W), depth=d, dtype=dt, max_span=max_span, orient=orient)          # a batch: one call, B key planes
 
 
 def invert_flow_raster(flow, depth=None, max_span=16, orient=0):
@@ -518,15 +515,9 @@ def invert_flow_raster(flow, depth=None, max_span=16, orient=0):
 
 # ---------------------------------------------------------------------------------------------- differentiable twins
 def _compose_dev(outer, inner, tdt):
-    """compose on the device: one pair, or one launch per sample of a batch (outer [B, aH, aW, 2] or one shared [aH, aW, 2])"""
-    import torch
+    """compose on the device: one pair, or a batch (outer [B, aH, aW, 2] or one shared [aH, aW, 2]) in one launch"""
     from . import ops
-    if inner.ndim == 3:
-        return ops.coords_compose(outer, inner, dtype=tdt)
-    out = torch.empty(tuple(inner.shape), dtype=tdt, device=inner.device)
-    for n in range(inner.shape[0]):
-        ops.coords_compose(outer if outer.ndim == 3 else outer[n], inner[n], out=out[n])
-    return out
+    return ops.coords_compose(outer, inner, dtype=tdt)
 
 
 _CHAIN_FNS = None
@@ -540,8 +531,8 @@ def _chain_fns():
         from . import ops
 
         class _ComposeFn(torch.autograd.Function):
-            """C = compose(outer, inner); backward: ops.coords_compose_bwd in float64, one launch per sample, a shared outer map's
-            gradient summed into one buffer; each gradient cast to its operand's dtype"""
+            """C = compose(outer, inner); backward: ops.coords_compose_bwd in float64, one launch for the whole batch, a shared outer map's
+            gradient summed into one buffer by the scatter's atomics; each gradient cast to its operand's dtype"""
 
             @staticmethod
             def forward(ctx, outer, inner, tdt):
@@ -556,12 +547,7 @@ def _chain_fns():
                 g = grad.contiguous().double()
                 ga = torch.zeros(tuple(outer.shape), dtype=torch.float64, device=g.device) if need[0] else None
                 gb = torch.zeros(tuple(inner.shape), dtype=torch.float64, device=g.device) if need[1] else None
-                if inner.ndim == 3:
-                    ops.coords_compose_bwd(outer, inner, g, ga, gb, need)
-                else:
-                    for n in range(inner.shape[0]):
-                        ops.coords_compose_bwd(outer if outer.ndim == 3 else outer[n], inner[n], g[n],
-                                               ga if ga is None or outer.ndim == 3 else ga[n], None if gb is None else gb[n], need)
+                ops.coords_compose_bwd(outer, inner, g, ga, gb, need)
                 return None if ga is None else ga.to(outer.dtype), None if gb is None else gb.to(inner.dtype), None
 
         class _InvertFn(torch.autograd.Function):
@@ -580,11 +566,7 @@ def _chain_fns():
                 map, out = ctx.saved_tensors
                 g = grad.contiguous().double()
                 gf = torch.zeros(tuple(map.shape), dtype=torch.float64, device=g.device)
-                if map.ndim == 3:
-                    ops.coords_invert_bwd(map, out, g, gf)
-                else:
-                    for n in range(map.shape[0]):
-                        ops.coords_invert_bwd(map[n], out[n], g[n], gf[n])
+                ops.coords_invert_bwd(map, out, g, gf)
                 return gf.to(map.dtype), None, None, None, None, None
 
         _CHAIN_FNS = (_ComposeFn, _InvertFn)
@@ -608,7 +590,8 @@ def compose_torch(outer, inner, dtype=None):
     inner map's is J^T g with the clip's gradient that of torch.clamp (it passes on the border, blocks outside) and the cell held
     constant at integer positions.  Floating-point device tensors only; dtype: C's, default the inner map's; each gradient is
     computed in float64 and cast to its operand's dtype.  A batch: inner [B, H, W, 2] with outer [B, aH, aW, 2] or one shared
-    [aH, aW, 2] (its gradient is the sum over the samples) -- one launch per sample.  compose_torch(phi, phi) returns the sum of
+    [aH, aW, 2] (its gradient is the sum over the samples) -- ONE launch forward and one backward, whatever B
+    (lerf_coords_compose_batched, lerf_coords_compose_bwd_batched).  compose_torch(phi, phi) returns the sum of
     both gradients to phi.  The differentiable path needs an outer map of at least 2 x 2.  Once differentiable."""
     import torch
     a, b = _device_map(outer, "compose_torch: outer"), _device_map(inner, "compose_torch: inner")
@@ -629,7 +612,8 @@ def invert_torch(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
     does not require grad); a map that requires grad stays in the graph through lerf_coords_invert_bwd, the implicit-function
     gradient of map(G[q]) = q at the inverse returned: the bilinear scatter of -J^-T g.  Entries of the inverse that are NaN, cells
     with a NaN corner and folded cells contribute nothing.  init is a constant (no gradient), as are max_iter and tol.
-    Floating-point device tensors only; a batch [B, fH, fW, 2] (init [B, H, W, 2]) runs one launch per map.  The gradient is
+    Floating-point device tensors only; a batch [B, fH, fW, 2] (init [B, H, W, 2]) runs ONE launch forward and one backward
+    (lerf_coords_invert_batched, lerf_coords_invert_bwd_batched).  The gradient is
     computed in float64 and cast to the map's dtype.  Once differentiable."""
     import torch
     a = _device_map(map, "invert_torch: map")

@@ -9,6 +9,9 @@
 //   OnDevice{stream}   launches entry_kernel<OP>: block 64 x 4 (4 waves, one row of 64 entries each, so a wave's stores are 64
 //                      consecutive entries of a row), grid (ceil(oW / 64), ceil(oH / 4), sets), the (i, j) guard, blockIdx.z = the set
 //   OnHost{}           the plain s, i, j loop over host pointers
+// A BATCH is the same launch with sets > 1: every chained operation (mesh, compose, invert, the two adjoints, the three passes of the
+// rasteriser, the two passes of the mesh adjoint) takes one set stride per operand, set s works on base + s * set_stride, and the
+// single-map entry points are n_sets = 1 of the same code.  The set is blockIdx.z, so the offsets are scalar.
 // and every operation is ONE function template over the runner (coords::build, mesh, compose, ...): the argument checks, the dtype and
 // model dispatch, run(Op{...}, oH, oW[, sets]).  The C entry points lerf_coords_X / lerf_coords_X_host are that template with one
 // runner or the other, so the device and the host twin cannot drift apart: they agree bit for bit by construction (the two
@@ -57,7 +60,9 @@
 // floating point before its conversion to int (raster_axis), so keys is indexed inside [oH][oW] whatever F holds; the resolve reads
 // keys at entry (i, j) and F at the three vertices of the triangle the key names -- a key this call's raster pass wrote, t < 2 (fH - 1)
 // (fW - 1) -- and writes entry (i, j) of out.  coords_math_kernel reads x (and y, for atan2 only) and writes
-// out at element e < n alone; no argument value forms an address.
+// out at element e < n alone; no argument value forms an address.  In a batch every statement above holds inside set s of the operand, base + s * set_stride
+// with s = blockIdx.z < n_sets: the host has checked that a set's extent lies inside its stride (or that the stride is 0 for an operand
+// that may be shared), so set s ends before set s + 1 begins.
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
 
@@ -89,7 +94,15 @@ struct MapReader {
     const T* m;
     int64_t stride;
     LERF_HD Point operator()(int r, int c) const { return load_entry(m, stride, r, c); }
+    LERF_HD MapReader set(int s, int64_t set_stride) const;      // the reader of set s
 };
+
+// Operands of a batch: set s of an operand lies at base + s * set_stride elements; s is blockIdx.z on the device, so the offset is
+// wave-uniform (scalar registers), and a single-map call is n_sets = 1 with every set stride 0.  A set stride of 0 shares the operand.
+// s is never negative: multiplied as unsigned 32 x 64 bits, which spares the scalar unit the sign extension's multiply and add.
+LERF_HD inline int64_t set_offset(int s, int64_t set_stride) { return (int64_t)((uint64_t)(uint32_t)s * (uint64_t)set_stride); }
+template <typename T>
+LERF_HD inline MapReader<T> MapReader<T>::set(int s, int64_t set_stride) const { return {m + set_offset(s, set_stride), stride}; }
 
 // the scatter of the two adjoints: grad [h][w][2] dense float64.  Device: two float64 atomicAdd per tap into global memory -- equal
 // from run to run up to the rounding of a reordered sum, like the image and hyper gradients of lerf_remap_bwd.  Host: a plain add.
@@ -143,8 +156,10 @@ struct MeshOp {
     TO* out;
     int64_t stride;
     int i0, j0;
-    LERF_HD void operator()(int i, int j, int) const {
-        store_entry(out, stride, i, j, mesh_point<INTERP>(ctrl, gh, gw, full_h, full_w, i0 + i, j0 + j));
+    int64_t ctrl_set, out_set;
+    LERF_HD void operator()(int i, int j, int s) const {
+        store_entry(out + set_offset(s, out_set), stride, i, j,
+                    mesh_point<INTERP>(ctrl + set_offset(s, ctrl_set), gh, gw, full_h, full_w, i0 + i, j0 + j));
     }
 };
 
@@ -156,9 +171,10 @@ struct ComposeOp {
     MapReader<TB> B;
     TO* out;
     int64_t stride;
-    LERF_HD void operator()(int i, int j, int) const {
-        const Point q = B(i, j);
-        store_entry(out, stride, i, j, compose_point(q.r, q.c, aH, aW, A));
+    int64_t a_set, b_set, out_set;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const Point q = B.set(s, b_set)(i, j);
+        store_entry(out + set_offset(s, out_set), stride, i, j, compose_point(q.r, q.c, aH, aW, A.set(s, a_set)));
     }
 };
 
@@ -175,10 +191,12 @@ struct InvertOp {
     int64_t stride;
     int i0, j0, max_iter;
     double tol;
-    LERF_HD void operator()(int i, int j, int) const {
+    int64_t f_set, init_set, out_set;
+    LERF_HD void operator()(int i, int j, int s) const {
         const double q_r = (double)(i0 + i), q_c = (double)(j0 + j);
-        const Point u0 = init.m ? init(i, j) : invert_start(q_r, q_c, fH, fW, F);
-        store_entry(out, stride, i, j, invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, F));
+        const MapReader<TF> Fs = F.set(s, f_set);
+        const Point u0 = init.m ? init.set(s, init_set)(i, j) : invert_start(q_r, q_c, fH, fW, Fs);
+        store_entry(out + set_offset(s, out_set), stride, i, j, invert_point(q_r, q_c, fH, fW, u0, max_iter, tol, Fs));
     }
 };
 
@@ -193,13 +211,16 @@ struct ComposeBwdOp {
     MapReader<TB> B;
     MapReader<double> gout;
     double *gA, *gB;
-    LERF_HD void operator()(int i, int j, int) const {
+    int64_t a_set, b_set, gout_set, ga_set, gb_set;
+    LERF_HD void operator()(int i, int j, int s) const {
 #pragma clang fp contract(off)
-        const Point q = B(i, j);
-        const Point d = compose_bwd_point(q.r, q.c, gout(i, j), aH, aW, gA != nullptr, gB != nullptr, A, Add2{gA, aW});
+        const Point q = B.set(s, b_set)(i, j);
+        const Point d = compose_bwd_point(q.r, q.c, gout.set(s, gout_set)(i, j), aH, aW, gA != nullptr, gB != nullptr, A.set(s, a_set),
+                                          Add2{gA + set_offset(s, ga_set), aW});
         if (gB) {
-            const Point v = load_entry(gB, gout.stride, i, j);
-            store_entry(gB, gout.stride, i, j, Point{v.r + d.r, v.c + d.c});
+            double* gb = gB + set_offset(s, gb_set);
+            const Point v = load_entry(gb, gout.stride, i, j);
+            store_entry(gb, gout.stride, i, j, Point{v.r + d.r, v.c + d.c});
         }
     }
 };
@@ -213,9 +234,10 @@ struct InvertBwdOp {
     MapReader<TG> G;
     MapReader<double> gout;
     double* gF;
-    LERF_HD void operator()(int i, int j, int) const {
-        const Point u = G(i, j);
-        invert_bwd_point(u.r, u.c, gout(i, j), fH, fW, F, Add2{gF, fW});
+    int64_t f_set, g_set, gout_set, gf_set;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const Point u = G.set(s, g_set)(i, j);
+        invert_bwd_point(u.r, u.c, gout.set(s, gout_set)(i, j), fH, fW, F.set(s, f_set), Add2{gF + set_offset(s, gf_set), fW});
     }
 };
 
@@ -232,16 +254,18 @@ struct RasterOp {
     int fW;
     const float* depth;
     int orient, max_span, i0, j0, oH, oW;
+    int64_t f_set, depth_set;
     template <typename MINKEY>
-    LERF_HD void operator()(int i, int j, MINKEY minkey) const {
-        raster_cell(i, j, fW, F, depth, orient, max_span, i0, j0, oH, oW, minkey);
+    LERF_HD void operator()(int i, int j, int s, MINKEY minkey) const {
+        raster_cell(i, j, fW, F.set(s, f_set), depth ? depth + set_offset(s, depth_set) : nullptr, orient, max_span, i0, j0, oH, oW, minkey);
     }
 };
 
 struct KeyFillOp {
     uint64_t* keys;
     int oW;
-    LERF_HD void operator()(int i, int j, int) const { keys[(int64_t)i * oW + j] = kNoKey; }
+    int64_t keys_set;
+    LERF_HD void operator()(int i, int j, int s) const { keys[set_offset(s, keys_set) + (int64_t)i * oW + j] = kNoKey; }
 };
 
 template <typename TF, typename TO>
@@ -252,8 +276,10 @@ struct ResolveOp {
     TO* out;
     int64_t stride;
     int i0, j0, oW;
-    LERF_HD void operator()(int i, int j, int) const {
-        store_entry(out, stride, i, j, raster_resolve(keys[(int64_t)i * oW + j], fW, (double)(i0 + i), (double)(j0 + j), F));
+    int64_t f_set, keys_set, out_set;
+    LERF_HD void operator()(int i, int j, int s) const {
+        store_entry(out + set_offset(s, out_set), stride, i, j,
+                    raster_resolve(keys[set_offset(s, keys_set) + (int64_t)i * oW + j], fW, (double)(i0 + i), (double)(j0 + j), F.set(s, f_set)));
     }
 };
 
@@ -287,8 +313,9 @@ struct OnHost {
     }
 };
 
-// The two runners of a SCATTER operation op(i, j, minkey) -- one call per cell (i, j) of [cH][cW], which hands (index, key) pairs to
-// minkey: keys[index] = min(keys[index], key).  The runner owns the combiner, the operation owns the arithmetic:
+// The two runners of a SCATTER operation op(i, j, s, minkey) -- one call per cell (i, j) of [cH][cW] of set s, which hands (index, key)
+// pairs to minkey: keys[index] = min(keys[index], key), keys = the plane of set s (keys + s * keys_set).  The runner owns the combiner,
+// the operation owns the arithmetic:
 //   ScatterOnDevice{stream}   cell_kernel<OP>: the block and grid of entry_kernel, one thread per cell; KeyMinDevice = one 64-bit
 //                             unsigned atomic min into global memory (a single hardware instruction on gfx950, no return value).  A
 //                             plain load first: keys only decrease, so a key that is already smaller stays smaller and the atomic
@@ -310,38 +337,41 @@ struct KeyMinHost {
 };
 
 template <typename OP>
-__global__ void __launch_bounds__(CB_COLS * CB_ROWS) cell_kernel(const OP op, int cH, int cW, uint64_t* keys) {
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS) cell_kernel(const OP op, int cH, int cW, uint64_t* keys, int64_t keys_set) {
     const int j = blockIdx.x * CB_COLS + threadIdx.x, i = blockIdx.y * CB_ROWS + threadIdx.y;
     if (i >= cH || j >= cW) return;
-    op(i, j, KeyMinDevice{keys});
+    op(i, j, (int)blockIdx.z, KeyMinDevice{keys + (int64_t)blockIdx.z * keys_set});
 }
 
 struct ScatterOnDevice {
     hipStream_t stream;
     template <typename OP>
-    int operator()(const OP& op, int cH, int cW, uint64_t* keys) const {
+    int operator()(const OP& op, int cH, int cW, uint64_t* keys, int sets = 1, int64_t keys_set = 0) const {
         clear_stale_error();
-        const dim3 grid((cW + CB_COLS - 1) / CB_COLS, (cH + CB_ROWS - 1) / CB_ROWS);
-        hipLaunchKernelGGL(cell_kernel<OP>, grid, dim3(CB_COLS, CB_ROWS), 0, stream, op, cH, cW, keys);
+        const dim3 grid((cW + CB_COLS - 1) / CB_COLS, (cH + CB_ROWS - 1) / CB_ROWS, sets);
+        hipLaunchKernelGGL(cell_kernel<OP>, grid, dim3(CB_COLS, CB_ROWS), 0, stream, op, cH, cW, keys, keys_set);
         return launch_status();
     }
 };
 
 struct ScatterOnHost {
     template <typename OP>
-    int operator()(const OP& op, int cH, int cW, uint64_t* keys) const {
-        for (int i = 0; i < cH; ++i)
-            for (int j = 0; j < cW; ++j) op(i, j, KeyMinHost{keys});
+    int operator()(const OP& op, int cH, int cW, uint64_t* keys, int sets = 1, int64_t keys_set = 0) const {
+        for (int s = 0; s < sets; ++s)
+            for (int i = 0; i < cH; ++i)
+                for (int j = 0; j < cW; ++j) op(i, j, s, KeyMinHost{keys + set_offset(s, keys_set)});
         return LERF_OK;
     }
 };
 
-// pass 1 of the adjoint: grid (ceil(oW / 64), gh), block (64, 4)
+// pass 1 of the adjoint: grid (ceil(oW / 64), gh, sets), block (64, 4); set s reads gmap + s * gmap_set (in entries) and owns tmp [s][gh][oW]
 template <int INTERP>
 __global__ void __launch_bounds__(CB_COLS * CB_ROWS)
-coords_mesh_bwd_rows_kernel(const double2* __restrict__ gmap, int oH, int oW, int gh, double2* __restrict__ tmp) {
+coords_mesh_bwd_rows_kernel(const double2* __restrict__ gmap, int oH, int oW, int gh, double2* __restrict__ tmp, int64_t gmap_set) {
 #pragma clang fp contract(off)
     __shared__ double2 part[CB_ROWS][CB_COLS];
+    gmap += (int64_t)blockIdx.z * gmap_set;
+    tmp += (int64_t)blockIdx.z * gh * oW;
     const int a = blockIdx.y, j = blockIdx.x * CB_COLS + threadIdx.x, w = threadIdx.y;
     int lo, hi;
     mesh_reach<INTERP>(a, oH, gh, &lo, &hi);
@@ -367,11 +397,13 @@ coords_mesh_bwd_rows_kernel(const double2* __restrict__ gmap, int oH, int oW, in
     }
 }
 
-// pass 2: grid (gw, gh), block 64 = one wave per vertex
+// pass 2: grid (gw, gh, sets), block 64 = one wave per vertex; set s reads tmp [s][gh][oW] and adds into gctrl + s * gctrl_set (in entries)
 template <int INTERP>
 __global__ void __launch_bounds__(64)
-coords_mesh_bwd_cols_kernel(const double2* __restrict__ tmp, int oW, int gw, double2* __restrict__ gctrl) {
+coords_mesh_bwd_cols_kernel(const double2* __restrict__ tmp, int oW, int gw, double2* __restrict__ gctrl, int64_t gctrl_set) {
 #pragma clang fp contract(off)
+    tmp += (int64_t)blockIdx.z * gridDim.y * oW;
+    gctrl += (int64_t)blockIdx.z * gctrl_set;
     const int b = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
     int lo, hi;
     mesh_reach<INTERP>(b, oW, gw, &lo, &hi);
@@ -602,6 +634,46 @@ inline int build_bwd_args(int model, const double* params, int n_sets, int n_par
     return LERF_OK;
 }
 
+// ---- the sets of a batched call.  One operand of it: set s at p + s * set_stride elements of `el` bytes, each set `span` elements from
+// its first to one past its last; pairs: the elements are (row, col) pairs (maps, gradients), so the stride is even; share: a set
+// stride of 0 (one operand for all sets) is allowed.  A null operand (init, depth, a skipped gradient) passes.
+struct SetOperand {
+    const void* p;
+    size_t el;
+    int64_t span, set_stride;
+    bool pairs, share;
+};
+inline int64_t map_span(int64_t stride, int h, int w) { return (int64_t)(h - 1) * stride + 2 * (int64_t)w; }
+inline SetOperand map_sets(const void* p, int dt, int64_t stride, int h, int w, int64_t set_stride, bool share) {
+    return {p, entry_bytes(dt) / 2, map_span(stride, h, w), set_stride, true, share};
+}
+inline SetOperand dense_sets(const void* p, int h, int w, int64_t set_stride, bool share) {
+    return {p, sizeof(double), 2 * (int64_t)h * w, set_stride, true, share};
+}
+inline SetOperand plane_sets(const void* p, size_t el, int h, int w, int64_t set_stride, bool share) {
+    return {p, el, (int64_t)h * w, set_stride, false, share};
+}
+
+// n_sets and every operand's set stride: LERF_EUNSUPPORTED beyond the grid's z, LERF_EINVAL for the rest
+template <size_t N>
+inline int sets_args(int n_sets, const SetOperand (&ops)[N]) {
+    if (n_sets < 1) return LERF_EINVAL;
+    if (n_sets > 65535) return LERF_EUNSUPPORTED;
+    for (const SetOperand& o : ops) {
+        if (!o.p) continue;
+        if (o.set_stride < 0 || (o.pairs && (o.set_stride & 1))) return LERF_EINVAL;
+        if (n_sets > 1 && o.set_stride < o.span && !(o.share && o.set_stride == 0)) return LERF_EINVAL;
+    }
+    return LERF_OK;
+}
+
+// the bytes of an operand over the whole batch (first element of set 0 to one past the last of the last set) intersect another's
+inline bool sets_overlap(int n_sets, const SetOperand& x, const SetOperand& y) {
+    if (!x.p || !y.p) return false;
+    return bytes_overlap(x.p, (size_t)((int64_t)(n_sets - 1) * x.set_stride + x.span) * x.el, y.p,
+                         (size_t)((int64_t)(n_sets - 1) * y.set_stride + y.span) * y.el);
+}
+
 // run F with MODEL = the compile-time constant of a model code the argument checks have accepted
 #define LERF_COORDS_MODEL(code, MODEL, ...)                                                                  \
     do {                                                                                                     \
@@ -645,70 +717,130 @@ int build_dev(RUN run, int model, const double* params, int n_sets, int n_params
         return run(BuildDevOp<MODEL, TO>{params, (TO*)out, set_stride, stride, i0, j0}, oH, oW, n_sets)));
 }
 
+// Each of the chained operations below takes n_sets and one set stride per operand; the single-map entry points leave them at 1 and 0.
+// The checks: sets_args (n_sets, the strides), the single-map *_args on set 0 (every set has its shapes and strides, and an even
+// stride keeps set 0's alignment), then the single-map form's overlap pairs over the whole batch.
 template <typename RUN>
 int mesh(RUN run, const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
-         int64_t stride, int oH, int oW, int i0, int j0) {
-    const int rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, stride, oH, oW, i0, j0);
+         int64_t stride, int oH, int oW, int i0, int j0, int n_sets = 1, int64_t ctrl_set = 0, int64_t out_set = 0) {
+    if (!float_dtype(ctrl_dtype) || !float_dtype(out_dtype) || gh < 2 || gw < 2 || oH < 1 || oW < 1) return LERF_EINVAL;
+    const SetOperand sets[2] = {{ctrl, entry_bytes(ctrl_dtype) / 2, 2 * (int64_t)gh * gw, ctrl_set, true, false},
+                                map_sets(out, out_dtype, stride, oH, oW, out_set, false)};
+    int rc = sets_args(n_sets, sets);
+    if (rc == LERF_OK) rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, stride, oH, oW, i0, j0);
     if (rc != LERF_OK) return rc;
+    if (n_sets > 1 && sets_overlap(n_sets, sets[0], sets[1])) return LERF_EINVAL;
     LERF_COORDS_DT(ctrl_dtype, TC, LERF_COORDS_DT(out_dtype, TO, {
         if (interp == LERF_MESH_BILINEAR)
-            return run(MeshOp<LERF_MESH_BILINEAR, TC, TO>{(const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, stride, i0, j0}, oH, oW);
-        return run(MeshOp<LERF_MESH_BICUBIC, TC, TO>{(const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, stride, i0, j0}, oH, oW);
+            return run(MeshOp<LERF_MESH_BILINEAR, TC, TO>{(const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, stride, i0, j0, ctrl_set, out_set},
+                       oH, oW, n_sets);
+        return run(MeshOp<LERF_MESH_BICUBIC, TC, TO>{(const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, stride, i0, j0, ctrl_set, out_set},
+                   oH, oW, n_sets);
     }));
 }
 
 template <typename RUN>
 int compose(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride, void* out,
-            int out_dtype, int64_t o_stride, int oH, int oW) {
-    const int rc = compose_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, out, out_dtype, o_stride, oH, oW);
+            int out_dtype, int64_t o_stride, int oH, int oW, int n_sets = 1, int64_t a_set = 0, int64_t b_set = 0, int64_t out_set = 0) {
+    if (!float_dtype(a_dtype) || !float_dtype(b_dtype) || !float_dtype(out_dtype) || aH < 1 || aW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
+    const SetOperand sets[3] = {map_sets(a, a_dtype, a_stride, aH, aW, a_set, true), map_sets(b, b_dtype, b_stride, oH, oW, b_set, false),
+                                map_sets(out, out_dtype, o_stride, oH, oW, out_set, false)};
+    int rc = sets_args(n_sets, sets);
+    if (rc == LERF_OK) rc = compose_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, out, out_dtype, o_stride, oH, oW);
     if (rc != LERF_OK) return rc;
+    const bool in_place = out == b && out_dtype == b_dtype && o_stride == b_stride && out_set == b_set;
+    if (n_sets > 1 && (sets_overlap(n_sets, sets[2], sets[0]) || (!in_place && sets_overlap(n_sets, sets[2], sets[1])))) return LERF_EINVAL;
     LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB, LERF_COORDS_DT(out_dtype, TO,
-        return run(ComposeOp<TA, TB, TO>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, (TO*)out, o_stride}, oH, oW))));
+        return run(ComposeOp<TA, TB, TO>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, (TO*)out, o_stride, a_set, b_set, out_set},
+                   oH, oW, n_sets))));
 }
 
 template <typename RUN>
 int invert(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* init, int init_dtype, int64_t i_stride,
-           void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol) {
-    const int rc = invert_args(f, f_dtype, f_stride, fH, fW, init, init_dtype, i_stride, out, out_dtype, o_stride, oH, oW, i0, j0, max_iter, tol);
+           void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol, int n_sets = 1,
+           int64_t f_set = 0, int64_t init_set = 0, int64_t out_set = 0) {
+    if (!float_dtype(f_dtype) || !float_dtype(out_dtype) || (init && !float_dtype(init_dtype)) || fH < 1 || fW < 1 || oH < 1 || oW < 1)
+        return LERF_EINVAL;
+    const SetOperand sets[3] = {map_sets(f, f_dtype, f_stride, fH, fW, f_set, true), map_sets(init, init_dtype, i_stride, oH, oW, init_set, true),
+                                map_sets(out, out_dtype, o_stride, oH, oW, out_set, false)};
+    int rc = sets_args(n_sets, sets);
+    if (rc == LERF_OK)
+        rc = invert_args(f, f_dtype, f_stride, fH, fW, init, init_dtype, i_stride, out, out_dtype, o_stride, oH, oW, i0, j0, max_iter, tol);
     if (rc != LERF_OK) return rc;
+    if (n_sets > 1 && (sets_overlap(n_sets, sets[2], sets[0]) || sets_overlap(n_sets, sets[2], sets[1]))) return LERF_EINVAL;
     if (!init) init_dtype = LERF_F64;                     // a null init is never read: one instantiation serves
     LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(init_dtype, TI, LERF_COORDS_DT(out_dtype, TO,
-        return run(InvertOp<TF, TI, TO>{{(const TF*)f, f_stride}, fH, fW, {(const TI*)init, i_stride}, (TO*)out, o_stride, i0, j0, max_iter, tol},
-                   oH, oW))));
+        return run(InvertOp<TF, TI, TO>{{(const TF*)f, f_stride}, fH, fW, {(const TI*)init, i_stride}, (TO*)out, o_stride, i0, j0, max_iter, tol,
+                                        f_set, init_set, out_set},
+                   oH, oW, n_sets))));
 }
 
 // fill, raster, resolve: three launches in stream order (the host: three loops), no sync, no allocation
 template <typename RUN, typename SCATTER>
 int invert_raster(RUN run, SCATTER scatter, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const float* depth, void* out,
-                  int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys) {
-    int rc = invert_raster_args(f, f_dtype, f_stride, fH, fW, depth, out, out_dtype, o_stride, oH, oW, i0, j0, max_span, orient, keys);
+                  int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, int n_sets = 1,
+                  int64_t f_set = 0, int64_t depth_set = 0, int64_t out_set = 0, int64_t keys_set = 0) {
+    if (!float_dtype(f_dtype) || !float_dtype(out_dtype) || fH < 1 || fW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
+    const SetOperand sets[4] = {map_sets(f, f_dtype, f_stride, fH, fW, f_set, true), plane_sets(depth, sizeof(float), fH, fW, depth_set, true),
+                                map_sets(out, out_dtype, o_stride, oH, oW, out_set, false),
+                                plane_sets(keys, sizeof(uint64_t), oH, oW, keys_set, false)};
+    int rc = sets_args(n_sets, sets);
+    if (rc == LERF_OK)
+        rc = invert_raster_args(f, f_dtype, f_stride, fH, fW, depth, out, out_dtype, o_stride, oH, oW, i0, j0, max_span, orient, keys);
     if (rc != LERF_OK) return rc;
-    rc = run(KeyFillOp{keys, oW}, oH, oW);
+    if (n_sets > 1 && (sets_overlap(n_sets, sets[2], sets[0]) || sets_overlap(n_sets, sets[3], sets[0]) || sets_overlap(n_sets, sets[2], sets[3]) ||
+                       sets_overlap(n_sets, sets[2], sets[1]) || sets_overlap(n_sets, sets[3], sets[1])))
+        return LERF_EINVAL;
+    rc = run(KeyFillOp{keys, oW, keys_set}, oH, oW, n_sets);
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(f_dtype, TF,
-        rc = scatter(RasterOp<TF>{{(const TF*)f, f_stride}, fW, depth, orient, max_span, i0, j0, oH, oW}, fH - 1, fW - 1, keys));
+        rc = scatter(RasterOp<TF>{{(const TF*)f, f_stride}, fW, depth, orient, max_span, i0, j0, oH, oW, f_set, depth_set}, fH - 1, fW - 1, keys,
+                     n_sets, keys_set));
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(out_dtype, TO,
-        return run(ResolveOp<TF, TO>{{(const TF*)f, f_stride}, fW, keys, (TO*)out, o_stride, i0, j0, oW}, oH, oW)));
+        return run(ResolveOp<TF, TO>{{(const TF*)f, f_stride}, fW, keys, (TO*)out, o_stride, i0, j0, oW, f_set, keys_set, out_set}, oH, oW, n_sets)));
 }
 
 template <typename RUN>
 int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
-                const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
-    const int rc = compose_bwd_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, grad_out, oH, oW, grad_a, grad_b);
+                const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets = 1, int64_t a_set = 0, int64_t b_set = 0,
+                int64_t gout_set = 0, int64_t ga_set = 0, int64_t gb_set = 0) {
+    if (!float_dtype(a_dtype) || !float_dtype(b_dtype) || aH < 1 || aW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
+    const SetOperand sets[5] = {map_sets(a, a_dtype, a_stride, aH, aW, a_set, true), map_sets(b, b_dtype, b_stride, oH, oW, b_set, false),
+                                dense_sets(grad_out, oH, oW, gout_set, false), dense_sets(grad_a, aH, aW, ga_set, true),
+                                dense_sets(grad_b, oH, oW, gb_set, false)};
+    int rc = sets_args(n_sets, sets);
+    if (rc == LERF_OK) rc = compose_bwd_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, grad_out, oH, oW, grad_a, grad_b);
     if (rc != LERF_OK) return rc;
+    if (n_sets > 1) {
+        if (grad_a && ga_set == 0 && a_set != 0) return LERF_EINVAL;          // one gradient buffer belongs to ONE shared outer map
+        for (int k = 3; k < 5; ++k)
+            if (sets_overlap(n_sets, sets[k], sets[0]) || sets_overlap(n_sets, sets[k], sets[1]) || sets_overlap(n_sets, sets[k], sets[2]))
+                return LERF_EINVAL;
+        if (sets_overlap(n_sets, sets[3], sets[4])) return LERF_EINVAL;
+    }
     LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB,
-        return run(ComposeBwdOp<TA, TB>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, {grad_out, 2 * (int64_t)oW}, grad_a, grad_b},
-                   oH, oW)));
+        return run(ComposeBwdOp<TA, TB>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, {grad_out, 2 * (int64_t)oW}, grad_a, grad_b,
+                                        a_set, b_set, gout_set, ga_set, gb_set},
+                   oH, oW, n_sets)));
 }
 
 template <typename RUN>
 int invert_bwd(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_stride,
-               const double* grad_out, int oH, int oW, double* grad_f) {
-    const int rc = invert_bwd_args(f, f_dtype, f_stride, fH, fW, g, g_dtype, g_stride, grad_out, oH, oW, grad_f);
+               const double* grad_out, int oH, int oW, double* grad_f, int n_sets = 1, int64_t f_set = 0, int64_t g_set = 0, int64_t gout_set = 0,
+               int64_t gf_set = 0) {
+    if (!float_dtype(f_dtype) || !float_dtype(g_dtype) || fH < 1 || fW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
+    const SetOperand sets[4] = {map_sets(f, f_dtype, f_stride, fH, fW, f_set, true), map_sets(g, g_dtype, g_stride, oH, oW, g_set, false),
+                                dense_sets(grad_out, oH, oW, gout_set, false), dense_sets(grad_f, fH, fW, gf_set, false)};
+    int rc = sets_args(n_sets, sets);
+    if (rc == LERF_OK) rc = invert_bwd_args(f, f_dtype, f_stride, fH, fW, g, g_dtype, g_stride, grad_out, oH, oW, grad_f);
     if (rc != LERF_OK) return rc;
+    if (n_sets > 1 && (sets_overlap(n_sets, sets[3], sets[0]) || sets_overlap(n_sets, sets[3], sets[1]) || sets_overlap(n_sets, sets[3], sets[2])))
+        return LERF_EINVAL;
     LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(g_dtype, TG,
-        return run(InvertBwdOp<TF, TG>{{(const TF*)f, f_stride}, fH, fW, {(const TG*)g, g_stride}, {grad_out, 2 * (int64_t)oW}, grad_f}, oH, oW)));
+        return run(InvertBwdOp<TF, TG>{{(const TF*)f, f_stride}, fH, fW, {(const TG*)g, g_stride}, {grad_out, 2 * (int64_t)oW}, grad_f, f_set, g_set,
+                                       gout_set, gf_set},
+                   oH, oW, n_sets)));
 }
 
 }  // namespace coords
@@ -806,26 +938,139 @@ size_t lerf_coords_mesh_bwd_workspace_bytes(int gh, int gw, int oH, int oW) {
     return (size_t)gh * (size_t)oW * 2 * sizeof(double);
 }
 
-int lerf_coords_mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
-                         size_t workspace_bytes, void* stream) {
+static int mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace, size_t workspace_bytes,
+                    int n_sets, int64_t gmap_set, int64_t gctrl_set, void* stream) {
     if (!grad_map || !grad_ctrl || !workspace || oH < 1 || oW < 1 || gh < 2 || gw < 2) return LERF_EINVAL;
+    const SetOperand sets[2] = {dense_sets(grad_map, oH, oW, gmap_set, false), dense_sets(grad_ctrl, gh, gw, gctrl_set, false)};
+    const int rc = sets_args(n_sets, sets);
+    if (rc != LERF_OK) return rc;
     if (interp != LERF_MESH_BILINEAR && interp != LERF_MESH_BICUBIC) return LERF_EINVAL;
     if ((size_t)(uintptr_t)grad_map % 16 != 0 || (size_t)(uintptr_t)grad_ctrl % 16 != 0 || (size_t)(uintptr_t)workspace % 16 != 0) return LERF_EINVAL;
-    if (workspace_bytes < lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW) || gh > 65535) return LERF_EINVAL;
+    const size_t need = (size_t)n_sets * lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW);
+    if (workspace_bytes < need || gh > 65535) return LERF_EINVAL;
+    if (n_sets > 1) {
+        const SetOperand ws = {workspace, 1, (int64_t)need, 0, false, true};
+        if (sets_overlap(n_sets, sets[1], sets[0]) || sets_overlap(n_sets, ws, sets[0]) || sets_overlap(n_sets, ws, sets[1])) return LERF_EINVAL;
+    }
     clear_stale_error();
     hipStream_t st = (hipStream_t)stream;
-    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + CB_COLS - 1) / CB_COLS, gh), b2(64), g2(gw, gh);
+    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + CB_COLS - 1) / CB_COLS, gh, n_sets), b2(64), g2(gw, gh, n_sets);
     const double2* gm = reinterpret_cast<const double2*>(grad_map);
     double2* tmp = reinterpret_cast<double2*>(workspace);
     double2* gc = reinterpret_cast<double2*>(grad_ctrl);
+    const int64_t gm_set = gmap_set / 2, gc_set = gctrl_set / 2;              // in entries
     if (interp == LERF_MESH_BILINEAR) {
-        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BILINEAR>), g1, b1, 0, st, gm, oH, oW, gh, tmp);
-        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BILINEAR>), g2, b2, 0, st, tmp, oW, gw, gc);
+        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BILINEAR>), g1, b1, 0, st, gm, oH, oW, gh, tmp, gm_set);
+        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BILINEAR>), g2, b2, 0, st, tmp, oW, gw, gc, gc_set);
     } else {
-        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BICUBIC>), g1, b1, 0, st, gm, oH, oW, gh, tmp);
-        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BICUBIC>), g2, b2, 0, st, tmp, oW, gw, gc);
+        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BICUBIC>), g1, b1, 0, st, gm, oH, oW, gh, tmp, gm_set);
+        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BICUBIC>), g2, b2, 0, st, tmp, oW, gw, gc, gc_set);
     }
     return launch_status();
+}
+
+int lerf_coords_mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return mesh_bwd(grad_map, oH, oW, interp, gh, gw, grad_ctrl, workspace, workspace_bytes, 1, 0, 0, stream);
+}
+
+int lerf_coords_mesh_bwd_batched(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
+                                 size_t workspace_bytes, int n_sets, int64_t grad_map_set_stride, int64_t grad_ctrl_set_stride, void* stream) {
+    return mesh_bwd(grad_map, oH, oW, interp, gh, gw, grad_ctrl, workspace, workspace_bytes, n_sets, grad_map_set_stride, grad_ctrl_set_stride,
+                    stream);
+}
+
+// the batched forms: the same templates with n_sets and the set strides passed on
+int lerf_coords_mesh_batched(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+                             int64_t row_stride, int oH, int oW, int i0, int j0, int n_sets, int64_t ctrl_set_stride, int64_t out_set_stride,
+                             void* stream) {
+    return mesh(OnDevice{(hipStream_t)stream}, ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0, n_sets,
+                ctrl_set_stride, out_set_stride);
+}
+
+int lerf_coords_mesh_batched_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+                                  int64_t row_stride, int oH, int oW, int i0, int j0, int n_sets, int64_t ctrl_set_stride,
+                                  int64_t out_set_stride) {
+    return mesh(OnHost{}, ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0, n_sets, ctrl_set_stride,
+                out_set_stride);
+}
+
+int lerf_coords_compose_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                int64_t b_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int n_sets,
+                                int64_t a_set_stride, int64_t b_set_stride, int64_t out_set_stride, void* stream) {
+    return compose(OnDevice{(hipStream_t)stream}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW,
+                   n_sets, a_set_stride, b_set_stride, out_set_stride);
+}
+
+int lerf_coords_compose_batched_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                     int64_t b_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int n_sets,
+                                     int64_t a_set_stride, int64_t b_set_stride, int64_t out_set_stride) {
+    return compose(OnHost{}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW, n_sets,
+                   a_set_stride, b_set_stride, out_set_stride);
+}
+
+int lerf_coords_invert_batched(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                               int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                               int max_iter, double tol, int n_sets, int64_t f_set_stride, int64_t init_set_stride, int64_t out_set_stride,
+                               void* stream) {
+    return invert(OnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype,
+                  out_row_stride, oH, oW, i0, j0, max_iter, tol, n_sets, f_set_stride, init_set_stride, out_set_stride);
+}
+
+int lerf_coords_invert_batched_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                                    int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                                    int max_iter, double tol, int n_sets, int64_t f_set_stride, int64_t init_set_stride,
+                                    int64_t out_set_stride) {
+    return invert(OnHost{}, f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW, i0, j0,
+                  max_iter, tol, n_sets, f_set_stride, init_set_stride, out_set_stride);
+}
+
+int lerf_coords_invert_raster_batched(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out,
+                                      int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient,
+                                      uint64_t* keys, int n_sets, int64_t f_set_stride, int64_t depth_set_stride, int64_t out_set_stride,
+                                      int64_t keys_set_stride, void* stream) {
+    return invert_raster(OnDevice{(hipStream_t)stream}, ScatterOnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, depth, out,
+                         out_dtype, out_row_stride, oH, oW, i0, j0, max_span, orient, keys, n_sets, f_set_stride, depth_set_stride,
+                         out_set_stride, keys_set_stride);
+}
+
+int lerf_coords_invert_raster_batched_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out,
+                                           int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient,
+                                           uint64_t* keys, int n_sets, int64_t f_set_stride, int64_t depth_set_stride, int64_t out_set_stride,
+                                           int64_t keys_set_stride) {
+    return invert_raster(OnHost{}, ScatterOnHost{}, f, f_dtype, f_row_stride, fH, fW, depth, out, out_dtype, out_row_stride, oH, oW, i0, j0,
+                         max_span, orient, keys, n_sets, f_set_stride, depth_set_stride, out_set_stride, keys_set_stride);
+}
+
+int lerf_coords_compose_bwd_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                    int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets,
+                                    int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride, int64_t grad_a_set_stride,
+                                    int64_t grad_b_set_stride, void* stream) {
+    return compose_bwd(OnDevice{(hipStream_t)stream}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b,
+                       n_sets, a_set_stride, b_set_stride, grad_out_set_stride, grad_a_set_stride, grad_b_set_stride);
+}
+
+int lerf_coords_compose_bwd_batched_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                         int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                         int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride,
+                                         int64_t grad_a_set_stride, int64_t grad_b_set_stride) {
+    return compose_bwd(OnHost{}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b, n_sets,
+                       a_set_stride, b_set_stride, grad_out_set_stride, grad_a_set_stride, grad_b_set_stride);
+}
+
+int lerf_coords_invert_bwd_batched(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                   int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f, int n_sets,
+                                   int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride, int64_t grad_f_set_stride,
+                                   void* stream) {
+    return invert_bwd(OnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f, n_sets,
+                      f_set_stride, g_set_stride, grad_out_set_stride, grad_f_set_stride);
+}
+
+int lerf_coords_invert_bwd_batched_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                        int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f, int n_sets,
+                                        int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride, int64_t grad_f_set_stride) {
+    return invert_bwd(OnHost{}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f, n_sets, f_set_stride,
+                      g_set_stride, grad_out_set_stride, grad_f_set_stride);
 }
 
 size_t lerf_coords_build_bwd_workspace_bytes(int n_params, int n_sets, int oH, int oW) {

@@ -5,6 +5,8 @@
 // dtypes of every operand, a batch of sets, init and the gradient halves null and given, the refusals -- and lerf_coords_invert_raster_host
 // on a folded map with NaN, +-inf and 1e300 entries, tiles at a non-zero origin, max_span 1 and 64.  The host twins of the six
 // run the very functors the device runs (OnHost, ScatterOnHost in lerf_coords.hip), so this pass checks the addressing of the shared code.
+// The batched twins (lerf_coords_*_batched_host) run three sets with padded set strides, a folded set with NaN / +-inf / 1e300 entries,
+// non-zero origins and shared operands, and must equal the single-map twins set by set (batched_ops).
 // It needs no GPU and is never loaded into another process.  Exit status 0 and "ok" on the last line: no report.
 #include "lerf_hip.h"
 
@@ -158,6 +160,188 @@ static void raster_ops(int oH, int oW) {
         }
 }
 
+// The batched host twins (lerf_coords_*_batched_host) on THREE sets in exactly-sized heap buffers: the set stride of every operand is
+// larger than a set (the gap holds the sentinel -7), the maps are strided tiles at origin (3, 7), set 1 holds a folded map with NaN,
+// +-inf and 1e300 entries.  Set s must equal the single-map twin on the same operands, byte for byte, and no gap may change.
+struct Batch {
+    int dt, n, h, w;
+    int64_t stride, set;
+    std::vector<double> d;
+    std::vector<float> f;
+    Batch(int dt_, int n_, int h_, int w_, int pad = 3, int gap = 4)
+        : dt(dt_), n(n_), h(h_), w(w_), stride(2 * (int64_t)(w_ + pad)), set((h_ - 1) * 2 * (int64_t)(w_ + pad) + 2 * w_ + gap) {
+        const size_t len = (size_t)((n - 1) * set + (h - 1) * stride + 2 * w);
+        if (dt == LERF_F64) d.assign(len, -7.0);
+        else f.assign(len, -7.0f);
+    }
+    void* p(int s = 0) { return dt == LERF_F64 ? (void*)(d.data() + s * set) : (void*)(f.data() + s * set); }
+    void set_entry(int s, int i, int j, double r, double c) {
+        const size_t e = (size_t)(s * set + i * stride + 2 * j);
+        if (dt == LERF_F64) { d[e] = r; d[e + 1] = c; }
+        else { f[e] = (float)r; f[e + 1] = (float)c; }
+    }
+    // the entries of set s equal those of the single map m, and everything between the entries is the sentinel
+    bool set_is(int s, Map& m) {
+        for (int i = 0; i < h; ++i)
+            for (int k = 0; k < 2 * w; ++k) {
+                const size_t e = (size_t)(s * set + i * stride + k), q = (size_t)(i * m.stride + k);
+                if (dt == LERF_F64 ? std::memcmp(&d[e], &m.d[q], 8) : std::memcmp(&f[e], &m.f[q], 4)) return false;
+            }
+        return true;
+    }
+    bool gaps_kept() const {
+        const size_t len = d.size() + f.size();
+        for (size_t e = 0; e < len; ++e) {
+            const size_t in_set = e % (size_t)set, row = in_set / (size_t)stride, col = in_set % (size_t)stride;
+            if ((int)row < h && (int)col < 2 * w) continue;
+            if (dt == LERF_F64 ? d[e] != -7.0 : f[e] != -7.0f) return false;
+        }
+        return true;
+    }
+};
+
+static void batched_ops(int oH, int oW) {
+    const int DT[2] = {LERF_F32, LERF_F64}, N = 3;
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int gh = 3, gw = 4, fH = 9, fW = 12;
+    for (int ta : DT)
+        for (int to : DT) {
+            // F: set 0 a sheared grid, set 1 a FOLDED map with NaN, +-inf and 1e300 entries, set 2 a stretched grid
+            Batch F(ta, N, fH, fW), B(ta, N, oH, oW), out(to, N, oH, oW);
+            for (int s = 0; s < N; ++s) {
+                for (int i = 0; i < fH; ++i)
+                    for (int j = 0; j < fW; ++j)
+                        F.set_entry(s, i, j, s == 1 ? 1.3 * i + 0.5 * std::sin(0.7 * j) : (0.9 + 0.3 * s) * i + 0.05 * j,
+                                    s == 1 ? 1.1 * j + 4.0 * std::sin(j / 2.5) + 0.25 * i : (1.1 + 0.2 * s) * j + 0.1 * i);
+                for (int i = 0; i < oH; ++i)
+                    for (int j = 0; j < oW; ++j) {
+                        const int k = i * oW + j + s;
+                        B.set_entry(s, i, j, s == 1 && k % 11 == 3 ? nan : s == 1 && k % 13 == 5 ? -inf : 0.9 * (i % fH) - 0.5,
+                                    s == 1 && k % 17 == 4 ? inf : s == 1 && k % 7 == 2 ? 1e300 : 0.11 * j - 0.75);
+                    }
+            }
+            F.set_entry(1, 2, 5, nan, 3.0); F.set_entry(1, 4, 9, inf, 1.0); F.set_entry(1, 5, 3, 2.0, -inf); F.set_entry(1, 6, 7, 1e300, 1e300);
+            F.set_entry(1, 0, 0, 1e300, -1e300);
+            auto single_map = [&](Batch& b, int s) {
+                Map m(b.dt, b.h, b.w);
+                for (int i = 0; i < b.h; ++i)
+                    for (int k = 0; k < 2 * b.w; ++k) {
+                        if (b.dt == LERF_F64) m.d[(size_t)(i * m.stride + k)] = b.d[(size_t)(s * b.set + i * b.stride + k)];
+                        else m.f[(size_t)(i * m.stride + k)] = b.f[(size_t)(s * b.set + i * b.stride + k)];
+                    }
+                return m;
+            };
+            // mesh: dense control meshes per set with a gap between them
+            {
+                const int64_t cset = 2 * gh * gw + 6;
+                std::vector<double> c64((size_t)((N - 1) * cset + 2 * gh * gw), -7.0);
+                std::vector<float> c32(c64.size(), -7.0f);
+                for (int s = 0; s < N; ++s)
+                    for (int k = 0; k < 2 * gh * gw; ++k) {
+                        const double v = s == 1 && k == 5 ? nan : s == 1 && k == 8 ? 1e300 : s == 1 && k == 11 ? -inf : 3.0 * (k / 2) + 0.25 * s - (s == 1 ? 9.0 * (k % 4) : 0.0);
+                        c64[(size_t)(s * cset + k)] = v;
+                        c32[(size_t)(s * cset + k)] = (float)v;
+                    }
+                void* c = ta == LERF_F64 ? (void*)c64.data() : (void*)c32.data();
+                const size_t el = ta == LERF_F64 ? 8 : 4;
+                for (int interp : {LERF_MESH_BILINEAR, LERF_MESH_BICUBIC}) {
+                    EXPECT(lerf_coords_mesh_batched_host(c, ta, gh, gw, interp, oH + 5, oW + 8, out.p(), to, out.stride, oH, oW, 3, 7, N, cset, out.set) == LERF_OK);
+                    for (int s = 0; s < N; ++s) {
+                        Map one(to, oH, oW);
+                        EXPECT(lerf_coords_mesh_host((char*)c + (size_t)(s * cset) * el, ta, gh, gw, interp, oH + 5, oW + 8, one.p(), to, one.stride, oH, oW, 3, 7) == LERF_OK);
+                        EXPECT(out.set_is(s, one));
+                    }
+                    EXPECT(out.gaps_kept());
+                }
+                EXPECT(lerf_coords_mesh_batched_host(c, ta, gh, gw, 0, oH + 5, oW + 8, out.p(), to, out.stride, oH, oW, 3, 7, N, cset, out.set + 1) == LERF_EINVAL);
+                EXPECT(lerf_coords_mesh_batched_host(c, ta, gh, gw, 0, oH + 5, oW + 8, out.p(), to, out.stride, oH, oW, 3, 7, N, cset, 0) == LERF_EINVAL);
+            }
+            // compose: per-set outer maps, then ONE shared outer map
+            for (int64_t a_set : {F.set, (int64_t)0}) {
+                EXPECT(lerf_coords_compose_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, out.p(), to, out.stride, oH, oW, N, a_set, B.set, out.set) == LERF_OK);
+                for (int s = 0; s < N; ++s) {
+                    Map one(to, oH, oW), a1 = single_map(F, a_set ? s : 0), b1 = single_map(B, s);
+                    EXPECT(lerf_coords_compose_host(a1.p(), ta, a1.stride, fH, fW, b1.p(), ta, b1.stride, one.p(), to, one.stride, oH, oW) == LERF_OK);
+                    EXPECT(out.set_is(s, one));
+                }
+                EXPECT(out.gaps_kept());
+            }
+            EXPECT(lerf_coords_compose_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, out.p(), to, out.stride, oH, oW, N, F.set, 0, out.set) == LERF_EINVAL);
+            EXPECT(lerf_coords_compose_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, out.p(), to, out.stride, oH, oW, 65536, F.set, B.set, out.set) == LERF_EUNSUPPORTED);
+            // invert at origin (3, 7): the affine start, then a start per set (B: NaN, inf and 1e300 in set 1)
+            for (int with_init : {0, 1}) {
+                EXPECT(lerf_coords_invert_batched_host(F.p(), ta, F.stride, fH, fW, with_init ? B.p() : nullptr, ta, B.stride, out.p(), to, out.stride, oH, oW, 3, 7,
+                                                       5, 1e-9, N, F.set, B.set, out.set) == LERF_OK);
+                for (int s = 0; s < N; ++s) {
+                    Map one(to, oH, oW), f1 = single_map(F, s), b1 = single_map(B, s);
+                    EXPECT(lerf_coords_invert_host(f1.p(), ta, f1.stride, fH, fW, with_init ? b1.p() : nullptr, ta, b1.stride, one.p(), to, one.stride, oH, oW, 3, 7,
+                                                   5, 1e-9) == LERF_OK);
+                    EXPECT(out.set_is(s, one));
+                }
+                EXPECT(out.gaps_kept());
+            }
+            // the rasterising inverse at origin (3, 7): keys and depth per set with gaps, then a shared depth
+            {
+                const int64_t kset = (int64_t)oH * oW + 3, dset = (int64_t)fH * fW + 5;
+                std::vector<uint64_t> keys((size_t)((N - 1) * kset + oH * oW), 5), one_keys((size_t)oH * oW);
+                std::vector<float> depth((size_t)((N - 1) * dset + fH * fW), -7.0f);
+                for (int s = 0; s < N; ++s)
+                    for (int k = 0; k < fH * fW; ++k) depth[(size_t)(s * dset + k)] = s == 1 && k % 31 == 7 ? (float)nan : 2.0f + std::sin(0.3f * (float)(k + s));
+                for (int64_t d_set : {dset, (int64_t)0}) {
+                    EXPECT(lerf_coords_invert_raster_batched_host(F.p(), ta, F.stride, fH, fW, depth.data(), out.p(), to, out.stride, oH, oW, 3, 7, 16, 0, keys.data(),
+                                                                  N, F.set, d_set, out.set, kset) == LERF_OK);
+                    for (int s = 0; s < N; ++s) {
+                        Map one(to, oH, oW), f1 = single_map(F, s);
+                        EXPECT(lerf_coords_invert_raster_host(f1.p(), ta, f1.stride, fH, fW, depth.data() + s * d_set, one.p(), to, one.stride, oH, oW, 3, 7, 16, 0,
+                                                              one_keys.data()) == LERF_OK);
+                        EXPECT(out.set_is(s, one) && !std::memcmp(one_keys.data(), keys.data() + s * kset, one_keys.size() * 8));
+                    }
+                    EXPECT(out.gaps_kept());
+                    for (int s = 0; s + 1 < N; ++s)
+                        for (int k = oH * oW; k < kset; ++k) EXPECT(keys[(size_t)(s * kset + k)] == 5);
+                }
+                EXPECT(lerf_coords_invert_raster_batched_host(F.p(), ta, F.stride, fH, fW, depth.data(), out.p(), to, out.stride, oH, oW, 3, 7, 16, 0, keys.data(), N,
+                                                              F.set, dset, out.set, 0) == LERF_EINVAL);
+            }
+            if (to == LERF_F32) continue;
+            // the adjoints: dense float64 gradients per set with gaps; a shared outer map with ONE grad_a
+            const int64_t gset = 2 * (int64_t)oH * oW + 4, fset = 2 * (int64_t)fH * fW + 6;
+            std::vector<double> g((size_t)((N - 1) * gset + 2 * oH * oW), -7.0), gB(g.size(), -7.0), gA((size_t)((N - 1) * fset + 2 * fH * fW), -7.0), gF(gA.size(), -7.0);
+            for (int s = 0; s < N; ++s) {
+                for (int k = 0; k < 2 * oH * oW; ++k) { g[(size_t)(s * gset + k)] = s == 1 && k % 29 == 9 ? nan : std::sin(0.37 * (double)(k + s)); gB[(size_t)(s * gset + k)] = 0.0; }
+                for (int k = 0; k < 2 * fH * fW; ++k) gA[(size_t)(s * fset + k)] = gF[(size_t)(s * fset + k)] = 0.0;
+            }
+            EXPECT(lerf_coords_compose_bwd_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, g.data(), oH, oW, gA.data(), gB.data(), N, F.set, B.set, gset,
+                                                        fset, gset) == LERF_OK);
+            EXPECT(lerf_coords_invert_bwd_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, g.data(), oH, oW, gF.data(), N, F.set, B.set, gset, fset) == LERF_OK);
+            std::vector<double> shared((size_t)2 * fH * fW, 0.0), acc(shared.size(), 0.0);
+            EXPECT(lerf_coords_compose_bwd_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, g.data(), oH, oW, shared.data(), nullptr, N, 0, B.set, gset, 0,
+                                                        0) == LERF_OK);
+            for (int s = 0; s < N; ++s) {
+                Map f1 = single_map(F, s), f0 = single_map(F, 0), b1 = single_map(B, s);
+                std::vector<double> a1((size_t)2 * fH * fW, 0.0), b_1((size_t)2 * oH * oW, 0.0), fg((size_t)2 * fH * fW, 0.0);
+                EXPECT(lerf_coords_compose_bwd_host(f1.p(), ta, f1.stride, fH, fW, b1.p(), ta, b1.stride, g.data() + s * gset, oH, oW, a1.data(), b_1.data()) == LERF_OK);
+                EXPECT(!std::memcmp(a1.data(), gA.data() + s * fset, a1.size() * 8) && !std::memcmp(b_1.data(), gB.data() + s * gset, b_1.size() * 8));
+                EXPECT(lerf_coords_invert_bwd_host(f1.p(), ta, f1.stride, fH, fW, b1.p(), ta, b1.stride, g.data() + s * gset, oH, oW, fg.data()) == LERF_OK);
+                EXPECT(!std::memcmp(fg.data(), gF.data() + s * fset, fg.size() * 8));
+                EXPECT(lerf_coords_compose_bwd_host(f0.p(), ta, f0.stride, fH, fW, b1.p(), ta, b1.stride, g.data() + s * gset, oH, oW, acc.data(), nullptr) == LERF_OK);
+            }
+            EXPECT(!std::memcmp(acc.data(), shared.data(), acc.size() * 8));               // the sum over the sets, in set order
+            for (int s = 0; s + 1 < N; ++s) {
+                for (int64_t k = 2 * oH * oW; k < gset; ++k) EXPECT(gB[(size_t)(s * gset + k)] == -7.0);
+                for (int64_t k = 2 * fH * fW; k < fset; ++k) EXPECT(gA[(size_t)(s * fset + k)] == -7.0 && gF[(size_t)(s * fset + k)] == -7.0);
+            }
+            const std::vector<double> keepA = gA, keepF = gF;
+            EXPECT(lerf_coords_compose_bwd_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, g.data(), oH, oW, gA.data(), gB.data(), N, F.set, B.set, gset, 0,
+                                                        gset) == LERF_EINVAL);              // one grad_a for three different outer maps
+            EXPECT(lerf_coords_compose_bwd_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, g.data(), oH, oW, gA.data(), gB.data(), N, F.set, B.set, 0, fset,
+                                                        gset) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_bwd_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, g.data(), oH, oW, gF.data(), N, F.set, B.set, gset, 0) == LERF_EINVAL);
+            EXPECT(lerf_coords_invert_bwd_batched_host(F.p(), ta, F.stride, fH, fW, B.p(), ta, B.stride, g.data(), oH, oW, gF.data(), 0, F.set, B.set, gset, fset) == LERF_EINVAL);
+            EXPECT(same(keepA, gA) && same(keepF, gF));
+        }
+}
+
 int main() {
     const double pi = 3.14159265358979323846;
     const double fish[17] = {1.0 / 35, 0, -27.5 / 35, 0, 1.0 / 33, -16.0 / 33, 0.001, -0.0005, 1, 61.5, 58.75, 25.25, 17.5, 0.05, -0.012, 0.004, -0.0009};
@@ -198,6 +382,9 @@ int main() {
     raster_ops(1, 1);
     raster_ops(2, 2);
     raster_ops(5, 67);
+    batched_ops(1, 1);
+    batched_ops(2, 2);
+    batched_ops(5, 67);
     std::printf(fails ? "%d check(s) failed\n" : "ok\n", fails);
     return fails ? 1 : 0;
 }

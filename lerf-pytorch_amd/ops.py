@@ -1114,39 +1114,52 @@ def coords_math(op, x, y=None):
 def coords_mesh(ctrl, out_hw, interp="bilinear", dtype=None, out=None, origin=(0, 0), full_hw=None):
     """lerf_coords_mesh: the control mesh ctrl [gh, gw, 2] (device, float32 / float64, absolute source positions at vertices
     placed align-corners over the map full_hw, default out_hw) upsampled to the tile out_hw at `origin`; interp "bilinear" or
-    "bicubic" (Keys A = -0.75, clamped border taps).  dtype: the map's, default ctrl's."""
+    "bicubic" (Keys A = -0.75, clamped border taps).  dtype: the map's, default ctrl's.  A batch ctrl [B, gh, gw, 2] gives
+    [B, oH, oW, 2] in one launch (lerf_coords_mesh_batched), map s bit-equal to the single call on ctrl[s]; out may be a strided
+    batch view (its batch stride becomes the set stride)."""
     return _lib.coords_mesh_on(_lib.DeviceOperands(), ctrl, out_hw, interp, dtype, out, origin, full_hw)
 
 
 def coords_mesh_bwd(grad_map, ctrl_hw, interp="bilinear", grad_ctrl=None):
     """lerf_coords_mesh_bwd: ACCUMULATE the adjoint of coords_mesh (whole map) of the float64 contiguous grad_map [oH, oW, 2] into
-    grad_ctrl (float64 contiguous [gh, gw, 2]; None: a zeroed one).  Deterministic: two calls on the same input are bit-equal."""
+    grad_ctrl (float64 contiguous [gh, gw, 2]; None: a zeroed one).  Deterministic: two calls on the same input are bit-equal.
+    A batch grad_map [B, oH, oW, 2] gives grad_ctrl [B, gh, gw, 2] in ONE call of lerf_coords_mesh_bwd_batched (its two launches
+    cover every sample; the workspace holds B row passes), sample s bit-equal to the single-map call."""
     torch = _torch()
     gh, gw = int(ctrl_hw[0]), int(ctrl_hw[1])
     code = _lib.mesh_interp_code(interp)
     g = grad_map
-    if not isinstance(g, torch.Tensor) or not g.is_cuda or g.ndim != 3 or g.shape[2] != 2 or g.dtype != torch.float64 or not g.is_contiguous():
-        raise ValueError("lerf_coords_mesh_bwd: grad_map must be a contiguous float64 device tensor [oH, oW, 2]")
+    if not isinstance(g, torch.Tensor) or not g.is_cuda or g.ndim not in (3, 4) or g.shape[-1] != 2 or g.dtype != torch.float64 \
+            or not g.is_contiguous() or g.shape[0] < 1:
+        raise ValueError("lerf_coords_mesh_bwd: grad_map must be a contiguous float64 device tensor [oH, oW, 2] or [B, oH, oW, 2]")
     if gh < 2 or gw < 2:
         raise ValueError("lerf_coords_mesh_bwd: the control mesh is at least 2 x 2")
+    lead = tuple(g.shape[:-3])
     if grad_ctrl is None:
-        grad_ctrl = torch.zeros((gh, gw, 2), dtype=torch.float64, device=g.device)
-    elif grad_ctrl.dtype != torch.float64 or tuple(grad_ctrl.shape) != (gh, gw, 2) or not grad_ctrl.is_contiguous() \
+        grad_ctrl = torch.zeros(lead + (gh, gw, 2), dtype=torch.float64, device=g.device)
+    elif grad_ctrl.dtype != torch.float64 or tuple(grad_ctrl.shape) != lead + (gh, gw, 2) or not grad_ctrl.is_contiguous() \
             or grad_ctrl.device != g.device:
-        raise ValueError("lerf_coords_mesh_bwd: grad_ctrl must be contiguous float64 [gh, gw, 2] on grad_map's device")
-    oH, oW = int(g.shape[0]), int(g.shape[1])
-    need = int(_lib.lib().lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW))
+        raise ValueError("lerf_coords_mesh_bwd: grad_ctrl must be contiguous float64 %s on grad_map's device" % (list(lead + (gh, gw, 2)),))
+    oH, oW = int(g.shape[-3]), int(g.shape[-2])
+    B = lead[0] if lead else 1
+    need = B * int(_lib.lib().lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW))
     with _lib.on_device(g):
         ws = _cached_workspace(need, g.device)
-        _lib.check(_lib.lib().lerf_coords_mesh_bwd(g.data_ptr(), oH, oW, code, gh, gw, grad_ctrl.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   _lib.current_stream(g.device)), "lerf_coords_mesh_bwd")
+        if lead:
+            _lib.check(_lib.lib().lerf_coords_mesh_bwd_batched(g.data_ptr(), oH, oW, code, gh, gw, grad_ctrl.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                               B, 2 * oH * oW if B > 1 else 0, 2 * gh * gw if B > 1 else 0,
+                                                               _lib.current_stream(g.device)), "lerf_coords_mesh_bwd_batched")
+        else:
+            _lib.check(_lib.lib().lerf_coords_mesh_bwd(g.data_ptr(), oH, oW, code, gh, gw, grad_ctrl.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       _lib.current_stream(g.device)), "lerf_coords_mesh_bwd")
     return grad_ctrl
 
 
 def coords_compose(outer, inner, dtype=None, out=None):
     """lerf_coords_compose: C[i, j] = outer(inner[i, j]) -- the outer map sampled bilinearly at the positions the inner map
     holds, so remap(remap(img, outer), inner) and remap(img, C) describe the same geometry.  Device maps under the strided
-    contract, any mix of float32 / float64; dtype: C's, default inner's."""
+    contract, any mix of float32 / float64; dtype: C's, default inner's.  A batch inner [B, oH, oW, 2] with outer [B, aH, aW, 2] or
+    one shared [aH, aW, 2] gives [B, oH, oW, 2] in one launch (lerf_coords_compose_batched)."""
     return _lib.coords_compose_on(_lib.DeviceOperands(), outer, inner, dtype, out)
 
 
@@ -1156,7 +1169,8 @@ def coords_invert(f, out_hw, init=None, dtype=None, out=None, origin=(0, 0), max
     max_iter passes, stopped at max |f(u) - target| <= tol; (NaN, NaN) where f does not reach, folds, or holds a NaN in the cell
     read.  out_hw: the size of the frame f points into.  Device maps under the strided contract (tile views of f, init and out
     with `origin` = the tile's place in the whole inverse), any mix of float32 / float64; dtype: G's, default f's.  One launch on
-    the current stream, no sync."""
+    the current stream, no sync.  A batch f [B, fH, fW, 2] (init [B, oH, oW, 2], one shared [oH, oW, 2] or None; a single f with a
+    batch of inits is shared too) gives [B, oH, oW, 2] in the same one launch (lerf_coords_invert_batched)."""
     return _lib.coords_invert_on(_lib.DeviceOperands(), f, out_hw, init, dtype, out, origin, max_iter, tol)
 
 
@@ -1169,7 +1183,9 @@ def coords_invert_raster(f, out_hw, depth=None, dtype=None, out=None, origin=(0,
     contiguous [oH, oW] workspace on f's device (None: a new one), which holds the winning 64-bit keys afterwards -- low 32 bits the
     triangle, -1 (all ones) for a hole.  -> G, or (G, keys) with return_keys=True.  Device maps under the strided contract, any mix
     of float32 / float64; dtype: G's, default f's.  Three launches on the current stream, no sync; bit-equal from run to run and to
-    _lib.coords_invert_raster_host."""
+    _lib.coords_invert_raster_host.  A batch f [B, fH, fW, 2] (depth [B, fH, fW], one shared [fH, fW] or None) gives [B, oH, oW, 2] in
+    the same three launches (lerf_coords_invert_raster_batched); keys is then [B, oH, oW]: ONE KEY PLANE PER SAMPLE, 8 bytes per
+    output pixel per sample."""
     return _lib.coords_invert_raster_on(_lib.DeviceOperands(), f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys)
 
 
@@ -1178,7 +1194,9 @@ def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None,
     into grad_outer (float64 contiguous [aH, aW, 2]: a bilinear scatter by float64 atomic adds, reproducible up to the rounding of
     a reordered sum) and grad_inner (float64 contiguous [oH, oW, 2]: one writer per entry, bit-reproducible); None: zeroed ones;
     need[k] False skips that half and returns None for it.  The maps are device tensors under the strided contract, the outer
-    map at least 2 x 2.  One launch on the current stream, no sync -> (grad_outer, grad_inner)."""
+    map at least 2 x 2.  One launch on the current stream, no sync -> (grad_outer, grad_inner).  A batch: inner, grad_out and
+    grad_inner [B, oH, oW, 2] with outer and grad_outer [B, aH, aW, 2], or ONE shared outer [aH, aW, 2] whose grad_outer [aH, aW, 2]
+    gains the sum over the samples -- still one launch (lerf_coords_compose_bwd_batched)."""
     return _lib.coords_compose_bwd_on(_lib.DeviceOperands(), outer, inner, grad_out, grad_outer, grad_inner, need)
 
 
@@ -1187,5 +1205,5 @@ def coords_invert_bwd(f, inverse, grad_out, grad_f=None):
     [oH, oW, 2]) into grad_f (float64 contiguous [fH, fW, 2]; None: a zeroed one) by the implicit function theorem: the bilinear
     scatter of -J^-T grad_out at the cell of every entry of the inverse (float64 atomic adds); NaN entries of the inverse, NaN
     corners and folded cells contribute nothing.  Device maps under the strided contract.  One launch on the current stream, no
-    sync."""
+    sync.  A batch: f and grad_f [B, fH, fW, 2], inverse and grad_out [B, oH, oW, 2], one launch (lerf_coords_invert_bwd_batched)."""
     return _lib.coords_invert_bwd_on(_lib.DeviceOperands(), f, inverse, grad_out, grad_f)
