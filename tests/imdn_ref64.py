@@ -1,5 +1,6 @@
 """Float64 numpy restatement of the reference's IMDN_RTC / IMDN2 (resample/model.py:434-545) at upscale 1, and the
-seeded weight rule of tests/golden/gen_imdn_golden.py (a helper for test_imdn_cpu.py and test_gpu_imdn.py, not a test).
+seeded weight rule of tests/golden/gen_imdn_golden.py (a helper for test_imdn_cpu.py and test_gpu_imdn.py, not a test);
+hazards() measures on the same net how close a batch comes to the thresholds of the backward (imdn_grad_ref.py).
 
 Every convolution is zero-padded by (k-1)/2 (PyTorch's Conv2d with padding=(k-1)/2); activations run NHWC in float64."""
 import hashlib
@@ -71,22 +72,57 @@ def _lrelu(x):
     return np.where(x > 0, x, 0.05 * x)
 
 
-def imdn_rtc(sd, prefix, x):
-    """one IMDN_RTC: x [B, in_nc, H, W] (any float) -> [B, out_nc, H, W] float64, sd keys under `prefix`"""
+def _net(sd, prefix, x, seen=None):
+    """imdn_rtc's arithmetic; seen(name, z) is handed every LeakyReLU input z [B, H, W, nf] under its conv's name"""
     g = lambda name: (sd[prefix + name + ".weight"], sd[prefix + name + ".bias"])
+
+    def act(h, name):
+        z = _conv(h, *g(name))
+        if seen is not None:
+            seen(name, z)
+        return _lrelu(z)
+
     h = np.transpose(np.asarray(x, np.float64), (0, 2, 3, 1))
     fea = _conv(h, *g("model.0"))
     d = fea.shape[-1] // 4
     h = fea
     for m in range(MODULES):
         p = "model.1.sub.%d." % m
-        o1 = _lrelu(_conv(h, *g(p + "c1")))
-        o2 = _lrelu(_conv(o1[..., d:], *g(p + "c2")))
-        o3 = _lrelu(_conv(o2[..., d:], *g(p + "c3")))
+        o1 = act(h, p + "c1")
+        o2 = act(o1[..., d:], p + "c2")
+        o3 = act(o2[..., d:], p + "c3")
         o4 = _conv(o3[..., d:], *g(p + "c4"))
         h = _conv(np.concatenate([o1[..., :d], o2[..., :d], o3[..., :d], o4], -1), *g(p + "c5")) + h
     y = _conv(_conv(h, *g("model.1.sub.5")) + fea, *g("model.2"))
     return np.transpose(y, (0, 3, 1, 2))
+
+
+def imdn_rtc(sd, prefix, x):
+    """one IMDN_RTC: x [B, in_nc, H, W] (any float) -> [B, out_nc, H, W] float64, sd keys under `prefix`"""
+    return _net(sd, prefix, x)
+
+
+def hazards(sd, prefix, x, exempt=()):
+    """how close each image of x [B, in_nc, H, W] comes to a threshold of the backward, in float64 -> (zmin, ymin), [B] each:
+    zmin[b] the smallest |z| over every LeakyReLU input (c1, c2, c3 of the five modules, all channels and pixels),
+    ymin[b] the smallest | |y| - 1 | over the raw output.  `exempt` leaves out the channels that sit on a threshold on
+    purpose: a pair ("model.1.sub.M.cJ", channel) is skipped in zmin, a bare output channel in ymin."""
+    skip_z = {}
+    for e in exempt:
+        if isinstance(e, tuple):
+            skip_z.setdefault(e[0], []).append(e[1])
+    skip_y = [e for e in exempt if not isinstance(e, tuple)]
+    zmin = np.full(np.shape(x)[0], np.inf)
+
+    def seen(name, z):
+        keep = np.ones(z.shape[-1], bool)
+        keep[skip_z.get(name, [])] = False
+        np.minimum(zmin, np.abs(z[..., keep]).min(axis=(1, 2, 3)), out=zmin)
+
+    y = _net(sd, prefix, x, seen)
+    keep = np.ones(y.shape[1], bool)
+    keep[skip_y] = False
+    return zmin, np.abs(np.abs(y[:, keep]) - 1).min(axis=(1, 2, 3))
 
 
 def post(y, stage, norm=255):

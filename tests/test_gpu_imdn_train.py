@@ -6,7 +6,9 @@ Tolerances.
     (imdn_grad_ref.net_grads, pinned to the reference by test_imdn_grad_cpu.py).  The same figure e_stock is taken for
     stock float32 torch autograd of imdn_ref64.torch_imdn_rtc on the GPU -- the reference's own arithmetic -- and the
     HIP backward must satisfy e_hip <= 4 e_stock + 1e-6: the factor 4 is the margin for another float32 summation order
-    (slab split-K against MIOpen's) over at most 782 pixels and 28 convolutions.  So that the comparison means something,
+    (slab split-K against MIOpen's) over at most 782 pixels (in this file: at most 25 tiles, one per slab;
+    test_gpu_imdn_train_tiles.py has the batches of more tiles than slabs, up to 5 400 pixels, under the same rule) and
+    28 convolutions.  So that the comparison means something,
     e_stock <= 1e-3 for every tensor, and with post != 0 no float64 raw output lies within 1e-4 of +-1 (no float32 run
     can flip the clamp mask); the seeds are chosen for that, and both are asserted.
   golden (g28_imdn_grads.npz, the reference's float32 CPU run of train_model.py:418-441): the terms of the same
