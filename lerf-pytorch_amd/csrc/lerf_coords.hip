@@ -13,9 +13,11 @@
 // rasteriser, the two passes of the mesh adjoint) takes one set stride per operand, set s works on base + s * set_stride, and the
 // single-map entry points are n_sets = 1 of the same code.  The set is blockIdx.z, so the offsets are scalar.
 // and every operation is ONE function template over the runner (coords::build, mesh, compose, ...): the argument checks, the dtype and
-// model dispatch, run(Op{...}, oH, oW[, sets]).  The C entry points lerf_coords_X / lerf_coords_X_host are that template with one
-// runner or the other, so the device and the host twin cannot drift apart: they agree bit for bit by construction (the two
-// float scatters excepted, below).  Add2 is the one float scatter: two float64 atomicAdd where compiled for the device, a plain add on the host.
+// model dispatch, run(Op{...}, oH, oW[, sets]).  The C entry points lerf_coords_X_batched / lerf_coords_X_batched_host are that template
+// with one runner or the other, and lerf_coords_X / lerf_coords_X_host call those with n_sets = 1 and set strides 0, so the device and
+// the host twin, the single map and the batch cannot drift apart: they agree bit for bit by construction (the two float scatters
+// excepted, below).  THE ARGUMENT CHECKS are one operand table per call (Operand, Pair, check_call, after the kernels):
+// an entry point lists its operands, its scalar rules and the pairs that must not intersect ONCE, and one function judges them.  Add2 is the one float scatter: two float64 atomicAdd where compiled for the device, a plain add on the host.
 // MapReader is the one strided-map reader handed to the *_point functions; a dense float64 gradient [h][w][2] is a map of row stride 2w.
 //
 // The rasterising inverse (lerf_coords_invert_raster) is three passes: KeyFillOp and ResolveOp are per-entry functors under the two
@@ -67,6 +69,7 @@
 #include "lerf_coords_models.h"
 
 #include <cmath>
+#include <initializer_list>
 #include <vector>
 
 namespace lerf {
@@ -492,9 +495,77 @@ coords_math_kernel(int op, const double* __restrict__ x, const double* __restric
 inline bool float_dtype(int dt) { return dt == LERF_F32 || dt == LERF_F64; }
 inline size_t entry_bytes(int dt) { return dt == LERF_F32 ? 8 : 16; }
 
-// a map operand under the strided contract
-inline bool map_ok(const void* p, int dt, int64_t stride, int h, int w) {
-    return p && float_dtype(dt) && h >= 1 && w >= 1 && !(stride & 1) && stride >= 2 * (int64_t)w && (size_t)(uintptr_t)p % entry_bytes(dt) == 0;
+// ONE OPERAND TABLE PER CALL.  Every entry point states its operands (Operand), its scalar rules (one bool) and the pairs of operands
+// that must not intersect (Pair), and check_call judges them: the one place that looks at a pointer, an alignment, a dtype, a row
+// stride, a set stride or an overlap, for a single map (n_sets = 1, set strides 0) and for a batch alike.
+//
+// One operand over the n_sets sets of a call: set s at p + s * set_stride elements of `el` bytes, each set `span` elements from its
+// first to one past its last (the ONE place an extent is computed: the constructors below); pairs: the elements are (row, col) pairs
+// (maps, gradients), so the set stride is even; SHARE: a set stride of 0 (one operand for all sets) is allowed; OPTIONAL: may be null
+// (init, depth, a skipped gradient, the workspace the host twin does not have) and then passes every check.  shape_ok is false for a
+// descriptor made of a dtype code or dimensions that are not valid: its extent means nothing, and check_call refuses it first.
+enum : unsigned { SHARE = 1, OPTIONAL = 2 };
+struct Operand {
+    const void* p;
+    size_t el, align;
+    int64_t span, set_stride;
+    bool pairs, share, optional, shape_ok, rows_ok;
+};
+
+// a map under the strided contract: [h][w] entries of dtype dt, rows `stride` elements apart (even, >= 2 w), h, w >= min_hw
+inline Operand map_operand(const void* p, int dt, int64_t stride, int h, int w, int64_t set_stride, unsigned flags = 0, int min_hw = 1) {
+    const bool null_ok = !p && (flags & OPTIONAL);
+    return {p, entry_bytes(dt) / 2, entry_bytes(dt), (int64_t)(h - 1) * stride + 2 * (int64_t)w, set_stride, true, (flags & SHARE) != 0,
+            (flags & OPTIONAL) != 0, null_ok || (float_dtype(dt) && h >= min_hw && w >= min_hw), !(stride & 1) && stride >= 2 * (int64_t)w};
+}
+// a dense gradient (float64) or control mesh [h][w][2]: the map of row stride 2 w
+inline Operand dense_operand(const void* p, int dt, int h, int w, int64_t set_stride, unsigned flags = 0, int min_hw = 1) {
+    return map_operand(p, dt, 2 * (int64_t)w, h, w, set_stride, flags, min_hw);
+}
+// a dense plane [h][w] of scalars of `el` bytes (keys, depth); its dimensions are those of a map of the same call, checked there
+inline Operand plane_operand(const void* p, size_t el, int h, int w, int64_t set_stride, unsigned flags = 0) {
+    return {p, el, el, (int64_t)h * w, set_stride, false, (flags & SHARE) != 0, (flags & OPTIONAL) != 0, true, true};
+}
+// `bytes` bytes per set, the sets one behind the other (params, grad_params, the workspaces)
+inline Operand bytes_operand(const void* p, int64_t bytes, size_t align, unsigned flags = 0) {
+    return {p, 1, align, bytes, bytes, false, false, (flags & OPTIONAL) != 0, true, true};
+}
+// a parameter block [n_sets][n_params] float64 (params, grad_params)
+inline Operand params_operand(const void* p, int n_params) { return bytes_operand(p, 8 * (int64_t)n_params, sizeof(double)); }
+
+// the bytes of two operands over the whole batch (first element of set 0 to one past the last of the last set) intersect
+inline bool operands_overlap(int n_sets, const Operand& x, const Operand& y) {
+    if (!x.p || !y.p) return false;
+    const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+    const size_t an = (size_t)((int64_t)(n_sets - 1) * x.set_stride + x.span) * x.el, bn = (size_t)((int64_t)(n_sets - 1) * y.set_stride + y.span) * y.el;
+    return a < b + bn && b < a + an;
+}
+
+// operands x and y of the call (indices into its table) must not intersect; on = false: not for this call (a pair that is refused
+// in a batch only is {x, y, n_sets > 1})
+struct Pair {
+    int x, y;
+    bool on = true;
+};
+
+// The judgement of a call, in the order the return codes have had since the batched forms exist: a descriptor without a shape and
+// n_sets < 1 are LERF_EINVAL, n_sets beyond the grid's z is `too_many` (LERF_EUNSUPPORTED for the chained operations), then the scalar
+// rules, every operand's pointer, alignment, row stride and set stride, and the pairs: LERF_EINVAL.  A refused call launches nothing.
+inline int check_call(int n_sets, std::initializer_list<Operand> ops, std::initializer_list<Pair> pairs, bool rules, int too_many = LERF_EUNSUPPORTED) {
+    for (const Operand& o : ops)
+        if (!o.shape_ok) return LERF_EINVAL;
+    if (n_sets < 1) return LERF_EINVAL;
+    if (n_sets > 65535) return too_many;
+    if (!rules) return LERF_EINVAL;
+    for (const Operand& o : ops) {
+        if (!o.p && o.optional) continue;
+        if (!o.p || (size_t)(uintptr_t)o.p % o.align != 0 || !o.rows_ok) return LERF_EINVAL;
+        if (o.set_stride < 0 || (o.pairs && (o.set_stride & 1))) return LERF_EINVAL;
+        if (n_sets > 1 && o.set_stride < o.span && !(o.share && o.set_stride == 0)) return LERF_EINVAL;
+    }
+    for (const Pair& q : pairs)
+        if (q.on && operands_overlap(n_sets, ops.begin()[q.x], ops.begin()[q.y])) return LERF_EINVAL;
+    return LERF_OK;
 }
 
 inline bool tile_ok(int oH, int oW, int i0, int j0) {
@@ -503,8 +574,9 @@ inline bool tile_ok(int oH, int oW, int i0, int j0) {
 
 inline int build_args(int model, const double* params, int n_params, const void* out, int out_dtype, int64_t stride, int oH, int oW,
                       int i0, int j0, Params& prm) {
-    if (!params || !map_ok(out, out_dtype, stride, oH, oW) || !tile_ok(oH, oW, i0, j0)) return LERF_EINVAL;
-    if (model_params(model) < 0 || n_params != model_params(model)) return LERF_EINVAL;
+    const int rc = check_call(1, {map_operand(out, out_dtype, stride, oH, oW, 0)}, {},
+                              params && tile_ok(oH, oW, i0, j0) && model_params(model) >= 0 && n_params == model_params(model));
+    if (rc != LERF_OK) return rc;
     for (int k = 0; k < kMaxParams; ++k) prm.p[k] = 0.0;
     for (int k = 0; k < n_params; ++k) {
         if (!std::isfinite(params[k])) return LERF_EINVAL;
@@ -513,165 +585,25 @@ inline int build_args(int model, const double* params, int n_params, const void*
     return LERF_OK;
 }
 
-inline int mesh_args(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, const void* out, int out_dtype,
-                     int64_t stride, int oH, int oW, int i0, int j0) {
-    if (!ctrl || !float_dtype(ctrl_dtype) || (size_t)(uintptr_t)ctrl % entry_bytes(ctrl_dtype) != 0 || gh < 2 || gw < 2) return LERF_EINVAL;
-    if (interp != LERF_MESH_BILINEAR && interp != LERF_MESH_BICUBIC) return LERF_EINVAL;
-    if (!map_ok(out, out_dtype, stride, oH, oW) || !tile_ok(oH, oW, i0, j0)) return LERF_EINVAL;
-    if (full_h < 1 || full_w < 1 || (int64_t)i0 + oH > full_h || (int64_t)j0 + oW > full_w) return LERF_EINVAL;
-    return LERF_OK;
-}
-
-inline int compose_args(const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
-                        const void* out, int out_dtype, int64_t o_stride, int oH, int oW) {
-    if (!map_ok(a, a_dtype, a_stride, aH, aW) || !map_ok(b, b_dtype, b_stride, oH, oW) || !map_ok(out, out_dtype, o_stride, oH, oW))
-        return LERF_EINVAL;
-    return tile_ok(oH, oW, 0, 0) ? LERF_OK : LERF_EINVAL;
-}
-
-// the bytes a map operand spans: first entry to one past the last
-inline bool maps_overlap(const void* p, int pdt, int64_t ps, int ph, int pw, const void* q, int qdt, int64_t qs, int qh, int qw) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    const uintptr_t ae = a + (uintptr_t)(((int64_t)(ph - 1) * ps + 2 * (int64_t)pw) * (int64_t)(entry_bytes(pdt) / 2));
-    const uintptr_t be = b + (uintptr_t)(((int64_t)(qh - 1) * qs + 2 * (int64_t)qw) * (int64_t)(entry_bytes(qdt) / 2));
-    return a < be && b < ae;
-}
-
-inline int invert_args(const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* init, int init_dtype, int64_t i_stride,
-                       const void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol) {
-    if (!map_ok(f, f_dtype, f_stride, fH, fW) || fH < 2 || fW < 2 || !map_ok(out, out_dtype, o_stride, oH, oW)) return LERF_EINVAL;
-    if (!tile_ok(oH, oW, i0, j0) || max_iter < 1 || max_iter > 64 || !(tol >= 0.0) || !std::isfinite(tol)) return LERF_EINVAL;
-    if (maps_overlap(out, out_dtype, o_stride, oH, oW, f, f_dtype, f_stride, fH, fW)) return LERF_EINVAL;
-    if (init && (!map_ok(init, init_dtype, i_stride, oH, oW) || maps_overlap(out, out_dtype, o_stride, oH, oW, init, init_dtype, i_stride, oH, oW)))
-        return LERF_EINVAL;
-    return LERF_OK;
-}
-
-// plain byte ranges [p, p + pn) and [q, q + qn)
-inline bool bytes_overlap(const void* p, size_t pn, const void* q, size_t qn) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
-
-// the bytes of a map operand, first entry to one past the last
-inline size_t map_bytes(int dt, int64_t stride, int h, int w) {
-    return (size_t)(((int64_t)(h - 1) * stride + 2 * (int64_t)w) * (int64_t)(entry_bytes(dt) / 2));
-}
-
-inline int invert_raster_args(const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const float* depth, const void* out, int out_dtype,
-                              int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, const uint64_t* keys) {
-    if (!map_ok(f, f_dtype, f_stride, fH, fW) || fH < 2 || fW < 2 || !map_ok(out, out_dtype, o_stride, oH, oW) || !tile_ok(oH, oW, i0, j0))
-        return LERF_EINVAL;
-    if (2 * (int64_t)(fH - 1) * (int64_t)(fW - 1) >= ((int64_t)1 << 32) || (fH - 1 + CB_ROWS - 1) / CB_ROWS > 65535) return LERF_EINVAL;
-    if (max_span < 1 || max_span > kMaxSpan || orient < -1 || orient > 1) return LERF_EINVAL;
-    if (!keys || (size_t)(uintptr_t)keys % 8 != 0 || (depth && (size_t)(uintptr_t)depth % 4 != 0)) return LERF_EINVAL;
-    const size_t fb = map_bytes(f_dtype, f_stride, fH, fW), ob = map_bytes(out_dtype, o_stride, oH, oW);
-    const size_t kb = (size_t)oH * oW * sizeof(uint64_t), db = (size_t)fH * fW * sizeof(float);
-    if (bytes_overlap(out, ob, f, fb) || bytes_overlap(keys, kb, f, fb) || bytes_overlap(out, ob, keys, kb)) return LERF_EINVAL;
-    if (depth && (bytes_overlap(out, ob, depth, db) || bytes_overlap(keys, kb, depth, db))) return LERF_EINVAL;
-    return LERF_OK;
-}
-
-// a dense float64 gradient [h][w][2]
-inline bool dense_ok(const void* p) { return p && (size_t)(uintptr_t)p % 16 == 0; }
-inline bool dense_overlaps_map(const void* d, int h, int w, const void* q, int qdt, int64_t qs, int qh, int qw) {
-    return maps_overlap(d, LERF_F64, 2 * (int64_t)w, h, w, q, qdt, qs, qh, qw);
-}
-inline bool dense_overlap(const void* d, int h, int w, const void* e, int eh, int ew) {
-    return dense_overlaps_map(d, h, w, e, LERF_F64, 2 * (int64_t)ew, eh, ew);
-}
-
-inline int compose_bwd_args(const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
-                            const double* grad_out, int oH, int oW, const double* grad_a, const double* grad_b) {
-    if (!map_ok(a, a_dtype, a_stride, aH, aW) || aH < 2 || aW < 2 || !map_ok(b, b_dtype, b_stride, oH, oW) || !tile_ok(oH, oW, 0, 0))
-        return LERF_EINVAL;
-    if (!dense_ok(grad_out) || (!grad_a && !grad_b) || (grad_a && !dense_ok(grad_a)) || (grad_b && !dense_ok(grad_b))) return LERF_EINVAL;
-    const void* grads[2] = {grad_a, grad_b};
-    const int gh[2] = {aH, oH}, gw[2] = {aW, oW};
-    for (int k = 0; k < 2; ++k) {
-        if (!grads[k]) continue;
-        if (dense_overlaps_map(grads[k], gh[k], gw[k], a, a_dtype, a_stride, aH, aW) ||
-            dense_overlaps_map(grads[k], gh[k], gw[k], b, b_dtype, b_stride, oH, oW) || dense_overlap(grads[k], gh[k], gw[k], grad_out, oH, oW))
-            return LERF_EINVAL;
-    }
-    if (grad_a && grad_b && dense_overlap(grad_a, aH, aW, grad_b, oH, oW)) return LERF_EINVAL;
-    return LERF_OK;
-}
-
-inline int invert_bwd_args(const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_stride,
-                           const double* grad_out, int oH, int oW, const double* grad_f) {
-    if (!map_ok(f, f_dtype, f_stride, fH, fW) || fH < 2 || fW < 2 || !map_ok(g, g_dtype, g_stride, oH, oW) || !tile_ok(oH, oW, 0, 0))
-        return LERF_EINVAL;
-    if (!dense_ok(grad_out) || !dense_ok(grad_f)) return LERF_EINVAL;
-    if (dense_overlaps_map(grad_f, fH, fW, f, f_dtype, f_stride, fH, fW) || dense_overlaps_map(grad_f, fH, fW, g, g_dtype, g_stride, oH, oW) ||
-        dense_overlap(grad_f, fH, fW, grad_out, oH, oW))
-        return LERF_EINVAL;
-    return LERF_OK;
-}
-
-// device parameters cannot be inspected here: their count, the pointers and the layout of the n_sets maps are what is checked
+// device parameters cannot be inspected here: their count, the pointers and the layout of the n_sets maps are what is checked.  For
+// this one and the next, n_sets beyond the grid's z is LERF_EINVAL
 inline int build_dev_args(int model, const double* params, int n_sets, int n_params, const void* out, int out_dtype, int64_t set_stride,
                           int64_t stride, int oH, int oW, int i0, int j0) {
-    if (!params || (size_t)(uintptr_t)params % sizeof(double) != 0 || !map_ok(out, out_dtype, stride, oH, oW) || !tile_ok(oH, oW, i0, j0))
-        return LERF_EINVAL;
-    if (model_params(model) < 0 || n_params != model_params(model) || n_sets < 1 || n_sets > 65535) return LERF_EINVAL;
-    const int64_t span = (int64_t)(oH - 1) * stride + 2 * (int64_t)oW;      // elements from a map's first entry to one past its last
-    if (set_stride < 0 || (set_stride & 1) || (n_sets > 1 && set_stride < span)) return LERF_EINVAL;
-    const size_t el = entry_bytes(out_dtype) / 2;
-    if (bytes_overlap(params, (size_t)n_sets * n_params * sizeof(double), out, (size_t)((int64_t)(n_sets - 1) * set_stride + span) * el))
-        return LERF_EINVAL;
-    return LERF_OK;
+    enum { PARAMS, OUT };
+    return check_call(n_sets,
+                      {params_operand(params, n_params), map_operand(out, out_dtype, stride, oH, oW, set_stride)},
+                      {{PARAMS, OUT}}, tile_ok(oH, oW, i0, j0) && model_params(model) >= 0 && n_params == model_params(model), LERF_EINVAL);
 }
 
+// ws: the partials of the device's two passes, null and OPTIONAL for the host twin; ws_fits: the caller's workspace_bytes hold them
 inline int build_bwd_args(int model, const double* params, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
-                          const double* grad_params) {
-    if (!params || !grad_params || (size_t)(uintptr_t)params % sizeof(double) != 0 || (size_t)(uintptr_t)grad_params % sizeof(double) != 0)
-        return LERF_EINVAL;
-    if (!dense_ok(grad_map) || oH < 1 || oW < 1 || !tile_ok(oH, oW, i0, j0)) return LERF_EINVAL;
-    if (model_params(model) < 0 || n_params != model_params(model) || n_sets < 1 || n_sets > 65535) return LERF_EINVAL;
-    const size_t pb = (size_t)n_sets * n_params * sizeof(double), mb = (size_t)n_sets * oH * oW * 2 * sizeof(double);
-    if (bytes_overlap(grad_params, pb, params, pb) || bytes_overlap(grad_params, pb, grad_map, mb)) return LERF_EINVAL;
-    return LERF_OK;
-}
-
-// ---- the sets of a batched call.  One operand of it: set s at p + s * set_stride elements of `el` bytes, each set `span` elements from
-// its first to one past its last; pairs: the elements are (row, col) pairs (maps, gradients), so the stride is even; share: a set
-// stride of 0 (one operand for all sets) is allowed.  A null operand (init, depth, a skipped gradient) passes.
-struct SetOperand {
-    const void* p;
-    size_t el;
-    int64_t span, set_stride;
-    bool pairs, share;
-};
-inline int64_t map_span(int64_t stride, int h, int w) { return (int64_t)(h - 1) * stride + 2 * (int64_t)w; }
-inline SetOperand map_sets(const void* p, int dt, int64_t stride, int h, int w, int64_t set_stride, bool share) {
-    return {p, entry_bytes(dt) / 2, map_span(stride, h, w), set_stride, true, share};
-}
-inline SetOperand dense_sets(const void* p, int h, int w, int64_t set_stride, bool share) {
-    return {p, sizeof(double), 2 * (int64_t)h * w, set_stride, true, share};
-}
-inline SetOperand plane_sets(const void* p, size_t el, int h, int w, int64_t set_stride, bool share) {
-    return {p, el, (int64_t)h * w, set_stride, false, share};
-}
-
-// n_sets and every operand's set stride: LERF_EUNSUPPORTED beyond the grid's z, LERF_EINVAL for the rest
-template <size_t N>
-inline int sets_args(int n_sets, const SetOperand (&ops)[N]) {
-    if (n_sets < 1) return LERF_EINVAL;
-    if (n_sets > 65535) return LERF_EUNSUPPORTED;
-    for (const SetOperand& o : ops) {
-        if (!o.p) continue;
-        if (o.set_stride < 0 || (o.pairs && (o.set_stride & 1))) return LERF_EINVAL;
-        if (n_sets > 1 && o.set_stride < o.span && !(o.share && o.set_stride == 0)) return LERF_EINVAL;
-    }
-    return LERF_OK;
-}
-
-// the bytes of an operand over the whole batch (first element of set 0 to one past the last of the last set) intersect another's
-inline bool sets_overlap(int n_sets, const SetOperand& x, const SetOperand& y) {
-    if (!x.p || !y.p) return false;
-    return bytes_overlap(x.p, (size_t)((int64_t)(n_sets - 1) * x.set_stride + x.span) * x.el, y.p,
-                         (size_t)((int64_t)(n_sets - 1) * y.set_stride + y.span) * y.el);
+                          const double* grad_params, const Operand& ws, bool ws_fits) {
+    enum { PARAMS, GMAP, GPARAMS, WS };
+    return check_call(n_sets,
+                      {params_operand(params, n_params),
+                       dense_operand(grad_map, LERF_F64, oH, oW, 2 * (int64_t)oH * oW), params_operand(grad_params, n_params), ws},
+                      {{GPARAMS, PARAMS}, {GPARAMS, GMAP}, {WS, GPARAMS}, {WS, PARAMS}, {WS, GMAP}},
+                      ws_fits && tile_ok(oH, oW, i0, j0) && model_params(model) >= 0 && n_params == model_params(model), LERF_EINVAL);
 }
 
 // run F with MODEL = the compile-time constant of a model code the argument checks have accepted
@@ -717,19 +649,19 @@ int build_dev(RUN run, int model, const double* params, int n_sets, int n_params
         return run(BuildDevOp<MODEL, TO>{params, (TO*)out, set_stride, stride, i0, j0}, oH, oW, n_sets)));
 }
 
-// Each of the chained operations below takes n_sets and one set stride per operand; the single-map entry points leave them at 1 and 0.
-// The checks: sets_args (n_sets, the strides), the single-map *_args on set 0 (every set has its shapes and strides, and an even
-// stride keeps set 0's alignment), then the single-map form's overlap pairs over the whole batch.
+// Each of the chained operations below takes n_sets and one set stride per operand; a single-map entry point is the batched one with
+// n_sets = 1 and every set stride 0.  Each states its table once: the operands, the pairs that must not intersect (over the whole
+// batch; `batch`: refused in a batch only, where the single-map form has always allowed it), the scalar rules.
 template <typename RUN>
 int mesh(RUN run, const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
-         int64_t stride, int oH, int oW, int i0, int j0, int n_sets = 1, int64_t ctrl_set = 0, int64_t out_set = 0) {
-    if (!float_dtype(ctrl_dtype) || !float_dtype(out_dtype) || gh < 2 || gw < 2 || oH < 1 || oW < 1) return LERF_EINVAL;
-    const SetOperand sets[2] = {{ctrl, entry_bytes(ctrl_dtype) / 2, 2 * (int64_t)gh * gw, ctrl_set, true, false},
-                                map_sets(out, out_dtype, stride, oH, oW, out_set, false)};
-    int rc = sets_args(n_sets, sets);
-    if (rc == LERF_OK) rc = mesh_args(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, stride, oH, oW, i0, j0);
+         int64_t stride, int oH, int oW, int i0, int j0, int n_sets, int64_t ctrl_set, int64_t out_set) {
+    enum { CTRL, OUT };
+    const bool batch = n_sets > 1;
+    const int rc = check_call(n_sets, {dense_operand(ctrl, ctrl_dtype, gh, gw, ctrl_set, 0, 2), map_operand(out, out_dtype, stride, oH, oW, out_set)},
+                              {{CTRL, OUT, batch}},
+                              (interp == LERF_MESH_BILINEAR || interp == LERF_MESH_BICUBIC) && tile_ok(oH, oW, i0, j0) && full_h >= 1 && full_w >= 1 &&
+                                  (int64_t)i0 + oH <= full_h && (int64_t)j0 + oW <= full_w);
     if (rc != LERF_OK) return rc;
-    if (n_sets > 1 && sets_overlap(n_sets, sets[0], sets[1])) return LERF_EINVAL;
     LERF_COORDS_DT(ctrl_dtype, TC, LERF_COORDS_DT(out_dtype, TO, {
         if (interp == LERF_MESH_BILINEAR)
             return run(MeshOp<LERF_MESH_BILINEAR, TC, TO>{(const TC*)ctrl, gh, gw, full_h, full_w, (TO*)out, stride, i0, j0, ctrl_set, out_set},
@@ -741,15 +673,14 @@ int mesh(RUN run, const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, 
 
 template <typename RUN>
 int compose(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride, void* out,
-            int out_dtype, int64_t o_stride, int oH, int oW, int n_sets = 1, int64_t a_set = 0, int64_t b_set = 0, int64_t out_set = 0) {
-    if (!float_dtype(a_dtype) || !float_dtype(b_dtype) || !float_dtype(out_dtype) || aH < 1 || aW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
-    const SetOperand sets[3] = {map_sets(a, a_dtype, a_stride, aH, aW, a_set, true), map_sets(b, b_dtype, b_stride, oH, oW, b_set, false),
-                                map_sets(out, out_dtype, o_stride, oH, oW, out_set, false)};
-    int rc = sets_args(n_sets, sets);
-    if (rc == LERF_OK) rc = compose_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, out, out_dtype, o_stride, oH, oW);
+            int out_dtype, int64_t o_stride, int oH, int oW, int n_sets, int64_t a_set, int64_t b_set, int64_t out_set) {
+    enum { A, B, OUT };
+    const bool batch = n_sets > 1, in_place = out == b && out_dtype == b_dtype && o_stride == b_stride && out_set == b_set;
+    const int rc = check_call(n_sets,
+                              {map_operand(a, a_dtype, a_stride, aH, aW, a_set, SHARE), map_operand(b, b_dtype, b_stride, oH, oW, b_set),
+                               map_operand(out, out_dtype, o_stride, oH, oW, out_set)},
+                              {{OUT, A, batch}, {OUT, B, batch && !in_place}}, tile_ok(oH, oW, 0, 0));
     if (rc != LERF_OK) return rc;
-    const bool in_place = out == b && out_dtype == b_dtype && o_stride == b_stride && out_set == b_set;
-    if (n_sets > 1 && (sets_overlap(n_sets, sets[2], sets[0]) || (!in_place && sets_overlap(n_sets, sets[2], sets[1])))) return LERF_EINVAL;
     LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB, LERF_COORDS_DT(out_dtype, TO,
         return run(ComposeOp<TA, TB, TO>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, (TO*)out, o_stride, a_set, b_set, out_set},
                    oH, oW, n_sets))));
@@ -757,17 +688,15 @@ int compose(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int a
 
 template <typename RUN>
 int invert(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* init, int init_dtype, int64_t i_stride,
-           void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol, int n_sets = 1,
-           int64_t f_set = 0, int64_t init_set = 0, int64_t out_set = 0) {
-    if (!float_dtype(f_dtype) || !float_dtype(out_dtype) || (init && !float_dtype(init_dtype)) || fH < 1 || fW < 1 || oH < 1 || oW < 1)
-        return LERF_EINVAL;
-    const SetOperand sets[3] = {map_sets(f, f_dtype, f_stride, fH, fW, f_set, true), map_sets(init, init_dtype, i_stride, oH, oW, init_set, true),
-                                map_sets(out, out_dtype, o_stride, oH, oW, out_set, false)};
-    int rc = sets_args(n_sets, sets);
-    if (rc == LERF_OK)
-        rc = invert_args(f, f_dtype, f_stride, fH, fW, init, init_dtype, i_stride, out, out_dtype, o_stride, oH, oW, i0, j0, max_iter, tol);
+           void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol, int n_sets, int64_t f_set,
+           int64_t init_set, int64_t out_set) {
+    enum { F, INIT, OUT };
+    const int rc = check_call(n_sets,
+                              {map_operand(f, f_dtype, f_stride, fH, fW, f_set, SHARE), map_operand(init, init_dtype, i_stride, oH, oW, init_set, SHARE | OPTIONAL),
+                               map_operand(out, out_dtype, o_stride, oH, oW, out_set)},
+                              {{OUT, F}, {OUT, INIT}},
+                              fH >= 2 && fW >= 2 && tile_ok(oH, oW, i0, j0) && max_iter >= 1 && max_iter <= 64 && tol >= 0.0 && std::isfinite(tol));
     if (rc != LERF_OK) return rc;
-    if (n_sets > 1 && (sets_overlap(n_sets, sets[2], sets[0]) || sets_overlap(n_sets, sets[2], sets[1]))) return LERF_EINVAL;
     if (!init) init_dtype = LERF_F64;                     // a null init is never read: one instantiation serves
     LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(init_dtype, TI, LERF_COORDS_DT(out_dtype, TO,
         return run(InvertOp<TF, TI, TO>{{(const TF*)f, f_stride}, fH, fW, {(const TI*)init, i_stride}, (TO*)out, o_stride, i0, j0, max_iter, tol,
@@ -778,19 +707,17 @@ int invert(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW
 // fill, raster, resolve: three launches in stream order (the host: three loops), no sync, no allocation
 template <typename RUN, typename SCATTER>
 int invert_raster(RUN run, SCATTER scatter, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const float* depth, void* out,
-                  int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, int n_sets = 1,
-                  int64_t f_set = 0, int64_t depth_set = 0, int64_t out_set = 0, int64_t keys_set = 0) {
-    if (!float_dtype(f_dtype) || !float_dtype(out_dtype) || fH < 1 || fW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
-    const SetOperand sets[4] = {map_sets(f, f_dtype, f_stride, fH, fW, f_set, true), plane_sets(depth, sizeof(float), fH, fW, depth_set, true),
-                                map_sets(out, out_dtype, o_stride, oH, oW, out_set, false),
-                                plane_sets(keys, sizeof(uint64_t), oH, oW, keys_set, false)};
-    int rc = sets_args(n_sets, sets);
-    if (rc == LERF_OK)
-        rc = invert_raster_args(f, f_dtype, f_stride, fH, fW, depth, out, out_dtype, o_stride, oH, oW, i0, j0, max_span, orient, keys);
+                  int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, int n_sets,
+                  int64_t f_set, int64_t depth_set, int64_t out_set, int64_t keys_set) {
+    enum { F, DEPTH, OUT, KEYS };
+    // the cells: a triangle's number fits the key's 32 bits, their rows the grid's y
+    const bool cells_ok = 2 * (int64_t)(fH - 1) * (int64_t)(fW - 1) < ((int64_t)1 << 32) && (fH - 1 + CB_ROWS - 1) / CB_ROWS <= 65535;
+    int rc = check_call(n_sets,
+                        {map_operand(f, f_dtype, f_stride, fH, fW, f_set, SHARE), plane_operand(depth, sizeof(float), fH, fW, depth_set, SHARE | OPTIONAL),
+                         map_operand(out, out_dtype, o_stride, oH, oW, out_set), plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set)},
+                        {{OUT, F}, {KEYS, F}, {OUT, KEYS}, {OUT, DEPTH}, {KEYS, DEPTH}},
+                        fH >= 2 && fW >= 2 && tile_ok(oH, oW, i0, j0) && cells_ok && max_span >= 1 && max_span <= kMaxSpan && orient >= -1 && orient <= 1);
     if (rc != LERF_OK) return rc;
-    if (n_sets > 1 && (sets_overlap(n_sets, sets[2], sets[0]) || sets_overlap(n_sets, sets[3], sets[0]) || sets_overlap(n_sets, sets[2], sets[3]) ||
-                       sets_overlap(n_sets, sets[2], sets[1]) || sets_overlap(n_sets, sets[3], sets[1])))
-        return LERF_EINVAL;
     rc = run(KeyFillOp{keys, oW, keys_set}, oH, oW, n_sets);
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(f_dtype, TF,
@@ -803,22 +730,17 @@ int invert_raster(RUN run, SCATTER scatter, const void* f, int f_dtype, int64_t 
 
 template <typename RUN>
 int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
-                const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets = 1, int64_t a_set = 0, int64_t b_set = 0,
-                int64_t gout_set = 0, int64_t ga_set = 0, int64_t gb_set = 0) {
-    if (!float_dtype(a_dtype) || !float_dtype(b_dtype) || aH < 1 || aW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
-    const SetOperand sets[5] = {map_sets(a, a_dtype, a_stride, aH, aW, a_set, true), map_sets(b, b_dtype, b_stride, oH, oW, b_set, false),
-                                dense_sets(grad_out, oH, oW, gout_set, false), dense_sets(grad_a, aH, aW, ga_set, true),
-                                dense_sets(grad_b, oH, oW, gb_set, false)};
-    int rc = sets_args(n_sets, sets);
-    if (rc == LERF_OK) rc = compose_bwd_args(a, a_dtype, a_stride, aH, aW, b, b_dtype, b_stride, grad_out, oH, oW, grad_a, grad_b);
+                const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets, int64_t a_set, int64_t b_set, int64_t gout_set,
+                int64_t ga_set, int64_t gb_set) {
+    enum { A, B, GOUT, GA, GB };
+    const bool one_ga_many_a = n_sets > 1 && grad_a && ga_set == 0 && a_set != 0;      // one gradient buffer belongs to ONE shared outer map
+    const int rc = check_call(n_sets,
+                              {map_operand(a, a_dtype, a_stride, aH, aW, a_set, SHARE), map_operand(b, b_dtype, b_stride, oH, oW, b_set),
+                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_a, LERF_F64, aH, aW, ga_set, SHARE | OPTIONAL),
+                               dense_operand(grad_b, LERF_F64, oH, oW, gb_set, OPTIONAL)},
+                              {{GA, A}, {GA, B}, {GA, GOUT}, {GB, A}, {GB, B}, {GB, GOUT}, {GA, GB}},
+                              aH >= 2 && aW >= 2 && tile_ok(oH, oW, 0, 0) && (grad_a || grad_b) && !one_ga_many_a);
     if (rc != LERF_OK) return rc;
-    if (n_sets > 1) {
-        if (grad_a && ga_set == 0 && a_set != 0) return LERF_EINVAL;          // one gradient buffer belongs to ONE shared outer map
-        for (int k = 3; k < 5; ++k)
-            if (sets_overlap(n_sets, sets[k], sets[0]) || sets_overlap(n_sets, sets[k], sets[1]) || sets_overlap(n_sets, sets[k], sets[2]))
-                return LERF_EINVAL;
-        if (sets_overlap(n_sets, sets[3], sets[4])) return LERF_EINVAL;
-    }
     LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB,
         return run(ComposeBwdOp<TA, TB>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, {grad_out, 2 * (int64_t)oW}, grad_a, grad_b,
                                         a_set, b_set, gout_set, ga_set, gb_set},
@@ -827,16 +749,13 @@ int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, i
 
 template <typename RUN>
 int invert_bwd(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_stride,
-               const double* grad_out, int oH, int oW, double* grad_f, int n_sets = 1, int64_t f_set = 0, int64_t g_set = 0, int64_t gout_set = 0,
-               int64_t gf_set = 0) {
-    if (!float_dtype(f_dtype) || !float_dtype(g_dtype) || fH < 1 || fW < 1 || oH < 1 || oW < 1) return LERF_EINVAL;
-    const SetOperand sets[4] = {map_sets(f, f_dtype, f_stride, fH, fW, f_set, true), map_sets(g, g_dtype, g_stride, oH, oW, g_set, false),
-                                dense_sets(grad_out, oH, oW, gout_set, false), dense_sets(grad_f, fH, fW, gf_set, false)};
-    int rc = sets_args(n_sets, sets);
-    if (rc == LERF_OK) rc = invert_bwd_args(f, f_dtype, f_stride, fH, fW, g, g_dtype, g_stride, grad_out, oH, oW, grad_f);
+               const double* grad_out, int oH, int oW, double* grad_f, int n_sets, int64_t f_set, int64_t g_set, int64_t gout_set, int64_t gf_set) {
+    enum { F, G, GOUT, GF };
+    const int rc = check_call(n_sets,
+                              {map_operand(f, f_dtype, f_stride, fH, fW, f_set, SHARE), map_operand(g, g_dtype, g_stride, oH, oW, g_set),
+                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_f, LERF_F64, fH, fW, gf_set)},
+                              {{GF, F}, {GF, G}, {GF, GOUT}}, fH >= 2 && fW >= 2 && tile_ok(oH, oW, 0, 0));
     if (rc != LERF_OK) return rc;
-    if (n_sets > 1 && (sets_overlap(n_sets, sets[3], sets[0]) || sets_overlap(n_sets, sets[3], sets[1]) || sets_overlap(n_sets, sets[3], sets[2])))
-        return LERF_EINVAL;
     LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(g_dtype, TG,
         return run(InvertBwdOp<TF, TG>{{(const TF*)f, f_stride}, fH, fW, {(const TG*)g, g_stride}, {grad_out, 2 * (int64_t)oW}, grad_f, f_set, g_set,
                                        gout_set, gf_set},
@@ -866,121 +785,7 @@ int lerf_coords_build_dev(int model, const double* params_dev, int n_sets, int n
     return build_dev(OnDevice{(hipStream_t)stream}, model, params_dev, n_sets, n_params, out, out_dtype, set_stride, row_stride, oH, oW, i0, j0);
 }
 
-int lerf_coords_mesh(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
-                     int64_t row_stride, int oH, int oW, int i0, int j0, void* stream) {
-    return mesh(OnDevice{(hipStream_t)stream}, ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
-}
-
-int lerf_coords_mesh_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
-                          int64_t row_stride, int oH, int oW, int i0, int j0) {
-    return mesh(OnHost{}, ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0);
-}
-
-int lerf_coords_compose(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
-                        void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, void* stream) {
-    return compose(OnDevice{(hipStream_t)stream}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
-}
-
-int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
-                             int64_t b_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW) {
-    return compose(OnHost{}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW);
-}
-
-int lerf_coords_invert(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
-                       int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_iter,
-                       double tol, void* stream) {
-    return invert(OnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype,
-                  out_row_stride, oH, oW, i0, j0, max_iter, tol);
-}
-
-int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
-                            int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
-                            int max_iter, double tol) {
-    return invert(OnHost{}, f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW, i0, j0,
-                  max_iter, tol);
-}
-
-int lerf_coords_invert_raster(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out, int out_dtype,
-                              int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, void* stream) {
-    return invert_raster(OnDevice{(hipStream_t)stream}, ScatterOnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, depth, out,
-                         out_dtype, out_row_stride, oH, oW, i0, j0, max_span, orient, keys);
-}
-
-int lerf_coords_invert_raster_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out,
-                                   int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient,
-                                   uint64_t* keys) {
-    return invert_raster(OnHost{}, ScatterOnHost{}, f, f_dtype, f_row_stride, fH, fW, depth, out, out_dtype, out_row_stride, oH, oW, i0, j0,
-                         max_span, orient, keys);
-}
-
-int lerf_coords_compose_bwd(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
-                            const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, void* stream) {
-    return compose_bwd(OnDevice{(hipStream_t)stream}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
-}
-
-int lerf_coords_compose_bwd_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
-                                 int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
-    return compose_bwd(OnHost{}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b);
-}
-
-int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_row_stride,
-                           const double* grad_out, int oH, int oW, double* grad_f, void* stream) {
-    return invert_bwd(OnDevice{(hipStream_t)stream}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
-}
-
-int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
-                                int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f) {
-    return invert_bwd(OnHost{}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f);
-}
-
-size_t lerf_coords_mesh_bwd_workspace_bytes(int gh, int gw, int oH, int oW) {
-    if (gh < 2 || gw < 2 || oH < 1 || oW < 1) return 0;
-    return (size_t)gh * (size_t)oW * 2 * sizeof(double);
-}
-
-static int mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace, size_t workspace_bytes,
-                    int n_sets, int64_t gmap_set, int64_t gctrl_set, void* stream) {
-    if (!grad_map || !grad_ctrl || !workspace || oH < 1 || oW < 1 || gh < 2 || gw < 2) return LERF_EINVAL;
-    const SetOperand sets[2] = {dense_sets(grad_map, oH, oW, gmap_set, false), dense_sets(grad_ctrl, gh, gw, gctrl_set, false)};
-    const int rc = sets_args(n_sets, sets);
-    if (rc != LERF_OK) return rc;
-    if (interp != LERF_MESH_BILINEAR && interp != LERF_MESH_BICUBIC) return LERF_EINVAL;
-    if ((size_t)(uintptr_t)grad_map % 16 != 0 || (size_t)(uintptr_t)grad_ctrl % 16 != 0 || (size_t)(uintptr_t)workspace % 16 != 0) return LERF_EINVAL;
-    const size_t need = (size_t)n_sets * lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW);
-    if (workspace_bytes < need || gh > 65535) return LERF_EINVAL;
-    if (n_sets > 1) {
-        const SetOperand ws = {workspace, 1, (int64_t)need, 0, false, true};
-        if (sets_overlap(n_sets, sets[1], sets[0]) || sets_overlap(n_sets, ws, sets[0]) || sets_overlap(n_sets, ws, sets[1])) return LERF_EINVAL;
-    }
-    clear_stale_error();
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + CB_COLS - 1) / CB_COLS, gh, n_sets), b2(64), g2(gw, gh, n_sets);
-    const double2* gm = reinterpret_cast<const double2*>(grad_map);
-    double2* tmp = reinterpret_cast<double2*>(workspace);
-    double2* gc = reinterpret_cast<double2*>(grad_ctrl);
-    const int64_t gm_set = gmap_set / 2, gc_set = gctrl_set / 2;              // in entries
-    if (interp == LERF_MESH_BILINEAR) {
-        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BILINEAR>), g1, b1, 0, st, gm, oH, oW, gh, tmp, gm_set);
-        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BILINEAR>), g2, b2, 0, st, tmp, oW, gw, gc, gc_set);
-    } else {
-        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BICUBIC>), g1, b1, 0, st, gm, oH, oW, gh, tmp, gm_set);
-        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BICUBIC>), g2, b2, 0, st, tmp, oW, gw, gc, gc_set);
-    }
-    return launch_status();
-}
-
-int lerf_coords_mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
-                         size_t workspace_bytes, void* stream) {
-    return mesh_bwd(grad_map, oH, oW, interp, gh, gw, grad_ctrl, workspace, workspace_bytes, 1, 0, 0, stream);
-}
-
-int lerf_coords_mesh_bwd_batched(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
-                                 size_t workspace_bytes, int n_sets, int64_t grad_map_set_stride, int64_t grad_ctrl_set_stride, void* stream) {
-    return mesh_bwd(grad_map, oH, oW, interp, gh, gw, grad_ctrl, workspace, workspace_bytes, n_sets, grad_map_set_stride, grad_ctrl_set_stride,
-                    stream);
-}
-
-// the batched forms: the same templates with n_sets and the set strides passed on
+// the batched forms: the one way into each template (the single-map entry points below call these with n_sets = 1, set strides 0)
 int lerf_coords_mesh_batched(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
                              int64_t row_stride, int oH, int oW, int i0, int j0, int n_sets, int64_t ctrl_set_stride, int64_t out_set_stride,
                              void* stream) {
@@ -1073,6 +878,115 @@ int lerf_coords_invert_bwd_batched_host(const void* f, int f_dtype, int64_t f_ro
                       g_set_stride, grad_out_set_stride, grad_f_set_stride);
 }
 
+// the single-map entry points: the batched one with one set
+int lerf_coords_mesh(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+                     int64_t row_stride, int oH, int oW, int i0, int j0, void* stream) {
+    return lerf_coords_mesh_batched(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0, 1, 0, 0, stream);
+}
+
+int lerf_coords_mesh_host(const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
+                          int64_t row_stride, int oH, int oW, int i0, int j0) {
+    return lerf_coords_mesh_batched_host(ctrl, ctrl_dtype, gh, gw, interp, full_h, full_w, out, out_dtype, row_stride, oH, oW, i0, j0, 1, 0, 0);
+}
+
+int lerf_coords_compose(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
+                        void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, void* stream) {
+    return lerf_coords_compose_batched(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW, 1, 0, 0, 0, stream);
+}
+
+int lerf_coords_compose_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                             int64_t b_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW) {
+    return lerf_coords_compose_batched_host(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, out, out_dtype, out_row_stride, oH, oW, 1, 0, 0, 0);
+}
+
+int lerf_coords_invert(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                       int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_iter,
+                       double tol, void* stream) {
+    return lerf_coords_invert_batched(f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH, oW,
+                                      i0, j0, max_iter, tol, 1, 0, 0, 0, stream);
+}
+
+int lerf_coords_invert_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* init, int init_dtype,
+                            int64_t init_row_stride, void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                            int max_iter, double tol) {
+    return lerf_coords_invert_batched_host(f, f_dtype, f_row_stride, fH, fW, init, init_dtype, init_row_stride, out, out_dtype, out_row_stride, oH,
+                                           oW, i0, j0, max_iter, tol, 1, 0, 0, 0);
+}
+
+int lerf_coords_invert_raster(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out, int out_dtype,
+                              int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, void* stream) {
+    return lerf_coords_invert_raster_batched(f, f_dtype, f_row_stride, fH, fW, depth, out, out_dtype, out_row_stride, oH, oW, i0, j0, max_span,
+                                             orient, keys, 1, 0, 0, 0, 0, stream);
+}
+
+int lerf_coords_invert_raster_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const float* depth, void* out,
+                                   int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient,
+                                   uint64_t* keys) {
+    return lerf_coords_invert_raster_batched_host(f, f_dtype, f_row_stride, fH, fW, depth, out, out_dtype, out_row_stride, oH, oW, i0, j0, max_span,
+                                                  orient, keys, 1, 0, 0, 0, 0);
+}
+
+int lerf_coords_compose_bwd(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_row_stride,
+                            const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, void* stream) {
+    return lerf_coords_compose_bwd_batched(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b, 1, 0, 0, 0, 0,
+                                           0, stream);
+}
+
+int lerf_coords_compose_bwd_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                 int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b) {
+    return lerf_coords_compose_bwd_batched_host(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b, 1, 0, 0,
+                                                0, 0, 0);
+}
+
+int lerf_coords_invert_bwd(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_row_stride,
+                           const double* grad_out, int oH, int oW, double* grad_f, void* stream) {
+    return lerf_coords_invert_bwd_batched(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f, 1, 0, 0, 0, 0, stream);
+}
+
+int lerf_coords_invert_bwd_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f) {
+    return lerf_coords_invert_bwd_batched_host(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f, 1, 0, 0, 0, 0);
+}
+
+size_t lerf_coords_mesh_bwd_workspace_bytes(int gh, int gw, int oH, int oW) {
+    if (gh < 2 || gw < 2 || oH < 1 || oW < 1) return 0;
+    return (size_t)gh * (size_t)oW * 2 * sizeof(double);
+}
+
+int lerf_coords_mesh_bwd_batched(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
+                                 size_t workspace_bytes, int n_sets, int64_t gmap_set, int64_t gctrl_set, void* stream) {
+    enum { GMAP, GCTRL, WS };
+    if (!grad_map || !grad_ctrl || !workspace) return LERF_EINVAL;          // this entry point names a null pointer before it looks at n_sets
+    const size_t per_set = lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW);
+    const bool batch = n_sets > 1;
+    const int rc = check_call(n_sets,
+                              {dense_operand(grad_map, LERF_F64, oH, oW, gmap_set), dense_operand(grad_ctrl, LERF_F64, gh, gw, gctrl_set, 0, 2),
+                               bytes_operand(workspace, (int64_t)per_set, 16)},
+                              {{GCTRL, GMAP, batch}, {WS, GMAP, batch}, {WS, GCTRL, batch}},
+                              (interp == LERF_MESH_BILINEAR || interp == LERF_MESH_BICUBIC) && workspace_bytes >= (size_t)n_sets * per_set && gh <= 65535);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + CB_COLS - 1) / CB_COLS, gh, n_sets), b2(64), g2(gw, gh, n_sets);
+    const double2* gm = reinterpret_cast<const double2*>(grad_map);
+    double2* tmp = reinterpret_cast<double2*>(workspace);
+    double2* gc = reinterpret_cast<double2*>(grad_ctrl);
+    const int64_t gm_set = gmap_set / 2, gc_set = gctrl_set / 2;              // in entries
+    if (interp == LERF_MESH_BILINEAR) {
+        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BILINEAR>), g1, b1, 0, st, gm, oH, oW, gh, tmp, gm_set);
+        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BILINEAR>), g2, b2, 0, st, tmp, oW, gw, gc, gc_set);
+    } else {
+        hipLaunchKernelGGL((coords_mesh_bwd_rows_kernel<LERF_MESH_BICUBIC>), g1, b1, 0, st, gm, oH, oW, gh, tmp, gm_set);
+        hipLaunchKernelGGL((coords_mesh_bwd_cols_kernel<LERF_MESH_BICUBIC>), g2, b2, 0, st, tmp, oW, gw, gc, gc_set);
+    }
+    return launch_status();
+}
+
+int lerf_coords_mesh_bwd(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return lerf_coords_mesh_bwd_batched(grad_map, oH, oW, interp, gh, gw, grad_ctrl, workspace, workspace_bytes, 1, 0, 0, stream);
+}
+
 size_t lerf_coords_build_bwd_workspace_bytes(int n_params, int n_sets, int oH, int oW) {
     if (n_params < 1 || n_params > kMaxParams || n_sets < 1 || n_sets > 65535 || oH < 1 || oW < 1) return 0;
     return (size_t)n_sets * (size_t)n_params * (size_t)build_bwd_blocks(oH, oW) * sizeof(double);
@@ -1080,14 +994,10 @@ size_t lerf_coords_build_bwd_workspace_bytes(int n_params, int n_sets, int oH, i
 
 int lerf_coords_build_bwd(int model, const double* params_dev, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
                           double* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
-    const int rc = build_bwd_args(model, params_dev, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params);
+    const int rc = build_bwd_args(model, params_dev, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params,
+                                  bytes_operand(workspace, (int64_t)lerf_coords_build_bwd_workspace_bytes(n_params, 1, oH, oW), 16),
+                                  workspace_bytes >= lerf_coords_build_bwd_workspace_bytes(n_params, n_sets, oH, oW));
     if (rc != LERF_OK) return rc;
-    const size_t need = lerf_coords_build_bwd_workspace_bytes(n_params, n_sets, oH, oW);
-    if (!workspace || (size_t)(uintptr_t)workspace % 16 != 0 || workspace_bytes < need) return LERF_EINVAL;
-    if (bytes_overlap(workspace, need, grad_params, (size_t)n_sets * n_params * sizeof(double)) ||
-        bytes_overlap(workspace, need, params_dev, (size_t)n_sets * n_params * sizeof(double)) ||
-        bytes_overlap(workspace, need, grad_map, (size_t)n_sets * oH * oW * 2 * sizeof(double)))
-        return LERF_EINVAL;
     clear_stale_error();
     hipStream_t st = (hipStream_t)stream;
     const dim3 b1(CB_COLS, CB_ROWS), g1((oW + kBwdCols - 1) / kBwdCols, (oH + kBwdBand - 1) / kBwdBand, n_sets), b2(64), g2(n_params, n_sets);
@@ -1121,7 +1031,7 @@ int lerf_coords_math_host(int op, const double* x, const double* y, int64_t n, d
 int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
                                double* grad_params) {
 #pragma clang fp contract(off)
-    const int rc = build_bwd_args(model, params, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params);
+    const int rc = build_bwd_args(model, params, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params, bytes_operand(nullptr, 0, 16, OPTIONAL), true);
     if (rc != LERF_OK) return rc;
     const int nbx = (oW + kBwdCols - 1) / kBwdCols, nby = (oH + kBwdBand - 1) / kBwdBand, nblk = nbx * nby;
     std::vector<double> part((size_t)n_params * nblk);

@@ -6,7 +6,7 @@ functors of csrc/lerf_coords.hip under OnHost / ScatterOnHost with sets > 1) and
      NaN, +-inf and 1e300 entries, one that folds), and the NaN sample leaves its neighbours' results unchanged;
   3. strides: padded set and row strides with a sentinel in every gap, tiles at a non-zero origin, float32 / float64 mixes;
   4. sharing: a shared outer map, F, init and depth; a shared grad_a is the single-map twin accumulated in set order, bit for bit;
-     n_sets = 1 with strides 0 is the plain entry point;
+     n_sets = 1 with strides 0 is the plain entry point, for valid calls and for any fuzzed argument tuple;
   5. every refused argument returns its code and writes nothing, on the host twins and (without a GPU) on the device entry points;
   6. coords.* on numpy batches: the per-sample results, from ONE call of the batched entry point.
 
@@ -363,6 +363,30 @@ def test_one_set_with_strides_zero_is_the_plain_entry_point():
     assert _compose_bwd_raw(L.lerf_coords_compose_bwd_batched_host, a, b, g, ga, gb, 1, (0, 0, 0, 0, 0)) == 0
     ra, rb = _lib.coords_compose_bwd_host(a, b, g)
     assert R.same_bits(ga, ra) and R.same_bits(gb, rb)
+
+
+def test_any_single_map_call_is_the_batched_call_of_one_set():
+    """Not the valid calls alone: 2 000 argument tuples per chained operation from the generator of tools/fuzz_coords_args.py (a valid
+    call on shapes <= 6 x 6 with zero to two arguments replaced by a value the contract tells apart; one arena holds every operand).
+    The single-map host twin and the batched host twin with n_sets = 1 and every set stride 0 return the same code and leave the same
+    bytes, and a refused call leaves the arena as it found it."""
+    import sys
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import fuzz_coords_args as Z
+    L = _lib.lib()
+    arena = Z.Arena()
+    untouched_arena = arena.fresh.tobytes()
+    for op in Z.CHAINED:
+        single, batched = getattr(L, "lerf_coords_%s_host" % op), getattr(L, "lerf_coords_%s_batched_host" % op)
+        codes = {0: 0, EINVAL: 0}
+        for args, args_of_one_set in Z.single_and_batched(op, 2000, seed=1):
+            rc, _ = Z.run_case(single, arena, args)
+            left = arena.buf.tobytes()
+            rc_b, _ = Z.run_case(batched, arena, args_of_one_set)
+            assert rc_b == rc and arena.buf.tobytes() == left, (op, args)
+            assert rc == 0 or left == untouched_arena, (op, args)
+            codes[rc] += 1
+        assert min(codes.values()) >= 500 and sum(codes.values()) == 2000, (op, codes)          # the generator accepts and refuses
 
 
 # ---------------------------------------------------------------------------------------------- 5. refusals
