@@ -909,6 +909,56 @@ enum { LERF_MATH_SQRT = 0, LERF_MATH_ATAN = 1, LERF_MATH_ATAN2 = 2 };
 int lerf_coords_math(int op, const double* x, const double* y, int64_t n, double* out, void* stream);
 int lerf_coords_math_host(int op, const double* x, const double* y, int64_t n, double* out);
 
+/* Reproject by depth (the rounding order of every statement and the order of the sums: the top of
+ * csrc/lerf_coords_models.h): the map that carries view A, with a depth per pixel, into view B.  Entry (i, j) of set s is the
+ * position (row, col) in view B of pixel (i0 + i, j0 + j) of view A, and depth_out its depth there:
+ *     a = M (x, y, 1),  x = j0 + j, y = i0 + i
+ *     LERF_DEPTH_Z       (depth = z):      (X, Y, W) = a z + q,    zo = W
+ *     LERF_DEPTH_INVERSE (depth = d = 1/z): (X, Y, W) = a + q d,   zo = W / d   (d == 0, a point at infinity: a finite entry, zo = +inf)
+ *     col = X / W,  row = Y / W
+ * with M = K_dst . R . inv(K_src) and q = K_dst . t for X_dst = R X_src + t; the last row of K_dst must be (0, 0, 1) for zo to be
+ * the depth in view B.  An entry is VALID when z > 0 (d >= 0), the depth is finite and W > 0; any other entry is (NaN, NaN) with
+ * zo = NaN, which the remap treats as "no source" and the rasterising inverse skips.
+ * params_dev: float64 [n_sets][LERF_REPROJECT_PARAMS] = m[9] row-major then q[3], dense, DEVICE memory for lerf_coords_reproject
+ * (non-finite parameters are not refused, as for lerf_coords_build_dev) and host memory for the host twins.  depth: one dense plane
+ * [oH][oW] of depth_dtype (LERF_F32, promoted exactly, or LERF_F64) per set -- the TILE's own plane -- set s at depth + s *
+ * depth_set_stride elements (>= oH * oW, or 0 = one plane shared by all sets).  out: n_sets maps under the strided contract, map s at
+ * out + s * out_set_stride elements (even, >= (oH - 1) * out_row_stride + 2 * oW for n_sets > 1).  depth_out: float [oH][oW] per
+ * set, dense, set s at depth_out + s * depth_out_set_stride (>= oH * oW for n_sets > 1) -- the layout lerf_coords_invert_raster's
+ * depth reads -- or NULL.  A float32 map or zo is the float64 value rounded once at the store.  One launch, one thread per entry, one
+ * map store per entry and one zo store when depth_out is given; no atomics, no allocation, no sync.  The host twin is bit-equal.
+ *
+ * lerf_coords_reproject_bwd ACCUMULATES the adjoint: grad_map float64 [n_sets][oH][oW][2] dense (required), grad_depth_out float64
+ * [n_sets][oH][oW] dense, the upstream of zo (NULL: none); grad_depth float64 [n_sets][oH][oW] gains d loss / d depth of every
+ * entry by a plain load-add-store with one writer per entry (a shared depth plane still has one gradient plane per set);
+ * grad_params float64 [n_sets][12] gains the sums over the entries of set s.  Either may be NULL to skip that half; both NULL is
+ * refused.  An entry that is not valid contributes EXACTLY NOTHING to either, whatever the upstreams hold (lerf_coords_build_bwd's
+ * rule); a zo that is not finite takes nothing from grad_depth_out.  grad_params is summed by lerf_coords_build_bwd's two passes
+ * in its order -- a function of (oH, oW, n_sets) only, no atomics -- so two runs are bit-equal and lerf_coords_reproject_bwd_host
+ * equals the device bit for bit.  workspace: device, >= lerf_coords_reproject_bwd_workspace_bytes(n_sets, oH, oW) bytes (n_sets * 12 *
+ * ceil(oW / 64) * ceil(oH / 64) doubles; 0 from the query for refused sizes), 16-byte aligned, needed when grad_params is given
+ * (else ignored: NULL will do).  One launch (two with grad_params) on `stream`, no sync, no allocation.
+ * Refused with LERF_EINVAL, launching and writing nothing: the family's list (a null required pointer, misalignment, an odd or
+ * short row stride, a bad dtype, oH or oW < 1, a bad tile origin), an unknown kind, n_sets outside 1 .. 65535, a set stride that is
+ * negative, odd (out) or short, a short or misaligned workspace, and the bytes of any output (out, depth_out, grad_depth,
+ * grad_params, the workspace) intersecting an operand's or another output's. */
+enum { LERF_DEPTH_Z = 0, LERF_DEPTH_INVERSE = 1 };
+#define LERF_REPROJECT_PARAMS 12
+int lerf_coords_reproject(int kind, const double* params_dev, int n_sets, const void* depth, int depth_dtype,
+                          int64_t depth_set_stride, void* out, int out_dtype, int64_t out_set_stride, int64_t out_row_stride,
+                          float* depth_out, int64_t depth_out_set_stride, int oH, int oW, int i0, int j0, void* stream);
+int lerf_coords_reproject_host(int kind, const double* params, int n_sets, const void* depth, int depth_dtype,
+                               int64_t depth_set_stride, void* out, int out_dtype, int64_t out_set_stride, int64_t out_row_stride,
+                               float* depth_out, int64_t depth_out_set_stride, int oH, int oW, int i0, int j0);
+size_t lerf_coords_reproject_bwd_workspace_bytes(int n_sets, int oH, int oW);
+int lerf_coords_reproject_bwd(int kind, const double* params_dev, int n_sets, const void* depth, int depth_dtype,
+                              int64_t depth_set_stride, const double* grad_map, const double* grad_depth_out, int oH, int oW,
+                              int i0, int j0, double* grad_depth, double* grad_params,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int lerf_coords_reproject_bwd_host(int kind, const double* params, int n_sets, const void* depth, int depth_dtype,
+                                   int64_t depth_set_stride, const double* grad_map, const double* grad_depth_out, int oH, int oW,
+                                   int i0, int j0, double* grad_depth, double* grad_params);
+
 /* The chained operations on a BATCH of n_sets maps in one launch: each entry point below is its single-map form with
  * n_sets and one SET STRIDE per operand appended; set s reads and writes operand base + s * set_stride ELEMENTS (of the operand's own
  * dtype: a map's floats or doubles, a float64 gradient's doubles, keys' uint64, depth's floats; the workspace of the mesh adjoint is

@@ -61,6 +61,8 @@ EXPORTS = [
     "lerf_coords_mesh_batched", "lerf_coords_mesh_batched_host", "lerf_coords_mesh_bwd_batched", "lerf_coords_compose_batched", "lerf_coords_compose_batched_host",
     "lerf_coords_invert_batched", "lerf_coords_invert_batched_host", "lerf_coords_invert_raster_batched", "lerf_coords_invert_raster_batched_host",
     "lerf_coords_compose_bwd_batched", "lerf_coords_compose_bwd_batched_host", "lerf_coords_invert_bwd_batched", "lerf_coords_invert_bwd_batched_host",
+    "lerf_coords_reproject", "lerf_coords_reproject_host", "lerf_coords_reproject_bwd_workspace_bytes", "lerf_coords_reproject_bwd",
+    "lerf_coords_reproject_bwd_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -335,6 +337,15 @@ def lib():
         getattr(L, "lerf_coords_%s_batched" % name).argtypes = batched + [C.c_void_p]
         getattr(L, "lerf_coords_%s_batched_host" % name).argtypes = batched
     L.lerf_coords_mesh_bwd_batched.argtypes = L.lerf_coords_mesh_bwd.argtypes[:-1] + [C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+    _reproject = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                  C.c_int, C.c_int, C.c_int, C.c_int]
+    L.lerf_coords_reproject.argtypes, L.lerf_coords_reproject_host.argtypes = _reproject + [C.c_void_p], _reproject
+    _reproject_bwd = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                      C.c_void_p, C.c_void_p]
+    L.lerf_coords_reproject_bwd.argtypes = _reproject_bwd + [C.c_void_p, C.c_size_t, C.c_void_p]
+    L.lerf_coords_reproject_bwd_host.argtypes = _reproject_bwd
+    L.lerf_coords_reproject_bwd_workspace_bytes.restype = C.c_size_t
+    L.lerf_coords_reproject_bwd_workspace_bytes.argtypes = [C.c_int] * 3
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -545,6 +556,10 @@ class HostOperands(_Operands):
     def call(self, name, anchor, *args):
         check(getattr(lib(), name)(*args), name)
 
+    def workspace(self, nbytes, device):
+        """the workspace arguments of a host twin: none (the host sums in place)"""
+        return ()
+
 
 class DeviceOperands(_Operands):
     suffix, noun = "", "a device tensor"
@@ -589,6 +604,14 @@ class DeviceOperands(_Operands):
         with on_device(anchor):
             check(getattr(lib(), name)(*args, current_stream(anchor.device)), name)
 
+    def workspace(self, nbytes, device):
+        """(pointer, bytes) of the per-stream scratch the adjoints share (ops._cached_workspace); nbytes 0: (None, 0)"""
+        if not nbytes:
+            return None, 0
+        from . import ops
+        ws = ops._cached_workspace(nbytes, device)
+        return ws.data_ptr(), ws.numel()
+
 
 def coords_model_count(model, n, what):
     """ValueError unless `model` is known and takes n parameters"""
@@ -617,7 +640,8 @@ _HOST = HostOperands()
 # The eight operations that exist on both sides, over X = HostOperands() or DeviceOperands(): ops.coords_* and coords_*_host below
 # bind them and carry the documentation.  Mesh, compose, invert, invert_raster and the two adjoints take a leading B on their maps
 # ([B, h, w, 2]) and then make ONE call of the batched entry point (lerf_coords_*_batched); a 3-D operand beside a batch is shared
-# where the C contract allows it.
+# where the C contract allows it.  Reproject and its adjoint (coords_reproject_on, coords_reproject_bwd_on) are on both sides too: their
+# batch is the entry point's own n_sets, one parameter set per depth plane.
 def coords_build_on(X, model, params, out_hw, dtype, out, origin, device=None):
     what = "lerf_coords_build" + X.suffix
     code, p = coords_model_params(model, params, what)
@@ -741,6 +765,58 @@ def coords_invert_bwd_on(X, f, inverse, grad_out, grad_f):
     return gf
 
 
+DEPTH_KINDS = {"z": 0, "inverse": 1}          # LERF_DEPTH_Z, LERF_DEPTH_INVERSE
+REPROJECT_PARAMS = 12                         # m[9] = K_dst . R . inv(K_src) row-major, q[3] = K_dst . t
+
+
+def _reproject_operands(X, what, kind, params, depth):
+    """(kind code, params, depth, B, depth's set stride, (H, W)): params float64 [12] with depth [H, W], or [B, 12] with depth [B, H, W] or
+    one shared [H, W]; B = 0 for the single form"""
+    if kind not in DEPTH_KINDS:
+        raise ValueError("%s: kind is one of %s, not %r" % (what, ", ".join(DEPTH_KINDS), kind))
+    if not X.is_array(params) or params.dtype != X.f64 or params.ndim not in (1, 2) or params.shape[-1] != REPROJECT_PARAMS or params.shape[0] < 1:
+        raise ValueError("%s: params must be float64 %s [%d] or [B, %d]" % (what, X.noun, REPROJECT_PARAMS, REPROJECT_PARAMS))
+    if not X.is_array(depth) or not X.is_float(depth) or depth.ndim not in (2, 3) or min(depth.shape) < 1:
+        raise ValueError("%s: depth must be float32 or float64 %s [H, W] or [B, H, W]" % (what, X.noun))
+    B = params.shape[0] if params.ndim == 2 else 0
+    if depth.ndim == 3 and depth.shape[0] != B:
+        raise ValueError("%s: a batch of depth planes [B, H, W] needs params [B, %d]" % (what, REPROJECT_PARAMS))
+    X.one_device(what, ("params", "depth"), params, depth)
+    hw = (int(depth.shape[-2]), int(depth.shape[-1]))
+    return DEPTH_KINDS[kind], X.contiguous(params), X.contiguous(depth), B, (hw[0] * hw[1] if B > 1 and depth.ndim == 3 else 0), hw
+
+
+def coords_reproject_on(X, kind, params, depth, dtype, out, origin, depth_out):
+    what = "lerf_coords_reproject" + X.suffix
+    code, p, d, B, d_set, hw = _reproject_operands(X, what, kind, params, depth)
+    out, so, to = X.outs(out, B, hw, dtype, X.f64, X.device(d), what)
+    X.one_device(what, ("depth", "out"), d, out)
+    zo = None
+    if depth_out is not None and depth_out is not False:
+        zo = X.dense(None if depth_out is True else depth_out, ((B,) if B else ()) + hw, X.f32, X.device(d), what + ": depth_out")
+    X.call(what, d, code, X.ptr(p), max(B, 1), X.ptr(d), X.code(d), d_set, X.ptr(out), X.code(out), to, so, X.ptr(zo),
+           hw[0] * hw[1] if B > 1 else 0, hw[0], hw[1], int(origin[0]), int(origin[1]))
+    return out if zo is None else (out, zo)
+
+
+def coords_reproject_bwd_on(X, kind, params, depth, grad_map, grad_depth_out, grad_depth, grad_params, need, origin):
+    what = "lerf_coords_reproject_bwd" + X.suffix
+    code, p, d, B, d_set, hw = _reproject_operands(X, what, kind, params, depth)
+    lead, dev = ((B,) if B else ()), X.device(d)
+    if grad_map is None:
+        raise ValueError("%s: grad_map must be contiguous float64 %s" % (what, list(lead + hw + (2,))))
+    if not (need[0] or need[1]):
+        raise ValueError("%s: at least one of the two gradients is needed" % what)
+    g = X.grad(grad_map, lead + hw + (2,), dev, what + ": grad_map")
+    gz = None if grad_depth_out is None else X.grad(grad_depth_out, lead + hw, dev, what + ": grad_depth_out")
+    gd = X.grad(grad_depth, lead + hw, dev, what + ": grad_depth") if need[0] else None
+    gp = X.grad(grad_params, tuple(p.shape), dev, what + ": grad_params") if need[1] else None
+    ws = X.workspace(int(lib().lerf_coords_reproject_bwd_workspace_bytes(max(B, 1), hw[0], hw[1])) if need[1] else 0, dev)
+    X.call(what, d, code, X.ptr(p), max(B, 1), X.ptr(d), X.code(d), d_set, X.ptr(g), X.ptr(gz), hw[0], hw[1], int(origin[0]), int(origin[1]),
+           X.ptr(gd), X.ptr(gp), *ws)
+    return gd, gp
+
+
 def coords_math_on(X, op, x, y):
     what = "lerf_coords_math" + X.suffix
     if op not in COORDS_MATH_OPS:
@@ -825,6 +901,25 @@ def coords_build_bwd_host(model, params, grad_map, origin=(0, 0)):
                                            g.shape[-3], g.shape[-2], int(origin[0]), int(origin[1]), out.ctypes.data),
           "lerf_coords_build_bwd_host")
     return out
+
+
+def coords_reproject_host(kind, params, depth, dtype=np.float64, out=None, origin=(0, 0), depth_out=None):
+    """lerf_coords_reproject_host: the map that carries a view with a depth per pixel into another view, by the host loop over the
+    kernel's own statements (bit-equal to ops.coords_reproject).  kind "z" (depth) or "inverse" (1 / depth); params float64 [12] =
+    (K_dst . R . inv(K_src))[9], (K_dst . t)[3] with depth [H, W] float32 / float64, or [B, 12] with depth [B, H, W] or one shared
+    [H, W] -> the map [H, W, 2] or [B, H, W, 2], (NaN, NaN) where the entry is not valid.  out: an array or a strided tile view, whose
+    depth plane is the TILE's, at `origin` of the whole map.  depth_out: True or a float32 array of depth's shape -> (map, zo), zo the
+    depth in the other view, what coords_invert_raster_host takes as depth."""
+    return coords_reproject_on(_HOST, kind, params, depth, dtype, out, origin, depth_out)
+
+
+def coords_reproject_bwd_host(kind, params, depth, grad_map, grad_depth_out=None, grad_depth=None, grad_params=None, need=(True, True),
+                              origin=(0, 0)):
+    """lerf_coords_reproject_bwd_host: ACCUMULATE the adjoint of coords_reproject_host of grad_map (float64 contiguous, the map's
+    shape) and grad_depth_out (float64, zo's shape, or None) into grad_depth (float64, depth's batch shape) and grad_params (float64,
+    params' shape); None: zeroed ones; need[k] False skips that half and returns None for it -> (grad_depth, grad_params).  The sums
+    run in the device's order: bit-equal to ops.coords_reproject_bwd."""
+    return coords_reproject_bwd_on(_HOST, kind, params, depth, grad_map, grad_depth_out, grad_depth, grad_params, need, origin)
 
 
 def coords_math_host(op, x, y=None):

@@ -30,6 +30,17 @@ invert_flow_torch (device tensors only) run the same forward kernels and keep th
 adjoints lerf_coords_compose_bwd and lerf_coords_invert_bwd, so a loss reaches a flow or a control mesh through
 chained maps: coarse-to-fine refinement (compose_torch(upsampled, residual)), scaling and squaring (compose_torch(phi, phi)),
 inverse-consistency losses (invert_torch).  Once differentiable; init, max_iter and tol have no gradient.
+
+reproject turns a DEPTH image and a camera pose into a map (lerf_coords_reproject): pixel (i, j) of one view, lifted by
+its depth (or inverse depth) and moved by X_dst = R X_src + t, lands at (row, col) of the other view; with return_depth=True its
+depth there comes back too, the plane invert_raster's depth test reads.  Two chains end in a remap:
+
+    remap(img_src, reproject(depth_dst, K_dst, K_src, R, t))                  backward warp: the target's depth reads the source
+    m, z = reproject(depth_src, K_src, K_dst, R, t, return_depth=True)
+    remap(img_src, invert_raster(m, hw, depth=z, orient=1))                   forward splat: the nearest surface wins, holes stay NaN
+
+reproject_torch (with reproject_params_torch) is the differentiable twin: depth, K_src, K_dst, R and t receive gradients through
+lerf_coords_reproject_bwd -- float64, a fixed summation order, an entry that is not valid contributes nothing.
 """
 from __future__ import annotations
 
@@ -836,3 +847,177 @@ def equirect_view_torch(pano_hw, K_view, R, out_hw, dtype=None):
     pano = torch.tensor([Wp / (2.0 * np.pi), Hp / np.pi, (Wp - 1) / 2.0, (Hp - 1) / 2.0], dtype=torch.float64, device=K_view.device)
     params = torch.cat([cam[..., :9], pano.expand(tuple(cam.shape[:-1]) + (4,))], dim=-1)
     return _build_torch("equirect", params, out_hw, _map_dtype(dtype, K_view.dtype))
+
+
+# ---------------------------------------------------------------------------------------------- reproject by depth
+def _last_row_ok(K_dst):
+    return bool(np.all(K_dst[..., 2, 0] == 0.0) and np.all(K_dst[..., 2, 1] == 0.0) and np.all(K_dst[..., 2, 2] == 1.0))
+
+
+def reproject_params(K_src, K_dst, R=None, t=None):
+    """The 12 parameters of reproject from two cameras and a pose: K_src, K_dst (3 x 3 camera matrices; the last row of K_dst must be
+    (0, 0, 1), so that the third homogeneous coordinate is the depth in the second view), R (3 x 3, default I) and t (3, default 0) with
+    X_dst = R X_src + t -> float64 [12] = (K_dst . R . inv(K_src))[9] row-major, (K_dst . t)[3]; the inverse is np.linalg.inv's.  Any
+    operand may carry a leading B (the others are shared) -> [B, 12].  Host numpy."""
+    Ks, Kd = _host(K_src), _host(K_dst)
+    Rm = np.eye(3) if R is None else _host(R)
+    tv = np.zeros(3) if t is None else _host(t)
+    for a, name, nd in ((Ks, "K_src", 2), (Kd, "K_dst", 2), (Rm, "R", 2), (tv, "t", 1)):
+        if a.ndim not in (nd, nd + 1) or a.shape[-nd:] != (3,) * nd or a.shape[0] < 1:
+            raise ValueError("%s must be %s, or that behind a leading batch size" % (name, "3x3" if nd == 2 else "[3]"))
+    if not _last_row_ok(Kd):
+        raise ValueError("the last row of K_dst must be (0, 0, 1): reproject's third coordinate is the depth in the second view")
+    sizes = {a.shape[0] for a, nd in ((Ks, 2), (Kd, 2), (Rm, 2), (tv, 1)) if a.ndim == nd + 1}
+    if len(sizes) > 1:
+        raise ValueError("the operands hold different numbers of samples")
+    m = np.matmul(np.matmul(Kd, Rm), np.linalg.inv(Ks))
+    q = np.matmul(Kd, tv[..., None])[..., 0]
+    lead = (sizes.pop(),) if sizes else ()
+    return np.ascontiguousarray(np.concatenate([np.broadcast_to(m, lead + (3, 3)).reshape(lead + (9,)), np.broadcast_to(q, lead + (3,))], axis=-1))
+
+
+def reproject_params_torch(K_src, K_dst, R=None, t=None):
+    """reproject_params in torch ops on the operands' device, differentiable in all four: K_src, K_dst [3, 3], R [3, 3] (None:
+    identity), t [3] (None: 0), each a float32 / float64 device tensor, single or behind a leading B (single operands are shared by
+    the batch) -> float64 [12] or [B, 12]: K_dst . R . inv(K_src) by torch.linalg.inv, K_dst . t.  The check of K_dst's last row
+    reads it (one sync)."""
+    import torch
+    what = "reproject_params_torch"
+    ops_, sizes = [K_src, K_dst], [_operand(K_src, what + ": K_src", [(3, 3)]), _operand(K_dst, what + ": K_dst", [(3, 3)])]
+    if R is not None:
+        ops_.append(R), sizes.append(_operand(R, what + ": R", [(3, 3)]))
+    if t is not None:
+        ops_.append(t), sizes.append(_operand(t, what + ": t", [(3,)]))
+    B = _one_batch(what, ops_, sizes)
+    lead = (B,) if B else ()
+    Kd = K_dst.double()
+    with torch.no_grad():
+        if bool(((Kd[..., 2, 0] != 0) | (Kd[..., 2, 1] != 0) | (Kd[..., 2, 2] != 1)).any()):
+            raise ValueError("the last row of K_dst must be (0, 0, 1): reproject's third coordinate is the depth in the second view")
+    KR = Kd if R is None else torch.matmul(Kd, R.double())
+    m = torch.matmul(KR, torch.linalg.inv(K_src.double())).expand(lead + (3, 3))
+    q = torch.zeros(lead + (3,), dtype=torch.float64, device=K_src.device) if t is None else \
+        torch.matmul(Kd, t.double().unsqueeze(-1)).squeeze(-1).expand(lead + (3,))
+    return torch.cat([m.reshape(lead + (9,)), q], dim=-1)
+
+
+def _depth_kind(inverse_depth):
+    return "inverse" if inverse_depth else "z"
+
+
+def reproject(depth, K_src, K_dst, R=None, t=None, inverse_depth=False, dtype=None, return_depth=False):
+    """The map that carries a view with a depth per pixel into another view (lerf_coords_reproject): depth [H, W] (or a
+    batch [B, H, W], one launch) is the depth z of every pixel of the view of K_src -- or 1 / z with inverse_depth=True, where 0 is
+    a point at infinity -- and K_dst, R, t (X_dst = R X_src + t; reproject_params) describe the other view.  -> [H, W, 2] (or
+    [B, H, W, 2]), float64 (default) or float32: entry (i, j) is (row, col) of pixel (i, j) in the other view, (NaN, NaN) where the
+    depth is not positive (inverse: negative), not finite, or the point lies behind the other camera.  return_depth=True -> (map, zo),
+    zo float32 of depth's shape: the depth in the other view (inverse_depth: +inf at infinity), NaN where the map is.
+
+    Two chains end in a remap (names of this module):
+
+        remap(img_src, reproject(depth_dst, K_dst, K_src, R, t))
+            BACKWARD warp: the map of the target view (its own depth, the pose target -> source) reads the source frame -- view
+            synthesis and the photometric loss of self-supervised depth; every target pixel has one source, occlusions are not seen.
+        m, z = reproject(depth_src, K_src, K_dst, R, t, return_depth=True)
+        remap(img_src, invert_raster(m, hw, depth=z, orient=1))
+            FORWARD splat: the source's own depth carries it into the target view, the rasterising inverse lets the nearest surface
+            win where several land on one pixel and leaves the disocclusions NaN (mask false in the remap).
+
+    numpy depth -> numpy (the kernel's host twin); a device tensor -> device tensors written by the kernel, bit-equal to the host's for
+    equal parameters.  The cameras and the pose are host values (arrays, lists, host tensors) or, beside a device depth, tensors on its
+    device; a device tensor beside a host depth, or a host tensor beside a device depth, is refused.  No autograd: an operand that
+    requires grad (with grad mode on) is refused -- reproject_torch is the differentiable twin."""
+    cams = [a for a in (K_src, K_dst, R, t) if a is not None]
+    on_dev = bool(getattr(depth, "is_cuda", False))
+    for a in cams:                                                       # an array or a list has no is_cuda: a host value, taken beside either
+        if hasattr(a, "is_cuda") and bool(a.is_cuda) != on_dev:
+            raise ValueError("reproject: the depth and the cameras on the host or on one device, not mixed")
+    _no_autograd("reproject", [depth] + cams)
+    if getattr(depth, "ndim", None) not in (2, 3) or min(depth.shape) < 1:
+        raise ValueError("reproject: depth is [H, W] or [B, H, W]")
+    p = reproject_params(K_src, K_dst, R, t)
+    B = depth.shape[0] if depth.ndim == 3 else 0
+    if p.ndim == 2 and B and p.shape[0] != B:
+        raise ValueError("reproject: depth and the cameras hold different numbers of samples")
+    if B and p.ndim == 1:
+        p = np.ascontiguousarray(np.broadcast_to(p, (B, 12)))
+    kind, want = _depth_kind(inverse_depth), (True if return_depth else None)
+    if on_dev:
+        import torch
+        from . import ops
+        d = depth.detach()
+        d = d if d.dtype in (torch.float32, torch.float64) else d.double()
+        return ops.coords_reproject(kind, torch.from_numpy(p).to(d.device), d, dtype=getattr(torch, _np_dtype(dtype).name), depth_out=want)
+    from . import _lib
+    d = np.asarray(depth.detach().numpy() if hasattr(depth, "detach") else depth)
+    d = d if d.dtype in (np.float32, np.float64) else d.astype(np.float64)
+    return _lib.coords_reproject_host(kind, p, d, _np_dtype(dtype), depth_out=want)
+
+
+_REPROJECT_FN = None
+
+
+def _reproject_fn():
+    global _REPROJECT_FN
+    if _REPROJECT_FN is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+        from . import ops
+
+        class _ReprojectFn(torch.autograd.Function):
+            """(map[, zo]) = ops.coords_reproject(params, depth); backward: ops.coords_reproject_bwd in float64, the half that is not
+            required skipped; the depth's gradient cast to its dtype, the 12-vector's handed on to autograd"""
+
+            @staticmethod
+            def forward(ctx, depth, params, kind, tdt, want_zo):
+                d, p = depth.detach().contiguous(), params.detach().contiguous()
+                ctx.save_for_backward(d, p)
+                ctx.kind, ctx.depth_dtype = kind, depth.dtype
+                ctx.set_materialize_grads(False)
+                return ops.coords_reproject(kind, p, d, dtype=tdt, depth_out=True if want_zo else None)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, gmap, gzo=None):
+                d, p = ctx.saved_tensors
+                need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+                if (gmap is None and gzo is None) or not (need[0] or need[1]):
+                    return None, None, None, None, None
+                lead = tuple(p.shape[:-1]) + tuple(d.shape[-2:])
+                gm = torch.zeros(lead + (2,), dtype=torch.float64, device=d.device) if gmap is None else gmap.contiguous().double()
+                gz = None if gzo is None else gzo.contiguous().double()
+                gd, gp = ops.coords_reproject_bwd(ctx.kind, p, d, gm, gz, need=need)
+                if gd is not None and gd.ndim > d.ndim:                  # one depth plane shared by the batch: the sum over the samples
+                    gd = gd.sum(0)
+                return None if gd is None else gd.to(ctx.depth_dtype), gp, None, None, None
+
+        _REPROJECT_FN = _ReprojectFn
+    return _REPROJECT_FN
+
+
+def reproject_torch(depth, K_src, K_dst, R=None, t=None, inverse_depth=False, dtype=None, return_depth=False):
+    """reproject on the operands' device, differentiable: depth [H, W] or [B, H, W] and the operands of reproject_params_torch, all
+    float32 / float64 DEVICE tensors (single camera operands are shared by a batch) -> the map (float64, or `dtype`), or (map, zo)
+    with return_depth=True.  depth, K_src, K_dst, R and t each receive a gradient when they require one: the map and zo go through
+    lerf_coords_reproject and its adjoint lerf_coords_reproject_bwd (float64, a fixed summation order: bit-equal from run to run),
+    the 12 parameters' assembly -- the inverse of K_src included -- through autograd.  An entry that is not valid contributes
+    nothing, unlike autograd of the same formulas.  The photometric loss of self-supervised depth and ego-motion: a remap class that
+    has opted in with enable_backward() hands this map its gradient.  Once differentiable."""
+    import torch
+    from . import ops
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dtype not in (torch.float32, torch.float64):
+        raise ValueError("reproject_torch: depth must be a float32 or float64 device tensor")
+    if depth.ndim not in (2, 3) or min(depth.shape) < 1:
+        raise ValueError("reproject_torch: depth is [H, W] or [B, H, W]")
+    params = reproject_params_torch(K_src, K_dst, R, t)
+    if params.device != depth.device:
+        raise ValueError("reproject_torch: the depth and the cameras live on different devices")
+    B = depth.shape[0] if depth.ndim == 3 else 0
+    if params.ndim == 2 and B and params.shape[0] != B:
+        raise ValueError("reproject_torch: depth and the cameras hold different numbers of samples")
+    if B and params.ndim == 1:
+        params = params.expand(B, 12)
+    kind, tdt = _depth_kind(inverse_depth), _map_dtype(dtype, torch.float64)
+    if torch.is_grad_enabled() and (depth.requires_grad or params.requires_grad):
+        return _reproject_fn().apply(depth, params, kind, tdt, bool(return_depth))
+    return ops.coords_reproject(kind, params.detach().contiguous(), depth.detach(), dtype=tdt, depth_out=True if return_depth else None)

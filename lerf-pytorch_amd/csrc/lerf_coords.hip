@@ -4,7 +4,7 @@
 // not from a math library).
 //
 // ONE TEXT FOR DEVICE AND HOST.  Every one-thread-per-entry operation is a small functor op(i, j, s) -- entry (i, j) of set s -- that
-// holds its operands by value (BuildOp, BuildDevOp, MeshOp, ComposeOp, InvertOp, ComposeBwdOp, InvertBwdOp; the notes on loads,
+// holds its operands by value (BuildOp, BuildDevOp, ReprojectOp, MeshOp, ComposeOp, InvertOp, ComposeBwdOp, InvertBwdOp; the notes on loads,
 // stores and atomics are with each).  Two runners with one call shape execute it:
 //   OnDevice{stream}   launches entry_kernel<OP>: block 64 x 4 (4 waves, one row of 64 entries each, so a wave's stores are 64
 //                      consecutive entries of a row), grid (ceil(oW / 64), ceil(oH / 4), sets), the (i, j) guard, blockIdx.z = the set
@@ -45,7 +45,11 @@
 //                LDS and are added in the order 0, 1, 2, 3; ONE partial vector per block goes to the workspace ([set][k][block])
 //       sum      ONE wave per (set, k): lane l adds the partials l, l + 64, ..., the same tree, lane 0 is the one writer (load-add-store)
 //       2160 x 3840: 2 040 blocks a set in pass 1 (8 per CU), 343 KB of partials for the 21 sums of brown; grad_map is read once, coalesced
-//       The host twin emulates the two passes lane by lane (lerf_coords_build_bwd_host, at the end of this file).
+//       The host twin emulates the two passes lane by lane (two_pass_sums_host; lerf_coords_build_bwd_host, at the end of this file).
+//   coords_reproject_bwd_kernel             the adjoint of reproject: pass 1's grid, band and lanes over reproject_point_bwd; every lane adds d depth
+//                                           into grad_depth at its own entries (one writer) and, when grad_params is wanted, keeps 12 running
+//                                           sums that leave as the block's partial vector for coords_build_bwd_sum_kernel -- the same fixed order
+//       2160 x 3840: 2 040 blocks a set, 196 KB of partials; depth, grad_map and grad_depth are each touched once, coalesced
 //   coords_math_kernel                      sqrt_pm / atan_pm / atan2_pm of lerf_coords_models.h, one thread per element: what the fisheye and
 //                                           equirect models are built on, exported so that their bit-equality with the host is tested directly
 //
@@ -146,6 +150,24 @@ struct BuildDevOp {
     LERF_HD void operator()(int i, int j, int s) const {
         const double* p = params + (size_t)s * model_params(MODEL);
         store_entry(out + (int64_t)s * set_stride, stride, i, j, model_point<MODEL>(p, i0 + i, j0 + j));
+    }
+};
+
+// one entry of reproject (reproject_point): the set's 12 parameters at a wave-uniform address (scalar loads), ONE 4- or 8-byte load of
+// the entry's depth (a wave reads 64 consecutive ones), one map store and, with depth_out, one 4-byte store of zo
+template <int KIND, typename TD, typename TO>
+struct ReprojectOp {
+    const double* params;
+    const TD* depth;
+    TO* out;
+    float* zo;
+    int64_t depth_set, out_set, stride, zo_set;
+    int oW, i0, j0;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const int64_t e = (int64_t)i * oW + j;
+        const Reprojected r = reproject_point<KIND>(params + (size_t)s * kReprojectParams, (double)depth[set_offset(s, depth_set) + e], i0 + i, j0 + j);
+        store_entry(out + set_offset(s, out_set), stride, i, j, r.q);
+        if (zo) zo[set_offset(s, zo_set) + e] = (float)r.zo;            // rounded once, here
     }
 };
 
@@ -483,6 +505,51 @@ coords_build_bwd_sum_kernel(const double* __restrict__ part, int nblk, double* _
     if (threadIdx.x == 0) gparams[e] = gparams[e] + v;
 }
 
+// the adjoint of reproject (reproject_point_bwd) in the shape of the build backward's pass 1 -- the same grid, block, band and lanes; part
+// [n_sets][12][nblk].  Every lane is the ONE writer of grad_depth at its entries (a plain load-add-store); SUMS: the 12 running sums, the
+// trees and the block's partial vector, then coords_build_bwd_sum_kernel as pass 2.  gzo, gdepth: null = not given (wave-uniform).
+template <int KIND, typename TD, bool SUMS>
+__global__ void __launch_bounds__(CB_COLS * CB_ROWS)
+coords_reproject_bwd_kernel(const double* __restrict__ params, const TD* __restrict__ depth, int64_t depth_set, const double2* __restrict__ gmap,
+                            const double* __restrict__ gzo, int oH, int oW, int i0, int j0, double* __restrict__ gdepth,
+                            double* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int NP = kReprojectParams;
+    __shared__ double wsum[kBwdWaves][NP];
+    const int s = blockIdx.z, w = threadIdx.y, j = blockIdx.x * CB_COLS + threadIdx.x;
+    const double* p = params + (size_t)s * NP;
+    const TD* dep = depth + set_offset(s, depth_set);
+    const size_t plane = (size_t)s * oH * oW;
+    double acc[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) acc[k] = 0.0;
+    if (j < oW)
+        for (int i = blockIdx.y * kBwdBand + w; i < oH && i < (int)(blockIdx.y + 1) * kBwdBand; i += kBwdWaves) {
+            const int64_t e = (int64_t)i * oW + j;
+            const double2 gv = gmap[plane + e];
+            double dp[NP];
+            const double dd = reproject_point_bwd<KIND>(p, (double)dep[e], i0 + i, j0 + j, Point{gv.x, gv.y}, gzo ? gzo[plane + e] : 0.0, dp);
+            if (gdepth) gdepth[plane + e] = gdepth[plane + e] + dd;
+            if (SUMS) {
+#pragma unroll
+                for (int k = 0; k < NP; ++k) acc[k] = acc[k] + dp[k];
+            }
+        }
+    if (!SUMS) return;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[k] = acc[k] + __shfl_down(acc[k], off, 64);
+        if (threadIdx.x == 0) wsum[w][k] = acc[k];
+    }
+    __syncthreads();
+    const int k = threadIdx.y * CB_COLS + threadIdx.x;
+    if (k < NP) {
+        const int nblk = gridDim.x * gridDim.y, blk = blockIdx.y * gridDim.x + blockIdx.x;
+        part[((size_t)s * NP + k) * nblk + blk] = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+    }
+}
+
 // the helpers of the lens models on their own (lerf_coords_math): one thread per element, grid ceil(n / 256)
 __global__ void __launch_bounds__(256)
 coords_math_kernel(int op, const double* __restrict__ x, const double* __restrict__ y, int64_t n, double* __restrict__ out) {
@@ -762,6 +829,94 @@ int invert_bwd(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, in
                    oH, oW, n_sets)));
 }
 
+// run F with KIND = the compile-time constant of a depth kind the argument checks have accepted
+#define LERF_COORDS_KIND(code, KIND, ...)                                          \
+    do {                                                                           \
+        if ((code) == LERF_DEPTH_Z) { constexpr int KIND = LERF_DEPTH_Z; __VA_ARGS__; } \
+        else { constexpr int KIND = LERF_DEPTH_INVERSE; __VA_ARGS__; }             \
+    } while (0)
+
+inline bool depth_kind(int kind) { return kind == LERF_DEPTH_Z || kind == LERF_DEPTH_INVERSE; }
+inline size_t depth_bytes(int dt) { return dt == LERF_F32 ? sizeof(float) : sizeof(double); }
+
+template <typename RUN>
+int reproject(RUN run, int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set, void* out, int out_dtype,
+              int64_t out_set, int64_t stride, float* depth_out, int64_t zo_set, int oH, int oW, int i0, int j0) {
+    enum { PARAMS, DEPTH, OUT, ZO };
+    const int rc = check_call(n_sets,
+                              {params_operand(params, kReprojectParams), plane_operand(depth, depth_bytes(depth_dtype), oH, oW, depth_set, SHARE),
+                               map_operand(out, out_dtype, stride, oH, oW, out_set), plane_operand(depth_out, sizeof(float), oH, oW, zo_set, OPTIONAL)},
+                              {{OUT, PARAMS}, {OUT, DEPTH}, {ZO, PARAMS}, {ZO, DEPTH}, {OUT, ZO}},
+                              depth_kind(kind) && float_dtype(depth_dtype) && tile_ok(oH, oW, i0, j0), LERF_EINVAL);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_KIND(kind, KIND, LERF_COORDS_DT(depth_dtype, TD, LERF_COORDS_DT(out_dtype, TO,
+        return run(ReprojectOp<KIND, TD, TO>{params, (const TD*)depth, (TO*)out, depth_out, depth_set, out_set, stride, zo_set, oW, i0, j0},
+                   oH, oW, n_sets))));
+}
+
+// ws: the partials of the device's two passes (needed with grad_params), null and OPTIONAL for the host twin; ws_fits: the caller's
+// workspace_bytes hold them
+inline int reproject_bwd_args(int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set,
+                              const double* grad_map, const double* grad_zo, int oH, int oW, int i0, int j0, const double* grad_depth,
+                              const double* grad_params, const Operand& ws, bool ws_fits) {
+    enum { PARAMS, DEPTH, GMAP, GZO, GDEPTH, GPARAMS, WS };
+    const int64_t plane = (int64_t)oH * oW;
+    Operand gp = params_operand(grad_params, kReprojectParams);
+    gp.optional = true;
+    return check_call(n_sets,
+                      {params_operand(params, kReprojectParams), plane_operand(depth, depth_bytes(depth_dtype), oH, oW, depth_set, SHARE),
+                       dense_operand(grad_map, LERF_F64, oH, oW, 2 * plane), plane_operand(grad_zo, sizeof(double), oH, oW, plane, OPTIONAL),
+                       plane_operand(grad_depth, sizeof(double), oH, oW, plane, OPTIONAL), gp, ws},
+                      {{GDEPTH, PARAMS}, {GDEPTH, DEPTH}, {GDEPTH, GMAP}, {GDEPTH, GZO}, {GPARAMS, PARAMS}, {GPARAMS, DEPTH}, {GPARAMS, GMAP},
+                       {GPARAMS, GZO}, {GPARAMS, GDEPTH}, {WS, PARAMS}, {WS, DEPTH}, {WS, GMAP}, {WS, GZO}, {WS, GDEPTH}, {WS, GPARAMS}},
+                      depth_kind(kind) && float_dtype(depth_dtype) && tile_ok(oH, oW, i0, j0) && (grad_depth || grad_params) && ws_fits, LERF_EINVAL);
+}
+
+// The fixed-order sum of the build backward and of the reproject backward on the host, lane by lane: the device's bands, trees and two
+// passes (the top of lerf_coords_models.h).  entry(s, i, j, dp) fills dp[n_params] of one entry; grad_params == nullptr: every entry is
+// visited once and nothing is summed.
+template <typename ENTRY>
+void two_pass_sums_host(int n_sets, int n_params, int oH, int oW, double* grad_params, ENTRY entry) {
+#pragma clang fp contract(off)
+    const int nbx = (oW + kBwdCols - 1) / kBwdCols, nby = (oH + kBwdBand - 1) / kBwdBand, nblk = nbx * nby;
+    std::vector<double> part((size_t)n_params * nblk);
+    std::vector<double> lanes((size_t)kMaxParams * 64);
+    for (int s = 0; s < n_sets; ++s) {
+        for (int by = 0; by < nby; ++by)
+            for (int bx = 0; bx < nbx; ++bx) {
+                double wsum[kBwdWaves][kMaxParams];
+                for (int w = 0; w < kBwdWaves; ++w) {
+                    for (int l = 0; l < 64; ++l) {
+                        const int j = bx * kBwdCols + l;
+                        double acc[kMaxParams];
+                        for (int k = 0; k < n_params; ++k) acc[k] = 0.0;
+                        if (j < oW)
+                            for (int i = by * kBwdBand + w; i < oH && i < (by + 1) * kBwdBand; i += kBwdWaves) {
+                                double dp[kMaxParams];
+                                entry(s, i, j, dp);
+                                for (int k = 0; k < n_params; ++k) acc[k] = acc[k] + dp[k];
+                            }
+                        for (int k = 0; k < n_params; ++k) lanes[(size_t)k * 64 + l] = acc[k];
+                    }
+                    for (int k = 0; k < n_params; ++k) wsum[w][k] = tree64(&lanes[(size_t)k * 64]);
+                }
+                for (int k = 0; k < n_params; ++k)
+                    part[(size_t)k * nblk + by * nbx + bx] = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+            }
+        if (!grad_params) continue;
+        for (int k = 0; k < n_params; ++k) {
+            double v[64];
+            for (int l = 0; l < 64; ++l) {
+                double acc = 0.0;
+                for (int b = l; b < nblk; b += 64) acc = acc + part[(size_t)k * nblk + b];
+                v[l] = acc;
+            }
+            double* dst = grad_params + (size_t)s * n_params + k;
+            *dst = *dst + tree64(v);
+        }
+    }
+}
+
 }  // namespace coords
 }  // namespace lerf
 
@@ -1033,46 +1188,73 @@ int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int 
 #pragma clang fp contract(off)
     const int rc = build_bwd_args(model, params, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params, bytes_operand(nullptr, 0, 16, OPTIONAL), true);
     if (rc != LERF_OK) return rc;
-    const int nbx = (oW + kBwdCols - 1) / kBwdCols, nby = (oH + kBwdBand - 1) / kBwdBand, nblk = nbx * nby;
-    std::vector<double> part((size_t)n_params * nblk);
-    std::vector<double> lanes((size_t)kMaxParams * 64);
-    for (int s = 0; s < n_sets; ++s) {
-        const double* p = params + (size_t)s * n_params;
-        const double* g = grad_map + (size_t)s * oH * oW * 2;
-        for (int by = 0; by < nby; ++by)
-            for (int bx = 0; bx < nbx; ++bx) {
-                double wsum[kBwdWaves][kMaxParams];
-                for (int w = 0; w < kBwdWaves; ++w) {
-                    for (int l = 0; l < 64; ++l) {
-                        const int j = bx * kBwdCols + l;
-                        double acc[kMaxParams];
-                        for (int k = 0; k < n_params; ++k) acc[k] = 0.0;
-                        if (j < oW)
-                            for (int i = by * kBwdBand + w; i < oH && i < (by + 1) * kBwdBand; i += kBwdWaves) {
-                                const int64_t e = 2 * ((int64_t)i * oW + j);
-                                const Point gv{g[e], g[e + 1]};
-                                double dp[kMaxParams];
-                                LERF_COORDS_MODEL(model, MODEL, model_point_bwd<MODEL>(p, i0 + i, j0 + j, gv, dp));
-                                for (int k = 0; k < n_params; ++k) acc[k] = acc[k] + dp[k];
-                            }
-                        for (int k = 0; k < n_params; ++k) lanes[(size_t)k * 64 + l] = acc[k];
-                    }
-                    for (int k = 0; k < n_params; ++k) wsum[w][k] = tree64(&lanes[(size_t)k * 64]);
-                }
-                for (int k = 0; k < n_params; ++k)
-                    part[(size_t)k * nblk + by * nbx + bx] = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
-            }
-        for (int k = 0; k < n_params; ++k) {
-            double v[64];
-            for (int l = 0; l < 64; ++l) {
-                double acc = 0.0;
-                for (int b = l; b < nblk; b += 64) acc = acc + part[(size_t)k * nblk + b];
-                v[l] = acc;
-            }
-            double* dst = grad_params + (size_t)s * n_params + k;
-            *dst = *dst + tree64(v);
-        }
-    }
+    two_pass_sums_host(n_sets, n_params, oH, oW, grad_params, [&](int s, int i, int j, double* dp) {
+        const double* g = grad_map + 2 * (((int64_t)s * oH + i) * oW + j);
+        LERF_COORDS_MODEL(model, MODEL, model_point_bwd<MODEL>(params + (size_t)s * n_params, i0 + i, j0 + j, Point{g[0], g[1]}, dp));
+    });
+    return LERF_OK;
+}
+
+int lerf_coords_reproject(int kind, const double* params_dev, int n_sets, const void* depth, int depth_dtype, int64_t depth_set_stride, void* out,
+                          int out_dtype, int64_t out_set_stride, int64_t out_row_stride, float* depth_out, int64_t depth_out_set_stride, int oH,
+                          int oW, int i0, int j0, void* stream) {
+    return reproject(OnDevice{(hipStream_t)stream}, kind, params_dev, n_sets, depth, depth_dtype, depth_set_stride, out, out_dtype, out_set_stride,
+                     out_row_stride, depth_out, depth_out_set_stride, oH, oW, i0, j0);
+}
+
+int lerf_coords_reproject_host(int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set_stride, void* out,
+                               int out_dtype, int64_t out_set_stride, int64_t out_row_stride, float* depth_out, int64_t depth_out_set_stride,
+                               int oH, int oW, int i0, int j0) {
+    return reproject(OnHost{}, kind, params, n_sets, depth, depth_dtype, depth_set_stride, out, out_dtype, out_set_stride, out_row_stride, depth_out,
+                     depth_out_set_stride, oH, oW, i0, j0);
+}
+
+size_t lerf_coords_reproject_bwd_workspace_bytes(int n_sets, int oH, int oW) {
+    return lerf_coords_build_bwd_workspace_bytes(kReprojectParams, n_sets, oH, oW);
+}
+
+int lerf_coords_reproject_bwd(int kind, const double* params_dev, int n_sets, const void* depth, int depth_dtype, int64_t depth_set_stride,
+                              const double* grad_map, const double* grad_depth_out, int oH, int oW, int i0, int j0, double* grad_depth,
+                              double* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
+    const Operand ws = bytes_operand(grad_params ? workspace : nullptr, (int64_t)lerf_coords_reproject_bwd_workspace_bytes(1, oH, oW), 16,
+                                     grad_params ? 0 : OPTIONAL);
+    const int rc = reproject_bwd_args(kind, params_dev, n_sets, depth, depth_dtype, depth_set_stride, grad_map, grad_depth_out, oH, oW, i0, j0,
+                                      grad_depth, grad_params, ws,
+                                      !grad_params || workspace_bytes >= lerf_coords_reproject_bwd_workspace_bytes(n_sets, oH, oW));
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + kBwdCols - 1) / kBwdCols, (oH + kBwdBand - 1) / kBwdBand, n_sets), b2(64), g2(kReprojectParams, n_sets);
+    const double2* gm = reinterpret_cast<const double2*>(grad_map);
+    double* part = reinterpret_cast<double*>(workspace);
+    LERF_COORDS_KIND(kind, KIND, LERF_COORDS_DT(depth_dtype, TD, {
+        if (grad_params)
+            hipLaunchKernelGGL((coords_reproject_bwd_kernel<KIND, TD, true>), g1, b1, 0, st, params_dev, (const TD*)depth, depth_set_stride, gm,
+                               grad_depth_out, oH, oW, i0, j0, grad_depth, part);
+        else
+            hipLaunchKernelGGL((coords_reproject_bwd_kernel<KIND, TD, false>), g1, b1, 0, st, params_dev, (const TD*)depth, depth_set_stride, gm,
+                               grad_depth_out, oH, oW, i0, j0, grad_depth, (double*)nullptr);
+    }));
+    if (grad_params) hipLaunchKernelGGL(coords_build_bwd_sum_kernel, g2, b2, 0, st, part, (int)(g1.x * g1.y), grad_params);
+    return launch_status();
+}
+
+// the device's kernel lane by lane: the same entries in the same order into the same sums
+int lerf_coords_reproject_bwd_host(int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set_stride,
+                                   const double* grad_map, const double* grad_depth_out, int oH, int oW, int i0, int j0, double* grad_depth,
+                                   double* grad_params) {
+#pragma clang fp contract(off)
+    const int rc = reproject_bwd_args(kind, params, n_sets, depth, depth_dtype, depth_set_stride, grad_map, grad_depth_out, oH, oW, i0, j0, grad_depth,
+                                      grad_params, bytes_operand(nullptr, 0, 16, OPTIONAL), true);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_KIND(kind, KIND, LERF_COORDS_DT(depth_dtype, TD,
+        two_pass_sums_host(n_sets, kReprojectParams, oH, oW, grad_params, [&](int s, int i, int j, double* dp) {
+            const int64_t e = (int64_t)i * oW + j, pe = (int64_t)s * oH * oW + e;
+            const double d = (double)((const TD*)depth)[set_offset(s, depth_set_stride) + e];
+            const double dd = reproject_point_bwd<KIND>(params + (size_t)s * kReprojectParams, d, i0 + i, j0 + j,
+                                                        Point{grad_map[2 * pe], grad_map[2 * pe + 1]}, grad_depth_out ? grad_depth_out[pe] : 0.0, dp);
+            if (grad_depth) grad_depth[pe] = grad_depth[pe] + dd;
+        })));
     return LERF_OK;
 }
 

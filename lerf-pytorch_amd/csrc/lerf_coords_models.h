@@ -212,6 +212,29 @@
 //                 pass 2, per (s, k): 64 lanes, lane l: acc = +0.0; for b = l, l + 64, ... < nblk: acc = acc + partial[s][k][b];
 //                   the same tree;  grad_params[s][k] = grad_params[s][k] + v[0]   (one writer: a plain load-add-store)
 //               The workspace holds the partials: n_sets * n_params * nblk doubles (2160 x 3840, brown: 60 * 34 * 21 * 8 B = 343 KB a set).
+//   reproject   (reproject_point<KIND>)   p = m[9] (K_dst . R . inv(K_src), row-major), q[3] (K_dst . t); one entry (i, j) of view A with
+//               depth `depth` (a float32 depth is promoted exactly) lands at (row, col) of view B with depth zo there:
+//                 x = (double)j,  y = (double)i                            -- (i, j) of the WHOLE map: the caller adds the tile's origin
+//                 a0 = (m0*x + m1*y) + m2,  a1 = (m3*x + m4*y) + m5,  a2 = (m6*x + m7*y) + m8
+//                 LERF_DEPTH_Z       (z = depth):  X = a0*z + q0,  Y = a1*z + q1,  W = a2*z + q2,  zo = W
+//                 LERF_DEPTH_INVERSE (d = depth):  X = a0 + q0*d,  Y = a1 + q1*d,  W = a2 + q2*d,  zo = W / d,  +inf where d == 0 (a select)
+//                 col = X / W,  row = Y / W
+//                 valid:  Z: z > 0, z - z == 0, W > 0;   INVERSE: d >= 0, d - d == 0, W > 0   (false for a NaN anywhere)
+//                 not valid: row = col = zo = NaN, by selects (fisheye's rule for a ray behind the camera)
+//               the map entry is stored like every map's (float32: rounded once), zo as float32 (rounded once; beyond float32: +inf)
+//   reproject backward (reproject_point_bwd<KIND>)   one entry with upstream g = (g.r, g.c) on (row, col) and gz on zo (0 when there is no
+//               upstream for zo); the forward is recomputed by the statements above.
+//                 not valid, or row or col not finite: dp[k] = 0 for every k and d depth = 0, whatever g and gz hold (selects)
+//                 dX = g.c / W,  dY = g.r / W,  dWm = -((g.c*col + g.r*row) / W)
+//                 Z:        gze = gz if zo is finite (zo - zo == 0), else 0;   dW = dWm + gze
+//                           d depth = (dX*a0 + dY*a1) + dW*a2
+//                           A = (dX*z, dY*z, dW*z),  Q = (dX, dY, dW)
+//                 INVERSE:  gzd = gz / d and gzz = gzd*zo if zo is finite, else both 0 (a point at infinity takes nothing from gz);  dW = dWm + gzd
+//                           d depth = ((dX*q0 + dY*q1) + dW*q2) - gzz
+//                           A = (dX, dY, dW),  Q = (dX*d, dY*d, dW*d)
+//                 dp[0..2] = A0*x, A0*y, A0;  dp[3..5] = A1*x, A1*y, A1;  dp[6..8] = A2*x, A2*y, A2;  dp[9..11] = Q
+//               grad_depth[s][i][j] += d depth: one writer per entry, a plain load-add-store.  grad_params[s][k] += the sum of dp[k] over the
+//               entries of set s in the ORDER OF THE BUILD BACKWARD above (the same bands, lanes, trees and two passes, n_params = 12).
 #pragma once
 
 #include "lerf_host_geometry.h"
@@ -467,6 +490,73 @@ inline double tree64(double* v) {
     for (int off = 32; off > 0; off >>= 1)
         for (int l = 0; l < off; ++l) v[l] = v[l] + v[l + off];
     return v[0];
+}
+
+// ---- reproject: a pixel of view A with its depth -> its position and depth in view B (the statement order: the top of this file)
+constexpr int kReprojectParams = LERF_REPROJECT_PARAMS;
+
+struct Reprojected {
+    Point q;
+    double zo;
+};
+
+template <int KIND>
+LERF_HD inline Reprojected reproject_point(const double* p, double depth, int i, int j) {
+#pragma clang fp contract(off)
+    const double x = (double)j, y = (double)i;
+    const double a0 = (p[0] * x + p[1] * y) + p[2], a1 = (p[3] * x + p[4] * y) + p[5], a2 = (p[6] * x + p[7] * y) + p[8];
+    double X, Y, W, zo;
+    bool ok;
+    if (KIND == LERF_DEPTH_Z) {
+        X = a0 * depth + p[9];
+        Y = a1 * depth + p[10];
+        W = a2 * depth + p[11];
+        zo = W;
+        ok = depth > 0.0;
+    } else {
+        X = a0 + p[9] * depth;
+        Y = a1 + p[10] * depth;
+        W = a2 + p[11] * depth;
+        zo = depth == 0.0 ? __builtin_inf() : W / depth;
+        ok = depth >= 0.0;
+    }
+    ok = ok && finite_value(depth) && W > 0.0;                           // false for a NaN in depth or W
+    const double nan = __builtin_nan("");
+    return {{ok ? Y / W : nan, ok ? X / W : nan}, ok ? zo : nan};
+}
+
+// dp[12] and, returned, the gradient on the entry's depth
+template <int KIND>
+LERF_HD inline double reproject_point_bwd(const double* p, double depth, int i, int j, Point g, double gz, double* dp) {
+#pragma clang fp contract(off)
+    const double x = (double)j, y = (double)i;
+    const double a0 = (p[0] * x + p[1] * y) + p[2], a1 = (p[3] * x + p[4] * y) + p[5], a2 = (p[6] * x + p[7] * y) + p[8];
+    const Reprojected f = reproject_point<KIND>(p, depth, i, j);
+    const double W = KIND == LERF_DEPTH_Z ? a2 * depth + p[11] : a2 + p[11] * depth;      // the forward's statement
+    const double dX = g.c / W, dY = g.r / W, dWm = -((g.c * f.q.c + g.r * f.q.r) / W);
+    const bool zf = finite_value(f.zo);
+    double dW, dd, A0, A1, A2, Q0, Q1, Q2;
+    if (KIND == LERF_DEPTH_Z) {
+        dW = dWm + (zf ? gz : 0.0);
+        dd = (dX * a0 + dY * a1) + dW * a2;
+        A0 = dX * depth; A1 = dY * depth; A2 = dW * depth;
+        Q0 = dX; Q1 = dY; Q2 = dW;
+    } else {
+        const double gzd = zf ? gz / depth : 0.0;
+        const double gzz = zf ? gzd * f.zo : 0.0;
+        dW = dWm + gzd;
+        dd = ((dX * p[9] + dY * p[10]) + dW * p[11]) - gzz;
+        A0 = dX; A1 = dY; A2 = dW;
+        Q0 = dX * depth; Q1 = dY * depth; Q2 = dW * depth;
+    }
+    dp[0] = A0 * x; dp[1] = A0 * y; dp[2] = A0;
+    dp[3] = A1 * x; dp[4] = A1 * y; dp[5] = A1;
+    dp[6] = A2 * x; dp[7] = A2 * y; dp[8] = A2;
+    dp[9] = Q0; dp[10] = Q1; dp[11] = Q2;
+    const bool fin = finite_value(f.q.r) && finite_value(f.q.c);         // an entry that is not valid holds NaN
+#pragma unroll
+    for (int k = 0; k < kReprojectParams; ++k) dp[k] = fin ? dp[k] : 0.0;
+    return fin ? dd : 0.0;
 }
 
 // ---- mesh: the taps of output index k along one axis of n outputs over g vertices; returns the tap count (2 or 4)

@@ -7,6 +7,8 @@
 // run the very functors the device runs (OnHost, ScatterOnHost in lerf_coords.hip), so this pass checks the addressing of the shared code.
 // The batched twins (lerf_coords_*_batched_host) run three sets with padded set strides, a folded set with NaN / +-inf / 1e300 entries,
 // non-zero origins and shared operands, and must equal the single-map twins set by set (batched_ops).
+// lerf_coords_reproject_host and lerf_coords_reproject_bwd_host (reproject_ops) run three sets of both kinds and both depth dtypes into a
+// strided out at a non-zero origin, depth_out and each gradient half null and given, special depths, and their refusals.
 // It needs no GPU and is never loaded into another process.  Exit status 0 and "ok" on the last line: no report.
 #include "lerf_hip.h"
 
@@ -342,6 +344,84 @@ static void batched_ops(int oH, int oW) {
         }
 }
 
+// reproject and its adjoint on tiles [oH][oW] at origin (3, 7): three sets, both kinds, both depth dtypes, a strided out of both dtypes,
+// depth_out and each gradient half null and given, special depths (0, negative, NaN, inf, 1e-300, 1e300, W <= 0), then the refusals
+template <typename TD>
+static void reproject_ops_of(int oH, int oW, int ddt) {
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int B = 3;
+    const size_t n = (size_t)oH * oW;
+    // m = K_dst . R . inv(K_src) of nearby cameras; set 2: W = depth - 3, so depths below 3 lie behind the second view
+    const double P[B * LERF_REPROJECT_PARAMS] = {1.25,   0.02,  -4.5, -0.03, 1.125, -2.0, 0.001, -0.002, 1.0, 8.0,  -3.6,  0.3,
+                                                 0.8,    -0.01, 3.2,  0.02,  0.9,   1.9,  -0.0005, 0.001, 1.0, -9.6, 8.0,   0.1,
+                                                 1.25,   0.0,   -4.5, 0.0,   1.125, -2.0, 0.0,   0.0,    1.0, 4.0,  7.2,   -3.0};
+    const double special[10] = {0.0, -1.5, nan, inf, 1e-300, 1e300, 3.0, 2.5, -0.0, -inf};
+    std::vector<TD> depth(B * n);
+    for (size_t k = 0; k < depth.size(); ++k) depth[k] = k % 3 == 0 && k / 3 < 10 ? (TD)special[k / 3] : (TD)(0.5 + 0.37 * (double)(k % 13));
+    std::vector<double> g(B * n * 2), gz(B * n);
+    for (size_t k = 0; k < g.size(); ++k) g[k] = k % 29 == 9 ? nan : std::sin(0.37 * (double)k);
+    for (size_t k = 0; k < gz.size(); ++k) gz[k] = k % 31 == 4 ? inf : std::cos(0.21 * (double)k);
+    for (int kind : {LERF_DEPTH_Z, LERF_DEPTH_INVERSE}) {
+        for (int to : {LERF_F32, LERF_F64}) {
+            const int64_t stride = 2 * (int64_t)(oW + 3), span = (oH - 1) * stride + 2 * oW, set = span + 6;      // padded rows and sets
+            std::vector<double> o64(to == LERF_F64 ? (size_t)((B - 1) * set + span) : 0, -7.0);
+            std::vector<float> o32(to == LERF_F32 ? (size_t)((B - 1) * set + span) : 0, -7.0f);
+            void* out = to == LERF_F64 ? (void*)o64.data() : (void*)o32.data();
+            std::vector<float> zo(B * n, -7.0f);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_OK);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, nullptr, 0, oH, oW, 3, 7) == LERF_OK);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, 0, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_OK);       // a shared plane
+            EXPECT(lerf_coords_reproject_host(kind, P, 1, depth.data(), ddt, 0, out, to, 0, stride, zo.data(), 0, oH, oW, 0, 0) == LERF_OK);
+            if (oW > 1) EXPECT(to == LERF_F64 ? o64[2 * oW] == -7.0 : o32[2 * oW] == -7.0f);                       // the padding of row 0
+            // the refusals write nothing
+            std::vector<float> keep = zo;
+            EXPECT(lerf_coords_reproject_host(2, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, nullptr, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, nullptr, ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), 0, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, 3, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, 0, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, 65536, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride + 1, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, 2 * (int64_t)oW - 2, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, span - 2, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            if (n > 1)                                          // a short set stride; on 1 x 1 it would be 0, the shared plane
+                EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n - 1, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n - 1, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, 0, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, -1, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, depth.data(), ddt, (int64_t)n, out, to, set, stride, (float*)depth.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(lerf_coords_reproject_host(kind, P, B, zo.data(), LERF_F32, 0, out, to, set, stride, zo.data(), (int64_t)n, oH, oW, 3, 7) == LERF_EINVAL);
+            EXPECT(keep == zo || std::memcmp(keep.data(), zo.data(), keep.size() * sizeof(float)) == 0);
+        }
+        // the adjoint: each half null and given, with and without the upstream of zo; gradients exactly sized
+        std::vector<double> gd(B * n, 0.5), gp(B * LERF_REPROJECT_PARAMS, -0.5);
+        const std::vector<double> gd0 = gd, gp0 = gp;
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, gd.data(), gp.data()) == LERF_OK);
+        EXPECT(!same(gd, gd0) && !same(gp, gp0));
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), nullptr, oH, oW, 3, 7, gd.data(), gp.data()) == LERF_OK);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, nullptr, gp.data()) == LERF_OK);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, gd.data(), nullptr) == LERF_OK);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, 0, g.data(), gz.data(), oH, oW, 3, 7, gd.data(), gp.data()) == LERF_OK);
+        gd = gd0; gp = gp0;
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, nullptr, nullptr) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(5, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, gd.data(), gp.data()) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, nullptr, gz.data(), oH, oW, 3, 7, gd.data(), gp.data()) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, g.data(), gp.data()) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, gz.data(), gp.data()) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, gd.data(), gd.data()) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, 7, gd.data(), (double*)P) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, 0, 3, 7, gd.data(), gp.data()) == LERF_EINVAL);
+        EXPECT(lerf_coords_reproject_bwd_host(kind, P, B, depth.data(), ddt, (int64_t)n, g.data(), gz.data(), oH, oW, 3, -7, gd.data(), gp.data()) == LERF_EINVAL);
+        EXPECT(same(gd, gd0) && same(gp, gp0));
+    }
+}
+
+static void reproject_ops(int oH, int oW) {
+    reproject_ops_of<float>(oH, oW, LERF_F32);
+    reproject_ops_of<double>(oH, oW, LERF_F64);
+}
+
 int main() {
     const double pi = 3.14159265358979323846;
     const double fish[17] = {1.0 / 35, 0, -27.5 / 35, 0, 1.0 / 33, -16.0 / 33, 0.001, -0.0005, 1, 61.5, 58.75, 25.25, 17.5, 0.05, -0.012, 0.004, -0.0009};
@@ -385,6 +465,10 @@ int main() {
     batched_ops(1, 1);
     batched_ops(2, 2);
     batched_ops(5, 67);
+    reproject_ops(1, 1);
+    reproject_ops(2, 2);
+    reproject_ops(5, 67);
+    reproject_ops(70, 130);                                     // two bands x three column blocks of the adjoint's sums
     std::printf(fails ? "%d check(s) failed\n" : "ok\n", fails);
     return fails ? 1 : 0;
 }

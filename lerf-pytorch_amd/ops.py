@@ -1207,3 +1207,27 @@ def coords_invert_bwd(f, inverse, grad_out, grad_f=None):
     corners and folded cells contribute nothing.  Device maps under the strided contract.  One launch on the current stream, no
     sync.  A batch: f and grad_f [B, fH, fW, 2], inverse and grad_out [B, oH, oW, 2], one launch (lerf_coords_invert_bwd_batched)."""
     return _lib.coords_invert_bwd_on(_lib.DeviceOperands(), f, inverse, grad_out, grad_f)
+
+
+def coords_reproject(kind, params, depth, dtype=None, out=None, origin=(0, 0), depth_out=None):
+    """lerf_coords_reproject: the map that carries a view with a depth per pixel into another view.  kind "z" (depth) or "inverse"
+    (1 / depth); params float64 device [12] = (K_dst . R . inv(K_src))[9], (K_dst . t)[3] with depth [H, W] (device, float32 /
+    float64), or [B, 12] with depth [B, H, W] or one shared [H, W] -> the map [H, W, 2] or [B, H, W, 2] of `dtype` (default float64):
+    entry (i, j) is (row, col) of pixel (i, j) in the other view, (NaN, NaN) where the depth is not positive (inverse: negative), not
+    finite, or the point lies behind the other camera.  out: a device tensor or a strided tile view (its depth plane is the TILE's)
+    at `origin` of the whole map.  depth_out: True or a float32 device tensor of depth's batch shape -> (map, zo), zo the depth in the
+    other view, what coords_invert_raster takes as depth.  ONE launch on the current stream whatever B, no sync; bit-equal to
+    _lib.coords_reproject_host."""
+    return _lib.coords_reproject_on(_lib.DeviceOperands(), kind, params, depth, dtype, out, origin, depth_out)
+
+
+def coords_reproject_bwd(kind, params, depth, grad_map, grad_depth_out=None, grad_depth=None, grad_params=None, need=(True, True),
+                         origin=(0, 0)):
+    """lerf_coords_reproject_bwd: ACCUMULATE the adjoint of coords_reproject of grad_map (float64 contiguous, the map's shape) and
+    grad_depth_out (float64 contiguous, zo's shape; None: no upstream) into grad_depth (float64, [H, W] or [B, H, W]: one writer per
+    entry) and grad_params (float64, params' shape: the build adjoint's two fixed-order passes, no atomics); None: zeroed ones;
+    need[k] False skips that half and returns None for it -> (grad_depth, grad_params).  An entry that is not valid contributes
+    nothing, whatever the upstreams hold.  One launch (two with grad_params) on the current stream, no sync; two calls are bit-equal,
+    and equal to _lib.coords_reproject_bwd_host."""
+    return _lib.coords_reproject_bwd_on(_lib.DeviceOperands(), kind, params, depth, grad_map, grad_depth_out, grad_depth, grad_params, need,
+                                        origin)

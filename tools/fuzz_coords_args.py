@@ -6,8 +6,8 @@ byte for byte:
 
     fuzz_coords_args.py --lib A/liblerf_hip.so --out a.jsonl && fuzz_coords_args.py --lib B/liblerf_hip.so --out b.jsonl && cmp a.jsonl b.jsonl
 
-For every host twin that takes maps (build, mesh, compose, invert, invert_raster, compose_bwd, invert_bwd, build_bwd and the six
-batched forms) it draws a VALID call on tiny shapes (h, w <= 6) and replaces zero to two of its arguments by a value the contract tells
+For every host twin that takes maps (build, mesh, compose, invert, invert_raster, compose_bwd, invert_bwd, build_bwd, reproject,
+reproject_bwd and the six batched forms) it draws a VALID call on tiny shapes (h, w <= 6) and replaces zero to two of its arguments by a value the contract tells
 apart: dtype codes in and out of range, dimensions -1 .. 6, row strides odd / short / exact / padded / negative, set strides
 -span / 0 / odd / span - 2 / span / padded, n_sets -1 .. 3 and 65536, null and misaligned pointers, a pointer moved onto another
 operand's bytes, the scalar limits.  All operands live in ONE arena (page-aligned, so alignment is the same in every process), each
@@ -15,7 +15,7 @@ in a slot of its own, the first and the last a margin away from the arena's ends
 The arena is reset before every call; one record per case goes to --out: entry point, arguments (pointers as arena offsets), return
 code, digest of the arena afterwards.
 
-The device-only entry points (mesh_bwd, mesh_bwd_batched, build_dev, build_bwd) get the same cases with HOST pointers, which a
+The device-only entry points (mesh_bwd, mesh_bwd_batched, build_dev, build_bwd, and the device forms of reproject and reproject_bwd) get the same cases with HOST pointers, which a
 refused call never reads; they run only where there is no device (lerf_device_count() <= 0), where a call that passes the checks
 fails at its launch and touches nothing either.
 
@@ -36,6 +36,7 @@ import numpy as np
 F32, F64 = 1, 2
 MARGIN, SLOT = 8192, 4096               # bytes: the arena's two margins, one operand's slot (3 padded sets of a 6 x 6 float64 map: 2304)
 N_PARAMS = {0: 9, 1: 8, 2: 21, 16: 17, 17: 13}
+REPROJECT_PARAMS = 12
 CHAINED = ("mesh", "compose", "invert", "invert_raster", "compose_bwd", "invert_bwd")
 N_SET_STRIDES = {"mesh": 2, "compose": 3, "invert": 3, "invert_raster": 4, "compose_bwd": 5, "invert_bwd": 4}
 
@@ -58,9 +59,9 @@ class Arena:
     def digest(self):
         return hashlib.blake2b(self.buf, digest_size=8).hexdigest()
 
-    def set_params(self, off, model, n_sets):
+    def set_params(self, off, n_params, n_sets):
         """a usable parameter block at offset `off`: near-identity numbers, so that every model stays finite"""
-        p = np.tile(np.linspace(0.9, 1.1, N_PARAMS[model]), n_sets)
+        p = np.tile(np.linspace(0.9, 1.1, n_params), n_sets)
         self.buf[off:off + p.nbytes] = p.view(np.uint8)
 
 
@@ -220,7 +221,7 @@ def invert_bwd(c):
 def _model(c):
     model = int(c.rng.choice(list(N_PARAMS)))
     c.add("model", model)
-    c.params = (c.ptr(), model)
+    c.params = (c.ptr(), N_PARAMS[model])
     return model
 
 
@@ -278,13 +279,58 @@ def mesh_bwd(c):
     c.tail = [None]
 
 
+def _reproject_head(c):
+    """kind, params, n_sets, depth, its dtype and set stride (0: one plane for every set) -> (oH, oW)"""
+    c.add("depth_kind", int(c.coin()))
+    c.params = (c.ptr(), REPROJECT_PARAMS)
+    c.n = int(c.rng.integers(1, 4))
+    c.add("nsets", c.n)
+    oH, oW = _hw(c.rng)
+    c.ptr()
+    c.add("dtype", int(c.rng.choice([F32, F64])))
+    c.add("sstride", 0 if c.coin(0.3) else oH * oW + 6 * int(c.coin()), span=oH * oW)
+    return oH, oW
+
+
+def reproject(c, device=False):
+    oH, oW = _reproject_head(c)
+    c.ptr()
+    c.add("dtype", int(c.rng.choice([F32, F64])))
+    rs = 2 * oW + 4 * int(c.coin())
+    span = (oH - 1) * rs + 2 * oW
+    c.add("sstride", span + 6 * int(c.coin()), span=span)
+    c.add("rstride", rs, w=oW)
+    c.ptr(null=c.coin(0.3))                             # depth_out
+    c.add("sstride", oH * oW + 6 * int(c.coin()), span=oH * oW)
+    _tile(c, oH, oW)
+    if device:
+        c.tail = [None]
+
+
+def reproject_bwd(c, device=False):
+    oH, oW = _reproject_head(c)
+    c.ptr()                                             # grad_map
+    c.ptr(null=c.coin(0.3))                             # grad_depth_out
+    _tile(c, oH, oW)
+    skip = int(c.rng.integers(0, 4))                    # 0, 3: both gradients; 1: no grad_depth; 2: no grad_params
+    c.ptr(null=skip == 1)
+    c.ptr(null=skip == 2)
+    if device:
+        need = c.n * REPROJECT_PARAMS * 8               # one block of 64 x 64 covers a tile of 6 x 6
+        c.ptr()
+        c.add("ws_bytes", need, need=need)
+        c.tail = [None]
+
+
 # entry point -> (the call's builder, batched)
-HOST = {"lerf_coords_build_host": (build, False), "lerf_coords_build_bwd_host": (build_bwd, False)}
+HOST = {"lerf_coords_build_host": (build, False), "lerf_coords_build_bwd_host": (build_bwd, False),
+        "lerf_coords_reproject_host": (reproject, False), "lerf_coords_reproject_bwd_host": (reproject_bwd, False)}
 for _op in CHAINED:
     HOST["lerf_coords_%s_host" % _op] = (globals()[_op], False)
     HOST["lerf_coords_%s_batched_host" % _op] = (globals()[_op], True)
 DEVICE_ONLY = {"lerf_coords_mesh_bwd": (mesh_bwd, False), "lerf_coords_mesh_bwd_batched": (mesh_bwd, True),
-               "lerf_coords_build_dev": (build_dev, False), "lerf_coords_build_bwd": (lambda c: build_bwd(c, True), False)}
+               "lerf_coords_build_dev": (build_dev, False), "lerf_coords_build_bwd": (lambda c: build_bwd(c, True), False),
+               "lerf_coords_reproject": (lambda c: reproject(c, True), False), "lerf_coords_reproject_bwd": (lambda c: reproject_bwd(c, True), False)}
 
 
 def _values(arg, call, i):
@@ -311,7 +357,7 @@ def _values(arg, call, i):
     if k in ("full", "ws_bytes"):
         return [m["need"] - 8 if k == "ws_bytes" else m["need"] - 1, 0, m["need"], m["need"] + 64]
     return {"max_iter": [0, 1, 64, 65], "tol": [-1.0, float("nan"), float("inf"), 0.0, 1e-9], "max_span": [0, 1, 64, 65],
-            "orient": [-2, -1, 0, 1, 2], "interp": [-1, 0, 1, 2], "origin": [-1, 0, 3, 7], "model": [-1, 0, 1, 2, 3, 16, 17, 18],
+            "orient": [-2, -1, 0, 1, 2], "interp": [-1, 0, 1, 2], "depth_kind": [-1, 0, 1, 2], "origin": [-1, 0, 3, 7], "model": [-1, 0, 1, 2, 3, 16, 17, 18],
             "n_params": [-1, 0, 8, 9, 10, 13, 17, 21]}[k]
 
 
