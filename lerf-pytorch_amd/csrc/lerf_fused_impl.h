@@ -48,16 +48,14 @@
 #include <type_traits>
 
 #include "lerf_kernels.h"
+#include "lerf_simplex_lds.h"
 #include "lerf_stage3.h"
 #include "lerf_warp_px.h"
 
 namespace lerf {
 namespace LERF_FUSED_NS {
 
-#ifndef LERF_FUSED_NT
-#define LERF_FUSED_NT 1024         // threads per workgroup
-#endif
-constexpr int NT = LERF_FUSED_NT;  // threads per workgroup
+constexpr int NT = 1024;           // threads per workgroup (the binning of LeRF-G stage 2 is written for 16 waves)
 constexpr int NW = NT / 64;        // waves
 constexpr int CH = LERF_FUSED_CH;  // channels per pixel of this instance
 static_assert(CH == 1 || CH == 3 || CH == 4, "192 pixel-channels per tile row");
@@ -72,19 +70,12 @@ constexpr int LUT_PAD = 83584;     // padded entries per LUT in the pack (16-B m
 // Stage-2 bins: a pixel-channel goes by the top-axis level (high nibble) of its centre value, which selects the slowest
 // LUT axis for every mode and rotation.  Bin b covers the levels [bin_lo(b), bin_lo(b + 1)); its piece of a packed LUT is
 // those levels plus the one above (the simplex walk steps up once).
-#ifndef LERF_NBIN
-#define LERF_NBIN 3
-#endif
-constexpr int NBIN = LERF_NBIN;
-#if LERF_NBIN == 4      // four bins of 4 levels, 5-level pieces of 96 KiB (24 phases per tile): the measured alternative
-__host__ __device__ constexpr int bin_lo(int b) { return 4 * b; }
-__device__ __forceinline__ uint32_t bin_of_level(uint32_t msb) { return msb >> 2; }
-constexpr int PIECE_LEVELS = 5;                               // levels per piece
-#else                   // three bins of 6, 5 and 5 levels, 7-level pieces of 134 KiB that fill the LDS: 18 longer phases
+// Three bins of 6, 5 and 5 levels, 7-level pieces of 134 KiB that fill the LDS: 18 long phases per tile (the measured
+// alternative, four bins of 4 levels with 5-level pieces of 96 KiB and 24 phases, lost).
+constexpr int NBIN = 3;
 __host__ __device__ constexpr int bin_lo(int b) { return b == 0 ? 0 : (b == 1 ? 6 : (b == 2 ? 11 : 16)); }
 __device__ __forceinline__ uint32_t bin_of_level(uint32_t msb) { return (msb >= 6u ? 1u : 0u) + (msb >= 11u ? 1u : 0u); }
-constexpr int PIECE_LEVELS = 7;
-#endif
+constexpr int PIECE_LEVELS = 7;                               // levels per piece
 constexpr int PIECE_ENTRIES = PIECE_LEVELS * kStrideA;
 constexpr int NSLAB = (PIECE_ENTRIES * 4 + 16 * NT - 1) / (16 * NT);   // 16 bytes per thread and slab
 constexpr int PIECE_BYTES = NSLAB * 16 * NT;                  // one piece in the pack (144 KiB, 34391 dwords used)
@@ -117,11 +108,7 @@ struct Dims {
     // stage 2, LeRF-G: one piece.  The position lists and the wave x bin count table only live between the binning and the
     // first piece store (the first piece waits in registers) and overlay the piece.
     // positions that are looked up: the hyper region without its last row and column (never read by an owned output, see the binning)
-#ifndef LERF_FULL_RING
     static constexpr int NHL = HR > 0 ? (HY - 1) * (HX - 1) * CH : NH;
-#else
-    static constexpr int NHL = NH;
-#endif
     static constexpr int MAXR = (NHL + NBIN * 63 + NT - 1) / NT;  // slot rounds: every bin padded to whole waves (13 for S = 2, 14 for S = 4)
     static constexpr int OFF_LST = OFF_X;
     static constexpr int OFF_TAB = OFF_LST + MAXR * NT * 2;       // [wave][4 bins] counts
@@ -230,129 +217,6 @@ __host__ __device__ constexpr Off3 tile_offsets(char mode, int rot) {
     return r;
 }
 
-// ---------------------------------------------------------------------------
-// simplex walk (index/weight computation only).  Keys are (LSB << 16) | axis stride so that one unsigned sort orders
-// the four axes by decreasing LSB (ties: zero weight, any order).  STRIDE_SCALE = bytes per LUT entry, folded into
-// the strides so the indices are byte offsets.
-//
-// Instruction budget (gfx950 issues v_and/or/add/sub/lshr in ~2.4 cycles per wave64, every 3-operand or min/max/
-// shift-left/24-bit-multiply op in ~4.3: profiles/r01_valu_instruction_rates.txt), per lookup:
-//   keys      3 x (v_and + v_lshl_or)                       the centre key is shared by the rotations of a position
-//   sort      7 three-input ops  m = max3(a,b,c)  e = med3(a,b,c)  n = min3(a,b,c)
-//                                s0 = max(m,d)  s1 = med3(m,e,d)  s2 = med3(e,n,d)  s3 = min(n,d)
-//             instead of the 10 of a 5-comparator network
-//   indices   the walk ends at base + (all four strides), a constant: vertex 4 is an immediate offset on vertex 0 and
-//             vertex 3 = vertex 4 - stride(s3), so only s0, s1, s3 contribute an AND + ADD/SUB (s2 is needed for its
-//             LSB alone)
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned umax3(unsigned a, unsigned b, unsigned c) {
-    unsigned r;
-    asm("v_max3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c) {
-    unsigned r;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ unsigned umin3(unsigned a, unsigned b, unsigned c) {
-    unsigned r;
-    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// (f << 16) | stride in one instruction (the compiler prefers shift-left + and + or)
-__device__ __forceinline__ unsigned make_key(unsigned f, unsigned stride) {
-    unsigned r;
-    asm("v_lshl_or_b32 %0, %1, 16, %2" : "=v"(r) : "v"(f), "s"(stride));
-    return r;
-}
-
-// LDS accesses by 32-bit LDS address.  `smem` is a link-time symbol: pointer arithmetic on it leaves one "+ smem" per
-// distinct address chain in the instruction stream (v_add 0); folding the table's LDS address into the walk's base
-// index once per position removes them, and constant parts still fold into the DS immediate offset.
-typedef __attribute__((address_space(3))) const uint32_t lds_cu32_t;
-typedef __attribute__((address_space(3))) const int8_t lds_ci8_t;
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-// OFF is applied as a constant element index so that it lands in the DS immediate offset
-template <int OFF = 0>
-__device__ __forceinline__ uint32_t lds_ld32(uint32_t a) { return ((lds_cu32_t*)a)[OFF / 4]; }
-template <int OFF = 0>
-__device__ __forceinline__ int lds_ldi8(uint32_t a) { return (int)((lds_ci8_t*)a)[OFF]; }
-
-// A tile pixel is needed twice: its LSB in bits 16..19 of the sort key and its MSB as an index digit.  ds_read_u8_d16_hi
-// returns the byte in bits 16..23 (v << 16 for free; what it leaves in the low half is not relied upon), so that
-//   key = (r & 0x000F0000) | stride   one v_and_or_b32          msb = r >> 20   one v_lshrrev_b32
-// instead of v_and + v_lshl_or + v_lshrrev on a zero-extended byte.  The compiler does not track inline-asm LDS
-// loads: pixels_ready() waits for them (it names the registers so that every use is ordered behind it).
-__device__ __forceinline__ uint32_t lds_pixel_hi(uint32_t addr) {
-    uint32_t r;
-    asm volatile("ds_read_u8_d16_hi %0, %1" : "=v"(r) : "v"(addr));
-    return r;
-}
-template <int OFF>
-__device__ __forceinline__ uint32_t lds_pixel_hi_off(uint32_t addr) {
-    uint32_t r;
-    asm volatile("ds_read_u8_d16_hi %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-__device__ __forceinline__ unsigned key_of(uint32_t r, unsigned stride) {
-    unsigned k;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(k) : "v"(r), "s"(0x000F0000u), "v"(stride));
-    return k;
-}
-__device__ __forceinline__ unsigned msb_of(uint32_t r) { return r >> 20; }
-
-// acc + d.lo16 * key.hi16 (signed): one Abel term of a byte-LUT walk, the LSB taken from the sorted key's high half in place --
-// sub + mad per term instead of sub + multiply (SDWA) + half a three-input add (round 5: -2 of ~30 instructions per walk)
-__device__ __forceinline__ int mad_i16_keyhi(int d, unsigned key, int acc) {
-    asm("v_mad_i32_i16 %0, %1, %2, %0 op_sel:[0,1,0,0]" : "+v"(acc) : "v"(d), "v"(key));
-    return acc;
-}
-
-// acc + w.lo16 * d.hi16: the upper half of a packed stage-2 entry multiplied in place (op_sel picks the high half of src1)
-__device__ __forceinline__ uint32_t mad_hi16(uint32_t w, uint32_t d, uint32_t acc) {
-    asm("v_mad_u32_u16 %0, %1, %2, %0 op_sel:[0,1,0,0]" : "+v"(acc) : "v"(w), "v"(d));
-    return acc;
-}
-
-template <int STRIDE_SCALE>
-struct Walk {
-    static constexpr int ALL = (kStrideA + kStrideB + kStrideC + kStrideD) * STRIDE_SCALE;   // vertex 4 - vertex 0
-    int i0, i1, i2, i3m;        // byte offsets of vertices 0, 1, 2 and (vertex 3 - ALL); vertex 4 = i0 + ALL
-    unsigned f0, f1, f2, f3;    // sorted LSBs
-    unsigned k0, k1, k2, k3;    // the sorted keys themselves (LSB in the high half: a v_mad_*_i16 reads it there with op_sel)
-    // vertex n = address a(n) + constant c(n): the constant goes into the DS immediate offset
-    __device__ __forceinline__ uint32_t a(int n) const { return (uint32_t)(n == 0 ? i0 : n == 1 ? i1 : n == 2 ? i2 : n == 3 ? i3m : i0); }
-    static constexpr int c(int n) { return n >= 3 ? ALL : 0; }
-    __device__ __forceinline__ uint32_t ld32(int n) const { return n >= 3 ? lds_ld32<ALL>(a(n)) : lds_ld32<0>(a(n)); }
-    __device__ __forceinline__ int ldi8(int n) const { return n >= 3 ? lds_ldi8<ALL>(a(n)) : lds_ldi8<0>(a(n)); }
-};
-
-// ka = key of the centre pixel, basea = its MSB contribution to the index (both shared by the rotations of a position);
-// rb, rc, rd = the other three pixels as lds_pixel_hi() returned them; sb, sc, sd = the axis strides (bytes) in VGPRs
-template <int STRIDE_SCALE>
-__device__ __forceinline__ Walk<STRIDE_SCALE> simplex_walk(unsigned ka, int basea, uint32_t rb, uint32_t rc, uint32_t rd,
-                                                           unsigned sb, unsigned sc, unsigned sd) {
-    Walk<STRIDE_SCALE> W;
-    const unsigned kb = key_of(rb, sb), kc = key_of(rc, sc), kd = key_of(rd, sd);
-    // base index, Horner over the MSBs: ((b * 17 + c) * 17 + d) * scale + a-part
-    const unsigned t = __umul24(__umul24(msb_of(rb), (unsigned)kL) + msb_of(rc), (unsigned)kL) + msb_of(rd);
-    W.i0 = basea + (int)(t * STRIDE_SCALE);
-    const unsigned m = umax3(ka, kb, kc), e = umed3(ka, kb, kc), n = umin3(ka, kb, kc);
-    const unsigned s0 = m > kd ? m : kd;
-    const unsigned s1 = umed3(m, e, kd);
-    const unsigned s2 = umed3(e, n, kd);
-    const unsigned s3 = n < kd ? n : kd;
-    W.i1 = W.i0 + (int)(s0 & 0xFFFFu);
-    W.i2 = W.i1 + (int)(s1 & 0xFFFFu);
-    W.i3m = W.i0 - (int)(s3 & 0xFFFFu);
-    W.f0 = s0 >> 16; W.f1 = s1 >> 16; W.f2 = s2 >> 16; W.f3 = s3 >> 16;
-    W.k0 = s0; W.k1 = s1; W.k2 = s2; W.k3 = s3;
-    return W;
-}
-
 // global -> LDS copy of `bytes` (rounded up to 16) by the whole workgroup; every load of a
 // thread is issued before its first LDS write so the L2 latency is paid once per copy
 template <int BYTES>
@@ -428,51 +292,22 @@ __device__ __forceinline__ int byte_walks(uint32_t lut_a, uint32_t ra, const uin
     const unsigned ka = key_of(ra, sa);
     const int basea = (int)(__umul24(msb_of(ra), kStrideA) + lut_a);      // LDS address of the base corner
     Walk<1> W[NROT];
-    int e[NROT][5];
-#ifndef LERF_S1_SPLIT
-#define LERF_S1_SPLIT 1
-#endif
-#if LERF_S1_SPLIT > 0
-    // the gathers of a walk (LERF_S1_SPLIT walks) are issued as soon as its indices exist and fly under the next walk (all
-    // 4 walks first, then all 20 gathers = LERF_S1_SPLIT 0: 0.8 % slower; groups of two: 0.2 % slower; A/B on one box): the
-    // LDS starts on a position's gathers ~100 instructions earlier.  The same split in the stage-2 slot LOST 0.25 %.
+    ByteCorners E[NROT];
+    // the gathers of a walk are issued as soon as its indices exist and fly under the next walk (all 4 walks first, then all
+    // 20 gathers: 0.8 % slower; groups of two: 0.2 % slower; A/B on one box): the LDS starts on a position's gathers ~100
+    // instructions earlier.  The same split in the stage-2 slot LOST 0.25 %.
 #pragma unroll
-    for (int h = 0; h < NROT; h += LERF_S1_SPLIT) {
-#pragma unroll
-        for (int i = h; i < h + LERF_S1_SPLIT; ++i) W[i] = simplex_walk<1>(ka, basea, rb[i], rc[i], rd[i], sb, sc, sd);
-#pragma unroll
-        for (int i = h; i < h + LERF_S1_SPLIT; ++i)
-#pragma unroll
-            for (int n = 0; n < 5; ++n) e[i][n] = W[i].ldi8(n);
+    for (int i = 0; i < NROT; ++i) {
+        W[i] = simplex_walk<1>(ka, basea, rb[i], rc[i], rd[i], sb, sc, sd);
+        E[i] = byte_gather(W[i]);
         __builtin_amdgcn_sched_barrier(0);
     }
-#else
-#pragma unroll
-    for (int i = 0; i < NROT; ++i) W[i] = simplex_walk<1>(ka, basea, rb[i], rc[i], rd[i], sb, sc, sd);
-    // stage C: all LUT gathers in flight together
-#pragma unroll
-    for (int i = 0; i < NROT; ++i)
-#pragma unroll
-        for (int n = 0; n < 5; ++n) e[i][n] = W[i].ldi8(n);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    // stage D: sum_n w_n P_n = 16 P_0 + sum_n f_n (P_{n+1} - P_n)   (w_0 = 16 - f_0, w_n = f_{n-1} - f_n, w_4 = f_3):
-    //          four multiply-adds and four subtractions per lookup instead of five weights + five multiply-adds
+    // stage D: the Abel sums of the walks (byte_abel) + 16 x the sum of their base corners
     int acc = 0, sum0 = 0;
 #pragma unroll
     for (int i = 0; i < NROT; ++i) {
-        sum0 += e[i][0];
-#ifndef LERF_S1_MUL24
-        acc = mad_i16_keyhi(e[i][1] - e[i][0], W[i].k0, acc);
-        acc = mad_i16_keyhi(e[i][2] - e[i][1], W[i].k1, acc);
-        acc = mad_i16_keyhi(e[i][3] - e[i][2], W[i].k2, acc);
-        acc = mad_i16_keyhi(e[i][4] - e[i][3], W[i].k3, acc);
-#else
-        acc += __mul24((int)W[i].f0, e[i][1] - e[i][0]);
-        acc += __mul24((int)W[i].f1, e[i][2] - e[i][1]);
-        acc += __mul24((int)W[i].f2, e[i][3] - e[i][2]);
-        acc += __mul24((int)W[i].f3, e[i][4] - e[i][3]);
-#endif
+        sum0 += E[i].e0;
+        acc = byte_abel(W[i], E[i], acc);
     }
     return acc + kQ * sum0;
 }
@@ -814,6 +649,75 @@ __device__ __forceinline__ void byte_phase_rt(const int8_t* lut, const uint8_t* 
 }
 
 // ---------------------------------------------------------------------------
+// The byte-LUT phase chain (stage 1, stage 2 of LeRF-L): LUT i + 1 rides in registers behind the lookups of LUT i, so that
+// only the LDS store of a LUT, not its L2 round trip, stands between two phases.  The chain is
+//   first LUT -> LDS, barrier;  per phase: load next, run, barrier, store next, barrier.
+// The registers are six named uint4 handed on by reference: an array or a struct that lives across the position loop
+// ends up in scratch (a struct with load() / store() methods: 96 bytes of it in every kernel that runs stage 1).
+// `pack` = the chain's first LUT, the others follow at LUT_PAD; `body` runs one phase; `mark(k)` is called behind every
+// barrier (k = 0: the first LUT has landed, 1 + 2 i: phase i is done, 2 + 2 i: LUT i + 1 has landed) for what a kernel hangs
+// there: its stamps, work that hides under the first phase.
+// ---------------------------------------------------------------------------
+constexpr int LUT_U4 = (LERF_LUT_ENTRIES + 15) / 16, LUT_U4_TAIL = LUT_U4 - 5 * NT;
+static_assert(LUT_U4_TAIL > 0 && LUT_U4_TAIL <= NT, "byte LUT = 5 full uint4 rounds + a tail");
+__device__ __forceinline__ void lut_regs_load(const uint8_t* __restrict__ src, int tid, uint4& n0, uint4& n1, uint4& n2, uint4& n3,
+                                              uint4& n4, uint4& n5) {
+    const uint4* s_ = reinterpret_cast<const uint4*>(src);
+    n0 = s_[tid]; n1 = s_[tid + NT]; n2 = s_[tid + 2 * NT]; n3 = s_[tid + 3 * NT]; n4 = s_[tid + 4 * NT];
+    if (tid < LUT_U4_TAIL) n5 = s_[tid + 5 * NT];
+}
+__device__ __forceinline__ void lut_regs_store(uint8_t* lut, int tid, const uint4& n0, const uint4& n1, const uint4& n2, const uint4& n3,
+                                               const uint4& n4, const uint4& n5) {
+    uint4* d_ = reinterpret_cast<uint4*>(lut);
+    d_[tid] = n0; d_[tid + NT] = n1; d_[tid + 2 * NT] = n2; d_[tid + 3 * NT] = n3; d_[tid + 4 * NT] = n4;
+    if (tid < LUT_U4_TAIL) d_[tid + 5 * NT] = n5;
+}
+struct NoMark { __device__ __forceinline__ void operator()(int) const {} };
+template <int I, int N, typename Body, typename Mark>
+__device__ __forceinline__ void lut_chain_step(uint8_t* lut, const uint8_t* __restrict__ pack, int tid, uint4& n0, uint4& n1, uint4& n2,
+                                               uint4& n3, uint4& n4, uint4& n5, Body& body, Mark& mark) {
+    if constexpr (I + 1 < N) lut_regs_load(pack + (I + 1) * LUT_PAD, tid, n0, n1, n2, n3, n4, n5);
+    body(std::integral_constant<int, I>{});
+    __syncthreads();
+    mark(1 + 2 * I);
+    if constexpr (I + 1 < N) {
+        lut_regs_store(lut, tid, n0, n1, n2, n3, n4, n5);
+        __syncthreads();
+        mark(2 + 2 * I);
+        lut_chain_step<I + 1, N>(lut, pack, tid, n0, n1, n2, n3, n4, n5, body, mark);
+    }
+}
+// N phases known at compile time: body(std::integral_constant<int, i>) runs phase i
+template <int N, typename Body, typename Mark>
+__device__ __forceinline__ void lut_chain(uint8_t* lut, const uint8_t* __restrict__ pack, int tid, Body body, Mark mark) {
+    uint4 n0, n1, n2, n3, n4, n5 = make_uint4(0, 0, 0, 0);
+    copy16<LERF_LUT_ENTRIES>(lut, pack, tid);
+    __syncthreads();
+    mark(0);
+    lut_chain_step<0, N>(lut, pack, tid, n0, n1, n2, n3, n4, n5, body, mark);
+}
+// n phases at run time (general kernels): body(i, more) runs phase i, more = another one follows
+template <typename Body, typename Mark>
+__device__ __forceinline__ void lut_chain_rt(uint8_t* lut, const uint8_t* __restrict__ pack, int n, int tid, Body body, Mark mark) {
+    uint4 n0, n1, n2, n3, n4, n5 = make_uint4(0, 0, 0, 0);
+    copy16<LERF_LUT_ENTRIES>(lut, pack, tid);
+    __syncthreads();
+    mark(0);
+#pragma unroll 1
+    for (int i = 0; i < n; ++i) {
+        const bool more = i + 1 < n;
+        if (more) lut_regs_load(pack + (size_t)(i + 1) * LUT_PAD, tid, n0, n1, n2, n3, n4, n5);
+        body(i, more);
+        __syncthreads();
+        if (more) {
+            lut_regs_store(lut, tid, n0, n1, n2, n3, n4, n5);
+            __syncthreads();
+        }
+    }
+}
+constexpr char kSctModes[3] = {'s', 'c', 't'};         // the published configuration's sampling patterns, in LUT order
+
+// ---------------------------------------------------------------------------
 // stage 3 helpers
 // ---------------------------------------------------------------------------
 // first i in [0,n) with a[i] >= key (a is non-decreasing), all 64 lanes of a wave cooperating:
@@ -987,6 +891,491 @@ __device__ __forceinline__ void warp_tile(const Params& P, const uint32_t* Dt, i
     }
 }
 
+// ---------------------------------------------------------------------------
+// The stages of the kernels up to the hyper region's packed dwords, in the order a workgroup runs them.  Each takes what it
+// needs of the tile as plain values (region origins in frame coordinates, LDS pointers) and is inlined into its kernel.
+// ---------------------------------------------------------------------------
+// ---- input tile (load_input_tile; `between()` rides behind its loads) and stage 1: the byte LUTs of the stage, 4 rotations
+//      each (eval_lut_sr.py:541-577), from the region at (fy0, fx0) of D::FY x D::FX pixels into dst8.  mark: see lut_chain.
+//      VMEM: interior tiles of device frames read their neighbourhood pixels over the vector-memory path (byte_phase_vmem;
+//      the specialised kernel then needs no input tile in LDS at all).  s1_kernel does; in sr_fused_kernel -- 72 x 72
+//      positions per tile -- it did not pay: 0.191 vs 0.184 ms per 1080 x 960 block; that kernel's stage 1 shares the CU
+//      with nothing else that uses the LDS less.  Pinned host frames (stream.StreamingSR) cross PCIe uncached: never.
+//      SKIP_OUTSIDE: see byte_phase.
+template <typename D, bool GEN, bool SKIP_OUTSIDE, bool VMEM, typename Between, typename Mark>
+__device__ __forceinline__ void stage1(uint8_t* smem, const Params& P, const uint8_t* __restrict__ img, int H, int W, int fy0, int fx0,
+                                       bool interior, uint8_t* dst8, int tid, Between between, Mark mark) {
+    const int iy0 = fy0 - R1, ix0 = fx0 - R1;
+    const int Hc = interior ? -1 : H, Wc = W;
+    uint8_t* lut8 = smem + D::OFF_LUT;
+    int8_t* lut = reinterpret_cast<int8_t*>(lut8);
+    int16_t* acc = reinterpret_cast<int16_t*>(smem + D::OFF_ACC);
+    const int div1 = kQ * 3;
+    const bool vmem = VMEM && interior && !P.host_input;
+    const uint8_t* vorg = img + ((int64_t)fy0 * W + fx0) * CH;
+    const int pitch = W * CH;
+    if (!GEN && vmem) {
+        lut_chain<3>(lut8, P.pack, tid, [&](auto I) {
+            constexpr int i = decltype(I)::value;
+            byte_phase_vmem<D::NF, D::FP, kSctModes[i], 0, 4, 1, i>(lut, vorg, pitch, acc, dst8, div1, 0, tid);
+        }, mark);
+        return;
+    }
+    const int cphase = load_input_tile<D::IY, D::IPB, D::IP>(smem + D::OFF_C, img, H, W, iy0, ix0, interior, tid, between);
+    const uint8_t* Ct = smem + D::OFF_C + cphase;
+    if constexpr (GEN) {
+        // any 1..4 patterns: the same phases with run-time offsets (lerf_luts_t.modes1 order)
+        const int dv = kQ * P.n1;
+        lut_chain_rt(lut8, P.pack, P.n1, tid, [&](int m, bool more) {
+            if (vmem) byte_phase_vmem_rt<D::NF, D::FP, 4>(lut, vorg, pitch, acc, dst8, dv, 0, tid, P.s1dyx[m], m == 0, !more);
+            else byte_phase_rt<D::NF, D::FP, D::IP, 4, SKIP_OUTSIDE>(lut, Ct, acc, dst8, fy0, fx0, iy0, ix0, Hc, Wc, dv, 0, tid, P.s1off[m], m == 0, !more);
+        }, mark);
+    } else {
+        lut_chain<3>(lut8, P.pack, tid, [&](auto I) {
+            constexpr int i = decltype(I)::value;
+            byte_phase<D::NF, D::FP, D::IP, kSctModes[i], 0, 4, 1, i, SKIP_OUTSIDE>(lut, Ct, acc, dst8, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
+        }, mark);
+    }
+}
+
+// ---- feat tile (with its halo) from the stage-1 launch -> Bt; out-of-frame positions take the clamped pixel, which is
+//      what stage 1 evaluates for them.  `between()` rides behind the loads
+template <typename D, typename Between>
+__device__ __forceinline__ void load_feat_tile(uint8_t* Bt, const uint8_t* feat, int H, int W, int fy0, int fx0, bool interior, int tid,
+                                               Between between) {
+    const uint8_t* __restrict__ fsrc = feat;
+    const bool dwords = interior && (D::FP & 3) == 0 && ((W * CH) & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & 3) == 0 && ((fx0 * CH) & 3) == 0;
+    if (dwords) {
+        constexpr int RD = D::FP / 4, ND = D::FY * RD, KD = (ND + NT - 1) / NT;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(fsrc + ((int64_t)fy0 * W + fx0) * CH);
+        const int rowdw = (W * CH) >> 2;
+        uint32_t v[KD];
+#pragma unroll
+        for (int k = 0; k < KD; ++k) {
+            const int p = min(tid + k * NT, ND - 1);
+            const int ry = p / RD;
+            v[k] = __builtin_nontemporal_load(&src[(int64_t)ry * rowdw + (p - ry * RD)]);
+        }
+        between();
+#pragma unroll
+        for (int k = 0; k < KD; ++k) {
+            const int p = tid + k * NT;
+            if (p < ND) reinterpret_cast<uint32_t*>(Bt)[p] = v[k];
+        }
+    } else {
+        constexpr int KI = (D::NF + NT - 1) / NT;
+        uint8_t v[KI];
+#pragma unroll
+        for (int k = 0; k < KI; ++k) {
+            const int p = min(tid + k * NT, D::NF - 1);
+            const int ry = p / D::FP;
+            const int r3 = p - ry * D::FP;
+            const int rx = r3 / CH;
+            const int gy = clampi(fy0 + ry, 0, H - 1), gx = clampi(fx0 + rx, 0, W - 1);
+            v[k] = fsrc[((int64_t)gy * W + gx) * CH + (r3 - rx * CH)];
+        }
+        between();
+#pragma unroll
+        for (int k = 0; k < KI; ++k) {
+            const int p = tid + k * NT;
+            if (p < D::NF) Bt[p] = v[k];
+        }
+    }
+}
+
+// ---- stage 2, LeRF-L: six byte LUTs (mode x rotation parity), 2 rotations each (eval_lut_sr.py:579-628); the hyper
+//      region's (alpha_q, 0, 0, feat-or-0) dwords go to Dt.  feat = the frame's stage-1 output (two-launch path)
+template <typename D, bool GEN, bool FROM_FEAT, typename Outside>
+__device__ __forceinline__ void stage2_linear(uint8_t* smem, const Params& P, const uint8_t* Bt, uint32_t* Dt, const uint8_t* feat, int W,
+                                              int hy0, int hx0, int fy0, int fx0, bool interior, int Hc, int Wc, int tid,
+                                              Outside outside_pixel) {
+    uint8_t* lut8 = smem + D::OFF_LUT;
+    int8_t* lut = reinterpret_cast<int8_t*>(lut8);
+    int16_t* acc = reinterpret_cast<int16_t*>(smem + D::OFF_ACC);
+    uint8_t* hq8 = smem + D::OFF_C;                   // input tile is dead: reuse for the u8 hyper values
+    const uint8_t* s2 = P.pack + (size_t)(GEN ? P.n1 : 3) * LUT_PAD;
+    // interior tiles of the two-launch path: the seven neighbourhood pixels of a position come from the stage-1 output
+    // in HBM/L2 over the vector-memory path, one position ahead (byte_phase_vmem); these phases are LDS-bound like stage 1
+    const bool vm2 = FROM_FEAT && interior;
+    const uint8_t* forg = FROM_FEAT ? feat + ((int64_t)hy0 * W + hx0) * CH : nullptr;
+    const int fpitch = W * CH;
+    if constexpr (GEN) {
+        // 2 * n2 LUTs (pattern x rotation parity), offsets of the two rotations of LUT l in P.s2off[l]
+        const int dv = kQ * 4 * P.n2;
+        lut_chain_rt(lut8, s2, 2 * P.n2, tid, [&](int l, bool more) {
+            if (vm2) byte_phase_vmem_rt<D::NH, D::HP, 2>(lut, forg, fpitch, acc, hq8, dv, 127, tid, P.s2dyx[l], l == 0, !more);
+            else byte_phase_rt<D::NH, D::HP, D::FP, 2>(lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, dv, 127, tid, P.s2off[l], l == 0, !more);
+        }, NoMark{});
+    } else {
+        const int div2 = kQ * 12;
+        lut_chain<6>(lut8, s2, tid, [&](auto I) {
+            constexpr int i = decltype(I)::value, PAR = i & 1, PH = i == 0 ? 0 : (i == 5 ? 2 : 1);
+            constexpr char MODE = kSctModes[i >> 1];
+            if (vm2) byte_phase_vmem<D::NH, D::HP, MODE, PAR, 2, 2, PH>(lut, forg, fpitch, acc, hq8, div2, 127, tid);
+            else byte_phase<D::NH, D::HP, D::FP, MODE, PAR, 2, 2, PH>(lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, div2, 127, tid);
+        }, NoMark{});
+    }
+    // pack (alpha_q, 0, 0, feat-or-0) dwords for stage 3
+    const bool pad_const = P.pad_mode == LERF_PAD_CONSTANT;
+    uint32_t tmp[(D::NH + NT - 1) / NT];
+#pragma unroll
+    for (int k = 0; k < (D::NH + NT - 1) / NT; ++k) {
+        int p = k * NT + tid;
+        tmp[k] = 0;
+        if (p < D::NH) {
+            bool inside;
+            int a = center_addr<D::HP, D::FP>(p, hy0, hx0, fy0, fx0, Hc, Wc, &inside);
+            uint32_t px = 0u;
+            if (inside) px = (uint32_t)Bt[a];
+            else if (!pad_const) {
+                const int ry = p / D::HP, r3 = p - ry * D::HP, rx = r3 / CH;
+                px = outside_pixel(hy0 + ry, hx0 + rx, r3 - rx * CH);
+            }
+            tmp[k] = (uint32_t)hq8[p] | (px << 24);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < (D::NH + NT - 1) / NT; ++k) {
+        int p = k * NT + tid;
+        if (p < D::NH) Dt[p] = tmp[k];
+    }
+}
+
+// ---- stage 2, LeRF-G: packed 3-channel LUT pieces, pixels binned by the top-axis level of their centre; the hyper
+//      region's (hq0, hq1, hq2, feat) dwords go to Dt
+template <typename D, bool GEN>
+__device__ __forceinline__ void stage2_gauss(uint8_t* smem, const Params& P, const uint8_t* Bt, uint32_t* Dt, int hy0, int hx0, int fy0,
+                                             int fx0, int Hc, int Wc, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    constexpr int MAXR = D::MAXR;
+    uint16_t* lst = reinterpret_cast<uint16_t*>(smem + D::OFF_LST);
+    int* tab = reinterpret_cast<int*>(smem + D::OFF_TAB);                // [wave][bin] counts
+    // Counting sort of the hyper-region positions by bin, every bin padded to whole waves: list entry i belongs to
+    // slot round i / NT of thread i % NT, so a 64-entry chunk (one wave in one round) never mixes bins.  One barrier:
+    // per-thread histograms -> wave scans -> the 16 x 4 wave totals through LDS -> every wave derives its own bases.
+    // Positions of the hyper region that lie outside the frame (tiles on the right / bottom edge, the halo ring of edge
+    // tiles) are not looked up at all: stage 3 reads them as replicas of the clamped position (edge-padded hyper maps,
+    // zero image), which fill_outside() below copies once the in-frame values exist.  A 28-row strip tile or the
+    // last tile row of a 1080-row frame then costs what its in-frame part costs.
+    for (int i = tid; i < MAXR * NT / 2; i += NT) reinterpret_cast<uint32_t*>(lst)[i] = 0xFFFFFFFFu;
+    constexpr int KH = (D::NH + NT - 1) / NT;
+    static_assert(KH <= 15 && NBIN <= 4 && NW == 16, "nibble counts, one byte field per bin, one lane per (wave, bin)");
+    uint32_t qlo = 0, qhi = 0;              // 4 bits per owned position p = tid * KH + k: its bin, 15 = not looked up (thread-major lists = position order)
+    uint32_t xa, xb;                        // per-thread counts of bins (0, 1) and (2, 3), two 16-bit fields per register
+    {
+        uint32_t hist = 0;                  // one byte per bin
+#pragma unroll
+        for (int k = 0; k < KH; ++k) {
+            const int p = tid * KH + k;
+            uint32_t q = 15;
+            if (p < D::NH) {
+                bool in = true;
+                const int a = center_addr<D::HP, D::FP>(p, hy0, hx0, fy0, fx0, Hc, Wc, &in);
+                // The last row and the last column of the hyper region are never read by an owned output: a tile owns the
+                // outputs whose first tap lies in [t0 - S/2, t0 + T - S/2), so their taps end at t0 + T + S/2 - 2, one short of
+                // the region's end (the frame's own trailing outputs reach it -- as out-of-frame positions, which fill_outside()
+                // supplies).  Not looked up: 3 % of the positions (66 x 66 -> 65 x 65), 13 slot rounds instead of 14.
+                if (D::HR > 0) {
+                    const int ry = p / D::HP, r3 = p - ry * D::HP;
+                    if (ry == D::HY - 1 || r3 >= (D::HX - 1) * CH) in = false;
+                }
+                if (in) q = bin_of_level((uint32_t)Bt[a] >> 4);
+            }
+            if (k < 8) qlo |= q << (4 * k); else qhi |= q << (4 * (k - 8));
+            hist += q < NBIN ? 1u << (8 * q) : 0u;
+        }
+        xa = (hist & 0xFFu) | ((hist << 8) & 0xFF0000u);
+        xb = ((hist >> 16) & 0xFFu) | ((hist >> 8) & 0xFF0000u);
+    }
+    // wave-inclusive scans of the packed count pairs (row shifts + the two row broadcasts of the DPP unit)
+    auto wave_scan = [](uint32_t v) {
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);     // row_shr:1
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);     // row_shr:2
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);     // row_shr:4
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);     // row_shr:8
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);     // row_bcast:15
+        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);     // row_bcast:31
+        return v;
+    };
+    const uint32_t ia = wave_scan(xa), ib = wave_scan(xb);
+    if (lane == 63) {
+        int* t = tab + wave * 4;
+        t[0] = (int)(ia & 0xFFFFu); t[1] = (int)(ia >> 16); t[2] = (int)(ib & 0xFFFFu); t[3] = (int)(ib >> 16);
+    }
+    __syncthreads();
+    // Every wave turns the 16 x 4 wave counts into what it needs itself (lane = w * 4 + b), in registers: the list base
+    // of each of its own bins, and -- the same in all waves -- each bin's first chunk and one past its last (a byte
+    // each) and the set of non-empty bins.  No second barrier, no table to read back.
+    uint32_t ne_bins, cs_pack, ce_pack;          // wave-uniform
+    uint32_t cur01, cur23;                       // this thread's list cursors, two 16-bit fields per register
+    {
+        const int bb = lane & 3;                             // lane = w * 4 + bb
+        const int c = tab[lane];
+        int incl = c;                                        // scan over the waves of a bin: lanes 4 apart
+#pragma unroll
+        for (int d = 4; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        const int total = __shfl(incl, 60 + bb);
+        const int padded = (total + 63) & ~63;
+        int start = padded;                                  // scan over the bins: 4 neighbouring lanes
+#pragma unroll
+        for (int d = 1; d < 4; d <<= 1) {
+            const int up = __shfl_up(start, d, 4);
+            if (bb >= d) start += up;
+        }
+        start -= padded;
+        const int base = start + incl - c;                   // list base of (wave w, bin bb)
+        const int wl = __builtin_amdgcn_readfirstlane(wave) * 4;
+        const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane(base, wl), b1 = (uint32_t)__builtin_amdgcn_readlane(base, wl + 1),
+                       b2 = (uint32_t)__builtin_amdgcn_readlane(base, wl + 2), b3 = (uint32_t)__builtin_amdgcn_readlane(base, wl + 3);
+        const uint32_t ea = ia - xa, eb = ib - xb;           // counts of the lanes below
+        cur01 = ((b0 + (ea & 0xFFFFu)) & 0xFFFFu) | ((b1 + (ea >> 16)) << 16);
+        cur23 = ((b2 + (eb & 0xFFFFu)) & 0xFFFFu) | ((b3 + (eb >> 16)) << 16);
+        const int sc = start >> 6, ec = (start + padded) >> 6;           // chunks: < 256
+        cs_pack = (uint32_t)__builtin_amdgcn_readlane(sc, 0) | ((uint32_t)__builtin_amdgcn_readlane(sc, 1) << 8) |
+                  ((uint32_t)__builtin_amdgcn_readlane(sc, 2) << 16) | ((uint32_t)__builtin_amdgcn_readlane(sc, 3) << 24);
+        ce_pack = (uint32_t)__builtin_amdgcn_readlane(ec, 0) | ((uint32_t)__builtin_amdgcn_readlane(ec, 1) << 8) |
+                  ((uint32_t)__builtin_amdgcn_readlane(ec, 2) << 16) | ((uint32_t)__builtin_amdgcn_readlane(ec, 3) << 24);
+        ne_bins = (uint32_t)(__ballot(total > 0) & 0xFull);
+    }
+    // The next piece rides in registers behind the lookups of the current one: NSLAB x 16 bytes per thread.
+    uint4 pr[NSLAB];
+#pragma unroll
+    for (int i = 0; i < NSLAB; ++i) pr[i] = make_uint4(0, 0, 0, 0);
+    const uint8_t* s2p = P.pack + (size_t)(GEN ? P.n1 : 3) * LUT_PAD;          // [LUT l][bin b][PIECE_BYTES], blocks pre-permuted
+    const int NL2 = GEN ? 2 * P.n2 : 6;                // stage-2 LUTs: pattern x rotation parity
+    auto pre_load = [&](int l, int bq) {
+        const uint4* s_ = reinterpret_cast<const uint4*>(s2p + ((size_t)l * NBIN + bq) * PIECE_BYTES) + (wave * 64 + lane);
+#pragma unroll
+        for (int i = 0; i < NSLAB; ++i) pr[i] = s_[i * NT];
+    };
+    const int nbins = __builtin_popcount(ne_bins);
+    const int nph = nbins * NL2;
+    if (nph > 0) pre_load(0, __builtin_ctz(ne_bins));      // in flight during the scatter and the slot set-up
+    {
+        // scatter: a position's list entry = the thread's cursor of its bin, which then moves on (registers only).
+        // The entry is the position's feat-tile ADDRESS (listed positions lie inside the frame, so it is the unclamped
+        // one: one increment per position, a row step every HP positions), which the slot set-up then reads back
+        // as it is -- no second address computation per slot.
+        const int p0 = tid * KH, ry0 = p0 / D::HP;
+        uint32_t col = (uint32_t)(p0 - ry0 * D::HP);
+        uint32_t ap = (uint32_t)((ry0 + D::HO) * D::FP + D::HO * CH) + col;
+#pragma unroll
+        for (int k = 0; k < KH; ++k) {
+            const uint32_t q = k < 8 ? (qlo >> (4 * k)) & 0xFu : (qhi >> (4 * (k - 8))) & 0xFu;
+            if (q < NBIN) {
+                const uint32_t pair = q < 2 ? cur01 : cur23;
+                const uint32_t v = (q & 1u) ? pair >> 16 : pair & 0xFFFFu;
+                lst[v] = (uint16_t)ap;
+                const uint32_t inc = (q & 1u) ? 0x10000u : 1u;
+                if (q < 2) cur01 += inc; else cur23 += inc;
+            }
+            ++ap;
+            if (++col == (uint32_t)D::HP) { col = 0; ap += (uint32_t)(D::FP - D::HP); }
+        }
+    }
+    __syncthreads();
+    // slots -> registers.  Per slot: the feat-tile address of its centre (16 bits, two slots per VGPR) and three
+    // accumulators (accA: e0 | e2 << 16 in 16-bit fields; accB: e2 + 256 e1).  Padding lanes of a partly filled wave repeat the wave's
+    // first real position (same bin, same LDS words: broadcast reads) into accumulators nobody reads, so the lookup
+    // loop needs no per-lane test; `vmask` remembers which slots are real, and the position id comes back out of the
+    // address when the sums are finalised (listed positions are inside the frame: the address is not clamped).
+    constexpr int MAXP = (MAXR + 1) / 2;
+    uint32_t slot2[MAXP];
+    uint32_t accA[MAXR], accB[MAXR];
+    uint32_t wrounds = 0;                 // bit k: this wave has a real position in round k (wave-uniform)
+    uint32_t vmask = 0;                   // bit k: this lane's slot k is real
+#pragma unroll
+    for (int k = 0; k < MAXR; ++k) {
+        const uint32_t p = lst[k * NT + tid];
+        uint32_t a = p;
+        if (p != 0xFFFFu) vmask |= 1u << k;
+        const unsigned long long real = __ballot(p != 0xFFFFu);
+        if (real != 0ull) {
+            const uint32_t a1 = (uint32_t)__builtin_amdgcn_readlane((int)a, (int)__builtin_ctzll(real));
+            if (p == 0xFFFFu) a = a1;
+            wrounds |= 1u << k;
+        }
+        if (k & 1) slot2[k >> 1] |= a << 16; else slot2[k >> 1] = a;
+        accA[k] = 0;
+        accB[k] = 0;
+    }
+    __syncthreads();                      // the lists are dead: the first piece may land on them
+
+    LERF_STAMP(7);
+    // The piece travels as NSLAB x 16 bytes per thread (wave w, slab i: 1-KiB block B = 16 i + w of the piece, lane L
+    // its bytes 16 L..16 L+15) and is stored with ds_write_addtid_b32 (address = M0 + offset + 4*lane, no address
+    // VGPR: 128 B/clk/CU against 79 for ds_write_b128).  addtid puts component c of all lanes at block + 256 c + 4 L,
+    // so the pack holds every block pre-permuted (global dword 4L+c = logical dword 64c+L) and LDS ends up in
+    // natural order.  M0 = the wave's block column; the 16-bit offset reaches 4 slabs.
+#define LERF_ADDTID(V, OFF) asm volatile("ds_write_addtid_b32 %0 offset:" #OFF :: "v"(V) : "memory")
+#define LERF_ADDTID4(R, OFF0, OFF1, OFF2, OFF3) \
+    LERF_ADDTID(R.x, OFF0); LERF_ADDTID(R.y, OFF1); LERF_ADDTID(R.z, OFF2); LERF_ADDTID(R.w, OFF3)
+#define LERF_SET_M0(V) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" :: "s"(V) : "memory")
+    auto pre_store = [&]() {
+        const uint32_t m0a = __builtin_amdgcn_readfirstlane((uint32_t)D::OFF_X + (uint32_t)wave * 1024u);
+        // slab i holds blocks 16 i + wave: the last slab is partial (blocks beyond PIECE_BLOCKS carry no data)
+#define LERF_SLAB_OK(I) ((I) < NSLAB && (16 * (I) + 15 < PIECE_BLOCKS || 16 * (I) + wave < PIECE_BLOCKS))
+        LERF_SET_M0(m0a);
+        if (LERF_SLAB_OK(0)) { LERF_ADDTID4(pr[0], 0, 256, 512, 768); }
+        if (LERF_SLAB_OK(1)) { LERF_ADDTID4(pr[1 < NSLAB ? 1 : 0], 16384, 16640, 16896, 17152); }
+        if (LERF_SLAB_OK(2)) { LERF_ADDTID4(pr[2 < NSLAB ? 2 : 0], 32768, 33024, 33280, 33536); }
+        if (LERF_SLAB_OK(3)) { LERF_ADDTID4(pr[3 < NSLAB ? 3 : 0], 49152, 49408, 49664, 49920); }
+        if (NSLAB > 4) {
+            LERF_SET_M0(m0a + 65536u);
+            if (LERF_SLAB_OK(4)) { LERF_ADDTID4(pr[4 < NSLAB ? 4 : 0], 0, 256, 512, 768); }
+            if (LERF_SLAB_OK(5)) { LERF_ADDTID4(pr[5 < NSLAB ? 5 : 0], 16384, 16640, 16896, 17152); }
+            if (LERF_SLAB_OK(6)) { LERF_ADDTID4(pr[6 < NSLAB ? 6 : 0], 32768, 33024, 33280, 33536); }
+            if (LERF_SLAB_OK(7)) { LERF_ADDTID4(pr[7 < NSLAB ? 7 : 0], 49152, 49408, 49664, 49920); }
+        }
+        if (NSLAB > 8) {
+            LERF_SET_M0(m0a + 81920u);       // slab 5's base: M0 stays below 128 KiB, the offset field supplies the rest
+            if (LERF_SLAB_OK(8)) { LERF_ADDTID4(pr[8 < NSLAB ? 8 : 0], 49152, 49408, 49664, 49920); }
+        }
+        static_assert(NSLAB <= 9, "three M0 windows");
+#undef LERF_SLAB_OK
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+    // phases = (non-empty bin) x (6 LUTs).  The next piece is fetched into registers while the current one is being
+    // used, so the L2 latency of the piece copies hides behind the lookups.
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    // per-bin scalars, refreshed when a bin's first LUT comes up (kept loop-carried on purpose: loop-invariant code
+    // motion out of an inner per-LUT loop would park every round's slot address in a register of its own)
+    int bq = 0, bq_next = 0, l = 0, bi = 0;
+    uint32_t ne_left = ne_bins;               // non-empty bins not yet started
+    uint32_t act = 0, qbase = 0;
+    for (int ph = 0; ph < nph; ++ph) {
+        if (l == 0) {
+            // its level range, and this wave's rounds: chunk 16 k + wave inside [cs, ce) -- one scalar bit test per
+            // unrolled round
+            bq = __builtin_ctz(ne_left);
+            ne_left &= ne_left - 1u;
+            bq_next = ne_left != 0u ? __builtin_ctz(ne_left) : 0;
+            const int cs = (int)((cs_pack >> (8 * bq)) & 0xFFu), ce = (int)((ce_pack >> (8 * bq)) & 0xFFu);
+            const int klo = cs > wv ? (cs - wv + 15) >> 4 : 0, khi = ce > wv ? (ce - wv + 15) >> 4 : 0;
+            act = wrounds & ((1u << khi) - 1u) & ~((1u << klo) - 1u);
+            // LDS address of the piece's logical entry 0 (the piece starts at top-axis level bin_lo(bq))
+            qbase = lds_addr(smem + D::OFF_X) - (uint32_t)bin_lo(bq) * (kStrideA * 4u);
+        }
+        const unsigned long long t_copy = LERF_NOW();
+        (void)t_copy;
+        pre_store();
+        Off3 o0, o1;                                     // LUT l = mode (l>>1), rotation parity (l&1)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            o0.o[i] = P.s2off[l][i];
+            o1.o[i] = P.s2off[l][3 + i];
+        }
+        const uint32_t bt_a = lds_addr(Bt);
+        const unsigned st_a = kStrideA * 4, st_b = kStrideB * 4, st_c = kStrideC * 4, st_d = kStrideD * 4;   // axis strides, bytes
+        __syncthreads();
+        if (l < NL2 - 1) pre_load(l + 1, bq);
+        else if (bi + 1 < nbins) pre_load(0, bq_next);
+        LERF_STAMP_ADD(8, t_copy);
+        const unsigned long long t_look = LERF_NOW();
+        (void)t_look;
+#pragma unroll
+        for (int k = 0; k < MAXR; ++k) {
+            if ((act >> k) & 1u) {
+                const uint32_t sa = (k & 1) ? (slot2[k >> 1] >> 16) : (slot2[k >> 1] & 0xFFFFu);
+                // stage A: the 7 pixel reads of the two rotations (high-half loads, see lds_pixel_hi)
+                const uint32_t cpa = bt_a + sa;
+                uint32_t ra = lds_pixel_hi(cpa);
+                uint32_t rb0 = lds_pixel_hi(cpa + (uint32_t)o0.o[0]), rc0 = lds_pixel_hi(cpa + (uint32_t)o0.o[1]),
+                         rd0 = lds_pixel_hi(cpa + (uint32_t)o0.o[2]);
+                uint32_t rb1 = lds_pixel_hi(cpa + (uint32_t)o1.o[0]), rc1 = lds_pixel_hi(cpa + (uint32_t)o1.o[1]),
+                         rd1 = lds_pixel_hi(cpa + (uint32_t)o1.o[2]);
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ra), "+v"(rb0), "+v"(rc0), "+v"(rd0), "+v"(rb1), "+v"(rc1), "+v"(rd1));
+                // stage B: both walks (LDS addresses into the piece)
+                const int basea = (int)(__umul24(msb_of(ra), kStrideA * 4) + qbase);
+                const unsigned ka = key_of(ra, st_a);
+                const Walk<4> W0 = simplex_walk<4>(ka, basea, rb0, rc0, rd0, st_b, st_c, st_d);
+                const Walk<4> W1 = simplex_walk<4>(ka, basea, rb1, rc1, rd1, st_b, st_c, st_d);
+                // stage C: ten dword gathers in flight together
+                uint32_t d0[5], d1[5];
+#pragma unroll
+                for (int n = 0; n < 5; ++n) d0[n] = W0.ld32(n);
+#pragma unroll
+                for (int n = 0; n < 5; ++n) d1[n] = W1.ld32(n);
+                __builtin_amdgcn_sched_barrier(0);
+                // stage D: two multiply-adds per corner.  The entry is e0 | 0 << 8 | e2 << 16 | e1 << 24: a 24-bit multiply reads
+                // bits 0..23 only, so the (e0, e2) pair needs no mask; the second one multiplies the entry's HIGH HALF
+                // (e2 + 256 e1, v_mad_u32_u16 with op_sel) without a shift -- accB = sum w e2 + 256 sum w e1, and the e2
+                // sum is already in accA's upper field, so the finalisation takes it out again (round 3: 3 -> 2
+                // instructions per corner, 87 -> 77 per slot)
+                const unsigned w0[5] = {(unsigned)kQ - W0.f0, W0.f0 - W0.f1, W0.f1 - W0.f2, W0.f2 - W0.f3, W0.f3};
+                const unsigned w1[5] = {(unsigned)kQ - W1.f0, W1.f0 - W1.f1, W1.f1 - W1.f2, W1.f2 - W1.f3, W1.f3};
+                uint32_t a = accA[k], bb = accB[k];
+#pragma unroll
+                for (int n = 0; n < 5; ++n) {
+                    a = mad_u24(w0[n], d0[n], a);
+                    bb = mad_hi16(w0[n], d0[n], bb);
+                }
+#pragma unroll
+                for (int n = 0; n < 5; ++n) {
+                    a = mad_u24(w1[n], d1[n], a);
+                    bb = mad_hi16(w1[n], d1[n], bb);
+                }
+                accA[k] = a;
+                accB[k] = bb;
+            }
+        }
+        __syncthreads();
+        LERF_STAMP_ADD(9, t_look);
+        if (++l == NL2) { l = 0; ++bi; }
+    }
+    LERF_STAMP(10);
+    // finalise: hq = rne(clip(N/192 + 127)); entries are biased by +128 -> 12 lookups * 16 * 128 = 24576
+    //           N + 127*192 = field - 24576 + 24384 = field - 192
+    const int div2 = GEN ? kQ * 4 * P.n2 : kQ * 12;     // general kernels: 4 rotations x n2 patterns (same bias algebra)
+#pragma unroll
+    for (int k = 0; k < MAXR; ++k) {
+        if ((vmask >> k) & 1u) {
+            int n0 = (int)(accA[k] & 0xFFFFu) - div2;
+            int n2 = (int)(accA[k] >> 16) - div2;
+            int n1 = (int)((accB[k] - (accA[k] >> 16)) >> 8) - div2;      // accB = (e2 sum) + 256 (e1 sum), see the slot's MACs
+            uint32_t h0 = (uint32_t)rne_div_clip255_fast(n0, div2);
+            uint32_t h1 = (uint32_t)rne_div_clip255_fast(n1, div2);
+            uint32_t h2 = (uint32_t)rne_div_clip255_fast(n2, div2);
+            // feat-tile address -> hyper-region position: row (ry + R2) of pitch FP -> row ry of pitch HP, R2 pixels left
+            const uint32_t a = (k & 1) ? (slot2[k >> 1] >> 16) : (slot2[k >> 1] & 0xFFFFu);
+            const uint32_t row = a / (uint32_t)D::FP;
+            const uint32_t p = a - row * (uint32_t)(D::FP - D::HP) - (uint32_t)(D::HO * D::HP + D::HO * CH);
+            Dt[p] = h0 | (h1 << 8) | (h2 << 16) | ((uint32_t)Bt[a] << 24);
+        }
+    }
+}
+
+// ---- fill_outside: out-of-frame positions of the hyper region = the clamped position's hyper bytes, image byte as
+//      outside_pixel() gives it (edge tiles of the LeRF-G kernels that run stage 3)
+template <typename D, typename Outside>
+__device__ __forceinline__ void fill_outside(uint32_t* Dt, int hy0, int hx0, int H, int W, int tid, Outside outside_pixel) {
+    __syncthreads();
+    for (int p = tid; p < D::NH; p += NT) {
+        const int ry = p / D::HP, r3 = p - ry * D::HP, rx = r3 / CH, c = r3 - rx * CH;
+        const int gy = hy0 + ry, gx = hx0 + rx;
+        const int cy = clampi(gy, 0, H - 1), cx = clampi(gx, 0, W - 1);
+        if (cy != gy || cx != gx)
+            Dt[p] = (Dt[(cy - hy0) * D::HP + (cx - hx0) * CH + c] & 0x00FFFFFFu) | (outside_pixel(gy, gx, c) << 24);
+    }
+}
+
+// ---- EMIT: the tile's own block of packed dwords -> emit ([H][W][CH] uint32)
+template <typename D>
+__device__ __forceinline__ void emit_tile(const uint32_t* Dt, uint32_t* eo, int H, int W, int ty0, int tx0, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    __syncthreads();
+    const int rows = min(TH, H - ty0), cols3 = min(TW, W - tx0) * CH;
+    for (int il = wave; il < rows; il += NW) {
+        const uint32_t* srow = Dt + (il + D::HR) * D::HP + D::HR * CH;
+        uint32_t* drow = eo + ((int64_t)(ty0 + il) * W + tx0) * CH;
+        for (int x = lane; x < cols3; x += 64) drow[x] = srow[x];
+    }
+}
+
 // KINDW = LERF_KIND_* (| LERF_FUSED_WARP: stage 3 is the homographic warp of the tile's own output pixels, warp_tile())
 constexpr int LERF_FUSED_WARP = 16;
 template <int S, int KINDW, bool EMIT, bool FROM_FEAT = false, bool GEN = false>
@@ -1060,115 +1449,20 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
 #ifdef LERF_STAMPS
     if (tid == 0) { P.stamps[(size_t)blockIdx.x * 16 + 8] = 0; P.stamps[(size_t)blockIdx.x * 16 + 9] = 0; P.stamps[(size_t)blockIdx.x * 16 + 15] = 0; }
 #endif
-    if (!FROM_FEAT) {
-    // ---- input tile (load_input_tile), the geometry search riding behind its loads.  (The vector-memory pixel path of
-    //      s1_kernel was tried here too -- 72 x 72 positions per tile -- and did not pay: 0.191 vs 0.184 ms per 1080 x 960
-    //      block; this kernel's stage 1 shares the CU with nothing else that uses the LDS less.)
-    const int cphase = load_input_tile<D::IY, D::IPB, D::IP>(smem + D::OFF_C, img, H, W, iy0, ix0, interior, tid,
-                                                             [&]() { if (D::GEO_EARLY && !EMIT && !WARP) geo_search(); });
-
-    // ---- stage 1: three byte LUTs, 4 rotations each (eval_lut_sr.py:541-577)
-    {
-        const uint8_t* Ct = smem + D::OFF_C + cphase;
-        int8_t* lut = reinterpret_cast<int8_t*>(smem + D::OFF_LUT);
-        int16_t* acc = reinterpret_cast<int16_t*>(smem + D::OFF_ACC);
-        const int div1 = kQ * 3;
-        copy16<LERF_LUT_ENTRIES>(smem + D::OFF_LUT, P.pack + 0 * LUT_PAD, tid);
-        __syncthreads();
-        if (D::GEO_EARLY && !EMIT && !WARP) geo_stage();            // search results are in ctl; its loads hide behind phase s
-        LERF_STAMP(1);
-        // the next LUT rides in registers behind the lookups (explicit scalars: an array/struct that lives
-        // across the position loop ends up in scratch)
-        constexpr int L1N = (LERF_LUT_ENTRIES + 15) / 16, L1TAIL = L1N - 5 * NT;
-        static_assert(L1TAIL > 0 && L1TAIL <= NT, "stage-1 LUT = 5 full uint4 rounds + a tail");
-        uint4 n0, n1, n2, n3, n4, n5 = make_uint4(0, 0, 0, 0);
-#define LERF_S1_LOAD(SRC)                                                                          \
-        do {                                                                                       \
-            const uint4* s_ = reinterpret_cast<const uint4*>(SRC);                                 \
-            n0 = s_[tid]; n1 = s_[tid + NT]; n2 = s_[tid + 2 * NT]; n3 = s_[tid + 3 * NT]; n4 = s_[tid + 4 * NT]; \
-            if (tid < L1TAIL) n5 = s_[tid + 5 * NT];                                               \
-        } while (0)
-#define LERF_S1_STORE()                                                                            \
-        do {                                                                                       \
-            uint4* d_ = reinterpret_cast<uint4*>(smem + D::OFF_LUT);                               \
-            d_[tid] = n0; d_[tid + NT] = n1; d_[tid + 2 * NT] = n2; d_[tid + 3 * NT] = n3; d_[tid + 4 * NT] = n4; \
-            if (tid < L1TAIL) d_[tid + 5 * NT] = n5;                                               \
-        } while (0)
-        if constexpr (GEN) {
-            // any 1..4 patterns: the same phases with run-time offsets (lerf_luts_t.modes1 order)
-            const int dv = kQ * P.n1;
-#pragma unroll 1
-            for (int m = 0; m < P.n1; ++m) {
-                const bool more = m + 1 < P.n1;
-                if (more) LERF_S1_LOAD(P.pack + (size_t)(m + 1) * LUT_PAD);
-                byte_phase_rt<D::NF, D::FP, D::IP, 4>(lut, Ct, acc, Bt, fy0, fx0, iy0, ix0, Hc, Wc, dv, 0, tid, P.s1off[m], m == 0, !more);
-                __syncthreads();
-                if (more) {
-                    LERF_S1_STORE();
-                    __syncthreads();
-                }
+    // ---- the feat tile: stage 1 on the input tile (the geometry search rides behind the tile's loads, the staging of its
+    //      results, which are in ctl by then, behind phase s), or the output of the stage-1 launch
+    auto early_search = [&]() { if (D::GEO_EARLY && !EMIT && !WARP) geo_search(); };
+    if constexpr (!FROM_FEAT) {
+        stage1<D, GEN, false, false>(smem, P, img, H, W, fy0, fx0, interior, Bt, tid, early_search, [&](int k) {
+            if (k == 0) {
+                if (D::GEO_EARLY && !EMIT && !WARP) geo_stage();
+                LERF_STAMP(1);
+            } else {
+                LERF_STAMP(1 + k);                                   // 2 .. 6: the phases and LUT stores of the specialised kernels
             }
-        } else {
-        LERF_S1_LOAD(P.pack + 1 * LUT_PAD);
-        byte_phase<D::NF, D::FP, D::IP, 's', 0, 4, 1, 0>(lut, Ct, acc, Bt, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
-        __syncthreads();
-        LERF_STAMP(2);
-        LERF_S1_STORE();
-        __syncthreads();
-        LERF_STAMP(3);
-        LERF_S1_LOAD(P.pack + 2 * LUT_PAD);
-        byte_phase<D::NF, D::FP, D::IP, 'c', 0, 4, 1, 1>(lut, Ct, acc, Bt, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
-        __syncthreads();
-        LERF_STAMP(4);
-        LERF_S1_STORE();
-        __syncthreads();
-        LERF_STAMP(5);
-        byte_phase<D::NF, D::FP, D::IP, 't', 0, 4, 1, 2>(lut, Ct, acc, Bt, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
-        __syncthreads();
-        LERF_STAMP(6);
-        }
-    }
+        });
     } else {
-        // ---- feat tile (with its halo) from the stage-1 launch; out-of-frame positions take the clamped pixel,
-        //      which is what stage 1 evaluates for them
-        const uint8_t* __restrict__ fsrc = F.feat;
-        const bool dwords = interior && (D::FP & 3) == 0 && ((W * CH) & 3) == 0 && (reinterpret_cast<uintptr_t>(F.feat) & 3) == 0 && ((fx0 * CH) & 3) == 0;
-        if (dwords) {
-            constexpr int RD = D::FP / 4, ND = D::FY * RD, KD = (ND + NT - 1) / NT;
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(fsrc + ((int64_t)fy0 * W + fx0) * CH);
-            const int rowdw = (W * CH) >> 2;
-            uint32_t v[KD];
-#pragma unroll
-            for (int k = 0; k < KD; ++k) {
-                const int p = min(tid + k * NT, ND - 1);
-                const int ry = p / RD;
-                v[k] = __builtin_nontemporal_load(&src[(int64_t)ry * rowdw + (p - ry * RD)]);
-            }
-            if (D::GEO_EARLY && !EMIT && !WARP) geo_search();
-#pragma unroll
-            for (int k = 0; k < KD; ++k) {
-                const int p = tid + k * NT;
-                if (p < ND) reinterpret_cast<uint32_t*>(Bt)[p] = v[k];
-            }
-        } else {
-            constexpr int KI = (D::NF + NT - 1) / NT;
-            uint8_t v[KI];
-#pragma unroll
-            for (int k = 0; k < KI; ++k) {
-                const int p = min(tid + k * NT, D::NF - 1);
-                const int ry = p / D::FP;
-                const int r3 = p - ry * D::FP;
-                const int rx = r3 / CH;
-                const int gy = clampi(fy0 + ry, 0, H - 1), gx = clampi(fx0 + rx, 0, W - 1);
-                v[k] = fsrc[((int64_t)gy * W + gx) * CH + (r3 - rx * CH)];
-            }
-            if (D::GEO_EARLY && !EMIT && !WARP) geo_search();
-#pragma unroll
-            for (int k = 0; k < KI; ++k) {
-                const int p = tid + k * NT;
-                if (p < D::NF) Bt[p] = v[k];
-            }
-        }
+        load_feat_tile<D>(Bt, F.feat, H, W, fy0, fx0, interior, tid, early_search);
         __syncthreads();
         if (D::GEO_EARLY && !EMIT && !WARP) geo_stage();
         LERF_STAMP(6);
@@ -1180,428 +1474,23 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
     // (resize_right2d_numpy.py:143, 208) -- zero for the default "constant", otherwise the feat byte at the remapped
     // coordinate (inside the feat tile for edge / reflect / symmetric; wrap may reach the far side of the frame, which
     // the two-launch path reads from the stage-1 output in HBM)
+    const int pad_mode = P.pad_mode;
     auto outside_pixel = [&](int gy, int gx, int c) -> uint32_t {
-        if (P.pad_mode == LERF_PAD_CONSTANT) return 0u;
+        if (pad_mode == LERF_PAD_CONSTANT) return 0u;
         bool zy, zx;
-        const int sy = pad_index(gy, H, P.pad_mode, &zy), sx = pad_index(gx, W, P.pad_mode, &zx);
+        const int sy = pad_index(gy, H, pad_mode, &zy), sx = pad_index(gx, W, pad_mode, &zx);
         const int ry = sy - fy0, rx = sx - fx0;
         if (ry >= 0 && ry < D::FY && rx >= 0 && rx < D::FX) return (uint32_t)Bt[ry * D::FP + rx * CH + c];
         if (FROM_FEAT) return (uint32_t)F.feat[((int64_t)sy * W + sx) * CH + c];
         return 0u;                      // not reached: the host sends wrap padding through the two-launch path
     };
 
-    if (KIND == LERF_KIND_LINEAR) {
-        // ---- stage 2, LeRF-L: six byte LUTs (mode x rotation parity), 2 rotations each (eval_lut_sr.py:579-628)
-        int8_t* lut = reinterpret_cast<int8_t*>(smem + D::OFF_LUT);
-        int16_t* acc = reinterpret_cast<int16_t*>(smem + D::OFF_ACC);
-        uint8_t* hq8 = smem + D::OFF_C;                   // input tile is dead: reuse for the u8 hyper values
-        const uint8_t* s2 = P.pack + (size_t)(GEN ? P.n1 : 3) * LUT_PAD;
-        const int div2 = kQ * 12;
-        // every LUT but the first rides in registers behind the lookups of the previous one (as in stage 1), so that only the
-        // LDS store of a LUT, not its L2 round trip, stands between two phases
-        constexpr int L2N = (LERF_LUT_ENTRIES + 15) / 16, L2TAIL = L2N - 5 * NT;
-        static_assert(L2TAIL > 0 && L2TAIL <= NT, "byte LUT = 5 full uint4 rounds + a tail");
-        uint4 m0, m1, m2, m3, m4, m5 = make_uint4(0, 0, 0, 0);
-#define LERF_L2_LOAD(IDX)                                                                          \
-        do {                                                                                       \
-            const uint4* s_ = reinterpret_cast<const uint4*>(s2 + (IDX) * LUT_PAD);                \
-            m0 = s_[tid]; m1 = s_[tid + NT]; m2 = s_[tid + 2 * NT]; m3 = s_[tid + 3 * NT]; m4 = s_[tid + 4 * NT]; \
-            if (tid < L2TAIL) m5 = s_[tid + 5 * NT];                                               \
-        } while (0)
-#define LERF_L2_STORE()                                                                            \
-        do {                                                                                       \
-            uint4* d_ = reinterpret_cast<uint4*>(smem + D::OFF_LUT);                               \
-            d_[tid] = m0; d_[tid + NT] = m1; d_[tid + 2 * NT] = m2; d_[tid + 3 * NT] = m3; d_[tid + 4 * NT] = m4; \
-            if (tid < L2TAIL) d_[tid + 5 * NT] = m5;                                               \
-        } while (0)
-        // interior tiles of the two-launch path: the seven neighbourhood pixels of a position come from the stage-1 output
-        // in HBM/L2 over the vector-memory path, one position ahead (byte_phase_vmem); these phases are LDS-bound like stage 1
-#ifndef LERF_S1_LDS_PIXELS
-        const bool vm2 = FROM_FEAT && !GEN && interior;
-#else
-        const bool vm2 = false;
-#endif
-        const uint8_t* forg = FROM_FEAT ? F.feat + ((int64_t)hy0 * W + hx0) * CH : nullptr;
-        const int fpitch = W * CH;
-#define LERF_L2(NEXT, MODE, PAR, PH)                                                                       \
-        if ((NEXT) < 6) LERF_L2_LOAD(NEXT);                                                                \
-        if (vm2) byte_phase_vmem<D::NH, D::HP, MODE, PAR, 2, 2, PH>(lut, forg, fpitch, acc, hq8, div2, 127, tid); \
-        else byte_phase<D::NH, D::HP, D::FP, MODE, PAR, 2, 2, PH>(lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, div2, 127, tid); \
-        __syncthreads();                                                                                   \
-        if ((NEXT) < 6) {                                                                                  \
-            LERF_L2_STORE();                                                                               \
-            __syncthreads();                                                                               \
-        }
-        copy16<LERF_LUT_ENTRIES>(smem + D::OFF_LUT, s2 + 0 * LUT_PAD, tid);
-        __syncthreads();
-        if constexpr (GEN) {
-            // 2 * n2 LUTs (pattern x rotation parity), offsets of the two rotations of LUT l in P.s2off[l]
-            const int nl = 2 * P.n2, dv = kQ * 4 * P.n2;
-#pragma unroll 1
-            for (int l = 0; l < nl; ++l) {
-                const bool more = l + 1 < nl;
-                if (more) LERF_L2_LOAD(l + 1);
-                if (FROM_FEAT && interior)
-                    byte_phase_vmem_rt<D::NH, D::HP, 2>(lut, forg, fpitch, acc, hq8, dv, 127, tid, P.s2dyx[l], l == 0, !more);
-                else
-                byte_phase_rt<D::NH, D::HP, D::FP, 2>(lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, dv, 127, tid, P.s2off[l], l == 0, !more);
-                __syncthreads();
-                if (more) {
-                    LERF_L2_STORE();
-                    __syncthreads();
-                }
-            }
-        } else {
-        LERF_L2(1, 's', 0, 0)
-        LERF_L2(2, 's', 1, 1)
-        LERF_L2(3, 'c', 0, 1)
-        LERF_L2(4, 'c', 1, 1)
-        LERF_L2(5, 't', 0, 1)
-        LERF_L2(6, 't', 1, 2)
-        }
-#undef LERF_L2
-#undef LERF_L2_LOAD
-#undef LERF_L2_STORE
-        // pack (alpha_q, 0, 0, feat-or-0) dwords for stage 3
-        uint32_t tmp[(D::NH + NT - 1) / NT];
-#pragma unroll
-        for (int k = 0; k < (D::NH + NT - 1) / NT; ++k) {
-            int p = k * NT + tid;
-            tmp[k] = 0;
-            if (p < D::NH) {
-                bool inside;
-                int a = center_addr<D::HP, D::FP>(p, hy0, hx0, fy0, fx0, Hc, Wc, &inside);
-                uint32_t px = 0u;
-                if (inside) px = (uint32_t)Bt[a];
-                else if (P.pad_mode != LERF_PAD_CONSTANT) {
-                    const int ry = p / D::HP, r3 = p - ry * D::HP, rx = r3 / CH;
-                    px = outside_pixel(hy0 + ry, hx0 + rx, r3 - rx * CH);
-                }
-                tmp[k] = (uint32_t)hq8[p] | (px << 24);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < (D::NH + NT - 1) / NT; ++k) {
-            int p = k * NT + tid;
-            if (p < D::NH) Dt[p] = tmp[k];
-        }
-    } else {
-        // ---- stage 2, LeRF-G: packed 3-channel LUT pieces, pixels binned by the top-axis level of their centre
-        constexpr int MAXR = D::MAXR;
-        uint16_t* lst = reinterpret_cast<uint16_t*>(smem + D::OFF_LST);
-        int* tab = reinterpret_cast<int*>(smem + D::OFF_TAB);                // [wave][bin] counts
-        // Counting sort of the hyper-region positions by bin, every bin padded to whole waves: list entry i belongs to
-        // slot round i / NT of thread i % NT, so a 64-entry chunk (one wave in one round) never mixes bins.  One barrier:
-        // per-thread histograms -> wave scans -> the 16 x 4 wave totals through LDS -> every wave derives its own bases.
-        // Positions of the hyper region that lie outside the frame (tiles on the right / bottom edge, the halo ring of edge
-        // tiles) are not looked up at all: stage 3 reads them as replicas of the clamped position (edge-padded hyper maps,
-        // zero image), which fill_outside() below copies once the in-frame values exist.  A 28-row strip tile or the
-        // last tile row of a 1080-row frame then costs what its in-frame part costs.
-        for (int i = tid; i < MAXR * NT / 2; i += NT) reinterpret_cast<uint32_t*>(lst)[i] = 0xFFFFFFFFu;
-        constexpr int KH = (D::NH + NT - 1) / NT;
-        static_assert(KH <= 15 && NBIN <= 4 && NW == 16, "nibble counts, one byte field per bin, one lane per (wave, bin)");
-        uint32_t qlo = 0, qhi = 0;              // 4 bits per owned position p = tid * KH + k: its bin, 15 = not looked up (thread-major lists = position order)
-        uint32_t xa, xb;                        // per-thread counts of bins (0, 1) and (2, 3), two 16-bit fields per register
-        {
-            uint32_t hist = 0;                  // one byte per bin
-#pragma unroll
-            for (int k = 0; k < KH; ++k) {
-                const int p = tid * KH + k;
-                uint32_t q = 15;
-                if (p < D::NH) {
-                    bool in = true;
-                    const int a = center_addr<D::HP, D::FP>(p, hy0, hx0, fy0, fx0, Hc, Wc, &in);
-#ifndef LERF_FULL_RING
-                    // The last row and the last column of the hyper region are never read by an owned output: a tile owns the
-                    // outputs whose first tap lies in [t0 - S/2, t0 + T - S/2), so their taps end at t0 + T + S/2 - 2, one short of
-                    // the region's end (the frame's own trailing outputs reach it -- as out-of-frame positions, which fill_outside()
-                    // supplies).  Not looked up: 3 % of the positions (66 x 66 -> 65 x 65), 13 slot rounds instead of 14.
-                    if (D::HR > 0) {
-                        const int ry = p / D::HP, r3 = p - ry * D::HP;
-                        if (ry == D::HY - 1 || r3 >= (D::HX - 1) * CH) in = false;
-                    }
-#endif
-                    if (in) q = bin_of_level((uint32_t)Bt[a] >> 4);
-                }
-                if (k < 8) qlo |= q << (4 * k); else qhi |= q << (4 * (k - 8));
-                hist += q < NBIN ? 1u << (8 * q) : 0u;
-            }
-            xa = (hist & 0xFFu) | ((hist << 8) & 0xFF0000u);
-            xb = ((hist >> 16) & 0xFFu) | ((hist >> 8) & 0xFF0000u);
-        }
-        // wave-inclusive scans of the packed count pairs (row shifts + the two row broadcasts of the DPP unit)
-        auto wave_scan = [](uint32_t v) {
-            v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);     // row_shr:1
-            v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);     // row_shr:2
-            v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);     // row_shr:4
-            v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);     // row_shr:8
-            v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);     // row_bcast:15
-            v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);     // row_bcast:31
-            return v;
-        };
-        const uint32_t ia = wave_scan(xa), ib = wave_scan(xb);
-        if (lane == 63) {
-            int* t = tab + wave * 4;
-            t[0] = (int)(ia & 0xFFFFu); t[1] = (int)(ia >> 16); t[2] = (int)(ib & 0xFFFFu); t[3] = (int)(ib >> 16);
-        }
-        __syncthreads();
-        // Every wave turns the 16 x 4 wave counts into what it needs itself (lane = w * 4 + b), in registers: the list base
-        // of each of its own bins, and -- the same in all waves -- each bin's first chunk and one past its last (a byte
-        // each) and the set of non-empty bins.  No second barrier, no table to read back.
-        uint32_t ne_bins, cs_pack, ce_pack;          // wave-uniform
-        uint32_t cur01, cur23;                       // this thread's list cursors, two 16-bit fields per register
-        {
-            const int bb = lane & 3;                             // lane = w * 4 + bb
-            const int c = tab[lane];
-            int incl = c;                                        // scan over the waves of a bin: lanes 4 apart
-#pragma unroll
-            for (int d = 4; d < 64; d <<= 1) {
-                const int up = __shfl_up(incl, d);
-                if (lane >= d) incl += up;
-            }
-            const int total = __shfl(incl, 60 + bb);
-            const int padded = (total + 63) & ~63;
-            int start = padded;                                  // scan over the bins: 4 neighbouring lanes
-#pragma unroll
-            for (int d = 1; d < 4; d <<= 1) {
-                const int up = __shfl_up(start, d, 4);
-                if (bb >= d) start += up;
-            }
-            start -= padded;
-            const int base = start + incl - c;                   // list base of (wave w, bin bb)
-            const int wl = __builtin_amdgcn_readfirstlane(wave) * 4;
-            const uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane(base, wl), b1 = (uint32_t)__builtin_amdgcn_readlane(base, wl + 1),
-                           b2 = (uint32_t)__builtin_amdgcn_readlane(base, wl + 2), b3 = (uint32_t)__builtin_amdgcn_readlane(base, wl + 3);
-            const uint32_t ea = ia - xa, eb = ib - xb;           // counts of the lanes below
-            cur01 = ((b0 + (ea & 0xFFFFu)) & 0xFFFFu) | ((b1 + (ea >> 16)) << 16);
-            cur23 = ((b2 + (eb & 0xFFFFu)) & 0xFFFFu) | ((b3 + (eb >> 16)) << 16);
-            const int sc = start >> 6, ec = (start + padded) >> 6;           // chunks: < 256
-            cs_pack = (uint32_t)__builtin_amdgcn_readlane(sc, 0) | ((uint32_t)__builtin_amdgcn_readlane(sc, 1) << 8) |
-                      ((uint32_t)__builtin_amdgcn_readlane(sc, 2) << 16) | ((uint32_t)__builtin_amdgcn_readlane(sc, 3) << 24);
-            ce_pack = (uint32_t)__builtin_amdgcn_readlane(ec, 0) | ((uint32_t)__builtin_amdgcn_readlane(ec, 1) << 8) |
-                      ((uint32_t)__builtin_amdgcn_readlane(ec, 2) << 16) | ((uint32_t)__builtin_amdgcn_readlane(ec, 3) << 24);
-            ne_bins = (uint32_t)(__ballot(total > 0) & 0xFull);
-        }
-        // The next piece rides in registers behind the lookups of the current one: NSLAB x 16 bytes per thread.
-        uint4 pr[NSLAB];
-#pragma unroll
-        for (int i = 0; i < NSLAB; ++i) pr[i] = make_uint4(0, 0, 0, 0);
-        const uint8_t* s2p = P.pack + (size_t)(GEN ? P.n1 : 3) * LUT_PAD;          // [LUT l][bin b][PIECE_BYTES], blocks pre-permuted
-        const int NL2 = GEN ? 2 * P.n2 : 6;                // stage-2 LUTs: pattern x rotation parity
-        auto pre_load = [&](int l, int bq) {
-            const uint4* s_ = reinterpret_cast<const uint4*>(s2p + ((size_t)l * NBIN + bq) * PIECE_BYTES) + (wave * 64 + lane);
-#pragma unroll
-            for (int i = 0; i < NSLAB; ++i) pr[i] = s_[i * NT];
-        };
-        const int nbins = __builtin_popcount(ne_bins);
-        const int nph = nbins * NL2;
-        if (nph > 0) pre_load(0, __builtin_ctz(ne_bins));      // in flight during the scatter and the slot set-up
-        {
-            // scatter: a position's list entry = the thread's cursor of its bin, which then moves on (registers only).
-            // The entry is the position's feat-tile ADDRESS (listed positions lie inside the frame, so it is the unclamped
-            // one: one increment per position, a row step every HP positions), which the slot set-up then reads back
-            // as it is -- no second address computation per slot.
-            const int p0 = tid * KH, ry0 = p0 / D::HP;
-            uint32_t col = (uint32_t)(p0 - ry0 * D::HP);
-            uint32_t ap = (uint32_t)((ry0 + D::HO) * D::FP + D::HO * CH) + col;
-#pragma unroll
-            for (int k = 0; k < KH; ++k) {
-                const uint32_t q = k < 8 ? (qlo >> (4 * k)) & 0xFu : (qhi >> (4 * (k - 8))) & 0xFu;
-                if (q < NBIN) {
-                    const uint32_t pair = q < 2 ? cur01 : cur23;
-                    const uint32_t v = (q & 1u) ? pair >> 16 : pair & 0xFFFFu;
-                    lst[v] = (uint16_t)ap;
-                    const uint32_t inc = (q & 1u) ? 0x10000u : 1u;
-                    if (q < 2) cur01 += inc; else cur23 += inc;
-                }
-                ++ap;
-                if (++col == (uint32_t)D::HP) { col = 0; ap += (uint32_t)(D::FP - D::HP); }
-            }
-        }
-        __syncthreads();
-        // slots -> registers.  Per slot: the feat-tile address of its centre (16 bits, two slots per VGPR) and three
-        // accumulators (accA: e0 | e2 << 16 in 16-bit fields; accB: e2 + 256 e1).  Padding lanes of a partly filled wave repeat the wave's
-        // first real position (same bin, same LDS words: broadcast reads) into accumulators nobody reads, so the lookup
-        // loop needs no per-lane test; `vmask` remembers which slots are real, and the position id comes back out of the
-        // address when the sums are finalised (listed positions are inside the frame: the address is not clamped).
-        constexpr int MAXP = (MAXR + 1) / 2;
-        uint32_t slot2[MAXP];
-        uint32_t accA[MAXR], accB[MAXR];
-        uint32_t wrounds = 0;                 // bit k: this wave has a real position in round k (wave-uniform)
-        uint32_t vmask = 0;                   // bit k: this lane's slot k is real
-#pragma unroll
-        for (int k = 0; k < MAXR; ++k) {
-            const uint32_t p = lst[k * NT + tid];
-            uint32_t a = p;
-            if (p != 0xFFFFu) vmask |= 1u << k;
-            const unsigned long long real = __ballot(p != 0xFFFFu);
-            if (real != 0ull) {
-                const uint32_t a1 = (uint32_t)__builtin_amdgcn_readlane((int)a, (int)__builtin_ctzll(real));
-                if (p == 0xFFFFu) a = a1;
-                wrounds |= 1u << k;
-            }
-            if (k & 1) slot2[k >> 1] |= a << 16; else slot2[k >> 1] = a;
-            accA[k] = 0;
-            accB[k] = 0;
-        }
-        __syncthreads();                      // the lists are dead: the first piece may land on them
-
-        LERF_STAMP(7);
-        // The piece travels as NSLAB x 16 bytes per thread (wave w, slab i: 1-KiB block B = 16 i + w of the piece, lane L
-        // its bytes 16 L..16 L+15) and is stored with ds_write_addtid_b32 (address = M0 + offset + 4*lane, no address
-        // VGPR: 128 B/clk/CU against 79 for ds_write_b128).  addtid puts component c of all lanes at block + 256 c + 4 L,
-        // so the pack holds every block pre-permuted (global dword 4L+c = logical dword 64c+L) and LDS ends up in
-        // natural order.  M0 = the wave's block column; the 16-bit offset reaches 4 slabs.
-#define LERF_ADDTID(V, OFF) asm volatile("ds_write_addtid_b32 %0 offset:" #OFF :: "v"(V) : "memory")
-#define LERF_ADDTID4(R, OFF0, OFF1, OFF2, OFF3) \
-        LERF_ADDTID(R.x, OFF0); LERF_ADDTID(R.y, OFF1); LERF_ADDTID(R.z, OFF2); LERF_ADDTID(R.w, OFF3)
-#define LERF_SET_M0(V) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" :: "s"(V) : "memory")
-        auto pre_store = [&]() {
-            const uint32_t m0a = __builtin_amdgcn_readfirstlane((uint32_t)D::OFF_X + (uint32_t)wave * 1024u);
-            // slab i holds blocks 16 i + wave: the last slab is partial (blocks beyond PIECE_BLOCKS carry no data)
-#define LERF_SLAB_OK(I) ((I) < NSLAB && (16 * (I) + 15 < PIECE_BLOCKS || 16 * (I) + wave < PIECE_BLOCKS))
-            LERF_SET_M0(m0a);
-            if (LERF_SLAB_OK(0)) { LERF_ADDTID4(pr[0], 0, 256, 512, 768); }
-            if (LERF_SLAB_OK(1)) { LERF_ADDTID4(pr[1 < NSLAB ? 1 : 0], 16384, 16640, 16896, 17152); }
-            if (LERF_SLAB_OK(2)) { LERF_ADDTID4(pr[2 < NSLAB ? 2 : 0], 32768, 33024, 33280, 33536); }
-            if (LERF_SLAB_OK(3)) { LERF_ADDTID4(pr[3 < NSLAB ? 3 : 0], 49152, 49408, 49664, 49920); }
-            if (NSLAB > 4) {
-                LERF_SET_M0(m0a + 65536u);
-                if (LERF_SLAB_OK(4)) { LERF_ADDTID4(pr[4 < NSLAB ? 4 : 0], 0, 256, 512, 768); }
-                if (LERF_SLAB_OK(5)) { LERF_ADDTID4(pr[5 < NSLAB ? 5 : 0], 16384, 16640, 16896, 17152); }
-                if (LERF_SLAB_OK(6)) { LERF_ADDTID4(pr[6 < NSLAB ? 6 : 0], 32768, 33024, 33280, 33536); }
-                if (LERF_SLAB_OK(7)) { LERF_ADDTID4(pr[7 < NSLAB ? 7 : 0], 49152, 49408, 49664, 49920); }
-            }
-            if (NSLAB > 8) {
-                LERF_SET_M0(m0a + 81920u);       // slab 5's base: M0 stays below 128 KiB, the offset field supplies the rest
-                if (LERF_SLAB_OK(8)) { LERF_ADDTID4(pr[8 < NSLAB ? 8 : 0], 49152, 49408, 49664, 49920); }
-            }
-            static_assert(NSLAB <= 9, "three M0 windows");
-#undef LERF_SLAB_OK
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        };
-        // phases = (non-empty bin) x (6 LUTs).  The next piece is fetched into registers while the current one is being
-        // used, so the L2 latency of the piece copies hides behind the lookups.
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
-        // per-bin scalars, refreshed when a bin's first LUT comes up (kept loop-carried on purpose: loop-invariant code
-        // motion out of an inner per-LUT loop would park every round's slot address in a register of its own)
-        int bq = 0, bq_next = 0, l = 0, bi = 0;
-        uint32_t ne_left = ne_bins;               // non-empty bins not yet started
-        uint32_t act = 0, qbase = 0;
-        for (int ph = 0; ph < nph; ++ph) {
-            if (l == 0) {
-                // its level range, and this wave's rounds: chunk 16 k + wave inside [cs, ce) -- one scalar bit test per
-                // unrolled round
-                bq = __builtin_ctz(ne_left);
-                ne_left &= ne_left - 1u;
-                bq_next = ne_left != 0u ? __builtin_ctz(ne_left) : 0;
-                const int cs = (int)((cs_pack >> (8 * bq)) & 0xFFu), ce = (int)((ce_pack >> (8 * bq)) & 0xFFu);
-                const int klo = cs > wv ? (cs - wv + 15) >> 4 : 0, khi = ce > wv ? (ce - wv + 15) >> 4 : 0;
-                act = wrounds & ((1u << khi) - 1u) & ~((1u << klo) - 1u);
-                // LDS address of the piece's logical entry 0 (the piece starts at top-axis level bin_lo(bq))
-                qbase = lds_addr(smem + D::OFF_X) - (uint32_t)bin_lo(bq) * (kStrideA * 4u);
-            }
-            const unsigned long long t_copy = LERF_NOW();
-            (void)t_copy;
-            pre_store();
-            Off3 o0, o1;                                     // LUT l = mode (l>>1), rotation parity (l&1)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                o0.o[i] = P.s2off[l][i];
-                o1.o[i] = P.s2off[l][3 + i];
-            }
-            const uint32_t bt_a = lds_addr(Bt);
-            const unsigned st_a = kStrideA * 4, st_b = kStrideB * 4, st_c = kStrideC * 4, st_d = kStrideD * 4;   // axis strides, bytes
-            __syncthreads();
-            if (l < NL2 - 1) pre_load(l + 1, bq);
-            else if (bi + 1 < nbins) pre_load(0, bq_next);
-            LERF_STAMP_ADD(8, t_copy);
-            const unsigned long long t_look = LERF_NOW();
-            (void)t_look;
-#pragma unroll
-            for (int k = 0; k < MAXR; ++k) {
-                if ((act >> k) & 1u) {
-                    const uint32_t sa = (k & 1) ? (slot2[k >> 1] >> 16) : (slot2[k >> 1] & 0xFFFFu);
-                    // stage A: the 7 pixel reads of the two rotations (high-half loads, see lds_pixel_hi)
-                    const uint32_t cpa = bt_a + sa;
-                    uint32_t ra = lds_pixel_hi(cpa);
-                    uint32_t rb0 = lds_pixel_hi(cpa + (uint32_t)o0.o[0]), rc0 = lds_pixel_hi(cpa + (uint32_t)o0.o[1]),
-                             rd0 = lds_pixel_hi(cpa + (uint32_t)o0.o[2]);
-                    uint32_t rb1 = lds_pixel_hi(cpa + (uint32_t)o1.o[0]), rc1 = lds_pixel_hi(cpa + (uint32_t)o1.o[1]),
-                             rd1 = lds_pixel_hi(cpa + (uint32_t)o1.o[2]);
-                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ra), "+v"(rb0), "+v"(rc0), "+v"(rd0), "+v"(rb1), "+v"(rc1), "+v"(rd1));
-                    // stage B: both walks (LDS addresses into the piece)
-                    const int basea = (int)(__umul24(msb_of(ra), kStrideA * 4) + qbase);
-                    const unsigned ka = key_of(ra, st_a);
-                    const Walk<4> W0 = simplex_walk<4>(ka, basea, rb0, rc0, rd0, st_b, st_c, st_d);
-                    const Walk<4> W1 = simplex_walk<4>(ka, basea, rb1, rc1, rd1, st_b, st_c, st_d);
-                    // stage C: ten dword gathers in flight together
-                    uint32_t d0[5], d1[5];
-#pragma unroll
-                    for (int n = 0; n < 5; ++n) d0[n] = W0.ld32(n);
-#pragma unroll
-                    for (int n = 0; n < 5; ++n) d1[n] = W1.ld32(n);
-                    __builtin_amdgcn_sched_barrier(0);
-                    // stage D: two multiply-adds per corner.  The entry is e0 | 0 << 8 | e2 << 16 | e1 << 24: a 24-bit multiply reads
-                    // bits 0..23 only, so the (e0, e2) pair needs no mask; the second one multiplies the entry's HIGH HALF
-                    // (e2 + 256 e1, v_mad_u32_u16 with op_sel) without a shift -- accB = sum w e2 + 256 sum w e1, and the e2
-                    // sum is already in accA's upper field, so the finalisation takes it out again (round 3: 3 -> 2
-                    // instructions per corner, 87 -> 77 per slot)
-                    const unsigned w0[5] = {(unsigned)kQ - W0.f0, W0.f0 - W0.f1, W0.f1 - W0.f2, W0.f2 - W0.f3, W0.f3};
-                    const unsigned w1[5] = {(unsigned)kQ - W1.f0, W1.f0 - W1.f1, W1.f1 - W1.f2, W1.f2 - W1.f3, W1.f3};
-                    uint32_t a = accA[k], bb = accB[k];
-#pragma unroll
-                    for (int n = 0; n < 5; ++n) {
-                        a += __umul24(w0[n], d0[n]);
-                        bb = mad_hi16(w0[n], d0[n], bb);
-                    }
-#pragma unroll
-                    for (int n = 0; n < 5; ++n) {
-                        a += __umul24(w1[n], d1[n]);
-                        bb = mad_hi16(w1[n], d1[n], bb);
-                    }
-                    accA[k] = a;
-                    accB[k] = bb;
-                }
-            }
-            __syncthreads();
-            LERF_STAMP_ADD(9, t_look);
-            if (++l == NL2) { l = 0; ++bi; }
-        }
-        LERF_STAMP(10);
-        // finalise: hq = rne(clip(N/192 + 127)); entries are biased by +128 -> 12 lookups * 16 * 128 = 24576
-        //           N + 127*192 = field - 24576 + 24384 = field - 192
-#pragma unroll
-        for (int k = 0; k < MAXR; ++k) {
-            if ((vmask >> k) & 1u) {
-                const int div2 = GEN ? kQ * 4 * P.n2 : kQ * 12;     // general kernels: 4 rotations x n2 patterns (same bias algebra)
-                int n0 = (int)(accA[k] & 0xFFFFu) - div2;
-                int n2 = (int)(accA[k] >> 16) - div2;
-                int n1 = (int)((accB[k] - (accA[k] >> 16)) >> 8) - div2;      // accB = (e2 sum) + 256 (e1 sum), see the slot's MACs
-                uint32_t h0 = (uint32_t)rne_div_clip255_fast(n0, div2);
-                uint32_t h1 = (uint32_t)rne_div_clip255_fast(n1, div2);
-                uint32_t h2 = (uint32_t)rne_div_clip255_fast(n2, div2);
-                // feat-tile address -> hyper-region position: row (ry + R2) of pitch FP -> row ry of pitch HP, R2 pixels left
-                const uint32_t a = (k & 1) ? (slot2[k >> 1] >> 16) : (slot2[k >> 1] & 0xFFFFu);
-                const uint32_t row = a / (uint32_t)D::FP;
-                const uint32_t p = a - row * (uint32_t)(D::FP - D::HP) - (uint32_t)(D::HO * D::HP + D::HO * CH);
-                Dt[p] = h0 | (h1 << 8) | (h2 << 16) | ((uint32_t)Bt[a] << 24);
-            }
-        }
-    }
-
-    if (!EMIT && !WARP && KIND == LERF_KIND_GAUSS && Hc >= 0) {
-        // fill_outside: out-of-frame positions of the hyper region = the clamped position's hyper bytes, image byte 0
-        __syncthreads();
-        for (int p = tid; p < D::NH; p += NT) {
-            const int ry = p / D::HP, r3 = p - ry * D::HP, rx = r3 / CH, c = r3 - rx * CH;
-            const int gy = hy0 + ry, gx = hx0 + rx;
-            const int cy = clampi(gy, 0, H - 1), cx = clampi(gx, 0, W - 1);
-            if (cy != gy || cx != gx)
-                Dt[p] = (Dt[(cy - hy0) * D::HP + (cx - hx0) * CH + c] & 0x00FFFFFFu) | (outside_pixel(gy, gx, c) << 24);
-        }
-    }
+    // ---- stage 2: the hyper region's packed dwords
+    if constexpr (KIND == LERF_KIND_LINEAR)
+        stage2_linear<D, GEN, FROM_FEAT>(smem, P, Bt, Dt, F.feat, W, hy0, hx0, fy0, fx0, interior, Hc, Wc, tid, outside_pixel);
+    else
+        stage2_gauss<D, GEN>(smem, P, Bt, Dt, hy0, hx0, fy0, fx0, Hc, Wc, tid);
+    if (!EMIT && !WARP && KIND == LERF_KIND_GAUSS && Hc >= 0) fill_outside<D>(Dt, hy0, hx0, H, W, tid, outside_pixel);
 
     if constexpr (WARP) {
         // ---- stage 3 of the warp: the output pixels this tile owns, taps from the tile's packed dwords in LDS
@@ -1610,14 +1499,7 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
         return;
     }
     if (EMIT) {
-        __syncthreads();
-        uint32_t* eo = F.emit;
-        const int rows = min(TH, H - ty0), cols3 = min(TW, W - tx0) * CH;
-        for (int il = wave; il < rows; il += NW) {
-            const uint32_t* srow = Dt + (il + D::HR) * D::HP + D::HR * CH;
-            uint32_t* drow = eo + ((int64_t)(ty0 + il) * W + tx0) * CH;
-            for (int x = lane; x < cols3; x += 64) drow[x] = srow[x];
-        }
+        emit_tile<D>(Dt, F.emit, H, W, ty0, tx0, tid);
         return;
     }
 
@@ -2460,83 +2342,10 @@ s1_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
     const int H = F.H, W = F.W;
     const uint8_t* __restrict__ img = F.img;
     const bool interior = iy0 >= 0 && ix0 >= 0 && iy0 + D::IY <= H && ix0 + D::IX <= W;
-    const int Hc = interior ? -1 : H, Wc = W;
     uint8_t* Ft = smem + D::OFF_F;
     LERF_STAMP(0);
-
-#ifndef LERF_S1_LDS_PIXELS
-    // interior tiles of the specialised kernel: pixel reads on the vector-memory path (byte_phase_vmem), no input tile in LDS
-    const bool vmem_pixels = !GEN && interior && !P.host_input;      // pinned host frames (stream.StreamingSR) cross PCIe uncached
-#else
-    const bool vmem_pixels = false;
-#endif
-    if (vmem_pixels) {
-        int8_t* lut = reinterpret_cast<int8_t*>(smem + D::OFF_LUT);
-        int16_t* acc = reinterpret_cast<int16_t*>(smem + D::OFF_ACC);
-        const int div1 = kQ * 3;
-        const uint8_t* org = img + ((int64_t)fy0 * W + fx0) * CH;
-        const int pitch = W * CH;
-        constexpr int L1N = (LERF_LUT_ENTRIES + 15) / 16, L1TAIL = L1N - 5 * NT;
-        uint4 n0, n1, n2, n3, n4, n5 = make_uint4(0, 0, 0, 0);
-        copy16<LERF_LUT_ENTRIES>(smem + D::OFF_LUT, P.pack + 0 * LUT_PAD, tid);
-        __syncthreads();
-        LERF_S1_LOAD(P.pack + 1 * LUT_PAD);
-        byte_phase_vmem<D::NF, D::FP, 's', 0, 4, 1, 0>(lut, org, pitch, acc, Ft, div1, 0, tid);
-        __syncthreads();
-        LERF_S1_STORE();
-        __syncthreads();
-        LERF_S1_LOAD(P.pack + 2 * LUT_PAD);
-        byte_phase_vmem<D::NF, D::FP, 'c', 0, 4, 1, 1>(lut, org, pitch, acc, Ft, div1, 0, tid);
-        __syncthreads();
-        LERF_S1_STORE();
-        __syncthreads();
-        byte_phase_vmem<D::NF, D::FP, 't', 0, 4, 1, 2>(lut, org, pitch, acc, Ft, div1, 0, tid);
-        __syncthreads();
-    } else {
-    const int cphase = load_input_tile<D::IY, D::IPB, D::IP>(smem + D::OFF_C, img, H, W, iy0, ix0, interior, tid, []() {});
-    {
-        const uint8_t* Ct = smem + D::OFF_C + cphase;
-        int8_t* lut = reinterpret_cast<int8_t*>(smem + D::OFF_LUT);
-        int16_t* acc = reinterpret_cast<int16_t*>(smem + D::OFF_ACC);
-        const int div1 = kQ * 3;
-        constexpr int L1N = (LERF_LUT_ENTRIES + 15) / 16, L1TAIL = L1N - 5 * NT;
-        uint4 n0, n1, n2, n3, n4, n5 = make_uint4(0, 0, 0, 0);
-        copy16<LERF_LUT_ENTRIES>(smem + D::OFF_LUT, P.pack + 0 * LUT_PAD, tid);
-        __syncthreads();
-        if constexpr (GEN) {
-            const int dv = kQ * P.n1;
-            // interior tiles: neighbourhood pixels over the vector-memory path (byte_phase_vmem_rt), like the specialised kernel
-            const bool vmg = interior && !P.host_input;
-            const uint8_t* vorg = img + ((int64_t)fy0 * W + fx0) * CH;
-#pragma unroll 1
-            for (int m = 0; m < P.n1; ++m) {
-                const bool more = m + 1 < P.n1;
-                if (more) LERF_S1_LOAD(P.pack + (size_t)(m + 1) * LUT_PAD);
-                if (vmg) byte_phase_vmem_rt<D::NF, D::FP, 4>(lut, vorg, W * CH, acc, Ft, dv, 0, tid, P.s1dyx[m], m == 0, !more);
-                else
-                byte_phase_rt<D::NF, D::FP, D::IP, 4, true>(lut, Ct, acc, Ft, fy0, fx0, iy0, ix0, Hc, Wc, dv, 0, tid, P.s1off[m], m == 0, !more);
-                __syncthreads();
-                if (more) {
-                    LERF_S1_STORE();
-                    __syncthreads();
-                }
-            }
-        } else {
-        LERF_S1_LOAD(P.pack + 1 * LUT_PAD);
-        byte_phase<D::NF, D::FP, D::IP, 's', 0, 4, 1, 0, true>(lut, Ct, acc, Ft, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
-        __syncthreads();
-        LERF_S1_STORE();
-        __syncthreads();
-        LERF_S1_LOAD(P.pack + 2 * LUT_PAD);
-        byte_phase<D::NF, D::FP, D::IP, 'c', 0, 4, 1, 1, true>(lut, Ct, acc, Ft, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
-        __syncthreads();
-        LERF_S1_STORE();
-        __syncthreads();
-        byte_phase<D::NF, D::FP, D::IP, 't', 0, 4, 1, 2, true>(lut, Ct, acc, Ft, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
-        __syncthreads();
-        }
-    }
-    }
+    // positions outside the frame are not evaluated; interior tiles read their pixels over the vector-memory path
+    stage1<D, GEN, true, true>(smem, P, img, H, W, fy0, fx0, interior, Ft, tid, []() {}, NoMark{});
     LERF_STAMP(1);
     // the block's rows to P.feat
     uint8_t* __restrict__ fdst = F.feat;
@@ -2562,8 +2371,6 @@ s1_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
 #endif
 }
 
-#undef LERF_S1_LOAD
-#undef LERF_S1_STORE
 #undef LERF_ADDTID
 #undef LERF_ADDTID4
 #undef LERF_SET_M0

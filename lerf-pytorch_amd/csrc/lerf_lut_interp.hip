@@ -16,6 +16,7 @@
 // lut_interp_kernel / lut_interp_any_kernel -- the direct forms (LUT gathered from L1 / L2): small launches, other
 //   intervals, patterns reaching further than 3 pixels, more than 4 channels.
 #include "lerf_kernels.h"
+#include "lerf_simplex_lds.h"
 
 namespace lerf {
 
@@ -137,7 +138,6 @@ constexpr int LI_LH = LI_TL + LI_REACH;
 constexpr int LI_CMAX = 4;
 constexpr int LI_ENTRIES = kL * kL * kL * kL;                 // 83 521
 constexpr int LI_LUT_BYTES = (LI_ENTRIES + 63) / 64 * 64;      // 83 584
-constexpr int LI_ALL = kStrideA + kStrideB + kStrideC + kStrideD;                   // vertex 4 - vertex 0
 
 // TO = tile extent along the other axis (32; 16: twice the tiles, for launches of few tiles per workgroup)
 template <int TO>
@@ -188,82 +188,7 @@ unsigned long long* g_li_stamps = nullptr;
 #define LI_STAMP_L(k) do {} while (0)
 #endif
 
-typedef __attribute__((address_space(3))) const int8_t li_lds_i8_t;
 typedef float li_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t li_lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-// ds_read_u8_d16_hi: the byte lands in bits 16..23 (v << 16 for free), so key = one v_and_or_b32 and the LUT digit one shift
-__device__ __forceinline__ uint32_t li_pixel_hi(uint32_t addr) {
-    uint32_t r;
-    asm volatile("ds_read_u8_d16_hi %0, %1" : "=v"(r) : "v"(addr));
-    return r;
-}
-__device__ __forceinline__ unsigned li_key(uint32_t r, unsigned stride) {
-    unsigned k;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(k) : "v"(r), "s"(0x000F0000u), "v"(stride));
-    return k;
-}
-__device__ __forceinline__ unsigned li_max3(unsigned a, unsigned b, unsigned c) {
-    unsigned r;
-    asm("v_max3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ unsigned li_med3(unsigned a, unsigned b, unsigned c) {
-    unsigned r;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ unsigned li_min3(unsigned a, unsigned b, unsigned c) {
-    unsigned r;
-    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// acc + d.lo16 * key.hi16 (signed): one Abel term, the LSB read in place from the sorted key's high half
-__device__ __forceinline__ int li_mad_keyhi(int d, unsigned key, int acc) {
-    asm("v_mad_i32_i16 %0, %1, %2, %0 op_sel:[0,1,0,0]" : "+v"(acc) : "v"(d), "v"(key));
-    return acc;
-}
-
-struct LiWalk {
-    uint32_t i0, i1, i2, i3m;        // LDS addresses of vertices 0, 1, 2 and (vertex 3 - LI_ALL); vertex 4 = i0 + LI_ALL
-    unsigned k0, k1, k2, k3;         // sorted keys (LSB << 16 | stride)
-};
-// ra..rd: the four pattern pixels as li_pixel_hi() returned them; lut_a: LDS address of the plane
-__device__ __forceinline__ LiWalk li_walk(uint32_t lut_a, uint32_t ra, uint32_t rb, uint32_t rc, uint32_t rd) {
-    LiWalk W;
-    const unsigned ka = li_key(ra, kStrideA), kb = li_key(rb, kStrideB), kc = li_key(rc, kStrideC), kd = li_key(rd, kStrideD);
-    const unsigned t = __umul24(__umul24(__umul24(ra >> 20, (unsigned)kL) + (rb >> 20), (unsigned)kL) + (rc >> 20), (unsigned)kL) + (rd >> 20);
-    W.i0 = lut_a + t;
-    const unsigned m = li_max3(ka, kb, kc), e = li_med3(ka, kb, kc), n = li_min3(ka, kb, kc);
-    W.k0 = m > kd ? m : kd;
-    W.k1 = li_med3(m, e, kd);
-    W.k2 = li_med3(e, n, kd);
-    W.k3 = n < kd ? n : kd;
-    W.i1 = W.i0 + (W.k0 & 0xFFFFu);
-    W.i2 = W.i1 + (W.k1 & 0xFFFFu);
-    W.i3m = W.i0 - (W.k3 & 0xFFFFu);
-    return W;
-}
-struct LiEntries { int e0, e1, e2, e3, e4; };
-__device__ __forceinline__ LiEntries li_gather(const LiWalk& W) {
-    LiEntries E;
-    E.e0 = (int)((li_lds_i8_t*)W.i0)[0];
-    E.e1 = (int)((li_lds_i8_t*)W.i1)[0];
-    E.e2 = (int)((li_lds_i8_t*)W.i2)[0];
-    E.e3 = (int)((li_lds_i8_t*)W.i3m)[LI_ALL];
-    E.e4 = (int)((li_lds_i8_t*)W.i0)[LI_ALL];
-    return E;
-}
-// sum_n w_n P_n = 16 P_0 + sum_n f_n (P_{n+1} - P_n)   (w_0 = 16 - f_0, w_n = f_{n-1} - f_n, w_4 = f_3)
-__device__ __forceinline__ int li_numerator(const LiWalk& W, const LiEntries& E) {
-    int acc = kQ * E.e0;
-    acc = li_mad_keyhi(E.e1 - E.e0, W.k0, acc);
-    acc = li_mad_keyhi(E.e2 - E.e1, W.k1, acc);
-    acc = li_mad_keyhi(E.e3 - E.e2, W.k2, acc);
-    acc = li_mad_keyhi(E.e4 - E.e3, W.k3, acc);
-    return acc;
-}
 
 // the two values of a lane (adjacent along the axis on which the plane is contiguous) leave as ONE store: 16 bytes of float64
 // per lane, 1 KB per wave-instruction (8-byte stores run at ~7 B/clk/CU, the issue rate of the store path; 16-byte ones twice that)
@@ -450,7 +375,7 @@ struct LiStager {
 #ifdef LERF_LI_STAMPS
         if ((threadIdx.x == 0 || threadIdx.x == LI_NCW * 64) && A.stamps && A.stamp_slot < 32) { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)); A.stamps[(size_t)blockIdx.x * 32 + A.stamp_slot] = t_; }
 #endif
-        const uint32_t pix_a = li_lds_addr(pix);
+        const uint32_t pix_a = lds_addr(pix);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             pf[i].landed();
@@ -591,7 +516,7 @@ lut_interp_lds_kernel(LiArgs A_) {
         __syncthreads();
     }
     LI_STAMP(2);
-    const uint32_t lut_a = li_lds_addr(li_smem);
+    const uint32_t lut_a = lds_addr(li_smem);
 
     // ---- the walks of one tile: wave-rows of 128 positions = (channel, other-axis index), two per lane; LI_NR rows interleaved
     const int lstride = A.lane_is_y ? A.pitch : A.xs, ostride = A.lane_is_y ? A.xs : A.pitch;
@@ -606,19 +531,19 @@ lut_interp_lds_kernel(LiArgs A_) {
         const bool ok0 = lpos < nl, ok1 = lpos + 1 < nl;
         // lower address of the pair: position lpos when the plane runs forwards, lpos + 1 when backwards
         const int lane_out = (int)((int64_t)(rev && ok1 ? lpos + 1 : lpos) * A.ol);
-        const uint32_t pa0 = li_lds_addr(pix) + (uint32_t)(2 * lane * lstride), pa1 = pa0 + (uint32_t)lstride;
+        const uint32_t pa0 = lds_addr(pix) + (uint32_t)(2 * lane * lstride), pa1 = pa0 + (uint32_t)lstride;
         const int ovalid = min(TO, no - o0);                               // rows of the tile inside the frame
         auto one_row = [&](int c, int o) {
             const uint32_t s0 = (uint32_t)(c * A.cs + o * ostride);
             uint32_t p[2][4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { p[0][k] = li_pixel_hi(pa0 + (s0 + A.koff[k])); p[1][k] = li_pixel_hi(pa1 + (s0 + A.koff[k])); }
+            for (int k = 0; k < 4; ++k) { p[0][k] = lds_pixel_hi(pa0 + (s0 + A.koff[k])); p[1][k] = lds_pixel_hi(pa1 + (s0 + A.koff[k])); }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p[0][0]), "+v"(p[0][1]), "+v"(p[0][2]), "+v"(p[0][3]), "+v"(p[1][0]), "+v"(p[1][1]), "+v"(p[1][2]), "+v"(p[1][3]));
-            const LiWalk W0 = li_walk(lut_a, p[0][0], p[0][1], p[0][2], p[0][3]);
-            const LiEntries E0 = li_gather(W0);
-            const LiWalk W1 = li_walk(lut_a, p[1][0], p[1][1], p[1][2], p[1][3]);
-            const LiEntries E1 = li_gather(W1);
-            const int n0 = li_numerator(W0, E0), n1 = li_numerator(W1, E1);
+            const Walk<1> W0 = simplex_walk_px(lut_a, p[0][0], p[0][1], p[0][2], p[0][3]);
+            const ByteCorners E0 = byte_gather(W0);
+            const Walk<1> W1 = simplex_walk_px(lut_a, p[1][0], p[1][1], p[1][2], p[1][3]);
+            const ByteCorners E1 = byte_gather(W1);
+            const int n0 = byte_abel(W0, E0, kQ * E0.e0), n1 = byte_abel(W1, E1, kQ * E1.e0);
 #ifdef LERF_LI_NO_STORE
             if (n0 == 0x7FFFFFF && ok0)
 #else
@@ -654,15 +579,15 @@ lut_interp_lds_kernel(LiArgs A_) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const uint32_t sk = s0 + (uint32_t)A.koff[k];      // scalar
-                        px[j][0][k] = li_pixel_hi(pa0 + sk);
-                        px[j][1][k] = li_pixel_hi(pa1 + sk);
+                        px[j][0][k] = lds_pixel_hi(pa0 + sk);
+                        px[j][1][k] = lds_pixel_hi(pa1 + sk);
                     }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)"
                              : "+v"(px[0][0][0]), "+v"(px[0][0][1]), "+v"(px[0][0][2]), "+v"(px[0][0][3]), "+v"(px[0][1][0]), "+v"(px[0][1][1]), "+v"(px[0][1][2]), "+v"(px[0][1][3]),
                                "+v"(px[1][0][0]), "+v"(px[1][0][1]), "+v"(px[1][0][2]), "+v"(px[1][0][3]), "+v"(px[1][1][0]), "+v"(px[1][1][1]), "+v"(px[1][1][2]), "+v"(px[1][1][3]));
-                LiWalk W[LI_NR][2];
-                LiEntries E[LI_NR][2];
+                Walk<1> W[LI_NR][2];
+                ByteCorners E[LI_NR][2];
 #pragma unroll
                 for (int j = 0; j < LI_NR; ++j)
 #pragma unroll
@@ -671,14 +596,14 @@ lut_interp_lds_kernel(LiArgs A_) {
                         W[j][q].k0 = px[j][q][0]; W[j][q].k1 = px[j][q][1]; W[j][q].k2 = px[j][q][2]; W[j][q].k3 = px[j][q][3];
                         E[j][q].e0 = px[j][q][0]; E[j][q].e1 = px[j][q][1]; E[j][q].e2 = px[j][q][2]; E[j][q].e3 = px[j][q][3]; E[j][q].e4 = px[j][q][0];
 #else
-                        W[j][q] = li_walk(lut_a, px[j][q][0], px[j][q][1], px[j][q][2], px[j][q][3]);
-                        E[j][q] = li_gather(W[j][q]);
+                        W[j][q] = simplex_walk_px(lut_a, px[j][q][0], px[j][q][1], px[j][q][2], px[j][q][3]);
+                        E[j][q] = byte_gather(W[j][q]);
                         __builtin_amdgcn_sched_barrier(0);                  // this walk's gathers fly under the next walk
 #endif
                     }
 #pragma unroll
                 for (int j = 0; j < LI_NR; ++j) {
-                    const int n0 = li_numerator(W[j][0], E[j][0]), n1 = li_numerator(W[j][1], E[j][1]);
+                    const int n0 = byte_abel(W[j][0], E[j][0], kQ * E[j][0].e0), n1 = byte_abel(W[j][1], E[j][1], kQ * E[j][1].e0);
 #ifdef LERF_LI_NO_STORE                                                     // ablation builds (tools/build_li_variant.sh): never the product
                     if (n0 == 0x7FFFFFF && ok0)
 #else

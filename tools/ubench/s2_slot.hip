@@ -3,7 +3,12 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I lerf-pytorch_amd/csrc tools/ubench/s2_slot.hip -o /tmp/s2_slot
 // Variants: V=0 the slot as in the kernel (round test + padding test); V=1 no tests; V=2 no LDS at all (loads replaced
 // by register moves); V=3 two slots interleaved by hand (loads of both, walks of both, gathers of both, MACs of both).
-#include "../../lerf-pytorch_amd/csrc/lerf_fused.hip"
+// The walk (lds_pixel_hi, key_of, Walk, simplex_walk) is the kernels' own, from lerf_simplex_lds.h; an RGB instance of the
+// fused header supplies the tile offsets (Off3, tile_offsets) and the piece size (PIECE_LDS) -- the header alone, not
+// lerf_fused.hip, whose launch dispatch needs the other instances to link.
+#define LERF_FUSED_NS fused
+#define LERF_FUSED_CH 3
+#include "../../lerf-pytorch_amd/csrc/lerf_fused_impl.h"
 #include <cstdio>
 #include <vector>
 
