@@ -145,6 +145,25 @@ struct Dims {
     static_assert(NT != 1024 || (MAXR <= 14 && (NH + NT - 1) / NT <= 15), "slot rounds / positions per thread the register budget was sized for");
 };
 
+// The int slots of the control block (Dims::OFF_CTL) that stage 3 uses: each is written by one wave and read by all of them
+// behind a barrier.  A kernel runs one kind, so the two kinds' answers about the rows share a slot.
+enum Ctl : int {
+    CTL_I0 = 16,            // first owned output row (CTL_I0 + w = the result of search wave w: i0, i1, j0, j1)
+    CTL_I1 = 17,            // one past the last owned output row
+    CTL_J0 = 18,            // first owned output column
+    CTL_J1 = 19,            // one past the last owned output column
+    CTL_NGRP = 21,          // row groups of the tile
+    CTL_GSAME = 22,         // rows per group when every group has as many, else 0
+    CTL_TQ_COUNT = 23,      // tie queue: outputs pushed so far (runs past the capacity when the queue is full)
+    CTL_CCODE = 24,         // LeRF-G: pair code of the columns (pair_census)
+    CTL_NCGRP = 25,         // LeRF-L: column groups
+    CTL_RCODE = 26,         // LeRF-G: pair code of the rows
+    CTL_LIN_ROWS_OK = 26,   // LeRF-L: no row group has more than two rows
+    CTL_LIN_COLS_OK = 27,   // LeRF-L: the column-group table holds every group
+    CTL_CSTEP = 28,         // LeRF-G: column pair h + 1 starts exactly one tap right of pair h (x2)
+    CTL_RSTEP = 29,         // LeRF-G: row pair h + 1 starts exactly one tap below pair h
+};
+
 // Frames of DIFFERENT sizes in one launch (general kernels only): the descriptors travel in the kernel-argument segment, so
 // a workgroup finds its frame with scalar loads.  first_block = index of the frame's first tile in the launch.
 constexpr int RAGGED_MAX = 16;
@@ -1376,6 +1395,745 @@ __device__ __forceinline__ void emit_tile(const uint32_t* Dt, uint32_t* eo, int 
     }
 }
 
+// ---------------------------------------------------------------------------
+// Stage 3 of the SR kernels, in the order a workgroup runs it: geometry search and staging, row groups and census, ONE task
+// form, the tie pass (and the flush of the block forms).  Consecutive output rows that start at the same source row (2 rows
+// at x2, 3 at x3 ...) form a row group and share their taps.  What the pieces share is one Stage3, built once.
+// ---------------------------------------------------------------------------
+// t / n for the task decodings (t * n < 2^32)
+struct MagicDiv {
+    unsigned n, magic;
+    __device__ __forceinline__ explicit MagicDiv(int n_)
+        : n((unsigned)n_), magic((unsigned)((0x100000000ull + (unsigned)n_ - 1) / (unsigned)(n_ > 0 ? n_ : 1))) {}
+    __device__ __forceinline__ int div(int t) const { return n == 1 ? t : (int)__umulhi((unsigned)t, magic); }   // (ceil(2^32 / 1) does not fit the 32-bit magic)
+};
+
+// the tile's geometry tables in LDS: first tap (hyper-region coordinates) and the S distances of every owned output row /
+// column, and the first row of every row group
+template <typename D, int S>
+struct GeoTables {
+    int* lr; float* dr; int* lc; float* dc; int* grp;
+    __device__ __forceinline__ explicit GeoTables(uint8_t* smem)
+        : lr(reinterpret_cast<int*>(smem + D::OFF_GEO)), dr(reinterpret_cast<float*>(lr + D::GEO_ROWS)), lc(reinterpret_cast<int*>(dr + D::GEO_ROWS * S)),
+          dc(reinterpret_cast<float*>(lc + D::GEO_COLS)), grp(reinterpret_cast<int*>(dc + D::GEO_COLS * S)) {}
+};
+
+// ---- owned output rows / columns: four wave-parallel searches in the global tables -> ctl[CTL_I0 .. CTL_J1]
+template <typename D>
+__device__ __forceinline__ void stage3_geo_search(const FrameView& F, int tyi, int txi, int ty0, int tx0, int* ctl, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    if (wave < 4) {
+        const bool rows = wave < 2;
+        const int* tab = rows ? F.left_r : F.left_c;
+        const int n = rows ? F.oH : F.oW;
+        const int ti = rows ? tyi : txi, tn = rows ? F.tiles_y : F.tiles_x, t0 = rows ? ty0 : tx0;
+        int r;
+        if (!(wave & 1)) r = ti == 0 ? 0 : wave_lower_bound(tab, n, t0 - D::R3, lane);
+        else r = ti == tn - 1 ? n : wave_lower_bound(tab, n, t0 + (rows ? TH : TW) - D::R3, lane);
+        if (lane == 0) ctl[CTL_I0 + wave] = r;
+    }
+}
+// ---- tables of the owned block into LDS; LeRF-G distances pre-multiplied by (max_sigma/255)*sqrt(0.5 log2 e)
+template <typename D, int S, int KIND>
+__device__ __forceinline__ void stage3_geo_stage(uint8_t* smem, const FrameView& F, float max_sigma, int hy0, int hx0, const int* ctl,
+                                                 int tid) {
+    const GeoTables<D, S> g(smem);
+    const int gi0 = ctl[CTL_I0], gi1 = ctl[CTL_I1], gj0 = ctl[CTL_J0], gj1 = ctl[CTL_J1];
+    const float gscale = KIND == LERF_KIND_GAUSS ? s3::gauss_scale(max_sigma) : 1.0f;
+    for (int e = tid; e < gi1 - gi0; e += NT) {
+        g.lr[e] = F.left_r[gi0 + e] - hy0;
+#pragma unroll
+        for (int b = 0; b < S; ++b) g.dr[e * S + b] = F.dis_r[(gi0 + e) * S + b] * gscale;
+    }
+    for (int e = tid; e < gj1 - gj0; e += NT) {
+        g.lc[e] = F.left_c[gj0 + e] - hx0;
+#pragma unroll
+        for (int a = 0; a < S; ++a) g.dc[e * S + a] = F.dis_c[(gj0 + e) * S + a] * gscale;
+    }
+}
+
+// what the stage-3 functions share
+template <typename D_, int S_, int KIND_>
+struct Stage3 {
+    using D = D_;
+    static constexpr int S = S_, SS = S_ * S_, KIND = KIND_;
+    static constexpr bool GAUSS = KIND_ == LERF_KIND_GAUSS;
+    static constexpr int GMAX = S_ == 2 ? 5 : 3;                                       // rows per group (larger runs are split)
+    static constexpr bool BLK = GAUSS && (S_ == 2 || S_ == 4) && D::OUT_FITS;          // block tasks (round 4: the 4 x 4 support too)
+    static constexpr bool BLKL = KIND_ == LERF_KIND_LINEAR && S_ == 2 && D::OUT_FITS;  // LeRF-L block tasks
+    static constexpr int QRP = S_ == 4 ? 2 : 1, QCP = S_ == 4 ? 2 : 1;                 // blocks per quad task (see stage3_quads)
+    static constexpr bool QUADS = BLK && QRP * QCP > 1;
+    GeoTables<D, S> g;
+    const uint32_t* Dt;                  // the hyper region's packed dwords
+    uint32_t* tq; int* tq_count;         // tie queue: (il << 16) | xc of the outputs the float32 path could not decide
+    uint8_t* outt;                       // block forms: LDS image of the output block, rows at the phase of their address mod 16
+    int* cgrp;                           // LeRF-L block tasks: first column of every column group
+    const double* dis_r64; const double* dis_c64;      // float64 distance tables (NULL: tie guard off)
+    uint8_t* seg0;                       // first byte of the owned block in the frame
+    int64_t rowpitch;                    // bytes per output row
+    bool rows_align;                     // dword columns line up across the rows of a group
+    int i0, j0, nrow, ncol;              // the owned block
+    int ncolc, ndw, ophase;              // bytes and dword columns per row, seg0 mod 16
+    MagicDiv by_ndw;                     // dword-column tasks: task -> row group (computed once: every variant of them divides by it)
+    // the census (read_census, behind the barrier that follows stage3_census)
+    int ngrp, gsame, rcode, ccode;
+    bool lin_ok;
+
+    __device__ __forceinline__ Stage3(uint8_t* smem, const Params& P, const FrameView& F, uint8_t* outp, int* ctl) : g(smem), by_ndw(1) {
+        Dt = reinterpret_cast<const uint32_t*>(smem + D::OFF_D);
+        tq = reinterpret_cast<uint32_t*>(smem + D::OFF_TQ);
+        tq_count = ctl + CTL_TQ_COUNT;                       // zeroed by stage3_census, with the group table
+        outt = smem + D::OFF_OUT;
+        cgrp = reinterpret_cast<int*>(smem + D::OFF_CGRP);
+        dis_r64 = F.dis_r64; dis_c64 = F.dis_c64;
+        i0 = ctl[CTL_I0]; j0 = ctl[CTL_J0];
+        nrow = ctl[CTL_I1] - i0; ncol = ctl[CTL_J1] - j0;
+        ncolc = ncol * CH;
+        // bytes per output row: dense, or the caller's pitch (a rank's block of 1919 / 1921 output columns lives in rows padded to a
+        // 16-byte multiple so that its tiles keep the dword-column / block tasks -- dense, every row was a group of its own)
+        rowpitch = P.out_pitch > 0 ? (int64_t)P.out_pitch : (int64_t)F.oW * CH;      // (ragged launches: always dense)
+        seg0 = outp + (int64_t)i0 * rowpitch + (int64_t)j0 * CH;
+        rows_align = (rowpitch & 3) == 0;
+        // dword columns per row: when every row of the block starts on a 4-byte boundary the block needs no slack column, and
+        // a 384-byte tile row is exactly 96 dwords = whole 128-byte lines per wave store
+        const bool seg_aligned = rows_align && (reinterpret_cast<uintptr_t>(seg0) & 3u) == 0;
+        ndw = seg_aligned ? (ncolc + 3) >> 2 : (ncolc + 6) >> 2;
+        ophase = (int)(reinterpret_cast<uintptr_t>(seg0) & 15u);
+    }
+    __device__ __forceinline__ void read_census(const int* ctl) {
+        ngrp = ctl[CTL_NGRP];
+        gsame = __builtin_amdgcn_readfirstlane(ctl[CTL_GSAME]);
+        rcode = __builtin_amdgcn_readfirstlane(ctl[CTL_RCODE]); ccode = __builtin_amdgcn_readfirstlane(ctl[CTL_CCODE]);
+        if constexpr (BLKL) lin_ok = ctl[CTL_LIN_ROWS_OK] != 0 && ctl[CTL_LIN_COLS_OK] != 0;   // (LeRF-G: slot 26 is rcode, 27 unwritten)
+        else lin_ok = false;
+        by_ndw = MagicDiv(ndw);
+    }
+};
+
+// Do the entries of a first-tap table pair up as (2h, 2h + 1) -- code 1 -- or, behind a leading single (the frame's top /
+// left edge), as (2h - 1, 2h) -- code 2?  A trailing single is fine either way.  step: pair h + 1 starts exactly one tap
+// behind pair h (x2).  One wave; lane 0 writes the answers.
+__device__ __forceinline__ void pair_census(const int* t, int n, int lane, int* code, int* step) {
+    bool ok0 = true, ok1 = true, step1 = true;
+    for (int base = 0; base < n; base += 64) {
+        const int k = base + lane;
+        if (k + 1 < n && t[k + 1] != t[k]) { if (k & 1) ok1 = false; else ok0 = false; }
+        if (!(k & 1) && k + 2 < n && t[k + 2] != t[k] + 1) step1 = false;
+    }
+    const bool p0 = __ballot(!ok0) == 0ull, p1 = __ballot(!ok1) == 0ull, q1 = __ballot(!step1) == 0ull;
+    if (lane == 0) { *code = p0 ? 1 : (p1 ? 2 : 0); *step = q1 ? 1 : 0; }
+}
+
+// ---- the row-group table (wave 0) and what the block forms ask about the tile's rows and columns (waves 1, 2)
+template <typename X_>
+__device__ __forceinline__ void stage3_census(const X_& X, int* ctl, int tid) {
+    constexpr int KIND = X_::KIND, GMAX = X_::GMAX;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int nrow = X.nrow, ncol = X.ncol;
+    const int* g_lr = X.g.lr;
+    const int* g_lc = X.g.lc;
+    int* g_grp = X.g.grp;
+    if (wave == 0) {
+        int ng = 0;
+        for (int base = 0; base < nrow; base += 64) {
+            const int il = base + lane;
+            bool start = false;
+            if (il < nrow)
+                start = il == 0 || !X.rows_align || g_lr[il] != g_lr[il - 1] || (il >= GMAX && g_lr[il - GMAX] == g_lr[il]);
+            const unsigned long long m = __ballot(start);
+            if (start) g_grp[ng + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = il;
+            ng += __popcll(m);
+        }
+        if (lane == 0) g_grp[ng] = nrow;
+        // every group of the tile the same size (integer scale factors, away from the frame's top and bottom): the
+        // task loop then runs with that size as a compile-time constant, without a row test per tap set
+        const int g0 = ng > 0 ? g_grp[1] - g_grp[0] : 0;
+        bool same = true, small = true;                      // small: no group of more than two rows (block tasks of LeRF-L)
+        for (int base = 0; base < ng; base += 64) {
+            const int idx = base + lane;
+            if (idx < ng && g_grp[idx + 1] - g_grp[idx] != g0) same = false;
+            if (X_::BLKL && idx < ng && g_grp[idx + 1] - g_grp[idx] > 2) small = false;
+        }
+        const bool uniform = __ballot(!same) == 0ull;
+        if (lane == 0) {
+            ctl[CTL_NGRP] = ng;
+            ctl[CTL_GSAME] = uniform ? g0 : 0;
+            ctl[CTL_TQ_COUNT] = 0;
+        }
+        if constexpr (X_::BLKL) {
+            const bool ok = __ballot(!small) == 0ull;
+            if (lane == 0) ctl[CTL_LIN_ROWS_OK] = ok ? 1 : 0;
+        }
+    } else if (wave == 1 && X_::BLKL) {
+        // LeRF-L block tasks: the columns in groups of at most two that share their taps (runs of equal left taps, every
+        // second column of a run starts a group); the table lies behind the output image, over the dead stage-2 areas
+        int* g_cgrp = X.cgrp;
+        constexpr int NCMAX = 2 * TW + 14;
+        int nc = 0;
+        for (int base = 0; base < ncol; base += 64) {
+            const int jl = base + lane;
+            bool start = false;
+            if (jl < ncol) {
+                int back = 0;                                // columns of the same run to the left
+                while (back < 16 && jl - back - 1 >= 0 && g_lc[jl - back - 1] == g_lc[jl]) ++back;
+                start = (back & 1) == 0;
+            }
+            const unsigned long long m = __ballot(start);
+            if (start) {
+                const int idx = nc + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                if (idx < NCMAX) g_cgrp[idx] = jl;
+            }
+            nc += __popcll(m);
+        }
+        if (lane == 0) {
+            if (nc <= NCMAX) g_cgrp[nc] = ncol;
+            ctl[CTL_NCGRP] = nc;
+            ctl[CTL_LIN_COLS_OK] = (nc <= NCMAX) ? 1 : 0;
+        }
+    } else if (wave == 1) {
+        pair_census(g_lc, ncol, lane, &ctl[CTL_CCODE], &ctl[CTL_CSTEP]);
+    } else if (wave == 2 && KIND == LERF_KIND_GAUSS) {
+        pair_census(g_lr, nrow, lane, &ctl[CTL_RCODE], &ctl[CTL_RSTEP]);
+    }
+}
+
+// ---- output (il, xc) of the owned block (row, byte column) re-evaluated in float64 exactly as the reference does
+//      (lerf_stage3.h, tie guard): its taps from the packed dwords, its distances from the frame's float64 tables
+template <typename X_>
+__device__ __forceinline__ uint8_t resolve_output(const X_& X, float max_sigma, int il, int xc) {
+    using D = typename X_::D;
+    constexpr int S = X_::S;
+    const int jl = xc / CH;
+    const int c = xc - jl * CH;
+    const uint32_t* dp = X.Dt + X.g.lr[il] * D::HP + X.g.lc[jl] * CH + c;
+    return s3::resolve_taps_u8<X_::GAUSS, S>([&](int a, int b) __attribute__((always_inline)) { return dp[b * D::HP + a * CH]; },
+                                            X.dis_r64 + (int64_t)(X.i0 + il) * S, X.dis_c64 + (int64_t)(X.j0 + jl) * S, max_sigma);
+}
+// bit q of the result: output q of a task lies within kTieEps of a rounding tie
+template <int N>
+__device__ __forceinline__ unsigned tie_mask(const float (&dist)[N]) {
+    unsigned m = 0;
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        if (__builtin_fabsf(dist[q]) > 0.5f - s3::kTieEps) m |= 1u << q;
+    return m;
+}
+// The undecided outputs of one task (bits of `mask`; decode(q, il, xc) names output q) are queued for the pass behind the
+// task loop; only a full queue is worked off on the spot, the byte handed to patch(q, byte).  Rare: one round per queued
+// output of the lane, not per output.
+template <typename X_, typename Decode, typename Patch>
+__device__ __forceinline__ void queue_ties(const X_& X, const Params& P, unsigned mask, Decode decode, Patch patch) {
+    while (mask != 0) {
+        const int q = __builtin_ctz(mask);
+        mask &= mask - 1;
+        int il, xc;
+        decode(q, il, xc);
+        const int slot = atomicAdd(X.tq_count, 1);
+        if (slot < P.tq_cap) {
+            X.tq[slot] = ((uint32_t)il << 16) | (uint32_t)xc;
+            continue;
+        }
+        patch(q, resolve_output(X, P.max_sigma, il, xc));
+    }
+}
+// the tail of an output of the block forms: xf -> its byte in the LDS image (when the block has this output), its distance
+// from the rounded value (0 when it has not) and the running maximum of |distance|
+__device__ __forceinline__ void put_block_byte(float xf, bool have, uint8_t* dst, float& dist, float& dmax) {
+    const float rr = __builtin_rintf(xf);
+    dist = have ? xf - rr : 0.0f;
+    dmax = __builtin_fmaxf(dmax, __builtin_fabsf(dist));
+    if (have) *dst = (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(rr, 0u, 0u);
+}
+
+// ---- dword-column tasks: one task = (row group, one 4-byte-aligned output dword column); the tap loads, the u8 -> f32
+//      conversions and the column-only terms are done once per group, the rows pay one multiply and two FMAs per tap.
+//      Same code for the 2x2 and the 4x4 support.  GS = rows per group, 0 = read it per group.
+template <int GS, typename X_>
+__device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int tid) {
+    using D = typename X_::D;
+    constexpr int S = X_::S, SS = X_::SS, KIND = X_::KIND;
+    constexpr int GN = GS > 0 ? GS : X_::GMAX;
+    const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc; const int* g_grp = X.g.grp;
+    const uint32_t* Dt = X.Dt;
+    const int ndw = X.ndw, ncolc = X.ncolc;
+    const int64_t rowpitch = X.rowpitch;
+    const float ms255 = P.max_sigma * (1.0f / 255.0f);
+    const int ntask = X.ngrp * ndw;
+    for (int t = tid; t < ntask; t += NT) {
+        const int g = X.by_ndw.div(t);
+        const int dw = t - g * ndw;
+        const int il0 = g_grp[g];
+        const int gs = GS > 0 ? GS : g_grp[g + 1] - il0;
+        uint8_t* seg = X.seg0 + il0 * rowpitch;
+        const int a0 = (int)(reinterpret_cast<uintptr_t>(seg) & 3u);
+        const int b0 = dw * 4 - a0;
+        const int lr = g_lr[il0];
+        uint32_t packed[GN];
+        // tie detection: the 2x2 kernels keep every output's distance from its rounded value and a running maximum
+        // (one v_max per output, the ties are looked for only when the maximum says there is one); the 4x4 kernel has
+        // no registers for that and sets a bit per output
+        constexpr bool DIST = S == 2;
+        float dist[DIST ? GN * 4 : 1];                        // [r*4+u]
+        float dmax = 0.0f;
+        unsigned tiebits = 0;                                 // bit r*4+u
+#pragma unroll
+        for (int r = 0; r < GN; ++r) packed[r] = 0;
+        s3::f2 DXP[S];                                        // packed 4x4 path: (row 0, row 1) distances of row tap b
+        if constexpr (KIND == LERF_KIND_GAUSS && S == 4 && GS == 2) {
+#pragma unroll
+            for (int b = 0; b < S; ++b) { DXP[b].x = g_dr[il0 * S + b]; DXP[b].y = g_dr[(il0 + 1) * S + b]; }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int xc = min(max(b0 + u, 0), ncolc - 1);    // clamped; invalid bytes are not stored
+            const int jl = xc / CH;
+            const int c = xc - jl * CH;
+            const int lc = g_lc[jl];
+            if constexpr (KIND == LERF_KIND_GAUSS && S == 4 && GS == 2) {
+                // The 4x4 support, two rows per group, in PACKED float32 over the two rows (lane x = row 0, lane y = row 1):
+                // per tap and row PAIR one v_pk_mul (tx), two v_pk_fma (the form), one v_pk_add and one v_pk_fma (the sums)
+                // instead of ten scalar operations; a tap's four scalars sit two to a register pair -- (p0, ty^2) and
+                // (k1, value) -- and are read through op_sel.  Same operations in the same order: the same bytes.
+                s3::f2 PT[SS], KV[SS];
+#pragma unroll
+                for (int a = 0; a < S; ++a) {
+                    const float dy = g_dc[jl * S + a];
+#pragma unroll
+                    for (int b = 0; b < S; ++b) {
+                        const uint32_t d = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
+                        const float tyv = s3::gauss_t_u8((float)((d >> 16) & 0xFFu), dy);
+                        PT[a * S + b].x = s3::gauss_m2rho_u8((float)(d & 0xFFu)) * tyv;
+                        PT[a * S + b].y = tyv * tyv;
+                        KV[a * S + b].x = (float)((d >> 8) & 0xFFu);
+                        KV[a * S + b].y = (float)(d >> 24);
+                    }
+                }
+                s3::f2 NUM, DEN;
+#pragma unroll
+                for (int a = 0; a < S; ++a)
+#pragma unroll
+                    for (int b = 0; b < S; ++b) {
+                        const int k = a * S + b;
+                        const s3::f2 TX = s3::pk_mul_blo(DXP[b], KV[k]);                       // k1 * dx[r][b]
+                        const s3::f2 E = s3::pk_fma_pb<false>(TX, PT[k], s3::pk_fma_ppb<true>(TX, PT[k]));   // fma(tx, p0, fma(tx, tx, ty2))
+                        s3::f2 W;
+                        W.x = __builtin_amdgcn_exp2f(-E.x);
+                        W.y = __builtin_amdgcn_exp2f(-E.y);
+                        if (k == 0) {
+                            DEN = W;
+                            NUM = s3::pk_mul_bhi_after_trans(W, KV[k]);
+                        } else {
+                            DEN = DEN + W;                                                  // (compiler-generated: see s3::BlockTap)
+                            NUM = s3::pk_fma_bhi_after_trans(W, KV[k], NUM);
+                        }
+                    }
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const float xf = s3::finish_div(r ? NUM.y : NUM.x, r ? DEN.y : DEN.x);
+                    bool tie;
+                    packed[r] = s3::pack_u8_tie(xf, u, packed[r], &tie);
+                    if (tie) tiebits |= 1u << (r * 4 + u);
+                }
+                continue;
+            }
+            // shared by the rows of the group: per tap (a = column offset major, numpy meshgrid 'xy' :95-98; b = row offset)
+            float p0[SS], k1[SS], ty[SS], v[SS];
+#pragma unroll
+            for (int a = 0; a < S; ++a) {
+                const float dy = g_dc[jl * S + a];
+#pragma unroll
+                for (int b = 0; b < S; ++b) {
+                    const uint32_t d = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
+                    v[a * S + b] = (float)(d >> 24);
+                    const float k0 = (float)(d & 0xFFu);
+                    if (KIND == LERF_KIND_GAUSS) {
+                        // column-only terms of the quadratic form: p0 <- (-2 rho) ty, ty <- ty^2 (gauss_form_cols)
+                        const float tyv = s3::gauss_t_u8((float)((d >> 16) & 0xFFu), dy);
+                        p0[a * S + b] = s3::gauss_m2rho_u8(k0) * tyv;
+                        k1[a * S + b] = (float)((d >> 8) & 0xFFu);
+                        ty[a * S + b] = tyv * tyv;
+                    } else {
+                        const float alpha = s3::lin_alpha_u8(k0, ms255);
+                        p0[a * S + b] = alpha;
+                        ty[a * S + b] = s3::lin_factor(alpha, dy, s3::dist_class_f(dy));
+                        k1[a * S + b] = 0.0f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < GN; ++r) {
+                if (r < gs) {
+                    float e[SS];
+#pragma unroll
+                    for (int a = 0; a < S; ++a)
+#pragma unroll
+                        for (int b = 0; b < S; ++b) {
+                            const float dx = g_dr[(il0 + r) * S + b];
+                            if (KIND == LERF_KIND_GAUSS)
+                                e[a * S + b] = s3::gauss_form_cols(s3::gauss_t_u8(k1[a * S + b], dx), ty[a * S + b], p0[a * S + b]);
+                            else
+                                e[a * S + b] = s3::lin_factor(p0[a * S + b], dx, s3::dist_class_f(dx)) * ty[a * S + b];
+                        }
+                    const float xf = s3::finish<KIND == LERF_KIND_GAUSS, SS, true, true, true>(e, v);
+                    if (DIST) {
+                        packed[r] = s3::pack_u8_dist(xf, u, packed[r], &dist[DIST ? r * 4 + u : 0]);
+                        dmax = __builtin_fmaxf(dmax, __builtin_fabsf(dist[DIST ? r * 4 + u : 0]));
+                    } else {
+                        bool tie;
+                        packed[r] = s3::pack_u8_tie(xf, u, packed[r], &tie);
+                        if (tie) tiebits |= 1u << (r * 4 + u);
+                    }
+                }
+            }
+        }
+        if ((DIST ? dmax > 0.5f - s3::kTieEps : tiebits != 0) && X.dis_r64 != nullptr) {
+            unsigned tiemask = tiebits;
+            if (DIST) {
+#pragma unroll
+                for (int q = 0; q < GN * 4; ++q)
+                    if ((GS > 0 || (q >> 2) < gs) && __builtin_fabsf(dist[DIST ? q : 0]) > 0.5f - s3::kTieEps) tiemask |= 1u << q;
+            }
+            queue_ties(X, P, tiemask,
+                       [&](int q, int& il, int& xc) __attribute__((always_inline)) { il = il0 + (q >> 2); xc = min(max(b0 + (q & 3), 0), ncolc - 1); },
+                       [&](int q, uint32_t r8) __attribute__((always_inline)) {
+                           const int r = q >> 2, u = q & 3;
+#pragma unroll
+                           for (int rr = 0; rr < GN; ++rr)       // (a select per row: `packed` is indexed by constants only and stays in registers)
+                               packed[rr] = rr == r ? (packed[rr] & ~(0xFFu << (8 * u))) | (r8 << (8 * u)) : packed[rr];
+                       });
+        }
+#pragma unroll
+        for (int r = 0; r < GN; ++r) {
+            if (r < gs) {
+                uint8_t* sr = seg + r * rowpitch;
+                if (b0 >= 0 && b0 + 3 < ncolc) {
+                    // streaming store: the output is never re-read here, keep the LUT pack resident in L2 instead
+                    __builtin_nontemporal_store(packed[r], reinterpret_cast<uint32_t*>(sr + b0));
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (b0 + u >= 0 && b0 + u < ncolc) sr[b0 + u] = (uint8_t)(packed[r] >> (8 * u));
+                }
+            }
+        }
+    }
+}
+
+// ---- block tasks: tiles whose output rows AND columns come in pairs that share their taps (integer x2, away from
+//      the frame's top and left).  One task = the 2 x 2 outputs of a (row pair, column pair), all CH channels: the
+//      four tap dwords of a channel are loaded and converted once for four outputs instead of once for two, the
+//      column-only terms serve both rows and the row-only products both columns (43 instead of 63 VALU instructions
+//      per output), and a tile is exactly 4 tasks per thread.  The bytes are assembled in an LDS image of the tile's
+//      output block (ties are patched there) and leave as whole 16-byte chunks.  Same arithmetic, operation for
+//      operation, as stage3_tasks: the outputs are bit-identical.  UNI: pairs from row 0 / column 0 on, even counts.
+template <bool UNI, typename X_>
+__device__ __forceinline__ void stage3_blocks(const X_& X, const Params& P, int tid) {
+    if constexpr (X_::BLK) {
+        using D = typename X_::D;
+        constexpr int S = X_::S;
+        const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc;
+        const int nrow = X.nrow, ncol = X.ncol, ophase = X.ophase;
+        const int rofs = UNI ? 0 : X.rcode - 1, cofs = UNI ? 0 : X.ccode - 1;
+        const int ncg = (ncol + cofs + 1) >> 1;
+        const int nblk = ((nrow + rofs + 1) >> 1) * ncg;
+        const MagicDiv by_ncg(ncg);
+        for (int t = tid; t < nblk; t += NT) {
+            const int g = by_ncg.div(t);
+            const int h = t - g * ncg;
+            const int il0 = 2 * g - rofs, jl0 = 2 * h - cofs;
+            const int lr = g_lr[UNI ? il0 : max(il0, 0)], lc = g_lc[UNI ? jl0 : max(jl0, 0)];
+            // distances as PAIRS: DX[b] = (row 0, row 1) of row tap b, DY[a] = (column 0, column 1) of column tap a
+            s3::f2 DX[S], DY[S];
+#pragma unroll
+            for (int b = 0; b < S; ++b) { DX[b].x = g_dr[il0 * S + b]; DX[b].y = g_dr[il0 * S + S + b]; }
+#pragma unroll
+            for (int a = 0; a < S; ++a) { DY[a].x = g_dc[jl0 * S + a]; DY[a].y = g_dc[jl0 * S + S + a]; }
+            const uint32_t* dp = X.Dt + lr * D::HP + lc * CH;
+            uint8_t* ob = X.outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
+            float dist[4 * CH];                                  // [c][r][q]
+            float dmax = 0.0f;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                s3::f2 NUM[2], DEN[2];                           // [row r], lanes = the two columns
+#pragma unroll
+                for (int a = 0; a < S; ++a)
+#pragma unroll
+                    for (int b = 0; b < S; ++b) {
+                        const s3::BlockTap T(dp[b * D::HP + a * CH + c]);
+                        s3::f2 P0, TY2;
+                        T.cols(DY[a], P0, TY2);
+                        T.sum(T.rows(DX[b]), P0, TY2, a == 0 && b == 0, NUM, DEN);
+                    }
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        const float den = q ? DEN[r].y : DEN[r].x, num = q ? NUM[r].y : NUM[r].x;
+                        const bool have = UNI || ((unsigned)(il0 + r) < (unsigned)nrow && (unsigned)(jl0 + q) < (unsigned)ncol);
+                        put_block_byte(s3::finish_div(num, den), have, ob + r * D::OUT_PITCH + q * CH + c, dist[(c * 2 + r) * 2 + q], dmax);
+                    }
+            }
+            if (dmax > 0.5f - s3::kTieEps && X.dis_r64 != nullptr)
+                queue_ties(X, P, tie_mask(dist),
+                           [&](int q, int& il, int& xc) __attribute__((always_inline)) { il = il0 + ((q >> 1) & 1); xc = (jl0 + (q & 1)) * CH + (q >> 2); },
+                           [&](int q, uint32_t r8) __attribute__((always_inline)) { ob[((q >> 1) & 1) * D::OUT_PITCH + (q & 1) * CH + (q >> 2)] = (uint8_t)r8; });
+        }
+    }
+}
+
+// ---- quad tasks (round 5): RP x CP neighbouring blocks of an INTERIOR x2 tile in one task.  Pair h + 1 starts exactly one
+//      tap right of / below pair h (CTL_CSTEP, CTL_RSTEP), so the (S + RP - 1) x (S + CP - 1) taps of the task serve up to
+//      RP x CP blocks each: a tap's load and u8 -> f32 conversions once per task instead of once per block (S = 4,
+//      2 x 2 blocks: 25 instead of 64), its column-only terms once per column pair (40 instead of 64), its row
+//      products once per row pair.  Every output still sums ITS S x S taps in the order (a outer, b inner) with the
+//      operations of stage3_blocks: identical bytes.  One task per thread on a 64 x 64 tile with 2 x 2 blocks.
+//      Measured (A/B on one box, profiles/r05_experiments.txt): S = 4: 2 x 2 blocks +1.7 % (23.58 -> 23.99 Gpix/s; 2 x 1: +1.6 %,
+//      1 x 2: +1.2 %) -- the four v_exp_f32 per (tap, block) and their packed consumers are not shared, they are 3/4 of a
+//      tap's issue time; S = 2: 2 x 2 blocks -1.4 % (one 48-output task per thread hides less latency than four of 12), 2 x 1
+//      and 1 x 2 +-0: the 2 x 2 support keeps its single blocks (Stage3::QRP, QCP).
+template <typename X_>
+__device__ __forceinline__ void stage3_quads(const X_& X, const Params& P, int tid) {
+    if constexpr (X_::QUADS) {
+        using D = typename X_::D;
+        constexpr int S = X_::S, RP = X_::QRP, CP = X_::QCP, TR = S + RP - 1, TC = S + CP - 1;
+        const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc;
+        const int ophase = X.ophase;
+        const int ncq = (X.ncol >> 1) / CP;
+        const int ntq = ((X.nrow >> 1) / RP) * ncq;
+        const MagicDiv by_ncq(ncq);
+        for (int t = tid; t < ntq; t += NT) {
+            const int g = by_ncq.div(t);
+            const int h = t - g * ncq;
+            const int il0 = 2 * RP * g, jl0 = 2 * CP * h;
+            const int lr = g_lr[il0], lc = g_lc[jl0];
+            s3::f2 DX[RP][S], DY[CP][S];               // [pair][tap]: lanes = the two rows / the two columns of the pair
+#pragma unroll
+            for (int rp = 0; rp < RP; ++rp)
+#pragma unroll
+                for (int b = 0; b < S; ++b) { DX[rp][b].x = g_dr[(il0 + 2 * rp) * S + b]; DX[rp][b].y = g_dr[(il0 + 2 * rp + 1) * S + b]; }
+#pragma unroll
+            for (int cp = 0; cp < CP; ++cp)
+#pragma unroll
+                for (int a = 0; a < S; ++a) { DY[cp][a].x = g_dc[(jl0 + 2 * cp) * S + a]; DY[cp][a].y = g_dc[(jl0 + 2 * cp + 1) * S + a]; }
+            const uint32_t* dp = X.Dt + lr * D::HP + lc * CH;
+            uint8_t* ob = X.outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
+#pragma unroll 1
+            for (int c = 0; c < CH; ++c) {
+                s3::f2 NUM[RP][CP][2], DEN[RP][CP][2];   // [row pair][column pair][row of the pair], lanes = columns of the pair
+#pragma unroll
+                for (int A = 0; A < TC; ++A) {
+#pragma unroll
+                    for (int B = 0; B < TR; ++B) {
+                        const s3::BlockTap T(dp[B * D::HP + A * CH + c]);
+                        s3::f2 P0[CP], TY2[CP], TX[RP];
+#pragma unroll
+                        for (int cp = 0; cp < CP; ++cp) {
+                            const int a = A - cp;
+                            if (a >= 0 && a < S) T.cols(DY[cp][a < 0 ? 0 : (a >= S ? 0 : a)], P0[cp], TY2[cp]);
+                        }
+#pragma unroll
+                        for (int rp = 0; rp < RP; ++rp) {
+                            const int b = B - rp;
+                            if (b >= 0 && b < S) TX[rp] = T.rows(DX[rp][b < 0 ? 0 : (b >= S ? 0 : b)]);
+                        }
+#pragma unroll
+                        for (int cp = 0; cp < CP; ++cp) {
+                            const int a = A - cp;
+                            if (a < 0 || a >= S) continue;
+#pragma unroll
+                            for (int rp = 0; rp < RP; ++rp) {
+                                const int b = B - rp;
+                                if (b < 0 || b >= S) continue;
+                                T.sum(TX[rp], P0[cp], TY2[cp], a == 0 && b == 0, NUM[rp][cp], DEN[rp][cp]);
+                            }
+                        }
+                    }
+                }
+                float dist[RP * CP * 4];                 // [rp][cp][r][q]
+                float dmax = 0.0f;
+#pragma unroll
+                for (int rp = 0; rp < RP; ++rp)
+#pragma unroll
+                    for (int cp = 0; cp < CP; ++cp)
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int q = 0; q < 2; ++q) {
+                                const float den = q ? DEN[rp][cp][r].y : DEN[rp][cp][r].x, num = q ? NUM[rp][cp][r].y : NUM[rp][cp][r].x;
+                                put_block_byte(s3::finish_div(num, den), true, ob + (2 * rp + r) * D::OUT_PITCH + (2 * cp + q) * CH + c,
+                                               dist[((rp * CP + cp) * 2 + r) * 2 + q], dmax);
+                            }
+                if (dmax > 0.5f - s3::kTieEps && X.dis_r64 != nullptr)
+                    queue_ties(X, P, tie_mask(dist),
+                               [&](int k, int& il, int& xc) __attribute__((always_inline)) {
+                                   const int rp = (k >> 2) / CP, cp = (k >> 2) - rp * CP;
+                                   il = il0 + 2 * rp + ((k >> 1) & 1);
+                                   xc = (jl0 + 2 * cp + (k & 1)) * CH + c;
+                               },
+                               [&](int k, uint32_t r8) __attribute__((always_inline)) {
+                                   const int rp = (k >> 2) / CP, cp = (k >> 2) - rp * CP;
+                                   ob[(2 * rp + ((k >> 1) & 1)) * D::OUT_PITCH + (2 * cp + (k & 1)) * CH + c] = (uint8_t)r8;
+                               });
+            }
+        }
+    }
+}
+
+// ---- LeRF-L block tasks (amplified-linear weights, 2 x 2 support): row groups and column groups of ONE or two
+//      members (x1.5 gives groups of 1, 2, 1, 2 ..., x2 pairs; the frame edges singles), one task = the up to 2 x 2
+//      outputs of a (row group, column group), all channels.  The dword-column tasks ran the general five-row form
+//      here (a group's size is not uniform at x1.5) and evaluated every tap's row factor per output; the block forms
+//      a tap's column factor once per column, its row factor once per row.  Weights as in lerf_stage3.h: the factor of
+//      a distance x is max(1 - alpha |x|, 0) for |x| <= 1 and 0 outside -- alpha * x + 1 (x < 0) and 1 - alpha * x
+//      (x >= 0) are the same float32 operations on |x| -- so the bytes are those of stage3_tasks.
+template <typename X_>
+__device__ __forceinline__ void stage3_blocks_lin(const X_& X, const Params& P, const int* ctl, int tid) {
+    if constexpr (X_::BLKL) {
+        using D = typename X_::D;
+        const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc; const int* g_grp = X.g.grp;
+        const int* g_cgrp = X.cgrp;
+        const int ophase = X.ophase;
+        const float ms255 = P.max_sigma * (1.0f / 255.0f);
+        const int ncg = __builtin_amdgcn_readfirstlane(ctl[CTL_NCGRP]);
+        const int nblk = X.ngrp * ncg;
+        const MagicDiv by_ncg(ncg);
+        for (int t = tid; t < nblk; t += NT) {
+            const int g = by_ncg.div(t);
+            const int h = t - g * ncg;
+            const int il0 = g_grp[g], jl0 = g_cgrp[h];
+            const bool two_r = g_grp[g + 1] - il0 > 1, two_c = g_cgrp[h + 1] - jl0 > 1;
+            const int lr = g_lr[il0], lc = g_lc[jl0];
+            // |distance| and inside-the-support mask (1 / 0) of the two rows [r][row tap b] and the two columns [q][column
+            // tap a]; a single's second member reads its neighbour's entries (computed, never stored)
+            float ax[2][2], mx[2][2], ay[2][2], my[2][2];
+            auto abs_and_mask = [](const float* d, float (&a)[2][2], float (&m)[2][2]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    a[k >> 1][k & 1] = __builtin_fabsf(d[k]);
+                    m[k >> 1][k & 1] = s3::dist_class_f(d[k]) != 0 ? 1.0f : 0.0f;
+                }
+            };
+            abs_and_mask(g_dr + il0 * 2, ax, mx);
+            abs_and_mask(g_dc + jl0 * 2, ay, my);
+            const uint32_t* dp = X.Dt + lr * D::HP + lc * CH;
+            uint8_t* ob = X.outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
+            float dist[4 * CH];                                  // [c][r][q]
+            float dmax = 0.0f;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                float v[4], fy[2][4], fx[2][4];
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const uint32_t d = dp[b * D::HP + a * CH + c];
+                        v[a * 2 + b] = (float)(d >> 24);
+                        const float alpha = s3::lin_alpha_u8((float)(d & 0xFFu), ms255);
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) fy[q][a * 2 + b] = s3::lin_factor_abs(alpha, ay[q][a], my[q][a]);
+#pragma unroll
+                        for (int r = 0; r < 2; ++r) fx[r][a * 2 + b] = s3::lin_factor_abs(alpha, ax[r][b], mx[r][b]);
+                    }
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        float e[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) e[k] = fx[r][k] * fy[q][k];
+                        const bool have = (r == 0 || two_r) && (q == 0 || two_c);
+                        put_block_byte(s3::finish<false, 4, true, true, true>(e, v), have, ob + r * D::OUT_PITCH + q * CH + c,
+                                       dist[(c * 2 + r) * 2 + q], dmax);
+                    }
+            }
+            if (dmax > 0.5f - s3::kTieEps && X.dis_r64 != nullptr)
+                queue_ties(X, P, tie_mask(dist),
+                           [&](int q, int& il, int& xc) __attribute__((always_inline)) { il = il0 + ((q >> 1) & 1); xc = (jl0 + (q & 1)) * CH + (q >> 2); },
+                           [&](int q, uint32_t r8) __attribute__((always_inline)) { ob[((q >> 1) & 1) * D::OUT_PITCH + (q & 1) * CH + (q >> 2)] = (uint8_t)r8; });
+        }
+    }
+}
+
+// ---- the LDS image of the output block -> the frame: whole 16-byte chunks with streaming stores, the ragged ends of a
+//      row (the neighbouring tiles' bytes share those chunks) dword by dword and byte by byte
+template <typename X_>
+__device__ __forceinline__ void flush_blocks(const X_& X, int tid) {
+    using D = typename X_::D;
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const int ophase = X.ophase, ncolc = X.ncolc, nrow = X.nrow;
+    const int64_t rowpitch = X.rowpitch;
+    const uint8_t* outt = X.outt;
+    const int nchunk = (ophase + ncolc + 15) >> 4;
+    const MagicDiv by_nchunk(nchunk);
+    uint8_t* gbase = X.seg0 - ophase;
+    const int total = nrow * nchunk;
+    const int full_lo = ophase == 0 ? 0 : 1, full_hi = ((ophase + ncolc) & 15) == 0 ? nchunk : nchunk - 1;   // whole chunks of a row
+    for (int i = tid; i < total; i += NT) {
+        const int row = by_nchunk.div(i);
+        const int ch = i - row * nchunk;
+        if (ch >= full_lo && ch < full_hi) {
+            const v4u x = *reinterpret_cast<const v4u*>(outt + row * D::OUT_PITCH + ch * 16);
+            uint8_t* dst = gbase + row * rowpitch + ch * 16;
+            // streaming stores for the 64-byte lines this tile writes completely; the first and the last line of a row
+            // are shared with the neighbouring tiles and go through the L2 (regular stores), which merges the two
+            // tiles' halves into one line -- as streaming stores they were two partial-line writes each (+67 MB per step)
+            const uintptr_t line = reinterpret_cast<uintptr_t>(dst) & ~(uintptr_t)63;
+            const uintptr_t r0 = reinterpret_cast<uintptr_t>(gbase + row * rowpitch) + (uintptr_t)ophase;
+            if (line >= r0 && line + 64 <= r0 + (uintptr_t)ncolc) __builtin_nontemporal_store(x, reinterpret_cast<v4u*>(dst));
+            else *reinterpret_cast<v4u*>(dst) = x;
+        }
+    }
+    // the ragged chunks, two per row at most, in a loop of their own (a few waves take it once, instead of every
+    // wave dragging the byte path through every round of the loop above)
+    for (int i = tid; i < 2 * nrow; i += NT) {
+        const int row = i >> 1;
+        const int ch = (i & 1) ? nchunk - 1 : 0;
+        if (ch >= full_lo && ch < full_hi) continue;             // that end of the row is a whole chunk
+        if ((i & 1) && nchunk == 1) continue;                    // a one-chunk row: its first-chunk lane has it
+        const uint8_t* src = outt + row * D::OUT_PITCH + ch * 16;
+        uint8_t* dst = gbase + row * rowpitch + ch * 16;
+        const int lo = max(ophase - ch * 16, 0), hi = min(ophase + ncolc - ch * 16, 16);
+        const v4u x = *reinterpret_cast<const v4u*>(src);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t w = x[k];
+            if (lo <= 4 * k && hi >= 4 * k + 4) {
+                *reinterpret_cast<uint32_t*>(dst + 4 * k) = w;
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (4 * k + u >= lo && 4 * k + u < hi) dst[4 * k + u] = (uint8_t)(w >> (8 * u));
+            }
+        }
+    }
+}
+
+// ---- tie pass: the queued outputs in float64, one per lane.  IMAGE (block forms): each patches its byte in the LDS image,
+//      between two barriers, before the image leaves in one piece.  Otherwise each patches its byte in the frame, behind the
+//      task loop's dword stores (drained and fenced by the barrier).
+template <bool IMAGE, typename X_>
+__device__ __forceinline__ void stage3_ties(const X_& X, const Params& P, int tid) {
+    using D = typename X_::D;
+    if (IMAGE) {
+        __syncthreads();
+        LERF_STAMP(15);
+    }
+    if (X.dis_r64 == nullptr) return;
+    if (!IMAGE) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    const int nq = min(*X.tq_count, P.tq_cap);
+    for (int i = tid; i < nq; i += NT) {
+        const uint32_t e = X.tq[i];
+        const int il = (int)(e >> 16), xc = (int)(e & 0xFFFFu);
+        const uint8_t r8 = resolve_output(X, P.max_sigma, il, xc);
+        if (IMAGE) X.outt[il * D::OUT_PITCH + X.ophase + xc] = r8;
+        else X.seg0[il * X.rowpitch + xc] = r8;
+    }
+    if (IMAGE && nq > 0) __syncthreads();
+}
+
 // KINDW = LERF_KIND_* (| LERF_FUSED_WARP: stage 3 is the homographic warp of the tile's own output pixels, warp_tile())
 constexpr int LERF_FUSED_WARP = 16;
 template <int S, int KINDW, bool EMIT, bool FROM_FEAT = false, bool GEN = false>
@@ -1387,8 +2145,6 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
     using D = Dims<S, GEN, EMIT>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
 
     int bid = xcd_order((int)blockIdx.x, (int)gridDim.x);
     const FrameView F = frame_view<GEN>(P, T, bid);
@@ -1411,39 +2167,6 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
                                     : (iy0 >= 0 && ix0 >= 0 && iy0 + D::IY <= F.H && ix0 + D::IX <= F.W);
     const int Hc = interior ? -1 : F.H, Wc = F.W;
 
-    int* g_lr = reinterpret_cast<int*>(smem + D::OFF_GEO);
-    float* g_dr = reinterpret_cast<float*>(g_lr + D::GEO_ROWS);
-    int* g_lc = reinterpret_cast<int*>(g_dr + D::GEO_ROWS * S);
-    float* g_dc = reinterpret_cast<float*>(g_lc + D::GEO_COLS);
-    // owned output rows / columns: four wave-parallel searches in the global tables
-    auto geo_search = [&]() {
-        if (wave < 4) {
-            const bool rows = wave < 2;
-            const int* tab = rows ? F.left_r : F.left_c;
-            const int n = rows ? F.oH : F.oW;
-            const int ti = rows ? tyi : txi, tn = rows ? F.tiles_y : F.tiles_x, t0 = rows ? ty0 : tx0;
-            int r;
-            if (!(wave & 1)) r = ti == 0 ? 0 : wave_lower_bound(tab, n, t0 - D::R3, lane);
-            else r = ti == tn - 1 ? n : wave_lower_bound(tab, n, t0 + (rows ? TH : TW) - D::R3, lane);
-            if (lane == 0) ctl[16 + wave] = r;
-        }
-    };
-    // tables of the owned block into LDS; LeRF-G distances pre-multiplied by (max_sigma/255)*sqrt(0.5 log2 e)
-    auto geo_stage = [&]() {
-        const int gi0 = ctl[16], gi1 = ctl[17], gj0 = ctl[18], gj1 = ctl[19];
-        const float gscale = KIND == LERF_KIND_GAUSS ? s3::gauss_scale(P.max_sigma) : 1.0f;
-        for (int e = tid; e < gi1 - gi0; e += NT) {
-            g_lr[e] = F.left_r[gi0 + e] - hy0;
-#pragma unroll
-            for (int b = 0; b < S; ++b) g_dr[e * S + b] = F.dis_r[(gi0 + e) * S + b] * gscale;
-        }
-        for (int e = tid; e < gj1 - gj0; e += NT) {
-            g_lc[e] = F.left_c[gj0 + e] - hx0;
-#pragma unroll
-            for (int a = 0; a < S; ++a) g_dc[e * S + a] = F.dis_c[(gj0 + e) * S + a] * gscale;
-        }
-    };
-
     LERF_STAMP_RT(13);
     LERF_STAMP(0);
 #ifdef LERF_STAMPS
@@ -1451,6 +2174,9 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
 #endif
     // ---- the feat tile: stage 1 on the input tile (the geometry search rides behind the tile's loads, the staging of its
     //      results, which are in ctl by then, behind phase s), or the output of the stage-1 launch
+    // (shorthands: the search and the staging are called early for S = 2 RGB -- under stage 1 or the feat load -- and late otherwise)
+    auto geo_search = [&]() { stage3_geo_search<D>(F, tyi, txi, ty0, tx0, ctl, tid); };
+    auto geo_stage = [&]() { stage3_geo_stage<D, S, KIND>(smem, F, P.max_sigma, hy0, hx0, ctl, tid); };
     auto early_search = [&]() { if (D::GEO_EARLY && !EMIT && !WARP) geo_search(); };
     if constexpr (!FROM_FEAT) {
         stage1<D, GEN, false, false>(smem, P, img, H, W, fy0, fx0, interior, Bt, tid, early_search, [&](int k) {
@@ -1510,799 +2236,40 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
         geo_stage();
     }
     __syncthreads();
-    const int i0 = ctl[16], i1 = ctl[17], j0 = ctl[18], j1 = ctl[19];
-    const int nrow = i1 - i0, ncol = j1 - j0;
-
+    using X3 = Stage3<D, S, KIND>;
+    X3 X(smem, P, F, outp, ctl);
     LERF_STAMP(11);
-    // ---- stage 3.  Consecutive output rows that start at the same source row (2 rows at x2, 3 at x3 ...) form a row
-    //      group and share their taps: one task = (row group, one 4-byte-aligned output dword column); the tap loads, the
-    //      u8 -> f32 conversions and the column-only terms are done once per group, the rows pay one multiply and two
-    //      FMAs per tap.  Same code for the 2x2 and the 4x4 support.
-    {
-        constexpr int SS = S * S;
-        constexpr int GMAX = S == 2 ? 5 : 3;                      // rows per group (larger runs are split)
-        int* g_grp = reinterpret_cast<int*>(g_dc + D::GEO_COLS * S);
-        const int ncolc = ncol * CH;
-        // bytes per output row: dense, or the caller's pitch (a rank's block of 1919 / 1921 output columns lives in rows padded to a
-        // 16-byte multiple so that its tiles keep the dword-column / block tasks -- dense, every row was a group of its own)
-        const int64_t rowpitch = P.out_pitch > 0 ? (int64_t)P.out_pitch : (int64_t)F.oW * CH;      // (ragged launches: always dense)
-        uint8_t* seg0 = outp + (int64_t)i0 * rowpitch + (int64_t)j0 * CH;
-        const bool rows_align = (rowpitch & 3) == 0;              // dword columns line up across the rows of a group
-        // dword columns per row: when every row of the block starts on a 4-byte boundary (a0 == 0 below) the block needs
-        // no slack column, and a 384-byte tile row is exactly 96 dwords = whole 128-byte lines per wave store
-        const bool seg_aligned = rows_align && (reinterpret_cast<uintptr_t>(seg0) & 3u) == 0;
-        const int ndw = seg_aligned ? (ncolc + 3) >> 2 : (ncolc + 6) >> 2;
-        if (wave == 0) {
-            int ng = 0;
-            for (int base = 0; base < nrow; base += 64) {
-                const int il = base + lane;
-                bool start = false;
-                if (il < nrow)
-                    start = il == 0 || !rows_align || g_lr[il] != g_lr[il - 1] || (il >= GMAX && g_lr[il - GMAX] == g_lr[il]);
-                const unsigned long long m = __ballot(start);
-                if (start) g_grp[ng + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = il;
-                ng += __popcll(m);
-            }
-            if (lane == 0) g_grp[ng] = nrow;
-            // every group of the tile the same size (integer scale factors, away from the frame's top and bottom): the
-            // task loop then runs with that size as a compile-time constant, without a row test per tap set
-            const int g0 = ng > 0 ? g_grp[1] - g_grp[0] : 0;
-            bool same = true;
-            for (int base = 0; base < ng; base += 64) {
-                const int idx = base + lane;
-                if (idx < ng && g_grp[idx + 1] - g_grp[idx] != g0) same = false;
-            }
-            const bool uniform = __ballot(!same) == 0ull;
-            if (lane == 0) {
-                ctl[21] = ng;
-                ctl[22] = uniform ? g0 : 0;
-                ctl[23] = 0;
-            }
-            if constexpr (KIND == LERF_KIND_LINEAR && S == 2 && D::OUT_FITS) {
-                bool small = true;                               // no group of more than two rows (block tasks of LeRF-L)
-                for (int base = 0; base < ng; base += 64) {
-                    const int idx = base + lane;
-                    if (idx < ng && g_grp[idx + 1] - g_grp[idx] > 2) small = false;
-                }
-                const bool ok = __ballot(!small) == 0ull;
-                if (lane == 0) ctl[26] = ok ? 1 : 0;
-            }
-        } else if (wave == 1 && KIND == LERF_KIND_LINEAR && S == 2 && D::OUT_FITS) {
-            // LeRF-L block tasks: the columns in groups of at most two that share their taps (runs of equal left taps, every
-            // second column of a run starts a group); the table lies behind the output image, over the dead stage-2 areas
-            int* g_cgrp = reinterpret_cast<int*>(smem + D::OFF_CGRP);
-            constexpr int NCMAX = 2 * TW + 14;
-            int nc = 0;
-            for (int base = 0; base < ncol; base += 64) {
-                const int jl = base + lane;
-                bool start = false;
-                if (jl < ncol) {
-                    int back = 0;                                // columns of the same run to the left
-                    while (back < 16 && jl - back - 1 >= 0 && g_lc[jl - back - 1] == g_lc[jl]) ++back;
-                    start = (back & 1) == 0;
-                }
-                const unsigned long long m = __ballot(start);
-                if (start) {
-                    const int idx = nc + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    if (idx < NCMAX) g_cgrp[idx] = jl;
-                }
-                nc += __popcll(m);
-            }
-            if (lane == 0) {
-                if (nc <= NCMAX) g_cgrp[nc] = ncol;
-                ctl[25] = nc;
-                ctl[27] = (nc <= NCMAX) ? 1 : 0;
-            }
-        } else if (wave == 1) {
-            // the columns (block tasks below): do they pair up as (2h, 2h + 1) -- code 1 -- or, behind a leading single (the
-            // frame's left edge), as (2h - 1, 2h) -- code 2?  A trailing single is fine either way.
-            bool ok0 = true, ok1 = true, step1 = true;
-            for (int base = 0; base < ncol; base += 64) {
-                const int jl = base + lane;
-                if (jl + 1 < ncol && g_lc[jl + 1] != g_lc[jl]) { if (jl & 1) ok1 = false; else ok0 = false; }
-                if (!(jl & 1) && jl + 2 < ncol && g_lc[jl + 2] != g_lc[jl] + 1) step1 = false;
-            }
-            const bool p0 = __ballot(!ok0) == 0ull, p1 = __ballot(!ok1) == 0ull, q1 = __ballot(!step1) == 0ull;
-            if (lane == 0) { ctl[24] = p0 ? 1 : (p1 ? 2 : 0); ctl[28] = q1 ? 1 : 0; }   // [28]: pair h + 1 starts one tap right of pair h (x2)
-        } else if (wave == 2 && KIND == LERF_KIND_GAUSS) {
-            // the rows, the same question on the rows' first taps
-            bool ok0 = true, ok1 = true, step1 = true;
-            for (int base = 0; base < nrow; base += 64) {
-                const int il = base + lane;
-                if (il + 1 < nrow && g_lr[il + 1] != g_lr[il]) { if (il & 1) ok1 = false; else ok0 = false; }
-                if (!(il & 1) && il + 2 < nrow && g_lr[il + 2] != g_lr[il] + 1) step1 = false;
-            }
-            const bool p0 = __ballot(!ok0) == 0ull, p1 = __ballot(!ok1) == 0ull, q1 = __ballot(!step1) == 0ull;
-            if (lane == 0) { ctl[26] = p0 ? 1 : (p1 ? 2 : 0); ctl[29] = q1 ? 1 : 0; }
-        }
-        __syncthreads();
-        const int ngrp = ctl[21];
-        const int gsame = __builtin_amdgcn_readfirstlane(ctl[22]);
-        const unsigned magic = (unsigned)((0x100000000ull + (unsigned)ndw - 1) / (unsigned)(ndw > 0 ? ndw : 1));
-        const float ms255 = P.max_sigma * (1.0f / 255.0f);
-        const int ntask = ngrp * ndw;
-        uint32_t* tq = reinterpret_cast<uint32_t*>(smem + D::OFF_TQ);
-        int* tq_count = ctl + 23;                               // zeroed with the group table below
-        auto run_tasks = [&](auto gs_const) {
-        constexpr int GS = decltype(gs_const)::value;          // rows per group, 0 = read it per group
-        constexpr int GN = GS > 0 ? GS : GMAX;
-        for (int t = tid; t < ntask; t += NT) {
-            const int g = ndw == 1 ? t : (int)__umulhi((unsigned)t, magic);      // (ceil(2^32 / 1) does not fit the 32-bit magic)
-            const int dw = t - g * ndw;
-            const int il0 = g_grp[g];
-            const int gs = GS > 0 ? GS : g_grp[g + 1] - il0;
-            uint8_t* seg = seg0 + il0 * rowpitch;
-            const int a0 = (int)(reinterpret_cast<uintptr_t>(seg) & 3u);
-            const int b0 = dw * 4 - a0;
-            const int lr = g_lr[il0];
-            uint32_t packed[GN];
-            // tie detection: the 2x2 kernels keep every output's distance from its rounded value and a running maximum
-            // (one v_max per output, the ties are looked for only when the maximum says there is one); the 4x4 kernel has
-            // no registers for that and sets a bit per output
-            constexpr bool DIST = S == 2;
-            float dist[DIST ? GN * 4 : 1];                        // [r*4+u]
-            float dmax = 0.0f;
-            unsigned tiebits = 0;                                 // bit r*4+u
-#pragma unroll
-            for (int r = 0; r < GN; ++r) packed[r] = 0;
-            s3::f2 DXP[S];                                        // packed 4x4 path: (row 0, row 1) distances of row tap b
-            if constexpr (KIND == LERF_KIND_GAUSS && S == 4 && GS == 2) {
-#pragma unroll
-                for (int b = 0; b < S; ++b) { DXP[b].x = g_dr[il0 * S + b]; DXP[b].y = g_dr[(il0 + 1) * S + b]; }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int xc = min(max(b0 + u, 0), ncolc - 1);    // clamped; invalid bytes are not stored
-                const int jl = xc / CH;
-                const int c = xc - jl * CH;
-                const int lc = g_lc[jl];
-                if constexpr (KIND == LERF_KIND_GAUSS && S == 4 && GS == 2) {
-                    // The 4x4 support, two rows per group, in PACKED float32 over the two rows (lane x = row 0, lane y = row 1):
-                    // per tap and row PAIR one v_pk_mul (tx), two v_pk_fma (the form), one v_pk_add and one v_pk_fma (the sums)
-                    // instead of ten scalar operations; a tap's four scalars sit two to a register pair -- (p0, ty^2) and
-                    // (k1, value) -- and are read through op_sel.  Same operations in the same order: the same bytes.
-                    s3::f2 PT[SS], KV[SS];
-#pragma unroll
-                    for (int a = 0; a < S; ++a) {
-                        const float dy = g_dc[jl * S + a];
-#pragma unroll
-                        for (int b = 0; b < S; ++b) {
-                            const uint32_t d = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
-                            const float tyv = s3::gauss_t_u8((float)((d >> 16) & 0xFFu), dy);
-                            PT[a * S + b].x = s3::gauss_m2rho_u8((float)(d & 0xFFu)) * tyv;
-                            PT[a * S + b].y = tyv * tyv;
-                            KV[a * S + b].x = (float)((d >> 8) & 0xFFu);
-                            KV[a * S + b].y = (float)(d >> 24);
-                        }
-                    }
-                    s3::f2 NUM, DEN;
-#pragma unroll
-                    for (int a = 0; a < S; ++a)
-#pragma unroll
-                        for (int b = 0; b < S; ++b) {
-                            const int k = a * S + b;
-                            const s3::f2 TX = s3::pk_mul_blo(DXP[b], KV[k]);                       // k1 * dx[r][b]
-                            const s3::f2 E = s3::pk_fma_pb<false>(TX, PT[k], s3::pk_fma_ppb<true>(TX, PT[k]));   // fma(tx, p0, fma(tx, tx, ty2))
-                            s3::f2 W;
-                            W.x = __builtin_amdgcn_exp2f(-E.x);
-                            W.y = __builtin_amdgcn_exp2f(-E.y);
-                            if (k == 0) {
-                                DEN = W;
-                                NUM = s3::pk_mul_bhi_after_trans(W, KV[k]);
-                            } else {
-                                DEN = DEN + W;                                                  // (compiler-generated: see the block tasks)
-                                NUM = s3::pk_fma_bhi_after_trans(W, KV[k], NUM);
-                            }
-                        }
-#pragma unroll
-                    for (int r = 0; r < 2; ++r) {
-                        const float xf = s3::finish_div(r ? NUM.y : NUM.x, r ? DEN.y : DEN.x);
-                        bool tie;
-                        packed[r] = s3::pack_u8_tie(xf, u, packed[r], &tie);
-                        if (tie) tiebits |= 1u << (r * 4 + u);
-                    }
-                    continue;
-                }
-                // shared by the rows of the group: per tap (a = column offset major, numpy meshgrid 'xy' :95-98; b = row offset)
-                float p0[SS], k1[SS], ty[SS], v[SS];
-#pragma unroll
-                for (int a = 0; a < S; ++a) {
-                    const float dy = g_dc[jl * S + a];
-#pragma unroll
-                    for (int b = 0; b < S; ++b) {
-                        const uint32_t d = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
-                        v[a * S + b] = (float)(d >> 24);
-                        const float k0 = (float)(d & 0xFFu);
-                        if (KIND == LERF_KIND_GAUSS) {
-                            // column-only terms of the quadratic form: p0 <- (-2 rho) ty, ty <- ty^2 (gauss_form_cols)
-                            const float tyv = s3::gauss_t_u8((float)((d >> 16) & 0xFFu), dy);
-                            p0[a * S + b] = s3::gauss_m2rho_u8(k0) * tyv;
-                            k1[a * S + b] = (float)((d >> 8) & 0xFFu);
-                            ty[a * S + b] = tyv * tyv;
-                        } else {
-                            const float alpha = s3::lin_alpha_u8(k0, ms255);
-                            p0[a * S + b] = alpha;
-                            ty[a * S + b] = s3::lin_factor(alpha, dy, s3::dist_class_f(dy));
-                            k1[a * S + b] = 0.0f;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < GN; ++r) {
-                    if (r < gs) {
-                        float e[SS];
-#pragma unroll
-                        for (int a = 0; a < S; ++a)
-#pragma unroll
-                            for (int b = 0; b < S; ++b) {
-                                const float dx = g_dr[(il0 + r) * S + b];
-                                if (KIND == LERF_KIND_GAUSS)
-                                    e[a * S + b] = s3::gauss_form_cols(s3::gauss_t_u8(k1[a * S + b], dx), ty[a * S + b], p0[a * S + b]);
-                                else
-                                    e[a * S + b] = s3::lin_factor(p0[a * S + b], dx, s3::dist_class_f(dx)) * ty[a * S + b];
-                            }
-                        const float xf = s3::finish<KIND == LERF_KIND_GAUSS, SS, true, true, true>(e, v);
-                        if (DIST) {
-                            packed[r] = s3::pack_u8_dist(xf, u, packed[r], &dist[DIST ? r * 4 + u : 0]);
-                            dmax = __builtin_fmaxf(dmax, __builtin_fabsf(dist[DIST ? r * 4 + u : 0]));
-                        } else {
-                            bool tie;
-                            packed[r] = s3::pack_u8_tie(xf, u, packed[r], &tie);
-                            if (tie) tiebits |= 1u << (r * 4 + u);
-                        }
-                    }
-                }
-            }
-            if ((DIST ? dmax > 0.5f - s3::kTieEps : tiebits != 0) && F.dis_r64 != nullptr) {
-                unsigned tiemask = tiebits;
-                if (DIST) {
-#pragma unroll
-                    for (int q = 0; q < GN * 4; ++q)
-                        if ((GS > 0 || (q >> 2) < gs) && __builtin_fabsf(dist[DIST ? q : 0]) > 0.5f - s3::kTieEps) tiemask |= 1u << q;
-                }
-                // rare: the output is re-evaluated in float64 exactly as the reference does (lerf_stage3.h, tie guard)
-                while (tiemask != 0) {                                     // one round per queued output of the lane, not per output
-                    const int q = __builtin_ctz(tiemask);
-                    tiemask &= tiemask - 1;
-                    const int r = q >> 2, u = q & 3;
-                    const int xc = min(max(b0 + u, 0), ncolc - 1);
-                    // queued for the pass behind the task loop; only a full queue is worked off on the spot
-                    const int slot = atomicAdd(tq_count, 1);
-                    if (slot < P.tq_cap) {
-                        tq[slot] = ((uint32_t)(il0 + r) << 16) | (uint32_t)xc;
-                        continue;
-                    }
-                    const int jl = xc / CH;
-                    const int c = xc - jl * CH;
-                    const int lc = g_lc[jl];
-                    uint32_t dd[SS];
-                    double dx64[S], dy64[S];
-#pragma unroll
-                    for (int b = 0; b < S; ++b) dx64[b] = F.dis_r64[(int64_t)(i0 + il0 + r) * S + b];
-#pragma unroll
-                    for (int a = 0; a < S; ++a) dy64[a] = F.dis_c64[(int64_t)(j0 + jl) * S + a];
-#pragma unroll
-                    for (int a = 0; a < S; ++a)
-#pragma unroll
-                        for (int b = 0; b < S; ++b) dd[a * S + b] = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
-                    const uint32_t r8 = s3::resolve_u8<KIND == LERF_KIND_GAUSS, S>(dd, dx64, dy64, P.max_sigma);
-#pragma unroll
-                    for (int rr = 0; rr < GN; ++rr)
-                        if (rr == r) packed[rr] = (packed[rr] & ~(0xFFu << (8 * u))) | (r8 << (8 * u));
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < GN; ++r) {
-                if (r < gs) {
-                    uint8_t* sr = seg + r * rowpitch;
-                    if (b0 >= 0 && b0 + 3 < ncolc) {
-                        // streaming store: the output is never re-read here, keep the LUT pack resident in L2 instead
-                        __builtin_nontemporal_store(packed[r], reinterpret_cast<uint32_t*>(sr + b0));
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (b0 + u >= 0 && b0 + u < ncolc) sr[b0 + u] = (uint8_t)(packed[r] >> (8 * u));
-                    }
-                }
-            }
-        }
-        };
-        // ---- block tasks: tiles whose output rows AND columns come in pairs that share their taps (integer x2, away from
-        //      the frame's top and left).  One task = the 2 x 2 outputs of a (row pair, column pair), all CH channels: the
-        //      four tap dwords of a channel are loaded and converted once for four outputs instead of once for two, the
-        //      column-only terms serve both rows and the row-only products both columns (43 instead of 63 VALU instructions
-        //      per output), and a tile is exactly 4 tasks per thread.  The bytes are assembled in an LDS image of the tile's
-        //      output block (ties are patched there) and leave as whole 16-byte chunks.  Same arithmetic, operation for
-        //      operation, as run_tasks: the outputs are bit-identical.
-        constexpr bool BLK = KIND == LERF_KIND_GAUSS && (S == 2 || S == 4) && D::OUT_FITS;      // (round 4: the 4 x 4 support too)
-        uint8_t* outt = smem + D::OFF_OUT;
-        const int ophase = (int)(reinterpret_cast<uintptr_t>(seg0) & 15u);
-#ifndef LERF_NO_BLOCK_TASKS
-        const int rcode = __builtin_amdgcn_readfirstlane(ctl[26]), ccode = __builtin_amdgcn_readfirstlane(ctl[24]);
-        const bool blk = BLK && rows_align && rcode != 0 && ccode != 0 && (rowpitch & 15) == 0 && nrow <= D::OUT_ROWS &&
-                         ophase + ncolc <= D::OUT_PITCH;
-        // interior tiles: pairs from row 0 / column 0 on, even counts -- no validity tests; tiles at the frame's edges: a leading
-        // and / or trailing single row or column, handled as a pair whose other member is not stored
-        const bool blk_uni = blk && rcode == 1 && ccode == 1 && ((nrow | ncol) & 1) == 0;
-#else
-        const bool blk = false, blk_uni = false;
-#endif
-        auto run_blocks = [&](auto uni_const) {
-            constexpr bool UNI = decltype(uni_const)::value;
-            if constexpr (BLK) {
-            constexpr int SS2 = S * S;
-            const int rofs = UNI ? 0 : rcode - 1, cofs = UNI ? 0 : ccode - 1;
-            const int ncg = (ncol + cofs + 1) >> 1;
-            const int nblk = ((nrow + rofs + 1) >> 1) * ncg;
-            const unsigned magicc = (unsigned)((0x100000000ull + (unsigned)ncg - 1) / (unsigned)(ncg > 0 ? ncg : 1));
-            for (int t = tid; t < nblk; t += NT) {
-                const int g = ncg == 1 ? t : (int)__umulhi((unsigned)t, magicc);
-                const int h = t - g * ncg;
-                const int il0 = 2 * g - rofs, jl0 = 2 * h - cofs;
-                const int lr = g_lr[UNI ? il0 : max(il0, 0)], lc = g_lc[UNI ? jl0 : max(jl0, 0)];
-                // distances as PAIRS: DX[b] = (row 0, row 1) of row tap b, DY[a] = (column 0, column 1) of column tap a
-                s3::f2 DX[S], DY[S];
-#pragma unroll
-                for (int b = 0; b < S; ++b) { DX[b].x = g_dr[il0 * S + b]; DX[b].y = g_dr[il0 * S + S + b]; }
-#pragma unroll
-                for (int a = 0; a < S; ++a) { DY[a].x = g_dc[jl0 * S + a]; DY[a].y = g_dc[jl0 * S + S + a]; }
-                const uint32_t* dp = Dt + lr * D::HP + lc * CH;
-                uint8_t* ob = outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
-                float dist[4 * CH];                                  // [c][r][q]
-                float dmax = 0.0f;
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    // packed over the two COLUMNS q of the block (lane x = column 0, lane y = column 1); the scalars of a tap
-                    // (its value, m2rho, k1, k2) sit in the low halves of register pairs and are read through op_sel
-                    s3::f2 NUM[2], DEN[2];                           // [row r]
-#pragma unroll
-                    for (int a = 0; a < S; ++a)
-#pragma unroll
-                        for (int b = 0; b < S; ++b) {
-                            const uint32_t d = dp[b * D::HP + a * CH + c];
-                            s3::f2 V, K1, K2, M2;
-                            V.x = V.y = (float)(d >> 24);                          // (both lanes: the weights' consumers below are plain vector code)
-                            K1.x = (float)((d >> 8) & 0xFFu);
-                            M2.x = s3::gauss_m2rho_u8((float)(d & 0xFFu));
-                            K2.x = (float)((d >> 16) & 0xFFu);
-                            const s3::f2 TYV = s3::pk_mul_blo(DY[a], K2);          // k2 * dy[q][a]
-                            const s3::f2 P0 = s3::pk_mul_blo(TYV, M2);             // m2rho * tyv
-                            const s3::f2 TY2 = s3::pk_mul(TYV, TYV);
-                            const s3::f2 TX = s3::pk_mul_blo(DX[b], K1);           // lanes = ROWS here: k1 * dx[r][b]
-                            // e[r][q] = fma(tx_r, p0_q, fma(tx_r, tx_r, ty2_q)), w = exp2(-e), num += w v, den += w
-                            const s3::f2 E0 = s3::pk_fma_ab<false>(TX, P0, s3::pk_fma_aa<false>(TX, TY2));
-                            const s3::f2 E1 = s3::pk_fma_ab<true>(TX, P0, s3::pk_fma_aa<true>(TX, TY2));
-                            s3::f2 W0, W1;
-                            W0.x = __builtin_amdgcn_exp2f(-E0.x); W0.y = __builtin_amdgcn_exp2f(-E0.y);
-                            W1.x = __builtin_amdgcn_exp2f(-E1.x); W1.y = __builtin_amdgcn_exp2f(-E1.y);
-                            // The consumers of the v_exp results are COMPILER-generated packed operations, not inline assembly: gfx950
-                            // needs a wait state between a transcendental instruction and a VALU read of its result, which the
-                            // compiler inserts for its own instructions only (an inline-asm consumer right behind v_exp read the stale
-                            // register: nondeterministic bytes).
-                            if (a == 0 && b == 0) {
-                                DEN[0] = W0; DEN[1] = W1;
-                                NUM[0] = W0 * V; NUM[1] = W1 * V;
-                            } else {
-                                NUM[0] = __builtin_elementwise_fma(W0, V, NUM[0]); NUM[1] = __builtin_elementwise_fma(W1, V, NUM[1]);
-                                DEN[0] = DEN[0] + W0; DEN[1] = DEN[1] + W1;
-                            }
-                        }
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const float den = q ? DEN[r].y : DEN[r].x, num = q ? NUM[r].y : NUM[r].x;
-                            const float xf = s3::finish_div(num, den);
-                            const float rr = __builtin_rintf(xf);
-                            const float ds = xf - rr;
-                            const bool have = UNI || ((unsigned)(il0 + r) < (unsigned)nrow && (unsigned)(jl0 + q) < (unsigned)ncol);
-                            dist[(c * 2 + r) * 2 + q] = have ? ds : 0.0f;
-                            dmax = __builtin_fmaxf(dmax, __builtin_fabsf(dist[(c * 2 + r) * 2 + q]));
-                            if (have) ob[r * D::OUT_PITCH + q * CH + c] = (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(rr, 0u, 0u);
-                        }
-                }
-                if (dmax > 0.5f - s3::kTieEps && F.dis_r64 != nullptr) {
-                    unsigned tiemask = 0;
-#pragma unroll
-                    for (int q = 0; q < 4 * CH; ++q)
-                        if (__builtin_fabsf(dist[q]) > 0.5f - s3::kTieEps) tiemask |= 1u << q;
-                    while (tiemask != 0) {                                 // one round per queued output of the lane, not per output
-                        const int q = __builtin_ctz(tiemask);
-                        tiemask &= tiemask - 1;
-                        const int c = q >> 2, r = (q >> 1) & 1, qq = q & 1;
-                        const int il = il0 + r, xc = (jl0 + qq) * CH + c;
-                        const int slot = atomicAdd(tq_count, 1);
-                        if (slot < P.tq_cap) {
-                            tq[slot] = ((uint32_t)il << 16) | (uint32_t)xc;
-                            continue;
-                        }
-                        // queue full: evaluated on the spot (float64, the reference's own dtype chain), patched behind the store above
-                        uint32_t dd[SS2];
-                        double dx64[S], dy64[S];
-#pragma unroll
-                        for (int b = 0; b < S; ++b) dx64[b] = F.dis_r64[(int64_t)(i0 + il) * S + b];
-#pragma unroll
-                        for (int a = 0; a < S; ++a) dy64[a] = F.dis_c64[(int64_t)(j0 + jl0 + qq) * S + a];
-#pragma unroll
-                        for (int a = 0; a < S; ++a)
-#pragma unroll
-                            for (int b = 0; b < S; ++b) dd[a * S + b] = dp[b * D::HP + a * CH + c];
-                        outt[il * D::OUT_PITCH + ophase + xc] = (uint8_t)s3::resolve_u8<true, S>(dd, dx64, dy64, P.max_sigma);
-                    }
-                }
-            }
-            }
-        };
-        // ---- quad tasks (round 5): RP x CP neighbouring blocks of an INTERIOR x2 tile in one task.  Pair h + 1 starts exactly one
-        //      tap right of / below pair h (ctl[28], ctl[29]), so the (S + RP - 1) x (S + CP - 1) taps of the task serve up to
-        //      RP x CP blocks each: a tap's load and u8 -> f32 conversions once per task instead of once per block (S = 4,
-        //      2 x 2 blocks: 25 instead of 64), its column-only terms once per column pair (40 instead of 64), its row
-        //      products once per row pair.  Every output still sums ITS S x S taps in the order (a outer, b inner) with the
-        //      operations of run_blocks: identical bytes.  One task per thread on a 64 x 64 tile with 2 x 2 blocks.
-        //      Measured (A/B on one box, profiles/r05_experiments.txt): S = 4: 2 x 2 blocks +1.7 % (23.58 -> 23.99 Gpix/s; 2 x 1: +1.6 %,
-        //      1 x 2: +1.2 %) -- the four v_exp_f32 per (tap, block) and their packed consumers are not shared, they are 3/4 of a
-        //      tap's issue time; S = 2: 2 x 2 blocks -1.4 % (one 48-output task per thread hides less latency than four of 12), 2 x 1
-        //      and 1 x 2 +-0: the 2 x 2 support keeps its single blocks.
-#ifdef LERF_QUAD_RP
-        constexpr int QRP = LERF_QUAD_RP, QCP = LERF_QUAD_CP;          // (A/B builds)
-#else
-        constexpr int QRP = S == 4 ? 2 : 1, QCP = S == 4 ? 2 : 1;
-#endif
-        const bool quad = BLK && QRP * QCP > 1 && blk_uni && __builtin_amdgcn_readfirstlane(ctl[28]) != 0 &&
-                          __builtin_amdgcn_readfirstlane(ctl[29]) != 0 && ((nrow >> 1) % QRP) == 0 && ((ncol >> 1) % QCP) == 0;
-        auto run_quads = [&]() {
-            if constexpr (BLK && QRP * QCP > 1) {
-            constexpr int RP = QRP, CP = QCP, TR = S + RP - 1, TC = S + CP - 1, SS2 = S * S;
-            const int ncq = (ncol >> 1) / CP;
-            const int ntq = ((nrow >> 1) / RP) * ncq;
-            const unsigned magicq = (unsigned)((0x100000000ull + (unsigned)ncq - 1) / (unsigned)(ncq > 0 ? ncq : 1));
-            for (int t = tid; t < ntq; t += NT) {
-                const int g = ncq == 1 ? t : (int)__umulhi((unsigned)t, magicq);
-                const int h = t - g * ncq;
-                const int il0 = 2 * RP * g, jl0 = 2 * CP * h;
-                const int lr = g_lr[il0], lc = g_lc[jl0];
-                s3::f2 DX[RP][S], DY[CP][S];               // [pair][tap]: lanes = the two rows / the two columns of the pair
-#pragma unroll
-                for (int rp = 0; rp < RP; ++rp)
-#pragma unroll
-                    for (int b = 0; b < S; ++b) { DX[rp][b].x = g_dr[(il0 + 2 * rp) * S + b]; DX[rp][b].y = g_dr[(il0 + 2 * rp + 1) * S + b]; }
-#pragma unroll
-                for (int cp = 0; cp < CP; ++cp)
-#pragma unroll
-                    for (int a = 0; a < S; ++a) { DY[cp][a].x = g_dc[(jl0 + 2 * cp) * S + a]; DY[cp][a].y = g_dc[(jl0 + 2 * cp + 1) * S + a]; }
-                const uint32_t* dp = Dt + lr * D::HP + lc * CH;
-                uint8_t* ob = outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
-#pragma unroll 1
-                for (int c = 0; c < CH; ++c) {
-                    s3::f2 NUM[RP][CP][2], DEN[RP][CP][2];   // [row pair][column pair][row of the pair], lanes = columns of the pair
-#pragma unroll
-                    for (int A = 0; A < TC; ++A) {
-#pragma unroll
-                        for (int B = 0; B < TR; ++B) {
-                            const uint32_t d = dp[B * D::HP + A * CH + c];
-                            s3::f2 V, K1, K2, M2;
-                            V.x = V.y = (float)(d >> 24);
-                            K1.x = (float)((d >> 8) & 0xFFu);
-                            M2.x = s3::gauss_m2rho_u8((float)(d & 0xFFu));
-                            K2.x = (float)((d >> 16) & 0xFFu);
-                            s3::f2 P0[CP], TY2[CP], TX[RP];
-#pragma unroll
-                            for (int cp = 0; cp < CP; ++cp) {
-                                const int a = A - cp;
-                                if (a >= 0 && a < S) {
-                                    const s3::f2 TYV = s3::pk_mul_blo(DY[cp][a < 0 ? 0 : (a >= S ? 0 : a)], K2);
-                                    P0[cp] = s3::pk_mul_blo(TYV, M2);
-                                    TY2[cp] = s3::pk_mul(TYV, TYV);
-                                }
-                            }
-#pragma unroll
-                            for (int rp = 0; rp < RP; ++rp) {
-                                const int b = B - rp;
-                                if (b >= 0 && b < S) TX[rp] = s3::pk_mul_blo(DX[rp][b < 0 ? 0 : (b >= S ? 0 : b)], K1);
-                            }
-#pragma unroll
-                            for (int cp = 0; cp < CP; ++cp) {
-                                const int a = A - cp;
-                                if (a < 0 || a >= S) continue;
-#pragma unroll
-                                for (int rp = 0; rp < RP; ++rp) {
-                                    const int b = B - rp;
-                                    if (b < 0 || b >= S) continue;
-                                    const s3::f2 E0 = s3::pk_fma_ab<false>(TX[rp], P0[cp], s3::pk_fma_aa<false>(TX[rp], TY2[cp]));
-                                    const s3::f2 E1 = s3::pk_fma_ab<true>(TX[rp], P0[cp], s3::pk_fma_aa<true>(TX[rp], TY2[cp]));
-                                    s3::f2 W0, W1;
-                                    W0.x = __builtin_amdgcn_exp2f(-E0.x); W0.y = __builtin_amdgcn_exp2f(-E0.y);
-                                    W1.x = __builtin_amdgcn_exp2f(-E1.x); W1.y = __builtin_amdgcn_exp2f(-E1.y);
-                                    // (compiler-generated consumers of the v_exp results: see run_blocks)
-                                    if (a == 0 && b == 0) {
-                                        DEN[rp][cp][0] = W0; DEN[rp][cp][1] = W1;
-                                        NUM[rp][cp][0] = W0 * V; NUM[rp][cp][1] = W1 * V;
-                                    } else {
-                                        NUM[rp][cp][0] = __builtin_elementwise_fma(W0, V, NUM[rp][cp][0]);
-                                        NUM[rp][cp][1] = __builtin_elementwise_fma(W1, V, NUM[rp][cp][1]);
-                                        DEN[rp][cp][0] = DEN[rp][cp][0] + W0; DEN[rp][cp][1] = DEN[rp][cp][1] + W1;
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    float dist[RP * CP * 4];
-                    float dmax = 0.0f;
-#pragma unroll
-                    for (int rp = 0; rp < RP; ++rp)
-#pragma unroll
-                        for (int cp = 0; cp < CP; ++cp)
-#pragma unroll
-                            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                                for (int q = 0; q < 2; ++q) {
-                                    const float den = q ? DEN[rp][cp][r].y : DEN[rp][cp][r].x, num = q ? NUM[rp][cp][r].y : NUM[rp][cp][r].x;
-                                    const float xf = s3::finish_div(num, den);
-                                    const float rr = __builtin_rintf(xf);
-                                    const float ds = xf - rr;
-                                    dist[((rp * CP + cp) * 2 + r) * 2 + q] = ds;
-                                    dmax = __builtin_fmaxf(dmax, __builtin_fabsf(ds));
-                                    ob[(2 * rp + r) * D::OUT_PITCH + (2 * cp + q) * CH + c] = (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(rr, 0u, 0u);
-                                }
-                    if (dmax > 0.5f - s3::kTieEps && F.dis_r64 != nullptr) {
-                        unsigned tiemask = 0;
-#pragma unroll
-                        for (int u = 0; u < RP * CP * 4; ++u)
-                            if (__builtin_fabsf(dist[u]) > 0.5f - s3::kTieEps) tiemask |= 1u << u;
-                        while (tiemask != 0) {                             // one round per queued output of the lane, not per output
-                            const int k = __builtin_ctz(tiemask);
-                            tiemask &= tiemask - 1;
-                            const int blkq = k >> 2, r = (k >> 1) & 1, q = k & 1;
-                            const int rp = blkq / CP, cp = blkq - rp * CP;
-                            const int il = il0 + 2 * rp + r, jl = jl0 + 2 * cp + q, xc = jl * CH + c;
-                            const int slot = atomicAdd(tq_count, 1);
-                            if (slot < P.tq_cap) {
-                                tq[slot] = ((uint32_t)il << 16) | (uint32_t)xc;
-                                continue;
-                            }
-                            // queue full: evaluated on the spot (float64, the reference's own dtype chain), patched behind the store above
-                            uint32_t dd[SS2];
-                            double dx64[S], dy64[S];
-#pragma unroll
-                            for (int b = 0; b < S; ++b) dx64[b] = F.dis_r64[(int64_t)(i0 + il) * S + b];
-#pragma unroll
-                            for (int a = 0; a < S; ++a) dy64[a] = F.dis_c64[(int64_t)(j0 + jl) * S + a];
-#pragma unroll
-                            for (int a = 0; a < S; ++a)
-#pragma unroll
-                                for (int b = 0; b < S; ++b) dd[a * S + b] = Dt[(lr + rp + b) * D::HP + (lc + cp + a) * CH + c];
-                            outt[il * D::OUT_PITCH + ophase + xc] = (uint8_t)s3::resolve_u8<true, S>(dd, dx64, dy64, P.max_sigma);
-                        }
-                    }
-                }
-            }
-            }
-        };
-        // ---- LeRF-L block tasks (amplified-linear weights, 2 x 2 support): row groups and column groups of ONE or two
-        //      members (x1.5 gives groups of 1, 2, 1, 2 ..., x2 pairs; the frame edges singles), one task = the up to 2 x 2
-        //      outputs of a (row group, column group), all channels.  The dword-column tasks ran the general five-row form
-        //      here (a group's size is not uniform at x1.5) and evaluated every tap's row factor per output; the block forms
-        //      a tap's column factor once per column, its row factor once per row.  Weights as in lerf_stage3.h: the factor of
-        //      a distance x is max(1 - alpha |x|, 0) for |x| <= 1 and 0 outside -- alpha * x + 1 (x < 0) and 1 - alpha * x
-        //      (x >= 0) are the same float32 operations on |x| -- so the bytes are those of run_tasks.
-        constexpr bool BLKL = KIND == LERF_KIND_LINEAR && S == 2 && D::OUT_FITS;
-#ifndef LERF_NO_BLOCK_TASKS
-        const bool blkl = BLKL && __builtin_amdgcn_readfirstlane((rows_align && ctl[26] != 0 && ctl[27] != 0 && (rowpitch & 15) == 0 &&
-                                                                  nrow <= D::OUT_ROWS && ophase + ncolc <= D::OUT_PITCH) ? 1 : 0) != 0;
-#else
-        const bool blkl = false;
-#endif
-        auto run_blocks_lin = [&]() {
-            if constexpr (BLKL) {
-            const int* g_cgrp = reinterpret_cast<const int*>(smem + D::OFF_CGRP);
-            const int ncg = __builtin_amdgcn_readfirstlane(ctl[25]);
-            const int nblk = ngrp * ncg;
-            const unsigned magicc = (unsigned)((0x100000000ull + (unsigned)ncg - 1) / (unsigned)(ncg > 0 ? ncg : 1));
-            for (int t = tid; t < nblk; t += NT) {
-                const int g = ncg == 1 ? t : (int)__umulhi((unsigned)t, magicc);
-                const int h = t - g * ncg;
-                const int il0 = g_grp[g], jl0 = g_cgrp[h];
-                const bool two_r = g_grp[g + 1] - il0 > 1, two_c = g_cgrp[h + 1] - jl0 > 1;
-                const int lr = g_lr[il0], lc = g_lc[jl0];
-                // |distance| and inside-the-support mask (1 / 0) of the two rows [r][row tap b] and the two columns [q][column
-                // tap a]; a single's second member reads its neighbour's entries (computed, never stored)
-                float ax[2][2], mx[2][2], ay[2][2], my[2][2];
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        const float x = g_dr[(il0 + r) * 2 + b];
-                        ax[r][b] = __builtin_fabsf(x);
-                        mx[r][b] = s3::dist_class_f(x) != 0 ? 1.0f : 0.0f;
-                    }
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-#pragma unroll
-                    for (int a = 0; a < 2; ++a) {
-                        const float y = g_dc[(jl0 + q) * 2 + a];
-                        ay[q][a] = __builtin_fabsf(y);
-                        my[q][a] = s3::dist_class_f(y) != 0 ? 1.0f : 0.0f;
-                    }
-                const uint32_t* dp = Dt + lr * D::HP + lc * CH;
-                uint8_t* ob = outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
-                float dist[4 * CH];                                  // [c][r][q]
-                float dmax = 0.0f;
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    float v[4], fy[2][4], fx[2][4];
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) {
-                            const uint32_t d = dp[b * D::HP + a * CH + c];
-                            v[a * 2 + b] = (float)(d >> 24);
-                            const float alpha = s3::lin_alpha_u8((float)(d & 0xFFu), ms255);
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) fy[q][a * 2 + b] = s3::lin_factor_abs(alpha, ay[q][a], my[q][a]);
-#pragma unroll
-                            for (int r = 0; r < 2; ++r) fx[r][a * 2 + b] = s3::lin_factor_abs(alpha, ax[r][b], mx[r][b]);
-                        }
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            float e[4];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) e[k] = fx[r][k] * fy[q][k];
-                            const float xf = s3::finish<false, 4, true, true, true>(e, v);
-                            const float rr = __builtin_rintf(xf);
-                            const bool have = (r == 0 || two_r) && (q == 0 || two_c);
-                            const float ds = have ? xf - rr : 0.0f;
-                            dist[(c * 2 + r) * 2 + q] = ds;
-                            dmax = __builtin_fmaxf(dmax, __builtin_fabsf(ds));
-                            if (have) ob[r * D::OUT_PITCH + q * CH + c] = (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(rr, 0u, 0u);
-                        }
-                }
-                if (dmax > 0.5f - s3::kTieEps && F.dis_r64 != nullptr) {
-                    unsigned tiemask = 0;
-#pragma unroll
-                    for (int q = 0; q < 4 * CH; ++q)
-                        if (__builtin_fabsf(dist[q]) > 0.5f - s3::kTieEps) tiemask |= 1u << q;
-                    while (tiemask != 0) {                                 // one round per queued output of the lane, not per output
-                        const int q = __builtin_ctz(tiemask);
-                        tiemask &= tiemask - 1;
-                        const int c = q >> 2, r = (q >> 1) & 1, qq = q & 1;
-                        const int il = il0 + r, xc = (jl0 + qq) * CH + c;
-                        const int slot = atomicAdd(tq_count, 1);
-                        if (slot < P.tq_cap) {
-                            tq[slot] = ((uint32_t)il << 16) | (uint32_t)xc;
-                            continue;
-                        }
-                        uint32_t dd[4];
-                        double dx64[2], dy64[2];
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) dx64[b] = F.dis_r64[(int64_t)(i0 + il) * 2 + b];
-#pragma unroll
-                        for (int a = 0; a < 2; ++a) dy64[a] = F.dis_c64[(int64_t)(j0 + jl0 + qq) * 2 + a];
-#pragma unroll
-                        for (int a = 0; a < 2; ++a)
-#pragma unroll
-                            for (int b = 0; b < 2; ++b) dd[a * 2 + b] = dp[b * D::HP + a * CH + c];
-                        outt[il * D::OUT_PITCH + ophase + xc] = (uint8_t)s3::resolve_u8<false, 2>(dd, dx64, dy64, P.max_sigma);
-                    }
-                }
-            }
-            }
-        };
-        // the LDS image of the output block -> the frame: whole 16-byte chunks with streaming stores, the ragged ends of a
-        // row (the neighbouring tiles' bytes share those chunks) dword by dword and byte by byte
-        auto flush_blocks = [&]() {
-            typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-            const int nchunk = (ophase + ncolc + 15) >> 4;
-            const unsigned magicf = (unsigned)((0x100000000ull + (unsigned)nchunk - 1) / (unsigned)nchunk);
-            uint8_t* gbase = seg0 - ophase;
-            const int total = nrow * nchunk;
-            const int full_lo = ophase == 0 ? 0 : 1, full_hi = ((ophase + ncolc) & 15) == 0 ? nchunk : nchunk - 1;   // whole chunks of a row
-            for (int i = tid; i < total; i += NT) {
-                const int row = nchunk == 1 ? i : (int)__umulhi((unsigned)i, magicf);
-                const int ch = i - row * nchunk;
-                if (ch >= full_lo && ch < full_hi) {
-                    const v4u x = *reinterpret_cast<const v4u*>(outt + row * D::OUT_PITCH + ch * 16);
-                    uint8_t* dst = gbase + row * rowpitch + ch * 16;
-                    // streaming stores for the 64-byte lines this tile writes completely; the first and the last line of a row
-                    // are shared with the neighbouring tiles and go through the L2 (regular stores), which merges the two
-                    // tiles' halves into one line -- as streaming stores they were two partial-line writes each (+67 MB per step)
-                    const uintptr_t line = reinterpret_cast<uintptr_t>(dst) & ~(uintptr_t)63;
-                    const uintptr_t r0 = reinterpret_cast<uintptr_t>(gbase + row * rowpitch) + (uintptr_t)ophase;
-                    if (line >= r0 && line + 64 <= r0 + (uintptr_t)ncolc) __builtin_nontemporal_store(x, reinterpret_cast<v4u*>(dst));
-                    else *reinterpret_cast<v4u*>(dst) = x;
-                }
-            }
-            // the ragged chunks, two per row at most, in a loop of their own (a few waves take it once, instead of every
-            // wave dragging the byte path through every round of the loop above)
-            for (int i = tid; i < 2 * nrow; i += NT) {
-                const int row = i >> 1;
-                const int ch = (i & 1) ? nchunk - 1 : 0;
-                if (ch >= full_lo && ch < full_hi) continue;             // that end of the row is a whole chunk
-                if ((i & 1) && nchunk == 1) continue;                    // a one-chunk row: its first-chunk lane has it
-                const uint8_t* src = outt + row * D::OUT_PITCH + ch * 16;
-                uint8_t* dst = gbase + row * rowpitch + ch * 16;
-                const int lo = max(ophase - ch * 16, 0), hi = min(ophase + ncolc - ch * 16, 16);
-                const v4u x = *reinterpret_cast<const v4u*>(src);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t w = x[k];
-                    if (lo <= 4 * k && hi >= 4 * k + 4) {
-                        *reinterpret_cast<uint32_t*>(dst + 4 * k) = w;
-                    } else {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (4 * k + u >= lo && 4 * k + u < hi) dst[4 * k + u] = (uint8_t)(w >> (8 * u));
-                    }
-                }
-            }
-        };
-        // the constant-size variants cover the integer scale factors (x2 -> 2 rows per group, ...); anything else reads
-        // the group size per task
-        constexpr bool WIDE = KIND == LERF_KIND_GAUSS && S == 2;      // x3 / x4 variants where the registers allow
-        // (max_sigma <= s3::kNoShiftMaxSigma here: the host sends larger values to the float64 direct kernel, lerf_fused.hip)
-        if (quad) run_quads();
-        else if (blk_uni) run_blocks(std::true_type{});
-        else if (blk) run_blocks(std::false_type{});
-        else if (blkl) run_blocks_lin();
-        else if (gsame == 2) run_tasks(std::integral_constant<int, 2>{});
-        else if (WIDE && gsame == 3) run_tasks(std::integral_constant<int, WIDE ? 3 : 0>{});
-        else if (WIDE && gsame == 4) run_tasks(std::integral_constant<int, WIDE ? 4 : 0>{});
-        else run_tasks(std::integral_constant<int, 0>{});
-        // ---- tie pass: the queued outputs in float64, one per lane; each patches its byte behind the task loop's
-        //      dword stores (drained and fenced by the barrier)
-        if (blk || blkl) {
-            // block tasks: the queued outputs are patched in the LDS image, which then leaves in one piece
-            __syncthreads();
-            LERF_STAMP(15);
-            if (F.dis_r64 != nullptr) {
-                const int nq = min(*tq_count, P.tq_cap);
-                if (nq > 0) {
-                    for (int i = tid; i < nq; i += NT) {
-                        const uint32_t e = tq[i];
-                        const int il = (int)(e >> 16), xc = (int)(e & 0xFFFFu);
-                        const int jl = xc / CH;
-                        const int c = xc - jl * CH;
-                        const int lr = g_lr[il], lc = g_lc[jl];
-                        uint32_t dd[SS];
-                        double dx64[S], dy64[S];
-#pragma unroll
-                        for (int b = 0; b < S; ++b) dx64[b] = F.dis_r64[(int64_t)(i0 + il) * S + b];
-#pragma unroll
-                        for (int a = 0; a < S; ++a) dy64[a] = F.dis_c64[(int64_t)(j0 + jl) * S + a];
-#pragma unroll
-                        for (int a = 0; a < S; ++a)
-#pragma unroll
-                            for (int b = 0; b < S; ++b) dd[a * S + b] = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
-                        outt[il * D::OUT_PITCH + ophase + xc] = (uint8_t)s3::resolve_u8<KIND == LERF_KIND_GAUSS, S>(dd, dx64, dy64, P.max_sigma);
-                    }
-                    __syncthreads();
-                }
-            }
-            flush_blocks();
-        } else if (F.dis_r64 != nullptr) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            const int nq = min(*tq_count, P.tq_cap);
-            for (int i = tid; i < nq; i += NT) {
-                const uint32_t e = tq[i];
-                const int il = (int)(e >> 16), xc = (int)(e & 0xFFFFu);
-                const int jl = xc / CH;
-                const int c = xc - jl * CH;
-                const int lr = g_lr[il], lc = g_lc[jl];
-                uint32_t dd[SS];
-                double dx64[S], dy64[S];
-#pragma unroll
-                for (int b = 0; b < S; ++b) dx64[b] = F.dis_r64[(int64_t)(i0 + il) * S + b];
-#pragma unroll
-                for (int a = 0; a < S; ++a) dy64[a] = F.dis_c64[(int64_t)(j0 + jl) * S + a];
-#pragma unroll
-                for (int a = 0; a < S; ++a)
-#pragma unroll
-                    for (int b = 0; b < S; ++b) dd[a * S + b] = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
-                seg0[il * rowpitch + xc] = (uint8_t)s3::resolve_u8<KIND == LERF_KIND_GAUSS, S>(dd, dx64, dy64, P.max_sigma);
-            }
-        }
+    // ---- stage 3: the row-group table and the census of the tile's rows and columns, then the cheapest task form they allow
+    //      (all forms give the same bytes), then the outputs the float32 path could not decide
+    stage3_census(X, ctl, tid);
+    __syncthreads();
+    X.read_census(ctl);
+    const bool image_ok = X.rows_align && (X.rowpitch & 15) == 0 && X.nrow <= D::OUT_ROWS && X.ophase + X.ncolc <= D::OUT_PITCH;
+    const bool blk = X3::BLK && image_ok && X.rcode != 0 && X.ccode != 0;
+    // interior tiles: pairs from row 0 / column 0 on, even counts -- no validity tests; tiles at the frame's edges: a leading
+    // and / or trailing single row or column, handled as a pair whose other member is not stored
+    const bool blk_uni = blk && X.rcode == 1 && X.ccode == 1 && ((X.nrow | X.ncol) & 1) == 0;
+    const bool quad = X3::QUADS && blk_uni && __builtin_amdgcn_readfirstlane(ctl[CTL_CSTEP]) != 0 && __builtin_amdgcn_readfirstlane(ctl[CTL_RSTEP]) != 0 &&
+                      ((X.nrow >> 1) % X3::QRP) == 0 && ((X.ncol >> 1) % X3::QCP) == 0;
+    const bool blkl = X3::BLKL && __builtin_amdgcn_readfirstlane((image_ok && X.lin_ok) ? 1 : 0) != 0;
+    // the constant-size variants of the dword-column tasks cover the integer scale factors (x2 -> 2 rows per group, ...);
+    // anything else reads the group size per task
+    constexpr bool WIDE = KIND == LERF_KIND_GAUSS && S == 2;      // x3 / x4 variants where the registers allow
+    // (max_sigma <= s3::kNoShiftMaxSigma here: the host sends larger values to the float64 direct kernel, lerf_fused.hip)
+    if (quad) stage3_quads(X, P, tid);
+    else if (blk_uni) stage3_blocks<true>(X, P, tid);
+    else if (blk) stage3_blocks<false>(X, P, tid);
+    else if (blkl) stage3_blocks_lin(X, P, ctl, tid);      // (ctl: it reads CTL_NCGRP itself -- read for every tile it cost SGPR spills, profiles/stage3_calls_resources.txt)
+    else if (X.gsame == 2) stage3_tasks<2>(X, P, tid);
+    else if (WIDE && X.gsame == 3) stage3_tasks<WIDE ? 3 : 0>(X, P, tid);
+    else if (WIDE && X.gsame == 4) stage3_tasks<WIDE ? 4 : 0>(X, P, tid);
+    else stage3_tasks<0>(X, P, tid);
+    if (blk || blkl) {
+        // block tasks: the queued outputs are patched in the LDS image, which then leaves in one piece
+        stage3_ties<true>(X, P, tid);
+        flush_blocks(X, tid);
+    } else {
+        stage3_ties<false>(X, P, tid);
     }
 #ifdef LERF_STAMPS
     __syncthreads();

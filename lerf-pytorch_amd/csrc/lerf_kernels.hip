@@ -202,13 +202,9 @@ resize_kernel(const TI* __restrict__ feat, int64_t fy, int64_t fx, int64_t fc,
         constexpr bool U8P = sizeof(TH) == 1 && sizeof(TO) == 1;
         const float xf = s3::finish<KIND == LERF_KIND_GAUSS, MAXS * MAXS, sizeof(TO) == 1, U8P, U8P>(e, v);
         if (sizeof(TH) == 1 && sizeof(TO) == 1 && dis_r64 != nullptr && s3::near_tie(xf)) {
-            double dx64[MAXS], dy64[MAXS];
-#pragma unroll
-            for (int b = 0; b < MAXS; ++b) dx64[b] = dis_r64[i * S + b];
-#pragma unroll
-            for (int a = 0; a < MAXS; ++a) dy64[a] = dis_c64[j * S + a];
-            Storer<TO>::put(out + i * oy + j * ox + c * oc,
-                            (float)s3::resolve_u8<KIND == LERF_KIND_GAUSS, MAXS>(dd, dx64, dy64, (float)max_sigma));
+            const uint8_t r8 = s3::resolve_taps_u8<KIND == LERF_KIND_GAUSS, MAXS>([&](int a, int b) __attribute__((always_inline)) { return dd[a * MAXS + b]; },
+                                                                                   dis_r64 + i * S, dis_c64 + j * S, (float)max_sigma);
+            Storer<TO>::put(out + i * oy + j * ox + c * oc, (float)r8);
             return;
         }
         Storer<TO>::put(out + i * oy + j * ox + c * oc, xf);
@@ -325,12 +321,7 @@ resize_cells_u8_kernel(const uint8_t* __restrict__ feat, int fy, int fx, int fc,
     auto put = [&](int i, int j, float xf) {
         uint8_t r;
         if (dis_r64 != nullptr && s3::near_tie(xf)) {
-            double dx64[S], dy64[S];
-#pragma unroll
-            for (int b = 0; b < S; ++b) dx64[b] = dis_r64[i * S + b];
-#pragma unroll
-            for (int a = 0; a < S; ++a) dy64[a] = dis_c64[j * S + a];
-            r = s3::resolve_u8<GAUSS, S>(dd, dx64, dy64, max_sigma);
+            r = s3::resolve_taps_u8<GAUSS, S>([&](int a, int b) __attribute__((always_inline)) { return dd[a * S + b]; }, dis_r64 + i * S, dis_c64 + j * S, max_sigma);
         } else {
             r = s3::to_u8(xf);
         }

@@ -260,6 +260,46 @@ __device__ __forceinline__ f2 pk_add(f2 a, f2 b) {
     return d;
 }
 
+// One tap of the block tasks of the fused kernel (LeRF-G): a block is the 2 x 2 outputs of a row pair and a column pair that
+// share their taps.  Packed over the two COLUMNS q of the block (lane x = column 0, lane y = column 1); the scalars of the tap
+// (its value, m2rho, k1, k2) sit in the low halves of register pairs and are read through op_sel.  The same operations in
+// the same order as the scalar path (gauss_t_u8, gauss_form_cols, finish): the same bytes.
+struct BlockTap {
+    f2 V, K1, K2, M2;
+    __device__ __forceinline__ explicit BlockTap(uint32_t d) {          // d = hq0 | hq1 << 8 | hq2 << 16 | value << 24
+        V.x = V.y = (float)(d >> 24);                                   // (both lanes: the weights' consumers below are plain vector code)
+        K1.x = (float)((d >> 8) & 0xFFu);
+        M2.x = gauss_m2rho_u8((float)(d & 0xFFu));
+        K2.x = (float)((d >> 16) & 0xFFu);
+    }
+    // the column-only terms, DY = the column pair's distances to this tap's column: p0 = m2rho * ty, ty2 = ty^2
+    __device__ __forceinline__ void cols(f2 DY, f2& P0, f2& TY2) const {
+        const f2 TYV = pk_mul_blo(DY, K2);                              // k2 * dy[q]
+        P0 = pk_mul_blo(TYV, M2);
+        TY2 = pk_mul(TYV, TYV);
+    }
+    // the row-only product, DX = the row pair's distances to this tap's row (lanes = ROWS here): k1 * dx[r]
+    __device__ __forceinline__ f2 rows(f2 DX) const { return pk_mul_blo(DX, K1); }
+    // e[r][q] = fma(tx_r, p0_q, fma(tx_r, tx_r, ty2_q)), w = exp2(-e), num[r] += w v, den[r] += w; `first`: the sums start here
+    __device__ __forceinline__ void sum(f2 TX, f2 P0, f2 TY2, bool first, f2 (&NUM)[2], f2 (&DEN)[2]) const {
+        const f2 E0 = pk_fma_ab<false>(TX, P0, pk_fma_aa<false>(TX, TY2));
+        const f2 E1 = pk_fma_ab<true>(TX, P0, pk_fma_aa<true>(TX, TY2));
+        f2 W0, W1;
+        W0.x = __builtin_amdgcn_exp2f(-E0.x); W0.y = __builtin_amdgcn_exp2f(-E0.y);
+        W1.x = __builtin_amdgcn_exp2f(-E1.x); W1.y = __builtin_amdgcn_exp2f(-E1.y);
+        // The consumers of the v_exp results are COMPILER-generated packed operations, not inline assembly: gfx950 needs a
+        // wait state between a transcendental instruction and a VALU read of its result, which the compiler inserts for its
+        // own instructions only (an inline-asm consumer right behind v_exp read the stale register: nondeterministic bytes).
+        if (first) {
+            DEN[0] = W0; DEN[1] = W1;
+            NUM[0] = W0 * V; NUM[1] = W1 * V;
+        } else {
+            NUM[0] = __builtin_elementwise_fma(W0, V, NUM[0]); NUM[1] = __builtin_elementwise_fma(W1, V, NUM[1]);
+            DEN[0] = DEN[0] + W0; DEN[1] = DEN[1] + W1;
+        }
+    }
+};
+
 // ---------------------------------------------------------------------------
 // Tie guard for uint8 outputs.  The float32 result can differ from the reference's float64 result
 // by up to ~1e-4 (0..255 scale), which flips clip(round(.)) only when the value sits that close to a
@@ -402,6 +442,24 @@ __device__ __forceinline__ uint8_t resolve_u8(const uint32_t (&d)[S * S], const 
             return (uint8_t)(int)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
     }
     return to_u8_d(eval64<GAUSS, S>(d, dx, dy, max_sigma));
+}
+
+// resolve_u8 behind its gather, the one form every SR kernel calls: tap(a, b) = the tie word of the output's tap (column
+// offset a, row offset b); dx64 / dy64 = the output's S entries of the float64 row / column distance tables
+template <bool GAUSS, int S, typename Tap>
+__device__ __forceinline__ uint8_t resolve_taps_u8(Tap tap, const double* __restrict__ dx64, const double* __restrict__ dy64,
+                                                   float max_sigma) {
+    uint32_t d[S * S];
+    double dx[S], dy[S];
+#pragma unroll
+    for (int b = 0; b < S; ++b) dx[b] = dx64[b];
+#pragma unroll
+    for (int a = 0; a < S; ++a) dy[a] = dy64[a];
+#pragma unroll
+    for (int a = 0; a < S; ++a)
+#pragma unroll
+        for (int b = 0; b < S; ++b) d[a * S + b] = tap(a, b);
+    return resolve_u8<GAUSS, S>(d, dx, dy, max_sigma);
 }
 
 // clip(np.round(v), 0, 255).astype(uint8)  (eval_lut_sr.py:663-665); NaN -> 0

@@ -133,6 +133,62 @@ def test_tie_queue_full_falls_back_in_loop(torch, co, eng_g, eng_g4, eng_l, luts
     assert eng_g.sr_geometry((540, 960), 2).struct.tie_queue_cap == 0          # the engine's cached geometry is untouched
 
 
+_COLUMN_TASK_CASES = {                     # name -> (engine fixture, scale, support, linear): tiles that run the dword-column tasks
+    "g-s2-x3": ("eng_g", 3, 2, False),     # row groups of three: gsame = 3
+    "g-s2-x2.4": ("eng_g", 2.4, 2, False), # groups of 2, 3, 2, 2, 3: the per-group size
+    "g-s4-x3": ("eng_g4", 3, 4, False),    # 4 x 4 support, tie bits instead of distances
+    "l-x3": ("eng_l", 3, 2, True),         # groups of three: the LeRF-L block tasks decline
+}
+
+
+@pytest.fixture(scope="module")
+def column_task_refs(co, luts_g, luts_l):
+    """the 70 x 80 noise frame of the column-task cases and, per case, the oracle's bytes and its count of outputs within
+    1.5e-4 of a rounding tie (float64 stage 3 on the oracle's stage outputs) among the outputs that tile (0, 0) of a launch
+    with 64-row tiles owns: those whose first tap, by the library's own axis tables, lies above row and left of column
+    64 - S / 2 (the bound of the kernel's ownership search)"""
+    from lerf_pytorch_amd import _lib
+    img = np.random.default_rng(77).integers(0, 256, (70, 80, 3), dtype=np.uint8)
+    refs = {}
+    for name, (_, s, S, linear) in _COLUMN_TASK_CASES.items():
+        luts = luts_l if linear else luts_g
+        feat, hq = co.lut_stages(img, luts, 1 if linear else 3)
+        x = co.resize(feat, hq, s, s, S=S, max_sigma=1.0 if linear else 10.0, kind="linear" if linear else "gauss")
+        left_r = _lib.sr_axis_tables(70, x.shape[0], s, S)[0]
+        left_c = _lib.sr_axis_tables(80, x.shape[1], s, S)[0]
+        owned = (np.abs(x - np.rint(x)) > 0.5 - 1.5e-4)[left_r < 64 - S // 2][:, left_c < 64 - S // 2]
+        near = int(owned.sum())
+        refs[name] = (co.sr_u8(img, luts, s, s, S=S, linear=linear).copy(), near)
+    return img, refs
+
+
+@pytest.mark.parametrize("cap", [0, 8, None])
+@pytest.mark.parametrize("name", list(_COLUMN_TASK_CASES))
+def test_tie_queue_full_on_column_tasks(request, torch, column_task_refs, name, cap):
+    """The dword-column tasks (scales whose row groups are not pairs) with the tie queue lowered to 0 / 8 entries: every
+    undecided output past the capacity is resolved on the spot, inside the task loop, and patched into the packed dword
+    before it is stored.  The launch is forced onto 64-row tiles (by default a 70 x 80 frame takes the 16-row instances, whose
+    tiles hold a handful of near ties each): tile (0, 0) then owns 191 x 191 (152 x 152 at x2.4) outputs and more undecided
+    ones than the queue holds -- counted on the CPU over exactly those outputs: 25 / 20 / 24 / 19 for the four cases, asserted
+    to be at least 9 -- so at cap = 8 both the queue and the on-the-spot branch run in one tile; cap = None is the shipped
+    capacity.  Bytes equal the oracle's on every route."""
+    from lerf_pytorch_amd import _lib, ops
+    img, refs = column_task_refs
+    eng = request.getfixturevalue(_COLUMN_TASK_CASES[name][0])
+    scale = _COLUMN_TASK_CASES[name][1]
+    ref, near = refs[name]
+    print("%s: %d outputs of tile (0, 0) within 1.5e-4 of a tie" % (name, near))
+    assert near >= 9, "the input no longer overflows a queue of 8 in tile (0, 0)"
+    geo = eng.sr_geometry((70, 80), scale).with_flags(_lib.GEO_TILE_ROWS_64)
+    assert geo.struct.flags & _lib.GEO_TILE_ROWS_64
+    if cap is not None:
+        geo = geo.with_tie_queue_cap(cap)
+        assert geo.struct.flags & _lib.GEO_TILE_ROWS_64
+        assert geo.struct.tie_queue_cap == (-1 if cap == 0 else cap)
+    out = ops.sr_fused_u8(torch.from_numpy(img).cuda(), eng.luts, geo, eng.kind, eng.max_sigma).cpu().numpy()
+    _bytes_equal(out, ref, "%s, tie queue of %s" % (name, cap))
+
+
 def test_repeated_launches_give_the_same_bytes(torch, eng_g, eng_g4, eng_l):
     """the same launch three times: a kernel that reads a register before its producer has finished (round 3: an inline-asm
     consumer right behind v_exp_f32, which the compiler's hazard recogniser cannot see) gives the right bytes on a fresh box

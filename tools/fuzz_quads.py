@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised sizes at the integer x2 scale with the 4 x 4 support: the quad tasks of stage 3 (round 5: 2 x 2 neighbouring blocks per
-task on interior tiles; lerf_fused_impl.h run_quads) vs the C port of the oracle, bytes.  Sizes around the tile grid of all three
+task on interior tiles; lerf_fused_impl.h stage3_quads) vs the C port of the oracle, bytes.  Sizes around the tile grid of all three
 tile heights (64 / 32 / 16 rows), batches of 1..3 frames; S = 2 rides along (single blocks).   usage: fuzz_quads.py [n_cases] [seed]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
