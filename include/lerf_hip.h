@@ -1042,6 +1042,61 @@ int lerf_coords_invert_bwd_batched_host(const void* f, int f_dtype, int64_t f_ro
                                         int n_sets, int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride,
                                         int64_t grad_f_set_stride);
 
+/* Forward warp by summation splatting (the rounding order of every statement: the top of csrc/lerf_splat_point.h).
+ * Every pixel of a source image is ADDED into an output frame at the position a forward map gives it -- the scatter that remap's
+ * gather is the adjoint of, and the differentiable counterpart of lerf_coords_invert_raster's hard depth test.
+ * Operands, for set s < n_sets (a single call is n_sets = 1, where the set strides are not used):
+ *   x     [n_sets][C][H][W] of `dtype` T (LERF_F32 or LERF_F64), dense NCHW, set s at x + s * x_set_stride elements
+ *   f     the forward map [H][W][2] of f_dtype (LERF_F32, promoted exactly, or LERF_F64) under the strided map contract (f_row_stride even,
+ *         >= 2 * W, entry-aligned); f[i][j] = (r, c) is the position in the [oH][oW] output frame at which source pixel (i, j) lands
+ *         (lerf_coords_invert_raster reads f the same way).  f_set_stride even; 0 = ONE map shared by every set
+ *   m     [n_sets][H][W] of T, a weight per source pixel, or NULL: every weight is 1
+ *   acc   [n_sets][C + with_norm][oH][oW] of T, dense; with_norm (0 / 1) adds the plane C that gathers the weights themselves
+ * Forward, per source pixel, in float64:
+ *   r or c not finite (NaN, +-inf): the pixel contributes nothing and forms no address -- "no target", the mirror of remap's "no source"
+ *   i0 = floor(r), tr = r - i0, wr = {1 - tr, tr}; the columns alike.  Taps (i0 + a, j0 + b), a, b in {0, 1}, in the order (0,0) (0,1)
+ *   (1,0) (1,1), each with w = wr[a] * wc[b]; a tap with wr[a] == 0 or wc[b] == 0 is skipped (an integer position touches ONE pixel,
+ *   r = oH - 1 is inside the frame); a tap outside [0, oH) x [0, oW) is DROPPED, NOT CLIPPED: mass that leaves the frame is lost.  floor
+ *   and the frame test run in floating point BEFORE any conversion to int: 1e300 forms no address and overflows nothing.
+ *   acc[s][k][q] += round_T((w * m) * x_k) for k < C, and acc[s][C][q] += round_T(w * m) with the norm plane.
+ *   acc is ACCUMULATED INTO (lerf_remap_bwd's contract): the caller zeroes it, and consecutive calls splat several frames into one
+ *   canvas.  Device: one thread per source pixel, one no-return atomic add of T per tap and plane (a hardware float add for both
+ *   dtypes on gfx950), so two runs are equal up to the rounding of a reordered sum in T; the host twin adds in row-major source order.
+ * lerf_splat_bwd, the adjoint, takes g [n_sets][C + with_norm][oH][oW] of T (the upstream of acc).  S(q) = sum_k x_k g[k][q] + g[C][q]
+ * (without the last term when with_norm == 0); S and g read as 0 at a dropped tap.  Per source pixel, ONE writer, a fixed tap order:
+ *   grad_x[k][i][j] = m * sum_taps w g[k][q]                                     [n_sets][C][H][W] of T
+ *   grad_m[i][j]    = sum_taps w S(q)                                            [n_sets][H][W] of T
+ *   grad_f[i][j].r  = m * sum_b wc[b] (S(i0 + 1, j0 + b) - S(i0, j0 + b)),  .c the transposed statement      float64 [n_sets][H][W][2] dense
+ * grad_f is the derivative of the cell that floor picked: ONE-SIDED (towards +) at an integer position.  A source pixel whose position
+ * is not finite gets exact zeros in all three, whatever g holds.  The three are STORED, rounded once at the store (no accumulation, no
+ * atomics: a pure gather), so the device equals lerf_splat_bwd_host bit for bit and two runs agree.  Each may be NULL to skip that half; all three
+ * NULL is refused.  A map shared by the batch (f_set_stride 0) still has one grad_f per set: the caller sums them.
+ * Both: caller-owned buffers, no allocation, no sync, one launch on `stream`.  Refused with LERF_EINVAL before anything is written: a null
+ * required pointer, a pointer not aligned to its element (f: to its entry), a dtype code that is not LERF_F32 / LERF_F64, an odd or short
+ * row stride, C < 1, H, W, oH or oW < 1, H > 262140 (the grid's y), with_norm not 0 / 1, n_sets outside 1 .. 65535, a set stride that is
+ * negative, odd (f, grad_f) or, for n_sets > 1, shorter than a set's extent (f alone may be 0), acc intersecting x, m or f, and any
+ * gradient intersecting x, f, m, g or another gradient (over the whole batch). */
+int lerf_splat(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride,
+               const void* f, int f_dtype, int64_t f_row_stride, int64_t f_set_stride,
+               const void* m, int64_t m_set_stride,
+               void* acc, int with_norm, int oH, int oW, int64_t acc_set_stride, int n_sets, void* stream);
+int lerf_splat_host(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride,
+                    const void* f, int f_dtype, int64_t f_row_stride, int64_t f_set_stride,
+                    const void* m, int64_t m_set_stride,
+                    void* acc, int with_norm, int oH, int oW, int64_t acc_set_stride, int n_sets);
+int lerf_splat_bwd(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride,
+                   const void* f, int f_dtype, int64_t f_row_stride, int64_t f_set_stride,
+                   const void* m, int64_t m_set_stride,
+                   const void* g, int with_norm, int oH, int oW, int64_t g_set_stride,
+                   void* grad_x, int64_t grad_x_set_stride, void* grad_m, int64_t grad_m_set_stride,
+                   double* grad_f, int64_t grad_f_set_stride, int n_sets, void* stream);
+int lerf_splat_bwd_host(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride,
+                        const void* f, int f_dtype, int64_t f_row_stride, int64_t f_set_stride,
+                        const void* m, int64_t m_set_stride,
+                        const void* g, int with_norm, int oH, int oW, int64_t g_set_stride,
+                        void* grad_x, int64_t grad_x_set_stride, void* grad_m, int64_t grad_m_set_stride,
+                        double* grad_f, int64_t grad_f_set_stride, int n_sets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,7 @@ EXPORTS = [
     "lerf_coords_compose_bwd_batched", "lerf_coords_compose_bwd_batched_host", "lerf_coords_invert_bwd_batched", "lerf_coords_invert_bwd_batched_host",
     "lerf_coords_reproject", "lerf_coords_reproject_host", "lerf_coords_reproject_bwd_workspace_bytes", "lerf_coords_reproject_bwd",
     "lerf_coords_reproject_bwd_host",
+    "lerf_splat", "lerf_splat_host", "lerf_splat_bwd", "lerf_splat_bwd_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -346,6 +347,11 @@ def lib():
     L.lerf_coords_reproject_bwd_host.argtypes = _reproject_bwd
     L.lerf_coords_reproject_bwd_workspace_bytes.restype = C.c_size_t
     L.lerf_coords_reproject_bwd_workspace_bytes.argtypes = [C.c_int] * 3
+    _splat_in = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+    _splat = _splat_in + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int]
+    _splat_bwd = _splat_in + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_void_p, C.c_int64] * 3 + [C.c_int]
+    L.lerf_splat.argtypes, L.lerf_splat_host.argtypes = _splat + [C.c_void_p], _splat
+    L.lerf_splat_bwd.argtypes, L.lerf_splat_bwd_host.argtypes = _splat_bwd + [C.c_void_p], _splat_bwd
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -817,6 +823,70 @@ def coords_reproject_bwd_on(X, kind, params, depth, grad_map, grad_depth_out, gr
     return gd, gp
 
 
+def _splat_operands(X, what, src, fmap, weight):
+    """(x, map, row stride, set stride, weight, B, C, (H, W), the call's leading arguments): src [C, H, W] or [B, C, H, W] float32 /
+    float64, map [H, W, 2] (shared by the batch) or [B, H, W, 2], weight None or src's dtype [H, W] / [B, H, W]; B = 0 for the single form"""
+    if not X.is_array(src) or not X.is_float(src) or src.ndim not in (3, 4) or min(src.shape) < 1:
+        raise ValueError("%s: src must be float32 or float64 %s [C, H, W] or [B, C, H, W]" % (what, X.noun))
+    x = X.contiguous(src)
+    B = x.shape[0] if x.ndim == 4 else 0
+    Cn, H, W = (int(v) for v in x.shape[-3:])
+    f, sf, tf, Bf = X.batch(fmap, "map")
+    if tuple(f.shape[-3:-1]) != (H, W) or (Bf and Bf != B):
+        raise ValueError("%s: map must be [%d, %d, 2], one per sample or one for the batch" % (what, H, W))
+    X.one_device(what, ("src", "map", "weight"), x, f, weight)
+    m = None
+    if weight is not None:
+        if not X.is_array(weight) or weight.dtype != x.dtype or tuple(weight.shape) != ((B,) if B else ()) + (H, W):
+            raise ValueError("%s: weight must be src's dtype, %s" % (what, list(((B,) if B else ()) + (H, W))))
+        m = X.contiguous(weight)
+    head = (X.ptr(x), X.code(x), Cn, H, W, Cn * H * W if B > 1 else 0, *X.operand(f, sf), tf if B > 1 else 0, X.ptr(m), H * W if B > 1 else 0)
+    return x, f, m, B, Cn, (H, W), head
+
+
+def splat_on(X, src, fmap, out_hw, weight=None, norm=False, acc=None):
+    """lerf_splat / lerf_splat_host: ADD src into acc [.., C (+ 1 with norm), oH, oW] along the forward map; acc None: a zeroed one"""
+    what = "lerf_splat" + X.suffix
+    x, f, m, B, Cn, hw, head = _splat_operands(X, what, src, fmap, weight)
+    oH, oW = int(out_hw[0]), int(out_hw[1])
+    if oH < 1 or oW < 1:
+        raise ValueError("%s: out_hw must be positive" % what)
+    planes = Cn + (1 if norm else 0)
+    shape = ((B,) if B else ()) + (planes, oH, oW)
+    if acc is None:
+        acc = X.new(shape, x.dtype, X.device(x), zero=True)
+    else:
+        acc = X.dense(acc, shape, x.dtype, X.device(x), what + ": acc")
+    X.call(what, x, *head, X.ptr(acc), int(bool(norm)), oH, oW, planes * oH * oW if B > 1 else 0, max(B, 1))
+    return acc
+
+
+def splat_bwd_on(X, src, fmap, grad, weight=None, norm=False, need=(True, True, True)):
+    """lerf_splat_bwd / lerf_splat_bwd_host: the adjoint of splat_on at grad [.., C (+ 1), oH, oW] (src's dtype, contiguous) ->
+    (grad_src, grad_weight, grad_map): new buffers, None for a half that need[k] skips; grad_map float64 of the map's shape (a map
+    shared by a batch: the sum over the samples)"""
+    what = "lerf_splat_bwd" + X.suffix
+    x, f, m, B, Cn, hw, head = _splat_operands(X, what, src, fmap, weight)
+    planes, lead, dev = Cn + (1 if norm else 0), ((B,) if B else ()), X.device(x)
+    if not X.is_array(grad) or grad.ndim != x.ndim or tuple(grad.shape[:-2]) != lead + (planes,) or min(grad.shape) < 1:
+        raise ValueError("%s: grad must be %s ... [%d, oH, oW]" % (what, X.noun, planes))
+    oH, oW = int(grad.shape[-2]), int(grad.shape[-1])
+    g = X.dense(grad, lead + (planes, oH, oW), x.dtype, dev, what + ": grad")
+    if not any(need):
+        raise ValueError("%s: at least one of the three gradients is needed" % what)
+    if need[1] and m is None:
+        raise ValueError("%s: the weight's gradient needs a weight" % what)
+    gx = X.new(tuple(x.shape), x.dtype, dev) if need[0] else None
+    gm = X.new(lead + hw, x.dtype, dev) if need[1] else None
+    gf = X.new(lead + hw + (2,), X.f64, dev) if need[2] else None
+    n = hw[0] * hw[1]
+    X.call(what, x, *head, X.ptr(g), int(bool(norm)), oH, oW, planes * oH * oW if B > 1 else 0, X.ptr(gx), Cn * n if B > 1 else 0, X.ptr(gm),
+           n if B > 1 else 0, X.ptr(gf), 2 * n if B > 1 else 0, max(B, 1))
+    if gf is not None and B and f.ndim == 3:
+        gf = gf.sum(0)
+    return gx, gm, gf
+
+
 def coords_math_on(X, op, x, y):
     what = "lerf_coords_math" + X.suffix
     if op not in COORDS_MATH_OPS:
@@ -920,6 +990,20 @@ def coords_reproject_bwd_host(kind, params, depth, grad_map, grad_depth_out=None
     params' shape); None: zeroed ones; need[k] False skips that half and returns None for it -> (grad_depth, grad_params).  The sums
     run in the device's order: bit-equal to ops.coords_reproject_bwd."""
     return coords_reproject_bwd_on(_HOST, kind, params, depth, grad_map, grad_depth_out, grad_depth, grad_params, need, origin)
+
+
+def splat_host(src, map, out_hw, weight=None, norm=False, acc=None):
+    """lerf_splat_host: the forward warp by summation splatting on the host, by the row-major loop over the kernel's own statements
+    (csrc/lerf_splat_point.h).  src [C, H, W] or [B, C, H, W] float32 / float64; map [H, W, 2] (shared) or [B, H, W, 2], float32 / float64,
+    map[i, j] = the (row, col) in the out_hw frame at which source pixel (i, j) lands; weight None or src's dtype [H, W] / [B, H, W]
+    -> acc [.., C (+ 1 with norm: the plane of the weights), oH, oW] of src's dtype.  acc given: ACCUMULATED INTO and returned."""
+    return splat_on(_HOST, src, map, out_hw, weight, norm, acc)
+
+
+def splat_bwd_host(src, map, grad, weight=None, norm=False, need=(True, True, True)):
+    """lerf_splat_bwd_host: the adjoint of splat_host at grad [.., C (+ 1), oH, oW] -> (grad_src, grad_weight, grad_map), bit-equal to
+    ops.splat_bwd; need[k] False skips that half (None); grad_map is float64"""
+    return splat_bwd_on(_HOST, src, map, grad, weight, norm, need)
 
 
 def coords_math_host(op, x, y=None):

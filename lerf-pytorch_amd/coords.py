@@ -41,6 +41,12 @@ depth there comes back too, the plane invert_raster's depth test reads.  Two cha
 
 reproject_torch (with reproject_params_torch) is the differentiable twin: depth, K_src, K_dst, R and t receive gradients through
 lerf_coords_reproject_bwd -- float64, a fixed summation order, an entry that is not valid contributes nothing.
+
+splat is FORWARD warping by summation splatting (lerf_splat): every source pixel is added into the target frame at the
+position a forward map gives it, with a normalisation plane for the modes "average", "linear" and "softmax"; splat_torch is the
+differentiable twin (lerf_splat_bwd: image, weight and map), the third chain beside reproject's two:
+    m, z = reproject_torch(depth_src, K_src, K_dst, R, t, return_depth=True)
+    splat_torch(img_src, m, hw, weight=-beta * z, mode="softmax")             forward, soft: the source's own depth, differentiable
 """
 from __future__ import annotations
 
@@ -1021,3 +1027,164 @@ def reproject_torch(depth, K_src, K_dst, R=None, t=None, inverse_depth=False, dt
     if torch.is_grad_enabled() and (depth.requires_grad or params.requires_grad):
         return _reproject_fn().apply(depth, params, kind, tdt, bool(return_depth))
     return ops.coords_reproject(kind, params.detach().contiguous(), depth.detach(), dtype=tdt, depth_out=True if return_depth else None)
+
+
+# ---------------------------------------------------------------------------------------------- forward warp by splatting
+SPLAT_MODES = ("sum", "average", "linear", "softmax")
+
+
+def _splat_args(what, src, map, out_hw, weight, mode):
+    if mode not in SPLAT_MODES:
+        raise ValueError("%s: mode is one of %s, not %r" % (what, ", ".join(SPLAT_MODES), mode))
+    if mode == "average" and weight is not None:
+        raise ValueError("%s: mode 'average' takes no weight (every pixel counts 1); 'linear' weighs" % what)
+    if mode in ("linear", "softmax") and weight is None:
+        raise ValueError("%s: mode %r needs a weight" % (what, mode))
+    if getattr(src, "ndim", None) not in (3, 4) or min(src.shape) < 1:
+        raise ValueError("%s: src is [C, H, W] or [B, C, H, W]" % what)
+    lead, hw = tuple(src.shape[:-3]), tuple(src.shape[-2:])
+    if getattr(map, "ndim", None) not in (3, 4) or tuple(map.shape[-3:]) != hw + (2,) or (map.ndim == 4 and tuple(map.shape[:1]) != lead):
+        raise ValueError("%s: map is [H, W, 2] (shared by the batch) or [B, H, W, 2], H and W the source's" % what)
+    if weight is not None and tuple(getattr(weight, "shape", ())) != lead + hw:
+        raise ValueError("%s: weight is [H, W], or [B, H, W] beside a batch" % what)
+    oH, oW = int(out_hw[0]), int(out_hw[1])
+    if oH < 1 or oW < 1:
+        raise ValueError("%s: out_hw must be positive" % what)
+    return oH, oW
+
+
+def splat(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False):
+    """Forward warp by SUMMATION SPLATTING (lerf_splat): every pixel of src [C, H, W] (or a batch [B, C, H, W]) is ADDED
+    into the frame out_hw = (oH, oW) at the position map[i, j] = (row, col) gives it -- map [H, W, 2], shared by the batch, or
+    [B, H, W, 2]; invert_raster reads a forward map the same way -- spread bilinearly over up to four pixels.  Mass that leaves the frame
+    is lost (a tap outside is dropped, not clipped); an entry that is not finite contributes nothing (NaN: "no target").  Where
+    invert_raster + remap lets the nearest surface win by a hard test, this sums, and a normalisation plane divides:
+
+        mode        what it returns
+        "sum"       the accumulator; weight (src's dtype, [H, W] or [B, H, W]) multiplies every pixel if given
+        "average"   weight must be None:  acc / (norm + eps),  norm = the splatted ones
+        "linear"    the same quotient with weight as the importance:  splat(weight * src) / (splat(weight) + eps)
+        "softmax"   the same with m = exp(weight - max over the sample) as the importance.  The shift cancels in the quotient (up to
+                    eps); it keeps exp in range.  weight = -beta * z with z from reproject(..., return_depth=True) is the soft depth
+                    test: the nearer surface dominates by exp(-beta * dz).  A NaN weight counts as -inf (m = 0): reproject's z is NaN
+                    exactly where its map is.
+
+    return_norm=True -> (out, norm) with norm [oH, oW] (or [B, oH, oW]) the splatted importance; norm == 0 is the hole mask.
+    numpy operands -> numpy (the kernel's host twin, row-major order); device tensors -> device tensors written by the kernel (float
+    atomic adds: equal from run to run up to the rounding of a reordered sum).  Mixed operands are refused.  The quotient and the exp
+    are elementwise array / tensor operations.  float32 / float64 src decides the dtype; the map may be either.  No autograd: an
+    operand that requires grad (with grad mode on) is refused -- splat_torch is the differentiable twin."""
+    oH, oW = _splat_args("splat", src, map, out_hw, weight, mode)
+    ops_ = [t for t in (src, map, weight) if t is not None]
+    dev = [bool(getattr(t, "is_cuda", False)) for t in ops_]
+    if any(d != dev[0] for d in dev):
+        raise ValueError("splat: src, map and weight on the host or all on one device, not mixed")
+    _no_autograd("splat", ops_)
+    norm = mode != "sum" or bool(return_norm)
+    if dev[0]:
+        import torch
+        from . import ops
+        x = src.detach()
+        x = x if x.dtype in (torch.float32, torch.float64) else x.double()
+        f = map.detach()
+        f = f if f.dtype in (torch.float32, torch.float64) else f.double()
+        w = None if weight is None else weight.detach().to(x.dtype)
+        if mode == "softmax":
+            w = _softmax_importance_torch(w)
+        acc = ops.splat(x, f, (oH, oW), w, norm)
+    else:
+        from . import _lib
+        x, f, w = (None if t is None else np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (src, map, weight))
+        x = x if x.dtype in (np.float32, np.float64) else x.astype(np.float64)
+        f = f if f.dtype in (np.float32, np.float64) else f.astype(np.float64)
+        w = None if w is None else w.astype(x.dtype, copy=False)
+        if mode == "softmax":
+            w = np.where(np.isnan(w), -np.inf, w)
+            top = w.max(axis=(-2, -1), keepdims=True)
+            w = np.exp(w - np.where(np.isfinite(top), top, 0)).astype(x.dtype, copy=False)
+        acc = _lib.splat_host(x, f, (oH, oW), w, norm)
+    C = x.shape[-3]
+    out = acc[..., :C, :, :]
+    if mode != "sum":
+        out = out / (acc[..., C:, :, :] + eps)
+    return (out, acc[..., C, :, :]) if return_norm else out
+
+
+def _softmax_importance_torch(w):
+    """exp(w - max over the sample); a NaN counts as -inf; in torch ops, so autograd carries it (the max is a constant: it cancels)"""
+    import torch
+    w = torch.where(torch.isnan(w), torch.full_like(w, float("-inf")), w)
+    top = w.detach().amax(dim=(-2, -1), keepdim=True)
+    return torch.exp(w - torch.where(torch.isfinite(top), top, torch.zeros_like(top)))
+
+
+_SPLAT_FN = None
+
+
+def _splat_fn():
+    global _SPLAT_FN
+    if _SPLAT_FN is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+        from . import ops
+
+        class _SplatFn(torch.autograd.Function):
+            """acc = ops.splat(src, map, weight); backward: ops.splat_bwd, the halves that are not required skipped; the map's
+            gradient (float64) cast to the map's dtype"""
+
+            @staticmethod
+            def forward(ctx, src, weight, map, hw, norm):
+                x, f = src.detach().contiguous(), map.detach()
+                m = None if weight is None else weight.detach().contiguous()
+                ctx.save_for_backward(x, f, *(() if m is None else (m,)))
+                ctx.hw, ctx.norm, ctx.map_dtype = hw, norm, map.dtype
+                return ops.splat(x, f, hw, m, norm)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                x, f = ctx.saved_tensors[:2]
+                m = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+                need = (ctx.needs_input_grad[0], m is not None and ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+                if not any(need):
+                    return None, None, None, None, None
+                gx, gm, gf = ops.splat_bwd(x, f, grad.contiguous().to(x.dtype), m, ctx.norm, need)
+                return gx, gm, None if gf is None else gf.to(ctx.map_dtype), None, None
+
+        _SPLAT_FN = _SplatFn
+    return _SPLAT_FN
+
+
+def splat_torch(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False):
+    """splat on the operands' device, differentiable: src [C, H, W] or [B, C, H, W], map [H, W, 2] or [B, H, W, 2] and weight ([H, W] or
+    [B, H, W], or None), all float32 / float64 DEVICE tensors (weight is cast to src's dtype) -> what splat returns.  src, weight and
+    map each receive a gradient when they require one, through lerf_splat_bwd -- a gather with one writer per source pixel, bit-equal
+    from run to run; a half that is not required is skipped.  The map's gradient is the derivative of the bilinear cell floor picked
+    (one-sided at integer positions); a non-finite entry gets exact zeros.  The modes are built from the one accumulator in torch ops,
+    so autograd carries the quotient and the exp.  The third chain beside reproject's two -- the source's own depth, differentiable:
+
+        m, z = reproject_torch(depth_src, K_src, K_dst, R, t, return_depth=True)
+        splat_torch(img_src, m, hw, weight=-beta * z, mode="softmax")
+
+    Once differentiable."""
+    import torch
+    oH, oW = _splat_args("splat_torch", src, map, out_hw, weight, mode)
+    for t, name in ((src, "src"), (map, "map"), (weight, "weight")):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.float32, torch.float64)):
+            raise ValueError("splat_torch: %s must be a float32 or float64 device tensor" % name)
+    if any(t is not None and t.device != src.device for t in (map, weight)):
+        raise ValueError("splat_torch: src, map and weight live on different devices")
+    w = None if weight is None else weight.to(src.dtype)
+    if mode == "softmax":
+        w = _softmax_importance_torch(w)
+    norm = mode != "sum" or bool(return_norm)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (src, map, w)):
+        acc = _splat_fn().apply(src, w, map, (oH, oW), norm)
+    else:
+        from . import ops
+        acc = ops.splat(src.detach(), map.detach(), (oH, oW), None if w is None else w.detach(), norm)
+    C = src.shape[-3]
+    out = acc[..., :C, :, :]
+    if mode != "sum":
+        out = out / (acc[..., C:, :, :] + eps)
+    return (out, acc[..., C, :, :]) if return_norm else out

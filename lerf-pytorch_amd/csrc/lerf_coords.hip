@@ -4,8 +4,8 @@
 // not from a math library).
 //
 // ONE TEXT FOR DEVICE AND HOST.  Every one-thread-per-entry operation is a small functor op(i, j, s) -- entry (i, j) of set s -- that
-// holds its operands by value (BuildOp, BuildDevOp, ReprojectOp, MeshOp, ComposeOp, InvertOp, ComposeBwdOp, InvertBwdOp; the notes on loads,
-// stores and atomics are with each).  Two runners with one call shape execute it:
+// holds its operands by value (BuildOp, BuildDevOp, ReprojectOp, MeshOp, ComposeOp, InvertOp, ComposeBwdOp, InvertBwdOp, SplatOp, SplatBwdOp; the
+// notes on loads, stores and atomics are with each).  Two runners with one call shape execute it:
 //   OnDevice{stream}   launches entry_kernel<OP>: block 64 x 4 (4 waves, one row of 64 entries each, so a wave's stores are 64
 //                      consecutive entries of a row), grid (ceil(oW / 64), ceil(oH / 4), sets), the (i, j) guard, blockIdx.z = the set
 //   OnHost{}           the plain s, i, j loop over host pointers
@@ -17,7 +17,7 @@
 // with one runner or the other, and lerf_coords_X / lerf_coords_X_host call those with n_sets = 1 and set strides 0, so the device and
 // the host twin, the single map and the batch cannot drift apart: they agree bit for bit by construction (the two float scatters
 // excepted, below).  THE ARGUMENT CHECKS are one operand table per call (Operand, Pair, check_call, after the kernels):
-// an entry point lists its operands, its scalar rules and the pairs that must not intersect ONCE, and one function judges them.  Add2 is the one float scatter: two float64 atomicAdd where compiled for the device, a plain add on the host.
+// an entry point lists its operands, its scalar rules and the pairs that must not intersect ONCE, and one function judges them.  Add2 is the float scatter of the map adjoints: two float64 atomicAdd where compiled for the device, a plain add on the host; AddPlane is the same pattern for one plane of an image (the forward warp, lerf_splat; its arithmetic is lerf_splat_point.h).
 // MapReader is the one strided-map reader handed to the *_point functions; a dense float64 gradient [h][w][2] is a map of row stride 2w.
 //
 // The rasterising inverse (lerf_coords_invert_raster) is three passes: KeyFillOp and ResolveOp are per-entry functors under the two
@@ -71,6 +71,7 @@
 // that may be shared), so set s ends before set s + 1 begins.
 #include "lerf_common.h"
 #include "lerf_coords_models.h"
+#include "lerf_splat_point.h"
 
 #include <cmath>
 #include <initializer_list>
@@ -305,6 +306,75 @@ struct ResolveOp {
     LERF_HD void operator()(int i, int j, int s) const {
         store_entry(out + set_offset(s, out_set), stride, i, j,
                     raster_resolve(keys[set_offset(s, keys_set) + (int64_t)i * oW + j], fW, (double)(i0 + i), (double)(j0 + j), F.set(s, f_set)));
+    }
+};
+
+// The forward warp by summation splatting (splat_point of lerf_splat_point.h): one call per SOURCE pixel (i, j) of set s -- ONE 8- or
+// 16-byte load of its map entry, one load of its weight when a weight plane is given, then the loop over the C (+ 1) planes INSIDE the
+// thread: one load of x_k (a wave reads 64 consecutive values of a row) and up to four adds through AddPlane, the Add2 pattern for one
+// plane of T: one no-return atomicAdd of T where compiled for the device, a plain add on the host.  The planes are outermost in
+// memory ([C + 1][oH][oW]), so for a smooth map the 64 lanes of a wave add, per tap and plane, into 64 neighbouring values of one row.
+// No LDS, no workspace.  Equal from run to run up to the rounding of a reordered sum in T.
+template <typename T>
+struct AddPlane {
+    T* acc;
+    int64_t plane;
+    LERF_HD void operator()(int k, int64_t q, double v) const {
+        T* p = acc + (int64_t)k * plane + q;
+        const T r = (T)v;                            // rounded once, here
+#ifdef __HIP_DEVICE_COMPILE__
+        atomicAdd(p, r);
+#else
+        *p = *p + r;
+#endif
+    }
+};
+
+template <typename T, typename TF>
+struct SplatOp {
+    const T* x;
+    MapReader<TF> F;
+    const T* m;
+    T* acc;
+    int C, W, oH, oW;
+    bool norm;
+    int64_t x_set, f_set, m_set, acc_set, in_plane, out_plane;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const int64_t e = (int64_t)i * W + j;
+        const T* xs = x + set_offset(s, x_set) + e;
+        const int64_t plane = in_plane;
+        splat_point(F.set(s, f_set)(i, j), m ? (double)m[set_offset(s, m_set) + e] : 1.0, C, norm, oH, oW,
+                    [xs, plane](int k) { return (double)xs[(int64_t)k * plane]; }, AddPlane<T>{acc + set_offset(s, acc_set), out_plane});
+    }
+};
+
+// the adjoint of the splat (splat_bwd_point): a GATHER -- per source pixel the same map entry and weight, per plane one load of x_k (when
+// grad_M or grad_F is wanted) and up to four loads of G at the taps, read through the caches like compose's taps; ONE writer per
+// source pixel and plain stores (a T per plane of grad_X, a T of grad_M, one 16-byte entry of grad_F), no atomics: bit-equal between device
+// and host and from run to run.  A null gradient pointer skips that half (wave-uniform).
+template <typename T, typename TF>
+struct SplatBwdOp {
+    const T* x;
+    MapReader<TF> F;
+    const T* m;
+    const T* g;
+    T* gx;
+    T* gm;
+    double* gf;
+    int C, W, oH, oW;
+    bool norm;
+    int64_t x_set, f_set, m_set, g_set, gx_set, gm_set, gf_set, in_plane, out_plane;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const int64_t e = (int64_t)i * W + j, iplane = in_plane, oplane = out_plane;
+        const T* xs = x + set_offset(s, x_set) + e;
+        const T* gs = g + set_offset(s, g_set);
+        T* gxs = gx ? gx + set_offset(s, gx_set) + e : nullptr;
+        const SplatGrad d = splat_bwd_point(F.set(s, f_set)(i, j), m ? (double)m[set_offset(s, m_set) + e] : 1.0, C, norm, oH, oW, gx != nullptr,
+                                            gm != nullptr, gf != nullptr, [xs, iplane](int k) { return (double)xs[(int64_t)k * iplane]; },
+                                            [gs, oplane](int k, int64_t q) { return (double)gs[(int64_t)k * oplane + q]; },
+                                            [gxs, iplane](int k, double v) { gxs[(int64_t)k * iplane] = (T)v; });
+        if (gm) gm[set_offset(s, gm_set) + e] = (T)d.m;
+        if (gf) store_entry(gf + set_offset(s, gf_set), 2 * (int64_t)W, i, j, d.f);
     }
 };
 
@@ -872,6 +942,54 @@ inline int reproject_bwd_args(int kind, const double* params, int n_sets, const 
                       depth_kind(kind) && float_dtype(depth_dtype) && tile_ok(oH, oW, i0, j0) && (grad_depth || grad_params) && ws_fits, LERF_EINVAL);
 }
 
+// `planes` dense planes [h][w] of scalars of `el` bytes, one behind the other (an NCHW image, the accumulator, their gradients)
+inline Operand planes_operand(const void* p, size_t el, int planes, int h, int w, int64_t set_stride, unsigned flags = 0) {
+    return {p, el, el, (int64_t)planes * h * w, set_stride, false, (flags & SHARE) != 0, (flags & OPTIONAL) != 0, true, true};
+}
+
+inline bool splat_dims(int dtype, int C, int H, int W, int oH, int oW) {
+    return float_dtype(dtype) && C >= 1 && C < 0x7fffffff && H >= 1 && W >= 1 && tile_ok(H, W, 0, 0) && oH >= 1 && oW >= 1;      // the grid is the SOURCE's
+}
+
+// the forward warp: x [n_sets][C][H][W], f the map of the SOURCE frame [H][W], m [n_sets][H][W] or null, acc [n_sets][C + norm][oH][oW]
+template <typename RUN>
+int splat(RUN run, const void* x, int dtype, int C, int H, int W, int64_t x_set, const void* f, int f_dtype, int64_t f_stride, int64_t f_set,
+          const void* m, int64_t m_set, void* acc, int with_norm, int oH, int oW, int64_t acc_set, int n_sets) {
+    enum { X, F, M, ACC };
+    const size_t el = depth_bytes(dtype);
+    const int rc = check_call(n_sets,
+                              {planes_operand(x, el, C, H, W, x_set), map_operand(f, f_dtype, f_stride, H, W, f_set, SHARE),
+                               planes_operand(m, el, 1, H, W, m_set, OPTIONAL), planes_operand(acc, el, C + (with_norm ? 1 : 0), oH, oW, acc_set)},
+                              {{ACC, X}, {ACC, M}, {ACC, F}}, splat_dims(dtype, C, H, W, oH, oW) && (with_norm == 0 || with_norm == 1), LERF_EINVAL);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(dtype, T, LERF_COORDS_DT(f_dtype, TF,
+        return run(SplatOp<T, TF>{(const T*)x, {(const TF*)f, f_stride}, (const T*)m, (T*)acc, C, W, oH, oW, with_norm != 0, x_set, f_set, m_set,
+                                  acc_set, (int64_t)H * W, (int64_t)oH * oW},
+                   H, W, n_sets)));
+}
+
+// its adjoint: g [n_sets][C + norm][oH][oW]; grad_x like x, grad_m like m (dtype T), grad_f float64 [n_sets][H][W][2]; each may be null
+template <typename RUN>
+int splat_bwd(RUN run, const void* x, int dtype, int C, int H, int W, int64_t x_set, const void* f, int f_dtype, int64_t f_stride,
+              int64_t f_set, const void* m, int64_t m_set, const void* g, int with_norm, int oH, int oW, int64_t g_set, void* grad_x,
+              int64_t gx_set, void* grad_m, int64_t gm_set, double* grad_f, int64_t gf_set, int n_sets) {
+    enum { X, F, M, G, GX, GM, GF };
+    const size_t el = depth_bytes(dtype);
+    const int rc = check_call(n_sets,
+                              {planes_operand(x, el, C, H, W, x_set), map_operand(f, f_dtype, f_stride, H, W, f_set, SHARE),
+                               planes_operand(m, el, 1, H, W, m_set, OPTIONAL), planes_operand(g, el, C + (with_norm ? 1 : 0), oH, oW, g_set),
+                               planes_operand(grad_x, el, C, H, W, gx_set, OPTIONAL), planes_operand(grad_m, el, 1, H, W, gm_set, OPTIONAL),
+                               dense_operand(grad_f, LERF_F64, H, W, gf_set, OPTIONAL)},
+                              {{GX, X}, {GX, F}, {GX, M}, {GX, G}, {GM, X}, {GM, F}, {GM, M}, {GM, G}, {GF, X}, {GF, F}, {GF, M}, {GF, G},
+                               {GX, GM}, {GX, GF}, {GM, GF}},
+                              splat_dims(dtype, C, H, W, oH, oW) && (with_norm == 0 || with_norm == 1) && (grad_x || grad_m || grad_f), LERF_EINVAL);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(dtype, T, LERF_COORDS_DT(f_dtype, TF,
+        return run(SplatBwdOp<T, TF>{(const T*)x, {(const TF*)f, f_stride}, (const T*)m, (const T*)g, (T*)grad_x, (T*)grad_m, grad_f, C, W, oH, oW,
+                                     with_norm != 0, x_set, f_set, m_set, g_set, gx_set, gm_set, gf_set, (int64_t)H * W, (int64_t)oH * oW},
+                   H, W, n_sets)));
+}
+
 // The fixed-order sum of the build backward and of the reproject backward on the host, lane by lane: the device's bands, trees and two
 // passes (the top of lerf_coords_models.h).  entry(s, i, j, dp) fills dp[n_params] of one entry; grad_params == nullptr: every entry is
 // visited once and nothing is summed.
@@ -1256,6 +1374,36 @@ int lerf_coords_reproject_bwd_host(int kind, const double* params, int n_sets, c
             if (grad_depth) grad_depth[pe] = grad_depth[pe] + dd;
         })));
     return LERF_OK;
+}
+
+int lerf_splat(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride, const void* f, int f_dtype, int64_t f_row_stride,
+               int64_t f_set_stride, const void* m, int64_t m_set_stride, void* acc, int with_norm, int oH, int oW, int64_t acc_set_stride,
+               int n_sets, void* stream) {
+    return splat(OnDevice{(hipStream_t)stream}, x, dtype, C, H, W, x_set_stride, f, f_dtype, f_row_stride, f_set_stride, m, m_set_stride, acc,
+                 with_norm, oH, oW, acc_set_stride, n_sets);
+}
+
+int lerf_splat_host(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride, const void* f, int f_dtype, int64_t f_row_stride,
+                    int64_t f_set_stride, const void* m, int64_t m_set_stride, void* acc, int with_norm, int oH, int oW,
+                    int64_t acc_set_stride, int n_sets) {
+    return splat(OnHost{}, x, dtype, C, H, W, x_set_stride, f, f_dtype, f_row_stride, f_set_stride, m, m_set_stride, acc, with_norm, oH, oW,
+                 acc_set_stride, n_sets);
+}
+
+int lerf_splat_bwd(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride, const void* f, int f_dtype, int64_t f_row_stride,
+                   int64_t f_set_stride, const void* m, int64_t m_set_stride, const void* g, int with_norm, int oH, int oW,
+                   int64_t g_set_stride, void* grad_x, int64_t grad_x_set_stride, void* grad_m, int64_t grad_m_set_stride, double* grad_f,
+                   int64_t grad_f_set_stride, int n_sets, void* stream) {
+    return splat_bwd(OnDevice{(hipStream_t)stream}, x, dtype, C, H, W, x_set_stride, f, f_dtype, f_row_stride, f_set_stride, m, m_set_stride, g,
+                     with_norm, oH, oW, g_set_stride, grad_x, grad_x_set_stride, grad_m, grad_m_set_stride, grad_f, grad_f_set_stride, n_sets);
+}
+
+int lerf_splat_bwd_host(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride, const void* f, int f_dtype, int64_t f_row_stride,
+                        int64_t f_set_stride, const void* m, int64_t m_set_stride, const void* g, int with_norm, int oH, int oW,
+                        int64_t g_set_stride, void* grad_x, int64_t grad_x_set_stride, void* grad_m, int64_t grad_m_set_stride,
+                        double* grad_f, int64_t grad_f_set_stride, int n_sets) {
+    return splat_bwd(OnHost{}, x, dtype, C, H, W, x_set_stride, f, f_dtype, f_row_stride, f_set_stride, m, m_set_stride, g, with_norm, oH, oW,
+                     g_set_stride, grad_x, grad_x_set_stride, grad_m, grad_m_set_stride, grad_f, grad_f_set_stride, n_sets);
 }
 
 }  // extern "C"

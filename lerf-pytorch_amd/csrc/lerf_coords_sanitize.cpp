@@ -9,6 +9,9 @@
 // non-zero origins and shared operands, and must equal the single-map twins set by set (batched_ops).
 // lerf_coords_reproject_host and lerf_coords_reproject_bwd_host (reproject_ops) run three sets of both kinds and both depth dtypes into a
 // strided out at a non-zero origin, depth_out and each gradient half null and given, special depths, and their refusals.
+// lerf_splat_host and lerf_splat_bwd_host (splat_ops) run one and three sets of both image dtypes and both map dtypes, C = 1 and 3, with and
+// without the norm plane and the weight, a shared and a per-set strided map with NaN, +-inf, 1e300 and frame-edge entries, each gradient
+// half null and given, and their refusals.
 // It needs no GPU and is never loaded into another process.  Exit status 0 and "ok" on the last line: no report.
 #include "lerf_hip.h"
 
@@ -422,6 +425,83 @@ static void reproject_ops(int oH, int oW) {
     reproject_ops_of<double>(oH, oW, LERF_F64);
 }
 
+// the forward warp by splatting and its adjoint (lerf_splat_host, lerf_splat_bwd_host): sources [H][W] into a frame [oH][oW] unequal to
+// it, C = 1 and 3, with and without the norm plane and the weight, both image dtypes and both map dtypes, one set and three sets with a
+// per-set and a shared strided map, exactly-sized heap buffers; the map holds NaN, +-inf, 1e300, -0.5, oH - 1 exactly, oH - 0.5 and
+// positions beyond every edge of the frame; each null half of the backward; then the refusals
+template <typename T>
+static void splat_ops_of(int H, int W, int oH, int oW, int dt) {
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int N = 3;
+    const size_t n = (size_t)H * W, on = (size_t)oH * oW;
+    const double special[12][2] = {{nan, 3.0}, {2.0, nan}, {inf, 1.0}, {1.0, -inf}, {1e300, 2.0}, {2.0, -1e300}, {-0.5, 1.25}, {oH - 1.0, 0.5},
+                                   {oH - 0.5, 2.0}, {1.5, oW - 0.5}, {oH - 1.0, oW - 1.0}, {-1.0, (double)oW}};
+    for (int tf : {LERF_F32, LERF_F64})
+        for (int C : {1, 3})
+            for (int norm : {0, 1}) {
+                Batch F(tf, N, H, W);
+                for (int s = 0; s < N; ++s)
+                    for (int i = 0; i < H; ++i)
+                        for (int j = 0; j < W; ++j) {
+                            const int k = i * W + j + s;
+                            if (k % 5 == 0 && (k / 5) % 16 < 12) F.set_entry(s, i, j, special[(k / 5) % 16][0], special[(k / 5) % 16][1]);
+                            else F.set_entry(s, i, j, (i + 0.37) * (oH + 2.0) / H - 1.5 + 0.7 * std::sin(0.31 * j + s), (j + 0.61) * (oW + 3.0) / W - 2.0);
+                        }
+                const int P = C + norm;
+                std::vector<T> x(N * C * n), m(N * n), acc(N * P * on, (T)0), g(N * P * on), gx(N * C * n, (T)-7), gm(N * n, (T)-7);
+                std::vector<double> gf(N * 2 * n, -7.0);
+                for (size_t k = 0; k < x.size(); ++k) x[k] = (T)std::sin(0.37 * (double)k);
+                for (size_t k = 0; k < m.size(); ++k) m[k] = (T)(1.0 + 0.5 * std::cos(0.21 * (double)k));
+                for (size_t k = 0; k < g.size(); ++k) g[k] = k % 29 == 9 ? (T)nan : (T)std::cos(0.13 * (double)k);
+                const int64_t xs = (int64_t)(C * n), ms = (int64_t)n, as = (int64_t)(P * on), gfs = (int64_t)(2 * n);
+                for (const T* mp : {(const T*)nullptr, (const T*)m.data()})
+                    for (int64_t fset : {F.set, (int64_t)0}) {
+                        EXPECT(lerf_splat_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, fset, mp, ms, acc.data(), norm, oH, oW, as, N) == LERF_OK);
+                        EXPECT(lerf_splat_host(x.data(), dt, C, H, W, 0, F.p(1), tf, F.stride, 0, mp, 0, acc.data(), norm, oH, oW, 0, 1) == LERF_OK);
+                        EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, fset, mp, ms, g.data(), norm, oH, oW, as, gx.data(), xs,
+                                                   gm.data(), ms, gf.data(), gfs, N) == LERF_OK);
+                        EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, fset, mp, ms, g.data(), norm, oH, oW, as, nullptr, 0,
+                                                   gm.data(), ms, gf.data(), gfs, N) == LERF_OK);
+                        EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, fset, mp, ms, g.data(), norm, oH, oW, as, gx.data(), xs,
+                                                   nullptr, 0, gf.data(), gfs, N) == LERF_OK);
+                        EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, fset, mp, ms, g.data(), norm, oH, oW, as, gx.data(), xs,
+                                                   gm.data(), ms, nullptr, 0, N) == LERF_OK);
+                        EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, 0, F.p(2), tf, F.stride, 0, mp, 0, g.data(), norm, oH, oW, 0, gx.data(), 0, nullptr, 0,
+                                                   nullptr, 0, 1) == LERF_OK);
+                    }
+                EXPECT(F.gaps_kept());
+                EXPECT(gx[0] != (T)-7 && gm[0] == (T)0 && gf[0] == 0.0 && gf[1] == 0.0);      // entry (0, 0) of set 0 is (NaN, 3): exact zeros under a g with NaNs
+                // the refusals write nothing
+                const std::vector<T> acc0 = acc, gx0 = gx, gm0 = gm;
+                const std::vector<double> gf0 = gf;
+                EXPECT(lerf_splat_host(nullptr, dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, acc.data(), norm, oH, oW, as, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_host(x.data(), 0, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, acc.data(), norm, oH, oW, as, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_host(x.data(), dt, 0, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, acc.data(), norm, oH, oW, as, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride + 1, F.set, m.data(), ms, acc.data(), norm, oH, oW, as, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, acc.data(), norm, 0, oW, as, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, acc.data(), norm, oH, oW, as - 1, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, (void*)x.data(), norm, oH, oW, as, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, acc.data(), norm, oH, oW, as, 0) == LERF_EINVAL);
+                EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, g.data(), norm, oH, oW, as, nullptr, 0, nullptr, 0,
+                                           nullptr, 0, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, nullptr, norm, oH, oW, as, gx.data(), xs, gm.data(),
+                                           ms, gf.data(), gfs, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, g.data(), norm, oH, oW, as, (void*)x.data(), xs,
+                                           gm.data(), ms, gf.data(), gfs, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, g.data(), norm, oH, oW, as, gx.data(), xs,
+                                           (void*)m.data(), ms, gf.data(), gfs, N) == LERF_EINVAL);
+                EXPECT(lerf_splat_bwd_host(x.data(), dt, C, H, W, xs, F.p(), tf, F.stride, F.set, m.data(), ms, g.data(), norm, oH, oW, as, gx.data(), xs,
+                                           gm.data(), ms, gf.data(), gfs - 2, N) == LERF_EINVAL);
+                EXPECT(!std::memcmp(acc.data(), acc0.data(), acc.size() * sizeof(T)) && !std::memcmp(gx.data(), gx0.data(), gx.size() * sizeof(T)) &&
+                       !std::memcmp(gm.data(), gm0.data(), gm.size() * sizeof(T)) && same(gf, gf0));
+            }
+}
+
+static void splat_ops(int H, int W, int oH, int oW) {
+    splat_ops_of<float>(H, W, oH, oW, LERF_F32);
+    splat_ops_of<double>(H, W, oH, oW, LERF_F64);
+}
+
 int main() {
     const double pi = 3.14159265358979323846;
     const double fish[17] = {1.0 / 35, 0, -27.5 / 35, 0, 1.0 / 33, -16.0 / 33, 0.001, -0.0005, 1, 61.5, 58.75, 25.25, 17.5, 0.05, -0.012, 0.004, -0.0009};
@@ -469,6 +549,10 @@ int main() {
     reproject_ops(2, 2);
     reproject_ops(5, 67);
     reproject_ops(70, 130);                                     // two bands x three column blocks of the adjoint's sums
+    splat_ops(1, 1, 1, 1);
+    splat_ops(1, 1, 5, 9);
+    splat_ops(5, 67, 7, 61);
+    splat_ops(23, 31, 29, 37);
     std::printf(fails ? "%d check(s) failed\n" : "ok\n", fails);
     return fails ? 1 : 0;
 }

@@ -1231,3 +1231,20 @@ def coords_reproject_bwd(kind, params, depth, grad_map, grad_depth_out=None, gra
     and equal to _lib.coords_reproject_bwd_host."""
     return _lib.coords_reproject_bwd_on(_lib.DeviceOperands(), kind, params, depth, grad_map, grad_depth_out, grad_depth, grad_params, need,
                                         origin)
+
+
+def splat(src, map, out_hw, weight=None, norm=False, acc=None):
+    """lerf_splat: the forward warp by summation splatting -- every pixel of src is ADDED into the out_hw frame at the position the
+    forward map gives it, bilinearly over up to four pixels; mass that leaves the frame is lost, a non-finite entry contributes nothing.
+    src [C, H, W] or [B, C, H, W] (device, float32 / float64); map [H, W, 2] (shared by the batch) or [B, H, W, 2], float32 / float64;
+    weight None or src's dtype [H, W] / [B, H, W] -> acc [.., C (+ 1 with norm: the plane of the weights), oH, oW] of src's dtype; acc
+    given: ACCUMULATED INTO (several frames into one canvas).  ONE launch on the current stream whatever B, no sync; one no-return float
+    atomic add per tap and plane, so two runs agree up to the rounding of a reordered sum (exactly, where every partial sum is exact)."""
+    return _lib.splat_on(_lib.DeviceOperands(), src, map, out_hw, weight, norm, acc)
+
+
+def splat_bwd(src, map, grad, weight=None, norm=False, need=(True, True, True)):
+    """lerf_splat_bwd: the adjoint of splat at grad [.., C (+ 1), oH, oW] (src's dtype) -> (grad_src, grad_weight, grad_map), None for a
+    half that need[k] skips; grad_map float64 of the map's shape.  A gather with one writer per source pixel: one launch, no atomics,
+    bit-equal from run to run and to _lib.splat_bwd_host."""
+    return _lib.splat_bwd_on(_lib.DeviceOperands(), src, map, grad, weight, norm, need)
