@@ -1097,6 +1097,93 @@ int lerf_splat_bwd_host(const void* x, int dtype, int C, int H, int W, int64_t x
                         void* grad_x, int64_t grad_x_set_stride, void* grad_m, int64_t grad_m_set_stride,
                         double* grad_f, int64_t grad_f_set_stride, int n_sets);
 
+/* The ORDERED scatter: a deterministic form of the three float scatters -- lerf_splat, the outer gradient of
+ * lerf_coords_compose_bwd, lerf_coords_invert_bwd.  Each _ordered entry point takes the arguments of its sibling plus a caller-owned
+ * workspace and max_adders, computes the same sums in the order of the HOST twin (entries in row-major order, the taps of an entry in
+ * the order (0,0) (0,1) (1,0) (1,1)) and so equals lerf_splat_host / lerf_coords_compose_bwd_host / lerf_coords_invert_bwd_host BIT
+ * FOR BIT, from run to run and with a pre-filled acc / grad (accumulated into, as ever).  Four passes on `stream` over the workspace:
+ * count the adders of every target element (integer atomics), an exclusive prefix sum of the counts, fill every target's list of
+ * entries, then one thread per target sorts its list and adds its terms -- recomputed from the operands by the sibling's own
+ * statements -- without atomics.  The inner gradient of compose (grad_b: one writer already) runs as in the sibling, in the same call.
+ *   An "entry" is one call of the operation: source pixel (i, j) of the splat ([H][W]), entry (i, j) of grad_out ([oH][oW]) for the two
+ *   adjoints; n_entries = their number per set.  A "target" is an element of the frame added into: [oH][oW] of acc, [aH][aW] of
+ *   grad_a, [fH][fW] of grad_f; n_targets = their number per set.
+ *   workspace   lerf_scatter_ordered_workspace_bytes(n_entries, n_targets, n_sets) bytes of device (host twin: host) memory, 4-byte
+ *               aligned, contents arbitrary on entry; in uint32 words: header [4], cursor [n_sets][n_targets], list [n_sets][4 n_entries],
+ *               scan partials [n_sets][P(n_targets)], P(n) = the sum of n_l = ceil(n_(l-1) / B) over the levels l >= 1 with
+ *               n_(l-1) > B, n_0 = n, B = lerf_scan_exclusive_u32_block().  0 from the size query for a size it does not serve.
+ *               After the call header word 1 (byte offset LERF_ORDERED_MAX_COUNT_OFFSET) holds the LARGEST number of adders any target
+ *               of the call has (0 when nothing was scattered); words 0, 2 and 3 are 0.
+ *   max_adders  the cap: a target with more adders than this is neither sorted nor summed -- every plane of it (both components of a
+ *               gradient entry) becomes NaN, which bounds the run time of its thread; every other target is exact.  The caller reads
+ *               the header word and refuses the result when it exceeds max_adders.
+ * No allocation, no sync.  Refused before anything is launched or written, the workspace included: everything the sibling refuses,
+ * and with LERF_EINVAL a null, misaligned or short workspace, a workspace intersecting any operand, max_adders < 1, and a target
+ * operand shared between sets (n_sets > 1 with grad_a_set_stride 0: two sets would be two writers of one element; acc and grad_f can
+ * never be shared).  4 * n_entries or n_targets beyond 2^32 - 1 is LERF_EUNSUPPORTED, judged before the pointers are looked at. */
+#define LERF_ORDERED_MAX_COUNT_OFFSET 4
+size_t lerf_scatter_ordered_workspace_bytes(int64_t n_entries, int64_t n_targets, int n_sets);
+int lerf_splat_ordered(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride,
+                       const void* f, int f_dtype, int64_t f_row_stride, int64_t f_set_stride,
+                       const void* m, int64_t m_set_stride,
+                       void* acc, int with_norm, int oH, int oW, int64_t acc_set_stride, int n_sets,
+                       void* workspace, size_t workspace_bytes, int max_adders, void* stream);
+int lerf_splat_ordered_host(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride,
+                            const void* f, int f_dtype, int64_t f_row_stride, int64_t f_set_stride,
+                            const void* m, int64_t m_set_stride,
+                            void* acc, int with_norm, int oH, int oW, int64_t acc_set_stride, int n_sets,
+                            void* workspace, size_t workspace_bytes, int max_adders);
+int lerf_coords_compose_bwd_ordered(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                    const void* b, int b_dtype, int64_t b_row_stride,
+                                    const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                    void* workspace, size_t workspace_bytes, int max_adders, void* stream);
+int lerf_coords_compose_bwd_ordered_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                         const void* b, int b_dtype, int64_t b_row_stride,
+                                         const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                         void* workspace, size_t workspace_bytes, int max_adders);
+int lerf_coords_compose_bwd_batched_ordered(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                            const void* b, int b_dtype, int64_t b_row_stride,
+                                            const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                            int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride,
+                                            int64_t grad_a_set_stride, int64_t grad_b_set_stride,
+                                            void* workspace, size_t workspace_bytes, int max_adders, void* stream);
+int lerf_coords_compose_bwd_batched_ordered_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
+                                                 const void* b, int b_dtype, int64_t b_row_stride,
+                                                 const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                                 int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride,
+                                                 int64_t grad_a_set_stride, int64_t grad_b_set_stride,
+                                                 void* workspace, size_t workspace_bytes, int max_adders);
+int lerf_coords_invert_bwd_ordered(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                   const void* g, int g_dtype, int64_t g_row_stride,
+                                   const double* grad_out, int oH, int oW, double* grad_f,
+                                   void* workspace, size_t workspace_bytes, int max_adders, void* stream);
+int lerf_coords_invert_bwd_ordered_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                        const void* g, int g_dtype, int64_t g_row_stride,
+                                        const double* grad_out, int oH, int oW, double* grad_f,
+                                        void* workspace, size_t workspace_bytes, int max_adders);
+int lerf_coords_invert_bwd_batched_ordered(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                           const void* g, int g_dtype, int64_t g_row_stride,
+                                           const double* grad_out, int oH, int oW, double* grad_f,
+                                           int n_sets, int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride,
+                                           int64_t grad_f_set_stride,
+                                           void* workspace, size_t workspace_bytes, int max_adders, void* stream);
+int lerf_coords_invert_bwd_batched_ordered_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW,
+                                                const void* g, int g_dtype, int64_t g_row_stride,
+                                                const double* grad_out, int oH, int oW, double* grad_f,
+                                                int n_sets, int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride,
+                                                int64_t grad_f_set_stride,
+                                                void* workspace, size_t workspace_bytes, int max_adders);
+
+/* The scan of pass 2 on its own: data [n] uint32 -> its exclusive prefix sums, in place, modulo 2^32.  Device: blocks of
+ * lerf_scan_exclusive_u32_block() elements scanned in LDS, the block sums scanned by the same kernels one level up, an add-back per
+ * level -- plain launches in stream order, no workgroup waits for another; workspace: lerf_scan_exclusive_u32_workspace_bytes(n)
+ * bytes of device memory (0, and then it may be NULL, when n fits one block).  No allocation, no sync.  LERF_EINVAL: a null or
+ * misaligned data, n < 1 or > 2^32 - 1, a needed workspace that is null, misaligned, short or intersects data. */
+int lerf_scan_exclusive_u32_block(void);
+size_t lerf_scan_exclusive_u32_workspace_bytes(int64_t n);
+int lerf_scan_exclusive_u32(uint32_t* data, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
+int lerf_scan_exclusive_u32_host(uint32_t* data, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,11 @@ EXPORTS = [
     "lerf_coords_reproject", "lerf_coords_reproject_host", "lerf_coords_reproject_bwd_workspace_bytes", "lerf_coords_reproject_bwd",
     "lerf_coords_reproject_bwd_host",
     "lerf_splat", "lerf_splat_host", "lerf_splat_bwd", "lerf_splat_bwd_host",
+    "lerf_scatter_ordered_workspace_bytes", "lerf_splat_ordered", "lerf_splat_ordered_host",
+    "lerf_coords_compose_bwd_ordered", "lerf_coords_compose_bwd_ordered_host", "lerf_coords_compose_bwd_batched_ordered",
+    "lerf_coords_compose_bwd_batched_ordered_host", "lerf_coords_invert_bwd_ordered", "lerf_coords_invert_bwd_ordered_host",
+    "lerf_coords_invert_bwd_batched_ordered", "lerf_coords_invert_bwd_batched_ordered_host",
+    "lerf_scan_exclusive_u32_block", "lerf_scan_exclusive_u32_workspace_bytes", "lerf_scan_exclusive_u32", "lerf_scan_exclusive_u32_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -352,6 +357,21 @@ def lib():
     _splat_bwd = _splat_in + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64] + [C.c_void_p, C.c_int64] * 3 + [C.c_int]
     L.lerf_splat.argtypes, L.lerf_splat_host.argtypes = _splat + [C.c_void_p], _splat
     L.lerf_splat_bwd.argtypes, L.lerf_splat_bwd_host.argtypes = _splat_bwd + [C.c_void_p], _splat_bwd
+    # the ordered scatter: the sibling's arguments, then workspace, workspace_bytes, max_adders (then the stream)
+    _ordered = [C.c_void_p, C.c_size_t, C.c_int]
+    L.lerf_scatter_ordered_workspace_bytes.restype = C.c_size_t
+    L.lerf_scatter_ordered_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int]
+    L.lerf_splat_ordered.argtypes, L.lerf_splat_ordered_host.argtypes = _splat + _ordered + [C.c_void_p], _splat + _ordered
+    for name, single, n_strides in (("compose_bwd", _compose_bwd, 5), ("invert_bwd", _invert_bwd, 4)):
+        batched = single + [C.c_int] + [C.c_int64] * n_strides
+        getattr(L, "lerf_coords_%s_ordered" % name).argtypes = single + _ordered + [C.c_void_p]
+        getattr(L, "lerf_coords_%s_ordered_host" % name).argtypes = single + _ordered
+        getattr(L, "lerf_coords_%s_batched_ordered" % name).argtypes = batched + _ordered + [C.c_void_p]
+        getattr(L, "lerf_coords_%s_batched_ordered_host" % name).argtypes = batched + _ordered
+    L.lerf_scan_exclusive_u32_workspace_bytes.restype = C.c_size_t
+    L.lerf_scan_exclusive_u32_workspace_bytes.argtypes = [C.c_int64]
+    L.lerf_scan_exclusive_u32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.lerf_scan_exclusive_u32_host.argtypes = [C.c_void_p, C.c_int64]
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -546,6 +566,62 @@ class _Operands:
     def operand(self, a, stride):
         return self.ptr(a), self.code(a), stride
 
+    def run_ordered(self, name, B, anchor, args, set_strides, n_entries, n_targets, max_adders):
+        """run() for the _ordered form of `name`: the same arguments, then a workspace of
+        lerf_scatter_ordered_workspace_bytes and the cap.  set_strides None: the entry point takes n_sets among its own arguments
+        (lerf_splat).  Afterwards the header's largest count is READ BACK -- one 4-byte copy, and on the device a synchronisation of the
+        stream -- and a count above max_adders raises LerfError: the elements over the cap hold NaN."""
+        max_adders = int(max_adders)
+        if max_adders < 1:
+            raise ValueError("%s_ordered: max_adders must be at least 1" % name)
+        n_sets = max(int(B), 1)
+        nbytes = int(lib().lerf_scatter_ordered_workspace_bytes(int(n_entries), int(n_targets), n_sets))
+        if not nbytes:
+            raise LerfError("%s_ordered: %d entries into %d targets are beyond the 32-bit ids of the ordered scatter" % (name, n_entries, n_targets))
+        ws = self.scratch(nbytes, self.device(anchor))
+        tail = (self.ptr(ws), nbytes, max_adders)
+        if set_strides is None:
+            self.call(name + "_ordered" + self.suffix, anchor, *args, *tail)
+        elif B:
+            self.call(name + "_batched_ordered" + self.suffix, anchor, *args, B, *[int(x) for x in set_strides], *tail)
+        else:
+            self.call(name + "_ordered" + self.suffix, anchor, *args, *tail)
+        most = self.max_count(ws)
+        if most > max_adders:
+            raise LerfError("%s_ordered: %d entries add into one element, more than max_adders = %d (that element holds NaN); raise "
+                            "max_adders or use the atomic path" % (name, most, max_adders))
+        return most
+
+
+ORDERED_MAX_COUNT_OFFSET = 4          # LERF_ORDERED_MAX_COUNT_OFFSET: the byte offset of the largest count in the workspace header
+
+
+def scan_block():
+    """the block length B of lerf_scan_exclusive_u32 (the seams of its levels lie at multiples of B and of B * B)"""
+    return int(lib().lerf_scan_exclusive_u32_block())
+
+
+def ordered_workspace_bytes(n_entries, n_targets, n_sets=1):
+    """lerf_scatter_ordered_workspace_bytes; its formula in Python is ordered_workspace_formula"""
+    return int(lib().lerf_scatter_ordered_workspace_bytes(int(n_entries), int(n_targets), int(n_sets)))
+
+
+def ordered_workspace_formula(n_entries, n_targets, n_sets=1):
+    """the documented layout in bytes: header [4], cursor [n_sets][n_targets], list [n_sets][4 n_entries], scan partials [n_sets][P]"""
+    B, n, P = scan_block(), int(n_targets), 0
+    while n > B:
+        n = -(-n // B)
+        P += n
+    return 4 * (4 + int(n_sets) * (int(n_targets) + 4 * int(n_entries) + P))
+
+
+def scan_exclusive_u32_host(data):
+    """lerf_scan_exclusive_u32_host: the exclusive prefix sums (modulo 2^32) of a contiguous uint32 numpy vector, in place"""
+    if not isinstance(data, np.ndarray) or data.dtype != np.uint32 or data.ndim != 1 or not data.flags.c_contiguous:
+        raise ValueError("lerf_scan_exclusive_u32_host: data must be a contiguous uint32 vector")
+    check(lib().lerf_scan_exclusive_u32_host(data.ctypes.data, int(data.size)), "lerf_scan_exclusive_u32_host")
+    return data
+
 
 class HostOperands(_Operands):
     suffix, noun, f32, f64, key = "_host", "a numpy array", np.float32, np.float64, np.uint64
@@ -565,6 +641,12 @@ class HostOperands(_Operands):
     def workspace(self, nbytes, device):
         """the workspace arguments of a host twin: none (the host sums in place)"""
         return ()
+
+    def scratch(self, nbytes, device):
+        return np.empty(int(nbytes), np.uint8)
+
+    def max_count(self, ws):
+        return int(ws[ORDERED_MAX_COUNT_OFFSET:ORDERED_MAX_COUNT_OFFSET + 4].view(np.uint32)[0])
 
 
 class DeviceOperands(_Operands):
@@ -617,6 +699,15 @@ class DeviceOperands(_Operands):
         from . import ops
         ws = ops._cached_workspace(nbytes, device)
         return ws.data_ptr(), ws.numel()
+
+    def scratch(self, nbytes, device):
+        """a device byte tensor of at least nbytes: the per-stream scratch of workspace()"""
+        from . import ops
+        return ops._cached_workspace(nbytes, device)
+
+    def max_count(self, ws):
+        """the header's largest count: a 4-byte copy to the host, which waits for the stream"""
+        return int(ws[ORDERED_MAX_COUNT_OFFSET:ORDERED_MAX_COUNT_OFFSET + 4].view(self.torch.int32).item()) & 0xffffffff
 
 
 def coords_model_count(model, n, what):
@@ -748,26 +839,42 @@ def _dense_set(B, t):
     return 0 if B < 2 or t is None or t.ndim == 3 else 2 * t.shape[-3] * t.shape[-2]
 
 
-def coords_compose_bwd_on(X, outer, inner, grad_out, grad_outer, grad_inner, need):
+def coords_compose_bwd_on(X, outer, inner, grad_out, grad_outer, grad_inner, need, max_adders=None):
+    """max_adders None: the atomic scatter; an int: the ORDERED scatter with that cap (run_ordered).  Ordered, with ONE outer map shared
+    by a batch: every set scatters into a gradient of its own (a target has one owner) and grad_outer gains them one after the other,
+    set 0 first -- a fixed order, so the result is reproducible (it is the host twin's sum only where that order does not matter)."""
     what = "lerf_coords_compose_bwd" + X.suffix
     a, sa, ta, b, sb, tb, B, g = _coords_bwd_operands(X, what, outer, inner, ("outer", "inner"), grad_out)
     if not (need[0] or need[1]):
         raise ValueError("%s: at least one of the two gradients is needed" % what)
     ga = X.grad(grad_outer, a.shape, X.device(b), what + ": grad_outer") if need[0] else None
     gb = X.grad(grad_inner, b.shape, X.device(b), what + ": grad_inner") if need[1] else None
-    X.run("lerf_coords_compose_bwd", B, b, (*X.operand(a, sa), a.shape[-3], a.shape[-2], *X.operand(b, sb), X.ptr(g), b.shape[-3], b.shape[-2],
-                                            X.ptr(ga), X.ptr(gb)), (ta, tb, _dense_set(B, g), _dense_set(B, ga), _dense_set(B, gb)))
+    args = (*X.operand(a, sa), a.shape[-3], a.shape[-2], *X.operand(b, sb), X.ptr(g), b.shape[-3], b.shape[-2])
+    if max_adders is None:
+        X.run("lerf_coords_compose_bwd", B, b, args + (X.ptr(ga), X.ptr(gb)), (ta, tb, _dense_set(B, g), _dense_set(B, ga), _dense_set(B, gb)))
+        return ga, gb
+    per_set = ga is not None and B > 1 and a.ndim == 3
+    gs = X.new((B,) + tuple(a.shape), X.f64, X.device(b), zero=True) if per_set else ga
+    X.run_ordered("lerf_coords_compose_bwd", B, b, args + (X.ptr(gs), X.ptr(gb)), (ta, tb, _dense_set(B, g), _dense_set(B, gs), _dense_set(B, gb)),
+                  b.shape[-3] * b.shape[-2], a.shape[-3] * a.shape[-2], max_adders)
+    if per_set:
+        for s in range(B):
+            ga += gs[s]
     return ga, gb
 
 
-def coords_invert_bwd_on(X, f, inverse, grad_out, grad_f):
+def coords_invert_bwd_on(X, f, inverse, grad_out, grad_f, max_adders=None):
     what = "lerf_coords_invert_bwd" + X.suffix
     a, sa, ta, b, sb, tb, B, g = _coords_bwd_operands(X, what, f, inverse, ("f", "inverse"), grad_out)
     if B and a.ndim == 3:
         raise ValueError("%s: a batch of inverses needs a batch of as many maps f (grad_f has one writer per set)" % what)
     gf = X.grad(grad_f, a.shape, X.device(b), what + ": grad_f")
-    X.run("lerf_coords_invert_bwd", B, b, (*X.operand(a, sa), a.shape[-3], a.shape[-2], *X.operand(b, sb), X.ptr(g), b.shape[-3], b.shape[-2],
-                                           X.ptr(gf)), (ta, tb, _dense_set(B, g), _dense_set(B, gf)))
+    args = (*X.operand(a, sa), a.shape[-3], a.shape[-2], *X.operand(b, sb), X.ptr(g), b.shape[-3], b.shape[-2], X.ptr(gf))
+    if max_adders is None:
+        X.run("lerf_coords_invert_bwd", B, b, args, (ta, tb, _dense_set(B, g), _dense_set(B, gf)))
+    else:
+        X.run_ordered("lerf_coords_invert_bwd", B, b, args, (ta, tb, _dense_set(B, g), _dense_set(B, gf)), b.shape[-3] * b.shape[-2],
+                      a.shape[-3] * a.shape[-2], max_adders)
     return gf
 
 
@@ -844,8 +951,9 @@ def _splat_operands(X, what, src, fmap, weight):
     return x, f, m, B, Cn, (H, W), head
 
 
-def splat_on(X, src, fmap, out_hw, weight=None, norm=False, acc=None):
-    """lerf_splat / lerf_splat_host: ADD src into acc [.., C (+ 1 with norm), oH, oW] along the forward map; acc None: a zeroed one"""
+def splat_on(X, src, fmap, out_hw, weight=None, norm=False, acc=None, max_adders=None):
+    """lerf_splat / lerf_splat_host: ADD src into acc [.., C (+ 1 with norm), oH, oW] along the forward map; acc None: a zeroed one.
+    max_adders an int: lerf_splat_ordered / lerf_splat_ordered_host with that cap (run_ordered)"""
     what = "lerf_splat" + X.suffix
     x, f, m, B, Cn, hw, head = _splat_operands(X, what, src, fmap, weight)
     oH, oW = int(out_hw[0]), int(out_hw[1])
@@ -857,7 +965,11 @@ def splat_on(X, src, fmap, out_hw, weight=None, norm=False, acc=None):
         acc = X.new(shape, x.dtype, X.device(x), zero=True)
     else:
         acc = X.dense(acc, shape, x.dtype, X.device(x), what + ": acc")
-    X.call(what, x, *head, X.ptr(acc), int(bool(norm)), oH, oW, planes * oH * oW if B > 1 else 0, max(B, 1))
+    args = (*head, X.ptr(acc), int(bool(norm)), oH, oW, planes * oH * oW if B > 1 else 0, max(B, 1))
+    if max_adders is None:
+        X.call(what, x, *args)
+    else:
+        X.run_ordered("lerf_splat", B, x, args, None, hw[0] * hw[1], oH * oW, max_adders)
     return acc
 
 
@@ -946,11 +1058,21 @@ def coords_compose_bwd_host(outer, inner, grad_out, grad_outer=None, grad_inner=
     return coords_compose_bwd_on(_HOST, outer, inner, grad_out, grad_outer, grad_inner, need)
 
 
+def coords_compose_bwd_ordered_host(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True), max_adders=4096):
+    """lerf_coords_compose_bwd_ordered_host: coords_compose_bwd_host by the four passes of the ordered scatter; the same bits"""
+    return coords_compose_bwd_on(_HOST, outer, inner, grad_out, grad_outer, grad_inner, need, max_adders)
+
+
 def coords_invert_bwd_host(f, inverse, grad_out, grad_f=None):
     """lerf_coords_invert_bwd_host: ACCUMULATE the implicit-function adjoint of inverse = invert(f) of the float64 grad_out
     [oH, oW, 2] into grad_f [fH, fW, 2] (None: a zeroed one).  A batch (every operand with a leading B) is one call of
     lerf_coords_invert_bwd_batched_host."""
     return coords_invert_bwd_on(_HOST, f, inverse, grad_out, grad_f)
+
+
+def coords_invert_bwd_ordered_host(f, inverse, grad_out, grad_f=None, max_adders=4096):
+    """lerf_coords_invert_bwd_ordered_host: coords_invert_bwd_host by the four passes of the ordered scatter; the same bits"""
+    return coords_invert_bwd_on(_HOST, f, inverse, grad_out, grad_f, max_adders)
 
 
 def coords_build_bwd_host(model, params, grad_map, origin=(0, 0)):
@@ -998,6 +1120,12 @@ def splat_host(src, map, out_hw, weight=None, norm=False, acc=None):
     map[i, j] = the (row, col) in the out_hw frame at which source pixel (i, j) lands; weight None or src's dtype [H, W] / [B, H, W]
     -> acc [.., C (+ 1 with norm: the plane of the weights), oH, oW] of src's dtype.  acc given: ACCUMULATED INTO and returned."""
     return splat_on(_HOST, src, map, out_hw, weight, norm, acc)
+
+
+def splat_ordered_host(src, map, out_hw, weight=None, norm=False, acc=None, max_adders=4096):
+    """lerf_splat_ordered_host: splat_host by the four passes of the ordered scatter (count, scan, fill, sort and sum); the same bits.
+    LerfError when more than max_adders source pixels add into one output pixel (that pixel holds NaN in every plane)."""
+    return splat_on(_HOST, src, map, out_hw, weight, norm, acc, max_adders)
 
 
 def splat_bwd_host(src, map, grad, weight=None, norm=False, need=(True, True, True)):

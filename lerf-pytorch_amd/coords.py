@@ -537,6 +537,17 @@ def _compose_dev(outer, inner, tdt):
     return ops.coords_compose(outer, inner, dtype=tdt)
 
 
+def _deterministic(flag):
+    """a twin's `deterministic`: None follows torch.are_deterministic_algorithms_enabled()"""
+    import torch
+    return bool(torch.are_deterministic_algorithms_enabled()) if flag is None else bool(flag)
+
+
+def _ordered_kw(ordered):
+    """the keyword arguments of an ops scatter: none for the atomic kernel (the call is today's), the cap for the ordered one"""
+    return {} if ordered is None else {"deterministic": True, "max_adders": ordered}
+
+
 _CHAIN_FNS = None
 
 
@@ -549,11 +560,13 @@ def _chain_fns():
 
         class _ComposeFn(torch.autograd.Function):
             """C = compose(outer, inner); backward: ops.coords_compose_bwd in float64, one launch for the whole batch, a shared outer map's
-            gradient summed into one buffer by the scatter's atomics; each gradient cast to its operand's dtype"""
+            gradient summed into one buffer by the scatter's atomics; each gradient cast to its operand's dtype.  ordered (None or
+            the cap): the outer gradient by the ordered scatter, a shared outer map's summed sample by sample"""
 
             @staticmethod
-            def forward(ctx, outer, inner, tdt):
+            def forward(ctx, outer, inner, tdt, ordered=None):
                 ctx.save_for_backward(outer, inner)
+                ctx.ordered = ordered
                 return _compose_dev(outer.detach(), inner.detach(), tdt)
 
             @staticmethod
@@ -564,17 +577,18 @@ def _chain_fns():
                 g = grad.contiguous().double()
                 ga = torch.zeros(tuple(outer.shape), dtype=torch.float64, device=g.device) if need[0] else None
                 gb = torch.zeros(tuple(inner.shape), dtype=torch.float64, device=g.device) if need[1] else None
-                ops.coords_compose_bwd(outer, inner, g, ga, gb, need)
-                return None if ga is None else ga.to(outer.dtype), None if gb is None else gb.to(inner.dtype), None
+                ops.coords_compose_bwd(outer, inner, g, ga, gb, need, **_ordered_kw(ctx.ordered))
+                return None if ga is None else ga.to(outer.dtype), None if gb is None else gb.to(inner.dtype), None, None
 
         class _InvertFn(torch.autograd.Function):
             """G = invert(map); backward: ops.coords_invert_bwd in float64 at the saved inverse (the implicit function theorem), cast
             to the map's dtype; init is a constant"""
 
             @staticmethod
-            def forward(ctx, map, init, hw, max_iter, tol, tdt):
+            def forward(ctx, map, init, hw, max_iter, tol, tdt, ordered=None):
                 out = _invert_maps(map.detach(), hw, None if init is None else init.detach(), max_iter, tol, tdt)
                 ctx.save_for_backward(map, out)
+                ctx.ordered = ordered
                 return out
 
             @staticmethod
@@ -583,8 +597,8 @@ def _chain_fns():
                 map, out = ctx.saved_tensors
                 g = grad.contiguous().double()
                 gf = torch.zeros(tuple(map.shape), dtype=torch.float64, device=g.device)
-                ops.coords_invert_bwd(map, out, g, gf)
-                return gf.to(map.dtype), None, None, None, None, None
+                ops.coords_invert_bwd(map, out, g, gf, **_ordered_kw(ctx.ordered))
+                return gf.to(map.dtype), None, None, None, None, None, None
 
         _CHAIN_FNS = (_ComposeFn, _InvertFn)
     return _CHAIN_FNS
@@ -600,7 +614,7 @@ def _device_map(t, what, batch=True):
     return t
 
 
-def compose_torch(outer, inner, dtype=None):
+def compose_torch(outer, inner, dtype=None, deterministic=None, max_adders=4096):
     """compose on the maps' device, differentiable: C[i, j] = outer(inner[i, j]) by the same kernel (bit-equal to compose when
     grad mode is off or no operand requires grad); an operand that requires grad stays in the graph through
     lerf_coords_compose_bwd: the outer map's gradient is the bilinear scatter of the upstream gradient (float64 atomic adds), the
@@ -609,7 +623,12 @@ def compose_torch(outer, inner, dtype=None):
     computed in float64 and cast to its operand's dtype.  A batch: inner [B, H, W, 2] with outer [B, aH, aW, 2] or one shared
     [aH, aW, 2] (its gradient is the sum over the samples) -- ONE launch forward and one backward, whatever B
     (lerf_coords_compose_batched, lerf_coords_compose_bwd_batched).  compose_torch(phi, phi) returns the sum of
-    both gradients to phi.  The differentiable path needs an outer map of at least 2 x 2.  Once differentiable."""
+    both gradients to phi.  The differentiable path needs an outer map of at least 2 x 2.  Once differentiable.
+    deterministic (None: follow torch.are_deterministic_algorithms_enabled(), read at this call): the outer map's gradient by the ORDERED
+    scatter (lerf_coords_compose_bwd_ordered) -- summed in the host twin's order, bit-equal from run to run and to
+    lerf_coords_compose_bwd_host.  Its backward ends with one 4-byte copy to the host and a synchronisation, and raises LerfError when
+    more than max_adders entries add into one element.  One shared outer map in a batch: every sample scatters into a gradient of its
+    own, and they are added one after the other, sample 0 first.  The inner map's gradient is the same either way."""
     import torch
     a, b = _device_map(outer, "compose_torch: outer"), _device_map(inner, "compose_torch: inner")
     if a.device != b.device:
@@ -621,17 +640,20 @@ def compose_torch(outer, inner, dtype=None):
         return _compose_dev(a.detach(), b.detach(), tdt)
     if a.shape[-3] < 2 or a.shape[-2] < 2:
         raise ValueError("compose_torch: the gradient needs an outer map of at least 2 x 2")
-    return _chain_fns()[0].apply(a, b, tdt)
+    return _chain_fns()[0].apply(a, b, tdt, int(max_adders) if _deterministic(deterministic) else None)
 
 
-def invert_torch(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
+def invert_torch(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None, deterministic=None, max_adders=4096):
     """invert on the map's device, differentiable: the same Newton kernel (bit-equal to invert when grad mode is off or the map
     does not require grad); a map that requires grad stays in the graph through lerf_coords_invert_bwd, the implicit-function
     gradient of map(G[q]) = q at the inverse returned: the bilinear scatter of -J^-T g.  Entries of the inverse that are NaN, cells
     with a NaN corner and folded cells contribute nothing.  init is a constant (no gradient), as are max_iter and tol.
     Floating-point device tensors only; a batch [B, fH, fW, 2] (init [B, H, W, 2]) runs ONE launch forward and one backward
     (lerf_coords_invert_batched, lerf_coords_invert_bwd_batched).  The gradient is
-    computed in float64 and cast to the map's dtype.  Once differentiable."""
+    computed in float64 and cast to the map's dtype.  Once differentiable.
+    deterministic (None: follow torch.are_deterministic_algorithms_enabled(), read at this call): the gradient by the ORDERED scatter
+    (lerf_coords_invert_bwd_ordered), bit-equal from run to run and to lerf_coords_invert_bwd_host; its backward ends with
+    one 4-byte copy to the host and a synchronisation, and raises LerfError when more than max_adders entries add into one element."""
     import torch
     a = _device_map(map, "invert_torch: map")
     H, W = int(in_hw[0]), int(in_hw[1])
@@ -646,17 +668,18 @@ def invert_torch(map, in_hw, init=None, max_iter=16, tol=1e-9, dtype=None):
     tdt = a.dtype if dtype is None else getattr(torch, _np_dtype(dtype).name)
     if not (torch.is_grad_enabled() and a.requires_grad):
         return _invert_maps(a.detach(), (H, W), None if init is None else init.detach(), max_iter, tol, tdt)
-    return _chain_fns()[1].apply(a, init, (H, W), int(max_iter), float(tol), tdt)
+    return _chain_fns()[1].apply(a, init, (H, W), int(max_iter), float(tol), tdt, int(max_adders) if _deterministic(deterministic) else None)
 
 
-def invert_flow_torch(flow, init=None, max_iter=16, tol=1e-9):
+def invert_flow_torch(flow, init=None, max_iter=16, tol=1e-9, deterministic=None, max_adders=4096):
     """invert_flow on the flow's device, differentiable: b = invert_torch(identity + flow, (H, W)) - identity in the flow's
-    dtype; a flow that requires grad receives its gradient through lerf_coords_invert_bwd.  init, max_iter, tol: invert_torch's."""
+    dtype; a flow that requires grad receives its gradient through lerf_coords_invert_bwd.  init, max_iter, tol, deterministic,
+    max_adders: invert_torch's."""
     import torch
     f = _device_map(flow, "invert_flow_torch: flow")
     H, W = int(f.shape[-3]), int(f.shape[-2])
     ident = from_flow_torch(torch.zeros((H, W, 2), dtype=f.dtype, device=f.device))
-    return invert_torch(ident + f, (H, W), init=init, max_iter=max_iter, tol=tol) - ident
+    return invert_torch(ident + f, (H, W), init=init, max_iter=max_iter, tol=tol, deterministic=deterministic, max_adders=max_adders) - ident
 
 
 # ---------------------------------------------------------------------------------------------- differentiable model builders
@@ -1053,7 +1076,7 @@ def _splat_args(what, src, map, out_hw, weight, mode):
     return oH, oW
 
 
-def splat(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False):
+def splat(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False, deterministic=False, max_adders=4096):
     """Forward warp by SUMMATION SPLATTING (lerf_splat): every pixel of src [C, H, W] (or a batch [B, C, H, W]) is ADDED
     into the frame out_hw = (oH, oW) at the position map[i, j] = (row, col) gives it -- map [H, W, 2], shared by the batch, or
     [B, H, W, 2]; invert_raster reads a forward map the same way -- spread bilinearly over up to four pixels.  Mass that leaves the frame
@@ -1073,7 +1096,12 @@ def splat(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False
     numpy operands -> numpy (the kernel's host twin, row-major order); device tensors -> device tensors written by the kernel (float
     atomic adds: equal from run to run up to the rounding of a reordered sum).  Mixed operands are refused.  The quotient and the exp
     are elementwise array / tensor operations.  float32 / float64 src decides the dtype; the map may be either.  No autograd: an
-    operand that requires grad (with grad mode on) is refused -- splat_torch is the differentiable twin."""
+    operand that requires grad (with grad mode on) is refused -- splat_torch is the differentiable twin.
+    deterministic=True (device tensors): the ORDERED scatter (lerf_splat_ordered) -- every output pixel adds its source
+    pixels in row-major order, so the accumulator equals the host twin's bit for bit and two runs agree exactly.  It ends with one
+    4-byte copy to the host and a synchronisation, and raises LerfError when more than max_adders source pixels add into one output
+    pixel (a map that collapses the frame; that pixel would hold NaN).  On numpy operands the flag is accepted and changes nothing: the
+    host twin is ordered already."""
     oH, oW = _splat_args("splat", src, map, out_hw, weight, mode)
     ops_ = [t for t in (src, map, weight) if t is not None]
     dev = [bool(getattr(t, "is_cuda", False)) for t in ops_]
@@ -1091,7 +1119,7 @@ def splat(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False
         w = None if weight is None else weight.detach().to(x.dtype)
         if mode == "softmax":
             w = _softmax_importance_torch(w)
-        acc = ops.splat(x, f, (oH, oW), w, norm)
+        acc = ops.splat(x, f, (oH, oW), w, norm, **_ordered_kw(int(max_adders) if deterministic else None))
     else:
         from . import _lib
         x, f, w = (None if t is None else np.asarray(t.detach().numpy() if hasattr(t, "detach") else t) for t in (src, map, weight))
@@ -1133,12 +1161,12 @@ def _splat_fn():
             gradient (float64) cast to the map's dtype"""
 
             @staticmethod
-            def forward(ctx, src, weight, map, hw, norm):
+            def forward(ctx, src, weight, map, hw, norm, ordered=None):
                 x, f = src.detach().contiguous(), map.detach()
                 m = None if weight is None else weight.detach().contiguous()
                 ctx.save_for_backward(x, f, *(() if m is None else (m,)))
                 ctx.hw, ctx.norm, ctx.map_dtype = hw, norm, map.dtype
-                return ops.splat(x, f, hw, m, norm)
+                return ops.splat(x, f, hw, m, norm, **_ordered_kw(ordered))
 
             @staticmethod
             @once_differentiable
@@ -1147,15 +1175,15 @@ def _splat_fn():
                 m = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
                 need = (ctx.needs_input_grad[0], m is not None and ctx.needs_input_grad[1], ctx.needs_input_grad[2])
                 if not any(need):
-                    return None, None, None, None, None
+                    return None, None, None, None, None, None
                 gx, gm, gf = ops.splat_bwd(x, f, grad.contiguous().to(x.dtype), m, ctx.norm, need)
-                return gx, gm, None if gf is None else gf.to(ctx.map_dtype), None, None
+                return gx, gm, None if gf is None else gf.to(ctx.map_dtype), None, None, None
 
         _SPLAT_FN = _SplatFn
     return _SPLAT_FN
 
 
-def splat_torch(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False):
+def splat_torch(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False, deterministic=None, max_adders=4096):
     """splat on the operands' device, differentiable: src [C, H, W] or [B, C, H, W], map [H, W, 2] or [B, H, W, 2] and weight ([H, W] or
     [B, H, W], or None), all float32 / float64 DEVICE tensors (weight is cast to src's dtype) -> what splat returns.  src, weight and
     map each receive a gradient when they require one, through lerf_splat_bwd -- a gather with one writer per source pixel, bit-equal
@@ -1166,7 +1194,10 @@ def splat_torch(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm
         m, z = reproject_torch(depth_src, K_src, K_dst, R, t, return_depth=True)
         splat_torch(img_src, m, hw, weight=-beta * z, mode="softmax")
 
-    Once differentiable."""
+    deterministic (None: follow torch.are_deterministic_algorithms_enabled(), read at this call): the forward by the ORDERED scatter
+    (lerf_splat_ordered) -- bit-equal from run to run and to lerf_splat_host.  The forward then ends with one 4-byte copy
+    to the host and a synchronisation, and raises LerfError when more than max_adders source pixels add into one output pixel.  The
+    backward is a gather and was reproducible all along.  Once differentiable."""
     import torch
     oH, oW = _splat_args("splat_torch", src, map, out_hw, weight, mode)
     for t, name in ((src, "src"), (map, "map"), (weight, "weight")):
@@ -1178,11 +1209,12 @@ def splat_torch(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm
     if mode == "softmax":
         w = _softmax_importance_torch(w)
     norm = mode != "sum" or bool(return_norm)
+    ordered = int(max_adders) if _deterministic(deterministic) else None
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (src, map, w)):
-        acc = _splat_fn().apply(src, w, map, (oH, oW), norm)
+        acc = _splat_fn().apply(src, w, map, (oH, oW), norm, ordered)
     else:
         from . import ops
-        acc = ops.splat(src.detach(), map.detach(), (oH, oW), None if w is None else w.detach(), norm)
+        acc = ops.splat(src.detach(), map.detach(), (oH, oW), None if w is None else w.detach(), norm, **_ordered_kw(ordered))
     C = src.shape[-3]
     out = acc[..., :C, :, :]
     if mode != "sum":

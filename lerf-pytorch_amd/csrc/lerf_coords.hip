@@ -18,6 +18,9 @@
 // the host twin, the single map and the batch cannot drift apart: they agree bit for bit by construction (the two float scatters
 // excepted, below).  THE ARGUMENT CHECKS are one operand table per call (Operand, Pair, check_call, after the kernels):
 // an entry point lists its operands, its scalar rules and the pairs that must not intersect ONCE, and one function judges them.  Add2 is the float scatter of the map adjoints: two float64 atomicAdd where compiled for the device, a plain add on the host; AddPlane is the same pattern for one plane of an image (the forward warp, lerf_splat; its arithmetic is lerf_splat_point.h).
+// The three float scatters (SplatOp, ComposeBwdOp, InvertBwdOp) also run under a THIRD pair of runners, OrderedOnDevice / OrderedOnHost
+// (after the scatter runners): the same op four times over a caller-owned workspace -- count, scan, fill, sort and sum -- which adds
+// in the host twin's order and so IS bit-equal to it (the _ordered entry points).
 // MapReader is the one strided-map reader handed to the *_point functions; a dense float64 gradient [h][w][2] is a map of row stride 2w.
 //
 // The rasterising inverse (lerf_coords_invert_raster) is three passes: KeyFillOp and ResolveOp are per-entry functors under the two
@@ -126,6 +129,75 @@ struct Add2 {
         p[0] += dr;
         p[1] += dc;
 #endif
+    }
+};
+
+// The combiners of the ORDERED scatter (OrderedOnDevice / OrderedOnHost, after the runners): the three scatter operations hand their
+// combiner calls to whatever apply() is given -- Add2 / AddPlane by default, or one of these.  Each answers both call shapes, the map
+// adjoints' (row, col, dr, dc) over a frame `w` wide and the splat's (plane, q, v); q is the TARGET, the element index in its frame.
+//   CountAt   pass 1: one uint32 atomic increment of count[q] per call (the splat runs with one plane: per tap, not per plane)
+//   FillAt    pass 3: slot = cursor[q]++ (atomic, returning), list[slot] = e -- the entry that called
+//   Keep2At / KeepPlaneAt   pass 4: the host branch of Add2 / AddPlane, a plain p = p + r into global memory, for calls whose target is
+//             q and no other; the thread that owns q is the element's only writer
+struct CountAt {
+    uint32_t* count;
+    int w;
+    LERF_HD void bump(int64_t q) const {
+#ifdef __HIP_DEVICE_COMPILE__
+        atomicAdd(count + q, 1u);
+#else
+        count[q] += 1u;
+#endif
+    }
+    LERF_HD void operator()(int r, int c, double, double) const { bump((int64_t)r * w + c); }
+    LERF_HD void operator()(int k, int64_t q, double) const { if (k == 0) bump(q); }
+};
+
+struct FillAt {
+    uint32_t* cursor;
+    uint32_t* list;
+    uint32_t e;
+    int w;
+    LERF_HD void put(int64_t q) const {
+#ifdef __HIP_DEVICE_COMPILE__
+        const uint32_t slot = atomicAdd(cursor + q, 1u);
+#else
+        const uint32_t slot = cursor[q]++;
+#endif
+        list[slot] = e;
+    }
+    LERF_HD void operator()(int r, int c, double, double) const { put((int64_t)r * w + c); }
+    LERF_HD void operator()(int k, int64_t q, double) const { if (k == 0) put(q); }
+};
+
+struct Keep2At {
+    double* grad;
+    int w;
+    int64_t q;
+    LERF_HD void operator()(int r, int c, double dr, double dc) const {
+#pragma clang fp contract(off)
+        if ((int64_t)r * w + c != q) return;
+        double* p = grad + 2 * q;
+        p[0] = p[0] + dr;
+        p[1] = p[1] + dc;
+    }
+    LERF_HD void poison() const { grad[2 * q] = grad[2 * q + 1] = __builtin_nan(""); }
+};
+
+template <typename T>
+struct KeepPlaneAt {
+    T* acc;
+    int64_t plane, q;
+    int planes;
+    LERF_HD void operator()(int k, int64_t at, double v) const {
+#pragma clang fp contract(off)
+        if (at != q) return;
+        T* p = acc + (int64_t)k * plane + q;
+        const T r = (T)v;                            // rounded once, here: AddPlane's statement
+        *p = *p + r;
+    }
+    LERF_HD void poison() const {
+        for (int k = 0; k < planes; ++k) acc[(int64_t)k * plane + q] = (T)__builtin_nan("");
     }
 };
 
@@ -238,17 +310,29 @@ struct ComposeBwdOp {
     MapReader<double> gout;
     double *gA, *gB;
     int64_t a_set, b_set, gout_set, ga_set, gb_set;
-    LERF_HD void operator()(int i, int j, int s) const {
+    LERF_HD void operator()(int i, int j, int s) const { apply(i, j, s, Add2{gA + set_offset(s, ga_set), aW}); }
+    // the operation with the outer gradient's taps handed to `add`
+    template <typename ADD>
+    LERF_HD void apply(int i, int j, int s, ADD add) const {
 #pragma clang fp contract(off)
         const Point q = B.set(s, b_set)(i, j);
-        const Point d = compose_bwd_point(q.r, q.c, gout.set(s, gout_set)(i, j), aH, aW, gA != nullptr, gB != nullptr, A.set(s, a_set),
-                                          Add2{gA + set_offset(s, ga_set), aW});
+        const Point d = compose_bwd_point(q.r, q.c, gout.set(s, gout_set)(i, j), aH, aW, gA != nullptr, gB != nullptr, A.set(s, a_set), add);
         if (gB) {
             double* gb = gB + set_offset(s, gb_set);
             const Point v = load_entry(gb, gout.stride, i, j);
             store_entry(gb, gout.stride, i, j, Point{v.r + d.r, v.c + d.c});
         }
     }
+    // what the ordered runners ask of a scatter operation: its target frame, the scatter alone (what passes 1, 3 and 4 run), the rest
+    // alone (one writer already: run as today), the combiner that keeps target q of set s
+    LERF_HD int target_h() const { return aH; }
+    LERF_HD int target_w() const { return aW; }
+    bool has_scatter() const { return gA != nullptr; }
+    bool has_rest() const { return gB != nullptr; }
+    LERF_HD ComposeBwdOp scatter_only() const { ComposeBwdOp o = *this; o.gB = nullptr; return o; }
+    LERF_HD ComposeBwdOp taps_only() const { return scatter_only(); }
+    ComposeBwdOp rest_only() const { ComposeBwdOp o = *this; o.gA = nullptr; o.ga_set = 0; return o; }      // a null base takes no offset
+    LERF_HD Keep2At keep_at(int s, int64_t q) const { return {gA + set_offset(s, ga_set), aW, q}; }
 };
 
 // the adjoint of invert by the implicit function theorem (invert_bwd_point): one load of G and of grad_out, the four corners of one cell
@@ -261,10 +345,20 @@ struct InvertBwdOp {
     MapReader<double> gout;
     double* gF;
     int64_t f_set, g_set, gout_set, gf_set;
-    LERF_HD void operator()(int i, int j, int s) const {
+    LERF_HD void operator()(int i, int j, int s) const { apply(i, j, s, Add2{gF + set_offset(s, gf_set), fW}); }
+    template <typename ADD>
+    LERF_HD void apply(int i, int j, int s, ADD add) const {
         const Point u = G.set(s, g_set)(i, j);
-        invert_bwd_point(u.r, u.c, gout.set(s, gout_set)(i, j), fH, fW, F.set(s, f_set), Add2{gF + set_offset(s, gf_set), fW});
+        invert_bwd_point(u.r, u.c, gout.set(s, gout_set)(i, j), fH, fW, F.set(s, f_set), add);
     }
+    LERF_HD int target_h() const { return fH; }
+    LERF_HD int target_w() const { return fW; }
+    bool has_scatter() const { return true; }
+    bool has_rest() const { return false; }
+    LERF_HD InvertBwdOp scatter_only() const { return *this; }
+    LERF_HD InvertBwdOp taps_only() const { return *this; }
+    InvertBwdOp rest_only() const { return *this; }
+    LERF_HD Keep2At keep_at(int s, int64_t q) const { return {gF + set_offset(s, gf_set), fW, q}; }
 };
 
 // The rasterising inverse (raster_cell / raster_resolve of lerf_coords_models.h) in three passes over caller-owned keys [oH][oW]:
@@ -346,6 +440,26 @@ struct SplatOp {
         splat_point(F.set(s, f_set)(i, j), m ? (double)m[set_offset(s, m_set) + e] : 1.0, C, norm, oH, oW,
                     [xs, plane](int k) { return (double)xs[(int64_t)k * plane]; }, AddPlane<T>{acc + set_offset(s, acc_set), out_plane});
     }
+    // operator() with the adds handed to `add`.  The statement is written twice ON PURPOSE: routed through apply(), the atomic kernel
+    // schedules its conversions to T differently (the same instructions, one VGPR fewer), and this file promises that it compiles to
+    // the device code it had.  Both hand the same operands to the one splat_point.
+    template <typename ADD>
+    LERF_HD void apply(int i, int j, int s, ADD add) const {
+        const int64_t e = (int64_t)i * W + j;
+        const T* xs = x + set_offset(s, x_set) + e;
+        const int64_t plane = in_plane;
+        splat_point(F.set(s, f_set)(i, j), m ? (double)m[set_offset(s, m_set) + e] : 1.0, C, norm, oH, oW,
+                    [xs, plane](int k) { return (double)xs[(int64_t)k * plane]; }, add);
+    }
+    // the ordered runners' view (ComposeBwdOp): the passes that only look for the taps run ONE plane, so a tap is counted and listed once
+    LERF_HD int target_h() const { return oH; }
+    LERF_HD int target_w() const { return oW; }
+    bool has_scatter() const { return true; }
+    bool has_rest() const { return false; }
+    LERF_HD SplatOp scatter_only() const { return *this; }
+    LERF_HD SplatOp taps_only() const { SplatOp o = *this; o.C = 1; o.norm = false; return o; }
+    SplatOp rest_only() const { return *this; }
+    LERF_HD KeepPlaneAt<T> keep_at(int s, int64_t q) const { return {acc + set_offset(s, acc_set), out_plane, q, C + (norm ? 1 : 0)}; }
 };
 
 // the adjoint of the splat (splat_bwd_point): a GATHER -- per source pixel the same map entry and weight, per plane one load of x_k (when
@@ -456,6 +570,283 @@ struct ScatterOnHost {
             for (int i = 0; i < cH; ++i)
                 for (int j = 0; j < cW; ++j) op(i, j, s, KeyMinHost{keys + set_offset(s, keys_set)});
         return LERF_OK;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ the ordered scatter
+// The two runners of a float scatter operation whose sums must not depend on the order the hardware takes: the call shape of OnDevice /
+// OnHost, over a caller-owned workspace, in four passes that run THE SAME op under four combiners --
+//   1 count   entry_kernel over the entries, CountAt: count[s][q] += 1 per combiner call; integer adds, so the counts are exact
+//   2 scan    the exclusive prefix sum of count per set (scan_exclusive_u32, below) = the start of every target's segment of `list`;
+//             its first level also folds the largest count into the header (an integer atomic max)
+//   3 fill    entry_kernel again, FillAt: list[s][cursor[s][q]++] = e; afterwards cursor[q] is the END of q's segment and cursor[q - 1]
+//             (0 for q = 0) its start -- one array serves count, start and end; the order inside a segment is whatever the atomics gave
+//   4 sum     ordered_sum_kernel, one thread per target: sort the segment ascending (sort_segment), walk it, skip an id equal to the
+//             one before (an entry listed twice runs once), and re-run the op for each entry e = i W + j under keep_at(s, q): the plain
+//             p = p + r of the host branch, for calls whose target is q only.  Entry order, then tap order inside the entry, then the
+//             planes each on their own element: the order of OnHost, from the same statements, so the sums are the host twin's bits.
+//             A target with more adders than max_adders is not sorted or summed: every plane of it becomes NaN (the thread's run
+//             time is bounded; the caller reads the header and refuses the result).
+// then the part of the op that had one writer all along (has_rest: compose's inner gradient), as today.
+// WORKSPACE, in uint32 words: header [4] (word 0 reserved and zeroed, word 1 = kOrderedMaxWord the largest count, 2 and 3 zero), cursor
+// [n_sets][n_targets], list [n_sets][4 n_entries], scan partials [n_sets][scan_partials(n_targets)].
+// Addresses: CountAt / FillAt index count / cursor at a target the op hands out -- the element it would have added into, inside
+// [tH][tW] by the op's own clamps and frame tests; a slot is below the segment's end because pass 3 repeats pass 1's calls exactly (the
+// operands are not written between them: the workspace intersects none); list holds e < n_entries; the sum reads list inside
+// [start, end) with end <= 4 n_entries and writes element q of every plane only.
+constexpr int kScanThreads = 256, kScanPerThread = 4, kScanBlock = kScanThreads * kScanPerThread;
+constexpr int kOrderedHeaderWords = 4, kOrderedMaxWord = 1;
+constexpr uint32_t kInsertionMax = 16;      // segments up to here: insertion sort; longer: heap sort
+
+// the scan partials one set of n elements needs: one word per block of every level that has more than one block
+inline int64_t scan_partials(int64_t n) {
+    int64_t total = 0;
+    while (n > kScanBlock) {
+        n = (n + kScanBlock - 1) / kScanBlock;
+        total += n;
+    }
+    return total;
+}
+
+// a block scans its kScanBlock elements of set blockIdx.y in place (exclusive) and writes their sum to sums[block] (when given); a
+// thread owns 4 consecutive elements, the 256 thread sums are scanned in LDS (Hillis-Steele, 8 steps); max_out: the largest element
+// seen, one atomic max per wave that saw one above 0
+__global__ void __launch_bounds__(kScanThreads)
+scan_block_kernel(uint32_t* __restrict__ data, int64_t n, int64_t set_stride, uint32_t* __restrict__ sums, int64_t sums_stride,
+                  uint32_t* __restrict__ max_out) {
+    __shared__ uint32_t part[kScanThreads];
+    data += (int64_t)blockIdx.y * set_stride;
+    const int64_t base = ((int64_t)blockIdx.x * kScanThreads + threadIdx.x) * kScanPerThread;
+    uint32_t v[kScanPerThread], sum = 0, big = 0;
+#pragma unroll
+    for (int k = 0; k < kScanPerThread; ++k) {
+        v[k] = base + k < n ? data[base + k] : 0u;
+        sum += v[k];
+        big = v[k] > big ? v[k] : big;
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < kScanThreads; d <<= 1) {
+        const uint32_t add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    uint32_t run = part[threadIdx.x] - sum;      // exclusive over the threads
+#pragma unroll
+    for (int k = 0; k < kScanPerThread; ++k) {
+        if (base + k < n) data[base + k] = run;
+        run += v[k];
+    }
+    if (sums && threadIdx.x == kScanThreads - 1) sums[(int64_t)blockIdx.y * sums_stride + blockIdx.x] = part[threadIdx.x];
+    if (max_out) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const uint32_t other = (uint32_t)__shfl_xor((int)big, o, 64);
+            big = other > big ? other : big;
+        }
+        if ((threadIdx.x & 63) == 0 && big) atomicMax(max_out, big);
+    }
+}
+
+// the add-back: every element of block b gains the scanned sum of the blocks before it
+__global__ void __launch_bounds__(kScanThreads)
+scan_add_kernel(uint32_t* __restrict__ data, int64_t n, int64_t set_stride, const uint32_t* __restrict__ sums, int64_t sums_stride) {
+    data += (int64_t)blockIdx.y * set_stride;
+    const uint32_t add = sums[(int64_t)blockIdx.y * sums_stride + blockIdx.x];
+    const int64_t base = ((int64_t)blockIdx.x * kScanThreads + threadIdx.x) * kScanPerThread;
+#pragma unroll
+    for (int k = 0; k < kScanPerThread; ++k)
+        if (base + k < n) data[base + k] += add;
+}
+
+// data [sets][n] (sets `set_stride` words apart) -> its exclusive prefix sums per set, in place, modulo 2^32; partials: [sets][P],
+// P = scan_partials(n).  Plain passes in stream order -- block scans, the scan of the block sums (this function again, one level
+// up), the add-back -- and no workgroup waits for another.  n <= 2^32 - 1: at most four levels.
+inline void scan_exclusive_u32(hipStream_t stream, uint32_t* data, int64_t n, int sets, int64_t set_stride, uint32_t* partials, uint32_t* max_out) {
+    const int64_t P = scan_partials(n);
+    int64_t len = n, off = 0, stride = set_stride;
+    uint32_t* level = data;
+    struct { uint32_t* data; int64_t n, stride, off; } up[4];
+    int levels = 0;
+    while (true) {
+        const int64_t blocks = (len + kScanBlock - 1) / kScanBlock;
+        uint32_t* sums = blocks > 1 ? partials + off : nullptr;
+        hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)blocks, sets), dim3(kScanThreads), 0, stream, level, len, stride, sums, P,
+                           levels == 0 ? max_out : (uint32_t*)nullptr);
+        if (blocks <= 1) break;
+        up[levels++] = {level, len, stride, off};
+        level = sums;
+        len = blocks;
+        stride = P;
+        off += blocks;
+    }
+    while (levels-- > 0) {
+        const int64_t blocks = (up[levels].n + kScanBlock - 1) / kScanBlock;
+        hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)blocks, sets), dim3(kScanThreads), 0, stream, up[levels].data, up[levels].n,
+                           up[levels].stride, partials + up[levels].off, P);
+    }
+}
+
+inline void scan_exclusive_u32_host(uint32_t* data, int64_t n) {
+    uint32_t run = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const uint32_t v = data[k];
+        data[k] = run;
+        run += v;
+    }
+}
+
+// ascending, in place, by the segment's one owner: insertion sort up to kInsertionMax ids, heap sort (no recursion, n log n at worst) beyond
+LERF_HD inline void sort_segment(uint32_t* a, uint32_t n) {
+    if (n <= kInsertionMax) {
+        for (uint32_t k = 1; k < n; ++k) {
+            const uint32_t v = a[k];
+            uint32_t h = k;
+            for (; h > 0 && a[h - 1] > v; --h) a[h] = a[h - 1];
+            a[h] = v;
+        }
+        return;
+    }
+    const auto sift = [a](uint32_t root, uint32_t end) {      // the max-heap property below `root`, inside [0, end)
+        const uint32_t v = a[root];
+        while (true) {
+            uint32_t child = 2 * root + 1;
+            if (child >= end) break;
+            if (child + 1 < end && a[child + 1] > a[child]) ++child;
+            if (a[child] <= v) break;
+            a[root] = a[child];
+            root = child;
+        }
+        a[root] = v;
+    };
+    for (uint32_t k = n / 2; k-- > 0;) sift(k, n);
+    for (uint32_t end = n - 1; end > 0; --end) {
+        const uint32_t top = a[0];
+        a[0] = a[end];
+        a[end] = top;
+        sift(0, end);
+    }
+}
+
+// pass 4 for target q of set s; op: the scatter_only() form; cursor and list: the set's own; W: the width of the ENTRY grid
+template <typename OP>
+LERF_HD inline void ordered_sum_target(const OP& op, int s, int64_t q, const uint32_t* cursor, uint32_t* list, int W, uint32_t max_adders) {
+    const uint32_t start = q ? cursor[q - 1] : 0u, n = cursor[q] - start;
+    if (n == 0) return;
+    const auto keep = op.keep_at(s, q);
+    if (n > max_adders) {
+        keep.poison();
+        return;
+    }
+    uint32_t* seg = list + start;
+    sort_segment(seg, n);
+    uint32_t last = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t e = seg[k];
+        if (k && e == last) continue;
+        last = e;
+        op.apply((int)(e / (uint32_t)W), (int)(e % (uint32_t)W), s, keep);
+    }
+}
+
+template <typename OP>
+struct CountPass {
+    OP op;      // the taps_only() form
+    uint32_t* count;
+    int64_t n_targets;
+    LERF_HD void operator()(int i, int j, int s) const { op.apply(i, j, s, CountAt{count + (int64_t)s * n_targets, op.target_w()}); }
+};
+
+template <typename OP>
+struct FillPass {
+    OP op;
+    uint32_t *cursor, *list;
+    int64_t n_targets, n_slots;
+    int W;
+    LERF_HD void operator()(int i, int j, int s) const {
+        op.apply(i, j, s, FillAt{cursor + (int64_t)s * n_targets, list + (int64_t)s * n_slots, (uint32_t)i * (uint32_t)W + (uint32_t)j, op.target_w()});
+    }
+};
+
+// one thread per target, 256 a block, the set is blockIdx.y; a wave's threads own 64 neighbouring targets
+template <typename OP>
+__global__ void __launch_bounds__(256)
+ordered_sum_kernel(const OP op, int64_t n_targets, const uint32_t* __restrict__ cursor, uint32_t* __restrict__ list, int64_t n_slots, int W,
+                   uint32_t max_adders) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_targets) return;
+    const int s = (int)blockIdx.y;
+    ordered_sum_target(op, s, q, cursor + (int64_t)s * n_targets, list + (int64_t)s * n_slots, W, max_adders);
+}
+
+struct OrderedLayout {
+    int64_t n_entries, n_targets, n_slots, partials;
+    uint32_t *header, *cursor, *list, *scan;
+    OrderedLayout(void* ws, int64_t entries, int64_t targets, int sets)
+        : n_entries(entries), n_targets(targets), n_slots(4 * entries), partials(scan_partials(targets)) {
+        header = (uint32_t*)ws;
+        cursor = header + kOrderedHeaderWords;
+        list = cursor + (int64_t)sets * n_targets;
+        scan = list + (int64_t)sets * n_slots;
+    }
+    static size_t bytes(int64_t entries, int64_t targets, int sets) {
+        return sizeof(uint32_t) * ((size_t)kOrderedHeaderWords + (size_t)sets * ((size_t)targets + 4 * (size_t)entries + (size_t)scan_partials(targets)));
+    }
+};
+
+struct OrderedOnDevice {
+    hipStream_t stream;
+    void* ws;
+    int max_adders;
+    template <typename OP>
+    int operator()(const OP& op, int oH, int oW, int sets = 1) const {
+        clear_stale_error();
+        const OrderedLayout L(ws, (int64_t)oH * oW, (int64_t)op.target_h() * op.target_w(), sets);
+        if (hipMemsetAsync(ws, 0, sizeof(uint32_t) * (kOrderedHeaderWords + (size_t)sets * L.n_targets), stream) != hipSuccess) return LERF_ELAUNCH;
+        if (op.has_scatter()) {
+            const OnDevice run{stream};
+            int rc = run(CountPass<OP>{op.taps_only(), L.cursor, L.n_targets}, oH, oW, sets);
+            if (rc != LERF_OK) return rc;
+            scan_exclusive_u32(stream, L.cursor, L.n_targets, sets, L.n_targets, L.scan, L.header + kOrderedMaxWord);
+            rc = run(FillPass<OP>{op.taps_only(), L.cursor, L.list, L.n_targets, L.n_slots, oW}, oH, oW, sets);
+            if (rc != LERF_OK) return rc;
+            hipLaunchKernelGGL(ordered_sum_kernel<OP>, dim3((unsigned)((L.n_targets + 255) / 256), sets), dim3(256), 0, stream, op.scatter_only(),
+                               L.n_targets, L.cursor, L.list, L.n_slots, oW, (uint32_t)max_adders);
+            rc = launch_status();
+            if (rc != LERF_OK) return rc;
+        }
+        return op.has_rest() ? OnDevice{stream}(op.rest_only(), oH, oW, sets) : LERF_OK;
+    }
+};
+
+// the same four passes, serially; pass 3 walks the entries in DESCENDING order, so every segment of two or more ids reaches the sort
+// reversed and the sort, the duplicate skip and the cap run here as they do on the device
+struct OrderedOnHost {
+    void* ws;
+    int max_adders;
+    template <typename OP>
+    int operator()(const OP& op, int oH, int oW, int sets = 1) const {
+        const OrderedLayout L(ws, (int64_t)oH * oW, (int64_t)op.target_h() * op.target_w(), sets);
+        for (int k = 0; k < kOrderedHeaderWords; ++k) L.header[k] = 0;
+        for (int64_t k = 0; k < (int64_t)sets * L.n_targets; ++k) L.cursor[k] = 0;
+        if (op.has_scatter()) {
+            OnHost{}(CountPass<OP>{op.taps_only(), L.cursor, L.n_targets}, oH, oW, sets);
+            for (int s = 0; s < sets; ++s) {
+                uint32_t* c = L.cursor + (int64_t)s * L.n_targets;
+                for (int64_t q = 0; q < L.n_targets; ++q) L.header[kOrderedMaxWord] = c[q] > L.header[kOrderedMaxWord] ? c[q] : L.header[kOrderedMaxWord];
+                scan_exclusive_u32_host(c, L.n_targets);
+            }
+            const FillPass<OP> fill{op.taps_only(), L.cursor, L.list, L.n_targets, L.n_slots, oW};
+            for (int s = 0; s < sets; ++s)
+                for (int i = oH - 1; i >= 0; --i)
+                    for (int j = oW - 1; j >= 0; --j) fill(i, j, s);
+            const OP scatter = op.scatter_only();
+            for (int s = 0; s < sets; ++s)
+                for (int64_t q = 0; q < L.n_targets; ++q)
+                    ordered_sum_target(scatter, s, q, L.cursor + (int64_t)s * L.n_targets, L.list + (int64_t)s * L.n_slots, oW, (uint32_t)max_adders);
+        }
+        return op.has_rest() ? OnHost{}(op.rest_only(), oH, oW, sets) : LERF_OK;
     }
 };
 
@@ -768,6 +1159,28 @@ inline int math_args(int op, const double* x, const double* y, int64_t n, const 
         else { using T = double; __VA_ARGS__; } \
     } while (0)
 
+// What an _ordered entry point adds to its sibling's table: the workspace as one more operand (4-byte aligned, one extent for the
+// whole call, intersecting no other operand) and three rules -- it is there, it holds ordered_bytes, max_adders >= 1.  The plain
+// entry points pass none (ord == nullptr) and their tables judge as before.  Sizes the uint32 ids cannot hold are judged FIRST, before
+// any pointer: LERF_EUNSUPPORTED.
+struct OrderedArgs {
+    void* ws;
+    size_t ws_bytes;
+    int max_adders;
+};
+
+inline bool ordered_sizes_ok(int64_t n_entries, int64_t n_targets) { return 4 * n_entries <= 0xffffffffLL && n_targets <= 0xffffffffLL; }
+
+inline Operand ordered_ws_operand(const OrderedArgs* ord, int64_t n_entries, int64_t n_targets, int n_sets) {
+    if (!ord) return bytes_operand(nullptr, 0, 4, OPTIONAL);
+    const bool sane = n_sets >= 1 && n_sets <= 65535 && n_entries >= 1 && n_targets >= 1 && ordered_sizes_ok(n_entries, n_targets);
+    return {ord->ws, 1, 4, sane ? (int64_t)OrderedLayout::bytes(n_entries, n_targets, n_sets) : 0, 0, false, true, false, true, true};
+}
+
+inline bool ordered_rules(const OrderedArgs* ord, const Operand& ws) {
+    return !ord || (ord->ws && ord->max_adders >= 1 && ord->ws_bytes >= (size_t)ws.span);
+}
+
 // ------------------------------------------------------------------------------------------------ the operations, over a runner
 template <typename RUN>
 int build(RUN run, int model, const double* params, int n_params, void* out, int out_dtype, int64_t stride, int oH, int oW, int i0, int j0) {
@@ -868,15 +1281,20 @@ int invert_raster(RUN run, SCATTER scatter, const void* f, int f_dtype, int64_t 
 template <typename RUN>
 int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
                 const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets, int64_t a_set, int64_t b_set, int64_t gout_set,
-                int64_t ga_set, int64_t gb_set) {
-    enum { A, B, GOUT, GA, GB };
+                int64_t ga_set, int64_t gb_set, const OrderedArgs* ord = nullptr) {
+    enum { A, B, GOUT, GA, GB, WS };
     const bool one_ga_many_a = n_sets > 1 && grad_a && ga_set == 0 && a_set != 0;      // one gradient buffer belongs to ONE shared outer map
+    const bool two_writers = ord && n_sets > 1 && grad_a && ga_set == 0;               // ordered: a target has ONE owner, so one set
+    const int64_t n_entries = (int64_t)oH * oW, n_targets = (int64_t)aH * aW;
+    if (ord && aH >= 2 && aW >= 2 && oH >= 1 && oW >= 1 && !ordered_sizes_ok(n_entries, n_targets)) return LERF_EUNSUPPORTED;
+    const Operand ws = ordered_ws_operand(ord, n_entries, n_targets, n_sets);
     const int rc = check_call(n_sets,
                               {map_operand(a, a_dtype, a_stride, aH, aW, a_set, SHARE), map_operand(b, b_dtype, b_stride, oH, oW, b_set),
                                dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_a, LERF_F64, aH, aW, ga_set, SHARE | OPTIONAL),
-                               dense_operand(grad_b, LERF_F64, oH, oW, gb_set, OPTIONAL)},
-                              {{GA, A}, {GA, B}, {GA, GOUT}, {GB, A}, {GB, B}, {GB, GOUT}, {GA, GB}},
-                              aH >= 2 && aW >= 2 && tile_ok(oH, oW, 0, 0) && (grad_a || grad_b) && !one_ga_many_a);
+                               dense_operand(grad_b, LERF_F64, oH, oW, gb_set, OPTIONAL), ws},
+                              {{GA, A}, {GA, B}, {GA, GOUT}, {GB, A}, {GB, B}, {GB, GOUT}, {GA, GB}, {WS, A}, {WS, B}, {WS, GOUT}, {WS, GA}, {WS, GB}},
+                              aH >= 2 && aW >= 2 && tile_ok(oH, oW, 0, 0) && (grad_a || grad_b) && !one_ga_many_a && !two_writers &&
+                                  ordered_rules(ord, ws));
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB,
         return run(ComposeBwdOp<TA, TB>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, {grad_out, 2 * (int64_t)oW}, grad_a, grad_b,
@@ -886,12 +1304,18 @@ int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, i
 
 template <typename RUN>
 int invert_bwd(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_stride,
-               const double* grad_out, int oH, int oW, double* grad_f, int n_sets, int64_t f_set, int64_t g_set, int64_t gout_set, int64_t gf_set) {
-    enum { F, G, GOUT, GF };
+               const double* grad_out, int oH, int oW, double* grad_f, int n_sets, int64_t f_set, int64_t g_set, int64_t gout_set, int64_t gf_set,
+               const OrderedArgs* ord = nullptr) {
+    enum { F, G, GOUT, GF, WS };
+    const int64_t n_entries = (int64_t)oH * oW, n_targets = (int64_t)fH * fW;
+    if (ord && fH >= 2 && fW >= 2 && oH >= 1 && oW >= 1 && !ordered_sizes_ok(n_entries, n_targets)) return LERF_EUNSUPPORTED;
+    const Operand ws = ordered_ws_operand(ord, n_entries, n_targets, n_sets);
+    // grad_f is never shared between sets (no SHARE: a set stride of 0 in a batch is refused), so a target has one owner
     const int rc = check_call(n_sets,
                               {map_operand(f, f_dtype, f_stride, fH, fW, f_set, SHARE), map_operand(g, g_dtype, g_stride, oH, oW, g_set),
-                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_f, LERF_F64, fH, fW, gf_set)},
-                              {{GF, F}, {GF, G}, {GF, GOUT}}, fH >= 2 && fW >= 2 && tile_ok(oH, oW, 0, 0));
+                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_f, LERF_F64, fH, fW, gf_set), ws},
+                              {{GF, F}, {GF, G}, {GF, GOUT}, {WS, F}, {WS, G}, {WS, GOUT}, {WS, GF}},
+                              fH >= 2 && fW >= 2 && tile_ok(oH, oW, 0, 0) && ordered_rules(ord, ws));
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(g_dtype, TG,
         return run(InvertBwdOp<TF, TG>{{(const TF*)f, f_stride}, fH, fW, {(const TG*)g, g_stride}, {grad_out, 2 * (int64_t)oW}, grad_f, f_set, g_set,
@@ -954,13 +1378,18 @@ inline bool splat_dims(int dtype, int C, int H, int W, int oH, int oW) {
 // the forward warp: x [n_sets][C][H][W], f the map of the SOURCE frame [H][W], m [n_sets][H][W] or null, acc [n_sets][C + norm][oH][oW]
 template <typename RUN>
 int splat(RUN run, const void* x, int dtype, int C, int H, int W, int64_t x_set, const void* f, int f_dtype, int64_t f_stride, int64_t f_set,
-          const void* m, int64_t m_set, void* acc, int with_norm, int oH, int oW, int64_t acc_set, int n_sets) {
-    enum { X, F, M, ACC };
+          const void* m, int64_t m_set, void* acc, int with_norm, int oH, int oW, int64_t acc_set, int n_sets, const OrderedArgs* ord = nullptr) {
+    enum { X, F, M, ACC, WS };
     const size_t el = depth_bytes(dtype);
+    const int64_t n_entries = (int64_t)H * W, n_targets = (int64_t)oH * oW;
+    if (ord && H >= 1 && W >= 1 && oH >= 1 && oW >= 1 && !ordered_sizes_ok(n_entries, n_targets)) return LERF_EUNSUPPORTED;
+    const Operand ws = ordered_ws_operand(ord, n_entries, n_targets, n_sets);
+    // acc is never shared between sets (no SHARE: a set stride of 0 in a batch is refused), so a target has one owner
     const int rc = check_call(n_sets,
                               {planes_operand(x, el, C, H, W, x_set), map_operand(f, f_dtype, f_stride, H, W, f_set, SHARE),
-                               planes_operand(m, el, 1, H, W, m_set, OPTIONAL), planes_operand(acc, el, C + (with_norm ? 1 : 0), oH, oW, acc_set)},
-                              {{ACC, X}, {ACC, M}, {ACC, F}}, splat_dims(dtype, C, H, W, oH, oW) && (with_norm == 0 || with_norm == 1), LERF_EINVAL);
+                               planes_operand(m, el, 1, H, W, m_set, OPTIONAL), planes_operand(acc, el, C + (with_norm ? 1 : 0), oH, oW, acc_set), ws},
+                              {{ACC, X}, {ACC, M}, {ACC, F}, {WS, X}, {WS, F}, {WS, M}, {WS, ACC}},
+                              splat_dims(dtype, C, H, W, oH, oW) && (with_norm == 0 || with_norm == 1) && ordered_rules(ord, ws), LERF_EINVAL);
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(dtype, T, LERF_COORDS_DT(f_dtype, TF,
         return run(SplatOp<T, TF>{(const T*)x, {(const TF*)f, f_stride}, (const T*)m, (T*)acc, C, W, oH, oW, with_norm != 0, x_set, f_set, m_set,
@@ -1404,6 +1833,118 @@ int lerf_splat_bwd_host(const void* x, int dtype, int C, int H, int W, int64_t x
                         double* grad_f, int64_t grad_f_set_stride, int n_sets) {
     return splat_bwd(OnHost{}, x, dtype, C, H, W, x_set_stride, f, f_dtype, f_row_stride, f_set_stride, m, m_set_stride, g, with_norm, oH, oW,
                      g_set_stride, grad_x, grad_x_set_stride, grad_m, grad_m_set_stride, grad_f, grad_f_set_stride, n_sets);
+}
+
+// ---- the ordered scatter: the same operation templates under OrderedOnDevice / OrderedOnHost
+size_t lerf_scatter_ordered_workspace_bytes(int64_t n_entries, int64_t n_targets, int n_sets) {
+    if (n_entries < 1 || n_targets < 1 || n_sets < 1 || n_sets > 65535 || !ordered_sizes_ok(n_entries, n_targets)) return 0;
+    return OrderedLayout::bytes(n_entries, n_targets, n_sets);
+}
+
+int lerf_scan_exclusive_u32_block(void) { return kScanBlock; }
+
+size_t lerf_scan_exclusive_u32_workspace_bytes(int64_t n) { return n < 1 || n > 0xffffffffLL ? 0 : sizeof(uint32_t) * (size_t)scan_partials(n); }
+
+int lerf_scan_exclusive_u32(uint32_t* data, int64_t n, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!data || (uintptr_t)data % 4 != 0 || n < 1 || n > 0xffffffffLL) return LERF_EINVAL;
+    const size_t need = lerf_scan_exclusive_u32_workspace_bytes(n);
+    if (need) {
+        if (!workspace || (uintptr_t)workspace % 4 != 0 || workspace_bytes < need) return LERF_EINVAL;
+        const uintptr_t a = (uintptr_t)data, b = (uintptr_t)workspace;
+        if (a < b + need && b < a + 4 * (size_t)n) return LERF_EINVAL;
+    }
+    clear_stale_error();
+    scan_exclusive_u32((hipStream_t)stream, data, n, 1, n, (uint32_t*)workspace, nullptr);
+    return launch_status();
+}
+
+int lerf_scan_exclusive_u32_host(uint32_t* data, int64_t n) {
+    if (!data || (uintptr_t)data % 4 != 0 || n < 1 || n > 0xffffffffLL) return LERF_EINVAL;
+    scan_exclusive_u32_host(data, n);
+    return LERF_OK;
+}
+
+int lerf_splat_ordered(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride, const void* f, int f_dtype, int64_t f_row_stride,
+                       int64_t f_set_stride, const void* m, int64_t m_set_stride, void* acc, int with_norm, int oH, int oW,
+                       int64_t acc_set_stride, int n_sets, void* workspace, size_t workspace_bytes, int max_adders, void* stream) {
+    const OrderedArgs ord{workspace, workspace_bytes, max_adders};
+    return splat(OrderedOnDevice{(hipStream_t)stream, workspace, max_adders}, x, dtype, C, H, W, x_set_stride, f, f_dtype, f_row_stride,
+                 f_set_stride, m, m_set_stride, acc, with_norm, oH, oW, acc_set_stride, n_sets, &ord);
+}
+
+int lerf_splat_ordered_host(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride, const void* f, int f_dtype,
+                            int64_t f_row_stride, int64_t f_set_stride, const void* m, int64_t m_set_stride, void* acc, int with_norm, int oH,
+                            int oW, int64_t acc_set_stride, int n_sets, void* workspace, size_t workspace_bytes, int max_adders) {
+    const OrderedArgs ord{workspace, workspace_bytes, max_adders};
+    return splat(OrderedOnHost{workspace, max_adders}, x, dtype, C, H, W, x_set_stride, f, f_dtype, f_row_stride, f_set_stride, m, m_set_stride,
+                 acc, with_norm, oH, oW, acc_set_stride, n_sets, &ord);
+}
+
+int lerf_coords_compose_bwd_batched_ordered(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                            int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                            int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride,
+                                            int64_t grad_a_set_stride, int64_t grad_b_set_stride, void* workspace, size_t workspace_bytes,
+                                            int max_adders, void* stream) {
+    const OrderedArgs ord{workspace, workspace_bytes, max_adders};
+    return compose_bwd(OrderedOnDevice{(hipStream_t)stream, workspace, max_adders}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride,
+                       grad_out, oH, oW, grad_a, grad_b, n_sets, a_set_stride, b_set_stride, grad_out_set_stride, grad_a_set_stride,
+                       grad_b_set_stride, &ord);
+}
+
+int lerf_coords_compose_bwd_batched_ordered_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                                 int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                                 int n_sets, int64_t a_set_stride, int64_t b_set_stride, int64_t grad_out_set_stride,
+                                                 int64_t grad_a_set_stride, int64_t grad_b_set_stride, void* workspace, size_t workspace_bytes,
+                                                 int max_adders) {
+    const OrderedArgs ord{workspace, workspace_bytes, max_adders};
+    return compose_bwd(OrderedOnHost{workspace, max_adders}, a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a,
+                       grad_b, n_sets, a_set_stride, b_set_stride, grad_out_set_stride, grad_a_set_stride, grad_b_set_stride, &ord);
+}
+
+int lerf_coords_invert_bwd_batched_ordered(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                           int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f, int n_sets,
+                                           int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride, int64_t grad_f_set_stride,
+                                           void* workspace, size_t workspace_bytes, int max_adders, void* stream) {
+    const OrderedArgs ord{workspace, workspace_bytes, max_adders};
+    return invert_bwd(OrderedOnDevice{(hipStream_t)stream, workspace, max_adders}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride,
+                      grad_out, oH, oW, grad_f, n_sets, f_set_stride, g_set_stride, grad_out_set_stride, grad_f_set_stride, &ord);
+}
+
+int lerf_coords_invert_bwd_batched_ordered_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                                int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f, int n_sets,
+                                                int64_t f_set_stride, int64_t g_set_stride, int64_t grad_out_set_stride,
+                                                int64_t grad_f_set_stride, void* workspace, size_t workspace_bytes, int max_adders) {
+    const OrderedArgs ord{workspace, workspace_bytes, max_adders};
+    return invert_bwd(OrderedOnHost{workspace, max_adders}, f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f,
+                      n_sets, f_set_stride, g_set_stride, grad_out_set_stride, grad_f_set_stride, &ord);
+}
+
+int lerf_coords_compose_bwd_ordered(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                    int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                    void* workspace, size_t workspace_bytes, int max_adders, void* stream) {
+    return lerf_coords_compose_bwd_batched_ordered(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a, grad_b, 1,
+                                                   0, 0, 0, 0, 0, workspace, workspace_bytes, max_adders, stream);
+}
+
+int lerf_coords_compose_bwd_ordered_host(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,
+                                         int64_t b_row_stride, const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,
+                                         void* workspace, size_t workspace_bytes, int max_adders) {
+    return lerf_coords_compose_bwd_batched_ordered_host(a, a_dtype, a_row_stride, aH, aW, b, b_dtype, b_row_stride, grad_out, oH, oW, grad_a,
+                                                        grad_b, 1, 0, 0, 0, 0, 0, workspace, workspace_bytes, max_adders);
+}
+
+int lerf_coords_invert_bwd_ordered(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                   int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f, void* workspace,
+                                   size_t workspace_bytes, int max_adders, void* stream) {
+    return lerf_coords_invert_bwd_batched_ordered(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f, 1, 0, 0, 0,
+                                                  0, workspace, workspace_bytes, max_adders, stream);
+}
+
+int lerf_coords_invert_bwd_ordered_host(const void* f, int f_dtype, int64_t f_row_stride, int fH, int fW, const void* g, int g_dtype,
+                                        int64_t g_row_stride, const double* grad_out, int oH, int oW, double* grad_f, void* workspace,
+                                        size_t workspace_bytes, int max_adders) {
+    return lerf_coords_invert_bwd_batched_ordered_host(f, f_dtype, f_row_stride, fH, fW, g, g_dtype, g_row_stride, grad_out, oH, oW, grad_f, 1, 0,
+                                                       0, 0, 0, workspace, workspace_bytes, max_adders);
 }
 
 }  // extern "C"

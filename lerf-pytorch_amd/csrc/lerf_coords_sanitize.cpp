@@ -12,6 +12,10 @@
 // lerf_splat_host and lerf_splat_bwd_host (splat_ops) run one and three sets of both image dtypes and both map dtypes, C = 1 and 3, with and
 // without the norm plane and the weight, a shared and a per-set strided map with NaN, +-inf, 1e300 and frame-edge entries, each gradient
 // half null and given, and their refusals.
+// The ordered twins (ordered_ops: lerf_splat_ordered_host, lerf_coords_compose_bwd_batched_ordered_host, lerf_coords_invert_bwd_batched_ordered_host
+// and lerf_scan_exclusive_u32_host) run their four passes over a workspace of exactly lerf_scatter_ordered_workspace_bytes bytes, two sets,
+// pre-filled targets, entries beyond every edge and NaN entries, with a generous cap (the result must be the plain twin's bytes) and with
+// a cap of 1 (the NaN branch), and a workspace one byte short is refused.
 // It needs no GPU and is never loaded into another process.  Exit status 0 and "ok" on the last line: no report.
 #include "lerf_hip.h"
 
@@ -502,6 +506,110 @@ static void splat_ops(int H, int W, int oH, int oW) {
     splat_ops_of<double>(H, W, oH, oW, LERF_F64);
 }
 
+// the ordered scatter's host twins against the plain ones, byte for byte, on exactly-sized heap buffers
+template <typename T>
+static void ordered_splat_of(int H, int W, int oH, int oW, int dt) {
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int N = 2, C = 3, P = C + 1;
+    const size_t n = (size_t)H * W, on = (size_t)oH * oW;
+    const double special[8][2] = {{nan, 3.0}, {inf, 1.0}, {1e300, 2.0}, {-0.5, 1.25}, {oH - 1.0, 0.5}, {oH - 0.5, 2.0}, {oH - 1.0, oW - 1.0}, {-1.0, (double)oW}};
+    std::vector<double> F(N * 2 * n);
+    for (int s = 0; s < N; ++s)
+        for (size_t e = 0; e < n; ++e) {
+            const int i = (int)(e / W), j = (int)(e % W);
+            const bool sp = (e + s) % 5 == 0 && ((e + s) / 5) % 16 < 8;
+            F[2 * (s * n + e)] = sp ? special[((e + s) / 5) % 16][0] : (i + 0.37) * (oH + 2.0) / H - 1.5 + 0.7 * std::sin(0.31 * j + s);
+            F[2 * (s * n + e) + 1] = sp ? special[((e + s) / 5) % 16][1] : (j + 0.61) * (oW + 3.0) / W - 2.0;
+        }
+    std::vector<T> x(N * C * n), m(N * n), acc(N * P * on), got, capped;
+    for (size_t k = 0; k < x.size(); ++k) x[k] = (T)std::sin(0.37 * (double)k);
+    for (size_t k = 0; k < m.size(); ++k) m[k] = (T)(1.0 + 0.5 * std::cos(0.21 * (double)k));
+    for (size_t k = 0; k < acc.size(); ++k) acc[k] = (T)std::cos(0.11 * (double)k);
+    got = capped = acc;
+    const size_t bytes = lerf_scatter_ordered_workspace_bytes((int64_t)n, (int64_t)on, N);
+    EXPECT(bytes >= 16 + 4 * N * (on + 4 * n));
+    std::vector<uint32_t> ws(bytes / 4, 0xa5a5a5a5u);
+    const int64_t xs = (int64_t)(C * n), fs = (int64_t)(2 * n), ms = (int64_t)n, as = (int64_t)(P * on);
+    EXPECT(lerf_splat_host(x.data(), dt, C, H, W, xs, F.data(), LERF_F64, 2 * W, fs, m.data(), ms, acc.data(), 1, oH, oW, as, N) == LERF_OK);
+    EXPECT(lerf_splat_ordered_host(x.data(), dt, C, H, W, xs, F.data(), LERF_F64, 2 * W, fs, m.data(), ms, got.data(), 1, oH, oW, as, N, ws.data(),
+                                   bytes, 1 << 20) == LERF_OK);
+    EXPECT(!std::memcmp(acc.data(), got.data(), acc.size() * sizeof(T)));
+    const uint32_t most = ws[1];
+    EXPECT(ws[0] == 0 && most >= 1 && most <= 4 * n);
+    EXPECT(lerf_splat_ordered_host(x.data(), dt, C, H, W, xs, F.data(), LERF_F64, 2 * W, fs, m.data(), ms, capped.data(), 1, oH, oW, as, N, ws.data(),
+                                   bytes, 1) == LERF_OK);
+    EXPECT(ws[1] == most);
+    const std::vector<T> before = capped;
+    EXPECT(lerf_splat_ordered_host(x.data(), dt, C, H, W, xs, F.data(), LERF_F64, 2 * W, fs, m.data(), ms, capped.data(), 1, oH, oW, as, N, ws.data(),
+                                   bytes - 1, 4) == LERF_EINVAL);
+    EXPECT(lerf_splat_ordered_host(x.data(), dt, C, H, W, xs, F.data(), LERF_F64, 2 * W, fs, m.data(), ms, capped.data(), 1, oH, oW, as, N, ws.data(),
+                                   bytes, 0) == LERF_EINVAL);
+    EXPECT(lerf_splat_ordered_host(x.data(), dt, C, H, W, xs, F.data(), LERF_F64, 2 * W, fs, m.data(), ms, capped.data(), 1, oH, oW, as, N, capped.data(),
+                                   bytes, 4) == LERF_EINVAL);
+    EXPECT(!std::memcmp(capped.data(), before.data(), capped.size() * sizeof(T)));
+}
+
+static void ordered_adjoints(int aH, int aW, int oH, int oW) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const int N = 2;
+    const size_t na = (size_t)2 * aH * aW, nb = (size_t)2 * oH * oW;
+    std::vector<double> A(N * na), B(N * nb), g(N * nb), ga(N * na), gb(N * nb), gf(N * na);
+    for (int s = 0; s < N; ++s)
+        for (int i = 0; i < aH; ++i)
+            for (int j = 0; j < aW; ++j) {
+                A[s * na + 2 * (i * aW + j)] = 1.1 * i + 0.2 * std::sin(0.9 * j + s) + 0.05 * i * j;
+                A[s * na + 2 * (i * aW + j) + 1] = 0.9 * j + 0.3 * std::cos(0.7 * i + s) - 0.03 * i * j;
+            }
+    for (size_t e = 0; e < N * nb / 2; ++e) {
+        B[2 * e] = e % 11 == 3 ? nan : -2.5 + std::fmod(0.731 * (double)e, aH + 4.0);      // beyond every edge: the taps clamp onto the border cells
+        B[2 * e + 1] = e % 13 == 5 ? 1e300 : -2.5 + std::fmod(1.137 * (double)e, aW + 4.0);
+    }
+    for (size_t k = 0; k < g.size(); ++k) g[k] = std::sin(0.37 * (double)k);
+    for (size_t k = 0; k < ga.size(); ++k) ga[k] = gf[k] = std::cos(0.19 * (double)k);
+    for (size_t k = 0; k < gb.size(); ++k) gb[k] = std::cos(0.23 * (double)k);
+    std::vector<double> ga2 = ga, gb2 = gb, gf2 = gf;
+    const size_t bytes = lerf_scatter_ordered_workspace_bytes((int64_t)oH * oW, (int64_t)aH * aW, N);
+    std::vector<uint32_t> ws(bytes / 4, 0x5a5a5a5au);
+    const int64_t sa = (int64_t)na, sb = (int64_t)nb;
+    EXPECT(lerf_coords_compose_bwd_batched_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, ga.data(), gb.data(), N, sa,
+                                                sb, sb, sa, sb) == LERF_OK);
+    EXPECT(lerf_coords_compose_bwd_batched_ordered_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, ga2.data(),
+                                                        gb2.data(), N, sa, sb, sb, sa, sb, ws.data(), bytes, 1 << 20) == LERF_OK);
+    EXPECT(same(ga, ga2) && same(gb, gb2) && ws[1] >= 1);
+    EXPECT(lerf_coords_invert_bwd_batched_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, gf.data(), N, sa, sb, sb,
+                                               sa) == LERF_OK);
+    EXPECT(lerf_coords_invert_bwd_batched_ordered_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, gf2.data(), N, sa,
+                                                       sb, sb, sa, ws.data(), bytes, 1 << 20) == LERF_OK);
+    EXPECT(same(gf, gf2));
+    // the cap of 1 (NaN in every target with two adders), each half alone, the single-map forms, a short workspace
+    EXPECT(lerf_coords_compose_bwd_batched_ordered_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, ga2.data(),
+                                                        nullptr, N, sa, sb, sb, sa, 0, ws.data(), bytes, 1) == LERF_OK);
+    EXPECT(lerf_coords_compose_bwd_ordered_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, nullptr, gb2.data(),
+                                                ws.data(), bytes, 4) == LERF_OK);
+    EXPECT(lerf_coords_invert_bwd_ordered_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, gf2.data(), ws.data(),
+                                               bytes, 1) == LERF_OK);
+    const std::vector<double> keep = gf2;
+    EXPECT(lerf_coords_invert_bwd_batched_ordered_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, gf2.data(), N, sa,
+                                                       sb, sb, sa, ws.data(), bytes - 1, 4) == LERF_EINVAL);
+    EXPECT(lerf_coords_compose_bwd_batched_ordered_host(A.data(), LERF_F64, 2 * aW, aH, aW, B.data(), LERF_F64, 2 * oW, g.data(), oH, oW, gf2.data(),
+                                                        nullptr, N, sa, sb, sb, 0, 0, ws.data(), bytes, 4) == LERF_EINVAL);
+    EXPECT(same(gf2, keep));
+}
+
+static void ordered_ops() {
+    ordered_splat_of<float>(1, 1, 1, 1, LERF_F32);
+    ordered_splat_of<float>(23, 31, 29, 37, LERF_F32);
+    ordered_splat_of<double>(5, 67, 7, 61, LERF_F64);
+    ordered_splat_of<float>(35, 65, 8, 8, LERF_F32);            // several hundred adders per target: the heap sort
+    ordered_splat_of<double>(35, 65, 3, 2, LERF_F64);
+    ordered_adjoints(2, 2, 1, 1);
+    ordered_adjoints(7, 9, 11, 13);
+    ordered_adjoints(3, 4, 40, 33);                             // segments beyond the insertion sort
+    std::vector<uint32_t> v(1024 * 3 + 5, 3u);
+    EXPECT(lerf_scan_exclusive_u32_host(v.data(), (int64_t)v.size()) == LERF_OK && v[0] == 0 && v.back() == 3u * (uint32_t)(v.size() - 1));
+    EXPECT(lerf_scan_exclusive_u32_host(v.data(), 0) == LERF_EINVAL && lerf_scan_exclusive_u32_host(nullptr, 4) == LERF_EINVAL);
+}
+
 int main() {
     const double pi = 3.14159265358979323846;
     const double fish[17] = {1.0 / 35, 0, -27.5 / 35, 0, 1.0 / 33, -16.0 / 33, 0.001, -0.0005, 1, 61.5, 58.75, 25.25, 17.5, 0.05, -0.012, 0.004, -0.0009};
@@ -553,6 +661,7 @@ int main() {
     splat_ops(1, 1, 5, 9);
     splat_ops(5, 67, 7, 61);
     splat_ops(23, 31, 29, 37);
+    ordered_ops();
     std::printf(fails ? "%d check(s) failed\n" : "ok\n", fails);
     return fails ? 1 : 0;
 }

@@ -1189,24 +1189,32 @@ def coords_invert_raster(f, out_hw, depth=None, dtype=None, out=None, origin=(0,
     return _lib.coords_invert_raster_on(_lib.DeviceOperands(), f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys)
 
 
-def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):
+def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True), deterministic=False, max_adders=4096):
     """lerf_coords_compose_bwd: ACCUMULATE the adjoint of coords_compose(outer, inner) of grad_out (float64 contiguous [oH, oW, 2])
     into grad_outer (float64 contiguous [aH, aW, 2]: a bilinear scatter by float64 atomic adds, reproducible up to the rounding of
     a reordered sum) and grad_inner (float64 contiguous [oH, oW, 2]: one writer per entry, bit-reproducible); None: zeroed ones;
     need[k] False skips that half and returns None for it.  The maps are device tensors under the strided contract, the outer
     map at least 2 x 2.  One launch on the current stream, no sync -> (grad_outer, grad_inner).  A batch: inner, grad_out and
     grad_inner [B, oH, oW, 2] with outer and grad_outer [B, aH, aW, 2], or ONE shared outer [aH, aW, 2] whose grad_outer [aH, aW, 2]
-    gains the sum over the samples -- still one launch (lerf_coords_compose_bwd_batched)."""
-    return _lib.coords_compose_bwd_on(_lib.DeviceOperands(), outer, inner, grad_out, grad_outer, grad_inner, need)
+    gains the sum over the samples -- still one launch (lerf_coords_compose_bwd_batched).
+    deterministic=True: lerf_coords_compose_bwd_ordered -- grad_outer is summed in the host twin's order and equals
+    _lib.coords_compose_bwd_host bit for bit, from run to run; the workspace is the stream's cached scratch.  After the launches the
+    largest number of entries adding into one element is read back (ONE 4-byte copy and a synchronisation of the stream); above
+    max_adders: LerfError, that element holds NaN.  One shared outer map in a batch: every sample scatters into a gradient of its own
+    and grad_outer gains them one after the other, sample 0 first."""
+    return _lib.coords_compose_bwd_on(_lib.DeviceOperands(), outer, inner, grad_out, grad_outer, grad_inner, need,
+                                      int(max_adders) if deterministic else None)
 
 
-def coords_invert_bwd(f, inverse, grad_out, grad_f=None):
+def coords_invert_bwd(f, inverse, grad_out, grad_f=None, deterministic=False, max_adders=4096):
     """lerf_coords_invert_bwd: ACCUMULATE the adjoint of inverse = coords_invert(f, ...) of grad_out (float64 contiguous
     [oH, oW, 2]) into grad_f (float64 contiguous [fH, fW, 2]; None: a zeroed one) by the implicit function theorem: the bilinear
     scatter of -J^-T grad_out at the cell of every entry of the inverse (float64 atomic adds); NaN entries of the inverse, NaN
     corners and folded cells contribute nothing.  Device maps under the strided contract.  One launch on the current stream, no
-    sync.  A batch: f and grad_f [B, fH, fW, 2], inverse and grad_out [B, oH, oW, 2], one launch (lerf_coords_invert_bwd_batched)."""
-    return _lib.coords_invert_bwd_on(_lib.DeviceOperands(), f, inverse, grad_out, grad_f)
+    sync.  A batch: f and grad_f [B, fH, fW, 2], inverse and grad_out [B, oH, oW, 2], one launch (lerf_coords_invert_bwd_batched).
+    deterministic=True: lerf_coords_invert_bwd_ordered (DESIGN 4.20), bit-equal to _lib.coords_invert_bwd_host and from run to run;
+    then the largest count is read back (one 4-byte copy and a synchronisation); above max_adders: LerfError."""
+    return _lib.coords_invert_bwd_on(_lib.DeviceOperands(), f, inverse, grad_out, grad_f, int(max_adders) if deterministic else None)
 
 
 def coords_reproject(kind, params, depth, dtype=None, out=None, origin=(0, 0), depth_out=None):
@@ -1233,14 +1241,35 @@ def coords_reproject_bwd(kind, params, depth, grad_map, grad_depth_out=None, gra
                                         origin)
 
 
-def splat(src, map, out_hw, weight=None, norm=False, acc=None):
+def splat(src, map, out_hw, weight=None, norm=False, acc=None, deterministic=False, max_adders=4096):
     """lerf_splat: the forward warp by summation splatting -- every pixel of src is ADDED into the out_hw frame at the position the
     forward map gives it, bilinearly over up to four pixels; mass that leaves the frame is lost, a non-finite entry contributes nothing.
     src [C, H, W] or [B, C, H, W] (device, float32 / float64); map [H, W, 2] (shared by the batch) or [B, H, W, 2], float32 / float64;
     weight None or src's dtype [H, W] / [B, H, W] -> acc [.., C (+ 1 with norm: the plane of the weights), oH, oW] of src's dtype; acc
     given: ACCUMULATED INTO (several frames into one canvas).  ONE launch on the current stream whatever B, no sync; one no-return float
-    atomic add per tap and plane, so two runs agree up to the rounding of a reordered sum (exactly, where every partial sum is exact)."""
-    return _lib.splat_on(_lib.DeviceOperands(), src, map, out_hw, weight, norm, acc)
+    atomic add per tap and plane, so two runs agree up to the rounding of a reordered sum (exactly, where every partial sum is exact).
+    deterministic=True: lerf_splat_ordered -- count, scan, fill, then one thread per output pixel sorts its source pixels
+    and adds them in row-major order: bit-equal to _lib.splat_host and from run to run, into a pre-filled acc too.  Six launches and a
+    memset on the current stream over the stream's cached scratch; afterwards the largest number of source pixels adding into one
+    output pixel is read back (ONE 4-byte copy and a synchronisation of the stream).  Above max_adders: LerfError -- that pixel holds
+    NaN in every plane, every other pixel is exact."""
+    return _lib.splat_on(_lib.DeviceOperands(), src, map, out_hw, weight, norm, acc, int(max_adders) if deterministic else None)
+
+
+def scan_exclusive_u32(data):
+    """lerf_scan_exclusive_u32: the exclusive prefix sums (modulo 2^32) of a contiguous int32 device vector (its bits read as
+    uint32), in place, by multi-kernel passes on the current stream -- pass 2 of the ordered scatter on its own"""
+    torch = _torch()
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.int32 and data.dim() == 1 and data.is_contiguous()
+            and data.numel() >= 1):
+        raise ValueError("lerf_scan_exclusive_u32: data must be a contiguous int32 device vector")
+    L = _lib.lib()
+    need = int(L.lerf_scan_exclusive_u32_workspace_bytes(data.numel()))
+    ws = _cached_workspace(need, data.device) if need else None
+    with _lib.on_device(data):
+        _lib.check(L.lerf_scan_exclusive_u32(data.data_ptr(), data.numel(), None if ws is None else ws.data_ptr(), need,
+                                             _lib.current_stream(data.device)), "lerf_scan_exclusive_u32")
+    return data
 
 
 def splat_bwd(src, map, grad, weight=None, norm=False, need=(True, True, True)):
