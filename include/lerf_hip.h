@@ -139,6 +139,16 @@ typedef struct {
 #define LERF_GEO_TILE_ROWS_16 256
 #define LERF_GEO_INPUT_DEVICE 4    /* lerf_sr_fused_u8: the input frames are device memory / pinned host memory (read over PCIe from inside the */
 #define LERF_GEO_INPUT_HOST 8      /* kernel, once per pixel); neither bit: the library asks the runtime (one hipPointerGetAttributes per call) */
+#define LERF_GEO_EXACT_X2 512      /* the caller's promise that the tables are the x2 SR tables of the WHOLE frame (lerf_sr_axis_tables with scale
+                                    * 2.0 and out = 2 x in on both axes, as lerf_sr_geometry_flags verifies): RGB launches of lerf_sr_fused_u8 then
+                                    * run the X2 flavour of the tile-fused kernels, which takes the stage-3 geometry from the closed form
+                                    * (lerf_sr_x2_tables) and never reads left_* / dis_* (they must still be passed; dis_*64 still arm the tie
+                                    * guard).  Taken only with S = 2 (the 4 x 4 support keeps the tables: registers), 64-row tiles (launches small
+                                    * enough for the 32- / 16-row tiles keep the tables), out_h = 2 H, out_w = 2 W and no region of interest,
+                                    * never by ragged launches; a launch that sets the bit
+                                    * with other sizes or a region runs the table path (a slice of x2 tables starts at an arbitrary origin).
+                                    * LERF_GEO_FORCE_GENERAL wins.  Same bytes either way */
+#define LERF_GEO_FORCE_TABLES 1024 /* diagnostic: the table path although LERF_GEO_EXACT_X2 is set (tests, A/B runs) */
 
 /* Homography geometry (resize_right/resize_right2d_numpy.py:306-407): evaluated
  * per output pixel on the device in float64; pad_* come from lerf_warp_pads. */
@@ -206,6 +216,20 @@ int lerf_sr_axis_tables(int n_in, int n_out, double scale, int S,
  * field_of_view / dis tensors, including the scales where float32 and float64 put a support boundary on different
  * sides (x3, S=2).  pads may be NULL. */
 int lerf_sr_axis_tables_f32(int n_in, int n_out, double scale, int S, int32_t* left, float* dis32, int32_t* pads);
+
+/* Exact x2 (scale 2.0, n_out = 2 n_in, even S) in closed form: output i has first tap (i + 1) / 2 - S / 2 and tap k at
+ * distance S / 2 - k - 1/4 (even i) or S / 2 - k - 3/4 (odd i) -- the same bits in float32 and float64.
+ * lerf_sr_x2_tables writes the closed form as tables (any of left / dis64 / dis32 may be NULL).
+ * lerf_sr_x2_owned writes, for every tile t of `tile` LR pixels along one axis of n_in pixels, the owned outputs
+ * ranges[2 t] .. ranges[2 t + 1] (half open) -- what the X2 kernels compute instead of searching `left`.
+ * lerf_sr_geometry_flags is the host geometry builder's verdict on a pair of axis tables it has just built (host memory):
+ * LERF_GEO_EXACT_X2 when both scales are exactly 2.0, out = 2 x in on both axes and every entry equals the closed form
+ * bit for bit, else 0 (also for bad arguments). */
+int lerf_sr_x2_tables(int n_out, int S, int32_t* left, double* dis64, float* dis32);
+int lerf_sr_x2_owned(int n_in, int tile, int32_t* ranges);
+int lerf_sr_geometry_flags(int H, int W, int out_h, int out_w, double scale_h, double scale_w, int S,
+                           const int32_t* left_r, const double* dis_r64, const float* dis_r32,
+                           const int32_t* left_c, const double* dis_c64, const float* dis_c32);
 
 /* ceil(scale * n_in) (resize_right/resize_right2d_numpy.py:41-45) */
 int lerf_out_size(int n_in, double scale);

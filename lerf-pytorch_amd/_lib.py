@@ -40,6 +40,7 @@ def pad_mode_code(name, allowed):
 
 EXPORTS = [
     "lerf_abi_version", "lerf_strerror", "lerf_device_count", "lerf_mode_offsets", "lerf_sr_axis_tables", "lerf_sr_axis_tables_f32",
+    "lerf_sr_x2_tables", "lerf_sr_x2_owned", "lerf_sr_geometry_flags",
     "lerf_out_size", "lerf_invert3x3", "lerf_warp_pads", "lerf_lut_interp_i16", "lerf_lut_interp", "lerf_lut_interp_ex", "lerf_numer_epilogue_f32", "lerf_fused_lutpack_bytes", "lerf_fused_lutpack_build",
     "lerf_lut_stages_u8",
     "lerf_resize", "lerf_warp", "lerf_sr_fused_workspace_bytes", "lerf_sr_fused_supported", "lerf_sr_fused_u8",
@@ -111,6 +112,7 @@ class SrGeo(C.Structure):
 
 GEO_FORCE_GENERAL, GEO_SINGLE_LAUNCH, GEO_INPUT_DEVICE, GEO_INPUT_HOST, GEO_X2_TABLES, GEO_NO_PERSIST = 1, 2, 4, 8, 16, 32
 GEO_TILE_ROWS_64, GEO_TILE_ROWS_32, GEO_TILE_ROWS_16 = 64, 128, 256
+GEO_EXACT_X2, GEO_FORCE_TABLES = 512, 1024      # the caller's promise of whole-frame x2 tables / diagnostic: the table path anyway
 
 
 class SrItem(C.Structure):          # lerf_sr_item_t: one frame of a ragged launch
@@ -210,6 +212,9 @@ def lib():
     L.lerf_mode_offsets.argtypes = [C.c_char, C.c_int, C.c_void_p, C.c_void_p]
     L.lerf_sr_axis_tables.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.lerf_sr_axis_tables_f32.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lerf_sr_x2_tables.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lerf_sr_x2_owned.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.lerf_sr_geometry_flags.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 6
     L.lerf_out_size.argtypes = [C.c_int, C.c_double]
     L.lerf_invert3x3.argtypes = [C.c_void_p, C.c_void_p]
     L.lerf_warp_pads.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -424,6 +429,33 @@ def sr_axis_tables(n_in: int, n_out: int, scale: float, S: int):
     check(lib().lerf_sr_axis_tables(int(n_in), int(n_out), float(scale), int(S), left.ctypes.data,
                                     dis64.ctypes.data, dis32.ctypes.data, pads.ctypes.data), "lerf_sr_axis_tables")
     return left, dis64, dis32, (int(pads[0]), int(pads[1]))
+
+
+def sr_x2_tables(n_out: int, S: int):
+    """(left, dis64, dis32) of exact x2 in closed form (lerf_sr_x2_tables): what sr_axis_tables(n, 2 n, 2.0, S) gives, bit for bit"""
+    left = np.empty(n_out, np.int32)
+    dis64 = np.empty((n_out, S), np.float64)
+    dis32 = np.empty((n_out, S), np.float32)
+    check(lib().lerf_sr_x2_tables(int(n_out), int(S), left.ctypes.data, dis64.ctypes.data, dis32.ctypes.data), "lerf_sr_x2_tables")
+    return left, dis64, dis32
+
+
+def sr_x2_owned(n_in: int, tile: int):
+    """[tiles][2] int32: the outputs [o0, o1) every tile of `tile` LR pixels owns along an axis of n_in pixels at exact x2"""
+    r = np.empty(((int(n_in) + int(tile) - 1) // int(tile), 2), np.int32)
+    check(lib().lerf_sr_x2_owned(int(n_in), int(tile), r.ctypes.data), "lerf_sr_x2_owned")
+    return r
+
+
+def sr_geometry_flags(in_hw, out_hw, scales, S, left_r, dis_r64, dis_r32, left_c, dis_c64, dis_c32) -> int:
+    """GEO_EXACT_X2 when the host tables of both axes are the exact x2 tables of the whole frame (lerf_sr_geometry_flags), else 0"""
+    arrs = [np.ascontiguousarray(a, t) for a, t in ((left_r, np.int32), (dis_r64, np.float64), (dis_r32, np.float32),
+                                                    (left_c, np.int32), (dis_c64, np.float64), (dis_c32, np.float32))]
+    if arrs[0].size != out_hw[0] or arrs[3].size != out_hw[1] or any(a.size != n * S for a, n in
+                                                                     zip(arrs[1:3] + arrs[4:6], (out_hw[0],) * 2 + (out_hw[1],) * 2)):
+        return 0
+    return int(lib().lerf_sr_geometry_flags(int(in_hw[0]), int(in_hw[1]), int(out_hw[0]), int(out_hw[1]), float(scales[0]), float(scales[1]),
+                                            int(S), *[a.ctypes.data for a in arrs]))
 
 
 def sr_axis_tables_f32(n_in: int, n_out: int, scale: float, S: int):

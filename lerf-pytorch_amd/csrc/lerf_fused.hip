@@ -9,6 +9,7 @@
 // AmplifiedLinearResize2dNumpy, resize_right/resize_right2d_numpy.py:142-282).
 #define LERF_FUSED_NS fused
 #define LERF_FUSED_CH 3
+#define LERF_FUSED_X2 1             // the exact-x2 flavour of the SR kernels (LERF_GEO_EXACT_X2)
 #define LERF_FUSED_WITH_WARP 1      // this instance also carries the tile-fused warp (launch_warp_fused)
 #include "lerf_fused_impl.h"
 

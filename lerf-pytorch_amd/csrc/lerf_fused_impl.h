@@ -30,7 +30,7 @@
 //   ACC  int16 partial sums             stage 1 (and stage 2 of LeRF-L)
 //   LST  pixel lists sorted by bin      stage 2 (LeRF-G), transient (under the piece, which waits in registers)
 //   D    (hq0,hq1,hq2,feat) dwords      stage 3, overlays LUT (52 KB / 55 KB)
-//   GEO  tile geometry tables           stage 3 (9 KB; staged at kernel start for S=2)
+//   GEO  tile geometry tables           stage 3 (9 KB; staged at kernel start for S=2; the exact-x2 kernels leave it unused: GeoX2)
 //   TQ   rounding-tie queue             stage 3 (8 KB, behind D)
 //   OUT  the tile's output block        stage 3, block tasks (2 x 2 outputs that share their taps: integer x2 LeRF-G, LeRF-L):
 //        assembled byte by byte (132 x 416 B behind TQ), ties patched in it, stored as whole 16-byte chunks
@@ -1405,22 +1405,118 @@ struct MagicDiv {
     unsigned n, magic;
     __device__ __forceinline__ explicit MagicDiv(int n_)
         : n((unsigned)n_), magic((unsigned)((0x100000000ull + (unsigned)n_ - 1) / (unsigned)(n_ > 0 ? n_ : 1))) {}
+    __device__ __forceinline__ constexpr MagicDiv(unsigned n_, unsigned magic_) : n(n_), magic(magic_) {}
     __device__ __forceinline__ int div(int t) const { return n == 1 ? t : (int)__umulhi((unsigned)t, magic); }   // (ceil(2^32 / 1) does not fit the 32-bit magic)
+    // n_ == the power of two N, known at compile time to be the common case (KNOWN: the interior tiles of the X2 kernels):
+    // the magic is 2^32 / N, a shift, and the 64-bit division is left to the other tiles
+    template <bool KNOWN, int N>
+    __device__ __forceinline__ static MagicDiv of(int n_) {
+        constexpr bool POW2 = N > 1 && (N & (N - 1)) == 0;               // (TW is one for RGB frames: 64)
+        if (KNOWN && POW2 && n_ == N) return MagicDiv((unsigned)N, (unsigned)(0x100000000ull / (unsigned)N));
+        return MagicDiv(n_);
+    }
 };
 
-// the tile's geometry tables in LDS: first tap (hyper-region coordinates) and the S distances of every owned output row /
-// column, and the first row of every row group
+// The GEOMETRY SOURCE of stage 3: first tap (hyper-region coordinates) and the S distances (LeRF-G: pre-multiplied by
+// gauss_scale) of every owned output row / column, the first row of every row group, the first column of every column group
+// (LeRF-L block tasks) and an output's float64 distances for the tie pass.  Stage3 and the task functions are written against
+// it; there are two:
+//   GeoTab  the tile's slice of the caller's tables, staged in LDS (Dims::OFF_GEO) -- any scale factors;
+//   GeoX2   the closed form of exact x2 (x2_left / x2_dis, lerf_host_geometry.h) -- the X2 kernels: no table is read.
 template <typename D, int S>
-struct GeoTables {
-    int* lr; float* dr; int* lc; float* dc; int* grp;
-    __device__ __forceinline__ explicit GeoTables(uint8_t* smem)
-        : lr(reinterpret_cast<int*>(smem + D::OFF_GEO)), dr(reinterpret_cast<float*>(lr + D::GEO_ROWS)), lc(reinterpret_cast<int*>(dr + D::GEO_ROWS * S)),
-          dc(reinterpret_cast<float*>(lc + D::GEO_COLS)), grp(reinterpret_cast<int*>(dc + D::GEO_COLS * S)) {}
+struct GeoTab {
+    static constexpr bool X2 = false;
+    int* lr_; float* dr_; int* lc_; float* dc_; int* grp_; int* cgrp_;
+    const double* dis_r64; const double* dis_c64;      // the frame's float64 tables (NULL: tie guard off)
+    int i0, j0;                                        // the owned block's first row / column in them
+    __device__ __forceinline__ explicit GeoTab(uint8_t* smem)
+        : lr_(reinterpret_cast<int*>(smem + D::OFF_GEO)), dr_(reinterpret_cast<float*>(lr_ + D::GEO_ROWS)), lc_(reinterpret_cast<int*>(dr_ + D::GEO_ROWS * S)),
+          dc_(reinterpret_cast<float*>(lc_ + D::GEO_COLS)), grp_(reinterpret_cast<int*>(dc_ + D::GEO_COLS * S)),
+          cgrp_(reinterpret_cast<int*>(smem + D::OFF_CGRP)), dis_r64(nullptr), dis_c64(nullptr), i0(0), j0(0) {}
+    __device__ __forceinline__ int lr(int il) const { return lr_[il]; }
+    __device__ __forceinline__ int lc(int jl) const { return lc_[jl]; }
+    __device__ __forceinline__ float dr(int il, int b) const { return dr_[il * S + b]; }
+    __device__ __forceinline__ float dc(int jl, int a) const { return dc_[jl * S + a]; }
+    // ... of row / column 2 * pair + off (the block forms: off is the same for every task of a tile)
+    __device__ __forceinline__ float dr_pair(int pair, int off, int b) const { return dr_[(2 * pair + off) * S + b]; }
+    __device__ __forceinline__ float dc_pair(int pair, int off, int a) const { return dc_[(2 * pair + off) * S + a]; }
+    __device__ __forceinline__ int grp(int g) const { return grp_[g]; }
+    __device__ __forceinline__ int cgrp(int h) const { return cgrp_[h]; }
+    __device__ __forceinline__ void dis64(int il, int jl, double (&dx)[S], double (&dy)[S]) const {
+#pragma unroll
+        for (int b = 0; b < S; ++b) dx[b] = dis_r64[(int64_t)(i0 + il) * S + b];
+#pragma unroll
+        for (int a = 0; a < S; ++a) dy[a] = dis_c64[(int64_t)(j0 + jl) * S + a];
+    }
 };
 
-// ---- owned output rows / columns: four wave-parallel searches in the global tables -> ctl[CTL_I0 .. CTL_J1]
-template <typename D>
+template <typename D, int S>
+struct GeoX2 {
+    static constexpr bool X2 = true;
+    static_assert(S == 2, "the exact-x2 flavour serves the 2 x 2 support");
+    // lr(il) = (il + rbase) >> 1.  rbase = 1 when the block starts with the frame's single first row (output 0), else 0: the block
+    // then starts at an odd output, so row il is an EVEN output of the frame exactly when (il + rbase) is odd.  Columns alike.
+    int rbase, cbase;
+    int nrow, ncol;
+    bool rows_align;                     // (Stage3::rows_align: without it every row is a group of its own)
+    float kd[2][S];                      // distance of tap k from an even / odd output, times the kind's scale: formed once per thread
+    __device__ __forceinline__ explicit GeoX2(uint8_t*) {}
+    __device__ __forceinline__ void set(int i0, int j0, int nrow_, int ncol_, int ty0, int tx0, bool rows_align_, float gscale) {
+        rbase = i0 + 1 - 2 * ty0; cbase = j0 + 1 - 2 * tx0;
+        nrow = nrow_; ncol = ncol_; rows_align = rows_align_;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                kd[p][k] = (float)x2_dis(p, k, S) * gscale;         // the product stage3_geo_stage forms
+            }
+    }
+    __device__ __forceinline__ int lr(int il) const { return (il + rbase) >> 1; }
+    __device__ __forceinline__ int lc(int jl) const { return (jl + cbase) >> 1; }
+    __device__ __forceinline__ float dr(int il, int b) const { return ((il + rbase) & 1) ? kd[0][b] : kd[1][b]; }
+    __device__ __forceinline__ float dc(int jl, int a) const { return ((jl + cbase) & 1) ? kd[0][a] : kd[1][a]; }
+    // row / column 2 * pair + off: its parity does not depend on the pair -- the block forms' distances are the same for every task
+    __device__ __forceinline__ float dr_pair(int, int off, int b) const { return ((off + rbase) & 1) ? kd[0][b] : kd[1][b]; }
+    __device__ __forceinline__ float dc_pair(int, int off, int a) const { return ((off + cbase) & 1) ? kd[0][a] : kd[1][a]; }
+    // row groups = the runs of equal first taps (pairs; a leading / trailing single), column groups of LeRF-L alike
+    __device__ __forceinline__ int grp(int g) const { return rows_align ? min(max(2 * g - rbase, 0), nrow) : g; }
+    __device__ __forceinline__ int ngrp() const { return rows_align ? (nrow + rbase + 1) >> 1 : nrow; }
+    __device__ __forceinline__ int cgrp(int h) const { return min(max(2 * h - cbase, 0), ncol); }
+    __device__ __forceinline__ int ncgrp() const { return (ncol + cbase + 1) >> 1; }
+    // rows per group when every group has as many, else 0 (what wave 0 of stage3_census finds in the group table)
+    __device__ __forceinline__ int gsame() const {
+        const int ng = ngrp();
+        if (ng == 0) return 0;
+        const int first = grp(1) - grp(0), last = nrow - grp(ng - 1);
+        return (first == last && (ng <= 2 || grp(2) - grp(1) == first)) ? first : 0;
+    }
+    // pair_census of lr / lc: pairs (2h, 2h + 1) -- code 1 -- or, behind the leading single, (2h - 1, 2h) -- code 2; the step
+    // of one tap from pair to pair always holds
+    __device__ __forceinline__ int rcode() const { return (rbase == 0 || nrow <= 1) ? 1 : 2; }
+    __device__ __forceinline__ int ccode() const { return (cbase == 0 || ncol <= 1) ? 1 : 2; }
+    __device__ __forceinline__ void dis64(int il, int jl, double (&dx)[S], double (&dy)[S]) const {
+#pragma unroll
+        for (int b = 0; b < S; ++b) dx[b] = x2_dis(il + rbase + 1, b, S);          // (only the parity of the output index matters)
+#pragma unroll
+        for (int a = 0; a < S; ++a) dy[a] = x2_dis(jl + cbase + 1, a, S);
+    }
+};
+
+// ---- owned output rows / columns -> ctl[CTL_I0 .. CTL_J1].  Tables: four wave-parallel searches in the global tables.  X2:
+//      arithmetic on the tile's position (x2_owned), no global read; the tie queue is reset here too (the X2 kernels run no census)
+template <typename D, bool X2>
 __device__ __forceinline__ void stage3_geo_search(const FrameView& F, int tyi, int txi, int ty0, int tx0, int* ctl, int tid) {
+    if constexpr (X2) {
+        if (tid < 2) {
+            int o0, o1;
+            if (tid == 0) x2_owned(tyi, F.tiles_y, ty0, TH, F.oH, &o0, &o1);
+            else x2_owned(txi, F.tiles_x, tx0, TW, F.oW, &o0, &o1);
+            ctl[CTL_I0 + 2 * tid] = o0;
+            ctl[CTL_I1 + 2 * tid] = o1;
+            if (tid == 0) ctl[CTL_TQ_COUNT] = 0;
+        }
+        return;
+    }
     const int lane = tid & 63, wave = tid >> 6;
     if (wave < 4) {
         const bool rows = wave < 2;
@@ -1437,23 +1533,23 @@ __device__ __forceinline__ void stage3_geo_search(const FrameView& F, int tyi, i
 template <typename D, int S, int KIND>
 __device__ __forceinline__ void stage3_geo_stage(uint8_t* smem, const FrameView& F, float max_sigma, int hy0, int hx0, const int* ctl,
                                                  int tid) {
-    const GeoTables<D, S> g(smem);
+    const GeoTab<D, S> g(smem);
     const int gi0 = ctl[CTL_I0], gi1 = ctl[CTL_I1], gj0 = ctl[CTL_J0], gj1 = ctl[CTL_J1];
     const float gscale = KIND == LERF_KIND_GAUSS ? s3::gauss_scale(max_sigma) : 1.0f;
     for (int e = tid; e < gi1 - gi0; e += NT) {
-        g.lr[e] = F.left_r[gi0 + e] - hy0;
+        g.lr_[e] = F.left_r[gi0 + e] - hy0;
 #pragma unroll
-        for (int b = 0; b < S; ++b) g.dr[e * S + b] = F.dis_r[(gi0 + e) * S + b] * gscale;
+        for (int b = 0; b < S; ++b) g.dr_[e * S + b] = F.dis_r[(gi0 + e) * S + b] * gscale;
     }
     for (int e = tid; e < gj1 - gj0; e += NT) {
-        g.lc[e] = F.left_c[gj0 + e] - hx0;
+        g.lc_[e] = F.left_c[gj0 + e] - hx0;
 #pragma unroll
-        for (int a = 0; a < S; ++a) g.dc[e * S + a] = F.dis_c[(gj0 + e) * S + a] * gscale;
+        for (int a = 0; a < S; ++a) g.dc_[e * S + a] = F.dis_c[(gj0 + e) * S + a] * gscale;
     }
 }
 
 // what the stage-3 functions share
-template <typename D_, int S_, int KIND_>
+template <typename D_, int S_, int KIND_, bool X2_ = false>
 struct Stage3 {
     using D = D_;
     static constexpr int S = S_, SS = S_ * S_, KIND = KIND_;
@@ -1463,12 +1559,12 @@ struct Stage3 {
     static constexpr bool BLKL = KIND_ == LERF_KIND_LINEAR && S_ == 2 && D::OUT_FITS;  // LeRF-L block tasks
     static constexpr int QRP = S_ == 4 ? 2 : 1, QCP = S_ == 4 ? 2 : 1;                 // blocks per quad task (see stage3_quads)
     static constexpr bool QUADS = BLK && QRP * QCP > 1;
-    GeoTables<D, S> g;
+    static constexpr bool X2 = X2_;
+    std::conditional_t<X2_, GeoX2<D_, S_>, GeoTab<D_, S_>> geo;                        // the geometry source
     const uint32_t* Dt;                  // the hyper region's packed dwords
     uint32_t* tq; int* tq_count;         // tie queue: (il << 16) | xc of the outputs the float32 path could not decide
     uint8_t* outt;                       // block forms: LDS image of the output block, rows at the phase of their address mod 16
-    int* cgrp;                           // LeRF-L block tasks: first column of every column group
-    const double* dis_r64; const double* dis_c64;      // float64 distance tables (NULL: tie guard off)
+    bool guard;                          // tie guard armed: the caller passed the float64 distance tables
     uint8_t* seg0;                       // first byte of the owned block in the frame
     int64_t rowpitch;                    // bytes per output row
     bool rows_align;                     // dword columns line up across the rows of a group
@@ -1476,18 +1572,22 @@ struct Stage3 {
     int ncolc, ndw, ophase;              // bytes and dword columns per row, seg0 mod 16
     MagicDiv by_ndw;                     // dword-column tasks: task -> row group (computed once: every variant of them divides by it)
     // the census (read_census, behind the barrier that follows stage3_census)
-    int ngrp, gsame, rcode, ccode;
+    int ngrp, gsame, rcode, ccode, ncgrp;
     bool lin_ok;
 
-    __device__ __forceinline__ Stage3(uint8_t* smem, const Params& P, const FrameView& F, uint8_t* outp, int* ctl) : g(smem), by_ndw(1) {
+    __device__ __forceinline__ Stage3(uint8_t* smem, const Params& P, const FrameView& F, uint8_t* outp, int* ctl, int ty0, int tx0)
+        : geo(smem), by_ndw(1) {
         Dt = reinterpret_cast<const uint32_t*>(smem + D::OFF_D);
         tq = reinterpret_cast<uint32_t*>(smem + D::OFF_TQ);
-        tq_count = ctl + CTL_TQ_COUNT;                       // zeroed by stage3_census, with the group table
+        tq_count = ctl + CTL_TQ_COUNT;                       // zeroed by stage3_census, with the group table (X2: by stage3_geo_search)
         outt = smem + D::OFF_OUT;
-        cgrp = reinterpret_cast<int*>(smem + D::OFF_CGRP);
-        dis_r64 = F.dis_r64; dis_c64 = F.dis_c64;
+        guard = F.dis_r64 != nullptr;
         i0 = ctl[CTL_I0]; j0 = ctl[CTL_J0];
         nrow = ctl[CTL_I1] - i0; ncol = ctl[CTL_J1] - j0;
+        if constexpr (X2) {                                  // (closed forms of the tile's position: keep them scalar)
+            i0 = __builtin_amdgcn_readfirstlane(i0); j0 = __builtin_amdgcn_readfirstlane(j0);
+            nrow = __builtin_amdgcn_readfirstlane(nrow); ncol = __builtin_amdgcn_readfirstlane(ncol);
+        }
         ncolc = ncol * CH;
         // bytes per output row: dense, or the caller's pitch (a rank's block of 1919 / 1921 output columns lives in rows padded to a
         // 16-byte multiple so that its tiles keep the dword-column / block tasks -- dense, every row was a group of its own)
@@ -1499,13 +1599,29 @@ struct Stage3 {
         const bool seg_aligned = rows_align && (reinterpret_cast<uintptr_t>(seg0) & 3u) == 0;
         ndw = seg_aligned ? (ncolc + 3) >> 2 : (ncolc + 6) >> 2;
         ophase = (int)(reinterpret_cast<uintptr_t>(seg0) & 15u);
+        if constexpr (X2) {
+            geo.set(i0, j0, nrow, ncol, ty0, tx0, rows_align, GAUSS ? s3::gauss_scale(P.max_sigma) : 1.0f);
+        } else {
+            geo.dis_r64 = F.dis_r64; geo.dis_c64 = F.dis_c64; geo.i0 = i0; geo.j0 = j0;
+        }
     }
+    // what the census found (tables: behind the barrier that follows stage3_census; X2: the same facts from the closed form)
     __device__ __forceinline__ void read_census(const int* ctl) {
+        if constexpr (X2) {
+            ngrp = geo.ngrp();
+            gsame = __builtin_amdgcn_readfirstlane(geo.gsame());
+            rcode = __builtin_amdgcn_readfirstlane(geo.rcode()); ccode = __builtin_amdgcn_readfirstlane(geo.ccode());
+            ncgrp = __builtin_amdgcn_readfirstlane(geo.ncgrp());
+            lin_ok = BLKL;
+            by_ndw = MagicDiv(ndw);
+            return;
+        }
         ngrp = ctl[CTL_NGRP];
         gsame = __builtin_amdgcn_readfirstlane(ctl[CTL_GSAME]);
         rcode = __builtin_amdgcn_readfirstlane(ctl[CTL_RCODE]); ccode = __builtin_amdgcn_readfirstlane(ctl[CTL_CCODE]);
         if constexpr (BLKL) lin_ok = ctl[CTL_LIN_ROWS_OK] != 0 && ctl[CTL_LIN_COLS_OK] != 0;   // (LeRF-G: slot 26 is rcode, 27 unwritten)
         else lin_ok = false;
+        ncgrp = 0;                                           // (stage3_blocks_lin reads CTL_NCGRP itself)
         by_ndw = MagicDiv(ndw);
     }
 };
@@ -1524,15 +1640,18 @@ __device__ __forceinline__ void pair_census(const int* t, int n, int lane, int* 
     if (lane == 0) { *code = p0 ? 1 : (p1 ? 2 : 0); *step = q1 ? 1 : 0; }
 }
 
-// ---- the row-group table (wave 0) and what the block forms ask about the tile's rows and columns (waves 1, 2)
+// ---- the row-group table (wave 0) and what the block forms ask about the tile's rows and columns (waves 1, 2).  Table
+//      geometry only: at exact x2 every answer is a closed form of the tile's position (GeoX2, Stage3::read_census), and
+//      the tie queue was reset by stage3_geo_search -- the X2 kernels run no census and skip its barrier
 template <typename X_>
 __device__ __forceinline__ void stage3_census(const X_& X, int* ctl, int tid) {
+  if constexpr (!X_::X2) {
     constexpr int KIND = X_::KIND, GMAX = X_::GMAX;
     const int lane = tid & 63, wave = tid >> 6;
     const int nrow = X.nrow, ncol = X.ncol;
-    const int* g_lr = X.g.lr;
-    const int* g_lc = X.g.lc;
-    int* g_grp = X.g.grp;
+    const int* g_lr = X.geo.lr_;
+    const int* g_lc = X.geo.lc_;
+    int* g_grp = X.geo.grp_;
     if (wave == 0) {
         int ng = 0;
         for (int base = 0; base < nrow; base += 64) {
@@ -1567,7 +1686,7 @@ __device__ __forceinline__ void stage3_census(const X_& X, int* ctl, int tid) {
     } else if (wave == 1 && X_::BLKL) {
         // LeRF-L block tasks: the columns in groups of at most two that share their taps (runs of equal left taps, every
         // second column of a run starts a group); the table lies behind the output image, over the dead stage-2 areas
-        int* g_cgrp = X.cgrp;
+        int* g_cgrp = X.geo.cgrp_;
         constexpr int NCMAX = 2 * TW + 14;
         int nc = 0;
         for (int base = 0; base < ncol; base += 64) {
@@ -1595,19 +1714,22 @@ __device__ __forceinline__ void stage3_census(const X_& X, int* ctl, int tid) {
     } else if (wave == 2 && KIND == LERF_KIND_GAUSS) {
         pair_census(g_lr, nrow, lane, &ctl[CTL_RCODE], &ctl[CTL_RSTEP]);
     }
+  }
 }
 
 // ---- output (il, xc) of the owned block (row, byte column) re-evaluated in float64 exactly as the reference does
-//      (lerf_stage3.h, tie guard): its taps from the packed dwords, its distances from the frame's float64 tables
+//      (lerf_stage3.h, tie guard): its taps from the packed dwords, its float64 distances from the geometry source (the
+//      frame's float64 tables, or the closed form -- the same bits)
 template <typename X_>
 __device__ __forceinline__ uint8_t resolve_output(const X_& X, float max_sigma, int il, int xc) {
     using D = typename X_::D;
     constexpr int S = X_::S;
     const int jl = xc / CH;
     const int c = xc - jl * CH;
-    const uint32_t* dp = X.Dt + X.g.lr[il] * D::HP + X.g.lc[jl] * CH + c;
-    return s3::resolve_taps_u8<X_::GAUSS, S>([&](int a, int b) __attribute__((always_inline)) { return dp[b * D::HP + a * CH]; },
-                                            X.dis_r64 + (int64_t)(X.i0 + il) * S, X.dis_c64 + (int64_t)(X.j0 + jl) * S, max_sigma);
+    const uint32_t* dp = X.Dt + X.geo.lr(il) * D::HP + X.geo.lc(jl) * CH + c;
+    double dx[S], dy[S];
+    X.geo.dis64(il, jl, dx, dy);
+    return s3::resolve_taps_u8<X_::GAUSS, S>([&](int a, int b) __attribute__((always_inline)) { return dp[b * D::HP + a * CH]; }, dx, dy, max_sigma);
 }
 // bit q of the result: output q of a task lies within kTieEps of a rounding tie
 template <int N>
@@ -1653,7 +1775,7 @@ __device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int t
     using D = typename X_::D;
     constexpr int S = X_::S, SS = X_::SS, KIND = X_::KIND;
     constexpr int GN = GS > 0 ? GS : X_::GMAX;
-    const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc; const int* g_grp = X.g.grp;
+    const auto& G = X.geo;
     const uint32_t* Dt = X.Dt;
     const int ndw = X.ndw, ncolc = X.ncolc;
     const int64_t rowpitch = X.rowpitch;
@@ -1662,12 +1784,12 @@ __device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int t
     for (int t = tid; t < ntask; t += NT) {
         const int g = X.by_ndw.div(t);
         const int dw = t - g * ndw;
-        const int il0 = g_grp[g];
-        const int gs = GS > 0 ? GS : g_grp[g + 1] - il0;
+        const int il0 = G.grp(g);
+        const int gs = GS > 0 ? GS : G.grp(g + 1) - il0;
         uint8_t* seg = X.seg0 + il0 * rowpitch;
         const int a0 = (int)(reinterpret_cast<uintptr_t>(seg) & 3u);
         const int b0 = dw * 4 - a0;
-        const int lr = g_lr[il0];
+        const int lr = G.lr(il0);
         uint32_t packed[GN];
         // tie detection: the 2x2 kernels keep every output's distance from its rounded value and a running maximum
         // (one v_max per output, the ties are looked for only when the maximum says there is one); the 4x4 kernel has
@@ -1681,14 +1803,14 @@ __device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int t
         s3::f2 DXP[S];                                        // packed 4x4 path: (row 0, row 1) distances of row tap b
         if constexpr (KIND == LERF_KIND_GAUSS && S == 4 && GS == 2) {
 #pragma unroll
-            for (int b = 0; b < S; ++b) { DXP[b].x = g_dr[il0 * S + b]; DXP[b].y = g_dr[(il0 + 1) * S + b]; }
+            for (int b = 0; b < S; ++b) { DXP[b].x = G.dr(il0, b); DXP[b].y = G.dr(il0 + 1, b); }
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int xc = min(max(b0 + u, 0), ncolc - 1);    // clamped; invalid bytes are not stored
             const int jl = xc / CH;
             const int c = xc - jl * CH;
-            const int lc = g_lc[jl];
+            const int lc = G.lc(jl);
             if constexpr (KIND == LERF_KIND_GAUSS && S == 4 && GS == 2) {
                 // The 4x4 support, two rows per group, in PACKED float32 over the two rows (lane x = row 0, lane y = row 1):
                 // per tap and row PAIR one v_pk_mul (tx), two v_pk_fma (the form), one v_pk_add and one v_pk_fma (the sums)
@@ -1697,7 +1819,7 @@ __device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int t
                 s3::f2 PT[SS], KV[SS];
 #pragma unroll
                 for (int a = 0; a < S; ++a) {
-                    const float dy = g_dc[jl * S + a];
+                    const float dy = G.dc(jl, a);
 #pragma unroll
                     for (int b = 0; b < S; ++b) {
                         const uint32_t d = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
@@ -1740,7 +1862,7 @@ __device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int t
             float p0[SS], k1[SS], ty[SS], v[SS];
 #pragma unroll
             for (int a = 0; a < S; ++a) {
-                const float dy = g_dc[jl * S + a];
+                const float dy = G.dc(jl, a);
 #pragma unroll
                 for (int b = 0; b < S; ++b) {
                     const uint32_t d = Dt[(lr + b) * D::HP + (lc + a) * CH + c];
@@ -1768,7 +1890,7 @@ __device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int t
                     for (int a = 0; a < S; ++a)
 #pragma unroll
                         for (int b = 0; b < S; ++b) {
-                            const float dx = g_dr[(il0 + r) * S + b];
+                            const float dx = G.dr(il0 + r, b);
                             if (KIND == LERF_KIND_GAUSS)
                                 e[a * S + b] = s3::gauss_form_cols(s3::gauss_t_u8(k1[a * S + b], dx), ty[a * S + b], p0[a * S + b]);
                             else
@@ -1786,7 +1908,7 @@ __device__ __forceinline__ void stage3_tasks(const X_& X, const Params& P, int t
                 }
             }
         }
-        if ((DIST ? dmax > 0.5f - s3::kTieEps : tiebits != 0) && X.dis_r64 != nullptr) {
+        if ((DIST ? dmax > 0.5f - s3::kTieEps : tiebits != 0) && X.guard) {
             unsigned tiemask = tiebits;
             if (DIST) {
 #pragma unroll
@@ -1831,23 +1953,23 @@ __device__ __forceinline__ void stage3_blocks(const X_& X, const Params& P, int 
     if constexpr (X_::BLK) {
         using D = typename X_::D;
         constexpr int S = X_::S;
-        const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc;
+        const auto& G = X.geo;
         const int nrow = X.nrow, ncol = X.ncol, ophase = X.ophase;
         const int rofs = UNI ? 0 : X.rcode - 1, cofs = UNI ? 0 : X.ccode - 1;
         const int ncg = (ncol + cofs + 1) >> 1;
         const int nblk = ((nrow + rofs + 1) >> 1) * ncg;
-        const MagicDiv by_ncg(ncg);
+        const MagicDiv by_ncg = MagicDiv::of<X_::X2, TW>(ncg);
         for (int t = tid; t < nblk; t += NT) {
             const int g = by_ncg.div(t);
             const int h = t - g * ncg;
             const int il0 = 2 * g - rofs, jl0 = 2 * h - cofs;
-            const int lr = g_lr[UNI ? il0 : max(il0, 0)], lc = g_lc[UNI ? jl0 : max(jl0, 0)];
+            const int lr = G.lr(UNI ? il0 : max(il0, 0)), lc = G.lc(UNI ? jl0 : max(jl0, 0));
             // distances as PAIRS: DX[b] = (row 0, row 1) of row tap b, DY[a] = (column 0, column 1) of column tap a
             s3::f2 DX[S], DY[S];
 #pragma unroll
-            for (int b = 0; b < S; ++b) { DX[b].x = g_dr[il0 * S + b]; DX[b].y = g_dr[il0 * S + S + b]; }
+            for (int b = 0; b < S; ++b) { DX[b].x = G.dr_pair(g, -rofs, b); DX[b].y = G.dr_pair(g, 1 - rofs, b); }
 #pragma unroll
-            for (int a = 0; a < S; ++a) { DY[a].x = g_dc[jl0 * S + a]; DY[a].y = g_dc[jl0 * S + S + a]; }
+            for (int a = 0; a < S; ++a) { DY[a].x = G.dc_pair(h, -cofs, a); DY[a].y = G.dc_pair(h, 1 - cofs, a); }
             const uint32_t* dp = X.Dt + lr * D::HP + lc * CH;
             uint8_t* ob = X.outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
             float dist[4 * CH];                                  // [c][r][q]
@@ -1873,7 +1995,7 @@ __device__ __forceinline__ void stage3_blocks(const X_& X, const Params& P, int 
                         put_block_byte(s3::finish_div(num, den), have, ob + r * D::OUT_PITCH + q * CH + c, dist[(c * 2 + r) * 2 + q], dmax);
                     }
             }
-            if (dmax > 0.5f - s3::kTieEps && X.dis_r64 != nullptr)
+            if (dmax > 0.5f - s3::kTieEps && X.guard)
                 queue_ties(X, P, tie_mask(dist),
                            [&](int q, int& il, int& xc) __attribute__((always_inline)) { il = il0 + ((q >> 1) & 1); xc = (jl0 + (q & 1)) * CH + (q >> 2); },
                            [&](int q, uint32_t r8) __attribute__((always_inline)) { ob[((q >> 1) & 1) * D::OUT_PITCH + (q & 1) * CH + (q >> 2)] = (uint8_t)r8; });
@@ -1896,7 +2018,7 @@ __device__ __forceinline__ void stage3_quads(const X_& X, const Params& P, int t
     if constexpr (X_::QUADS) {
         using D = typename X_::D;
         constexpr int S = X_::S, RP = X_::QRP, CP = X_::QCP, TR = S + RP - 1, TC = S + CP - 1;
-        const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc;
+        const auto& G = X.geo;
         const int ophase = X.ophase;
         const int ncq = (X.ncol >> 1) / CP;
         const int ntq = ((X.nrow >> 1) / RP) * ncq;
@@ -1905,16 +2027,16 @@ __device__ __forceinline__ void stage3_quads(const X_& X, const Params& P, int t
             const int g = by_ncq.div(t);
             const int h = t - g * ncq;
             const int il0 = 2 * RP * g, jl0 = 2 * CP * h;
-            const int lr = g_lr[il0], lc = g_lc[jl0];
+            const int lr = G.lr(il0), lc = G.lc(jl0);
             s3::f2 DX[RP][S], DY[CP][S];               // [pair][tap]: lanes = the two rows / the two columns of the pair
 #pragma unroll
             for (int rp = 0; rp < RP; ++rp)
 #pragma unroll
-                for (int b = 0; b < S; ++b) { DX[rp][b].x = g_dr[(il0 + 2 * rp) * S + b]; DX[rp][b].y = g_dr[(il0 + 2 * rp + 1) * S + b]; }
+                for (int b = 0; b < S; ++b) { DX[rp][b].x = G.dr_pair(RP * g + rp, 0, b); DX[rp][b].y = G.dr_pair(RP * g + rp, 1, b); }
 #pragma unroll
             for (int cp = 0; cp < CP; ++cp)
 #pragma unroll
-                for (int a = 0; a < S; ++a) { DY[cp][a].x = g_dc[(jl0 + 2 * cp) * S + a]; DY[cp][a].y = g_dc[(jl0 + 2 * cp + 1) * S + a]; }
+                for (int a = 0; a < S; ++a) { DY[cp][a].x = G.dc_pair(CP * h + cp, 0, a); DY[cp][a].y = G.dc_pair(CP * h + cp, 1, a); }
             const uint32_t* dp = X.Dt + lr * D::HP + lc * CH;
             uint8_t* ob = X.outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
 #pragma unroll 1
@@ -1963,7 +2085,7 @@ __device__ __forceinline__ void stage3_quads(const X_& X, const Params& P, int t
                                 put_block_byte(s3::finish_div(num, den), true, ob + (2 * rp + r) * D::OUT_PITCH + (2 * cp + q) * CH + c,
                                                dist[((rp * CP + cp) * 2 + r) * 2 + q], dmax);
                             }
-                if (dmax > 0.5f - s3::kTieEps && X.dis_r64 != nullptr)
+                if (dmax > 0.5f - s3::kTieEps && X.guard)
                     queue_ties(X, P, tie_mask(dist),
                                [&](int k, int& il, int& xc) __attribute__((always_inline)) {
                                    const int rp = (k >> 2) / CP, cp = (k >> 2) - rp * CP;
@@ -1990,31 +2112,31 @@ template <typename X_>
 __device__ __forceinline__ void stage3_blocks_lin(const X_& X, const Params& P, const int* ctl, int tid) {
     if constexpr (X_::BLKL) {
         using D = typename X_::D;
-        const int* g_lr = X.g.lr; const float* g_dr = X.g.dr; const int* g_lc = X.g.lc; const float* g_dc = X.g.dc; const int* g_grp = X.g.grp;
-        const int* g_cgrp = X.cgrp;
+        const auto& G = X.geo;
         const int ophase = X.ophase;
         const float ms255 = P.max_sigma * (1.0f / 255.0f);
-        const int ncg = __builtin_amdgcn_readfirstlane(ctl[CTL_NCGRP]);
+        const int ncg = X_::X2 ? X.ncgrp : __builtin_amdgcn_readfirstlane(ctl[CTL_NCGRP]);
         const int nblk = X.ngrp * ncg;
-        const MagicDiv by_ncg(ncg);
+        const MagicDiv by_ncg = MagicDiv::of<X_::X2, TW>(ncg);
         for (int t = tid; t < nblk; t += NT) {
             const int g = by_ncg.div(t);
             const int h = t - g * ncg;
-            const int il0 = g_grp[g], jl0 = g_cgrp[h];
-            const bool two_r = g_grp[g + 1] - il0 > 1, two_c = g_cgrp[h + 1] - jl0 > 1;
-            const int lr = g_lr[il0], lc = g_lc[jl0];
+            const int il0 = G.grp(g), jl0 = G.cgrp(h);
+            const bool two_r = G.grp(g + 1) - il0 > 1, two_c = G.cgrp(h + 1) - jl0 > 1;
+            const int lr = G.lr(il0), lc = G.lc(jl0);
             // |distance| and inside-the-support mask (1 / 0) of the two rows [r][row tap b] and the two columns [q][column
             // tap a]; a single's second member reads its neighbour's entries (computed, never stored)
             float ax[2][2], mx[2][2], ay[2][2], my[2][2];
-            auto abs_and_mask = [](const float* d, float (&a)[2][2], float (&m)[2][2]) __attribute__((always_inline)) {
+            auto abs_and_mask = [](auto d, float (&a)[2][2], float (&m)[2][2]) __attribute__((always_inline)) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    a[k >> 1][k & 1] = __builtin_fabsf(d[k]);
-                    m[k >> 1][k & 1] = s3::dist_class_f(d[k]) != 0 ? 1.0f : 0.0f;
+                    const float dk = d(k >> 1, k & 1);                   // (member, tap)
+                    a[k >> 1][k & 1] = __builtin_fabsf(dk);
+                    m[k >> 1][k & 1] = s3::dist_class_f(dk) != 0 ? 1.0f : 0.0f;
                 }
             };
-            abs_and_mask(g_dr + il0 * 2, ax, mx);
-            abs_and_mask(g_dc + jl0 * 2, ay, my);
+            abs_and_mask([&](int r, int b) __attribute__((always_inline)) { return G.dr(il0 + r, b); }, ax, mx);
+            abs_and_mask([&](int q, int a) __attribute__((always_inline)) { return G.dc(jl0 + q, a); }, ay, my);
             const uint32_t* dp = X.Dt + lr * D::HP + lc * CH;
             uint8_t* ob = X.outt + il0 * D::OUT_PITCH + ophase + jl0 * CH;
             float dist[4 * CH];                                  // [c][r][q]
@@ -2046,7 +2168,7 @@ __device__ __forceinline__ void stage3_blocks_lin(const X_& X, const Params& P, 
                                        dist[(c * 2 + r) * 2 + q], dmax);
                     }
             }
-            if (dmax > 0.5f - s3::kTieEps && X.dis_r64 != nullptr)
+            if (dmax > 0.5f - s3::kTieEps && X.guard)
                 queue_ties(X, P, tie_mask(dist),
                            [&](int q, int& il, int& xc) __attribute__((always_inline)) { il = il0 + ((q >> 1) & 1); xc = (jl0 + (q & 1)) * CH + (q >> 2); },
                            [&](int q, uint32_t r8) __attribute__((always_inline)) { ob[((q >> 1) & 1) * D::OUT_PITCH + (q & 1) * CH + (q >> 2)] = (uint8_t)r8; });
@@ -2118,7 +2240,7 @@ __device__ __forceinline__ void stage3_ties(const X_& X, const Params& P, int ti
         __syncthreads();
         LERF_STAMP(15);
     }
-    if (X.dis_r64 == nullptr) return;
+    if (!X.guard) return;
     if (!IMAGE) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -2136,11 +2258,15 @@ __device__ __forceinline__ void stage3_ties(const X_& X, const Params& P, int ti
 
 // KINDW = LERF_KIND_* (| LERF_FUSED_WARP: stage 3 is the homographic warp of the tile's own output pixels, warp_tile())
 constexpr int LERF_FUSED_WARP = 16;
-template <int S, int KINDW, bool EMIT, bool FROM_FEAT = false, bool GEN = false>
+// X2: the exact-x2 flavour -- whole frames at scale 2.0 on both axes (LERF_GEO_EXACT_X2): stage 3 takes its geometry from the
+// closed form (GeoX2) instead of the caller's tables: no search in left_r / left_c, no staging of the tile's slices, no census
+template <int S, int KINDW, bool EMIT, bool FROM_FEAT = false, bool GEN = false, bool X2 = false>
 __global__ void __launch_bounds__(NT)
 sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
     constexpr int KIND = KINDW & 15;
     constexpr bool WARP = (KINDW & LERF_FUSED_WARP) != 0;
+    static_assert(!X2 || (!EMIT && !WARP && CH == 3 && S == 2), "exact-x2 flavour: the RGB SR kernels that run stage 3, 2 x 2 support");
+    static_assert(!X2 || Dims<S, GEN, EMIT>::GEO_EARLY, "exact-x2 flavour: the specialised RGB layout (geometry slot early: nothing to stage late)");
     static_assert(!WARP || (!EMIT && S == 2 && CH == 3 && !GEN), "tile-fused warp: RGB, 2 x 2 support, specialised kernel");
     using D = Dims<S, GEN, EMIT>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -2175,8 +2301,8 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
     // ---- the feat tile: stage 1 on the input tile (the geometry search rides behind the tile's loads, the staging of its
     //      results, which are in ctl by then, behind phase s), or the output of the stage-1 launch
     // (shorthands: the search and the staging are called early for S = 2 RGB -- under stage 1 or the feat load -- and late otherwise)
-    auto geo_search = [&]() { stage3_geo_search<D>(F, tyi, txi, ty0, tx0, ctl, tid); };
-    auto geo_stage = [&]() { stage3_geo_stage<D, S, KIND>(smem, F, P.max_sigma, hy0, hx0, ctl, tid); };
+    auto geo_search = [&]() { stage3_geo_search<D, X2>(F, tyi, txi, ty0, tx0, ctl, tid); };
+    auto geo_stage = [&]() { if constexpr (!X2) stage3_geo_stage<D, S, KIND>(smem, F, P.max_sigma, hy0, hx0, ctl, tid); };
     auto early_search = [&]() { if (D::GEO_EARLY && !EMIT && !WARP) geo_search(); };
     if constexpr (!FROM_FEAT) {
         stage1<D, GEN, false, false>(smem, P, img, H, W, fy0, fx0, interior, Bt, tid, early_search, [&](int k) {
@@ -2236,13 +2362,15 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
         geo_stage();
     }
     __syncthreads();
-    using X3 = Stage3<D, S, KIND>;
-    X3 X(smem, P, F, outp, ctl);
+    using X3 = Stage3<D, S, KIND, X2>;
+    X3 X(smem, P, F, outp, ctl, ty0, tx0);
     LERF_STAMP(11);
     // ---- stage 3: the row-group table and the census of the tile's rows and columns, then the cheapest task form they allow
     //      (all forms give the same bytes), then the outputs the float32 path could not decide
-    stage3_census(X, ctl, tid);
-    __syncthreads();
+    if constexpr (!X2) {
+        stage3_census(X, ctl, tid);
+        __syncthreads();
+    }
     X.read_census(ctl);
     const bool image_ok = X.rows_align && (X.rowpitch & 15) == 0 && X.nrow <= D::OUT_ROWS && X.ophase + X.ncolc <= D::OUT_PITCH;
     const bool blk = X3::BLK && image_ok && X.rcode != 0 && X.ccode != 0;
@@ -2362,7 +2490,7 @@ static int ensure_lds(int bytes) {
 
 inline size_t feat_slice_bytes(int H, int W) { return ((size_t)H * W * CH + 15) / 16 * 16; }
 
-template <int S, int KIND, bool EMIT, bool GEN>
+template <int S, int KIND, bool EMIT, bool GEN, bool X2 = false>
 static int launch_fused_t(const FusedArgs& a, hipStream_t st) {
     using D = Dims<S, GEN, EMIT>;
     using TableT = std::conditional_t<GEN, RaggedTable, NoTable>;
@@ -2431,15 +2559,15 @@ static int launch_fused_t(const FusedArgs& a, hipStream_t st) {
     }
 #endif
     auto ka = s1_kernel<GEN>;
-    auto kb = sr_fused_kernel<S, KIND, EMIT, true, GEN>;
-    auto kc = sr_fused_kernel<S, KIND, EMIT, false, GEN>;
+    auto kb = sr_fused_kernel<S, KIND, EMIT, true, GEN, X2>;
+    auto kc = sr_fused_kernel<S, KIND, EMIT, false, GEN, X2>;
     int rc;
     if (two) {
         if ((rc = ensure_lds<s1_kernel<GEN>>(DimsA::LDS_BYTES)) != LERF_OK) return rc;
-        if ((rc = ensure_lds<sr_fused_kernel<S, KIND, EMIT, true, GEN>>(D::LDS_BYTES)) != LERF_OK) return rc;
-    } else if ((rc = ensure_lds<sr_fused_kernel<S, KIND, EMIT, false, GEN>>(D::LDS_BYTES)) != LERF_OK) return rc;
+        if ((rc = ensure_lds<sr_fused_kernel<S, KIND, EMIT, true, GEN, X2>>(D::LDS_BYTES)) != LERF_OK) return rc;
+    } else if ((rc = ensure_lds<sr_fused_kernel<S, KIND, EMIT, false, GEN, X2>>(D::LDS_BYTES)) != LERF_OK) return rc;
 
-    if constexpr (GEN) {
+    if constexpr (GEN && !X2) {
         if (a.items != nullptr) {
             // frames of different sizes: chunks of RAGGED_MAX descriptors per launch (pair)
             size_t ws_off = 0;
@@ -2513,9 +2641,27 @@ static int launch_fused_t(const FusedArgs& a, hipStream_t st) {
     return LERF_OK;
 }
 
+// The exact-x2 flavour serves a launch whose caller vouches for x2 tables of the whole frame (LERF_GEO_EXACT_X2) and whose
+// sizes say the same: out = 2 x in on both axes, no region of interest (a region's owned ranges start at arbitrary origins: it
+// keeps the table path), one frame size.  A set bit with other sizes runs the table path.  LERF_GEO_FORCE_TABLES: diagnostic.
+// The 2 x 2 support only (LeRF-G and LeRF-L): the 4 x 4 kernels have no register for the closed form's constants.
+static bool takes_x2(const FusedArgs& a) {
+    if (!(a.flags & LERF_GEO_EXACT_X2) || (a.flags & LERF_GEO_FORCE_TABLES) || CH != 3 || a.items != nullptr) return false;
+    if (a.S != 2) return false;
+    if (a.roi_h > 0 && a.roi_w > 0) return false;
+    return (int64_t)a.oH == 2 * (int64_t)a.H && (int64_t)a.oW == 2 * (int64_t)a.W;
+}
+
 // dispatch over (support, kind) for one (EMIT, GEN) family of this instance
 template <bool GEN>
 static int launch_sr(const FusedArgs& a, hipStream_t st) {
+#ifdef LERF_FUSED_X2          // (lerf_fused.hip: the specialised RGB kernels, 64-row tiles)
+    if (takes_x2(a)) {
+        if (a.kind == LERF_KIND_GAUSS) return launch_fused_t<2, LERF_KIND_GAUSS, false, GEN, true>(a, st);
+        if (a.kind == LERF_KIND_LINEAR) return launch_fused_t<2, LERF_KIND_LINEAR, false, GEN, true>(a, st);
+        return LERF_EUNSUPPORTED;
+    }
+#endif
     if (a.kind == LERF_KIND_GAUSS) {
         if (a.S == 2) return launch_fused_t<2, LERF_KIND_GAUSS, false, GEN>(a, st);
         if (a.S == 4) return launch_fused_t<4, LERF_KIND_GAUSS, false, GEN>(a, st);

@@ -9,6 +9,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "lerf_hip.h"
 
@@ -81,6 +82,21 @@ LERF_HD inline int left_boundary(double g, int S) {
     return (int)ceil(g - (double)S / 2 - (double)kEps32);
 }
 
+
+// Exact x2 SR geometry (scale 2.0, n_out = 2 n_in) in closed form: what sr_axis_tables (below) computes for that case, without
+// a table.  g = i / 2 - 1 / 4 exactly, so output i has first tap (i + 1) / 2 - S / 2 and tap k lies at distance
+// S / 2 - k - 1 / 4 (even i) or S / 2 - k - 3 / 4 (odd i): exact binary fractions, the same bits in float32 and float64.  The
+// X2 flavour of the tile-fused kernels (lerf_fused_impl.h) takes its geometry from here; host::sr_x2_exact checks a pair of
+// tables against it and tests/test_x2_geometry_cpu.py pins the two against each other.
+LERF_HD inline int x2_left(int i, int S) { return ((i + 1) >> 1) - S / 2; }
+LERF_HD inline double x2_dis(int i, int k, int S) { return (double)(S / 2 - k) - ((i & 1) ? 0.75 : 0.25); }
+// outputs [o0, o1) owned by tile ti of tn along one axis (LR pixels [t0, t0 + tpx) of the whole frame): those whose first
+// tap lies in [t0 - S / 2, t0 + tpx - S / 2), the first and the last tile taking what lies beyond the frame's borders --
+// the lower bounds the table kernels search for
+LERF_HD inline void x2_owned(int ti, int tn, int t0, int tpx, int n_out, int* o0, int* o1) {
+    *o0 = ti == 0 ? 0 : 2 * t0 - 1;
+    *o1 = ti == tn - 1 ? n_out : 2 * (t0 + tpx) - 1;
+}
 
 // Source index of padded position i (unpadded coordinates, may lie outside [0, n)) under the padding rule of the IMAGE
 // operand: np.pad(input, pad_vec, mode=self.pad_mode) (resize_right/resize_right2d_numpy.py:208, :560) /
@@ -261,6 +277,50 @@ inline int sr_axis_tables_f32(int n_in, int n_out, double scale, int S, int32_t*
         pads[1] = left[n_out - 1] + S - 1 - n_in + 1;   // :81
     }
     return LERF_OK;
+}
+
+// the closed form as tables (any of the three may be NULL)
+inline int sr_x2_tables(int n_out, int S, int32_t* left, double* dis64, float* dis32) {
+    if (n_out < 1 || S < 1 || S > LERF_MAX_SUPPORT || (S & 1)) return LERF_EINVAL;
+    for (int i = 0; i < n_out; ++i) {
+        if (left) left[i] = x2_left(i, S);
+        for (int k = 0; k < S; ++k) {
+            if (dis64) dis64[i * S + k] = x2_dis(i, k, S);
+            if (dis32) dis32[i * S + k] = (float)x2_dis(i, k, S);
+        }
+    }
+    return LERF_OK;
+}
+
+// 1: the tables of one axis ARE the exact x2 tables -- scale 2.0, n_out = 2 n_in, every entry the closed form bit for bit
+inline int sr_x2_exact(int n_in, int n_out, double scale, int S, const int32_t* left, const double* dis64, const float* dis32) {
+    if (n_in < 1 || S < 1 || S > LERF_MAX_SUPPORT || (S & 1) || !left || !dis64 || !dis32) return 0;
+    if (scale != 2.0 || (int64_t)n_out != 2 * (int64_t)n_in) return 0;
+    for (int i = 0; i < n_out; ++i) {
+        if (left[i] != x2_left(i, S)) return 0;
+        for (int k = 0; k < S; ++k) {
+            const double d = x2_dis(i, k, S);
+            const float f = (float)d;
+            if (memcmp(&dis64[i * S + k], &d, sizeof d) != 0 || memcmp(&dis32[i * S + k], &f, sizeof f) != 0) return 0;
+        }
+    }
+    return 1;
+}
+
+// the owned output ranges of every tile of `tile` LR pixels along one axis: ranges[2 t] .. ranges[2 t + 1] (half open)
+inline int sr_x2_owned(int n_in, int tile, int32_t* ranges) {
+    if (n_in < 1 || tile < 1 || !ranges) return LERF_EINVAL;
+    const int tn = (n_in + tile - 1) / tile;
+    for (int t = 0; t < tn; ++t) x2_owned(t, tn, t * tile, tile, 2 * n_in, &ranges[2 * t], &ranges[2 * t + 1]);
+    return LERF_OK;
+}
+
+// the builder's verdict on the tables of both axes: LERF_GEO_EXACT_X2 or 0
+inline int sr_geometry_flags(int H, int W, int out_h, int out_w, double scale_h, double scale_w, int S, const int32_t* left_r,
+                             const double* dis_r64, const float* dis_r32, const int32_t* left_c, const double* dis_c64,
+                             const float* dis_c32) {
+    return sr_x2_exact(H, out_h, scale_h, S, left_r, dis_r64, dis_r32) && sr_x2_exact(W, out_w, scale_w, S, left_c, dis_c64, dis_c32)
+               ? LERF_GEO_EXACT_X2 : 0;
 }
 
 inline int invert3x3(const double m[9], double out[9]) {

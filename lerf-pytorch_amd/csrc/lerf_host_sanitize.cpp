@@ -18,6 +18,15 @@ int lerf_sr_axis_tables(int n_in, int n_out, double scale, int S, int32_t* left,
 int lerf_sr_axis_tables_f32(int n_in, int n_out, double scale, int S, int32_t* left, float* dis32, int32_t* pads) {
     return host::sr_axis_tables_f32(n_in, n_out, scale, S, left, dis32, pads);
 }
+int lerf_sr_x2_tables(int n_out, int S, int32_t* left, double* dis64, float* dis32) {
+    return host::sr_x2_tables(n_out, S, left, dis64, dis32);
+}
+int lerf_sr_x2_owned(int n_in, int tile, int32_t* ranges) { return host::sr_x2_owned(n_in, tile, ranges); }
+int lerf_sr_geometry_flags(int H, int W, int out_h, int out_w, double scale_h, double scale_w, int S, const int32_t* left_r,
+                           const double* dis_r64, const float* dis_r32, const int32_t* left_c, const double* dis_c64,
+                           const float* dis_c32) {
+    return host::sr_geometry_flags(H, W, out_h, out_w, scale_h, scale_w, S, left_r, dis_r64, dis_r32, left_c, dis_c64, dis_c32);
+}
 int lerf_invert3x3(const double m[9], double out[9]) { return host::invert3x3(m, out); }
 int lerf_warp_pads(const double minv[9], int in_h, int in_w, int out_h, int out_w, int S, int32_t pads[4]) {
     return host::warp_pads(minv, in_h, in_w, out_h, out_w, S, pads);

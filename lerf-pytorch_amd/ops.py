@@ -58,6 +58,12 @@ class SrGeometry:
         if sh == 2.0 and sw == 2.0 and arithmetic == "f64" and float(dis_scale) == 1.0 and self.S == 2 \
                 and self.out_hw == (2 * H, 2 * W):
             self.flags = _lib.GEO_X2_TABLES
+        # the native builder's verdict on the tables just built: exact x2 of the WHOLE frame, any even support -- the promise
+        # (LERF_GEO_EXACT_X2) that lets lerf_sr_fused_u8 take the X2 flavour of the tile-fused kernels.  Slices (row_slice,
+        # block_slice) drop it: their owned ranges start at arbitrary origins and keep the table path.
+        if arithmetic == "f64":
+            self.flags = int(getattr(self, "flags", 0)) | _lib.sr_geometry_flags(self.in_hw, self.out_hw, self.scales, self.S,
+                                                                                 lr, dr64, dr32, lc, dc64, dc32)
         self._upload()
 
     def _upload(self):
@@ -111,7 +117,7 @@ class SrGeometry:
         g.out_hw = (int(out_row1 - out_row0), self.out_hw[1])
         g.scales, g.S, g.device, g.pad_vec = self.scales, self.S, self.device, self.pad_vec
         g.pad_mode = self.pad_mode
-        g.flags = int(getattr(self, "flags", 0))
+        g.flags = int(getattr(self, "flags", 0)) & ~_lib.GEO_EXACT_X2      # a slice is not the whole frame's tables
         h = self.host
         g.host = dict(left_r=(h["left_r"][out_row0:out_row1] - lr_row0).astype(np.int32),
                       dis_r=h["dis_r"][out_row0:out_row1], dis_r32=h["dis_r32"][out_row0:out_row1],
