@@ -215,25 +215,32 @@ struct Params {
 #define LERF_NOW() 0ull
 #endif
 
-// byte offsets of the 3 non-centre pixels of (mode, rot) in a u8 tile of pitch P
+// (dy, dx) of the 3 non-centre pixels b, c, d of (mode, rot): mode_offsets (lerf_host_geometry.h), the one pattern table
+struct DyDx { int dy[3], dx[3]; };
+__host__ __device__ constexpr DyDx pattern_dydx(char mode, int rot) {
+    int8_t dy[4] = {0, 0, 0, 0}, dx[4] = {0, 0, 0, 0};
+    mode_offsets(mode, rot, dy, dx);
+    return DyDx{{dy[1], dy[2], dy[3]}, {dx[1], dx[2], dx[3]}};
+}
+// their byte offsets in a u8 tile of pitch P
 struct Off3 { int o[3]; };
+__host__ __device__ constexpr Off3 tile_offsets(char mode, int rot, int pitch) {
+    const DyDx q = pattern_dydx(mode, rot);
+    return Off3{{q.dy[0] * pitch + q.dx[0] * CH, q.dy[1] * pitch + q.dx[1] * CH, q.dy[2] * pitch + q.dx[2] * CH}};
+}
 template <int P>
-__host__ __device__ constexpr Off3 tile_offsets(char mode, int rot) {
-    int dy[4] = {0, 0, 0, 0}, dx[4] = {0, 0, 0, 0};
-    switch (mode) {                                                  // resample/eval_lut_sr.py:30-81
-        case 's': dy[1] = 0; dx[1] = 1; dy[2] = 1; dx[2] = 0; dy[3] = 1; dx[3] = 1; break;
-        case 'd': dy[1] = 0; dx[1] = 2; dy[2] = 2; dx[2] = 0; dy[3] = 2; dx[3] = 2; break;
-        case 'y': dy[1] = 1; dx[1] = 1; dy[2] = 1; dx[2] = 2; dy[3] = 2; dx[3] = 1; break;
-        case 'c': dy[1] = 0; dx[1] = 1; dy[2] = 0; dx[2] = 2; dy[3] = 0; dx[3] = 3; break;
-        default:  dy[1] = 1; dx[1] = 1; dy[2] = 2; dx[2] = 2; dy[3] = 3; dx[3] = 3; break;   // 't'
+__host__ __device__ constexpr Off3 tile_offsets(char mode, int rot) { return tile_offsets(mode, rot, P); }
+// The pattern tables of the general kernels (Params): rotations rot0 + h * rstep, h < nrot, of `mode` as byte offsets in an
+// LDS tile of `pitch` bytes (off) and as (dy << 16) | (dx & 0xFFFF) in the frame (dyx)
+inline void pattern_tables(char mode, int rot0, int rstep, int nrot, int pitch, int* off, int* dyx) {
+    for (int h = 0; h < nrot; ++h) {
+        const DyDx q = pattern_dydx(mode, rot0 + h * rstep);
+        const Off3 o = tile_offsets(mode, rot0 + h * rstep, pitch);
+        for (int i = 0; i < 3; ++i) {
+            off[3 * h + i] = o.o[i];
+            dyx[3 * h + i] = (q.dy[i] << 16) | (q.dx[i] & 0xFFFF);
+        }
     }
-    Off3 r{};
-    for (int k = 1; k < 4; ++k) {
-        int y = dy[k], x = dx[k];
-        for (int i = 0; i < (rot & 3); ++i) { int t = y; y = x; x = -t; }
-        r.o[k - 1] = y * P + x * CH;
-    }
-    return r;
 }
 
 // global -> LDS copy of `bytes` (rounded up to 16) by the whole workgroup; every load of a
@@ -267,10 +274,26 @@ __device__ __forceinline__ void copy16(uint8_t* dst, const uint8_t* __restrict__
     st.store(dst, tid);
 }
 
-// One byte-LUT phase over a destination region of NDST px-ch positions (row pitch DP)
-// whose centres live in a source tile (pitch SP).  MODE/ROT0/NROT/RSTEP are static so
-// the neighbour offsets fold into DS immediates.  PHASE: 0 = first (store), 1 = add,
-// 2 = add and finalise with (div, bias) into `dst8`.
+// ---------------------------------------------------------------------------
+// The byte-LUT phase (stage 1, stage 2 of LeRF-L): one LUT, NROT (4 or 2) rotations of its sampling pattern, over a region
+// of NDST px-ch positions (row pitch DPc).  A position is: read the centre pixel and the 3 pattern pixels of every rotation
+// (a pixel SOURCE: issue, ready), walk the LUT (byte_walks), add the 16-bit partial sum and store or finalise it (a phase
+// KIND: phase_finish).  Written once over sources x kinds:
+//   sources   where the pixels come from      x   how the pattern is known
+//     LdsStatic / LdsRt     the tile in LDS (pitch SP): byte_phase_lds walks the region, interior tiles without clamping
+//     VmemStatic / VmemRt   the frame in HBM / L2 over the vector-memory path, interior regions only: stage 1 and these
+//                           phases are bound by the LDS (the byte-LUT gathers keep its array 82 % busy, PMC) while the texture
+//                           path idles, so byte_phase_vmem fetches a position's pixels (global_load_ubyte_d16_hi: the same
+//                           "byte in bits 16..23" form the LDS reads deliver; L1 / L2 hits, the tile's rows are read 13
+//                           times over) one position AHEAD of its lookups, and the LDS serves the LUT gathers and the
+//                           partial sums only
+//     *Static   MODE / ROT0 / NROT / RSTEP at compile time (the published "sct" kernels): the pattern offsets fold into
+//               DS / global-load immediates
+//     *Rt       the general kernels, any of the five patterns: wave-uniform offsets from the kernel arguments
+//               (Params::s1off / s2off / s1dyx / s2dyx), one address add per pixel
+//   kinds     PhaseIs<0 / 1 / 2>: first (store the sums) / add / add and finalise with (div, bias) into dst8, at compile
+//             time; PhaseRt{first, last}: the same at run time, wave-uniform
+// ---------------------------------------------------------------------------
 // smallest (most negative) neighbour byte offset over the rotations of a phase: DS immediates are unsigned
 template <int SP>
 __host__ __device__ constexpr int min_tile_offset(char mode, int rot0, int nrot, int rstep) {
@@ -281,7 +304,10 @@ __host__ __device__ constexpr int min_tile_offset(char mode, int rot0, int nrot,
     }
     return m;
 }
-// the eight neighbours of the 3x3 block around a pixel (byte offsets in a tile of pitch SP) and the index of an offset among them
+// The four rotations of the 2x2 pattern 's' cover the 3x3 block around the centre; its edge neighbours E, S, W, N are pixel b of
+// one rotation and pixel c of the previous one, its corners pixel d of one rotation: 8 reads serve the 12 operands (the
+// static sources).  block3_offset: the eight neighbours, row by row (byte offsets in a tile of pitch SP); block3_slot: where
+// neighbour i sits in a PixSet -- r = b[r], 4 + r = d[r] (pix_slot)
 template <int SP>
 __host__ __device__ constexpr int block3_offset(int i) {
     const int dy = i < 3 ? -1 : (i < 5 ? 0 : 1);
@@ -289,18 +315,16 @@ __host__ __device__ constexpr int block3_offset(int i) {
     return dy * SP + dx * CH;
 }
 template <int SP>
-__host__ __device__ constexpr int block3_index(int off) {
-    for (int i = 0; i < 8; ++i)
-        if (block3_offset<SP>(i) == off) return i;
+__host__ __device__ constexpr int block3_slot(int i) {
+    for (int r = 0; r < 4; ++r) {
+        const Off3 o = tile_offsets<SP>('s', r);
+        if (o.o[0] == block3_offset<SP>(i)) return r;
+        if (o.o[2] == block3_offset<SP>(i)) return 4 + r;
+    }
     return 0;
 }
-template <int SP, char MODE, int ROT, int MINO>
-__device__ __forceinline__ void load_rotation(uint32_t base, uint32_t& rb, uint32_t& rc, uint32_t& rd) {
-    constexpr Off3 o = tile_offsets<SP>(MODE, ROT);
-    rb = lds_pixel_hi_off<o.o[0] - MINO>(base);
-    rc = lds_pixel_hi_off<o.o[1] - MINO>(base);
-    rd = lds_pixel_hi_off<o.o[2] - MINO>(base);
-}
+static_assert(pattern_dydx('s', 0).dy[1] == pattern_dydx('s', 1).dy[0] && pattern_dydx('s', 0).dx[1] == pattern_dydx('s', 1).dx[0],
+              "pixel c of rotation r = pixel b of rotation r + 1");
 
 // stages B-D of a byte-LUT position: NROT simplex walks around the centre pixel ra, all their gathers in flight together,
 // and the numerator sum_rot sum_n w_n P_n (weights sum to 16 per lookup)
@@ -332,70 +356,202 @@ __device__ __forceinline__ int byte_walks(uint32_t lut_a, uint32_t ra, const uin
 }
 
 
-// NROT (2 or 4) lookups of one byte LUT around the pixel at LDS address `center`; lut_a = LDS address of the LUT.
-// Returns the numerator sum_rot sum_n w_n P_n (weights sum to 16 per lookup).
-template <int SP, char MODE, int ROT0, int NROT, int RSTEP>
-__device__ __forceinline__ int byte_lookups(uint32_t lut_a, uint32_t center) {
-    static_assert(NROT == 2 || NROT == 4, "rotation pairs or all four");
-    constexpr int MINO = min_tile_offset<SP>(MODE, ROT0, NROT, RSTEP);
-    // stage A: every pixel read of the NROT rotations (high-half loads, see lds_pixel_hi)
-    const uint32_t base = center + (uint32_t)MINO;
-    uint32_t ra = lds_pixel_hi_off<-MINO>(base);
-    uint32_t rb[4], rc[4], rd[4];
-    if constexpr (MODE == 's' && NROT == 4 && ROT0 == 0 && RSTEP == 1) {
-        // the four rotations of the 2x2 pattern cover the 3x3 block around the centre: its four edge neighbours are used
-        // by two rotations each, so 8 reads serve the 12 operands
-        uint32_t nb[8];
-        nb[0] = lds_pixel_hi_off<block3_offset<SP>(0) - MINO>(base); nb[1] = lds_pixel_hi_off<block3_offset<SP>(1) - MINO>(base);
-        nb[2] = lds_pixel_hi_off<block3_offset<SP>(2) - MINO>(base); nb[3] = lds_pixel_hi_off<block3_offset<SP>(3) - MINO>(base);
-        nb[4] = lds_pixel_hi_off<block3_offset<SP>(4) - MINO>(base); nb[5] = lds_pixel_hi_off<block3_offset<SP>(5) - MINO>(base);
-        nb[6] = lds_pixel_hi_off<block3_offset<SP>(6) - MINO>(base); nb[7] = lds_pixel_hi_off<block3_offset<SP>(7) - MINO>(base);
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(ra), "+v"(nb[0]), "+v"(nb[1]), "+v"(nb[2]), "+v"(nb[3]), "+v"(nb[4]), "+v"(nb[5]), "+v"(nb[6]), "+v"(nb[7]));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const Off3 o = tile_offsets<SP>('s', r);
-            rb[r] = nb[block3_index<SP>(o.o[0])];
-            rc[r] = nb[block3_index<SP>(o.o[1])];
-            rd[r] = nb[block3_index<SP>(o.o[2])];
-        }
-    } else {
-    load_rotation<SP, MODE, ROT0, MINO>(base, rb[0], rc[0], rd[0]);
-    load_rotation<SP, MODE, ROT0 + RSTEP, MINO>(base, rb[1], rc[1], rd[1]);
-    if constexpr (NROT == 4) {
-        load_rotation<SP, MODE, ROT0 + 2 * RSTEP, MINO>(base, rb[2], rc[2], rd[2]);
-        load_rotation<SP, MODE, ROT0 + 3 * RSTEP, MINO>(base, rb[3], rc[3], rd[3]);
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(ra), "+v"(rb[0]), "+v"(rc[0]), "+v"(rd[0]), "+v"(rb[1]), "+v"(rc[1]), "+v"(rd[1]), "+v"(rb[2]),
-                       "+v"(rc[2]), "+v"(rd[2]), "+v"(rb[3]), "+v"(rc[3]), "+v"(rd[3]));
-    } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ra), "+v"(rb[0]), "+v"(rc[0]), "+v"(rd[0]), "+v"(rb[1]), "+v"(rc[1]), "+v"(rd[1]));
-    }
-    }
-    return byte_walks<NROT>(lut_a, ra, rb, rc, rd);
+// ---- phase kinds
+template <int PHASE>
+struct PhaseIs { static constexpr bool first = PHASE == 0, last = PHASE == 2; };
+struct PhaseRt { bool first, last; };
+// the epilogue of a position: v = the numerator of this phase's lookups
+template <typename Kind>
+__device__ __forceinline__ void phase_finish(Kind kind, int v, int16_t* acc16, uint8_t* dst8, int p, int div, int bias) {
+    if (!kind.first) v += (int)acc16[p];
+    if (kind.last)
+        dst8[p] = (uint8_t)rne_div_clip255_fast(v + bias * div, div);
+    else
+        acc16[p] = (int16_t)v;
 }
 
-// The same with the neighbour offsets at run time (general kernels: any of the five sampling patterns).  o[3 i .. 3 i + 2] =
-// byte offsets of pixels b, c, d of rotation i in the source tile, wave-uniform (kernel arguments): one address add per
-// pixel instead of a DS immediate.
-template <int NROT>
-__device__ __forceinline__ int byte_lookups_rt(uint32_t lut_a, uint32_t center, const int* __restrict__ o) {
+// ---- pixel sources.  The pixels of a position as the high-half byte loads deliver them (see lds_pixel_hi): the centre a and
+// pixels b, c, d of rotation i.  A source has NROT, issue(PixSet&, address) = every read of a position, nothing waited for,
+// and ready(PixSet&) = wait for them (wait_pixels: the counter of the source's memory path; the operand list pins every
+// pixel register behind the wait).
+struct PixSet { uint32_t a, b[4], c[4], d[4]; };
+template <int S>
+__device__ __forceinline__ uint32_t& pix_slot(PixSet& X) {
+    if constexpr (S < 4) return X.b[S];
+    else return X.d[S - 4];
+}
+enum class Wait { LDS, VMEM };
+#define LERF_WAIT_PIXELS(...)                                                           \
+    do {                                                                                \
+        if constexpr (CNT == Wait::LDS) asm volatile("s_waitcnt lgkmcnt(0)" : __VA_ARGS__); \
+        else asm volatile("s_waitcnt vmcnt(0)" : __VA_ARGS__);                          \
+    } while (0)
+template <Wait CNT, int NROT>
+__device__ __forceinline__ void wait_pixels(PixSet& X) {
     static_assert(NROT == 2 || NROT == 4, "rotation pairs or all four");
-    uint32_t ra = lds_pixel_hi(center);
-    uint32_t rb[4], rc[4], rd[4];
-#pragma unroll
-    for (int i = 0; i < NROT; ++i) {
-        rb[i] = lds_pixel_hi(center + (uint32_t)o[3 * i]);
-        rc[i] = lds_pixel_hi(center + (uint32_t)o[3 * i + 1]);
-        rd[i] = lds_pixel_hi(center + (uint32_t)o[3 * i + 2]);
-    }
     if constexpr (NROT == 4)
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(ra), "+v"(rb[0]), "+v"(rc[0]), "+v"(rd[0]), "+v"(rb[1]), "+v"(rc[1]), "+v"(rd[1]), "+v"(rb[2]),
-                       "+v"(rc[2]), "+v"(rd[2]), "+v"(rb[3]), "+v"(rc[3]), "+v"(rd[3]));
+        LERF_WAIT_PIXELS("+v"(X.a), "+v"(X.b[0]), "+v"(X.c[0]), "+v"(X.d[0]), "+v"(X.b[1]), "+v"(X.c[1]), "+v"(X.d[1]), "+v"(X.b[2]),
+                         "+v"(X.c[2]), "+v"(X.d[2]), "+v"(X.b[3]), "+v"(X.c[3]), "+v"(X.d[3]));
     else
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ra), "+v"(rb[0]), "+v"(rc[0]), "+v"(rd[0]), "+v"(rb[1]), "+v"(rc[1]), "+v"(rd[1]));
-    return byte_walks<NROT>(lut_a, ra, rb, rc, rd);
+        LERF_WAIT_PIXELS("+v"(X.a), "+v"(X.b[0]), "+v"(X.c[0]), "+v"(X.d[0]), "+v"(X.b[1]), "+v"(X.c[1]), "+v"(X.d[1]));
+}
+// the centre and the eight neighbours of the shared 3x3 block, in the order they were read; then pixel c of every rotation
+template <Wait CNT>
+__device__ __forceinline__ void wait_block3(PixSet& X, uint32_t& n0, uint32_t& n1, uint32_t& n2, uint32_t& n3, uint32_t& n4, uint32_t& n5,
+                                            uint32_t& n6, uint32_t& n7) {
+    LERF_WAIT_PIXELS("+v"(X.a), "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3), "+v"(n4), "+v"(n5), "+v"(n6), "+v"(n7));
+    X.c[0] = X.b[1]; X.c[1] = X.b[2]; X.c[2] = X.b[3]; X.c[3] = X.b[0];
+}
+#undef LERF_WAIT_PIXELS
+template <char MODE, int ROT0, int NROT, int RSTEP>
+constexpr bool kShare3 = MODE == 's' && NROT == 4 && ROT0 == 0 && RSTEP == 1;
+
+// pixels from a u8 tile in LDS of pitch SP_; address = LDS address of the centre pixel
+template <int SP_, char MODE, int ROT0, int NROT_, int RSTEP>
+struct LdsStatic {
+    static constexpr int SP = SP_, NROT = NROT_;
+    static constexpr bool STATIC = true;
+    static constexpr int MINO = min_tile_offset<SP>(MODE, ROT0, NROT, RSTEP);
+    template <int I>
+    __device__ __forceinline__ static void rotation(PixSet& X, uint32_t base) {
+        constexpr Off3 o = tile_offsets<SP>(MODE, ROT0 + I * RSTEP);
+        X.b[I] = lds_pixel_hi_off<o.o[0] - MINO>(base);
+        X.c[I] = lds_pixel_hi_off<o.o[1] - MINO>(base);
+        X.d[I] = lds_pixel_hi_off<o.o[2] - MINO>(base);
+    }
+    template <int I>
+    __device__ __forceinline__ static uint32_t& block3(PixSet& X) { return pix_slot<block3_slot<SP>(I)>(X); }
+    template <int I>
+    __device__ __forceinline__ static void read_block3(PixSet& X, uint32_t base) { block3<I>(X) = lds_pixel_hi_off<block3_offset<SP>(I) - MINO>(base); }
+    __device__ __forceinline__ void issue(PixSet& X, uint32_t center) const {
+        const uint32_t base = center + (uint32_t)MINO;
+        X.a = lds_pixel_hi_off<-MINO>(base);
+        if constexpr (kShare3<MODE, ROT0, NROT, RSTEP>) {
+            read_block3<0>(X, base); read_block3<1>(X, base); read_block3<2>(X, base); read_block3<3>(X, base);
+            read_block3<4>(X, base); read_block3<5>(X, base); read_block3<6>(X, base); read_block3<7>(X, base);
+        } else {
+            rotation<0>(X, base);
+            rotation<1>(X, base);
+            if constexpr (NROT == 4) {
+                rotation<2>(X, base);
+                rotation<3>(X, base);
+            }
+        }
+    }
+    __device__ __forceinline__ void ready(PixSet& X) const {
+        if constexpr (kShare3<MODE, ROT0, NROT, RSTEP>)
+            wait_block3<Wait::LDS>(X, block3<0>(X), block3<1>(X), block3<2>(X), block3<3>(X), block3<4>(X), block3<5>(X), block3<6>(X), block3<7>(X));
+        else
+            wait_pixels<Wait::LDS, NROT>(X);
+    }
+};
+// o[3 i .. 3 i + 2] = byte offsets of pixels b, c, d of rotation i in the tile
+template <int SP_, int NROT_>
+struct LdsRt {
+    static constexpr int SP = SP_, NROT = NROT_;
+    static constexpr bool STATIC = false;
+    const int* __restrict__ o;
+    __device__ __forceinline__ void issue(PixSet& X, uint32_t center) const {
+        X.a = lds_pixel_hi(center);
+#pragma unroll
+        for (int i = 0; i < NROT; ++i) {
+            X.b[i] = lds_pixel_hi(center + (uint32_t)o[3 * i]);
+            X.c[i] = lds_pixel_hi(center + (uint32_t)o[3 * i + 1]);
+            X.d[i] = lds_pixel_hi(center + (uint32_t)o[3 * i + 2]);
+        }
+    }
+    __device__ __forceinline__ void ready(PixSet& X) const { wait_pixels<Wait::LDS, NROT>(X); }
+};
+
+// pixels of an INTERIOR region from the frame (stage 1: the input, stage 2 of LeRF-L: the stage-1 output); origin = address of
+// the region's first centre pixel, pitch = bytes per frame row, address = voff(row, byte in the row) of the position
+template <int IMM>
+__device__ __forceinline__ uint32_t gl_pixel_hi(uint32_t voff, uint64_t rowbase) {
+    uint32_t r;
+    asm volatile("global_load_ubyte_d16_hi %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(rowbase), "n"(IMM));
+    return r;
+}
+__device__ __forceinline__ uint32_t gl_pixel_hi_rt(uint32_t voff, uint64_t origin) {
+    uint32_t r;
+    asm volatile("global_load_ubyte_d16_hi %0, %1, %2" : "=v"(r) : "v"(voff), "s"(origin));
+    return r;
+}
+// addresses cost nothing: row base (one SGPR pair per dy in -3..3) + the position's byte offset (one VGPR) + dx * CH (immediate)
+template <char MODE, int ROT0, int NROT_, int RSTEP>
+struct VmemStatic {
+    static constexpr int NROT = NROT_;
+    uint64_t rows[7];             // rows[dy + 3] = address of the region's first centre pixel, dy rows away
+    int pitch;
+    __device__ __forceinline__ VmemStatic(const uint8_t* __restrict__ origin, int pitch_) : pitch(pitch_) {
+#pragma unroll
+        for (int dy = -3; dy <= 3; ++dy) rows[dy + 3] = (uint64_t)reinterpret_cast<uintptr_t>(origin + (int64_t)dy * pitch);
+    }
+    __device__ __forceinline__ uint32_t voff(int ry, int rb) const { return (uint32_t)(ry * pitch + rb); }
+    template <int I, int K>       // pixel K (0..2 = b, c, d) of rotation I
+    __device__ __forceinline__ uint32_t pixel(uint32_t at) const {
+        constexpr DyDx q = pattern_dydx(MODE, ROT0 + I * RSTEP);
+        return gl_pixel_hi<q.dx[K] * CH>(at, rows[q.dy[K] + 3]);
+    }
+    template <int I>
+    __device__ __forceinline__ void rotation(PixSet& X, uint32_t at) const {
+        X.b[I] = pixel<I, 0>(at); X.c[I] = pixel<I, 1>(at); X.d[I] = pixel<I, 2>(at);
+    }
+    __device__ __forceinline__ void issue(PixSet& X, uint32_t at) const {
+        X.a = gl_pixel_hi<0>(at, rows[3]);
+        if constexpr (kShare3<MODE, ROT0, NROT, RSTEP>) {
+            X.b[0] = pixel<0, 0>(at); X.b[1] = pixel<1, 0>(at); X.b[2] = pixel<2, 0>(at); X.b[3] = pixel<3, 0>(at);
+            X.d[0] = pixel<0, 2>(at); X.d[1] = pixel<1, 2>(at); X.d[2] = pixel<2, 2>(at); X.d[3] = pixel<3, 2>(at);
+        } else {
+            rotation<0>(X, at);
+            rotation<1>(X, at);
+            if constexpr (NROT == 4) {
+                rotation<2>(X, at);
+                rotation<3>(X, at);
+            }
+        }
+    }
+    __device__ __forceinline__ void ready(PixSet& X) const {
+        if constexpr (kShare3<MODE, ROT0, NROT, RSTEP>)
+            wait_block3<Wait::VMEM>(X, X.b[0], X.b[1], X.b[2], X.b[3], X.d[0], X.d[1], X.d[2], X.d[3]);
+        else
+            wait_pixels<Wait::VMEM, NROT>(X);
+    }
+};
+// dyx[3 i + k] = (dy << 16) | (dx & 0xFFFF) of pixel k + 1 of rotation i (frame coordinates); a pixel's address = base +
+// (position offset + dy * pitch + dx * CH)
+template <int NROT_>
+struct VmemRt {
+    static constexpr int NROT = NROT_;
+    // the VGPR offset of a global load is UNSIGNED: the base is moved up-left by the largest pattern reach (3 rows, 3 pixels;
+    // inside the frame for an interior region) so that every pixel offset is non-negative
+    int pitch, reach;
+    uint64_t org;
+    int off[NROT * 3];
+    __device__ __forceinline__ VmemRt(const uint8_t* __restrict__ origin, int pitch_, const int* __restrict__ dyx)
+        : pitch(pitch_), reach(3 * pitch_ + 3 * CH), org((uint64_t)reinterpret_cast<uintptr_t>(origin - (3 * pitch_ + 3 * CH))) {
+#pragma unroll
+        for (int i = 0; i < NROT * 3; ++i) off[i] = (dyx[i] >> 16) * pitch + (int)(int16_t)(dyx[i] & 0xFFFF) * CH;
+    }
+    __device__ __forceinline__ uint32_t voff(int ry, int rb) const { return (uint32_t)(ry * pitch + rb + reach); }
+    __device__ __forceinline__ void issue(PixSet& X, uint32_t at) const {
+        X.a = gl_pixel_hi_rt(at, org);
+#pragma unroll
+        for (int i = 0; i < NROT; ++i) {
+            X.b[i] = gl_pixel_hi_rt(at + (uint32_t)off[3 * i], org);
+            X.c[i] = gl_pixel_hi_rt(at + (uint32_t)off[3 * i + 1], org);
+            X.d[i] = gl_pixel_hi_rt(at + (uint32_t)off[3 * i + 2], org);
+        }
+    }
+    __device__ __forceinline__ void ready(PixSet& X) const { wait_pixels<Wait::VMEM, NROT>(X); }
+};
+
+// the lookups of one position, all its pixels read and waited for at once; lut_a = LDS address of the LUT
+template <typename Src>
+__device__ __forceinline__ int byte_lookups(const Src& src, uint32_t lut_a, uint32_t center) {
+    PixSet X;
+    src.issue(X, center);
+    src.ready(X);
+    return byte_walks<Src::NROT>(lut_a, X.a, X.b, X.c, X.d);
 }
 
 // position p of a region (pitch DPc px-ch per row, origin (y0g,x0g) in the frame) ->
@@ -416,245 +572,42 @@ __device__ __forceinline__ int center_addr(int p, int y0g, int x0g, int sy0g, in
     return (cy - sy0g) * SP + (cx - sx0g) * CH + c;
 }
 
-// SKIP_OUTSIDE: positions outside the frame are not evaluated (callers that never read them: s1_kernel).
-// Interior tiles (H < 0, a workgroup-uniform fact) take a loop of their own: a scalar trip count and no clamping or
-// frame tests, instead of a per-position interior branch, a vector loop condition and an inside-the-frame mask.
-template <int NDST, int DPc, int SP, char MODE, int ROT0, int NROT, int RSTEP, int PHASE>
-__device__ __forceinline__ void byte_position(uint32_t lut_a, uint32_t center, int16_t* acc16, uint8_t* dst8, int p, int div, int bias) {
-    int v = byte_lookups<SP, MODE, ROT0, NROT, RSTEP>(lut_a, center);
-    if (PHASE != 0) v += (int)acc16[p];
-    if (PHASE == 2)
-        dst8[p] = (uint8_t)rne_div_clip255_fast(v + bias * div, div);
-    else
-        acc16[p] = (int16_t)v;
+template <typename Src, typename Kind>
+__device__ __forceinline__ void byte_position(const Src& src, Kind kind, uint32_t lut_a, uint32_t center, int16_t* acc16, uint8_t* dst8, int p,
+                                              int div, int bias) {
+    phase_finish(kind, byte_lookups(src, lut_a, center), acc16, dst8, p, div, bias);
 }
-template <int NDST, int DPc, int SP, char MODE, int ROT0, int NROT, int RSTEP, int PHASE, bool SKIP_OUTSIDE = false>
-__device__ __forceinline__ void byte_phase(const int8_t* lut, const uint8_t* src, int16_t* acc16, uint8_t* dst8,
-                                           int y0g, int x0g, int sy0g, int sx0g, int H, int W, int div, int bias,
-                                           int tid) {
-    const uint32_t lut_a = lds_addr(lut), src_a = lds_addr(src);
-    if (H < 0) {
-        constexpr int FULL = NDST / NT, TAIL = NDST - FULL * NT;
-        const uint32_t org = src_a + (uint32_t)((y0g - sy0g) * SP + (x0g - sx0g) * CH);
-#pragma unroll 1
-        for (int k = 0; k < FULL; ++k) {
-            const int p = tid + k * NT;
-            const int ry = p / DPc;
-            byte_position<NDST, DPc, SP, MODE, ROT0, NROT, RSTEP, PHASE>(lut_a, org + (uint32_t)(ry * (SP - DPc) + p), acc16, dst8, p, div, bias);
-        }
-        if (TAIL > 0 && tid < TAIL) {
-            const int p = tid + FULL * NT;
-            const int ry = p / DPc;
-            byte_position<NDST, DPc, SP, MODE, ROT0, NROT, RSTEP, PHASE>(lut_a, org + (uint32_t)(ry * (SP - DPc) + p), acc16, dst8, p, div, bias);
-        }
-        return;
-    }
-    for (int p = tid; p < NDST; p += NT) {
-        bool in = true;
-        int a = center_addr<DPc, SP>(p, y0g, x0g, sy0g, sx0g, H, W, SKIP_OUTSIDE ? &in : nullptr);
-        if (SKIP_OUTSIDE && !in) continue;
-        byte_position<NDST, DPc, SP, MODE, ROT0, NROT, RSTEP, PHASE>(lut_a, src_a + (uint32_t)a, acc16, dst8, p, div, bias);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Stage-1 positions of INTERIOR tiles with the pixel reads on the vector-memory path (s1_kernel): stage 1 is bound by the
-// LDS (the byte-LUT gathers keep its array 82 % busy, PMC) while the texture path idles -- so the 9 / 13 neighbourhood
-// pixels of a position are fetched straight from the frame (global_load_ubyte_d16_hi: the same "byte in bits 16..23" form
-// the LDS reads deliver; L1 / L2 hits, the tile's rows are read 13 times over), one position AHEAD of the lookups, and the
-// LDS serves the LUT gathers and the partial sums only.  Addresses cost nothing: address = row base (one SGPR pair per
-// dy in -3..3) + the position's byte offset (one VGPR) + dx * CH (immediate).
-// ---------------------------------------------------------------------------
-struct DyDx { int dy[3], dx[3]; };
-__host__ __device__ constexpr DyDx pattern_dydx(char mode, int rot) {
-    int dy[4] = {0, 0, 0, 0}, dx[4] = {0, 0, 0, 0};
-    switch (mode) {
-        case 's': dy[1] = 0; dx[1] = 1; dy[2] = 1; dx[2] = 0; dy[3] = 1; dx[3] = 1; break;
-        case 'd': dy[1] = 0; dx[1] = 2; dy[2] = 2; dx[2] = 0; dy[3] = 2; dx[3] = 2; break;
-        case 'y': dy[1] = 1; dx[1] = 1; dy[2] = 1; dx[2] = 2; dy[3] = 2; dx[3] = 1; break;
-        case 'c': dy[1] = 0; dx[1] = 1; dy[2] = 0; dx[2] = 2; dy[3] = 0; dx[3] = 3; break;
-        default:  dy[1] = 1; dx[1] = 1; dy[2] = 2; dx[2] = 2; dy[3] = 3; dx[3] = 3; break;   // 't'
-    }
-    DyDx r{};
-    for (int k = 1; k < 4; ++k) {
-        int y = dy[k], x = dx[k];
-        for (int i = 0; i < (rot & 3); ++i) { int t = y; y = x; x = -t; }
-        r.dy[k - 1] = y;
-        r.dx[k - 1] = x;
-    }
-    return r;
-}
-template <int IMM>
-__device__ __forceinline__ uint32_t gl_pixel_hi(uint32_t voff, uint64_t rowbase) {
-    uint32_t r;
-    asm volatile("global_load_ubyte_d16_hi %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(rowbase), "n"(IMM));
-    return r;
-}
-struct PixSet { uint32_t a, b[4], c[4], d[4]; };
-// rows[dy + 3] = address of the region's first centre pixel, dy rows away; rotations ROT0 + i * RSTEP, i < NROT
-template <char MODE, int ROT0, int NROT, int RSTEP>
-__device__ __forceinline__ void pix_issue(PixSet& P, uint32_t voff, const uint64_t (&rows)[7]) {
-    P.a = gl_pixel_hi<0>(voff, rows[3]);
-#define LERF_PX(I, K) gl_pixel_hi<pattern_dydx(MODE, ROT0 + (I) * RSTEP).dx[K] * CH>(voff, rows[pattern_dydx(MODE, ROT0 + (I) * RSTEP).dy[K] + 3])
-    if constexpr (MODE == 's' && NROT == 4 && ROT0 == 0 && RSTEP == 1) {
-        // the four rotations of the 2x2 pattern cover the 3x3 block: its edge neighbours E, S, W, N are pixel b of one
-        // rotation and pixel c of the previous one -- 8 loads serve the 12 operands (pix_ready hands them out)
-        P.b[0] = LERF_PX(0, 0); P.b[1] = LERF_PX(1, 0); P.b[2] = LERF_PX(2, 0); P.b[3] = LERF_PX(3, 0);
-        P.d[0] = LERF_PX(0, 2); P.d[1] = LERF_PX(1, 2); P.d[2] = LERF_PX(2, 2); P.d[3] = LERF_PX(3, 2);
-    } else {
-        P.b[0] = LERF_PX(0, 0); P.c[0] = LERF_PX(0, 1); P.d[0] = LERF_PX(0, 2);
-        P.b[1] = LERF_PX(1, 0); P.c[1] = LERF_PX(1, 1); P.d[1] = LERF_PX(1, 2);
-        if constexpr (NROT == 4) {
-            P.b[2] = LERF_PX(2, 0); P.c[2] = LERF_PX(2, 1); P.d[2] = LERF_PX(2, 2);
-            P.b[3] = LERF_PX(3, 0); P.c[3] = LERF_PX(3, 1); P.d[3] = LERF_PX(3, 2);
-        }
-    }
-#undef LERF_PX
-}
-template <char MODE, int ROT0, int NROT, int RSTEP>
-__device__ __forceinline__ void pix_ready(PixSet& P) {
-    if constexpr (MODE == 's' && NROT == 4 && ROT0 == 0 && RSTEP == 1) {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(P.a), "+v"(P.b[0]), "+v"(P.b[1]), "+v"(P.b[2]), "+v"(P.b[3]), "+v"(P.d[0]), "+v"(P.d[1]),
-                     "+v"(P.d[2]), "+v"(P.d[3]));
-        static_assert(pattern_dydx('s', 0).dy[1] == pattern_dydx('s', 1).dy[0] && pattern_dydx('s', 0).dx[1] == pattern_dydx('s', 1).dx[0],
-                      "pixel c of rotation r = pixel b of rotation r + 1");
-        P.c[0] = P.b[1]; P.c[1] = P.b[2]; P.c[2] = P.b[3]; P.c[3] = P.b[0];
-    } else if constexpr (NROT == 4) {
-        asm volatile("s_waitcnt vmcnt(0)"
-                     : "+v"(P.a), "+v"(P.b[0]), "+v"(P.c[0]), "+v"(P.d[0]), "+v"(P.b[1]), "+v"(P.c[1]), "+v"(P.d[1]), "+v"(P.b[2]),
-                       "+v"(P.c[2]), "+v"(P.d[2]), "+v"(P.b[3]), "+v"(P.c[3]), "+v"(P.d[3]));
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(P.a), "+v"(P.b[0]), "+v"(P.c[0]), "+v"(P.d[0]), "+v"(P.b[1]), "+v"(P.c[1]), "+v"(P.d[1]));
-    }
-}
-// one byte-LUT phase over the NDST positions (row pitch DPc) of an INTERIOR region; origin = address of the region's first
-// centre pixel in the frame (stage 1: the input, stage 2 of LeRF-L: the stage-1 output), pitch = bytes per frame row.
-// PHASE as in byte_position.  Threads past the last position of the final round repeat it (loads only).
-template <int NDST, int DPc, char MODE, int ROT0, int NROT, int RSTEP, int PHASE>
-__device__ __forceinline__ void byte_phase_vmem(const int8_t* lut, const uint8_t* __restrict__ origin, int pitch, int16_t* acc16,
-                                                uint8_t* dst8, int div, int bias, int tid) {
-    constexpr int ROUNDS = (NDST + NT - 1) / NT, PAIRS = (ROUNDS + 1) / 2;
-    const uint32_t lut_a = lds_addr(lut);
-    uint64_t rows[7];
-#pragma unroll
-    for (int dy = -3; dy <= 3; ++dy) rows[dy + 3] = (uint64_t)reinterpret_cast<uintptr_t>(origin + (int64_t)dy * pitch);
-    auto voff_of = [&](int p) {
-        p = p < NDST ? p : NDST - 1;
-        const int ry = p / DPc;
-        return (uint32_t)(ry * pitch + (p - ry * DPc));
-    };
-    auto finish = [&](const PixSet& X, int p) {
-        if (NDST % NT != 0 && p >= NDST) return;
-        int v = byte_walks<NROT>(lut_a, X.a, X.b, X.c, X.d);
-        if (PHASE != 0) v += (int)acc16[p];
-        if (PHASE == 2)
-            dst8[p] = (uint8_t)rne_div_clip255_fast(v + bias * div, div);
-        else
-            acc16[p] = (int16_t)v;
-    };
-    PixSet A, B;
-    pix_issue<MODE, ROT0, NROT, RSTEP>(A, voff_of(tid), rows);
-#pragma unroll 1
-    for (int k = 0; k < PAIRS; ++k) {
-        const int p = tid + 2 * k * NT;
-        pix_ready<MODE, ROT0, NROT, RSTEP>(A);
-        pix_issue<MODE, ROT0, NROT, RSTEP>(B, voff_of(p + NT), rows);
-        finish(A, p);
-        pix_ready<MODE, ROT0, NROT, RSTEP>(B);
-        if (k + 1 < PAIRS) pix_issue<MODE, ROT0, NROT, RSTEP>(A, voff_of(p + 2 * NT), rows);
-        if (2 * k + 1 < ROUNDS) finish(B, p + NT);
-    }
-}
-
-// The same for the general kernels: pattern offsets at run time.  dyx[3 i + k] = (dy << 16) | (dx & 0xFFFF) of pixel k + 1 of
-// rotation i (frame coordinates, wave-uniform kernel arguments); a pixel's address = origin + (position offset + dy * pitch
-// + dx * CH): one VALU add per pixel, like the LDS path of byte_lookups_rt.
-__device__ __forceinline__ uint32_t gl_pixel_hi_rt(uint32_t voff, uint64_t origin) {
-    uint32_t r;
-    asm volatile("global_load_ubyte_d16_hi %0, %1, %2" : "=v"(r) : "v"(voff), "s"(origin));
-    return r;
-}
-template <int NDST, int DPc, int NROT>
-__device__ __forceinline__ void byte_phase_vmem_rt(const int8_t* lut, const uint8_t* __restrict__ origin, int pitch, int16_t* acc16,
-                                                   uint8_t* dst8, int div, int bias, int tid, const int* __restrict__ dyx, bool first,
-                                                   bool last) {
-    constexpr int ROUNDS = (NDST + NT - 1) / NT, PAIRS = (ROUNDS + 1) / 2;
-    const uint32_t lut_a = lds_addr(lut);
-    // the VGPR offset of a global load is UNSIGNED: the base is moved up-left by the largest pattern reach (3 rows, 3 pixels;
-    // inside the frame for an interior region) so that every pixel offset is non-negative
-    const int reach = 3 * pitch + 3 * CH;
-    const uint64_t org = (uint64_t)reinterpret_cast<uintptr_t>(origin - reach);
-    int off[NROT * 3];
-#pragma unroll
-    for (int i = 0; i < NROT * 3; ++i) off[i] = (dyx[i] >> 16) * pitch + (int)(int16_t)(dyx[i] & 0xFFFF) * CH;
-    auto voff_of = [&](int p) {
-        p = p < NDST ? p : NDST - 1;
-        const int ry = p / DPc;
-        return (uint32_t)(ry * pitch + (p - ry * DPc) + reach);
-    };
-    auto issue = [&](PixSet& X, uint32_t voff) {
-        X.a = gl_pixel_hi_rt(voff, org);
-#pragma unroll
-        for (int i = 0; i < NROT; ++i) {
-            X.b[i] = gl_pixel_hi_rt(voff + (uint32_t)off[3 * i], org);
-            X.c[i] = gl_pixel_hi_rt(voff + (uint32_t)off[3 * i + 1], org);
-            X.d[i] = gl_pixel_hi_rt(voff + (uint32_t)off[3 * i + 2], org);
-        }
-    };
-    auto ready = [&](PixSet& X) {
-        if constexpr (NROT == 4)
-            asm volatile("s_waitcnt vmcnt(0)"
-                         : "+v"(X.a), "+v"(X.b[0]), "+v"(X.c[0]), "+v"(X.d[0]), "+v"(X.b[1]), "+v"(X.c[1]), "+v"(X.d[1]), "+v"(X.b[2]),
-                           "+v"(X.c[2]), "+v"(X.d[2]), "+v"(X.b[3]), "+v"(X.c[3]), "+v"(X.d[3]));
-        else
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(X.a), "+v"(X.b[0]), "+v"(X.c[0]), "+v"(X.d[0]), "+v"(X.b[1]), "+v"(X.c[1]), "+v"(X.d[1]));
-    };
-    auto finish = [&](const PixSet& X, int p) {
-        if (NDST % NT != 0 && p >= NDST) return;
-        int v = byte_walks<NROT>(lut_a, X.a, X.b, X.c, X.d);
-        if (!first) v += (int)acc16[p];
-        if (last)
-            dst8[p] = (uint8_t)rne_div_clip255_fast(v + bias * div, div);
-        else
-            acc16[p] = (int16_t)v;
-    };
-    PixSet A, B;
-    issue(A, voff_of(tid));
-#pragma unroll 1
-    for (int k = 0; k < PAIRS; ++k) {
-        const int p = tid + 2 * k * NT;
-        ready(A);
-        issue(B, voff_of(p + NT));
-        finish(A, p);
-        ready(B);
-        if (k + 1 < PAIRS) issue(A, voff_of(p + 2 * NT));
-        if (2 * k + 1 < ROUNDS) finish(B, p + NT);
-    }
-}
-
-// General kernels: the same phase with the pattern offsets `o` (see byte_lookups_rt) and the phase kind at run time --
-// `first`: store the partial sums, otherwise add; `last`: finalise with (div, bias) into dst8.  All wave-uniform.
-template <int NROT>
-__device__ __forceinline__ void byte_position_rt(uint32_t lut_a, uint32_t center, int16_t* acc16, uint8_t* dst8, int p, int div,
-                                                 int bias, const int* __restrict__ o, bool first, bool last) {
-    int v = byte_lookups_rt<NROT>(lut_a, center, o);
-    if (!first) v += (int)acc16[p];
-    if (last)
-        dst8[p] = (uint8_t)rne_div_clip255_fast(v + bias * div, div);
-    else
-        acc16[p] = (int16_t)v;
-}
-template <int NDST, int DPc, int SP, int NROT, bool SKIP_OUTSIDE = false>
-__device__ __forceinline__ void byte_phase_rt(const int8_t* lut, const uint8_t* src, int16_t* acc16, uint8_t* dst8, int y0g, int x0g,
-                                              int sy0g, int sx0g, int H, int W, int div, int bias, int tid,
-                                              const int* __restrict__ o, bool first, bool last) {
-    const uint32_t lut_a = lds_addr(lut), src_a = lds_addr(src);
+// One phase over a region (origin (y0g, x0g) in the frame) whose centres lie in the LDS tile `tile` (pitch Src::SP, origin
+// (sy0g, sx0g)).  SKIP_OUTSIDE: positions outside the frame are not evaluated (callers that never read them: s1_kernel).
+// Interior tiles (H < 0, a workgroup-uniform fact) take a loop of their own: no clamping or frame tests, instead of a
+// per-position interior branch and an inside-the-frame mask; with a static source also a scalar trip count (whole rounds + a
+// masked tail) instead of a vector loop condition -- the loop shape each kind of kernel has been measured with.
+template <int NDST, int DPc, bool SKIP_OUTSIDE = false, typename Src, typename Kind>
+__device__ __forceinline__ void byte_phase_lds(const Src& src, Kind kind, const int8_t* lut, const uint8_t* tile, int16_t* acc16, uint8_t* dst8,
+                                               int y0g, int x0g, int sy0g, int sx0g, int H, int W, int div, int bias, int tid) {
+    constexpr int SP = Src::SP;
+    const uint32_t lut_a = lds_addr(lut), src_a = lds_addr(tile);
     if (H < 0) {
         const uint32_t org = src_a + (uint32_t)((y0g - sy0g) * SP + (x0g - sx0g) * CH);
+        if constexpr (Src::STATIC) {
+            constexpr int FULL = NDST / NT, TAIL = NDST - FULL * NT;
 #pragma unroll 1
-        for (int p = tid; p < NDST; p += NT) {
-            const int ry = p / DPc;
-            byte_position_rt<NROT>(lut_a, org + (uint32_t)(ry * (SP - DPc) + p), acc16, dst8, p, div, bias, o, first, last);
+            for (int k = 0; k < FULL; ++k) {
+                const int p = tid + k * NT;
+                const int ry = p / DPc;
+                byte_position(src, kind, lut_a, org + (uint32_t)(ry * (SP - DPc) + p), acc16, dst8, p, div, bias);
+            }
+            if (TAIL > 0 && tid < TAIL) {
+                const int p = tid + FULL * NT;
+                const int ry = p / DPc;
+                byte_position(src, kind, lut_a, org + (uint32_t)(ry * (SP - DPc) + p), acc16, dst8, p, div, bias);
+            }
+        } else {
+#pragma unroll 1
+            for (int p = tid; p < NDST; p += NT) {
+                const int ry = p / DPc;
+                byte_position(src, kind, lut_a, org + (uint32_t)(ry * (SP - DPc) + p), acc16, dst8, p, div, bias);
+            }
         }
         return;
     }
@@ -663,7 +616,36 @@ __device__ __forceinline__ void byte_phase_rt(const int8_t* lut, const uint8_t* 
         bool in = true;
         int a = center_addr<DPc, SP>(p, y0g, x0g, sy0g, sx0g, H, W, SKIP_OUTSIDE ? &in : nullptr);
         if (SKIP_OUTSIDE && !in) continue;
-        byte_position_rt<NROT>(lut_a, src_a + (uint32_t)a, acc16, dst8, p, div, bias, o, first, last);
+        byte_position(src, kind, lut_a, src_a + (uint32_t)a, acc16, dst8, p, div, bias);
+    }
+}
+// One phase over an INTERIOR region with a vector-memory source, two positions deep: the pixels of the next position are in
+// flight under the lookups of this one.  Threads past the last position of the final round repeat it (loads only).
+template <int NDST, int DPc, typename Src, typename Kind>
+__device__ __forceinline__ void byte_phase_vmem(const Src& src, Kind kind, const int8_t* lut, int16_t* acc16, uint8_t* dst8, int div, int bias,
+                                                int tid) {
+    constexpr int ROUNDS = (NDST + NT - 1) / NT, PAIRS = (ROUNDS + 1) / 2;
+    const uint32_t lut_a = lds_addr(lut);
+    auto issue = [&](PixSet& X, int p) {
+        p = p < NDST ? p : NDST - 1;
+        const int ry = p / DPc;
+        src.issue(X, src.voff(ry, p - ry * DPc));
+    };
+    auto finish = [&](const PixSet& X, int p) {
+        if (NDST % NT != 0 && p >= NDST) return;
+        phase_finish(kind, byte_walks<Src::NROT>(lut_a, X.a, X.b, X.c, X.d), acc16, dst8, p, div, bias);
+    };
+    PixSet A, B;
+    issue(A, tid);
+#pragma unroll 1
+    for (int k = 0; k < PAIRS; ++k) {
+        const int p = tid + 2 * k * NT;
+        src.ready(A);
+        issue(B, p + NT);
+        finish(A, p);
+        src.ready(B);
+        if (k + 1 < PAIRS) issue(A, p + 2 * NT);
+        if (2 * k + 1 < ROUNDS) finish(B, p + NT);
     }
 }
 
@@ -920,7 +902,7 @@ __device__ __forceinline__ void warp_tile(const Params& P, const uint32_t* Dt, i
 //      the specialised kernel then needs no input tile in LDS at all).  s1_kernel does; in sr_fused_kernel -- 72 x 72
 //      positions per tile -- it did not pay: 0.191 vs 0.184 ms per 1080 x 960 block; that kernel's stage 1 shares the CU
 //      with nothing else that uses the LDS less.  Pinned host frames (stream.StreamingSR) cross PCIe uncached: never.
-//      SKIP_OUTSIDE: see byte_phase.
+//      SKIP_OUTSIDE: see byte_phase_lds.
 template <typename D, bool GEN, bool SKIP_OUTSIDE, bool VMEM, typename Between, typename Mark>
 __device__ __forceinline__ void stage1(uint8_t* smem, const Params& P, const uint8_t* __restrict__ img, int H, int W, int fy0, int fx0,
                                        bool interior, uint8_t* dst8, int tid, Between between, Mark mark) {
@@ -936,7 +918,7 @@ __device__ __forceinline__ void stage1(uint8_t* smem, const Params& P, const uin
     if (!GEN && vmem) {
         lut_chain<3>(lut8, P.pack, tid, [&](auto I) {
             constexpr int i = decltype(I)::value;
-            byte_phase_vmem<D::NF, D::FP, kSctModes[i], 0, 4, 1, i>(lut, vorg, pitch, acc, dst8, div1, 0, tid);
+            byte_phase_vmem<D::NF, D::FP>(VmemStatic<kSctModes[i], 0, 4, 1>(vorg, pitch), PhaseIs<i>{}, lut, acc, dst8, div1, 0, tid);
         }, mark);
         return;
     }
@@ -946,13 +928,16 @@ __device__ __forceinline__ void stage1(uint8_t* smem, const Params& P, const uin
         // any 1..4 patterns: the same phases with run-time offsets (lerf_luts_t.modes1 order)
         const int dv = kQ * P.n1;
         lut_chain_rt(lut8, P.pack, P.n1, tid, [&](int m, bool more) {
-            if (vmem) byte_phase_vmem_rt<D::NF, D::FP, 4>(lut, vorg, pitch, acc, dst8, dv, 0, tid, P.s1dyx[m], m == 0, !more);
-            else byte_phase_rt<D::NF, D::FP, D::IP, 4, SKIP_OUTSIDE>(lut, Ct, acc, dst8, fy0, fx0, iy0, ix0, Hc, Wc, dv, 0, tid, P.s1off[m], m == 0, !more);
+            const int *dyx = P.s1dyx[m], *off = P.s1off[m];
+            const PhaseRt kind{m == 0, !more};
+            if (vmem) byte_phase_vmem<D::NF, D::FP>(VmemRt<4>(vorg, pitch, dyx), kind, lut, acc, dst8, dv, 0, tid);
+            else byte_phase_lds<D::NF, D::FP, SKIP_OUTSIDE>(LdsRt<D::IP, 4>{off}, kind, lut, Ct, acc, dst8, fy0, fx0, iy0, ix0, Hc, Wc, dv, 0, tid);
         }, mark);
     } else {
         lut_chain<3>(lut8, P.pack, tid, [&](auto I) {
             constexpr int i = decltype(I)::value;
-            byte_phase<D::NF, D::FP, D::IP, kSctModes[i], 0, 4, 1, i, SKIP_OUTSIDE>(lut, Ct, acc, dst8, fy0, fx0, iy0, ix0, Hc, Wc, div1, 0, tid);
+            byte_phase_lds<D::NF, D::FP, SKIP_OUTSIDE>(LdsStatic<D::IP, kSctModes[i], 0, 4, 1>{}, PhaseIs<i>{}, lut, Ct, acc, dst8, fy0, fx0, iy0, ix0, Hc, Wc,
+                                                       div1, 0, tid);
         }, mark);
     }
 }
@@ -1022,16 +1007,18 @@ __device__ __forceinline__ void stage2_linear(uint8_t* smem, const Params& P, co
         // 2 * n2 LUTs (pattern x rotation parity), offsets of the two rotations of LUT l in P.s2off[l]
         const int dv = kQ * 4 * P.n2;
         lut_chain_rt(lut8, s2, 2 * P.n2, tid, [&](int l, bool more) {
-            if (vm2) byte_phase_vmem_rt<D::NH, D::HP, 2>(lut, forg, fpitch, acc, hq8, dv, 127, tid, P.s2dyx[l], l == 0, !more);
-            else byte_phase_rt<D::NH, D::HP, D::FP, 2>(lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, dv, 127, tid, P.s2off[l], l == 0, !more);
+            const int *dyx = P.s2dyx[l], *off = P.s2off[l];
+            const PhaseRt kind{l == 0, !more};
+            if (vm2) byte_phase_vmem<D::NH, D::HP>(VmemRt<2>(forg, fpitch, dyx), kind, lut, acc, hq8, dv, 127, tid);
+            else byte_phase_lds<D::NH, D::HP>(LdsRt<D::FP, 2>{off}, kind, lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, dv, 127, tid);
         }, NoMark{});
     } else {
         const int div2 = kQ * 12;
         lut_chain<6>(lut8, s2, tid, [&](auto I) {
             constexpr int i = decltype(I)::value, PAR = i & 1, PH = i == 0 ? 0 : (i == 5 ? 2 : 1);
             constexpr char MODE = kSctModes[i >> 1];
-            if (vm2) byte_phase_vmem<D::NH, D::HP, MODE, PAR, 2, 2, PH>(lut, forg, fpitch, acc, hq8, div2, 127, tid);
-            else byte_phase<D::NH, D::HP, D::FP, MODE, PAR, 2, 2, PH>(lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, div2, 127, tid);
+            if (vm2) byte_phase_vmem<D::NH, D::HP>(VmemStatic<MODE, PAR, 2, 2>(forg, fpitch), PhaseIs<PH>{}, lut, acc, hq8, div2, 127, tid);
+            else byte_phase_lds<D::NH, D::HP>(LdsStatic<D::FP, MODE, PAR, 2, 2>{}, PhaseIs<PH>{}, lut, Bt, acc, hq8, hy0, hx0, fy0, fx0, Hc, Wc, div2, 127, tid);
         }, NoMark{});
     }
     // pack (alpha_q, 0, 0, feat-or-0) dwords for stage 3
@@ -2512,24 +2499,7 @@ static int launch_fused_t(const FusedArgs& a, hipStream_t st) {
     P.max_sigma = a.max_sigma;
     P.n1 = L->n_modes1; P.n2 = L->n_modes2;
     P.stamps = EMIT ? nullptr : (unsigned long long*)a.workspace;
-    for (int l = 0; l < 2 * P.n2; ++l) {
-        const char mc = L->modes2[l >> 1];
-        const Off3 o0 = tile_offsets<D::FP>(mc, l & 1), o1 = tile_offsets<D::FP>(mc, (l & 1) + 2);
-        for (int i = 0; i < 3; ++i) {
-            P.s2off[l][i] = o0.o[i];
-            P.s2off[l][3 + i] = o1.o[i];
-        }
-    }
-    for (int m = 0; m < P.n1; ++m)
-        for (int r = 0; r < 4; ++r) {
-            const DyDx q = pattern_dydx(L->modes1[m], r);
-            for (int i = 0; i < 3; ++i) P.s1dyx[m][3 * r + i] = (q.dy[i] << 16) | (q.dx[i] & 0xFFFF);
-        }
-    for (int l = 0; l < 2 * P.n2; ++l)
-        for (int h = 0; h < 2; ++h) {
-            const DyDx q = pattern_dydx(L->modes2[l >> 1], (l & 1) + 2 * h);
-            for (int i = 0; i < 3; ++i) P.s2dyx[l][3 * h + i] = (q.dy[i] << 16) | (q.dx[i] & 0xFFFF);
-        }
+    for (int l = 0; l < 2 * P.n2; ++l) pattern_tables(L->modes2[l >> 1], l & 1, 2, 2, D::FP, P.s2off[l], P.s2dyx[l]);
     P.emit = (uint32_t*)a.emit; P.emit_sn = a.emit_sn;
     P.feat = nullptr; P.feat_sn = 0;
     if constexpr ((KIND & LERF_FUSED_WARP) != 0) {
@@ -2537,14 +2507,10 @@ static int launch_fused_t(const FusedArgs& a, hipStream_t st) {
         P.wgeo = *a.wgeo;
         P.wboxes = a.wboxes;
     }
-    auto set_s1off = [&](Params& Q, int pitch_kind) {          // stage-1 pattern offsets in the input tile of the kernel that runs it
-        for (int m = 0; m < Q.n1; ++m)
-            for (int r = 0; r < 4; ++r) {
-                const Off3 o = pitch_kind == 0 ? tile_offsets<D::IP>(L->modes1[m], r) : tile_offsets<DimsA::IP>(L->modes1[m], r);
-                for (int i = 0; i < 3; ++i) Q.s1off[m][3 * r + i] = o.o[i];
-            }
+    auto set_s1off = [&](Params& Q, int ip) {          // stage-1 pattern offsets; ip = pitch of the input tile of the kernel that runs it
+        for (int m = 0; m < Q.n1; ++m) pattern_tables(L->modes1[m], 0, 1, 4, ip, Q.s1off[m], Q.s1dyx[m]);
     };
-    set_s1off(P, 0);
+    set_s1off(P, D::IP);
     bool two = a.workspace != nullptr && !(a.flags & LERF_GEO_SINGLE_LAUNCH);
 #ifdef LERF_STAMPS
     // diagnostic build: the stamps live at the START of the workspace -- [n x tiles x 16] of the stages-2+3 (or single) launch,
@@ -2593,7 +2559,7 @@ static int launch_fused_t(const FusedArgs& a, hipStream_t st) {
                 // every tile of the tie guard needs both float64 tables: the kernel tests P.dis_r64 (set per frame)
                 if (two) {
                     Params Pa = P;
-                    set_s1off(Pa, 1);
+                    set_s1off(Pa, DimsA::IP);
                     hipLaunchKernelGGL(ka, dim3((unsigned)blocks), dim3(NT), DimsA::LDS_BYTES, st, Pa, T);
                     hipLaunchKernelGGL(kb, dim3((unsigned)blocks), dim3(NT), D::LDS_BYTES, st, P, T);
                 } else {
@@ -2618,7 +2584,7 @@ static int launch_fused_t(const FusedArgs& a, hipStream_t st) {
 #ifdef LERF_STAMPS
         Pa.stamps = P.stamps + (size_t)blocks * 16;
 #endif
-        set_s1off(Pa, 1);
+        set_s1off(Pa, DimsA::IP);
         int64_t blocks1 = blocks;
         if (roi) {
             // region of interest: stage 1 over the region widened by the reach of stages 2 + 3 (whole 64 x 64 blocks from an

@@ -26,7 +26,7 @@ constexpr float kEps32 = 1.1920928955078125e-07f;  // np.finfo(np.float32).eps
 LERF_HD inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Sampling patterns of resample/eval_lut_sr.py:30-81, (dy, dx) of pixels a,b,c,d.
-LERF_HD inline bool mode_pattern(char mode, int8_t dy[4], int8_t dx[4]) {
+LERF_HD constexpr bool mode_pattern(char mode, int8_t dy[4], int8_t dx[4]) {
     dy[0] = 0; dx[0] = 0;
     switch (mode) {
         case 's': dy[1] = 0; dx[1] = 1; dy[2] = 1; dx[2] = 0; dy[3] = 1; dx[3] = 1; return true;
@@ -40,7 +40,7 @@ LERF_HD inline bool mode_pattern(char mode, int8_t dy[4], int8_t dx[4]) {
 
 // np.rot90(img, r) + bottom/right edge pad + pattern + rot90 back
 // == offsets rotated r times by (dy,dx)->(dx,-dy) with clamped coordinates.
-LERF_HD inline bool mode_offsets(char mode, int rot, int8_t dy[4], int8_t dx[4]) {
+LERF_HD constexpr bool mode_offsets(char mode, int rot, int8_t dy[4], int8_t dx[4]) {
     if (!mode_pattern(mode, dy, dx)) return false;
     rot &= 3;
     for (int k = 0; k < 4; ++k)

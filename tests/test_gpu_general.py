@@ -58,7 +58,7 @@ CASES = [
     (3, "lerf-l", "sct", "sct", 2, 64, 64, (8.0, 1.0)),
     (1, "lerf-l", "tcs", "y", 2, 9, 200, 5),
     # frames large enough for INTERIOR tiles (region + halo inside the frame): the vector-memory pixel path of the general
-    # kernels (byte_phase_vmem_rt), stage 1 and the LeRF-L stage 2
+    # kernels (byte_phase_vmem with a VmemRt source), stage 1 and the LeRF-L stage 2
     (3, "lerf-g", "sdy", "yct", 2, 210, 220, 2),
     (3, "lerf-l", "dyc", "ts", 2, 215, 205, (1.5, 2.0)),
     (1, "lerf-g", "sct", "sct", 2, 150, 600, 2),
