@@ -1045,6 +1045,70 @@ int lerf_coords_invert_raster_batched_host(const void* f, int f_dtype, int64_t f
                                            int max_span, int orient, uint64_t* keys,
                                            int n_sets, int64_t f_set_stride, int64_t depth_set_stride, int64_t out_set_stride,
                                            int64_t keys_set_stride);
+/* An indexed TRIANGLE MESH rasterised into a map: entry (i, j) of out [oH][oW][2] is the attribute -- the source
+ * position -- the mesh holds at pixel (i0 + i, j0 + j) of the output frame, interpolated over the face that covers the pixel;
+ * (NaN, NaN) where no face does, which lerf_remap treats as "no source".  The per-pixel arithmetic is lerf_coords_invert_raster's:
+ * a closed, watertight inside test and a 64-bit key (sortable(z) << 32) | face under an integer minimum, so the nearest surface wins,
+ * ties go to the lowest face, and out, keys and depth_out are bit-equal from run to run and to the host twin.
+ *   pos        [V][2] (row, col) of pos_dtype (LERF_F32 promoted exactly / LERF_F64), dense, aligned to one entry: vertex positions in
+ *              the output frame
+ *   attr       [Va][2] (row, col) of attr_dtype, dense: what the map holds at a vertex
+ *   faces      [F][3] int32, dense: indices into pos
+ *   attr_faces [F][3] int32 indices into attr, or NULL = faces: welded positions may carry per-corner attributes (the OBJ v/vt model)
+ *   depth      [V] float32 or NULL: per-vertex depth, interpolated affinely in the frame (float64, rounded once); NULL: z = +0
+ *   w          [V] of w_dtype (LERF_F32 promoted exactly / LERF_F64) or NULL: per-vertex homogeneous w; attr is then interpolated perspective-correctly,
+ *              u = (sum l_k a_k / w_k) / (sum l_k / w_k).  There is NO near-plane clipping: a face with a w that is not finite or <= 0 is skipped
+ *   out        under the strided map contract, tile origin (i0, j0) >= 0 as in lerf_coords_invert_raster
+ *   keys       [oH][oW] uint64, caller-owned, contents arbitrary: on return the winning key, low 32 bits the face, all ones = a hole
+ *   depth_out  [oH][oW] float32 dense or NULL: the float of the winning key's high word (NaN in a hole); refused without depth
+ *   max_span   0 = no tear rule, else 1..65536: a face whose box of integer pixels, before the clip, is wider than this on an axis is skipped
+ *   orient     +1 / -1 keeps faces with area2 = (B - A) x (C - A) > 0 / < 0 only, 0 both
+ *   workspace  device memory (the host twin: any memory; it is checked alike and not used), 4-byte aligned, at least
+ *              lerf_coords_trimesh_workspace_bytes(F, n_sets) bytes: [n_sets][F + 1] uint32 counts and the partials of their scan
+ * A face is skipped -- it contributes nothing and forms no address -- when one of its indices is outside [0, V) (attr_faces: [0, Va);
+ * an unsigned compare before any vertex is read), a coordinate is not finite, a depth is NaN, a w is not finite or <= 0, area2 is 0 or
+ * not finite (a repeated index), the cull, the tear rule, or a box that misses the tile.  Each edge function is evaluated with its
+ * endpoints in ascending index of `faces`, so two faces that share an edge BY INDEX see one number with opposite signs; on the grid
+ * triangulation (coords.grid_faces) the call returns lerf_coords_invert_raster's out and keys bit for bit.  The statement order: the
+ * top of csrc/lerf_coords_models.h.
+ * Device: fill keys; one thread per face counts the 4 x 16 pixel item tiles of its clipped box; an exclusive scan over all sets; a
+ * fixed grid in which every wave draws one contiguous chunk of (face, tile) items, a pixel a lane, one 64-bit atomic min per
+ * covered pixel; one thread per entry resolves its key.  Plain launches on the stream: no sync, no allocation, no read-back.
+ * THE SIZE RULE, judged from the sizes before any pointer: n_sets * F * b <= 2^32 - 1 and n_sets * (F + 1) <= 2^32 - 1, b the most
+ * item tiles one face can have = ceil(oH / 4) * ceil(oW / 16), or with max_span > 0 the fewer tiles a box max_span wide can touch,
+ * else LERF_EUNSUPPORTED (2160 x 3840 with max_span = 0: about 33 000 faces; a finer mesh passes a max_span).
+ * Batched: every operand takes a set stride in its own elements (pos / attr: floats or doubles, even; faces: int32;
+ * depth / depth_out: floats; w: floats or doubles; keys: uint64); 0 shares a read-only operand (pos, attr, faces, attr_faces, depth, w) across the batch.
+ * Refused with LERF_EINVAL, launching and writing nothing: the family's list, V, Va, F, oH or oW < 1, max_span outside 0..65536, orient
+ * outside -1..1, depth_out without depth, a null, misaligned or short workspace, a negative i0 / j0, any of out, keys, depth_out and
+ * the workspace intersecting an input or each other over the whole batch, an output shared between sets. */
+size_t lerf_coords_trimesh_workspace_bytes(int64_t F, int n_sets);      /* 0: sizes that are not valid */
+int lerf_coords_trimesh(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                        const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                        void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                        int max_span, int orient, uint64_t* keys, float* depth_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int lerf_coords_trimesh_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                             const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                             void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                             int max_span, int orient, uint64_t* keys, float* depth_out,
+                             void* workspace, size_t workspace_bytes);
+int lerf_coords_trimesh_batched(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                                const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                                void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                                int max_span, int orient, uint64_t* keys, float* depth_out,
+                                void* workspace, size_t workspace_bytes,
+                                int n_sets, int64_t pos_set_stride, int64_t attr_set_stride, int64_t faces_set_stride,
+                                int64_t attr_faces_set_stride, int64_t depth_set_stride, int64_t w_set_stride,
+                                int64_t out_set_stride, int64_t keys_set_stride, int64_t depth_out_set_stride, void* stream);
+int lerf_coords_trimesh_batched_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                                     const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                                     void* out, int out_dtype, int64_t out_row_stride, int oH, int oW, int i0, int j0,
+                                     int max_span, int orient, uint64_t* keys, float* depth_out,
+                                     void* workspace, size_t workspace_bytes,
+                                     int n_sets, int64_t pos_set_stride, int64_t attr_set_stride, int64_t faces_set_stride,
+                                     int64_t attr_faces_set_stride, int64_t depth_set_stride, int64_t w_set_stride,
+                                     int64_t out_set_stride, int64_t keys_set_stride, int64_t depth_out_set_stride);
 int lerf_coords_compose_bwd_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
                                     const void* b, int b_dtype, int64_t b_row_stride,
                                     const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,

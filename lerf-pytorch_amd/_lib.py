@@ -70,6 +70,8 @@ EXPORTS = [
     "lerf_coords_compose_bwd_batched_ordered_host", "lerf_coords_invert_bwd_ordered", "lerf_coords_invert_bwd_ordered_host",
     "lerf_coords_invert_bwd_batched_ordered", "lerf_coords_invert_bwd_batched_ordered_host",
     "lerf_scan_exclusive_u32_block", "lerf_scan_exclusive_u32_workspace_bytes", "lerf_scan_exclusive_u32", "lerf_scan_exclusive_u32_host",
+    "lerf_coords_trimesh_workspace_bytes", "lerf_coords_trimesh", "lerf_coords_trimesh_host", "lerf_coords_trimesh_batched",
+    "lerf_coords_trimesh_batched_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -377,6 +379,15 @@ def lib():
     L.lerf_scan_exclusive_u32_workspace_bytes.argtypes = [C.c_int64]
     L.lerf_scan_exclusive_u32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
     L.lerf_scan_exclusive_u32_host.argtypes = [C.c_void_p, C.c_int64]
+    # pos, attr, faces, attr_faces, F, depth, w and its dtype; out and its tile; max_span, orient, keys, depth_out; workspace; (n_sets, nine set strides)
+    _trimesh = ([C.c_void_p, C.c_int, C.c_int] * 2 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_int, C.c_int, C.c_void_p, C.c_void_p] +
+                [C.c_void_p, C.c_size_t])
+    _trimesh_batched = _trimesh + [C.c_int] + [C.c_int64] * 9
+    L.lerf_coords_trimesh_workspace_bytes.restype = C.c_size_t
+    L.lerf_coords_trimesh_workspace_bytes.argtypes = [C.c_int64, C.c_int]
+    L.lerf_coords_trimesh.argtypes, L.lerf_coords_trimesh_host.argtypes = _trimesh + [C.c_void_p], _trimesh
+    L.lerf_coords_trimesh_batched.argtypes, L.lerf_coords_trimesh_batched_host.argtypes = _trimesh_batched + [C.c_void_p], _trimesh_batched
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -656,7 +667,7 @@ def scan_exclusive_u32_host(data):
 
 
 class HostOperands(_Operands):
-    suffix, noun, f32, f64, key = "_host", "a numpy array", np.float32, np.float64, np.uint64
+    suffix, noun, f32, f64, key, i32 = "_host", "a numpy array", np.float32, np.float64, np.uint64, np.int32
     is_array = staticmethod(lambda a: isinstance(a, np.ndarray))
     strides = staticmethod(lambda a: tuple(s // a.itemsize if s % a.itemsize == 0 else None for s in a.strides))
     is_contiguous = staticmethod(lambda a: a.flags.c_contiguous)
@@ -692,6 +703,7 @@ class DeviceOperands(_Operands):
             cls._one = super().__new__(cls)
             cls._one.torch, cls._one.f32, cls._one.f64 = torch, torch.float32, torch.float64
             cls._one.key = torch.int64                 # the 64 bits of a raster key (numpy's side holds them as uint64)
+            cls._one.i32 = torch.int32
         return cls._one
 
     strides = staticmethod(lambda t: t.stride())
@@ -851,6 +863,78 @@ def coords_invert_raster_on(X, f, out_hw, depth, dtype, out, origin, max_span, o
                                               int(origin[1]), int(max_span), int(orient), X.ptr(k)),
           (ta, fhw[0] * fhw[1] if Bd > 1 else 0, to, ohw[0] * ohw[1] if B > 1 else 0))
     return (out, k) if return_keys else out
+
+
+TRIMESH_TILE = (4, 16)          # kTileRows x kTileCols: the item tile of the rasteriser's hot path
+TRIMESH_MAX_SPAN = 65536
+
+
+def trimesh_max_items(F, n_sets, out_hw, max_span):
+    """the size rule of lerf_coords_trimesh in Python: n_sets * F * b, b the most item tiles one face can have; the call is refused
+    (LERF_EUNSUPPORTED) when this exceeds 2^32 - 1"""
+    b = 1
+    for n, tile in zip(out_hw, TRIMESH_TILE):
+        plane = -(-int(n) // tile)
+        b *= min(plane, (int(max_span) + tile - 2) // tile + 1) if max_span > 0 else plane
+    return int(n_sets) * int(F) * b
+
+
+def coords_trimesh_on(X, pos, attr, faces, out_hw, attr_faces, depth, w, dtype, out, origin, max_span, orient, keys, return_keys, return_depth):
+    what = "lerf_coords_trimesh" + X.suffix
+    for a, name in ((pos, "pos"), (attr, "attr")):
+        if not X.is_array(a) or a.ndim not in (2, 3) or a.shape[-1] != 2 or min(a.shape) < 1 or not X.is_float(a):
+            raise ValueError("%s: %s must be %s [V, 2] or [B, V, 2], float32 or float64" % (what, name, X.noun))
+    p, a = X.contiguous(pos), X.contiguous(attr)
+    dev = X.device(p)
+    B = _one_batch(what, ("pos", "attr"), p.shape[0] if p.ndim == 3 else 0, a.shape[0] if a.ndim == 3 else 0)
+    V, Va = p.shape[-2], a.shape[-2]
+
+    def indices(f, name):
+        if not X.is_array(f) or f.dtype != X.i32 or f.ndim not in (2, 3) or f.shape[-1] != 3 or min(f.shape) < 1:
+            raise ValueError("%s: %s must be %s [F, 3] or [B, F, 3], int32" % (what, name, X.noun))
+        if f.ndim == 3 and f.shape[0] != B:
+            raise ValueError("%s: %s holds %d sets of faces for a batch of %d" % (what, name, f.shape[0], B))
+        return X.contiguous(f)
+
+    fc = indices(faces, "faces")
+    F = fc.shape[-2]
+    af = None if attr_faces is None else indices(attr_faces, "attr_faces")
+    if af is not None and af.shape[-2] != F:
+        raise ValueError("%s: attr_faces must hold one triple per face" % what)
+
+    def per_vertex(v, name, dtypes):
+        if v is None:
+            return None
+        if not X.is_array(v) or v.dtype not in dtypes or v.ndim not in (1, 2) or v.shape[-1] != V or (v.ndim == 2 and v.shape[0] != B):
+            raise ValueError("%s: %s must be %s [V] or [B, V], float32%s" % (what, name, X.noun, " or float64" if len(dtypes) > 1 else ""))
+        return X.contiguous(v)
+
+    d, wv = per_vertex(depth, "depth", (X.f32,)), per_vertex(w, "w", (X.f32, X.f64))
+    if return_depth and d is None:
+        raise ValueError("%s: depth_out needs depth" % what)
+    if not 0 <= int(max_span) <= TRIMESH_MAX_SPAN or not -1 <= int(orient) <= 1:
+        raise ValueError("%s: max_span is 0 (no tear rule) or 1..%d, orient -1, 0 or 1" % (what, TRIMESH_MAX_SPAN))
+    ohw = (int(out_hw[0]), int(out_hw[1]))
+    n_sets = max(B, 1)
+    if min(ohw) < 1:
+        raise ValueError("%s: out_hw must be positive" % what)
+    if trimesh_max_items(F, n_sets, ohw, int(max_span)) > 0xffffffff or n_sets * (F + 1) > 0xffffffff:
+        raise LerfError("%s: %d faces x %d sets into %d x %d with max_span = %d may need more than 2^32 - 1 (face, tile) items; pass a "
+                        "max_span (a face wider than that is skipped), or split the mesh" % (what, F, n_sets, ohw[0], ohw[1], max_span))
+    out, so, to = X.outs(out, B, ohw, a.dtype if dtype is None else dtype, a.dtype, dev, what)
+    k = X.dense(keys, tuple(out.shape[:-1]), X.key, dev, what + ": keys")
+    zo = X.new(tuple(out.shape[:-1]), X.f32, dev) if return_depth else None
+    X.one_device(what, ("pos", "attr", "faces", "attr_faces", "depth", "w", "out"), p, a, fc, af, d, wv, out)
+    nbytes = int(lib().lerf_coords_trimesh_workspace_bytes(F, n_sets))
+    ws = X.scratch(nbytes, dev)
+    per = lambda t, base, n: 0 if t is None or t.ndim == base or B < 2 else n          # the set stride of a dense operand: 0 shares it
+    X.run("lerf_coords_trimesh", B, p, (X.ptr(p), X.code(p), V, X.ptr(a), X.code(a), Va, X.ptr(fc), X.ptr(af), F, X.ptr(d), X.ptr(wv), LERF_F32 if wv is None else X.code(wv),
+                                        *X.operand(out, so), ohw[0], ohw[1], int(origin[0]), int(origin[1]), int(max_span), int(orient), X.ptr(k),
+                                        X.ptr(zo), X.ptr(ws), nbytes),
+          (per(p, 2, 2 * V), per(a, 2, 2 * Va), per(fc, 2, 3 * F), per(af, 2, 3 * F), per(d, 1, V), per(wv, 1, V), to,
+           ohw[0] * ohw[1] if B > 1 else 0, ohw[0] * ohw[1] if B > 1 else 0))
+    res = (out,) + ((k,) if return_keys else ()) + ((zo,) if return_depth else ())
+    return res if len(res) > 1 else out
 
 
 def _coords_bwd_operands(X, what, first, second, names, grad_out):
@@ -1080,6 +1164,17 @@ def coords_invert_raster_host(f, out_hw, depth=None, dtype=np.float64, out=None,
     return_keys=True: the winning keys, low 32 bits the triangle, all ones for a hole.  A batch f [B, fH, fW, 2] (depth [B, fH, fW], one
     shared [fH, fW] or None; keys [B, oH, oW], one plane per sample) -> [B, oH, oW, 2] by one call of lerf_coords_invert_raster_batched_host."""
     return coords_invert_raster_on(_HOST, f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys)
+
+
+def coords_trimesh_host(pos, attr, faces, out_hw, attr_faces=None, depth=None, w=None, dtype=None, out=None, origin=(0, 0), max_span=0, orient=0,
+                        keys=None, return_keys=False, return_depth=False):
+    """lerf_coords_trimesh_host: the indexed triangle mesh (pos [V, 2], attr [Va, 2] float32 / float64; faces, attr_faces [F, 3] int32;
+    depth [V] float32; w [V] float32 / float64) rasterised into the tile out_hw at `origin` by the plain loop over faces and their pixel boxes with the
+    kernel's own per-face and per-pixel functions: bit-equal to ops.coords_trimesh in out, keys and depth.  -> out, or (out[, keys]
+    [, depth_out]) with return_keys / return_depth.  dtype: out's, default attr's.  pos / attr [B, V, 2] (faces, attr_faces, depth, w
+    batched alike or shared) -> [B, oH, oW, 2] by one call of lerf_coords_trimesh_batched_host."""
+    return coords_trimesh_on(_HOST, pos, attr, faces, out_hw, attr_faces, depth, w, dtype, out, origin, max_span, orient, keys, return_keys,
+                             return_depth)
 
 
 def coords_compose_bwd_host(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):

@@ -47,6 +47,12 @@ position a forward map gives it, with a normalisation plane for the modes "avera
 differentiable twin (lerf_splat_bwd: image, weight and map), the third chain beside reproject's two:
     m, z = reproject_torch(depth_src, K_src, K_dst, R, t, return_depth=True)
     splat_torch(img_src, m, hw, weight=-beta * z, mode="softmax")             forward, soft: the source's own depth, differentiable
+
+from_triangles builds a map from an irregular TRIANGLE MESH (lerf_coords_trimesh): vertex positions in the output
+frame, the source position every vertex shows, faces by index, optionally per-corner attributes (attr_faces), a per-vertex depth
+(the nearest face wins) and a per-vertex w (perspective-correct interpolation) -- landmark-driven piecewise-affine warps, UV-mapped
+meshes, any warp whose control points are not a grid.  invert_raster's watertight inside test and integer-min key over faces of any
+size, bit-equal to its host twin; pixels no face covers stay NaN.  grid_faces is invert_raster's own triangulation.  No autograd.
 """
 from __future__ import annotations
 
@@ -528,6 +534,92 @@ def invert_flow_raster(flow, depth=None, max_span=16, orient=0):
     f = f if f.dtype in (np.float32, np.float64) else f.astype(np.float64)
     ident = from_flow(np.zeros((H, W, 2))).astype(f.dtype)
     return invert_raster(ident + f, (H, W), depth, max_span, orient) - ident
+
+
+def grid_faces(fH, fW):
+    """The triangulation invert_raster draws of a map [fH, fW, 2] (fH, fW >= 2), as faces for from_triangles: int32
+    [2 (fH - 1) (fW - 1), 3] indices into the map's vertices in row-major order (vertex (i, j) = i fW + j), in invert_raster's
+    numbering and vertex order -- cell (i, j) gives face 2 (i (fW - 1) + j) = (i, j), (i, j + 1), (i + 1, j) and the next face
+    = (i + 1, j + 1), (i + 1, j), (i, j + 1).  from_triangles(map.reshape(-1, 2), grid indices, grid_faces(fH, fW), hw) IS
+    invert_raster(map, hw), bit for bit."""
+    fH, fW = int(fH), int(fW)
+    if fH < 2 or fW < 2:
+        raise ValueError("grid_faces: fH and fW must be at least 2")
+    i, j = np.meshgrid(np.arange(fH - 1, dtype=np.int64), np.arange(fW - 1, dtype=np.int64), indexing="ij")
+    v = (i * fW + j).reshape(-1)
+    faces = np.stack([np.stack([v, v + 1, v + fW], axis=-1), np.stack([v + fW + 1, v + fW, v + 1], axis=-1)], axis=1).reshape(-1, 3)
+    if faces.max() > 0x7fffffff:
+        raise ValueError("grid_faces: the vertex indices do not fit int32")
+    return faces.astype(np.int32)
+
+
+def from_triangles(pos, attr, faces, out_hw, attr_faces=None, depth=None, w=None, max_span=0, orient=0, dtype=None, return_depth=False,
+                   return_faces=False):
+    """An irregular TRIANGLE MESH rasterised into a dense map [oH, oW, 2] for remap: landmark-driven piecewise-affine warps, UV-mapped
+    meshes, any warp whose control points are not a grid.  pos [V, 2]: the (row, col) of every vertex in the OUTPUT frame; attr
+    [Va, 2]: what the map holds at a vertex, the SOURCE position (row, col); faces [F, 3] integer indices into pos; attr_faces
+    [F, 3] indices into attr (None: faces) -- welded positions with per-corner texture coordinates, the OBJ v/vt model.  Inside a
+    face the attribute is interpolated affinely in the frame, or perspective-correctly when w [V] (the homogeneous w of every
+    vertex) is given; there is no near-plane clipping, a face with a w <= 0 is skipped.  depth [V]: where faces overlap the
+    smallest interpolated depth wins the pixel (None, and ties: the lowest face).  Pixels no face covers hold (NaN, NaN), which the
+    remap reads as "no source" (mask false).  The inside test is closed and watertight for faces that share an edge BY INDEX.
+
+    max_span: 0 = none, else a face whose box of pixels is wider than this on either axis is skipped (the tear rule of
+    invert_raster).  orient +1 / -1 keeps only faces with (B - A) x (C - A) > 0 / < 0 in (row, col), 0 both.  A face with an index
+    outside the mesh, a vertex that is not finite, a NaN depth or no area is skipped.  THE SIZE RULE: the (face, tile) items of one
+    call are numbered in 32 bits, B * F * b <= 2^32 - 1 with b the 4 x 16 pixel tiles of the frame (or of a box max_span wide) --
+    about 33 000 faces into 2160 x 3840 with max_span = 0; a finer mesh passes a max_span.
+
+    numpy in -> numpy out (the kernel's host twin, bit-equal); device tensors in -> a device tensor (lerf_coords_trimesh: fill, count,
+    scan, one wave per (face, tile), resolve; no sync); mixed operands are refused.  dtype: the map's, default attr's.  pos (and / or
+    attr) [B, V, 2] give [B, oH, oW, 2] in ONE batched call; faces, attr_faces, depth and w are then batched alike or shared.
+    return_depth: also the winning depth, float32 [oH, oW], NaN in holes (needs depth); return_faces: also the winning face,
+    int64 [oH, oW], -1 in holes -> map, or (map[, depth][, faces]).  Bit-equal from run to run.  No autograd: an operand that requires
+    grad (with grad mode on) is refused."""
+    given = [t for t in (pos, attr, faces, attr_faces, depth, w) if t is not None]
+    dev = [bool(getattr(t, "is_cuda", False)) for t in given]
+    if any(d != dev[0] for d in dev):
+        raise ValueError("from_triangles: every operand on the host or all on one device, not mixed")
+    _no_autograd("from_triangles", given)
+    H, W = int(out_hw[0]), int(out_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("out_hw must be positive")
+    if return_depth and depth is None:
+        raise ValueError("from_triangles: return_depth needs depth")
+    if dev[0]:
+        import torch
+        from . import ops
+        fl = lambda t: t.detach().contiguous() if t.dtype in (torch.float32, torch.float64) else t.detach().to(torch.float64).contiguous()
+        f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+        i32 = lambda t: None if t is None else _int32_indices(t.detach(), torch.int32, lambda x, dt: x.to(dt).contiguous())
+        dt = None if dtype is None else getattr(torch, _np_dtype(dtype).name)
+        one, hole = ops.coords_trimesh, lambda k: k == -1
+        low = lambda k: torch.where(hole(k), k, k & 0xffffffff)
+    else:
+        from . import _lib
+        host = lambda t: np.asarray(t.detach().numpy() if hasattr(t, "detach") else t)
+        fl = lambda t: np.ascontiguousarray(host(t) if host(t).dtype in (np.float32, np.float64) else host(t).astype(np.float64))
+        f32 = lambda t: None if t is None else np.ascontiguousarray(host(t), dtype=np.float32)
+        i32 = lambda t: None if t is None else _int32_indices(host(t), np.int32, lambda x, dt: np.ascontiguousarray(x, dtype=dt))
+        dt = None if dtype is None else _np_dtype(dtype)
+        one = _lib.coords_trimesh_host
+        low = lambda k: np.where(k == np.uint64(2 ** 64 - 1), np.int64(-1), (k & np.uint64(0xffffffff)).astype(np.int64))
+    res = one(fl(pos), fl(attr), i32(faces), (H, W), attr_faces=i32(attr_faces), depth=f32(depth), w=None if w is None else fl(w), dtype=dt, max_span=max_span,
+              orient=orient, return_keys=bool(return_faces), return_depth=bool(return_depth))
+    if not (return_faces or return_depth):
+        return res
+    m, rest = res[0], list(res[1:])
+    k = low(rest.pop(0)) if return_faces else None
+    return (m,) + ((rest.pop(0),) if return_depth else ()) + ((k,) if return_faces else ())
+
+
+def _int32_indices(t, int32, cast):
+    """face indices as int32.  An int64 index beyond int32 is clamped to -1 / 2^31 - 1 first, which no mesh holds (V < 2^31): its
+    face is skipped like any face with an index outside the mesh, where a plain cast would wrap it into a valid one.  No read-back."""
+    name = str(t.dtype).replace("torch.", "")
+    if name not in ("int8", "uint8", "int16", "int32", "int64"):
+        raise ValueError("from_triangles: faces and attr_faces hold integer indices, not %s" % name)
+    return cast(t.clip(-1, 0x7fffffff) if name == "int64" else t, int32)
 
 
 # ---------------------------------------------------------------------------------------------- differentiable twins

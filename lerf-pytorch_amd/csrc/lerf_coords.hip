@@ -27,6 +27,10 @@
 // runners above; RasterOp is a SCATTER operation, one call per cell of F, under ScatterOnDevice{stream} (cell_kernel<OP>, the same
 // block and grid, a 64-bit integer atomic min) / ScatterOnHost{} (the row-major loop, a plain min).  An integer minimum does not
 // depend on the order of its operands, so this scatter IS bit-equal between the two and from run to run.
+// The triangle-mesh rasteriser (lerf_coords_trimesh) draws an INDEXED mesh with the same per-pixel functions in five
+// passes: KeyFillOp, TriCountOp and TriResolveOp are per-entry functors under the two runners; the raster pass is trimesh_raster_kernel,
+// one wave per (face, 4 x 16 pixel tile) item of a scanned item list (TriRasterOnDevice), or the plain loop over faces and their boxes
+// (TriRasterOnHost).  Its notes are with it, after the ordered scatter's scan.
 //
 // Kernels of their own shape (unchanged by the above):
 //   coords_mesh_bwd_{rows,cols}_kernel      the adjoint of the mesh upsample, map = Wr . ctrl . Wc^T  =>  grad_ctrl = Wr^T . grad_map . Wc,
@@ -729,6 +733,207 @@ LERF_HD inline void sort_segment(uint32_t* a, uint32_t n) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the triangle-mesh rasteriser
+// An INDEXED mesh drawn into a map: invert_raster's per-pixel arithmetic (closed watertight inside test, 64-bit (depth, face) key, integer
+// atomic min) over faces of any size.  One thread per cell cannot serve a face hundreds of pixels wide, so the faces are BINNED into item
+// tiles -- kTileRows x kTileCols = 4 x 16 pixels of the key plane, aligned to the plane -- and one WAVE draws one (face, tile) item, a
+// pixel a lane: its 64 atomics are four runs of 16 consecutive keys (128 bytes).  Five passes in stream order, no sync, no read-back:
+//   1 fill     KeyFillOp under entry_kernel
+//   2 count    TriCountOp under entry_kernel, one thread per face: the set-up (tri_setup) and the number of item tiles of its clipped
+//              box (tri_tiles), a uint32 in count[set][f]; slot F of every set holds 0
+//   3 scan     scan_exclusive_u32 over the CONCATENATED [n_sets (F + 1)] counts: start[g] = the first item of face slot g, and the last
+//              slot (a pad, count 0) holds the total.  One item list spans the batch, so the sets balance each other.
+//   4 raster   trimesh_raster_kernel: a grid fixed by sizes the host knows; wave k takes the items [k n, (k + 1) n), n = ceil(total / waves),
+//              total read from start.  One upper_bound for the face of its first item, then a forward walk (++g while item >= start[g + 1],
+//              guarded by the last slot); per item the wave re-runs the face's set-up and its lanes take the tile's 64 pixels through
+//              tri_pixel and KeyMinDevice.  The search, the walk and the set-up are wave-uniform.
+//   5 resolve  TriResolveOp under entry_kernel: one key load, the face's indices, three positions and three attributes, one store
+// The host twin runs passes 1 and 5 under OnHost and, for pass 2 - 4, the plain loop over sets, faces and box pixels with KeyMinHost: an
+// integer minimum does not depend on the order, so the tile shape and the chunking cannot show in the result.
+// Addresses: an index is compared UNSIGNED against V (Va) before it forms an address (tri_index_ok); a pixel is drawn only inside the
+// face's clipped box, which raster_axis's rule puts inside the tile in floating point before the conversion to int, so keys is indexed
+// inside [oH][oW] WHATEVER start holds; the walk over start stops at its last slot, and an item number beyond the face's recomputed tile
+// count is dropped; count is written at slots < n_sets (F + 1) only.  The resolve reads the face a key names only when it is < F.
+template <typename TP>
+struct TriMesh {
+    const TP* pos;
+    int V, Va;
+    const int32_t* faces;
+    const int32_t* attr_faces;
+    int F;
+    const float* depth;
+    const void* w;      // float32 or float64 (w_f64)
+    bool w_f64;
+    int orient, max_span, i0, j0, oH, oW;
+    int64_t pos_set, faces_set, afaces_set, depth_set, w_set;
+
+    // face f of set s with its vertices read: t, the indices into attr (ai) and the three w (1 without); false: an index outside the mesh
+    LERF_HD bool read(int s, int f, TriFace* t, int32_t* ai, double* wv) const {
+        const int32_t* fp = faces + set_offset(s, faces_set) + 3 * (int64_t)f;
+        const int32_t* ap = attr_faces ? attr_faces + set_offset(s, afaces_set) + 3 * (int64_t)f : fp;
+        t->ia = fp[0]; t->ib = fp[1]; t->ic = fp[2];
+        ai[0] = ap[0]; ai[1] = ap[1]; ai[2] = ap[2];
+        if (!tri_index_ok(t->ia, t->ib, t->ic, V) || !tri_index_ok(ai[0], ai[1], ai[2], Va)) return false;
+        const TP* p = pos + set_offset(s, pos_set);
+        t->A = load_entry(p, 0, 0, t->ia);
+        t->B = load_entry(p, 0, 0, t->ib);
+        t->C = load_entry(p, 0, 0, t->ic);
+        t->zA = t->zB = t->zC = 0.0f;
+        if (depth) {
+            const float* d = depth + set_offset(s, depth_set);
+            t->zA = d[t->ia]; t->zB = d[t->ib]; t->zC = d[t->ic];
+        }
+        wv[0] = wv[1] = wv[2] = 1.0;
+        if (w && w_f64) {
+            const double* q = (const double*)w + set_offset(s, w_set);
+            wv[0] = q[t->ia]; wv[1] = q[t->ib]; wv[2] = q[t->ic];
+        } else if (w) {
+            const float* q = (const float*)w + set_offset(s, w_set);
+            wv[0] = (double)q[t->ia]; wv[1] = (double)q[t->ib]; wv[2] = (double)q[t->ic];
+        }
+        return true;
+    }
+
+    LERF_HD bool setup(int s, int f, TriFace* t, RasterBox* box) const {
+        int32_t ai[3];
+        double wv[3];
+        return read(s, f, t, ai, wv) && tri_setup(*t, depth != nullptr, w != nullptr, wv[0], wv[1], wv[2], orient, max_span, i0, j0, oH, oW, box);
+    }
+};
+
+// the face slots [n_sets][F + 1] as an entry grid of 4 rows: slot = i * cw + j, cw = ceil((F + 1) / 4)
+constexpr int kTriCountRows = 4;
+
+template <typename TP>
+struct TriCountOp {
+    TriMesh<TP> mesh;
+    uint32_t* count;
+    int cw;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const int64_t slot = (int64_t)i * cw + j;
+        if (slot > mesh.F) return;
+        uint32_t n = 0;
+        TriFace t;
+        RasterBox box;
+        if (slot < mesh.F && mesh.setup(s, (int)slot, &t, &box)) {
+            const TriTiles tt = tri_tiles(box, mesh.i0, mesh.j0);
+            n = (uint32_t)tt.ntr * (uint32_t)tt.ntc;
+        }
+        count[(int64_t)s * ((int64_t)mesh.F + 1) + slot] = n;
+    }
+};
+
+template <typename TP, typename TA, typename TO>
+struct TriResolveOp {
+    TriMesh<TP> mesh;
+    const TA* attr;
+    const uint64_t* keys;
+    TO* out;
+    int64_t stride;
+    float* depth_out;
+    int64_t attr_set, keys_set, out_set, dout_set;
+    LERF_HD void operator()(int i, int j, int s) const {
+        const uint64_t key = keys[set_offset(s, keys_set) + (int64_t)i * mesh.oW + j];
+        Point u{__builtin_nan(""), __builtin_nan("")};
+        float z = __builtin_nanf("");
+        TriFace t;
+        int32_t ai[3];
+        double wv[3];
+        if (key != kNoKey && (uint32_t)key < (uint32_t)mesh.F && mesh.read(s, (int)(uint32_t)key, &t, ai, wv)) {
+            const TA* a = attr + set_offset(s, attr_set);
+            u = tri_attr(t, load_entry(a, 0, 0, ai[0]), load_entry(a, 0, 0, ai[1]), load_entry(a, 0, 0, ai[2]), mesh.w != nullptr, wv[0], wv[1], wv[2],
+                         (double)(mesh.i0 + i), (double)(mesh.j0 + j));
+            z = key_depth(key);
+        }
+        store_entry(out + set_offset(s, out_set), stride, i, j, u);
+        if (depth_out) depth_out[set_offset(s, dout_set) + (int64_t)i * mesh.oW + j] = z;
+    }
+};
+
+constexpr int kTriWaves = 4;           // waves per block of the raster pass
+constexpr int kTriBlocks = 2048;       // its largest grid: 8 blocks per CU of 256
+
+// the blocks of the raster pass, from sizes alone: no more waves than there can be items
+inline unsigned tri_blocks(uint64_t max_items) {
+    const uint64_t want = (max_items + kTriWaves - 1) / kTriWaves;
+    return (unsigned)(want < 1 ? 1 : want > (uint64_t)kTriBlocks ? (uint64_t)kTriBlocks : want);
+}
+
+template <typename TP>
+__global__ void __launch_bounds__(64 * kTriWaves)
+trimesh_raster_kernel(const TriMesh<TP> mesh, const uint32_t* __restrict__ start, uint32_t n_slots, uint64_t* keys, int64_t keys_set) {
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kTriWaves + threadIdx.x / 64));
+    const uint32_t waves = gridDim.x * kTriWaves;
+    const uint32_t total = start[n_slots - 1];
+    const uint32_t per = (uint32_t)(((uint64_t)total + waves - 1) / waves);
+    const uint64_t first64 = (uint64_t)wave * per;
+    if (first64 >= total) return;                                  // an empty chunk
+    const uint32_t first = (uint32_t)first64;
+    const uint32_t end = total - first < per ? total : first + per;
+    uint32_t lo = 0, hi = n_slots;                                 // upper_bound: the first slot whose start is beyond `first`
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (start[mid] <= first) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0) return;                                           // start[0] is 0 after an exclusive scan
+    uint32_t g = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lo - 1));
+    const uint32_t slots = (uint32_t)mesh.F + 1u;
+    int s = (int)(g / slots), f = (int)(g % slots);
+    const int lane = threadIdx.x & 63, lr = lane / kTileCols, lc = lane % kTileCols;
+    for (uint32_t item = first; item < end; ++item) {
+        while (g + 1 < n_slots && item >= start[g + 1]) {          // zero-count slots are stepped over; the last slot ends the walk
+            ++g;
+            if (++f == (int)slots) { f = 0; ++s; }
+        }
+        if (g + 1 >= n_slots || f >= mesh.F) return;               // the pad slots hold no items
+        TriFace t;
+        RasterBox box;
+        if (!mesh.setup(s, f, &t, &box)) continue;
+        const TriTiles tt = tri_tiles(box, mesh.i0, mesh.j0);
+        const uint32_t k = item - start[g];
+        if (k >= (uint32_t)tt.ntr * (uint32_t)tt.ntc) continue;
+        const int rr = (tt.tr0 + (int)(k / (uint32_t)tt.ntc)) * kTileRows + lr, qq = (tt.tc0 + (int)(k % (uint32_t)tt.ntc)) * kTileCols + lc;
+        if (rr < box.r0 - mesh.i0 || rr > box.r1 - mesh.i0 || qq < box.c0 - mesh.j0 || qq > box.c1 - mesh.j0) continue;
+        tri_pixel(t, box, mesh.depth != nullptr, (uint32_t)f, mesh.i0 + rr, mesh.j0 + qq, mesh.i0, mesh.j0, mesh.oW,
+                  KeyMinDevice{keys + set_offset(s, keys_set)});
+    }
+}
+
+// passes 2 - 4 on the device; count: [n_slots] uint32, partials: the scan's
+struct TriRasterOnDevice {
+    hipStream_t stream;
+    template <typename TP>
+    int operator()(const TriMesh<TP>& mesh, uint64_t* keys, int64_t keys_set, int n_sets, uint32_t* count, uint64_t max_items) const {
+        const int64_t n_slots = (int64_t)n_sets * ((int64_t)mesh.F + 1);
+        const int cw = (int)(((int64_t)mesh.F + kTriCountRows) / kTriCountRows);
+        int rc = OnDevice{stream}(TriCountOp<TP>{mesh, count, cw}, kTriCountRows, cw, n_sets);
+        if (rc != LERF_OK) return rc;
+        clear_stale_error();
+        scan_exclusive_u32(stream, count, n_slots, 1, n_slots, count + n_slots, nullptr);
+        hipLaunchKernelGGL(trimesh_raster_kernel<TP>, dim3(tri_blocks(max_items)), dim3(64 * kTriWaves), 0, stream, mesh, count, (uint32_t)n_slots,
+                           keys, keys_set);
+        return launch_status();
+    }
+};
+
+// the plain loop over sets, faces and the pixels of their boxes
+struct TriRasterOnHost {
+    template <typename TP>
+    int operator()(const TriMesh<TP>& mesh, uint64_t* keys, int64_t keys_set, int n_sets, uint32_t*, uint64_t) const {
+        for (int s = 0; s < n_sets; ++s)
+            for (int f = 0; f < mesh.F; ++f) {
+                TriFace t;
+                RasterBox box;
+                if (!mesh.setup(s, f, &t, &box)) continue;
+                for (int r = box.r0; r <= box.r1; ++r)
+                    for (int q = box.c0; q <= box.c1; ++q)
+                        tri_pixel(t, box, mesh.depth != nullptr, (uint32_t)f, r, q, mesh.i0, mesh.j0, mesh.oW, KeyMinHost{keys + set_offset(s, keys_set)});
+            }
+        return LERF_OK;
+    }
+};
+
 // pass 4 for target q of set s; op: the scatter_only() form; cursor and list: the set's own; W: the width of the ENTRY grid
 template <typename OP>
 LERF_HD inline void ordered_sum_target(const OP& op, int s, int64_t q, const uint32_t* cursor, uint32_t* list, int W, uint32_t max_adders) {
@@ -1278,6 +1483,63 @@ int invert_raster(RUN run, SCATTER scatter, const void* f, int f_dtype, int64_t 
         return run(ResolveOp<TF, TO>{{(const TF*)f, f_stride}, fW, keys, (TO*)out, o_stride, i0, j0, oW, f_set, keys_set, out_set}, oH, oW, n_sets)));
 }
 
+// The triangle-mesh rasteriser.  THE SIZE RULE is judged from sizes alone, before any pointer: the item list is indexed
+// by uint32, so n_sets * F * b <= 2^32 - 1 with b the most item tiles one face can have (tri_axis_tiles per axis), and the scan's
+// n_sets * (F + 1) slots fit too.  0: the sizes are not valid or beyond the rule.
+inline uint64_t tri_max_items(int64_t F, int n_sets, int oH, int oW, int max_span) {
+    if (F < 1 || F > 0x7fffffffLL || n_sets < 1 || n_sets > 65535 || oH < 1 || oW < 1 || max_span < 0) return 0;
+    const uint64_t b = (uint64_t)tri_axis_tiles(oH, max_span, kTileRows) * (uint64_t)tri_axis_tiles(oW, max_span, kTileCols);
+    const uint64_t faces = (uint64_t)n_sets * (uint64_t)F, cap = 0xffffffffULL;
+    if (faces + (uint64_t)n_sets > cap || b > cap || faces > cap / b) return 0;
+    return faces * b;
+}
+
+inline int64_t tri_workspace_words(int64_t F, int n_sets) {
+    if (F < 1 || F > 0x7fffffffLL || n_sets < 1 || n_sets > 65535 || (int64_t)n_sets * (F + 1) > 0xffffffffLL) return 0;
+    const int64_t n_slots = (int64_t)n_sets * (F + 1);
+    return n_slots + scan_partials(n_slots);
+}
+
+// fill, count, scan, raster, resolve in stream order (the host: fill, the loop over faces, resolve); no sync, no allocation, no read-back
+template <typename RUN, typename RASTER>
+int trimesh(RUN run, RASTER raster, const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+            const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0,
+            int j0, int max_span, int orient, uint64_t* keys, float* depth_out, void* workspace, size_t workspace_bytes, int n_sets, int64_t pos_set,
+            int64_t attr_set, int64_t faces_set, int64_t afaces_set, int64_t depth_set, int64_t w_set, int64_t out_set, int64_t keys_set,
+            int64_t dout_set) {
+    enum { POS, ATTR, FACES, AFACES, DEPTH, W, OUT, KEYS, DOUT, WS };
+    const bool sizes = V >= 1 && Va >= 1 && F >= 1 && oH >= 1 && oW >= 1 && n_sets >= 1 && n_sets <= 65535 && max_span >= 0 && max_span <= kMaxTriSpan;
+    const uint64_t max_items = sizes ? tri_max_items(F, n_sets, oH, oW, max_span) : 0;
+    if (sizes && !max_items) return LERF_EUNSUPPORTED;
+    const int64_t words = sizes ? tri_workspace_words(F, n_sets) : 0;
+    const Operand ws{workspace, 1, 4, 4 * words, 0, false, true, false, true, true};
+    int rc = check_call(n_sets,
+                        {dense_operand(pos, pos_dtype, V, 1, pos_set, SHARE), dense_operand(attr, attr_dtype, Va, 1, attr_set, SHARE),
+                         plane_operand(faces, sizeof(int32_t), F, 3, faces_set, SHARE),
+                         plane_operand(attr_faces, sizeof(int32_t), F, 3, afaces_set, SHARE | OPTIONAL),
+                         plane_operand(depth, sizeof(float), V, 1, depth_set, SHARE | OPTIONAL), plane_operand(w, w_dtype == LERF_F64 ? sizeof(double) : sizeof(float), V, 1, w_set, SHARE | OPTIONAL),
+                         map_operand(out, out_dtype, o_stride, oH, oW, out_set), plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set),
+                         plane_operand(depth_out, sizeof(float), oH, oW, dout_set, OPTIONAL), ws},
+                        {{OUT, POS}, {OUT, ATTR}, {OUT, FACES}, {OUT, AFACES}, {OUT, DEPTH}, {OUT, W},
+                         {KEYS, POS}, {KEYS, ATTR}, {KEYS, FACES}, {KEYS, AFACES}, {KEYS, DEPTH}, {KEYS, W},
+                         {DOUT, POS}, {DOUT, ATTR}, {DOUT, FACES}, {DOUT, AFACES}, {DOUT, DEPTH}, {DOUT, W},
+                         {WS, POS}, {WS, ATTR}, {WS, FACES}, {WS, AFACES}, {WS, DEPTH}, {WS, W},
+                         {OUT, KEYS}, {OUT, DOUT}, {OUT, WS}, {KEYS, DOUT}, {KEYS, WS}, {DOUT, WS}},
+                        sizes && tile_ok(oH, oW, i0, j0) && (!w || float_dtype(w_dtype)) && orient >= -1 && orient <= 1 && !(depth_out && !depth) && workspace_bytes >= (size_t)(4 * words));
+    if (rc != LERF_OK) return rc;
+    rc = run(KeyFillOp{keys, oW, keys_set}, oH, oW, n_sets);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(pos_dtype, TP, {
+        const TriMesh<TP> mesh{(const TP*)pos, V, Va, faces, attr_faces, F, depth, w, w_dtype == LERF_F64, orient, max_span, i0, j0, oH, oW,
+                               pos_set, faces_set, afaces_set, depth_set, w_set};
+        rc = raster(mesh, keys, keys_set, n_sets, (uint32_t*)workspace, max_items);
+        if (rc != LERF_OK) return rc;
+        LERF_COORDS_DT(attr_dtype, TA, LERF_COORDS_DT(out_dtype, TO,
+            return run(TriResolveOp<TP, TA, TO>{mesh, (const TA*)attr, keys, (TO*)out, o_stride, depth_out, attr_set, keys_set, out_set, dout_set},
+                       oH, oW, n_sets)));
+    });
+}
+
 template <typename RUN>
 int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
                 const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets, int64_t a_set, int64_t b_set, int64_t gout_set,
@@ -1547,6 +1809,48 @@ int lerf_coords_invert_raster_batched_host(const void* f, int f_dtype, int64_t f
                                            int64_t keys_set_stride) {
     return invert_raster(OnHost{}, ScatterOnHost{}, f, f_dtype, f_row_stride, fH, fW, depth, out, out_dtype, out_row_stride, oH, oW, i0, j0,
                          max_span, orient, keys, n_sets, f_set_stride, depth_set_stride, out_set_stride, keys_set_stride);
+}
+
+size_t lerf_coords_trimesh_workspace_bytes(int64_t F, int n_sets) { return sizeof(uint32_t) * (size_t)tri_workspace_words(F, n_sets); }
+
+int lerf_coords_trimesh_batched(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                                const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, void* out, int out_dtype,
+                                int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, float* depth_out,
+                                void* workspace, size_t workspace_bytes, int n_sets, int64_t pos_set_stride, int64_t attr_set_stride,
+                                int64_t faces_set_stride, int64_t attr_faces_set_stride, int64_t depth_set_stride, int64_t w_set_stride,
+                                int64_t out_set_stride, int64_t keys_set_stride, int64_t depth_out_set_stride, void* stream) {
+    return trimesh(OnDevice{(hipStream_t)stream}, TriRasterOnDevice{(hipStream_t)stream}, pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F,
+                   depth, w, w_dtype, out, out_dtype, out_row_stride, oH, oW, i0, j0, max_span, orient, keys, depth_out, workspace, workspace_bytes, n_sets,
+                   pos_set_stride, attr_set_stride, faces_set_stride, attr_faces_set_stride, depth_set_stride, w_set_stride, out_set_stride,
+                   keys_set_stride, depth_out_set_stride);
+}
+
+int lerf_coords_trimesh_batched_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                                     const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, void* out, int out_dtype,
+                                     int64_t out_row_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys,
+                                     float* depth_out, void* workspace, size_t workspace_bytes, int n_sets, int64_t pos_set_stride,
+                                     int64_t attr_set_stride, int64_t faces_set_stride, int64_t attr_faces_set_stride, int64_t depth_set_stride,
+                                     int64_t w_set_stride, int64_t out_set_stride, int64_t keys_set_stride, int64_t depth_out_set_stride) {
+    return trimesh(OnHost{}, TriRasterOnHost{}, pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, out, out_dtype,
+                   out_row_stride, oH, oW, i0, j0, max_span, orient, keys, depth_out, workspace, workspace_bytes, n_sets, pos_set_stride,
+                   attr_set_stride, faces_set_stride, attr_faces_set_stride, depth_set_stride, w_set_stride, out_set_stride, keys_set_stride,
+                   depth_out_set_stride);
+}
+
+int lerf_coords_trimesh(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                        const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, void* out, int out_dtype, int64_t out_row_stride,
+                        int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, float* depth_out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    return lerf_coords_trimesh_batched(pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, out, out_dtype, out_row_stride, oH,
+                                       oW, i0, j0, max_span, orient, keys, depth_out, workspace, workspace_bytes, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, stream);
+}
+
+int lerf_coords_trimesh_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                             const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, void* out, int out_dtype, int64_t out_row_stride,
+                             int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, float* depth_out, void* workspace,
+                             size_t workspace_bytes) {
+    return lerf_coords_trimesh_batched_host(pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, out, out_dtype, out_row_stride,
+                                            oH, oW, i0, j0, max_span, orient, keys, depth_out, workspace, workspace_bytes, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0);
 }
 
 int lerf_coords_compose_bwd_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,

@@ -125,6 +125,38 @@
 //                 keys[q] = min(keys[q], key)     (the device: one 64-bit atomic min; an integer min does not depend on the order)
 //               resolve, per entry: keys[q] all ones (untouched): (NaN, NaN);  else t = the low 32 bits, cell = t >> 1, i = cell / (fW - 1),
 //               j = cell % (fW - 1), the triangle's three vertices are read again, area2 = edge(A, B, C), tri_edges, tri_value: u.
+//   trimesh     out[q] = the attribute an INDEXED triangle mesh holds at pixel q = ((double)(i0 + i), (double)(j0 + j)): pos [V][2] the vertices in
+//               the output frame, attr [Va][2] what the map holds at a vertex, faces [F][3] indices into pos, attr_faces [F][3] into attr (null:
+//               faces), depth [V] float32 and w [V] float32 / float64 optional (promoted exactly).  invert_raster's edge, inside test, tri_depth
+//               and key, over faces of any size; face f has vertices A, B, C = pos at faces[f][0..2] (indices ia, ib, ic).
+//               set-up of one face (TriMesh::read, tri_setup); a face that fails a test is SKIPPED: it contributes nothing, forms no address:
+//                 (uint32)index < (uint32)V for the three of faces, < (uint32)Va for the three of attr_faces (of faces when null): ONE unsigned
+//                 compare each, BEFORE any vertex is read, so -1, V and 2^31 - 1 read nothing               (tri_index_ok)
+//                 the six coordinates finite (v - v == 0); with depth, no NaN among zA, zB, zC
+//                 with w: wA, wB, wC finite and > 0   (no near-plane clipping: a face that crosses w = 0 is skipped)
+//                 area2 = edge(A, B, C);  area2 != 0 and finite (a repeated index gives exactly 0);  not (orient > 0 and area2 < 0), not
+//                 (orient < 0 and area2 > 0)
+//                 per axis:  lo = ceil(min v), hi = floor(max v);  max_span > 0 and (hi - lo) + 1 > (double)max_span: skipped  (tri_axis:
+//                 raster_axis with the tear rule optional);  the clip onto the tile in floating point, lo > hi: skipped, only then the int
+//               per pixel q of the clipped box (tri_pixel; tri_edges_indexed: every directed edge of A -> B -> C -> A from its LOWER vertex
+//               index, so two faces that share an edge by index compare ONE number against 0 with opposite signs):
+//                 e_c = ia < ib ? edge(A, B, q) : -edge(B, A, q)
+//                 e_a = ib < ic ? edge(B, C, q) : -edge(C, B, q)
+//                 e_b = ic < ia ? edge(C, A, q) : -edge(A, C, q)            (on grid_faces' triangulation: tri_edges' numbers, even and odd)
+//                 inside (closed): tri_inside;  z = tri_depth(e, area2, zA, zB, zC), +0.0f without depth;  key = raster_key(z, f)
+//                 keys[q] = min(keys[q], key)
+//               resolve, per entry (TriResolveOp, tri_attr): keys[q] all ones: (NaN, NaN) and NaN in depth_out;  else f = the low 32 bits, the
+//               indices, positions, attributes aA, aB, aC (and w) are read again, area2 = edge(A, B, C), tri_edges_indexed, then per component
+//                 l_b = e_b / area2,  l_c = e_c / area2
+//                 without w:  u = aA + (l_b*(aB - aA) + l_c*(aC - aA))
+//                 with w:     ia = 1 / wA, ib = 1 / wB, ic = 1 / wC
+//                             d = ia + (l_b*(ib - ia) + l_c*(ic - ia))
+//                             n = aA*ia + (l_b*(aB*ib - aA*ia) + l_c*(aC*ic - aA*ia)),  u = n / d
+//                 depth_out = the float whose bits invert sortable() on the key's high word (key_depth): b = s & 0x7FFFFFFF if s has its top bit,
+//                 else ~s;  u is rounded once to out's dtype
+//               The device bins the faces into item tiles of kTileRows x kTileCols = 4 x 16 pixels aligned to the tile's own rows and columns
+//               (tri_tiles: tr0 = (r0 - i0) / 4 .. (r1 - i0) / 4, tc0 = (c0 - j0) / 16 .. (c1 - j0) / 16) and draws one (face, tile) item a wave;
+//               the host loops over faces and boxes.  An integer min does not depend on the order: neither the tiles nor the chunks show.
 //   compose backward (compose_bwd_point; aH, aW >= 2)   one entry with inner point (row, col) and upstream g = (g.r, g.c):
 //                 a NaN in row or col: nothing is read, nothing is scattered, the inner gradient is (0, 0) whatever g holds (a select)
 //                 R = compose_axis(row, aH), Cx = compose_axis(col, aW), wr = {R.w0, R.w1}, wc = {Cx.w0, Cx.w1}: the forward's
@@ -913,6 +945,115 @@ LERF_HD inline Point raster_resolve(uint64_t key, int fW, double q_r, double q_c
     const Point A = odd ? load(i + 1, j + 1) : load(i, j), B = odd ? load(i + 1, j) : load(i, j + 1), C = odd ? load(i, j + 1) : load(i + 1, j);
     const double area2 = edge_fn(A, B, C.r, C.c);
     return tri_value(i, j, odd, tri_edges(A, B, C, odd, q_r, q_c), area2);
+}
+
+// ---- trimesh: an INDEXED triangle mesh drawn into a map (the statement order: the top of this file).  The per-pixel functions are
+// invert_raster's (edge_fn, tri_inside, tri_depth, raster_key); what is new is the edge rule by vertex index, the optional tear rule,
+// the w test, the interpolated attribute and the item tiles of the device's hot path.
+constexpr int kTileRows = 4, kTileCols = 16;      // an item tile of the key plane: a wave's 64 pixels, four runs of 128 contiguous bytes of keys
+constexpr int kMaxTriSpan = 65536;
+
+// all three indices inside [0, n): ONE unsigned compare each, so a negative index is a large one
+LERF_HD inline bool tri_index_ok(int32_t a, int32_t b, int32_t c, int n) {
+    return (uint32_t)a < (uint32_t)n && (uint32_t)b < (uint32_t)n && (uint32_t)c < (uint32_t)n;
+}
+
+// tri_edges with `odd` generalised: every directed edge P -> Q of A -> B -> C -> A is evaluated from its lower vertex index
+LERF_HD inline TriEdges tri_edges_indexed(Point A, Point B, Point C, int32_t ia, int32_t ib, int32_t ic, double q_r, double q_c) {
+#pragma clang fp contract(off)
+    TriEdges e;
+    e.c = ia < ib ? edge_fn(A, B, q_r, q_c) : -edge_fn(B, A, q_r, q_c);
+    e.a = ib < ic ? edge_fn(B, C, q_r, q_c) : -edge_fn(C, B, q_r, q_c);
+    e.b = ic < ia ? edge_fn(C, A, q_r, q_c) : -edge_fn(A, C, q_r, q_c);
+    return e;
+}
+
+// raster_axis with the tear rule optional (max_span == 0: none)
+LERF_HD inline bool tri_axis(double a, double b, double c, int max_span, int first, int n, int* lo_i, int* hi_i) {
+#pragma clang fp contract(off)
+    double lo = ceil(min3(a, b, c)), hi = floor(max3(a, b, c));
+    if (max_span > 0 && (hi - lo) + 1.0 > (double)max_span) return false;
+    const double f = (double)first, l = (double)first + (double)(n - 1);
+    lo = lo < f ? f : lo;
+    hi = hi > l ? l : hi;
+    if (lo > hi) return false;
+    *lo_i = (int)lo;
+    *hi_i = (int)hi;
+    return true;
+}
+
+// one face with its vertices read: what the set-up, the pixels and the resolve share
+struct TriFace {
+    Point A, B, C;
+    int32_t ia, ib, ic;      // indices into pos: the edge rule
+    float zA, zB, zC;        // +0.0f without depth
+};
+
+// false: the face is skipped.  raster_setup's tests with the w test after the depths and the tear rule optional
+LERF_HD inline bool tri_setup(const TriFace& t, bool has_depth, bool has_w, double wA, double wB, double wC, int orient, int max_span, int i0, int j0,
+                              int oH, int oW, RasterBox* box) {
+#pragma clang fp contract(off)
+    if (!(finite_value(t.A.r) && finite_value(t.A.c) && finite_value(t.B.r) && finite_value(t.B.c) && finite_value(t.C.r) && finite_value(t.C.c)))
+        return false;
+    if (has_depth && (t.zA != t.zA || t.zB != t.zB || t.zC != t.zC)) return false;
+    if (has_w && !(finite_value(wA) && finite_value(wB) && finite_value(wC) && wA > 0.0 && wB > 0.0 && wC > 0.0)) return false;
+    const double area2 = edge_fn(t.A, t.B, t.C.r, t.C.c);
+    if (!finite_nonzero(area2)) return false;
+    if ((orient > 0 && area2 < 0.0) || (orient < 0 && area2 > 0.0)) return false;
+    box->area2 = area2;
+    return tri_axis(t.A.r, t.B.r, t.C.r, max_span, i0, oH, &box->r0, &box->r1) && tri_axis(t.A.c, t.B.c, t.C.c, max_span, j0, oW, &box->c0, &box->c1);
+}
+
+// the item tiles a clipped box touches: tiles are aligned to the plane's own rows and columns (relative to the tile origin (i0, j0))
+struct TriTiles {
+    int tr0, tc0, ntr, ntc;
+};
+
+LERF_HD inline TriTiles tri_tiles(const RasterBox& box, int i0, int j0) {
+    TriTiles t;
+    t.tr0 = (box.r0 - i0) / kTileRows;
+    t.tc0 = (box.c0 - j0) / kTileCols;
+    t.ntr = (box.r1 - i0) / kTileRows - t.tr0 + 1;
+    t.ntc = (box.c1 - j0) / kTileCols - t.tc0 + 1;
+    return t;
+}
+
+// the most item tiles one face can have: the tiles of the plane, or of a box max_span wide where that is fewer (sizes only)
+inline int64_t tri_axis_tiles(int n, int max_span, int tile) {
+    const int64_t plane = ((int64_t)n + tile - 1) / tile;
+    const int64_t span = max_span > 0 ? ((int64_t)max_span + tile - 2) / tile + 1 : plane;
+    return span < plane ? span : plane;
+}
+
+// pixel (r, q) of the frame against one face that passed the set-up: MINKEY(index, key) as in raster_cell
+template <typename MINKEY>
+LERF_HD inline void tri_pixel(const TriFace& t, const RasterBox& box, bool has_depth, uint32_t f, int r, int q, int i0, int j0, int oW, MINKEY minkey) {
+#pragma clang fp contract(off)
+    const TriEdges e = tri_edges_indexed(t.A, t.B, t.C, t.ia, t.ib, t.ic, (double)r, (double)q);
+    if (!tri_inside(e, box.area2)) return;
+    const float z = has_depth ? tri_depth(e, box.area2, t.zA, t.zB, t.zC) : 0.0f;
+    minkey((int64_t)(r - i0) * oW + (q - j0), raster_key(z, f));
+}
+
+// the float a key's high word stands for: the exact inverse of raster_key's sortable()
+LERF_HD inline float key_depth(uint64_t key) {
+    const uint32_t s = (uint32_t)(key >> 32);
+    const uint32_t b = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s;
+    return __builtin_bit_cast(float, b);
+}
+
+// the attribute at pixel q of the face whose attributes are aA, aB, aC; has_w: perspective-correct with the vertices' w (a float32 w promoted exactly)
+LERF_HD inline Point tri_attr(const TriFace& t, Point aA, Point aB, Point aC, bool has_w, double wA, double wB, double wC, double q_r, double q_c) {
+#pragma clang fp contract(off)
+    const double area2 = edge_fn(t.A, t.B, t.C.r, t.C.c);
+    const TriEdges e = tri_edges_indexed(t.A, t.B, t.C, t.ia, t.ib, t.ic, q_r, q_c);
+    const double lb = e.b / area2, lc = e.c / area2;
+    if (!has_w) return {aA.r + (lb * (aB.r - aA.r) + lc * (aC.r - aA.r)), aA.c + (lb * (aB.c - aA.c) + lc * (aC.c - aA.c))};
+    const double ia = 1.0 / wA, ib = 1.0 / wB, ic = 1.0 / wC;
+    const double d = ia + (lb * (ib - ia) + lc * (ic - ia));
+    const double nr = aA.r * ia + (lb * (aB.r * ib - aA.r * ia) + lc * (aC.r * ic - aA.r * ia));
+    const double nc = aA.c * ia + (lb * (aB.c * ib - aA.c * ia) + lc * (aC.c * ic - aA.c * ia));
+    return {nr / d, nc / d};
 }
 
 }  // namespace coords

@@ -16,10 +16,14 @@
 // and lerf_scan_exclusive_u32_host) run their four passes over a workspace of exactly lerf_scatter_ordered_workspace_bytes bytes, two sets,
 // pre-filled targets, entries beyond every edge and NaN entries, with a generous cap (the result must be the plain twin's bytes) and with
 // a cap of 1 (the NaN branch), and a workspace one byte short is refused.
+// The triangle-mesh rasteriser's host twins (trimesh_ops: lerf_coords_trimesh_host, lerf_coords_trimesh_batched_host) draw a fan wider than
+// the tile, with indices -1, V and 2^31 - 1, NaN, +-inf and 1e300 vertices and w <= 0 among its faces, into a strided out at a non-zero
+// origin, every dtype mix, two sets with shared faces; a workspace one byte short is refused.
 // It needs no GPU and is never loaded into another process.  Exit status 0 and "ok" on the last line: no report.
 #include "lerf_hip.h"
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -596,6 +600,106 @@ static void ordered_adjoints(int aH, int aW, int oH, int oW) {
     EXPECT(same(gf2, keep));
 }
 
+// the triangle-mesh rasteriser (lerf_coords_trimesh_host / _batched_host) on exactly-sized heap buffers: a fan wider than the tile with
+// skipped faces among the drawn ones -- indices -1, V and 2^31 - 1, NaN, +-inf and 1e300 vertices, NaN depth, w <= 0 -- drawn into a
+// strided out at origin (3, 7), every dtype mix, with and without depth, w (both dtypes), attr_faces and depth_out, every orient, max_span
+// 0, 1 and 300; two sets that share their faces; a far tile; a workspace one byte short and the other refusals
+static void trimesh_ops(int oH, int oW) {
+    const int DT[2] = {LERF_F32, LERF_F64};
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    const int V = 14, Va = 16, F = 20;
+    const double P[V][2] = {{14.3, 18.6}, {-150.0, 20.0}, {-20.0, 210.0}, {160.0, 150.0}, {170.0, -90.0}, {10.0, -160.0}, {5.5, 9.25}, {8.0, 40.0},
+                            {nan, 4.0}, {3.0, inf}, {-inf, 2.0}, {1e300, 1e300}, {-1e300, 1e300}, {1e300, 6.0}};
+    const int32_t faces[F][3] = {{-1, 1, 2}, {0, 1, 2}, {0, V, 3}, {0, 2, 3}, {0, 3, 0x7fffffff}, {0, 3, 4}, {0, 8, 1}, {0, 4, 5}, {9, 0, 1}, {0, 5, 1},
+                                 {10, 2, 3}, {11, 12, 0}, {6, 7, 13}, {6, 6, 7}, {6, 7, 0}, {0, 7, 6}, {12, 0, 11}, {1, 3, 5}, {INT32_MIN, 0, 1}, {7, 6, 13}};
+    int32_t afaces[F][3];
+    for (int f = 0; f < F; ++f)
+        for (int k = 0; k < 3; ++k) afaces[f][k] = f == 7 ? Va : faces[f][k] < 0 || faces[f][k] >= V ? faces[f][k] : faces[f][k] + (f & 1) * 2;
+    std::vector<int32_t> fc(&faces[0][0], &faces[0][0] + 3 * F), af(&afaces[0][0], &afaces[0][0] + 3 * F);
+    std::vector<float> depth(V), w32(V), zo((size_t)oH * oW, -7.0f);
+    std::vector<double> w64(V);
+    for (int v = 0; v < V; ++v) {
+        depth[v] = v == 5 ? (float)nan : 1.0f + 0.125f * (float)(v % 4);
+        w64[v] = v == 4 ? 0.0 : v == 2 ? -0.75 : v == 7 ? inf : 1.0 + 0.0625 * v;
+        w32[v] = (float)w64[v];
+    }
+    const size_t need = lerf_coords_trimesh_workspace_bytes(F, 1), need2 = lerf_coords_trimesh_workspace_bytes(F, 2);
+    EXPECT(need == 4 * (size_t)(F + 1) && need2 == 2 * need && lerf_coords_trimesh_workspace_bytes(0, 1) == 0);
+    std::vector<unsigned char> ws(need, 0x55), ws2(need2, 0x55);
+    for (int tp : DT)
+        for (int ta : DT)
+            for (int to : DT) {
+                Map pos(tp, V, 1, 0), attr(ta, Va, 1, 0), out(to, oH, oW), keep(to, oH, oW);
+                for (int v = 0; v < V; ++v) pos.set(v, 0, P[v][0], P[v][1]);
+                for (int v = 0; v < Va; ++v) attr.set(v, 0, 1.25 * v, 50.0 - 0.5 * v);
+                std::vector<uint64_t> keys((size_t)oH * oW, 5), keys0 = keys;
+                int drawn = 0;
+                for (int with = 0; with < 8; ++with)
+                    for (int span : {0, 1, 300})
+                        for (int orient : {-1, 0, 1}) {
+                            const float* d = (with & 1) ? depth.data() : nullptr;
+                            const void* w = (with & 2) ? ((with & 4) ? (const void*)w64.data() : (const void*)w32.data()) : nullptr;
+                            EXPECT(lerf_coords_trimesh_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), (with & 4) ? af.data() : nullptr, F, d, w,
+                                                            (with & 4) ? LERF_F64 : LERF_F32, out.p(), to, out.stride, oH, oW, 3, 7, span, orient, keys.data(),
+                                                            d ? zo.data() : nullptr, ws.data(), need) == LERF_OK);
+                            EXPECT(keys != keys0);
+                            for (uint64_t k : keys) drawn += k != ~(uint64_t)0;
+                        }
+                EXPECT(drawn > 0);
+                // a far tile: nothing unclipped may become an int
+                EXPECT(lerf_coords_trimesh_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), nullptr, F, depth.data(), nullptr, LERF_F32, out.p(), to, out.stride,
+                                                oH, oW, 0x7fffffff - oH, 0x7fffffff - oW, 0, 0, keys.data(), nullptr, ws.data(), need) == LERF_OK);
+                EXPECT(keys[0] == ~(uint64_t)0);
+                // two sets: their own positions and outputs, shared faces, attributes, depth and w
+                {
+                    Map pos2(tp, 2 * V, 1, 0), out2(to, 2 * oH, oW);
+                    for (int v = 0; v < 2 * V; ++v) pos2.set(v, 0, P[v % V][0] + (v / V) * 0.5, P[v % V][1]);
+                    std::vector<uint64_t> keys2((size_t)2 * oH * oW, 5);
+                    std::vector<float> zo2((size_t)2 * oH * oW, -7.0f);
+                    EXPECT(lerf_coords_trimesh_batched_host(pos2.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, out2.p(), to,
+                                                            out2.stride, oH, oW, 3, 7, 0, 0, keys2.data(), zo2.data(), ws2.data(), need2, 2, 2 * V, 0, 0, 0, 0, 0,
+                                                            oH * out2.stride, (int64_t)oH * oW, (int64_t)oH * oW) == LERF_OK);
+                    EXPECT(lerf_coords_trimesh_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, out.p(), to,
+                                                    out.stride, oH, oW, 3, 7, 0, 0, keys.data(), zo.data(), ws.data(), need) == LERF_OK);
+                    EXPECT(!std::memcmp(keys.data(), keys2.data(), keys.size() * sizeof(uint64_t)) && !std::memcmp(zo.data(), zo2.data(), zo.size() * sizeof(float)));
+                    // the sets' outputs must not be shared; the workspace of one set is short for two
+                    EXPECT(lerf_coords_trimesh_batched_host(pos2.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, keep.p(), to,
+                                                            keep.stride, oH, oW, 3, 7, 0, 0, keys2.data(), nullptr, ws2.data(), need2, 2, 2 * V, 0, 0, 0, 0, 0, 0,
+                                                            (int64_t)oH * oW, 0) == LERF_EINVAL);
+                    EXPECT(lerf_coords_trimesh_batched_host(pos2.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, out2.p(), to,
+                                                            out2.stride, oH, oW, 3, 7, 0, 0, keys2.data(), nullptr, ws.data(), need, 2, 2 * V, 0, 0, 0, 0, 0,
+                                                            oH * out2.stride, (int64_t)oH * oW, 0) == LERF_EINVAL);
+                }
+                keys = keys0;
+                const int64_t s = keep.stride;
+                auto call = [&](const void* pp, int v, const int32_t* ff, int nf, const float* d, float* z, int span, int orient, int i0, uint64_t* k, void* wsp,
+                                size_t wb) {
+                    return lerf_coords_trimesh_host(pp, tp, v, attr.p(), ta, Va, ff, nullptr, nf, d, nullptr, LERF_F32, keep.p(), to, s, oH, oW, i0, 7, span, orient, k,
+                                                    z, wsp, wb);
+                };
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 0, 3, keys.data(), ws.data(), need - 1) == LERF_EINVAL);      // one byte short
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 0, 3, keys.data(), ws.data() + 1, need - 1) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 0, 3, keys.data(), nullptr, need) == LERF_EINVAL);
+                EXPECT(call(nullptr, V, fc.data(), F, nullptr, nullptr, 0, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), 0, fc.data(), F, nullptr, nullptr, 0, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, nullptr, F, nullptr, nullptr, 0, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), 0, nullptr, nullptr, 0, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, zo.data(), 0, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);      // depth_out without depth
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, -1, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 65537, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 2, 3, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 0, -1, keys.data(), ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 0, 3, nullptr, ws.data(), need) == LERF_EINVAL);
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 0, 3, (uint64_t*)ws.data(), ws.data(), need) == LERF_EINVAL);      // keys IS the workspace
+                EXPECT(call(pos.p(), V, fc.data(), F, nullptr, nullptr, 0, 0, 3, keys.data(), fc.data(), need) == LERF_EINVAL);               // the workspace IS faces
+                EXPECT(call(keep.p(), 1, fc.data(), F, nullptr, nullptr, 0, 0, 3, keys.data(), ws.data(), need) == LERF_EINVAL);              // out IS pos
+                EXPECT(lerf_coords_trimesh_host(nullptr, tp, 3, nullptr, ta, 3, nullptr, nullptr, 40000, nullptr, nullptr, LERF_F32, nullptr, to, 2 * 3840, 2160, 3840, 0, 0,
+                                                0, 0, nullptr, nullptr, nullptr, 0) == LERF_EUNSUPPORTED);                               // the size rule, before any pointer
+                EXPECT(keep.same(Map(to, oH, oW)) && keys == keys0);
+                for (unsigned char b : ws) EXPECT(b == 0x55);
+            }
+}
+
 static void ordered_ops() {
     ordered_splat_of<float>(1, 1, 1, 1, LERF_F32);
     ordered_splat_of<float>(23, 31, 29, 37, LERF_F32);
@@ -662,6 +766,10 @@ int main() {
     splat_ops(5, 67, 7, 61);
     splat_ops(23, 31, 29, 37);
     ordered_ops();
+    trimesh_ops(1, 1);
+    trimesh_ops(2, 2);
+    trimesh_ops(5, 67);
+    trimesh_ops(29, 37);
     std::printf(fails ? "%d check(s) failed\n" : "ok\n", fails);
     return fails ? 1 : 0;
 }

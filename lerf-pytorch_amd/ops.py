@@ -1195,6 +1195,25 @@ def coords_invert_raster(f, out_hw, depth=None, dtype=None, out=None, origin=(0,
     return _lib.coords_invert_raster_on(_lib.DeviceOperands(), f, out_hw, depth, dtype, out, origin, max_span, orient, keys, return_keys)
 
 
+def coords_trimesh(pos, attr, faces, out_hw, attr_faces=None, depth=None, w=None, dtype=None, out=None, origin=(0, 0), max_span=0, orient=0,
+                   keys=None, return_keys=False, return_depth=False):
+    """lerf_coords_trimesh: an indexed triangle mesh rasterised into the tile out_hw at `origin` of a coordinate map.  pos [V, 2]:
+    the (row, col) of every vertex in the output frame; attr [Va, 2]: what the map holds there (the source position), float32 or
+    float64 each; faces [F, 3] int32 indices into pos; attr_faces [F, 3] int32 indices into attr (None: faces); depth [V] float32:
+    the smallest interpolated depth wins a pixel (None: the lowest face); w [V] float32 or float64: perspective-correct interpolation of attr
+    (a face with a w <= 0 is skipped: no near-plane clipping); max_span 0 = no tear rule, else a face whose pixel box is wider is
+    skipped; orient +1 / -1 culls, 0 keeps both; (NaN, NaN) where no face lands.  keys: an int64 contiguous [oH, oW] workspace on the
+    mesh's device (None: a new one) that holds the winning 64-bit keys afterwards, low 32 bits the face, -1 for a hole.  -> out, or
+    (out[, keys][, depth_out]) with return_keys / return_depth (depth_out float32 [oH, oW], NaN in holes; needs depth).  dtype:
+    out's, default attr's.  Five launches on the current stream (fill, count, scan, raster, resolve), no sync; bit-equal from run to
+    run and to _lib.coords_trimesh_host.  The (face, tile) items of one call are numbered in 32 bits: n_sets * F * b <= 2^32 - 1 with
+    b the 4 x 16 pixel tiles of the frame, or of a box max_span wide when max_span > 0 -- about 33 000 faces into 2160 x 3840 with
+    max_span = 0; a finer mesh passes a max_span.  pos / attr [B, V, 2] (faces, attr_faces [B, F, 3], depth, w [B, V] batched alike,
+    or one shared) give [B, oH, oW, 2] in the same five launches (lerf_coords_trimesh_batched); keys is then [B, oH, oW]."""
+    return _lib.coords_trimesh_on(_lib.DeviceOperands(), pos, attr, faces, out_hw, attr_faces, depth, w, dtype, out, origin, max_span, orient, keys,
+                                  return_keys, return_depth)
+
+
 def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True), deterministic=False, max_adders=4096):
     """lerf_coords_compose_bwd: ACCUMULATE the adjoint of coords_compose(outer, inner) of grad_out (float64 contiguous [oH, oW, 2])
     into grad_outer (float64 contiguous [aH, aW, 2]: a bilinear scatter by float64 atomic adds, reproducible up to the rounding of
