@@ -1109,6 +1109,55 @@ int lerf_coords_trimesh_batched_host(const void* pos, int pos_dtype, int V, cons
                                      int n_sets, int64_t pos_set_stride, int64_t attr_set_stride, int64_t faces_set_stride,
                                      int64_t attr_faces_set_stride, int64_t depth_set_stride, int64_t w_set_stride,
                                      int64_t out_set_stride, int64_t keys_set_stride, int64_t depth_out_set_stride);
+/* The ADJOINT of lerf_coords_trimesh: the gradients of a loss on the map with respect to attr, pos and w at FIXED
+ * VISIBILITY -- every pixel belongs to the face in the low word of its key; coverage, edges and the depth test are piecewise constant
+ * and get no gradient, so depth gets none and depth_out is not differentiable.  The mesh operands, i0, j0, max_span and orient are
+ * the forward's, and keys is the plane the forward wrote.
+ *   grad_out   [oH][oW][2] float64, dense: the upstream gradient.  It is read ONLY at pixels a face won: a NaN at a hole reaches nothing
+ *   grad_attr  [Va][2] float64, grad_pos [V][2] float64, grad_w [V] float64, dense: ACCUMULATED INTO (the caller zeroes); each may be
+ *              NULL (that gradient is skipped), not all three; grad_w needs w
+ *   workspace  8-byte aligned, lerf_coords_trimesh_bwd_workspace_bytes(F, V, Va, n_sets) bytes (the host twin uses it too): header [4]
+ *              uint32, terms [n_sets][F][15] float64, cursor [n_sets][max(V, Va)], list [n_sets][3 F], the scan's partials
+ *   max_adders >= 1: a vertex with more incident DRAWN faces (corners) than this is not summed: all its components become NaN.  After
+ *              the call header word 1 (byte offset LERF_ORDERED_MAX_COUNT_OFFSET) holds the largest such count, as in the ordered scatter
+ * Two passes whose sums have ONE order, stated at the top of csrc/lerf_coords_models.h, so the device equals the host twin BIT FOR BIT
+ * and two runs agree exactly: a face pass (one workgroup of 4 waves per face reduces the face's 6 or 15 sums over the pixels it won by a
+ * fixed tree) and a vertex pass (the ordered scatter's count, scan, fill, sort and sum with the faces as entries: one writer per element
+ * adds its incident faces' terms in ascending (face, corner) order).  A face the forward's set-up skips adds nothing.  Plain launches on
+ * the stream: no sync, no allocation, no read-back.
+ * THE SIZE RULE, before any pointer: the forward's, and F <= 2^24 - 1, else LERF_EUNSUPPORTED.  Set strides as in the forward, the
+ * gradients' in doubles; 0 shares a read-only mesh operand.  Refused with LERF_EINVAL, launching and writing nothing: the forward's
+ * list, all three gradients NULL, grad_w without w, max_adders < 1, a null, misaligned or short workspace, a gradient or the workspace
+ * intersecting an input or each other over the whole batch, a gradient shared between sets. */
+size_t lerf_coords_trimesh_bwd_workspace_bytes(int64_t F, int64_t V, int64_t Va, int n_sets);      /* 0: sizes that are not valid */
+int lerf_coords_trimesh_bwd(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                            const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                            int oH, int oW, int i0, int j0, int max_span, int orient, const uint64_t* keys,
+                            const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w,
+                            void* workspace, size_t workspace_bytes, int max_adders, void* stream);
+int lerf_coords_trimesh_bwd_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                                 const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                                 int oH, int oW, int i0, int j0, int max_span, int orient, const uint64_t* keys,
+                                 const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w,
+                                 void* workspace, size_t workspace_bytes, int max_adders);
+int lerf_coords_trimesh_bwd_batched(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                                    const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                                    int oH, int oW, int i0, int j0, int max_span, int orient, const uint64_t* keys,
+                                    const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w,
+                                    void* workspace, size_t workspace_bytes, int max_adders,
+                                    int n_sets, int64_t pos_set_stride, int64_t attr_set_stride, int64_t faces_set_stride,
+                                    int64_t attr_faces_set_stride, int64_t depth_set_stride, int64_t w_set_stride, int64_t keys_set_stride,
+                                    int64_t grad_out_set_stride, int64_t grad_attr_set_stride, int64_t grad_pos_set_stride,
+                                    int64_t grad_w_set_stride, void* stream);
+int lerf_coords_trimesh_bwd_batched_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va,
+                                         const int32_t* faces, const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype,
+                                         int oH, int oW, int i0, int j0, int max_span, int orient, const uint64_t* keys,
+                                         const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w,
+                                         void* workspace, size_t workspace_bytes, int max_adders,
+                                         int n_sets, int64_t pos_set_stride, int64_t attr_set_stride, int64_t faces_set_stride,
+                                         int64_t attr_faces_set_stride, int64_t depth_set_stride, int64_t w_set_stride, int64_t keys_set_stride,
+                                         int64_t grad_out_set_stride, int64_t grad_attr_set_stride, int64_t grad_pos_set_stride,
+                                         int64_t grad_w_set_stride);
 int lerf_coords_compose_bwd_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW,
                                     const void* b, int b_dtype, int64_t b_row_stride,
                                     const double* grad_out, int oH, int oW, double* grad_a, double* grad_b,

@@ -72,6 +72,8 @@ EXPORTS = [
     "lerf_scan_exclusive_u32_block", "lerf_scan_exclusive_u32_workspace_bytes", "lerf_scan_exclusive_u32", "lerf_scan_exclusive_u32_host",
     "lerf_coords_trimesh_workspace_bytes", "lerf_coords_trimesh", "lerf_coords_trimesh_host", "lerf_coords_trimesh_batched",
     "lerf_coords_trimesh_batched_host",
+    "lerf_coords_trimesh_bwd_workspace_bytes", "lerf_coords_trimesh_bwd", "lerf_coords_trimesh_bwd_host", "lerf_coords_trimesh_bwd_batched",
+    "lerf_coords_trimesh_bwd_batched_host",
     "lerf_ubench_lds_gather",
 ]
 
@@ -388,6 +390,14 @@ def lib():
     L.lerf_coords_trimesh_workspace_bytes.argtypes = [C.c_int64, C.c_int]
     L.lerf_coords_trimesh.argtypes, L.lerf_coords_trimesh_host.argtypes = _trimesh + [C.c_void_p], _trimesh
     L.lerf_coords_trimesh_batched.argtypes, L.lerf_coords_trimesh_batched_host.argtypes = _trimesh_batched + [C.c_void_p], _trimesh_batched
+    _trimesh_bwd = ([C.c_void_p, C.c_int, C.c_int] * 2 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * 6 +
+                    [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_int])
+    _trimesh_bwd_batched = _trimesh_bwd + [C.c_int] + [C.c_int64] * 11
+    L.lerf_coords_trimesh_bwd_workspace_bytes.restype = C.c_size_t
+    L.lerf_coords_trimesh_bwd_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    L.lerf_coords_trimesh_bwd.argtypes, L.lerf_coords_trimesh_bwd_host.argtypes = _trimesh_bwd + [C.c_void_p], _trimesh_bwd
+    L.lerf_coords_trimesh_bwd_batched.argtypes = _trimesh_bwd_batched + [C.c_void_p]
+    L.lerf_coords_trimesh_bwd_batched_host.argtypes = _trimesh_bwd_batched
     L.lerf_ubench_lds_gather.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     for name in EXPORTS:          # AttributeError here = the .so does not match include/lerf_hip.h
         getattr(L, name)
@@ -937,6 +947,82 @@ def coords_trimesh_on(X, pos, attr, faces, out_hw, attr_faces, depth, w, dtype, 
     return res if len(res) > 1 else out
 
 
+def coords_trimesh_bwd_on(X, pos, attr, faces, out_hw, keys, grad_out, attr_faces, depth, w, origin, max_span, orient, need, grad_attr, grad_pos,
+                          grad_w, max_adders, raise_over):
+    """lerf_coords_trimesh_bwd over X: the mesh operands as coords_trimesh_on takes them, keys the forward's plane, grad_out float64 of the
+    map's shape -> (grad_attr, grad_pos, grad_w, most): float64 of attr's, pos's and w's shapes with a leading B where the call is a batch
+    (an operand shared by the batch gets one gradient PER SET), None where need[k] is false; most: the header's largest valence.
+    raise_over: a count above max_adders raises LerfError (the vertices over the cap hold NaN)."""
+    what = "lerf_coords_trimesh_bwd" + X.suffix
+    for a, name in ((pos, "pos"), (attr, "attr")):
+        if not X.is_array(a) or a.ndim not in (2, 3) or a.shape[-1] != 2 or min(a.shape) < 1 or not X.is_float(a):
+            raise ValueError("%s: %s must be %s [V, 2] or [B, V, 2], float32 or float64" % (what, name, X.noun))
+    p, a = X.contiguous(pos), X.contiguous(attr)
+    dev = X.device(p)
+    ohw = (int(out_hw[0]), int(out_hw[1]))
+    if not X.is_array(keys) or keys.dtype != X.key or keys.ndim not in (2, 3) or tuple(keys.shape[-2:]) != ohw or not X.is_contiguous(keys):
+        raise ValueError("%s: keys must be the forward's contiguous key plane [oH, oW] or [B, oH, oW]" % what)
+    B = _one_batch(what, ("pos", "attr", "keys"), p.shape[0] if p.ndim == 3 else 0, a.shape[0] if a.ndim == 3 else 0, keys.shape[0] if keys.ndim == 3 else 0)
+    if B and keys.ndim != 3:
+        raise ValueError("%s: a batch needs one key plane per set" % what)
+    V, Va = p.shape[-2], a.shape[-2]
+
+    def indices(f, name):
+        if not X.is_array(f) or f.dtype != X.i32 or f.ndim not in (2, 3) or f.shape[-1] != 3 or min(f.shape) < 1:
+            raise ValueError("%s: %s must be %s [F, 3] or [B, F, 3], int32" % (what, name, X.noun))
+        if f.ndim == 3 and f.shape[0] != B:
+            raise ValueError("%s: %s holds %d sets of faces for a batch of %d" % (what, name, f.shape[0], B))
+        return X.contiguous(f)
+
+    fc = indices(faces, "faces")
+    F = fc.shape[-2]
+    af = None if attr_faces is None else indices(attr_faces, "attr_faces")
+    if af is not None and af.shape[-2] != F:
+        raise ValueError("%s: attr_faces must hold one triple per face" % what)
+
+    def per_vertex(v, name, dtypes):
+        if v is None:
+            return None
+        if not X.is_array(v) or v.dtype not in dtypes or v.ndim not in (1, 2) or v.shape[-1] != V or (v.ndim == 2 and v.shape[0] != B):
+            raise ValueError("%s: %s must be %s [V] or [B, V], float32%s" % (what, name, X.noun, " or float64" if len(dtypes) > 1 else ""))
+        return X.contiguous(v)
+
+    d, wv = per_vertex(depth, "depth", (X.f32,)), per_vertex(w, "w", (X.f32, X.f64))
+    need = tuple(bool(n) for n in need)
+    if len(need) != 3 or not any(need):
+        raise ValueError("%s: need = (attr, pos, w), at least one of them" % what)
+    if need[2] and wv is None:
+        raise ValueError("%s: a gradient for w needs w" % what)
+    if not 0 <= int(max_span) <= TRIMESH_MAX_SPAN or not -1 <= int(orient) <= 1:
+        raise ValueError("%s: max_span is 0 (no tear rule) or 1..%d, orient -1, 0 or 1" % (what, TRIMESH_MAX_SPAN))
+    max_adders = int(max_adders)
+    if max_adders < 1:
+        raise ValueError("%s: max_adders must be at least 1" % what)
+    n_sets = max(B, 1)
+    lead = (B,) if B else ()
+    nbytes = int(lib().lerf_coords_trimesh_bwd_workspace_bytes(F, V, Va, n_sets))
+    if not nbytes or trimesh_max_items(F, n_sets, ohw, int(max_span)) > 0xffffffff:
+        raise LerfError("%s: %d faces x %d sets into %d x %d are beyond the size rule (F <= 2^24 - 1 and the forward's)" % (what, F, n_sets, ohw[0], ohw[1]))
+    g = X.grad(grad_out, lead + ohw + (2,), dev, what + ": grad_out")
+    ga = X.grad(grad_attr, lead + (Va, 2), dev, what + ": grad_attr") if need[0] else None
+    gp = X.grad(grad_pos, lead + (V, 2), dev, what + ": grad_pos") if need[1] else None
+    gw = X.grad(grad_w, lead + (V,), dev, what + ": grad_w") if need[2] else None
+    X.one_device(what, ("pos", "attr", "faces", "attr_faces", "depth", "w", "keys"), p, a, fc, af, d, wv, keys)
+    ws = X.scratch(nbytes, dev)
+    per = lambda t, base, n: 0 if t is None or t.ndim == base or B < 2 else n          # the set stride of a dense operand: 0 shares it
+    own = lambda t, n: 0 if t is None or B < 2 else n
+    X.run("lerf_coords_trimesh_bwd", B, p, (X.ptr(p), X.code(p), V, X.ptr(a), X.code(a), Va, X.ptr(fc), X.ptr(af), F, X.ptr(d), X.ptr(wv),
+                                            LERF_F32 if wv is None else X.code(wv), ohw[0], ohw[1], int(origin[0]), int(origin[1]), int(max_span),
+                                            int(orient), X.ptr(keys), X.ptr(g), X.ptr(ga), X.ptr(gp), X.ptr(gw), X.ptr(ws), nbytes, max_adders),
+          (per(p, 2, 2 * V), per(a, 2, 2 * Va), per(fc, 2, 3 * F), per(af, 2, 3 * F), per(d, 1, V), per(wv, 1, V), own(keys, ohw[0] * ohw[1]),
+           own(g, 2 * ohw[0] * ohw[1]), own(ga, 2 * Va), own(gp, 2 * V), own(gw, V)))
+    most = X.max_count(ws)
+    if raise_over and most > max_adders:
+        raise LerfError("%s: %d face corners add into one vertex, more than max_adders = %d (that vertex holds NaN); raise max_adders"
+                        % (what, most, max_adders))
+    return ga, gp, gw, most
+
+
 def _coords_bwd_operands(X, what, first, second, names, grad_out):
     """the two maps (or batches) of an adjoint and its upstream gradient, which has the second one's shape"""
     a, sa, ta, Ba = X.batch(first, names[0])
@@ -1175,6 +1261,19 @@ def coords_trimesh_host(pos, attr, faces, out_hw, attr_faces=None, depth=None, w
     batched alike or shared) -> [B, oH, oW, 2] by one call of lerf_coords_trimesh_batched_host."""
     return coords_trimesh_on(_HOST, pos, attr, faces, out_hw, attr_faces, depth, w, dtype, out, origin, max_span, orient, keys, return_keys,
                              return_depth)
+
+
+def coords_trimesh_bwd_host(pos, attr, faces, out_hw, keys, grad_out, attr_faces=None, depth=None, w=None, origin=(0, 0), max_span=0, orient=0,
+                            need=(True, True, False), grad_attr=None, grad_pos=None, grad_w=None, max_adders=4096, return_most=False):
+    """lerf_coords_trimesh_bwd_host: the adjoint of coords_trimesh_host at fixed visibility by the kernel's own statement -- a
+    256-slot array per face, the same tree, the same sorted lists per vertex: bit-equal to ops.coords_trimesh_bwd.  keys: the uint64 plane
+    of the forward (return_keys=True); grad_out float64 of the map's shape; need = (attr, pos, w).  -> (grad_attr, grad_pos, grad_w)
+    float64, ACCUMULATED INTO the ones given (None: zeroed ones), None where not needed; with return_most also the largest number of
+    drawn face corners at one vertex.  A vertex above max_adders holds NaN in every component; nothing is raised here.  A batch:
+    [B, ...] operands and keys [B, oH, oW]; every gradient then has the leading B, also for an operand the batch shares."""
+    ga, gp, gw, most = coords_trimesh_bwd_on(_HOST, pos, attr, faces, out_hw, keys, grad_out, attr_faces, depth, w, origin, max_span, orient, need,
+                                             grad_attr, grad_pos, grad_w, max_adders, False)
+    return (ga, gp, gw, most) if return_most else (ga, gp, gw)
 
 
 def coords_compose_bwd_host(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True)):

@@ -52,7 +52,9 @@ from_triangles builds a map from an irregular TRIANGLE MESH (lerf_coords_trimesh
 frame, the source position every vertex shows, faces by index, optionally per-corner attributes (attr_faces), a per-vertex depth
 (the nearest face wins) and a per-vertex w (perspective-correct interpolation) -- landmark-driven piecewise-affine warps, UV-mapped
 meshes, any warp whose control points are not a grid.  invert_raster's watertight inside test and integer-min key over faces of any
-size, bit-equal to its host twin; pixels no face covers stay NaN.  grid_faces is invert_raster's own triangulation.  No autograd.
+size, bit-equal to its host twin; pixels no face covers stay NaN.  grid_faces is invert_raster's own triangulation.
+from_triangles_torch is the differentiable twin (lerf_coords_trimesh_bwd): attr, pos and w receive gradients at fixed
+visibility, in a fixed order -- bit-equal from run to run.
 """
 from __future__ import annotations
 
@@ -574,8 +576,9 @@ def from_triangles(pos, attr, faces, out_hw, attr_faces=None, depth=None, w=None
     scan, one wave per (face, tile), resolve; no sync); mixed operands are refused.  dtype: the map's, default attr's.  pos (and / or
     attr) [B, V, 2] give [B, oH, oW, 2] in ONE batched call; faces, attr_faces, depth and w are then batched alike or shared.
     return_depth: also the winning depth, float32 [oH, oW], NaN in holes (needs depth); return_faces: also the winning face,
-    int64 [oH, oW], -1 in holes -> map, or (map[, depth][, faces]).  Bit-equal from run to run.  No autograd: an operand that requires
-    grad (with grad mode on) is refused."""
+    int64 [oH, oW], -1 in holes -> map, or (map[, depth][, faces]).  Bit-equal from run to run.  No autograd here: an operand that
+    requires grad (with grad mode on) is refused -- from_triangles_torch is the differentiable twin (gradients to attr, pos and w at
+    fixed visibility)."""
     given = [t for t in (pos, attr, faces, attr_faces, depth, w) if t is not None]
     dev = [bool(getattr(t, "is_cuda", False)) for t in given]
     if any(d != dev[0] for d in dev):
@@ -1273,6 +1276,113 @@ def _splat_fn():
 
         _SPLAT_FN = _SplatFn
     return _SPLAT_FN
+
+
+_TRIANGLES_FN = None
+
+
+def _triangles_fn():
+    global _TRIANGLES_FN
+    if _TRIANGLES_FN is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+        from . import ops
+
+        class _TrianglesFn(torch.autograd.Function):
+            """map (, depth_out), keys = ops.coords_trimesh(...); backward: ops.coords_trimesh_bwd at the saved keys in float64, one call
+            for the whole batch; an operand the batch shares gains the sum of its per-set gradients; each gradient cast to its
+            operand's dtype"""
+
+            @staticmethod
+            def forward(ctx, pos, attr, w, faces, attr_faces, depth, hw, tdt, max_span, orient, want_depth, max_adders):
+                p, a = pos.detach().contiguous(), attr.detach().contiguous()
+                wv = None if w is None else w.detach().contiguous()
+                res = ops.coords_trimesh(p, a, faces, hw, attr_faces=attr_faces, depth=depth, w=wv, dtype=tdt, max_span=max_span, orient=orient,
+                                         return_keys=True, return_depth=want_depth)
+                out, keys = res[0], res[1]
+                ctx.save_for_backward(p, a, keys, *(() if wv is None else (wv,)))
+                ctx.mesh = (faces, attr_faces, depth, hw, max_span, orient, max_adders)
+                ctx.dtypes = (pos.dtype, attr.dtype, None if w is None else w.dtype)
+                ctx.mark_non_differentiable(keys)
+                if want_depth:
+                    ctx.mark_non_differentiable(res[2])
+                    return out, keys, res[2]
+                return out, keys
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad, *unused):
+                p, a, keys = ctx.saved_tensors[:3]
+                wv = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+                faces, attr_faces, depth, hw, max_span, orient, max_adders = ctx.mesh
+                need = (ctx.needs_input_grad[1], ctx.needs_input_grad[0], wv is not None and ctx.needs_input_grad[2])
+                none = (None,) * 12
+                if not any(need):
+                    return none
+                ga, gp, gw = ops.coords_trimesh_bwd(p, a, faces, hw, keys, grad.detach().to(torch.float64).contiguous(), attr_faces=attr_faces,
+                                                    depth=depth, w=wv, max_span=max_span, orient=orient, need=need, max_adders=max_adders)
+                batch = keys.dim() == 3
+
+                def fit(g, operand, base, dt):
+                    if g is None:
+                        return None
+                    if batch and operand.dim() == base:          # shared across the batch: the per-set gradients summed, set 0 first
+                        total = g[0]
+                        for s in range(1, g.shape[0]):
+                            total = total + g[s]
+                        g = total
+                    return g.to(dt)
+
+                return (fit(gp, p, 2, ctx.dtypes[0]), fit(ga, a, 2, ctx.dtypes[1]), fit(gw, wv, 1, ctx.dtypes[2])) + none[3:]
+
+        _TRIANGLES_FN = _TrianglesFn
+    return _TRIANGLES_FN
+
+
+def from_triangles_torch(pos, attr, faces, out_hw, attr_faces=None, depth=None, w=None, max_span=0, orient=0, dtype=None, return_depth=False,
+                         return_faces=False, max_adders=4096):
+    """from_triangles on the operands' device, DIFFERENTIABLE (lerf_coords_trimesh_bwd): pos [V, 2], attr [Va, 2] and
+    w [V] (or None) are float32 / float64 DEVICE tensors, faces / attr_faces integer device tensors, depth [V] a device tensor; the
+    rest as from_triangles -> what from_triangles returns, bit for bit.  pos, attr and w each receive a gradient when they require
+    one: landmark positions fitted by a photometric loss, refined UVs, the vertices of a projected mesh --
+
+        remap(img, from_triangles_torch(pos, attr, faces, hw))          # through a *Remap2dTorch twin after enable_backward()
+
+    VISIBILITY IS HELD FIXED: every pixel belongs to the face that won it in the forward (the key plane, saved for the backward);
+    coverage, edges and the depth test are piecewise constant and give no gradient, as in any rasterise-then-interpolate renderer.
+    So depth gets no gradient (a depth that requires grad is refused), the depth and faces results are not differentiable, and a
+    NaN the loss puts at a hole reaches nothing.  The backward is a face pass (one workgroup per face reduces its pixels by a fixed
+    tree) and a vertex pass (one writer per vertex adds its faces in ascending (face, corner) order): bit-equal from run to run.  It
+    ends with one 4-byte copy to the host and a synchronisation, and raises LerfError when more than max_adders drawn face corners
+    meet in one vertex.  pos / attr [B, V, 2] run one call forward and one backward; an operand without the B axis is shared and
+    gains the sum over the batch.  Gradients are computed in float64 and cast to each operand's dtype.  Once differentiable."""
+    import torch
+    for t, name in ((pos, "pos"), (attr, "attr"), (w, "w")):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.float32, torch.float64)):
+            raise ValueError("from_triangles_torch: %s must be a float32 or float64 device tensor" % name)
+    for t, name in ((faces, "faces"), (attr_faces, "attr_faces"), (depth, "depth")):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda):
+            raise ValueError("from_triangles_torch: %s must be a device tensor" % name)
+    if any(t is not None and t.device != pos.device for t in (attr, faces, attr_faces, depth, w)):
+        raise ValueError("from_triangles_torch: the operands live on different devices")
+    if depth is not None and depth.requires_grad and torch.is_grad_enabled():
+        raise ValueError("from_triangles_torch: depth gets no gradient -- visibility is held fixed, the depth test is piecewise constant; "
+                         "pass depth.detach()")
+    H, W = int(out_hw[0]), int(out_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("out_hw must be positive")
+    if return_depth and depth is None:
+        raise ValueError("from_triangles_torch: return_depth needs depth")
+    fc = _int32_indices(faces.detach(), torch.int32, lambda x, dt: x.to(dt).contiguous())
+    af = None if attr_faces is None else _int32_indices(attr_faces.detach(), torch.int32, lambda x, dt: x.to(dt).contiguous())
+    d = None if depth is None else depth.detach().to(torch.float32).contiguous()
+    tdt = None if dtype is None else (dtype if isinstance(dtype, torch.dtype) else getattr(torch, _np_dtype(dtype).name))
+    res = _triangles_fn().apply(pos, attr, w, fc, af, d, (H, W), tdt, int(max_span), int(orient), bool(return_depth), int(max_adders))
+    m, k = res[0], res[1]
+    if not (return_faces or return_depth):
+        return m
+    low = torch.where(k == -1, k, k & 0xffffffff)
+    return (m,) + ((res[2],) if return_depth else ()) + ((low,) if return_faces else ())
 
 
 def splat_torch(src, map, out_hw, weight=None, mode="sum", eps=1e-7, return_norm=False, deterministic=None, max_adders=4096):

@@ -30,7 +30,9 @@
 // The triangle-mesh rasteriser (lerf_coords_trimesh) draws an INDEXED mesh with the same per-pixel functions in five
 // passes: KeyFillOp, TriCountOp and TriResolveOp are per-entry functors under the two runners; the raster pass is trimesh_raster_kernel,
 // one wave per (face, 4 x 16 pixel tile) item of a scanned item list (TriRasterOnDevice), or the plain loop over faces and their boxes
-// (TriRasterOnHost).  Its notes are with it, after the ordered scatter's scan.
+// (TriRasterOnHost).  Its notes are with it, after the ordered scatter's scan.  Its adjoint (lerf_coords_trimesh_bwd) is a
+// face pass of its own shape (trimesh_bwd_face_kernel: one workgroup per face, a fixed reduction tree) and the ordered scatter's four
+// passes over TriVertexOp, whose entries are the faces (TriBwdOnDevice / TriBwdOnHost, after the ordered runners).
 //
 // Kernels of their own shape (unchanged by the above):
 //   coords_mesh_bwd_{rows,cols}_kernel      the adjoint of the mesh upsample, map = Wr . ctrl . Wc^T  =>  grad_ctrl = Wr^T . grad_map . Wc,
@@ -1055,6 +1057,262 @@ struct OrderedOnHost {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ the adjoint of the triangle mesh
+// Gradients of the resolve's attribute with respect to attr, pos and w at FIXED VISIBILITY (the keys of the forward), in two passes whose
+// sums have ONE order, the statement's (tri_bwd_thread, tri_face_terms: the top of lerf_coords_models.h), on the device and in the host twin:
+//   face pass    trimesh_bwd_face_kernel: one workgroup of kTriBwdWaves = 4 waves per (set, face), grid (F, n_sets).  The set-up and the
+//                clipped box are the forward's (TriMesh::read, tri_setup, tri_tiles); a skipped face exits at once.  Thread 64 r + l owns
+//                lane pixel l of the item tiles r, r + 4, ...; 6 (15 with w) running sums in registers, one 8-byte load of the key per
+//                pixel and one 16-byte load of grad_out for a pixel the face won only; a butterfly over the lanes per sum, the four waves
+//                through LDS as ((p0 + p1) + p2) + p3, and thread 0 stores the face's 15 terms at terms[set][f][15].
+//   vertex pass  the ordered scatter's four passes (count, scan, fill, sort and sum) over TriVertexOp, whose ENTRIES are the faces (entry grid
+//                1 x F) and whose TARGETS are the vertices: a drawn face hands its three corners' terms to the combiner, so vertex v's one
+//                writer adds them in ascending (face, corner) order into what the gradient holds.  Two target spaces, one after the other over
+//                the same cursor and list: the vertices of `faces` (grad_pos and grad_w from one segment) and those of attr_faces (grad_attr);
+//                a face that names one attribute twice is listed twice and, by the duplicate skip, runs once and delivers both corners.
+// WORKSPACE, 8-byte aligned: header [4] uint32 (word 1 the largest valence of either space), terms [n_sets][F][15] float64, cursor
+// [n_sets][max(V, Va)] uint32, list [n_sets][3 F] uint32, scan partials [n_sets][scan_partials(max(V, Va))].
+// Addresses: the face pass indexes keys and grad_out inside the face's clipped box, which tri_axis puts inside [oH][oW] in floating point
+// before the conversion to int, and terms at (set, f) with f < F; TriVertexOp hands out a corner's index only after tri_index_ok compared it
+// against V and Va, so cursor and the gradients are indexed inside [V] / [Va]; a face lists at most 3 ids, the list holds 3 F per set.
+struct KeepVertexAt {
+    double *g2, *g1;      // [n][2] and [n], either may be null
+    int64_t q;
+    LERF_HD void operator()(int, int c, double dr, double dc) const {
+#pragma clang fp contract(off)
+        if ((int64_t)c != q || !g2) return;
+        double* p = g2 + 2 * q;
+        p[0] = p[0] + dr;
+        p[1] = p[1] + dc;
+    }
+    LERF_HD void operator()(int, int64_t at, double v) const {
+#pragma clang fp contract(off)
+        if (at != q || !g1) return;
+        g1[q] = g1[q] + v;
+    }
+    LERF_HD void poison() const {
+        if (g2) g2[2 * q] = g2[2 * q + 1] = __builtin_nan("");
+        if (g1) g1[q] = __builtin_nan("");
+    }
+};
+
+// SPACE 0: targets = the vertices of `faces`, g2 = grad_pos, g1 = grad_w;  SPACE 1: targets = the vertices of attr_faces, g2 = grad_attr
+template <typename TP, int SPACE>
+struct TriVertexOp {
+    TriMesh<TP> mesh;
+    const double* terms;      // [n_sets][F][15]; null: the taps alone (count and fill)
+    double *g2, *g1;
+    int64_t g2_set, g1_set;
+    int n;                    // V or Va
+    template <typename ADD>
+    LERF_HD void apply(int, int f, int s, ADD add) const {
+        TriFace t;
+        int32_t ai[3];
+        double wv[3];
+        RasterBox box;
+        if (!mesh.read(s, f, &t, ai, wv) ||
+            !tri_setup(t, mesh.depth != nullptr, mesh.w != nullptr, wv[0], wv[1], wv[2], mesh.orient, mesh.max_span, mesh.i0, mesh.j0, mesh.oH, mesh.oW, &box))
+            return;
+        const int32_t idx[3] = {SPACE ? ai[0] : t.ia, SPACE ? ai[1] : t.ib, SPACE ? ai[2] : t.ic};
+        const double* T = terms ? terms + ((int64_t)s * mesh.F + f) * kTriBwdTerms : nullptr;
+        for (int k = 0; k < 3; ++k) {
+            const int o = 5 * k + (SPACE ? 0 : 2);
+            add(0, (int)idx[k], T ? T[o] : 0.0, T ? T[o + 1] : 0.0);
+            if (SPACE == 0 && T && g1) add(1, (int64_t)idx[k], T[5 * k + 4]);      // plane 1: neither counted nor listed (CountAt, FillAt)
+        }
+    }
+    LERF_HD int target_h() const { return 1; }
+    LERF_HD int target_w() const { return n; }
+    LERF_HD TriVertexOp scatter_only() const { return *this; }
+    LERF_HD TriVertexOp taps_only() const { TriVertexOp o = *this; o.terms = nullptr; return o; }
+    LERF_HD KeepVertexAt keep_at(int s, int64_t q) const {
+        return {g2 ? g2 + set_offset(s, g2_set) : nullptr, g1 ? g1 + set_offset(s, g1_set) : nullptr, q};
+    }
+};
+
+struct TriBwdLayout {
+    int64_t n_max, n_slots, partials;
+    uint32_t *header, *cursor, *list, *scan;
+    double* terms;
+    TriBwdLayout(void* ws, int64_t F, int64_t V, int64_t Va, int sets) : n_max(V > Va ? V : Va), n_slots(3 * F), partials(scan_partials(V > Va ? V : Va)) {
+        header = (uint32_t*)ws;
+        terms = (double*)(header + kOrderedHeaderWords);
+        cursor = (uint32_t*)(terms + (int64_t)sets * F * kTriBwdTerms);
+        list = cursor + (int64_t)sets * n_max;
+        scan = list + (int64_t)sets * n_slots;
+    }
+    static size_t bytes(int64_t F, int64_t V, int64_t Va, int sets) {
+        const int64_t n = V > Va ? V : Va;
+        return sizeof(uint32_t) * kOrderedHeaderWords + sizeof(double) * (size_t)sets * (size_t)F * kTriBwdTerms +
+               sizeof(uint32_t) * (size_t)sets * ((size_t)n + 3 * (size_t)F + (size_t)scan_partials(n));
+    }
+};
+
+template <typename TP, typename TA, bool HAS_W>
+__global__ void __launch_bounds__(64 * kTriBwdWaves)
+trimesh_bwd_face_kernel(const TriMesh<TP> mesh, const TA* __restrict__ attr, int64_t attr_set, const uint64_t* __restrict__ keys, int64_t keys_set,
+                        const double* __restrict__ gout, int64_t gout_set, double* __restrict__ terms) {
+#pragma clang fp contract(off)
+    constexpr int NS = HAS_W ? kTriBwdTerms : 6;
+    __shared__ double wsum[kTriBwdWaves][NS];
+    const int f = (int)blockIdx.x, s = (int)blockIdx.y;
+    const int r = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64)), l = threadIdx.x & 63;
+    TriFace t;
+    int32_t ai[3];
+    double wv[3];
+    RasterBox box;
+    if (!mesh.read(s, f, &t, ai, wv) ||
+        !tri_setup(t, mesh.depth != nullptr, HAS_W, wv[0], wv[1], wv[2], mesh.orient, mesh.max_span, mesh.i0, mesh.j0, mesh.oH, mesh.oW, &box))
+        return;                                                          // the whole workgroup: f and s are the block's
+    const TA* a = attr + set_offset(s, attr_set);
+    const Point aA = load_entry(a, 0, 0, ai[0]), aB = load_entry(a, 0, 0, ai[1]), aC = load_entry(a, 0, 0, ai[2]);
+    const TriGrads G = tri_grads(t, box.area2);
+    double acc[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+    tri_bwd_thread<HAS_W>(t, box, G, aA, aB, aC, wv[0], wv[1], wv[2], (uint32_t)f, mesh.i0, mesh.j0, mesh.oW, keys + set_offset(s, keys_set),
+                          gout + set_offset(s, gout_set), r, l, acc);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) acc[k] = acc[k] + __shfl_xor(acc[k], m, 64);
+        if (l == 0) wsum[r][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double S[kTriBwdTerms], T[kTriBwdTerms];
+#pragma unroll
+    for (int k = 0; k < kTriBwdTerms; ++k) S[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) S[HAS_W ? k : 5 * (k / 2) + (k & 1)] = ((wsum[0][k] + wsum[1][k]) + wsum[2][k]) + wsum[3][k];
+    tri_face_terms(G, aA, aB, aC, HAS_W, S, T);
+    double* dst = terms + ((int64_t)s * mesh.F + f) * kTriBwdTerms;
+#pragma unroll
+    for (int k = 0; k < kTriBwdTerms; ++k) dst[k] = T[k];
+}
+
+// the face pass of the host twin: the 256 slots of every face one after the other, the same tree
+template <typename TP, typename TA, bool HAS_W>
+void trimesh_bwd_faces_host(const TriMesh<TP>& mesh, const TA* attr, int64_t attr_set, const uint64_t* keys, int64_t keys_set, const double* gout,
+                            int64_t gout_set, int n_sets, double* terms) {
+#pragma clang fp contract(off)
+    constexpr int NS = HAS_W ? kTriBwdTerms : 6, NT = 64 * kTriBwdWaves;
+    std::vector<double> part((size_t)NT * NS);
+    for (int s = 0; s < n_sets; ++s)
+        for (int f = 0; f < mesh.F; ++f) {
+            TriFace t;
+            int32_t ai[3];
+            double wv[3];
+            RasterBox box;
+            if (!mesh.read(s, f, &t, ai, wv) ||
+                !tri_setup(t, mesh.depth != nullptr, HAS_W, wv[0], wv[1], wv[2], mesh.orient, mesh.max_span, mesh.i0, mesh.j0, mesh.oH, mesh.oW, &box))
+                continue;
+            const TA* a = attr + set_offset(s, attr_set);
+            const Point aA = load_entry(a, 0, 0, ai[0]), aB = load_entry(a, 0, 0, ai[1]), aC = load_entry(a, 0, 0, ai[2]);
+            const TriGrads G = tri_grads(t, box.area2);
+            for (int th = 0; th < NT; ++th) {
+                double* acc = &part[(size_t)th * NS];
+                for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+                tri_bwd_thread<HAS_W>(t, box, G, aA, aB, aC, wv[0], wv[1], wv[2], (uint32_t)f, mesh.i0, mesh.j0, mesh.oW, keys + set_offset(s, keys_set),
+                                      gout + set_offset(s, gout_set), th / 64, th % 64, acc);
+            }
+            double S[kTriBwdTerms], T[kTriBwdTerms];
+            for (int k = 0; k < kTriBwdTerms; ++k) S[k] = 0.0;
+            for (int k = 0; k < NS; ++k) {
+                double p[kTriBwdWaves];
+                for (int r = 0; r < kTriBwdWaves; ++r) {
+                    double x[64], y[64];
+                    for (int l = 0; l < 64; ++l) x[l] = part[(size_t)(64 * r + l) * NS + k];
+                    for (int m = 32; m > 0; m >>= 1) {
+                        for (int l = 0; l < 64; ++l) y[l] = x[l] + x[l ^ m];
+                        for (int l = 0; l < 64; ++l) x[l] = y[l];
+                    }
+                    p[r] = x[0];
+                }
+                S[HAS_W ? k : 5 * (k / 2) + (k & 1)] = ((p[0] + p[1]) + p[2]) + p[3];
+            }
+            tri_face_terms(G, aA, aB, aC, HAS_W, S, T);
+            double* dst = terms + ((int64_t)s * mesh.F + f) * kTriBwdTerms;
+            for (int k = 0; k < kTriBwdTerms; ++k) dst[k] = T[k];
+        }
+}
+
+// the two runners of the adjoint: the face pass, then the vertex pass per target space that is wanted
+struct TriBwdOnDevice {
+    hipStream_t stream;
+    template <typename OP>
+    int vertices(const OP& op, const TriBwdLayout& L, int F, int sets, int max_adders) const {
+        const int64_t n = op.n;
+        if (hipMemsetAsync(L.cursor, 0, sizeof(uint32_t) * (size_t)sets * (size_t)n, stream) != hipSuccess) return LERF_ELAUNCH;
+        const OnDevice run{stream};
+        int rc = run(CountPass<OP>{op.taps_only(), L.cursor, n}, 1, F, sets);
+        if (rc != LERF_OK) return rc;
+        clear_stale_error();
+        scan_exclusive_u32(stream, L.cursor, n, sets, n, L.scan, L.header + kOrderedMaxWord);
+        rc = launch_status();
+        if (rc != LERF_OK) return rc;
+        rc = run(FillPass<OP>{op.taps_only(), L.cursor, L.list, n, L.n_slots, F}, 1, F, sets);
+        if (rc != LERF_OK) return rc;
+        clear_stale_error();
+        hipLaunchKernelGGL(ordered_sum_kernel<OP>, dim3((unsigned)((n + 255) / 256), sets), dim3(256), 0, stream, op.scatter_only(), n, L.cursor, L.list,
+                           L.n_slots, F, (uint32_t)max_adders);
+        return launch_status();
+    }
+    template <typename TP, typename TA>
+    int operator()(const TriMesh<TP>& mesh, const TA* attr, int64_t attr_set, const uint64_t* keys, int64_t keys_set, const double* gout,
+                   int64_t gout_set, int n_sets, double* gattr, int64_t gattr_set, double* gpos, int64_t gpos_set, double* gw, int64_t gw_set, void* ws,
+                   int max_adders) const {
+        const TriBwdLayout L(ws, mesh.F, mesh.V, mesh.Va, n_sets);
+        clear_stale_error();
+        if (hipMemsetAsync(L.header, 0, sizeof(uint32_t) * kOrderedHeaderWords, stream) != hipSuccess) return LERF_ELAUNCH;
+        const dim3 grid((unsigned)mesh.F, (unsigned)n_sets), block(64 * kTriBwdWaves);
+        if (mesh.w)
+            hipLaunchKernelGGL((trimesh_bwd_face_kernel<TP, TA, true>), grid, block, 0, stream, mesh, attr, attr_set, keys, keys_set, gout, gout_set, L.terms);
+        else
+            hipLaunchKernelGGL((trimesh_bwd_face_kernel<TP, TA, false>), grid, block, 0, stream, mesh, attr, attr_set, keys, keys_set, gout, gout_set, L.terms);
+        int rc = launch_status();
+        if (rc != LERF_OK) return rc;
+        if (gpos || gw) rc = vertices(TriVertexOp<TP, 0>{mesh, L.terms, gpos, gw, gpos_set, gw_set, mesh.V}, L, mesh.F, n_sets, max_adders);
+        if (rc != LERF_OK) return rc;
+        if (gattr) rc = vertices(TriVertexOp<TP, 1>{mesh, L.terms, gattr, nullptr, gattr_set, 0, mesh.Va}, L, mesh.F, n_sets, max_adders);
+        return rc;
+    }
+};
+
+// the same passes serially; the fill walks the faces in DESCENDING order, so the sort, the duplicate skip and the cap run as on the device
+struct TriBwdOnHost {
+    template <typename OP>
+    int vertices(const OP& op, const TriBwdLayout& L, int F, int sets, int max_adders) const {
+        const int64_t n = op.n;
+        for (int64_t k = 0; k < (int64_t)sets * n; ++k) L.cursor[k] = 0;
+        OnHost{}(CountPass<OP>{op.taps_only(), L.cursor, n}, 1, F, sets);
+        for (int s = 0; s < sets; ++s) {
+            uint32_t* c = L.cursor + (int64_t)s * n;
+            for (int64_t q = 0; q < n; ++q) L.header[kOrderedMaxWord] = c[q] > L.header[kOrderedMaxWord] ? c[q] : L.header[kOrderedMaxWord];
+            scan_exclusive_u32_host(c, n);
+        }
+        const FillPass<OP> fill{op.taps_only(), L.cursor, L.list, n, L.n_slots, F};
+        for (int s = 0; s < sets; ++s)
+            for (int f = F - 1; f >= 0; --f) fill(0, f, s);
+        const OP scatter = op.scatter_only();
+        for (int s = 0; s < sets; ++s)
+            for (int64_t q = 0; q < n; ++q) ordered_sum_target(scatter, s, q, L.cursor + (int64_t)s * n, L.list + (int64_t)s * L.n_slots, F, (uint32_t)max_adders);
+        return LERF_OK;
+    }
+    template <typename TP, typename TA>
+    int operator()(const TriMesh<TP>& mesh, const TA* attr, int64_t attr_set, const uint64_t* keys, int64_t keys_set, const double* gout,
+                   int64_t gout_set, int n_sets, double* gattr, int64_t gattr_set, double* gpos, int64_t gpos_set, double* gw, int64_t gw_set, void* ws,
+                   int max_adders) const {
+        const TriBwdLayout L(ws, mesh.F, mesh.V, mesh.Va, n_sets);
+        for (int k = 0; k < kOrderedHeaderWords; ++k) L.header[k] = 0;
+        if (mesh.w) trimesh_bwd_faces_host<TP, TA, true>(mesh, attr, attr_set, keys, keys_set, gout, gout_set, n_sets, L.terms);
+        else trimesh_bwd_faces_host<TP, TA, false>(mesh, attr, attr_set, keys, keys_set, gout, gout_set, n_sets, L.terms);
+        if (gpos || gw) vertices(TriVertexOp<TP, 0>{mesh, L.terms, gpos, gw, gpos_set, gw_set, mesh.V}, L, mesh.F, n_sets, max_adders);
+        if (gattr) vertices(TriVertexOp<TP, 1>{mesh, L.terms, gattr, nullptr, gattr_set, 0, mesh.Va}, L, mesh.F, n_sets, max_adders);
+        return LERF_OK;
+    }
+};
+
 // pass 1 of the adjoint: grid (ceil(oW / 64), gh, sets), block (64, 4); set s reads gmap + s * gmap_set (in entries) and owns tmp [s][gh][oW]
 template <int INTERP>
 __global__ void __launch_bounds__(CB_COLS * CB_ROWS)
@@ -1540,6 +1798,53 @@ int trimesh(RUN run, RASTER raster, const void* pos, int pos_dtype, int V, const
     });
 }
 
+// The adjoint of the triangle mesh.  THE SIZE RULE, from sizes alone and before any pointer: the forward's (the item tiles
+// of a face are counted in uint32), and F <= 2^24 - 1: the face pass is one workgroup of 256 threads a face, and a face lists three ids.
+constexpr int64_t kTriBwdMaxFaces = 0xffffff;
+
+inline size_t tri_bwd_workspace_bytes(int64_t F, int64_t V, int64_t Va, int n_sets) {
+    if (F < 1 || F > kTriBwdMaxFaces || V < 1 || V > 0x7fffffffLL || Va < 1 || Va > 0x7fffffffLL || n_sets < 1 || n_sets > 65535) return 0;
+    return TriBwdLayout::bytes(F, V, Va, n_sets);
+}
+
+// the face pass, then the vertex pass per wanted target space, in stream order (the host: the same loops); no sync, no allocation, no read-back
+template <typename RUN>
+int trimesh_bwd(RUN run, const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces, const int32_t* attr_faces,
+                int F, const float* depth, const void* w, int w_dtype, int oH, int oW, int i0, int j0, int max_span, int orient, const uint64_t* keys,
+                const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w, void* workspace, size_t workspace_bytes, int max_adders,
+                int n_sets, int64_t pos_set, int64_t attr_set, int64_t faces_set, int64_t afaces_set, int64_t depth_set, int64_t w_set, int64_t keys_set,
+                int64_t gout_set, int64_t gattr_set, int64_t gpos_set, int64_t gw_set) {
+    enum { POS, ATTR, FACES, AFACES, DEPTH, W, KEYS, GOUT, GATTR, GPOS, GW, WS };
+    const bool sizes = V >= 1 && Va >= 1 && F >= 1 && oH >= 1 && oW >= 1 && n_sets >= 1 && n_sets <= 65535 && max_span >= 0 && max_span <= kMaxTriSpan;
+    if (sizes && (!tri_max_items(F, n_sets, oH, oW, max_span) || F > kTriBwdMaxFaces)) return LERF_EUNSUPPORTED;
+    const size_t need = sizes ? tri_bwd_workspace_bytes(F, V, Va, n_sets) : 0;
+    const Operand ws{workspace, 1, 8, (int64_t)need, 0, false, true, false, true, true};
+    const int rc = check_call(n_sets,
+                              {dense_operand(pos, pos_dtype, V, 1, pos_set, SHARE), dense_operand(attr, attr_dtype, Va, 1, attr_set, SHARE),
+                               plane_operand(faces, sizeof(int32_t), F, 3, faces_set, SHARE),
+                               plane_operand(attr_faces, sizeof(int32_t), F, 3, afaces_set, SHARE | OPTIONAL),
+                               plane_operand(depth, sizeof(float), V, 1, depth_set, SHARE | OPTIONAL),
+                               plane_operand(w, w_dtype == LERF_F64 ? sizeof(double) : sizeof(float), V, 1, w_set, SHARE | OPTIONAL),
+                               plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set), dense_operand(grad_out, LERF_F64, oH, oW, gout_set),
+                               dense_operand(grad_attr, LERF_F64, Va, 1, gattr_set, OPTIONAL), dense_operand(grad_pos, LERF_F64, V, 1, gpos_set, OPTIONAL),
+                               plane_operand(grad_w, sizeof(double), V, 1, gw_set, OPTIONAL), ws},
+                              {{GATTR, POS}, {GATTR, ATTR}, {GATTR, FACES}, {GATTR, AFACES}, {GATTR, DEPTH}, {GATTR, W}, {GATTR, KEYS}, {GATTR, GOUT},
+                               {GPOS, POS}, {GPOS, ATTR}, {GPOS, FACES}, {GPOS, AFACES}, {GPOS, DEPTH}, {GPOS, W}, {GPOS, KEYS}, {GPOS, GOUT},
+                               {GW, POS}, {GW, ATTR}, {GW, FACES}, {GW, AFACES}, {GW, DEPTH}, {GW, W}, {GW, KEYS}, {GW, GOUT},
+                               {WS, POS}, {WS, ATTR}, {WS, FACES}, {WS, AFACES}, {WS, DEPTH}, {WS, W}, {WS, KEYS}, {WS, GOUT},
+                               {GATTR, GPOS}, {GATTR, GW}, {GATTR, WS}, {GPOS, GW}, {GPOS, WS}, {GW, WS}},
+                              sizes && tile_ok(oH, oW, i0, j0) && (!w || float_dtype(w_dtype)) && orient >= -1 && orient <= 1 &&
+                                  (grad_attr || grad_pos || grad_w) && !(grad_w && !w) && max_adders >= 1 && workspace_bytes >= need);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_DT(pos_dtype, TP, {
+        const TriMesh<TP> mesh{(const TP*)pos, V, Va, faces, attr_faces, F, depth, w, w_dtype == LERF_F64, orient, max_span, i0, j0, oH, oW,
+                               pos_set, faces_set, afaces_set, depth_set, w_set};
+        LERF_COORDS_DT(attr_dtype, TA,
+            return run(mesh, (const TA*)attr, attr_set, keys, keys_set, grad_out, gout_set, n_sets, grad_attr, gattr_set, grad_pos, gpos_set, grad_w, gw_set,
+                       workspace, max_adders));
+    });
+}
+
 template <typename RUN>
 int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
                 const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets, int64_t a_set, int64_t b_set, int64_t gout_set,
@@ -1851,6 +2156,52 @@ int lerf_coords_trimesh_host(const void* pos, int pos_dtype, int V, const void* 
                              size_t workspace_bytes) {
     return lerf_coords_trimesh_batched_host(pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, out, out_dtype, out_row_stride,
                                             oH, oW, i0, j0, max_span, orient, keys, depth_out, workspace, workspace_bytes, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0);
+}
+
+size_t lerf_coords_trimesh_bwd_workspace_bytes(int64_t F, int64_t V, int64_t Va, int n_sets) { return tri_bwd_workspace_bytes(F, V, Va, n_sets); }
+
+int lerf_coords_trimesh_bwd_batched(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                                    const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, int oH, int oW, int i0, int j0,
+                                    int max_span, int orient, const uint64_t* keys, const double* grad_out, double* grad_attr, double* grad_pos,
+                                    double* grad_w, void* workspace, size_t workspace_bytes, int max_adders, int n_sets, int64_t pos_set_stride,
+                                    int64_t attr_set_stride, int64_t faces_set_stride, int64_t attr_faces_set_stride, int64_t depth_set_stride,
+                                    int64_t w_set_stride, int64_t keys_set_stride, int64_t grad_out_set_stride, int64_t grad_attr_set_stride,
+                                    int64_t grad_pos_set_stride, int64_t grad_w_set_stride, void* stream) {
+    return trimesh_bwd(TriBwdOnDevice{(hipStream_t)stream}, pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, oH, oW, i0, j0,
+                       max_span, orient, keys, grad_out, grad_attr, grad_pos, grad_w, workspace, workspace_bytes, max_adders, n_sets, pos_set_stride,
+                       attr_set_stride, faces_set_stride, attr_faces_set_stride, depth_set_stride, w_set_stride, keys_set_stride, grad_out_set_stride,
+                       grad_attr_set_stride, grad_pos_set_stride, grad_w_set_stride);
+}
+
+int lerf_coords_trimesh_bwd_batched_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                                         const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, int oH, int oW, int i0, int j0,
+                                         int max_span, int orient, const uint64_t* keys, const double* grad_out, double* grad_attr, double* grad_pos,
+                                         double* grad_w, void* workspace, size_t workspace_bytes, int max_adders, int n_sets, int64_t pos_set_stride,
+                                         int64_t attr_set_stride, int64_t faces_set_stride, int64_t attr_faces_set_stride, int64_t depth_set_stride,
+                                         int64_t w_set_stride, int64_t keys_set_stride, int64_t grad_out_set_stride, int64_t grad_attr_set_stride,
+                                         int64_t grad_pos_set_stride, int64_t grad_w_set_stride) {
+    return trimesh_bwd(TriBwdOnHost{}, pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, oH, oW, i0, j0, max_span, orient,
+                       keys, grad_out, grad_attr, grad_pos, grad_w, workspace, workspace_bytes, max_adders, n_sets, pos_set_stride, attr_set_stride,
+                       faces_set_stride, attr_faces_set_stride, depth_set_stride, w_set_stride, keys_set_stride, grad_out_set_stride, grad_attr_set_stride,
+                       grad_pos_set_stride, grad_w_set_stride);
+}
+
+int lerf_coords_trimesh_bwd(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                            const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, int oH, int oW, int i0, int j0, int max_span,
+                            int orient, const uint64_t* keys, const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w, void* workspace,
+                            size_t workspace_bytes, int max_adders, void* stream) {
+    return lerf_coords_trimesh_bwd_batched(pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, oH, oW, i0, j0, max_span, orient,
+                                           keys, grad_out, grad_attr, grad_pos, grad_w, workspace, workspace_bytes, max_adders, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+                                           0, stream);
+}
+
+int lerf_coords_trimesh_bwd_host(const void* pos, int pos_dtype, int V, const void* attr, int attr_dtype, int Va, const int32_t* faces,
+                                 const int32_t* attr_faces, int F, const float* depth, const void* w, int w_dtype, int oH, int oW, int i0, int j0,
+                                 int max_span, int orient, const uint64_t* keys, const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w,
+                                 void* workspace, size_t workspace_bytes, int max_adders) {
+    return lerf_coords_trimesh_bwd_batched_host(pos, pos_dtype, V, attr, attr_dtype, Va, faces, attr_faces, F, depth, w, w_dtype, oH, oW, i0, j0, max_span,
+                                                orient, keys, grad_out, grad_attr, grad_pos, grad_w, workspace, workspace_bytes, max_adders, 1, 0, 0, 0, 0, 0,
+                                                0, 0, 0, 0, 0, 0);
 }
 
 int lerf_coords_compose_bwd_batched(const void* a, int a_dtype, int64_t a_row_stride, int aH, int aW, const void* b, int b_dtype,

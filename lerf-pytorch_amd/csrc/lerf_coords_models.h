@@ -157,6 +157,27 @@
 //               The device bins the faces into item tiles of kTileRows x kTileCols = 4 x 16 pixels aligned to the tile's own rows and columns
 //               (tri_tiles: tr0 = (r0 - i0) / 4 .. (r1 - i0) / 4, tc0 = (c0 - j0) / 16 .. (c1 - j0) / 16) and draws one (face, tile) item a wave;
 //               the host loops over faces and boxes.  An integer min does not depend on the order: neither the tiles nor the chunks show.
+//   trimesh backward (tri_attr_bwd, tri_face_terms; lerf_coords_trimesh_bwd)   the adjoint of the resolve at FIXED VISIBILITY: pixel q
+//               belongs to the face f in the low word of keys[q]; coverage and the depth test get no gradient.  g = grad_out[q].
+//               per face, once (tri_grads):  area2 = edge(A, B, C);  the constant gradients of the barycentrics, (d/dq.r, d/dq.c):
+//                 Ga = ((C.c - B.c) / area2, -((C.r - B.r) / area2)),  Gb = ((A.c - C.c) / area2, -((A.r - C.r) / area2)),
+//                 Gc = ((B.c - A.c) / area2, -((B.r - A.r) / area2))
+//               per pixel:  l_b = e_b / area2,  l_c = e_c / area2 (tri_attr's),  l_a = (1 - l_b) - l_c
+//                 without w:  attr_k = (l_k*g.r, l_k*g.c)                                            -- 6 sums S_k a face
+//                 with w:     ia, ib, ic, d, n, u = n / d as in tri_attr;  m_k = (l_k*i_k) / d
+//                             h_k = ((a_k.r - u.r)*g.r + (a_k.c - u.c)*g.c) * i_k
+//                             v.r = ((h_a*Ga.r + h_b*Gb.r) + h_c*Gc.r) / d,  v.c likewise with the .c of Ga, Gb, Gc
+//                             attr_k = (m_k*g.r, m_k*g.c),  pos_k = (-(l_k*v.r), -(l_k*v.c)),  w_k = -(m_k*h_k)       -- 15 sums a face
+//               THE ORDER OF THE SUMS IS PART OF THE CONTRACT (tri_bwd_thread): one face = 4 x 64 slots (kTriBwdWaves); slot (r, l) owns lane
+//               pixel l (row l / 16, column l % 16) of the item tiles k = r, r + 4, ... < ntr*ntc of the face's clipped box (tri_tiles: tile
+//               k is row k / ntc, column k % ntc) and adds its pixels' terms in ascending k into sums that start at +0.0; a pixel adds only
+//               when it lies in the box, its key is not all ones and the key's low word is f.  Then per sum the butterfly over the 64
+//               lanes x[l] = x[l] + x[l ^ m], m = 32, 16, 8, 4, 2, 1, and the four slots r as ((p0 + p1) + p2) + p3.
+//               the face's terms (tri_face_terms):  with w the sums themselves;  without w  attr_k = S_k,  w_k = 0 and
+//                 Jrr = (aA.r*Ga.r + aB.r*Gb.r) + aC.r*Gc.r,  Jrc = the same with Ga.c, Gb.c, Gc.c,  Jcr, Jcc = the same from the a.c
+//                 pos_k = (-(Jrr*S_k.r + Jcr*S_k.c), -(Jrc*S_k.r + Jcc*S_k.c));  a NaN term is the canonical quiet NaN
+//               the vertices: element v of grad_pos (grad_w; grad_attr through attr_faces) = what it held + the terms of the corners that name
+//               v, one after the other in ascending (face, corner) order.  A face the forward's set-up skips adds nothing anywhere.
 //   compose backward (compose_bwd_point; aH, aW >= 2)   one entry with inner point (row, col) and upstream g = (g.r, g.c):
 //                 a NaN in row or col: nothing is read, nothing is scattered, the inner gradient is (0, 0) whatever g holds (a select)
 //                 R = compose_axis(row, aH), Cx = compose_axis(col, aW), wr = {R.w0, R.w1}, wc = {Cx.w0, Cx.w1}: the forward's
@@ -1054,6 +1075,107 @@ LERF_HD inline Point tri_attr(const TriFace& t, Point aA, Point aB, Point aC, bo
     const double nr = aA.r * ia + (lb * (aB.r * ib - aA.r * ia) + lc * (aC.r * ic - aA.r * ia));
     const double nc = aA.c * ia + (lb * (aB.c * ib - aA.c * ia) + lc * (aC.c * ic - aA.c * ia));
     return {nr / d, nc / d};
+}
+
+// ---- trimesh backward: the adjoint of tri_attr at fixed visibility (the statement order: the top of this file)
+constexpr int kTriBwdWaves = 4;       // waves of the face pass: thread t = 64 r + l owns lane pixel l of the item tiles r, r + 4, ...
+constexpr int kTriBwdTerms = 15;      // a face's terms: [corner A, B, C][attr.r, attr.c, pos.r, pos.c, w]
+
+// the constant gradients of the barycentrics with respect to the pixel: (d l_k / d q.r, d l_k / d q.c)
+struct TriGrads {
+    Point a, b, c;
+};
+
+LERF_HD inline TriGrads tri_grads(const TriFace& t, double area2) {
+#pragma clang fp contract(off)
+    TriGrads G;
+    G.a = {(t.C.c - t.B.c) / area2, -((t.C.r - t.B.r) / area2)};
+    G.b = {(t.A.c - t.C.c) / area2, -((t.A.r - t.C.r) / area2)};
+    G.c = {(t.B.c - t.A.c) / area2, -((t.B.r - t.A.r) / area2)};
+    return G;
+}
+
+// the terms pixel q adds to the sums of the face that won it, upstream g: d[5 k + 0, 1] for attr of corner k, with w also d[5 k + 2, 3]
+// for pos and d[5 k + 4] for w; without w only the six attr terms are written (the pos terms come from their SUMS: tri_face_terms)
+template <bool HAS_W>
+LERF_HD inline void tri_attr_bwd(const TriFace& t, const TriGrads& G, Point aA, Point aB, Point aC, double wA, double wB, double wC, double q_r,
+                                 double q_c, Point g, double* d) {
+#pragma clang fp contract(off)
+    const double area2 = edge_fn(t.A, t.B, t.C.r, t.C.c);
+    const TriEdges e = tri_edges_indexed(t.A, t.B, t.C, t.ia, t.ib, t.ic, q_r, q_c);
+    const double lb = e.b / area2, lc = e.c / area2;
+    const double la = (1.0 - lb) - lc;
+    if (!HAS_W) {
+        d[0] = la * g.r; d[1] = la * g.c;
+        d[5] = lb * g.r; d[6] = lb * g.c;
+        d[10] = lc * g.r; d[11] = lc * g.c;
+        return;
+    }
+    const double ia = 1.0 / wA, ib = 1.0 / wB, ic = 1.0 / wC;
+    const double dd = ia + (lb * (ib - ia) + lc * (ic - ia));
+    const double nr = aA.r * ia + (lb * (aB.r * ib - aA.r * ia) + lc * (aC.r * ic - aA.r * ia));
+    const double nc = aA.c * ia + (lb * (aB.c * ib - aA.c * ia) + lc * (aC.c * ic - aA.c * ia));
+    const double ur = nr / dd, uc = nc / dd;                                                      // tri_attr's value
+    const double ma = (la * ia) / dd, mb = (lb * ib) / dd, mc = (lc * ic) / dd;
+    const double ha = ((aA.r - ur) * g.r + (aA.c - uc) * g.c) * ia;
+    const double hb = ((aB.r - ur) * g.r + (aB.c - uc) * g.c) * ib;
+    const double hc = ((aC.r - ur) * g.r + (aC.c - uc) * g.c) * ic;
+    const double vr = ((ha * G.a.r + hb * G.b.r) + hc * G.c.r) / dd;                              // J(q)^T g
+    const double vc = ((ha * G.a.c + hb * G.b.c) + hc * G.c.c) / dd;
+    d[0] = ma * g.r; d[1] = ma * g.c; d[2] = -(la * vr); d[3] = -(la * vc); d[4] = -(ma * ha);
+    d[5] = mb * g.r; d[6] = mb * g.c; d[7] = -(lb * vr); d[8] = -(lb * vc); d[9] = -(mb * hb);
+    d[10] = mc * g.r; d[11] = mc * g.c; d[12] = -(lc * vr); d[13] = -(lc * vc); d[14] = -(mc * hc);
+}
+
+// the face's 15 terms T from its reduced sums S (both [corner][5]); without w the pos terms are -J^T S_m, J the face's constant Jacobian
+LERF_HD inline void tri_face_terms(const TriGrads& G, Point aA, Point aB, Point aC, bool has_w, const double* S, double* T) {
+#pragma clang fp contract(off)
+    const double Jrr = (aA.r * G.a.r + aB.r * G.b.r) + aC.r * G.c.r, Jrc = (aA.r * G.a.c + aB.r * G.b.c) + aC.r * G.c.c;
+    const double Jcr = (aA.c * G.a.r + aB.c * G.b.r) + aC.c * G.c.r, Jcc = (aA.c * G.a.c + aB.c * G.b.c) + aC.c * G.c.c;
+    for (int m = 0; m < 3; ++m) {
+        const double sr = S[5 * m], sc = S[5 * m + 1];
+        T[5 * m] = sr;
+        T[5 * m + 1] = sc;
+        T[5 * m + 2] = has_w ? S[5 * m + 2] : -(Jrr * sr + Jcr * sc);
+        T[5 * m + 3] = has_w ? S[5 * m + 3] : -(Jrc * sr + Jcc * sc);
+        T[5 * m + 4] = has_w ? S[5 * m + 4] : 0.0;
+    }
+    for (int k = 0; k < kTriBwdTerms; ++k)
+        if (T[k] != T[k]) T[k] = __builtin_nan("");      // the canonical quiet NaN: the host and the device agree on its bits
+}
+
+// the sums of one thread of the face pass: wave slot r, lane l (pixel lr = l / 16, lc = l % 16 of an item tile), over the item tiles
+// k = r, r + kTriBwdWaves, ... of the face's clipped box, in ascending k, into acc (NS values: 15 with w, the 6 attr sums without,
+// in the order of the terms).  A pixel adds only when it lies in the box, its key is not all ones and the key's low word is f; any
+// other pixel forms no address in gout.  keys, gout: the planes of the face's set, [oH][oW] and [oH][oW][2].
+template <bool HAS_W>
+LERF_HD inline void tri_bwd_thread(const TriFace& t, const RasterBox& box, const TriGrads& G, Point aA, Point aB, Point aC, double wA, double wB,
+                                   double wC, uint32_t f, int i0, int j0, int oW, const uint64_t* keys, const double* gout, int r, int l, double* acc) {
+#pragma clang fp contract(off)
+    constexpr int NS = HAS_W ? kTriBwdTerms : 6;
+    const TriTiles tt = tri_tiles(box, i0, j0);
+    const uint32_t n = (uint32_t)tt.ntr * (uint32_t)tt.ntc;
+    const int lr = l / kTileCols, lc = l % kTileCols;
+    for (uint32_t k = (uint32_t)r; k < n; k += (uint32_t)kTriBwdWaves) {
+        const int rr = (tt.tr0 + (int)(k / (uint32_t)tt.ntc)) * kTileRows + lr, qq = (tt.tc0 + (int)(k % (uint32_t)tt.ntc)) * kTileCols + lc;
+        if (rr < box.r0 - i0 || rr > box.r1 - i0 || qq < box.c0 - j0 || qq > box.c1 - j0) continue;
+        const int64_t e = (int64_t)rr * oW + qq;
+        const uint64_t key = keys[e];
+        if (key == kNoKey || (uint32_t)key != f) continue;
+        const Entry<double> g = *reinterpret_cast<const Entry<double>*>(gout + 2 * e);
+        double d[kTriBwdTerms];
+        tri_attr_bwd<HAS_W>(t, G, aA, aB, aC, wA, wB, wC, (double)(i0 + rr), (double)(j0 + qq), Point{g.r, g.c}, d);
+        if (HAS_W) {
+#pragma unroll
+            for (int k2 = 0; k2 < NS; ++k2) acc[k2] = acc[k2] + d[k2];
+        } else {
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                acc[2 * m] = acc[2 * m] + d[5 * m];
+                acc[2 * m + 1] = acc[2 * m + 1] + d[5 * m + 1];
+            }
+        }
+    }
 }
 
 }  // namespace coords

@@ -19,6 +19,8 @@
 // The triangle-mesh rasteriser's host twins (trimesh_ops: lerf_coords_trimesh_host, lerf_coords_trimesh_batched_host) draw a fan wider than
 // the tile, with indices -1, V and 2^31 - 1, NaN, +-inf and 1e300 vertices and w <= 0 among its faces, into a strided out at a non-zero
 // origin, every dtype mix, two sets with shared faces; a workspace one byte short is refused.
+// Its adjoint's host twins (lerf_coords_trimesh_bwd_host, lerf_coords_trimesh_bwd_batched_host) run inside trimesh_ops at the keys of every one of
+// those forwards: upstream NaN in every hole, exactly-sized gradients and workspace, every NULL combination, a cap of 64 and of 1, two sets.
 // It needs no GPU and is never loaded into another process.  Exit status 0 and "ok" on the last line: no report.
 #include "lerf_hip.h"
 
@@ -644,6 +646,30 @@ static void trimesh_ops(int oH, int oW) {
                                                             d ? zo.data() : nullptr, ws.data(), need) == LERF_OK);
                             EXPECT(keys != keys0);
                             for (uint64_t k : keys) drawn += k != ~(uint64_t)0;
+                            // the adjoint at these keys (lerf_coords_trimesh_bwd_host) on exactly-sized heap buffers: NaN upstream in every hole, a
+                            // generous cap (every gradient finite) and a cap of 1 (the NaN branch), every NULL combination, one byte short
+                            std::vector<double> go((size_t)oH * oW * 2), ga((size_t)2 * Va), gp((size_t)2 * V), gw((size_t)V);
+                            for (size_t k = 0; k < go.size(); ++k) go[k] = keys[k / 2] == ~(uint64_t)0 ? nan : std::sin(0.37 * (double)k);
+                            const size_t nb = lerf_coords_trimesh_bwd_workspace_bytes(F, V, Va, 1);
+                            EXPECT(nb == 16 + 8 * 15 * (size_t)F + 4 * ((size_t)Va + 3 * (size_t)F));
+                            std::vector<unsigned char> bws(nb, 0x55);
+                            for (int cap : {64, 1})
+                                for (int mask = 1; mask < 8; ++mask) {
+                                    if ((mask & 4) && !w) continue;
+                                    std::fill(ga.begin(), ga.end(), 0.0); std::fill(gp.begin(), gp.end(), 0.0); std::fill(gw.begin(), gw.end(), 0.0);
+                                    EXPECT(lerf_coords_trimesh_bwd_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), (with & 4) ? af.data() : nullptr, F, d, w,
+                                                                        (with & 4) ? LERF_F64 : LERF_F32, oH, oW, 3, 7, span, orient, keys.data(), go.data(),
+                                                                        (mask & 1) ? ga.data() : nullptr, (mask & 2) ? gp.data() : nullptr,
+                                                                        (mask & 4) ? gw.data() : nullptr, bws.data(), nb, cap) == LERF_OK);
+                                    if (cap == 64)
+                                        for (const std::vector<double>* g : {&ga, &gp, &gw})
+                                            for (double v : *g) EXPECT(v - v == 0.0);
+                                }
+                            EXPECT(lerf_coords_trimesh_bwd_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), nullptr, F, d, w, (with & 4) ? LERF_F64 : LERF_F32, oH, oW, 3,
+                                                                7, span, orient, keys.data(), go.data(), ga.data(), gp.data(), nullptr, bws.data(), nb - 1, 64) ==
+                                   LERF_EINVAL);
+                            EXPECT(lerf_coords_trimesh_bwd_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), nullptr, F, d, w, (with & 4) ? LERF_F64 : LERF_F32, oH, oW, 3,
+                                                                7, span, orient, keys.data(), go.data(), nullptr, nullptr, nullptr, bws.data(), nb, 64) == LERF_EINVAL);
                         }
                 EXPECT(drawn > 0);
                 // a far tile: nothing unclipped may become an int
@@ -662,6 +688,28 @@ static void trimesh_ops(int oH, int oW) {
                     EXPECT(lerf_coords_trimesh_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, out.p(), to,
                                                     out.stride, oH, oW, 3, 7, 0, 0, keys.data(), zo.data(), ws.data(), need) == LERF_OK);
                     EXPECT(!std::memcmp(keys.data(), keys2.data(), keys.size() * sizeof(uint64_t)) && !std::memcmp(zo.data(), zo2.data(), zo.size() * sizeof(float)));
+                    // the adjoint of the two sets in one call: per-set gradients, exactly sized; set 0 equals the single call
+                    {
+                        const size_t nb2 = lerf_coords_trimesh_bwd_workspace_bytes(F, V, Va, 2), nb1 = lerf_coords_trimesh_bwd_workspace_bytes(F, V, Va, 1);
+                        std::vector<unsigned char> bws2(nb2, 0x55);
+                        std::vector<double> go2((size_t)2 * oH * oW * 2), ga2((size_t)4 * Va, 0.0), gp2((size_t)4 * V, 0.0), gw2((size_t)2 * V, 0.0);
+                        std::vector<double> ga1((size_t)2 * Va, 0.0), gp1((size_t)2 * V, 0.0), gw1((size_t)V, 0.0);
+                        for (size_t k = 0; k < go2.size(); ++k) go2[k] = keys2[k / 2] == ~(uint64_t)0 ? nan : std::cos(0.21 * (double)k);
+                        EXPECT(lerf_coords_trimesh_bwd_batched_host(pos2.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, oH,
+                                                                    oW, 3, 7, 0, 0, keys2.data(), go2.data(), ga2.data(), gp2.data(), gw2.data(), bws2.data(), nb2, 64, 2,
+                                                                    2 * V, 0, 0, 0, 0, 0, (int64_t)oH * oW, 2 * (int64_t)oH * oW, 2 * Va, 2 * V, V) == LERF_OK);
+                        EXPECT(lerf_coords_trimesh_bwd_host(pos.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, oH, oW, 3, 7, 0,
+                                                            0, keys.data(), go2.data(), ga1.data(), gp1.data(), gw1.data(), bws2.data(), nb1, 64) == LERF_OK);
+                        EXPECT(!std::memcmp(ga1.data(), ga2.data(), ga1.size() * 8) && !std::memcmp(gp1.data(), gp2.data(), gp1.size() * 8) &&
+                               !std::memcmp(gw1.data(), gw2.data(), gw1.size() * 8));
+                        // a gradient shared between the sets, and the workspace of one set for two
+                        EXPECT(lerf_coords_trimesh_bwd_batched_host(pos2.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, oH,
+                                                                    oW, 3, 7, 0, 0, keys2.data(), go2.data(), ga2.data(), gp2.data(), gw2.data(), bws2.data(), nb2, 64, 2,
+                                                                    2 * V, 0, 0, 0, 0, 0, (int64_t)oH * oW, 2 * (int64_t)oH * oW, 0, 2 * V, V) == LERF_EINVAL);
+                        EXPECT(lerf_coords_trimesh_bwd_batched_host(pos2.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, oH,
+                                                                    oW, 3, 7, 0, 0, keys2.data(), go2.data(), ga2.data(), gp2.data(), gw2.data(), bws2.data(), nb1, 64, 2,
+                                                                    2 * V, 0, 0, 0, 0, 0, (int64_t)oH * oW, 2 * (int64_t)oH * oW, 2 * Va, 2 * V, V) == LERF_EINVAL);
+                    }
                     // the sets' outputs must not be shared; the workspace of one set is short for two
                     EXPECT(lerf_coords_trimesh_batched_host(pos2.p(), tp, V, attr.p(), ta, Va, fc.data(), af.data(), F, depth.data(), w32.data(), LERF_F32, keep.p(), to,
                                                             keep.stride, oH, oW, 3, 7, 0, 0, keys2.data(), nullptr, ws2.data(), need2, 2, 2 * V, 0, 0, 0, 0, 0, 0,

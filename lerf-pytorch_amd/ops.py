@@ -1214,6 +1214,22 @@ def coords_trimesh(pos, attr, faces, out_hw, attr_faces=None, depth=None, w=None
                                   return_keys, return_depth)
 
 
+def coords_trimesh_bwd(pos, attr, faces, out_hw, keys, grad_out, attr_faces=None, depth=None, w=None, origin=(0, 0), max_span=0, orient=0,
+                       need=(True, True, False), grad_attr=None, grad_pos=None, grad_w=None, max_adders=4096):
+    """lerf_coords_trimesh_bwd: ACCUMULATE the adjoint of coords_trimesh at FIXED VISIBILITY of grad_out (float64
+    contiguous, the map's shape) into grad_attr [Va, 2], grad_pos [V, 2] and grad_w [V] (float64 contiguous; None: zeroed ones);
+    need = (attr, pos, w): a false one is skipped and returned as None; w's needs w.  The mesh operands, origin, max_span and orient are
+    the forward's; keys is the int64 plane the forward wrote (return_keys=True).  Every pixel belongs to the face its key names;
+    coverage and the depth test get no gradient; grad_out is read at won pixels only.  A face pass (one workgroup per face, a fixed
+    tree) and a vertex pass (the ordered scatter's four passes, the faces as entries) on the current stream over the stream's cached
+    scratch: bit-equal from run to run and to _lib.coords_trimesh_bwd_host.  Afterwards the largest number of drawn face corners at one
+    vertex is read back (ONE 4-byte copy and a synchronisation of the stream); above max_adders: LerfError -- that vertex holds NaN.
+    A batch ([B, V, 2] operands, keys [B, oH, oW]) is one call; every gradient then has the leading B, also for an operand the batch
+    shares (the caller sums those) -> (grad_attr, grad_pos, grad_w)."""
+    return _lib.coords_trimesh_bwd_on(_lib.DeviceOperands(), pos, attr, faces, out_hw, keys, grad_out, attr_faces, depth, w, origin, max_span,
+                                      orient, need, grad_attr, grad_pos, grad_w, max_adders, True)[:3]
+
+
 def coords_compose_bwd(outer, inner, grad_out, grad_outer=None, grad_inner=None, need=(True, True), deterministic=False, max_adders=4096):
     """lerf_coords_compose_bwd: ACCUMULATE the adjoint of coords_compose(outer, inner) of grad_out (float64 contiguous [oH, oW, 2])
     into grad_outer (float64 contiguous [aH, aW, 2]: a bilinear scatter by float64 atomic adds, reproducible up to the rounding of
