@@ -16,11 +16,12 @@
 // model dispatch, run(Op{...}, oH, oW[, sets]).  The C entry points lerf_coords_X_batched / lerf_coords_X_batched_host are that template
 // with one runner or the other, and lerf_coords_X / lerf_coords_X_host call those with n_sets = 1 and set strides 0, so the device and
 // the host twin, the single map and the batch cannot drift apart: they agree bit for bit by construction (the two float scatters
-// excepted, below).  THE ARGUMENT CHECKS are one operand table per call (Operand, Pair, check_call, after the kernels):
-// an entry point lists its operands, its scalar rules and the pairs that must not intersect ONCE, and one function judges them.  Add2 is the float scatter of the map adjoints: two float64 atomicAdd where compiled for the device, a plain add on the host; AddPlane is the same pattern for one plane of an image (the forward warp, lerf_splat; its arithmetic is lerf_splat_point.h).
+// excepted, below).  THE ARGUMENT CHECKS are one operand table per call (Operand, check_call, after the kernels):
+// an entry point lists its operands with their roles and its scalar rules ONCE, and one function judges them; which operands may
+// intersect is derived from the roles (a WRITTEN operand intersects no other), not listed.  Add2 is the float scatter of the map adjoints: two float64 atomicAdd where compiled for the device, a plain add on the host; AddPlane is the same pattern for one plane of an image (the forward warp, lerf_splat; its arithmetic is lerf_splat_point.h).
 // The three float scatters (SplatOp, ComposeBwdOp, InvertBwdOp) also run under a THIRD pair of runners, OrderedOnDevice / OrderedOnHost
-// (after the scatter runners): the same op four times over a caller-owned workspace -- count, scan, fill, sort and sum -- which adds
-// in the host twin's order and so IS bit-equal to it (the _ordered entry points).
+// (after the scatter runners): the same op four times over a caller-owned workspace -- count, scan, fill, sort and sum (ordered_passes_
+// device / _host) -- which adds in the host twin's order and so IS bit-equal to it (the _ordered entry points).
 // MapReader is the one strided-map reader handed to the *_point functions; a dense float64 gradient [h][w][2] is a map of row stride 2w.
 //
 // The rasterising inverse (lerf_coords_invert_raster) is three passes: KeyFillOp and ResolveOp are per-entry functors under the two
@@ -32,7 +33,7 @@
 // one wave per (face, 4 x 16 pixel tile) item of a scanned item list (TriRasterOnDevice), or the plain loop over faces and their boxes
 // (TriRasterOnHost).  Its notes are with it, after the ordered scatter's scan.  Its adjoint (lerf_coords_trimesh_bwd) is a
 // face pass of its own shape (trimesh_bwd_face_kernel: one workgroup per face, a fixed reduction tree) and the ordered scatter's four
-// passes over TriVertexOp, whose entries are the faces (TriBwdOnDevice / TriBwdOnHost, after the ordered runners).
+// passes (the same two functions) over TriVertexOp, whose entries are the faces (TriBwdOnDevice / TriBwdOnHost, after the ordered runners).
 //
 // Kernels of their own shape (unchanged by the above):
 //   coords_mesh_bwd_{rows,cols}_kernel      the adjoint of the mesh upsample, map = Wr . ctrl . Wc^T  =>  grad_ctrl = Wr^T . grad_map . Wc,
@@ -54,7 +55,7 @@
 //                LDS and are added in the order 0, 1, 2, 3; ONE partial vector per block goes to the workspace ([set][k][block])
 //       sum      ONE wave per (set, k): lane l adds the partials l, l + 64, ..., the same tree, lane 0 is the one writer (load-add-store)
 //       2160 x 3840: 2 040 blocks a set in pass 1 (8 per CU), 343 KB of partials for the 21 sums of brown; grad_map is read once, coalesced
-//       The host twin emulates the two passes lane by lane (two_pass_sums_host; lerf_coords_build_bwd_host, at the end of this file).
+//       The host twin emulates the two passes lane by lane (two_pass_sums_host); the runner pair is TwoPassOnDevice / TwoPassOnHost.
 //   coords_reproject_bwd_kernel             the adjoint of reproject: pass 1's grid, band and lanes over reproject_point_bwd; every lane adds d depth
 //                                           into grad_depth at its own entries (one writer) and, when grad_params is wanted, keeps 12 running
 //                                           sums that leave as the block's partial vector for coords_build_bwd_sum_kernel -- the same fixed order
@@ -987,6 +988,13 @@ ordered_sum_kernel(const OP op, int64_t n_targets, const uint32_t* __restrict__ 
     ordered_sum_target(op, s, q, cursor + (int64_t)s * n_targets, list + (int64_t)s * n_slots, W, max_adders);
 }
 
+// one target space of a call as passes 1 - 4 see it: where the largest count goes, the cursor [sets][n_targets], the list [sets][n_slots]
+// and the scan's partials; OrderedLayout and TriBwdLayout each hand one out
+struct OrderedView {
+    uint32_t *max_word, *cursor, *list, *scan;
+    int64_t n_targets, n_slots;
+};
+
 struct OrderedLayout {
     int64_t n_entries, n_targets, n_slots, partials;
     uint32_t *header, *cursor, *list, *scan;
@@ -997,10 +1005,51 @@ struct OrderedLayout {
         list = cursor + (int64_t)sets * n_targets;
         scan = list + (int64_t)sets * n_slots;
     }
+    OrderedView view() const { return {header + kOrderedMaxWord, cursor, list, scan, n_targets, n_slots}; }
     static size_t bytes(int64_t entries, int64_t targets, int sets) {
         return sizeof(uint32_t) * ((size_t)kOrderedHeaderWords + (size_t)sets * ((size_t)targets + 4 * (size_t)entries + (size_t)scan_partials(targets)));
     }
 };
+
+// THE FOUR PASSES, once per side: op over the entry grid [eH][eW] of every set into the view's zeroed cursor (zeroing stays with the
+// callers: the ordered scatter clears header and cursor in one memset, the mesh adjoint the cursor once per target space).  Device:
+// plain launches in stream order, the launch status looked at after every pass.
+template <typename OP>
+int ordered_passes_device(hipStream_t stream, const OP& op, int eH, int eW, int sets, const OrderedView& v, int max_adders) {
+    const OnDevice run{stream};
+    int rc = run(CountPass<OP>{op.taps_only(), v.cursor, v.n_targets}, eH, eW, sets);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    scan_exclusive_u32(stream, v.cursor, v.n_targets, sets, v.n_targets, v.scan, v.max_word);
+    rc = launch_status();
+    if (rc != LERF_OK) return rc;
+    rc = run(FillPass<OP>{op.taps_only(), v.cursor, v.list, v.n_targets, v.n_slots, eW}, eH, eW, sets);
+    if (rc != LERF_OK) return rc;
+    clear_stale_error();
+    hipLaunchKernelGGL(ordered_sum_kernel<OP>, dim3((unsigned)((v.n_targets + 255) / 256), sets), dim3(256), 0, stream, op.scatter_only(), v.n_targets,
+                       v.cursor, v.list, v.n_slots, eW, (uint32_t)max_adders);
+    return launch_status();
+}
+
+// the same four passes, serially; pass 3 walks the entries in DESCENDING order, so every segment of two or more ids reaches the sort
+// reversed and the sort, the duplicate skip and the cap run here as they do on the device
+template <typename OP>
+void ordered_passes_host(const OP& op, int eH, int eW, int sets, const OrderedView& v, int max_adders) {
+    OnHost{}(CountPass<OP>{op.taps_only(), v.cursor, v.n_targets}, eH, eW, sets);
+    for (int s = 0; s < sets; ++s) {
+        uint32_t* c = v.cursor + (int64_t)s * v.n_targets;
+        for (int64_t q = 0; q < v.n_targets; ++q) *v.max_word = c[q] > *v.max_word ? c[q] : *v.max_word;
+        scan_exclusive_u32_host(c, v.n_targets);
+    }
+    const FillPass<OP> fill{op.taps_only(), v.cursor, v.list, v.n_targets, v.n_slots, eW};
+    for (int s = 0; s < sets; ++s)
+        for (int i = eH - 1; i >= 0; --i)
+            for (int j = eW - 1; j >= 0; --j) fill(i, j, s);
+    const OP scatter = op.scatter_only();
+    for (int s = 0; s < sets; ++s)
+        for (int64_t q = 0; q < v.n_targets; ++q)
+            ordered_sum_target(scatter, s, q, v.cursor + (int64_t)s * v.n_targets, v.list + (int64_t)s * v.n_slots, eW, (uint32_t)max_adders);
+}
 
 struct OrderedOnDevice {
     hipStream_t stream;
@@ -1012,23 +1061,13 @@ struct OrderedOnDevice {
         const OrderedLayout L(ws, (int64_t)oH * oW, (int64_t)op.target_h() * op.target_w(), sets);
         if (hipMemsetAsync(ws, 0, sizeof(uint32_t) * (kOrderedHeaderWords + (size_t)sets * L.n_targets), stream) != hipSuccess) return LERF_ELAUNCH;
         if (op.has_scatter()) {
-            const OnDevice run{stream};
-            int rc = run(CountPass<OP>{op.taps_only(), L.cursor, L.n_targets}, oH, oW, sets);
-            if (rc != LERF_OK) return rc;
-            scan_exclusive_u32(stream, L.cursor, L.n_targets, sets, L.n_targets, L.scan, L.header + kOrderedMaxWord);
-            rc = run(FillPass<OP>{op.taps_only(), L.cursor, L.list, L.n_targets, L.n_slots, oW}, oH, oW, sets);
-            if (rc != LERF_OK) return rc;
-            hipLaunchKernelGGL(ordered_sum_kernel<OP>, dim3((unsigned)((L.n_targets + 255) / 256), sets), dim3(256), 0, stream, op.scatter_only(),
-                               L.n_targets, L.cursor, L.list, L.n_slots, oW, (uint32_t)max_adders);
-            rc = launch_status();
+            const int rc = ordered_passes_device(stream, op, oH, oW, sets, L.view(), max_adders);
             if (rc != LERF_OK) return rc;
         }
         return op.has_rest() ? OnDevice{stream}(op.rest_only(), oH, oW, sets) : LERF_OK;
     }
 };
 
-// the same four passes, serially; pass 3 walks the entries in DESCENDING order, so every segment of two or more ids reaches the sort
-// reversed and the sort, the duplicate skip and the cap run here as they do on the device
 struct OrderedOnHost {
     void* ws;
     int max_adders;
@@ -1037,22 +1076,7 @@ struct OrderedOnHost {
         const OrderedLayout L(ws, (int64_t)oH * oW, (int64_t)op.target_h() * op.target_w(), sets);
         for (int k = 0; k < kOrderedHeaderWords; ++k) L.header[k] = 0;
         for (int64_t k = 0; k < (int64_t)sets * L.n_targets; ++k) L.cursor[k] = 0;
-        if (op.has_scatter()) {
-            OnHost{}(CountPass<OP>{op.taps_only(), L.cursor, L.n_targets}, oH, oW, sets);
-            for (int s = 0; s < sets; ++s) {
-                uint32_t* c = L.cursor + (int64_t)s * L.n_targets;
-                for (int64_t q = 0; q < L.n_targets; ++q) L.header[kOrderedMaxWord] = c[q] > L.header[kOrderedMaxWord] ? c[q] : L.header[kOrderedMaxWord];
-                scan_exclusive_u32_host(c, L.n_targets);
-            }
-            const FillPass<OP> fill{op.taps_only(), L.cursor, L.list, L.n_targets, L.n_slots, oW};
-            for (int s = 0; s < sets; ++s)
-                for (int i = oH - 1; i >= 0; --i)
-                    for (int j = oW - 1; j >= 0; --j) fill(i, j, s);
-            const OP scatter = op.scatter_only();
-            for (int s = 0; s < sets; ++s)
-                for (int64_t q = 0; q < L.n_targets; ++q)
-                    ordered_sum_target(scatter, s, q, L.cursor + (int64_t)s * L.n_targets, L.list + (int64_t)s * L.n_slots, oW, (uint32_t)max_adders);
-        }
+        if (op.has_scatter()) ordered_passes_host(op, oH, oW, sets, L.view(), max_adders);
         return op.has_rest() ? OnHost{}(op.rest_only(), oH, oW, sets) : LERF_OK;
     }
 };
@@ -1141,6 +1165,7 @@ struct TriBwdLayout {
         list = cursor + (int64_t)sets * n_max;
         scan = list + (int64_t)sets * n_slots;
     }
+    OrderedView view(int64_t n_targets) const { return {header + kOrderedMaxWord, cursor, list, scan, n_targets, n_slots}; }      // V or Va
     static size_t bytes(int64_t F, int64_t V, int64_t Va, int sets) {
         const int64_t n = V > Va ? V : Va;
         return sizeof(uint32_t) * kOrderedHeaderWords + sizeof(double) * (size_t)sets * (size_t)F * kTriBwdTerms +
@@ -1242,21 +1267,8 @@ struct TriBwdOnDevice {
     hipStream_t stream;
     template <typename OP>
     int vertices(const OP& op, const TriBwdLayout& L, int F, int sets, int max_adders) const {
-        const int64_t n = op.n;
-        if (hipMemsetAsync(L.cursor, 0, sizeof(uint32_t) * (size_t)sets * (size_t)n, stream) != hipSuccess) return LERF_ELAUNCH;
-        const OnDevice run{stream};
-        int rc = run(CountPass<OP>{op.taps_only(), L.cursor, n}, 1, F, sets);
-        if (rc != LERF_OK) return rc;
-        clear_stale_error();
-        scan_exclusive_u32(stream, L.cursor, n, sets, n, L.scan, L.header + kOrderedMaxWord);
-        rc = launch_status();
-        if (rc != LERF_OK) return rc;
-        rc = run(FillPass<OP>{op.taps_only(), L.cursor, L.list, n, L.n_slots, F}, 1, F, sets);
-        if (rc != LERF_OK) return rc;
-        clear_stale_error();
-        hipLaunchKernelGGL(ordered_sum_kernel<OP>, dim3((unsigned)((n + 255) / 256), sets), dim3(256), 0, stream, op.scatter_only(), n, L.cursor, L.list,
-                           L.n_slots, F, (uint32_t)max_adders);
-        return launch_status();
+        if (hipMemsetAsync(L.cursor, 0, sizeof(uint32_t) * (size_t)sets * (size_t)op.n, stream) != hipSuccess) return LERF_ELAUNCH;
+        return ordered_passes_device(stream, op, 1, F, sets, L.view(op.n), max_adders);
     }
     template <typename TP, typename TA>
     int operator()(const TriMesh<TP>& mesh, const TA* attr, int64_t attr_set, const uint64_t* keys, int64_t keys_set, const double* gout,
@@ -1279,24 +1291,11 @@ struct TriBwdOnDevice {
     }
 };
 
-// the same passes serially; the fill walks the faces in DESCENDING order, so the sort, the duplicate skip and the cap run as on the device
 struct TriBwdOnHost {
     template <typename OP>
     int vertices(const OP& op, const TriBwdLayout& L, int F, int sets, int max_adders) const {
-        const int64_t n = op.n;
-        for (int64_t k = 0; k < (int64_t)sets * n; ++k) L.cursor[k] = 0;
-        OnHost{}(CountPass<OP>{op.taps_only(), L.cursor, n}, 1, F, sets);
-        for (int s = 0; s < sets; ++s) {
-            uint32_t* c = L.cursor + (int64_t)s * n;
-            for (int64_t q = 0; q < n; ++q) L.header[kOrderedMaxWord] = c[q] > L.header[kOrderedMaxWord] ? c[q] : L.header[kOrderedMaxWord];
-            scan_exclusive_u32_host(c, n);
-        }
-        const FillPass<OP> fill{op.taps_only(), L.cursor, L.list, n, L.n_slots, F};
-        for (int s = 0; s < sets; ++s)
-            for (int f = F - 1; f >= 0; --f) fill(0, f, s);
-        const OP scatter = op.scatter_only();
-        for (int s = 0; s < sets; ++s)
-            for (int64_t q = 0; q < n; ++q) ordered_sum_target(scatter, s, q, L.cursor + (int64_t)s * n, L.list + (int64_t)s * L.n_slots, F, (uint32_t)max_adders);
+        for (int64_t k = 0; k < (int64_t)sets * op.n; ++k) L.cursor[k] = 0;
+        ordered_passes_host(op, 1, F, sets, L.view(op.n), max_adders);
         return LERF_OK;
     }
     template <typename TP, typename TA>
@@ -1474,40 +1473,48 @@ coords_reproject_bwd_kernel(const double* __restrict__ params, const TD* __restr
     }
 }
 
+// the three-way choice of lerf_coords_math for element e; y is read for atan2 alone
+LERF_HD inline double math_element(int op, const double* x, const double* y, int64_t e) {
+    return op == LERF_MATH_SQRT ? sqrt_pm(x[e]) : op == LERF_MATH_ATAN ? atan_pm(x[e]) : atan2_pm(x[e], y[e]);
+}
+
 // the helpers of the lens models on their own (lerf_coords_math): one thread per element, grid ceil(n / 256)
 __global__ void __launch_bounds__(256)
 coords_math_kernel(int op, const double* __restrict__ x, const double* __restrict__ y, int64_t n, double* __restrict__ out) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
-    out[e] = op == LERF_MATH_SQRT ? sqrt_pm(x[e]) : op == LERF_MATH_ATAN ? atan_pm(x[e]) : atan2_pm(x[e], y[e]);
+    out[e] = math_element(op, x, y, e);
 }
 
 // ------------------------------------------------------------------------------------------------ argument checks (host)
 inline bool float_dtype(int dt) { return dt == LERF_F32 || dt == LERF_F64; }
 inline size_t entry_bytes(int dt) { return dt == LERF_F32 ? 8 : 16; }
 
-// ONE OPERAND TABLE PER CALL.  Every entry point states its operands (Operand), its scalar rules (one bool) and the pairs of operands
-// that must not intersect (Pair), and check_call judges them: the one place that looks at a pointer, an alignment, a dtype, a row
-// stride, a set stride or an overlap, for a single map (n_sets = 1, set strides 0) and for a batch alike.
+// ONE OPERAND TABLE PER CALL.  Every entry point states its operands (Operand), each with its ROLE, and its scalar rules (one bool),
+// and check_call judges them: the one place that looks at a pointer, an alignment, a dtype, a row stride, a set stride or an overlap,
+// for a single map (n_sets = 1, set strides 0) and for a batch alike.  WHICH OPERANDS MAY INTERSECT is not listed but derived from the
+// roles: an operand the call writes intersects no other operand of the call (check_call; its two stated exceptions are there).
 //
 // One operand over the n_sets sets of a call: set s at p + s * set_stride elements of `el` bytes, each set `span` elements from its
 // first to one past its last (the ONE place an extent is computed: the constructors below); pairs: the elements are (row, col) pairs
 // (maps, gradients), so the set stride is even; SHARE: a set stride of 0 (one operand for all sets) is allowed; OPTIONAL: may be null
-// (init, depth, a skipped gradient, the workspace the host twin does not have) and then passes every check.  shape_ok is false for a
-// descriptor made of a dtype code or dimensions that are not valid: its extent means nothing, and check_call refuses it first.
-enum : unsigned { SHARE = 1, OPTIONAL = 2 };
+// (init, depth, a skipped gradient, the workspace the host twin does not have) and then passes every check; WRITTEN: the call writes
+// it (an output, keys, a gradient, a workspace).  shape_ok is false for a descriptor made of a dtype code or dimensions that are not
+// valid: its extent means nothing, and check_call refuses it first.
+enum : unsigned { SHARE = 1, OPTIONAL = 2, WRITTEN = 4 };
 struct Operand {
     const void* p;
     size_t el, align;
     int64_t span, set_stride;
-    bool pairs, share, optional, shape_ok, rows_ok;
+    bool pairs, share, optional, written, shape_ok, rows_ok;
 };
 
 // a map under the strided contract: [h][w] entries of dtype dt, rows `stride` elements apart (even, >= 2 w), h, w >= min_hw
 inline Operand map_operand(const void* p, int dt, int64_t stride, int h, int w, int64_t set_stride, unsigned flags = 0, int min_hw = 1) {
     const bool null_ok = !p && (flags & OPTIONAL);
     return {p, entry_bytes(dt) / 2, entry_bytes(dt), (int64_t)(h - 1) * stride + 2 * (int64_t)w, set_stride, true, (flags & SHARE) != 0,
-            (flags & OPTIONAL) != 0, null_ok || (float_dtype(dt) && h >= min_hw && w >= min_hw), !(stride & 1) && stride >= 2 * (int64_t)w};
+            (flags & OPTIONAL) != 0, (flags & WRITTEN) != 0, null_ok || (float_dtype(dt) && h >= min_hw && w >= min_hw),
+            !(stride & 1) && stride >= 2 * (int64_t)w};
 }
 // a dense gradient (float64) or control mesh [h][w][2]: the map of row stride 2 w
 inline Operand dense_operand(const void* p, int dt, int h, int w, int64_t set_stride, unsigned flags = 0, int min_hw = 1) {
@@ -1515,14 +1522,16 @@ inline Operand dense_operand(const void* p, int dt, int h, int w, int64_t set_st
 }
 // a dense plane [h][w] of scalars of `el` bytes (keys, depth); its dimensions are those of a map of the same call, checked there
 inline Operand plane_operand(const void* p, size_t el, int h, int w, int64_t set_stride, unsigned flags = 0) {
-    return {p, el, el, (int64_t)h * w, set_stride, false, (flags & SHARE) != 0, (flags & OPTIONAL) != 0, true, true};
+    return {p, el, el, (int64_t)h * w, set_stride, false, (flags & SHARE) != 0, (flags & OPTIONAL) != 0, (flags & WRITTEN) != 0, true, true};
 }
-// `bytes` bytes per set, the sets one behind the other (params, grad_params, the workspaces)
+// `bytes` bytes per set, the sets one behind the other (params, grad_params, the partials of the two-pass adjoints)
 inline Operand bytes_operand(const void* p, int64_t bytes, size_t align, unsigned flags = 0) {
-    return {p, 1, align, bytes, bytes, false, false, (flags & OPTIONAL) != 0, true, true};
+    return {p, 1, align, bytes, bytes, false, false, (flags & OPTIONAL) != 0, (flags & WRITTEN) != 0, true, true};
 }
+// a workspace of `bytes` bytes for the WHOLE call (the rasteriser's, the mesh adjoint's, the ordered scatter's): one extent, shared, written
+inline Operand workspace_operand(const void* p, int64_t bytes, size_t align) { return {p, 1, align, bytes, 0, false, true, false, true, true, true}; }
 // a parameter block [n_sets][n_params] float64 (params, grad_params)
-inline Operand params_operand(const void* p, int n_params) { return bytes_operand(p, 8 * (int64_t)n_params, sizeof(double)); }
+inline Operand params_operand(const void* p, int n_params, unsigned flags = 0) { return bytes_operand(p, 8 * (int64_t)n_params, sizeof(double), flags); }
 
 // the bytes of two operands over the whole batch (first element of set 0 to one past the last of the last set) intersect
 inline bool operands_overlap(int n_sets, const Operand& x, const Operand& y) {
@@ -1532,17 +1541,16 @@ inline bool operands_overlap(int n_sets, const Operand& x, const Operand& y) {
     return a < b + bn && b < a + an;
 }
 
-// operands x and y of the call (indices into its table) must not intersect; on = false: not for this call (a pair that is refused
-// in a batch only is {x, y, n_sets > 1})
-struct Pair {
-    int x, y;
-    bool on = true;
-};
+// THE TWO EXCEPTIONS to "a written operand intersects no other": batch_only -- mesh, compose and the mesh adjoint judge overlaps for
+// n_sets > 1 only, their single-map forms have always allowed them; Allow -- compose's out may lie on b when it IS b (in place).
+struct Allow { int written = -1, other = -1; };      // indices into the call's table
 
 // The judgement of a call, in the order the return codes have had since the batched forms exist: a descriptor without a shape and
 // n_sets < 1 are LERF_EINVAL, n_sets beyond the grid's z is `too_many` (LERF_EUNSUPPORTED for the chained operations), then the scalar
-// rules, every operand's pointer, alignment, row stride and set stride, and the pairs: LERF_EINVAL.  A refused call launches nothing.
-inline int check_call(int n_sets, std::initializer_list<Operand> ops, std::initializer_list<Pair> pairs, bool rules, int too_many = LERF_EUNSUPPORTED) {
+// rules, every operand's pointer, alignment, row stride and set stride, and the overlaps -- every present WRITTEN operand against
+// every other present operand, over the whole batch: LERF_EINVAL.  A refused call launches nothing.
+inline int check_call(int n_sets, std::initializer_list<Operand> ops, bool rules, int too_many = LERF_EUNSUPPORTED, bool batch_only = false,
+                      Allow allow = {}) {
     for (const Operand& o : ops)
         if (!o.shape_ok) return LERF_EINVAL;
     if (n_sets < 1) return LERF_EINVAL;
@@ -1554,8 +1562,12 @@ inline int check_call(int n_sets, std::initializer_list<Operand> ops, std::initi
         if (o.set_stride < 0 || (o.pairs && (o.set_stride & 1))) return LERF_EINVAL;
         if (n_sets > 1 && o.set_stride < o.span && !(o.share && o.set_stride == 0)) return LERF_EINVAL;
     }
-    for (const Pair& q : pairs)
-        if (q.on && operands_overlap(n_sets, ops.begin()[q.x], ops.begin()[q.y])) return LERF_EINVAL;
+    if (batch_only && n_sets == 1) return LERF_OK;
+    const int n = (int)ops.size();
+    for (int x = 0; x < n; ++x)
+        for (int y = 0; y < n; ++y)
+            if (x != y && ops.begin()[x].written && !(x == allow.written && y == allow.other) && operands_overlap(n_sets, ops.begin()[x], ops.begin()[y]))
+                return LERF_EINVAL;
     return LERF_OK;
 }
 
@@ -1565,7 +1577,7 @@ inline bool tile_ok(int oH, int oW, int i0, int j0) {
 
 inline int build_args(int model, const double* params, int n_params, const void* out, int out_dtype, int64_t stride, int oH, int oW,
                       int i0, int j0, Params& prm) {
-    const int rc = check_call(1, {map_operand(out, out_dtype, stride, oH, oW, 0)}, {},
+    const int rc = check_call(1, {map_operand(out, out_dtype, stride, oH, oW, 0, WRITTEN)},
                               params && tile_ok(oH, oW, i0, j0) && model_params(model) >= 0 && n_params == model_params(model));
     if (rc != LERF_OK) return rc;
     for (int k = 0; k < kMaxParams; ++k) prm.p[k] = 0.0;
@@ -1577,24 +1589,10 @@ inline int build_args(int model, const double* params, int n_params, const void*
 }
 
 // device parameters cannot be inspected here: their count, the pointers and the layout of the n_sets maps are what is checked.  For
-// this one and the next, n_sets beyond the grid's z is LERF_EINVAL
+// this one and the two-pass adjoints, n_sets beyond the grid's z is LERF_EINVAL
 inline int build_dev_args(int model, const double* params, int n_sets, int n_params, const void* out, int out_dtype, int64_t set_stride,
                           int64_t stride, int oH, int oW, int i0, int j0) {
-    enum { PARAMS, OUT };
-    return check_call(n_sets,
-                      {params_operand(params, n_params), map_operand(out, out_dtype, stride, oH, oW, set_stride)},
-                      {{PARAMS, OUT}}, tile_ok(oH, oW, i0, j0) && model_params(model) >= 0 && n_params == model_params(model), LERF_EINVAL);
-}
-
-// ws: the partials of the device's two passes, null and OPTIONAL for the host twin; ws_fits: the caller's workspace_bytes hold them
-inline int build_bwd_args(int model, const double* params, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
-                          const double* grad_params, const Operand& ws, bool ws_fits) {
-    enum { PARAMS, GMAP, GPARAMS, WS };
-    return check_call(n_sets,
-                      {params_operand(params, n_params),
-                       dense_operand(grad_map, LERF_F64, oH, oW, 2 * (int64_t)oH * oW), params_operand(grad_params, n_params), ws},
-                      {{GPARAMS, PARAMS}, {GPARAMS, GMAP}, {WS, GPARAMS}, {WS, PARAMS}, {WS, GMAP}},
-                      ws_fits && tile_ok(oH, oW, i0, j0) && model_params(model) >= 0 && n_params == model_params(model), LERF_EINVAL);
+    return check_call(n_sets, {params_operand(params, n_params), map_operand(out, out_dtype, stride, oH, oW, set_stride, WRITTEN)}, tile_ok(oH, oW, i0, j0) && model_params(model) >= 0 && n_params == model_params(model), LERF_EINVAL);
 }
 
 // run F with MODEL = the compile-time constant of a model code the argument checks have accepted
@@ -1637,7 +1635,7 @@ inline bool ordered_sizes_ok(int64_t n_entries, int64_t n_targets) { return 4 * 
 inline Operand ordered_ws_operand(const OrderedArgs* ord, int64_t n_entries, int64_t n_targets, int n_sets) {
     if (!ord) return bytes_operand(nullptr, 0, 4, OPTIONAL);
     const bool sane = n_sets >= 1 && n_sets <= 65535 && n_entries >= 1 && n_targets >= 1 && ordered_sizes_ok(n_entries, n_targets);
-    return {ord->ws, 1, 4, sane ? (int64_t)OrderedLayout::bytes(n_entries, n_targets, n_sets) : 0, 0, false, true, false, true, true};
+    return workspace_operand(ord->ws, sane ? (int64_t)OrderedLayout::bytes(n_entries, n_targets, n_sets) : 0, 4);
 }
 
 inline bool ordered_rules(const OrderedArgs* ord, const Operand& ws) {
@@ -1663,17 +1661,15 @@ int build_dev(RUN run, int model, const double* params, int n_sets, int n_params
 }
 
 // Each of the chained operations below takes n_sets and one set stride per operand; a single-map entry point is the batched one with
-// n_sets = 1 and every set stride 0.  Each states its table once: the operands, the pairs that must not intersect (over the whole
-// batch; `batch`: refused in a batch only, where the single-map form has always allowed it), the scalar rules.
+// n_sets = 1 and every set stride 0.  Each states its table once: the operands with their roles (a WRITTEN one intersects no other,
+// over the whole batch; batch_only: judged in a batch only, where the single-map form has always allowed it), the scalar rules.
 template <typename RUN>
 int mesh(RUN run, const void* ctrl, int ctrl_dtype, int gh, int gw, int interp, int full_h, int full_w, void* out, int out_dtype,
          int64_t stride, int oH, int oW, int i0, int j0, int n_sets, int64_t ctrl_set, int64_t out_set) {
-    enum { CTRL, OUT };
-    const bool batch = n_sets > 1;
-    const int rc = check_call(n_sets, {dense_operand(ctrl, ctrl_dtype, gh, gw, ctrl_set, 0, 2), map_operand(out, out_dtype, stride, oH, oW, out_set)},
-                              {{CTRL, OUT, batch}},
+    const int rc = check_call(n_sets, {dense_operand(ctrl, ctrl_dtype, gh, gw, ctrl_set, 0, 2), map_operand(out, out_dtype, stride, oH, oW, out_set, WRITTEN)},
                               (interp == LERF_MESH_BILINEAR || interp == LERF_MESH_BICUBIC) && tile_ok(oH, oW, i0, j0) && full_h >= 1 && full_w >= 1 &&
-                                  (int64_t)i0 + oH <= full_h && (int64_t)j0 + oW <= full_w);
+                                  (int64_t)i0 + oH <= full_h && (int64_t)j0 + oW <= full_w,
+                              LERF_EUNSUPPORTED, /*batch_only=*/true);
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(ctrl_dtype, TC, LERF_COORDS_DT(out_dtype, TO, {
         if (interp == LERF_MESH_BILINEAR)
@@ -1688,11 +1684,11 @@ template <typename RUN>
 int compose(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride, void* out,
             int out_dtype, int64_t o_stride, int oH, int oW, int n_sets, int64_t a_set, int64_t b_set, int64_t out_set) {
     enum { A, B, OUT };
-    const bool batch = n_sets > 1, in_place = out == b && out_dtype == b_dtype && o_stride == b_stride && out_set == b_set;
+    const bool in_place = out == b && out_dtype == b_dtype && o_stride == b_stride && out_set == b_set;
     const int rc = check_call(n_sets,
                               {map_operand(a, a_dtype, a_stride, aH, aW, a_set, SHARE), map_operand(b, b_dtype, b_stride, oH, oW, b_set),
-                               map_operand(out, out_dtype, o_stride, oH, oW, out_set)},
-                              {{OUT, A, batch}, {OUT, B, batch && !in_place}}, tile_ok(oH, oW, 0, 0));
+                               map_operand(out, out_dtype, o_stride, oH, oW, out_set, WRITTEN)},
+                              tile_ok(oH, oW, 0, 0), LERF_EUNSUPPORTED, /*batch_only=*/true, in_place ? Allow{OUT, B} : Allow{});
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(a_dtype, TA, LERF_COORDS_DT(b_dtype, TB, LERF_COORDS_DT(out_dtype, TO,
         return run(ComposeOp<TA, TB, TO>{{(const TA*)a, a_stride}, aH, aW, {(const TB*)b, b_stride}, (TO*)out, o_stride, a_set, b_set, out_set},
@@ -1703,11 +1699,9 @@ template <typename RUN>
 int invert(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* init, int init_dtype, int64_t i_stride,
            void* out, int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_iter, double tol, int n_sets, int64_t f_set,
            int64_t init_set, int64_t out_set) {
-    enum { F, INIT, OUT };
     const int rc = check_call(n_sets,
                               {map_operand(f, f_dtype, f_stride, fH, fW, f_set, SHARE), map_operand(init, init_dtype, i_stride, oH, oW, init_set, SHARE | OPTIONAL),
-                               map_operand(out, out_dtype, o_stride, oH, oW, out_set)},
-                              {{OUT, F}, {OUT, INIT}},
+                               map_operand(out, out_dtype, o_stride, oH, oW, out_set, WRITTEN)},
                               fH >= 2 && fW >= 2 && tile_ok(oH, oW, i0, j0) && max_iter >= 1 && max_iter <= 64 && tol >= 0.0 && std::isfinite(tol));
     if (rc != LERF_OK) return rc;
     if (!init) init_dtype = LERF_F64;                     // a null init is never read: one instantiation serves
@@ -1722,13 +1716,11 @@ template <typename RUN, typename SCATTER>
 int invert_raster(RUN run, SCATTER scatter, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const float* depth, void* out,
                   int out_dtype, int64_t o_stride, int oH, int oW, int i0, int j0, int max_span, int orient, uint64_t* keys, int n_sets,
                   int64_t f_set, int64_t depth_set, int64_t out_set, int64_t keys_set) {
-    enum { F, DEPTH, OUT, KEYS };
     // the cells: a triangle's number fits the key's 32 bits, their rows the grid's y
     const bool cells_ok = 2 * (int64_t)(fH - 1) * (int64_t)(fW - 1) < ((int64_t)1 << 32) && (fH - 1 + CB_ROWS - 1) / CB_ROWS <= 65535;
     int rc = check_call(n_sets,
                         {map_operand(f, f_dtype, f_stride, fH, fW, f_set, SHARE), plane_operand(depth, sizeof(float), fH, fW, depth_set, SHARE | OPTIONAL),
-                         map_operand(out, out_dtype, o_stride, oH, oW, out_set), plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set)},
-                        {{OUT, F}, {KEYS, F}, {OUT, KEYS}, {OUT, DEPTH}, {KEYS, DEPTH}},
+                         map_operand(out, out_dtype, o_stride, oH, oW, out_set, WRITTEN), plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set, WRITTEN)},
                         fH >= 2 && fW >= 2 && tile_ok(oH, oW, i0, j0) && cells_ok && max_span >= 1 && max_span <= kMaxSpan && orient >= -1 && orient <= 1);
     if (rc != LERF_OK) return rc;
     rc = run(KeyFillOp{keys, oW, keys_set}, oH, oW, n_sets);
@@ -1765,24 +1757,17 @@ int trimesh(RUN run, RASTER raster, const void* pos, int pos_dtype, int V, const
             int j0, int max_span, int orient, uint64_t* keys, float* depth_out, void* workspace, size_t workspace_bytes, int n_sets, int64_t pos_set,
             int64_t attr_set, int64_t faces_set, int64_t afaces_set, int64_t depth_set, int64_t w_set, int64_t out_set, int64_t keys_set,
             int64_t dout_set) {
-    enum { POS, ATTR, FACES, AFACES, DEPTH, W, OUT, KEYS, DOUT, WS };
     const bool sizes = V >= 1 && Va >= 1 && F >= 1 && oH >= 1 && oW >= 1 && n_sets >= 1 && n_sets <= 65535 && max_span >= 0 && max_span <= kMaxTriSpan;
     const uint64_t max_items = sizes ? tri_max_items(F, n_sets, oH, oW, max_span) : 0;
     if (sizes && !max_items) return LERF_EUNSUPPORTED;
     const int64_t words = sizes ? tri_workspace_words(F, n_sets) : 0;
-    const Operand ws{workspace, 1, 4, 4 * words, 0, false, true, false, true, true};
     int rc = check_call(n_sets,
                         {dense_operand(pos, pos_dtype, V, 1, pos_set, SHARE), dense_operand(attr, attr_dtype, Va, 1, attr_set, SHARE),
                          plane_operand(faces, sizeof(int32_t), F, 3, faces_set, SHARE),
                          plane_operand(attr_faces, sizeof(int32_t), F, 3, afaces_set, SHARE | OPTIONAL),
                          plane_operand(depth, sizeof(float), V, 1, depth_set, SHARE | OPTIONAL), plane_operand(w, w_dtype == LERF_F64 ? sizeof(double) : sizeof(float), V, 1, w_set, SHARE | OPTIONAL),
-                         map_operand(out, out_dtype, o_stride, oH, oW, out_set), plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set),
-                         plane_operand(depth_out, sizeof(float), oH, oW, dout_set, OPTIONAL), ws},
-                        {{OUT, POS}, {OUT, ATTR}, {OUT, FACES}, {OUT, AFACES}, {OUT, DEPTH}, {OUT, W},
-                         {KEYS, POS}, {KEYS, ATTR}, {KEYS, FACES}, {KEYS, AFACES}, {KEYS, DEPTH}, {KEYS, W},
-                         {DOUT, POS}, {DOUT, ATTR}, {DOUT, FACES}, {DOUT, AFACES}, {DOUT, DEPTH}, {DOUT, W},
-                         {WS, POS}, {WS, ATTR}, {WS, FACES}, {WS, AFACES}, {WS, DEPTH}, {WS, W},
-                         {OUT, KEYS}, {OUT, DOUT}, {OUT, WS}, {KEYS, DOUT}, {KEYS, WS}, {DOUT, WS}},
+                         map_operand(out, out_dtype, o_stride, oH, oW, out_set, WRITTEN), plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set, WRITTEN),
+                         plane_operand(depth_out, sizeof(float), oH, oW, dout_set, OPTIONAL | WRITTEN), workspace_operand(workspace, 4 * words, 4)},
                         sizes && tile_ok(oH, oW, i0, j0) && (!w || float_dtype(w_dtype)) && orient >= -1 && orient <= 1 && !(depth_out && !depth) && workspace_bytes >= (size_t)(4 * words));
     if (rc != LERF_OK) return rc;
     rc = run(KeyFillOp{keys, oW, keys_set}, oH, oW, n_sets);
@@ -1814,11 +1799,9 @@ int trimesh_bwd(RUN run, const void* pos, int pos_dtype, int V, const void* attr
                 const double* grad_out, double* grad_attr, double* grad_pos, double* grad_w, void* workspace, size_t workspace_bytes, int max_adders,
                 int n_sets, int64_t pos_set, int64_t attr_set, int64_t faces_set, int64_t afaces_set, int64_t depth_set, int64_t w_set, int64_t keys_set,
                 int64_t gout_set, int64_t gattr_set, int64_t gpos_set, int64_t gw_set) {
-    enum { POS, ATTR, FACES, AFACES, DEPTH, W, KEYS, GOUT, GATTR, GPOS, GW, WS };
     const bool sizes = V >= 1 && Va >= 1 && F >= 1 && oH >= 1 && oW >= 1 && n_sets >= 1 && n_sets <= 65535 && max_span >= 0 && max_span <= kMaxTriSpan;
     if (sizes && (!tri_max_items(F, n_sets, oH, oW, max_span) || F > kTriBwdMaxFaces)) return LERF_EUNSUPPORTED;
     const size_t need = sizes ? tri_bwd_workspace_bytes(F, V, Va, n_sets) : 0;
-    const Operand ws{workspace, 1, 8, (int64_t)need, 0, false, true, false, true, true};
     const int rc = check_call(n_sets,
                               {dense_operand(pos, pos_dtype, V, 1, pos_set, SHARE), dense_operand(attr, attr_dtype, Va, 1, attr_set, SHARE),
                                plane_operand(faces, sizeof(int32_t), F, 3, faces_set, SHARE),
@@ -1826,13 +1809,9 @@ int trimesh_bwd(RUN run, const void* pos, int pos_dtype, int V, const void* attr
                                plane_operand(depth, sizeof(float), V, 1, depth_set, SHARE | OPTIONAL),
                                plane_operand(w, w_dtype == LERF_F64 ? sizeof(double) : sizeof(float), V, 1, w_set, SHARE | OPTIONAL),
                                plane_operand(keys, sizeof(uint64_t), oH, oW, keys_set), dense_operand(grad_out, LERF_F64, oH, oW, gout_set),
-                               dense_operand(grad_attr, LERF_F64, Va, 1, gattr_set, OPTIONAL), dense_operand(grad_pos, LERF_F64, V, 1, gpos_set, OPTIONAL),
-                               plane_operand(grad_w, sizeof(double), V, 1, gw_set, OPTIONAL), ws},
-                              {{GATTR, POS}, {GATTR, ATTR}, {GATTR, FACES}, {GATTR, AFACES}, {GATTR, DEPTH}, {GATTR, W}, {GATTR, KEYS}, {GATTR, GOUT},
-                               {GPOS, POS}, {GPOS, ATTR}, {GPOS, FACES}, {GPOS, AFACES}, {GPOS, DEPTH}, {GPOS, W}, {GPOS, KEYS}, {GPOS, GOUT},
-                               {GW, POS}, {GW, ATTR}, {GW, FACES}, {GW, AFACES}, {GW, DEPTH}, {GW, W}, {GW, KEYS}, {GW, GOUT},
-                               {WS, POS}, {WS, ATTR}, {WS, FACES}, {WS, AFACES}, {WS, DEPTH}, {WS, W}, {WS, KEYS}, {WS, GOUT},
-                               {GATTR, GPOS}, {GATTR, GW}, {GATTR, WS}, {GPOS, GW}, {GPOS, WS}, {GW, WS}},
+                               dense_operand(grad_attr, LERF_F64, Va, 1, gattr_set, OPTIONAL | WRITTEN),
+                               dense_operand(grad_pos, LERF_F64, V, 1, gpos_set, OPTIONAL | WRITTEN),
+                               plane_operand(grad_w, sizeof(double), V, 1, gw_set, OPTIONAL | WRITTEN), workspace_operand(workspace, (int64_t)need, 8)},
                               sizes && tile_ok(oH, oW, i0, j0) && (!w || float_dtype(w_dtype)) && orient >= -1 && orient <= 1 &&
                                   (grad_attr || grad_pos || grad_w) && !(grad_w && !w) && max_adders >= 1 && workspace_bytes >= need);
     if (rc != LERF_OK) return rc;
@@ -1849,7 +1828,6 @@ template <typename RUN>
 int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, int aW, const void* b, int b_dtype, int64_t b_stride,
                 const double* grad_out, int oH, int oW, double* grad_a, double* grad_b, int n_sets, int64_t a_set, int64_t b_set, int64_t gout_set,
                 int64_t ga_set, int64_t gb_set, const OrderedArgs* ord = nullptr) {
-    enum { A, B, GOUT, GA, GB, WS };
     const bool one_ga_many_a = n_sets > 1 && grad_a && ga_set == 0 && a_set != 0;      // one gradient buffer belongs to ONE shared outer map
     const bool two_writers = ord && n_sets > 1 && grad_a && ga_set == 0;               // ordered: a target has ONE owner, so one set
     const int64_t n_entries = (int64_t)oH * oW, n_targets = (int64_t)aH * aW;
@@ -1857,9 +1835,8 @@ int compose_bwd(RUN run, const void* a, int a_dtype, int64_t a_stride, int aH, i
     const Operand ws = ordered_ws_operand(ord, n_entries, n_targets, n_sets);
     const int rc = check_call(n_sets,
                               {map_operand(a, a_dtype, a_stride, aH, aW, a_set, SHARE), map_operand(b, b_dtype, b_stride, oH, oW, b_set),
-                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_a, LERF_F64, aH, aW, ga_set, SHARE | OPTIONAL),
-                               dense_operand(grad_b, LERF_F64, oH, oW, gb_set, OPTIONAL), ws},
-                              {{GA, A}, {GA, B}, {GA, GOUT}, {GB, A}, {GB, B}, {GB, GOUT}, {GA, GB}, {WS, A}, {WS, B}, {WS, GOUT}, {WS, GA}, {WS, GB}},
+                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_a, LERF_F64, aH, aW, ga_set, SHARE | OPTIONAL | WRITTEN),
+                               dense_operand(grad_b, LERF_F64, oH, oW, gb_set, OPTIONAL | WRITTEN), ws},
                               aH >= 2 && aW >= 2 && tile_ok(oH, oW, 0, 0) && (grad_a || grad_b) && !one_ga_many_a && !two_writers &&
                                   ordered_rules(ord, ws));
     if (rc != LERF_OK) return rc;
@@ -1873,15 +1850,13 @@ template <typename RUN>
 int invert_bwd(RUN run, const void* f, int f_dtype, int64_t f_stride, int fH, int fW, const void* g, int g_dtype, int64_t g_stride,
                const double* grad_out, int oH, int oW, double* grad_f, int n_sets, int64_t f_set, int64_t g_set, int64_t gout_set, int64_t gf_set,
                const OrderedArgs* ord = nullptr) {
-    enum { F, G, GOUT, GF, WS };
     const int64_t n_entries = (int64_t)oH * oW, n_targets = (int64_t)fH * fW;
     if (ord && fH >= 2 && fW >= 2 && oH >= 1 && oW >= 1 && !ordered_sizes_ok(n_entries, n_targets)) return LERF_EUNSUPPORTED;
     const Operand ws = ordered_ws_operand(ord, n_entries, n_targets, n_sets);
     // grad_f is never shared between sets (no SHARE: a set stride of 0 in a batch is refused), so a target has one owner
     const int rc = check_call(n_sets,
                               {map_operand(f, f_dtype, f_stride, fH, fW, f_set, SHARE), map_operand(g, g_dtype, g_stride, oH, oW, g_set),
-                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_f, LERF_F64, fH, fW, gf_set), ws},
-                              {{GF, F}, {GF, G}, {GF, GOUT}, {WS, F}, {WS, G}, {WS, GOUT}, {WS, GF}},
+                               dense_operand(grad_out, LERF_F64, oH, oW, gout_set), dense_operand(grad_f, LERF_F64, fH, fW, gf_set, WRITTEN), ws},
                               fH >= 2 && fW >= 2 && tile_ok(oH, oW, 0, 0) && ordered_rules(ord, ws));
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(f_dtype, TF, LERF_COORDS_DT(g_dtype, TG,
@@ -1903,11 +1878,10 @@ inline size_t depth_bytes(int dt) { return dt == LERF_F32 ? sizeof(float) : size
 template <typename RUN>
 int reproject(RUN run, int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set, void* out, int out_dtype,
               int64_t out_set, int64_t stride, float* depth_out, int64_t zo_set, int oH, int oW, int i0, int j0) {
-    enum { PARAMS, DEPTH, OUT, ZO };
     const int rc = check_call(n_sets,
                               {params_operand(params, kReprojectParams), plane_operand(depth, depth_bytes(depth_dtype), oH, oW, depth_set, SHARE),
-                               map_operand(out, out_dtype, stride, oH, oW, out_set), plane_operand(depth_out, sizeof(float), oH, oW, zo_set, OPTIONAL)},
-                              {{OUT, PARAMS}, {OUT, DEPTH}, {ZO, PARAMS}, {ZO, DEPTH}, {OUT, ZO}},
+                               map_operand(out, out_dtype, stride, oH, oW, out_set, WRITTEN),
+                               plane_operand(depth_out, sizeof(float), oH, oW, zo_set, OPTIONAL | WRITTEN)},
                               depth_kind(kind) && float_dtype(depth_dtype) && tile_ok(oH, oW, i0, j0), LERF_EINVAL);
     if (rc != LERF_OK) return rc;
     LERF_COORDS_KIND(kind, KIND, LERF_COORDS_DT(depth_dtype, TD, LERF_COORDS_DT(out_dtype, TO,
@@ -1915,27 +1889,9 @@ int reproject(RUN run, int kind, const double* params, int n_sets, const void* d
                    oH, oW, n_sets))));
 }
 
-// ws: the partials of the device's two passes (needed with grad_params), null and OPTIONAL for the host twin; ws_fits: the caller's
-// workspace_bytes hold them
-inline int reproject_bwd_args(int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set,
-                              const double* grad_map, const double* grad_zo, int oH, int oW, int i0, int j0, const double* grad_depth,
-                              const double* grad_params, const Operand& ws, bool ws_fits) {
-    enum { PARAMS, DEPTH, GMAP, GZO, GDEPTH, GPARAMS, WS };
-    const int64_t plane = (int64_t)oH * oW;
-    Operand gp = params_operand(grad_params, kReprojectParams);
-    gp.optional = true;
-    return check_call(n_sets,
-                      {params_operand(params, kReprojectParams), plane_operand(depth, depth_bytes(depth_dtype), oH, oW, depth_set, SHARE),
-                       dense_operand(grad_map, LERF_F64, oH, oW, 2 * plane), plane_operand(grad_zo, sizeof(double), oH, oW, plane, OPTIONAL),
-                       plane_operand(grad_depth, sizeof(double), oH, oW, plane, OPTIONAL), gp, ws},
-                      {{GDEPTH, PARAMS}, {GDEPTH, DEPTH}, {GDEPTH, GMAP}, {GDEPTH, GZO}, {GPARAMS, PARAMS}, {GPARAMS, DEPTH}, {GPARAMS, GMAP},
-                       {GPARAMS, GZO}, {GPARAMS, GDEPTH}, {WS, PARAMS}, {WS, DEPTH}, {WS, GMAP}, {WS, GZO}, {WS, GDEPTH}, {WS, GPARAMS}},
-                      depth_kind(kind) && float_dtype(depth_dtype) && tile_ok(oH, oW, i0, j0) && (grad_depth || grad_params) && ws_fits, LERF_EINVAL);
-}
-
 // `planes` dense planes [h][w] of scalars of `el` bytes, one behind the other (an NCHW image, the accumulator, their gradients)
 inline Operand planes_operand(const void* p, size_t el, int planes, int h, int w, int64_t set_stride, unsigned flags = 0) {
-    return {p, el, el, (int64_t)planes * h * w, set_stride, false, (flags & SHARE) != 0, (flags & OPTIONAL) != 0, true, true};
+    return {p, el, el, (int64_t)planes * h * w, set_stride, false, (flags & SHARE) != 0, (flags & OPTIONAL) != 0, (flags & WRITTEN) != 0, true, true};
 }
 
 inline bool splat_dims(int dtype, int C, int H, int W, int oH, int oW) {
@@ -1946,7 +1902,6 @@ inline bool splat_dims(int dtype, int C, int H, int W, int oH, int oW) {
 template <typename RUN>
 int splat(RUN run, const void* x, int dtype, int C, int H, int W, int64_t x_set, const void* f, int f_dtype, int64_t f_stride, int64_t f_set,
           const void* m, int64_t m_set, void* acc, int with_norm, int oH, int oW, int64_t acc_set, int n_sets, const OrderedArgs* ord = nullptr) {
-    enum { X, F, M, ACC, WS };
     const size_t el = depth_bytes(dtype);
     const int64_t n_entries = (int64_t)H * W, n_targets = (int64_t)oH * oW;
     if (ord && H >= 1 && W >= 1 && oH >= 1 && oW >= 1 && !ordered_sizes_ok(n_entries, n_targets)) return LERF_EUNSUPPORTED;
@@ -1954,8 +1909,7 @@ int splat(RUN run, const void* x, int dtype, int C, int H, int W, int64_t x_set,
     // acc is never shared between sets (no SHARE: a set stride of 0 in a batch is refused), so a target has one owner
     const int rc = check_call(n_sets,
                               {planes_operand(x, el, C, H, W, x_set), map_operand(f, f_dtype, f_stride, H, W, f_set, SHARE),
-                               planes_operand(m, el, 1, H, W, m_set, OPTIONAL), planes_operand(acc, el, C + (with_norm ? 1 : 0), oH, oW, acc_set), ws},
-                              {{ACC, X}, {ACC, M}, {ACC, F}, {WS, X}, {WS, F}, {WS, M}, {WS, ACC}},
+                               planes_operand(m, el, 1, H, W, m_set, OPTIONAL), planes_operand(acc, el, C + (with_norm ? 1 : 0), oH, oW, acc_set, WRITTEN), ws},
                               splat_dims(dtype, C, H, W, oH, oW) && (with_norm == 0 || with_norm == 1) && ordered_rules(ord, ws), LERF_EINVAL);
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(dtype, T, LERF_COORDS_DT(f_dtype, TF,
@@ -1969,15 +1923,12 @@ template <typename RUN>
 int splat_bwd(RUN run, const void* x, int dtype, int C, int H, int W, int64_t x_set, const void* f, int f_dtype, int64_t f_stride,
               int64_t f_set, const void* m, int64_t m_set, const void* g, int with_norm, int oH, int oW, int64_t g_set, void* grad_x,
               int64_t gx_set, void* grad_m, int64_t gm_set, double* grad_f, int64_t gf_set, int n_sets) {
-    enum { X, F, M, G, GX, GM, GF };
     const size_t el = depth_bytes(dtype);
     const int rc = check_call(n_sets,
                               {planes_operand(x, el, C, H, W, x_set), map_operand(f, f_dtype, f_stride, H, W, f_set, SHARE),
                                planes_operand(m, el, 1, H, W, m_set, OPTIONAL), planes_operand(g, el, C + (with_norm ? 1 : 0), oH, oW, g_set),
-                               planes_operand(grad_x, el, C, H, W, gx_set, OPTIONAL), planes_operand(grad_m, el, 1, H, W, gm_set, OPTIONAL),
-                               dense_operand(grad_f, LERF_F64, H, W, gf_set, OPTIONAL)},
-                              {{GX, X}, {GX, F}, {GX, M}, {GX, G}, {GM, X}, {GM, F}, {GM, M}, {GM, G}, {GF, X}, {GF, F}, {GF, M}, {GF, G},
-                               {GX, GM}, {GX, GF}, {GM, GF}},
+                               planes_operand(grad_x, el, C, H, W, gx_set, OPTIONAL | WRITTEN), planes_operand(grad_m, el, 1, H, W, gm_set, OPTIONAL | WRITTEN),
+                               dense_operand(grad_f, LERF_F64, H, W, gf_set, OPTIONAL | WRITTEN)},
                               splat_dims(dtype, C, H, W, oH, oW) && (with_norm == 0 || with_norm == 1) && (grad_x || grad_m || grad_f), LERF_EINVAL);
     if (rc != LERF_OK) return rc;
     LERF_COORDS_DT(dtype, T, LERF_COORDS_DT(f_dtype, TF,
@@ -2029,6 +1980,104 @@ void two_pass_sums_host(int n_sets, int n_params, int oH, int oW, double* grad_p
             *dst = *dst + tree64(v);
         }
     }
+}
+
+// The runners of the two-pass adjoints: TwoPassOnDevice{stream, partials} launches pass 1 and, with grad_params, pass 2 (kPartials: the
+// operation's table judges the caller's partials); TwoPassOnHost{} is two_pass_sums_host over the same per-entry statement.
+struct TwoPassOnDevice {
+    static constexpr bool kPartials = true;
+    hipStream_t stream;
+    double* partials;
+    static dim3 grid(int n_sets, int oH, int oW) { return dim3((oW + kBwdCols - 1) / kBwdCols, (oH + kBwdBand - 1) / kBwdBand, n_sets); }
+    int pass2(int n_params, int n_sets, const dim3& g1, double* grad_params) const {
+        if (grad_params) hipLaunchKernelGGL(coords_build_bwd_sum_kernel, dim3(n_params, n_sets), dim3(64), 0, stream, partials, (int)(g1.x * g1.y), grad_params);
+        return launch_status();
+    }
+    template <int MODEL>
+    int build(const double* params, int n_sets, const double* grad_map, int oH, int oW, int i0, int j0, double* grad_params) const {
+        clear_stale_error();
+        const dim3 g1 = grid(n_sets, oH, oW);
+        hipLaunchKernelGGL((coords_build_bwd_partial_kernel<MODEL>), g1, dim3(CB_COLS, CB_ROWS), 0, stream, params, reinterpret_cast<const double2*>(grad_map),
+                           oH, oW, i0, j0, partials);
+        return pass2(model_params(MODEL), n_sets, g1, grad_params);
+    }
+    template <int KIND, typename TD>
+    int reproject(const double* params, int n_sets, const TD* depth, int64_t depth_set, const double* grad_map, const double* grad_zo, int oH, int oW,
+                  int i0, int j0, double* grad_depth, double* grad_params) const {
+        clear_stale_error();
+        const dim3 g1 = grid(n_sets, oH, oW), b1(CB_COLS, CB_ROWS);
+        const double2* gm = reinterpret_cast<const double2*>(grad_map);
+        if (grad_params)
+            hipLaunchKernelGGL((coords_reproject_bwd_kernel<KIND, TD, true>), g1, b1, 0, stream, params, depth, depth_set, gm, grad_zo, oH, oW, i0, j0,
+                               grad_depth, partials);
+        else
+            hipLaunchKernelGGL((coords_reproject_bwd_kernel<KIND, TD, false>), g1, b1, 0, stream, params, depth, depth_set, gm, grad_zo, oH, oW, i0, j0,
+                               grad_depth, (double*)nullptr);
+        return pass2(kReprojectParams, n_sets, g1, grad_params);
+    }
+};
+
+struct TwoPassOnHost {
+    static constexpr bool kPartials = false;
+    template <int MODEL>
+    int build(const double* params, int n_sets, const double* grad_map, int oH, int oW, int i0, int j0, double* grad_params) const {
+#pragma clang fp contract(off)
+        constexpr int NP = model_params(MODEL);
+        two_pass_sums_host(n_sets, NP, oH, oW, grad_params, [&](int s, int i, int j, double* dp) {
+            model_point_bwd<MODEL>(params + (size_t)s * NP, i0 + i, j0 + j, load_entry(grad_map + 2 * (size_t)s * oH * oW, 2 * (int64_t)oW, i, j), dp);
+        });
+        return LERF_OK;
+    }
+    template <int KIND, typename TD>
+    int reproject(const double* params, int n_sets, const TD* depth, int64_t depth_set, const double* grad_map, const double* grad_zo, int oH, int oW,
+                  int i0, int j0, double* grad_depth, double* grad_params) const {
+#pragma clang fp contract(off)
+        two_pass_sums_host(n_sets, kReprojectParams, oH, oW, grad_params, [&](int s, int i, int j, double* dp) {
+            const int64_t e = (int64_t)i * oW + j, pe = (int64_t)s * oH * oW + e;
+            const double dd = reproject_point_bwd<KIND>(params + (size_t)s * kReprojectParams, (double)depth[set_offset(s, depth_set) + e], i0 + i, j0 + j,
+                                                        load_entry(grad_map + 2 * (size_t)s * oH * oW, 2 * (int64_t)oW, i, j), grad_zo ? grad_zo[pe] : 0.0, dp);
+            if (grad_depth) grad_depth[pe] = grad_depth[pe] + dd;
+        });
+        return LERF_OK;
+    }
+};
+
+// the partials as an operand: one vector per block and set where the runner keeps them (the device) and they are `wanted`
+inline Operand partials_operand(const void* ws, int n_params, int oH, int oW, bool wanted) {
+    return bytes_operand(wanted ? ws : nullptr, (int64_t)lerf_coords_build_bwd_workspace_bytes(n_params, 1, oH, oW), 16, wanted ? WRITTEN : OPTIONAL);
+}
+
+// the adjoint of the builders and of reproject: the table, the dispatch, the runner
+template <typename RUN>
+int build_bwd(RUN run, int model, const double* params, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
+              double* grad_params, void* workspace, size_t workspace_bytes) {
+    const int rc = check_call(n_sets,
+                              {params_operand(params, n_params), dense_operand(grad_map, LERF_F64, oH, oW, 2 * (int64_t)oH * oW),
+                               params_operand(grad_params, n_params, WRITTEN), partials_operand(workspace, n_params, oH, oW, RUN::kPartials)},
+                              (!RUN::kPartials || workspace_bytes >= lerf_coords_build_bwd_workspace_bytes(n_params, n_sets, oH, oW)) && tile_ok(oH, oW, i0, j0) &&
+                                  model_params(model) >= 0 && n_params == model_params(model),
+                              LERF_EINVAL);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_MODEL(model, MODEL, return run.template build<MODEL>(params, n_sets, grad_map, oH, oW, i0, j0, grad_params));
+}
+
+template <typename RUN>
+int reproject_bwd(RUN run, int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set, const double* grad_map,
+                  const double* grad_zo, int oH, int oW, int i0, int j0, double* grad_depth, double* grad_params, void* workspace, size_t workspace_bytes) {
+    const int64_t plane = (int64_t)oH * oW;
+    const bool partials = RUN::kPartials && grad_params;
+    const int rc = check_call(n_sets,
+                              {params_operand(params, kReprojectParams), plane_operand(depth, depth_bytes(depth_dtype), oH, oW, depth_set, SHARE),
+                               dense_operand(grad_map, LERF_F64, oH, oW, 2 * plane), plane_operand(grad_zo, sizeof(double), oH, oW, plane, OPTIONAL),
+                               plane_operand(grad_depth, sizeof(double), oH, oW, plane, OPTIONAL | WRITTEN),
+                               params_operand(grad_params, kReprojectParams, OPTIONAL | WRITTEN),
+                               partials_operand(workspace, kReprojectParams, oH, oW, partials)},
+                              depth_kind(kind) && float_dtype(depth_dtype) && tile_ok(oH, oW, i0, j0) && (grad_depth || grad_params) &&
+                                  (!partials || workspace_bytes >= lerf_coords_reproject_bwd_workspace_bytes(n_sets, oH, oW)),
+                              LERF_EINVAL);
+    if (rc != LERF_OK) return rc;
+    LERF_COORDS_KIND(kind, KIND, LERF_COORDS_DT(depth_dtype, TD,
+        return run.template reproject<KIND, TD>(params, n_sets, (const TD*)depth, depth_set, grad_map, grad_zo, oH, oW, i0, j0, grad_depth, grad_params)));
 }
 
 }  // namespace coords
@@ -2312,15 +2361,13 @@ size_t lerf_coords_mesh_bwd_workspace_bytes(int gh, int gw, int oH, int oW) {
 
 int lerf_coords_mesh_bwd_batched(const double* grad_map, int oH, int oW, int interp, int gh, int gw, double* grad_ctrl, void* workspace,
                                  size_t workspace_bytes, int n_sets, int64_t gmap_set, int64_t gctrl_set, void* stream) {
-    enum { GMAP, GCTRL, WS };
     if (!grad_map || !grad_ctrl || !workspace) return LERF_EINVAL;          // this entry point names a null pointer before it looks at n_sets
     const size_t per_set = lerf_coords_mesh_bwd_workspace_bytes(gh, gw, oH, oW);
-    const bool batch = n_sets > 1;
     const int rc = check_call(n_sets,
-                              {dense_operand(grad_map, LERF_F64, oH, oW, gmap_set), dense_operand(grad_ctrl, LERF_F64, gh, gw, gctrl_set, 0, 2),
-                               bytes_operand(workspace, (int64_t)per_set, 16)},
-                              {{GCTRL, GMAP, batch}, {WS, GMAP, batch}, {WS, GCTRL, batch}},
-                              (interp == LERF_MESH_BILINEAR || interp == LERF_MESH_BICUBIC) && workspace_bytes >= (size_t)n_sets * per_set && gh <= 65535);
+                              {dense_operand(grad_map, LERF_F64, oH, oW, gmap_set), dense_operand(grad_ctrl, LERF_F64, gh, gw, gctrl_set, WRITTEN, 2),
+                               bytes_operand(workspace, (int64_t)per_set, 16, WRITTEN)},
+                              (interp == LERF_MESH_BILINEAR || interp == LERF_MESH_BICUBIC) && workspace_bytes >= (size_t)n_sets * per_set && gh <= 65535,
+                              LERF_EUNSUPPORTED, /*batch_only=*/true);
     if (rc != LERF_OK) return rc;
     clear_stale_error();
     hipStream_t st = (hipStream_t)stream;
@@ -2351,19 +2398,8 @@ size_t lerf_coords_build_bwd_workspace_bytes(int n_params, int n_sets, int oH, i
 
 int lerf_coords_build_bwd(int model, const double* params_dev, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
                           double* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
-    const int rc = build_bwd_args(model, params_dev, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params,
-                                  bytes_operand(workspace, (int64_t)lerf_coords_build_bwd_workspace_bytes(n_params, 1, oH, oW), 16),
-                                  workspace_bytes >= lerf_coords_build_bwd_workspace_bytes(n_params, n_sets, oH, oW));
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + kBwdCols - 1) / kBwdCols, (oH + kBwdBand - 1) / kBwdBand, n_sets), b2(64), g2(n_params, n_sets);
-    const double2* gm = reinterpret_cast<const double2*>(grad_map);
-    double* part = reinterpret_cast<double*>(workspace);
-    LERF_COORDS_MODEL(model, MODEL,
-        hipLaunchKernelGGL((coords_build_bwd_partial_kernel<MODEL>), g1, b1, 0, st, params_dev, gm, oH, oW, i0, j0, part));
-    hipLaunchKernelGGL(coords_build_bwd_sum_kernel, g2, b2, 0, st, part, (int)(g1.x * g1.y), grad_params);
-    return launch_status();
+    return build_bwd(TwoPassOnDevice{(hipStream_t)stream, (double*)workspace}, model, params_dev, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params,
+                     workspace, workspace_bytes);
 }
 
 int lerf_coords_math(int op, const double* x, const double* y, int64_t n, double* out, void* stream) {
@@ -2375,26 +2411,17 @@ int lerf_coords_math(int op, const double* x, const double* y, int64_t n, double
     return launch_status();
 }
 
-// the host twins that are not a runner away: a plain loop, and the device's two passes lane by lane
+// the host twin that is not a runner away: a plain loop
 int lerf_coords_math_host(int op, const double* x, const double* y, int64_t n, double* out) {
     const int rc = math_args(op, x, y, n, out);
     if (rc != LERF_OK) return rc;
-    for (int64_t e = 0; e < n; ++e)
-        out[e] = op == LERF_MATH_SQRT ? sqrt_pm(x[e]) : op == LERF_MATH_ATAN ? atan_pm(x[e]) : atan2_pm(x[e], y[e]);
+    for (int64_t e = 0; e < n; ++e) out[e] = math_element(op, x, y, e);
     return LERF_OK;
 }
 
-// the device's two passes, lane by lane: the same bands, the same trees, the same order (the top of lerf_coords_models.h)
 int lerf_coords_build_bwd_host(int model, const double* params, int n_sets, int n_params, const double* grad_map, int oH, int oW, int i0, int j0,
                                double* grad_params) {
-#pragma clang fp contract(off)
-    const int rc = build_bwd_args(model, params, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params, bytes_operand(nullptr, 0, 16, OPTIONAL), true);
-    if (rc != LERF_OK) return rc;
-    two_pass_sums_host(n_sets, n_params, oH, oW, grad_params, [&](int s, int i, int j, double* dp) {
-        const double* g = grad_map + 2 * (((int64_t)s * oH + i) * oW + j);
-        LERF_COORDS_MODEL(model, MODEL, model_point_bwd<MODEL>(params + (size_t)s * n_params, i0 + i, j0 + j, Point{g[0], g[1]}, dp));
-    });
-    return LERF_OK;
+    return build_bwd(TwoPassOnHost{}, model, params, n_sets, n_params, grad_map, oH, oW, i0, j0, grad_params, nullptr, 0);
 }
 
 int lerf_coords_reproject(int kind, const double* params_dev, int n_sets, const void* depth, int depth_dtype, int64_t depth_set_stride, void* out,
@@ -2418,46 +2445,15 @@ size_t lerf_coords_reproject_bwd_workspace_bytes(int n_sets, int oH, int oW) {
 int lerf_coords_reproject_bwd(int kind, const double* params_dev, int n_sets, const void* depth, int depth_dtype, int64_t depth_set_stride,
                               const double* grad_map, const double* grad_depth_out, int oH, int oW, int i0, int j0, double* grad_depth,
                               double* grad_params, void* workspace, size_t workspace_bytes, void* stream) {
-    const Operand ws = bytes_operand(grad_params ? workspace : nullptr, (int64_t)lerf_coords_reproject_bwd_workspace_bytes(1, oH, oW), 16,
-                                     grad_params ? 0 : OPTIONAL);
-    const int rc = reproject_bwd_args(kind, params_dev, n_sets, depth, depth_dtype, depth_set_stride, grad_map, grad_depth_out, oH, oW, i0, j0,
-                                      grad_depth, grad_params, ws,
-                                      !grad_params || workspace_bytes >= lerf_coords_reproject_bwd_workspace_bytes(n_sets, oH, oW));
-    if (rc != LERF_OK) return rc;
-    clear_stale_error();
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 b1(CB_COLS, CB_ROWS), g1((oW + kBwdCols - 1) / kBwdCols, (oH + kBwdBand - 1) / kBwdBand, n_sets), b2(64), g2(kReprojectParams, n_sets);
-    const double2* gm = reinterpret_cast<const double2*>(grad_map);
-    double* part = reinterpret_cast<double*>(workspace);
-    LERF_COORDS_KIND(kind, KIND, LERF_COORDS_DT(depth_dtype, TD, {
-        if (grad_params)
-            hipLaunchKernelGGL((coords_reproject_bwd_kernel<KIND, TD, true>), g1, b1, 0, st, params_dev, (const TD*)depth, depth_set_stride, gm,
-                               grad_depth_out, oH, oW, i0, j0, grad_depth, part);
-        else
-            hipLaunchKernelGGL((coords_reproject_bwd_kernel<KIND, TD, false>), g1, b1, 0, st, params_dev, (const TD*)depth, depth_set_stride, gm,
-                               grad_depth_out, oH, oW, i0, j0, grad_depth, (double*)nullptr);
-    }));
-    if (grad_params) hipLaunchKernelGGL(coords_build_bwd_sum_kernel, g2, b2, 0, st, part, (int)(g1.x * g1.y), grad_params);
-    return launch_status();
+    return reproject_bwd(TwoPassOnDevice{(hipStream_t)stream, (double*)workspace}, kind, params_dev, n_sets, depth, depth_dtype, depth_set_stride, grad_map,
+                         grad_depth_out, oH, oW, i0, j0, grad_depth, grad_params, workspace, workspace_bytes);
 }
 
-// the device's kernel lane by lane: the same entries in the same order into the same sums
 int lerf_coords_reproject_bwd_host(int kind, const double* params, int n_sets, const void* depth, int depth_dtype, int64_t depth_set_stride,
                                    const double* grad_map, const double* grad_depth_out, int oH, int oW, int i0, int j0, double* grad_depth,
                                    double* grad_params) {
-#pragma clang fp contract(off)
-    const int rc = reproject_bwd_args(kind, params, n_sets, depth, depth_dtype, depth_set_stride, grad_map, grad_depth_out, oH, oW, i0, j0, grad_depth,
-                                      grad_params, bytes_operand(nullptr, 0, 16, OPTIONAL), true);
-    if (rc != LERF_OK) return rc;
-    LERF_COORDS_KIND(kind, KIND, LERF_COORDS_DT(depth_dtype, TD,
-        two_pass_sums_host(n_sets, kReprojectParams, oH, oW, grad_params, [&](int s, int i, int j, double* dp) {
-            const int64_t e = (int64_t)i * oW + j, pe = (int64_t)s * oH * oW + e;
-            const double d = (double)((const TD*)depth)[set_offset(s, depth_set_stride) + e];
-            const double dd = reproject_point_bwd<KIND>(params + (size_t)s * kReprojectParams, d, i0 + i, j0 + j,
-                                                        Point{grad_map[2 * pe], grad_map[2 * pe + 1]}, grad_depth_out ? grad_depth_out[pe] : 0.0, dp);
-            if (grad_depth) grad_depth[pe] = grad_depth[pe] + dd;
-        })));
-    return LERF_OK;
+    return reproject_bwd(TwoPassOnHost{}, kind, params, n_sets, depth, depth_dtype, depth_set_stride, grad_map, grad_depth_out, oH, oW, i0, j0, grad_depth,
+                         grad_params, nullptr, 0);
 }
 
 int lerf_splat(const void* x, int dtype, int C, int H, int W, int64_t x_set_stride, const void* f, int f_dtype, int64_t f_row_stride,
