@@ -1048,9 +1048,67 @@ __device__ __forceinline__ void stage2_linear(uint8_t* smem, const Params& P, co
     }
 }
 
+// row of a feat-tile address: a / FP as one 24-bit multiply and a shift, exact for every address of the tile (checked here)
+template <typename D>
+constexpr bool feat_row_exact(uint32_t m, int sh) {
+    for (uint32_t a = 0; a < (uint32_t)D::NF; ++a)
+        if ((uint32_t)(((uint64_t)a * m) >> sh) != a / (uint32_t)D::FP || (uint64_t)a * m >> 32 != 0) return false;
+    return true;
+}
+template <typename D>
+__device__ __forceinline__ uint32_t feat_row(uint32_t a) {
+    constexpr int SH = 25;
+    constexpr uint32_t M = ((1u << SH) + D::FP - 1) / D::FP;
+    static_assert(M < (1u << 24) && D::NF <= (1 << 24) && feat_row_exact<D>(M, SH), "a * M >> SH == a / FP for a < NF, in 32 bits");
+    return (uint32_t)__umul24(a, M) >> SH;      // (the product passes 2^31: an unsigned shift)
+}
+
+// The lean binning of stage2_gauss (exact-x2 LeRF-G kernel, interior tile): the bins of the thread's KH positions, 4 bits each
+// (3 = not looked up), and its counts of bins (0, 1) and 2 as stage2_gauss packs them
+template <typename D>
+__device__ __forceinline__ void lean_bins(const uint8_t* Bt, int tid, uint32_t& qlo, uint32_t& qhi, uint32_t& xa, uint32_t& xb) {
+    constexpr int KH = (D::NH + NT - 1) / NT;
+    // The thread's positions p0 .. p0 + KH - 1 cross at most one row end: the first kw of them lie in row ry0 from column
+    // col0 on, the rest in row ry0 + 1 from column 0.  Looked up: rows below HY - 1, columns below (HX - 1) * CH (the ring
+    // exclusion of the generic loop; a position past the region's end has a row >= HY): in row ry0 the positions k < kw - CH,
+    // and the positions k >= kw where row ry0 + 1 is in.  All KH bytes are read at once, ahead of the arithmetic.
+    static_assert(NBIN == 3 && D::HR > 0 && KH <= (D::HX - 1) * CH, "three bins + the mark 3; a ring; one row end per thread");
+    static_assert(((NT * KH - 1) / D::HP + D::HO) * D::FP + D::HO * CH + D::HP <= D::NF, "the reads of the last threads stay in the feat tile");
+    const int p0 = tid * KH, ry0 = p0 / D::HP, col0 = p0 - ry0 * D::HP;
+    const int kw = D::HP - col0;
+    const uint32_t ap0 = (uint32_t)((ry0 + D::HO) * D::FP + D::HO * CH + col0), ap1 = ap0 + (uint32_t)(D::FP - D::HP);
+    uint32_t v[KH];
+#pragma unroll
+    for (int k = 0; k < KH; ++k) v[k] = (uint32_t)Bt[(k >= kw ? ap1 : ap0) + (uint32_t)k];
+    // which of the KH positions are looked up, once per thread: bit 4 k of a 64-bit mask (the nibble layout of qlo | qhi << 32)
+    constexpr unsigned long long ONES = 0x1111111111111111ull, ALL = ONES & ((1ull << (4 * KH)) - 1ull);
+    auto below = [&](int n) { return ONES & ((1ull << (4 * min(max(n, 0), KH))) - 1ull); };      // positions k < n
+    const int lim = ry0 < D::HY - 1 ? kw - CH : 0, from = ry0 < D::HY - 2 ? kw : KH;
+    const unsigned long long in = below(lim) | (ALL & ~below(from));
+    // the bin of a value as two carries of ONE multiply-add: (v + 256 - 16 bin_lo(2)) | (v + 256 - 16 bin_lo(1)) << 16 has
+    // v >= 16 bin_lo(2) in bit 8 and v >= 16 bin_lo(1) in bit 24; either flag goes to the position's nibble by a shift and an
+    // and-or, the nibble's value is their sum, the bin counts are three population counts -- no compare, no select
+    constexpr uint32_t CARRY = ((256u - 16u * (uint32_t)bin_lo(1)) << 16) | (256u - 16u * (uint32_t)bin_lo(2));
+    uint32_t f1[2] = {0, 0}, f2[2] = {0, 0};
+#pragma unroll
+    for (int k = 0; k < KH; ++k) {
+        const uint32_t w = (uint32_t)__umul24(v[k], 0x10001u) + CARRY;
+        const int t = 4 * (k & 7), h = k >> 3;
+        f1[h] |= (t <= 24 ? w >> (24 - t) : w << (t - 24)) & (1u << t);
+        f2[h] |= (t >= 8 ? w << (t - 8) : w >> (8 - t)) & (1u << t);
+    }
+    const uint32_t inlo = (uint32_t)in, inhi = (uint32_t)(in >> 32);
+    qlo = (f1[0] + f2[0]) | (((uint32_t)ALL & ~inlo) * 3u);
+    qhi = (f1[1] + f2[1]) | (((uint32_t)(ALL >> 32) & ~inhi) * 3u);
+    const uint32_t n = (uint32_t)(__popc(inlo) + __popc(inhi));
+    const uint32_t n1 = (uint32_t)(__popc(f1[0] & inlo) + __popc(f1[1] & inhi)), n2 = (uint32_t)(__popc(f2[0] & inlo) + __popc(f2[1] & inhi));
+    xa = (n - n1) | ((n1 - n2) << 16);
+    xb = n2;
+}
+
 // ---- stage 2, LeRF-G: packed 3-channel LUT pieces, pixels binned by the top-axis level of their centre; the hyper
-//      region's (hq0, hq1, hq2, feat) dwords go to Dt
-template <typename D, bool GEN>
+//      region's (hq0, hq1, hq2, feat) dwords go to Dt.  LEAN: the exact-x2 kernel, whose interior tiles take the lean set-up
+template <typename D, bool GEN, bool LEAN = false>
 __device__ __forceinline__ void stage2_gauss(uint8_t* smem, const Params& P, const uint8_t* Bt, uint32_t* Dt, int hy0, int hx0, int fy0,
                                              int fx0, int Hc, int Wc, int tid) {
     const int lane = tid & 63, wave = tid >> 6;
@@ -1064,12 +1122,19 @@ __device__ __forceinline__ void stage2_gauss(uint8_t* smem, const Params& P, con
     // tiles) are not looked up at all: stage 3 reads them as replicas of the clamped position (edge-padded hyper maps,
     // zero image), which fill_outside() below copies once the in-frame values exist.  A 28-row strip tile or the
     // last tile row of a 1080-row frame then costs what its in-frame part costs.
-    for (int i = tid; i < MAXR * NT / 2; i += NT) reinterpret_cast<uint32_t*>(lst)[i] = 0xFFFFFFFFu;
+    // LEAN (the exact-x2 LeRF-G kernel) && an interior tile: the lean set-up.  Nothing of the region lies outside the frame, so
+    // the binning walks its KH consecutive positions by one running address, and the lists get their 0xFFFF only where it is
+    // needed (the padding tail of each bin; what the read-back loads from the chunks behind the last bin is discarded).  One wave-uniform branch each.
+    const bool lean = LEAN && Hc < 0;
+    if (!lean)
+        for (int i = tid; i < MAXR * NT / 2; i += NT) reinterpret_cast<uint32_t*>(lst)[i] = 0xFFFFFFFFu;
     constexpr int KH = (D::NH + NT - 1) / NT;
     static_assert(KH <= 15 && NBIN <= 4 && NW == 16, "nibble counts, one byte field per bin, one lane per (wave, bin)");
-    uint32_t qlo = 0, qhi = 0;              // 4 bits per owned position p = tid * KH + k: its bin, 15 = not looked up (thread-major lists = position order)
+    uint32_t qlo = 0, qhi = 0;              // 4 bits per owned position p = tid * KH + k: its bin, >= NBIN = not looked up (thread-major lists = position order)
     uint32_t xa, xb;                        // per-thread counts of bins (0, 1) and (2, 3), two 16-bit fields per register
-    {
+    if (lean) {
+        if constexpr (LEAN) lean_bins<D>(Bt, tid, qlo, qhi, xa, xb);
+    } else {
         uint32_t hist = 0;                  // one byte per bin
 #pragma unroll
         for (int k = 0; k < KH; ++k) {
@@ -1146,6 +1211,12 @@ __device__ __forceinline__ void stage2_gauss(uint8_t* smem, const Params& P, con
         ce_pack = (uint32_t)__builtin_amdgcn_readlane(ec, 0) | ((uint32_t)__builtin_amdgcn_readlane(ec, 1) << 8) |
                   ((uint32_t)__builtin_amdgcn_readlane(ec, 2) << 16) | ((uint32_t)__builtin_amdgcn_readlane(ec, 3) << 24);
         ne_bins = (uint32_t)(__ballot(total > 0) & 0xFull);
+        // lean set-up: the lists were not pre-filled.  Wave b marks the padding tail of bin b (at most 63 entries); the chunks
+        // behind the last bin stay unwritten, and the slot read-back below does not read them.
+        if (lean && wl < NBIN * 4) {
+            const int tail = __builtin_amdgcn_readlane(start + total, wl >> 2), npad = __builtin_amdgcn_readlane(padded - total, wl >> 2);
+            if (lane < npad) lst[tail + lane] = (uint16_t)0xFFFFu;
+        }
     }
     // The next piece rides in registers behind the lookups of the current one: NSLAB x 16 bytes per thread.
     uint4 pr[NSLAB];
@@ -1194,9 +1265,13 @@ __device__ __forceinline__ void stage2_gauss(uint8_t* smem, const Params& P, con
     uint32_t accA[MAXR], accB[MAXR];
     uint32_t wrounds = 0;                 // bit k: this wave has a real position in round k (wave-uniform)
     uint32_t vmask = 0;                   // bit k: this lane's slot k is real
+    const int wvl = LEAN ? __builtin_amdgcn_readfirstlane(wave) : 0;
 #pragma unroll
     for (int k = 0; k < MAXR; ++k) {
-        const uint32_t p = lst[k * NT + tid];
+        uint32_t p = lst[k * NT + tid];
+        // lean set-up: a chunk behind the last bin was never written and reads as padding.  Only the rounds whose chunks may lie
+        // there carry the test: the bins hold NHL positions, so the first NHL / 64 chunks always belong to one.
+        if (16 * k + 15 >= D::NHL / 64 && lean && 16 * k + wvl >= (int)((ce_pack >> (8 * (NBIN - 1))) & 0xFFu)) p = 0xFFFFu;
         uint32_t a = p;
         if (p != 0xFFFFu) vmask |= 1u << k;
         const unsigned long long real = __ballot(p != 0xFFFFu);
@@ -1348,7 +1423,8 @@ __device__ __forceinline__ void stage2_gauss(uint8_t* smem, const Params& P, con
             uint32_t h2 = (uint32_t)rne_div_clip255_fast(n2, div2);
             // feat-tile address -> hyper-region position: row (ry + R2) of pitch FP -> row ry of pitch HP, R2 pixels left
             const uint32_t a = (k & 1) ? (slot2[k >> 1] >> 16) : (slot2[k >> 1] & 0xFFFFu);
-            const uint32_t row = a / (uint32_t)D::FP;
+            uint32_t row;
+            if constexpr (LEAN) row = feat_row<D>(a); else row = a / (uint32_t)D::FP;
             const uint32_t p = a - row * (uint32_t)(D::FP - D::HP) - (uint32_t)(D::HO * D::HP + D::HO * CH);
             Dt[p] = h0 | (h1 << 8) | (h2 << 16) | ((uint32_t)Bt[a] << 24);
         }
@@ -2328,7 +2404,7 @@ sr_fused_kernel(Params P, std::conditional_t<GEN, RaggedTable, NoTable> T) {
     if constexpr (KIND == LERF_KIND_LINEAR)
         stage2_linear<D, GEN, FROM_FEAT>(smem, P, Bt, Dt, F.feat, W, hy0, hx0, fy0, fx0, interior, Hc, Wc, tid, outside_pixel);
     else
-        stage2_gauss<D, GEN>(smem, P, Bt, Dt, hy0, hx0, fy0, fx0, Hc, Wc, tid);
+        stage2_gauss<D, GEN, X2>(smem, P, Bt, Dt, hy0, hx0, fy0, fx0, Hc, Wc, tid);
     if (!EMIT && !WARP && KIND == LERF_KIND_GAUSS && Hc >= 0) fill_outside<D>(Dt, hy0, hx0, H, W, tid, outside_pixel);
 
     if constexpr (WARP) {

@@ -18,8 +18,8 @@ $LL/lld -flavor gnu -m elf64_amdgpu --no-undefined -shared -o $tmp/dev.hsaco $tm
 $LL/clang-offload-bundler -type=o -bundle-align=4096 -targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950 \
     -input=/dev/null -input=$tmp/dev.hsaco -output=$tmp/dev.hipfb
 /opt/rocm/bin/hipcc $flags --cuda-host-only -Xclang -fcuda-include-gpubinary -Xclang $tmp/dev.hipfb -c -o $tmp/lerf_fused.o $src/lerf_fused.hip
-objs=""
-for o in lerf_api lerf_kernels lerf_fused_g3 lerf_fused_h32 lerf_fused_h16 lerf_fused_c1 lerf_fused_c4 lerf_metrics lerf_train lerf_transfer lerf_ubench; do objs="$objs $src/build/$o.o"; done
+objs=""          # every object of the product library (the Makefile's SRCS) but lerf_fused.o
+for o in $src/build/*.o; do [ "$(basename $o)" = lerf_fused.o ] || objs="$objs $o"; done
 mkdir -p $src/build_variants
 /opt/rocm/bin/hipcc -fPIC --offload-arch=gfx950 -shared -o $src/build_variants/liblerf_hip_$name.so $objs $tmp/lerf_fused.o
 cp $tmp/dev2.s /tmp/variant_$name.s
